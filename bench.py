@@ -22,6 +22,10 @@ Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the
 the dominant kernel; `cpu_baseline` times the CPU oracle (oracle/, the restatement of the reference's
 CPU plugin) on a bounded sample of the same stream on the host cores; `pcie_inclusive` is the same
 pipeline fed from pinned host memory (double-buffered H2D) with the results copied back (D2H).
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 (keypoints, descriptors, matches and 3-D points of a
+fixed seeded sample of the batch's frames, the per-frame counts of all of them) as DIR/<name>.npy, so that two builds can be
+compared output for output; the inputs depend only on the arguments.
 """
 import argparse
 import hashlib
@@ -162,6 +166,68 @@ def baseline_metric():
         return "ORB keypoints extracted+matched /sec, 640×480 RGB-D, 1/2/4/8 GPU; HBM GB/s vs roofline"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pkg, ctx, B, first_frame, pnp, bow):
+    """Write what the last step handed its caller as DIR/<name>.npy (float32, or float64 where the values need it).
+    Per-frame counts (and the PnP poses / best loop entries) cover every frame of the batch; the per-keypoint arrays
+    cover a fixed seeded sample of frames, concatenated in frame order (`*_offset`: the sample's slices), sized from the
+    context's per-frame capacity so that the files stay under DUMP_LIMIT_BYTES."""
+    v, pv = ctx.batch_view(), ctx.points_view()
+    K = v.capacity
+
+    def rd(ptr, shape, dt):
+        return pkg.read_device(ctx, ptr, shape, dt)
+
+    out = {"kp_count": rd(v.count, (B,), np.int32).astype(np.float32),
+           "match_count": rd(v.match_count, (B,), np.int32).astype(np.float32)}
+    # per sampled frame at full capacity: xy 2, desc 32, octave, angle, response, valid, match from/to (4 B each) + xyz 3 x 8 B
+    per_frame = K * (4 * (2 + 32 + 4 + 2) + 8 * 3)
+    if bow:
+        bv = ctx.bow_view()
+        per_frame += bv.capacity * (8 + 8)
+    fixed = 8 * B * (1 + 16 + 2)  # the per-frame arrays above and below, generously
+    n_sample = int(max(1, min(B, 64, (DUMP_LIMIT_BYTES - fixed) // per_frame)))
+    idx = np.sort(np.random.default_rng(0).choice(B, n_sample, replace=False))
+    out["frames"] = (first_frame + idx).astype(np.float64)  # index of each sampled frame in the synthetic stream
+    cnt, mc = out["kp_count"][idx].astype(np.int64), out["match_count"][idx].astype(np.int64)
+    out["kp_offset"] = np.concatenate([[0], np.cumsum(cnt)]).astype(np.float64)
+    out["match_offset"] = np.concatenate([[0], np.cumsum(mc)]).astype(np.float64)
+    rows = {"xy": [], "desc": [], "octave": [], "angle": [], "response": [], "xyz": [], "valid": [], "match_from": [],
+            "match_to": []}
+    for t, n, m in zip(idx.tolist(), cnt.tolist(), mc.tolist()):
+        rows["xy"].append(rd(v.xy + t * K * 8, (n, 2), np.float32))
+        rows["desc"].append(rd(v.desc + t * K * 32, (n, 32), np.uint8).astype(np.float32))
+        rows["octave"].append(rd(v.octave + t * K * 4, (n,), np.int32).astype(np.float32))
+        rows["angle"].append(rd(v.angle + t * K * 4, (n,), np.float32))
+        rows["response"].append(rd(v.response + t * K * 4, (n,), np.float32))
+        rows["xyz"].append(rd(pv.xyz + t * pv.capacity * 24, (n, 3), np.float64))
+        rows["valid"].append(rd(pv.valid + t * pv.capacity, (n,), np.uint8).astype(np.float32))
+        rows["match_from"].append(rd(v.match_from + t * K * 4, (m,), np.int32).astype(np.float32))
+        rows["match_to"].append(rd(v.match_to + t * K * 4, (m,), np.int32).astype(np.float32))
+    if pnp:
+        out["pnp_pose"] = rd(ctx.pnp_view().pose, (B, 16), np.float64)
+    if bow:
+        nw = rd(bv.n_words, (B,), np.int32)
+        out["bow_n_words"] = nw.astype(np.float32)
+        out["bow_best_entry"] = rd(bv.best_entry, (B,), np.int32).astype(np.float64)
+        out["bow_best_score"] = rd(bv.best_score, (B,), np.float64)
+        out["bow_word_offset"] = np.concatenate([[0], np.cumsum(nw[idx].astype(np.int64))]).astype(np.float64)
+        rows["bow_words"], rows["bow_values"] = [], []
+        for t in idx.tolist():
+            rows["bow_words"].append(rd(bv.words + t * bv.capacity * 4, (int(nw[t]),), np.uint32).astype(np.float64))
+            rows["bow_values"].append(rd(bv.values + t * bv.capacity * 8, (int(nw[t]),), np.float64))
+    for k, parts in rows.items():
+        out[k] = np.concatenate(parts)
+    total = sum(x.nbytes for x in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return {"dir": out_dir, "files": len(out), "bytes": int(total), "frames_sampled": n_sample}
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -201,7 +267,12 @@ def parse():
                     help="single-GPU runs: create a one-rank process group on the nccl (= RCCL) backend and issue the cfg4 leg's "
                          "all-gather as a real RCCL collective instead of the world-1 device copy (what one GPU can exercise of "
                          "the RCCL path; not part of the default run: a box without a usable RCCL would hang it)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def spawn_ranks(a):
@@ -833,6 +904,10 @@ def main():
 
     # ---- after the timed region ---------------------------------------------------------------------------
     extras = {}
+    if a.dump_outputs and rank == 0:
+        # before any leg below runs the context again: its views still hold the last timed step
+        extras["dump_outputs"] = dump_outputs(a.dump_outputs, pkg, ctx, B, ((w_eff + a.steps - 1) % n_batches) * B,
+                                              a.pnp, a.bow)
     # Nothing after the timed region may cost the headline line: a failure in an extra leg is recorded in the line, and
     # with several ranks a watchdog prints the line without the extras if a collective of the extras never completes
     # (rank 0) / ends the rank quietly (the others).

@@ -63,13 +63,8 @@ def test_pattern_table_checksum():
     h = 0x811C9DC5
     for v in vals:
         h = ((h ^ (v & 0xFF)) * 0x01000193) & 0xFFFFFFFF
+    # 0x28710593 is the FNV-1a of the reference's own orb_point_pairs table (tools/gen_pattern.py): the pin to its numbers
     assert h == fnv == 0x28710593
-    ref = "/root/reference/src/lib/modular_slam/distributed_cv_feature.cpp"
-    if os.path.exists(ref):  # build container only: the table equals the reference's numbers
-        import sys
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import gen_pattern
-        assert gen_pattern.parse_reference() == vals
 
 
 def test_no_product_code_touches_the_oracle():
