@@ -313,21 +313,30 @@ size_t mslam_hip_packed_capacity(const mslam_hip_ctx* ctx, int n_frames, int wit
  * image_points = n x 2 f32 (:33-40), pin-hole intrinsics as in :52-53.  rvec / tvec (3 doubles each, Rodrigues vector
  * and translation of the world -> camera transform, OpenCV's convention) are the extrinsic guess on input when
  * use_extrinsic_guess is non-zero, and the result on output; inliers (n bytes, may be NULL) is the consensus mask of
- * the best hypothesis.  Returns MSLAM_HIP_E_NO_MODEL when no hypothesis reaches 4 inliers (solvePnPRansac == false).
+ * the best hypothesis.  Returns MSLAM_HIP_E_NO_MODEL when no hypothesis reaches 5 inliers (solvePnPRansac == false).
  * Against cv::solvePnPRansac as OpenCV 4.8.1 runs it for this call (restated piece by piece in
- * oracle/mslam_cv_pnp_oracle.py from the library's published algorithm), of the four pieces
+ * oracle/mslam_cv_pnp_oracle.py from the library's published algorithm), of the four pieces and two edges
  *   1 sampler          DEVIATES: splitmix64 counter streams keyed by (`seed`, hypothesis) — hypotheses are independent of
  *                      each other, which is what lets them run in parallel — not cv::RNG((uint64)-1)'s one sequential
  *                      multiply-with-carry stream drawing 5-point subsets;
- *   2 minimal solver   DEVIATES: P3P on three points, the fourth picks the branch — not EPnP on five points;
+ *   2 minimal solver   DEVIATES: P3P on three points, the fourth picks the branch — not EPnP on five points; a sample
+ *                      whose three P3P pixels are not pairwise distinct yields no hypothesis;
  *   3 consensus loop   SAME: squared reprojection error <= 5^2 px, a hypothesis replaces the best one only with MORE inliers
- *                      (and at least 4), RANSACUpdateNumIters(confidence, outlier share, 5 model points) after every new
+ *                      (and at least 5: goodCount > max(maxGoodCount, modelPoints - 1), modelPoints = 5; a best
+ *                      hypothesis of 4 inliers is no model), RANSACUpdateNumIters(confidence, outlier share, 5 model points) after every new
  *                      best one, hypotheses looked at in order (the kernel scores them in parallel rounds and walks each
  *                      round in order);
  *   4 final refit      SAME objective and set (reprojection error over the inliers of the best hypothesis, all in double),
  *                      other minimiser and start: damped Gauss-Newton to convergence from the caller's guess (or the best
  *                      hypothesis) — OpenCV runs <= 20 Levenberg-Marquardt steps from the LAST hypothesis its loop
- *                      evaluated (the callback writes every hypothesis into the guess buffers).
+ *                      evaluated (the callback writes every hypothesis into the guess buffers);
+ *   5 points behind    DEVIATES: a point is an inlier only in front of the camera (depth > 1e-9).  cv::projectPoints
+ *     the camera       divides by a negative depth, so OpenCV counts a point behind the camera whose mirrored projection
+ *                      lands within 5 px; such a point is no evidence for the pose, and the library keeps its test;
+ *   6 n <= 5           DEVIATES: when n equals its model points (n = 4: P3P, n = 5: EPnP), solvePnPRansac solves on all
+ *                      n points and reports every one an inlier, with no consensus test (from OpenCV's published
+ *                      solvepnp.cpp; not checked against a build).  This library runs the same RANSAC loop for every n >= 4:
+ *                      n = 4 never has a model, n = 5 has one only when all five agree within 5 px.
  * So the hypothesis sequence differs, the result the call site consumes (success, consensus set, refined pose,
  * cv_ransac_pnp.cpp:59-83) agrees wherever the consensus set is unambiguous: tests/test_pnp.py compares both entry
  * points with that oracle (masks equal, rvec / tvec within 1e-6 on noise-free scenes with 0 - 60 % outliers; within
@@ -357,7 +366,7 @@ typedef struct
 {
     int32_t capacity;          /* per-frame stride of the correspondence arrays (max_keypoints)                 */
     const double* pose;        /* [max_batch][16]: R row-major (9), t (3), inliers, best hypothesis, status, cost;
-                                * status 1 = a model was found, 0 = none (fewer than 4 points / 4 inliers)      */
+                                * status 1 = a model was found, 0 = none (fewer than 4 points / 5 inliers)      */
     const int32_t* n_points;   /* [max_batch] correspondences of the frame                                      */
     const float* object_points; /* [max_batch][capacity][3]                                                     */
     const float* image_points;  /* [max_batch][capacity][2]                                                     */

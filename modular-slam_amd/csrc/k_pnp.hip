@@ -24,6 +24,7 @@
 #include "context.hpp"
 #include "../../include/mslam_sincos.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -193,6 +194,10 @@ __device__ __forceinline__ bool is_inlier(const Cam& k, const double* R, const d
 // P3P on points 0..2 of the sample (Grunert's quartic), the 4th point picks among the solutions
 __device__ bool p3p_hypothesis(const Cam& k, const V3* P, const double* uv, double* R, double* t)
 {
+    // two of the three pixels the same: the sample says nothing about the pose (all-equal pixels admit a camera
+    // arbitrarily far away that explains every point), so it yields no hypothesis
+    if((uv[0] == uv[2] && uv[1] == uv[3]) || (uv[0] == uv[4] && uv[1] == uv[5]) || (uv[2] == uv[4] && uv[3] == uv[5]))
+        return false;
     V3 f[3];
     for(int i = 0; i < 3; ++i)
     {
@@ -284,7 +289,8 @@ __device__ __forceinline__ int ransac_update_iters(double p, double ep, int mode
 // cv_ransac_pnp.cpp:56-57) samples 5 points per hypothesis when there are more than 4 (its minimal solver is then EPnP), so its
 // loop ends after log(1 - p) / log(1 - w^5) samples.  This library's hypotheses come from 3 + 1 points (P3P), but the stopping
 // rule follows the call site: with 4 the loop would stop earlier than the reference's (17 instead of 25 hypotheses at 30 %
-// outliers).
+// outliers).  So does the consensus floor of the same loop: a hypothesis needs more than modelPoints - 1 inliers, i.e. at
+// least 5, to become the best one, and with no such hypothesis there is no model.
 constexpr int kPnpModelPoints = 5;
 constexpr int kPnpThreads = 256;
 
@@ -451,7 +457,7 @@ __device__ __forceinline__ void pnp_problem(const PnpArgs& a, double* red /* LDS
                 {
                     const int hh = h0 + k;
                     // RANSACPointSetRegistrator::run: goodCount > max(maxGoodCount, modelPoints - 1)
-                    if(counts[hh] > max(bc, 3))
+                    if(counts[hh] > max(bc, kPnpModelPoints - 1))
                     {
                         bc = counts[hh], best = hh;
                         niters = ransac_update_iters(a.confidence, (double)(n - bc) / (double)n, kPnpModelPoints, niters);
@@ -463,7 +469,7 @@ __device__ __forceinline__ void pnp_problem(const PnpArgs& a, double* red /* LDS
         }
     }
     const int best = s_best;
-    if(best < 0 || s_cnt < 4)
+    if(best < 0 || s_cnt < kPnpModelPoints)
     {
         if(tid == 0)
         {
@@ -853,7 +859,7 @@ extern "C" int mslam_hip_pnp_ransac(mslam_hip_ctx* c, const float* object_points
     };
     if(!object_points || !image_points || !rvec || !tvec || n < 4 || iterations < 1 || iterations > 4096 ||
        !(reprojection_error > 0) || !(fx != 0.0) || !(fy != 0.0))
-        return fail(MSLAM_HIP_E_INVALID, "pnp_ransac: bad argument (at least 4 points, 1..4096 iterations)");
+        return fail(MSLAM_HIP_E_INVALID, "pnp_ransac: bad argument (at least 4 points, 1..4096 iterations; a model needs 5 inliers)");
     if(n_inliers)
         *n_inliers = 0;
     hipError_t e = hipSetDevice(c->p.device);
@@ -873,8 +879,10 @@ extern "C" int mslam_hip_pnp_ransac(mslam_hip_ctx* c, const float* object_points
         c->d_pnp1_hyp = c->d_pnp1_out = nullptr;
         c->d_pnp1_counts = nullptr;
         c->d_pnp1_mask = nullptr;
+        // (never below the old capacities: a large call followed by one with more iterations must not shrink the point
+        // buffers, or the next large call reallocates again)
+        const int n_cap = std::max({n, 1024, c->pnp1_n_cap}), it_cap = std::max({iterations, 128, c->pnp1_it_cap});
         c->pnp1_n_cap = c->pnp1_it_cap = 0;
-        const int n_cap = std::max(n, 1024), it_cap = std::max(iterations, 128);
         PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_obj), (size_t)n_cap * 12));
         PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_img), (size_t)n_cap * 8));
         PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_hyp), (size_t)it_cap * 12 * 8));
@@ -918,7 +926,7 @@ extern "C" int mslam_hip_pnp_ransac(mslam_hip_ctx* c, const float* object_points
         return MSLAM_HIP_E_RUNTIME;
     }
     if(out[14] != 1.0)
-        return fail(MSLAM_HIP_E_NO_MODEL, "pnp_ransac: no hypothesis reached 4 inliers");
+        return fail(MSLAM_HIP_E_NO_MODEL, "pnp_ransac: no hypothesis reached 5 inliers");
     R_to_rodrigues(out, rvec);
     tvec[0] = out[9], tvec[1] = out[10], tvec[2] = out[11];
     if(inliers)

@@ -96,6 +96,8 @@ def p3p(P, uv, cam):
 def hypothesis(obj, img, cam, idx):
     P, uv = obj[idx].astype(np.float64), img[idx].astype(np.float64)
     best = None
+    if any((uv[i] == uv[j]).all() for i, j in ((0, 1), (0, 2), (1, 2))):
+        return None            # two of the three P3P pixels the same: no hypothesis (as the kernel)
     try:
         sols = p3p(P[:3], uv[:3], cam)
     except (np.linalg.LinAlgError, FloatingPointError, ZeroDivisionError):
@@ -155,8 +157,9 @@ def refine(R, t, obj, img, cam, mask, iters=50):
     return R, t, c
 
 
-# modelPoints of RANSACUpdateNumIters as cv::solvePnPRansac sets it for the reference's call (default flags, more than 4
-# points: 5, calib3d/src/solvepnp.cpp) — the library's own minimal sample is 3 + 1 points, its stopping rule is the call site's
+# modelPoints of RANSACUpdateNumIters and of the consensus floor as cv::solvePnPRansac sets it for the reference's call
+# (default flags, more than 4 points: 5, calib3d/src/solvepnp.cpp) — the library's own minimal sample is 3 + 1 points, its
+# stopping rule and floor are the call site's
 MODEL_POINTS = 5
 
 
@@ -176,10 +179,11 @@ def update_num_iters(p, ep, model_points, max_iters):
     return int(np.rint(num / denom))                  # cvRound
 
 
-def pnp_ransac(obj, img, cam, iterations=100, thr=5.0, seed=0, guess=None, confidence=0.99):
-    """-> dict(R, t, mask, best, counts, hyps, looked_at) or None.  cam = (fx, fy, cx, cy); guess = (R0, t0) or None.
-    The loop is RANSACPointSetRegistrator::run's: hypotheses in order, a new best one (more inliers than the best so far
-    and at least 4) lowers the iteration count for `confidence` (cv_ransac_pnp.cpp:57 passes 0.99)."""
+def consensus(obj, img, cam, iterations=100, thr=5.0, seed=0, confidence=0.99):
+    """RANSACPointSetRegistrator::run's loop on the kernel's hypotheses -> dict(best, counts, hyps, looked_at); best = -1
+    when no hypothesis reached the floor.  Hypotheses are looked at in order; one becomes the best only with more inliers
+    than the best so far and more than MODEL_POINTS - 1 (goodCount > max(maxGoodCount, modelPoints - 1)), and a new best
+    one lowers the iteration count for `confidence` (cv_ransac_pnp.cpp:57 passes 0.99)."""
     obj, img = np.asarray(obj, np.float32), np.asarray(img, np.float32)
     n = len(obj)
     hyps, counts = [], []
@@ -189,13 +193,22 @@ def pnp_ransac(obj, img, cam, iterations=100, thr=5.0, seed=0, guess=None, confi
         hy = hypothesis(obj, img, cam, idx) if idx is not None else None
         hyps.append(hy)
         counts.append(-1 if hy is None else int(inliers_of(hy[0], hy[1], obj, img, cam, thr).sum()))
-        if counts[h] > max(bc, 3):
+        if counts[h] > max(bc, MODEL_POINTS - 1):
             bc, best = counts[h], h
             niters = update_num_iters(confidence, (n - bc) / n, MODEL_POINTS, niters)
         h += 1
+    return dict(best=best, counts=counts, hyps=hyps, looked_at=h)
+
+
+def pnp_ransac(obj, img, cam, iterations=100, thr=5.0, seed=0, guess=None, confidence=0.99):
+    """-> dict(R, t, mask, best, counts, hyps, looked_at) or None (no hypothesis reached MODEL_POINTS inliers).
+    cam = (fx, fy, cx, cy); guess = (R0, t0) or None.  The loop: consensus() above."""
+    obj, img = np.asarray(obj, np.float32), np.asarray(img, np.float32)
+    run = consensus(obj, img, cam, iterations, thr, seed, confidence)
+    best, hyps = run["best"], run["hyps"]
     if best < 0:
         return None
     mask = inliers_of(hyps[best][0], hyps[best][1], obj, img, cam, thr)
     R0, t0 = guess if guess is not None else hyps[best]
     R, t, c = refine(np.array(R0, np.float64), np.array(t0, np.float64), obj, img, cam, mask)
-    return dict(R=R, t=t, mask=mask, best=best, counts=counts, hyps=hyps, cost=c, looked_at=h)
+    return dict(R=R, t=t, mask=mask, best=best, counts=run["counts"], hyps=hyps, cost=c, looked_at=run["looked_at"])

@@ -142,17 +142,22 @@ def test_plugin_cv_orb_detector(built, orc, bundled_frames, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("negative_w", [False, True])
+@pytest.mark.parametrize("negative_w", [False, True, "four_inliers"])
 def test_plugin_pnp(built, tmp_path, negative_w):
     """hipRansacPnpFactory: the OpenCvRansacPnp drop-in (cv_ransac_pnp.cpp:14-85) through the loader — sensor pose in,
     sensor pose out (the adapter does the world->camera inversions of :42-50 and :65-78 around the solver).  The initial
     orientation is also passed as -q (w < 0: the same rotation; Eigen::AngleAxisd folds the sign into the axis,
-    cv_ransac_pnp.cpp:44-48): the extrinsic guess, and so the result, must not change."""
+    cv_ransac_pnp.cpp:44-48): the extrinsic guess, and so the result, must not change.  "four_inliers": a scene whose best
+    hypothesis explains exactly 4 points — below the consensus floor of 5, so the adapter returns nullopt."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import mslam_pnp_oracle as po
     from test_pnp import CAM, scene, rot_err
     obj, img, R, t, good = scene(21, n=500, outliers=0.25)
+    if negative_w == "four_inliers":
+        from test_pnp_edges import four_inlier_scene
+        obj, img = four_inlier_scene()[:2]
+        assert max(po.consensus(obj, img, CAM, seed=0)["counts"]) == 4     # the plugin samples with seed 0
     # the sensor pose (world frame) that corresponds to the camera transform (R, t): orientation R^T, position -R^T t
     Rs, ps = R.T, -R.T @ t
     # start from a perturbed sensor pose (what the frontend passes: the previous frame's pose)
@@ -171,6 +176,9 @@ def test_plugin_pnp(built, tmp_path, negative_w):
         f.write(struct.pack("<4d", *CAM))
     r = subprocess.run([HARNESS, PLUGIN, "--pnp", str(path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
+    if negative_w == "four_inliers":
+        assert "pnp none" in r.stdout.splitlines() and "Didnt find pnp solution" in r.stderr, (r.stdout, r.stderr)
+        return
     line = [l for l in r.stdout.splitlines() if l.startswith("pnp position")][0].split()
     pos = np.array([float(x) for x in line[2:5]])
     q = np.array([float(x) for x in line[6:10]])
