@@ -195,7 +195,10 @@ int mslam_hip_bow_info(mslam_hip_ctx* ctx, int* k, int* L, int* n_nodes, int* n_
  * distance, first child on ties) — what DBoW3 does, the default;
  * FLAT = the exhaustive descriptor-vs-vocabulary search the descent approximates (BASELINE.json north_star's
  * "batched descriptor-vs-vocabulary Hamming kernel", SURVEY.md §8d bow_flat): the leaf with the least distance
- * over ALL words, lower word id on ties.  n x n_words distance evaluations: a stress mode, not a DBoW3 drop-in. */
+ * over ALL words, lower word id on ties.  n x n_words distance evaluations: a stress mode, not a DBoW3 drop-in.
+ * FLAT is available only when the vocabulary's word table maps one-to-one onto its leaves (distinct word ids, one per
+ * leaf, none on an inner node) and holds at most 2^20 words; otherwise setting it fails with MSLAM_HIP_E_INVALID and
+ * the mode stays as it was, whatever modes were set before. */
 enum
 {
     MSLAM_BOW_ASSIGN_TREE = 0,

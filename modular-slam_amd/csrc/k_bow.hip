@@ -64,6 +64,7 @@ struct BowState
     double* d_leaf_weight = nullptr; // [n_words]
     uint32_t* d_fbest = nullptr;     // [B+1][cap] (distance << 20) | word
     int flat = 0;                    // MSLAM_BOW_ASSIGN_*
+    bool flat_ok = false;            // the word table maps one-to-one onto the leaves, <= 2^20 words
     // inverted file of the database (DBoW3 Database: m_ifile, word -> (entry, value) rows).  Postings live in an
     // append-only log, entry after entry; the rows of a word are a linked list threaded through the log
     // (ix_prev), newest first, anchored at ix_head[word].  Index 0 is the null posting.
@@ -395,10 +396,10 @@ __global__ __launch_bounds__(VT) void k_bow_vector(const uint32_t* __restrict__ 
             const uint32_t pos = running + pre + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
             const uint32_t wid = (uint32_t)(key >> 32);
             const double w = fv[(uint32_t)key];
-            double v = w; // addWeight: first hit inserts w, later hits += w (same word => same weight)
-            if(tf)
+            double v = w; // addWeight: the first hit inserts its weight, every later hit adds its own (two leaves
+            if(tf)        // can share a word id, with different weights), in feature order
                 for(int j = i + 1; j < npow2 && (uint32_t)(keys[j] >> 32) == wid && keys[j] != ~0ull; ++j)
-                    v += w;
+                    v += fv[(uint32_t)keys[j]];
             ow[pos] = wid;
             ov[pos] = v;
         }
@@ -1083,14 +1084,21 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
         nchild[par]++;
     }
     const uint32_t n_words = r.get<uint32_t>();
-    if(!r.ok)
+    if(!r.ok || (size_t)n_words * 8 > size - r.pos)
         return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: truncated stream");
+    // word records per node and per word id, for the flat mode's one-to-one check below
+    std::vector<uint32_t> node_words(n_nodes, 0);
+    std::vector<uint8_t> wid_seen(n_words, 0);
+    bool wids_distinct = true;
     for(uint32_t i = 0; i < n_words; ++i)
     {
         const uint32_t wid = r.get<uint32_t>(), nid = r.get<uint32_t>();
         if(!r.ok || wid >= n_words || nid >= n_nodes)
             return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad word record");
         word[nid] = wid;
+        wids_distinct = wids_distinct && !wid_seen[wid];
+        wid_seen[wid] = 1;
+        node_words[nid]++;
     }
     // children in stream order (m_nodes[parent].children.push_back, :2626)
     std::vector<uint32_t> coff(n_nodes + 1, 0), fill(n_nodes, 0), child(n_nodes, 0);
@@ -1209,25 +1217,24 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
               hipMemcpy(b->d_weight, sweight.data(), n_nodes * 8, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemset(b->d_rn, 0, RP * 4) == hipSuccess && hipMemset(b->d_bn, 0, (B + 1) * 4) == hipSuccess;
     {
-        // leaves in word-id order for the flat search (a word id is 20 bits in its key)
+        // leaves in word-id order for the flat search (a word id is 20 bits in its key).  The flat search stands in
+        // for the descent only when the word table is a one-to-one map onto the leaves: n_words distinct ids, exactly
+        // one record per leaf and none on an inner node (so n_words == number of leaves).
         std::vector<uint8_t> ldesc((size_t)n_words * 32, 0);
         std::vector<double> lweight(n_words, 0.0);
-        std::vector<uint8_t> seen(n_words, 0);
-        bool leaves_ok = n_words <= (1u << 20);
+        bool leaves_ok = n_words <= (1u << 20) && wids_distinct;
         for(uint32_t nid = 0; nid < n_nodes && leaves_ok; ++nid)
-            if(nid != 0 && nchild[nid] == 0)
+        {
+            const bool leaf = nid != 0 && nchild[nid] == 0;
+            leaves_ok = node_words[nid] == (leaf ? 1u : 0u);
+            if(leaf && leaves_ok)
             {
-                const uint32_t w = word[nid];
-                if(w >= n_words || seen[w])
-                    leaves_ok = false;
-                else
-                {
-                    seen[w] = 1;
-                    std::memcpy(&ldesc[(size_t)w * 32], &desc[(size_t)nid * 32], 32);
-                    lweight[w] = weight[nid];
-                }
+                std::memcpy(&ldesc[(size_t)word[nid] * 32], &desc[(size_t)nid * 32], 32);
+                lweight[word[nid]] = weight[nid];
             }
-        b->flat = leaves_ok ? 0 : -1; // -1: flat mode unavailable for this vocabulary (words are not 1:1 with leaves)
+        }
+        b->flat = MSLAM_BOW_ASSIGN_TREE;
+        b->flat_ok = leaves_ok;
         ok = ok && hipMemcpy(b->d_leaf_desc, ldesc.data(), ldesc.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(b->d_leaf_weight, lweight.data(), lweight.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
     }
@@ -1636,8 +1643,9 @@ int mslam_hip_bow_set_assignment(mslam_hip_ctx* c, int mode)
         return rc;
     if(mode != MSLAM_BOW_ASSIGN_TREE && mode != MSLAM_BOW_ASSIGN_FLAT)
         return bfail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: unknown mode");
-    if(mode == MSLAM_BOW_ASSIGN_FLAT && c->bow->flat < 0)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: this vocabulary's words are not one per leaf (or more than 2^20)");
+    if(mode == MSLAM_BOW_ASSIGN_FLAT && !c->bow->flat_ok)
+        return bfail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: this vocabulary's word table does not map one-to-one onto "
+                                             "its leaves (or has more than 2^20 words)");
     c->bow->flat = mode;
     return MSLAM_HIP_OK;
 }

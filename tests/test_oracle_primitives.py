@@ -265,6 +265,45 @@ def test_bow_against_python(orc):
         assert list(bw) == keys and list(bv) == [acc[k] / norm for k in keys]
     assert orc.bow_score_l1(bw, bv, bw, bv) == pytest.approx(1.0, abs=1e-12)
     assert orc.bow_score_l1(bw[:0], bv[:0], bw, bv) == 0.0
+    # the same walk on trees that are not heap-numbered (vocab_shapes): children in stream order, the word through
+    # the word table, stopped (zero-weight) words left out of the vector
+    import vocab_shapes
+    docs = [rng.integers(0, 256, (300, 32), dtype=np.uint8) for _ in range(4)]
+    for weighting in (0, 1, 2, 3):
+        for blob in (vocab_shapes.make_irregular_vocabulary("mixed", seed=1, weighting=weighting),
+                     vocab_shapes.make_dbow3_vocabulary(docs, 5, 3, seed=2, weighting=weighting)):
+            V = orc.Vocabulary(blob)
+            n_nodes, = np.frombuffer(blob, "<u4", 1, 9)
+            nodes = np.frombuffer(blob, rec, n_nodes - 1, 13 + 16)
+            n_words, = np.frombuffer(blob, "<u4", 1, 29 + nodes.nbytes)
+            table = np.frombuffer(blob, "<u4", 2 * n_words, 33 + nodes.nbytes).reshape(-1, 2)
+            word_of = {int(n): int(w) for w, n in table}
+            by_id = {int(n["id"]): n for n in nodes}
+            children = {}
+            for n in nodes:
+                children.setdefault(int(n["pid"]), []).append(int(n["id"]))
+            d = rng.integers(0, 256, (200, 32), dtype=np.uint8)
+            d[:40] = np.stack([by_id[c]["d"] for c in rng.choice(list(word_of), 40)])   # leaf descriptors
+            w, wt = V.words(d)
+            acc = {}
+            for r in range(200):
+                cur = 0
+                while cur in children:
+                    dist = [int(np.unpackbits(d[r] ^ by_id[c]["d"]).sum()) for c in children[cur]]
+                    cur = children[cur][int(np.argmin(dist))]
+                assert w[r] == word_of[cur] and wt[r] == by_id[cur]["w"]
+                if not wt[r] > 0:
+                    continue
+                if weighting in (0, 1):
+                    acc[w[r]] = acc[w[r]] + wt[r] if w[r] in acc else wt[r]
+                else:
+                    acc.setdefault(w[r], wt[r])
+            keys = sorted(acc)
+            norm = 0.0
+            for k in keys:
+                norm += abs(acc[k])
+            bw, bv = V.bow_vector(d)
+            assert list(bw) == keys and list(bv) == [acc[k] / norm for k in keys]
 
 
 def test_backproject_against_numpy(orc, bundled_depth):
