@@ -377,6 +377,58 @@ typedef struct
 } mslam_hip_pnp_view;
 int mslam_hip_get_pnp_view(mslam_hip_ctx* ctx, mslam_hip_pnp_view* view);
 
+/* ---- MinMseTracker::solvePnp (ceres_reprojection_error_pnp.cpp:18-110): min-MSE PnP -----------------------------------
+ * The reference's second IPnpAlgorithm: a Ceres Levenberg-Marquardt solve over x = (r, t), r an angle-axis vector and t a
+ * translation, of cost = 1/2 sum_i |observed_i - projected_i|^2 with
+ *   projected_i = (fx X/Z + cx, fy Y/Z + cy),  (X, Y, Z) = ceres::AngleAxisRotatePoint(r, P_i) + t,
+ * no loss function, all in double, started from the caller's (r, t).  Every point takes part (no outlier rejection).
+ * object_points = n x 3 f64, image_points = n x 2 f64, rvec / tvec = the start on input, the result on output.
+ * termination (ceres::TerminationType: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE), iterations (trust-region iterations
+ * after iteration 0: the index of the iteration that ended the solve) and final_cost may be NULL.
+ * Returns MSLAM_HIP_OK for 0 and 1 (Summary::IsSolutionUsable()), MSLAM_HIP_E_NO_MODEL for FAILURE with rvec / tvec left
+ * unchanged, MSLAM_HIP_E_INVALID for bad arguments.  n = 0 is OK, termination 0, pose unchanged, cost 0: Ceres's
+ * solver.cc Minimize() reports "No non-constant parameter blocks found" as CONVERGENCE for a problem whose reduced
+ * program has no parameter blocks (restated from the published source; not checked against a build).
+ * Against Ceres 2.2 as the call site configures it (gradient / function / parameter tolerance 1e-8, :88-90; all else the
+ * Solver::Options defaults), restated from the published trust_region_minimizer.cc, levenberg_marquardt_strategy.cc,
+ * trust_region_step_evaluator.cc and solver.h.  PARITY UNPINNED: no Ceres build exists to compare with; the tests compare
+ * with an independent numpy restatement (tests/mse_pnp_ref.py) and with ground truth.
+ *   residual + derivatives   SAME function (AngleAxisRotatePoint with its theta^2 <= DBL_EPSILON branch p + r x p, then
+ *                            the pin-hole, then observed - projected); derivatives by forward-mode dual numbers with
+ *                            jet.h's formulas (the rotation on 3-slot jets: its translation slots are exactly 0);
+ *   sin / cos                DEVIATES in the last bits: the device's f64 sin / cos, not the host C library's;
+ *   sums                     DEVIATES in rounding: cost, J^T J and J^T f are summed per lane, then by a fixed butterfly,
+ *                            not in Ceres's evaluation order;
+ *   linear solver            DEVIATES in rounding: Cholesky of the 6x6 normal equations (J_s^T J_s + D^2) y = J_s^T f
+ *                            with D^2 = clamp(diag(J_s^T J_s), 1e-6, 1e32) / radius, instead of DENSE_QR (or
+ *                            SPARSE_NORMAL_CHOLESKY) on the D-augmented system; the model cost change
+ *                            -(f^T J_s d + |J_s d|^2 / 2) is evaluated from the normal equations.  A non-positive pivot
+ *                            or a non-finite step is a linear-solver failure = an invalid step, as in Ceres;
+ *   Jacobi scaling           SAME: 1 / (1 + |J_col|) from the Jacobian at the start, once;
+ *   trust region             SAME: radius 1e4 .. 1e16, ends below 1e-32; accepted step (relative decrease > 1e-3,
+ *                            monotonic): radius /= max(1/3, 1 - (2 rho - 1)^3), decrease factor 2; rejected step:
+ *                            radius /= factor, factor *= 2; 5 invalid steps in a row: FAILURE;
+ *   candidate point          SAME: a candidate whose cost is not finite counts as cost DBL_MAX (a rejected step, as
+ *                            ComputeCandidatePointAndEvaluateCost does; it is not an "invalid step");
+ *   termination              SAME order: iteration 50 -> NO_CONVERGENCE; successful step with |x - (x - g)|_inf <= 1e-8,
+ *                            radius <= 1e-32, |x - x_candidate| <= 1e-8 (|x| + 1e-8) or |cost change| <= 1e-8 cost
+ *                            -> CONVERGENCE (the candidate of the last two is not taken); non-finite cost or Jacobian
+ *                            at the start or at an accepted point -> FAILURE;
+ *   FAILURE result           DEVIATES: the pose is left unchanged (Ceres writes its best point back; the reference
+ *                            discards it: IsSolutionUsable() is false);
+ *   progress printout        not reproduced (minimizer_progress_to_stdout, :91). */
+int mslam_hip_pnp_min_mse(mslam_hip_ctx* ctx, const double* object_points /* n x 3 */, const double* image_points /* n x 2 */,
+                          int n, double fx, double fy, double cx, double cy,
+                          double* rvec /* in: start, out: result */, double* tvec /* in/out */,
+                          int* termination /* may be NULL */, int* iterations /* may be NULL */, double* final_cost /* may be NULL */);
+/* Batched, device pointers, asynchronous on the context's stream (one wave64 per problem): problem p has n[p] <= capacity
+ * points at object[p*capacity*3], image[p*capacity*2]; pose[p*6 .. +6] = (r, t) in / out (out only when the termination
+ * is not FAILURE); info[p*4 .. +4] = termination, iterations, initial cost, final cost.  n[p] outside [0, capacity] is
+ * FAILURE.  The single-problem call launches this same kernel, so a problem gives bit-identical results either way. */
+int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* ctx, const double* d_object, const double* d_image, const int32_t* d_n,
+                                    int n_problems, int capacity, double fx, double fy, double cx, double cy,
+                                    double* d_pose, double* d_info);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "mslam_hip_join_matcher", "mslam_hip_bow_db_remove", "mslam_hip_bow_set_assignment",
     "mslam_hip_bow_db_reserve", "mslam_hip_bow_db_size", "mslam_hip_qlz_decompress",
     "mslam_hip_pnp_ransac", "mslam_hip_pnp_batch_dev", "mslam_hip_get_pnp_view", "mslam_hip_pnp_set_confidence", "mslam_hip_pack_batch_dev", "mslam_hip_packed_capacity",
-    "mslam_hip_set_cv_keypoint_order",
+    "mslam_hip_set_cv_keypoint_order", "mslam_hip_pnp_min_mse", "mslam_hip_pnp_min_mse_batch_dev",
 ]
 
 
@@ -324,6 +324,34 @@ class Context:
             return None
         self._chk(rc)
         return r, t, mask.astype(bool)
+
+    # ---- min-MSE PnP (MinMseTracker, ceres_reprojection_error_pnp.cpp:18-110) --------------------
+    def pnp_min_mse(self, object_points, image_points, focal=(525.0, 525.0), principal=(319.5, 239.5), rvec=(0, 0, 0),
+                    tvec=(0, 0, 0)):
+        """Levenberg-Marquardt on the reprojection error of every point, from (rvec, tvec) (angle-axis, translation)
+        -> (rvec, tvec, termination, iterations, final cost); termination 0 CONVERGENCE, 1 NO_CONVERGENCE.
+        Raises MslamHipError(E_NO_MODEL) when the minimiser ends in FAILURE (Summary::IsSolutionUsable() == false)."""
+        obj = np.ascontiguousarray(object_points, np.float64).reshape(-1, 3)
+        img = np.ascontiguousarray(image_points, np.float64).reshape(-1, 2)
+        if len(obj) != len(img):
+            raise MslamHipError(E_INVALID, "pnp_min_mse: %d object points, %d image points" % (len(obj), len(img)))
+        r = np.array(rvec, np.float64).reshape(3)
+        t = np.array(tvec, np.float64).reshape(3)
+        term, iters, cost = C.c_int(-1), C.c_int(0), C.c_double(0)
+        self._chk(self.L.mslam_hip_pnp_min_mse(self._h, _p(obj), _p(img), len(obj), C.c_double(focal[0]), C.c_double(focal[1]),
+                                               C.c_double(principal[0]), C.c_double(principal[1]), _p(r), _p(t),
+                                               C.byref(term), C.byref(iters), C.byref(cost)))
+        return r, t, term.value, iters.value, cost.value
+
+    def pnp_min_mse_batch_dev(self, d_object, d_image, d_n, n_problems, capacity, d_pose, d_info, focal=(525.0, 525.0),
+                              principal=(319.5, 239.5)):
+        """one min-MSE PnP per problem on device data (raw device pointers), asynchronous on the context's stream:
+        object f64[n_problems][capacity][3], image f64[n_problems][capacity][2], n i32[n_problems],
+        pose f64[n_problems][6] (r, t) in / out, info f64[n_problems][4] = termination, iterations, initial cost, final cost"""
+        self._chk(self.L.mslam_hip_pnp_min_mse_batch_dev(self._h, C.c_void_p(d_object), C.c_void_p(d_image), C.c_void_p(d_n),
+                                                         int(n_problems), int(capacity), C.c_double(focal[0]),
+                                                         C.c_double(focal[1]), C.c_double(principal[0]),
+                                                         C.c_double(principal[1]), C.c_void_p(d_pose), C.c_void_p(d_info)))
 
     # ---- bag of words --------------------------------------------------------------------------
     def bow_load(self, blob):

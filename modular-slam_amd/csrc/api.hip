@@ -374,7 +374,7 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
                     c->quad.child_cnt, c->quad.ninfo, c->quad.best, c->d_flags, c->d_hm_from, c->d_hm_out, c->d_hm_partial,
                     c->d_xyz, c->d_valid, c->d_pnp_obj, c->d_pnp_img, c->d_pnp_n, c->d_pnp_counts, c->d_pnp_hyp, c->d_pnp_out,
                     c->d_pnp_mask, c->d_blur_waves, c->d_pnp1_obj, c->d_pnp1_img, c->d_pnp1_hyp, c->d_pnp1_out,
-                    c->d_pnp1_counts, c->d_pnp1_mask};
+                    c->d_pnp1_counts, c->d_pnp1_mask, c->d_mse1};
     for(void* b : bufs)
         if(b)
             (void)hipFree(b);

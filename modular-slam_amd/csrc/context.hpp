@@ -149,6 +149,9 @@ struct mslam_hip_ctx
     int32_t* d_pnp1_counts = nullptr;
     uint8_t* d_pnp1_mask = nullptr;
     int pnp1_n_cap = 0, pnp1_it_cap = 0;
+    // single-problem min-MSE PnP scratch (mslam_hip_pnp_min_mse): [obj | img | pose | info | n] in one block, grown on demand
+    double* d_mse1 = nullptr;
+    size_t mse1_words = 0;
     bool pnp_attr_set = false; // the > 64 KB dynamic-LDS attribute of the PnP kernels, per context (= per device)
 
     mslam::BowState* bow = nullptr;

@@ -6,6 +6,9 @@
 // usage: mslam_harness <plugin.so> <width> <height> <frame0.bgr> <frame1.bgr>     raw B,G,R frames
 //        mslam_harness <plugin.so> --tum <associations.txt>                       a TUM RGB-D sequence, read the way
 //                                                                                 the reference's RgbdFileProvider does
+//        mslam_harness <plugin.so> --pnp <scene>                                   hipRansacPnpFactory on one scene
+//        mslam_harness <plugin.so> --pnp-mse <scene>                               hipMinMseTrackerFactory on the same
+//                                                                                 scene format and output line
 //        mslam_harness <plugin.so> --bow <vocabulary.dbow3> <width> <height> <frame.bgr>...
 //                                    the BoW boundary: relocalizer + loop detector factories (one shared database),
 //                                    fed in the frontend's order: detect -> addKeyframe (rgbd_feature_frontend.cpp:176)
@@ -48,7 +51,8 @@ int main(int argc, char** argv)
         std::unique_ptr<mslam::IOrbFeatureDetector> detector = makeDetector();
         std::unique_ptr<mslam::IOrbMatcher> matcher = makeMatcher();
         std::printf("loaded %s\n", detector && matcher ? "ok" : "null");
-        if(argc == 4 && std::strcmp(argv[2], "--pnp") == 0)
+        const bool pnp_mse = argc == 4 && std::strcmp(argv[2], "--pnp-mse") == 0;
+        if(argc == 4 && (std::strcmp(argv[2], "--pnp") == 0 || pnp_mse))
         {
             // scene file: u32 n, then n x (3 f64 landmark, 2 f64 image point), then the initial sensor pose (3 f64 position,
             // 4 f64 quaternion w x y z) and fx fy cx cy
@@ -74,7 +78,8 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "cannot read %s\n", argv[3]);
                 return 5;
             }
-            auto makePnp = mslam::loadFactoryMethod<mslam::ISlam3dPnp>(argv[1], "hipRansacPnpFactory");
+            auto makePnp = mslam::loadFactoryMethod<mslam::ISlam3dPnp>(argv[1], pnp_mse ? "hipMinMseTrackerFactory"
+                                                                                          : "hipRansacPnpFactory");
             std::unique_ptr<mslam::ISlam3dPnp> pnp = makePnp();
             mslam::CameraParameters cp;
             cp.focal = mslam::Vector2(cam[0], cam[1]);

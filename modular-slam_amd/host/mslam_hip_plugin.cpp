@@ -9,6 +9,8 @@
 //   HipOrbRelocalizer : IRelocalizer                       what OrbRelocalizer is wired for
 //                                                           (orb_relocalizer.cpp:26-50, rgbd_feature_frontend.cpp:153,176)
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
+//   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
+//                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
 //
@@ -84,6 +86,20 @@ void gather_descriptors(const std::vector<OrbKeypoint>& kps, std::vector<std::ui
     out.resize(kps.size() * 32);
     for(std::size_t i = 0; i < kps.size(); ++i)
         std::memcpy(&out[i * 32], kps[i].descriptor.data(), 32);
+}
+void toRodrigues(double w, double x, double y, double z, double r[3])
+{
+    // Eigen::AngleAxisd(q) (cv_ransac_pnp.cpp:44-48): angle = 2 atan2(|v|, |w|) from the POSITIVE norm, then the axis is
+    // v / |v| for w >= 0 and -v / |v| for w < 0 (q and -q are the same rotation)
+    const double nv = std::sqrt(x * x + y * y + z * z);
+    if(nv < 1e-300)
+    {
+        r[0] = r[1] = r[2] = 0;
+        return;
+    }
+    const double angle = 2.0 * std::atan2(nv, std::fabs(w));
+    const double d = w < 0 ? -nv : nv;
+    r[0] = x / d * angle, r[1] = y / d * angle, r[2] = z / d * angle;
 }
 } // namespace
 
@@ -358,23 +374,65 @@ class HipRansacPnp : public ISlam3dPnp
     }
 
   private:
-    static void toRodrigues(double w, double x, double y, double z, double r[3])
-    {
-        // Eigen::AngleAxisd(q) (cv_ransac_pnp.cpp:44-48): angle = 2 atan2(|v|, |w|) from the POSITIVE norm, then the axis is
-        // v / |v| for w >= 0 and -v / |v| for w < 0 (q and -q are the same rotation)
-        const double nv = std::sqrt(x * x + y * y + z * z);
-        if(nv < 1e-300)
-        {
-            r[0] = r[1] = r[2] = 0;
-            return;
-        }
-        const double angle = 2.0 * std::atan2(nv, std::fabs(w));
-        const double d = w < 0 ? -nv : nv;
-        r[0] = x / d * angle, r[1] = y / d * angle, r[2] = z / d * angle;
-    }
     Ctx ctx;
     std::vector<float> obj, img;
     std::vector<std::uint8_t> mask;
+};
+
+// drop-in for MinMseTracker (ceres_reprojection_error_pnp.cpp:64-110), keeping its conventions where they differ from
+// OpenCvRansacPnp's: the initial orientation becomes angle-axis as Eigen::AngleAxisd(q) does it and the initial position is
+// the translation itself, with no world -> camera inversion (:71-75); the result's angle, axis and position are cast to
+// float and the axis is divided by the float angle before the quaternion is built (:99-109); the inlier set stays empty
+// (the reference never sizes it).  DEVIATES: a result angle of exactly 0 gives the identity quaternion (the reference
+// divides by zero and returns NaN).  Ceres's progress printout (minimizer_progress_to_stdout, :91) is not reproduced.
+class HipMinMseTracker : public ISlam3dPnp
+{
+  public:
+    std::optional<PnpResult> solvePnp(const std::vector<std::shared_ptr<Landmark<Vector3>>>& landmarks,
+                                      const std::vector<Vector2>& sensorPoints, const slam3d::SensorState& initial) override
+    {
+        if(landmarks.size() != sensorPoints.size()) // the reference asserts it (:68)
+            return std::nullopt;
+        const std::size_t n = landmarks.size();
+        obj.resize(3 * n);
+        img.resize(2 * n);
+        for(std::size_t i = 0; i < n; ++i)
+        {
+            obj[3 * i] = landmarks[i]->state.x();
+            obj[3 * i + 1] = landmarks[i]->state.y();
+            obj[3 * i + 2] = landmarks[i]->state.z();
+            img[2 * i] = sensorPoints[i].x();
+            img[2 * i + 1] = sensorPoints[i].y();
+        }
+        double rvec[3], tvec[3] = {initial.position.x(), initial.position.y(), initial.position.z()};
+        const Quaternion& q = initial.orientation;
+        toRodrigues(q.w(), q.x(), q.y(), q.z(), rvec);
+        ctx.ensure(0, 0);
+        const int rc = mslam_hip_pnp_min_mse(ctx.h, obj.data(), img.data(), static_cast<int>(n), cameraParams.focal.x(),
+                                             cameraParams.focal.y(), cameraParams.principalPoint.x(),
+                                             cameraParams.principalPoint.y(), rvec, tvec, nullptr, nullptr, nullptr);
+        if(rc == MSLAM_HIP_E_NO_MODEL) // !summary.IsSolutionUsable() (:95-96)
+            return std::nullopt;
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_pnp_min_mse", rc);
+        const float resultAngle = static_cast<float>(std::sqrt(rvec[0] * rvec[0] + rvec[1] * rvec[1] + rvec[2] * rvec[2]));
+        PnpResult result;
+        result.pose.position = Vector3(static_cast<float>(tvec[0]), static_cast<float>(tvec[1]), static_cast<float>(tvec[2]));
+        if(resultAngle != 0.0f)
+        {
+            // Vector3 resultAxis = float(r); resultAxis /= resultAngle; Quaternion{AngleAxis(resultAngle, resultAxis)}
+            const double angle = resultAngle;
+            const double axis[3] = {static_cast<float>(rvec[0]) / angle, static_cast<float>(rvec[1]) / angle,
+                                    static_cast<float>(rvec[2]) / angle};
+            const double ha = 0.5 * angle, s = std::sin(ha);
+            result.pose.orientation = Quaternion(std::cos(ha), s * axis[0], s * axis[1], s * axis[2]);
+        }
+        return result;
+    }
+
+  private:
+    Ctx ctx;
+    std::vector<double> obj, img;
 };
 
 // ---- factories + aliases (what loadFactoryMethod<T>(lib, name) imports) -------------------------------
@@ -389,6 +447,7 @@ std::unique_ptr<IOrbMatcher> createHipOrbMatcher() { return std::make_unique<Hip
 std::unique_ptr<IOrbRelocalizer> createHipOrbRelocalizer() { return std::make_unique<HipOrbRelocalizer>(); }
 std::unique_ptr<IOrbLoopDetector> createHipLoopDetector() { return std::make_unique<HipLoopDetector>(); }
 std::unique_ptr<ISlam3dPnp> createHipRansacPnp() { return std::make_unique<HipRansacPnp>(); }
+std::unique_ptr<ISlam3dPnp> createHipMinMseTracker() { return std::make_unique<HipMinMseTracker>(); }
 
 } // namespace mslam
 
@@ -398,3 +457,4 @@ MSLAM_DLL_ALIAS(mslam::createHipOrbMatcher, hipOrbMatcherFactory)
 MSLAM_DLL_ALIAS(mslam::createHipOrbRelocalizer, hipOrbRelocalizerFactory)
 MSLAM_DLL_ALIAS(mslam::createHipLoopDetector, loopDetection) // key used by test/plugin_config.json
 MSLAM_DLL_ALIAS(mslam::createHipRansacPnp, hipRansacPnpFactory)
+MSLAM_DLL_ALIAS(mslam::createHipMinMseTracker, hipMinMseTrackerFactory)
