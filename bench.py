@@ -7,20 +7,26 @@ match of every frame against its predecessor (chained across batches) — the ca
 RgbdFeatureFrontend (rgbd_feature_frontend.cpp:187,237) — and the depth lookup + back-projection of the
 keypoints (rgbd_feature_frontend.cpp:101-138), the step that consumes the D of RGB-D.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes its outputs when
+`--dump-outputs` is given, and prints the line.  `--full` adds everything else the benchmark measures and checks, after the
+timed region: the popcount-matcher rate, every stage alone on the GPU, the PCIe-inclusive rate, the other configurations'
+legs (cfg3, cfg5, cfg2_k2000, cfg4_one_rank, single-frame latency; with N > 1 the exchange and cfg4) and the CPU baseline;
+`--no-extras`, `--no-legs` and `--no-cpu-baseline` leave parts of it out.
 
 N > 1: one rank per GPU.  When started WITHOUT a torch.distributed environment, bench.py spawns the N
 ranks itself (a child `python -m torch.distributed.run ... bench.py <same arguments>`, before anything
 touches the GPU) and exits with the child's code; started by torch.distributed.run it reads RANK /
 LOCAL_RANK / WORLD_SIZE.  Every rank runs its own stream (seed 1234 + 100*rank); extract + match need no
 data-path collective ("weak" scaling); timing is barrier + synchronize on both sides and the MAX over
-ranks.  With N > 1 the loop-candidate exchange (DBoW3 vectors, ONE all-gather per batch over RCCL,
-cross-stream scoring) is exercised and timed after the headline region ("exchange"); `--bow` puts BoW
+ranks.  With N > 1 and `--full` the loop-candidate exchange (DBoW3 vectors, ONE all-gather per batch over
+RCCL, cross-stream scoring) is exercised and timed after the headline region ("exchange"); `--bow` puts BoW
 scoring and the exchange inside the step (cfg3 / cfg4).
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launching stream for
-the dominant kernel; `cpu_baseline` times the CPU oracle (oracle/, the restatement of the reference's
-CPU plugin) on a bounded sample of the same stream on the host cores; `pcie_inclusive` is the same
+the dominant kernel; with `--full`, `cpu_baseline` times the CPU oracle (oracle/, the restatement of the reference's
+CPU plugin) on a bounded sample of the same stream on the host cores, and `pcie_inclusive` is the same
 pipeline fed from pinned host memory (double-buffered H2D) with the results copied back (D2H).
 
 `--dump-outputs DIR` writes what the last timed step computed on rank 0 (keypoints, descriptors, matches and 3-D points of a
@@ -248,7 +254,11 @@ def parse():
                          "with N>1, the RCCL all-gather of BoW vectors + cross-stream scoring")
     ap.add_argument("--voc-levels", type=int, default=6, help="vocabulary depth L (k=10): 6 -> 1e6 words")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the real multi-GPU run) or gloo (rehearsal)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run everything the headline does not need: the popcount matcher, "
+                         "serialized stages, PCIe-inclusive, the other configurations' legs, the exchange (N > 1) and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--pnp", action="store_true",
                     help="also estimate the frame-to-frame pose of every frame in the step (batched RANSAC PnP on the "
                          "matches + back-projected points: mslam_hip_pnp_batch_dev)")
@@ -258,15 +268,15 @@ def parse():
                     help="with several ranks: seconds the legs after the timed region may take before rank 0 prints "
                          "the line without them")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the cfg3 / cfg5 / single-frame-latency legs that follow the timed region of the default run")
+                    help="skip the cfg3 / cfg5 / single-frame-latency legs that follow the timed region of a --full run")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs after the timed region (popcount matcher, serialized stages, PCIe-inclusive, "
-                         "exchange): what the profiling passes use")
+                    help="skip the legs after the timed region of a --full run (popcount matcher, serialized stages, "
+                         "PCIe-inclusive, exchange)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU work budget of the cpu_baseline leg")
     ap.add_argument("--rccl-world1", action="store_true",
-                    help="single-GPU runs: create a one-rank process group on the nccl (= RCCL) backend and issue the cfg4 leg's "
-                         "all-gather as a real RCCL collective instead of the world-1 device copy (what one GPU can exercise of "
-                         "the RCCL path; not part of the default run: a box without a usable RCCL would hang it)")
+                    help="single-GPU --full runs: create a one-rank process group on the nccl (= RCCL) backend and issue the "
+                         "cfg4 leg's all-gather as a real RCCL collective instead of the world-1 device copy (what one GPU can "
+                         "exercise of the RCCL path; not part of the default run: a box without a usable RCCL would hang it)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy")
     a = ap.parse_args()
@@ -522,8 +532,9 @@ def dry_run(a, rank, world):
         dist.barrier()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(k, op=dist.ReduceOp.SUM)
-        # the loop-candidate exchange of the real run, on host tensors of the real shape: ONE all_gather_into_tensor of
-        # the rank's packed BoW set per batch (modular_slam_amd/multi_stream.py), here 3 batches of 8 frames
+    if world > 1 and a.full:
+        # the loop-candidate exchange of the real --full run, on host tensors of the real shape: ONE all_gather_into_tensor
+        # of the rank's packed BoW set per batch (modular_slam_amd/multi_stream.py), here 3 batches of 8 frames
         import __graft_entry__ as graft
         graft.load_package()
         from modular_slam_amd.multi_stream import CrossStreamLoopCandidates, set_dwords, pack_vectors, unpack_set
@@ -644,7 +655,8 @@ def main():
                       detector=pkg.DETECTOR_CV_ORB if cv else pkg.DETECTOR_DISTRIBUTED, n_features=a.n_features)
     n_batches = n_unique // B
     cross = None
-    need_voc = a.bow or (world > 1 and not a.no_extras)
+    extras_on = a.full and not a.no_extras  # the legs after the timed region run only in a --full run
+    need_voc = a.bow or (world > 1 and extras_on)
     if need_voc:
         ctx.bow_load(synth.make_vocabulary(10, a.voc_levels, seed=77))
         if a.bow:
@@ -737,7 +749,7 @@ def main():
             sb["select"] = sb["quadtree"]
         # the kernel that binds: the stage with the largest duration ALONE on the GPU (the serialized pass; an in-place
         # interval on one of the two chunk streams is inflated unevenly by the sibling chunk's kernels), falling back to
-        # the in-place sums when the serialized pass did not run (--no-extras)
+        # the in-place sums when the serialized pass did not run (a plain run, or --no-extras)
         ser = extras.get("stages_ms_serialized", {})
         ser_ok = {k: v for k, v in ser.items() if k in sb and k in acc}
         dom = max(ser_ok, key=ser_ok.get) if ser_ok else max((k for k in acc if k in sb), key=acc.get)
@@ -897,7 +909,7 @@ def main():
         if "pcie_inclusive" in out:
             # the same step fed from page-locked host memory and with its results copied back: never `value`
             out["value_pcie_inclusive"] = out["pcie_inclusive"]["keypoints_per_s"]
-        if with_cpu and not a.no_cpu_baseline and world == 1:
+        if with_cpu and a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(frames, dict(n_levels=a.levels, min_size=a.min_area), a.cpu_seconds, cv,
                                                a.n_features)
         return out
@@ -926,8 +938,8 @@ def main():
 
     # the fallback line is a snapshot of the headline taken NOW, on the main thread, before any extra leg runs: the
     # watchdog thread only copies it, it never calls into the context or reads `extras` while the main thread works on them
-    # (also armed for --rccl-world1: its collective is a real RCCL call, and a hung one must end the run non-zero)
-    armed = world > 1 or a.rccl_world1
+    # (also armed for --full --rccl-world1: its collective is a real RCCL call, and a hung one must end the run non-zero)
+    armed = world > 1 or (a.rccl_world1 and extras_on)
     headline = make_line({}, with_cpu=False) if (armed and rank == 0) else None
     if armed:
         def give_up():
@@ -943,8 +955,8 @@ def main():
         watchdog.daemon = True
         watchdog.start()
     try:
-        if not a.no_extras:
-            # the same run with the xor/popcount matcher (the form north_star names): both values are always quoted
+        if extras_on:
+            # the same run with the xor/popcount matcher (the form north_star names): a --full line quotes both values
             ctx.set_matcher(pkg.MATCHER_POPCOUNT)
             for i in range(2):
                 step(i)

@@ -18,7 +18,7 @@ def _env(**kw):
 
 
 def test_gpus_2_spawns_two_ranks():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"], env=_env(),
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], env=_env(),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -34,6 +34,18 @@ def test_gpus_2_spawns_two_ranks():
     # checked against the oracle on the vectors as transmitted): rehearsed on host tensors over the same process group
     assert j["cfg4"]["n_gpus"] == 2 and j["cfg4"]["oracle_check"] is True
     assert j["cfg4"]["exchange"]["world_size"] == 2 and j["cfg4"]["exchange"]["collectives_per_step"] == 1.0
+
+
+def test_gpus_2_plain_run_leaves_the_exchange_to_full():
+    """without --full the ranks only do what the headline needs: rendezvous, timing reductions, one line"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"], env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 2 and j["dist"]["world_size"] == 2 and j["t_max"] == 2.0 and j["units"] == 200.0
+    assert "exchange" not in j and "cfg4" not in j
 
 
 def test_single_rank_needs_no_launcher():

@@ -22,7 +22,7 @@ python tools/summarize_counters.py 3 "$OUT/pmc_per_step.json" "$OUT/fetch/f_coun
 cat "$OUT/pmc_per_step.txt"
 # the bench line proper reads the summary from profiles/: put it there for this run
 cp "$OUT/pmc_per_step.json" profiles/r06_pmc_per_step.json
-timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cp "$OUT/fetch/f_counter_collection.csv" "$OUT/pmc_fetch_counter_collection.csv"
 cp "$OUT/write/w_counter_collection.csv" "$OUT/pmc_write_counter_collection.csv"
 find "$OUT" -name "*kernel_trace.csv" -delete   # large; the stats CSV is what is kept

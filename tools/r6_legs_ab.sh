@@ -1,11 +1,13 @@
 #!/bin/bash
-# round 6: the default bench line (all legs) per environment setting; prints headline, cfg3, cfg5, cfg4_one_rank, latency
+# round 6: the --full bench line (all legs) per environment setting; prints headline, cfg3, cfg5, cfg4_one_rank, latency.
+# The bench lines are kept under $BENCH_OUT/<tag>/ (default bench_out/).
 TAG=$1; shift
-mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG
+mkdir -p "$OUT"
 i=0
 for cfg in "$@"; do
-  env $cfg timeout -k 10 400 python bench.py --no-cpu-baseline > gpurun_out/$TAG/legs_$i.json 2> gpurun_out/$TAG/legs_$i.err || { echo "FAILED: $cfg"; tail -3 gpurun_out/$TAG/legs_$i.err; exit 1; }
-  python - "gpurun_out/$TAG/legs_$i.json" "$cfg" <<'PY'
+  env $cfg timeout -k 10 400 python bench.py --full --no-cpu-baseline > "$OUT/legs_$i.json" 2> "$OUT/legs_$i.err" || { echo "FAILED: $cfg"; tail -3 "$OUT/legs_$i.err"; exit 1; }
+  python - "$OUT/legs_$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 def leg(k):
