@@ -429,6 +429,74 @@ int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* ctx, const double* d_object, 
                                     int n_problems, int capacity, double fx, double fy, double cx, double cy,
                                     double* d_pose, double* d_info);
 
+/* ---- verified relocalisation: keyframe store + one query against N keyframes (match -> correspondences -> PnP) --------
+ * What RgbdFeatureFrontend::relocalize is written to do with the relocalizer's candidates (rgbd_feature_frontend.cpp:495-534,
+ * its body is commented out there and the function returns nullptr): per candidate keyframe matchLandmarks(keypoints,
+ * keyframe) (:509 -> :237), pnpAlgorithm->solvePnp on the matched landmarks (:519), the candidate with the most inliers
+ * (boost::range::max_element, :527-529), a score threshold of 60 (:531-533).  track() (:279-400) runs the same
+ * match -> correspondences -> PnP step against the reference keyframe's landmarks.
+ *
+ * Keyframe store: per context, on the device, grown by doubling (mslam_hip_kf_reserve pre-allocates).  An entry is
+ * n <= max_keypoints landmarks — a 32-byte descriptor and a world point (3 f64) each — under a caller-chosen integer id
+ * (the adapters use the BoW database's entry id, so one id names both).  Adding an id that exists replaces its entry.
+ * An id that is not in the store is MSLAM_HIP_E_INVALID everywhere; n > max_keypoints is MSLAM_HIP_E_CAPACITY. */
+int mslam_hip_kf_add(mslam_hip_ctx* ctx, int id, const uint8_t* desc /* n x 32 */, const double* world_xyz /* n x 3 */, int n);
+/* Frame `frame` of the last detect batch, which mslam_hip_backproject_batch_dev has run on, lifted as addNewLandmarks does
+ * (rgbd_feature_frontend.cpp:402-431): a keypoint becomes a landmark when its depth is valid and its camera-frame z is
+ * <= z_max (the reference: zThreshold = 3.f); its world point is R p + t (toGlobalCoordinates, projection.cpp:51-54;
+ * R = 9 doubles row-major, t = 3 doubles: the keyframe's sensor pose), evaluated in f64 as ((R0 x + R1 y) + R2 z) + t per
+ * row, every operation rounded separately (DEVIATES in the last bits from Eigen's quaternion * vector product, which
+ * the reference's pose type uses).  Kept keypoints stay in keypoint order.  Asynchronous on the context's stream. */
+int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* ctx, int id, int frame, const double* R, const double* t, double z_max);
+int mslam_hip_kf_remove(mslam_hip_ctx* ctx, int id);
+int mslam_hip_kf_clear(mslam_hip_ctx* ctx);
+int mslam_hip_kf_size(mslam_hip_ctx* ctx, int* n_entries);
+int mslam_hip_kf_reserve(mslam_hip_ctx* ctx, int max_entries);
+/* test / debug read-back of an entry (synchronises): *n = its landmark count; desc / world_xyz (either may be NULL) receive
+ * the landmarks when `capacity` holds them, otherwise nothing is copied and the call returns MSLAM_HIP_E_CAPACITY. */
+int mslam_hip_kf_read(mslam_hip_ctx* ctx, int id, uint8_t* desc, double* world_xyz, int capacity, int* n);
+
+/* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
+ * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
+ * valid; a mask is track()'s depth filter, :317-334).  Per candidate c = cand_ids[k]:
+ *   matches          match(from = query keypoints, to = keyframe c's landmarks) exactly as mslam_hip_match computes it
+ *                    (knn-2 with query = to and train = from, ratio test, ordered by `to`), with either matcher kind;
+ *   correspondences  match i -> object = (float)world_xyz[c][to_i], image = xy[from_i], in match order; matches whose
+ *                    `from` keypoint is masked out are dropped;
+ *   pose             one RANSAC PnP as mslam_hip_pnp_ransac runs it (same kernel code, the context's confidence), sampling
+ *                    seed = seed + k, the guess (rvec, tvec; use_extrinsic_guess != 0) shared by all candidates; fewer
+ *                    than 4 correspondences: status 0, as in mslam_hip_pnp_batch_dev;
+ * best = the position in cand_ids of the candidate with the most inliers among those with a model, the first one on ties
+ * (max_element), or -1 when there is none or the winner has fewer than min_inliers inliers.
+ * out[k] is always written.  pair_from / pair_to ([n_cand][pair_stride], the first n_matches entries of a row) and inliers
+ * ([n_cand][pair_stride], the first n_correspondences entries: the consensus mask in correspondence order) may be NULL;
+ * a row that does not fit pair_stride makes the call return MSLAM_HIP_E_CAPACITY.
+ * Returns MSLAM_HIP_OK when best >= 0, MSLAM_HIP_E_NO_MODEL when best = -1 (n_cand = 0 and n < 2 included: the matcher
+ * defines fewer than 2 `from` rows as zero matches), MSLAM_HIP_E_INVALID for an id that is not in the store.
+ * Against the reference's (commented-out) body:
+ *   matching, correspondences   SAME: matchLandmarks' call and the landmark / keypoint pairing of :513-517;
+ *   PnP                         as mslam_hip_pnp_ransac (see its SAME / DEVIATES list);
+ *   ranking                     SAME: most inliers, first maximum; a candidate without a model scores 0 there and is
+ *                               never the winner here;
+ *   threshold                   DEVIATES: `result->score >= scoreThreshold ? result->keyframe : result->keyframe` (:533)
+ *                               returns the keyframe either way; min_inliers is this library's reading of
+ *                               scoreThreshold = 60 (pass 0 for the expression as written);
+ *   guess, depth filter         DEVIATES: the commented code passes no guess and filters nothing; both are optional here
+ *                               so that the same call serves track()'s step (guess = currentPose, mask = valid depth). */
+typedef struct
+{
+    int32_t n_matches;         /* ratio-test survivors                                                     */
+    int32_t n_correspondences; /* of those, with an unmasked query keypoint                                */
+    int32_t n_inliers;         /* consensus of the best hypothesis (0 without a model)                     */
+    int32_t status;            /* 1 = a model was found, 0 = none                                          */
+    double rvec[3], tvec[3];   /* world -> camera, OpenCV's convention (zeros without a model)             */
+} mslam_hip_reloc_candidate;
+int mslam_hip_relocalize(mslam_hip_ctx* ctx, const uint8_t* desc, const float* xy, const uint8_t* valid, int n,
+                         const int32_t* cand_ids, int n_cand, double fx, double fy, double cx, double cy, double ratio,
+                         int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess,
+                         const double* rvec, const double* tvec, int min_inliers, mslam_hip_reloc_candidate* out,
+                         int* best, int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "mslam_hip_bow_db_reserve", "mslam_hip_bow_db_size", "mslam_hip_qlz_decompress",
     "mslam_hip_pnp_ransac", "mslam_hip_pnp_batch_dev", "mslam_hip_get_pnp_view", "mslam_hip_pnp_set_confidence", "mslam_hip_pack_batch_dev", "mslam_hip_packed_capacity",
     "mslam_hip_set_cv_keypoint_order", "mslam_hip_pnp_min_mse", "mslam_hip_pnp_min_mse_batch_dev",
+    "mslam_hip_kf_add", "mslam_hip_kf_add_from_batch_dev", "mslam_hip_kf_remove", "mslam_hip_kf_clear", "mslam_hip_kf_size",
+    "mslam_hip_kf_reserve", "mslam_hip_kf_read", "mslam_hip_relocalize",
 ]
 
 
@@ -105,6 +107,11 @@ def unpack_batch(buf):
 class PnpView(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("pose", C.c_void_p), ("n_points", C.c_void_p), ("object_points", C.c_void_p),
                 ("image_points", C.c_void_p), ("inliers", C.c_void_p)]
+
+
+class RelocCandidate(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("n_correspondences", C.c_int32), ("n_inliers", C.c_int32), ("status", C.c_int32),
+                ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
 
 
 class BowView(C.Structure):
@@ -353,6 +360,85 @@ class Context:
                                                          C.c_double(focal[1]), C.c_double(principal[0]),
                                                          C.c_double(principal[1]), C.c_void_p(d_pose), C.c_void_p(d_info)))
 
+    # ---- keyframe store + verified relocalisation (rgbd_feature_frontend.cpp:402-431, :495-534) ----
+    def kf_add(self, id, desc, world_xyz):
+        """store keyframe `id`: n landmarks = descriptors (n x 32) + world points (n x 3 f64); an existing id is replaced"""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        w = np.ascontiguousarray(world_xyz, np.float64).reshape(-1, 3)
+        if len(d) != len(w):
+            raise MslamHipError(E_INVALID, "kf_add: %d descriptors, %d world points" % (len(d), len(w)))
+        self._chk(self.L.mslam_hip_kf_add(self._h, int(id), _p(d), _p(w), len(d)))
+
+    def kf_add_from_batch_dev(self, id, frame, R=np.eye(3), t=(0, 0, 0), z_max=3.0):
+        """store frame `frame` of the last detect + back-project batch as keyframe `id` (valid depth, z <= z_max,
+        world = R p + t); asynchronous on the context's stream"""
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        self._chk(self.L.mslam_hip_kf_add_from_batch_dev(self._h, int(id), int(frame), _p(R), _p(t), C.c_double(z_max)))
+
+    def kf_remove(self, id):
+        self._chk(self.L.mslam_hip_kf_remove(self._h, int(id)))
+
+    def kf_clear(self):
+        self._chk(self.L.mslam_hip_kf_clear(self._h))
+
+    def kf_reserve(self, max_entries):
+        self._chk(self.L.mslam_hip_kf_reserve(self._h, int(max_entries)))
+
+    def kf_size(self):
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_size(self._h, C.byref(n)))
+        return n.value
+
+    def kf_read(self, id):
+        """-> (desc [n, 32] u8, world_xyz [n, 3] f64) of a stored keyframe (debug read-back; synchronises)"""
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_read(self._h, int(id), None, None, 0, C.byref(n)))
+        d = np.empty((max(n.value, 1), 32), np.uint8)
+        w = np.empty((max(n.value, 1), 3), np.float64)
+        self._chk(self.L.mslam_hip_kf_read(self._h, int(id), _p(d), _p(w), n.value, C.byref(n)))
+        return d[:n.value].copy(), w[:n.value].copy()
+
+    def relocalize(self, desc, xy, cand_ids, focal=(525.0, 525.0), principal=(319.5, 239.5), valid=None, ratio=0.7,
+                   iterations=100, reprojection_error=5.0, seed=0, rvec=None, tvec=None, min_inliers=60, with_pairs=False):
+        """one query frame (desc [n, 32], xy [n, 2], optional valid [n]) against the stored keyframes cand_ids (<= 64):
+        per candidate match -> correspondences -> RANSAC PnP (seed + position), then the ranking.
+        -> dict(best = position in cand_ids or -1, candidates = [dict(n_matches, n_correspondences, n_inliers, status,
+        rvec, tvec)], and with with_pairs also pairs = [(from, to)] and inliers = [mask over the correspondences]).
+        best = -1 is a result here (MSLAM_HIP_E_NO_MODEL), not an exception."""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        p2 = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        if len(d) != len(p2):
+            raise MslamHipError(E_INVALID, "relocalize: %d descriptors, %d points" % (len(d), len(p2)))
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(-1)
+        if v is not None and len(v) != len(d):
+            raise MslamHipError(E_INVALID, "relocalize: valid mask of the wrong length")
+        ids = np.ascontiguousarray(cand_ids, np.int32).reshape(-1)
+        P = len(ids)
+        guess = rvec is not None and tvec is not None
+        r = np.array(rvec if guess else (0, 0, 0), np.float64)
+        t = np.array(tvec if guess else (0, 0, 0), np.float64)
+        out = (RelocCandidate * max(P, 1))()
+        best = C.c_int(-1)
+        stride = self.params.max_keypoints if with_pairs else 0
+        pf = np.zeros((max(P, 1), stride), np.int32) if with_pairs else None
+        pt = np.zeros((max(P, 1), stride), np.int32) if with_pairs else None
+        inl = np.zeros((max(P, 1), stride), np.uint8) if with_pairs else None
+        rc = self.L.mslam_hip_relocalize(self._h, _p(d), _p(p2), _p(v), len(d), _p(ids), P, C.c_double(focal[0]),
+                                         C.c_double(focal[1]), C.c_double(principal[0]), C.c_double(principal[1]),
+                                         C.c_double(ratio), int(iterations), C.c_double(reprojection_error), C.c_uint64(seed),
+                                         int(guess), _p(r), _p(t), int(min_inliers), out, C.byref(best), _p(pf), _p(pt),
+                                         _p(inl), int(stride))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        cands = [dict(n_matches=o.n_matches, n_correspondences=o.n_correspondences, n_inliers=o.n_inliers, status=o.status,
+                      rvec=np.array(o.rvec[:]), tvec=np.array(o.tvec[:])) for o in out[:P]]
+        res = dict(best=best.value, candidates=cands)
+        if with_pairs:
+            res["pairs"] = [(pf[k, :c["n_matches"]].copy(), pt[k, :c["n_matches"]].copy()) for k, c in enumerate(cands)]
+            res["inliers"] = [inl[k, :c["n_correspondences"]].astype(bool) for k, c in enumerate(cands)]
+        return res
+
     # ---- bag of words --------------------------------------------------------------------------
     def bow_load(self, blob):
         b = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob)
@@ -549,6 +635,7 @@ class HipOrbRelocalizer:
         self.ctx.bow_load(vocabulary_blob)
         self.max_results = max_results
         self._entry_to_keyframe = {}
+        self._with_landmarks = set()   # entries addKeyframeLandmarks has stored landmarks for
 
     def addKeyframe(self, keyframe, keypoints):
         assert len(keypoints) > 0  # orb_relocalizer.cpp:42
@@ -560,6 +647,43 @@ class HipOrbRelocalizer:
             if k is keyframe:
                 del self._entry_to_keyframe[e]
                 self.ctx.bow_db_remove(e)
+                if e in self._with_landmarks:
+                    self._with_landmarks.discard(e)
+                    self.ctx.kf_remove(e)
+
+    def addKeyframeLandmarks(self, keyframe, keypoints, worldPoints):
+        """extension: the landmarks of a keyframe addKeyframe has fed (descriptors of `keypoints` + their world points),
+        stored on the device under the keyframe's BoW entry id — what relocalizePose verifies candidates against"""
+        d = np.array([k.descriptor for k in keypoints], np.uint8).reshape(-1, 32)
+        for e, k in self._entry_to_keyframe.items():
+            if k is keyframe:
+                self.ctx.kf_add(e, d, np.asarray(worldPoints, np.float64).reshape(-1, 3))
+                self._with_landmarks.add(e)
+                return
+        raise KeyError("addKeyframeLandmarks: the keyframe has not been added")
+
+    def _verify(self, keypoints, entries, camera, valid, rvec, tvec, min_inliers, seed):
+        d = np.array([k.descriptor for k in keypoints], np.uint8).reshape(-1, 32)
+        xy = np.array([k.coordinates for k in keypoints], np.float32).reshape(-1, 2)
+        focal, principal = camera
+        r = self.ctx.relocalize(d, xy, entries, focal, principal, valid=valid, rvec=rvec, tvec=tvec, min_inliers=min_inliers,
+                                seed=seed)
+        table = [dict(c, keyframe=self._entry_to_keyframe[e]) for e, c in zip(entries, r["candidates"])]
+        if r["best"] < 0:
+            return None, None, 0, table
+        b = table[r["best"]]
+        return b["keyframe"], (b["rvec"], b["tvec"]), b["n_inliers"], table
+
+    def relocalizePose(self, keypoints, camera=((525.0, 525.0), (319.5, 239.5)), valid=None, rvec=None, tvec=None,
+                       min_inliers=60, seed=0):
+        """extension (what RgbdFeatureFrontend::relocalize's commented body does, rgbd_feature_frontend.cpp:495-534): the BoW
+        candidates of relocalize(), each verified by match + RANSAC PnP against its stored landmarks
+        -> (keyframe, (rvec, tvec), inliers, per-candidate table), keyframe None when no candidate reaches min_inliers"""
+        d = np.array([k.descriptor for k in keypoints], np.uint8).reshape(-1, 32)
+        ids, _ = self.ctx.bow_db_query(d, self.max_results + len(self._entry_to_keyframe))
+        entries = [int(i) for i in ids if i in self._entry_to_keyframe][:self.max_results]   # relocalize()'s candidates
+        entries = [e for e in entries if e in self._with_landmarks]                           # (only stored ones can be verified)
+        return self._verify(keypoints, entries, camera, valid, rvec, tvec, min_inliers, seed)
 
     def relocalize(self, keypoints):
         d = np.array([k.descriptor for k in keypoints], np.uint8).reshape(-1, 32)
@@ -578,20 +702,32 @@ class HipLoopDetector:
         self.min_score = min_score
         self.exclude_recent = exclude_recent
         self._last = None
+        self._last_entry, self._last_keypoints = None, None
 
     def feed(self, keyframe, keypoints):
         d = np.array([k.descriptor for k in keypoints], np.uint8).reshape(-1, 32)
         n_db = len(self.reloc._entry_to_keyframe)
         ids, sc = self.reloc.ctx.bow_db_query(d, n_db) if n_db else (np.empty(0, np.int32), np.empty(0))
         self._last = None
+        self._last_entry, self._last_keypoints = None, keypoints
         for i, s in zip(ids, sc):
             if s >= self.min_score and i < n_db - self.exclude_recent and i in self.reloc._entry_to_keyframe:
                 self._last = self.reloc._entry_to_keyframe[i]
+                self._last_entry = int(i)
                 break
         self.reloc.addKeyframe(keyframe, keypoints)
 
     def detectLoop(self):
         return self._last
+
+    def detectLoopVerified(self, camera=((525.0, 525.0), (319.5, 239.5)), valid=None, rvec=None, tvec=None, min_inliers=60,
+                           seed=0):
+        """extension: detectLoop()'s candidate for the last fed keyframe, verified by match + RANSAC PnP against its stored
+        landmarks -> (keyframe, (rvec, tvec), inliers, per-candidate table); keyframe None when there is no candidate, it has
+        no stored landmarks, or it has fewer than min_inliers inliers"""
+        if self._last_entry is None or self._last_entry not in self.reloc._with_landmarks:
+            return None, None, 0, []
+        return self.reloc._verify(self._last_keypoints, [self._last_entry], camera, valid, rvec, tvec, min_inliers, seed)
 
 
 # ---- harness helper (bench / tests): copy a context-owned device array to the host ------------------

@@ -435,6 +435,8 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
     }
     if(c->bow)
         bow_destroy(c->bow);
+    if(c->reloc)
+        reloc_destroy(c->reloc);
     if(c->own_stream && c->stream)
         (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1392,6 +1394,8 @@ static int upload_ratio_table(mslam_hip_ctx* c, double ratio)
     c->ratio_cached = ratio;
     return MSLAM_HIP_OK;
 }
+// the same table for mslam_hip_relocalize (k_reloc.hip)
+__attribute__((visibility("hidden"))) int mslam_ratio_table(mslam_hip_ctx* c, double ratio) { return upload_ratio_table(c, ratio); }
 
 int mslam_hip_match_batch_dev(mslam_hip_ctx* c, double ratio, int chain_previous)
 {

@@ -10,6 +10,8 @@ namespace mslam
 {
 struct BowState; // k_bow.hip
 void bow_destroy(BowState*);
+struct RelocState; // k_reloc.hip: keyframe store + scratch of mslam_hip_relocalize
+void reloc_destroy(RelocState*);
 void set_blur_taps(const int* taps);
 void build_blur_waves(const Geometry& g, int first_level, std::vector<BlurWave>& out);
 
@@ -155,6 +157,7 @@ struct mslam_hip_ctx
     bool pnp_attr_set = false; // the > 64 KB dynamic-LDS attribute of the PnP kernels, per context (= per device)
 
     mslam::BowState* bow = nullptr;
+    mslam::RelocState* reloc = nullptr;
 
     bool profiling = false;      // mode 1: every stage timed, everything serialised on the context's stream
     bool inplace_timing = false; // mode 2: every stage launch is timed in place on the stream it runs on
@@ -200,4 +203,30 @@ struct StageScope
 
 // bow entry points used by api.hip
 int bow_batch(mslam_hip_ctx* c, int add_to_db);
+
+// k_pnp.hip for k_reloc.hip: k_pnp_ransac_batch on caller-owned device arrays — problem p reads obj / img / mask at
+// p * cap, hyp / counts at p * iterations, writes out[p * 16 ..] and samples with seed + p; the guess (when use_guess) is
+// shared by all problems.  The launch is enqueued on c->stream; returns a MSLAM_HIP_* status.
+struct PnpBatchLaunch
+{
+    const float* obj;
+    const float* img;
+    const int32_t* n; // [n_problems]
+    int n_problems, cap;
+    double fx, fy, cx, cy;
+    int use_guess;
+    double rvec[3], tvec[3];
+    int iterations;
+    double reprojection_error;
+    unsigned long long seed;
+    double* hyp;
+    int32_t* counts;
+    uint8_t* mask;
+    double* out;
+};
+int pnp_launch_batch(mslam_hip_ctx* c, const PnpBatchLaunch& l);
+void pnp_rotation_to_rvec(const double R[9], double rvec[3]);
 } // namespace mslam
+
+// api.hip: uploads the ratio-test table of `ratio` unless it is the cached one (not part of the C ABI)
+extern "C" int mslam_ratio_table(mslam_hip_ctx* c, double ratio);

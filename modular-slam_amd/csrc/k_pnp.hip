@@ -1017,6 +1017,45 @@ extern "C" int mslam_hip_pnp_batch_dev(mslam_hip_ctx* c, double fx, double fy, d
     return MSLAM_HIP_OK;
 }
 
+// the batched kernel on another caller's correspondences (mslam_hip_relocalize, k_reloc.hip)
+namespace mslam
+{
+int pnp_launch_batch(mslam_hip_ctx* c, const PnpBatchLaunch& l)
+{
+    PnpBatchArgs b{};
+    PnpArgs& a = b.proto;
+    a.obj = l.obj, a.img = l.img, a.n = 0;
+    a.fx = l.fx, a.fy = l.fy, a.cx = l.cx, a.cy = l.cy;
+    a.use_guess = l.use_guess ? 1 : 0;
+    rodrigues_to_R(l.rvec, a.R0);
+    a.t0[0] = l.tvec[0], a.t0[1] = l.tvec[1], a.t0[2] = l.tvec[2];
+    a.iterations = l.iterations;
+    a.thr2 = l.reprojection_error * l.reprojection_error;
+    a.confidence = c->pnp_confidence;
+    a.seed = l.seed;
+    a.hyp = l.hyp, a.counts = l.counts, a.mask = l.mask, a.out = l.out;
+    b.n = l.n;
+    b.cap = l.cap;
+    const size_t lds = (size_t)kPnpRed * 8 + (size_t)kPnpLdsHyp * (96 + 4) + (size_t)kPnpLdsPts * 21;
+    if(pnp_lds_attributes(c, lds) != hipSuccess)
+    {
+        c->err = "relocalize: hipFuncSetAttribute";
+        return MSLAM_HIP_E_RUNTIME;
+    }
+    {
+        StageScope t(c, "pnp_ransac");
+        hipLaunchKernelGGL(k_pnp_ransac_batch, dim3(l.n_problems), dim3(kPnpThreads), lds, c->stream, b);
+    }
+    if(hipGetLastError() != hipSuccess)
+    {
+        c->err = "relocalize: PnP launch failed";
+        return MSLAM_HIP_E_RUNTIME;
+    }
+    return MSLAM_HIP_OK;
+}
+void pnp_rotation_to_rvec(const double R[9], double rvec[3]) { R_to_rodrigues(R, rvec); }
+} // namespace mslam
+
 extern "C" int mslam_hip_get_pnp_view(mslam_hip_ctx* c, mslam_hip_pnp_view* v)
 {
     if(!c || !v)

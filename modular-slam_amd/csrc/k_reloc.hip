@@ -1,0 +1,719 @@
+// k_reloc.hip — verified relocalisation: a device-resident keyframe store and one query frame against N stored keyframes.
+//
+// What RgbdFeatureFrontend::relocalize is written to do with the relocalizer's candidates (reference
+// rgbd_feature_frontend.cpp:495-534; the body is commented out there): per candidate matchLandmarks (:509 -> :237), solvePnp
+// on the matched landmarks (:519), the candidate with the most inliers (:527-529).  Landmarks enter the store the way
+// addNewLandmarks creates them (:402-431): valid depth, z <= zThreshold, toGlobalCoordinates (projection.cpp:51-54).
+//
+// The matcher and the PnP solver are the existing kernels (k_match.hip through launch_match_knn2 / launch_ratio_compact with
+// from_stride = 0: the query descriptors are uploaded once and are every pair's train side; k_pnp.hip through
+// pnp_launch_batch).  New here: the store, the gather of the candidates' descriptor blocks into the contiguous layout the
+// matcher addresses, the match -> correspondence gather, and the ranking.  One upload, one synchronisation per call.
+#include "context.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace mslam
+{
+
+constexpr int kRelocMaxCand = 64; // the BoW query's own limit (mslam_hip_bow_db_query callers ask for at most 64)
+
+// what k_reloc_rank leaves per candidate in the mapped result block
+struct RelocRes
+{
+    int32_t n_matches, n_corr, n_inliers, status;
+    double R[9], t[3];
+};
+
+struct RelocState
+{
+    // ---- keyframe store: slot s holds up to K landmarks at desc + s * K * 32, world + s * K * 3, count n[s]
+    int slots = 0;
+    uint8_t* d_desc = nullptr;
+    double* d_world = nullptr;
+    int32_t* d_n = nullptr;
+    std::unordered_map<int, int> slot_of; // id -> slot
+    std::vector<int> free_slots;
+    std::vector<int> n_upper;             // per slot: an upper bound of n the host knows (exact for host adds, K for device lifts)
+    // ---- scratch of mslam_hip_relocalize, grown on demand
+    uint8_t* h_up = nullptr;  // page-locked staging of the upload: [desc | xy | valid | slots]
+    uint8_t* d_up = nullptr;
+    size_t up_bytes = 0;
+    uint8_t* d_arena = nullptr; // every per-candidate array of one call
+    size_t arena_bytes = 0;
+    uint8_t *h_res = nullptr, *d_h_res = nullptr; // page-locked, device-mapped: [best | RelocRes[64] | pair_from | pair_to | inliers]
+    size_t res_bytes = 0;
+};
+
+void reloc_destroy(RelocState* r)
+{
+    if(!r)
+        return;
+    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_up, r->d_arena};
+    for(void* p : dev)
+        if(p)
+            (void)hipFree(p);
+    if(r->h_up)
+        (void)hipHostFree(r->h_up);
+    if(r->h_res)
+        (void)hipHostFree(r->h_res);
+    delete r;
+}
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------
+
+struct KfPose
+{
+    double R[9], t[3], z_max;
+};
+
+// One workgroup lifts one frame of the last batch into a store slot: keypoints with a valid depth and z <= z_max, in
+// keypoint order (ballot / popcount compaction, as k_pnp_gather), world = R p + t in f64.
+__global__ __launch_bounds__(256) void k_kf_lift(const uint8_t* __restrict__ desc, const double* __restrict__ xyz,
+                                                 const uint8_t* __restrict__ valid, const int32_t* __restrict__ count, int cap,
+                                                 KfPose pose, uint8_t* __restrict__ out_desc, double* __restrict__ out_world,
+                                                 int32_t* __restrict__ out_n)
+{
+    __shared__ uint32_t wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(*count, 0), cap);
+    uint32_t running = 0;
+    for(int base = 0; base < n; base += 256)
+    {
+        const int i = base + tid;
+        bool ok = false;
+        double px = 0, py = 0, pz = 0;
+        if(i < n && valid[i] != 0)
+        {
+            px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
+            ok = pz <= pose.z_max;
+        }
+        const unsigned long long b = __ballot(ok);
+        if(lane == 0)
+            wsum[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for(int k = 0; k < 4; ++k)
+        {
+            pre += k < wave ? wsum[k] : 0;
+            tot += wsum[k];
+        }
+        if(ok)
+        {
+            const size_t o = running + pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); // < n <= cap
+            const uint4* src = reinterpret_cast<const uint4*>(desc + (size_t)i * 32);
+            uint4* dst = reinterpret_cast<uint4*>(out_desc + o * 32);
+            dst[0] = src[0];
+            dst[1] = src[1];
+            out_world[o * 3] = ((pose.R[0] * px + pose.R[1] * py) + pose.R[2] * pz) + pose.t[0];
+            out_world[o * 3 + 1] = ((pose.R[3] * px + pose.R[4] * py) + pose.R[5] * pz) + pose.t[1];
+            out_world[o * 3 + 2] = ((pose.R[6] * px + pose.R[7] * py) + pose.R[8] * pz) + pose.t[2];
+        }
+        running += tot;
+        __syncthreads();
+    }
+    if(tid == 0)
+        *out_n = (int32_t)running;
+}
+
+// The matcher addresses pair p's query side as base + p * stride: candidate p's descriptor block (store slot slots[p]) is
+// copied into row p of a contiguous scratch; blockIdx.y = p, one uint4 (half a descriptor) per thread.
+__global__ __launch_bounds__(256) void k_reloc_gather_desc(const uint8_t* __restrict__ store_desc, const int32_t* __restrict__ store_n,
+                                                           const int32_t* __restrict__ slots, int K, int S,
+                                                           uint8_t* __restrict__ g_desc, int32_t* __restrict__ g_cnt)
+{
+    const int p = blockIdx.y;
+    const int slot = slots[p];
+    const int n = min(min(max(store_n[slot], 0), K), S);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if(i == 0)
+        g_cnt[p] = n;
+    if(i < 2 * n)
+        reinterpret_cast<uint4*>(g_desc + (size_t)p * S * 32)[i] = reinterpret_cast<const uint4*>(store_desc + (size_t)slot * K * 32)[i];
+}
+
+// candidate p (one workgroup): its matches whose query keypoint is not masked out become correspondences, in match order:
+// object = (float) world point of landmark `to`, image = xy of keypoint `from`
+__global__ __launch_bounds__(256) void k_reloc_corr(const int32_t* __restrict__ mfrom, const int32_t* __restrict__ mto,
+                                                    const int32_t* __restrict__ mcount, const int32_t* __restrict__ g_cnt,
+                                                    const int32_t* __restrict__ slots, const double* __restrict__ store_world, int K,
+                                                    int S, const float* __restrict__ xy, const uint8_t* __restrict__ valid, int nq,
+                                                    float* __restrict__ obj, float* __restrict__ img, uint8_t* __restrict__ mask,
+                                                    int32_t* __restrict__ n_out)
+{
+    __shared__ uint32_t wsum[4];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = min(max(mcount[p], 0), S), n_to = g_cnt[p];
+    const size_t row = (size_t)p * S;
+    const double* world = store_world + (size_t)slots[p] * K * 3;
+    uint32_t running = 0;
+    for(int base = 0; base < m; base += 256)
+    {
+        const int i = base + tid;
+        int from = 0, to = 0;
+        bool ok = false;
+        if(i < m)
+        {
+            from = mfrom[row + i], to = mto[row + i];
+            ok = (unsigned)from < (unsigned)nq && (unsigned)to < (unsigned)n_to && (!valid || valid[from] != 0);
+        }
+        const unsigned long long b = __ballot(ok);
+        if(lane == 0)
+            wsum[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for(int k = 0; k < 4; ++k)
+        {
+            pre += k < wave ? wsum[k] : 0;
+            tot += wsum[k];
+        }
+        if(ok)
+        {
+            const size_t o = row + running + pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); // < row + m <= row + S
+            const double* P = world + (size_t)to * 3;
+            obj[o * 3] = (float)P[0], obj[o * 3 + 1] = (float)P[1], obj[o * 3 + 2] = (float)P[2];
+            img[o * 2] = xy[(size_t)from * 2], img[o * 2 + 1] = xy[(size_t)from * 2 + 1];
+        }
+        running += tot;
+        __syncthreads();
+    }
+    // fewer than 4 correspondences: the PnP kernel reports "no model" without touching the mask
+    if(running < 4 && tid < (int)running)
+        mask[row + tid] = 0;
+    if(tid == 0)
+        n_out[p] = (int32_t)running;
+}
+
+// block 0: the ranking (one wave, lane k = candidate k <= 63) and the per-candidate records; block 1 + p (want_pairs): the
+// matches and the consensus mask of candidate p.  Everything lands in the page-locked, device-mapped result block: these
+// stores are the transfer.
+__global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ mcount, const int32_t* __restrict__ ncorr,
+                                                    const double* __restrict__ pnp_out, int n_cand, int min_inliers, int S,
+                                                    const int32_t* __restrict__ mfrom, const int32_t* __restrict__ mto,
+                                                    const uint8_t* __restrict__ mask, uint8_t* __restrict__ res)
+{
+    const int tid = threadIdx.x;
+    if(blockIdx.x == 0)
+    {
+        if(tid >= 64)
+            return;
+        const bool live = tid < n_cand;
+        RelocRes r{};
+        if(live)
+        {
+            const double* o = pnp_out + (size_t)tid * 16;
+            r.n_matches = mcount[tid];
+            r.n_corr = ncorr[tid];
+            r.status = o[14] == 1.0 ? 1 : 0;
+            r.n_inliers = r.status ? (int32_t)o[12] : 0;
+            for(int j = 0; j < 9; ++j)
+                r.R[j] = r.status ? o[j] : 0.0;
+            for(int j = 0; j < 3; ++j)
+                r.t[j] = r.status ? o[9 + j] : 0.0;
+            reinterpret_cast<RelocRes*>(res + 16)[tid] = r;
+        }
+        // most inliers among the candidates with a model, the first one on ties (max_element): key = (inliers + 1, 63 - k)
+        int key = live && r.status ? ((r.n_inliers + 1) << 6) | (63 - tid) : 0;
+        for(int o = 32; o > 0; o >>= 1)
+            key = max(key, __shfl_xor(key, o));
+        if(tid == 0)
+        {
+            int best = -1;
+            if(key != 0 && (key >> 6) - 1 >= min_inliers)
+                best = 63 - (key & 63);
+            reinterpret_cast<int32_t*>(res)[0] = best;
+        }
+        return;
+    }
+    const int p = blockIdx.x - 1;
+    const size_t row = (size_t)p * S, all = (size_t)n_cand * S;
+    int32_t* h_from = reinterpret_cast<int32_t*>(res + 16 + kRelocMaxCand * sizeof(RelocRes));
+    int32_t* h_to = h_from + all;
+    uint8_t* h_mask = reinterpret_cast<uint8_t*>(h_to + all);
+    const int m = min(max(mcount[p], 0), S), nc = min(max(ncorr[p], 0), S);
+    for(int i = tid; i < m; i += 256)
+    {
+        h_from[row + i] = mfrom[row + i];
+        h_to[row + i] = mto[row + i];
+    }
+    for(int i = tid; i < nc; i += 256)
+        h_mask[row + i] = mask[row + i];
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+#define RCHK(c, call)                                                                                                  \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t e_ = (call);                                                                                        \
+        if(e_ != hipSuccess)                                                                                           \
+        {                                                                                                              \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
+            return MSLAM_HIP_E_RUNTIME;                                                                                \
+        }                                                                                                              \
+    } while(0)
+
+static int rfail(mslam_hip_ctx* c, int code, const std::string& msg)
+{
+    c->err = msg;
+    return code;
+}
+
+static int reloc_enter(mslam_hip_ctx* c)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    RCHK(c, hipSetDevice(c->p.device));
+    if(!c->reloc)
+        c->reloc = new RelocState();
+    return MSLAM_HIP_OK;
+}
+
+// at least `want` slots; the live entries move with the store
+static int store_reserve(mslam_hip_ctx* c, int want)
+{
+    RelocState* r = c->reloc;
+    if(want <= r->slots)
+        return MSLAM_HIP_OK;
+    const size_t K = (size_t)c->p.max_keypoints;
+    const int slots = std::max({want, 2 * r->slots, 16});
+    uint8_t* nd = nullptr;
+    double* nw = nullptr;
+    int32_t* nn = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nd), (size_t)slots * K * 32);
+    if(e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&nw), (size_t)slots * K * 3 * sizeof(double));
+    if(e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&nn), (size_t)slots * 4);
+    if(e == hipSuccess)
+        e = hipMemsetAsync(nn, 0, (size_t)slots * 4, c->stream);
+    if(e == hipSuccess && r->slots > 0)
+    {
+        e = hipMemcpyAsync(nd, r->d_desc, (size_t)r->slots * K * 32, hipMemcpyDeviceToDevice, c->stream);
+        if(e == hipSuccess)
+            e = hipMemcpyAsync(nw, r->d_world, (size_t)r->slots * K * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+        if(e == hipSuccess)
+            e = hipMemcpyAsync(nn, r->d_n, (size_t)r->slots * 4, hipMemcpyDeviceToDevice, c->stream);
+    }
+    if(e == hipSuccess)
+        e = hipStreamSynchronize(c->stream); // everything that reads the old blocks has finished before they are freed
+    if(e != hipSuccess)
+    {
+        void* fresh[] = {nd, nw, nn};
+        for(void* p : fresh)
+            if(p)
+                (void)hipFree(p);
+        return rfail(c, MSLAM_HIP_E_RUNTIME, std::string("kf store: ") + hipGetErrorString(e));
+    }
+    void* old[] = {r->d_desc, r->d_world, r->d_n};
+    for(void* p : old)
+        if(p)
+            (void)hipFree(p);
+    r->d_desc = nd, r->d_world = nw, r->d_n = nn;
+    for(int s = slots - 1; s >= r->slots; --s)
+        r->free_slots.push_back(s); // (handed out in ascending order)
+    r->n_upper.resize((size_t)slots, 0);
+    r->slots = slots;
+    return MSLAM_HIP_OK;
+}
+
+// the slot of `id`: its own when the id exists (the entry is replaced), a free one otherwise
+static int store_slot_for(mslam_hip_ctx* c, int id, int* slot)
+{
+    RelocState* r = c->reloc;
+    auto it = r->slot_of.find(id);
+    if(it != r->slot_of.end())
+    {
+        *slot = it->second;
+        return MSLAM_HIP_OK;
+    }
+    if(r->free_slots.empty())
+    {
+        const int rc = store_reserve(c, r->slots + 1);
+        if(rc)
+            return rc;
+    }
+    *slot = r->free_slots.back();
+    r->free_slots.pop_back();
+    r->slot_of[id] = *slot;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" {
+
+int mslam_hip_kf_reserve(mslam_hip_ctx* c, int max_entries)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(max_entries < 0)
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_reserve: bad argument");
+    return store_reserve(c, max_entries);
+}
+
+int mslam_hip_kf_size(mslam_hip_ctx* c, int* n_entries)
+{
+    if(!c || !n_entries)
+        return MSLAM_HIP_E_INVALID;
+    *n_entries = c->reloc ? (int)c->reloc->slot_of.size() : 0;
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_add(mslam_hip_ctx* c, int id, const uint8_t* desc, const double* world_xyz, int n)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(n < 0 || (n > 0 && (!desc || !world_xyz)))
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add: bad argument");
+    if(n > c->p.max_keypoints)
+        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_add: more landmarks than the context's max_keypoints");
+    int slot = -1;
+    rc = store_slot_for(c, id, &slot);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    const size_t K = (size_t)c->p.max_keypoints;
+    const int32_t n32 = n;
+    if(n > 0)
+    {
+        RCHK(c, hipMemcpyAsync(r->d_desc + (size_t)slot * K * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+        RCHK(c, hipMemcpyAsync(r->d_world + (size_t)slot * K * 3, world_xyz, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    }
+    RCHK(c, hipMemcpyAsync(r->d_n + slot, &n32, 4, hipMemcpyHostToDevice, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream)); // host-pointer entry point: the caller's buffers are free on return
+    r->n_upper[(size_t)slot] = n;
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const double* R, const double* t, double z_max)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(!R || !t || !(z_max == z_max))
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: bad argument");
+    if(frame < 0 || frame >= c->n_last)
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: no such frame in the last detect batch");
+    if(!c->d_xyz || c->points_seq != c->detect_seq)
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: the last detect batch has not been back-projected");
+    int slot = -1;
+    rc = store_slot_for(c, id, &slot);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    const size_t K = (size_t)c->p.max_keypoints;
+    KfPose pose;
+    std::memcpy(pose.R, R, sizeof(pose.R));
+    std::memcpy(pose.t, t, sizeof(pose.t));
+    pose.z_max = z_max;
+    {
+        StageScope ts(c, "kf_lift");
+        // frame f of the batch: descriptors in output slot f + 1, points in row f of the back-projection
+        hipLaunchKernelGGL(k_kf_lift, dim3(1), dim3(256), 0, c->stream, c->d_desc + (size_t)(frame + 1) * K * 32,
+                           c->d_xyz + (size_t)frame * K * 3, c->d_valid + (size_t)frame * K, c->d_count + 1 + frame,
+                           c->p.max_keypoints, pose, r->d_desc + (size_t)slot * K * 32, r->d_world + (size_t)slot * K * 3,
+                           r->d_n + slot);
+    }
+    RCHK(c, hipGetLastError());
+    r->n_upper[(size_t)slot] = c->p.max_keypoints; // (the count stays on the device)
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_remove(mslam_hip_ctx* c, int id)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    auto it = r->slot_of.find(id);
+    if(it == r->slot_of.end())
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_remove: no such keyframe id");
+    // (work already enqueued on the slot runs before anything a later add enqueues: one stream)
+    r->free_slots.push_back(it->second);
+    r->slot_of.erase(it);
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_clear(mslam_hip_ctx* c)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    r->slot_of.clear();
+    r->free_slots.clear();
+    for(int s = r->slots - 1; s >= 0; --s)
+        r->free_slots.push_back(s);
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_read(mslam_hip_ctx* c, int id, uint8_t* desc, double* world_xyz, int capacity, int* n)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(!n || capacity < 0)
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read: bad argument");
+    RelocState* r = c->reloc;
+    auto it = r->slot_of.find(id);
+    if(it == r->slot_of.end())
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read: no such keyframe id");
+    const size_t K = (size_t)c->p.max_keypoints, slot = (size_t)it->second;
+    int32_t n32 = 0;
+    RCHK(c, hipMemcpyAsync(&n32, r->d_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream));
+    if(n32 < 0 || (size_t)n32 > K)
+        return rfail(c, MSLAM_HIP_E_RUNTIME, "kf_read: impossible landmark count");
+    *n = n32;
+    r->n_upper[slot] = n32; // now known exactly
+    if(!desc && !world_xyz)
+        return MSLAM_HIP_OK;
+    if(n32 > capacity)
+        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_read: the entry has more landmarks than `capacity`");
+    if(desc && n32 > 0)
+        RCHK(c, hipMemcpyAsync(desc, r->d_desc + slot * K * 32, (size_t)n32 * 32, hipMemcpyDeviceToHost, c->stream));
+    if(world_xyz && n32 > 0)
+        RCHK(c, hipMemcpyAsync(world_xyz, r->d_world + slot * K * 3, (size_t)n32 * 24, hipMemcpyDeviceToHost, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream));
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint8_t* valid, int n,
+                         const int32_t* cand_ids, int n_cand, double fx, double fy, double cx, double cy, double ratio,
+                         int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess, const double* rvec,
+                         const double* tvec, int min_inliers, mslam_hip_reloc_candidate* out, int* best, int32_t* pair_from,
+                         int32_t* pair_to, uint8_t* inliers, int pair_stride)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(best)
+        *best = -1;
+    const bool want_pairs = pair_from || pair_to || inliers;
+    if(!best || n < 0 || n_cand < 0 || n_cand > kRelocMaxCand || (n > 0 && (!desc || !xy)) || (n_cand > 0 && (!cand_ids || !out)) ||
+       iterations < 1 || iterations > 4096 || !(reprojection_error > 0) || !(fx != 0.0) || !(fy != 0.0) ||
+       (use_extrinsic_guess && (!rvec || !tvec)) || (want_pairs && pair_stride < 0))
+        return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: bad argument (at most 64 candidates, 1..4096 iterations)");
+    if(n > 65535)
+        return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: more than 65535 query keypoints are not supported");
+    RelocState* r = c->reloc;
+    const int K = c->p.max_keypoints;
+    int32_t slots[kRelocMaxCand];
+    int n_max = 0;
+    for(int k = 0; k < n_cand; ++k)
+    {
+        auto it = r->slot_of.find(cand_ids[k]);
+        if(it == r->slot_of.end())
+            return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: candidate id " + std::to_string(cand_ids[k]) + " is not in the keyframe store");
+        slots[k] = it->second;
+        n_max = std::max(n_max, r->n_upper[(size_t)it->second]);
+    }
+    for(int k = 0; k < n_cand; ++k)
+        out[k] = mslam_hip_reloc_candidate{};
+    if(n_cand == 0 || n < 2)
+        return rfail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate, or fewer than 2 query keypoints (no matches)");
+    rc = mslam_ratio_table(c, ratio);
+    if(rc)
+        return rc;
+
+    // per-candidate row stride of every scratch array: the largest candidate, in whole 256-row blocks
+    const size_t S = ((size_t)std::max(n_max, 1) + 255) & ~(size_t)255, P = (size_t)n_cand, PS = P * S;
+    // ---- upload block: [desc n x 32 | xy n x 8 | slots 64 x 4 | valid n], one copy
+    const size_t off_xy = (size_t)n * 32, off_slots = off_xy + (size_t)n * 8, off_valid = off_slots + kRelocMaxCand * 4;
+    const size_t up = off_valid + (valid ? (size_t)n : 0);
+    if(up > r->up_bytes)
+    {
+        RCHK(c, hipStreamSynchronize(c->stream));
+        if(r->h_up)
+            (void)hipHostFree(r->h_up);
+        if(r->d_up)
+            (void)hipFree(r->d_up);
+        r->h_up = r->d_up = nullptr;
+        r->up_bytes = 0;
+        const size_t bytes = std::max(up, (size_t)4096 * 41 + kRelocMaxCand * 4);
+        RCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_up), bytes, hipHostMallocDefault));
+        RCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_up), bytes));
+        r->up_bytes = bytes;
+    }
+    // ---- device arena: every per-candidate array of this call, 256-byte aligned
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t o_gdesc = carve(PS * 32), o_gcnt = carve(P * 4), o_idx0 = carve(PS * 4), o_idx1 = carve(PS * 4),
+                 o_dist0 = carve(PS * 4), o_dist1 = carve(PS * 4), o_mfrom = carve(PS * 4), o_mto = carve(PS * 4),
+                 o_mcount = carve(P * 4), o_obj = carve(PS * 12), o_img = carve(PS * 8), o_ncorr = carve(P * 4),
+                 o_mask = carve(PS), o_hyp = carve(P * (size_t)iterations * 96), o_counts = carve(P * (size_t)iterations * 4),
+                 o_out = carve(P * 128);
+    if(off > r->arena_bytes)
+    {
+        RCHK(c, hipStreamSynchronize(c->stream));
+        if(r->d_arena)
+            (void)hipFree(r->d_arena);
+        r->d_arena = nullptr;
+        r->arena_bytes = 0;
+        RCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_arena), off));
+        r->arena_bytes = off;
+    }
+    // ---- result block (mapped): [best, pad | RelocRes[64] | pair_from P x S | pair_to P x S | inliers P x S]
+    const size_t res_head = 16 + kRelocMaxCand * sizeof(RelocRes);
+    const size_t res = res_head + (want_pairs ? PS * 9 : 0);
+    if(res > r->res_bytes)
+    {
+        RCHK(c, hipStreamSynchronize(c->stream));
+        if(r->h_res)
+            (void)hipHostFree(r->h_res);
+        r->h_res = r->d_h_res = nullptr;
+        r->res_bytes = 0;
+        RCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_res), res, hipHostMallocMapped));
+        RCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_res), r->h_res, 0));
+        r->res_bytes = res;
+    }
+
+    std::memcpy(r->h_up, desc, (size_t)n * 32);
+    std::memcpy(r->h_up + off_xy, xy, (size_t)n * 8);
+    std::memcpy(r->h_up + off_slots, slots, P * 4);
+    if(valid)
+        std::memcpy(r->h_up + off_valid, valid, (size_t)n);
+    reinterpret_cast<int32_t*>(r->h_res)[0] = -2; // (overwritten by k_reloc_rank; checked after the synchronisation)
+    hipStream_t s = c->stream;
+    RCHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
+    uint8_t* A = r->d_arena;
+    const int32_t* d_slots = reinterpret_cast<const int32_t*>(r->d_up + off_slots);
+    const float* d_xy = reinterpret_cast<const float*>(r->d_up + off_xy);
+    const uint8_t* d_valid = valid ? r->d_up + off_valid : nullptr;
+    int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o_gcnt);
+    {
+        StageScope ts(c, "reloc_gather_desc");
+        hipLaunchKernelGGL(k_reloc_gather_desc, dim3((unsigned)((2 * S + 255) / 256), (unsigned)P), dim3(256), 0, s, r->d_desc, r->d_n,
+                           d_slots, K, (int)S, A + o_gdesc, g_cnt);
+    }
+    // match(from = query keypoints, to = landmarks of candidate p): knn-2 with query = `to` and train = `from`
+    MatchArgs m{};
+    m.from_desc = r->d_up;
+    m.from_stride = 0; // every pair's train side is the one uploaded query block
+    m.from_cnt = nullptr;
+    m.n_from_fixed = n;
+    m.to_desc = A + o_gdesc;
+    m.to_stride = (long long)S * 32;
+    m.to_cnt = g_cnt;
+    m.cap = (int)S;
+    m.cap_from = n;
+    m.popcount_only = c->matcher_kind == MSLAM_HIP_MATCHER_POPCOUNT;
+    m.idx0 = reinterpret_cast<int32_t*>(A + o_idx0);
+    m.idx1 = reinterpret_cast<int32_t*>(A + o_idx1);
+    m.dist0 = reinterpret_cast<int32_t*>(A + o_dist0);
+    m.dist1 = reinterpret_cast<int32_t*>(A + o_dist1);
+    {
+        StageScope ts(c, "match_knn2");
+        c->last_match_kernel = launch_match_knn2(m, n_cand, s);
+    }
+    RatioArgs q{};
+    q.idx0 = m.idx0, q.dist0 = m.dist0, q.dist1 = m.dist1;
+    q.from_cnt = nullptr, q.n_from_fixed = n;
+    q.to_cnt = g_cnt;
+    q.cap = (int)S;
+    q.thr = c->d_ratio_thr;
+    q.from_idx = reinterpret_cast<int32_t*>(A + o_mfrom);
+    q.to_idx = reinterpret_cast<int32_t*>(A + o_mto);
+    q.n_out = reinterpret_cast<int32_t*>(A + o_mcount);
+    {
+        StageScope ts(c, "ratio_compact");
+        launch_ratio_compact(q, n_cand, s);
+    }
+    float* d_obj = reinterpret_cast<float*>(A + o_obj);
+    float* d_img = reinterpret_cast<float*>(A + o_img);
+    int32_t* d_ncorr = reinterpret_cast<int32_t*>(A + o_ncorr);
+    uint8_t* d_mask = A + o_mask;
+    {
+        StageScope ts(c, "reloc_corr");
+        hipLaunchKernelGGL(k_reloc_corr, dim3((unsigned)P), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, d_slots, r->d_world, K,
+                           (int)S, d_xy, d_valid, n, d_obj, d_img, d_mask, d_ncorr);
+    }
+    RCHK(c, hipGetLastError());
+    PnpBatchLaunch l{};
+    l.obj = d_obj, l.img = d_img, l.n = d_ncorr;
+    l.n_problems = n_cand, l.cap = (int)S;
+    l.fx = fx, l.fy = fy, l.cx = cx, l.cy = cy;
+    l.use_guess = use_extrinsic_guess ? 1 : 0;
+    for(int j = 0; j < 3; ++j)
+    {
+        l.rvec[j] = use_extrinsic_guess ? rvec[j] : 0.0;
+        l.tvec[j] = use_extrinsic_guess ? tvec[j] : 0.0;
+    }
+    l.iterations = iterations;
+    l.reprojection_error = reprojection_error;
+    l.seed = seed;
+    l.hyp = reinterpret_cast<double*>(A + o_hyp);
+    l.counts = reinterpret_cast<int32_t*>(A + o_counts);
+    l.mask = d_mask;
+    l.out = reinterpret_cast<double*>(A + o_out);
+    rc = pnp_launch_batch(c, l);
+    if(rc)
+        return rc;
+    {
+        StageScope ts(c, "reloc_rank");
+        hipLaunchKernelGGL(k_reloc_rank, dim3(want_pairs ? 1u + (unsigned)P : 1u), dim3(256), 0, s, q.n_out, d_ncorr, l.out, n_cand,
+                           min_inliers, (int)S, q.from_idx, q.to_idx, d_mask, r->d_h_res);
+    }
+    RCHK(c, hipGetLastError());
+    RCHK(c, hipStreamSynchronize(s));
+
+    const int32_t b = reinterpret_cast<const int32_t*>(r->h_res)[0];
+    if(b < -1 || b >= n_cand)
+        return rfail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the ranking kernel left no result");
+    const RelocRes* rr = reinterpret_cast<const RelocRes*>(r->h_res + 16);
+    bool fits = true;
+    for(int k = 0; k < n_cand; ++k)
+    {
+        // (counts from mapped memory size the copies below: never trust them blindly)
+        if(rr[k].n_matches < 0 || (size_t)rr[k].n_matches > S || rr[k].n_corr < 0 || rr[k].n_corr > rr[k].n_matches)
+            return rfail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the kernels reported impossible counts");
+        out[k].n_matches = rr[k].n_matches;
+        out[k].n_correspondences = rr[k].n_corr;
+        out[k].n_inliers = rr[k].n_inliers;
+        out[k].status = rr[k].status;
+        if(rr[k].status)
+        {
+            pnp_rotation_to_rvec(rr[k].R, out[k].rvec);
+            out[k].tvec[0] = rr[k].t[0], out[k].tvec[1] = rr[k].t[1], out[k].tvec[2] = rr[k].t[2];
+        }
+        if(want_pairs && rr[k].n_matches > pair_stride)
+            fits = false;
+    }
+    if(want_pairs && !fits)
+        return rfail(c, MSLAM_HIP_E_CAPACITY, "relocalize: a candidate has more matches than pair_stride");
+    if(want_pairs)
+    {
+        const int32_t* h_from = reinterpret_cast<const int32_t*>(r->h_res + res_head);
+        const int32_t* h_to = h_from + PS;
+        const uint8_t* h_mask = reinterpret_cast<const uint8_t*>(h_to + PS);
+        for(int k = 0; k < n_cand; ++k)
+        {
+            const size_t src = (size_t)k * S, dst = (size_t)k * (size_t)pair_stride;
+            if(pair_from)
+                std::memcpy(pair_from + dst, h_from + src, (size_t)rr[k].n_matches * 4);
+            if(pair_to)
+                std::memcpy(pair_to + dst, h_to + src, (size_t)rr[k].n_matches * 4);
+            if(inliers)
+                std::memcpy(inliers + dst, h_mask + src, (size_t)rr[k].n_corr);
+        }
+    }
+    *best = b;
+    if(b < 0)
+        return rfail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate reached min_inliers");
+    return MSLAM_HIP_OK;
+}
+
+} // extern "C"

@@ -13,6 +13,10 @@
 //                                    the BoW boundary: relocalizer + loop detector factories (one shared database),
 //                                    fed in the frontend's order: detect -> addKeyframe (rgbd_feature_frontend.cpp:176)
 //                                    -> detectLoop (:202); then relocalize / removeKeyframe / relocalize
+//        mslam_harness <plugin.so> --reloc <vocabulary.dbow3> <scene>
+//                                    the verified relocalisation: addKeyframe + addKeyframeLandmarks per keyframe of the scene,
+//                                    relocalizePose(query), then the query fed as a keyframe and detectLoopVerified,
+//                                    then removeKeyframe(winner) and relocalizePose again
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -102,6 +106,91 @@ int main(int argc, char** argv)
                         result->pose.position.x(), result->pose.position.y(), result->pose.position.z(),
                         result->pose.orientation.w(), result->pose.orientation.x(), result->pose.orientation.y(),
                         result->pose.orientation.z(), inl);
+            return 0;
+        }
+        if(argc == 5 && std::strcmp(argv[2], "--reloc") == 0)
+        {
+            // scene file: u32 n_keyframes, per keyframe u32 n, n x 32 descriptor bytes, n x 3 f64 world points; then the
+            // query: u32 n, n x 32 descriptor bytes, n x 2 f64 keypoint coordinates; then fx fy cx cy (f64)
+            setenv("MSLAM_ORB_VOCABULARY", argv[3], 1);
+            auto makeReloc = mslam::loadFactoryMethod<mslam::IOrbRelocalizer>(argv[1], "hipOrbRelocalizerFactory");
+            auto makeLoop = mslam::loadFactoryMethod<mslam::IOrbLoopDetector>(argv[1], "loopDetection");
+            std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
+            std::unique_ptr<mslam::IOrbLoopDetector> loopDetector = makeLoop();
+            auto* verified = dynamic_cast<mslam::IVerifiedRelocalizer*>(relocalizer.get());
+            auto* verifiedLoop = dynamic_cast<mslam::IVerifiedLoopDetector*>(loopDetector.get());
+            if(!verified || !verifiedLoop)
+            {
+                std::fprintf(stderr, "the plugin does not offer the verified relocalisation\n");
+                return 6;
+            }
+            std::ifstream in(argv[4], std::ios::binary);
+            auto readKeypoints = [&in](std::vector<mslam::OrbKeypoint>& kps) {
+                std::uint32_t n = 0;
+                in.read(reinterpret_cast<char*>(&n), 4);
+                kps.resize(n);
+                for(std::uint32_t i = 0; i < n; ++i)
+                {
+                    kps[i].keypoint.id = i;
+                    in.read(reinterpret_cast<char*>(kps[i].descriptor.data()), 32);
+                }
+            };
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::uint32_t nKeyframes = 0;
+            in.read(reinterpret_cast<char*>(&nKeyframes), 4);
+            std::vector<std::shared_ptr<Kf>> keyframes;
+            for(std::uint32_t f = 0; f < nKeyframes; ++f)
+            {
+                std::vector<mslam::OrbKeypoint> kps;
+                readKeypoints(kps);
+                std::vector<mslam::Vector3> world(kps.size());
+                for(auto& w : world)
+                    in.read(reinterpret_cast<char*>(w.v), sizeof(w.v));
+                auto kf = std::make_shared<Kf>();
+                kf->id = 100 + f;
+                relocalizer->addKeyframe(kf, kps);
+                verified->addKeyframeLandmarks(kf, kps, world);
+                keyframes.push_back(kf);
+            }
+            std::vector<mslam::OrbKeypoint> query;
+            readKeypoints(query);
+            for(auto& k : query)
+            {
+                double xy[2];
+                in.read(reinterpret_cast<char*>(xy), sizeof(xy));
+                k.keypoint.coordinates = mslam::Vector2(xy[0], xy[1]);
+            }
+            double cam[4];
+            if(!in.read(reinterpret_cast<char*>(cam), sizeof(cam)))
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[4]);
+                return 5;
+            }
+            mslam::CameraParameters cp;
+            cp.focal = mslam::Vector2(cam[0], cam[1]);
+            cp.principalPoint = mslam::Vector2(cam[2], cam[3]);
+            cp.factor = 1.0f / 5000.0f;
+            auto print = [](const char* what, const mslam::VerifiedRelocalization& r) {
+                std::printf("%s keyframe %lld inliers %d rvec %.17g %.17g %.17g tvec %.17g %.17g %.17g\n", what,
+                            r.keyframe ? (long long)r.keyframe->id : -1LL, r.inliers, r.rvec[0], r.rvec[1], r.rvec[2], r.tvec[0],
+                            r.tvec[1], r.tvec[2]);
+                for(const auto& c : r.candidates)
+                    std::printf("%s candidate %llu matches %d correspondences %d inliers %d model %d\n", what,
+                                (unsigned long long)c.keyframe->id, c.matches, c.correspondences, c.inliers, c.hasModel ? 1 : 0);
+            };
+            const auto first = verified->relocalizePose(query, cp);
+            print("reloc", first);
+            auto kf = std::make_shared<Kf>();
+            kf->id = 100 + nKeyframes;
+            relocalizer->addKeyframe(kf, query);
+            const auto loop = loopDetector->detectLoop();
+            std::printf("loop %lld\n", loop ? (long long)loop->id : -1LL);
+            print("loop-verified", verifiedLoop->detectLoopVerified(cp));
+            if(first.keyframe)
+            {
+                relocalizer->removeKeyframe(first.keyframe);
+                print("after-remove", verified->relocalizePose(query, cp));
+            }
             return 0;
         }
         if(argc >= 7 && std::strcmp(argv[2], "--bow") == 0)

@@ -30,6 +30,7 @@
 #include <fstream>
 #include <map>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 
@@ -253,6 +254,7 @@ class BowDatabase
         // loop candidate = best earlier keyframe for the one being added
         const auto candidates = relocalize(keypoints);
         lastLoop = candidates.empty() ? nullptr : candidates.front();
+        lastFed = keypoints; // (detectLoopVerified verifies the candidate against these)
         int entry = -1;
         const int rc = mslam_hip_bow_db_add(ctx.h, desc.data(), static_cast<int>(keypoints.size()), &entry);
         if(rc != MSLAM_HIP_OK)
@@ -269,6 +271,12 @@ class BowDatabase
                 const int rc = mslam_hip_bow_db_remove(ctx.h, it->first); // never scored again
                 if(rc != MSLAM_HIP_OK)
                     raise(ctx.h, "mslam_hip_bow_db_remove", rc);
+                if(withLandmarks.erase(it->first)) // its landmarks leave the keyframe store with it
+                {
+                    const int rk = mslam_hip_kf_remove(ctx.h, it->first);
+                    if(rk != MSLAM_HIP_OK)
+                        raise(ctx.h, "mslam_hip_kf_remove", rk);
+                }
                 it = entryToKeyframe.erase(it);
             }
             else
@@ -280,14 +288,108 @@ class BowDatabase
 
     KeyframePtr detectLoop() const { return lastLoop; }
 
+    // ---- extension: candidates verified against stored landmarks (mslam_hip_relocalize) ----
+    void addKeyframeLandmarks(const KeyframePtr& keyframe, const std::vector<OrbKeypoint>& keypoints,
+                              const std::vector<Vector3>& worldPoints)
+    {
+        if(keypoints.size() != worldPoints.size())
+            throw std::runtime_error("addKeyframeLandmarks: one world point per keypoint");
+        for(const auto& e : entryToKeyframe)
+            if(e.second == keyframe)
+            {
+                gather_descriptors(keypoints, desc);
+                std::vector<double> world(3 * worldPoints.size());
+                for(std::size_t i = 0; i < worldPoints.size(); ++i)
+                    world[3 * i] = worldPoints[i].x(), world[3 * i + 1] = worldPoints[i].y(), world[3 * i + 2] = worldPoints[i].z();
+                // the store's id is the BoW entry id: one id names both
+                const int rc = mslam_hip_kf_add(ctx.h, e.first, desc.data(), world.data(), static_cast<int>(keypoints.size()));
+                if(rc != MSLAM_HIP_OK)
+                    raise(ctx.h, "mslam_hip_kf_add", rc);
+                withLandmarks.insert(e.first);
+                return;
+            }
+        throw std::runtime_error("addKeyframeLandmarks: the keyframe has not been added");
+    }
+
+    // relocalize()'s candidates (those with stored landmarks), each matched and solved; OpenCvRansacPnp's operating point
+    // (cv_ransac_pnp.cpp:56-57: 100 iterations, 5 px) and the matcher's ratio (orb_feature.cpp:101), no guess (:519)
+    VerifiedRelocalization relocalizePose(const std::vector<OrbKeypoint>& keypoints, const CameraParameters& camera, int minInliers)
+    {
+        std::vector<std::int32_t> entries;
+        gather_descriptors(keypoints, desc);
+        std::int32_t ids[64];
+        double scores[64];
+        int n = 0;
+        const int rc = mslam_hip_bow_db_query(ctx.h, desc.data(), static_cast<int>(keypoints.size()), 64, ids, scores, &n);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_bow_db_query", rc);
+        int taken = 0;
+        for(int i = 0; i < n && taken < 4; ++i)
+            if(entryToKeyframe.count(ids[i]))
+            {
+                ++taken; // the same four relocalize() returns
+                if(withLandmarks.count(ids[i]))
+                    entries.push_back(ids[i]);
+            }
+        return verify(keypoints, entries, camera, minInliers);
+    }
+
+    VerifiedRelocalization detectLoopVerified(const CameraParameters& camera, int minInliers)
+    {
+        std::vector<std::int32_t> entries;
+        for(const auto& e : entryToKeyframe)
+            if(lastLoop && e.second == lastLoop && withLandmarks.count(e.first))
+                entries.push_back(e.first);
+        return verify(lastFed, entries, camera, minInliers);
+    }
+
   private:
+    VerifiedRelocalization verify(const std::vector<OrbKeypoint>& keypoints, const std::vector<std::int32_t>& entries,
+                                  const CameraParameters& camera, int minInliers)
+    {
+        gather_descriptors(keypoints, desc);
+        std::vector<float> xy(2 * keypoints.size());
+        for(std::size_t i = 0; i < keypoints.size(); ++i)
+        {
+            xy[2 * i] = static_cast<float>(keypoints[i].keypoint.coordinates.x());
+            xy[2 * i + 1] = static_cast<float>(keypoints[i].keypoint.coordinates.y());
+        }
+        std::vector<mslam_hip_reloc_candidate> out(entries.size() + 1);
+        int best = -1;
+        const int rc = mslam_hip_relocalize(ctx.h, desc.data(), xy.data(), nullptr, static_cast<int>(keypoints.size()), entries.data(),
+                                            static_cast<int>(entries.size()), camera.focal.x(), camera.focal.y(),
+                                            camera.principalPoint.x(), camera.principalPoint.y(), 0.7, 100, 5.0, 0, 0, nullptr,
+                                            nullptr, minInliers, out.data(), &best, nullptr, nullptr, nullptr, 0);
+        if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
+            raise(ctx.h, "mslam_hip_relocalize", rc);
+        VerifiedRelocalization result;
+        for(std::size_t k = 0; k < entries.size(); ++k)
+        {
+            VerifiedCandidate c;
+            c.keyframe = entryToKeyframe[entries[k]];
+            c.matches = out[k].n_matches, c.correspondences = out[k].n_correspondences, c.inliers = out[k].n_inliers;
+            c.hasModel = out[k].status != 0;
+            result.candidates.push_back(c);
+        }
+        if(best >= 0)
+        {
+            result.keyframe = result.candidates[static_cast<std::size_t>(best)].keyframe;
+            result.inliers = out[best].n_inliers;
+            std::memcpy(result.rvec, out[best].rvec, sizeof(result.rvec));
+            std::memcpy(result.tvec, out[best].tvec, sizeof(result.tvec));
+        }
+        return result;
+    }
+
     Ctx ctx;
     std::vector<std::uint8_t> desc;
     std::map<int, KeyframePtr> entryToKeyframe;
+    std::set<int> withLandmarks; // entries addKeyframeLandmarks has stored landmarks for
     KeyframePtr lastLoop;
+    std::vector<OrbKeypoint> lastFed;
 };
 
-class HipOrbRelocalizer : public IOrbRelocalizer
+class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -300,16 +402,30 @@ class HipOrbRelocalizer : public IOrbRelocalizer
         db->addKeyframe(std::move(keyframe), keypoints);
     }
     void removeKeyframe(BowDatabase::KeyframePtr keyframe) override { db->removeKeyframe(keyframe); }
+    void addKeyframeLandmarks(BowDatabase::KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints,
+                              const std::vector<Vector3>& worldPoints) override
+    {
+        db->addKeyframeLandmarks(keyframe, keypoints, worldPoints);
+    }
+    VerifiedRelocalization relocalizePose(const std::vector<OrbKeypoint>& keypoints, const CameraParameters& camera,
+                                          int minInliers) override
+    {
+        return db->relocalizePose(keypoints, camera, minInliers);
+    }
 
   private:
     std::shared_ptr<BowDatabase> db;
 };
 
-class HipLoopDetector : public IOrbLoopDetector
+class HipLoopDetector : public IOrbLoopDetector, public IVerifiedLoopDetector
 {
   public:
     HipLoopDetector() : db(BowDatabase::shared()) {}
     BowDatabase::KeyframePtr detectLoop() override { return db->detectLoop(); }
+    VerifiedRelocalization detectLoopVerified(const CameraParameters& camera, int minInliers) override
+    {
+        return db->detectLoopVerified(camera, minInliers);
+    }
 
   private:
     std::shared_ptr<BowDatabase> db;

@@ -195,4 +195,39 @@ static_assert(sizeof(OrbKeypoint) == 64, "OrbKeypoint is expected to be a 64-byt
 using IOrbRelocalizer = IRelocalizer<slam3d::SensorState, std::uint8_t, 32>;
 using IOrbLoopDetector = ILoopDetector<slam3d::SensorState>;
 using ISlam3dPnp = IPnpAlgorithm<slam3d::SensorState, Vector3>;
+
+// ---- extension (not in the reference): candidates verified by match + RANSAC PnP against stored landmarks -----------------
+// What RgbdFeatureFrontend::relocalize's commented-out body does with IRelocalizer::relocalize's candidates
+// (rgbd_feature_frontend.cpp:495-534).  IRelocalizer / ILoopDetector themselves are untouched: an adapter that offers the
+// extension derives from these as well, and a caller reaches it with dynamic_cast.
+struct VerifiedCandidate
+{
+    std::shared_ptr<Keyframe<slam3d::SensorState>> keyframe;
+    int matches = 0, correspondences = 0, inliers = 0;
+    bool hasModel = false;
+};
+struct VerifiedRelocalization
+{
+    std::shared_ptr<Keyframe<slam3d::SensorState>> keyframe; // null: no candidate reached minInliers
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};         // world -> camera (cv::solvePnPRansac's convention)
+    int inliers = 0;
+    std::vector<VerifiedCandidate> candidates;               // in candidate order
+};
+class IVerifiedRelocalizer
+{
+  public:
+    // the landmarks of a keyframe addKeyframe has fed: worldPoints[i] belongs to keypoints[i]
+    virtual void addKeyframeLandmarks(std::shared_ptr<Keyframe<slam3d::SensorState>> keyframe,
+                                      const std::vector<OrbKeypoint>& keypoints, const std::vector<Vector3>& worldPoints) = 0;
+    virtual VerifiedRelocalization relocalizePose(const std::vector<OrbKeypoint>& keypoints, const CameraParameters& camera,
+                                                  int minInliers = 60) = 0;
+    virtual ~IVerifiedRelocalizer() = default;
+};
+class IVerifiedLoopDetector
+{
+  public:
+    // detectLoop()'s candidate for the keyframe fed last, verified the same way
+    virtual VerifiedRelocalization detectLoopVerified(const CameraParameters& camera, int minInliers = 60) = 0;
+    virtual ~IVerifiedLoopDetector() = default;
+};
 } // namespace mslam
