@@ -497,6 +497,84 @@ int mslam_hip_relocalize(mslam_hip_ctx* ctx, const uint8_t* desc, const float* x
                          const double* rvec, const double* tvec, int min_inliers, mslam_hip_reloc_candidate* out,
                          int* best, int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride);
 
+/* ---- the keyframe tracking step: track, reference vote, keyframe insertion -------------------------------------------
+ * findBetterReferenceKeyframe's count (rgbd_feature_frontend.cpp:544-575; isVisibleInFrame / projectOnImage,
+ * projection.cpp:42-62): for each of n_ids <= 64 stored keyframes, how many of its landmarks project into a frame of
+ * width x height seen from the pose (R = 9 doubles row-major, t = 3 doubles: world -> camera, the library's convention).
+ * Per landmark (X, Y, Z), in f64, every operation rounded on its own:
+ *   c_r = ((R[r][0] X + R[r][1] Y) + R[r][2] Z) + t[r];   u = (c_0 / c_2) fx + cx;   v = (c_1 / c_2) fy + cy;
+ *   visible <=> u >= 0 && u < (double)(float)width && v >= 0 && v < (double)(float)height && c_2 > 0.
+ * counts[k] = the visible landmarks of ids[k]; *best = the position in ids of the largest count, the first one on ties, or
+ * -1 when n_ids == 0.  One upload, two launches, one synchronisation.  An id that is not in the store: MSLAM_HIP_E_INVALID.
+ *   count    SAME as keyframeCount[kf], provided an entry holds the landmarks its keyframe observes (the reference walks
+ *            keyframe -> observed landmarks through the map; the store has the entry's own landmarks);
+ *   winner   DEVIATES: the first maximum in the caller's list order.  The reference iterates a std::map keyed by the
+ *            keyframes' pointer values, an unspecified order, and keeps the first maximum of that;
+ *   camera   DEVIATES in the last bits: the camera point is R p + t, not q^-1 p - q^-1 position (toLocalCoordinates). */
+int mslam_hip_kf_visible(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids /* <= 64 */, const double* R, const double* t,
+                         double fx, double fy, double cx, double cy, int width, int height, int32_t* counts /* n_ids */,
+                         int* best /* position in ids, -1 if n_ids == 0 */);
+
+/* RgbdFeatureFrontend::track (rgbd_feature_frontend.cpp:279-400) against the store, in one call with one upload and one
+ * host synchronisation: the depth filter, the match against the reference keyframe, PnP, the reference vote and the new
+ * keyframe, each a launch on the context's stream.
+ *   depth filter   mslam_hip_backproject's kernel on the uploaded depth frame (width x height u16, `factor`): a keypoint
+ *                  without a valid depth takes no part in PnP (:286, :317-334);
+ *   step           exactly mslam_hip_relocalize with the one candidate ref_id, that mask and the guess: matches,
+ *                  correspondences, RANSAC PnP with `seed`;
+ *   tracked        n_correspondences >= min_matched_points (:336, the reference: 10) and PnP found a model;
+ *   vote           mslam_hip_kf_visible over vote_ids (<= 64) with the PnP kernel's own pose record, read on the device;
+ *   keyframe       required <=> tracked && n_inliers < new_keyframe_min_landmarks (:156-162, the reference: 30).  With
+ *                  new_id >= 0 the entry is built in the store under new_id (:373-397):
+ *                    part A  every inlier correspondence, in correspondence order: the query's descriptor desc[from], the
+ *                            reference entry's world point world[to] copied bit for bit; entry_src = to, entry_kp = from;
+ *                    part B  every keypoint that no correspondence used (matched with a valid depth, inlier or not:
+ *                            usedKeypointIndices, :314-334; set_difference, :377-385), with a valid depth and z <= z_max, in
+ *                            keypoint order, lifted as addNewLandmarks does (:402-431):
+ *                            world_r = ((R[0][r] (x - t0) + R[1][r] (y - t1)) + R[2][r] (z - t2)), the inverse of the
+ *                            tracked world -> camera pose; entry_src = -1, entry_kp = the keypoint;
+ *                  The matcher gives one match per landmark of ref_id, so two landmarks can be matched to the same
+ *                  keypoint: part A then lists that keypoint twice (two observations, as the reference would push both).
+ *                  Without such duplicates A and B are disjoint subsets of the keypoints and the entry holds at most n
+ *                  landmarks; with them it can hold more, and it is cut at max_keypoints (part A first, n_entry says what
+ *                  was kept).  n > max_keypoints is MSLAM_HIP_E_CAPACITY (an entry's capacity).
+ * `out` is always written.  vote_counts (n_vote), pair_from / pair_to / inliers (one row, as mslam_hip_relocalize) and
+ * entry_src / entry_kp (entry_capacity) may be NULL.
+ * Returns MSLAM_HIP_OK when tracked; MSLAM_HIP_E_NO_MODEL when not: the store is untouched, a slot reserved for new_id is
+ * released; MSLAM_HIP_E_INVALID for a ref_id or vote id that is not in the store, or a new_id that ref_id or the vote list
+ * names; MSLAM_HIP_E_CAPACITY when the matches do not fit pair_stride or the entry does not fit entry_capacity: the step has
+ * run, `out` is complete and a keyframe that `out` reports as added is in the store; only the rows are not copied.  A
+ * new_id that exists is replaced when a keyframe is added and left alone otherwise.  The store grows for new_id on the host
+ * before anything is enqueued.
+ * Against the reference:
+ *   matching       DEVIATES: against the reference keyframe's own entry only, not against the union of the most recent
+ *                  observations within graph depth 2 (getLandmarksWithKeypoints, :256-277): the store has no landmark
+ *                  identity across entries.  entry_src / entry_kp are what let the caller keep that identity on the host:
+ *                  entry i of the new keyframe is landmark entry_src[i] of ref_id (or a new landmark), seen at keypoint
+ *                  entry_kp[i];
+ *   PnP            as mslam_hip_pnp_ransac (see its SAME / DEVIATES list); tracked, keyframe_required SAME;
+ *   vote           see mslam_hip_kf_visible; the caller chooses the neighbourhood (vote_ids);
+ *   new keyframe   SAME observations and landmarks; the lift DEVIATES in the last bits as mslam_hip_kf_add_from_batch_dev's;
+ *   debug drawing  (:291-309) not reproduced. */
+typedef struct
+{
+    int32_t n_matches, n_correspondences, n_inliers, status; /* as mslam_hip_reloc_candidate                                */
+    double rvec[3], tvec[3], R[9];                           /* the tracked pose; R row-major (zeros without a model)      */
+    int32_t tracked;             /* 1: n_correspondences >= min_matched_points and PnP found a model                      */
+    int32_t keyframe_required;   /* tracked && n_inliers < new_keyframe_min_landmarks                                     */
+    int32_t keyframe_added;      /* keyframe_required && new_id >= 0                                                      */
+    int32_t n_entry, n_inherited;/* landmarks of the new entry; how many of them are part A                               */
+    int32_t vote_best, vote_best_count; /* position in vote_ids / its count; -1 / 0 when not tracked or n_vote == 0       */
+} mslam_hip_track_result;
+int mslam_hip_track(mslam_hip_ctx* ctx, const uint8_t* desc, const float* xy, int n, const uint16_t* depth, int width,
+                    int height, float factor, double fx, double fy, double cx, double cy, int ref_id,
+                    const int32_t* vote_ids, int n_vote, double ratio, int iterations, double reprojection_error,
+                    uint64_t seed, int use_extrinsic_guess, const double* rvec, const double* tvec,
+                    int min_matched_points /* 10 */, int new_keyframe_min_landmarks /* 30 */, int new_id /* < 0: never insert */,
+                    double z_max /* 3.0 */, mslam_hip_track_result* out, int32_t* vote_counts /* n_vote, may be NULL */,
+                    int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride,
+                    int32_t* entry_src, int32_t* entry_kp, int entry_capacity);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

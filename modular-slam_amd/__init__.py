@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_cv_keypoint_order", "mslam_hip_pnp_min_mse", "mslam_hip_pnp_min_mse_batch_dev",
     "mslam_hip_kf_add", "mslam_hip_kf_add_from_batch_dev", "mslam_hip_kf_remove", "mslam_hip_kf_clear", "mslam_hip_kf_size",
     "mslam_hip_kf_reserve", "mslam_hip_kf_read", "mslam_hip_relocalize",
+    "mslam_hip_kf_visible", "mslam_hip_track",
 ]
 
 
@@ -112,6 +113,13 @@ class PnpView(C.Structure):
 class RelocCandidate(C.Structure):
     _fields_ = [("n_matches", C.c_int32), ("n_correspondences", C.c_int32), ("n_inliers", C.c_int32), ("status", C.c_int32),
                 ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("n_correspondences", C.c_int32), ("n_inliers", C.c_int32), ("status", C.c_int32),
+                ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("R", C.c_double * 9), ("tracked", C.c_int32),
+                ("keyframe_required", C.c_int32), ("keyframe_added", C.c_int32), ("n_entry", C.c_int32),
+                ("n_inherited", C.c_int32), ("vote_best", C.c_int32), ("vote_best_count", C.c_int32)]
 
 
 class BowView(C.Structure):
@@ -439,6 +447,67 @@ class Context:
             res["inliers"] = [inl[k, :c["n_correspondences"]].astype(bool) for k, c in enumerate(cands)]
         return res
 
+    # ---- the keyframe tracking step (rgbd_feature_frontend.cpp:279-400, :544-575) -----------------
+    def kf_visible(self, ids, R, t, focal=(525.0, 525.0), principal=(319.5, 239.5), width=640, height=480):
+        """findBetterReferenceKeyframe's count: per stored keyframe of ids (<= 64) the landmarks that project into a
+        width x height frame seen from the world -> camera pose (R, t) -> (counts [len(ids)], best = position of the first
+        maximum, -1 for an empty list)"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        counts = np.zeros(max(len(ids), 1), np.int32)
+        best = C.c_int(-1)
+        self._chk(self.L.mslam_hip_kf_visible(self._h, _p(ids), len(ids), _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]),
+                                              C.c_double(principal[0]), C.c_double(principal[1]), int(width), int(height),
+                                              _p(counts), C.byref(best)))
+        return counts[:len(ids)].copy(), best.value
+
+    def track(self, desc, xy, depth, ref_id, vote_ids=(), new_id=-1, factor=1.0 / 5000.0, focal=(525.0, 525.0),
+              principal=(319.5, 239.5), ratio=0.7, iterations=100, reprojection_error=5.0, seed=0, rvec=None, tvec=None,
+              min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0, with_pairs=False, with_entry=False,
+              pair_stride=None, entry_capacity=None):
+        """RgbdFeatureFrontend::track against the stored keyframe ref_id in one call: depth filter, match, PnP (guess =
+        rvec, tvec), the reference vote over vote_ids, and — when a keyframe is required and new_id >= 0 — the new entry.
+        -> dict of mslam_hip_track_result's fields (R as [3, 3]) plus vote_counts, and with with_pairs pairs = (from, to)
+        and inliers, with with_entry entry_src / entry_kp.  tracked = 0 is a result here (MSLAM_HIP_E_NO_MODEL)."""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        p2 = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        if len(d) != len(p2):
+            raise MslamHipError(E_INVALID, "track: %d descriptors, %d points" % (len(d), len(p2)))
+        depth = np.ascontiguousarray(depth, np.uint16)
+        h, w = depth.shape
+        ids = np.ascontiguousarray(vote_ids, np.int32).reshape(-1)
+        guess = rvec is not None and tvec is not None
+        r = np.array(rvec if guess else (0, 0, 0), np.float64)
+        t = np.array(tvec if guess else (0, 0, 0), np.float64)
+        K = self.params.max_keypoints
+        stride = (K if pair_stride is None else int(pair_stride)) if with_pairs else 0
+        cap = (K if entry_capacity is None else int(entry_capacity)) if with_entry else 0
+        pf = np.zeros(max(stride, 1), np.int32) if with_pairs else None
+        pt = np.zeros(max(stride, 1), np.int32) if with_pairs else None
+        inl = np.zeros(max(stride, 1), np.uint8) if with_pairs else None
+        es = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        ek = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        counts = np.zeros(max(len(ids), 1), np.int32)
+        out = TrackResult()
+        rc = self.L.mslam_hip_track(self._h, _p(d), _p(p2), len(d), _p(depth), w, h, C.c_float(factor), C.c_double(focal[0]),
+                                    C.c_double(focal[1]), C.c_double(principal[0]), C.c_double(principal[1]), int(ref_id),
+                                    _p(ids), len(ids), C.c_double(ratio), int(iterations), C.c_double(reprojection_error),
+                                    C.c_uint64(seed), int(guess), _p(r), _p(t), int(min_matched_points),
+                                    int(new_keyframe_min_landmarks), int(new_id), C.c_double(z_max), C.byref(out), _p(counts),
+                                    _p(pf), _p(pt), _p(inl), int(stride), _p(es), _p(ek), int(cap))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        res = {k: getattr(out, k) for k, _ in TrackResult._fields_ if k not in ("rvec", "tvec", "R")}
+        res.update(rvec=np.array(out.rvec[:]), tvec=np.array(out.tvec[:]), R=np.array(out.R[:]).reshape(3, 3),
+                   vote_counts=counts[:len(ids)].copy())
+        if with_pairs:
+            res["pairs"] = (pf[:out.n_matches].copy(), pt[:out.n_matches].copy())
+            res["inliers"] = inl[:out.n_correspondences].astype(bool)
+        if with_entry:
+            res["entry_src"], res["entry_kp"] = es[:out.n_entry].copy(), ek[:out.n_entry].copy()
+        return res
+
     # ---- bag of words --------------------------------------------------------------------------
     def bow_load(self, blob):
         b = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob)
@@ -728,6 +797,62 @@ class HipLoopDetector:
         if self._last_entry is None or self._last_entry not in self.reloc._with_landmarks:
             return None, None, 0, []
         return self.reloc._verify(self._last_keypoints, [self._last_entry], camera, valid, rvec, tvec, min_inliers, seed)
+
+
+class HipKeyframeTracker:
+    """The reference front end's loop over frames (RgbdFeatureFrontend::processSensorData, rgbd_feature_frontend.cpp:185-222)
+    on the device-resident keyframe store: initFirstKeyframe on the first frame (:433-470: every keypoint with a valid
+    depth and z <= z_max, at the identity pose), then per frame one Context.track call against the reference keyframe with
+    the previous pose as the guess; the vote's winner becomes the reference (:366-371), a required keyframe is inserted
+    and becomes the reference (:373-397); when tracking fails, Context.relocalize over the stored keyframes names the new
+    reference (:210-217).  Keyframe ids are 0, 1, ...; the vote list and the relocalisation candidates are the most recent
+    64 of them.  Poses are world -> camera (rvec, tvec / R, t)."""
+
+    def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
+                 reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
+                 reloc_min_inliers=60):
+        self.ctx = ctx
+        self.focal, self.principal, self.factor = tuple(focal), tuple(principal), factor
+        self.ratio, self.iterations, self.reprojection_error, self.seed = ratio, iterations, reprojection_error, seed
+        self.min_matched_points, self.new_keyframe_min_landmarks = min_matched_points, new_keyframe_min_landmarks
+        self.z_max, self.reloc_min_inliers = z_max, reloc_min_inliers
+        self.ids = []
+        self.reference = None
+        self.rvec, self.tvec, self.R = np.zeros(3), np.zeros(3), np.eye(3)
+        self.frame = 0
+
+    def processSensorData(self, desc, xy, depth):
+        """one frame: descriptors [n, 32], keypoint coordinates [n, 2], depth image [h, w] u16
+        -> dict(tracked, n_inliers, rvec, tvec, R, reference, keyframe = the id added or -1, relocalized, step)"""
+        seed = self.seed + self.frame
+        self.frame += 1
+        if self.reference is None:
+            xyz, valid = self.ctx.backproject(depth, xy, self.factor, self.focal, self.principal)
+            keep = valid & (xyz[:, 2] <= self.z_max)
+            self.ctx.kf_add(0, np.asarray(desc, np.uint8).reshape(-1, 32)[keep], xyz[keep])   # identity pose: world = camera point
+            self.ids, self.reference = [0], 0
+            return dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
+                        keyframe=0, relocalized=False, step=None)
+        vote = self.ids[-64:]
+        new_id = self.ids[-1] + 1
+        res = self.ctx.track(desc, xy, depth, self.reference, vote, new_id, self.factor, self.focal, self.principal, self.ratio,
+                             self.iterations, self.reprojection_error, seed, self.rvec, self.tvec, self.min_matched_points,
+                             self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
+        out = dict(tracked=bool(res["tracked"]), n_inliers=res["n_inliers"], keyframe=-1, relocalized=False, step=res)
+        if res["tracked"]:
+            self.rvec, self.tvec, self.R = res["rvec"], res["tvec"], res["R"]
+            if res["vote_best"] >= 0:
+                self.reference = vote[res["vote_best"]]
+            if res["keyframe_added"]:
+                self.ids.append(new_id)
+                self.reference = out["keyframe"] = new_id
+        else:
+            reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
+                                        self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
+            if reloc["best"] >= 0:
+                self.reference, out["relocalized"] = vote[reloc["best"]], True
+        out.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
+        return out
 
 
 # ---- harness helper (bench / tests): copy a context-owned device array to the host ------------------

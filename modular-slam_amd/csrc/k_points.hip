@@ -7,7 +7,7 @@
 //   valid    = depth > FLT_EPSILON
 //   X = (x - cx) * z * (1/fx),  Y = (y - cy) * z * (1/fy),  Z = z      (double, left to right; z = (double)depth)
 // One lane per keypoint; pure element-wise f64 arithmetic (products only, so nothing can contract).
-#include "context.hpp"
+#include "reloc.hpp"
 
 #include <cfloat>
 
@@ -43,6 +43,15 @@ __global__ __launch_bounds__(256) void k_backproject(const uint16_t* __restrict_
     xyz[3 * o + 1] = ok ? (y - cam.cy) * z * cam.inv_fy : 0.0;
     xyz[3 * o + 2] = ok ? z : 0.0;
     valid[o] = ok ? 1 : 0;
+}
+
+// for k_track.hip: one frame, device pointers, the launch mslam_hip_backproject makes
+void launch_backproject(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy, double cx,
+                        double cy, const float* d_xy, int n, double* d_xyz, uint8_t* d_valid)
+{
+    const Camera cam{cx, cy, 1.0 / fx, 1.0 / fy, factor};
+    hipLaunchKernelGGL(k_backproject, dim3((n + 255) / 256, 1), dim3(256), 0, s, d_depth, 0ll, width, height, cam, d_xy, 0ll, nullptr, n,
+                       n, d_xyz, d_valid);
 }
 
 } // namespace mslam

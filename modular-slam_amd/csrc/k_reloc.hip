@@ -9,51 +9,21 @@
 // from_stride = 0: the query descriptors are uploaded once and are every pair's train side; k_pnp.hip through
 // pnp_launch_batch).  New here: the store, the gather of the candidates' descriptor blocks into the contiguous layout the
 // matcher addresses, the match -> correspondence gather, and the ranking.  One upload, one synchronisation per call.
-#include "context.hpp"
+#include "reloc.hpp"
 
 #include <algorithm>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 namespace mslam
 {
 
-constexpr int kRelocMaxCand = 64; // the BoW query's own limit (mslam_hip_bow_db_query callers ask for at most 64)
-
-// what k_reloc_rank leaves per candidate in the mapped result block
-struct RelocRes
-{
-    int32_t n_matches, n_corr, n_inliers, status;
-    double R[9], t[3];
-};
-
-struct RelocState
-{
-    // ---- keyframe store: slot s holds up to K landmarks at desc + s * K * 32, world + s * K * 3, count n[s]
-    int slots = 0;
-    uint8_t* d_desc = nullptr;
-    double* d_world = nullptr;
-    int32_t* d_n = nullptr;
-    std::unordered_map<int, int> slot_of; // id -> slot
-    std::vector<int> free_slots;
-    std::vector<int> n_upper;             // per slot: an upper bound of n the host knows (exact for host adds, K for device lifts)
-    // ---- scratch of mslam_hip_relocalize, grown on demand
-    uint8_t* h_up = nullptr;  // page-locked staging of the upload: [desc | xy | valid | slots]
-    uint8_t* d_up = nullptr;
-    size_t up_bytes = 0;
-    uint8_t* d_arena = nullptr; // every per-candidate array of one call
-    size_t arena_bytes = 0;
-    uint8_t *h_res = nullptr, *d_h_res = nullptr; // page-locked, device-mapped: [best | RelocRes[64] | pair_from | pair_to | inliers]
-    size_t res_bytes = 0;
-};
-
 void reloc_destroy(RelocState* r)
 {
     if(!r)
         return;
-    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_up, r->d_arena};
+    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_up, r->d_arena, r->d_vote};
     for(void* p : dev)
         if(p)
             (void)hipFree(p);
@@ -61,15 +31,12 @@ void reloc_destroy(RelocState* r)
         (void)hipHostFree(r->h_up);
     if(r->h_res)
         (void)hipHostFree(r->h_res);
+    if(r->h_vote)
+        (void)hipHostFree(r->h_vote);
     delete r;
 }
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------
-
-struct KfPose
-{
-    double R[9], t[3], z_max;
-};
 
 // One workgroup lifts one frame of the last batch into a store slot: keypoints with a valid depth and z <= z_max, in
 // keypoint order (ballot / popcount compaction, as k_pnp_gather), world = R p + t in f64.
@@ -267,7 +234,12 @@ static int rfail(mslam_hip_ctx* c, int code, const std::string& msg)
     return code;
 }
 
-static int reloc_enter(mslam_hip_ctx* c)
+int mslam::reloc_fail(mslam_hip_ctx* c, int code, const std::string& msg)
+{
+    return rfail(c, code, msg);
+}
+
+int mslam::reloc_enter(mslam_hip_ctx* c)
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
@@ -278,7 +250,7 @@ static int reloc_enter(mslam_hip_ctx* c)
 }
 
 // at least `want` slots; the live entries move with the store
-static int store_reserve(mslam_hip_ctx* c, int want)
+int mslam::store_reserve(mslam_hip_ctx* c, int want)
 {
     RelocState* r = c->reloc;
     if(want <= r->slots)
@@ -326,7 +298,7 @@ static int store_reserve(mslam_hip_ctx* c, int want)
 }
 
 // the slot of `id`: its own when the id exists (the entry is replaced), a free one otherwise
-static int store_slot_for(mslam_hip_ctx* c, int id, int* slot)
+int mslam::store_slot_for(mslam_hip_ctx* c, int id, int* slot)
 {
     RelocState* r = c->reloc;
     auto it = r->slot_of.find(id);
@@ -487,11 +459,13 @@ int mslam_hip_kf_read(mslam_hip_ctx* c, int id, uint8_t* desc, double* world_xyz
     return MSLAM_HIP_OK;
 }
 
-int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint8_t* valid, int n,
-                         const int32_t* cand_ids, int n_cand, double fx, double fy, double cx, double cy, double ratio,
-                         int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess, const double* rvec,
-                         const double* tvec, int min_inliers, mslam_hip_reloc_candidate* out, int* best, int32_t* pair_from,
-                         int32_t* pair_to, uint8_t* inliers, int pair_stride)
+} // extern "C"
+
+int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint8_t* valid, int n, const int32_t* cand_ids,
+                     int n_cand, double fx, double fy, double cx, double cy, double ratio, int iterations, double reprojection_error,
+                     unsigned long long seed, int use_extrinsic_guess, const double* rvec, const double* tvec, int min_inliers,
+                     mslam_hip_reloc_candidate* out, int* best, int32_t* pair_from, int32_t* pair_to, uint8_t* inliers,
+                     int pair_stride, const RelocHooks* hooks)
 {
     int rc = reloc_enter(c);
     if(rc)
@@ -529,7 +503,9 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
     const size_t S = ((size_t)std::max(n_max, 1) + 255) & ~(size_t)255, P = (size_t)n_cand, PS = P * S;
     // ---- upload block: [desc n x 32 | xy n x 8 | slots 64 x 4 | valid n], one copy
     const size_t off_xy = (size_t)n * 32, off_slots = off_xy + (size_t)n * 8, off_valid = off_slots + kRelocMaxCand * 4;
-    const size_t up = off_valid + (valid ? (size_t)n : 0);
+    const size_t off_extra = (off_valid + (valid ? (size_t)n : 0) + 255) & ~(size_t)255; // a hook's own upload, 256-byte aligned
+    const size_t extra_bytes = hooks ? hooks->extra_up_bytes[0] + hooks->extra_up_bytes[1] : 0;
+    const size_t up = extra_bytes ? off_extra + extra_bytes : off_valid + (valid ? (size_t)n : 0);
     if(up > r->up_bytes)
     {
         RCHK(c, hipStreamSynchronize(c->stream));
@@ -555,7 +531,7 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
                  o_dist0 = carve(PS * 4), o_dist1 = carve(PS * 4), o_mfrom = carve(PS * 4), o_mto = carve(PS * 4),
                  o_mcount = carve(P * 4), o_obj = carve(PS * 12), o_img = carve(PS * 8), o_ncorr = carve(P * 4),
                  o_mask = carve(PS), o_hyp = carve(P * (size_t)iterations * 96), o_counts = carve(P * (size_t)iterations * 4),
-                 o_out = carve(P * 128);
+                 o_out = carve(P * 128), o_extra = carve(hooks ? hooks->extra_arena_bytes : 0);
     if(off > r->arena_bytes)
     {
         RCHK(c, hipStreamSynchronize(c->stream));
@@ -568,7 +544,8 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
     }
     // ---- result block (mapped): [best, pad | RelocRes[64] | pair_from P x S | pair_to P x S | inliers P x S]
     const size_t res_head = 16 + kRelocMaxCand * sizeof(RelocRes);
-    const size_t res = res_head + (want_pairs ? PS * 9 : 0);
+    const size_t res_extra = (res_head + (want_pairs ? PS * 9 : 0) + 15) & ~(size_t)15; // a hook's own results
+    const size_t res = hooks && hooks->extra_res_bytes ? res_extra + hooks->extra_res_bytes : res_head + (want_pairs ? PS * 9 : 0);
     if(res > r->res_bytes)
     {
         RCHK(c, hipStreamSynchronize(c->stream));
@@ -586,6 +563,9 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
     std::memcpy(r->h_up + off_slots, slots, P * 4);
     if(valid)
         std::memcpy(r->h_up + off_valid, valid, (size_t)n);
+    for(int k = 0; hooks && k < 2; ++k) // straight from the caller's buffers into the staging block
+        if(hooks->extra_up_bytes[k])
+            std::memcpy(r->h_up + off_extra + (k ? hooks->extra_up_bytes[0] : 0), hooks->extra_up[k], hooks->extra_up_bytes[k]);
     reinterpret_cast<int32_t*>(r->h_res)[0] = -2; // (overwritten by k_reloc_rank; checked after the synchronisation)
     hipStream_t s = c->stream;
     RCHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
@@ -594,6 +574,20 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
     const float* d_xy = reinterpret_cast<const float*>(r->d_up + off_xy);
     const uint8_t* d_valid = valid ? r->d_up + off_valid : nullptr;
     int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o_gcnt);
+    RelocDev dev{};
+    if(hooks)
+    {
+        dev.desc = r->d_up, dev.xy = d_xy, dev.n = n, dev.S = (int)S, dev.valid = d_valid;
+        dev.extra_up = r->d_up + off_extra, dev.extra_arena = A + o_extra;
+        dev.extra_res = r->d_h_res + res_extra, dev.h_extra_res = r->h_res + res_extra;
+        if(hooks->after_upload)
+        {
+            rc = hooks->after_upload(c, hooks->user, dev);
+            if(rc)
+                return rc;
+            d_valid = dev.valid;
+        }
+    }
     {
         StageScope ts(c, "reloc_gather_desc");
         hipLaunchKernelGGL(k_reloc_gather_desc, dim3((unsigned)((2 * S + 255) / 256), (unsigned)P), dim3(256), 0, s, r->d_desc, r->d_n,
@@ -668,6 +662,14 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
                            min_inliers, (int)S, q.from_idx, q.to_idx, d_mask, r->d_h_res);
     }
     RCHK(c, hipGetLastError());
+    if(hooks && hooks->before_sync)
+    {
+        dev.g_cnt = g_cnt, dev.mfrom = q.from_idx, dev.mto = q.to_idx, dev.mcount = q.n_out, dev.ncorr = d_ncorr;
+        dev.mask = d_mask, dev.pnp_out = l.out;
+        rc = hooks->before_sync(c, hooks->user, dev);
+        if(rc)
+            return rc;
+    }
     RCHK(c, hipStreamSynchronize(s));
 
     const int32_t b = reinterpret_cast<const int32_t*>(r->h_res)[0];
@@ -716,4 +718,12 @@ int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy,
     return MSLAM_HIP_OK;
 }
 
-} // extern "C"
+extern "C" int mslam_hip_relocalize(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint8_t* valid, int n,
+                                    const int32_t* cand_ids, int n_cand, double fx, double fy, double cx, double cy, double ratio,
+                                    int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess,
+                                    const double* rvec, const double* tvec, int min_inliers, mslam_hip_reloc_candidate* out,
+                                    int* best, int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride)
+{
+    return reloc_run(c, desc, xy, valid, n, cand_ids, n_cand, fx, fy, cx, cy, ratio, iterations, reprojection_error, seed,
+                     use_extrinsic_guess, rvec, tvec, min_inliers, out, best, pair_from, pair_to, inliers, pair_stride, nullptr);
+}

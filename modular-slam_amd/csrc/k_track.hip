@@ -1,0 +1,571 @@
+// k_track.hip — the keyframe tracking step against the keyframe store: RgbdFeatureFrontend::track
+// (reference rgbd_feature_frontend.cpp:279-400) in one call, and findBetterReferenceKeyframe's count (:544-575 with
+// isVisibleInFrame / projectOnImage, projection.cpp:42-62) on its own.
+//
+// The depth filter is k_backproject on the uploaded depth frame (k_points.hip); matching, ratio test, correspondences and
+// PnP are mslam_hip_relocalize's sequence for one candidate (reloc_run, k_reloc.hip), unchanged.  New here: the vote over
+// the stored world points and the construction of the new keyframe's entry in its store slot.  Both kernels read the PnP
+// kernel's own record on the device (16 doubles: R, t, inliers, -, status, -) and leave at once when the step failed; the
+// pose never visits the host between PnP and them.  All arithmetic is f64, every operation rounded on its own
+// (-ffp-contract=off), in the order written.
+#include "reloc.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+namespace mslam
+{
+
+// what the step's kernels leave in the call's mapped result block, followed by counts[64], entry_src[K], entry_kp[K]
+struct TrackRes
+{
+    int32_t n_entry, n_inherited, vote_best, vote_best_count;
+};
+
+struct VoteCam
+{
+    double fx, fy, cx, cy, w, h; // w, h = (double)(float)width / height: the reference compares against Vector2f's casts
+};
+
+// tracked <=> enough correspondences and a model; ncorr == nullptr (mslam_hip_kf_visible): the record alone decides
+__device__ __forceinline__ bool track_ok(const double* __restrict__ rec, const int32_t* __restrict__ ncorr, int min_matched)
+{
+    return rec[14] == 1.0 && (!ncorr || *ncorr >= min_matched);
+}
+
+// One workgroup per listed keyframe, lanes strided over its landmarks: how many of them project into the frame.
+__global__ __launch_bounds__(256) void k_track_vote(const double* __restrict__ store_world, const int32_t* __restrict__ store_n,
+                                                    const int32_t* __restrict__ slots, int K, const double* __restrict__ rec,
+                                                    const int32_t* __restrict__ ncorr, int min_matched, VoteCam cam,
+                                                    int32_t* __restrict__ counts)
+{
+    __shared__ uint32_t wsum[4];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if(!track_ok(rec, ncorr, min_matched))
+    {
+        if(tid == 0)
+            counts[k] = 0;
+        return;
+    }
+    const int slot = slots[k];
+    const int n = min(max(store_n[slot], 0), K);
+    const double* world = store_world + (size_t)slot * K * 3;
+    uint32_t mine = 0; // (wave-uniform: every lane adds the same popcount)
+    for(int base = 0; base < n; base += 256)
+    {
+        const int i = base + tid;
+        bool vis = false;
+        if(i < n)
+        {
+            const double X = world[3 * (size_t)i], Y = world[3 * (size_t)i + 1], Z = world[3 * (size_t)i + 2];
+            const double c0 = ((rec[0] * X + rec[1] * Y) + rec[2] * Z) + rec[9];
+            const double c1 = ((rec[3] * X + rec[4] * Y) + rec[5] * Z) + rec[10];
+            const double c2 = ((rec[6] * X + rec[7] * Y) + rec[8] * Z) + rec[11];
+            const double u = (c0 / c2) * cam.fx + cam.cx, v = (c1 / c2) * cam.fy + cam.cy;
+            vis = u >= 0.0 && u < cam.w && v >= 0.0 && v < cam.h && c2 > 0.0;
+        }
+        mine += (uint32_t)__popcll(__ballot(vis));
+    }
+    if(lane == 0)
+        wsum[wave] = mine;
+    __syncthreads();
+    if(tid == 0)
+        counts[k] = (int32_t)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+}
+
+// One wave: the first maximum in list order (max-butterfly on (count + 1) << 6 | 63 - k, as k_reloc_rank), and the
+// counts; everything lands in mapped host memory.
+__global__ __launch_bounds__(64) void k_track_vote_pick(const int32_t* __restrict__ counts, int n_vote, int32_t* __restrict__ h_best,
+                                                        int32_t* __restrict__ h_counts)
+{
+    const int k = threadIdx.x;
+    const bool live = k < n_vote;
+    const int cnt = live ? counts[k] : 0;
+    if(live)
+        h_counts[k] = cnt;
+    int key = live ? ((cnt + 1) << 6) | (63 - k) : 0;
+    for(int o = 32; o > 0; o >>= 1)
+        key = max(key, __shfl_xor(key, o));
+    if(k == 0)
+    {
+        h_best[0] = key ? 63 - (key & 63) : -1;
+        h_best[1] = key ? (key >> 6) - 1 : 0;
+    }
+}
+
+struct KeyframeArgs
+{
+    // the step's outputs for the one candidate (row 0)
+    const int32_t *mfrom, *mto, *mcount, *g_cnt, *ncorr;
+    const uint8_t* mask;
+    const double* rec;
+    int min_matched, kf_min_landmarks;
+    // the query
+    const uint8_t* desc;
+    const double* xyz;
+    const uint8_t* valid;
+    int nq, S;
+    double z_max;
+    // the store: the reference entry's world points, the new entry's slot
+    const double* ref_world;
+    uint8_t* out_desc;
+    double* out_world;
+    int32_t* out_n;
+    int cap;
+    // mapped host block
+    TrackRes* h_res;
+    int32_t *h_src, *h_kp;
+};
+
+__device__ __forceinline__ void copy_desc(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
+{
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = s[0];
+    d[1] = s[1];
+}
+
+// One workgroup builds the new keyframe's entry in its store slot.  Part A: the inlier correspondences in correspondence
+// order, with the reference entry's world points copied bit for bit.  Part B: every keypoint no correspondence used, with a
+// valid depth and z <= z_max, in keypoint order, lifted with world = R^T (p - t).  Ordered ballot / prefix compaction as
+// k_kf_lift.  nq <= 65536 (the host checks nq <= cap <= 65535).  There is one match per reference landmark, so two
+// landmarks can name the same keypoint and part A then lists it twice: A and B together can exceed nq, and every store
+// is guarded by o < cap (the entry is cut at cap, part A first).
+__global__ __launch_bounds__(256) void k_track_keyframe(KeyframeArgs a)
+{
+    __shared__ uint32_t used[2048];
+    __shared__ uint32_t wsum[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* rec = a.rec;
+    if(!track_ok(rec, a.ncorr, a.min_matched) || (int)rec[12] >= a.kf_min_landmarks)
+        return; // not tracked, or no keyframe required: the slot and the (pre-zeroed) result stay as they are
+    for(int i = tid; i < 2048; i += 256)
+        used[i] = 0;
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int m = min(max(a.mcount[0], 0), a.S), n_to = a.g_cnt[0];
+    uint32_t run_c = 0, run_a = 0; // correspondences / part A entries so far
+    for(int base = 0; base < m; base += 256)
+    {
+        const int i = base + tid;
+        int from = 0, to = 0;
+        bool ok = false; // k_reloc_corr's own condition: the j-th `ok` match is correspondence j
+        if(i < m)
+        {
+            from = a.mfrom[i], to = a.mto[i];
+            ok = (unsigned)from < (unsigned)a.nq && (unsigned)to < (unsigned)n_to && a.valid[from] != 0;
+        }
+        const unsigned long long bc = __ballot(ok);
+        if(lane == 0)
+            wsum[0][wave] = (uint32_t)__popcll(bc);
+        __syncthreads();
+        uint32_t pre_c = 0, tot_c = 0;
+        for(int k = 0; k < 4; ++k)
+        {
+            pre_c += k < wave ? wsum[0][k] : 0;
+            tot_c += wsum[0][k];
+        }
+        bool inl = false;
+        if(ok)
+        {
+            atomicOr(&used[from >> 5], 1u << (from & 31)); // used = matched with a valid depth, inlier or not (:314-334)
+            inl = a.mask[run_c + pre_c + (uint32_t)__popcll(bc & below)] != 0;
+        }
+        const unsigned long long ba = __ballot(inl);
+        if(lane == 0)
+            wsum[1][wave] = (uint32_t)__popcll(ba);
+        __syncthreads();
+        uint32_t pre_a = 0, tot_a = 0;
+        for(int k = 0; k < 4; ++k)
+        {
+            pre_a += k < wave ? wsum[1][k] : 0;
+            tot_a += wsum[1][k];
+        }
+        const size_t o = run_a + pre_a + (uint32_t)__popcll(ba & below);
+        if(inl && o < (size_t)a.cap)
+        {
+            copy_desc(a.desc + (size_t)from * 32, a.out_desc + o * 32);
+            const double* P = a.ref_world + (size_t)to * 3;
+            a.out_world[o * 3] = P[0], a.out_world[o * 3 + 1] = P[1], a.out_world[o * 3 + 2] = P[2];
+            a.h_src[o] = to, a.h_kp[o] = from;
+        }
+        run_c += tot_c;
+        run_a += tot_a;
+        __syncthreads(); // wsum is rewritten by the next round; after the last round: the bitmap is complete
+    }
+    const uint32_t n_a = min(run_a, (uint32_t)a.cap);
+    const double t0 = rec[9], t1 = rec[10], t2 = rec[11];
+    uint32_t run = n_a;
+    for(int base = 0; base < a.nq; base += 256)
+    {
+        const int i = base + tid;
+        bool ok = false;
+        double x = 0, y = 0, z = 0;
+        if(i < a.nq && !((used[i >> 5] >> (i & 31)) & 1u) && a.valid[i] != 0)
+        {
+            x = a.xyz[3 * (size_t)i], y = a.xyz[3 * (size_t)i + 1], z = a.xyz[3 * (size_t)i + 2];
+            ok = z <= a.z_max;
+        }
+        const unsigned long long b = __ballot(ok);
+        if(lane == 0)
+            wsum[0][wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for(int k = 0; k < 4; ++k)
+        {
+            pre += k < wave ? wsum[0][k] : 0;
+            tot += wsum[0][k];
+        }
+        const size_t o = run + pre + (uint32_t)__popcll(b & below);
+        if(ok && o < (size_t)a.cap)
+        {
+            copy_desc(a.desc + (size_t)i * 32, a.out_desc + o * 32);
+            const double dx = x - t0, dy = y - t1, dz = z - t2;
+            a.out_world[o * 3] = (rec[0] * dx + rec[3] * dy) + rec[6] * dz; // R^T (p - t): column r of R
+            a.out_world[o * 3 + 1] = (rec[1] * dx + rec[4] * dy) + rec[7] * dz;
+            a.out_world[o * 3 + 2] = (rec[2] * dx + rec[5] * dy) + rec[8] * dz;
+            a.h_src[o] = -1, a.h_kp[o] = i;
+        }
+        run += tot;
+        __syncthreads();
+    }
+    if(tid == 0)
+    {
+        const int32_t n_entry = (int32_t)min(run, (uint32_t)a.cap);
+        *a.out_n = n_entry;
+        a.h_res->n_entry = n_entry;
+        a.h_res->n_inherited = (int32_t)n_a;
+    }
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+#define TCHK(c, call)                                                                                                  \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t e_ = (call);                                                                                        \
+        if(e_ != hipSuccess)                                                                                           \
+        {                                                                                                              \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
+            return MSLAM_HIP_E_RUNTIME;                                                                                \
+        }                                                                                                              \
+    } while(0)
+
+static VoteCam vote_cam(double fx, double fy, double cx, double cy, int width, int height)
+{
+    return VoteCam{fx, fy, cx, cy, (double)(float)width, (double)(float)height};
+}
+
+namespace
+{
+// one mslam_hip_track call: what its two hooks into the relocalize sequence need
+struct TrackCall
+{
+    const uint16_t* depth;
+    int width, height;
+    float factor;
+    double fx, fy, cx, cy;
+    int n, n_vote, ref_slot, new_slot;
+    int min_matched, kf_min_landmarks;
+    double z_max;
+    size_t off_depth;              // in the extra upload block: [vote slots 64 x i32 | depth]
+    size_t off_valid, off_counts;  // in the extra arena: [xyz n x 3 f64 | valid n | vote counts 64 x i32]
+    double* d_xyz = nullptr;
+    const uint8_t* d_valid = nullptr;
+    uint8_t* h_res = nullptr;      // host address of the extra result block, once the kernels are enqueued
+};
+
+int track_after_upload(mslam_hip_ctx* c, void* user, RelocDev& d)
+{
+    TrackCall* t = static_cast<TrackCall*>(user);
+    t->d_xyz = reinterpret_cast<double*>(d.extra_arena);
+    uint8_t* valid = d.extra_arena + t->off_valid;
+    {
+        StageScope ts(c, "backproject");
+        launch_backproject(c->stream, reinterpret_cast<const uint16_t*>(d.extra_up + t->off_depth), t->width, t->height, t->factor,
+                           t->fx, t->fy, t->cx, t->cy, d.xy, t->n, t->d_xyz, valid);
+    }
+    TCHK(c, hipGetLastError());
+    d.valid = t->d_valid = valid; // the depth filter of :317-334 is the matcher's mask
+    return MSLAM_HIP_OK;
+}
+
+int track_before_sync(mslam_hip_ctx* c, void* user, const RelocDev& d)
+{
+    TrackCall* t = static_cast<TrackCall*>(user);
+    RelocState* r = c->reloc;
+    const int K = c->p.max_keypoints;
+    TrackRes* res = reinterpret_cast<TrackRes*>(d.extra_res);
+    int32_t* res_counts = reinterpret_cast<int32_t*>(d.extra_res + sizeof(TrackRes));
+    // (host stores into the mapped block before the kernels that may overwrite it are enqueued)
+    TrackRes* h = reinterpret_cast<TrackRes*>(d.h_extra_res);
+    *h = TrackRes{0, 0, -1, 0};
+    std::memset(d.h_extra_res + sizeof(TrackRes), 0, kRelocMaxCand * 4);
+    if(t->n_vote > 0)
+    {
+        int32_t* counts = reinterpret_cast<int32_t*>(d.extra_arena + t->off_counts);
+        {
+            StageScope ts(c, "track_vote");
+            hipLaunchKernelGGL(k_track_vote, dim3((unsigned)t->n_vote), dim3(256), 0, c->stream, r->d_world, r->d_n,
+                               reinterpret_cast<const int32_t*>(d.extra_up), K, d.pnp_out, d.ncorr, t->min_matched,
+                               vote_cam(t->fx, t->fy, t->cx, t->cy, t->width, t->height), counts);
+        }
+        {
+            StageScope ts(c, "track_vote_pick");
+            hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, c->stream, counts, t->n_vote, &res->vote_best, res_counts);
+        }
+    }
+    if(t->new_slot >= 0)
+    {
+        KeyframeArgs a{};
+        a.mfrom = d.mfrom, a.mto = d.mto, a.mcount = d.mcount, a.g_cnt = d.g_cnt, a.ncorr = d.ncorr;
+        a.mask = d.mask, a.rec = d.pnp_out;
+        a.min_matched = t->min_matched, a.kf_min_landmarks = t->kf_min_landmarks;
+        a.desc = d.desc, a.xyz = t->d_xyz, a.valid = t->d_valid, a.nq = t->n, a.S = d.S, a.z_max = t->z_max;
+        a.ref_world = r->d_world + (size_t)t->ref_slot * K * 3;
+        a.out_desc = r->d_desc + (size_t)t->new_slot * K * 32;
+        a.out_world = r->d_world + (size_t)t->new_slot * K * 3;
+        a.out_n = r->d_n + t->new_slot;
+        a.cap = K;
+        a.h_res = res;
+        a.h_src = res_counts + kRelocMaxCand;
+        a.h_kp = a.h_src + K;
+        StageScope ts(c, "track_keyframe");
+        hipLaunchKernelGGL(k_track_keyframe, dim3(1), dim3(256), 0, c->stream, a);
+    }
+    TCHK(c, hipGetLastError());
+    t->h_res = d.h_extra_res;
+    return MSLAM_HIP_OK;
+}
+} // namespace
+
+extern "C" {
+
+int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const double* R, const double* t, double fx, double fy,
+                         double cx, double cy, int width, int height, int32_t* counts, int* best)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(best)
+        *best = -1;
+    if(!best || n_ids < 0 || n_ids > kRelocMaxCand || (n_ids > 0 && (!ids || !counts)) || !R || !t || width <= 0 || height <= 0)
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_visible: bad argument (at most 64 ids)");
+    RelocState* r = c->reloc;
+    // upload block: [slots 64 x i32 | pose record 16 x f64]; device counts behind it
+    struct
+    {
+        int32_t slots[kRelocMaxCand];
+        double rec[16];
+    } up{};
+    for(int k = 0; k < n_ids; ++k)
+    {
+        auto it = r->slot_of.find(ids[k]);
+        if(it == r->slot_of.end())
+            return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_visible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
+        up.slots[k] = it->second;
+    }
+    if(n_ids == 0)
+        return MSLAM_HIP_OK;
+    std::memcpy(up.rec, R, 9 * sizeof(double));
+    std::memcpy(up.rec + 9, t, 3 * sizeof(double));
+    up.rec[14] = 1.0; // (the PnP record's "model found")
+    if(!r->d_vote || !r->h_vote || !r->d_h_vote)
+    {
+        // all three or none: a call after a failed allocation starts over
+        if(r->d_vote)
+            (void)hipFree(r->d_vote);
+        if(r->h_vote)
+            (void)hipHostFree(r->h_vote);
+        r->d_vote = r->h_vote = r->d_h_vote = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&r->d_vote), sizeof(up) + kRelocMaxCand * 4);
+        if(e == hipSuccess)
+            e = hipHostMalloc(reinterpret_cast<void**>(&r->h_vote), 16 + kRelocMaxCand * 4, hipHostMallocMapped);
+        if(e == hipSuccess)
+            e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_vote), r->h_vote, 0);
+        if(e != hipSuccess)
+        {
+            if(r->d_vote)
+                (void)hipFree(r->d_vote);
+            if(r->h_vote)
+                (void)hipHostFree(r->h_vote);
+            r->d_vote = r->h_vote = r->d_h_vote = nullptr;
+            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, std::string("kf_visible: ") + hipGetErrorString(e));
+        }
+    }
+    int32_t* h = reinterpret_cast<int32_t*>(r->h_vote);
+    h[0] = -2; // (overwritten by k_track_vote_pick; checked after the synchronisation)
+    hipStream_t s = c->stream;
+    TCHK(c, hipMemcpyAsync(r->d_vote, &up, sizeof(up), hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
+    int32_t* d_counts = reinterpret_cast<int32_t*>(r->d_vote + sizeof(up));
+    {
+        StageScope ts(c, "track_vote");
+        hipLaunchKernelGGL(k_track_vote, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_world, r->d_n,
+                           reinterpret_cast<const int32_t*>(r->d_vote), c->p.max_keypoints,
+                           reinterpret_cast<const double*>(r->d_vote + sizeof(up.slots)), nullptr, 0,
+                           vote_cam(fx, fy, cx, cy, width, height), d_counts);
+    }
+    {
+        StageScope ts(c, "track_vote_pick");
+        hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, s, d_counts, n_ids, reinterpret_cast<int32_t*>(r->d_h_vote),
+                           reinterpret_cast<int32_t*>(r->d_h_vote + 16));
+    }
+    TCHK(c, hipGetLastError());
+    TCHK(c, hipStreamSynchronize(s));
+    if(h[0] < 0 || h[0] >= n_ids)
+        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_visible: the vote kernel left no result");
+    std::memcpy(counts, r->h_vote + 16, (size_t)n_ids * 4);
+    *best = h[0];
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int n, const uint16_t* depth, int width, int height,
+                    float factor, double fx, double fy, double cx, double cy, int ref_id, const int32_t* vote_ids, int n_vote,
+                    double ratio, int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess,
+                    const double* rvec, const double* tvec, int min_matched_points, int new_keyframe_min_landmarks, int new_id,
+                    double z_max, mslam_hip_track_result* out, int32_t* vote_counts, int32_t* pair_from, int32_t* pair_to,
+                    uint8_t* inliers, int pair_stride, int32_t* entry_src, int32_t* entry_kp, int entry_capacity)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(out)
+    {
+        *out = mslam_hip_track_result{};
+        out->vote_best = -1;
+    }
+    if(!out || !depth || width <= 0 || height <= 0 || n < 0 || n_vote < 0 || n_vote > kRelocMaxCand || (n_vote > 0 && !vote_ids) ||
+       !(z_max == z_max) || ((entry_src || entry_kp) && entry_capacity < 0))
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: bad argument (at most 64 vote ids)");
+    const int K = c->p.max_keypoints;
+    if(n > K)
+        return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "track: more query keypoints than the context's max_keypoints (a store entry's capacity)");
+    RelocState* r = c->reloc;
+    struct
+    {
+        int32_t slots[kRelocMaxCand];
+    } vote{};
+    auto ref = r->slot_of.find(ref_id);
+    if(ref == r->slot_of.end())
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: reference id " + std::to_string(ref_id) + " is not in the keyframe store");
+    bool collides = new_id >= 0 && new_id == ref_id;
+    for(int k = 0; k < n_vote; ++k)
+    {
+        auto it = r->slot_of.find(vote_ids[k]);
+        if(it == r->slot_of.end())
+            return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: vote id " + std::to_string(vote_ids[k]) + " is not in the keyframe store");
+        vote.slots[k] = it->second;
+        collides = collides || (new_id >= 0 && vote_ids[k] == new_id);
+    }
+    if(collides)
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: new_id names the reference keyframe or a keyframe of the vote list");
+    TrackCall tc{};
+    tc.ref_slot = ref->second;
+    // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
+    tc.new_slot = -1;
+    const bool existed = new_id >= 0 && r->slot_of.count(new_id) != 0;
+    if(new_id >= 0)
+    {
+        rc = store_slot_for(c, new_id, &tc.new_slot);
+        if(rc)
+            return rc;
+    }
+    auto release = [&]() { // a slot reserved for new_id that received no entry
+        if(new_id >= 0 && !existed)
+        {
+            r->slot_of.erase(new_id);
+            r->free_slots.push_back(tc.new_slot);
+        }
+    };
+    tc.depth = depth, tc.width = width, tc.height = height, tc.factor = factor;
+    tc.fx = fx, tc.fy = fy, tc.cx = cx, tc.cy = cy;
+    tc.n = n, tc.n_vote = n_vote;
+    tc.min_matched = min_matched_points, tc.kf_min_landmarks = new_keyframe_min_landmarks;
+    tc.z_max = z_max;
+    // extra upload: [vote slots | depth], copied by reloc_run from these two spans into its page-locked staging block
+    const size_t npx = (size_t)width * height;
+    tc.off_depth = sizeof(vote);
+    tc.off_valid = (size_t)std::max(n, 1) * 24;
+    tc.off_counts = (tc.off_valid + (size_t)std::max(n, 1) + 255) & ~(size_t)255;
+    RelocHooks hooks{};
+    hooks.extra_up[0] = &vote, hooks.extra_up_bytes[0] = sizeof(vote);
+    hooks.extra_up[1] = depth, hooks.extra_up_bytes[1] = npx * 2;
+    hooks.extra_arena_bytes = tc.off_counts + kRelocMaxCand * 4;
+    hooks.extra_res_bytes = sizeof(TrackRes) + kRelocMaxCand * 4 + (size_t)K * 8;
+    hooks.user = &tc;
+    hooks.after_upload = track_after_upload;
+    hooks.before_sync = track_before_sync;
+    mslam_hip_reloc_candidate cand{};
+    int best = -1;
+    const int32_t ref_id32 = ref_id;
+    rc = reloc_run(c, desc, xy, nullptr, n, &ref_id32, 1, fx, fy, cx, cy, ratio, iterations, reprojection_error, seed,
+                   use_extrinsic_guess, rvec, tvec, 0, &cand, &best, pair_from, pair_to, inliers, pair_stride, &hooks);
+    if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL && rc != MSLAM_HIP_E_CAPACITY)
+    {
+        // the sequence failed part-way: what it enqueued may still run and may write the slot.  Wait for it before the slot
+        // goes back to the free list (keeping reloc_run's message); an entry that existed under new_id may have been
+        // replaced, so all the host still knows about its size is the capacity
+        const std::string msg = c->err;
+        (void)hipStreamSynchronize(c->stream);
+        c->err = msg;
+        if(existed)
+            r->n_upper[(size_t)tc.new_slot] = K;
+        release();
+        return rc;
+    }
+    out->n_matches = cand.n_matches, out->n_correspondences = cand.n_correspondences;
+    out->n_inliers = cand.n_inliers, out->status = cand.status;
+    std::memcpy(out->rvec, cand.rvec, sizeof(cand.rvec));
+    std::memcpy(out->tvec, cand.tvec, sizeof(cand.tvec));
+    if(!tc.h_res)
+    {
+        // nothing ran (fewer than 2 query keypoints): no matches, not tracked
+        release();
+        return rc;
+    }
+    if(cand.status)
+        std::memcpy(out->R, reinterpret_cast<const RelocRes*>(r->h_res + 16)[0].R, sizeof(out->R));
+    out->tracked = cand.status && cand.n_correspondences >= min_matched_points ? 1 : 0;
+    out->keyframe_required = out->tracked && cand.n_inliers < new_keyframe_min_landmarks ? 1 : 0;
+    out->keyframe_added = out->keyframe_required && new_id >= 0 ? 1 : 0;
+    const TrackRes* tr = reinterpret_cast<const TrackRes*>(tc.h_res);
+    const int32_t* h_counts = reinterpret_cast<const int32_t*>(tc.h_res + sizeof(TrackRes));
+    if(tr->n_entry < 0 || tr->n_entry > K || tr->n_inherited < 0 || tr->n_inherited > tr->n_entry || tr->vote_best < -1 ||
+       tr->vote_best >= std::max(n_vote, 1) || (!out->keyframe_added && tr->n_entry != 0))
+    {
+        if(existed)
+            r->n_upper[(size_t)tc.new_slot] = K;
+        release();
+        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "track: the kernels reported impossible counts");
+    }
+    if(out->keyframe_added)
+    {
+        out->n_entry = tr->n_entry, out->n_inherited = tr->n_inherited;
+        r->n_upper[(size_t)tc.new_slot] = tr->n_entry;
+    }
+    else
+        release();
+    if(out->tracked && n_vote > 0)
+        out->vote_best = tr->vote_best, out->vote_best_count = tr->vote_best_count;
+    if(vote_counts && n_vote > 0)
+        std::memcpy(vote_counts, h_counts, (size_t)n_vote * 4);
+    if(rc == MSLAM_HIP_E_CAPACITY)
+        return rc; // (the pair rows; reloc_run left the message)
+    if(out->keyframe_added && (entry_src || entry_kp))
+    {
+        if(out->n_entry > entry_capacity)
+            return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "track: the new entry has more landmarks than entry_capacity");
+        if(entry_src)
+            std::memcpy(entry_src, h_counts + kRelocMaxCand, (size_t)out->n_entry * 4);
+        if(entry_kp)
+            std::memcpy(entry_kp, h_counts + kRelocMaxCand + K, (size_t)out->n_entry * 4);
+    }
+    if(!out->tracked)
+        return reloc_fail(c, MSLAM_HIP_E_NO_MODEL, "track: fewer than min_matched_points correspondences, or no model");
+    return MSLAM_HIP_OK;
+}
+
+} // extern "C"

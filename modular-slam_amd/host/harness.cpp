@@ -17,6 +17,11 @@
 //                                    the verified relocalisation: addKeyframe + addKeyframeLandmarks per keyframe of the scene,
 //                                    relocalizePose(query), then the query fed as a keyframe and detectLoopVerified,
 //                                    then removeKeyframe(winner) and relocalizePose again
+//        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene>
+//                                    the frontend's loop over a recorded sequence (processSensorData, :185-222) on
+//                                    IKeyframeTracker: initFirstKeyframe, then per frame trackKeyframe against the reference
+//                                    keyframe with the previous pose as the guess; the vote's winner becomes the reference,
+//                                    an inserted keyframe too; relocalizePose when tracking fails.  One line per frame.
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -190,6 +195,115 @@ int main(int argc, char** argv)
             {
                 relocalizer->removeKeyframe(first.keyframe);
                 print("after-remove", verified->relocalizePose(query, cp));
+            }
+            return 0;
+        }
+        if(argc == 5 && std::strcmp(argv[2], "--track") == 0)
+        {
+            // scene file, little-endian: 'MSTK', i32 version = 1, n_frames, width, height; f64 fx, fy, cx, cy; f32 factor; i32 seed,
+            // min_matched_points, new_keyframe_min_landmarks; f64 z_max; per frame: i32 n, n x 32 descriptor bytes, n x 2 f32
+            // keypoint coordinates, height x width u16 depth
+            setenv("MSLAM_ORB_VOCABULARY", argv[3], 1);
+            auto makeReloc = mslam::loadFactoryMethod<mslam::IOrbRelocalizer>(argv[1], "hipOrbRelocalizerFactory");
+            std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
+            auto* tracker = dynamic_cast<mslam::IKeyframeTracker*>(relocalizer.get());
+            auto* verified = dynamic_cast<mslam::IVerifiedRelocalizer*>(relocalizer.get());
+            if(!tracker || !verified)
+            {
+                std::fprintf(stderr, "the plugin does not offer the keyframe tracking step\n");
+                return 6;
+            }
+            std::ifstream in(argv[4], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[4] = {0, 0, 0, 0}, par[3] = {0, 0, 0};
+            double cam[4], zMax = 0;
+            float factor = 0;
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            in.read(reinterpret_cast<char*>(cam), sizeof(cam));
+            in.read(reinterpret_cast<char*>(&factor), 4);
+            in.read(reinterpret_cast<char*>(par), sizeof(par));
+            if(!in.read(reinterpret_cast<char*>(&zMax), 8) || std::memcmp(magic, "MSTK", 4) != 0 || head[0] != 1 || head[2] <= 0 || head[3] <= 0)
+            {
+                std::fprintf(stderr, "%s is not a tracking scene\n", argv[4]);
+                return 5;
+            }
+            const int nFrames = head[1], width = head[2], height = head[3];
+            mslam::CameraParameters cp;
+            cp.focal = mslam::Vector2(cam[0], cam[1]);
+            cp.principalPoint = mslam::Vector2(cam[2], cam[3]);
+            cp.factor = factor;
+            mslam::KeyframeTrackOptions opt;
+            opt.minMatchedPoints = par[1], opt.newKeyframeMinLandmarks = par[2], opt.zMax = zMax;
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::vector<std::shared_ptr<Kf>> keyframes; // in insertion order: the vote's list (its most recent 64)
+            std::shared_ptr<Kf> reference;
+            double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+            std::vector<std::uint16_t> depth(static_cast<std::size_t>(width) * height);
+            for(int f = 0; f < nFrames; ++f)
+            {
+                std::int32_t n = 0;
+                in.read(reinterpret_cast<char*>(&n), 4);
+                std::vector<mslam::OrbKeypoint> kps(static_cast<std::size_t>(n > 0 ? n : 0));
+                for(std::size_t i = 0; i < kps.size(); ++i)
+                {
+                    kps[i].keypoint.id = i;
+                    in.read(reinterpret_cast<char*>(kps[i].descriptor.data()), 32);
+                }
+                for(auto& k : kps)
+                {
+                    float xy[2];
+                    in.read(reinterpret_cast<char*>(xy), sizeof(xy));
+                    k.keypoint.coordinates = mslam::Vector2(xy[0], xy[1]);
+                }
+                if(!in.read(reinterpret_cast<char*>(depth.data()), static_cast<std::streamsize>(depth.size() * 2)))
+                {
+                    std::fprintf(stderr, "cannot read frame %d of %s\n", f, argv[4]);
+                    return 5;
+                }
+                int tracked = 1, inliers = 0, relocalized = 0;
+                long long added = -1;
+                if(!reference)
+                {
+                    auto kf = std::make_shared<Kf>();
+                    kf->id = 0;
+                    tracker->initFirstKeyframe(kf, kps, depth.data(), width, height, cp, zMax);
+                    keyframes.push_back(kf);
+                    reference = kf;
+                    added = 0;
+                }
+                else
+                {
+                    const std::size_t first = keyframes.size() > 64 ? keyframes.size() - 64 : 0;
+                    const std::vector<std::shared_ptr<Kf>> neighbours(keyframes.begin() + static_cast<std::ptrdiff_t>(first), keyframes.end());
+                    auto kf = std::make_shared<Kf>();
+                    kf->id = keyframes.back()->id + 1;
+                    opt.seed = static_cast<std::uint64_t>(par[0]) + static_cast<std::uint64_t>(f);
+                    const auto r = tracker->trackKeyframe(kps, depth.data(), width, height, cp, reference, neighbours, rvec, tvec, kf, opt);
+                    tracked = r.tracked ? 1 : 0, inliers = r.inliers;
+                    if(r.tracked)
+                    {
+                        std::memcpy(rvec, r.rvec, sizeof(rvec));
+                        std::memcpy(tvec, r.tvec, sizeof(tvec));
+                        if(r.bestReference)
+                            reference = r.bestReference; // (:366-371)
+                        if(r.keyframeAdded)
+                        {
+                            keyframes.push_back(kf);
+                            reference = kf; // (:395-396)
+                            added = static_cast<long long>(kf->id);
+                        }
+                    }
+                    else if(auto found = verified->relocalizePose(kps, cp).keyframe) // (:210-217)
+                    {
+                        reference = found;
+                        relocalized = 1;
+                    }
+                }
+                std::printf("track frame %d tracked %d inliers %d rvec %.17g %.17g %.17g tvec %.17g %.17g %.17g reference %llu keyframe %lld "
+                            "relocalized %d\n",
+                            f, tracked, inliers, rvec[0], rvec[1], rvec[2], tvec[0], tvec[1], tvec[2],
+                            (unsigned long long)reference->id, added, relocalized);
             }
             return 0;
         }

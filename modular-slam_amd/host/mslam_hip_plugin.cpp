@@ -247,10 +247,10 @@ class BowDatabase
         return out;
     }
 
-    void addKeyframe(KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints)
+    int addKeyframe(KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints) // -> the BoW entry id, -1: not fed
     {
         if(keypoints.empty()) // the reference asserts non-empty (orb_relocalizer.cpp:42)
-            return;
+            return -1;
         // loop candidate = best earlier keyframe for the one being added
         const auto candidates = relocalize(keypoints);
         lastLoop = candidates.empty() ? nullptr : candidates.front();
@@ -260,6 +260,7 @@ class BowDatabase
         if(rc != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_bow_db_add", rc);
         entryToKeyframe[entry] = std::move(keyframe);
+        return entry;
     }
 
     void removeKeyframe(const KeyframePtr& keyframe)
@@ -271,9 +272,11 @@ class BowDatabase
                 const int rc = mslam_hip_bow_db_remove(ctx.h, it->first); // never scored again
                 if(rc != MSLAM_HIP_OK)
                     raise(ctx.h, "mslam_hip_bow_db_remove", rc);
-                if(withLandmarks.erase(it->first)) // its landmarks leave the keyframe store with it
+                auto lm = storeId.find(it->first);
+                if(lm != storeId.end()) // its landmarks leave the keyframe store with it
                 {
-                    const int rk = mslam_hip_kf_remove(ctx.h, it->first);
+                    const int rk = mslam_hip_kf_remove(ctx.h, lm->second);
+                    storeId.erase(lm);
                     if(rk != MSLAM_HIP_OK)
                         raise(ctx.h, "mslam_hip_kf_remove", rk);
                 }
@@ -301,11 +304,11 @@ class BowDatabase
                 std::vector<double> world(3 * worldPoints.size());
                 for(std::size_t i = 0; i < worldPoints.size(); ++i)
                     world[3 * i] = worldPoints[i].x(), world[3 * i + 1] = worldPoints[i].y(), world[3 * i + 2] = worldPoints[i].z();
-                // the store's id is the BoW entry id: one id names both
+                // the store's id is the BoW entry id: one id names both (a keyframe track() inserted has an id of its own)
                 const int rc = mslam_hip_kf_add(ctx.h, e.first, desc.data(), world.data(), static_cast<int>(keypoints.size()));
                 if(rc != MSLAM_HIP_OK)
                     raise(ctx.h, "mslam_hip_kf_add", rc);
-                withLandmarks.insert(e.first);
+                storeId[e.first] = e.first;
                 return;
             }
         throw std::runtime_error("addKeyframeLandmarks: the keyframe has not been added");
@@ -328,7 +331,7 @@ class BowDatabase
             if(entryToKeyframe.count(ids[i]))
             {
                 ++taken; // the same four relocalize() returns
-                if(withLandmarks.count(ids[i]))
+                if(storeId.count(ids[i]))
                     entries.push_back(ids[i]);
             }
         return verify(keypoints, entries, camera, minInliers);
@@ -338,12 +341,128 @@ class BowDatabase
     {
         std::vector<std::int32_t> entries;
         for(const auto& e : entryToKeyframe)
-            if(lastLoop && e.second == lastLoop && withLandmarks.count(e.first))
+            if(lastLoop && e.second == lastLoop && storeId.count(e.first))
                 entries.push_back(e.first);
         return verify(lastFed, entries, camera, minInliers);
     }
 
+    // ---- extension: the tracking step on the stored landmarks (mslam_hip_track, mslam_hip_kf_visible) ----
+    int initFirstKeyframe(const KeyframePtr& keyframe, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width,
+                          int height, const CameraParameters& camera, double zMax)
+    {
+        const int n = static_cast<int>(keypoints.size());
+        gather(keypoints);
+        std::vector<double> xyz(3 * keypoints.size() + 3);
+        std::vector<std::uint8_t> valid(keypoints.size() + 1);
+        const int rb = mslam_hip_backproject(ctx.h, depth, width, height, camera.factor, camera.focal.x(), camera.focal.y(),
+                                             camera.principalPoint.x(), camera.principalPoint.y(), xy.data(), n, xyz.data(), valid.data());
+        if(rb != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_backproject", rb);
+        const int entry = addKeyframe(keyframe, keypoints); // (:176; gathers `desc` again: the same bytes)
+        if(entry < 0)
+            throw std::runtime_error("initFirstKeyframe: no keypoints");
+        std::vector<std::uint8_t> d;
+        std::vector<double> world; // identity pose: the camera point is the world point
+        for(int i = 0; i < n; ++i)
+            if(valid[i] && xyz[3 * i + 2] <= zMax)
+            {
+                d.insert(d.end(), &desc[32 * (std::size_t)i], &desc[32 * (std::size_t)i] + 32);
+                world.insert(world.end(), &xyz[3 * (std::size_t)i], &xyz[3 * (std::size_t)i] + 3);
+            }
+        const int count = static_cast<int>(world.size() / 3);
+        const int rc = mslam_hip_kf_add(ctx.h, entry, d.data(), world.data(), count);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_add", rc);
+        storeId[entry] = entry;
+        return count;
+    }
+
+    KeyframeTrackResult trackKeyframe(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                      const CameraParameters& camera, const KeyframePtr& reference,
+                                      const std::vector<KeyframePtr>& neighbours, const double* rvecGuess, const double* tvecGuess,
+                                      const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
+    {
+        const int refId = storedLandmarksOf(reference);
+        std::vector<std::int32_t> vote(neighbours.size() + 1), counts(neighbours.size() + 1);
+        for(std::size_t k = 0; k < neighbours.size(); ++k)
+            vote[k] = storedLandmarksOf(neighbours[k]);
+        gather(keypoints);
+        const int newId = newKeyframe ? nextTrackedId : -1;
+        const int cap = static_cast<int>(keypoints.size());
+        std::vector<std::int32_t> src(keypoints.size() + 1), kp(keypoints.size() + 1);
+        const bool guess = rvecGuess && tvecGuess;
+        mslam_hip_track_result out;
+        // the matcher's ratio and OpenCvRansacPnp's operating point, as relocalizePose (orb_feature.cpp:101, cv_ransac_pnp.cpp:56-57)
+        const int rc = mslam_hip_track(ctx.h, desc.data(), xy.data(), cap, depth, width, height, camera.factor, camera.focal.x(),
+                                       camera.focal.y(), camera.principalPoint.x(), camera.principalPoint.y(), refId, vote.data(),
+                                       static_cast<int>(neighbours.size()), 0.7, 100, 5.0, o.seed, guess ? 1 : 0, rvecGuess, tvecGuess,
+                                       o.minMatchedPoints, o.newKeyframeMinLandmarks, newId, o.zMax, &out, counts.data(), nullptr,
+                                       nullptr, nullptr, 0, src.data(), kp.data(), cap);
+        if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
+            raise(ctx.h, "mslam_hip_track", rc);
+        KeyframeTrackResult r;
+        r.tracked = out.tracked != 0, r.keyframeRequired = out.keyframe_required != 0, r.keyframeAdded = out.keyframe_added != 0;
+        r.matches = out.n_matches, r.correspondences = out.n_correspondences, r.inliers = out.n_inliers;
+        std::memcpy(r.rvec, out.rvec, sizeof(r.rvec));
+        std::memcpy(r.tvec, out.tvec, sizeof(r.tvec));
+        std::memcpy(r.R, out.R, sizeof(r.R));
+        r.visible.assign(counts.begin(), counts.begin() + static_cast<std::ptrdiff_t>(neighbours.size()));
+        if(out.vote_best >= 0)
+            r.bestReference = neighbours[static_cast<std::size_t>(out.vote_best)];
+        if(r.keyframeAdded)
+        {
+            ++nextTrackedId;
+            const int entry = addKeyframe(newKeyframe, keypoints); // (:375 -> :176)
+            if(entry < 0)
+                throw std::runtime_error("trackKeyframe: the new keyframe could not be fed");
+            storeId[entry] = newId;
+            r.landmarks = out.n_entry, r.inherited = out.n_inherited;
+            r.entrySource.assign(src.begin(), src.begin() + out.n_entry);
+            r.entryKeypoint.assign(kp.begin(), kp.begin() + out.n_entry);
+        }
+        return r;
+    }
+
+    std::vector<int> visibleLandmarks(const std::vector<KeyframePtr>& neighbours, const double R[9], const double t[3],
+                                      const CameraParameters& camera, int width, int height, int* best)
+    {
+        std::vector<std::int32_t> ids(neighbours.size() + 1), counts(neighbours.size() + 1);
+        for(std::size_t k = 0; k < neighbours.size(); ++k)
+            ids[k] = storedLandmarksOf(neighbours[k]);
+        int b = -1;
+        const int rc = mslam_hip_kf_visible(ctx.h, ids.data(), static_cast<int>(neighbours.size()), R, t, camera.focal.x(), camera.focal.y(),
+                                            camera.principalPoint.x(), camera.principalPoint.y(), width, height, counts.data(), &b);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_visible", rc);
+        if(best)
+            *best = b;
+        return std::vector<int>(counts.begin(), counts.begin() + static_cast<std::ptrdiff_t>(neighbours.size()));
+    }
+
   private:
+    // descriptors into `desc`, coordinates (as float, what the detector produced) into `xy`
+    void gather(const std::vector<OrbKeypoint>& keypoints)
+    {
+        gather_descriptors(keypoints, desc);
+        xy.resize(2 * keypoints.size() + 2);
+        for(std::size_t i = 0; i < keypoints.size(); ++i)
+        {
+            xy[2 * i] = static_cast<float>(keypoints[i].keypoint.coordinates.x());
+            xy[2 * i + 1] = static_cast<float>(keypoints[i].keypoint.coordinates.y());
+        }
+    }
+    int storedLandmarksOf(const KeyframePtr& keyframe) const
+    {
+        for(const auto& e : entryToKeyframe)
+            if(e.second == keyframe)
+            {
+                auto it = storeId.find(e.first);
+                if(it != storeId.end())
+                    return it->second;
+            }
+        throw std::runtime_error("the keyframe has no stored landmarks");
+    }
+
     VerifiedRelocalization verify(const std::vector<OrbKeypoint>& keypoints, const std::vector<std::int32_t>& entries,
                                   const CameraParameters& camera, int minInliers)
     {
@@ -355,8 +474,11 @@ class BowDatabase
             xy[2 * i + 1] = static_cast<float>(keypoints[i].keypoint.coordinates.y());
         }
         std::vector<mslam_hip_reloc_candidate> out(entries.size() + 1);
+        std::vector<std::int32_t> stored(entries.size());
+        for(std::size_t k = 0; k < entries.size(); ++k)
+            stored[k] = storeId.at(entries[k]);
         int best = -1;
-        const int rc = mslam_hip_relocalize(ctx.h, desc.data(), xy.data(), nullptr, static_cast<int>(keypoints.size()), entries.data(),
+        const int rc = mslam_hip_relocalize(ctx.h, desc.data(), xy.data(), nullptr, static_cast<int>(keypoints.size()), stored.data(),
                                             static_cast<int>(entries.size()), camera.focal.x(), camera.focal.y(),
                                             camera.principalPoint.x(), camera.principalPoint.y(), 0.7, 100, 5.0, 0, 0, nullptr,
                                             nullptr, minInliers, out.data(), &best, nullptr, nullptr, nullptr, 0);
@@ -384,12 +506,14 @@ class BowDatabase
     Ctx ctx;
     std::vector<std::uint8_t> desc;
     std::map<int, KeyframePtr> entryToKeyframe;
-    std::set<int> withLandmarks; // entries addKeyframeLandmarks has stored landmarks for
+    std::map<int, int> storeId; // BoW entry -> id of its landmarks in the keyframe store (entries without landmarks: absent)
+    int nextTrackedId = 1 << 30; // store ids of the keyframes trackKeyframe inserts (BoW entry ids count from 0)
+    std::vector<float> xy;
     KeyframePtr lastLoop;
     std::vector<OrbKeypoint> lastFed;
 };
 
-class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer
+class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, public IKeyframeTracker
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -411,6 +535,24 @@ class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer
                                           int minInliers) override
     {
         return db->relocalizePose(keypoints, camera, minInliers);
+    }
+    int initFirstKeyframe(BowDatabase::KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth,
+                          int width, int height, const CameraParameters& camera, double zMax) override
+    {
+        return db->initFirstKeyframe(keyframe, keypoints, depth, width, height, camera, zMax);
+    }
+    KeyframeTrackResult trackKeyframe(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                      const CameraParameters& camera, BowDatabase::KeyframePtr reference,
+                                      const std::vector<BowDatabase::KeyframePtr>& neighbours, const double* rvecGuess,
+                                      const double* tvecGuess, BowDatabase::KeyframePtr newKeyframe,
+                                      const KeyframeTrackOptions& options) override
+    {
+        return db->trackKeyframe(keypoints, depth, width, height, camera, reference, neighbours, rvecGuess, tvecGuess, newKeyframe, options);
+    }
+    std::vector<int> visibleLandmarks(const std::vector<BowDatabase::KeyframePtr>& neighbours, const double R[9], const double t[3],
+                                      const CameraParameters& camera, int width, int height, int* best) override
+    {
+        return db->visibleLandmarks(neighbours, R, t, camera, width, height, best);
     }
 
   private:

@@ -230,4 +230,46 @@ class IVerifiedLoopDetector
     virtual VerifiedRelocalization detectLoopVerified(const CameraParameters& camera, int minInliers = 60) = 0;
     virtual ~IVerifiedLoopDetector() = default;
 };
+// ---- extension (not in the reference): RgbdFeatureFrontend::track against the stored landmarks (mslam_hip_track) ----------
+// The adapter that owns the landmark store (the one offering IVerifiedRelocalizer) also runs the frontend's tracking step
+// on it: rgbd_feature_frontend.cpp:279-400 in one device call, and findBetterReferenceKeyframe's count (:544-575) alone.
+// Poses are world -> camera (cv::solvePnPRansac's convention), R row-major.
+struct KeyframeTrackOptions
+{
+    std::uint64_t seed = 0;
+    int minMatchedPoints = 10;        // rgbd_feature_frontend/min_matched_points
+    int newKeyframeMinLandmarks = 30; // rgbd_feature_frontend/new_keyframe_min_landmarks (:156-162)
+    double zMax = 3.0;                // addNewLandmarks' zThreshold (:407)
+};
+struct KeyframeTrackResult
+{
+    bool tracked = false, keyframeRequired = false, keyframeAdded = false;
+    int matches = 0, correspondences = 0, inliers = 0;
+    double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0}, R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::shared_ptr<Keyframe<slam3d::SensorState>> bestReference; // the vote's winner among `neighbours` (null: not tracked / none given)
+    std::vector<int> visible;                                     // per neighbour: its landmarks visible in the frame
+    int landmarks = 0, inherited = 0;                             // of the new keyframe's entry; `inherited` of them observe landmarks of `reference`
+    std::vector<std::int32_t> entrySource, entryKeypoint;         // entry i: landmark entrySource[i] of `reference` (-1: new), seen at keypoints[entryKeypoint[i]]
+};
+class IKeyframeTracker
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    // initFirstKeyframe (:433-470): the keyframe is fed as addKeyframe feeds it, and every keypoint with a valid depth and
+    // z <= zMax becomes a landmark at the identity pose; returns the number of landmarks
+    virtual int initFirstKeyframe(KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width,
+                                  int height, const CameraParameters& camera, double zMax = 3.0) = 0;
+    // one frame against `reference`; rvecGuess / tvecGuess = currentPose (both null: no guess).  When a keyframe is required
+    // and newKeyframe is not null, newKeyframe is fed as addKeyframe feeds it and its landmarks are stored on the device.
+    virtual KeyframeTrackResult trackKeyframe(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                              const CameraParameters& camera, KeyframePtr reference,
+                                              const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
+                                              const double* tvecGuess, KeyframePtr newKeyframe,
+                                              const KeyframeTrackOptions& options = KeyframeTrackOptions()) = 0;
+    // per keyframe of `neighbours` (at most 64, each with stored landmarks): its landmarks that project into a width x height
+    // frame seen from (R, t); *best = the position of the first maximum, -1 for an empty list
+    virtual std::vector<int> visibleLandmarks(const std::vector<KeyframePtr>& neighbours, const double R[9], const double t[3],
+                                              const CameraParameters& camera, int width, int height, int* best) = 0;
+    virtual ~IKeyframeTracker() = default;
+};
 } // namespace mslam

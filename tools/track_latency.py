@@ -1,0 +1,100 @@
+"""Latency of one mslam_hip_track call that inserts a keyframe (about 1900 query keypoints, a reference entry of 600
+landmarks, 8 vote ids) against the composition it replaces on the same inputs: mslam_hip_backproject, mslam_hip_relocalize
+with one candidate and the depth mask, the vote in numpy on copies of the entries read beforehand, and the entry assembled
+on the host and uploaded with mslam_hip_kf_add.  Both go through the Python mirror with arrays prepared beforehand; the two
+are timed alternately, in blocks, so that drift of the machine hits both, and the whole measurement is repeated (--runs) in
+the same process: the difference between the runs is the spread a difference between the sides has to exceed.
+
+usage: python tools/track_latency.py [--blocks 12] [--calls 100] [--runs 2] [--out file.json] [--trace new|old]
+       (--trace: a short run of one side only, for rocprofv3 --kernel-trace --stats)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as graft  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=12)
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--out")
+    ap.add_argument("--trace", choices=["new", "old"])
+    a = ap.parse_args()
+    import reloc_ref as rr
+    import track_ref as tr
+    pkg = graft.load_package()
+    sc = rr.make_scene(seed=0, n_kf=8, n_landmarks=600, n_distractors=1360)        # 540 + 1360 = 1900 query keypoints
+    ids, ref_id, new_id = sc["ids"], sc["target_id"], 500
+    desc, xy = sc["desc"], sc["xy"]
+    # a depth image consistent with the query: the landmark's camera z at its pixel, a 2 .. 4 m slope elsewhere
+    depth = np.tile(((2.0 + 2.0 * np.arange(640) / 640) * 5000).astype(np.uint16), (480, 1))
+    world = sc["store"][ref_id][1]
+    for i, l in enumerate(sc["from_landmark"]):
+        x, y = int(xy[i, 0]), int(xy[i, 1])
+        if l >= 0 and 0 <= x < 640 and 0 <= y < 480:
+            depth[y, x] = np.uint16(round(float((sc["R"] @ world[l] + sc["t"])[2]) * 5000))
+    c = pkg.Context(width=0, height=0, max_keypoints=2048)
+    for cid in ids:
+        c.kf_add(cid, *sc["store"][cid])
+    copies = {cid: c.kf_read(cid) for cid in ids}
+    kw = dict(seed=1, new_keyframe_min_landmarks=1 << 20)                           # every tracked step requires a keyframe
+
+    def new():
+        return c.track(desc, xy, depth, ref_id, ids, new_id, with_entry=True, **kw)
+
+    def old():
+        xyz, valid = c.backproject(depth, xy)
+        r = c.relocalize(desc, xy, [ref_id], valid=valid, seed=1, min_inliers=0, with_pairs=True)
+        w = r["candidates"][0]
+        R, t = tr.po.rodrigues(w["rvec"]), w["tvec"]
+        counts, best = tr.vote(copies, ids, R, t)
+        e = tr.build_entry(desc, xyz, valid, r["pairs"][0], r["inliers"][0], copies[ref_id][1], R, t, 3.0)
+        c.kf_add(new_id, e["desc"], e["world"])
+        return w, counts, best, e
+    # same answer (the composition's pose goes through rvec: the lifted points agree to rounding, the rest exactly)
+    rn = new()
+    gd, gw = c.kf_read(new_id)
+    w, counts, best, e = old()
+    assert rn["tracked"] and rn["keyframe_added"] and rn["n_inliers"] == w["n_inliers"] and rn["n_entry"] == len(e["kp"])
+    assert np.array_equal(rn["vote_counts"], counts) and rn["vote_best"] == best
+    assert np.array_equal(rn["entry_kp"], e["kp"]) and np.array_equal(gd, e["desc"]) and np.abs(gw - e["world"]).max() < 1e-9
+    if a.trace:
+        f = new if a.trace == "new" else old
+        for _ in range(50):
+            f()
+        return
+    for _ in range(30):
+        new(), old()
+    runs = []
+    for _ in range(a.runs):
+        res = {"new": [], "old": []}
+        for _ in range(a.blocks):
+            for name, f in (("new", new), ("old", old)):
+                t0 = time.perf_counter()
+                for _ in range(a.calls):
+                    f()                               # every call ends in a device synchronise
+                res[name].append((time.perf_counter() - t0) / a.calls * 1e6)
+        runs.append({k: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v)),
+                             blocks=[round(x, 2) for x in v]) for k, v in res.items()})
+    out = dict(runs=runs, shape=dict(query=len(desc), reference_landmarks=600, vote_ids=len(ids), calls_per_block=a.calls,
+                                     blocks=a.blocks),
+               step=dict(n_matches=rn["n_matches"], n_correspondences=rn["n_correspondences"], n_inliers=rn["n_inliers"],
+                         n_entry=rn["n_entry"], n_inherited=rn["n_inherited"]))
+    text = json.dumps(out, indent=1)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
