@@ -439,8 +439,28 @@ int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* ctx, const double* d_object, 
  * Keyframe store: per context, on the device, grown by doubling (mslam_hip_kf_reserve pre-allocates).  An entry is
  * n <= max_keypoints landmarks — a 32-byte descriptor and a world point (3 f64) each — under a caller-chosen integer id
  * (the adapters use the BoW database's entry id, so one id names both).  Adding an id that exists replaces its entry.
- * An id that is not in the store is MSLAM_HIP_E_INVALID everywhere; n > max_keypoints is MSLAM_HIP_E_CAPACITY. */
+ * An id that is not in the store is MSLAM_HIP_E_INVALID everywhere; n > max_keypoints is MSLAM_HIP_E_CAPACITY.
+ *
+ * Landmark ids: next to its descriptor and world point every landmark carries a 64-bit landmark id, the landmark's
+ * identity across entries (the reference's shared_ptr<Landmark>): two landmarks of two entries are the same landmark exactly
+ * when their ids are equal.  Every way of making an entry writes them:
+ *   fresh ids       (1 << 62) | (serial << 16) | position, position = the landmark's place in the entry (< 65536) and
+ *                   serial = the context's creation serial: 1 for the first entry made, one more for every later call
+ *                   that fills or replaces a slot — mslam_hip_kf_add, mslam_hip_kf_add_ids,
+ *                   mslam_hip_kf_add_from_batch_dev, mslam_hip_kf_union[_dev], and mslam_hip_track with new_id >= 0 (the
+ *                   serial is taken on the host before anything is enqueued, so it advances whether or not the step makes
+ *                   the keyframe).  mslam_hip_kf_add, mslam_hip_kf_add_from_batch_dev (in kept order) and part B of
+ *                   mslam_hip_track's new entry give fresh ids;
+ *   inherited ids   part A of mslam_hip_track's new entry copies the id of the reference entry's landmark `to` next to
+ *                   its world point; mslam_hip_kf_union copies ids with the observations it keeps;
+ *   caller's ids    mslam_hip_kf_add_ids takes them from the caller: each in [0, 2^62) (anything else is
+ *                   MSLAM_HIP_E_INVALID), so they never collide with fresh ids.  Keeping them distinct inside one entry
+ *                   is the caller's business; a repeat inside an entry is one landmark to mslam_hip_kf_covisible, and
+ *                   in a union the higher position wins.
+ * Nothing else reads the ids: every entry point of ABI 5 that existed before them gives byte-identical outputs. */
 int mslam_hip_kf_add(mslam_hip_ctx* ctx, int id, const uint8_t* desc /* n x 32 */, const double* world_xyz /* n x 3 */, int n);
+int mslam_hip_kf_add_ids(mslam_hip_ctx* ctx, int id, const uint8_t* desc /* n x 32 */, const double* world_xyz /* n x 3 */,
+                         const int64_t* landmark_ids /* n, each in [0, 2^62) */, int n);
 /* Frame `frame` of the last detect batch, which mslam_hip_backproject_batch_dev has run on, lifted as addNewLandmarks does
  * (rgbd_feature_frontend.cpp:402-431): a keypoint becomes a landmark when its depth is valid and its camera-frame z is
  * <= z_max (the reference: zThreshold = 3.f); its world point is R p + t (toGlobalCoordinates, projection.cpp:51-54;
@@ -455,6 +475,42 @@ int mslam_hip_kf_reserve(mslam_hip_ctx* ctx, int max_entries);
 /* test / debug read-back of an entry (synchronises): *n = its landmark count; desc / world_xyz (either may be NULL) receive
  * the landmarks when `capacity` holds them, otherwise nothing is copied and the call returns MSLAM_HIP_E_CAPACITY. */
 int mslam_hip_kf_read(mslam_hip_ctx* ctx, int id, uint8_t* desc, double* world_xyz, int capacity, int* n);
+/* the same for the entry's landmark ids (landmark_ids may be NULL: only *n is written) */
+int mslam_hip_kf_read_ids(mslam_hip_ctx* ctx, int id, int64_t* landmark_ids, int capacity, int* n);
+
+/* ---- the local map: covisibility and the union of entries -----------------------------------------------------------
+ * BasicMap::updateCovisibility's edge test (basic_map.cpp:141-164): counts[k] = the number of distinct landmark ids of
+ * entry `id` that entry ids[k] (n_ids <= 64) holds as well.  `id` may be listed: it then counts its own distinct ids.  No
+ * upload (the list travels as a kernel argument), three launches, one synchronisation.  An id that is not in the store:
+ * MSLAM_HIP_E_INVALID.
+ *   edge     SAME: counts[k] > 0 <=> the reference makes the two keyframes neighbours, provided an entry holds the
+ *            landmarks its keyframe observes; the count itself is extra (the reference keeps a set, no weight);
+ *   when     DEVIATES: the reference updates the graph inside addKeyframe from the observations handed to it; here the
+ *            caller asks, for the entries it names. */
+int mslam_hip_kf_covisible(mslam_hip_ctx* ctx, int id, const int32_t* ids, int n_ids /* <= 64 */, int32_t* counts /* n_ids */);
+
+/* getLandmarksWithKeypoints' result (rgbd_feature_frontend.cpp:256-277 with RecentObservationsVisitor, :57-80) as an
+ * ordinary store entry: entry dst_id is created — or replaced, under a new serial — and holds one landmark per distinct
+ * landmark id found in the n_ids (1..64) listed entries.  For each id the observation kept is the one from the listed entry
+ * with the largest keyframe id (`observation.keyframe->id > it->second.keyframe->id`); its descriptor, world point and
+ * landmark id are copied bit for bit.  A landmark id repeated inside that entry: the higher position wins.
+ * Because the result is an ordinary entry, mslam_hip_track and mslam_hip_relocalize run on it unchanged: pass dst_id as
+ * ref_id (entry_src then indexes the union, whose ids mslam_hip_kf_read_ids returns).
+ * The caller chooses the listed entries (the reference: BasicMap::getNeighbourKeyframes of the reference keyframe, depth 2).
+ * mslam_hip_kf_union_dev is asynchronous on the context's stream (a clear and four launches, nothing uploaded);
+ * mslam_hip_kf_union is the same followed by one synchronisation, *n_out (may be NULL) = the number of distinct landmarks.
+ * Errors: dst_id among ids, an id listed twice, an id that is not in the store, n_ids outside 1..64: MSLAM_HIP_E_INVALID,
+ * the store is untouched.  More than max_keypoints distinct landmarks: MSLAM_HIP_E_CAPACITY, *n_out = the count that was
+ * needed, and entry dst_id exists with 0 landmarks (no partial result is valid); the _dev form reports it through
+ * mslam_hip_sync, once, like the other *_dev launches.  A context meant for local-map tracking is created with
+ * max_keypoints sized for the union, not for one frame.
+ *   observation kept   SAME rule (largest keyframe id; ids are distinct, so there are no ties between entries);
+ *   order              DEVIATES: by the position of the winning entry in `ids`, then by the landmark's position inside it:
+ *                      deterministic.  The reference iterates an unordered_map keyed by the landmarks' pointer values,
+ *                      an unspecified order;
+ *   size               DEVIATES: at most 64 entries and max_keypoints landmarks; the reference has no bound. */
+int mslam_hip_kf_union_dev(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */);
+int mslam_hip_kf_union(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */, int* n_out /* may be NULL */);
 
 /* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
  * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
@@ -527,12 +583,13 @@ int mslam_hip_kf_visible(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids /* <=
  *   keyframe       required <=> tracked && n_inliers < new_keyframe_min_landmarks (:156-162, the reference: 30).  With
  *                  new_id >= 0 the entry is built in the store under new_id (:373-397):
  *                    part A  every inlier correspondence, in correspondence order: the query's descriptor desc[from], the
- *                            reference entry's world point world[to] copied bit for bit; entry_src = to, entry_kp = from;
+ *                            reference entry's world point world[to] and landmark id copied bit for bit; entry_src = to,
+ *                            entry_kp = from;
  *                    part B  every keypoint that no correspondence used (matched with a valid depth, inlier or not:
  *                            usedKeypointIndices, :314-334; set_difference, :377-385), with a valid depth and z <= z_max, in
  *                            keypoint order, lifted as addNewLandmarks does (:402-431):
  *                            world_r = ((R[0][r] (x - t0) + R[1][r] (y - t1)) + R[2][r] (z - t2)), the inverse of the
- *                            tracked world -> camera pose; entry_src = -1, entry_kp = the keypoint;
+ *                            tracked world -> camera pose; a fresh landmark id; entry_src = -1, entry_kp = the keypoint;
  *                  The matcher gives one match per landmark of ref_id, so two landmarks can be matched to the same
  *                  keypoint: part A then lists that keypoint twice (two observations, as the reference would push both).
  *                  Without such duplicates A and B are disjoint subsets of the keypoints and the entry holds at most n
@@ -547,11 +604,13 @@ int mslam_hip_kf_visible(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids /* <=
  * new_id that exists is replaced when a keyframe is added and left alone otherwise.  The store grows for new_id on the host
  * before anything is enqueued.
  * Against the reference:
- *   matching       DEVIATES: against the reference keyframe's own entry only, not against the union of the most recent
- *                  observations within graph depth 2 (getLandmarksWithKeypoints, :256-277): the store has no landmark
- *                  identity across entries.  entry_src / entry_kp are what let the caller keep that identity on the host:
- *                  entry i of the new keyframe is landmark entry_src[i] of ref_id (or a new landmark), seen at keypoint
- *                  entry_kp[i];
+ *   matching       against entry ref_id.  DEVIATES when that is the reference keyframe's own entry: the reference matches
+ *                  against the union of the most recent observations within graph depth 2 (getLandmarksWithKeypoints,
+ *                  :256-277).  SAME up to the order of the landmarks when ref_id is a mslam_hip_kf_union of that
+ *                  neighbourhood (the order decides which of two equally good landmarks the matcher names, nothing else).
+ *                  entry_src / entry_kp tell the caller what the new entry is made of: entry i of the new keyframe is
+ *                  landmark entry_src[i] of ref_id (or a new landmark), seen at keypoint entry_kp[i]; the landmark ids
+ *                  carry the same identity on the device;
  *   PnP            as mslam_hip_pnp_ransac (see its SAME / DEVIATES list); tracked, keyframe_required SAME;
  *   vote           see mslam_hip_kf_visible; the caller chooses the neighbourhood (vote_ids);
  *   new keyframe   SAME observations and landmarks; the lift DEVIATES in the last bits as mslam_hip_kf_add_from_batch_dev's;

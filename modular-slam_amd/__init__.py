@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_add", "mslam_hip_kf_add_from_batch_dev", "mslam_hip_kf_remove", "mslam_hip_kf_clear", "mslam_hip_kf_size",
     "mslam_hip_kf_reserve", "mslam_hip_kf_read", "mslam_hip_relocalize",
     "mslam_hip_kf_visible", "mslam_hip_track",
+    "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
 ]
 
 
@@ -369,13 +370,20 @@ class Context:
                                                          C.c_double(principal[1]), C.c_void_p(d_pose), C.c_void_p(d_info)))
 
     # ---- keyframe store + verified relocalisation (rgbd_feature_frontend.cpp:402-431, :495-534) ----
-    def kf_add(self, id, desc, world_xyz):
-        """store keyframe `id`: n landmarks = descriptors (n x 32) + world points (n x 3 f64); an existing id is replaced"""
+    def kf_add(self, id, desc, world_xyz, lids=None):
+        """store keyframe `id`: n landmarks = descriptors (n x 32) + world points (n x 3 f64); an existing id is replaced.
+        lids = None: the landmarks get fresh landmark ids; otherwise n caller-chosen ids in [0, 2^62) (mslam_hip_kf_add_ids)"""
         d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         w = np.ascontiguousarray(world_xyz, np.float64).reshape(-1, 3)
         if len(d) != len(w):
             raise MslamHipError(E_INVALID, "kf_add: %d descriptors, %d world points" % (len(d), len(w)))
-        self._chk(self.L.mslam_hip_kf_add(self._h, int(id), _p(d), _p(w), len(d)))
+        if lids is None:
+            self._chk(self.L.mslam_hip_kf_add(self._h, int(id), _p(d), _p(w), len(d)))
+            return
+        l = np.ascontiguousarray(lids, np.int64).reshape(-1)
+        if len(l) != len(d):
+            raise MslamHipError(E_INVALID, "kf_add: %d descriptors, %d landmark ids" % (len(d), len(l)))
+        self._chk(self.L.mslam_hip_kf_add_ids(self._h, int(id), _p(d), _p(w), _p(l), len(d)))
 
     def kf_add_from_batch_dev(self, id, frame, R=np.eye(3), t=(0, 0, 0), z_max=3.0):
         """store frame `frame` of the last detect + back-project batch as keyframe `id` (valid depth, z <= z_max,
@@ -406,6 +414,40 @@ class Context:
         w = np.empty((max(n.value, 1), 3), np.float64)
         self._chk(self.L.mslam_hip_kf_read(self._h, int(id), _p(d), _p(w), n.value, C.byref(n)))
         return d[:n.value].copy(), w[:n.value].copy()
+
+    def kf_read_ids(self, id):
+        """-> landmark ids [n] i64 of a stored keyframe (debug read-back; synchronises)"""
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_read_ids(self._h, int(id), None, 0, C.byref(n)))
+        l = np.empty(max(n.value, 1), np.int64)
+        self._chk(self.L.mslam_hip_kf_read_ids(self._h, int(id), _p(l), n.value, C.byref(n)))
+        return l[:n.value].copy()
+
+    # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
+    def kf_covisible(self, id, ids):
+        """-> counts [len(ids)]: how many distinct landmark ids of entry `id` each entry of ids (<= 64) holds as well"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        counts = np.zeros(max(len(ids), 1), np.int32)
+        self._chk(self.L.mslam_hip_kf_covisible(self._h, int(id), _p(ids), len(ids), _p(counts)))
+        return counts[:len(ids)].copy()
+
+    def kf_union(self, dst_id, ids, sync=True):
+        """entry dst_id = one landmark per distinct landmark id of the listed entries (1..64), each the observation of the
+        listed entry with the largest id, ordered by list position, then landmark position.
+        sync=True -> the number of landmarks (MslamHipError E_CAPACITY carries `needed` when they exceed max_keypoints);
+        sync=False enqueues only -> None, and an overflow surfaces at the next sync()"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if not sync:
+            self._chk(self.L.mslam_hip_kf_union_dev(self._h, int(dst_id), _p(ids), len(ids)))
+            return None
+        n = C.c_int(0)
+        rc = self.L.mslam_hip_kf_union(self._h, int(dst_id), _p(ids), len(ids), C.byref(n))
+        if rc == E_CAPACITY:
+            e = MslamHipError(rc, (self.L.mslam_hip_last_error(self._h) or b"").decode())
+            e.needed = n.value
+            raise e
+        self._chk(rc)
+        return n.value
 
     def relocalize(self, desc, xy, cand_ids, focal=(525.0, 525.0), principal=(319.5, 239.5), valid=None, ratio=0.7,
                    iterations=100, reprojection_error=5.0, seed=0, rvec=None, tvec=None, min_inliers=60, with_pairs=False):
@@ -806,12 +848,31 @@ class HipKeyframeTracker:
     the previous pose as the guess; the vote's winner becomes the reference (:366-371), a required keyframe is inserted
     and becomes the reference (:373-397); when tracking fails, Context.relocalize over the stored keyframes names the new
     reference (:210-217).  Keyframe ids are 0, 1, ...; the vote list and the relocalisation candidates are the most recent
-    64 of them.  Poses are world -> camera (rvec, tvec / R, t)."""
+    64 of them.  Poses are world -> camera (rvec, tvec / R, t).
+
+    local_map_depth = None: track against the reference keyframe's own entry.  local_map_depth = d (the reference: 2): track
+    against the local map, as the reference does (getLandmarksWithKeypoints, :256-277).  The tracker keeps the covisibility
+    graph on the host (id -> set of ids); after a keyframe is added, Context.kf_covisible of the new entry against the
+    members of the local map it was tracked on (part A inherits from their union, so only they can share landmarks with it)
+    adds a symmetric edge wherever the count is positive (updateCovisibility, basic_map.cpp:141-164).  The local map is the
+    Context.kf_union, under the reserved id LOCAL_MAP_ID, of the reference keyframe's neighbourhood: getNeighbourKeyframes
+    (basic_map.cpp:209-237) restated with its `level <= deepLevel` test, which still expands the nodes at level d and so
+    reaches d + 1 hops — the reference's behaviour, kept.  A neighbourhood of more than 64 keyframes keeps its 64 largest
+    ids (DEVIATES: a union lists at most 64 entries).  The union is enqueued without a synchronisation, only when the
+    reference keyframe changed or a keyframe was added, and track runs with ref_id = LOCAL_MAP_ID; the reserved id is never
+    in self.ids, the vote list or the relocalisation candidates.  The context's max_keypoints must hold the union; one that
+    does not fit raises MslamHipError(E_CAPACITY)."""
+
+    LOCAL_MAP_ID = 0x7fffffff
 
     def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
                  reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
-                 reloc_min_inliers=60):
+                 reloc_min_inliers=60, local_map_depth=None):
         self.ctx = ctx
+        self.local_map_depth = local_map_depth
+        self.graph = {}            # covisibility: id -> set of ids
+        self.local_map = []        # the entries the current union lists
+        self._local_map_of = None  # the reference keyframe the current union was built for (None: rebuild)
         self.focal, self.principal, self.factor = tuple(focal), tuple(principal), factor
         self.ratio, self.iterations, self.reprojection_error, self.seed = ratio, iterations, reprojection_error, seed
         self.min_matched_points, self.new_keyframe_min_landmarks = min_matched_points, new_keyframe_min_landmarks
@@ -831,13 +892,23 @@ class HipKeyframeTracker:
             keep = valid & (xyz[:, 2] <= self.z_max)
             self.ctx.kf_add(0, np.asarray(desc, np.uint8).reshape(-1, 32)[keep], xyz[keep])   # identity pose: world = camera point
             self.ids, self.reference = [0], 0
+            self.graph = {0: set()}
             return dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
                         keyframe=0, relocalized=False, step=None)
         vote = self.ids[-64:]
         new_id = self.ids[-1] + 1
-        res = self.ctx.track(desc, xy, depth, self.reference, vote, new_id, self.factor, self.focal, self.principal, self.ratio,
+        ref_id, rebuilt = self.reference, False
+        if self.local_map_depth is not None:
+            if self._local_map_of != self.reference:
+                self.local_map = self.neighbours(self.reference)
+                self.ctx.kf_union(self.LOCAL_MAP_ID, self.local_map, sync=False)   # track's own synchronisation covers it
+                self._local_map_of, rebuilt = self.reference, True
+            ref_id = self.LOCAL_MAP_ID
+        res = self.ctx.track(desc, xy, depth, ref_id, vote, new_id, self.factor, self.focal, self.principal, self.ratio,
                              self.iterations, self.reprojection_error, seed, self.rvec, self.tvec, self.min_matched_points,
                              self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
+        if rebuilt:
+            self.ctx.sync()   # a union that did not fit max_keypoints left an empty entry: it surfaces here as E_CAPACITY
         out = dict(tracked=bool(res["tracked"]), n_inliers=res["n_inliers"], keyframe=-1, relocalized=False, step=res)
         if res["tracked"]:
             self.rvec, self.tvec, self.R = res["rvec"], res["tvec"], res["R"]
@@ -846,6 +917,13 @@ class HipKeyframeTracker:
             if res["keyframe_added"]:
                 self.ids.append(new_id)
                 self.reference = out["keyframe"] = new_id
+                if self.local_map_depth is not None:
+                    self.graph[new_id] = set()
+                    for other, n in zip(self.local_map, self.ctx.kf_covisible(new_id, self.local_map)):
+                        if n > 0 and other != new_id:
+                            self.graph[new_id].add(other)
+                            self.graph[other].add(new_id)
+                    self._local_map_of = None   # a keyframe was added: the local map is rebuilt
         else:
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
@@ -853,6 +931,17 @@ class HipKeyframeTracker:
                 self.reference, out["relocalized"] = vote[reloc["best"]], True
         out.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
         return out
+
+    def neighbours(self, ref):
+        """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than
+        64: the 64 largest ids"""
+        result, queue = set(), [(ref, 0)]
+        while queue:
+            cur, level = queue.pop(0)
+            result.add(cur)
+            if level <= self.local_map_depth:
+                queue.extend((nb, level + 1) for nb in sorted(self.graph.get(cur, ())) if nb not in result)
+        return sorted(result)[-64:]
 
 
 # ---- harness helper (bench / tests): copy a context-owned device array to the host ------------------

@@ -831,6 +831,8 @@ static int check_flags(mslam_hip_ctx* c)
         m += " a BoW vector has more words than the exchange format's k_max;";
     if(f & kFlagPackOverflow)
         m += " packed batch results larger than the buffer given to mslam_hip_pack_batch_dev (header.bytes);";
+    if(f & kFlagUnionOverflow)
+        m += " a union of store entries has more distinct landmarks than max_keypoints (mslam_hip_kf_union_dev);";
     return fail(c, MSLAM_HIP_E_CAPACITY, m);
 }
 

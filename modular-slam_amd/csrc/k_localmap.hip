@@ -1,0 +1,471 @@
+// k_localmap.hip — the local map on the keyframe store: the union of up to 64 entries as an ordinary entry
+// (mslam_hip_kf_union[_dev]) and covisibility counts (mslam_hip_kf_covisible), both on the landmark ids the store keeps
+// next to every landmark.
+//
+// What getLandmarksWithKeypoints builds for track() (reference rgbd_feature_frontend.cpp:256-277): the most recent
+// observation of every landmark seen from a set of keyframes (RecentObservationsVisitor, :57-80: the observation whose
+// keyframe id is the largest), and the edge test of BasicMap::updateCovisibility (basic_map.cpp:141-164: two keyframes are
+// neighbours when they observe a landmark in common).
+//
+// Both run on one open-addressing hash table in device scratch: {u64 key, u64 val} buckets, a power of two of them and
+// at least twice the landmarks that can be inserted, cleared to all-ones (a landmark id is never all-ones: ids are below
+// 2^63), linear probing.  A key is claimed with one compare-and-swap; what the value holds differs:
+//   union        ~pack, pack = (rank + 1) << 32 | list position << 16 | landmark position, lowered with atomicMin: the
+//                smallest ~pack is the largest pack, i.e. the listed entry with the largest keyframe id (rank = the rank
+//                of its id among the listed ids), and inside one entry the highest position.  The cleared value (all
+//                ones) is above every ~pack;
+//   covisible    a 64-bit mask, bit k = "entry ids[k] holds this landmark id", so a repeat inside an entry counts once.
+// The union's result order is by list position, then landmark position: the grid is laid out that way (blockIdx.y = list
+// position), winners are counted per block, one workgroup scans the block counts, and the scatter places every winner
+// at its block's offset plus its ballot / popcount prefix, as k_kf_lift does inside one block.
+#include "reloc.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+namespace mslam
+{
+
+struct LmBucket
+{
+    unsigned long long key, val;
+};
+
+constexpr unsigned long long kLmEmpty = ~0ull;
+
+// the listed entries of one call, passed by value: nothing is uploaded
+struct LmList
+{
+    int32_t slot[kRelocMaxCand];
+    int32_t rank[kRelocMaxCand];
+};
+
+struct LmHead // the mapped result block's first 16 bytes, then counts[64]
+{
+    int32_t needed, pad[3];
+};
+
+__device__ __forceinline__ unsigned long long lm_hash(unsigned long long x)
+{
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the bucket of `key`, claimed if no thread has claimed one for it yet.  The table has at least twice as many buckets as
+// keys are ever inserted, so the walk ends; it is bounded by the table's size all the same (-1: cannot happen).
+__device__ __forceinline__ long long lm_claim(LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
+{
+    unsigned long long h = lm_hash(key) & mask;
+    for(unsigned long long step = 0; step <= mask; ++step)
+    {
+        const unsigned long long prev = atomicCAS(&table[h].key, kLmEmpty, key);
+        if(prev == kLmEmpty || prev == key)
+            return (long long)h;
+        h = (h + 1) & mask;
+    }
+    return -1;
+}
+
+// the bucket of `key`, -1 when the table does not hold it (read-only: every insert is in an earlier launch)
+__device__ __forceinline__ long long lm_find(const LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
+{
+    unsigned long long h = lm_hash(key) & mask;
+    for(unsigned long long step = 0; step <= mask; ++step)
+    {
+        const unsigned long long k = table[h].key;
+        if(k == key)
+            return (long long)h;
+        if(k == kLmEmpty)
+            return -1;
+        h = (h + 1) & mask;
+    }
+    return -1;
+}
+
+__device__ __forceinline__ unsigned long long lm_pack(int rank, int k, int i)
+{
+    return ((unsigned long long)(rank + 1) << 32) | ((unsigned long long)k << 16) | (unsigned long long)i;
+}
+
+// One thread per (list position k = blockIdx.y, landmark position i).  as_mask = 0: the union's insert (atomicMin of
+// ~pack); as_mask = 1: covisible's insert, every value becomes the empty mask 0.
+__global__ __launch_bounds__(256) void k_lm_insert(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
+                                                   int K, LmBucket* __restrict__ table, unsigned long long mask, int as_mask)
+{
+    const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int slot = list.slot[k];
+    const int n = min(max(store_n[slot], 0), K);
+    if(i >= n)
+        return;
+    const unsigned long long key = (unsigned long long)store_lid[(size_t)slot * K + i];
+    const long long b = lm_claim(table, mask, key);
+    if(b < 0)
+        return;
+    if(as_mask)
+        atomicAnd(&table[b].val, 0ull);
+    else
+        atomicMin(&table[b].val, ~lm_pack(list.rank[k], k, i));
+}
+
+// Same grid: a thread wins when the bucket of its landmark id holds its own pack.  Per wave the ballot of the winners,
+// per block their count.
+__global__ __launch_bounds__(256) void k_lm_select(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
+                                                   int K, const LmBucket* __restrict__ table, unsigned long long mask,
+                                                   unsigned long long* __restrict__ win, uint32_t* __restrict__ cnt)
+{
+    __shared__ uint32_t wsum[4];
+    const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = blockIdx.x * 256 + tid;
+    const size_t blk = (size_t)k * gridDim.x + blockIdx.x;
+    const int slot = list.slot[k];
+    const int n = min(max(store_n[slot], 0), K);
+    bool w = false;
+    if(i < n)
+    {
+        const long long b = lm_find(table, mask, (unsigned long long)store_lid[(size_t)slot * K + i]);
+        w = b >= 0 && table[b].val == ~lm_pack(list.rank[k], k, i);
+    }
+    const unsigned long long bal = __ballot(w);
+    if(lane == 0)
+    {
+        win[blk * 4 + wave] = bal;
+        wsum[wave] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    if(tid == 0)
+        cnt[blk] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// One workgroup: the exclusive scan of the block counts (ofs[nb] = the total), the new entry's count — 0 when the total
+// exceeds the capacity, with the overflow flag when the caller reads no result of its own — and the total for the host.
+__global__ __launch_bounds__(256) void k_lm_scan(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ ofs, int nb, int cap,
+                                                 int32_t* __restrict__ out_n, uint32_t* __restrict__ flags, int set_flag,
+                                                 LmHead* __restrict__ h_res)
+{
+    __shared__ uint32_t wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t running = 0;
+    for(int base = 0; base < nb; base += 256)
+    {
+        const int b = base + tid;
+        const uint32_t v = b < nb ? cnt[b] : 0u;
+        uint32_t inc = v; // inclusive scan inside the wave
+        for(int o = 1; o < 64; o <<= 1)
+        {
+            const uint32_t up = __shfl_up(inc, o);
+            if(lane >= o)
+                inc += up;
+        }
+        if(lane == 63)
+            wsum[wave] = inc;
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for(int w = 0; w < 4; ++w)
+        {
+            pre += w < wave ? wsum[w] : 0;
+            tot += wsum[w];
+        }
+        if(b < nb)
+            ofs[b] = running + pre + (inc - v);
+        running += tot;
+        __syncthreads();
+    }
+    if(tid == 0)
+    {
+        ofs[nb] = running;
+        const bool fits = running <= (uint32_t)cap;
+        *out_n = fits ? (int32_t)running : 0;
+        if(!fits && set_flag)
+            atomicOr(flags, kFlagUnionOverflow);
+        h_res->needed = (int32_t)running;
+    }
+}
+
+// Same grid as k_lm_select: every winner copies its descriptor, world point and landmark id, bit for bit, to position
+// ofs[block] + (winners before it in the block) of the new entry.  Nothing is written when the union does not fit.
+__global__ __launch_bounds__(256) void k_lm_scatter(const uint8_t* __restrict__ store_desc, const double* __restrict__ store_world,
+                                                    const int64_t* __restrict__ store_lid, LmList list, int K,
+                                                    const unsigned long long* __restrict__ win, const uint32_t* __restrict__ ofs, int nb,
+                                                    uint8_t* __restrict__ out_desc, double* __restrict__ out_world,
+                                                    int64_t* __restrict__ out_lid)
+{
+    if(ofs[nb] > (uint32_t)K)
+        return;
+    const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = blockIdx.x * 256 + tid;
+    const size_t blk = (size_t)k * gridDim.x + blockIdx.x;
+    const unsigned long long mine = win[blk * 4 + wave];
+    if(!((mine >> lane) & 1ull))
+        return;
+    uint32_t pre = 0;
+    for(int w = 0; w < wave; ++w)
+        pre += (uint32_t)__popcll(win[blk * 4 + w]);
+    const size_t o = (size_t)ofs[blk] + pre + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull)); // < ofs[nb] <= K
+    const size_t src = (size_t)list.slot[k] * K + i; // a winner has i < n <= K
+    const uint4* s = reinterpret_cast<const uint4*>(store_desc + src * 32);
+    uint4* d = reinterpret_cast<uint4*>(out_desc + o * 32);
+    d[0] = s[0];
+    d[1] = s[1];
+    out_world[o * 3] = store_world[src * 3], out_world[o * 3 + 1] = store_world[src * 3 + 1], out_world[o * 3 + 2] = store_world[src * 3 + 2];
+    out_lid[o] = store_lid[src];
+}
+
+// One workgroup per listed entry k, over a table built from entry `id` with empty masks: a landmark id the table holds
+// sets bit k of its mask, and counts when the bit was clear (a repeat inside entry k counts once).
+__global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
+                                                      int K, LmBucket* __restrict__ table, unsigned long long mask,
+                                                      int32_t* __restrict__ h_counts)
+{
+    __shared__ uint32_t wsum[4];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slot = list.slot[k];
+    const int n = min(max(store_n[slot], 0), K);
+    const unsigned long long bit = 1ull << k;
+    uint32_t mine = 0; // (wave-uniform: every lane adds the same popcount)
+    for(int base = 0; base < n; base += 256)
+    {
+        const int i = base + tid;
+        bool hit = false;
+        if(i < n)
+        {
+            const long long b = lm_find(table, mask, (unsigned long long)store_lid[(size_t)slot * K + i]);
+            hit = b >= 0 && !(atomicOr(&table[b].val, bit) & bit);
+        }
+        mine += (uint32_t)__popcll(__ballot(hit));
+    }
+    if(lane == 0)
+        wsum[wave] = mine;
+    __syncthreads();
+    if(tid == 0)
+        h_counts[k] = (int32_t)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+#define LCHK(c, call)                                                                                                  \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t e_ = (call);                                                                                        \
+        if(e_ != hipSuccess)                                                                                           \
+        {                                                                                                              \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
+            return MSLAM_HIP_E_RUNTIME;                                                                                \
+        }                                                                                                              \
+    } while(0)
+
+// the scratch both calls share: a table of `buckets` buckets, per-block arrays for `blocks` blocks, the mapped result
+static int lm_scratch(mslam_hip_ctx* c, size_t buckets, size_t blocks)
+{
+    RelocState* r = c->reloc;
+    if(buckets > r->lm_buckets)
+    {
+        LCHK(c, hipStreamSynchronize(c->stream)); // what reads the old table has finished before it is freed
+        if(r->d_lm_table)
+            (void)hipFree(r->d_lm_table);
+        r->d_lm_table = nullptr;
+        r->lm_buckets = 0;
+        LCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_table), buckets * sizeof(LmBucket)));
+        r->lm_buckets = buckets;
+    }
+    if(blocks > r->lm_blocks)
+    {
+        LCHK(c, hipStreamSynchronize(c->stream));
+        if(r->d_lm_blocks)
+            (void)hipFree(r->d_lm_blocks);
+        r->d_lm_blocks = nullptr;
+        r->lm_blocks = 0;
+        const size_t nb = std::max(blocks, (size_t)256);
+        LCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_blocks), nb * 32 + nb * 4 + (nb + 1) * 4)); // [win nb x 4 u64 | cnt | ofs]
+        r->lm_blocks = nb;
+    }
+    if(!r->h_lm)
+    {
+        LCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_lm), sizeof(LmHead) + kRelocMaxCand * 4, hipHostMallocMapped));
+        if(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_lm), r->h_lm, 0) != hipSuccess)
+        {
+            (void)hipHostFree(r->h_lm);
+            r->h_lm = r->d_h_lm = nullptr;
+            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: no device address for the result block");
+        }
+    }
+    return MSLAM_HIP_OK;
+}
+
+static size_t lm_bucket_count(size_t keys)
+{
+    size_t b = 64;
+    while(b < 2 * keys)
+        b <<= 1;
+    return b;
+}
+
+// the launches of both union forms; *dst_slot receives the new entry's slot
+static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const int32_t* ids, int n_ids, int set_flag, int* dst_slot)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(!ids || n_ids < 1 || n_ids > kRelocMaxCand)
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument (1 to 64 ids)");
+    RelocState* r = c->reloc;
+    const int K = c->p.max_keypoints;
+    LmList list{};
+    size_t keys = 0;
+    int n_max = 0;
+    for(int k = 0; k < n_ids; ++k)
+    {
+        auto it = r->slot_of.find(ids[k]);
+        if(it == r->slot_of.end())
+            return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is not in the keyframe store");
+        if(ids[k] == dst_id)
+            return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": dst_id is one of the listed ids");
+        int rank = 0;
+        for(int j = 0; j < n_ids; ++j)
+        {
+            if(j != k && ids[j] == ids[k])
+                return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is listed twice");
+            rank += ids[j] < ids[k] ? 1 : 0;
+        }
+        list.slot[k] = it->second;
+        list.rank[k] = rank;
+        keys += (size_t)r->n_upper[(size_t)it->second];
+        n_max = std::max(n_max, r->n_upper[(size_t)it->second]);
+    }
+    const unsigned bx = (unsigned)std::max((n_max + 255) / 256, 1);
+    const size_t nb = (size_t)bx * (size_t)n_ids, buckets = lm_bucket_count(keys);
+    rc = lm_scratch(c, buckets, nb);
+    if(rc)
+        return rc;
+    // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
+    rc = store_slot_for(c, dst_id, dst_slot);
+    if(rc)
+        return rc;
+    (void)store_next_lid_base(c); // a new serial for the entry; its landmarks keep the ids they have
+    const size_t slot = (size_t)*dst_slot;
+    hipStream_t s = c->stream;
+    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table);
+    unsigned long long* win = reinterpret_cast<unsigned long long*>(r->d_lm_blocks);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(r->d_lm_blocks + r->lm_blocks * 32);
+    uint32_t* ofs = cnt + r->lm_blocks;
+    const dim3 grid(bx, (unsigned)n_ids);
+    {
+        StageScope ts(c, "union_clear");
+        LCHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+    }
+    {
+        StageScope ts(c, "union_insert");
+        hipLaunchKernelGGL(k_lm_insert, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, (unsigned long long)(buckets - 1), 0);
+    }
+    {
+        StageScope ts(c, "union_select");
+        hipLaunchKernelGGL(k_lm_select, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, (unsigned long long)(buckets - 1), win, cnt);
+    }
+    {
+        StageScope ts(c, "union_scan");
+        hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(256), 0, s, cnt, ofs, (int)nb, K, r->d_n + slot, c->d_flags, set_flag,
+                           reinterpret_cast<LmHead*>(r->d_h_lm));
+    }
+    {
+        StageScope ts(c, "union_scatter");
+        hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, s, r->d_desc, r->d_world, r->d_lid, list, K, win, ofs, (int)nb,
+                           r->d_desc + slot * K * 32, r->d_world + slot * K * 3, r->d_lid + slot * K);
+    }
+    LCHK(c, hipGetLastError());
+    r->n_upper[slot] = (int)std::min(keys, (size_t)K); // (the count stays on the device)
+    return MSLAM_HIP_OK;
+}
+
+extern "C" {
+
+int mslam_hip_kf_union_dev(mslam_hip_ctx* c, int dst_id, const int32_t* ids, int n_ids)
+{
+    int slot = -1;
+    return union_enqueue(c, "kf_union_dev", dst_id, ids, n_ids, 1, &slot);
+}
+
+int mslam_hip_kf_union(mslam_hip_ctx* c, int dst_id, const int32_t* ids, int n_ids, int* n_out)
+{
+    if(n_out)
+        *n_out = 0;
+    int slot = -1;
+    const int rc = union_enqueue(c, "kf_union", dst_id, ids, n_ids, 0, &slot);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    LCHK(c, hipStreamSynchronize(c->stream));
+    const int32_t needed = reinterpret_cast<const LmHead*>(r->h_lm)->needed;
+    if(needed < 0)
+        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: the kernels reported an impossible count");
+    if(n_out)
+        *n_out = needed;
+    if(needed > c->p.max_keypoints)
+    {
+        r->n_upper[(size_t)slot] = 0;
+        return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "kf_union: " + std::to_string(needed) + " distinct landmarks, more than the context's max_keypoints");
+    }
+    r->n_upper[(size_t)slot] = needed;
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_ids, int32_t* counts)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(n_ids < 0 || n_ids > kRelocMaxCand || (n_ids > 0 && (!ids || !counts)))
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: bad argument (at most 64 ids)");
+    RelocState* r = c->reloc;
+    const int K = c->p.max_keypoints;
+    auto own = r->slot_of.find(id);
+    if(own == r->slot_of.end())
+        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(id) + " is not in the keyframe store");
+    LmList list{}, self{};
+    for(int k = 0; k < n_ids; ++k)
+    {
+        auto it = r->slot_of.find(ids[k]);
+        if(it == r->slot_of.end())
+            return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
+        list.slot[k] = it->second;
+    }
+    if(n_ids == 0)
+        return MSLAM_HIP_OK;
+    self.slot[0] = own->second;
+    const int n_own = r->n_upper[(size_t)own->second];
+    const size_t buckets = lm_bucket_count((size_t)n_own);
+    rc = lm_scratch(c, buckets, 1);
+    if(rc)
+        return rc;
+    hipStream_t s = c->stream;
+    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table);
+    int32_t* h_counts = reinterpret_cast<int32_t*>(r->h_lm + sizeof(LmHead));
+    for(int k = 0; k < n_ids; ++k)
+        h_counts[k] = -1; // (overwritten by k_lm_covisible; checked after the synchronisation)
+    {
+        StageScope ts(c, "covisible_clear");
+        LCHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+    }
+    {
+        StageScope ts(c, "covisible_insert");
+        hipLaunchKernelGGL(k_lm_insert, dim3((unsigned)std::max((n_own + 255) / 256, 1), 1), dim3(256), 0, s, r->d_lid, r->d_n, self, K, table,
+                           (unsigned long long)(buckets - 1), 1);
+    }
+    {
+        StageScope ts(c, "covisible_count");
+        hipLaunchKernelGGL(k_lm_covisible, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_lid, r->d_n, list, K, table,
+                           (unsigned long long)(buckets - 1), reinterpret_cast<int32_t*>(r->d_h_lm + sizeof(LmHead)));
+    }
+    LCHK(c, hipGetLastError());
+    LCHK(c, hipStreamSynchronize(s));
+    for(int k = 0; k < n_ids; ++k)
+        if(h_counts[k] < 0 || h_counts[k] > K)
+            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_covisible: the kernel left no result");
+    std::memcpy(counts, h_counts, (size_t)n_ids * 4);
+    return MSLAM_HIP_OK;
+}
+
+} // extern "C"

@@ -23,7 +23,7 @@ void reloc_destroy(RelocState* r)
 {
     if(!r)
         return;
-    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_up, r->d_arena, r->d_vote};
+    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_lid, r->d_up, r->d_arena, r->d_vote, r->d_lm_table, r->d_lm_blocks};
     for(void* p : dev)
         if(p)
             (void)hipFree(p);
@@ -33,17 +33,20 @@ void reloc_destroy(RelocState* r)
         (void)hipHostFree(r->h_res);
     if(r->h_vote)
         (void)hipHostFree(r->h_vote);
+    if(r->h_lm)
+        (void)hipHostFree(r->h_lm);
     delete r;
 }
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------
 
 // One workgroup lifts one frame of the last batch into a store slot: keypoints with a valid depth and z <= z_max, in
-// keypoint order (ballot / popcount compaction, as k_pnp_gather), world = R p + t in f64.
+// keypoint order (ballot / popcount compaction, as k_pnp_gather), world = R p + t in f64; landmark o of the entry gets the
+// fresh id lid_base | o.
 __global__ __launch_bounds__(256) void k_kf_lift(const uint8_t* __restrict__ desc, const double* __restrict__ xyz,
                                                  const uint8_t* __restrict__ valid, const int32_t* __restrict__ count, int cap,
                                                  KfPose pose, uint8_t* __restrict__ out_desc, double* __restrict__ out_world,
-                                                 int32_t* __restrict__ out_n)
+                                                 int32_t* __restrict__ out_n, int64_t* __restrict__ out_lid, int64_t lid_base)
 {
     __shared__ uint32_t wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -79,6 +82,7 @@ __global__ __launch_bounds__(256) void k_kf_lift(const uint8_t* __restrict__ des
             out_world[o * 3] = ((pose.R[0] * px + pose.R[1] * py) + pose.R[2] * pz) + pose.t[0];
             out_world[o * 3 + 1] = ((pose.R[3] * px + pose.R[4] * py) + pose.R[5] * pz) + pose.t[1];
             out_world[o * 3 + 2] = ((pose.R[6] * px + pose.R[7] * py) + pose.R[8] * pz) + pose.t[2];
+            out_lid[o] = lid_base | (int64_t)o;
         }
         running += tot;
         __syncthreads();
@@ -260,11 +264,14 @@ int mslam::store_reserve(mslam_hip_ctx* c, int want)
     uint8_t* nd = nullptr;
     double* nw = nullptr;
     int32_t* nn = nullptr;
+    int64_t* nl = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&nd), (size_t)slots * K * 32);
     if(e == hipSuccess)
         e = hipMalloc(reinterpret_cast<void**>(&nw), (size_t)slots * K * 3 * sizeof(double));
     if(e == hipSuccess)
         e = hipMalloc(reinterpret_cast<void**>(&nn), (size_t)slots * 4);
+    if(e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&nl), (size_t)slots * K * 8);
     if(e == hipSuccess)
         e = hipMemsetAsync(nn, 0, (size_t)slots * 4, c->stream);
     if(e == hipSuccess && r->slots > 0)
@@ -274,22 +281,24 @@ int mslam::store_reserve(mslam_hip_ctx* c, int want)
             e = hipMemcpyAsync(nw, r->d_world, (size_t)r->slots * K * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
         if(e == hipSuccess)
             e = hipMemcpyAsync(nn, r->d_n, (size_t)r->slots * 4, hipMemcpyDeviceToDevice, c->stream);
+        if(e == hipSuccess)
+            e = hipMemcpyAsync(nl, r->d_lid, (size_t)r->slots * K * 8, hipMemcpyDeviceToDevice, c->stream);
     }
     if(e == hipSuccess)
         e = hipStreamSynchronize(c->stream); // everything that reads the old blocks has finished before they are freed
     if(e != hipSuccess)
     {
-        void* fresh[] = {nd, nw, nn};
+        void* fresh[] = {nd, nw, nn, nl};
         for(void* p : fresh)
             if(p)
                 (void)hipFree(p);
         return rfail(c, MSLAM_HIP_E_RUNTIME, std::string("kf store: ") + hipGetErrorString(e));
     }
-    void* old[] = {r->d_desc, r->d_world, r->d_n};
+    void* old[] = {r->d_desc, r->d_world, r->d_n, r->d_lid};
     for(void* p : old)
         if(p)
             (void)hipFree(p);
-    r->d_desc = nd, r->d_world = nw, r->d_n = nn;
+    r->d_desc = nd, r->d_world = nw, r->d_n = nn, r->d_lid = nl;
     for(int s = slots - 1; s >= r->slots; --s)
         r->free_slots.push_back(s); // (handed out in ascending order)
     r->n_upper.resize((size_t)slots, 0);
@@ -319,6 +328,53 @@ int mslam::store_slot_for(mslam_hip_ctx* c, int id, int* slot)
     return MSLAM_HIP_OK;
 }
 
+int64_t mslam::store_next_lid_base(mslam_hip_ctx* c)
+{
+    return fresh_lid_base(++c->reloc->serial);
+}
+
+// mslam_hip_kf_add (landmark_ids == nullptr: fresh ids) and mslam_hip_kf_add_ids
+static int kf_add_host(mslam_hip_ctx* c, const char* who, int id, const uint8_t* desc, const double* world_xyz,
+                       const int64_t* landmark_ids, bool own_ids, int n)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(n < 0 || (n > 0 && (!desc || !world_xyz || (own_ids && !landmark_ids))))
+        return rfail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument");
+    if(n > c->p.max_keypoints)
+        return rfail(c, MSLAM_HIP_E_CAPACITY, std::string(who) + ": more landmarks than the context's max_keypoints");
+    for(int i = 0; own_ids && i < n; ++i)
+        if(landmark_ids[i] < 0 || landmark_ids[i] >= kFreshLidBit)
+            return rfail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": landmark ids lie in [0, 2^62)");
+    int slot = -1;
+    rc = store_slot_for(c, id, &slot);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    const size_t K = (size_t)c->p.max_keypoints;
+    const int32_t n32 = n;
+    const int64_t base = store_next_lid_base(c);
+    std::vector<int64_t> fresh;
+    if(!own_ids)
+    {
+        fresh.resize((size_t)n);
+        for(int i = 0; i < n; ++i)
+            fresh[(size_t)i] = base | (int64_t)i;
+        landmark_ids = fresh.data();
+    }
+    if(n > 0)
+    {
+        RCHK(c, hipMemcpyAsync(r->d_desc + (size_t)slot * K * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+        RCHK(c, hipMemcpyAsync(r->d_world + (size_t)slot * K * 3, world_xyz, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+        RCHK(c, hipMemcpyAsync(r->d_lid + (size_t)slot * K, landmark_ids, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    RCHK(c, hipMemcpyAsync(r->d_n + slot, &n32, 4, hipMemcpyHostToDevice, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream)); // host-pointer entry point: the caller's buffers are free on return
+    r->n_upper[(size_t)slot] = n;
+    return MSLAM_HIP_OK;
+}
+
 extern "C" {
 
 int mslam_hip_kf_reserve(mslam_hip_ctx* c, int max_entries)
@@ -341,29 +397,12 @@ int mslam_hip_kf_size(mslam_hip_ctx* c, int* n_entries)
 
 int mslam_hip_kf_add(mslam_hip_ctx* c, int id, const uint8_t* desc, const double* world_xyz, int n)
 {
-    int rc = reloc_enter(c);
-    if(rc)
-        return rc;
-    if(n < 0 || (n > 0 && (!desc || !world_xyz)))
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add: bad argument");
-    if(n > c->p.max_keypoints)
-        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_add: more landmarks than the context's max_keypoints");
-    int slot = -1;
-    rc = store_slot_for(c, id, &slot);
-    if(rc)
-        return rc;
-    RelocState* r = c->reloc;
-    const size_t K = (size_t)c->p.max_keypoints;
-    const int32_t n32 = n;
-    if(n > 0)
-    {
-        RCHK(c, hipMemcpyAsync(r->d_desc + (size_t)slot * K * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-        RCHK(c, hipMemcpyAsync(r->d_world + (size_t)slot * K * 3, world_xyz, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-    }
-    RCHK(c, hipMemcpyAsync(r->d_n + slot, &n32, 4, hipMemcpyHostToDevice, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream)); // host-pointer entry point: the caller's buffers are free on return
-    r->n_upper[(size_t)slot] = n;
-    return MSLAM_HIP_OK;
+    return kf_add_host(c, "kf_add", id, desc, world_xyz, nullptr, false, n);
+}
+
+int mslam_hip_kf_add_ids(mslam_hip_ctx* c, int id, const uint8_t* desc, const double* world_xyz, const int64_t* landmark_ids, int n)
+{
+    return kf_add_host(c, "kf_add_ids", id, desc, world_xyz, landmark_ids, true, n);
 }
 
 int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const double* R, const double* t, double z_max)
@@ -387,13 +426,14 @@ int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const d
     std::memcpy(pose.R, R, sizeof(pose.R));
     std::memcpy(pose.t, t, sizeof(pose.t));
     pose.z_max = z_max;
+    const int64_t lid_base = store_next_lid_base(c);
     {
         StageScope ts(c, "kf_lift");
         // frame f of the batch: descriptors in output slot f + 1, points in row f of the back-projection
         hipLaunchKernelGGL(k_kf_lift, dim3(1), dim3(256), 0, c->stream, c->d_desc + (size_t)(frame + 1) * K * 32,
                            c->d_xyz + (size_t)frame * K * 3, c->d_valid + (size_t)frame * K, c->d_count + 1 + frame,
                            c->p.max_keypoints, pose, r->d_desc + (size_t)slot * K * 32, r->d_world + (size_t)slot * K * 3,
-                           r->d_n + slot);
+                           r->d_n + slot, r->d_lid + (size_t)slot * K, lid_base);
     }
     RCHK(c, hipGetLastError());
     r->n_upper[(size_t)slot] = c->p.max_keypoints; // (the count stays on the device)
@@ -455,6 +495,35 @@ int mslam_hip_kf_read(mslam_hip_ctx* c, int id, uint8_t* desc, double* world_xyz
         RCHK(c, hipMemcpyAsync(desc, r->d_desc + slot * K * 32, (size_t)n32 * 32, hipMemcpyDeviceToHost, c->stream));
     if(world_xyz && n32 > 0)
         RCHK(c, hipMemcpyAsync(world_xyz, r->d_world + slot * K * 3, (size_t)n32 * 24, hipMemcpyDeviceToHost, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream));
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_read_ids(mslam_hip_ctx* c, int id, int64_t* landmark_ids, int capacity, int* n)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(!n || capacity < 0)
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read_ids: bad argument");
+    RelocState* r = c->reloc;
+    auto it = r->slot_of.find(id);
+    if(it == r->slot_of.end())
+        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read_ids: no such keyframe id");
+    const size_t K = (size_t)c->p.max_keypoints, slot = (size_t)it->second;
+    int32_t n32 = 0;
+    RCHK(c, hipMemcpyAsync(&n32, r->d_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
+    RCHK(c, hipStreamSynchronize(c->stream));
+    if(n32 < 0 || (size_t)n32 > K)
+        return rfail(c, MSLAM_HIP_E_RUNTIME, "kf_read_ids: impossible landmark count");
+    *n = n32;
+    r->n_upper[slot] = n32; // now known exactly
+    if(!landmark_ids)
+        return MSLAM_HIP_OK;
+    if(n32 > capacity)
+        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_read_ids: the entry has more landmarks than `capacity`");
+    if(n32 > 0)
+        RCHK(c, hipMemcpyAsync(landmark_ids, r->d_lid + slot * K, (size_t)n32 * 8, hipMemcpyDeviceToHost, c->stream));
     RCHK(c, hipStreamSynchronize(c->stream));
     return MSLAM_HIP_OK;
 }

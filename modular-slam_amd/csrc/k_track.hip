@@ -107,10 +107,13 @@ struct KeyframeArgs
     const uint8_t* valid;
     int nq, S;
     double z_max;
-    // the store: the reference entry's world points, the new entry's slot
+    // the store: the reference entry's world points and landmark ids, the new entry's slot
     const double* ref_world;
+    const int64_t* ref_lid;
     uint8_t* out_desc;
     double* out_world;
+    int64_t* out_lid;
+    int64_t lid_base; // landmark o of part B gets the fresh id lid_base | o
     int32_t* out_n;
     int cap;
     // mapped host block
@@ -127,7 +130,7 @@ __device__ __forceinline__ void copy_desc(const uint8_t* __restrict__ src, uint8
 }
 
 // One workgroup builds the new keyframe's entry in its store slot.  Part A: the inlier correspondences in correspondence
-// order, with the reference entry's world points copied bit for bit.  Part B: every keypoint no correspondence used, with a
+// order, with the reference entry's world points and landmark ids copied bit for bit.  Part B: every keypoint no correspondence used, with a
 // valid depth and z <= z_max, in keypoint order, lifted with world = R^T (p - t).  Ordered ballot / prefix compaction as
 // k_kf_lift.  nq <= 65536 (the host checks nq <= cap <= 65535).  There is one match per reference landmark, so two
 // landmarks can name the same keypoint and part A then lists it twice: A and B together can exceed nq, and every store
@@ -188,6 +191,7 @@ __global__ __launch_bounds__(256) void k_track_keyframe(KeyframeArgs a)
             copy_desc(a.desc + (size_t)from * 32, a.out_desc + o * 32);
             const double* P = a.ref_world + (size_t)to * 3;
             a.out_world[o * 3] = P[0], a.out_world[o * 3 + 1] = P[1], a.out_world[o * 3 + 2] = P[2];
+            a.out_lid[o] = a.ref_lid[to];
             a.h_src[o] = to, a.h_kp[o] = from;
         }
         run_c += tot_c;
@@ -225,6 +229,7 @@ __global__ __launch_bounds__(256) void k_track_keyframe(KeyframeArgs a)
             a.out_world[o * 3] = (rec[0] * dx + rec[3] * dy) + rec[6] * dz; // R^T (p - t): column r of R
             a.out_world[o * 3 + 1] = (rec[1] * dx + rec[4] * dy) + rec[7] * dz;
             a.out_world[o * 3 + 2] = (rec[2] * dx + rec[5] * dy) + rec[8] * dz;
+            a.out_lid[o] = a.lid_base | (int64_t)o;
             a.h_src[o] = -1, a.h_kp[o] = i;
         }
         run += tot;
@@ -271,6 +276,7 @@ struct TrackCall
     int n, n_vote, ref_slot, new_slot;
     int min_matched, kf_min_landmarks;
     double z_max;
+    int64_t lid_base;
     size_t off_depth;              // in the extra upload block: [vote slots 64 x i32 | depth]
     size_t off_valid, off_counts;  // in the extra arena: [xyz n x 3 f64 | valid n | vote counts 64 x i32]
     double* d_xyz = nullptr;
@@ -326,6 +332,9 @@ int track_before_sync(mslam_hip_ctx* c, void* user, const RelocDev& d)
         a.min_matched = t->min_matched, a.kf_min_landmarks = t->kf_min_landmarks;
         a.desc = d.desc, a.xyz = t->d_xyz, a.valid = t->d_valid, a.nq = t->n, a.S = d.S, a.z_max = t->z_max;
         a.ref_world = r->d_world + (size_t)t->ref_slot * K * 3;
+        a.ref_lid = r->d_lid + (size_t)t->ref_slot * K;
+        a.out_lid = r->d_lid + (size_t)t->new_slot * K;
+        a.lid_base = t->lid_base;
         a.out_desc = r->d_desc + (size_t)t->new_slot * K * 32;
         a.out_world = r->d_world + (size_t)t->new_slot * K * 3;
         a.out_n = r->d_n + t->new_slot;
@@ -472,6 +481,7 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
         rc = store_slot_for(c, new_id, &tc.new_slot);
         if(rc)
             return rc;
+        tc.lid_base = store_next_lid_base(c); // (the serial advances whether or not the step makes the keyframe)
     }
     auto release = [&]() { // a slot reserved for new_id that received no entry
         if(new_id >= 0 && !existed)

@@ -27,6 +27,8 @@ struct RelocState
     uint8_t* d_desc = nullptr;
     double* d_world = nullptr;
     int32_t* d_n = nullptr;
+    int64_t* d_lid = nullptr;             // [slots][K] landmark ids: what makes a landmark the same one in two entries
+    uint64_t serial = 0;                  // creation serial of the last entry made (the first one is 1): part of its fresh ids
     std::unordered_map<int, int> slot_of; // id -> slot
     std::vector<int> free_slots;
     std::vector<int> n_upper;             // per slot: an upper bound of n the host knows (exact for host adds, K for device lifts)
@@ -42,7 +44,24 @@ struct RelocState
     // result [best, best count, pad | counts 64 x i32] page-locked and device-mapped
     uint8_t* d_vote = nullptr;
     uint8_t *h_vote = nullptr, *d_h_vote = nullptr;
+    // ---- scratch of mslam_hip_kf_union / mslam_hip_kf_covisible (k_localmap.hip), grown on demand: the hash table
+    // ({u64 key, u64 val} buckets), the per-block arrays [win masks | counts | offsets], and the mapped result
+    // [needed count, pad | covisibility counts 64 x i32]
+    uint8_t* d_lm_table = nullptr;
+    size_t lm_buckets = 0;
+    uint8_t* d_lm_blocks = nullptr;
+    size_t lm_blocks = 0;
+    uint8_t *h_lm = nullptr, *d_h_lm = nullptr;
 };
+
+// A fresh landmark id: (1 << 62) | (serial << 16) | position in the entry.  Entries hold at most 65535 landmarks and the
+// serial is known on the host before anything is enqueued, so no device counter is involved.  Caller-supplied ids lie in
+// [0, 2^62) and can never collide with these.
+constexpr int64_t kFreshLidBit = (int64_t)1 << 62;
+inline int64_t fresh_lid_base(uint64_t serial)
+{
+    return kFreshLidBit | (int64_t)((serial << 16) & (((uint64_t)1 << 62) - 1));
+}
 
 struct KfPose
 {
@@ -87,6 +106,7 @@ int reloc_enter(mslam_hip_ctx* c);
 int reloc_fail(mslam_hip_ctx* c, int code, const std::string& msg);
 int store_reserve(mslam_hip_ctx* c, int want);
 int store_slot_for(mslam_hip_ctx* c, int id, int* slot);
+int64_t store_next_lid_base(mslam_hip_ctx* c); // advances the creation serial: call once per entry made, after store_slot_for
 
 // k_points.hip: k_backproject on one frame of n keypoints, device pointers, enqueued on `s`
 void launch_backproject(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy, double cx,

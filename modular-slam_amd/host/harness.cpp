@@ -22,6 +22,10 @@
 //                                    IKeyframeTracker: initFirstKeyframe, then per frame trackKeyframe against the reference
 //                                    keyframe with the previous pose as the guess; the vote's winner becomes the reference,
 //                                    an inserted keyframe too; relocalizePose when tracking fails.  One line per frame.
+//        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> --local-map <depth>
+//                                    the same loop against the local map, as the reference tracks (:256-277): ILocalMapTracker's
+//                                    buildLocalMap over the reference keyframe's covisibility neighbourhood (rebuilt when the
+//                                    reference changes or a keyframe is added), trackLocalMap, covisibleLandmarks for the edges
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -30,7 +34,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <fstream>
+#include <map>
+#include <set>
 
 static std::uint32_t fnv(const void* p, std::size_t n, std::uint32_t h = 0x811C9DC5u)
 {
@@ -198,8 +205,11 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if(argc == 5 && std::strcmp(argv[2], "--track") == 0)
+        if((argc == 5 || (argc == 7 && std::strcmp(argv[5], "--local-map") == 0)) && std::strcmp(argv[2], "--track") == 0)
         {
+            // --local-map <depth>: track against the union of the reference keyframe's covisibility neighbourhood
+            // (ILocalMapTracker) instead of the reference keyframe's own landmarks; the reference uses depth 2
+            const int mapDepth = argc == 7 ? std::atoi(argv[6]) : -1;
             // scene file, little-endian: 'MSTK', i32 version = 1, n_frames, width, height; f64 fx, fy, cx, cy; f32 factor; i32 seed,
             // min_matched_points, new_keyframe_min_landmarks; f64 z_max; per frame: i32 n, n x 32 descriptor bytes, n x 2 f32
             // keypoint coordinates, height x width u16 depth
@@ -208,7 +218,8 @@ int main(int argc, char** argv)
             std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
             auto* tracker = dynamic_cast<mslam::IKeyframeTracker*>(relocalizer.get());
             auto* verified = dynamic_cast<mslam::IVerifiedRelocalizer*>(relocalizer.get());
-            if(!tracker || !verified)
+            auto* localMap = dynamic_cast<mslam::ILocalMapTracker*>(relocalizer.get());
+            if(!tracker || !verified || (mapDepth >= 0 && !localMap))
             {
                 std::fprintf(stderr, "the plugin does not offer the keyframe tracking step\n");
                 return 6;
@@ -238,6 +249,11 @@ int main(int argc, char** argv)
             using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
             std::vector<std::shared_ptr<Kf>> keyframes; // in insertion order: the vote's list (its most recent 64)
             std::shared_ptr<Kf> reference;
+            // the local map: the covisibility graph over keyframe ids (updateCovisibility, basic_map.cpp:141-164), the members of
+            // the union built last and the reference keyframe it was built for (null: rebuild)
+            std::map<mslam::Id, std::set<mslam::Id>> graph;
+            std::vector<std::shared_ptr<Kf>> members;
+            std::shared_ptr<Kf> mapOf;
             double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
             std::vector<std::uint16_t> depth(static_cast<std::size_t>(width) * height);
             for(int f = 0; f < nFrames; ++f)
@@ -271,6 +287,7 @@ int main(int argc, char** argv)
                     keyframes.push_back(kf);
                     reference = kf;
                     added = 0;
+                    graph[kf->id];
                 }
                 else
                 {
@@ -279,7 +296,33 @@ int main(int argc, char** argv)
                     auto kf = std::make_shared<Kf>();
                     kf->id = keyframes.back()->id + 1;
                     opt.seed = static_cast<std::uint64_t>(par[0]) + static_cast<std::uint64_t>(f);
-                    const auto r = tracker->trackKeyframe(kps, depth.data(), width, height, cp, reference, neighbours, rvec, tvec, kf, opt);
+                    if(mapDepth >= 0 && mapOf != reference)
+                    {
+                        // getNeighbourKeyframes (basic_map.cpp:209-237) as written: `level <= deepLevel` still expands the nodes
+                        // at level mapDepth, so the walk reaches mapDepth + 1 hops; more than 64 keyframes: the 64 largest ids
+                        std::set<mslam::Id> result;
+                        std::deque<std::pair<mslam::Id, int>> queue{{reference->id, 0}};
+                        while(!queue.empty())
+                        {
+                            const auto [cur, level] = queue.front();
+                            queue.pop_front();
+                            result.insert(cur);
+                            if(level <= mapDepth)
+                                for(const mslam::Id nb : graph[cur])
+                                    if(!result.count(nb))
+                                        queue.emplace_back(nb, level + 1);
+                        }
+                        members.clear();
+                        for(const auto& k : keyframes) // (ascending ids)
+                            if(result.count(k->id))
+                                members.push_back(k);
+                        if(members.size() > 64)
+                            members.erase(members.begin(), members.end() - 64);
+                        localMap->buildLocalMap(members);
+                        mapOf = reference;
+                    }
+                    const auto r = mapDepth >= 0 ? localMap->trackLocalMap(kps, depth.data(), width, height, cp, neighbours, rvec, tvec, kf, opt)
+                                                 : tracker->trackKeyframe(kps, depth.data(), width, height, cp, reference, neighbours, rvec, tvec, kf, opt);
                     tracked = r.tracked ? 1 : 0, inliers = r.inliers;
                     if(r.tracked)
                     {
@@ -292,6 +335,19 @@ int main(int argc, char** argv)
                             keyframes.push_back(kf);
                             reference = kf; // (:395-396)
                             added = static_cast<long long>(kf->id);
+                            if(mapDepth >= 0)
+                            {
+                                // part A of the new entry inherits from the union: only its members can share landmarks with it
+                                const auto shared = localMap->covisibleLandmarks(kf, members);
+                                graph[kf->id];
+                                for(std::size_t k = 0; k < members.size(); ++k)
+                                    if(shared[k] > 0 && members[k]->id != kf->id)
+                                    {
+                                        graph[kf->id].insert(members[k]->id);
+                                        graph[members[k]->id].insert(kf->id);
+                                    }
+                                mapOf = nullptr; // a keyframe was added: the local map is rebuilt
+                            }
                         }
                     }
                     else if(auto found = verified->relocalizePose(kps, cp).keyframe) // (:210-217)

@@ -293,10 +293,10 @@ class BowDatabase
 
     // ---- extension: candidates verified against stored landmarks (mslam_hip_relocalize) ----
     void addKeyframeLandmarks(const KeyframePtr& keyframe, const std::vector<OrbKeypoint>& keypoints,
-                              const std::vector<Vector3>& worldPoints)
+                              const std::vector<Vector3>& worldPoints, const std::vector<std::int64_t>* landmarkIds = nullptr)
     {
-        if(keypoints.size() != worldPoints.size())
-            throw std::runtime_error("addKeyframeLandmarks: one world point per keypoint");
+        if(keypoints.size() != worldPoints.size() || (landmarkIds && landmarkIds->size() != keypoints.size()))
+            throw std::runtime_error("addKeyframeLandmarks: one world point (and one landmark id) per keypoint");
         for(const auto& e : entryToKeyframe)
             if(e.second == keyframe)
             {
@@ -305,9 +305,11 @@ class BowDatabase
                 for(std::size_t i = 0; i < worldPoints.size(); ++i)
                     world[3 * i] = worldPoints[i].x(), world[3 * i + 1] = worldPoints[i].y(), world[3 * i + 2] = worldPoints[i].z();
                 // the store's id is the BoW entry id: one id names both (a keyframe track() inserted has an id of its own)
-                const int rc = mslam_hip_kf_add(ctx.h, e.first, desc.data(), world.data(), static_cast<int>(keypoints.size()));
+                const int n = static_cast<int>(keypoints.size());
+                const int rc = landmarkIds ? mslam_hip_kf_add_ids(ctx.h, e.first, desc.data(), world.data(), landmarkIds->data(), n)
+                                           : mslam_hip_kf_add(ctx.h, e.first, desc.data(), world.data(), n);
                 if(rc != MSLAM_HIP_OK)
-                    raise(ctx.h, "mslam_hip_kf_add", rc);
+                    raise(ctx.h, landmarkIds ? "mslam_hip_kf_add_ids" : "mslam_hip_kf_add", rc);
                 storeId[e.first] = e.first;
                 return;
             }
@@ -382,7 +384,63 @@ class BowDatabase
                                       const std::vector<KeyframePtr>& neighbours, const double* rvecGuess, const double* tvecGuess,
                                       const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
     {
-        const int refId = storedLandmarksOf(reference);
+        return trackAgainst(storedLandmarksOf(reference), keypoints, depth, width, height, camera, neighbours, rvecGuess, tvecGuess,
+                            newKeyframe, o);
+    }
+
+    // ---- extension: the local map (mslam_hip_kf_read_ids, mslam_hip_kf_covisible, mslam_hip_kf_union) ----
+    std::vector<std::int64_t> landmarkIds(const KeyframePtr& keyframe)
+    {
+        const int id = storedLandmarksOf(keyframe);
+        int n = 0;
+        int rc = mslam_hip_kf_read_ids(ctx.h, id, nullptr, 0, &n);
+        std::vector<std::int64_t> out(static_cast<std::size_t>(n) + 1);
+        if(rc == MSLAM_HIP_OK)
+            rc = mslam_hip_kf_read_ids(ctx.h, id, out.data(), n, &n);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_read_ids", rc);
+        out.resize(static_cast<std::size_t>(n));
+        return out;
+    }
+
+    std::vector<int> covisibleLandmarks(const KeyframePtr& keyframe, const std::vector<KeyframePtr>& others)
+    {
+        std::vector<std::int32_t> ids(others.size() + 1), counts(others.size() + 1);
+        for(std::size_t k = 0; k < others.size(); ++k)
+            ids[k] = storedLandmarksOf(others[k]);
+        const int rc = mslam_hip_kf_covisible(ctx.h, storedLandmarksOf(keyframe), ids.data(), static_cast<int>(others.size()), counts.data());
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_covisible", rc);
+        return std::vector<int>(counts.begin(), counts.begin() + static_cast<std::ptrdiff_t>(others.size()));
+    }
+
+    int buildLocalMap(const std::vector<KeyframePtr>& members)
+    {
+        std::vector<std::int32_t> ids(members.size() + 1);
+        for(std::size_t k = 0; k < members.size(); ++k)
+            ids[k] = storedLandmarksOf(members[k]);
+        int n = 0;
+        const int rc = mslam_hip_kf_union(ctx.h, kLocalMapId, ids.data(), static_cast<int>(members.size()), &n);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_union", rc);
+        haveLocalMap = true;
+        return n;
+    }
+
+    KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                      const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours,
+                                      const double* rvecGuess, const double* tvecGuess, const KeyframePtr& newKeyframe,
+                                      const KeyframeTrackOptions& o)
+    {
+        if(!haveLocalMap)
+            throw std::runtime_error("trackLocalMap: no local map has been built");
+        return trackAgainst(kLocalMapId, keypoints, depth, width, height, camera, neighbours, rvecGuess, tvecGuess, newKeyframe, o);
+    }
+
+    KeyframeTrackResult trackAgainst(int refId, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                     const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
+                                     const double* tvecGuess, const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
+    {
         std::vector<std::int32_t> vote(neighbours.size() + 1), counts(neighbours.size() + 1);
         for(std::size_t k = 0; k < neighbours.size(); ++k)
             vote[k] = storedLandmarksOf(neighbours[k]);
@@ -508,12 +566,14 @@ class BowDatabase
     std::map<int, KeyframePtr> entryToKeyframe;
     std::map<int, int> storeId; // BoW entry -> id of its landmarks in the keyframe store (entries without landmarks: absent)
     int nextTrackedId = 1 << 30; // store ids of the keyframes trackKeyframe inserts (BoW entry ids count from 0)
+    static constexpr int kLocalMapId = 0x7fffffff; // the store id of the local map (above every keyframe's)
+    bool haveLocalMap = false;
     std::vector<float> xy;
     KeyframePtr lastLoop;
     std::vector<OrbKeypoint> lastFed;
 };
 
-class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, public IKeyframeTracker
+class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, public IKeyframeTracker, public ILocalMapTracker
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -553,6 +613,24 @@ class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, p
                                       const CameraParameters& camera, int width, int height, int* best) override
     {
         return db->visibleLandmarks(neighbours, R, t, camera, width, height, best);
+    }
+    void addKeyframeLandmarksWithIds(BowDatabase::KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints,
+                                     const std::vector<Vector3>& worldPoints, const std::vector<std::int64_t>& landmarkIds) override
+    {
+        db->addKeyframeLandmarks(keyframe, keypoints, worldPoints, &landmarkIds);
+    }
+    std::vector<std::int64_t> landmarkIds(BowDatabase::KeyframePtr keyframe) override { return db->landmarkIds(keyframe); }
+    std::vector<int> covisibleLandmarks(BowDatabase::KeyframePtr keyframe, const std::vector<BowDatabase::KeyframePtr>& others) override
+    {
+        return db->covisibleLandmarks(keyframe, others);
+    }
+    int buildLocalMap(const std::vector<BowDatabase::KeyframePtr>& members) override { return db->buildLocalMap(members); }
+    KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                      const CameraParameters& camera, const std::vector<BowDatabase::KeyframePtr>& neighbours,
+                                      const double* rvecGuess, const double* tvecGuess, BowDatabase::KeyframePtr newKeyframe,
+                                      const KeyframeTrackOptions& options) override
+    {
+        return db->trackLocalMap(keypoints, depth, width, height, camera, neighbours, rvecGuess, tvecGuess, newKeyframe, options);
     }
 
   private:

@@ -272,4 +272,32 @@ class IKeyframeTracker
                                               const CameraParameters& camera, int width, int height, int* best) = 0;
     virtual ~IKeyframeTracker() = default;
 };
+// ---- extension (not in the reference): tracking against the local map (mslam_hip_kf_union, mslam_hip_kf_covisible) ---------
+// What getLandmarksWithKeypoints gives track() (rgbd_feature_frontend.cpp:256-277): the most recent observation of every
+// landmark seen from a set of keyframes, built on the device from the landmark ids the store keeps.  The caller owns the
+// covisibility graph and chooses the members (BasicMap::getNeighbourKeyframes, basic_map.cpp:209-237); the adapter keeps
+// the union under a store id of its own.  Offered by the adapter that offers IKeyframeTracker.
+class ILocalMapTracker
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    // addKeyframeLandmarks with the caller's landmark ids (each in [0, 2^62)): landmarkIds[i] belongs to keypoints[i]
+    virtual void addKeyframeLandmarksWithIds(KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints,
+                                             const std::vector<Vector3>& worldPoints, const std::vector<std::int64_t>& landmarkIds) = 0;
+    // the landmark ids of a keyframe's stored landmarks, in entry order
+    virtual std::vector<std::int64_t> landmarkIds(KeyframePtr keyframe) = 0;
+    // per keyframe of `others` (at most 64): how many distinct landmarks of `keyframe` it observes as well; > 0 is
+    // updateCovisibility's edge (basic_map.cpp:141-164)
+    virtual std::vector<int> covisibleLandmarks(KeyframePtr keyframe, const std::vector<KeyframePtr>& others) = 0;
+    // the local map of `members` (1 to 64 keyframes): per landmark the observation of the member with the largest store
+    // id (the one stored last); returns its number of landmarks.  Throws when they exceed the context's max_keypoints.
+    virtual int buildLocalMap(const std::vector<KeyframePtr>& members) = 0;
+    // IKeyframeTracker::trackKeyframe against the local map built last instead of a reference keyframe's own landmarks;
+    // entrySource indexes the local map
+    virtual KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+                                              const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours,
+                                              const double* rvecGuess, const double* tvecGuess, KeyframePtr newKeyframe,
+                                              const KeyframeTrackOptions& options = KeyframeTrackOptions()) = 0;
+    virtual ~ILocalMapTracker() = default;
+};
 } // namespace mslam

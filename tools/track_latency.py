@@ -6,7 +6,13 @@ are timed alternately, in blocks, so that drift of the machine hits both, and th
 the same process: the difference between the runs is the spread a difference between the sides has to exceed.
 
 usage: python tools/track_latency.py [--blocks 12] [--calls 100] [--runs 2] [--out file.json] [--trace new|old]
-       (--trace: a short run of one side only, for rocprofv3 --kernel-trace --stats)"""
+       (--trace: a short run of one side only, for rocprofv3 --kernel-trace --stats)
+
+--local-map: tracking against the local map instead (16 keyframes of 1500 landmarks, each sharing half of them with the
+next one, so their union holds 12750; the same query).  Timed alternately, in blocks, in the same process: the union
+build on its own (mslam_hip_kf_union of the 16 entries, one synchronisation), the track step against the union, and the
+single-reference track step against one of the 16 entries.  A tracker pays the build only when the reference keyframe
+changes or a keyframe is added, the step every frame."""
 import argparse
 import json
 import os
@@ -28,10 +34,13 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--out")
     ap.add_argument("--trace", choices=["new", "old"])
+    ap.add_argument("--local-map", action="store_true")
     a = ap.parse_args()
     import reloc_ref as rr
     import track_ref as tr
     pkg = graft.load_package()
+    if a.local_map:
+        return local_map(a, pkg, rr)
     sc = rr.make_scene(seed=0, n_kf=8, n_landmarks=600, n_distractors=1360)        # 540 + 1360 = 1900 query keypoints
     ids, ref_id, new_id = sc["ids"], sc["target_id"], 500
     desc, xy = sc["desc"], sc["xy"]
@@ -94,6 +103,63 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
+
+
+def local_map(a, pkg, rr):
+    n_kf, n_lm, U = 16, 1500, 0x7fffffff
+    sc = rr.make_scene(seed=0, n_kf=n_kf, n_landmarks=n_lm, n_distractors=400)
+    ids, ref_id, new_id = sc["ids"], sc["target_id"], 500
+    desc, xy = sc["desc"], sc["xy"]
+    depth = np.tile(((2.0 + 2.0 * np.arange(640) / 640) * 5000).astype(np.uint16), (480, 1))
+    world = sc["store"][ref_id][1]
+    for i, l in enumerate(sc["from_landmark"]):
+        x, y = int(xy[i, 0]), int(xy[i, 1])
+        if l >= 0 and 0 <= x < 640 and 0 <= y < 480:
+            depth[y, x] = np.uint16(round(float((sc["R"] @ world[l] + sc["t"])[2]) * 5000))
+    c = pkg.Context(width=0, height=0, max_keypoints=16384)
+    for k, cid in enumerate(ids):                       # entry k shares its upper half with the lower half of entry k + 1
+        c.kf_add(cid, *sc["store"][cid], lids=k * (n_lm // 2) + np.arange(n_lm))
+    kw = dict(seed=1, new_keyframe_min_landmarks=1 << 20)
+
+    def build():
+        return c.kf_union(U, ids)
+
+    def step_map():
+        return c.track(desc, xy, depth, U, ids, new_id, with_entry=True, **kw)
+
+    def step_single():
+        return c.track(desc, xy, depth, ref_id, ids, new_id, with_entry=True, **kw)
+    n_union = build()
+    rm, rs = step_map(), step_single()
+    assert n_union == (n_kf + 1) * (n_lm // 2) and rm["tracked"] and rs["tracked"] and rm["keyframe_added"] and rs["keyframe_added"]
+    sides = (("union_build", build), ("track_local_map", step_map), ("track_single_reference", step_single))
+    for _ in range(30):
+        for _, f in sides:
+            f()
+    runs = []
+    for _ in range(a.runs):
+        res = {name: [] for name, _ in sides}
+        for _ in range(a.blocks):
+            for name, f in sides:
+                t0 = time.perf_counter()
+                for _ in range(a.calls):
+                    f()                               # every call ends in a device synchronise
+                res[name].append((time.perf_counter() - t0) / a.calls * 1e6)
+        runs.append({k: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v)),
+                             blocks=[round(x, 2) for x in v]) for k, v in res.items()})
+    c.set_profiling(2)
+    build()
+    stages = [(n, round(ms * 1e3, 2)) for n, ms in c.stage_times() if n.startswith("union_")]
+    c.set_profiling(0)
+    out = dict(runs=runs, shape=dict(query=len(desc), keyframes=n_kf, landmarks_per_keyframe=n_lm, union_landmarks=n_union,
+                                     vote_ids=len(ids), calls_per_block=a.calls, blocks=a.blocks),
+               union_stages_us=stages,
+               step_local_map=dict(n_matches=rm["n_matches"], n_correspondences=rm["n_correspondences"], n_inliers=rm["n_inliers"]),
+               step_single=dict(n_matches=rs["n_matches"], n_correspondences=rs["n_correspondences"], n_inliers=rs["n_inliers"]))
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
