@@ -270,7 +270,10 @@ int mslam_hip_qlz_decompress(const void* src, size_t src_size, uint32_t n_packet
  * isDepthValid (types/depth_frame.hpp:20-30).  depth = DepthFrame::data (u16, row-major, width*height),
  * factor / focal / principal point = CameraParameters (sensors/camera_parameters.hpp:7-12; TUM: 1/5000, 525,
  * 525, 319.5, 239.5 — rgbd_file_provider.cpp:136-145).  xy = keypoint coordinates as returned by detect.
- * xyz[3i..3i+2] is the camera-frame point, valid[i] = 1 iff the depth is valid (std::optional engaged). */
+ * xyz[3i..3i+2] is the camera-frame point, valid[i] = 1 iff the depth is valid (std::optional engaged).
+ * The pixel is the coordinate truncated toward zero (-0.5 is pixel 0, -1.0 is outside).  A coordinate that is not finite
+ * (NaN, +-inf), or whose pixel is outside the image, gives valid[i] = 0 and the point (0, 0, 0), as every invalid depth
+ * does.  fx or fy of zero or NaN: MSLAM_HIP_E_INVALID. */
 int mslam_hip_backproject(mslam_hip_ctx* ctx, const uint16_t* depth, int width, int height, float factor, double fx,
                           double fy, double cx, double cy, const float* xy, int n, double* xyz, uint8_t* valid);
 /* Batched device form: every keypoint of the last detect batch against d_depth = n_frames back-to-back

@@ -2,7 +2,8 @@
 //
 // Replaces pointsFromRgbdKeypoints + reconstructPoint (reference rgbd_feature_frontend.cpp:101-138) with
 // getDepth / isDepthValid (types/depth_frame.hpp:20-30):
-//   imgPoint = coordinates.cast<int>()                      (truncation of the double coordinates)
+//   imgPoint = coordinates.cast<int>()                      (truncation of the double coordinates toward zero)
+//   no depth  for a coordinate that is not finite or whose pixel is outside [0, w) x [0, h): valid = 0, the point is zero
 //   depth    = (float)data[w*y + x] * factor                (float multiply; TUM factor = 1/5000, rgbd_file_provider.cpp:136-145)
 //   valid    = depth > FLT_EPSILON
 //   X = (x - cx) * z * (1/fx),  Y = (y - cy) * z * (1/fy),  Z = z      (double, left to right; z = (double)depth)
@@ -32,10 +33,15 @@ __global__ __launch_bounds__(256) void k_backproject(const uint16_t* __restrict_
         return;
     const float* p = xy + frame * xy_stride + 2 * (size_t)i;
     const double x = (double)p[0], y = (double)p[1]; // the adapter widens the float coordinates (:1207-1208)
-    const int ix = (int)x, iy = (int)y;
+    // A coordinate that is not finite has no pixel.  The range test runs on the doubles and the cast only on values that
+    // passed it: (int)NaN is whatever the conversion instruction makes of it (0 on gfx950: the point would read column or
+    // row 0 and come back valid with NaN in it), and casting a value no int holds is undefined.  Truncation toward zero
+    // puts (-1, 0) into pixel 0, so "pixel in [0, n)" is "-1 < c < n": false for NaN (every comparison is) and for +-inf.
+    // (& not &&: one test, not a ladder of branches)
+    const bool inside = (x > -1.0) & (x < (double)w) & (y > -1.0) & (y < (double)h);
     float d = 0.f;
-    if(ix >= 0 && ix < w && iy >= 0 && iy < h)
-        d = __fmul_rn((float)depth[frame * depth_stride + (size_t)w * iy + ix], cam.factor);
+    if(inside)
+        d = __fmul_rn((float)depth[frame * depth_stride + (size_t)w * (int)y + (int)x], cam.factor);
     const bool ok = d > FLT_EPSILON;
     const size_t o = (size_t)frame * cap + i;
     const double z = (double)d;
@@ -212,6 +218,12 @@ static int pfail(mslam_hip_ctx* c, const char* m)
     return MSLAM_HIP_E_INVALID;
 }
 
+// a focal length of zero or NaN has no inverse to project with (NaN != 0.0 is true: it needs its own test)
+static bool bad_focal(double f)
+{
+    return f == 0.0 || f != f;
+}
+
 static int ensure_points(mslam_hip_ctx* c)
 {
     if(c->d_xyz)
@@ -229,7 +241,7 @@ int mslam_hip_backproject_batch_dev(mslam_hip_ctx* c, const uint16_t* d_depth, f
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    if(!d_depth || !(fx != 0.0) || !(fy != 0.0))
+    if(!d_depth || bad_focal(fx) || bad_focal(fy))
         return pfail(c, "backproject_batch_dev: bad argument");
     if(c->n_last < 1)
         return pfail(c, "backproject_batch_dev: no detect batch");
@@ -302,7 +314,7 @@ int mslam_hip_backproject(mslam_hip_ctx* c, const uint16_t* depth, int width, in
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    if(!depth || width <= 0 || height <= 0 || n < 0 || (n > 0 && (!xy || !xyz || !valid)) || !(fx != 0.0) || !(fy != 0.0))
+    if(!depth || width <= 0 || height <= 0 || n < 0 || (n > 0 && (!xy || !xyz || !valid)) || bad_focal(fx) || bad_focal(fy))
         return pfail(c, "backproject: bad argument");
     if(n == 0)
         return MSLAM_HIP_OK;

@@ -877,10 +877,12 @@ void mso_backproject(const uint16_t* depth, int width, int height, float factor,
     for(int i = 0; i < n; ++i)
     {
         const double x = xy[2 * i], y = xy[2 * i + 1];
-        const int ix = (int)x, iy = (int)y; /* coordinates.cast<int>() (:129) */
+        /* coordinates.cast<int>() (:129) truncates toward zero: pixel in [0, n) is -1 < c < n.  A coordinate that is not
+         * finite has no pixel, and neither has one no int holds: both casts are undefined in C, so the test comes first. */
+        const int inside = isfinite(x) && isfinite(y) && x > -1.0 && x < (double)width && y > -1.0 && y < (double)height;
         float d = 0.f;
-        if(ix >= 0 && ix < width && iy >= 0 && iy < height)
-            d = (float)depth[(size_t)width * iy + ix] * factor; /* getDepth, depth_frame.hpp:20-25 */
+        if(inside)
+            d = (float)depth[(size_t)width * (int)y + (int)x] * factor; /* getDepth, depth_frame.hpp:20-25 */
         const int ok = d > FLT_EPSILON;                         /* isDepthValid, depth_frame.hpp:27-30 */
         const double z = d;                                     /* :111 */
         xyz[3 * i] = ok ? (x - cx) * z * inv_fx : 0.0;          /* :112 */
