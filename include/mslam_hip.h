@@ -417,6 +417,13 @@ int mslam_hip_get_pnp_view(mslam_hip_ctx* ctx, mslam_hip_pnp_view* view);
  *                            radius <= 1e-32, |x - x_candidate| <= 1e-8 (|x| + 1e-8) or |cost change| <= 1e-8 cost
  *                            -> CONVERGENCE (the candidate of the last two is not taken); non-finite cost or Jacobian
  *                            at the start or at an accepted point -> FAILURE;
+ *   evaluation valid         DEVIATES for derivatives above about 1.3e154 (sqrt(DBL_MAX)): the kernel keeps sums, not
+ *                            entries, and calls an evaluation valid when the cost, the diagonal of J^T J and J^T f are
+ *                            finite.  A NaN or infinite residual or derivative always shows there.  A finite residual
+ *                            derivative whose square overflows also does, and is treated as a failed evaluation
+ *                            (FAILURE at the start or at an accepted point); Ceres tests the entries themselves
+ *                            (ResidualBlock::Evaluate) and would continue.  It takes a point at a depth near 1e-150 of
+ *                            its lateral offset; tests/test_gpu_mse_pnp_edges.py pins the case;
  *   FAILURE result           DEVIATES: the pose is left unchanged (Ceres writes its best point back; the reference
  *                            discards it: IsSolutionUsable() is false);
  *   progress printout        not reproduced (minimizer_progress_to_stdout, :91). */

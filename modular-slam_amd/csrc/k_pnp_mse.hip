@@ -249,8 +249,10 @@ __device__ void mse_sweep(const MseArgs& a, const double* obj, const double* img
 
 __device__ __forceinline__ int tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c
 
-// the sums are usable as an evaluation with a Jacobian: ResidualBlock::Evaluate rejects non-finite residuals or Jacobian
-// entries, and any such entry makes the cost or a diagonal entry of J^T J (a sum of squares) non-finite
+// the sums are usable as an evaluation with a Jacobian.  ResidualBlock::Evaluate rejects non-finite residuals or Jacobian
+// entries, and any such entry makes the cost or a diagonal entry of J^T J (a sum of squares) non-finite.  The converse
+// does not hold: a finite entry above sqrt(DBL_MAX), about 1.3e154, squares to infinity, so such an evaluation fails here
+// and would pass in Ceres (DEVIATES `evaluation valid` in include/mslam_hip.h; no physical scene reaches such values)
 __device__ __forceinline__ bool sums_finite(const MseSums& S)
 {
     bool ok = isfinite(S.cost);

@@ -32,6 +32,12 @@ call exercises, each from the published source named beside it:
     (the kernel uses normal equations instead: the two differ in rounding only);
   * solver.cc Minimize(): a problem without parameter blocks (n = 0) is CONVERGENCE at cost 0, parameters untouched.
 
+min_mse_pnp(..., linear_solver="normal") is a second solver for the same step, written from DESIGN.md's description of
+what the kernel does and not from the kernel: Cholesky of (Js^T Js + diag(D^2)) y = Js^T f, the model cost change from
+the normal equations.  The two solvers are both correct and differ in rounding only, so their distance on a case says how
+far two correct implementations may drift apart there; the GPU tests take their bound from it.  Every solve also
+returns `trace`, which counts the paths it took (see min_mse_pnp).
+
 PARITY UNPINNED: no Ceres build exists here, so nothing pins this restatement to Ceres itself; it is pinned to ground
 truth (noise-free scenes) and to finite differences (derivatives), and the GPU tests pin the kernel to it.
 This is test infrastructure (not a conftest.py, not under oracle/).
@@ -160,9 +166,13 @@ def cost(x, obj, img, cam):
         return float(np.sum(0.5 * (res[:, 0] ** 2 + res[:, 1] ** 2)))
 
 
-def _evaluate(x, obj, img, cam):
+def _evaluate(x, obj, img, cam, trace=None):
     """Evaluator::Evaluate: (ok, cost, residuals f (2n), gradient J^T f, Jacobian (2n, 6)); ok is False when a residual or
     a Jacobian entry is not finite (ResidualBlock::Evaluate's IsEvaluationValid)"""
+    if trace is not None:                                 # the branch AngleAxisRotatePoint takes at x
+        small = not (x[0] * x[0] + x[1] * x[1] + x[2] * x[2] > DBL_EPSILON)
+        trace["small_angle" if small else "rodrigues"] += 1
+        trace["branches"] += "s" if small else "R"
     res, J = residuals_and_jacobian(x, obj, img, cam)
     f = res.reshape(-1)
     Jm = J.reshape(-1, 6)
@@ -177,23 +187,55 @@ def _gradient_max_norm(x, g):
     return float(np.max(np.abs(x - (x + (-g))))) if len(x) else 0.0       # |x - Plus(x, -g)|_inf
 
 
-def min_mse_pnp(obj, img, cam, x0):
+def _lm_step_qr(Js, D, f):
+    """DenseQRSolver on the D-augmented system: (step, model cost change -(Js d)^T (f + Js d / 2))"""
+    A = np.vstack([Js, np.diag(D)])
+    b = np.concatenate([f, np.zeros(6)])
+    q, rr = np.linalg.qr(A)
+    y = np.linalg.solve(rr, q.T @ b) if np.all(np.isfinite(rr)) else np.full(6, np.nan)
+    step = -y
+    model_residuals = Js @ step
+    return step, -model_residuals.dot(f + model_residuals / 2.0)
+
+
+def _lm_step_normal(Js, D, f):
+    """the normal equations (Js^T Js + diag(D^2)) y = Js^T f by Cholesky; the model cost change
+    -(f^T Js d + |Js d|^2 / 2) from Js^T f and the undamped Js^T Js.  A failed factorisation is a non-finite step, which
+    the caller counts as an invalid one."""
+    H = Js.T @ Js
+    gs = Js.T @ f
+    try:
+        L = np.linalg.cholesky(H + np.diag(D * D))
+    except np.linalg.LinAlgError:
+        return np.full(6, np.nan), np.nan
+    step = -np.linalg.solve(L.T, np.linalg.solve(L, gs))
+    return step, -(gs.dot(step) + 0.5 * step.dot(H @ step))
+
+
+def min_mse_pnp(obj, img, cam, x0, linear_solver="qr"):
     """MinMseTracker::solvePnp's ceres::Solve -> dict(x, termination, iterations, initial_cost, final_cost,
-    gradient_max_norm, reason).  `iterations` is the index of the trust-region iteration that ended the solve (0 when
-    the start already met a test); x is the start when termination is FAILURE."""
+    gradient_max_norm, reason, trace).  `iterations` is the index of the trust-region iteration that ended the solve (0
+    when the start already met a test); x is the start when termination is FAILURE.  linear_solver: "qr" (Ceres's
+    DENSE_QR) or "normal" (Cholesky of the normal equations, see the module's text).  trace counts the paths taken:
+    evaluations on the small-angle / Rodrigues branch of AngleAxisRotatePoint (`small_angle`, `rodrigues`; `branches` is
+    their sequence, one letter s / R per evaluation, the start first), `rejected` steps, accepted steps that reset a
+    grown decrease factor (`accepted_after_rejected`), `invalid` steps and candidates whose cost was replaced by DBL_MAX
+    (`dbl_max`)."""
+    lm_step = {"qr": _lm_step_qr, "normal": _lm_step_normal}[linear_solver]
+    trace = dict(small_angle=0, rodrigues=0, rejected=0, accepted_after_rejected=0, invalid=0, dbl_max=0, branches="")
     obj = np.asarray(obj, np.float64).reshape(-1, 3)
     img = np.asarray(img, np.float64).reshape(-1, 2)
     x = np.array(x0, np.float64).reshape(6)
 
     def out(term, it, c0, c, reason, gmax=np.nan, xr=None):
         return dict(x=x.copy() if xr is None else xr, termination=term, iterations=it, initial_cost=c0, final_cost=c,
-                    gradient_max_norm=gmax, reason=reason)
+                    gradient_max_norm=gmax, reason=reason, trace=trace)
 
     if len(obj) == 0:                                     # solver.cc Minimize(): no parameter blocks
         return out(CONVERGENCE, 0, 0.0, 0.0, "no parameter blocks", 0.0)
     x_start = x.copy()
     # IterationZero
-    ok, x_cost, f, g, J = _evaluate(x, obj, img, cam)
+    ok, x_cost, f, g, J = _evaluate(x, obj, img, cam, trace)
     initial_cost = x_cost
     if not ok or not np.isfinite(x_cost):
         return out(FAILURE, 0, initial_cost, initial_cost, "initial evaluation failed", xr=x_start)
@@ -219,16 +261,11 @@ def min_mse_pnp(obj, img, cam, x0):
         diagonal = np.minimum(np.maximum(np.sum(Js * Js, axis=0), MIN_LM_DIAGONAL), MAX_LM_DIAGONAL)
         D = np.sqrt(diagonal / radius)
         with np.errstate(all="ignore"):
-            A = np.vstack([Js, np.diag(D)])
-            b = np.concatenate([f, np.zeros(6)])
-            q, rr = np.linalg.qr(A)
-            y = np.linalg.solve(rr, q.T @ b) if np.all(np.isfinite(rr)) else np.full(6, np.nan)
-            step = -y
-            model_residuals = Js @ step
-            model_cost_change = -model_residuals.dot(f + model_residuals / 2.0)
+            step, model_cost_change = lm_step(Js, D, f)
         if not (np.all(np.isfinite(step)) and model_cost_change > 0.0):
             # HandleInvalidStep
             invalid += 1
+            trace["invalid"] += 1
             if invalid >= MAX_NUM_CONSECUTIVE_INVALID_STEPS:
                 return out(FAILURE, iteration, initial_cost, x_cost, "too many invalid steps", gmax, xr=x_start)
             radius /= decrease_factor
@@ -238,9 +275,10 @@ def min_mse_pnp(obj, img, cam, x0):
         delta = step * scale
         candidate = x + delta
         # ComputeCandidatePointAndEvaluateCost
-        c_ok, candidate_cost, c_f, c_g, c_J = _evaluate(candidate, obj, img, cam)
+        c_ok, candidate_cost, c_f, c_g, c_J = _evaluate(candidate, obj, img, cam, trace)
         if not np.isfinite(candidate_cost):
             candidate_cost = DBL_MAX
+            trace["dbl_max"] += 1
         # ParameterToleranceReached
         step_norm = np.linalg.norm(x - candidate)
         if step_norm <= PARAMETER_TOLERANCE * (np.linalg.norm(x) + PARAMETER_TOLERANCE):
@@ -264,7 +302,9 @@ def min_mse_pnp(obj, img, cam, x0):
             successful = True
             radius = radius / max(1.0 / 3.0, 1.0 - (2.0 * relative_decrease - 1.0) ** 3)
             radius = min(MAX_TRUST_REGION_RADIUS, radius)
+            trace["accepted_after_rejected"] += decrease_factor != 2.0
             decrease_factor = 2.0
         else:
+            trace["rejected"] += 1
             radius /= decrease_factor                     # StepRejected
             decrease_factor *= 2.0
