@@ -1808,6 +1808,12 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
         if(n)
             HIPCHK(c, hipMemcpy(tmp.data(), (cand ? c->quad.cand : c->quad.sel) + slot * (size_t)c->p.max_candidates,
                                 (size_t)n * 4, hipMemcpyDeviceToHost));
+        // cv::ORB mode, library order, a level beyond k_cv_select's LDS arrays: both retainBest calls permute the level's list
+        // in place (every other array of the slot is rank scratch, there is none to keep a copy in), so what is left is
+        // FAST's SET in libstdc++'s order.  FAST's order is ascending order of the packed words: put it back here — only
+        // in this case, so that everywhere else the item still shows what the kernel's own sort left.
+        if(cand && c->p.detector == MSLAM_HIP_DETECTOR_CV_ORB && c->cv_order == MSLAM_HIP_CV_ORDER_LIBSTDCXX && n > (uint32_t)kSelLds)
+            std::sort(tmp.begin(), tmp.end());
         float* out = static_cast<float*>(dst);
         for(uint32_t i = 0; i < n; ++i)
         {

@@ -269,6 +269,8 @@ struct CvSelectArgs
     int quota[kMaxLevels]; // nfeaturesPerLevel
     int std_order;         // 1: retainBest leaves its survivors where libstdc++'s nth_element + partition put them (the reference's order), 0: raster order
 };
+constexpr int kSelLds = 4096;      // k_cv_select: levels with at most this many FAST keypoints are selected entirely in LDS
+constexpr int kSelLdsSmall = 1024; // ... and those with at most this many by the small instance (9 KB of LDS instead of 34)
 void launch_zero_u32(uint32_t* p, int n, hipStream_t s);
 void launch_fast_tiles(const uint8_t* d_pyr, const Geometry& g, int thr, const CvSelectArgs& a, int frame0, int n_frames,
                        hipStream_t s);

@@ -823,9 +823,7 @@ __device__ __forceinline__ void cv_select_run(uint32_t* keys, uint32_t* kept, fl
         *sel_cnt = (uint32_t)m2;
 }
 
-constexpr int kSelLds = 4096;      // levels with at most this many FAST keypoints are selected entirely in LDS
-constexpr int kSelLdsSmall = 1024; // ... and those with at most this many by the small instance (9 KB of LDS instead of 34)
-
+// (kSelLds = 4096 and kSelLdsSmall = 1024, the sizes of the two instances' LDS arrays, are in common.hpp)
 // Two instances on the same grid (as k_quadtree's classes): a (level, frame) pair is taken by the instance whose LDS
 // arrays its keypoints fit — the passes are barrier + LDS latency, so workgroups per CU set the rate — and the other
 // instance leaves at once (the count is one load).
