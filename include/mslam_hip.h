@@ -644,6 +644,52 @@ int mslam_hip_track(mslam_hip_ctx* ctx, const uint8_t* desc, const float* xy, in
                     int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride,
                     int32_t* entry_src, int32_t* entry_kp, int entry_capacity);
 
+/* mslam_hip_track for a window of S consecutive frames (1 <= S <= 256) against ONE store entry, in one call with one upload
+ * and one host synchronisation.  Between two events of the front end's loop — a new keyframe, a change of the reference
+ * keyframe, a tracking failure — consecutive frames are matched against the same landmarks and are independent of each
+ * other, so the window runs as S matcher pairs, S PnP problems and S votes in one launch each.
+ *   layout        desc [S][stride][32] u8, xy [S][stride][2] f32, n [S] keypoint counts (0 <= n[s] <= stride; rows past n[s]
+ *                 are never read), depth [S][height][width] u16.  out: S records; vote_counts [S][n_vote] or NULL;
+ *   per frame s   out[s] is exactly what mslam_hip_track writes for that frame alone with ref_id, the same vote_ids,
+ *                 new_id = -1, the seed `seed + s` and the call's one guess (shared by all frames as mslam_hip_relocalize
+ *                 shares its guess among candidates): SAME kernels on the same operands, equal bit for bit;
+ *   event         frame s is an event when it is not tracked, or keyframe_required is set, or
+ *                 n_vote > 0 && ref_vote_pos >= 0 && vote_best != ref_vote_pos (ref_vote_pos: the position of the current
+ *                 reference keyframe in vote_ids, -1: votes never raise an event).  *first_event = the smallest such s, or S;
+ *                 found on the device.  Frames behind it are still reported, as computed against ref_id: the caller discards
+ *                 them (its state changes at the event);
+ *   keyframe      with new_id >= 0, when frame *first_event has keyframe_required the device builds its entry under new_id
+ *                 by mslam_hip_track's rules (part A, part B, landmark ids, the cut at max_keypoints, entry_src / entry_kp)
+ *                 without a host round trip for the decision; keyframe_added, n_entry and n_inherited are set on that one
+ *                 record.  A keyframe-requiring frame behind the first event inserts nothing.
+ * Slot reservation, the serial, the release of an unused slot and the MSLAM_HIP_E_INVALID / _E_CAPACITY rules are
+ * mslam_hip_track's (n[s] > max_keypoints for any s: E_CAPACITY; S outside 1..256: E_INVALID).  Returns MSLAM_HIP_OK when
+ * frame 0 is tracked and MSLAM_HIP_E_NO_MODEL when not (the records and *first_event = 0 are complete).
+ * Against the reference:
+ *   guess         DEVIATES from a frame-by-frame loop, which hands each frame the previous frame's pose: here the frames of a
+ *                 window share the guess of the window's start.  The guess only starts the final refit (see
+ *                 mslam_hip_pnp_ransac), so the consensus sets are the same and the poses agree to the refit's convergence;
+ *   the rest      as mslam_hip_track. */
+typedef mslam_hip_track_result mslam_hip_track_window_result; /* pair rows are not returned; entry fields: see `keyframe` */
+int mslam_hip_track_window(mslam_hip_ctx* ctx, const uint8_t* desc, const float* xy, const int32_t* n, int stride,
+                           const uint16_t* depth, int S, int width, int height, float factor, double fx, double fy, double cx,
+                           double cy, int ref_id, const int32_t* vote_ids, int n_vote, int ref_vote_pos, double ratio,
+                           int iterations, double reprojection_error, uint64_t seed, int use_extrinsic_guess,
+                           const double* rvec, const double* tvec, int min_matched_points, int new_keyframe_min_landmarks,
+                           int new_id, double z_max, mslam_hip_track_window_result* out /* S */, int* first_event,
+                           int32_t* vote_counts /* [S][n_vote], may be NULL */, int32_t* entry_src, int32_t* entry_kp,
+                           int entry_capacity);
+/* The same on frames first_frame .. first_frame + n_frames - 1 of the last mslam_hip_detect_batch_dev that
+ * mslam_hip_backproject_batch_dev has run on: descriptors, coordinates and counts from the batch view, points and `valid`
+ * from the points view (no depth filter launch of its own), the frame size from the context.  Nothing is uploaded but the
+ * vote list; apart from the first stage every kernel is the host form's.  The intrinsics are those of the back-projection. */
+int mslam_hip_track_window_dev(mslam_hip_ctx* ctx, int first_frame, int n_frames, double fx, double fy, double cx, double cy,
+                               int ref_id, const int32_t* vote_ids, int n_vote, int ref_vote_pos, double ratio, int iterations,
+                               double reprojection_error, uint64_t seed, int use_extrinsic_guess, const double* rvec,
+                               const double* tvec, int min_matched_points, int new_keyframe_min_landmarks, int new_id,
+                               double z_max, mslam_hip_track_window_result* out /* n_frames */, int* first_event,
+                               int32_t* vote_counts, int32_t* entry_src, int32_t* entry_kp, int entry_capacity);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

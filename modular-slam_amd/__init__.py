@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_cv_keypoint_order", "mslam_hip_pnp_min_mse", "mslam_hip_pnp_min_mse_batch_dev",
     "mslam_hip_kf_add", "mslam_hip_kf_add_from_batch_dev", "mslam_hip_kf_remove", "mslam_hip_kf_clear", "mslam_hip_kf_size",
     "mslam_hip_kf_reserve", "mslam_hip_kf_read", "mslam_hip_relocalize",
-    "mslam_hip_kf_visible", "mslam_hip_track",
+    "mslam_hip_kf_visible", "mslam_hip_track", "mslam_hip_track_window", "mslam_hip_track_window_dev",
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
 ]
 
@@ -550,6 +550,98 @@ class Context:
             res["entry_src"], res["entry_kp"] = es[:out.n_entry].copy(), ek[:out.n_entry].copy()
         return res
 
+    # ---- the tracking step on a window of frames (between two events of the loop the frames are independent) ----
+    def _window_records(self, out, counts, S, n_vote, first, es, ek):
+        recs = []
+        for s in range(S):
+            o = out[s]
+            r = {k: getattr(o, k) for k, _ in TrackResult._fields_ if k not in ("rvec", "tvec", "R")}
+            r.update(rvec=np.array(o.rvec[:]), tvec=np.array(o.tvec[:]), R=np.array(o.R[:]).reshape(3, 3),
+                     vote_counts=counts[s, :n_vote].copy())
+            if es is not None:
+                k = o.n_entry if s == first else 0
+                r["entry_src"], r["entry_kp"] = es[:k].copy(), ek[:k].copy()
+            recs.append(r)
+        return recs
+
+    def track_window(self, descs, xys, depths, ref_id, vote_ids=(), new_id=-1, ref_vote_pos=-1, factor=1.0 / 5000.0,
+                     focal=(525.0, 525.0), principal=(319.5, 239.5), ratio=0.7, iterations=100, reprojection_error=5.0, seed=0,
+                     rvec=None, tvec=None, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0, with_entry=False,
+                     entry_capacity=None, stride=None, pad_value=0):
+        """Context.track for S = len(descs) frames (1..256) against the one stored keyframe ref_id in one call: descs[s]
+        [n_s, 32], xys[s] [n_s, 2], depths[s] [h, w] u16 (one size).  Frame s gets the seed `seed + s`; all frames share the
+        guess (rvec, tvec).  ref_vote_pos = the position of the current reference keyframe in vote_ids (-1: a vote never is
+        an event).  stride (default: the largest n_s) and pad_value shape the padded arrays the C call takes.
+        -> (records, first_event): per frame the dict Context.track returns (without pairs), as computed against ref_id;
+        first_event = the first frame that is not tracked, requires a keyframe or votes for another keyframe, or S.  With
+        new_id >= 0 a keyframe the frame first_event requires is built in the store (keyframe_added, n_entry, n_inherited
+        and, with with_entry, entry_src / entry_kp on that record).  Frame 0 not tracked is a result here, not an exception."""
+        S = len(descs)
+        ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descs]
+        ps = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in xys]
+        if len(ps) != S or len(depths) != S or any(len(d) != len(p) for d, p in zip(ds, ps)):
+            raise MslamHipError(E_INVALID, "track_window: descriptors, points and depth frames do not pair up")
+        n = np.array([len(d) for d in ds], np.int32)
+        st = int(n.max() if S else 0) if stride is None else int(stride)
+        if S and st < n.max():
+            raise MslamHipError(E_INVALID, "track_window: stride is smaller than a frame's keypoint count")
+        d = np.full((max(S, 1), max(st, 1), 32), pad_value, np.uint8)
+        p2 = np.full((max(S, 1), max(st, 1), 2), pad_value, np.float32)
+        for s in range(S):
+            d[s, :n[s]], p2[s, :n[s]] = ds[s], ps[s]
+        depth = np.ascontiguousarray(np.stack([np.asarray(x, np.uint16) for x in depths]) if S else np.zeros((1, 1, 1)), np.uint16)
+        h, w = depth.shape[1:]
+        ids = np.ascontiguousarray(vote_ids, np.int32).reshape(-1)
+        guess = rvec is not None and tvec is not None
+        r = np.array(rvec if guess else (0, 0, 0), np.float64)
+        t = np.array(tvec if guess else (0, 0, 0), np.float64)
+        K = self.params.max_keypoints
+        cap = (K if entry_capacity is None else int(entry_capacity)) if with_entry else 0
+        es = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        ek = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        counts = np.zeros((max(S, 1), max(len(ids), 1)), np.int32)
+        out = (TrackResult * max(S, 1))()
+        first = C.c_int(0)
+        rc = self.L.mslam_hip_track_window(self._h, _p(d), _p(p2), _p(n), st, _p(depth), S, w, h, C.c_float(factor),
+                                           C.c_double(focal[0]), C.c_double(focal[1]), C.c_double(principal[0]),
+                                           C.c_double(principal[1]), int(ref_id), _p(ids), len(ids), int(ref_vote_pos),
+                                           C.c_double(ratio), int(iterations), C.c_double(reprojection_error), C.c_uint64(seed),
+                                           int(guess), _p(r), _p(t), int(min_matched_points), int(new_keyframe_min_landmarks),
+                                           int(new_id), C.c_double(z_max), out, C.byref(first), _p(counts), _p(es), _p(ek),
+                                           int(cap))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        return self._window_records(out, counts, S, len(ids), first.value, es, ek), first.value
+
+    def track_window_dev(self, first_frame, n_frames, ref_id, vote_ids=(), new_id=-1, ref_vote_pos=-1, focal=(525.0, 525.0),
+                         principal=(319.5, 239.5), ratio=0.7, iterations=100, reprojection_error=5.0, seed=0, rvec=None,
+                         tvec=None, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0, with_entry=False,
+                         entry_capacity=None):
+        """track_window on frames first_frame .. first_frame + n_frames - 1 of the last detect_batch_dev +
+        backproject_batch_dev batch: nothing is uploaded but the vote list -> (records, first_event)"""
+        S = int(n_frames)
+        ids = np.ascontiguousarray(vote_ids, np.int32).reshape(-1)
+        guess = rvec is not None and tvec is not None
+        r = np.array(rvec if guess else (0, 0, 0), np.float64)
+        t = np.array(tvec if guess else (0, 0, 0), np.float64)
+        K = self.params.max_keypoints
+        cap = (K if entry_capacity is None else int(entry_capacity)) if with_entry else 0
+        es = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        ek = np.zeros(max(cap, 1), np.int32) if with_entry else None
+        counts = np.zeros((max(S, 1), max(len(ids), 1)), np.int32)
+        out = (TrackResult * max(S, 1))()
+        first = C.c_int(0)
+        rc = self.L.mslam_hip_track_window_dev(self._h, int(first_frame), S, C.c_double(focal[0]), C.c_double(focal[1]),
+                                               C.c_double(principal[0]), C.c_double(principal[1]), int(ref_id), _p(ids),
+                                               len(ids), int(ref_vote_pos), C.c_double(ratio), int(iterations),
+                                               C.c_double(reprojection_error), C.c_uint64(seed), int(guess), _p(r), _p(t),
+                                               int(min_matched_points), int(new_keyframe_min_landmarks), int(new_id),
+                                               C.c_double(z_max), out, C.byref(first), _p(counts), _p(es), _p(ek), int(cap))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        S = S if 1 <= S <= 256 else 0
+        return self._window_records(out, counts, S, len(ids), first.value, es, ek), first.value
+
     # ---- bag of words --------------------------------------------------------------------------
     def bow_load(self, blob):
         b = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob)
@@ -881,6 +973,7 @@ class HipKeyframeTracker:
         self.reference = None
         self.rvec, self.tvec, self.R = np.zeros(3), np.zeros(3), np.eye(3)
         self.frame = 0
+        self.window_calls = self.window_computed = self.window_discarded = 0   # process_window's counters
 
     def processSensorData(self, desc, xy, depth):
         """one frame: descriptors [n, 32], keypoint coordinates [n, 2], depth image [h, w] u16
@@ -931,6 +1024,79 @@ class HipKeyframeTracker:
                 self.reference, out["relocalized"] = vote[reloc["best"]], True
         out.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
         return out
+
+    def process_window(self, descs, xys, depths, window=16):
+        """processSensorData over a list of frames, `window` frames per Context.track_window call: the guess is the current
+        pose and the seed self.seed + the absolute frame index; the frames up to and including the call's first event are
+        accepted, the event is handled exactly as processSensorData handles it (a keyframe: the id is appended and, in
+        local-map mode, the covisibility edges are added and the union is rebuilt; a vote: the reference switches; a
+        failure: relocalize), and the loop continues behind the event frame.  -> the per-frame dicts of processSensorData.
+        DEVIATES from the frame-by-frame loop: the frames of one window share the guess of the window's start (the guess
+        only starts PnP's final refit: the consensus sets are the same).  window = 1 is processSensorData.
+        self.window_calls / window_computed / window_discarded count the calls, the frames they computed and the frames
+        computed behind an event and thrown away."""
+        out, i, N = [], 0, len(descs)
+        while i < N:
+            if self.reference is None:
+                out.append(self.processSensorData(descs[i], xys[i], depths[i]))
+                i += 1
+                continue
+            vote = self.ids[-64:]
+            new_id = self.ids[-1] + 1
+            pos = vote.index(self.reference) if self.reference in vote else -1
+            S = min(int(window), N - i, 256) if pos >= 0 else 1   # a reference outside the vote list: frame by frame
+            seed = self.seed + self.frame
+            ref_id, rebuilt = self.reference, False
+            if self.local_map_depth is not None:
+                if self._local_map_of != self.reference:
+                    self.local_map = self.neighbours(self.reference)
+                    self.ctx.kf_union(self.LOCAL_MAP_ID, self.local_map, sync=False)   # the call's own synchronisation covers it
+                    self._local_map_of, rebuilt = self.reference, True
+                ref_id = self.LOCAL_MAP_ID
+            recs, first = self.ctx.track_window(descs[i:i + S], xys[i:i + S], depths[i:i + S], ref_id, vote, new_id, pos, self.factor,
+                                                self.focal, self.principal, self.ratio, self.iterations, self.reprojection_error,
+                                                seed, self.rvec, self.tvec, self.min_matched_points,
+                                                self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
+            if rebuilt:
+                self.ctx.sync()   # a union that did not fit max_keypoints left an empty entry: it surfaces here as E_CAPACITY
+            n_acc = min(first + 1, S)
+            self.window_calls += 1
+            self.window_computed += S
+            self.window_discarded += S - n_acc
+            for s in range(n_acc):
+                res = recs[s]
+                o = dict(tracked=bool(res["tracked"]), n_inliers=res["n_inliers"], keyframe=-1, relocalized=False, step=res)
+                if res["tracked"]:
+                    self.rvec, self.tvec, self.R = res["rvec"], res["tvec"], res["R"]
+                    if res["vote_best"] >= 0:
+                        self.reference = vote[res["vote_best"]]
+                    if res["keyframe_added"]:
+                        self._keyframe_added(new_id)
+                        o["keyframe"] = new_id
+                else:
+                    reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
+                                                self.iterations, self.reprojection_error, seed + s,
+                                                min_inliers=self.reloc_min_inliers)
+                    if reloc["best"] >= 0:
+                        self.reference, o["relocalized"] = vote[reloc["best"]], True
+                o.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
+                out.append(o)
+            self.frame += n_acc
+            i += n_acc
+        return out
+
+    def _keyframe_added(self, new_id):
+        """the bookkeeping behind a keyframe track_window built (processSensorData's, restated): the id, the reference, and
+        in local-map mode the covisibility edges and the rebuild of the union"""
+        self.ids.append(new_id)
+        self.reference = new_id
+        if self.local_map_depth is not None:
+            self.graph[new_id] = set()
+            for other, n in zip(self.local_map, self.ctx.kf_covisible(new_id, self.local_map)):
+                if n > 0 and other != new_id:
+                    self.graph[new_id].add(other)
+                    self.graph[other].add(new_id)
+            self._local_map_of = None
 
     def neighbours(self, ref):
         """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than

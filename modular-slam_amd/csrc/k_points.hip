@@ -60,6 +60,17 @@ void launch_backproject(hipStream_t s, const uint16_t* d_depth, int width, int h
                        n, d_xyz, d_valid);
 }
 
+// for k_track_window.hip: n_frames depth frames back to back, frame f's coordinates at d_xy + f * stride * 2 with the device
+// count d_n[f] (at most `stride`), outputs `stride` rows apart — the launch mslam_hip_backproject_batch_dev makes
+void launch_backproject_batch(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy,
+                              double cx, double cy, const float* d_xy, const int32_t* d_n, int stride, int n_frames, double* d_xyz,
+                              uint8_t* d_valid)
+{
+    const Camera cam{cx, cy, 1.0 / fx, 1.0 / fy, factor};
+    hipLaunchKernelGGL(k_backproject, dim3((stride + 255) / 256, n_frames), dim3(256), 0, s, d_depth, (long long)width * height, width,
+                       height, cam, d_xy, (long long)stride * 2, d_n, 0, stride, d_xyz, d_valid);
+}
+
 } // namespace mslam
 
 using namespace mslam;

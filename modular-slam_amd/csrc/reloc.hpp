@@ -111,5 +111,9 @@ int64_t store_next_lid_base(mslam_hip_ctx* c); // advances the creation serial: 
 // k_points.hip: k_backproject on one frame of n keypoints, device pointers, enqueued on `s`
 void launch_backproject(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy, double cx,
                         double cy, const float* d_xy, int n, double* d_xyz, uint8_t* d_valid);
+// ... and on n_frames frames in one launch (per-frame device counts, rows `stride` apart)
+void launch_backproject_batch(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy,
+                              double cx, double cy, const float* d_xy, const int32_t* d_n, int stride, int n_frames, double* d_xyz,
+                              uint8_t* d_valid);
 
 } // namespace mslam
