@@ -24,7 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmslam_hip.so")
 
 OK, E_INVALID, E_RUNTIME, E_CAPACITY, E_NO_VOCABULARY, E_FORMAT, E_NO_MODEL = range(7)
-DBG_PYRAMID, DBG_BLURRED, DBG_CANDIDATES, DBG_SELECTED = range(4)
+DBG_PYRAMID, DBG_BLURRED, DBG_CANDIDATES, DBG_SELECTED, DBG_CELLS, DBG_FORMS = range(6)
 MATCHER_AUTO, MATCHER_POPCOUNT = 0, 1
 DETECTOR_DISTRIBUTED, DETECTOR_CV_ORB = 0, 1
 BOW_ASSIGN_TREE, BOW_ASSIGN_FLAT = 0, 1
@@ -751,6 +751,21 @@ class Context:
         self._chk(self.L.mslam_hip_debug_read(self._h, what, frame, level, _p(out), C.c_size_t(out.nbytes),
                                               C.byref(n)))
         return out[:n.value].copy()
+
+    def debug_cells(self, level):
+        """[n_cells, 6] the level's FAST cells (x0, y0, cw, ch, ox, oy) in launch order (in-tree detector)"""
+        out = np.empty((2048, 6), np.int32)
+        n = C.c_size_t(0)
+        self._chk(self.L.mslam_hip_debug_read(self._h, DBG_CELLS, 0, level, _p(out), C.c_size_t(out.nbytes),
+                                              C.byref(n)))
+        return out[:n.value].copy()
+
+    def debug_forms(self):
+        """(levels produced by the fused level kernels, 1 when the blurred slab is kept in tiles) of this context"""
+        out = np.zeros(2, np.int32)
+        n = C.c_size_t(0)
+        self._chk(self.L.mslam_hip_debug_read(self._h, DBG_FORMS, 0, 0, _p(out), C.c_size_t(out.nbytes), C.byref(n)))
+        return int(out[0]), int(out[1])
 
     def debug_counts(self, what, n_frames):
         """[n_frames, n_levels] FAST candidates (DBG_CANDIDATES) or selected keypoints (DBG_SELECTED) of the last batch"""

@@ -1838,6 +1838,29 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
         }
         return MSLAM_HIP_OK;
     }
+    if(what == MSLAM_HIP_DBG_CELLS && c->p.detector == MSLAM_HIP_DETECTOR_DISTRIBUTED)
+    {
+        *n_items = (size_t)lv.n_cells;
+        if(dst_bytes < (size_t)lv.n_cells * 24)
+            return fail(c, MSLAM_HIP_E_CAPACITY, "debug_read: buffer too small");
+        int32_t* out = static_cast<int32_t*>(dst);
+        for(int i = 0; i < lv.n_cells; ++i)
+        {
+            const CellDesc& cd = c->cells[(size_t)lv.cell_base + i];
+            const int32_t rec[6] = {cd.x0, cd.y0, cd.cw, cd.ch, cd.ox, cd.oy};
+            std::memcpy(out + 6 * i, rec, sizeof(rec));
+        }
+        return MSLAM_HIP_OK;
+    }
+    if(what == MSLAM_HIP_DBG_FORMS)
+    {
+        *n_items = 2;
+        if(dst_bytes < 8)
+            return fail(c, MSLAM_HIP_E_CAPACITY, "debug_read: buffer too small");
+        const int32_t rec[2] = {c->fused_levels, c->geom.blur_tiled};
+        std::memcpy(dst, rec, sizeof(rec));
+        return MSLAM_HIP_OK;
+    }
     return fail(c, MSLAM_HIP_E_INVALID, "debug_read: unknown item");
 }
 
