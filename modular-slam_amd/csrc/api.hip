@@ -21,17 +21,6 @@ using namespace mslam;
 
 static thread_local std::string g_create_error;
 
-#define HIPCHK(c, call)                                                                                                \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
 // HIP's current device is per host thread: make the context's device current on every entry so that
 // allocations and launches land on it no matter what the caller did in between.
 #define ENTER(c)                                                                                                       \
@@ -39,14 +28,8 @@ static thread_local std::string g_create_error;
     {                                                                                                                  \
         if(!(c))                                                                                                       \
             return MSLAM_HIP_E_INVALID;                                                                                \
-        HIPCHK(c, hipSetDevice((c)->p.device));                                                                        \
+        MSLAM_CHK(c, hipSetDevice((c)->p.device));                                                                     \
     } while(0)
-
-static int fail(mslam_hip_ctx* c, int code, const std::string& msg)
-{
-    c->err = msg;
-    return code;
-}
 
 // ---- host helpers ---------------------------------------------------------------------------------
 static inline int cv_round_f(float v) { return (int)lrintf(v); }
@@ -529,12 +512,12 @@ static int create_impl(mslam_hip_ctx* c)
     int n_dev = 0;
     if(hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return fail(c, MSLAM_HIP_E_RUNTIME, "no HIP device available (the product path has no CPU fallback)");
-    HIPCHK(c, hipSetDevice(p.device));
+    MSLAM_CHK(c, hipSetDevice(p.device));
     if(p.stream)
         c->stream = (hipStream_t)p.stream;
     else
     {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        MSLAM_CHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         c->own_stream = true;
     }
 
@@ -543,11 +526,11 @@ static int create_impl(mslam_hip_ctx* c)
             c->use_graph = atoi(ge) != 0;
         const char* e = getenv("MSLAM_HIP_STREAMS");
         c->n_side = e ? std::max(1, std::min(atoi(e), 4)) : 2; // measured in one run (batch 250): 1 / 2 / 3 / 4 chunks = 366 / 375 / 369 / 361 M kp/s
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        MSLAM_CHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         for(int k = 0; k < c->n_side; ++k)
         {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming));
+            MSLAM_CHK(c, hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking));
+            MSLAM_CHK(c, hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming));
         }
         const char* fb = getenv("MSLAM_HIP_FORK_BLUR");
         c->fork_blur = fb && atoi(fb) != 0;
@@ -555,9 +538,9 @@ static int create_impl(mslam_hip_ctx* c)
         // queue run one after the other — idle streams here can push a later context's chunk / matcher streams onto one queue)
         for(int k = 0; k < 4 && c->fork_blur; ++k)
         {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->blur_stream[k], hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_blur_fork[k], hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_blur_join[k], hipEventDisableTiming));
+            MSLAM_CHK(c, hipStreamCreateWithFlags(&c->blur_stream[k], hipStreamNonBlocking));
+            MSLAM_CHK(c, hipEventCreateWithFlags(&c->ev_blur_fork[k], hipEventDisableTiming));
+            MSLAM_CHK(c, hipEventCreateWithFlags(&c->ev_blur_join[k], hipEventDisableTiming));
         }
     }
     // tables
@@ -600,20 +583,20 @@ static int create_impl(mslam_hip_ctx* c)
             for(int l = 1; l < p.n_levels; ++l)
                 build_quad_table(ofs, coef, c->cv_x[l], g.lv[l].w, p.max_batch, qt, c->rs_q[l], c->rs_need[l]);
             qt.push_back(make_uint4(0, 0, 0, 0));
-            HIPCHK(c, dmalloc(c->d_rs_qt, qt.size()));
-            HIPCHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
+            MSLAM_CHK(c, dmalloc(c->d_rs_qt, qt.size()));
+            MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
         }
         ofs.push_back(0);
         coef.push_back(0);
-        HIPCHK(c, dmalloc(c->d_cv_ofs, ofs.size()));
-        HIPCHK(c, dmalloc(c->d_cv_coef, coef.size()));
-        HIPCHK(c, hipMemcpy(c->d_cv_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_cv_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
+        MSLAM_CHK(c, dmalloc(c->d_cv_ofs, ofs.size()));
+        MSLAM_CHK(c, dmalloc(c->d_cv_coef, coef.size()));
+        MSLAM_CHK(c, hipMemcpy(c->d_cv_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
+        MSLAM_CHK(c, hipMemcpy(c->d_cv_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
     }
     if(has_detector && !cv_mode)
     {
-    HIPCHK(c, dmalloc(c->d_cells, c->cells.size()));
-    HIPCHK(c, hipMemcpy(c->d_cells, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
+    MSLAM_CHK(c, dmalloc(c->d_cells, c->cells.size()));
+    MSLAM_CHK(c, hipMemcpy(c->d_cells, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
     {
         std::vector<int32_t> ofs;
         std::vector<uint32_t> coef;
@@ -633,48 +616,48 @@ static int create_impl(mslam_hip_ctx* c)
         for(int l = 1; l < p.n_levels; ++l)
             build_quad_table(ofs, coef, c->rs_x[l], g.lv[l].w, p.max_batch, qt, c->rs_q[l], c->rs_need[l]);
         qt.push_back(make_uint4(0, 0, 0, 0));
-        HIPCHK(c, dmalloc(c->d_rs_qt, qt.size()));
-        HIPCHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
+        MSLAM_CHK(c, dmalloc(c->d_rs_qt, qt.size()));
+        MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
         ofs.push_back(0);
         coef.push_back(0);
-        HIPCHK(c, dmalloc(c->d_rs_ofs, ofs.size()));
-        HIPCHK(c, dmalloc(c->d_rs_coef, coef.size()));
-        HIPCHK(c, hipMemcpy(c->d_rs_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_rs_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
+        MSLAM_CHK(c, dmalloc(c->d_rs_ofs, ofs.size()));
+        MSLAM_CHK(c, dmalloc(c->d_rs_coef, coef.size()));
+        MSLAM_CHK(c, hipMemcpy(c->d_rs_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
+        MSLAM_CHK(c, hipMemcpy(c->d_rs_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
     }
     } // has_detector
-    HIPCHK(c, dmalloc(c->d_ratio_thr, 257));
+    MSLAM_CHK(c, dmalloc(c->d_ratio_thr, 257));
     {
         uint32_t w[2 * 256];
         build_orient_weights(umax, w);
-        HIPCHK(c, dmalloc(c->d_orient_w, 2 * 256));
-        HIPCHK(c, hipMemcpy(c->d_orient_w, w, sizeof(w), hipMemcpyHostToDevice));
+        MSLAM_CHK(c, dmalloc(c->d_orient_w, 2 * 256));
+        MSLAM_CHK(c, hipMemcpy(c->d_orient_w, w, sizeof(w), hipMemcpyHostToDevice));
     }
 
     const size_t B = (size_t)p.max_batch, L = (size_t)p.n_levels, cap = (size_t)p.max_candidates;
     const size_t K = (size_t)p.max_keypoints;
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), 16 + K * 52, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_out), c->h_out, 0));
-    HIPCHK(c, dmalloc(c->d_flags, 1));
-    HIPCHK(c, hipMemset(c->d_flags, 0, 4));
+    MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), 16 + K * 52, hipHostMallocMapped));
+    MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_out), c->h_out, 0));
+    MSLAM_CHK(c, dmalloc(c->d_flags, 1));
+    MSLAM_CHK(c, hipMemset(c->d_flags, 0, 4));
     if(has_detector)
     {
     {
         // the FAST score kernels order f16 denormal bit patterns (arc_score.hpp): checked once, on the device, in this build
         uint32_t ok = 0;
         launch_denorm_selfcheck(c->d_flags, c->stream);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(&ok, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemset(c->d_flags, 0, 4));
+        MSLAM_CHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipMemcpyAsync(&ok, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipMemset(c->d_flags, 0, 4));
         if(ok != 1u)
             return fail(c, MSLAM_HIP_E_RUNTIME, "v_pk_minimum3_f16 / v_pk_maximum3_f16 do not preserve f16 denormals in this build "
                                                 "(the FAST score kernels need .amdhsa_float_denorm_mode_16_64 3): refusing to run");
     }
-    HIPCHK(c, dmalloc(c->d_stage, (size_t)p.width * p.height * 3));
+    MSLAM_CHK(c, dmalloc(c->d_stage, (size_t)p.width * p.height * 3));
     // + 64: the patch loads of k_describe may run a few bytes past the last row of the last frame
-    HIPCHK(c, dmalloc(c->d_pyr, B * g.slab + 256));
-    HIPCHK(c, dmalloc(c->d_blur, B * g.slab + 256));
+    MSLAM_CHK(c, dmalloc(c->d_pyr, B * g.slab + 256));
+    MSLAM_CHK(c, dmalloc(c->d_blur, B * g.slab + 256));
     {
         // k_level.hip (fused gray + blur): needs dword columns, 32-bit batch offsets and the exact float index split
         {
@@ -715,25 +698,25 @@ static int create_impl(mslam_hip_ctx* c)
         c->blur_wpf = (int)bw.size();
         if(!bw.empty())
         {
-            HIPCHK(c, dmalloc(c->d_blur_waves, bw.size()));
-            HIPCHK(c, hipMemcpy(c->d_blur_waves, bw.data(), bw.size() * sizeof(BlurWave), hipMemcpyHostToDevice));
+            MSLAM_CHK(c, dmalloc(c->d_blur_waves, bw.size()));
+            MSLAM_CHK(c, hipMemcpy(c->d_blur_waves, bw.data(), bw.size() * sizeof(BlurWave), hipMemcpyHostToDevice));
         }
     }
-    HIPCHK(c, dmalloc(c->d_cell_cnt, B * g.n_cells));
-    HIPCHK(c, dmalloc(c->d_cell_kp, B * g.n_cells * (size_t)kCellCap));
+    MSLAM_CHK(c, dmalloc(c->d_cell_cnt, B * g.n_cells));
+    MSLAM_CHK(c, dmalloc(c->d_cell_kp, B * g.n_cells * (size_t)kCellCap));
     QuadArgs& q = c->quad;
-    HIPCHK(c, dmalloc(q.cand, B * L * cap));
-    HIPCHK(c, dmalloc(q.cand_cnt, B * L));
-    HIPCHK(c, dmalloc(q.sel, B * L * cap));
-    HIPCHK(c, dmalloc(q.sel_cnt, B * L));
-    HIPCHK(c, dmalloc(q.kp_node, B * L * cap));
-    HIPCHK(c, dmalloc(q.nodes_a, B * L * cap));
-    HIPCHK(c, dmalloc(q.nodes_b, B * L * cap));
-    HIPCHK(c, dmalloc(q.ncnt_a, B * L * cap));
-    HIPCHK(c, dmalloc(q.ncnt_b, B * L * cap));
-    HIPCHK(c, dmalloc(q.child_cnt, B * L * cap * 4));
-    HIPCHK(c, dmalloc(q.ninfo, B * L * cap));
-    HIPCHK(c, dmalloc(q.best, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.cand, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.cand_cnt, B * L));
+    MSLAM_CHK(c, dmalloc(q.sel, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.sel_cnt, B * L));
+    MSLAM_CHK(c, dmalloc(q.kp_node, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.nodes_a, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.nodes_b, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.ncnt_a, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.ncnt_b, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.child_cnt, B * L * cap * 4));
+    MSLAM_CHK(c, dmalloc(q.ninfo, B * L * cap));
+    MSLAM_CHK(c, dmalloc(q.best, B * L * cap));
     q.cell_cnt = c->d_cell_cnt;
     q.cell_kp = c->d_cell_kp;
     q.flags = c->d_flags;
@@ -743,28 +726,28 @@ static int create_impl(mslam_hip_ctx* c)
 
     for(auto& o : c->out)
     {
-        HIPCHK(c, dmalloc(o.xy, (B + 1) * K * 2));
-        HIPCHK(c, dmalloc(o.desc, (B + 1) * K * 32));
-        HIPCHK(c, dmalloc(o.octave, (B + 1) * K));
-        HIPCHK(c, dmalloc(o.angle, (B + 1) * K));
-        HIPCHK(c, dmalloc(o.response, (B + 1) * K));
-        HIPCHK(c, dmalloc(o.count, B + 1));
-        HIPCHK(c, hipMemset(o.count, 0, (B + 1) * 4));
-        HIPCHK(c, dmalloc(o.idx0, B * K));
-        HIPCHK(c, dmalloc(o.idx1, B * K));
-        HIPCHK(c, dmalloc(o.dist0, B * K));
-        HIPCHK(c, dmalloc(o.dist1, B * K));
-        HIPCHK(c, dmalloc(o.mfrom, B * K));
-        HIPCHK(c, dmalloc(o.mto, B * K));
-        HIPCHK(c, dmalloc(o.mcount, B));
-        HIPCHK(c, hipMemset(o.mcount, 0, B * 4));
-        HIPCHK(c, hipEventCreateWithFlags(&o.ev_detect, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&o.ev_match, hipEventDisableTiming));
+        MSLAM_CHK(c, dmalloc(o.xy, (B + 1) * K * 2));
+        MSLAM_CHK(c, dmalloc(o.desc, (B + 1) * K * 32));
+        MSLAM_CHK(c, dmalloc(o.octave, (B + 1) * K));
+        MSLAM_CHK(c, dmalloc(o.angle, (B + 1) * K));
+        MSLAM_CHK(c, dmalloc(o.response, (B + 1) * K));
+        MSLAM_CHK(c, dmalloc(o.count, B + 1));
+        MSLAM_CHK(c, hipMemset(o.count, 0, (B + 1) * 4));
+        MSLAM_CHK(c, dmalloc(o.idx0, B * K));
+        MSLAM_CHK(c, dmalloc(o.idx1, B * K));
+        MSLAM_CHK(c, dmalloc(o.dist0, B * K));
+        MSLAM_CHK(c, dmalloc(o.dist1, B * K));
+        MSLAM_CHK(c, dmalloc(o.mfrom, B * K));
+        MSLAM_CHK(c, dmalloc(o.mto, B * K));
+        MSLAM_CHK(c, dmalloc(o.mcount, B));
+        MSLAM_CHK(c, hipMemset(o.mcount, 0, B * 4));
+        MSLAM_CHK(c, hipEventCreateWithFlags(&o.ev_detect, hipEventDisableTiming));
+        MSLAM_CHK(c, hipEventCreateWithFlags(&o.ev_match, hipEventDisableTiming));
     }
     // (the chunk streams and this one should sit on different hardware queues: streams that share a queue run one after the
     // other.  Giving them different PRIORITY classes to force that was measured — cfg5 380 -> 308 M, a second 640x480 context
     // 625 -> 491 M keypoints/s: the low class starves — and is not done.)
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stream_m, hipStreamNonBlocking));
+    MSLAM_CHK(c, hipStreamCreateWithFlags(&c->stream_m, hipStreamNonBlocking));
     {
         const char* e = getenv("MSLAM_HIP_OVERLAP_MATCH");
         c->overlap_match = !(e && atoi(e) == 0);
@@ -782,7 +765,7 @@ static int create_impl(mslam_hip_ctx* c)
         c->matcher_kind = (m && std::strcmp(m, "popcount") == 0) ? MSLAM_HIP_MATCHER_POPCOUNT : MSLAM_HIP_MATCHER_AUTO;
     }
     select_set(c, 0);
-    HIPCHK(c, hipDeviceSynchronize());
+    MSLAM_CHK(c, hipDeviceSynchronize());
     return MSLAM_HIP_OK;
 }
 
@@ -812,12 +795,12 @@ constexpr int kMinChunk = 8; // do not cut batches into chunks smaller than this
 static int check_flags(mslam_hip_ctx* c)
 {
     uint32_t f = 0;
-    HIPCHK(c, hipStreamSynchronize(c->stream_m));
-    HIPCHK(c, hipMemcpyAsync(&f, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream_m));
+    MSLAM_CHK(c, hipMemcpyAsync(&f, c->d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     if(f == 0)
         return MSLAM_HIP_OK;
-    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 4, c->stream));
+    MSLAM_CHK(c, hipMemsetAsync(c->d_flags, 0, 4, c->stream));
     std::string m = "capacity exceeded:";
     if(f & kFlagCandOverflow)
         m += " FAST candidates on a level > max_candidates;";
@@ -944,14 +927,14 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
     // everything runs on the context's stream so that the per-stage events are meaningful.
     const int n_chunks = (c->profiling || n_frames < 2 * kMinChunk) ? 1 : std::min<int>(c->n_side, n_frames / kMinChunk);
     if(n_chunks > 1)
-        HIPCHK(c, hipEventRecord(c->ev_fork, s));
+        MSLAM_CHK(c, hipEventRecord(c->ev_fork, s));
     for(int k = 0; k < n_chunks; ++k)
     {
         const int f0 = (int)((long long)n_frames * k / n_chunks), f1 = (int)((long long)n_frames * (k + 1) / n_chunks);
         const int nf = f1 - f0;
         hipStream_t cs = n_chunks > 1 ? c->side[k] : s;
         if(n_chunks > 1)
-            HIPCHK(c, hipStreamWaitEvent(cs, c->ev_fork, 0));
+            MSLAM_CHK(c, hipStreamWaitEvent(cs, c->ev_fork, 0));
         const bool cv_mode = c->p.detector == MSLAM_HIP_DETECTOR_CV_ORB;
         // gray + every level of the chunk in ONE launch (k_level_chain): batches whose levels all come from k_level.hip
         bool chained = false;
@@ -1117,20 +1100,20 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
         if(forked)
         {
             // quadtree (latency-bound, LDS-heavy) and blur (vector-ALU-bound, no LDS) only read the pyramid: side by side
-            HIPCHK(c, hipEventRecord(c->ev_blur_fork[k], cs));
-            HIPCHK(c, hipStreamWaitEvent(c->blur_stream[k], c->ev_blur_fork[k], 0));
+            MSLAM_CHK(c, hipEventRecord(c->ev_blur_fork[k], cs));
+            MSLAM_CHK(c, hipStreamWaitEvent(c->blur_stream[k], c->ev_blur_fork[k], 0));
             {
                 StageScope t(c, "blur", c->blur_stream[k]);
                 launch_blur(c->d_pyr, c->d_blur, g, c->d_blur_waves, c->blur_wpf, f0, nf, c->blur_stream[k]);
             }
-            HIPCHK(c, hipEventRecord(c->ev_blur_join[k], c->blur_stream[k]));
+            MSLAM_CHK(c, hipEventRecord(c->ev_blur_join[k], c->blur_stream[k]));
         }
         {
             StageScope t(c, "quadtree", cs);
             launch_quadtree(g, c->quad, f0, nf, cs);
         }
         if(forked)
-            HIPCHK(c, hipStreamWaitEvent(cs, c->ev_blur_join[k], 0));
+            MSLAM_CHK(c, hipStreamWaitEvent(cs, c->ev_blur_join[k], 0));
         else if(blur_needed)
         {
             StageScope t(c, "blur", cs);
@@ -1170,11 +1153,11 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
         }
         if(n_chunks > 1)
         {
-            HIPCHK(c, hipEventRecord(c->ev_join[k], cs));
-            HIPCHK(c, hipStreamWaitEvent(s, c->ev_join[k], 0));
+            MSLAM_CHK(c, hipEventRecord(c->ev_join[k], cs));
+            MSLAM_CHK(c, hipStreamWaitEvent(s, c->ev_join[k], 0));
         }
     }
-    HIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1193,7 +1176,7 @@ static int detect_prologue(mslam_hip_ctx* c)
         const int prev = c->cur, nxt = prev ^ 1;
         if(c->out[nxt].match_pending)
         {
-            HIPCHK(c, hipStreamWaitEvent(s, c->out[nxt].ev_match, 0));
+            MSLAM_CHK(c, hipStreamWaitEvent(s, c->out[nxt].ev_match, 0));
             c->out[nxt].match_pending = false;
         }
         // carry the last frame of the previous batch into slot 0 (predecessor of the new frame 0)
@@ -1202,7 +1185,7 @@ static int detect_prologue(mslam_hip_ctx* c)
         hipLaunchKernelGGL(k_carry_prev, dim3(16), dim3(256), 0, s, reinterpret_cast<uint4*>(c->out[nxt].desc),
                            reinterpret_cast<const uint4*>(c->out[prev].desc + last * K * 32), c->out[nxt].count,
                            c->out[prev].count + last, (int)K);
-        HIPCHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipGetLastError());
         c->have_prev = true;
         select_set(c, nxt);
     }
@@ -1222,7 +1205,7 @@ int mslam_hip_detect_batch_dev(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_fra
     rc = enqueue_detect(c, d_bgr, n_frames);
     if(rc)
         return rc;
-    HIPCHK(c, hipEventRecord(c->out[c->cur].ev_detect, c->stream));
+    MSLAM_CHK(c, hipEventRecord(c->out[c->cur].ev_detect, c->stream));
     c->n_last = n_frames;
     ++c->detect_seq;
     return MSLAM_HIP_OK;
@@ -1282,10 +1265,10 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
             return MSLAM_HIP_OK;
         hipLaunchKernelGGL(k_pack_results, dim3(32), dim3(256), 0, c->stream, c->d_xy + K * 2, c->d_desc + K * 32, c->d_octave + K,
                            c->d_angle + K, c->d_response + K, c->d_count + 1, c->d_flags, c->d_h_out, (int)K);
-        HIPCHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipGetLastError());
         return MSLAM_HIP_OK;
     };
-    HIPCHK(c, hipStreamSynchronize(c->stream_m));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream_m));
     // (the carry kernel of the prologue is queued first: it runs while the host stages the pageable frame for the copy)
     int rc = detect_prologue(c);
     if(rc)
@@ -1302,14 +1285,14 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
     {
         if(!c->h_stage)
         {
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), (size_t)width * height * 3, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_stage), c->h_stage, 0));
+            MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), (size_t)width * height * 3, hipHostMallocMapped));
+            MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_stage), c->h_stage, 0));
         }
         std::memcpy(c->h_stage, bgr, (size_t)width * height * 3);
         frame_src = c->d_h_stage;
     }
     else
-        HIPCHK(c, hipMemcpyAsync(c->d_stage, bgr, (size_t)width * height * 3, hipMemcpyHostToDevice, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(c->d_stage, bgr, (size_t)width * height * 3, hipMemcpyHostToDevice, c->stream));
     // The single-frame call is launch-bound (11 small kernels), so its fixed sequence — kernels + the result packing
     // kernel — is captured once per output set into a HIP graph and replayed.  With stage timing on, the plain path runs.
     if(!c->profiling && !c->inplace_timing && c->use_graph)
@@ -1318,7 +1301,7 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
         if(!exec)
         {
             hipGraph_t graph = nullptr;
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
+            MSLAM_CHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
             rc = enqueue_detect(c, frame_src, 1);
             if(!rc)
                 rc = enqueue_results();
@@ -1331,10 +1314,10 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
                 exec = nullptr;
             if(rc)
                 return rc;
-            HIPCHK(c, e);
-            HIPCHK(c, e_inst);
+            MSLAM_CHK(c, e);
+            MSLAM_CHK(c, e_inst);
         }
-        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+        MSLAM_CHK(c, hipGraphLaunch(exec, c->stream));
     }
     else
     {
@@ -1345,10 +1328,10 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
         if(rc)
             return rc;
     }
-    HIPCHK(c, hipEventRecord(c->out[c->cur].ev_detect, c->stream));
+    MSLAM_CHK(c, hipEventRecord(c->out[c->cur].ev_detect, c->stream));
     c->n_last = 1;
     ++c->detect_seq;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     uint32_t flags;
     int32_t n;
     std::memcpy(&n, h, 4);
@@ -1390,9 +1373,9 @@ static int upload_ratio_table(mslam_hip_ctx* c, double ratio)
         thr[d1] = n;
     }
     // a ratio test of an earlier batch may still be reading the table on the matcher stream
-    HIPCHK(c, hipStreamSynchronize(c->stream_m));
-    HIPCHK(c, hipMemcpyAsync(c->d_ratio_thr, thr, sizeof(thr), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // thr is a stack buffer
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream_m));
+    MSLAM_CHK(c, hipMemcpyAsync(c->d_ratio_thr, thr, sizeof(thr), hipMemcpyHostToDevice, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // thr is a stack buffer
     c->ratio_cached = ratio;
     return MSLAM_HIP_OK;
 }
@@ -1416,9 +1399,9 @@ int mslam_hip_match_batch_dev(mslam_hip_ctx* c, double ratio, int chain_previous
     const bool own = c->overlap_match && !c->profiling;
     hipStream_t s = own ? c->stream_m : c->stream;
     if(own)
-        HIPCHK(c, hipStreamWaitEvent(s, c->out[c->cur].ev_detect, 0));
+        MSLAM_CHK(c, hipStreamWaitEvent(s, c->out[c->cur].ev_detect, 0));
     if(first == 1)
-        HIPCHK(c, hipMemsetAsync(c->d_mcount, 0, 4, s));
+        MSLAM_CHK(c, hipMemsetAsync(c->d_mcount, 0, 4, s));
     if(n_pairs > 0)
     {
         MatchArgs m{};
@@ -1455,10 +1438,10 @@ int mslam_hip_match_batch_dev(mslam_hip_ctx* c, double ratio, int chain_previous
             launch_ratio_compact(r, n_pairs, s);
         }
     }
-    HIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     if(own)
     {
-        HIPCHK(c, hipEventRecord(c->out[c->cur].ev_match, s));
+        MSLAM_CHK(c, hipEventRecord(c->out[c->cur].ev_match, s));
         c->out[c->cur].match_pending = true;
     }
     return MSLAM_HIP_OK;
@@ -1470,7 +1453,7 @@ static int host_match_prepare(mslam_hip_ctx* c, const uint8_t* from_desc, int n_
     // device descriptors: ONE buffer [train rows | query rows], so that one copy fills both
     if(n_from > c->hm_from_cap || n_to > c->hm_to_cap)
     {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
         const int from_cap = std::max(n_from, std::max(c->hm_from_cap, 2048)), to_cap = std::max(n_to, std::max(c->hm_to_cap, 2048));
         if(c->d_hm_from)
             (void)hipFree(c->d_hm_from);
@@ -1484,12 +1467,12 @@ static int host_match_prepare(mslam_hip_ctx* c, const uint8_t* from_desc, int n_
         c->h_hm = nullptr;
         c->d_h_hm = nullptr;
         c->hm_from_cap = c->hm_to_cap = 0;
-        HIPCHK(c, dmalloc(c->d_hm_from, (size_t)(from_cap + to_cap) * 32 + 16)); // (+ 16: the captured form's counts ride behind the rows)
-        HIPCHK(c, dmalloc(c->d_hm_out, (size_t)to_cap * 6 + 4));
+        MSLAM_CHK(c, dmalloc(c->d_hm_from, (size_t)(from_cap + to_cap) * 32 + 16)); // (+ 16: the captured form's counts ride behind the rows)
+        MSLAM_CHK(c, dmalloc(c->d_hm_out, (size_t)to_cap * 6 + 4));
         if(c->d_hm_partial)
             (void)hipFree(c->d_hm_partial);
         c->d_hm_partial = nullptr;
-        HIPCHK(c, dmalloc(c->d_hm_partial, (size_t)kHostMatchSlices * 2 * to_cap));
+        MSLAM_CHK(c, dmalloc(c->d_hm_partial, (size_t)kHostMatchSlices * 2 * to_cap));
         // page-locked, device-mapped: [descriptor staging (from | to) | from_idx | to_idx | n_out] — the caller's
         // (pageable) descriptors are copied here by the CPU and go up in ONE asynchronous copy (two blocking pageable
         // copies cost 25 us of the 84 us call); the ratio kernel writes its compacted pairs straight into the block
@@ -1499,8 +1482,8 @@ static int host_match_prepare(mslam_hip_ctx* c, const uint8_t* from_desc, int n_
             (void)hipGraphExecDestroy(c->match_graph); // captured on the buffers just freed
             c->match_graph = nullptr;
         }
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_hm), bytes, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_hm), c->h_hm, 0));
+        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_hm), bytes, hipHostMallocMapped));
+        MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_hm), c->h_hm, 0));
         c->hm_from_cap = from_cap;
         c->hm_to_cap = to_cap;
     }
@@ -1508,7 +1491,7 @@ static int host_match_prepare(mslam_hip_ctx* c, const uint8_t* from_desc, int n_
     if(n_from > 0)
         std::memcpy(c->h_hm, from_desc, (size_t)n_from * 32);
     std::memcpy(c->h_hm + (size_t)n_from * 32, to_desc, (size_t)n_to * 32);
-    HIPCHK(c, hipMemcpyAsync(c->d_hm_from, c->h_hm, (size_t)(n_from + n_to) * 32, hipMemcpyHostToDevice, c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(c->d_hm_from, c->h_hm, (size_t)(n_from + n_to) * 32, hipMemcpyHostToDevice, c->stream));
     return MSLAM_HIP_OK;
 }
 
@@ -1557,7 +1540,7 @@ static int host_match_graph(mslam_hip_ctx* c, const uint8_t* from_desc, int n_fr
             (void)hipGraphExecDestroy(c->match_graph);
         c->match_graph = nullptr;
         hipGraph_t graph = nullptr;
-        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
+        MSLAM_CHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
         hipError_t e = hipMemcpyAsync(c->d_hm_from, c->h_hm, (fcap + tcap) * 32 + 16, hipMemcpyHostToDevice, c->stream);
         const int32_t* d_cnt = reinterpret_cast<const int32_t*>(c->d_hm_from + (fcap + tcap) * 32);
         MatchArgs m{};
@@ -1602,18 +1585,18 @@ static int host_match_graph(mslam_hip_ctx* c, const uint8_t* from_desc, int n_fr
             (void)hipGraphDestroy(graph);
         if(e3 != hipSuccess)
             c->match_graph = nullptr;
-        HIPCHK(c, e);
-        HIPCHK(c, e_launch);
-        HIPCHK(c, e2);
-        HIPCHK(c, e3);
+        MSLAM_CHK(c, e);
+        MSLAM_CHK(c, e_launch);
+        MSLAM_CHK(c, e2);
+        MSLAM_CHK(c, e3);
         c->match_graph_from_cap = c->hm_from_cap;
         c->match_graph_to_cap = c->hm_to_cap;
         c->match_graph_kind = c->matcher_kind;
         c->match_graph_kernel = c->last_match_kernel;
     }
     c->last_match_kernel = c->match_graph_kernel;
-    HIPCHK(c, hipGraphLaunch(c->match_graph, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipGraphLaunch(c->match_graph, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     const int32_t n = res[2 * tcap];
     if(n < 0 || n > n_to || (size_t)n > tcap) // (a count from mapped memory sizes the copies below: never trust it blindly)
         return fail(c, MSLAM_HIP_E_RUNTIME, "match: the kernel reported an impossible match count");
@@ -1628,7 +1611,7 @@ int mslam_hip_join_matcher(mslam_hip_ctx* c)
     ENTER(c);
     for(auto& o : c->out)
         if(o.match_pending)
-            HIPCHK(c, hipStreamWaitEvent(c->stream, o.ev_match, 0)); // stays pending: detect_prologue still orders on it
+            MSLAM_CHK(c, hipStreamWaitEvent(c->stream, o.ev_match, 0)); // stays pending: detect_prologue still orders on it
     return MSLAM_HIP_OK;
 }
 
@@ -1652,7 +1635,7 @@ int mslam_hip_set_cv_keypoint_order(mslam_hip_ctx* c, int order)
     if(order == c->cv_order)
         return MSLAM_HIP_OK;
     // the captured single-frame sequences carry the order as a kernel argument: drop them, the next call captures again
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     for(auto& e : c->detect_graph)
         if(e)
         {
@@ -1680,12 +1663,12 @@ int mslam_hip_match_knn2(mslam_hip_ctx* c, const uint8_t* from_desc, int n_from,
     MatchArgs m;
     host_match_args(c, n_from, n_to, m);
     c->last_match_kernel = launch_match_knn2(m, 1, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(idx0, m.idx0, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(idx1, m.idx1, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dist0, m.dist0, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dist1, m.dist1, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipMemcpyAsync(idx0, m.idx0, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(idx1, m.idx1, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(dist0, m.dist0, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(dist1, m.dist1, (size_t)n_to * 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     return MSLAM_HIP_OK;
 }
 
@@ -1717,7 +1700,7 @@ int mslam_hip_match(mslam_hip_ctx* c, const uint8_t* from_desc, int n_from, cons
        c->hm_from_cap + c->hm_to_cap <= 2 * (n_from + n_to) + 2048)
     {
         // (first call / the buffers have just grown: the plain path's copy is queued — let it drain, then take the captured form)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
         return host_match_graph(c, from_desc, n_from, to_desc, n_to, n_out, from_idx, to_idx);
     }
     MatchArgs m;
@@ -1739,8 +1722,8 @@ int mslam_hip_match(mslam_hip_ctx* c, const uint8_t* from_desc, int n_from, cons
     r.to_idx = res_dev + cap;
     r.n_out = res_dev + 2 * cap;
     launch_ratio_compact(r, 1, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     const int32_t n = res[2 * cap];
     std::memcpy(from_idx, res, (size_t)n * 4);
     std::memcpy(to_idx, res + cap, (size_t)n * 4);
@@ -1771,7 +1754,7 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
     ENTER(c);
     if(c->p.width == 0 || frame < 0 || frame >= c->p.max_batch || level < 0 || level >= c->geom.n_levels || !dst || !n_items)
         return fail(c, MSLAM_HIP_E_INVALID, "debug_read: bad argument");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     const LevelGeom& lv = c->geom.lv[level];
     if(what == MSLAM_HIP_DBG_PYRAMID || what == MSLAM_HIP_DBG_BLURRED)
     {
@@ -1784,14 +1767,14 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
         {
             // the blurred slab is stored in tiles: copy the plane's tile rows and put the rows back together here
             std::vector<uint8_t> tmp((size_t)lv.pitch * ((lv.h + kTileH - 1) & ~(kTileH - 1)));
-            HIPCHK(c, hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost));
+            MSLAM_CHK(c, hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost));
             uint8_t* out = static_cast<uint8_t*>(dst);
             for(int y = 0; y < lv.h; ++y)
                 for(int x = 0; x < lv.w; ++x)
                     out[(size_t)y * lv.w + x] = tmp[tiled_off((unsigned)lv.pitch, x, y)];
             return MSLAM_HIP_OK;
         }
-        HIPCHK(c, hipMemcpy2D(dst, lv.w, src, lv.pitch, lv.w, lv.h, hipMemcpyDeviceToHost));
+        MSLAM_CHK(c, hipMemcpy2D(dst, lv.w, src, lv.pitch, lv.w, lv.h, hipMemcpyDeviceToHost));
         return MSLAM_HIP_OK;
     }
     if(what == MSLAM_HIP_DBG_CANDIDATES || what == MSLAM_HIP_DBG_SELECTED)
@@ -1799,15 +1782,15 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
         const size_t slot = (size_t)frame * c->geom.n_levels + level;
         const bool cand = what == MSLAM_HIP_DBG_CANDIDATES;
         uint32_t n = 0;
-        HIPCHK(c, hipMemcpy(&n, (cand ? c->quad.cand_cnt : c->quad.sel_cnt) + slot, 4, hipMemcpyDeviceToHost));
+        MSLAM_CHK(c, hipMemcpy(&n, (cand ? c->quad.cand_cnt : c->quad.sel_cnt) + slot, 4, hipMemcpyDeviceToHost));
         n = std::min<uint32_t>(n, (uint32_t)c->p.max_candidates); // an overflowing level keeps counting (flagged separately)
         *n_items = n;
         if(dst_bytes < (size_t)n * 12)
             return fail(c, MSLAM_HIP_E_CAPACITY, "debug_read: buffer too small");
         std::vector<uint32_t> tmp(n);
         if(n)
-            HIPCHK(c, hipMemcpy(tmp.data(), (cand ? c->quad.cand : c->quad.sel) + slot * (size_t)c->p.max_candidates,
-                                (size_t)n * 4, hipMemcpyDeviceToHost));
+            MSLAM_CHK(c, hipMemcpy(tmp.data(), (cand ? c->quad.cand : c->quad.sel) + slot * (size_t)c->p.max_candidates,
+                                   (size_t)n * 4, hipMemcpyDeviceToHost));
         // cv::ORB mode, library order, a level beyond k_cv_select's LDS arrays: both retainBest calls permute the level's list
         // in place (every other array of the slot is rank scratch, there is none to keep a copy in), so what is left is
         // FAST's SET in libstdc++'s order.  FAST's order is ascending order of the packed words: put it back here — only
@@ -1827,8 +1810,8 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
             // Harris response
             std::vector<float> resp(n);
             if(n)
-                HIPCHK(c, hipMemcpy(resp.data(), reinterpret_cast<const float*>(c->quad.best) + slot * (size_t)c->p.max_candidates,
-                                    (size_t)n * 4, hipMemcpyDeviceToHost));
+                MSLAM_CHK(c, hipMemcpy(resp.data(), reinterpret_cast<const float*>(c->quad.best) + slot * (size_t)c->p.max_candidates,
+                                       (size_t)n * 4, hipMemcpyDeviceToHost));
             for(uint32_t i = 0; i < n; ++i)
             {
                 out[3 * i] += (float)kBorder;
@@ -1869,12 +1852,12 @@ int mslam_hip_debug_counts(mslam_hip_ctx* c, int what, int32_t* out, int n_frame
     ENTER(c);
     if(c->p.width == 0 || !out || n_frames < 1 || (what != MSLAM_HIP_DBG_CANDIDATES && what != MSLAM_HIP_DBG_SELECTED))
         return fail(c, MSLAM_HIP_E_INVALID, "debug_counts: bad argument");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     // the scratch arrays are indexed by the frame's position in the batch: [frame][level]; never more rows than the
     // caller has room for
     const int rows = std::min(n_frames, std::max(c->n_last, 1));
-    HIPCHK(c, hipMemcpy(out, what == MSLAM_HIP_DBG_CANDIDATES ? c->quad.cand_cnt : c->quad.sel_cnt,
-                        (size_t)rows * c->geom.n_levels * 4, hipMemcpyDeviceToHost));
+    MSLAM_CHK(c, hipMemcpy(out, what == MSLAM_HIP_DBG_CANDIDATES ? c->quad.cand_cnt : c->quad.sel_cnt,
+                           (size_t)rows * c->geom.n_levels * 4, hipMemcpyDeviceToHost));
     return MSLAM_HIP_OK;
 }
 
@@ -1883,9 +1866,9 @@ int mslam_hip_copy_to_host(mslam_hip_ctx* c, void* dst_host, const void* src_dev
     ENTER(c);
     if(!dst_host || !src_dev)
         return fail(c, MSLAM_HIP_E_INVALID, "copy_to_host: null pointer");
-    HIPCHK(c, hipStreamSynchronize(c->stream_m));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream_m));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
     return MSLAM_HIP_OK;
 }
 
@@ -1904,13 +1887,13 @@ int mslam_hip_get_stage_times(mslam_hip_ctx* c, const char** names, float* ms, i
     ENTER(c);
     if(!n)
         return fail(c, MSLAM_HIP_E_INVALID, "get_stage_times: null output");
-    HIPCHK(c, hipStreamSynchronize(c->stream_m));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream_m));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     int k = 0;
     for(size_t i = 0; i < c->timers_used && k < cap; ++i, ++k)
     {
         float t = 0;
-        HIPCHK(c, hipEventElapsedTime(&t, c->timers[i].start, c->timers[i].stop));
+        MSLAM_CHK(c, hipEventElapsedTime(&t, c->timers[i].start, c->timers[i].stop));
         if(names)
             names[k] = c->timers[i].name;
         if(ms)

@@ -13,6 +13,8 @@ constexpr int kCell = 64;      // cell_size, :853
 constexpr int kOverlap = 6;    // overlap,   :852
 constexpr int kCellCap = 1024; // NMS keeps at most one corner per 2x2 block of a 64x64 tested area
 
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; } // scratch arrays start on 256-byte boundaries
+
 // One pyramid level inside a frame's slab.  All fields are filled on the host at context creation.
 struct LevelGeom
 {

@@ -165,8 +165,26 @@ struct mslam_hip_ctx
     size_t timers_used = 0;
 };
 
+// a failed HIP call ends the entry point: the call's own text and HIP's message become the context's error
+#define MSLAM_CHK(c, call)                                                                                             \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t e_ = (call);                                                                                        \
+        if(e_ != hipSuccess)                                                                                           \
+        {                                                                                                              \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
+            return MSLAM_HIP_E_RUNTIME;                                                                                \
+        }                                                                                                              \
+    } while(0)
+
 namespace mslam
 {
+inline int fail(mslam_hip_ctx* c, int code, const std::string& msg)
+{
+    c->err = msg;
+    return code;
+}
+
 // Records a [start, stop] HIP-event pair around a stage.  Mode 1 (profiling): everything runs on the context's
 // stream, so the events go there and the stages do not overlap.  Mode 2 (inplace_timing): the events are
 // recorded on the stream the stage is launched on, which does not change the schedule; entries accumulate until

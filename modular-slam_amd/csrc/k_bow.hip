@@ -989,23 +989,6 @@ __global__ __launch_bounds__(256) void k_bow_cross_packed(const uint32_t* __rest
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-#define BHIPCHK(c, call)                                                                                               \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
-static int bfail(mslam_hip_ctx* c, int code, const char* msg)
-{
-    c->err = msg;
-    return code;
-}
-
 template <typename T>
 static hipError_t bmalloc(T*& p, size_t n)
 {
@@ -1045,27 +1028,27 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
     // Vocabulary::fromStream (dbow3.patch:2544-2651)
     Reader r{static_cast<const uint8_t*>(blob), size};
     if(r.get<uint64_t>() != 88877711233ull)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad magic (not a DBoW3 binary vocabulary)");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad magic (not a DBoW3 binary vocabulary)");
     const uint8_t compressed = r.get<uint8_t>();
     const uint32_t n_nodes = r.get<uint32_t>();
     if(!r.ok || n_nodes == 0)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: empty vocabulary");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: empty vocabulary");
     std::vector<uint8_t> body; // the decompressed stream when the file was saved with compressed = true
     if(compressed)
     {
         // dbow3.patch:2594-2611: u32 nChunks, then one QuickLZ packet per 10 000 bytes of the stream below
         const uint32_t n_chunks = r.get<uint32_t>();
         if(!r.ok || qlz_decode_stream(r.p + r.pos, size - r.pos, n_chunks, body) != MSLAM_HIP_OK)
-            return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: cannot decode the QuickLZ packets of a compressed vocabulary "
-                                                "(levels 1 and 3 of QuickLZ 1.5 are handled)");
+            return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: cannot decode the QuickLZ packets of a compressed vocabulary "
+                                               "(levels 1 and 3 of QuickLZ 1.5 are handled)");
         r = Reader{body.data(), body.size()};
         size = body.size();
     }
     const int k = r.get<int32_t>(), L = r.get<int32_t>(), scoring = r.get<int32_t>(), weighting = r.get<int32_t>();
     if(!r.ok || k < 1 || weighting < 0 || weighting > 3 || scoring < 0 || scoring > 5)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad header");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad header");
     if(scoring != MSLAM_BOW_L1_NORM)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: only L1_NORM scoring vocabularies are supported");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: only L1_NORM scoring vocabularies are supported");
     std::vector<uint32_t> parent(n_nodes, 0), order(n_nodes, 0), nchild(n_nodes, 0), word(n_nodes, 0);
     std::vector<double> weight(n_nodes, 0.0);
     std::vector<uint8_t> desc((size_t)n_nodes * 32, 0);
@@ -1075,7 +1058,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
         const double w = r.get<double>();
         const int32_t cols = r.get<int32_t>(), rows = r.get<int32_t>(), type = r.get<int32_t>(); // DescManip::fromStream
         if(!r.ok || nid >= n_nodes || par >= n_nodes || cols != 32 || rows != 1 || type != 0 || r.pos + 32 > size)
-            return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad node record (only 32-byte CV_8U descriptors are supported)");
+            return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad node record (only 32-byte CV_8U descriptors are supported)");
         parent[nid] = par;
         weight[nid] = w;
         std::memcpy(&desc[(size_t)nid * 32], r.p + r.pos, 32);
@@ -1085,7 +1068,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
     }
     const uint32_t n_words = r.get<uint32_t>();
     if(!r.ok || (size_t)n_words * 8 > size - r.pos)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: truncated stream");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: truncated stream");
     // word records per node and per word id, for the flat mode's one-to-one check below
     std::vector<uint32_t> node_words(n_nodes, 0);
     std::vector<uint8_t> wid_seen(n_words, 0);
@@ -1094,7 +1077,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
     {
         const uint32_t wid = r.get<uint32_t>(), nid = r.get<uint32_t>();
         if(!r.ok || wid >= n_words || nid >= n_nodes)
-            return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad word record");
+            return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: bad word record");
         word[nid] = wid;
         wids_distinct = wids_distinct && !wid_seen[wid];
         wid_seen[wid] = 1;
@@ -1114,7 +1097,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
     uint32_t next = 1, head = 0;
     int max_children = 0;
     if(nchild[0] == 0)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: root has no children");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: root has no children");
     while(head < next)
     {
         const uint32_t nid = slot_node[head++];
@@ -1123,15 +1106,15 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
         {
             const uint32_t ch = child[coff[nid] + j];
             if(next >= n_nodes)
-                return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: tree is not connected");
+                return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: tree is not connected");
             node_slot[ch] = next;
             slot_node[next++] = ch;
         }
     }
     if(next != n_nodes)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: unreachable nodes");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: unreachable nodes");
     if(max_children > 65535)
-        return bfail(c, MSLAM_HIP_E_FORMAT, "bow_load: branching factor too large");
+        return fail(c, MSLAM_HIP_E_FORMAT, "bow_load: branching factor too large");
     std::vector<uint8_t> sdesc((size_t)n_nodes * 32);
     std::vector<uint32_t> sfirst(n_nodes), snchild(n_nodes), sword(n_nodes);
     std::vector<double> sweight(n_nodes);
@@ -1153,7 +1136,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
             slots <<= 1;
         const size_t lds = (size_t)c->p.max_keypoints * 8 + ((size_t)slots + c->p.max_keypoints) * 4;
         if(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->p.device) != hipSuccess)
-            return bfail(c, MSLAM_HIP_E_RUNTIME, "bow_load: cannot query the LDS size");
+            return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: cannot query the LDS size");
         if(lds > (size_t)lds_max || c->p.max_keypoints > 8192)
         {
             c->err = "bow_load: max_keypoints = " + std::to_string(c->p.max_keypoints) + " needs " + std::to_string(lds) +
@@ -1260,7 +1243,7 @@ static int bow_transform_dev(mslam_hip_ctx* c, const uint8_t* d_desc, long long 
     {
         StageScope t(c, "bow_flat");
         uint32_t* best = b->d_fbest + (size_t)slot0 * cap;
-        BHIPCHK(c, hipMemsetAsync(best, 0xFF, (size_t)n_frames * cap * 4, s));
+        MSLAM_CHK(c, hipMemsetAsync(best, 0xFF, (size_t)n_frames * cap * 4, s));
         // slices: enough workgroups to fill 256 CUs x 8 even for a single frame, at least 2048 words each
         const int qblocks = (cap + 63) / 64;
         int n_slices = std::max(1, std::min((int)((b->n_words + 2047) / 2048), std::max(1, 4096 / std::max(1, qblocks * n_frames))));
@@ -1284,13 +1267,13 @@ static int bow_transform_dev(mslam_hip_ctx* c, const uint8_t* d_desc, long long 
         StageScope t(c, "bow_vector");
         const int npow2 = pow2_at_least(cap);
         if((size_t)npow2 * 8 > 48 * 1024)
-            BHIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_vector),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, npow2 * 8));
+            MSLAM_CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_vector),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, npow2 * 8));
         hipLaunchKernelGGL(k_bow_vector, dim3(n_frames), dim3(VT), (size_t)npow2 * 8, s, b->d_fword + (size_t)slot0 * cap,
                            b->d_fweight + (size_t)slot0 * cap, d_counts, n_fixed, cap, npow2, b->weighting, b->scoring,
                            b->d_bwords, b->d_bvalues, b->d_bn, slot0);
     }
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1303,8 +1286,8 @@ static int bow_score_dev(mslam_hip_ctx* c, int qslot, int n_frames, long long ba
         slots <<= 1;
     const size_t lds = (size_t)b->cap * 8 + (size_t)(slots + b->cap) * 4;
     if(lds > 48 * 1024)
-        BHIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_score),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MSLAM_CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_score),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_bow_score, dim3(kScoreBlocksPerFrame, n_frames), dim3(64 * kScoreWaves), lds, c->stream, b->d_bwords, b->d_bvalues, b->d_bn, qslot,
                        b->cap, b->d_rwords, b->d_rvalues, b->d_rn, base_id, per_frame_id, b->R, b->RP, slots, b->d_contrib,
                        b->d_match_cnt);
@@ -1312,7 +1295,7 @@ static int bow_score_dev(mslam_hip_ctx* c, int qslot, int n_frames, long long ba
                        qslot, b->cap, b->R, b->d_scores);
     hipLaunchKernelGGL(k_bow_best, dim3(n_frames), dim3(64), 0, c->stream, b->d_scores, qslot, base_id, per_frame_id, b->R,
                        b->d_best_entry, b->d_best_score);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1321,12 +1304,12 @@ template <typename T>
 static int ix_grow(mslam_hip_ctx* c, T*& ptr, size_t old_n, size_t new_n, bool zero)
 {
     T* np = nullptr;
-    BHIPCHK(c, bmalloc(np, new_n));
+    MSLAM_CHK(c, bmalloc(np, new_n));
     if(zero)
-        BHIPCHK(c, hipMemsetAsync(np, 0, new_n * sizeof(T), c->stream));
+        MSLAM_CHK(c, hipMemsetAsync(np, 0, new_n * sizeof(T), c->stream));
     if(ptr && old_n)
-        BHIPCHK(c, hipMemcpyAsync(np, ptr, old_n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(np, ptr, old_n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     if(ptr)
         (void)hipFree(ptr);
     ptr = np;
@@ -1340,7 +1323,7 @@ static int ix_reserve(mslam_hip_ctx* c, long long max_entries)
     if(max_entries <= b->ix_max_entries)
         return MSLAM_HIP_OK;
     if(max_entries > (1ll << 31) / std::max(b->cap, 1))
-        return bfail(c, MSLAM_HIP_E_CAPACITY, "bow database: more postings than a 32-bit index can address");
+        return fail(c, MSLAM_HIP_E_CAPACITY, "bow database: more postings than a 32-bit index can address");
     const size_t old_e = (size_t)b->ix_max_entries, new_e = (size_t)max_entries;
     const size_t old_p = b->ix_cap_postings ? b->ix_cap_postings + 1 : 0, new_p = new_e * (size_t)b->cap + 1;
     int rc = 0;
@@ -1377,7 +1360,7 @@ static int ix_add(mslam_hip_ctx* c, int slot0, int n)
     hipLaunchKernelGGL(k_ix_append, dim3(n), dim3(256), 0, c->stream, b->d_bwords + (size_t)slot0 * b->cap,
                        b->d_bvalues + (size_t)slot0 * b->cap, b->d_bn + slot0, b->cap, b->next_id, b->ix_ofs, b->ix_size,
                        (uint32_t)b->ix_cap_postings, b->ix_head, b->ix_entry, b->ix_prev, b->ix_value);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1387,8 +1370,8 @@ static int ix_query(mslam_hip_ctx* c, int qslot, long long id_limit)
     BowState* b = c->bow;
     hipStream_t s = c->stream;
     const long long N = id_limit;
-    BHIPCHK(c, hipMemsetAsync(b->ix_cnt, 0, (size_t)N * 4, s));
-    BHIPCHK(c, hipMemsetAsync(b->ix_fill, 0, (size_t)N * 4, s));
+    MSLAM_CHK(c, hipMemsetAsync(b->ix_cnt, 0, (size_t)N * 4, s));
+    MSLAM_CHK(c, hipMemsetAsync(b->ix_fill, 0, (size_t)N * 4, s));
     const uint32_t* qw = b->d_bwords + (size_t)qslot * b->cap;
     const double* qv = b->d_bvalues + (size_t)qslot * b->cap;
     const int32_t* qn = b->d_bn + qslot;
@@ -1402,7 +1385,7 @@ static int ix_query(mslam_hip_ctx* c, int qslot, long long id_limit)
                        (uint32_t)b->ix_cap_terms);
     const unsigned blocks = (unsigned)std::min<long long>((N + 3) / 4, 4096);
     hipLaunchKernelGGL(k_ix_sum, dim3(blocks), dim3(256), 0, s, b->ix_cnt, b->ix_ofs, b->ix_keys, b->ix_vals, N, b->ix_scores);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1410,7 +1393,7 @@ int bow_batch(mslam_hip_ctx* c, int add_to_db)
 {
     BowState* b = c->bow;
     if(c->n_last < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_batch_dev: no detect batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_batch_dev: no detect batch");
     const size_t K = (size_t)c->p.max_keypoints;
     const int n = c->n_last;
     int rc = bow_transform_dev(c, c->d_desc + K * 32, (long long)K * 32, c->d_count + 1, 0, n, 0);
@@ -1445,7 +1428,7 @@ static int need_voc(mslam_hip_ctx* c)
         c->err = "no vocabulary loaded (call mslam_hip_bow_load first)";
         return MSLAM_HIP_E_NO_VOCABULARY;
     }
-    BHIPCHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     return MSLAM_HIP_OK;
 }
 
@@ -1454,9 +1437,9 @@ static int host_transform(mslam_hip_ctx* c, const uint8_t* desc, int n)
 {
     BowState* b = c->bow;
     if(n < 0 || n > b->cap || (n > 0 && !desc))
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow: descriptor count outside [0, max_keypoints]");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow: descriptor count outside [0, max_keypoints]");
     if(n > 0)
-        BHIPCHK(c, hipMemcpyAsync(b->d_hdesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(b->d_hdesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
     return bow_transform_dev(c, b->d_hdesc, 0, nullptr, n, 1, b->B);
 }
 
@@ -1467,17 +1450,17 @@ int mslam_hip_bow_load(mslam_hip_ctx* c, const void* blob, size_t size)
     if(!c)
         return MSLAM_HIP_E_INVALID;
     if(!blob)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_load: null blob");
-    BHIPCHK(c, hipSetDevice(c->p.device));
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_load: null blob");
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     if(hipStreamSynchronize(c->stream) != hipSuccess)
-        return bfail(c, MSLAM_HIP_E_RUNTIME, "bow_load: stream sync failed");
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: stream sync failed");
     try
     {
         return bow_load_impl(c, blob, size);
     }
     catch(const std::bad_alloc&) // an untrusted header can ask for more host memory than there is: no exception crosses the C ABI
     {
-        return bfail(c, MSLAM_HIP_E_RUNTIME, "bow_load: out of host memory while decoding the vocabulary");
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: out of host memory while decoding the vocabulary");
     }
 }
 
@@ -1505,14 +1488,14 @@ int mslam_hip_bow_words(mslam_hip_ctx* c, const uint8_t* desc, int n, uint32_t* 
     if(n == 0)
         return MSLAM_HIP_OK;
     if(!word || !weight)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_words: null output");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_words: null output");
     rc = host_transform(c, desc, n);
     if(rc)
         return rc;
     const size_t o = (size_t)b->B * b->cap;
-    BHIPCHK(c, hipMemcpyAsync(word, b->d_fword + o, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    BHIPCHK(c, hipMemcpyAsync(weight, b->d_fweight + o, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(word, b->d_fword + o, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(weight, b->d_fweight + o, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     return MSLAM_HIP_OK;
 }
 
@@ -1523,21 +1506,21 @@ int mslam_hip_bow_transform(mslam_hip_ctx* c, const uint8_t* desc, int n, uint32
         return rc;
     BowState* b = c->bow;
     if(!n_words)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_transform: null output");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_transform: null output");
     *n_words = 0;
     rc = host_transform(c, desc, n);
     if(rc)
         return rc;
     int32_t m = 0;
-    BHIPCHK(c, hipMemcpyAsync(&m, b->d_bn + b->B, 4, hipMemcpyDeviceToHost, c->stream));
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(&m, b->d_bn + b->B, 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     if(m > 0)
     {
         if(!words || !values)
-            return bfail(c, MSLAM_HIP_E_INVALID, "bow_transform: null output");
+            return fail(c, MSLAM_HIP_E_INVALID, "bow_transform: null output");
         const size_t o = (size_t)b->B * b->cap;
-        BHIPCHK(c, hipMemcpy(words, b->d_bwords + o, (size_t)m * 4, hipMemcpyDeviceToHost));
-        BHIPCHK(c, hipMemcpy(values, b->d_bvalues + o, (size_t)m * 8, hipMemcpyDeviceToHost));
+        MSLAM_CHK(c, hipMemcpy(words, b->d_bwords + o, (size_t)m * 4, hipMemcpyDeviceToHost));
+        MSLAM_CHK(c, hipMemcpy(values, b->d_bvalues + o, (size_t)m * 8, hipMemcpyDeviceToHost));
     }
     *n_words = m;
     return MSLAM_HIP_OK;
@@ -1551,7 +1534,7 @@ int mslam_hip_bow_score(mslam_hip_ctx* c, const uint32_t* w1, const double* v1, 
         return rc;
     BowState* b = c->bow;
     if(!score || n1 < 0 || n2 < 0 || n1 > b->cap || n2 > b->cap || (n1 > 0 && (!w1 || !v1)) || (n2 > 0 && (!w2 || !v2)))
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_score: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_score: bad argument");
     // vector 1 -> the host-query batch slot, vector 2 -> the per-feature scratch of that slot
     const size_t o = (size_t)b->B * b->cap;
     uint32_t* tw = b->d_fword + o;
@@ -1559,19 +1542,19 @@ int mslam_hip_bow_score(mslam_hip_ctx* c, const uint32_t* w1, const double* v1, 
     hipStream_t s = c->stream;
     if(n1 > 0)
     {
-        BHIPCHK(c, hipMemcpyAsync(b->d_bwords + o, w1, (size_t)n1 * 4, hipMemcpyHostToDevice, s));
-        BHIPCHK(c, hipMemcpyAsync(b->d_bvalues + o, v1, (size_t)n1 * 8, hipMemcpyHostToDevice, s));
+        MSLAM_CHK(c, hipMemcpyAsync(b->d_bwords + o, w1, (size_t)n1 * 4, hipMemcpyHostToDevice, s));
+        MSLAM_CHK(c, hipMemcpyAsync(b->d_bvalues + o, v1, (size_t)n1 * 8, hipMemcpyHostToDevice, s));
     }
     if(n2 > 0)
     {
-        BHIPCHK(c, hipMemcpyAsync(tw, w2, (size_t)n2 * 4, hipMemcpyHostToDevice, s));
-        BHIPCHK(c, hipMemcpyAsync(tv, v2, (size_t)n2 * 8, hipMemcpyHostToDevice, s));
+        MSLAM_CHK(c, hipMemcpyAsync(tw, w2, (size_t)n2 * 4, hipMemcpyHostToDevice, s));
+        MSLAM_CHK(c, hipMemcpyAsync(tv, v2, (size_t)n2 * 8, hipMemcpyHostToDevice, s));
     }
     hipLaunchKernelGGL(k_bow_score_pair, dim3(1), dim3(1), 0, s, b->d_bwords + o, b->d_bvalues + o, n1, tw, tv, n2,
                        b->d_best_score + b->B);
-    BHIPCHK(c, hipGetLastError());
-    BHIPCHK(c, hipMemcpyAsync(score, b->d_best_score + b->B, 8, hipMemcpyDeviceToHost, s));
-    BHIPCHK(c, hipStreamSynchronize(s));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipMemcpyAsync(score, b->d_best_score + b->B, 8, hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
     return MSLAM_HIP_OK;
 }
 
@@ -1587,11 +1570,11 @@ int mslam_hip_bow_db_add(mslam_hip_ctx* c, const uint8_t* desc, int n, int* entr
     const size_t o = (size_t)b->B * b->cap;
     hipLaunchKernelGGL(k_bow_commit, dim3(1), dim3(256), 0, c->stream, b->d_bwords + o, b->d_bvalues + o, b->d_bn + b->B,
                        b->cap, b->next_id, b->RP, b->d_rwords, b->d_rvalues, b->d_rn);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     rc = ix_add(c, b->B, 1);
     if(rc)
         return rc;
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     if(entry_id)
         *entry_id = (int)b->next_id;
     b->next_id += 1;
@@ -1606,7 +1589,7 @@ int mslam_hip_bow_db_query(mslam_hip_ctx* c, const uint8_t* desc, int n, int max
         return rc;
     BowState* b = c->bow;
     if(!n_results || max_results < 0 || (max_results > 0 && (!entry_ids || !scores)))
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_db_query: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_db_query: bad argument");
     *n_results = 0;
     rc = host_transform(c, desc, n);
     if(rc)
@@ -1619,8 +1602,8 @@ int mslam_hip_bow_db_query(mslam_hip_ctx* c, const uint8_t* desc, int n, int max
     if(rc)
         return rc;
     std::vector<double> sc((size_t)N);
-    BHIPCHK(c, hipMemcpyAsync(sc.data(), b->ix_scores, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipMemcpyAsync(sc.data(), b->ix_scores, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     std::vector<std::pair<double, long long>> res;
     for(long long id = 0; id < N; ++id)
         if(sc[(size_t)id] >= 0)
@@ -1642,10 +1625,10 @@ int mslam_hip_bow_set_assignment(mslam_hip_ctx* c, int mode)
     if(rc)
         return rc;
     if(mode != MSLAM_BOW_ASSIGN_TREE && mode != MSLAM_BOW_ASSIGN_FLAT)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: unknown mode");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: unknown mode");
     if(mode == MSLAM_BOW_ASSIGN_FLAT && !c->bow->flat_ok)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: this vocabulary's word table does not map one-to-one onto "
-                                             "its leaves (or has more than 2^20 words)");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_set_assignment: this vocabulary's word table does not map one-to-one onto "
+                                            "its leaves (or has more than 2^20 words)");
     c->bow->flat = mode;
     return MSLAM_HIP_OK;
 }
@@ -1657,11 +1640,11 @@ int mslam_hip_bow_db_remove(mslam_hip_ctx* c, int entry_id)
         return rc;
     BowState* b = c->bow;
     if(entry_id < 0 || entry_id >= b->next_id)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_db_remove: no such entry");
-    BHIPCHK(c, hipMemsetAsync(b->ix_removed + entry_id, 1, 1, c->stream)); // its postings are skipped from now on
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_db_remove: no such entry");
+    MSLAM_CHK(c, hipMemsetAsync(b->ix_removed + entry_id, 1, 1, c->stream)); // its postings are skipped from now on
     if(entry_id >= b->next_id - b->R)
         // the batched path's window: an entry without words shares no word with any query
-        BHIPCHK(c, hipMemsetAsync(b->d_rn + (entry_id % b->RP), 0, 4, c->stream));
+        MSLAM_CHK(c, hipMemsetAsync(b->d_rn + (entry_id % b->RP), 0, 4, c->stream));
     return MSLAM_HIP_OK;
 }
 
@@ -1670,12 +1653,12 @@ int mslam_hip_bow_db_clear(mslam_hip_ctx* c)
     int rc = need_voc(c);
     if(rc)
         return rc;
-    BHIPCHK(c, hipStreamSynchronize(c->stream));
-    BHIPCHK(c, hipMemset(c->bow->d_rn, 0, (size_t)c->bow->RP * 4));
-    BHIPCHK(c, hipMemset(c->bow->ix_head, 0, (size_t)c->bow->n_words * 4));
-    BHIPCHK(c, hipMemset(c->bow->ix_size, 0, 4));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipMemset(c->bow->d_rn, 0, (size_t)c->bow->RP * 4));
+    MSLAM_CHK(c, hipMemset(c->bow->ix_head, 0, (size_t)c->bow->n_words * 4));
+    MSLAM_CHK(c, hipMemset(c->bow->ix_size, 0, 4));
     if(c->bow->ix_removed)
-        BHIPCHK(c, hipMemset(c->bow->ix_removed, 0, (size_t)c->bow->ix_max_entries));
+        MSLAM_CHK(c, hipMemset(c->bow->ix_removed, 0, (size_t)c->bow->ix_max_entries));
     c->bow->next_id = 0;
     return MSLAM_HIP_OK;
 }
@@ -1686,7 +1669,7 @@ int mslam_hip_bow_db_reserve(mslam_hip_ctx* c, int max_entries)
     if(rc)
         return rc;
     if(max_entries < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_db_reserve: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_db_reserve: bad argument");
     return ix_reserve(c, max_entries);
 }
 
@@ -1716,13 +1699,13 @@ int mslam_hip_bow_cross_score_dev(mslam_hip_ctx* c, const uint32_t* d_words, con
         return rc;
     const BowState* b = c->bow;
     if(!d_words || !d_values || !d_n || !d_scores || n_sets < 1 || capacity < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_dev: bad argument");
     if(c->n_last < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_dev: no BoW batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_dev: no BoW batch");
     const int total = c->n_last * n_sets;
     hipLaunchKernelGGL(k_bow_cross_score, dim3((total + 63) / 64), dim3(64), 0, c->stream, b->d_bwords, b->d_bvalues,
                        b->d_bn, b->cap, c->n_last, d_words, d_values, d_n, n_sets, capacity, b->B, d_scores);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1733,12 +1716,12 @@ int mslam_hip_bow_pack_dev(mslam_hip_ctx* c, int k_max, uint32_t* d_out)
         return rc;
     const BowState* b = c->bow;
     if(!d_out || k_max < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_pack_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_pack_dev: bad argument");
     if(c->n_last < 1)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_pack_dev: no BoW batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_pack_dev: no BoW batch");
     hipLaunchKernelGGL(k_bow_pack, dim3(c->n_last), dim3(256), 0, c->stream, b->d_bwords, b->d_bvalues, b->d_bn, b->cap,
                        c->n_last, k_max, d_out, c->d_flags);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -1747,17 +1730,17 @@ int mslam_hip_bow_cross_score_packed_dev(mslam_hip_ctx* c, const uint32_t* d_set
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    BHIPCHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     if(!d_sets || !d_scores || n_sets < 1 || self_set < 0 || self_set >= n_sets || n_frames < 1 || k_max < 1 ||
        k_max > 16384)
-        return bfail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_packed_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "bow_cross_score_packed_dev: bad argument");
     const size_t lds = (size_t)k_max * 8;
     if(lds > 48 * 1024)
-        BHIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_cross_packed),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MSLAM_CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bow_cross_packed),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_bow_cross_packed, dim3(n_frames), dim3(256), lds, stream ? (hipStream_t)stream : c->stream, d_sets,
                        n_sets, self_set, n_frames, k_max, d_scores);
-    BHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 

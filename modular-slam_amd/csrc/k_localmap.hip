@@ -205,10 +205,7 @@ __global__ __launch_bounds__(256) void k_lm_scatter(const uint8_t* __restrict__ 
         pre += (uint32_t)__popcll(win[blk * 4 + w]);
     const size_t o = (size_t)ofs[blk] + pre + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull)); // < ofs[nb] <= K
     const size_t src = (size_t)list.slot[k] * K + i; // a winner has i < n <= K
-    const uint4* s = reinterpret_cast<const uint4*>(store_desc + src * 32);
-    uint4* d = reinterpret_cast<uint4*>(out_desc + o * 32);
-    d[0] = s[0];
-    d[1] = s[1];
+    copy_desc(store_desc + src * 32, out_desc + o * 32);
     out_world[o * 3] = store_world[src * 3], out_world[o * 3 + 1] = store_world[src * 3 + 1], out_world[o * 3 + 2] = store_world[src * 3 + 2];
     out_lid[o] = store_lid[src];
 }
@@ -247,50 +244,39 @@ __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict_
 
 using namespace mslam;
 
-#define LCHK(c, call)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
 // the scratch both calls share: a table of `buckets` buckets, per-block arrays for `blocks` blocks, the mapped result
 static int lm_scratch(mslam_hip_ctx* c, size_t buckets, size_t blocks)
 {
     RelocState* r = c->reloc;
     if(buckets > r->lm_buckets)
     {
-        LCHK(c, hipStreamSynchronize(c->stream)); // what reads the old table has finished before it is freed
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // what reads the old table has finished before it is freed
         if(r->d_lm_table)
             (void)hipFree(r->d_lm_table);
         r->d_lm_table = nullptr;
         r->lm_buckets = 0;
-        LCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_table), buckets * sizeof(LmBucket)));
+        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_table), buckets * sizeof(LmBucket)));
         r->lm_buckets = buckets;
     }
     if(blocks > r->lm_blocks)
     {
-        LCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
         if(r->d_lm_blocks)
             (void)hipFree(r->d_lm_blocks);
         r->d_lm_blocks = nullptr;
         r->lm_blocks = 0;
         const size_t nb = std::max(blocks, (size_t)256);
-        LCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_blocks), nb * 32 + nb * 4 + (nb + 1) * 4)); // [win nb x 4 u64 | cnt | ofs]
+        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_blocks), nb * 32 + nb * 4 + (nb + 1) * 4)); // [win nb x 4 u64 | cnt | ofs]
         r->lm_blocks = nb;
     }
     if(!r->h_lm)
     {
-        LCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_lm), sizeof(LmHead) + kRelocMaxCand * 4, hipHostMallocMapped));
+        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_lm), sizeof(LmHead) + kRelocMaxCand * 4, hipHostMallocMapped));
         if(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_lm), r->h_lm, 0) != hipSuccess)
         {
             (void)hipHostFree(r->h_lm);
             r->h_lm = r->d_h_lm = nullptr;
-            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: no device address for the result block");
+            return fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: no device address for the result block");
         }
     }
     return MSLAM_HIP_OK;
@@ -311,7 +297,7 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     if(rc)
         return rc;
     if(!ids || n_ids < 1 || n_ids > kRelocMaxCand)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument (1 to 64 ids)");
+        return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument (1 to 64 ids)");
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints;
     LmList list{};
@@ -321,14 +307,14 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     {
         auto it = r->slot_of.find(ids[k]);
         if(it == r->slot_of.end())
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is not in the keyframe store");
+            return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is not in the keyframe store");
         if(ids[k] == dst_id)
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": dst_id is one of the listed ids");
+            return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": dst_id is one of the listed ids");
         int rank = 0;
         for(int j = 0; j < n_ids; ++j)
         {
             if(j != k && ids[j] == ids[k])
-                return reloc_fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is listed twice");
+                return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is listed twice");
             rank += ids[j] < ids[k] ? 1 : 0;
         }
         list.slot[k] = it->second;
@@ -355,7 +341,7 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     const dim3 grid(bx, (unsigned)n_ids);
     {
         StageScope ts(c, "union_clear");
-        LCHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+        MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
     }
     {
         StageScope ts(c, "union_insert");
@@ -375,7 +361,7 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
         hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, s, r->d_desc, r->d_world, r->d_lid, list, K, win, ofs, (int)nb,
                            r->d_desc + slot * K * 32, r->d_world + slot * K * 3, r->d_lid + slot * K);
     }
-    LCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     r->n_upper[slot] = (int)std::min(keys, (size_t)K); // (the count stays on the device)
     return MSLAM_HIP_OK;
 }
@@ -397,16 +383,16 @@ int mslam_hip_kf_union(mslam_hip_ctx* c, int dst_id, const int32_t* ids, int n_i
     if(rc)
         return rc;
     RelocState* r = c->reloc;
-    LCHK(c, hipStreamSynchronize(c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     const int32_t needed = reinterpret_cast<const LmHead*>(r->h_lm)->needed;
     if(needed < 0)
-        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: the kernels reported an impossible count");
+        return fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: the kernels reported an impossible count");
     if(n_out)
         *n_out = needed;
     if(needed > c->p.max_keypoints)
     {
         r->n_upper[(size_t)slot] = 0;
-        return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "kf_union: " + std::to_string(needed) + " distinct landmarks, more than the context's max_keypoints");
+        return fail(c, MSLAM_HIP_E_CAPACITY, "kf_union: " + std::to_string(needed) + " distinct landmarks, more than the context's max_keypoints");
     }
     r->n_upper[(size_t)slot] = needed;
     return MSLAM_HIP_OK;
@@ -418,18 +404,18 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
     if(rc)
         return rc;
     if(n_ids < 0 || n_ids > kRelocMaxCand || (n_ids > 0 && (!ids || !counts)))
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: bad argument (at most 64 ids)");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: bad argument (at most 64 ids)");
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints;
     auto own = r->slot_of.find(id);
     if(own == r->slot_of.end())
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(id) + " is not in the keyframe store");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(id) + " is not in the keyframe store");
     LmList list{}, self{};
     for(int k = 0; k < n_ids; ++k)
     {
         auto it = r->slot_of.find(ids[k]);
         if(it == r->slot_of.end())
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
+            return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
         list.slot[k] = it->second;
     }
     if(n_ids == 0)
@@ -447,7 +433,7 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
         h_counts[k] = -1; // (overwritten by k_lm_covisible; checked after the synchronisation)
     {
         StageScope ts(c, "covisible_clear");
-        LCHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+        MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
     }
     {
         StageScope ts(c, "covisible_insert");
@@ -459,11 +445,11 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
         hipLaunchKernelGGL(k_lm_covisible, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_lid, r->d_n, list, K, table,
                            (unsigned long long)(buckets - 1), reinterpret_cast<int32_t*>(r->d_h_lm + sizeof(LmHead)));
     }
-    LCHK(c, hipGetLastError());
-    LCHK(c, hipStreamSynchronize(s));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipStreamSynchronize(s));
     for(int k = 0; k < n_ids; ++k)
         if(h_counts[k] < 0 || h_counts[k] > K)
-            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_covisible: the kernel left no result");
+            return fail(c, MSLAM_HIP_E_RUNTIME, "kf_covisible: the kernel left no result");
     std::memcpy(counts, h_counts, (size_t)n_ids * 4);
     return MSLAM_HIP_OK;
 }

@@ -75,18 +75,6 @@ void launch_backproject_batch(hipStream_t s, const uint16_t* d_depth, int width,
 
 using namespace mslam;
 
-#define PHIPCHK(c, call)                                                                                               \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
-
 // ---- packed results of a batch (mslam_hip_pack_batch_dev) ---------------------------------------------------------------
 // The batch views are capacity-strided ([max_batch][max_keypoints]...): copied back as they are, more than half of what
 // crosses PCIe is padding.  k_pack_plan turns the per-frame counts into offsets (one workgroup, a 1024-wide scan) and writes
@@ -223,12 +211,6 @@ __global__ __launch_bounds__(256) void k_pack_copy(const float* __restrict__ xy,
     }
 }
 
-static int pfail(mslam_hip_ctx* c, const char* m)
-{
-    c->err = m;
-    return MSLAM_HIP_E_INVALID;
-}
-
 // a focal length of zero or NaN has no inverse to project with (NaN != 0.0 is true: it needs its own test)
 static bool bad_focal(double f)
 {
@@ -240,8 +222,8 @@ static int ensure_points(mslam_hip_ctx* c)
     if(c->d_xyz)
         return MSLAM_HIP_OK;
     const size_t n = (size_t)c->p.max_batch * c->p.max_keypoints;
-    PHIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_xyz), n * 3 * sizeof(double)));
-    PHIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_valid), n));
+    MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_xyz), n * 3 * sizeof(double)));
+    MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_valid), n));
     return MSLAM_HIP_OK;
 }
 
@@ -253,10 +235,10 @@ int mslam_hip_backproject_batch_dev(mslam_hip_ctx* c, const uint16_t* d_depth, f
     if(!c)
         return MSLAM_HIP_E_INVALID;
     if(!d_depth || bad_focal(fx) || bad_focal(fy))
-        return pfail(c, "backproject_batch_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "backproject_batch_dev: bad argument");
     if(c->n_last < 1)
-        return pfail(c, "backproject_batch_dev: no detect batch");
-    PHIPCHK(c, hipSetDevice(c->p.device));
+        return fail(c, MSLAM_HIP_E_INVALID, "backproject_batch_dev: no detect batch");
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     int rc = ensure_points(c);
     if(rc)
         return rc;
@@ -267,7 +249,7 @@ int mslam_hip_backproject_batch_dev(mslam_hip_ctx* c, const uint16_t* d_depth, f
     hipLaunchKernelGGL(k_backproject, grid, dim3(256), 0, c->stream, d_depth, (long long)c->p.width * c->p.height,
                        c->p.width, c->p.height, cam, c->d_xy + K * 2, (long long)K * 2, c->d_count + 1, 0,
                        c->p.max_keypoints, c->d_xyz, c->d_valid);
-    PHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     c->points_seq = c->detect_seq;
     return MSLAM_HIP_OK;
 }
@@ -277,12 +259,12 @@ int mslam_hip_pack_batch_dev(mslam_hip_ctx* c, void* out, size_t capacity_bytes,
     if(!c)
         return MSLAM_HIP_E_INVALID;
     if(!out || capacity_bytes < sizeof(mslam_hip_packed_header))
-        return pfail(c, "pack_batch_dev: no output buffer (at least the header must fit)");
+        return fail(c, MSLAM_HIP_E_INVALID, "pack_batch_dev: no output buffer (at least the header must fit)");
     if(c->n_last < 1)
-        return pfail(c, "pack_batch_dev: no detect batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "pack_batch_dev: no detect batch");
     if(with_points && (!c->d_xyz || c->points_seq != c->detect_seq))
-        return pfail(c, "pack_batch_dev: with_points, but the last detect batch has not been back-projected");
-    PHIPCHK(c, hipSetDevice(c->p.device));
+        return fail(c, MSLAM_HIP_E_INVALID, "pack_batch_dev: with_points, but the last detect batch has not been back-projected");
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     int rc = mslam_hip_join_matcher(c); // the matches come from the matcher's own stream
     if(rc)
         return rc;
@@ -295,7 +277,7 @@ int mslam_hip_pack_batch_dev(mslam_hip_ctx* c, void* out, size_t capacity_bytes,
     hipLaunchKernelGGL(k_pack_copy, dim3(c->n_last, 4), dim3(256), 0, c->stream, c->d_xy + K * 2, c->d_desc + K * 32, c->d_octave + K,
                        c->d_angle + K, c->d_response + K, c->d_xyz, c->d_valid, c->d_mfrom, c->d_mto, c->p.max_keypoints,
                        static_cast<uint8_t*>(out));
-    PHIPCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
 }
 
@@ -326,10 +308,10 @@ int mslam_hip_backproject(mslam_hip_ctx* c, const uint16_t* depth, int width, in
     if(!c)
         return MSLAM_HIP_E_INVALID;
     if(!depth || width <= 0 || height <= 0 || n < 0 || (n > 0 && (!xy || !xyz || !valid)) || bad_focal(fx) || bad_focal(fy))
-        return pfail(c, "backproject: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "backproject: bad argument");
     if(n == 0)
         return MSLAM_HIP_OK;
-    PHIPCHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     uint16_t* d_depth = nullptr;
     float* d_xy = nullptr;
     double* d_xyz = nullptr;

@@ -9,6 +9,8 @@
 // from_stride = 0: the query descriptors are uploaded once and are every pair's train side; k_pnp.hip through
 // pnp_launch_batch).  New here: the store, the gather of the candidates' descriptor blocks into the contiguous layout the
 // matcher addresses, the match -> correspondence gather, and the ranking.  One upload, one synchronisation per call.
+// Gather to PnP are seq_enqueue, which a tracking window (k_track_window.hip) enqueues as well, with its frames as the rows
+// and one entry for all of them; the scratch blocks of every such call are grown by reloc_scratch.
 #include "reloc.hpp"
 
 #include <algorithm>
@@ -23,7 +25,7 @@ void reloc_destroy(RelocState* r)
 {
     if(!r)
         return;
-    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_lid, r->d_up, r->d_arena, r->d_vote, r->d_lm_table, r->d_lm_blocks};
+    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_lid, r->d_up, r->d_arena, r->d_lm_table, r->d_lm_blocks};
     for(void* p : dev)
         if(p)
             (void)hipFree(p);
@@ -31,8 +33,6 @@ void reloc_destroy(RelocState* r)
         (void)hipHostFree(r->h_up);
     if(r->h_res)
         (void)hipHostFree(r->h_res);
-    if(r->h_vote)
-        (void)hipHostFree(r->h_vote);
     if(r->h_lm)
         (void)hipHostFree(r->h_lm);
     delete r;
@@ -75,10 +75,7 @@ __global__ __launch_bounds__(256) void k_kf_lift(const uint8_t* __restrict__ des
         if(ok)
         {
             const size_t o = running + pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); // < n <= cap
-            const uint4* src = reinterpret_cast<const uint4*>(desc + (size_t)i * 32);
-            uint4* dst = reinterpret_cast<uint4*>(out_desc + o * 32);
-            dst[0] = src[0];
-            dst[1] = src[1];
+            copy_desc(desc + (size_t)i * 32, out_desc + o * 32);
             out_world[o * 3] = ((pose.R[0] * px + pose.R[1] * py) + pose.R[2] * pz) + pose.t[0];
             out_world[o * 3 + 1] = ((pose.R[3] * px + pose.R[4] * py) + pose.R[5] * pz) + pose.t[1];
             out_world[o * 3 + 2] = ((pose.R[6] * px + pose.R[7] * py) + pose.R[8] * pz) + pose.t[2];
@@ -91,36 +88,45 @@ __global__ __launch_bounds__(256) void k_kf_lift(const uint8_t* __restrict__ des
         *out_n = (int32_t)running;
 }
 
-// The matcher addresses pair p's query side as base + p * stride: candidate p's descriptor block (store slot slots[p]) is
-// copied into row p of a contiguous scratch; blockIdx.y = p, one uint4 (half a descriptor) per thread.
+// The matcher addresses row r's query side as base + r * stride: the descriptor block of store slot slots[p] is copied into
+// row p of a contiguous scratch; blockIdx.y = p, one uint4 (half a descriptor) per thread.  Gathered row p is the entry
+// of `share` rows of the sequence (1: its own; all of them when there is one entry, share <= 256: block 0), which each
+// get its landmark count.
 __global__ __launch_bounds__(256) void k_reloc_gather_desc(const uint8_t* __restrict__ store_desc, const int32_t* __restrict__ store_n,
-                                                           const int32_t* __restrict__ slots, int K, int S,
+                                                           const int32_t* __restrict__ slots, int K, int S, int share,
                                                            uint8_t* __restrict__ g_desc, int32_t* __restrict__ g_cnt)
 {
     const int p = blockIdx.y;
     const int slot = slots[p];
     const int n = min(min(max(store_n[slot], 0), K), S);
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if(i == 0)
-        g_cnt[p] = n;
+    if(i < share)
+        g_cnt[(size_t)p * share + i] = n;
     if(i < 2 * n)
         reinterpret_cast<uint4*>(g_desc + (size_t)p * S * 32)[i] = reinterpret_cast<const uint4*>(store_desc + (size_t)slot * K * 32)[i];
 }
 
-// candidate p (one workgroup): its matches whose query keypoint is not masked out become correspondences, in match order:
-// object = (float) world point of landmark `to`, image = xy of keypoint `from`
+// row p (one workgroup): its matches whose keypoint is not masked out become correspondences, in match order:
+// object = (float) world point of landmark `to` of the row's entry, image = xy of keypoint `from`.  Rows are from_stride
+// keypoints and slot_stride list positions apart (0: shared); n_kp == nullptr: every row has nq keypoints.
 __global__ __launch_bounds__(256) void k_reloc_corr(const int32_t* __restrict__ mfrom, const int32_t* __restrict__ mto,
                                                     const int32_t* __restrict__ mcount, const int32_t* __restrict__ g_cnt,
-                                                    const int32_t* __restrict__ slots, const double* __restrict__ store_world, int K,
-                                                    int S, const float* __restrict__ xy, const uint8_t* __restrict__ valid, int nq,
+                                                    const int32_t* __restrict__ slots, int slot_stride,
+                                                    const double* __restrict__ store_world, int K, int S,
+                                                    const float* __restrict__ xy_all, const uint8_t* __restrict__ valid_all,
+                                                    long long from_stride, const int32_t* __restrict__ n_kp, int nq,
                                                     float* __restrict__ obj, float* __restrict__ img, uint8_t* __restrict__ mask,
                                                     int32_t* __restrict__ n_out)
 {
     __shared__ uint32_t wsum[4];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m = min(max(mcount[p], 0), S), n_to = g_cnt[p];
+    if(n_kp)
+        nq = (int)min((long long)max(n_kp[p], 0), from_stride);
+    const float* xy = xy_all + (size_t)p * from_stride * 2;
+    const uint8_t* valid = valid_all ? valid_all + (size_t)p * from_stride : nullptr;
     const size_t row = (size_t)p * S;
-    const double* world = store_world + (size_t)slots[p] * K * 3;
+    const double* world = store_world + (size_t)slots[(size_t)p * slot_stride] * K * 3;
     uint32_t running = 0;
     for(int base = 0; base < m; base += 256)
     {
@@ -176,15 +182,7 @@ __global__ __launch_bounds__(256) void k_reloc_rank(const int32_t* __restrict__ 
         RelocRes r{};
         if(live)
         {
-            const double* o = pnp_out + (size_t)tid * 16;
-            r.n_matches = mcount[tid];
-            r.n_corr = ncorr[tid];
-            r.status = o[14] == 1.0 ? 1 : 0;
-            r.n_inliers = r.status ? (int32_t)o[12] : 0;
-            for(int j = 0; j < 9; ++j)
-                r.R[j] = r.status ? o[j] : 0.0;
-            for(int j = 0; j < 3; ++j)
-                r.t[j] = r.status ? o[9 + j] : 0.0;
+            r = reloc_record(pnp_out + (size_t)tid * 16, mcount[tid], ncorr[tid]);
             reinterpret_cast<RelocRes*>(res + 16)[tid] = r;
         }
         // most inliers among the candidates with a model, the first one on ties (max_element): key = (inliers + 1, 63 - k)
@@ -221,33 +219,11 @@ using namespace mslam;
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-#define RCHK(c, call)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
-static int rfail(mslam_hip_ctx* c, int code, const std::string& msg)
-{
-    c->err = msg;
-    return code;
-}
-
-int mslam::reloc_fail(mslam_hip_ctx* c, int code, const std::string& msg)
-{
-    return rfail(c, code, msg);
-}
-
 int mslam::reloc_enter(mslam_hip_ctx* c)
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    RCHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
     if(!c->reloc)
         c->reloc = new RelocState();
     return MSLAM_HIP_OK;
@@ -292,7 +268,7 @@ int mslam::store_reserve(mslam_hip_ctx* c, int want)
         for(void* p : fresh)
             if(p)
                 (void)hipFree(p);
-        return rfail(c, MSLAM_HIP_E_RUNTIME, std::string("kf store: ") + hipGetErrorString(e));
+        return fail(c, MSLAM_HIP_E_RUNTIME, std::string("kf store: ") + hipGetErrorString(e));
     }
     void* old[] = {r->d_desc, r->d_world, r->d_n, r->d_lid};
     for(void* p : old)
@@ -333,6 +309,64 @@ int64_t mslam::store_next_lid_base(mslam_hip_ctx* c)
     return fresh_lid_base(++c->reloc->serial);
 }
 
+int TrackSlots::resolve(mslam_hip_ctx* c, const char* who, int ref_id, const int32_t* vote_ids, int n_vote, int new_id_)
+{
+    RelocState* r = c->reloc;
+    const std::string me = who;
+    new_id = new_id_;
+    auto ref = r->slot_of.find(ref_id);
+    if(ref == r->slot_of.end())
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": reference id " + std::to_string(ref_id) + " is not in the keyframe store");
+    ref_slot = ref->second;
+    bool collides = new_id >= 0 && new_id == ref_id;
+    for(int k = 0; k < n_vote; ++k)
+    {
+        auto it = r->slot_of.find(vote_ids[k]);
+        if(it == r->slot_of.end())
+            return fail(c, MSLAM_HIP_E_INVALID, me + ": vote id " + std::to_string(vote_ids[k]) + " is not in the keyframe store");
+        vote_slots[k] = it->second;
+        collides = collides || (new_id >= 0 && vote_ids[k] == new_id);
+    }
+    if(collides)
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": new_id names the reference keyframe or a keyframe of the vote list");
+    return MSLAM_HIP_OK;
+}
+
+int TrackSlots::reserve(mslam_hip_ctx* c)
+{
+    if(new_id < 0)
+        return MSLAM_HIP_OK;
+    existed = c->reloc->slot_of.count(new_id) != 0;
+    const int rc = store_slot_for(c, new_id, &new_slot);
+    if(rc)
+        return rc;
+    lid_base = store_next_lid_base(c);
+    return MSLAM_HIP_OK;
+}
+
+void TrackSlots::commit(mslam_hip_ctx* c, int n_entry)
+{
+    c->reloc->n_upper[(size_t)new_slot] = n_entry;
+}
+
+void TrackSlots::rollback(mslam_hip_ctx* c, bool enqueued_work_may_still_run)
+{
+    RelocState* r = c->reloc;
+    if(enqueued_work_may_still_run)
+    {
+        const std::string msg = c->err;
+        (void)hipStreamSynchronize(c->stream);
+        c->err = msg;
+        if(existed)
+            r->n_upper[(size_t)new_slot] = c->p.max_keypoints;
+    }
+    if(new_id >= 0 && !existed)
+    {
+        r->slot_of.erase(new_id);
+        r->free_slots.push_back(new_slot);
+    }
+}
+
 // mslam_hip_kf_add (landmark_ids == nullptr: fresh ids) and mslam_hip_kf_add_ids
 static int kf_add_host(mslam_hip_ctx* c, const char* who, int id, const uint8_t* desc, const double* world_xyz,
                        const int64_t* landmark_ids, bool own_ids, int n)
@@ -341,12 +375,12 @@ static int kf_add_host(mslam_hip_ctx* c, const char* who, int id, const uint8_t*
     if(rc)
         return rc;
     if(n < 0 || (n > 0 && (!desc || !world_xyz || (own_ids && !landmark_ids))))
-        return rfail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument");
     if(n > c->p.max_keypoints)
-        return rfail(c, MSLAM_HIP_E_CAPACITY, std::string(who) + ": more landmarks than the context's max_keypoints");
+        return fail(c, MSLAM_HIP_E_CAPACITY, std::string(who) + ": more landmarks than the context's max_keypoints");
     for(int i = 0; own_ids && i < n; ++i)
         if(landmark_ids[i] < 0 || landmark_ids[i] >= kFreshLidBit)
-            return rfail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": landmark ids lie in [0, 2^62)");
+            return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": landmark ids lie in [0, 2^62)");
     int slot = -1;
     rc = store_slot_for(c, id, &slot);
     if(rc)
@@ -365,13 +399,38 @@ static int kf_add_host(mslam_hip_ctx* c, const char* who, int id, const uint8_t*
     }
     if(n > 0)
     {
-        RCHK(c, hipMemcpyAsync(r->d_desc + (size_t)slot * K * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-        RCHK(c, hipMemcpyAsync(r->d_world + (size_t)slot * K * 3, world_xyz, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-        RCHK(c, hipMemcpyAsync(r->d_lid + (size_t)slot * K, landmark_ids, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(r->d_desc + (size_t)slot * K * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(r->d_world + (size_t)slot * K * 3, world_xyz, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(r->d_lid + (size_t)slot * K, landmark_ids, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     }
-    RCHK(c, hipMemcpyAsync(r->d_n + slot, &n32, 4, hipMemcpyHostToDevice, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream)); // host-pointer entry point: the caller's buffers are free on return
+    MSLAM_CHK(c, hipMemcpyAsync(r->d_n + slot, &n32, 4, hipMemcpyHostToDevice, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // host-pointer entry point: the caller's buffers are free on return
     r->n_upper[(size_t)slot] = n;
+    return MSLAM_HIP_OK;
+}
+
+// what mslam_hip_kf_read and mslam_hip_kf_read_ids start with: the slot of entry `id` and its landmark count, read from the
+// device
+static int kf_entry_count(mslam_hip_ctx* c, const char* who, int id, int capacity, int* n, size_t* slot)
+{
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    const std::string me = who;
+    if(!n || capacity < 0)
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
+    RelocState* r = c->reloc;
+    auto it = r->slot_of.find(id);
+    if(it == r->slot_of.end())
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": no such keyframe id");
+    *slot = (size_t)it->second;
+    int32_t n32 = 0;
+    MSLAM_CHK(c, hipMemcpyAsync(&n32, r->d_n + *slot, 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+    if(n32 < 0 || n32 > c->p.max_keypoints)
+        return fail(c, MSLAM_HIP_E_RUNTIME, me + ": impossible landmark count");
+    *n = n32;
+    r->n_upper[*slot] = n32; // now known exactly
     return MSLAM_HIP_OK;
 }
 
@@ -383,7 +442,7 @@ int mslam_hip_kf_reserve(mslam_hip_ctx* c, int max_entries)
     if(rc)
         return rc;
     if(max_entries < 0)
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_reserve: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_reserve: bad argument");
     return store_reserve(c, max_entries);
 }
 
@@ -411,11 +470,11 @@ int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const d
     if(rc)
         return rc;
     if(!R || !t || !(z_max == z_max))
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: bad argument");
     if(frame < 0 || frame >= c->n_last)
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: no such frame in the last detect batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: no such frame in the last detect batch");
     if(!c->d_xyz || c->points_seq != c->detect_seq)
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: the last detect batch has not been back-projected");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_add_from_batch_dev: the last detect batch has not been back-projected");
     int slot = -1;
     rc = store_slot_for(c, id, &slot);
     if(rc)
@@ -435,7 +494,7 @@ int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const d
                            c->p.max_keypoints, pose, r->d_desc + (size_t)slot * K * 32, r->d_world + (size_t)slot * K * 3,
                            r->d_n + slot, r->d_lid + (size_t)slot * K, lid_base);
     }
-    RCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     r->n_upper[(size_t)slot] = c->p.max_keypoints; // (the count stays on the device)
     return MSLAM_HIP_OK;
 }
@@ -448,7 +507,7 @@ int mslam_hip_kf_remove(mslam_hip_ctx* c, int id)
     RelocState* r = c->reloc;
     auto it = r->slot_of.find(id);
     if(it == r->slot_of.end())
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_remove: no such keyframe id");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_remove: no such keyframe id");
     // (work already enqueued on the slot runs before anything a later add enqueues: one stream)
     r->free_slots.push_back(it->second);
     r->slot_of.erase(it);
@@ -470,65 +529,198 @@ int mslam_hip_kf_clear(mslam_hip_ctx* c)
 
 int mslam_hip_kf_read(mslam_hip_ctx* c, int id, uint8_t* desc, double* world_xyz, int capacity, int* n)
 {
-    int rc = reloc_enter(c);
-    if(rc)
+    size_t slot = 0;
+    const int rc = kf_entry_count(c, "kf_read", id, capacity, n, &slot);
+    if(rc || (!desc && !world_xyz))
         return rc;
-    if(!n || capacity < 0)
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read: bad argument");
     RelocState* r = c->reloc;
-    auto it = r->slot_of.find(id);
-    if(it == r->slot_of.end())
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read: no such keyframe id");
-    const size_t K = (size_t)c->p.max_keypoints, slot = (size_t)it->second;
-    int32_t n32 = 0;
-    RCHK(c, hipMemcpyAsync(&n32, r->d_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream));
-    if(n32 < 0 || (size_t)n32 > K)
-        return rfail(c, MSLAM_HIP_E_RUNTIME, "kf_read: impossible landmark count");
-    *n = n32;
-    r->n_upper[slot] = n32; // now known exactly
-    if(!desc && !world_xyz)
-        return MSLAM_HIP_OK;
-    if(n32 > capacity)
-        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_read: the entry has more landmarks than `capacity`");
+    const size_t K = (size_t)c->p.max_keypoints, n32 = (size_t)*n;
+    if(*n > capacity)
+        return fail(c, MSLAM_HIP_E_CAPACITY, "kf_read: the entry has more landmarks than `capacity`");
     if(desc && n32 > 0)
-        RCHK(c, hipMemcpyAsync(desc, r->d_desc + slot * K * 32, (size_t)n32 * 32, hipMemcpyDeviceToHost, c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(desc, r->d_desc + slot * K * 32, n32 * 32, hipMemcpyDeviceToHost, c->stream));
     if(world_xyz && n32 > 0)
-        RCHK(c, hipMemcpyAsync(world_xyz, r->d_world + slot * K * 3, (size_t)n32 * 24, hipMemcpyDeviceToHost, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(world_xyz, r->d_world + slot * K * 3, n32 * 24, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     return MSLAM_HIP_OK;
 }
 
 int mslam_hip_kf_read_ids(mslam_hip_ctx* c, int id, int64_t* landmark_ids, int capacity, int* n)
 {
-    int rc = reloc_enter(c);
-    if(rc)
+    size_t slot = 0;
+    const int rc = kf_entry_count(c, "kf_read_ids", id, capacity, n, &slot);
+    if(rc || !landmark_ids)
         return rc;
-    if(!n || capacity < 0)
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read_ids: bad argument");
     RelocState* r = c->reloc;
-    auto it = r->slot_of.find(id);
-    if(it == r->slot_of.end())
-        return rfail(c, MSLAM_HIP_E_INVALID, "kf_read_ids: no such keyframe id");
-    const size_t K = (size_t)c->p.max_keypoints, slot = (size_t)it->second;
-    int32_t n32 = 0;
-    RCHK(c, hipMemcpyAsync(&n32, r->d_n + slot, 4, hipMemcpyDeviceToHost, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream));
-    if(n32 < 0 || (size_t)n32 > K)
-        return rfail(c, MSLAM_HIP_E_RUNTIME, "kf_read_ids: impossible landmark count");
-    *n = n32;
-    r->n_upper[slot] = n32; // now known exactly
-    if(!landmark_ids)
-        return MSLAM_HIP_OK;
-    if(n32 > capacity)
-        return rfail(c, MSLAM_HIP_E_CAPACITY, "kf_read_ids: the entry has more landmarks than `capacity`");
+    const size_t K = (size_t)c->p.max_keypoints, n32 = (size_t)*n;
+    if(*n > capacity)
+        return fail(c, MSLAM_HIP_E_CAPACITY, "kf_read_ids: the entry has more landmarks than `capacity`");
     if(n32 > 0)
-        RCHK(c, hipMemcpyAsync(landmark_ids, r->d_lid + slot * K, (size_t)n32 * 8, hipMemcpyDeviceToHost, c->stream));
-    RCHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipMemcpyAsync(landmark_ids, r->d_lid + slot * K, n32 * 8, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
     return MSLAM_HIP_OK;
 }
 
 } // extern "C"
+
+int mslam::reloc_scratch(mslam_hip_ctx* c, size_t up, size_t arena, size_t res)
+{
+    RelocState* r = c->reloc;
+    if(up > r->up_bytes)
+    {
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // what reads the old block has finished before it is freed
+        if(r->h_up)
+            (void)hipHostFree(r->h_up);
+        if(r->d_up)
+            (void)hipFree(r->d_up);
+        r->h_up = r->d_up = nullptr;
+        r->up_bytes = 0;
+        // (never less than a 4096-keypoint relocalize query takes, whichever call grows the block first: small callers such as
+        // mslam_hip_kf_visible share the 168 KB instead of holding blocks of their own)
+        const size_t bytes = std::max(up, (size_t)4096 * 41 + kRelocMaxCand * 4);
+        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_up), bytes, hipHostMallocDefault));
+        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_up), bytes));
+        r->up_bytes = bytes;
+    }
+    if(arena > r->arena_bytes)
+    {
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+        if(r->d_arena)
+            (void)hipFree(r->d_arena);
+        r->d_arena = nullptr;
+        r->arena_bytes = 0;
+        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_arena), arena));
+        r->arena_bytes = arena;
+    }
+    if(res > r->res_bytes)
+    {
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+        if(r->h_res)
+            (void)hipHostFree(r->h_res);
+        r->h_res = r->d_h_res = nullptr;
+        r->res_bytes = 0;
+        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_res), res, hipHostMallocMapped));
+        MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_res), r->h_res, 0));
+        r->res_bytes = res;
+    }
+    return MSLAM_HIP_OK;
+}
+
+// ---- the match-to-PnP sequence -----------------------------------------------------------------------------------------
+
+namespace
+{
+// where the sequence's arrays lie in the arena, each 256-byte aligned
+struct SeqArena
+{
+    size_t gdesc, gcnt, idx0, idx1, dist0, dist1, mfrom, mto, mcount, obj, img, ncorr, mask, hyp, counts, out, bytes;
+};
+
+SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot)
+{
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off += al256(bytes);
+        return o;
+    };
+    const size_t R = (size_t)rows, RS = R * S, it = (size_t)iterations;
+    SeqArena a{};
+    a.gdesc = carve((one_slot ? S : RS) * 32), a.gcnt = carve(R * 4);
+    a.idx0 = carve(RS * 4), a.idx1 = carve(RS * 4), a.dist0 = carve(RS * 4), a.dist1 = carve(RS * 4);
+    a.mfrom = carve(RS * 4), a.mto = carve(RS * 4), a.mcount = carve(R * 4);
+    a.obj = carve(RS * 12), a.img = carve(RS * 8), a.ncorr = carve(R * 4), a.mask = carve(RS);
+    a.hyp = carve(R * it * 96), a.counts = carve(R * it * 4), a.out = carve(R * 128);
+    a.bytes = off;
+    return a;
+}
+} // namespace
+
+size_t mslam::seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot)
+{
+    return seq_carve(rows, S, iterations, one_slot).bytes;
+}
+
+int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* out)
+{
+    RelocState* r = c->reloc;
+    const int K = c->p.max_keypoints, R = a.rows, S = (int)a.S;
+    const SeqArena o = seq_carve(R, a.S, a.iterations, a.one_slot);
+    hipStream_t s = c->stream;
+    int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o.gcnt);
+    {
+        StageScope ts(c, "reloc_gather_desc");
+        hipLaunchKernelGGL(k_reloc_gather_desc, dim3((unsigned)((2 * a.S + 255) / 256), a.one_slot ? 1u : (unsigned)R), dim3(256), 0, s,
+                           r->d_desc, r->d_n, a.slots, K, S, a.one_slot ? R : 1, A + o.gdesc, g_cnt);
+    }
+    // match(from = keypoints of row r, to = landmarks of its entry): knn-2 with query = `to` and train = `from`
+    MatchArgs m{};
+    m.from_desc = a.desc;
+    m.from_stride = (long long)a.from_stride * 32;
+    m.from_cnt = a.from_cnt;
+    m.n_from_fixed = a.n_from_fixed;
+    m.to_desc = A + o.gdesc;
+    m.to_stride = a.one_slot ? 0 : (long long)S * 32;
+    m.to_cnt = g_cnt;
+    m.cap = S;
+    m.cap_from = a.cap_from;
+    m.popcount_only = c->matcher_kind == MSLAM_HIP_MATCHER_POPCOUNT;
+    m.idx0 = reinterpret_cast<int32_t*>(A + o.idx0);
+    m.idx1 = reinterpret_cast<int32_t*>(A + o.idx1);
+    m.dist0 = reinterpret_cast<int32_t*>(A + o.dist0);
+    m.dist1 = reinterpret_cast<int32_t*>(A + o.dist1);
+    {
+        StageScope ts(c, "match_knn2");
+        c->last_match_kernel = launch_match_knn2(m, R, s);
+    }
+    RatioArgs q{};
+    q.idx0 = m.idx0, q.dist0 = m.dist0, q.dist1 = m.dist1;
+    q.from_cnt = a.from_cnt, q.n_from_fixed = a.n_from_fixed;
+    q.to_cnt = g_cnt;
+    q.cap = S;
+    q.thr = c->d_ratio_thr;
+    q.from_idx = reinterpret_cast<int32_t*>(A + o.mfrom);
+    q.to_idx = reinterpret_cast<int32_t*>(A + o.mto);
+    q.n_out = reinterpret_cast<int32_t*>(A + o.mcount);
+    {
+        StageScope ts(c, "ratio_compact");
+        launch_ratio_compact(q, R, s);
+    }
+    float* d_obj = reinterpret_cast<float*>(A + o.obj);
+    float* d_img = reinterpret_cast<float*>(A + o.img);
+    int32_t* d_ncorr = reinterpret_cast<int32_t*>(A + o.ncorr);
+    uint8_t* d_mask = A + o.mask;
+    {
+        StageScope ts(c, "reloc_corr");
+        hipLaunchKernelGGL(k_reloc_corr, dim3((unsigned)R), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, a.slots,
+                           a.one_slot ? 0 : 1, r->d_world, K, S, a.xy, a.valid, (long long)a.from_stride, a.from_cnt, a.n_from_fixed,
+                           d_obj, d_img, d_mask, d_ncorr);
+    }
+    MSLAM_CHK(c, hipGetLastError());
+    PnpBatchLaunch l{};
+    l.obj = d_obj, l.img = d_img, l.n = d_ncorr;
+    l.n_problems = R, l.cap = S;
+    l.fx = a.fx, l.fy = a.fy, l.cx = a.cx, l.cy = a.cy;
+    l.use_guess = a.use_guess ? 1 : 0;
+    for(int j = 0; j < 3; ++j)
+    {
+        l.rvec[j] = a.use_guess ? a.rvec[j] : 0.0;
+        l.tvec[j] = a.use_guess ? a.tvec[j] : 0.0;
+    }
+    l.iterations = a.iterations;
+    l.reprojection_error = a.reprojection_error;
+    l.seed = a.seed; // problem r samples with seed + r
+    l.hyp = reinterpret_cast<double*>(A + o.hyp);
+    l.counts = reinterpret_cast<int32_t*>(A + o.counts);
+    l.mask = d_mask;
+    l.out = reinterpret_cast<double*>(A + o.out);
+    const int rc = pnp_launch_batch(c, l);
+    if(rc)
+        return rc;
+    out->g_cnt = g_cnt, out->mfrom = q.from_idx, out->mto = q.to_idx, out->mcount = q.n_out, out->ncorr = d_ncorr;
+    out->mask = d_mask, out->pnp_out = l.out, out->S = S;
+    return MSLAM_HIP_OK;
+}
 
 int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint8_t* valid, int n, const int32_t* cand_ids,
                      int n_cand, double fx, double fy, double cx, double cy, double ratio, int iterations, double reprojection_error,
@@ -545,87 +737,44 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     if(!best || n < 0 || n_cand < 0 || n_cand > kRelocMaxCand || (n > 0 && (!desc || !xy)) || (n_cand > 0 && (!cand_ids || !out)) ||
        iterations < 1 || iterations > 4096 || !(reprojection_error > 0) || !(fx != 0.0) || !(fy != 0.0) ||
        (use_extrinsic_guess && (!rvec || !tvec)) || (want_pairs && pair_stride < 0))
-        return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: bad argument (at most 64 candidates, 1..4096 iterations)");
+        return fail(c, MSLAM_HIP_E_INVALID, "relocalize: bad argument (at most 64 candidates, 1..4096 iterations)");
     if(n > 65535)
-        return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: more than 65535 query keypoints are not supported");
+        return fail(c, MSLAM_HIP_E_INVALID, "relocalize: more than 65535 query keypoints are not supported");
     RelocState* r = c->reloc;
-    const int K = c->p.max_keypoints;
     int32_t slots[kRelocMaxCand];
     int n_max = 0;
     for(int k = 0; k < n_cand; ++k)
     {
         auto it = r->slot_of.find(cand_ids[k]);
         if(it == r->slot_of.end())
-            return rfail(c, MSLAM_HIP_E_INVALID, "relocalize: candidate id " + std::to_string(cand_ids[k]) + " is not in the keyframe store");
+            return fail(c, MSLAM_HIP_E_INVALID, "relocalize: candidate id " + std::to_string(cand_ids[k]) + " is not in the keyframe store");
         slots[k] = it->second;
         n_max = std::max(n_max, r->n_upper[(size_t)it->second]);
     }
     for(int k = 0; k < n_cand; ++k)
         out[k] = mslam_hip_reloc_candidate{};
     if(n_cand == 0 || n < 2)
-        return rfail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate, or fewer than 2 query keypoints (no matches)");
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate, or fewer than 2 query keypoints (no matches)");
     rc = mslam_ratio_table(c, ratio);
     if(rc)
         return rc;
 
     // per-candidate row stride of every scratch array: the largest candidate, in whole 256-row blocks
-    const size_t S = ((size_t)std::max(n_max, 1) + 255) & ~(size_t)255, P = (size_t)n_cand, PS = P * S;
+    const size_t S = seq_row_stride(n_max), P = (size_t)n_cand, PS = P * S;
     // ---- upload block: [desc n x 32 | xy n x 8 | slots 64 x 4 | valid n], one copy
     const size_t off_xy = (size_t)n * 32, off_slots = off_xy + (size_t)n * 8, off_valid = off_slots + kRelocMaxCand * 4;
-    const size_t off_extra = (off_valid + (valid ? (size_t)n : 0) + 255) & ~(size_t)255; // a hook's own upload, 256-byte aligned
+    const size_t off_extra = al256(off_valid + (valid ? (size_t)n : 0)); // a hook's own upload, 256-byte aligned
     const size_t extra_bytes = hooks ? hooks->extra_up_bytes[0] + hooks->extra_up_bytes[1] : 0;
     const size_t up = extra_bytes ? off_extra + extra_bytes : off_valid + (valid ? (size_t)n : 0);
-    if(up > r->up_bytes)
-    {
-        RCHK(c, hipStreamSynchronize(c->stream));
-        if(r->h_up)
-            (void)hipHostFree(r->h_up);
-        if(r->d_up)
-            (void)hipFree(r->d_up);
-        r->h_up = r->d_up = nullptr;
-        r->up_bytes = 0;
-        const size_t bytes = std::max(up, (size_t)4096 * 41 + kRelocMaxCand * 4);
-        RCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_up), bytes, hipHostMallocDefault));
-        RCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_up), bytes));
-        r->up_bytes = bytes;
-    }
-    // ---- device arena: every per-candidate array of this call, 256-byte aligned
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_gdesc = carve(PS * 32), o_gcnt = carve(P * 4), o_idx0 = carve(PS * 4), o_idx1 = carve(PS * 4),
-                 o_dist0 = carve(PS * 4), o_dist1 = carve(PS * 4), o_mfrom = carve(PS * 4), o_mto = carve(PS * 4),
-                 o_mcount = carve(P * 4), o_obj = carve(PS * 12), o_img = carve(PS * 8), o_ncorr = carve(P * 4),
-                 o_mask = carve(PS), o_hyp = carve(P * (size_t)iterations * 96), o_counts = carve(P * (size_t)iterations * 4),
-                 o_out = carve(P * 128), o_extra = carve(hooks ? hooks->extra_arena_bytes : 0);
-    if(off > r->arena_bytes)
-    {
-        RCHK(c, hipStreamSynchronize(c->stream));
-        if(r->d_arena)
-            (void)hipFree(r->d_arena);
-        r->d_arena = nullptr;
-        r->arena_bytes = 0;
-        RCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_arena), off));
-        r->arena_bytes = off;
-    }
+    // ---- device arena: the sequence's arrays, then a hook's own
+    const size_t o_extra = seq_arena_bytes(n_cand, S, iterations, false);
     // ---- result block (mapped): [best, pad | RelocRes[64] | pair_from P x S | pair_to P x S | inliers P x S]
     const size_t res_head = 16 + kRelocMaxCand * sizeof(RelocRes);
     const size_t res_extra = (res_head + (want_pairs ? PS * 9 : 0) + 15) & ~(size_t)15; // a hook's own results
     const size_t res = hooks && hooks->extra_res_bytes ? res_extra + hooks->extra_res_bytes : res_head + (want_pairs ? PS * 9 : 0);
-    if(res > r->res_bytes)
-    {
-        RCHK(c, hipStreamSynchronize(c->stream));
-        if(r->h_res)
-            (void)hipHostFree(r->h_res);
-        r->h_res = r->d_h_res = nullptr;
-        r->res_bytes = 0;
-        RCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_res), res, hipHostMallocMapped));
-        RCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_res), r->h_res, 0));
-        r->res_bytes = res;
-    }
+    rc = reloc_scratch(c, up, o_extra + al256(hooks ? hooks->extra_arena_bytes : 0), res);
+    if(rc)
+        return rc;
 
     std::memcpy(r->h_up, desc, (size_t)n * 32);
     std::memcpy(r->h_up + off_xy, xy, (size_t)n * 8);
@@ -637,120 +786,57 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
             std::memcpy(r->h_up + off_extra + (k ? hooks->extra_up_bytes[0] : 0), hooks->extra_up[k], hooks->extra_up_bytes[k]);
     reinterpret_cast<int32_t*>(r->h_res)[0] = -2; // (overwritten by k_reloc_rank; checked after the synchronisation)
     hipStream_t s = c->stream;
-    RCHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
-    uint8_t* A = r->d_arena;
-    const int32_t* d_slots = reinterpret_cast<const int32_t*>(r->d_up + off_slots);
-    const float* d_xy = reinterpret_cast<const float*>(r->d_up + off_xy);
-    const uint8_t* d_valid = valid ? r->d_up + off_valid : nullptr;
-    int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o_gcnt);
+    MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
+    // every candidate's train side is the one uploaded query block
+    SeqArgs a{};
+    a.rows = n_cand, a.S = S;
+    a.desc = r->d_up, a.xy = reinterpret_cast<const float*>(r->d_up + off_xy), a.valid = valid ? r->d_up + off_valid : nullptr;
+    a.n_from_fixed = a.cap_from = n;
+    a.slots = reinterpret_cast<const int32_t*>(r->d_up + off_slots);
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
+    a.use_guess = use_extrinsic_guess, a.rvec = rvec, a.tvec = tvec;
+    a.iterations = iterations, a.reprojection_error = reprojection_error, a.seed = seed;
     RelocDev dev{};
     if(hooks)
     {
-        dev.desc = r->d_up, dev.xy = d_xy, dev.n = n, dev.S = (int)S, dev.valid = d_valid;
-        dev.extra_up = r->d_up + off_extra, dev.extra_arena = A + o_extra;
+        dev.desc = a.desc, dev.xy = a.xy, dev.n = n, dev.valid = a.valid;
+        dev.extra_up = r->d_up + off_extra, dev.extra_arena = r->d_arena + o_extra;
         dev.extra_res = r->d_h_res + res_extra, dev.h_extra_res = r->h_res + res_extra;
         if(hooks->after_upload)
         {
             rc = hooks->after_upload(c, hooks->user, dev);
             if(rc)
                 return rc;
-            d_valid = dev.valid;
+            a.valid = dev.valid;
         }
     }
-    {
-        StageScope ts(c, "reloc_gather_desc");
-        hipLaunchKernelGGL(k_reloc_gather_desc, dim3((unsigned)((2 * S + 255) / 256), (unsigned)P), dim3(256), 0, s, r->d_desc, r->d_n,
-                           d_slots, K, (int)S, A + o_gdesc, g_cnt);
-    }
-    // match(from = query keypoints, to = landmarks of candidate p): knn-2 with query = `to` and train = `from`
-    MatchArgs m{};
-    m.from_desc = r->d_up;
-    m.from_stride = 0; // every pair's train side is the one uploaded query block
-    m.from_cnt = nullptr;
-    m.n_from_fixed = n;
-    m.to_desc = A + o_gdesc;
-    m.to_stride = (long long)S * 32;
-    m.to_cnt = g_cnt;
-    m.cap = (int)S;
-    m.cap_from = n;
-    m.popcount_only = c->matcher_kind == MSLAM_HIP_MATCHER_POPCOUNT;
-    m.idx0 = reinterpret_cast<int32_t*>(A + o_idx0);
-    m.idx1 = reinterpret_cast<int32_t*>(A + o_idx1);
-    m.dist0 = reinterpret_cast<int32_t*>(A + o_dist0);
-    m.dist1 = reinterpret_cast<int32_t*>(A + o_dist1);
-    {
-        StageScope ts(c, "match_knn2");
-        c->last_match_kernel = launch_match_knn2(m, n_cand, s);
-    }
-    RatioArgs q{};
-    q.idx0 = m.idx0, q.dist0 = m.dist0, q.dist1 = m.dist1;
-    q.from_cnt = nullptr, q.n_from_fixed = n;
-    q.to_cnt = g_cnt;
-    q.cap = (int)S;
-    q.thr = c->d_ratio_thr;
-    q.from_idx = reinterpret_cast<int32_t*>(A + o_mfrom);
-    q.to_idx = reinterpret_cast<int32_t*>(A + o_mto);
-    q.n_out = reinterpret_cast<int32_t*>(A + o_mcount);
-    {
-        StageScope ts(c, "ratio_compact");
-        launch_ratio_compact(q, n_cand, s);
-    }
-    float* d_obj = reinterpret_cast<float*>(A + o_obj);
-    float* d_img = reinterpret_cast<float*>(A + o_img);
-    int32_t* d_ncorr = reinterpret_cast<int32_t*>(A + o_ncorr);
-    uint8_t* d_mask = A + o_mask;
-    {
-        StageScope ts(c, "reloc_corr");
-        hipLaunchKernelGGL(k_reloc_corr, dim3((unsigned)P), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, d_slots, r->d_world, K,
-                           (int)S, d_xy, d_valid, n, d_obj, d_img, d_mask, d_ncorr);
-    }
-    RCHK(c, hipGetLastError());
-    PnpBatchLaunch l{};
-    l.obj = d_obj, l.img = d_img, l.n = d_ncorr;
-    l.n_problems = n_cand, l.cap = (int)S;
-    l.fx = fx, l.fy = fy, l.cx = cx, l.cy = cy;
-    l.use_guess = use_extrinsic_guess ? 1 : 0;
-    for(int j = 0; j < 3; ++j)
-    {
-        l.rvec[j] = use_extrinsic_guess ? rvec[j] : 0.0;
-        l.tvec[j] = use_extrinsic_guess ? tvec[j] : 0.0;
-    }
-    l.iterations = iterations;
-    l.reprojection_error = reprojection_error;
-    l.seed = seed;
-    l.hyp = reinterpret_cast<double*>(A + o_hyp);
-    l.counts = reinterpret_cast<int32_t*>(A + o_counts);
-    l.mask = d_mask;
-    l.out = reinterpret_cast<double*>(A + o_out);
-    rc = pnp_launch_batch(c, l);
+    rc = seq_enqueue(c, a, r->d_arena, &dev.seq);
     if(rc)
         return rc;
     {
         StageScope ts(c, "reloc_rank");
-        hipLaunchKernelGGL(k_reloc_rank, dim3(want_pairs ? 1u + (unsigned)P : 1u), dim3(256), 0, s, q.n_out, d_ncorr, l.out, n_cand,
-                           min_inliers, (int)S, q.from_idx, q.to_idx, d_mask, r->d_h_res);
+        hipLaunchKernelGGL(k_reloc_rank, dim3(want_pairs ? 1u + (unsigned)P : 1u), dim3(256), 0, s, dev.seq.mcount, dev.seq.ncorr,
+                           dev.seq.pnp_out, n_cand, min_inliers, (int)S, dev.seq.mfrom, dev.seq.mto, dev.seq.mask, r->d_h_res);
     }
-    RCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     if(hooks && hooks->before_sync)
     {
-        dev.g_cnt = g_cnt, dev.mfrom = q.from_idx, dev.mto = q.to_idx, dev.mcount = q.n_out, dev.ncorr = d_ncorr;
-        dev.mask = d_mask, dev.pnp_out = l.out;
         rc = hooks->before_sync(c, hooks->user, dev);
         if(rc)
             return rc;
     }
-    RCHK(c, hipStreamSynchronize(s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
 
     const int32_t b = reinterpret_cast<const int32_t*>(r->h_res)[0];
     if(b < -1 || b >= n_cand)
-        return rfail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the ranking kernel left no result");
+        return fail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the ranking kernel left no result");
     const RelocRes* rr = reinterpret_cast<const RelocRes*>(r->h_res + 16);
     bool fits = true;
     for(int k = 0; k < n_cand; ++k)
     {
         // (counts from mapped memory size the copies below: never trust them blindly)
         if(rr[k].n_matches < 0 || (size_t)rr[k].n_matches > S || rr[k].n_corr < 0 || rr[k].n_corr > rr[k].n_matches)
-            return rfail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the kernels reported impossible counts");
+            return fail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the kernels reported impossible counts");
         out[k].n_matches = rr[k].n_matches;
         out[k].n_correspondences = rr[k].n_corr;
         out[k].n_inliers = rr[k].n_inliers;
@@ -764,7 +850,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
             fits = false;
     }
     if(want_pairs && !fits)
-        return rfail(c, MSLAM_HIP_E_CAPACITY, "relocalize: a candidate has more matches than pair_stride");
+        return fail(c, MSLAM_HIP_E_CAPACITY, "relocalize: a candidate has more matches than pair_stride");
     if(want_pairs)
     {
         const int32_t* h_from = reinterpret_cast<const int32_t*>(r->h_res + res_head);
@@ -783,7 +869,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     }
     *best = b;
     if(b < 0)
-        return rfail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate reached min_inliers");
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "relocalize: no candidate reached min_inliers");
     return MSLAM_HIP_OK;
 }
 

@@ -52,21 +52,9 @@ __global__ __launch_bounds__(256) void k_track_keyframe(KeyframeArgs a)
     track_keyframe_block(a);
 }
 
-
 } // namespace mslam
 
 using namespace mslam;
-
-#define TCHK(c, call)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
 
 static VoteCam vote_cam(double fx, double fy, double cx, double cy, int width, int height)
 {
@@ -103,7 +91,7 @@ int track_after_upload(mslam_hip_ctx* c, void* user, RelocDev& d)
         launch_backproject(c->stream, reinterpret_cast<const uint16_t*>(d.extra_up + t->off_depth), t->width, t->height, t->factor,
                            t->fx, t->fy, t->cx, t->cy, d.xy, t->n, t->d_xyz, valid);
     }
-    TCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     d.valid = t->d_valid = valid; // the depth filter of :317-334 is the matcher's mask
     return MSLAM_HIP_OK;
 }
@@ -125,7 +113,7 @@ int track_before_sync(mslam_hip_ctx* c, void* user, const RelocDev& d)
         {
             StageScope ts(c, "track_vote");
             hipLaunchKernelGGL(k_track_vote, dim3((unsigned)t->n_vote), dim3(256), 0, c->stream, r->d_world, r->d_n,
-                               reinterpret_cast<const int32_t*>(d.extra_up), K, d.pnp_out, d.ncorr, t->min_matched,
+                               reinterpret_cast<const int32_t*>(d.extra_up), K, d.seq.pnp_out, d.seq.ncorr, t->min_matched,
                                vote_cam(t->fx, t->fy, t->cx, t->cy, t->width, t->height), counts);
         }
         {
@@ -136,10 +124,10 @@ int track_before_sync(mslam_hip_ctx* c, void* user, const RelocDev& d)
     if(t->new_slot >= 0)
     {
         KeyframeArgs a{};
-        a.mfrom = d.mfrom, a.mto = d.mto, a.mcount = d.mcount, a.g_cnt = d.g_cnt, a.ncorr = d.ncorr;
-        a.mask = d.mask, a.rec = d.pnp_out;
+        a.mfrom = d.seq.mfrom, a.mto = d.seq.mto, a.mcount = d.seq.mcount, a.g_cnt = d.seq.g_cnt, a.ncorr = d.seq.ncorr;
+        a.mask = d.seq.mask, a.rec = d.seq.pnp_out;
         a.min_matched = t->min_matched, a.kf_min_landmarks = t->kf_min_landmarks;
-        a.desc = d.desc, a.xyz = t->d_xyz, a.valid = t->d_valid, a.nq = t->n, a.S = d.S, a.z_max = t->z_max;
+        a.desc = d.desc, a.xyz = t->d_xyz, a.valid = t->d_valid, a.nq = t->n, a.S = d.seq.S, a.z_max = t->z_max;
         a.ref_world = r->d_world + (size_t)t->ref_slot * K * 3;
         a.ref_lid = r->d_lid + (size_t)t->ref_slot * K;
         a.out_lid = r->d_lid + (size_t)t->new_slot * K;
@@ -154,7 +142,7 @@ int track_before_sync(mslam_hip_ctx* c, void* user, const RelocDev& d)
         StageScope ts(c, "track_keyframe");
         hipLaunchKernelGGL(k_track_keyframe, dim3(1), dim3(256), 0, c->stream, a);
     }
-    TCHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipGetLastError());
     t->h_res = d.h_extra_res;
     return MSLAM_HIP_OK;
 }
@@ -171,9 +159,9 @@ int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const 
     if(best)
         *best = -1;
     if(!best || n_ids < 0 || n_ids > kRelocMaxCand || (n_ids > 0 && (!ids || !counts)) || !R || !t || width <= 0 || height <= 0)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_visible: bad argument (at most 64 ids)");
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_visible: bad argument (at most 64 ids)");
     RelocState* r = c->reloc;
-    // upload block: [slots 64 x i32 | pose record 16 x f64]; device counts behind it
+    // upload block: [slots 64 x i32 | pose record 16 x f64]; counts 64 x i32 in the arena; result [best, best count, pad | counts]
     struct
     {
         int32_t slots[kRelocMaxCand];
@@ -183,7 +171,7 @@ int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const 
     {
         auto it = r->slot_of.find(ids[k]);
         if(it == r->slot_of.end())
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, "kf_visible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
+            return fail(c, MSLAM_HIP_E_INVALID, "kf_visible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
         up.slots[k] = it->second;
     }
     if(n_ids == 0)
@@ -191,51 +179,32 @@ int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const 
     std::memcpy(up.rec, R, 9 * sizeof(double));
     std::memcpy(up.rec + 9, t, 3 * sizeof(double));
     up.rec[14] = 1.0; // (the PnP record's "model found")
-    if(!r->d_vote || !r->h_vote || !r->d_h_vote)
-    {
-        // all three or none: a call after a failed allocation starts over
-        if(r->d_vote)
-            (void)hipFree(r->d_vote);
-        if(r->h_vote)
-            (void)hipHostFree(r->h_vote);
-        r->d_vote = r->h_vote = r->d_h_vote = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&r->d_vote), sizeof(up) + kRelocMaxCand * 4);
-        if(e == hipSuccess)
-            e = hipHostMalloc(reinterpret_cast<void**>(&r->h_vote), 16 + kRelocMaxCand * 4, hipHostMallocMapped);
-        if(e == hipSuccess)
-            e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_vote), r->h_vote, 0);
-        if(e != hipSuccess)
-        {
-            if(r->d_vote)
-                (void)hipFree(r->d_vote);
-            if(r->h_vote)
-                (void)hipHostFree(r->h_vote);
-            r->d_vote = r->h_vote = r->d_h_vote = nullptr;
-            return reloc_fail(c, MSLAM_HIP_E_RUNTIME, std::string("kf_visible: ") + hipGetErrorString(e));
-        }
-    }
-    int32_t* h = reinterpret_cast<int32_t*>(r->h_vote);
+    rc = reloc_scratch(c, sizeof(up), kRelocMaxCand * 4, 16 + kRelocMaxCand * 4);
+    if(rc)
+        return rc;
+    std::memcpy(r->h_up, &up, sizeof(up));
+    int32_t* h = reinterpret_cast<int32_t*>(r->h_res);
     h[0] = -2; // (overwritten by k_track_vote_pick; checked after the synchronisation)
     hipStream_t s = c->stream;
-    TCHK(c, hipMemcpyAsync(r->d_vote, &up, sizeof(up), hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
-    int32_t* d_counts = reinterpret_cast<int32_t*>(r->d_vote + sizeof(up));
+    MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, sizeof(up), hipMemcpyHostToDevice, s));
+    int32_t* d_counts = reinterpret_cast<int32_t*>(r->d_arena);
     {
         StageScope ts(c, "track_vote");
         hipLaunchKernelGGL(k_track_vote, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_world, r->d_n,
-                           reinterpret_cast<const int32_t*>(r->d_vote), c->p.max_keypoints,
-                           reinterpret_cast<const double*>(r->d_vote + sizeof(up.slots)), nullptr, 0,
+                           reinterpret_cast<const int32_t*>(r->d_up), c->p.max_keypoints,
+                           reinterpret_cast<const double*>(r->d_up + sizeof(up.slots)), nullptr, 0,
                            vote_cam(fx, fy, cx, cy, width, height), d_counts);
     }
     {
         StageScope ts(c, "track_vote_pick");
-        hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, s, d_counts, n_ids, reinterpret_cast<int32_t*>(r->d_h_vote),
-                           reinterpret_cast<int32_t*>(r->d_h_vote + 16));
+        hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, s, d_counts, n_ids, reinterpret_cast<int32_t*>(r->d_h_res),
+                           reinterpret_cast<int32_t*>(r->d_h_res + 16));
     }
-    TCHK(c, hipGetLastError());
-    TCHK(c, hipStreamSynchronize(s));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipStreamSynchronize(s));
     if(h[0] < 0 || h[0] >= n_ids)
-        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "kf_visible: the vote kernel left no result");
-    std::memcpy(counts, r->h_vote + 16, (size_t)n_ids * 4);
+        return fail(c, MSLAM_HIP_E_RUNTIME, "kf_visible: the vote kernel left no result");
+    std::memcpy(counts, r->h_res + 16, (size_t)n_ids * 4);
     *best = h[0];
     return MSLAM_HIP_OK;
 }
@@ -257,48 +226,19 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
     }
     if(!out || !depth || width <= 0 || height <= 0 || n < 0 || n_vote < 0 || n_vote > kRelocMaxCand || (n_vote > 0 && !vote_ids) ||
        !(z_max == z_max) || ((entry_src || entry_kp) && entry_capacity < 0))
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: bad argument (at most 64 vote ids)");
+        return fail(c, MSLAM_HIP_E_INVALID, "track: bad argument (at most 64 vote ids)");
     const int K = c->p.max_keypoints;
     if(n > K)
-        return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "track: more query keypoints than the context's max_keypoints (a store entry's capacity)");
+        return fail(c, MSLAM_HIP_E_CAPACITY, "track: more query keypoints than the context's max_keypoints (a store entry's capacity)");
     RelocState* r = c->reloc;
-    struct
-    {
-        int32_t slots[kRelocMaxCand];
-    } vote{};
-    auto ref = r->slot_of.find(ref_id);
-    if(ref == r->slot_of.end())
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: reference id " + std::to_string(ref_id) + " is not in the keyframe store");
-    bool collides = new_id >= 0 && new_id == ref_id;
-    for(int k = 0; k < n_vote; ++k)
-    {
-        auto it = r->slot_of.find(vote_ids[k]);
-        if(it == r->slot_of.end())
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: vote id " + std::to_string(vote_ids[k]) + " is not in the keyframe store");
-        vote.slots[k] = it->second;
-        collides = collides || (new_id >= 0 && vote_ids[k] == new_id);
-    }
-    if(collides)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track: new_id names the reference keyframe or a keyframe of the vote list");
+    TrackSlots slots;
+    rc = slots.resolve(c, "track", ref_id, vote_ids, n_vote, new_id);
+    if(!rc)
+        rc = slots.reserve(c);
+    if(rc)
+        return rc;
     TrackCall tc{};
-    tc.ref_slot = ref->second;
-    // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
-    tc.new_slot = -1;
-    const bool existed = new_id >= 0 && r->slot_of.count(new_id) != 0;
-    if(new_id >= 0)
-    {
-        rc = store_slot_for(c, new_id, &tc.new_slot);
-        if(rc)
-            return rc;
-        tc.lid_base = store_next_lid_base(c); // (the serial advances whether or not the step makes the keyframe)
-    }
-    auto release = [&]() { // a slot reserved for new_id that received no entry
-        if(new_id >= 0 && !existed)
-        {
-            r->slot_of.erase(new_id);
-            r->free_slots.push_back(tc.new_slot);
-        }
-    };
+    tc.ref_slot = slots.ref_slot, tc.new_slot = slots.new_slot, tc.lid_base = slots.lid_base;
     tc.depth = depth, tc.width = width, tc.height = height, tc.factor = factor;
     tc.fx = fx, tc.fy = fy, tc.cx = cx, tc.cy = cy;
     tc.n = n, tc.n_vote = n_vote;
@@ -306,11 +246,11 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
     tc.z_max = z_max;
     // extra upload: [vote slots | depth], copied by reloc_run from these two spans into its page-locked staging block
     const size_t npx = (size_t)width * height;
-    tc.off_depth = sizeof(vote);
+    tc.off_depth = sizeof(slots.vote_slots);
     tc.off_valid = (size_t)std::max(n, 1) * 24;
-    tc.off_counts = (tc.off_valid + (size_t)std::max(n, 1) + 255) & ~(size_t)255;
+    tc.off_counts = al256(tc.off_valid + (size_t)std::max(n, 1));
     RelocHooks hooks{};
-    hooks.extra_up[0] = &vote, hooks.extra_up_bytes[0] = sizeof(vote);
+    hooks.extra_up[0] = slots.vote_slots, hooks.extra_up_bytes[0] = sizeof(slots.vote_slots);
     hooks.extra_up[1] = depth, hooks.extra_up_bytes[1] = npx * 2;
     hooks.extra_arena_bytes = tc.off_counts + kRelocMaxCand * 4;
     hooks.extra_res_bytes = sizeof(TrackRes) + kRelocMaxCand * 4 + (size_t)K * 8;
@@ -324,15 +264,7 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
                    use_extrinsic_guess, rvec, tvec, 0, &cand, &best, pair_from, pair_to, inliers, pair_stride, &hooks);
     if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL && rc != MSLAM_HIP_E_CAPACITY)
     {
-        // the sequence failed part-way: what it enqueued may still run and may write the slot.  Wait for it before the slot
-        // goes back to the free list (keeping reloc_run's message); an entry that existed under new_id may have been
-        // replaced, so all the host still knows about its size is the capacity
-        const std::string msg = c->err;
-        (void)hipStreamSynchronize(c->stream);
-        c->err = msg;
-        if(existed)
-            r->n_upper[(size_t)tc.new_slot] = K;
-        release();
+        slots.rollback(c, true); // the sequence failed part-way (reloc_run's message stays)
         return rc;
     }
     out->n_matches = cand.n_matches, out->n_correspondences = cand.n_correspondences;
@@ -342,7 +274,7 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
     if(!tc.h_res)
     {
         // nothing ran (fewer than 2 query keypoints): no matches, not tracked
-        release();
+        slots.rollback(c, false);
         return rc;
     }
     if(cand.status)
@@ -355,18 +287,16 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
     if(tr->n_entry < 0 || tr->n_entry > K || tr->n_inherited < 0 || tr->n_inherited > tr->n_entry || tr->vote_best < -1 ||
        tr->vote_best >= std::max(n_vote, 1) || (!out->keyframe_added && tr->n_entry != 0))
     {
-        if(existed)
-            r->n_upper[(size_t)tc.new_slot] = K;
-        release();
-        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, "track: the kernels reported impossible counts");
+        slots.rollback(c, true);
+        return fail(c, MSLAM_HIP_E_RUNTIME, "track: the kernels reported impossible counts");
     }
     if(out->keyframe_added)
     {
         out->n_entry = tr->n_entry, out->n_inherited = tr->n_inherited;
-        r->n_upper[(size_t)tc.new_slot] = tr->n_entry;
+        slots.commit(c, tr->n_entry);
     }
     else
-        release();
+        slots.rollback(c, false);
     if(out->tracked && n_vote > 0)
         out->vote_best = tr->vote_best, out->vote_best_count = tr->vote_best_count;
     if(vote_counts && n_vote > 0)
@@ -376,14 +306,14 @@ int mslam_hip_track(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, int 
     if(out->keyframe_added && (entry_src || entry_kp))
     {
         if(out->n_entry > entry_capacity)
-            return reloc_fail(c, MSLAM_HIP_E_CAPACITY, "track: the new entry has more landmarks than entry_capacity");
+            return fail(c, MSLAM_HIP_E_CAPACITY, "track: the new entry has more landmarks than entry_capacity");
         if(entry_src)
             std::memcpy(entry_src, h_counts + kRelocMaxCand, (size_t)out->n_entry * 4);
         if(entry_kp)
             std::memcpy(entry_kp, h_counts + kRelocMaxCand + K, (size_t)out->n_entry * 4);
     }
     if(!out->tracked)
-        return reloc_fail(c, MSLAM_HIP_E_NO_MODEL, "track: fewer than min_matched_points correspondences, or no model");
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "track: fewer than min_matched_points correspondences, or no model");
     return MSLAM_HIP_OK;
 }
 

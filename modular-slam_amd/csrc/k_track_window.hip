@@ -4,10 +4,9 @@
 // Between two events of the front end's loop (a new keyframe, a change of the reference keyframe, a tracking failure)
 // consecutive frames are matched against the same landmarks and do not depend on each other, so they run as one batch:
 //   k_backproject       S depth frames in one launch (host form only; the _dev form reads the points view)
-//   k_tw_gather         the reference entry's descriptors, once, into the contiguous block the matcher addresses
-//   match_knn2 / ratio  S pairs in one launch: train side = frame s (stride, device count), query side = that block
-//   k_tw_corr           per frame: matches with a valid depth -> correspondences (k_reloc_corr's rule and order)
-//   k_pnp_ransac_batch  S problems, problem s samples with seed + s, one guess for all
+//   seq_enqueue         mslam_hip_relocalize's own sequence (k_reloc.hip) with S rows on one entry: k_reloc_gather_desc once,
+//                       match_knn2 / ratio_compact for S pairs (train side = frame s: stride, device count), k_reloc_corr
+//                       per frame on the keypoints with a valid depth, k_pnp_ransac_batch (problem s samples with seed + s)
 //   k_tw_vote           (n_vote, S) workgroups, each reading its frame's pose record (track_vote_block)
 //   k_tw_scan           one workgroup: per frame the record, the vote's winner and the event flag; the first event of the
 //                       window by ballot + a four-entry minimum; everything the host reads lands in mapped memory
@@ -28,8 +27,8 @@ constexpr int kWindowMax = 256; // frames per window: one lane of k_tw_scan's wo
 // per frame, in the mapped result block
 struct WinRec
 {
-    int32_t n_matches, n_corr, n_inliers, status, tracked, required, vote_best, vote_best_count;
-    double R[9], t[3];
+    RelocRes res;
+    int32_t tracked, required, vote_best, vote_best_count;
 };
 
 // head of the mapped result block: [WinHead | WinRec[S] | vote counts S x 64 | entry_src K | entry_kp K]
@@ -38,73 +37,6 @@ struct WinHead
     int32_t first_event, pad;
     TrackRes entry; // n_entry, n_inherited of the keyframe the window made (vote fields unused)
 };
-
-// the reference entry's descriptor block, copied once; g_cnt[s] = its landmark count for every pair s
-__global__ __launch_bounds__(256) void k_tw_gather(const uint8_t* __restrict__ store_desc, const int32_t* __restrict__ store_n, int slot,
-                                                   int K, int Srow, int n_frames, uint8_t* __restrict__ g_desc,
-                                                   int32_t* __restrict__ g_cnt)
-{
-    const int n = min(min(max(store_n[slot], 0), K), Srow);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if(i < n_frames) // n_frames <= 256: block 0
-        g_cnt[i] = n;
-    if(i < 2 * n)
-        reinterpret_cast<uint4*>(g_desc)[i] = reinterpret_cast<const uint4*>(store_desc + (size_t)slot * K * 32)[i];
-}
-
-// frame s (one workgroup): its matches whose keypoint has a valid depth become correspondences, in match order — k_reloc_corr
-// with the frame's own xy / valid / count and the one reference entry
-__global__ __launch_bounds__(256) void k_tw_corr(const int32_t* __restrict__ mfrom, const int32_t* __restrict__ mto,
-                                                 const int32_t* __restrict__ mcount, const int32_t* __restrict__ g_cnt,
-                                                 const double* __restrict__ world, int Srow, const float* __restrict__ xy_all,
-                                                 const uint8_t* __restrict__ valid_all, const int32_t* __restrict__ n_kp,
-                                                 long long stride, float* __restrict__ obj, float* __restrict__ img,
-                                                 uint8_t* __restrict__ mask, int32_t* __restrict__ n_out)
-{
-    __shared__ uint32_t wsum[4];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m = min(max(mcount[s], 0), Srow), n_to = g_cnt[s];
-    const int nq = (int)min((long long)max(n_kp[s], 0), stride);
-    const float* xy = xy_all + (size_t)s * stride * 2;
-    const uint8_t* valid = valid_all + (size_t)s * stride;
-    const size_t row = (size_t)s * Srow;
-    uint32_t running = 0;
-    for(int base = 0; base < m; base += 256)
-    {
-        const int i = base + tid;
-        int from = 0, to = 0;
-        bool ok = false;
-        if(i < m)
-        {
-            from = mfrom[row + i], to = mto[row + i];
-            ok = (unsigned)from < (unsigned)nq && (unsigned)to < (unsigned)n_to && valid[from] != 0;
-        }
-        const unsigned long long b = __ballot(ok);
-        if(lane == 0)
-            wsum[wave] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t pre = 0, tot = 0;
-        for(int k = 0; k < 4; ++k)
-        {
-            pre += k < wave ? wsum[k] : 0;
-            tot += wsum[k];
-        }
-        if(ok)
-        {
-            const size_t o = row + running + pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); // < row + m <= row + Srow
-            const double* P = world + (size_t)to * 3;
-            obj[o * 3] = (float)P[0], obj[o * 3 + 1] = (float)P[1], obj[o * 3 + 2] = (float)P[2];
-            img[o * 2] = xy[(size_t)from * 2], img[o * 2 + 1] = xy[(size_t)from * 2 + 1];
-        }
-        running += tot;
-        __syncthreads();
-    }
-    // fewer than 4 correspondences: the PnP kernel reports "no model" without touching the mask
-    if(running < 4 && tid < (int)running)
-        mask[row + tid] = 0;
-    if(tid == 0)
-        n_out[s] = (int32_t)running;
-}
 
 // workgroup (k, s): listed keyframe k seen from frame s's pose
 __global__ __launch_bounds__(256) void k_tw_vote(const double* __restrict__ store_world, const int32_t* __restrict__ store_n,
@@ -137,18 +69,10 @@ __global__ __launch_bounds__(256) void k_tw_scan(ScanArgs a)
     bool event = false;
     if(s < a.n_frames)
     {
-        const double* o = a.rec + (size_t)s * 16;
         WinRec r{};
-        r.n_matches = a.mcount[s];
-        r.n_corr = a.ncorr[s];
-        r.status = o[14] == 1.0 ? 1 : 0;
-        r.n_inliers = r.status ? (int32_t)o[12] : 0;
-        for(int j = 0; j < 9; ++j)
-            r.R[j] = r.status ? o[j] : 0.0;
-        for(int j = 0; j < 3; ++j)
-            r.t[j] = r.status ? o[9 + j] : 0.0;
-        r.tracked = r.status && r.n_corr >= a.min_matched ? 1 : 0;
-        r.required = r.tracked && r.n_inliers < a.kf_min_landmarks ? 1 : 0;
+        r.res = reloc_record(a.rec + (size_t)s * 16, a.mcount[s], a.ncorr[s]);
+        r.tracked = r.res.status && r.res.n_corr >= a.min_matched ? 1 : 0;
+        r.required = r.tracked && r.res.n_inliers < a.kf_min_landmarks ? 1 : 0;
         r.vote_best = -1, r.vote_best_count = 0;
         int top = -1;
         for(int k = 0; k < a.n_vote; ++k)
@@ -196,17 +120,6 @@ __global__ __launch_bounds__(256) void k_tw_keyframe(KeyframeArgs a, const int32
 
 using namespace mslam;
 
-#define WCHK(c, call)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                        \
-        if(e_ != hipSuccess)                                                                                           \
-        {                                                                                                              \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                              \
-            return MSLAM_HIP_E_RUNTIME;                                                                                \
-        }                                                                                                              \
-    } while(0)
-
 namespace
 {
 
@@ -249,89 +162,40 @@ struct WindowParams
     int entry_capacity;
 };
 
-size_t al256(size_t x)
-{
-    return (x + 255) & ~(size_t)255;
-}
-
-// the relocalize scratch, grown as reloc_run grows it (a call of either kind finds blocks at least as large as it needs)
-int grow_scratch(mslam_hip_ctx* c, size_t up, size_t arena, size_t res)
-{
-    RelocState* r = c->reloc;
-    if(up > r->up_bytes)
-    {
-        WCHK(c, hipStreamSynchronize(c->stream));
-        if(r->h_up)
-            (void)hipHostFree(r->h_up);
-        if(r->d_up)
-            (void)hipFree(r->d_up);
-        r->h_up = r->d_up = nullptr;
-        r->up_bytes = 0;
-        WCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_up), up, hipHostMallocDefault));
-        WCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_up), up));
-        r->up_bytes = up;
-    }
-    if(arena > r->arena_bytes)
-    {
-        WCHK(c, hipStreamSynchronize(c->stream));
-        if(r->d_arena)
-            (void)hipFree(r->d_arena);
-        r->d_arena = nullptr;
-        r->arena_bytes = 0;
-        WCHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_arena), arena));
-        r->arena_bytes = arena;
-    }
-    if(res > r->res_bytes)
-    {
-        WCHK(c, hipStreamSynchronize(c->stream));
-        if(r->h_res)
-            (void)hipHostFree(r->h_res);
-        r->h_res = r->d_h_res = nullptr;
-        r->res_bytes = 0;
-        WCHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_res), res, hipHostMallocMapped));
-        WCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_res), r->h_res, 0));
-        r->res_bytes = res;
-    }
-    return MSLAM_HIP_OK;
-}
-
 // everything between the upload and the synchronisation; a failure in here leaves work enqueued (the caller waits for it)
-int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& p, int ref_slot, int new_slot, int64_t lid_base,
-                   const int32_t* vote_slots, WinHead** h_head)
+int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& p, const TrackSlots& slots, WinHead** h_head)
 {
     RelocState* r = c->reloc;
-    const int K = c->p.max_keypoints, S = w.S;
+    const int K = c->p.max_keypoints, S = w.S, ref_slot = slots.ref_slot, new_slot = slots.new_slot;
     const bool host = w.d_desc == nullptr;
     const size_t stride = (size_t)w.stride, st1 = std::max(stride, (size_t)1);
-    const size_t Srow = ((size_t)std::max(r->n_upper[(size_t)ref_slot], 1) + 255) & ~(size_t)255, PS = (size_t)S * Srow;
+    const size_t Srow = seq_row_stride(r->n_upper[(size_t)ref_slot]);
     const size_t npx = (size_t)w.width * w.height;
-    // ---- upload block: [vote slots 64 x i32 | n S x i32 | desc S x stride x 32 | xy S x stride x 8 | depth S x h x w x 2]
-    const size_t u_n = al256(kRelocMaxCand * 4), u_desc = u_n + al256((size_t)S * 4);
+    // ---- upload block: [vote slots 64 x i32, reference slot | n S x i32 | desc S x stride x 32 | xy S x stride x 8 |
+    // depth S x h x w x 2]
+    const size_t u_n = al256((kRelocMaxCand + 1) * 4), u_desc = u_n + al256((size_t)S * 4);
     const size_t u_xy = host ? u_desc + al256((size_t)S * st1 * 32) : u_desc;
     const size_t u_depth = host ? u_xy + al256((size_t)S * st1 * 8) : u_desc;
     const size_t up = host ? u_depth + al256((size_t)S * npx * 2) : u_desc;
-    // ---- device arena
-    size_t off = 0;
+    // ---- device arena: the sequence's arrays, then the window's own
+    size_t off = seq_arena_bytes(S, Srow, p.iterations, true);
     auto carve = [&](size_t bytes) {
         const size_t o = off;
         off += al256(bytes);
         return o;
     };
-    const size_t o_gdesc = carve(Srow * 32), o_gcnt = carve((size_t)S * 4), o_idx0 = carve(PS * 4), o_idx1 = carve(PS * 4),
-                 o_dist0 = carve(PS * 4), o_dist1 = carve(PS * 4), o_mfrom = carve(PS * 4), o_mto = carve(PS * 4),
-                 o_mcount = carve((size_t)S * 4), o_obj = carve(PS * 12), o_img = carve(PS * 8), o_ncorr = carve((size_t)S * 4),
-                 o_mask = carve(PS), o_hyp = carve((size_t)S * p.iterations * 96), o_counts = carve((size_t)S * p.iterations * 4),
-                 o_out = carve((size_t)S * 128), o_xyz = carve(host ? (size_t)S * st1 * 24 : 0),
-                 o_valid = carve(host ? (size_t)S * st1 : 0), o_vote = carve((size_t)S * kRelocMaxCand * 4), o_event = carve(4);
+    const size_t o_xyz = carve(host ? (size_t)S * st1 * 24 : 0), o_valid = carve(host ? (size_t)S * st1 : 0),
+                 o_vote = carve((size_t)S * kRelocMaxCand * 4), o_event = carve(4);
     // ---- mapped result block
     const size_t r_rec = sizeof(WinHead), r_counts = r_rec + (size_t)S * sizeof(WinRec),
                  r_src = r_counts + (size_t)S * kRelocMaxCand * 4, res = r_src + (size_t)K * 8;
-    int rc = grow_scratch(c, up, off, res);
+    int rc = reloc_scratch(c, up, off, res);
     if(rc)
         return rc;
 
-    std::memset(r->h_up, 0, kRelocMaxCand * 4);
-    std::memcpy(r->h_up, vote_slots, (size_t)p.n_vote * 4);
+    int32_t* h_slots = reinterpret_cast<int32_t*>(r->h_up);
+    std::memcpy(h_slots, slots.vote_slots, kRelocMaxCand * 4);
+    h_slots[kRelocMaxCand] = ref_slot;
     if(host)
     {
         std::memcpy(r->h_up + u_n, w.n, (size_t)S * 4);
@@ -347,7 +211,7 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     WinHead* hh = reinterpret_cast<WinHead*>(r->h_res);
     *hh = WinHead{-2, 0, TrackRes{0, 0, -1, 0}}; // (first_event is overwritten by k_tw_scan; checked after the synchronisation)
     hipStream_t s = c->stream;
-    WCHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
+    MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
     uint8_t* A = r->d_arena;
     const int32_t* d_slots = reinterpret_cast<const int32_t*>(r->d_up);
     const uint8_t* d_desc = host ? r->d_up + u_desc : w.d_desc;
@@ -361,74 +225,18 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
         launch_backproject_batch(s, reinterpret_cast<const uint16_t*>(r->d_up + u_depth), w.width, w.height, w.factor, p.fx, p.fy, p.cx,
                                  p.cy, d_xy, d_n, w.stride, S, reinterpret_cast<double*>(A + o_xyz), A + o_valid);
     }
-    int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o_gcnt);
-    {
-        StageScope ts(c, "track_window_gather");
-        hipLaunchKernelGGL(k_tw_gather, dim3((unsigned)((2 * Srow + 255) / 256)), dim3(256), 0, s, r->d_desc, r->d_n, ref_slot, K, (int)Srow,
-                           S, A + o_gdesc, g_cnt);
-    }
-    // match(from = keypoints of frame s, to = landmarks of the reference entry): knn-2 with query = `to` and train = `from`
-    MatchArgs m{};
-    m.from_desc = d_desc;
-    m.from_stride = (long long)stride * 32;
-    m.from_cnt = d_n;
-    m.n_from_fixed = 0;
-    m.to_desc = A + o_gdesc;
-    m.to_stride = 0; // every pair's query side is the one gathered entry
-    m.to_cnt = g_cnt;
-    m.cap = (int)Srow;
-    m.cap_from = w.cap_from;
-    m.popcount_only = c->matcher_kind == MSLAM_HIP_MATCHER_POPCOUNT;
-    m.idx0 = reinterpret_cast<int32_t*>(A + o_idx0);
-    m.idx1 = reinterpret_cast<int32_t*>(A + o_idx1);
-    m.dist0 = reinterpret_cast<int32_t*>(A + o_dist0);
-    m.dist1 = reinterpret_cast<int32_t*>(A + o_dist1);
-    {
-        StageScope ts(c, "match_knn2");
-        c->last_match_kernel = launch_match_knn2(m, S, s);
-    }
-    RatioArgs q{};
-    q.idx0 = m.idx0, q.dist0 = m.dist0, q.dist1 = m.dist1;
-    q.from_cnt = d_n, q.n_from_fixed = 0;
-    q.to_cnt = g_cnt;
-    q.cap = (int)Srow;
-    q.thr = c->d_ratio_thr;
-    q.from_idx = reinterpret_cast<int32_t*>(A + o_mfrom);
-    q.to_idx = reinterpret_cast<int32_t*>(A + o_mto);
-    q.n_out = reinterpret_cast<int32_t*>(A + o_mcount);
-    {
-        StageScope ts(c, "ratio_compact");
-        launch_ratio_compact(q, S, s);
-    }
-    float* d_obj = reinterpret_cast<float*>(A + o_obj);
-    float* d_img = reinterpret_cast<float*>(A + o_img);
-    int32_t* d_ncorr = reinterpret_cast<int32_t*>(A + o_ncorr);
-    uint8_t* d_mask = A + o_mask;
-    const double* ref_world = r->d_world + (size_t)ref_slot * K * 3;
-    {
-        StageScope ts(c, "track_window_corr");
-        hipLaunchKernelGGL(k_tw_corr, dim3((unsigned)S), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, ref_world, (int)Srow, d_xy,
-                           d_valid, d_n, (long long)stride, d_obj, d_img, d_mask, d_ncorr);
-    }
-    WCHK(c, hipGetLastError());
-    PnpBatchLaunch l{};
-    l.obj = d_obj, l.img = d_img, l.n = d_ncorr;
-    l.n_problems = S, l.cap = (int)Srow;
-    l.fx = p.fx, l.fy = p.fy, l.cx = p.cx, l.cy = p.cy;
-    l.use_guess = p.use_guess ? 1 : 0;
-    for(int j = 0; j < 3; ++j)
-    {
-        l.rvec[j] = p.use_guess ? p.rvec[j] : 0.0;
-        l.tvec[j] = p.use_guess ? p.tvec[j] : 0.0;
-    }
-    l.iterations = p.iterations;
-    l.reprojection_error = p.reprojection_error;
-    l.seed = p.seed; // problem s samples with seed + s
-    l.hyp = reinterpret_cast<double*>(A + o_hyp);
-    l.counts = reinterpret_cast<int32_t*>(A + o_counts);
-    l.mask = d_mask;
-    l.out = reinterpret_cast<double*>(A + o_out);
-    rc = pnp_launch_batch(c, l);
+    // every frame's query side is the one reference entry; its train side is the frame (stride, device count), masked by
+    // its valid depths
+    SeqArgs a{};
+    a.rows = S, a.S = Srow;
+    a.desc = d_desc, a.xy = d_xy, a.valid = d_valid;
+    a.from_stride = stride, a.from_cnt = d_n, a.cap_from = w.cap_from;
+    a.slots = d_slots + kRelocMaxCand, a.one_slot = true;
+    a.fx = p.fx, a.fy = p.fy, a.cx = p.cx, a.cy = p.cy;
+    a.use_guess = p.use_guess, a.rvec = p.rvec, a.tvec = p.tvec;
+    a.iterations = p.iterations, a.reprojection_error = p.reprojection_error, a.seed = p.seed;
+    SeqDev d{};
+    rc = seq_enqueue(c, a, A, &d);
     if(rc)
         return rc;
     int32_t* d_vote = reinterpret_cast<int32_t*>(A + o_vote);
@@ -436,45 +244,45 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     {
         StageScope ts(c, "track_window_vote");
         const VoteCam cam{p.fx, p.fy, p.cx, p.cy, (double)(float)w.width, (double)(float)w.height};
-        hipLaunchKernelGGL(k_tw_vote, dim3((unsigned)p.n_vote, (unsigned)S), dim3(256), 0, s, r->d_world, r->d_n, d_slots, K, l.out, d_ncorr,
-                           p.min_matched, cam, d_vote);
+        hipLaunchKernelGGL(k_tw_vote, dim3((unsigned)p.n_vote, (unsigned)S), dim3(256), 0, s, r->d_world, r->d_n, d_slots, K, d.pnp_out,
+                           d.ncorr, p.min_matched, cam, d_vote);
     }
     int32_t* d_event = reinterpret_cast<int32_t*>(A + o_event);
     {
-        ScanArgs a{};
-        a.mcount = q.n_out, a.ncorr = d_ncorr, a.counts = d_vote, a.rec = l.out;
-        a.n_frames = S, a.n_vote = p.n_vote, a.ref_vote_pos = p.ref_vote_pos;
-        a.min_matched = p.min_matched, a.kf_min_landmarks = p.kf_min_landmarks;
-        a.d_event = d_event;
-        a.h_head = reinterpret_cast<WinHead*>(r->d_h_res);
-        a.h_rec = reinterpret_cast<WinRec*>(r->d_h_res + r_rec);
-        a.h_counts = reinterpret_cast<int32_t*>(r->d_h_res + r_counts);
+        ScanArgs sa{};
+        sa.mcount = d.mcount, sa.ncorr = d.ncorr, sa.counts = d_vote, sa.rec = d.pnp_out;
+        sa.n_frames = S, sa.n_vote = p.n_vote, sa.ref_vote_pos = p.ref_vote_pos;
+        sa.min_matched = p.min_matched, sa.kf_min_landmarks = p.kf_min_landmarks;
+        sa.d_event = d_event;
+        sa.h_head = reinterpret_cast<WinHead*>(r->d_h_res);
+        sa.h_rec = reinterpret_cast<WinRec*>(r->d_h_res + r_rec);
+        sa.h_counts = reinterpret_cast<int32_t*>(r->d_h_res + r_counts);
         StageScope ts(c, "track_window_scan");
-        hipLaunchKernelGGL(k_tw_scan, dim3(1), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_tw_scan, dim3(1), dim3(256), 0, s, sa);
     }
     if(new_slot >= 0)
     {
-        KeyframeArgs a{};
-        a.mfrom = q.from_idx, a.mto = q.to_idx, a.mcount = q.n_out, a.g_cnt = g_cnt, a.ncorr = d_ncorr;
-        a.mask = d_mask, a.rec = l.out;
-        a.min_matched = p.min_matched, a.kf_min_landmarks = p.kf_min_landmarks;
-        a.desc = d_desc, a.xyz = d_xyz, a.valid = d_valid, a.nq = 0, a.S = (int)Srow, a.z_max = p.z_max;
-        a.ref_world = ref_world;
-        a.ref_lid = r->d_lid + (size_t)ref_slot * K;
-        a.out_lid = r->d_lid + (size_t)new_slot * K;
-        a.lid_base = lid_base;
-        a.out_desc = r->d_desc + (size_t)new_slot * K * 32;
-        a.out_world = r->d_world + (size_t)new_slot * K * 3;
-        a.out_n = r->d_n + new_slot;
-        a.cap = K;
-        a.h_res = &reinterpret_cast<WinHead*>(r->d_h_res)->entry;
-        a.h_src = reinterpret_cast<int32_t*>(r->d_h_res + r_src);
-        a.h_kp = a.h_src + K;
+        KeyframeArgs ka{};
+        ka.mfrom = d.mfrom, ka.mto = d.mto, ka.mcount = d.mcount, ka.g_cnt = d.g_cnt, ka.ncorr = d.ncorr;
+        ka.mask = d.mask, ka.rec = d.pnp_out;
+        ka.min_matched = p.min_matched, ka.kf_min_landmarks = p.kf_min_landmarks;
+        ka.desc = d_desc, ka.xyz = d_xyz, ka.valid = d_valid, ka.nq = 0, ka.S = d.S, ka.z_max = p.z_max;
+        ka.ref_world = r->d_world + (size_t)ref_slot * K * 3;
+        ka.ref_lid = r->d_lid + (size_t)ref_slot * K;
+        ka.out_lid = r->d_lid + (size_t)new_slot * K;
+        ka.lid_base = slots.lid_base;
+        ka.out_desc = r->d_desc + (size_t)new_slot * K * 32;
+        ka.out_world = r->d_world + (size_t)new_slot * K * 3;
+        ka.out_n = r->d_n + new_slot;
+        ka.cap = K;
+        ka.h_res = &reinterpret_cast<WinHead*>(r->d_h_res)->entry;
+        ka.h_src = reinterpret_cast<int32_t*>(r->d_h_res + r_src);
+        ka.h_kp = ka.h_src + K;
         StageScope ts(c, "track_window_keyframe");
-        hipLaunchKernelGGL(k_tw_keyframe, dim3(1), dim3(256), 0, s, a, d_event, d_n, S, (long long)stride);
+        hipLaunchKernelGGL(k_tw_keyframe, dim3(1), dim3(256), 0, s, ka, d_event, d_n, S, (long long)stride);
     }
-    WCHK(c, hipGetLastError());
-    WCHK(c, hipStreamSynchronize(s));
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipStreamSynchronize(s));
     *h_head = hh;
     return MSLAM_HIP_OK;
 }
@@ -490,84 +298,51 @@ int window_run(mslam_hip_ctx* c, const char* who, const WindowSource& w, const W
         p.out[s].vote_best = -1;
     }
     *p.first_event = S;
-    int32_t vote_slots[kRelocMaxCand] = {0};
-    auto ref = r->slot_of.find(p.ref_id);
-    if(ref == r->slot_of.end())
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, me + ": reference id " + std::to_string(p.ref_id) + " is not in the keyframe store");
-    bool collides = p.new_id >= 0 && p.new_id == p.ref_id;
-    for(int k = 0; k < p.n_vote; ++k)
-    {
-        auto it = r->slot_of.find(p.vote_ids[k]);
-        if(it == r->slot_of.end())
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, me + ": vote id " + std::to_string(p.vote_ids[k]) + " is not in the keyframe store");
-        vote_slots[k] = it->second;
-        collides = collides || (p.new_id >= 0 && p.vote_ids[k] == p.new_id);
-    }
-    if(collides)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, me + ": new_id names the reference keyframe or a keyframe of the vote list");
-    int rc = mslam_ratio_table(c, p.ratio);
+    TrackSlots slots;
+    int rc = slots.resolve(c, who, p.ref_id, p.vote_ids, p.n_vote, p.new_id);
+    if(!rc)
+        rc = mslam_ratio_table(c, p.ratio);
+    if(!rc)
+        rc = slots.reserve(c);
     if(rc)
         return rc;
-    const int ref_slot = ref->second;
-    // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
-    int new_slot = -1;
-    int64_t lid_base = 0;
-    const bool existed = p.new_id >= 0 && r->slot_of.count(p.new_id) != 0;
-    if(p.new_id >= 0)
-    {
-        rc = store_slot_for(c, p.new_id, &new_slot);
-        if(rc)
-            return rc;
-        lid_base = store_next_lid_base(c); // (the serial advances whether or not the window makes the keyframe)
-    }
-    auto release = [&]() { // a slot reserved for new_id that received no entry
-        if(p.new_id >= 0 && !existed)
-        {
-            r->slot_of.erase(p.new_id);
-            r->free_slots.push_back(new_slot);
-        }
-    };
     WinHead* head = nullptr;
-    rc = window_enqueue(c, w, p, ref_slot, new_slot, lid_base, vote_slots, &head);
+    rc = window_enqueue(c, w, p, slots, &head);
     if(rc)
     {
-        // what was enqueued may still run and may write the slot: wait for it before the slot goes back to the free list
-        const std::string msg = c->err;
-        (void)hipStreamSynchronize(c->stream);
-        c->err = msg;
-        if(existed)
-            r->n_upper[(size_t)new_slot] = K;
-        release();
+        slots.rollback(c, true);
         return rc;
     }
     const WinRec* rec = reinterpret_cast<const WinRec*>(r->h_res + sizeof(WinHead));
     const int32_t* h_counts = reinterpret_cast<const int32_t*>(r->h_res + sizeof(WinHead) + (size_t)S * sizeof(WinRec));
     const int32_t* h_src = h_counts + (size_t)S * kRelocMaxCand;
-    const size_t Srow = ((size_t)std::max(r->n_upper[(size_t)ref_slot], 1) + 255) & ~(size_t)255;
+    const size_t Srow = seq_row_stride(r->n_upper[(size_t)slots.ref_slot]);
     const int first = head->first_event;
     const TrackRes tr = head->entry;
     bool sane = first >= 0 && first <= S && tr.n_entry >= 0 && tr.n_entry <= K && tr.n_inherited >= 0 && tr.n_inherited <= tr.n_entry;
     for(int s = 0; sane && s < S; ++s) // (counts from mapped memory: never trust them blindly)
-        sane = rec[s].n_matches >= 0 && (size_t)rec[s].n_matches <= Srow && rec[s].n_corr >= 0 && rec[s].n_corr <= rec[s].n_matches &&
+    {
+        const RelocRes& q = rec[s].res;
+        sane = q.n_matches >= 0 && (size_t)q.n_matches <= Srow && q.n_corr >= 0 && q.n_corr <= q.n_matches &&
                rec[s].vote_best >= -1 && rec[s].vote_best < std::max(p.n_vote, 1);
+    }
     const bool added = sane && first < S && rec[first].required && p.new_id >= 0;
     if(!sane || (!added && tr.n_entry != 0))
     {
-        if(existed)
-            r->n_upper[(size_t)new_slot] = K;
-        release();
-        return reloc_fail(c, MSLAM_HIP_E_RUNTIME, me + ": the kernels reported impossible counts");
+        slots.rollback(c, true);
+        return fail(c, MSLAM_HIP_E_RUNTIME, me + ": the kernels reported impossible counts");
     }
     for(int s = 0; s < S; ++s)
     {
         mslam_hip_track_window_result& o = p.out[s];
-        o.n_matches = rec[s].n_matches, o.n_correspondences = rec[s].n_corr;
-        o.n_inliers = rec[s].n_inliers, o.status = rec[s].status;
-        if(rec[s].status)
+        const RelocRes& q = rec[s].res;
+        o.n_matches = q.n_matches, o.n_correspondences = q.n_corr;
+        o.n_inliers = q.n_inliers, o.status = q.status;
+        if(q.status)
         {
-            std::memcpy(o.R, rec[s].R, sizeof(o.R));
-            std::memcpy(o.tvec, rec[s].t, sizeof(o.tvec));
-            pnp_rotation_to_rvec(rec[s].R, o.rvec);
+            std::memcpy(o.R, q.R, sizeof(o.R));
+            std::memcpy(o.tvec, q.t, sizeof(o.tvec));
+            pnp_rotation_to_rvec(q.R, o.rvec);
         }
         o.tracked = rec[s].tracked, o.keyframe_required = rec[s].required;
         o.vote_best = rec[s].vote_best, o.vote_best_count = rec[s].vote_best_count;
@@ -579,21 +354,21 @@ int window_run(mslam_hip_ctx* c, const char* who, const WindowSource& w, const W
     {
         p.out[first].keyframe_added = 1;
         p.out[first].n_entry = tr.n_entry, p.out[first].n_inherited = tr.n_inherited;
-        r->n_upper[(size_t)new_slot] = tr.n_entry;
+        slots.commit(c, tr.n_entry);
     }
     else
-        release();
+        slots.rollback(c, false);
     if(added && (p.entry_src || p.entry_kp))
     {
         if(tr.n_entry > p.entry_capacity)
-            return reloc_fail(c, MSLAM_HIP_E_CAPACITY, me + ": the new entry has more landmarks than entry_capacity");
+            return fail(c, MSLAM_HIP_E_CAPACITY, me + ": the new entry has more landmarks than entry_capacity");
         if(p.entry_src)
             std::memcpy(p.entry_src, h_src, (size_t)tr.n_entry * 4);
         if(p.entry_kp)
             std::memcpy(p.entry_kp, h_src + K, (size_t)tr.n_entry * 4);
     }
     if(!p.out[0].tracked)
-        return reloc_fail(c, MSLAM_HIP_E_NO_MODEL, me + ": frame 0 has fewer than min_matched_points correspondences, or no model");
+        return fail(c, MSLAM_HIP_E_NO_MODEL, me + ": frame 0 has fewer than min_matched_points correspondences, or no model");
     return MSLAM_HIP_OK;
 }
 
@@ -605,8 +380,8 @@ int window_check(mslam_hip_ctx* c, const char* who, int S, double fx, double fy,
     if(S < 1 || S > kWindowMax || n_vote < 0 || n_vote > kRelocMaxCand || (n_vote > 0 && !vote_ids) || ref_vote_pos < -1 ||
        ref_vote_pos >= n_vote || iterations < 1 || iterations > 4096 || !(reprojection_error > 0) || !(fx != 0.0) ||
        !(fy != 0.0) || (use_guess && (!rvec || !tvec)) || !(z_max == z_max) || ((entry_src || entry_kp) && entry_capacity < 0))
-        return reloc_fail(c, MSLAM_HIP_E_INVALID,
-                          std::string(who) + ": bad argument (1..256 frames, at most 64 vote ids, ref_vote_pos in [-1, n_vote), 1..4096 iterations)");
+        return fail(c, MSLAM_HIP_E_INVALID,
+                    std::string(who) + ": bad argument (1..256 frames, at most 64 vote ids, ref_vote_pos in [-1, n_vote), 1..4096 iterations)");
     return MSLAM_HIP_OK;
 }
 
@@ -629,7 +404,7 @@ int mslam_hip_track_window(mslam_hip_ctx* c, const uint8_t* desc, const float* x
     if(first_event)
         *first_event = 0;
     if(!out || !first_event || !n || !depth || width <= 0 || height <= 0 || stride < 0 || (stride > 0 && (!desc || !xy)))
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track_window: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "track_window: bad argument");
     rc = window_check(c, who, S, fx, fy, vote_ids, n_vote, ref_vote_pos, iterations, reprojection_error, use_extrinsic_guess, rvec, tvec,
                       z_max, entry_src, entry_kp, entry_capacity);
     if(rc)
@@ -638,12 +413,12 @@ int mslam_hip_track_window(mslam_hip_ctx* c, const uint8_t* desc, const float* x
     for(int s = 0; s < S; ++s)
     {
         if(n[s] < 0 || n[s] > stride)
-            return reloc_fail(c, MSLAM_HIP_E_INVALID, "track_window: a frame's keypoint count is negative or exceeds stride");
+            return fail(c, MSLAM_HIP_E_INVALID, "track_window: a frame's keypoint count is negative or exceeds stride");
         n_max = std::max(n_max, n[s]);
     }
     if(n_max > c->p.max_keypoints)
-        return reloc_fail(c, MSLAM_HIP_E_CAPACITY,
-                          "track_window: a frame has more keypoints than the context's max_keypoints (a store entry's capacity)");
+        return fail(c, MSLAM_HIP_E_CAPACITY,
+                    "track_window: a frame has more keypoints than the context's max_keypoints (a store entry's capacity)");
     WindowSource w{};
     w.desc = desc, w.xy = xy, w.n = n, w.depth = depth, w.factor = factor;
     w.stride = stride, w.S = S, w.width = width, w.height = height, w.cap_from = n_max;
@@ -667,15 +442,15 @@ int mslam_hip_track_window_dev(mslam_hip_ctx* c, int first_frame, int n_frames, 
     if(first_event)
         *first_event = 0;
     if(!out || !first_event)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: bad argument");
+        return fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: bad argument");
     rc = window_check(c, who, n_frames, fx, fy, vote_ids, n_vote, ref_vote_pos, iterations, reprojection_error, use_extrinsic_guess, rvec,
                       tvec, z_max, entry_src, entry_kp, entry_capacity);
     if(rc)
         return rc;
     if(first_frame < 0 || first_frame + n_frames > c->n_last)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: no such frames in the last detect batch");
+        return fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: no such frames in the last detect batch");
     if(!c->d_xyz || c->points_seq != c->detect_seq)
-        return reloc_fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: the last detect batch has not been back-projected");
+        return fail(c, MSLAM_HIP_E_INVALID, "track_window_dev: the last detect batch has not been back-projected");
     const size_t K = (size_t)c->p.max_keypoints, f = (size_t)first_frame;
     WindowSource w{};
     // frame f of the batch: descriptors / coordinates / count in output slot f + 1, points in row f of the back-projection

@@ -1,6 +1,7 @@
-// reloc.hpp — what k_reloc.hip (keyframe store, mslam_hip_relocalize) shares with k_track.hip (mslam_hip_track,
-// mslam_hip_kf_visible): the store's state, the one-query-against-N-keyframes sequence with two places where a caller can
-// enqueue work of its own, and the launcher of k_backproject.
+// reloc.hpp — what the files on the keyframe store share (k_reloc.hip: the store and mslam_hip_relocalize; k_track.hip,
+// k_track_window.hip, k_localmap.hip): the store's state and scratch, the match-to-PnP sequence over R rows that relocalize
+// (one query, R entries) and a tracking window (R frames, one entry) both enqueue, relocalize's body with two places where a
+// caller can enqueue work of its own, and the launchers of k_backproject.
 #pragma once
 #include "context.hpp"
 
@@ -13,12 +14,36 @@ namespace mslam
 
 constexpr int kRelocMaxCand = 64; // the BoW query's own limit (mslam_hip_bow_db_query callers ask for at most 64)
 
-// what k_reloc_rank leaves per candidate in the mapped result block
+// what one row of the sequence comes to, in the mapped result block: per candidate (k_reloc_rank) or per frame (k_tw_scan)
 struct RelocRes
 {
     int32_t n_matches, n_corr, n_inliers, status;
     double R[9], t[3];
 };
+
+// the PnP kernel's record of a row (16 doubles: R, t, inliers, -, status, -) and the row's counts as a RelocRes; inliers,
+// R and t are zero when there is no model
+__device__ __forceinline__ RelocRes reloc_record(const double* __restrict__ o, int32_t n_matches, int32_t n_corr)
+{
+    RelocRes r{};
+    r.n_matches = n_matches;
+    r.n_corr = n_corr;
+    r.status = o[14] == 1.0 ? 1 : 0;
+    r.n_inliers = r.status ? (int32_t)o[12] : 0;
+    for(int j = 0; j < 9; ++j)
+        r.R[j] = r.status ? o[j] : 0.0;
+    for(int j = 0; j < 3; ++j)
+        r.t[j] = r.status ? o[9 + j] : 0.0;
+    return r;
+}
+
+__device__ __forceinline__ void copy_desc(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
+{
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = s[0];
+    d[1] = s[1];
+}
 
 struct RelocState
 {
@@ -32,18 +57,15 @@ struct RelocState
     std::unordered_map<int, int> slot_of; // id -> slot
     std::vector<int> free_slots;
     std::vector<int> n_upper;             // per slot: an upper bound of n the host knows (exact for host adds, K for device lifts)
-    // ---- scratch of mslam_hip_relocalize, grown on demand
-    uint8_t* h_up = nullptr;  // page-locked staging of the upload: [desc | xy | valid | slots]
+    // ---- scratch of every call that ends in a synchronisation (relocalize, track, track_window, kf_visible), grown on
+    // demand by reloc_scratch; the layout inside each block is the call's own
+    uint8_t* h_up = nullptr;  // page-locked staging of the call's one upload
     uint8_t* d_up = nullptr;
     size_t up_bytes = 0;
-    uint8_t* d_arena = nullptr; // every per-candidate array of one call
+    uint8_t* d_arena = nullptr; // every device array of one call
     size_t arena_bytes = 0;
-    uint8_t *h_res = nullptr, *d_h_res = nullptr; // page-locked, device-mapped: [best | RelocRes[64] | pair_from | pair_to | inliers]
+    uint8_t *h_res = nullptr, *d_h_res = nullptr; // page-locked, device-mapped: what the host reads after the synchronisation
     size_t res_bytes = 0;
-    // ---- scratch of mslam_hip_kf_visible: [slots 64 x i32 | pose record 16 x f64 | counts 64 x i32] on the device, the
-    // result [best, best count, pad | counts 64 x i32] page-locked and device-mapped
-    uint8_t* d_vote = nullptr;
-    uint8_t *h_vote = nullptr, *d_h_vote = nullptr;
     // ---- scratch of mslam_hip_kf_union / mslam_hip_kf_covisible (k_localmap.hip), grown on demand: the hash table
     // ({u64 key, u64 val} buckets), the per-block arrays [win masks | counts | offsets], and the mapped result
     // [needed count, pad | covisibility counts 64 x i32]
@@ -68,19 +90,61 @@ struct KfPose
     double R[9], t[3], z_max;
 };
 
-// Device addresses of one relocalize sequence, for the hooks below.  Rows of the per-candidate arrays are S entries apart.
+// One match-to-PnP sequence over `rows` rows: gather the entries' descriptors, knn-2, ratio test, matches ->
+// correspondences, batched PnP (problem r samples with seed + r, one guess for all).  Row r matches its keypoints ("from")
+// against the landmarks of its store entry ("to").  Addressed as MatchArgs is: a stride of 0 means all rows share the one
+// block, a null count array the fixed count.
+struct SeqArgs
+{
+    int rows = 0;
+    size_t S = 0; // row stride of every per-row array: seq_row_stride of the largest entry
+    // from: device pointers, row r at + r * from_stride keypoints
+    const uint8_t* desc = nullptr; // x 32
+    const float* xy = nullptr;     // x 2
+    const uint8_t* valid = nullptr; // x 1, or nullptr: every keypoint counts
+    size_t from_stride = 0;
+    const int32_t* from_cnt = nullptr; // [rows], clamped to from_stride
+    int n_from_fixed = 0, cap_from = 0; // cap_from: an upper bound of every row's count
+    // to: device list of store slots, one per row or (one_slot) one for all rows
+    const int32_t* slots = nullptr;
+    bool one_slot = false;
+    // PnP
+    double fx = 0, fy = 0, cx = 0, cy = 0;
+    int use_guess = 0;
+    const double *rvec = nullptr, *tvec = nullptr; // host, read when use_guess
+    int iterations = 0;
+    double reprojection_error = 0;
+    unsigned long long seed = 0;
+};
+
+// what the sequence leaves on the device; rows of the per-row arrays are S entries apart
+struct SeqDev
+{
+    const int32_t *g_cnt = nullptr, *mfrom = nullptr, *mto = nullptr, *mcount = nullptr, *ncorr = nullptr;
+    const uint8_t* mask = nullptr;   // consensus masks, correspondence order
+    const double* pnp_out = nullptr; // 16 doubles per row: R, t, inliers, -, status, -
+    int S = 0;
+};
+
+inline size_t seq_row_stride(int n_upper) // an entry of at most n_upper landmarks, in whole 256-row blocks
+{
+    return al256((size_t)(n_upper > 1 ? n_upper : 1));
+}
+size_t seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot); // a multiple of 256: a caller's own arrays follow
+// enqueues the sequence on c->stream, its arrays carved from `arena`; sets c->last_match_kernel
+int seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* arena, SeqDev* out);
+
+// Device addresses of one relocalize call, for the hooks below.
 struct RelocDev
 {
     const uint8_t* desc = nullptr; // the uploaded query: n x 32
     const float* xy = nullptr;     // n x 2
-    int n = 0, S = 0;
+    int n = 0;
     const uint8_t* valid = nullptr; // the mask k_reloc_corr applies; after_upload may point it at a mask it produces
     const uint8_t* extra_up = nullptr; // the hook's own upload block, on the device
     uint8_t* extra_arena = nullptr;    // the hook's own device scratch
     uint8_t *extra_res = nullptr, *h_extra_res = nullptr; // the hook's own part of the mapped result block (device / host address)
-    const int32_t *g_cnt = nullptr, *mfrom = nullptr, *mto = nullptr, *mcount = nullptr, *ncorr = nullptr;
-    const uint8_t* mask = nullptr;    // consensus masks, correspondence order
-    const double* pnp_out = nullptr;  // 16 doubles per candidate: R, t, inliers, -, status, -
+    SeqDev seq;                     // filled in when the sequence is enqueued: before_sync reads it
 };
 
 // A caller's own work inside the sequence: after_upload runs when the upload is enqueued (before the gather and the
@@ -103,10 +167,34 @@ int reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, const uint
               mslam_hip_reloc_candidate* out, int* best, int32_t* pair_from, int32_t* pair_to, uint8_t* inliers, int pair_stride,
               const RelocHooks* hooks);
 int reloc_enter(mslam_hip_ctx* c);
-int reloc_fail(mslam_hip_ctx* c, int code, const std::string& msg);
+// at least `up` bytes of h_up / d_up, `arena` of d_arena, `res` of h_res; growing waits for the stream first
+int reloc_scratch(mslam_hip_ctx* c, size_t up, size_t arena, size_t res);
 int store_reserve(mslam_hip_ctx* c, int want);
 int store_slot_for(mslam_hip_ctx* c, int id, int* slot);
 int64_t store_next_lid_base(mslam_hip_ctx* c); // advances the creation serial: call once per entry made, after store_slot_for
+
+// The store slots of one tracking call (mslam_hip_track, mslam_hip_track_window[_dev]).  resolve() looks the reference and the vote list up and rejects a
+// new_id that names one of them; reserve() then takes new_id's slot (its own when the id exists: the entry is replaced)
+// and the landmark id base — on the host, before anything is enqueued; slots keep their numbers, and the serial advances
+// whether or not the call makes the keyframe.  Every path after reserve() ends in commit() or rollback().
+struct TrackSlots
+{
+    int ref_slot = -1, new_slot = -1; // new_slot = -1: the call makes no keyframe (new_id < 0)
+    int64_t lid_base = 0;
+    int32_t vote_slots[kRelocMaxCand] = {};
+    int new_id = -1;
+    bool existed = false; // new_id named an entry before the call
+
+    int resolve(mslam_hip_ctx* c, const char* who, int ref_id, const int32_t* vote_ids, int n_vote, int new_id_);
+    int reserve(mslam_hip_ctx* c);
+    // the keyframe was made: the host knows its size
+    void commit(mslam_hip_ctx* c, int n_entry);
+    // no keyframe: the slot goes back to the free list unless its id existed before.  enqueued_work_may_still_run: wait for
+    // the stream first (keeping c->err) — what was enqueued may write the slot, and of an entry that may have been
+    // replaced all the host still knows is the capacity (also passed after a synchronisation that found impossible
+    // counts: the wait is then idle, the size just as unknown)
+    void rollback(mslam_hip_ctx* c, bool enqueued_work_may_still_run);
+};
 
 // k_points.hip: k_backproject on one frame of n keypoints, device pointers, enqueued on `s`
 void launch_backproject(hipStream_t s, const uint16_t* d_depth, int width, int height, float factor, double fx, double fy, double cx,

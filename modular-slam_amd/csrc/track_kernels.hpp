@@ -91,14 +91,6 @@ struct KeyframeArgs
     int32_t *h_src, *h_kp;
 };
 
-__device__ __forceinline__ void copy_desc(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
-{
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    d[0] = s[0];
-    d[1] = s[1];
-}
-
 // One workgroup builds the new keyframe's entry in its store slot.  Part A: the inlier correspondences in correspondence
 // order, with the reference entry's world points and landmark ids copied bit for bit.  Part B: every keypoint no correspondence used, with a
 // valid depth and z <= z_max, in keypoint order, lifted with world = R^T (p - t).  Ordered ballot / prefix compaction as

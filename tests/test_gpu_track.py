@@ -345,3 +345,68 @@ def test_track_leaves_its_neighbours_results_alone(pkg, sequence):
     ref = rr.relocalize(q["desc"], q["xy"], store, [0, 1, 2], seed=3)
     assert ref["best"] == after[1]["best"] and [x["n_inliers"] for x in ref["candidates"]] == [x["n_inliers"] for x in after[1]["candidates"]]
     c.close()
+
+
+def _bits_equal(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_bits_equal(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return len(a) == len(b) and all(_bits_equal(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    if isinstance(a, float):
+        return np.float64(a).tobytes() == np.float64(b).tobytes()
+    return a == b
+
+
+@KINDS
+def test_calls_sharing_the_scratch_equal_a_fresh_context(pkg, sequence, kind):
+    """kf_visible, relocalize, track and track_window stage their upload, their device arrays and their results in the same
+    three blocks of the context.  One context makes five such calls in a row — the blocks grow between them, and the row
+    stride of the per-row arrays goes from 256 (relocalize on entries of 200 and 250 landmarks) to 512 (the full entry 0)
+    — and every result equals, field for field and bit for bit, what a fresh context holding the same store returns for
+    the same call as its first."""
+    seq, rows, trk = sequence
+    rng = np.random.default_rng(5)
+    fr, q, win = seq["frames"][6], seq["frames"][9], seq["frames"][6:8]
+    R, t = rows[5]["R"], rows[5]["t"]
+    store = {0: trk.store[0], 1: tuple(x[:200] for x in trk.store[1]), 2: tuple(x[:250] for x in trk.store[2])}
+    assert 256 < len(store[0][0]) <= 512 and 290 <= len(fr["desc"]) and len(q["desc"]) > 256
+    for i, n in enumerate([1, 255, 256, 257] + [int(v) for v in rng.integers(40, 301, 57)]):
+        store[100 + i] = (rng.integers(0, 256, (n, 32), dtype=np.uint8),
+                          np.stack([rng.uniform(-4, 4, n), rng.uniform(-3, 3, n), rng.uniform(-1, 6, n)], 1))
+    ids64 = [0, 1, 60] + [100 + i for i in range(61)]
+    kw = dict(seed=6, rvec=_rvec(R), tvec=t, new_keyframe_min_landmarks=100)
+
+    def track(c):
+        got = c.track(fr["desc"], fr["xy"], fr["depth"], 0, [0, 1, 2], 60, with_pairs=True, with_entry=True, **kw)
+        assert got["tracked"] and got["keyframe_added"]
+        return got, c.kf_read(60)
+
+    def window(c):
+        recs, first = c.track_window([x["desc"] for x in win], [x["xy"] for x in win], [x["depth"] for x in win], 0, [0, 1, 2], 61, 0,
+                                     focal=CAM[:2], principal=CAM[2:], with_entry=True, **kw)
+        assert first == 0 and recs[0]["keyframe_added"] and recs[1]["tracked"]
+        return recs, first, c.kf_read(61)
+
+    calls = [("kf_visible, 3 ids", lambda c: c.kf_visible([0, 1, 2], R, t, CAM[:2], CAM[2:])),
+             ("relocalize", lambda c: c.relocalize(q["desc"], q["xy"], [1, 2], seed=3, with_pairs=True)),
+             ("track", track),
+             ("kf_visible, 64 ids", lambda c: c.kf_visible(ids64, R, t, CAM[:2], CAM[2:])),
+             ("track_window", window)]
+    c = _ctx(pkg, kind)
+    _fill(c, store)
+    for what, call in calls:
+        fresh = _ctx(pkg, kind)
+        _fill(fresh, store)
+        want = call(fresh)
+        fresh.close()
+        got = call(c)
+        assert _bits_equal(got, want), what
+        if what == "relocalize":
+            assert max(x["n_inliers"] for x in got["candidates"]) >= 60 and len(got["pairs"][1][0]) > 60
+        if what == "track":
+            store[60] = got[1]                     # the keyframe the step made: part of the store from here on
+        if what == "kf_visible, 64 ids":
+            assert got[0][:3].min() > 0 and np.count_nonzero(got[0]) > 32
+    c.close()
