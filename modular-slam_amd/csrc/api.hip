@@ -312,12 +312,6 @@ static void exact_axis(int ssize, int dsize, std::vector<int32_t>& ofs, std::vec
     }
 }
 
-template <typename T>
-static hipError_t dmalloc(T*& p, size_t n)
-{
-    return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T));
-}
-
 // ---- C ABI ------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -351,22 +345,6 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
         return;
     if(c->stream)
         (void)hipStreamSynchronize(c->stream);
-    void* bufs[] = {c->d_cells,   c->d_rs_ofs, c->d_rs_coef, c->d_rs_qt, c->d_ratio_thr, c->d_orient_w, c->d_stage,  c->d_pyr,
-                    c->d_blur,    c->d_cv_ofs, c->d_cv_coef, c->d_cell_cnt, c->d_cell_kp, c->quad.cand, c->quad.cand_cnt, c->quad.sel,
-                    c->quad.sel_cnt, c->quad.kp_node, c->quad.nodes_a, c->quad.nodes_b, c->quad.ncnt_a, c->quad.ncnt_b,
-                    c->quad.child_cnt, c->quad.ninfo, c->quad.best, c->d_flags, c->d_hm_from, c->d_hm_out, c->d_hm_partial,
-                    c->d_xyz, c->d_valid, c->d_pnp_obj, c->d_pnp_img, c->d_pnp_n, c->d_pnp_counts, c->d_pnp_hyp, c->d_pnp_out,
-                    c->d_pnp_mask, c->d_blur_waves, c->d_pnp1_obj, c->d_pnp1_img, c->d_pnp1_hyp, c->d_pnp1_out,
-                    c->d_pnp1_counts, c->d_pnp1_mask, c->d_mse1};
-    for(void* b : bufs)
-        if(b)
-            (void)hipFree(b);
-    if(c->h_out)
-        (void)hipHostFree(c->h_out);
-    if(c->h_hm)
-        (void)hipHostFree(c->h_hm);
-    if(c->h_stage)
-        (void)hipHostFree(c->h_stage);
     if(c->match_graph)
         (void)hipGraphExecDestroy(c->match_graph);
     for(auto& e : c->detect_graph)
@@ -376,10 +354,6 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
         (void)hipStreamSynchronize(c->stream_m);
     for(auto& o : c->out)
     {
-        void* ob[] = {o.xy, o.desc, o.octave, o.angle, o.response, o.count, o.idx0, o.idx1, o.dist0, o.dist1, o.mfrom, o.mto, o.mcount};
-        for(void* b : ob)
-            if(b)
-                (void)hipFree(b);
         if(o.ev_detect)
             (void)hipEventDestroy(o.ev_detect);
         if(o.ev_match)
@@ -422,16 +396,7 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
         reloc_destroy(c->reloc);
     if(c->own_stream && c->stream)
         (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-static void select_set(mslam_hip_ctx* c, int k)
-{
-    const mslam_out_set& o = c->out[k];
-    c->cur = k;
-    c->d_xy = o.xy, c->d_desc = o.desc, c->d_octave = o.octave, c->d_angle = o.angle, c->d_response = o.response;
-    c->d_count = o.count, c->d_idx0 = o.idx0, c->d_idx1 = o.idx1, c->d_dist0 = o.dist0, c->d_dist1 = o.dist1;
-    c->d_mfrom = o.mfrom, c->d_mto = o.mto, c->d_mcount = o.mcount;
+    delete c; // every device and page-locked block goes with its owner (devmem.hpp)
 }
 
 // Quad table of one level for k_resize_col (both interpolation flavours): every 4 destination pixels share one aligned
@@ -583,19 +548,19 @@ static int create_impl(mslam_hip_ctx* c)
             for(int l = 1; l < p.n_levels; ++l)
                 build_quad_table(ofs, coef, c->cv_x[l], g.lv[l].w, p.max_batch, qt, c->rs_q[l], c->rs_need[l]);
             qt.push_back(make_uint4(0, 0, 0, 0));
-            MSLAM_CHK(c, dmalloc(c->d_rs_qt, qt.size()));
+            MSLAM_CHK(c, c->d_rs_qt.alloc(qt.size()));
             MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
         }
         ofs.push_back(0);
         coef.push_back(0);
-        MSLAM_CHK(c, dmalloc(c->d_cv_ofs, ofs.size()));
-        MSLAM_CHK(c, dmalloc(c->d_cv_coef, coef.size()));
+        MSLAM_CHK(c, c->d_cv_ofs.alloc(ofs.size()));
+        MSLAM_CHK(c, c->d_cv_coef.alloc(coef.size()));
         MSLAM_CHK(c, hipMemcpy(c->d_cv_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
         MSLAM_CHK(c, hipMemcpy(c->d_cv_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
     }
     if(has_detector && !cv_mode)
     {
-    MSLAM_CHK(c, dmalloc(c->d_cells, c->cells.size()));
+    MSLAM_CHK(c, c->d_cells.alloc(c->cells.size()));
     MSLAM_CHK(c, hipMemcpy(c->d_cells, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
     {
         std::vector<int32_t> ofs;
@@ -616,29 +581,28 @@ static int create_impl(mslam_hip_ctx* c)
         for(int l = 1; l < p.n_levels; ++l)
             build_quad_table(ofs, coef, c->rs_x[l], g.lv[l].w, p.max_batch, qt, c->rs_q[l], c->rs_need[l]);
         qt.push_back(make_uint4(0, 0, 0, 0));
-        MSLAM_CHK(c, dmalloc(c->d_rs_qt, qt.size()));
+        MSLAM_CHK(c, c->d_rs_qt.alloc(qt.size()));
         MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
         ofs.push_back(0);
         coef.push_back(0);
-        MSLAM_CHK(c, dmalloc(c->d_rs_ofs, ofs.size()));
-        MSLAM_CHK(c, dmalloc(c->d_rs_coef, coef.size()));
+        MSLAM_CHK(c, c->d_rs_ofs.alloc(ofs.size()));
+        MSLAM_CHK(c, c->d_rs_coef.alloc(coef.size()));
         MSLAM_CHK(c, hipMemcpy(c->d_rs_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice));
         MSLAM_CHK(c, hipMemcpy(c->d_rs_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
     }
     } // has_detector
-    MSLAM_CHK(c, dmalloc(c->d_ratio_thr, 257));
+    MSLAM_CHK(c, c->d_ratio_thr.alloc(257));
     {
         uint32_t w[2 * 256];
         build_orient_weights(umax, w);
-        MSLAM_CHK(c, dmalloc(c->d_orient_w, 2 * 256));
+        MSLAM_CHK(c, c->d_orient_w.alloc(2 * 256));
         MSLAM_CHK(c, hipMemcpy(c->d_orient_w, w, sizeof(w), hipMemcpyHostToDevice));
     }
 
     const size_t B = (size_t)p.max_batch, L = (size_t)p.n_levels, cap = (size_t)p.max_candidates;
     const size_t K = (size_t)p.max_keypoints;
-    MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), 16 + K * 52, hipHostMallocMapped));
-    MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_out), c->h_out, 0));
-    MSLAM_CHK(c, dmalloc(c->d_flags, 1));
+    MSLAM_CHK(c, c->h_out.alloc(16 + K * 52));
+    MSLAM_CHK(c, c->d_flags.alloc(1));
     MSLAM_CHK(c, hipMemset(c->d_flags, 0, 4));
     if(has_detector)
     {
@@ -654,10 +618,10 @@ static int create_impl(mslam_hip_ctx* c)
             return fail(c, MSLAM_HIP_E_RUNTIME, "v_pk_minimum3_f16 / v_pk_maximum3_f16 do not preserve f16 denormals in this build "
                                                 "(the FAST score kernels need .amdhsa_float_denorm_mode_16_64 3): refusing to run");
     }
-    MSLAM_CHK(c, dmalloc(c->d_stage, (size_t)p.width * p.height * 3));
+    MSLAM_CHK(c, c->d_stage.alloc((size_t)p.width * p.height * 3));
     // + 64: the patch loads of k_describe may run a few bytes past the last row of the last frame
-    MSLAM_CHK(c, dmalloc(c->d_pyr, B * g.slab + 256));
-    MSLAM_CHK(c, dmalloc(c->d_blur, B * g.slab + 256));
+    MSLAM_CHK(c, c->d_pyr.alloc(B * g.slab + 256));
+    MSLAM_CHK(c, c->d_blur.alloc(B * g.slab + 256));
     {
         // k_level.hip (fused gray + blur): needs dword columns, 32-bit batch offsets and the exact float index split
         {
@@ -698,25 +662,28 @@ static int create_impl(mslam_hip_ctx* c)
         c->blur_wpf = (int)bw.size();
         if(!bw.empty())
         {
-            MSLAM_CHK(c, dmalloc(c->d_blur_waves, bw.size()));
+            MSLAM_CHK(c, c->d_blur_waves.alloc(bw.size()));
             MSLAM_CHK(c, hipMemcpy(c->d_blur_waves, bw.data(), bw.size() * sizeof(BlurWave), hipMemcpyHostToDevice));
         }
     }
-    MSLAM_CHK(c, dmalloc(c->d_cell_cnt, B * g.n_cells));
-    MSLAM_CHK(c, dmalloc(c->d_cell_kp, B * g.n_cells * (size_t)kCellCap));
+    MSLAM_CHK(c, c->d_cell_cnt.alloc(B * g.n_cells));
+    MSLAM_CHK(c, c->d_cell_kp.alloc(B * g.n_cells * (size_t)kCellCap));
     QuadArgs& q = c->quad;
-    MSLAM_CHK(c, dmalloc(q.cand, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.cand_cnt, B * L));
-    MSLAM_CHK(c, dmalloc(q.sel, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.sel_cnt, B * L));
-    MSLAM_CHK(c, dmalloc(q.kp_node, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.nodes_a, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.nodes_b, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.ncnt_a, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.ncnt_b, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.child_cnt, B * L * cap * 4));
-    MSLAM_CHK(c, dmalloc(q.ninfo, B * L * cap));
-    MSLAM_CHK(c, dmalloc(q.best, B * L * cap));
+    MSLAM_CHK(c, c->q_cand.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_cand_cnt.alloc(B * L));
+    MSLAM_CHK(c, c->q_sel.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_sel_cnt.alloc(B * L));
+    MSLAM_CHK(c, c->q_kp_node.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_nodes_a.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_nodes_b.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_ncnt_a.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_ncnt_b.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_child_cnt.alloc(B * L * cap * 4));
+    MSLAM_CHK(c, c->q_ninfo.alloc(B * L * cap));
+    MSLAM_CHK(c, c->q_best.alloc(B * L * cap));
+    q.cand = c->q_cand, q.cand_cnt = c->q_cand_cnt, q.sel = c->q_sel, q.sel_cnt = c->q_sel_cnt, q.kp_node = c->q_kp_node;
+    q.nodes_a = c->q_nodes_a, q.nodes_b = c->q_nodes_b, q.ncnt_a = c->q_ncnt_a, q.ncnt_b = c->q_ncnt_b;
+    q.child_cnt = c->q_child_cnt, q.ninfo = c->q_ninfo, q.best = c->q_best;
     q.cell_cnt = c->d_cell_cnt;
     q.cell_kp = c->d_cell_kp;
     q.flags = c->d_flags;
@@ -726,20 +693,20 @@ static int create_impl(mslam_hip_ctx* c)
 
     for(auto& o : c->out)
     {
-        MSLAM_CHK(c, dmalloc(o.xy, (B + 1) * K * 2));
-        MSLAM_CHK(c, dmalloc(o.desc, (B + 1) * K * 32));
-        MSLAM_CHK(c, dmalloc(o.octave, (B + 1) * K));
-        MSLAM_CHK(c, dmalloc(o.angle, (B + 1) * K));
-        MSLAM_CHK(c, dmalloc(o.response, (B + 1) * K));
-        MSLAM_CHK(c, dmalloc(o.count, B + 1));
+        MSLAM_CHK(c, o.xy.alloc((B + 1) * K * 2));
+        MSLAM_CHK(c, o.desc.alloc((B + 1) * K * 32));
+        MSLAM_CHK(c, o.octave.alloc((B + 1) * K));
+        MSLAM_CHK(c, o.angle.alloc((B + 1) * K));
+        MSLAM_CHK(c, o.response.alloc((B + 1) * K));
+        MSLAM_CHK(c, o.count.alloc(B + 1));
         MSLAM_CHK(c, hipMemset(o.count, 0, (B + 1) * 4));
-        MSLAM_CHK(c, dmalloc(o.idx0, B * K));
-        MSLAM_CHK(c, dmalloc(o.idx1, B * K));
-        MSLAM_CHK(c, dmalloc(o.dist0, B * K));
-        MSLAM_CHK(c, dmalloc(o.dist1, B * K));
-        MSLAM_CHK(c, dmalloc(o.mfrom, B * K));
-        MSLAM_CHK(c, dmalloc(o.mto, B * K));
-        MSLAM_CHK(c, dmalloc(o.mcount, B));
+        MSLAM_CHK(c, o.idx0.alloc(B * K));
+        MSLAM_CHK(c, o.idx1.alloc(B * K));
+        MSLAM_CHK(c, o.dist0.alloc(B * K));
+        MSLAM_CHK(c, o.dist1.alloc(B * K));
+        MSLAM_CHK(c, o.mfrom.alloc(B * K));
+        MSLAM_CHK(c, o.mto.alloc(B * K));
+        MSLAM_CHK(c, o.mcount.alloc(B));
         MSLAM_CHK(c, hipMemset(o.mcount, 0, B * 4));
         MSLAM_CHK(c, hipEventCreateWithFlags(&o.ev_detect, hipEventDisableTiming));
         MSLAM_CHK(c, hipEventCreateWithFlags(&o.ev_match, hipEventDisableTiming));
@@ -764,7 +731,7 @@ static int create_impl(mslam_hip_ctx* c)
         const char* m = getenv("MSLAM_HIP_MATCHER");
         c->matcher_kind = (m && std::strcmp(m, "popcount") == 0) ? MSLAM_HIP_MATCHER_POPCOUNT : MSLAM_HIP_MATCHER_AUTO;
     }
-    select_set(c, 0);
+    c->cur = 0;
     MSLAM_CHK(c, hipDeviceSynchronize());
     return MSLAM_HIP_OK;
 }
@@ -1135,12 +1102,12 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
             a.orient_w = c->d_orient_w;
             a.cand_cap = c->p.max_candidates;
             a.max_kp = c->p.max_keypoints;
-            a.xy = c->d_xy + K * 2;
-            a.desc = c->d_desc + K * 32;
-            a.octave = c->d_octave + K;
-            a.angle = c->d_angle + K;
-            a.response = c->d_response + K;
-            a.count = c->d_count + 1;
+            a.xy = cur_out(c).xy + K * 2;
+            a.desc = cur_out(c).desc + K * 32;
+            a.octave = cur_out(c).octave + K;
+            a.angle = cur_out(c).angle + K;
+            a.response = cur_out(c).response + K;
+            a.count = cur_out(c).count + 1;
             a.flags = c->d_flags;
             if(cv_mode)
             {
@@ -1148,7 +1115,7 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
                 a.cv_mode = 1;
             }
             if(c->mirror_results && n_frames == 1)
-                a.h_mirror = c->d_h_out;
+                a.h_mirror = c->h_out.dev();
             launch_describe(g, a, f0, nf, cs);
         }
         if(n_chunks > 1)
@@ -1182,12 +1149,12 @@ static int detect_prologue(mslam_hip_ctx* c)
         // carry the last frame of the previous batch into slot 0 (predecessor of the new frame 0)
         const size_t last = (size_t)c->n_last;
         // (one small kernel: the count and exactly that many descriptors, instead of two copy launches of the capacity)
-        hipLaunchKernelGGL(k_carry_prev, dim3(16), dim3(256), 0, s, reinterpret_cast<uint4*>(c->out[nxt].desc),
+        hipLaunchKernelGGL(k_carry_prev, dim3(16), dim3(256), 0, s, reinterpret_cast<uint4*>(c->out[nxt].desc.get()),
                            reinterpret_cast<const uint4*>(c->out[prev].desc + last * K * 32), c->out[nxt].count,
                            c->out[prev].count + last, (int)K);
         MSLAM_CHK(c, hipGetLastError());
         c->have_prev = true;
-        select_set(c, nxt);
+        c->cur = nxt;
     }
     return MSLAM_HIP_OK;
 }
@@ -1218,15 +1185,15 @@ int mslam_hip_get_batch_view(mslam_hip_ctx* c, mslam_hip_batch_view* v)
     const size_t K = (size_t)c->p.max_keypoints;
     v->n_frames = c->n_last;
     v->capacity = c->p.max_keypoints;
-    v->xy = c->d_xy + K * 2;
-    v->desc = c->d_desc + K * 32;
-    v->octave = c->d_octave + K;
-    v->angle = c->d_angle + K;
-    v->response = c->d_response + K;
-    v->count = c->d_count + 1;
-    v->match_from = c->d_mfrom;
-    v->match_to = c->d_mto;
-    v->match_count = c->d_mcount;
+    v->xy = cur_out(c).xy + K * 2;
+    v->desc = cur_out(c).desc + K * 32;
+    v->octave = cur_out(c).octave + K;
+    v->angle = cur_out(c).angle + K;
+    v->response = cur_out(c).response + K;
+    v->count = cur_out(c).count + 1;
+    v->match_from = cur_out(c).mfrom;
+    v->match_to = cur_out(c).mto;
+    v->match_count = cur_out(c).mcount;
     return MSLAM_HIP_OK;
 }
 
@@ -1263,8 +1230,9 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
     auto enqueue_results = [&]() -> int {
         if(c->mirror_results)
             return MSLAM_HIP_OK;
-        hipLaunchKernelGGL(k_pack_results, dim3(32), dim3(256), 0, c->stream, c->d_xy + K * 2, c->d_desc + K * 32, c->d_octave + K,
-                           c->d_angle + K, c->d_response + K, c->d_count + 1, c->d_flags, c->d_h_out, (int)K);
+        const mslam_out_set& o = cur_out(c);
+        hipLaunchKernelGGL(k_pack_results, dim3(32), dim3(256), 0, c->stream, o.xy + K * 2, o.desc + K * 32, o.octave + K,
+                           o.angle + K, o.response + K, o.count + 1, c->d_flags, c->h_out.dev(), (int)K);
         MSLAM_CHK(c, hipGetLastError());
         return MSLAM_HIP_OK;
     };
@@ -1285,11 +1253,10 @@ int mslam_hip_detect(mslam_hip_ctx* c, const uint8_t* bgr, int width, int height
     {
         if(!c->h_stage)
         {
-            MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), (size_t)width * height * 3, hipHostMallocMapped));
-            MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_stage), c->h_stage, 0));
+            MSLAM_CHK(c, c->h_stage.alloc((size_t)width * height * 3));
         }
         std::memcpy(c->h_stage, bgr, (size_t)width * height * 3);
-        frame_src = c->d_h_stage;
+        frame_src = c->h_stage.dev();
     }
     else
         MSLAM_CHK(c, hipMemcpyAsync(c->d_stage, bgr, (size_t)width * height * 3, hipMemcpyHostToDevice, c->stream));
@@ -1401,23 +1368,23 @@ int mslam_hip_match_batch_dev(mslam_hip_ctx* c, double ratio, int chain_previous
     if(own)
         MSLAM_CHK(c, hipStreamWaitEvent(s, c->out[c->cur].ev_detect, 0));
     if(first == 1)
-        MSLAM_CHK(c, hipMemsetAsync(c->d_mcount, 0, 4, s));
+        MSLAM_CHK(c, hipMemsetAsync(cur_out(c).mcount, 0, 4, s));
     if(n_pairs > 0)
     {
         MatchArgs m{};
         // pair t: from = frame t (slot t+1), to = frame t-1 (slot t)
-        m.from_desc = c->d_desc + (size_t)(first + 1) * K * 32;
-        m.to_desc = c->d_desc + (size_t)first * K * 32;
+        m.from_desc = cur_out(c).desc + (size_t)(first + 1) * K * 32;
+        m.to_desc = cur_out(c).desc + (size_t)first * K * 32;
         m.from_stride = m.to_stride = (long long)K * 32;
-        m.from_cnt = c->d_count + first + 1;
-        m.to_cnt = c->d_count + first;
+        m.from_cnt = cur_out(c).count + first + 1;
+        m.to_cnt = cur_out(c).count + first;
         m.cap = c->p.max_keypoints;
         m.cap_from = c->p.max_keypoints;
         m.popcount_only = c->matcher_kind == MSLAM_HIP_MATCHER_POPCOUNT;
-        m.idx0 = c->d_idx0 + (size_t)first * K;
-        m.idx1 = c->d_idx1 + (size_t)first * K;
-        m.dist0 = c->d_dist0 + (size_t)first * K;
-        m.dist1 = c->d_dist1 + (size_t)first * K;
+        m.idx0 = cur_out(c).idx0 + (size_t)first * K;
+        m.idx1 = cur_out(c).idx1 + (size_t)first * K;
+        m.dist0 = cur_out(c).dist0 + (size_t)first * K;
+        m.dist1 = cur_out(c).dist1 + (size_t)first * K;
         {
             StageScope t(c, "match_knn2", s);
             c->last_match_kernel = launch_match_knn2(m, n_pairs, s);
@@ -1430,9 +1397,9 @@ int mslam_hip_match_batch_dev(mslam_hip_ctx* c, double ratio, int chain_previous
         r.to_cnt = m.to_cnt;
         r.cap = m.cap;
         r.thr = c->d_ratio_thr;
-        r.from_idx = c->d_mfrom + (size_t)first * K;
-        r.to_idx = c->d_mto + (size_t)first * K;
-        r.n_out = c->d_mcount + first;
+        r.from_idx = cur_out(c).mfrom + (size_t)first * K;
+        r.to_idx = cur_out(c).mto + (size_t)first * K;
+        r.n_out = cur_out(c).mcount + first;
         {
             StageScope t(c, "ratio_compact", s);
             launch_ratio_compact(r, n_pairs, s);
@@ -1453,37 +1420,23 @@ static int host_match_prepare(mslam_hip_ctx* c, const uint8_t* from_desc, int n_
     // device descriptors: ONE buffer [train rows | query rows], so that one copy fills both
     if(n_from > c->hm_from_cap || n_to > c->hm_to_cap)
     {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+        MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // what reads the old blocks has finished before they are freed
         const int from_cap = std::max(n_from, std::max(c->hm_from_cap, 2048)), to_cap = std::max(n_to, std::max(c->hm_to_cap, 2048));
-        if(c->d_hm_from)
-            (void)hipFree(c->d_hm_from);
-        if(c->d_hm_out)
-            (void)hipFree(c->d_hm_out);
-        if(c->h_hm)
-            (void)hipHostFree(c->h_hm);
-        c->d_hm_from = nullptr;
-        c->d_hm_to = nullptr;
-        c->d_hm_out = nullptr;
-        c->h_hm = nullptr;
-        c->d_h_hm = nullptr;
+        // until every block is there the capacities are 0: a failure below leaves a set the next call allocates afresh
         c->hm_from_cap = c->hm_to_cap = 0;
-        MSLAM_CHK(c, dmalloc(c->d_hm_from, (size_t)(from_cap + to_cap) * 32 + 16)); // (+ 16: the captured form's counts ride behind the rows)
-        MSLAM_CHK(c, dmalloc(c->d_hm_out, (size_t)to_cap * 6 + 4));
-        if(c->d_hm_partial)
-            (void)hipFree(c->d_hm_partial);
-        c->d_hm_partial = nullptr;
-        MSLAM_CHK(c, dmalloc(c->d_hm_partial, (size_t)kHostMatchSlices * 2 * to_cap));
+        c->d_hm_to = nullptr;
+        if(c->match_graph)
+        {
+            (void)hipGraphExecDestroy(c->match_graph); // captured on the buffers about to be freed
+            c->match_graph = nullptr;
+        }
+        MSLAM_CHK(c, c->d_hm_from.alloc((size_t)(from_cap + to_cap) * 32 + 16)); // (+ 16: the captured form's counts ride behind the rows)
+        MSLAM_CHK(c, c->d_hm_out.alloc((size_t)to_cap * 6 + 4));
+        MSLAM_CHK(c, c->d_hm_partial.alloc((size_t)kHostMatchSlices * 2 * to_cap));
         // page-locked, device-mapped: [descriptor staging (from | to) | from_idx | to_idx | n_out] — the caller's
         // (pageable) descriptors are copied here by the CPU and go up in ONE asynchronous copy (two blocking pageable
         // copies cost 25 us of the 84 us call); the ratio kernel writes its compacted pairs straight into the block
-        const size_t bytes = (size_t)(from_cap + to_cap) * 32 + 16 + ((size_t)to_cap * 2 + 4) * 4;
-        if(c->match_graph)
-        {
-            (void)hipGraphExecDestroy(c->match_graph); // captured on the buffers just freed
-            c->match_graph = nullptr;
-        }
-        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_hm), bytes, hipHostMallocMapped));
-        MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_h_hm), c->h_hm, 0));
+        MSLAM_CHK(c, c->h_hm.alloc((size_t)(from_cap + to_cap) * 32 + 16 + ((size_t)to_cap * 2 + 4) * 4));
         c->hm_from_cap = from_cap;
         c->hm_to_cap = to_cap;
     }
@@ -1531,7 +1484,7 @@ static int host_match_graph(mslam_hip_ctx* c, const uint8_t* from_desc, int n_fr
         std::memcpy(c->h_hm + fcap * 32, to_desc, (size_t)n_to * 32);
     const int32_t counts[4] = {n_from, n_to, 0, 0};
     std::memcpy(h_cnt, counts, sizeof(counts));
-    int32_t* res_dev = reinterpret_cast<int32_t*>(c->d_h_hm + (fcap + tcap) * 32 + 16);
+    int32_t* res_dev = reinterpret_cast<int32_t*>(c->h_hm.dev() + (fcap + tcap) * 32 + 16);
     const int32_t* res = reinterpret_cast<const int32_t*>(c->h_hm + (fcap + tcap) * 32 + 16);
     if(!c->match_graph || c->match_graph_from_cap != c->hm_from_cap || c->match_graph_to_cap != c->hm_to_cap ||
        c->match_graph_kind != c->matcher_kind)
@@ -1716,7 +1669,7 @@ int mslam_hip_match(mslam_hip_ctx* c, const uint8_t* from_desc, int n_from, cons
     r.cap = n_to;
     r.thr = c->d_ratio_thr;
     // the compacted pairs and their count land in the mapped host block (they are small: 8 bytes per match)
-    int32_t* res_dev = reinterpret_cast<int32_t*>(c->d_h_hm + (size_t)(c->hm_from_cap + c->hm_to_cap) * 32 + 16);
+    int32_t* res_dev = reinterpret_cast<int32_t*>(c->h_hm.dev() + (size_t)(c->hm_from_cap + c->hm_to_cap) * 32 + 16);
     const int32_t* res = reinterpret_cast<const int32_t*>(c->h_hm + (size_t)(c->hm_from_cap + c->hm_to_cap) * 32 + 16);
     r.from_idx = res_dev;
     r.to_idx = res_dev + cap;

@@ -18,6 +18,7 @@
 #include "context.hpp"
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <cmath>
 #include <cstring>
@@ -34,78 +35,60 @@ struct BowState
     uint32_t n_nodes = 0, n_words = 0;
     int max_children = 0;
     // device tree, indexed by "slot": the children of a node occupy consecutive slots in stream order
-    uint4* d_desc = nullptr;        // [n_nodes][2]
-    uint32_t* d_first = nullptr;    // first child slot (0 = leaf)
-    uint32_t* d_nchild = nullptr;
-    uint32_t* d_word = nullptr;     // word id of a leaf
-    double* d_weight = nullptr;
+    DevBuf<uint4> d_desc;        // [n_nodes][2]
+    DevBuf<uint32_t> d_first;    // first child slot (0 = leaf)
+    DevBuf<uint32_t> d_nchild;
+    DevBuf<uint32_t> d_word;     // word id of a leaf
+    DevBuf<double> d_weight;
     // per-feature scratch for a batch
-    uint32_t* d_fword = nullptr;    // [B][cap]
-    double* d_fweight = nullptr;    // [B][cap]
+    DevBuf<uint32_t> d_fword;    // [B][cap]
+    DevBuf<double> d_fweight;    // [B][cap]
     // BoW vectors of the current batch (slot B = the host-pointer query)
-    uint32_t* d_bwords = nullptr;   // [B+1][cap]
-    double* d_bvalues = nullptr;    // [B+1][cap]
-    int32_t* d_bn = nullptr;        // [B+1]
+    DevBuf<uint32_t> d_bwords;   // [B+1][cap]
+    DevBuf<double> d_bvalues;    // [B+1][cap]
+    DevBuf<int32_t> d_bn;        // [B+1]
     // database ring: R live entries + B in flight
     int R = 64, RP = 0;
-    uint32_t* d_rwords = nullptr;   // [RP][cap]
-    double* d_rvalues = nullptr;
-    int32_t* d_rn = nullptr;        // [RP]
+    DevBuf<uint32_t> d_rwords;   // [RP][cap]
+    DevBuf<double> d_rvalues;
+    DevBuf<int32_t> d_rn;        // [RP]
     long long next_id = 0;
     // scoring outputs
-    double* d_contrib = nullptr;    // [B+1][R][cap] matched terms of every (query, entry) pair, ascending word order
-    int32_t* d_match_cnt = nullptr; // [B+1][R]
-    double* d_scores = nullptr;     // [B+1][R]   score against entry (id_t - 1 - j), -1 when absent / no common word
-    int32_t* d_best_entry = nullptr; // [B+1]
-    double* d_best_score = nullptr;
-    uint8_t* d_hdesc = nullptr;     // host-pointer query descriptors [cap][32]
+    DevBuf<double> d_contrib;    // [B+1][R][cap] matched terms of every (query, entry) pair, ascending word order
+    DevBuf<int32_t> d_match_cnt; // [B+1][R]
+    DevBuf<double> d_scores;     // [B+1][R]   score against entry (id_t - 1 - j), -1 when absent / no common word
+    DevBuf<int32_t> d_best_entry; // [B+1]
+    DevBuf<double> d_best_score;
+    DevBuf<uint8_t> d_hdesc;     // host-pointer query descriptors [cap][32]
     // flat mode (SURVEY.md §8d bow_flat): the leaves' descriptors / weights in word-id order, per-feature best keys
-    uint32_t* d_leaf_desc = nullptr; // [n_words][8]
-    double* d_leaf_weight = nullptr; // [n_words]
-    uint32_t* d_fbest = nullptr;     // [B+1][cap] (distance << 20) | word
+    DevBuf<uint32_t> d_leaf_desc; // [n_words][8]
+    DevBuf<double> d_leaf_weight; // [n_words]
+    DevBuf<uint32_t> d_fbest;     // [B+1][cap] (distance << 20) | word
     int flat = 0;                    // MSLAM_BOW_ASSIGN_*
     bool flat_ok = false;            // the word table maps one-to-one onto the leaves, <= 2^20 words
     // inverted file of the database (DBoW3 Database: m_ifile, word -> (entry, value) rows).  Postings live in an
     // append-only log, entry after entry; the rows of a word are a linked list threaded through the log
     // (ix_prev), newest first, anchored at ix_head[word].  Index 0 is the null posting.
-    uint32_t* ix_head = nullptr;     // [n_words]
-    uint32_t* ix_entry = nullptr;    // [ix_cap_postings + 1]
-    uint32_t* ix_prev = nullptr;
-    double* ix_value = nullptr;
-    uint32_t* ix_size = nullptr;     // device counter: postings used
-    uint8_t* ix_removed = nullptr;   // [ix_max_entries]
+    DevBuf<uint32_t> ix_head;     // [n_words]
+    DevBuf<uint32_t> ix_entry;    // [ix_cap_postings + 1]
+    DevBuf<uint32_t> ix_prev;
+    DevBuf<double> ix_value;
+    DevBuf<uint32_t> ix_size;     // device counter: postings used
+    DevBuf<uint8_t> ix_removed;   // [ix_max_entries]
     // query scratch
-    uint32_t* ix_cnt = nullptr;      // [ix_max_entries] common words per entry
-    uint32_t* ix_ofs = nullptr;      // [ix_max_entries + 1]
-    uint32_t* ix_fill = nullptr;     // [ix_max_entries]
-    uint32_t* ix_keys = nullptr;     // [ix_cap_terms] rank of the query word
-    double* ix_vals = nullptr;       // [ix_cap_terms] the L1 term
-    double* ix_scores = nullptr;     // [ix_max_entries]
-    uint32_t* ix_total = nullptr;    // device: number of terms of the last query (for the capacity check)
+    DevBuf<uint32_t> ix_cnt;      // [ix_max_entries] common words per entry
+    DevBuf<uint32_t> ix_ofs;      // [ix_max_entries + 1]
+    DevBuf<uint32_t> ix_fill;     // [ix_max_entries]
+    DevBuf<uint32_t> ix_keys;     // [ix_cap_terms] rank of the query word
+    DevBuf<double> ix_vals;       // [ix_cap_terms] the L1 term
+    DevBuf<double> ix_scores;     // [ix_max_entries]
+    DevBuf<uint32_t> ix_total;    // device: number of terms of the last query (for the capacity check)
     long long ix_max_entries = 0;
     size_t ix_cap_postings = 0, ix_cap_terms = 0;
     int cap = 0, B = 0;
 };
 
-static void bow_free(BowState* b)
-{
-    void* bufs[] = {b->d_desc,   b->d_first,   b->d_nchild, b->d_word,   b->d_weight,     b->d_fword,      b->d_fweight,
-                    b->d_bwords, b->d_bvalues, b->d_bn,     b->d_rwords, b->d_rvalues,    b->d_rn,         b->d_scores,
-                    b->d_best_entry, b->d_best_score, b->d_hdesc, b->d_contrib, b->d_match_cnt,
-                    b->d_leaf_desc,  b->d_leaf_weight, b->d_fbest, b->ix_head, b->ix_entry, b->ix_prev, b->ix_value,
-                    b->ix_size, b->ix_removed, b->ix_cnt, b->ix_ofs, b->ix_fill, b->ix_keys, b->ix_vals, b->ix_scores,
-                    b->ix_total};
-    for(void* p : bufs)
-        if(p)
-            (void)hipFree(p);
-}
-void bow_destroy(BowState* b)
-{
-    if(!b)
-        return;
-    bow_free(b);
-    delete b;
-}
+void bow_destroy(BowState* b) { delete b; }
 
 // ---- kernels ------------------------------------------------------------------------------------------
 
@@ -989,12 +972,6 @@ __global__ __launch_bounds__(256) void k_bow_cross_packed(const uint32_t* __rest
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-template <typename T>
-static hipError_t bmalloc(T*& p, size_t n)
-{
-    return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T));
-}
-
 static int pow2_at_least(int n)
 {
     int p = 64;
@@ -1145,23 +1122,16 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
             return MSLAM_HIP_E_INVALID;
         }
     }
-    BowState* b = new BowState();
+    std::unique_ptr<BowState> b(new BowState()); // goes with everything it holds on every early way out
     b->k = k, b->L = L, b->scoring = scoring, b->weighting = weighting;
     b->n_nodes = n_nodes, b->n_words = n_words, b->max_children = max_children;
     b->cap = c->p.max_keypoints;
     b->B = c->p.max_batch;
     b->RP = b->R + b->B;
     const size_t cap = (size_t)b->cap, B = (size_t)b->B, RP = (size_t)b->RP;
-    auto fail_free = [&](int rc) {
-        bow_destroy(b);
-        return rc;
-    };
-#define BALLOC(ptr, n)                                                                                                 \
-    if(bmalloc(ptr, n) != hipSuccess)                                                                                  \
-    {                                                                                                                  \
-        c->err = "bow_load: device allocation failed";                                                                 \
-        return fail_free(MSLAM_HIP_E_RUNTIME);                                                                         \
-    }
+#define BALLOC(buf, n)                                                                                                 \
+    if(buf.alloc(n) != hipSuccess)                                                                                     \
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: device allocation failed");
     BALLOC(b->d_desc, (size_t)n_nodes * 2);
     BALLOC(b->d_first, n_nodes);
     BALLOC(b->d_nchild, n_nodes);
@@ -1189,10 +1159,7 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
     BALLOC(b->ix_total, 1);
 #undef BALLOC
     if(hipMemset(b->ix_head, 0, (size_t)n_words * 4) != hipSuccess || hipMemset(b->ix_size, 0, 4) != hipSuccess)
-    {
-        c->err = "bow_load: upload failed";
-        return fail_free(MSLAM_HIP_E_RUNTIME);
-    }
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: upload failed");
     bool ok = hipMemcpy(b->d_desc, sdesc.data(), sdesc.size(), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(b->d_first, sfirst.data(), n_nodes * 4, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(b->d_nchild, snchild.data(), n_nodes * 4, hipMemcpyHostToDevice) == hipSuccess &&
@@ -1222,13 +1189,9 @@ static int bow_load_impl(mslam_hip_ctx* c, const void* blob, size_t size)
              hipMemcpy(b->d_leaf_weight, lweight.data(), lweight.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
     }
     if(!ok)
-    {
-        c->err = "bow_load: upload failed";
-        return fail_free(MSLAM_HIP_E_RUNTIME);
-    }
-    if(c->bow)
-        bow_destroy(c->bow);
-    c->bow = b;
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bow_load: upload failed");
+    bow_destroy(c->bow); // a reload: the old vocabulary and its database go
+    c->bow = b.release();
     return MSLAM_HIP_OK;
 }
 
@@ -1300,23 +1263,9 @@ static int bow_score_dev(mslam_hip_ctx* c, int qslot, int n_frames, long long ba
 }
 
 // ---- inverted file: host side -----------------------------------------------------------------------------------
-template <typename T>
-static int ix_grow(mslam_hip_ctx* c, T*& ptr, size_t old_n, size_t new_n, bool zero)
-{
-    T* np = nullptr;
-    MSLAM_CHK(c, bmalloc(np, new_n));
-    if(zero)
-        MSLAM_CHK(c, hipMemsetAsync(np, 0, new_n * sizeof(T), c->stream));
-    if(ptr && old_n)
-        MSLAM_CHK(c, hipMemcpyAsync(np, ptr, old_n * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-    if(ptr)
-        (void)hipFree(ptr);
-    ptr = np;
-    return MSLAM_HIP_OK;
-}
-
-// make room for `max_entries` database entries (postings: max_entries x max_keypoints in the worst case)
+// make room for `max_entries` database entries (postings: max_entries x max_keypoints in the worst case): every array grows
+// into a fresh block (the log and the removal marks keep their contents, the query scratch starts over), one wait, then
+// the swap — a failure leaves the arrays and the capacities as they were
 static int ix_reserve(mslam_hip_ctx* c, long long max_entries)
 {
     BowState* b = c->bow;
@@ -1326,19 +1275,24 @@ static int ix_reserve(mslam_hip_ctx* c, long long max_entries)
         return fail(c, MSLAM_HIP_E_CAPACITY, "bow database: more postings than a 32-bit index can address");
     const size_t old_e = (size_t)b->ix_max_entries, new_e = (size_t)max_entries;
     const size_t old_p = b->ix_cap_postings ? b->ix_cap_postings + 1 : 0, new_p = new_e * (size_t)b->cap + 1;
-    int rc = 0;
-    rc = rc ? rc : ix_grow(c, b->ix_entry, old_p, new_p, false);
-    rc = rc ? rc : ix_grow(c, b->ix_prev, old_p, new_p, false);
-    rc = rc ? rc : ix_grow(c, b->ix_value, old_p, new_p, false);
-    rc = rc ? rc : ix_grow(c, b->ix_removed, old_e, new_e, true);
-    rc = rc ? rc : ix_grow(c, b->ix_cnt, 0, new_e, true);
-    rc = rc ? rc : ix_grow(c, b->ix_ofs, 0, new_e + 1, true);
-    rc = rc ? rc : ix_grow(c, b->ix_fill, 0, new_e, true);
-    rc = rc ? rc : ix_grow(c, b->ix_scores, 0, new_e, false);
-    rc = rc ? rc : ix_grow(c, b->ix_keys, 0, new_p, false);
-    rc = rc ? rc : ix_grow(c, b->ix_vals, 0, new_p, false);
-    if(rc)
-        return rc;
+    hipStream_t s = c->stream;
+    DevBuf<uint32_t> entry, prev, cnt, ofs, fill, keys;
+    DevBuf<double> value, scores, vals;
+    DevBuf<uint8_t> removed;
+    MSLAM_CHK(c, grown_copy(entry, b->ix_entry, new_p, old_p, false, s));
+    MSLAM_CHK(c, grown_copy(prev, b->ix_prev, new_p, old_p, false, s));
+    MSLAM_CHK(c, grown_copy(value, b->ix_value, new_p, old_p, false, s));
+    MSLAM_CHK(c, grown_copy(removed, b->ix_removed, new_e, old_e, true, s));
+    MSLAM_CHK(c, grown_copy(cnt, b->ix_cnt, new_e, 0, true, s));
+    MSLAM_CHK(c, grown_copy(ofs, b->ix_ofs, new_e + 1, 0, true, s));
+    MSLAM_CHK(c, grown_copy(fill, b->ix_fill, new_e, 0, true, s));
+    MSLAM_CHK(c, grown_copy(scores, b->ix_scores, new_e, 0, false, s));
+    MSLAM_CHK(c, grown_copy(keys, b->ix_keys, new_p, 0, false, s));
+    MSLAM_CHK(c, grown_copy(vals, b->ix_vals, new_p, 0, false, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s)); // everything that reads the old blocks has finished before they are freed
+    b->ix_entry = std::move(entry), b->ix_prev = std::move(prev), b->ix_value = std::move(value), b->ix_removed = std::move(removed);
+    b->ix_cnt = std::move(cnt), b->ix_ofs = std::move(ofs), b->ix_fill = std::move(fill), b->ix_scores = std::move(scores);
+    b->ix_keys = std::move(keys), b->ix_vals = std::move(vals);
     b->ix_max_entries = max_entries;
     b->ix_cap_postings = new_p - 1;
     b->ix_cap_terms = new_p;
@@ -1396,7 +1350,7 @@ int bow_batch(mslam_hip_ctx* c, int add_to_db)
         return fail(c, MSLAM_HIP_E_INVALID, "bow_batch_dev: no detect batch");
     const size_t K = (size_t)c->p.max_keypoints;
     const int n = c->n_last;
-    int rc = bow_transform_dev(c, c->d_desc + K * 32, (long long)K * 32, c->d_count + 1, 0, n, 0);
+    int rc = bow_transform_dev(c, cur_out(c).desc + K * 32, (long long)K * 32, cur_out(c).count + 1, 0, n, 0);
     if(rc)
         return rc;
     if(add_to_db)

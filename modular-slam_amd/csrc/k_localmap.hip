@@ -244,41 +244,18 @@ __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict_
 
 using namespace mslam;
 
+// the per-block arrays of nb blocks, in bytes: [win nb x 4 u64 | cnt nb | ofs nb + 1]; and nb of a block of `bytes`
+static size_t lm_blocks_bytes(size_t nb) { return nb * 32 + nb * 4 + (nb + 1) * 4; }
+static size_t lm_blocks_cap(size_t bytes) { return (bytes - 4) / 40; }
+
 // the scratch both calls share: a table of `buckets` buckets, per-block arrays for `blocks` blocks, the mapped result
 static int lm_scratch(mslam_hip_ctx* c, size_t buckets, size_t blocks)
 {
     RelocState* r = c->reloc;
-    if(buckets > r->lm_buckets)
-    {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // what reads the old table has finished before it is freed
-        if(r->d_lm_table)
-            (void)hipFree(r->d_lm_table);
-        r->d_lm_table = nullptr;
-        r->lm_buckets = 0;
-        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_table), buckets * sizeof(LmBucket)));
-        r->lm_buckets = buckets;
-    }
-    if(blocks > r->lm_blocks)
-    {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-        if(r->d_lm_blocks)
-            (void)hipFree(r->d_lm_blocks);
-        r->d_lm_blocks = nullptr;
-        r->lm_blocks = 0;
-        const size_t nb = std::max(blocks, (size_t)256);
-        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_lm_blocks), nb * 32 + nb * 4 + (nb + 1) * 4)); // [win nb x 4 u64 | cnt | ofs]
-        r->lm_blocks = nb;
-    }
+    MSLAM_CHK(c, grow(r->d_lm_table, buckets * sizeof(LmBucket), c->stream));
+    MSLAM_CHK(c, grow(r->d_lm_blocks, lm_blocks_bytes(std::max(blocks, (size_t)256)), c->stream));
     if(!r->h_lm)
-    {
-        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_lm), sizeof(LmHead) + kRelocMaxCand * 4, hipHostMallocMapped));
-        if(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_lm), r->h_lm, 0) != hipSuccess)
-        {
-            (void)hipHostFree(r->h_lm);
-            r->h_lm = r->d_h_lm = nullptr;
-            return fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: no device address for the result block");
-        }
-    }
+        MSLAM_CHK(c, r->h_lm.alloc(sizeof(LmHead) + kRelocMaxCand * 4));
     return MSLAM_HIP_OK;
 }
 
@@ -334,10 +311,11 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     (void)store_next_lid_base(c); // a new serial for the entry; its landmarks keep the ids they have
     const size_t slot = (size_t)*dst_slot;
     hipStream_t s = c->stream;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table);
-    unsigned long long* win = reinterpret_cast<unsigned long long*>(r->d_lm_blocks);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(r->d_lm_blocks + r->lm_blocks * 32);
-    uint32_t* ofs = cnt + r->lm_blocks;
+    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
+    unsigned long long* win = reinterpret_cast<unsigned long long*>(r->d_lm_blocks.get());
+    const size_t cap_blocks = lm_blocks_cap(r->d_lm_blocks.size());
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(r->d_lm_blocks + cap_blocks * 32);
+    uint32_t* ofs = cnt + cap_blocks;
     const dim3 grid(bx, (unsigned)n_ids);
     {
         StageScope ts(c, "union_clear");
@@ -354,7 +332,7 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     {
         StageScope ts(c, "union_scan");
         hipLaunchKernelGGL(k_lm_scan, dim3(1), dim3(256), 0, s, cnt, ofs, (int)nb, K, r->d_n + slot, c->d_flags, set_flag,
-                           reinterpret_cast<LmHead*>(r->d_h_lm));
+                           reinterpret_cast<LmHead*>(r->h_lm.dev()));
     }
     {
         StageScope ts(c, "union_scatter");
@@ -384,7 +362,7 @@ int mslam_hip_kf_union(mslam_hip_ctx* c, int dst_id, const int32_t* ids, int n_i
         return rc;
     RelocState* r = c->reloc;
     MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-    const int32_t needed = reinterpret_cast<const LmHead*>(r->h_lm)->needed;
+    const int32_t needed = reinterpret_cast<const LmHead*>(r->h_lm.get())->needed;
     if(needed < 0)
         return fail(c, MSLAM_HIP_E_RUNTIME, "kf_union: the kernels reported an impossible count");
     if(n_out)
@@ -427,7 +405,7 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
     if(rc)
         return rc;
     hipStream_t s = c->stream;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table);
+    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
     int32_t* h_counts = reinterpret_cast<int32_t*>(r->h_lm + sizeof(LmHead));
     for(int k = 0; k < n_ids; ++k)
         h_counts[k] = -1; // (overwritten by k_lm_covisible; checked after the synchronisation)
@@ -443,7 +421,7 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
     {
         StageScope ts(c, "covisible_count");
         hipLaunchKernelGGL(k_lm_covisible, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_lid, r->d_n, list, K, table,
-                           (unsigned long long)(buckets - 1), reinterpret_cast<int32_t*>(r->d_h_lm + sizeof(LmHead)));
+                           (unsigned long long)(buckets - 1), reinterpret_cast<int32_t*>(r->h_lm.dev() + sizeof(LmHead)));
     }
     MSLAM_CHK(c, hipGetLastError());
     MSLAM_CHK(c, hipStreamSynchronize(s));

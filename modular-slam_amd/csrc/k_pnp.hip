@@ -867,30 +867,22 @@ extern "C" int mslam_hip_pnp_ransac(mslam_hip_ctx* c, const float* object_points
     if(e == hipSuccess)                                                                                                \
     e = (call)
     // scratch of the single-problem call lives in the context and only grows (this is the per-frame tracking path of the
-    // plugin: six hipMalloc + six hipFree, each a device synchronisation, per call would cost more than the solve)
+    // plugin: six allocations and six frees, each a device synchronisation, per call would cost more than the solve)
     if(n > c->pnp1_n_cap || iterations > c->pnp1_it_cap)
     {
-        PCHK(hipStreamSynchronize(c->stream));
-        void* old[] = {c->d_pnp1_obj, c->d_pnp1_img, c->d_pnp1_hyp, c->d_pnp1_out, c->d_pnp1_counts, c->d_pnp1_mask};
-        for(void* b : old)
-            if(b)
-                (void)hipFree(b);
-        c->d_pnp1_obj = c->d_pnp1_img = nullptr;
-        c->d_pnp1_hyp = c->d_pnp1_out = nullptr;
-        c->d_pnp1_counts = nullptr;
-        c->d_pnp1_mask = nullptr;
+        PCHK(hipStreamSynchronize(c->stream)); // what reads the old blocks has finished before they are freed
         // (never below the old capacities: a large call followed by one with more iterations must not shrink the point
         // buffers, or the next large call reallocates again)
-        const int n_cap = std::max({n, 1024, c->pnp1_n_cap}), it_cap = std::max({iterations, 128, c->pnp1_it_cap});
+        const size_t n_cap = std::max({n, 1024, c->pnp1_n_cap}), it_cap = std::max({iterations, 128, c->pnp1_it_cap});
         c->pnp1_n_cap = c->pnp1_it_cap = 0;
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_obj), (size_t)n_cap * 12));
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_img), (size_t)n_cap * 8));
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_hyp), (size_t)it_cap * 12 * 8));
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_out), 16 * 8));
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_counts), (size_t)it_cap * 4));
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_pnp1_mask), (size_t)n_cap));
+        PCHK(c->d_pnp1_obj.alloc(n_cap * 3));
+        PCHK(c->d_pnp1_img.alloc(n_cap * 2));
+        PCHK(c->d_pnp1_hyp.alloc(it_cap * 12));
+        PCHK(c->d_pnp1_out.alloc(16));
+        PCHK(c->d_pnp1_counts.alloc(it_cap));
+        PCHK(c->d_pnp1_mask.alloc(n_cap));
         if(e == hipSuccess)
-            c->pnp1_n_cap = n_cap, c->pnp1_it_cap = it_cap;
+            c->pnp1_n_cap = (int)n_cap, c->pnp1_it_cap = (int)it_cap;
     }
     float *d_obj = c->d_pnp1_obj, *d_img = c->d_pnp1_img;
     double *d_hyp = c->d_pnp1_hyp, *d_out = c->d_pnp1_out;
@@ -942,19 +934,15 @@ static int pnp_batch_buffers(mslam_hip_ctx* c, int iterations)
     const size_t B = (size_t)c->p.max_batch, K = (size_t)c->p.max_keypoints;
     if(c->d_pnp_obj && c->pnp_iterations >= iterations)
         return MSLAM_HIP_OK;
-    void* old[] = {c->d_pnp_obj, c->d_pnp_img, c->d_pnp_n, c->d_pnp_counts, c->d_pnp_hyp, c->d_pnp_out, c->d_pnp_mask};
-    for(void* p : old)
-        if(p)
-            (void)hipFree(p);
-    c->d_pnp_obj = c->d_pnp_img = nullptr, c->d_pnp_n = c->d_pnp_counts = nullptr, c->d_pnp_hyp = c->d_pnp_out = nullptr;
-    c->d_pnp_mask = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_obj), B * K * 12);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_img), B * K * 8);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_n), B * 4);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_counts), B * (size_t)iterations * 4);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_hyp), B * (size_t)iterations * 12 * 8);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_out), B * 16 * 8);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_pnp_mask), B * K);
+    const size_t it = (size_t)iterations;
+    c->pnp_iterations = 0; // until every block is there
+    hipError_t e = c->d_pnp_obj.alloc(B * K * 3);
+    if(e == hipSuccess) e = c->d_pnp_img.alloc(B * K * 2);
+    if(e == hipSuccess) e = c->d_pnp_n.alloc(B);
+    if(e == hipSuccess) e = c->d_pnp_counts.alloc(B * it);
+    if(e == hipSuccess) e = c->d_pnp_hyp.alloc(B * it * 12);
+    if(e == hipSuccess) e = c->d_pnp_out.alloc(B * 16);
+    if(e == hipSuccess) e = c->d_pnp_mask.alloc(B * K);
     if(e == hipSuccess) e = hipMemset(c->d_pnp_n, 0, B * 4);
     if(e == hipSuccess) e = hipMemset(c->d_pnp_out, 0, B * 16 * 8);
     if(e != hipSuccess)
@@ -990,8 +978,8 @@ extern "C" int mslam_hip_pnp_batch_dev(mslam_hip_ctx* c, double fx, double fy, d
     const int K = c->p.max_keypoints, n = c->n_last;
     {
         StageScope t(c, "pnp_gather");
-        hipLaunchKernelGGL(k_pnp_gather, dim3(n), dim3(256), 0, c->stream, c->d_mfrom, c->d_mto, c->d_mcount,
-                           c->d_xy + (size_t)K * 2, c->d_xyz, c->d_valid, K, c->d_pnp_obj, c->d_pnp_img, c->d_pnp_n);
+        hipLaunchKernelGGL(k_pnp_gather, dim3(n), dim3(256), 0, c->stream, cur_out(c).mfrom, cur_out(c).mto, cur_out(c).mcount,
+                           cur_out(c).xy + (size_t)K * 2, c->d_xyz, c->d_valid, K, c->d_pnp_obj, c->d_pnp_img, c->d_pnp_n);
     }
     PnpBatchArgs b{};
     PnpArgs& a = b.proto;

@@ -516,18 +516,8 @@ extern "C" int mslam_hip_pnp_min_mse(mslam_hip_ctx* c, const double* object_poin
     // one device block: [obj n*3 | img n*2 | pose 6 | info 4 | n (int32 in an 8-byte slot)], grown on demand, so the call
     // is one upload, one launch (the batched kernel with one problem of capacity n) and one download
     const size_t words = (size_t)n * 5 + 11;
-    if(words > c->mse1_words)
-    {
-        PCHK(hipStreamSynchronize(c->stream));
-        if(c->d_mse1)
-            (void)hipFree(c->d_mse1);
-        c->d_mse1 = nullptr;
-        c->mse1_words = 0;
-        const size_t cap = std::max<size_t>(words, 5 * 1024 + 11);
-        PCHK(hipMalloc(reinterpret_cast<void**>(&c->d_mse1), cap * 8));
-        if(e == hipSuccess)
-            c->mse1_words = cap;
-    }
+    if(words > c->d_mse1.size())
+        PCHK(grow(c->d_mse1, std::max<size_t>(words, 5 * 1024 + 11), c->stream));
     std::vector<double> stage(words);
     if(n > 0)
     {

@@ -222,8 +222,8 @@ static int ensure_points(mslam_hip_ctx* c)
     if(c->d_xyz)
         return MSLAM_HIP_OK;
     const size_t n = (size_t)c->p.max_batch * c->p.max_keypoints;
-    MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_xyz), n * 3 * sizeof(double)));
-    MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_valid), n));
+    MSLAM_CHK(c, c->d_xyz.alloc(n * 3));
+    MSLAM_CHK(c, c->d_valid.alloc(n));
     return MSLAM_HIP_OK;
 }
 
@@ -247,7 +247,7 @@ int mslam_hip_backproject_batch_dev(mslam_hip_ctx* c, const uint16_t* d_depth, f
     StageScope t(c, "backproject");
     dim3 grid((c->p.max_keypoints + 255) / 256, c->n_last);
     hipLaunchKernelGGL(k_backproject, grid, dim3(256), 0, c->stream, d_depth, (long long)c->p.width * c->p.height,
-                       c->p.width, c->p.height, cam, c->d_xy + K * 2, (long long)K * 2, c->d_count + 1, 0,
+                       c->p.width, c->p.height, cam, cur_out(c).xy + K * 2, (long long)K * 2, cur_out(c).count + 1, 0,
                        c->p.max_keypoints, c->d_xyz, c->d_valid);
     MSLAM_CHK(c, hipGetLastError());
     c->points_seq = c->detect_seq;
@@ -271,11 +271,12 @@ int mslam_hip_pack_batch_dev(mslam_hip_ctx* c, void* out, size_t capacity_bytes,
     const size_t K = (size_t)c->p.max_keypoints;
     // the matcher's outputs belong to the batch match_batch_dev last ran on: when that is not this detect batch (match_seq), the
     // slot still holds an older batch's pairs, and the batch is packed with zero matches instead of those
-    const int32_t* mcount = c->match_seq == c->detect_seq ? c->d_mcount : nullptr;
-    hipLaunchKernelGGL(k_pack_plan, dim3(1), dim3(1024), 0, c->stream, c->d_count + 1, mcount, c->n_last, c->p.max_keypoints,
+    const mslam_out_set& o = cur_out(c);
+    const int32_t* mcount = c->match_seq == c->detect_seq ? o.mcount : nullptr;
+    hipLaunchKernelGGL(k_pack_plan, dim3(1), dim3(1024), 0, c->stream, o.count + 1, mcount, c->n_last, c->p.max_keypoints,
                        with_points ? 1 : 0, (unsigned long long)capacity_bytes, static_cast<uint8_t*>(out), c->d_flags);
-    hipLaunchKernelGGL(k_pack_copy, dim3(c->n_last, 4), dim3(256), 0, c->stream, c->d_xy + K * 2, c->d_desc + K * 32, c->d_octave + K,
-                       c->d_angle + K, c->d_response + K, c->d_xyz, c->d_valid, c->d_mfrom, c->d_mto, c->p.max_keypoints,
+    hipLaunchKernelGGL(k_pack_copy, dim3(c->n_last, 4), dim3(256), 0, c->stream, o.xy + K * 2, o.desc + K * 32, o.octave + K,
+                       o.angle + K, o.response + K, c->d_xyz, c->d_valid, o.mfrom, o.mto, c->p.max_keypoints,
                        static_cast<uint8_t*>(out));
     MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
@@ -312,16 +313,16 @@ int mslam_hip_backproject(mslam_hip_ctx* c, const uint16_t* depth, int width, in
     if(n == 0)
         return MSLAM_HIP_OK;
     MSLAM_CHK(c, hipSetDevice(c->p.device));
-    uint16_t* d_depth = nullptr;
-    float* d_xy = nullptr;
-    double* d_xyz = nullptr;
-    uint8_t* d_valid = nullptr;
+    DevBuf<uint16_t> d_depth; // the call's own temporaries: released on every way out
+    DevBuf<float> d_xy;
+    DevBuf<double> d_xyz;
+    DevBuf<uint8_t> d_valid;
     const size_t npx = (size_t)width * height;
     hipStream_t s = c->stream;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_depth), npx * 2);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_xy), (size_t)n * 8);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_xyz), (size_t)n * 24);
-    if(e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_valid), (size_t)n);
+    hipError_t e = d_depth.alloc(npx);
+    if(e == hipSuccess) e = d_xy.alloc((size_t)n * 2);
+    if(e == hipSuccess) e = d_xyz.alloc((size_t)n * 3);
+    if(e == hipSuccess) e = d_valid.alloc((size_t)n);
     if(e == hipSuccess) e = hipMemcpyAsync(d_depth, depth, npx * 2, hipMemcpyHostToDevice, s);
     if(e == hipSuccess) e = hipMemcpyAsync(d_xy, xy, (size_t)n * 8, hipMemcpyHostToDevice, s);
     if(e == hipSuccess)
@@ -334,10 +335,6 @@ int mslam_hip_backproject(mslam_hip_ctx* c, const uint16_t* depth, int width, in
     if(e == hipSuccess) e = hipMemcpyAsync(xyz, d_xyz, (size_t)n * 24, hipMemcpyDeviceToHost, s);
     if(e == hipSuccess) e = hipMemcpyAsync(valid, d_valid, (size_t)n, hipMemcpyDeviceToHost, s);
     if(e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_depth);
-    (void)hipFree(d_xy);
-    (void)hipFree(d_xyz);
-    (void)hipFree(d_valid);
     if(e != hipSuccess)
     {
         c->err = std::string("backproject: ") + hipGetErrorString(e);

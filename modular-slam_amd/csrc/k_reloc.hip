@@ -21,22 +21,7 @@
 namespace mslam
 {
 
-void reloc_destroy(RelocState* r)
-{
-    if(!r)
-        return;
-    void* dev[] = {r->d_desc, r->d_world, r->d_n, r->d_lid, r->d_up, r->d_arena, r->d_lm_table, r->d_lm_blocks};
-    for(void* p : dev)
-        if(p)
-            (void)hipFree(p);
-    if(r->h_up)
-        (void)hipHostFree(r->h_up);
-    if(r->h_res)
-        (void)hipHostFree(r->h_res);
-    if(r->h_lm)
-        (void)hipHostFree(r->h_lm);
-    delete r;
-}
+void reloc_destroy(RelocState* r) { delete r; }
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------
 
@@ -237,44 +222,24 @@ int mslam::store_reserve(mslam_hip_ctx* c, int want)
         return MSLAM_HIP_OK;
     const size_t K = (size_t)c->p.max_keypoints;
     const int slots = std::max({want, 2 * r->slots, 16});
-    uint8_t* nd = nullptr;
-    double* nw = nullptr;
-    int32_t* nn = nullptr;
-    int64_t* nl = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nd), (size_t)slots * K * 32);
+    // fresh blocks, the live slots copied across; one wait, then the swap — a failure leaves the store as it was
+    const size_t n = (size_t)slots, old = (size_t)r->slots;
+    DevBuf<uint8_t> nd;
+    DevBuf<double> nw;
+    DevBuf<int32_t> nn;
+    DevBuf<int64_t> nl;
+    hipError_t e = grown_copy(nd, r->d_desc, n * K * 32, old * K * 32, false, c->stream);
     if(e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&nw), (size_t)slots * K * 3 * sizeof(double));
+        e = grown_copy(nw, r->d_world, n * K * 3, old * K * 3, false, c->stream);
     if(e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&nn), (size_t)slots * 4);
+        e = grown_copy(nn, r->d_n, n, old, true, c->stream);
     if(e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void**>(&nl), (size_t)slots * K * 8);
-    if(e == hipSuccess)
-        e = hipMemsetAsync(nn, 0, (size_t)slots * 4, c->stream);
-    if(e == hipSuccess && r->slots > 0)
-    {
-        e = hipMemcpyAsync(nd, r->d_desc, (size_t)r->slots * K * 32, hipMemcpyDeviceToDevice, c->stream);
-        if(e == hipSuccess)
-            e = hipMemcpyAsync(nw, r->d_world, (size_t)r->slots * K * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if(e == hipSuccess)
-            e = hipMemcpyAsync(nn, r->d_n, (size_t)r->slots * 4, hipMemcpyDeviceToDevice, c->stream);
-        if(e == hipSuccess)
-            e = hipMemcpyAsync(nl, r->d_lid, (size_t)r->slots * K * 8, hipMemcpyDeviceToDevice, c->stream);
-    }
+        e = grown_copy(nl, r->d_lid, n * K, old * K, false, c->stream);
     if(e == hipSuccess)
         e = hipStreamSynchronize(c->stream); // everything that reads the old blocks has finished before they are freed
     if(e != hipSuccess)
-    {
-        void* fresh[] = {nd, nw, nn, nl};
-        for(void* p : fresh)
-            if(p)
-                (void)hipFree(p);
         return fail(c, MSLAM_HIP_E_RUNTIME, std::string("kf store: ") + hipGetErrorString(e));
-    }
-    void* old[] = {r->d_desc, r->d_world, r->d_n, r->d_lid};
-    for(void* p : old)
-        if(p)
-            (void)hipFree(p);
-    r->d_desc = nd, r->d_world = nw, r->d_n = nn, r->d_lid = nl;
+    r->d_desc = std::move(nd), r->d_world = std::move(nw), r->d_n = std::move(nn), r->d_lid = std::move(nl);
     for(int s = slots - 1; s >= r->slots; --s)
         r->free_slots.push_back(s); // (handed out in ascending order)
     r->n_upper.resize((size_t)slots, 0);
@@ -489,8 +454,8 @@ int mslam_hip_kf_add_from_batch_dev(mslam_hip_ctx* c, int id, int frame, const d
     {
         StageScope ts(c, "kf_lift");
         // frame f of the batch: descriptors in output slot f + 1, points in row f of the back-projection
-        hipLaunchKernelGGL(k_kf_lift, dim3(1), dim3(256), 0, c->stream, c->d_desc + (size_t)(frame + 1) * K * 32,
-                           c->d_xyz + (size_t)frame * K * 3, c->d_valid + (size_t)frame * K, c->d_count + 1 + frame,
+        hipLaunchKernelGGL(k_kf_lift, dim3(1), dim3(256), 0, c->stream, cur_out(c).desc + (size_t)(frame + 1) * K * 32,
+                           c->d_xyz + (size_t)frame * K * 3, c->d_valid + (size_t)frame * K, cur_out(c).count + 1 + frame,
                            c->p.max_keypoints, pose, r->d_desc + (size_t)slot * K * 32, r->d_world + (size_t)slot * K * 3,
                            r->d_n + slot, r->d_lid + (size_t)slot * K, lid_base);
     }
@@ -566,43 +531,16 @@ int mslam_hip_kf_read_ids(mslam_hip_ctx* c, int id, int64_t* landmark_ids, int c
 int mslam::reloc_scratch(mslam_hip_ctx* c, size_t up, size_t arena, size_t res)
 {
     RelocState* r = c->reloc;
-    if(up > r->up_bytes)
+    // (never less than a 4096-keypoint relocalize query takes, whichever call grows the block first: small callers such as
+    // mslam_hip_kf_visible share the 168 KB instead of holding blocks of their own)
+    if(up > r->h_up.size() || up > r->d_up.size())
     {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream)); // what reads the old block has finished before it is freed
-        if(r->h_up)
-            (void)hipHostFree(r->h_up);
-        if(r->d_up)
-            (void)hipFree(r->d_up);
-        r->h_up = r->d_up = nullptr;
-        r->up_bytes = 0;
-        // (never less than a 4096-keypoint relocalize query takes, whichever call grows the block first: small callers such as
-        // mslam_hip_kf_visible share the 168 KB instead of holding blocks of their own)
         const size_t bytes = std::max(up, (size_t)4096 * 41 + kRelocMaxCand * 4);
-        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_up), bytes, hipHostMallocDefault));
-        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_up), bytes));
-        r->up_bytes = bytes;
+        MSLAM_CHK(c, grow(r->h_up, bytes, c->stream));
+        MSLAM_CHK(c, grow(r->d_up, bytes, c->stream));
     }
-    if(arena > r->arena_bytes)
-    {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-        if(r->d_arena)
-            (void)hipFree(r->d_arena);
-        r->d_arena = nullptr;
-        r->arena_bytes = 0;
-        MSLAM_CHK(c, hipMalloc(reinterpret_cast<void**>(&r->d_arena), arena));
-        r->arena_bytes = arena;
-    }
-    if(res > r->res_bytes)
-    {
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-        if(r->h_res)
-            (void)hipHostFree(r->h_res);
-        r->h_res = r->d_h_res = nullptr;
-        r->res_bytes = 0;
-        MSLAM_CHK(c, hipHostMalloc(reinterpret_cast<void**>(&r->h_res), res, hipHostMallocMapped));
-        MSLAM_CHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r->d_h_res), r->h_res, 0));
-        r->res_bytes = res;
-    }
+    MSLAM_CHK(c, grow(r->d_arena, arena, c->stream));
+    MSLAM_CHK(c, grow(r->h_res, res, c->stream));
     return MSLAM_HIP_OK;
 }
 
@@ -784,7 +722,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     for(int k = 0; hooks && k < 2; ++k) // straight from the caller's buffers into the staging block
         if(hooks->extra_up_bytes[k])
             std::memcpy(r->h_up + off_extra + (k ? hooks->extra_up_bytes[0] : 0), hooks->extra_up[k], hooks->extra_up_bytes[k]);
-    reinterpret_cast<int32_t*>(r->h_res)[0] = -2; // (overwritten by k_reloc_rank; checked after the synchronisation)
+    reinterpret_cast<int32_t*>(r->h_res.get())[0] = -2; // (overwritten by k_reloc_rank; checked after the synchronisation)
     hipStream_t s = c->stream;
     MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
     // every candidate's train side is the one uploaded query block
@@ -801,7 +739,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     {
         dev.desc = a.desc, dev.xy = a.xy, dev.n = n, dev.valid = a.valid;
         dev.extra_up = r->d_up + off_extra, dev.extra_arena = r->d_arena + o_extra;
-        dev.extra_res = r->d_h_res + res_extra, dev.h_extra_res = r->h_res + res_extra;
+        dev.extra_res = r->h_res.dev() + res_extra, dev.h_extra_res = r->h_res + res_extra;
         if(hooks->after_upload)
         {
             rc = hooks->after_upload(c, hooks->user, dev);
@@ -816,7 +754,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     {
         StageScope ts(c, "reloc_rank");
         hipLaunchKernelGGL(k_reloc_rank, dim3(want_pairs ? 1u + (unsigned)P : 1u), dim3(256), 0, s, dev.seq.mcount, dev.seq.ncorr,
-                           dev.seq.pnp_out, n_cand, min_inliers, (int)S, dev.seq.mfrom, dev.seq.mto, dev.seq.mask, r->d_h_res);
+                           dev.seq.pnp_out, n_cand, min_inliers, (int)S, dev.seq.mfrom, dev.seq.mto, dev.seq.mask, r->h_res.dev());
     }
     MSLAM_CHK(c, hipGetLastError());
     if(hooks && hooks->before_sync)
@@ -827,7 +765,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     }
     MSLAM_CHK(c, hipStreamSynchronize(s));
 
-    const int32_t b = reinterpret_cast<const int32_t*>(r->h_res)[0];
+    const int32_t b = reinterpret_cast<const int32_t*>(r->h_res.get())[0];
     if(b < -1 || b >= n_cand)
         return fail(c, MSLAM_HIP_E_RUNTIME, "relocalize: the ranking kernel left no result");
     const RelocRes* rr = reinterpret_cast<const RelocRes*>(r->h_res + 16);

@@ -183,22 +183,22 @@ int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const 
     if(rc)
         return rc;
     std::memcpy(r->h_up, &up, sizeof(up));
-    int32_t* h = reinterpret_cast<int32_t*>(r->h_res);
+    int32_t* h = reinterpret_cast<int32_t*>(r->h_res.get());
     h[0] = -2; // (overwritten by k_track_vote_pick; checked after the synchronisation)
     hipStream_t s = c->stream;
     MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, sizeof(up), hipMemcpyHostToDevice, s));
-    int32_t* d_counts = reinterpret_cast<int32_t*>(r->d_arena);
+    int32_t* d_counts = reinterpret_cast<int32_t*>(r->d_arena.get());
     {
         StageScope ts(c, "track_vote");
         hipLaunchKernelGGL(k_track_vote, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_world, r->d_n,
-                           reinterpret_cast<const int32_t*>(r->d_up), c->p.max_keypoints,
+                           reinterpret_cast<const int32_t*>(r->d_up.get()), c->p.max_keypoints,
                            reinterpret_cast<const double*>(r->d_up + sizeof(up.slots)), nullptr, 0,
                            vote_cam(fx, fy, cx, cy, width, height), d_counts);
     }
     {
         StageScope ts(c, "track_vote_pick");
-        hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, s, d_counts, n_ids, reinterpret_cast<int32_t*>(r->d_h_res),
-                           reinterpret_cast<int32_t*>(r->d_h_res + 16));
+        hipLaunchKernelGGL(k_track_vote_pick, dim3(1), dim3(64), 0, s, d_counts, n_ids, reinterpret_cast<int32_t*>(r->h_res.dev()),
+                           reinterpret_cast<int32_t*>(r->h_res.dev() + 16));
     }
     MSLAM_CHK(c, hipGetLastError());
     MSLAM_CHK(c, hipStreamSynchronize(s));

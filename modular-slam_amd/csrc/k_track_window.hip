@@ -193,7 +193,7 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     if(rc)
         return rc;
 
-    int32_t* h_slots = reinterpret_cast<int32_t*>(r->h_up);
+    int32_t* h_slots = reinterpret_cast<int32_t*>(r->h_up.get());
     std::memcpy(h_slots, slots.vote_slots, kRelocMaxCand * 4);
     h_slots[kRelocMaxCand] = ref_slot;
     if(host)
@@ -208,12 +208,12 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
         }
         std::memcpy(r->h_up + u_depth, w.depth, (size_t)S * npx * 2);
     }
-    WinHead* hh = reinterpret_cast<WinHead*>(r->h_res);
+    WinHead* hh = reinterpret_cast<WinHead*>(r->h_res.get());
     *hh = WinHead{-2, 0, TrackRes{0, 0, -1, 0}}; // (first_event is overwritten by k_tw_scan; checked after the synchronisation)
     hipStream_t s = c->stream;
     MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
     uint8_t* A = r->d_arena;
-    const int32_t* d_slots = reinterpret_cast<const int32_t*>(r->d_up);
+    const int32_t* d_slots = reinterpret_cast<const int32_t*>(r->d_up.get());
     const uint8_t* d_desc = host ? r->d_up + u_desc : w.d_desc;
     const float* d_xy = host ? reinterpret_cast<const float*>(r->d_up + u_xy) : w.d_xy;
     const int32_t* d_n = host ? reinterpret_cast<const int32_t*>(r->d_up + u_n) : w.d_n;
@@ -254,9 +254,9 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
         sa.n_frames = S, sa.n_vote = p.n_vote, sa.ref_vote_pos = p.ref_vote_pos;
         sa.min_matched = p.min_matched, sa.kf_min_landmarks = p.kf_min_landmarks;
         sa.d_event = d_event;
-        sa.h_head = reinterpret_cast<WinHead*>(r->d_h_res);
-        sa.h_rec = reinterpret_cast<WinRec*>(r->d_h_res + r_rec);
-        sa.h_counts = reinterpret_cast<int32_t*>(r->d_h_res + r_counts);
+        sa.h_head = reinterpret_cast<WinHead*>(r->h_res.dev());
+        sa.h_rec = reinterpret_cast<WinRec*>(r->h_res.dev() + r_rec);
+        sa.h_counts = reinterpret_cast<int32_t*>(r->h_res.dev() + r_counts);
         StageScope ts(c, "track_window_scan");
         hipLaunchKernelGGL(k_tw_scan, dim3(1), dim3(256), 0, s, sa);
     }
@@ -275,8 +275,8 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
         ka.out_world = r->d_world + (size_t)new_slot * K * 3;
         ka.out_n = r->d_n + new_slot;
         ka.cap = K;
-        ka.h_res = &reinterpret_cast<WinHead*>(r->d_h_res)->entry;
-        ka.h_src = reinterpret_cast<int32_t*>(r->d_h_res + r_src);
+        ka.h_res = &reinterpret_cast<WinHead*>(r->h_res.dev())->entry;
+        ka.h_src = reinterpret_cast<int32_t*>(r->h_res.dev() + r_src);
         ka.h_kp = ka.h_src + K;
         StageScope ts(c, "track_window_keyframe");
         hipLaunchKernelGGL(k_tw_keyframe, dim3(1), dim3(256), 0, s, ka, d_event, d_n, S, (long long)stride);
@@ -454,9 +454,9 @@ int mslam_hip_track_window_dev(mslam_hip_ctx* c, int first_frame, int n_frames, 
     const size_t K = (size_t)c->p.max_keypoints, f = (size_t)first_frame;
     WindowSource w{};
     // frame f of the batch: descriptors / coordinates / count in output slot f + 1, points in row f of the back-projection
-    w.d_desc = c->d_desc + (f + 1) * K * 32;
-    w.d_xy = c->d_xy + (f + 1) * K * 2;
-    w.d_n = c->d_count + 1 + f;
+    w.d_desc = cur_out(c).desc + (f + 1) * K * 32;
+    w.d_xy = cur_out(c).xy + (f + 1) * K * 2;
+    w.d_n = cur_out(c).count + 1 + f;
     w.d_xyz = c->d_xyz + f * K * 3;
     w.d_valid = c->d_valid + f * K;
     w.stride = (int)K, w.S = n_frames, w.width = c->p.width, w.height = c->p.height, w.cap_from = (int)K;

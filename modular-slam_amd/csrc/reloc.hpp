@@ -49,31 +49,25 @@ struct RelocState
 {
     // ---- keyframe store: slot s holds up to K landmarks at desc + s * K * 32, world + s * K * 3, count n[s]
     int slots = 0;
-    uint8_t* d_desc = nullptr;
-    double* d_world = nullptr;
-    int32_t* d_n = nullptr;
-    int64_t* d_lid = nullptr;             // [slots][K] landmark ids: what makes a landmark the same one in two entries
+    DevBuf<uint8_t> d_desc;
+    DevBuf<double> d_world;
+    DevBuf<int32_t> d_n;
+    DevBuf<int64_t> d_lid;                // [slots][K] landmark ids: what makes a landmark the same one in two entries
     uint64_t serial = 0;                  // creation serial of the last entry made (the first one is 1): part of its fresh ids
     std::unordered_map<int, int> slot_of; // id -> slot
     std::vector<int> free_slots;
     std::vector<int> n_upper;             // per slot: an upper bound of n the host knows (exact for host adds, K for device lifts)
     // ---- scratch of every call that ends in a synchronisation (relocalize, track, track_window, kf_visible), grown on
     // demand by reloc_scratch; the layout inside each block is the call's own
-    uint8_t* h_up = nullptr;  // page-locked staging of the call's one upload
-    uint8_t* d_up = nullptr;
-    size_t up_bytes = 0;
-    uint8_t* d_arena = nullptr; // every device array of one call
-    size_t arena_bytes = 0;
-    uint8_t *h_res = nullptr, *d_h_res = nullptr; // page-locked, device-mapped: what the host reads after the synchronisation
-    size_t res_bytes = 0;
+    PinnedBuf<uint8_t> h_up{/*mapped=*/false};     // page-locked staging of the call's one upload
+    DevBuf<uint8_t> d_up;                          // as large as h_up
+    DevBuf<uint8_t> d_arena;                       // every device array of one call
+    PinnedBuf<uint8_t> h_res;                      // mapped: what the host reads after the synchronisation
     // ---- scratch of mslam_hip_kf_union / mslam_hip_kf_covisible (k_localmap.hip), grown on demand: the hash table
     // ({u64 key, u64 val} buckets), the per-block arrays [win masks | counts | offsets], and the mapped result
     // [needed count, pad | covisibility counts 64 x i32]
-    uint8_t* d_lm_table = nullptr;
-    size_t lm_buckets = 0;
-    uint8_t* d_lm_blocks = nullptr;
-    size_t lm_blocks = 0;
-    uint8_t *h_lm = nullptr, *d_h_lm = nullptr;
+    DevBuf<uint8_t> d_lm_table, d_lm_blocks;
+    PinnedBuf<uint8_t> h_lm;
 };
 
 // A fresh landmark id: (1 << 62) | (serial << 16) | position in the entry.  Entries hold at most 65535 landmarks and the
