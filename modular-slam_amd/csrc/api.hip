@@ -445,6 +445,53 @@ static void build_quad_table(const std::vector<int32_t>& ofs, const std::vector<
     need_out = need;
 }
 
+// octet tables for k_level.hip's eight-pixel lanes: 8 destination pixels share one dword-aligned 16-byte source window;
+// pixel k takes its pair from window dwords (m, m + 1) with m fixed per position (0 0 0 0 1 1 1 2), one further up for the
+// pixels of kOctNeed where the octet's flag says so.  A level with a pixel that fits neither keeps the quad table.
+static void build_oct_table(const std::vector<int32_t>& ofs, const std::vector<uint32_t>& coef, size_t x0, int dw,
+                            std::vector<uint4>& qt, size_t& start_out)
+{
+    static const int dword_of[8] = {0, 0, 0, 0, 1, 1, 1, 2};
+    const int no = (dw + 7) / 8;
+    const size_t start = qt.size() / 5;
+    bool ok = true;
+    for(int o = 0; o < no && ok; ++o)
+    {
+        const uint32_t base = (uint32_t)ofs[x0 + 8 * o] & ~3u;
+        uint32_t sel[8], cf[8], flags = 0;
+        for(int k = 0; k < 8; ++k)
+        {
+            const int dx = std::min(8 * o + k, dw - 1);
+            const int shift = ofs[x0 + dx] - (int)base;
+            const uint32_t a0 = coef[x0 + dx] & 0xFFFF, a1 = coef[x0 + dx] >> 16;
+            if(a0 > 0xFFF || a1 > 0xFFF)
+                ok = false;
+            // bytes shift, shift + 1 lie in dwords (m, m + 1) when 4 m <= shift <= 4 m + 6
+            int m = dword_of[k];
+            bool fits = shift >= 4 * m && shift <= 4 * m + 6;
+            if(!fits && ((kOctNeed >> k) & 1) && shift >= 4 * m + 4 && shift <= 4 * m + 10)
+                ++m, flags |= 1u << k, fits = true;
+            if(!fits && 8 * o + k < dw)
+                ok = false;
+            // (a pixel beyond the row that does not fit: its byte lands in the row's padding, any pair will do)
+            sel[k] = 0x0c010c00u + (uint32_t)(fits ? shift - 4 * m : 0) * 0x00010001u;
+            cf[k] = a0 | (a1 << 16);
+        }
+        qt.push_back(make_uint4(base, flags, sel[0], sel[1]));
+        qt.push_back(make_uint4(sel[2], sel[3], sel[4], sel[5]));
+        qt.push_back(make_uint4(sel[6], sel[7], cf[0], cf[1]));
+        qt.push_back(make_uint4(cf[2], cf[3], cf[4], cf[5]));
+        qt.push_back(make_uint4(cf[6], cf[7], 0, 0));
+    }
+    if(!ok)
+    {
+        qt.resize(start * 5);
+        start_out = SIZE_MAX;
+        return;
+    }
+    start_out = start;
+}
+
 static int create_impl(mslam_hip_ctx* c)
 {
     const mslam_hip_params& p = c->p;
@@ -550,6 +597,13 @@ static int create_impl(mslam_hip_ctx* c)
             qt.push_back(make_uint4(0, 0, 0, 0));
             MSLAM_CHK(c, c->d_rs_qt.alloc(qt.size()));
             MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
+            std::vector<uint4> qt8;
+            c->rs_q8.assign(p.n_levels, SIZE_MAX);
+            for(int l = 1; l < p.n_levels; ++l)
+                build_oct_table(ofs, coef, c->cv_x[l], g.lv[l].w, qt8, c->rs_q8[l]);
+            qt8.push_back(make_uint4(0, 0, 0, 0));
+            MSLAM_CHK(c, c->d_rs_qt8.alloc(qt8.size()));
+            MSLAM_CHK(c, hipMemcpy(c->d_rs_qt8, qt8.data(), qt8.size() * 16, hipMemcpyHostToDevice));
         }
         ofs.push_back(0);
         coef.push_back(0);
@@ -583,6 +637,13 @@ static int create_impl(mslam_hip_ctx* c)
         qt.push_back(make_uint4(0, 0, 0, 0));
         MSLAM_CHK(c, c->d_rs_qt.alloc(qt.size()));
         MSLAM_CHK(c, hipMemcpy(c->d_rs_qt, qt.data(), qt.size() * 16, hipMemcpyHostToDevice));
+        std::vector<uint4> qt8;
+        c->rs_q8.assign(p.n_levels, SIZE_MAX);
+        for(int l = 1; l < p.n_levels; ++l)
+            build_oct_table(ofs, coef, c->rs_x[l], g.lv[l].w, qt8, c->rs_q8[l]);
+        qt8.push_back(make_uint4(0, 0, 0, 0));
+        MSLAM_CHK(c, c->d_rs_qt8.alloc(qt8.size()));
+        MSLAM_CHK(c, hipMemcpy(c->d_rs_qt8, qt8.data(), qt8.size() * 16, hipMemcpyHostToDevice));
         ofs.push_back(0);
         coef.push_back(0);
         MSLAM_CHK(c, c->d_rs_ofs.alloc(ofs.size()));
@@ -644,7 +705,8 @@ static int create_impl(mslam_hip_ctx* c)
                     c->level_chain_waves = 8;
                 c->level_chain_k6 = lk ? std::max(1, std::min(9, atoi(lk))) : 9;
             }
-            c->level_k6 = k ? std::max(1, atoi(k)) : 9; // 9 -> 56-row blocks: the halo re-reads cost 11 % instead of 19 % (32 rows); the step time is the same
+            c->level_k6 = k ? std::max(1, atoi(k)) : 5; // 5 -> 32-row blocks: with eight-pixel lanes a launch has half the waves, and shorter blocks (more waves, 19 % halo rows)
+                                                         // beat 56-row ones (k6 = 9) by 2 % of the step; k6 = 4 and 6 measure the same
             const bool fits = (p.width & 3) == 0 && (double)B * p.width * p.height * 3 < 4294967296.0 &&
                               (double)B * g.slab < 4294901760.0 /* below k_level.hip's kDropLane */ && (size_t)B * (p.width / 4) < (1u << 22) && p.height >= 8;
             int n_fused = fits ? 1 : 0;
@@ -848,11 +910,14 @@ static void enqueue_resize_blur(mslam_hip_ctx* c, int l, const int32_t* yofs, co
     ra.slab = g.slab;
     ra.src_off = sl.offset, ra.sh = sl.h, ra.spitch = sl.pitch;
     ra.dst_off = dl.offset, ra.dw = dl.w, ra.dh = dl.h, ra.dpitch = dl.pitch;
-    ra.qt = c->d_rs_qt + 3 * c->rs_q[l];
+    // batches: eight pixels per lane where the level's windows fit the octet table.  The handful-of-frames launches (fewer
+    // waves than SIMDs, deep prefetch) and the one-launch chain keep four.
+    ra.wide = nf >= 8 && !chain_out && c->rs_q8[l] != SIZE_MAX ? 1 : 0;
+    ra.qt = ra.wide ? c->d_rs_qt8 + 5 * c->rs_q8[l] : c->d_rs_qt + 3 * c->rs_q[l];
     ra.yofs = yofs;
     ra.ycoef = ycoef;
     ra.frame0 = f0, ra.n_frames = nf;
-    ra.quads = (dl.w + 3) / 4;
+    ra.quads = ra.wide ? (dl.w + 7) / 8 : (dl.w + 3) / 4;
     ra.inv_quads = 1.0f / (float)ra.quads;
     // (k6 = 0, the single-frame launches: 2-row blocks pay on the smaller levels only — measured per level, 640x480 pyramid:
     // 333 rows and below 6.0-8.0 -> 4.7-7.6 us, 400 rows and above 7.9-8.2 -> 9.6-10.3 us)
@@ -937,7 +1002,8 @@ static int enqueue_detect(mslam_hip_ctx* c, const uint8_t* d_bgr, int n_frames)
                 ga.W = g.W, ga.H = g.H, ga.pitch = g.lv[0].pitch;
                 ga.slab = g.slab;
                 ga.n_frames = nf, ga.frame0 = f0;
-                ga.quads = g.W / 4;
+                ga.wide = nf >= 8 ? 1 : 0; // batches: eight pixels per lane (k_level.hip)
+                ga.quads = ga.wide ? (g.W + 7) / 8 : g.W / 4;
                 ga.inv_quads = 1.0f / (float)ga.quads;
                 ga.k6 = std::max(k6_batch == 0 && g.H < 380 ? 0 : 1, std::min(k6_batch, (g.H - 2) / 6));
                 ga.blur_tiled = g.blur_tiled;

@@ -159,8 +159,9 @@ struct GrayBlurArgs
     int W, H, pitch;
     unsigned slab;
     int n_frames, frame0;
-    int quads;          // W / 4
+    int quads;          // lane items per row: W / 4, or ceil(W / 8) when wide
     float inv_quads;
+    int wide;           // 1: a lane owns eight adjacent pixels of a row (two quads), 0: four
     int k6;             // rows per block = 6 k6 + 2
     int waves_per_xcd;  // filled in by the launcher
     int blur_tiled;     // Geometry::blur_tiled
@@ -174,12 +175,13 @@ struct ResizeBlurArgs
     uint8_t* blur;
     unsigned slab;
     int src_off, sh, spitch, dst_off, dw, dh, dpitch;
-    const uint4* qt;       // [quads][3], as ResizeColArgs
+    const uint4* qt;       // [quads][3], as ResizeColArgs; wide: [quads][5] (api.hip: build_oct_table)
     const int32_t* yofs;   // [dh]
     const uint32_t* ycoef; // [dh] b0 | b1 << 16
     int frame0, n_frames;
-    int quads;
+    int quads;             // lane items per row: ceil(dw / 4), or ceil(dw / 8) when wide
     float inv_quads;
+    int wide;      // 1: a lane owns eight adjacent destination pixels and one 16-byte source window per source row
     int k6;        // rows per block = 6 k6 + 2 (<= 58: the block's row table lives in lane registers)
     int need_mask; // bit k: pixel k of some quad takes its pair from dwords (1,2)
     int exact;     // 0: INTER_LINEAR, 1: INTER_LINEAR_EXACT
@@ -189,6 +191,10 @@ struct ResizeBlurArgs
     BlurK bk;
 };
 void launch_resize_blur(const ResizeBlurArgs& a, hipStream_t s);
+// eight-pixel lanes: pixel k of a lane takes its source pair from window dwords (m, m + 1), m = 0 0 0 0 1 1 1 2 for
+// k = 0 .. 7, or one dword further up for the pixels of kOctNeed (what scale factors around 1.2 need; levels whose pixels
+// do not fit keep the four-pixel walk)
+constexpr int kOctNeed = 0x48;
 // k_level.hip: gray + blur and every resize + blur level of a batch in ONE launch (a small workgroup walks the levels of its
 // frames in sequence); false = this pyramid cannot take the chain (the caller launches per level)
 constexpr int kChainLevels = 8;

@@ -66,6 +66,8 @@ struct mslam_hip_ctx
     mslam::DevBuf<uint4> d_rs_qt;   // quad tables (k_resize_col), all levels, 3 x uint4 per quad
     std::vector<size_t> rs_q;       // per-level start (in quads) into the quad tables; SIZE_MAX = use the generic kernel
     std::vector<int> rs_need;       // per level: which pixel positions of a quad ever use the upper dword pair
+    mslam::DevBuf<uint4> d_rs_qt8;  // octet tables (k_level.hip's eight-pixel lanes), 5 x uint4 per octet
+    std::vector<size_t> rs_q8;      // per-level start (in octets) into the octet tables; SIZE_MAX = the level keeps the four-pixel walk
     // cv::ORB mode: INTER_LINEAR_EXACT tables (all levels) and per-level quota
     mslam::DevBuf<int32_t> d_cv_ofs;
     mslam::DevBuf<uint32_t> d_cv_coef;
@@ -93,7 +95,7 @@ struct mslam_hip_ctx
     mslam::DevBuf<mslam::BlurWave> d_blur_waves; // k_blur2 wave descriptors of one frame
     int blur_wpf = 0;
     int fused_levels = 0;  // levels 0 .. fused_levels-1 are produced and blurred by k_level.hip; k_blur2 takes the rest
-    int level_k6 = 9;      // k_level.hip: rows per block = 6 k6 + 2
+    int level_k6 = 5;      // k_level.hip: rows per block = 6 k6 + 2
     bool knob_mirror_results = true, knob_zero_copy = true, knob_match_graph = true; // MSLAM_HIP_MIRROR_RESULTS / _ZERO_COPY_FRAME / _MATCH_GRAPH at creation
     size_t zero_copy_max_bytes = 1200000; // frames above this size are copied by DMA instead of read over PCIe by the gray kernel
     int level_chain = 0, level_chain_frames = 2, level_chain_waves = 8, level_chain_k6 = 9; // k_level_chain (k_level.hip)

@@ -10,7 +10,8 @@
 //
 // Shape (both kernels): lanes are flattened over (frame, 4-pixel column) of the level, as in k_resize_col, and walk DOWN
 // a block of R = 6k + 2 rows (+ 6 halo rows, REFLECT_101 at the top and bottom: the row index is wave-uniform, so the
-// reflection is scalar).  Per row a lane owns ONE dword of raw pixels; the 7-tap needs the dword left and right of it:
+// reflection is scalar).  Per row a lane owns ONE dword of raw pixels (batches of 8 frames and more: TWO adjacent dwords, NQ = 2
+// below — 8-byte stores, the inner neighbours in the lane's own registers); the 7-tap needs the dword left and right of it:
 // these come from the neighbouring LANES with two DPP wave shifts (no LDS, no re-load).  Lanes 0 and 63 of every wave
 // are halo lanes (they produce their dword but no output): waves overlap by one lane on each side, 62 of 64 lanes are
 // productive.  At the first / last column of a frame REFLECT_101 replaces the neighbour (v_perm selectors computed once
@@ -29,7 +30,9 @@ namespace mslam
 {
 
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, (short)0, 0, 0)) BufRsrc;
 
 __device__ __forceinline__ uint32_t lv_dot2u(uint32_t pair, uint32_t taps, uint32_t acc)
@@ -79,51 +82,79 @@ __device__ __forceinline__ EdgeSel edge_selectors(int x0, int w)
     return e;
 }
 
-// the blur's register state of one lane: six (row, row+1) pair rows and the previous row's horizontal sums
+// the blur's register state of one lane (NQ quads = 4 NQ pixels per row): six (row, row+1) pair rows
+template <int NQ>
 struct BlurRing
 {
-    uint32_t pr[6][4]; // pr[p][j]: horizontal sums of rows (i - 1, i) of pixel j as a u16 pair, written when row i with (i + 5) % 6 == p arrives
+    uint32_t pr[6][4 * NQ]; // pr[p][j]: horizontal sums of rows (i - 1, i) of pixel j as a u16 pair, written when row i with (i + 5) % 6 == p arrives
 };
 
-// Feeds raw row i (i % 6 == PH) of the lane's column into the filter.  Returns true and the blurred dword of row i - 3
-// (the block's output row i - 6) when EMIT.
-template <int PH, bool EMIT>
-__device__ __forceinline__ uint32_t blur_feed(BlurRing& st, uint32_t B, const EdgeSel& e, const BlurK& k)
+// horizontal 7-tap of one quad B from the window (L, B, R) = (dword left of it, own, dword right of it)
+__device__ __forceinline__ void hblur4(uint32_t L, uint32_t B, uint32_t R, const EdgeSel& e, const BlurK& k, uint32_t* hv)
 {
-    // neighbour dwords: lane l-1's and lane l+1's raw dword of this row (DPP wave shifts; lanes 0 / 63 are halo lanes)
-    const uint32_t L = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)B, 0x138, 0xF, 0xF, true); // wave_shr:1
-    const uint32_t R = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)B, 0x130, 0xF, 0xF, true); // wave_shl:1
     const uint32_t A2 = __builtin_amdgcn_perm(B, L, e.selA);
     const uint32_t B2 = __builtin_amdgcn_perm(B, L, e.selB);
     const uint32_t T = __builtin_amdgcn_perm(B, L, e.selT);
     const uint32_t U = __builtin_amdgcn_perm(R, B, e.selU);
     uint32_t C2; // (T & maskT) | (U & ~maskT) as one instruction (the compiler builds it from two)
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(C2) : "v"(e.maskT), "v"(T), "v"(U));
-    uint32_t hv[4];
     hv[0] = __builtin_amdgcn_udot4(A2, k.ta[0], __builtin_amdgcn_udot4(B2, k.tb[0], 0u, false), false);
     hv[1] = __builtin_amdgcn_udot4(A2, k.ta[1], __builtin_amdgcn_udot4(B2, k.tb[1], __builtin_amdgcn_udot4(C2, k.tc[1], 0u, false), false), false);
     hv[2] = __builtin_amdgcn_udot4(A2, k.ta[2], __builtin_amdgcn_udot4(B2, k.tb[2], __builtin_amdgcn_udot4(C2, k.tc[2], 0u, false), false), false);
     hv[3] = __builtin_amdgcn_udot4(B2, k.tb[3], __builtin_amdgcn_udot4(C2, k.tc[3], 0u, false), false);
-    // pair (row i-1, row i): row i-1's sum is the high half of the pair written one row ago — v_alignbit takes it from there
-    // (no separate copy of the previous row's sums: four registers)
+}
+
+// Feeds raw row i (i % 6 == PH) of the lane's NQ quads into the filter.  When EMIT, out[] is the blurred row i - 3 (the
+// block's output row i - 6).  The quads of a lane are each other's neighbours; only the dword left of the first and right
+// of the last come from the neighbouring lanes.
+template <int PH, bool EMIT, int NQ>
+__device__ __forceinline__ void blur_feed(BlurRing<NQ>& st, const uint32_t (&B)[NQ], const EdgeSel (&e)[NQ], const BlurK& k, uint32_t (&out)[NQ])
+{
+    // neighbour dwords: lane l-1's last and lane l+1's first raw dword of this row (DPP wave shifts; lanes 0 / 63 are halo lanes)
+    const uint32_t L = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)B[NQ - 1], 0x138, 0xF, 0xF, true); // wave_shr:1
+    const uint32_t R = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)B[0], 0x130, 0xF, 0xF, true);      // wave_shl:1
+    uint32_t hv[4 * NQ];
 #pragma unroll
-    for(int j = 0; j < 4; ++j)
+    for(int q = 0; q < NQ; ++q)
+        hblur4(q == 0 ? L : B[q > 0 ? q - 1 : 0], B[q], q == NQ - 1 ? R : B[q < NQ - 1 ? q + 1 : q], e[q], k, hv + 4 * q);
+    // pair (row i-1, row i): row i-1's sum is the high half of the pair written one row ago — v_alignbit takes it from there
+    // (no separate copy of the previous row's sums: four registers per quad)
+#pragma unroll
+    for(int j = 0; j < 4 * NQ; ++j)
         st.pr[(PH + 5) % 6][j] = __builtin_amdgcn_alignbit(hv[j], st.pr[(PH + 4) % 6][j], 16);
-    uint32_t out = 0;
+#pragma unroll
+    for(int q = 0; q < NQ; ++q)
+        out[q] = 0;
     if(EMIT)
     {
-        uint32_t acc[4];
+        uint32_t acc[4 * NQ];
 #pragma unroll
-        for(int j = 0; j < 4; ++j)
+        for(int j = 0; j < 4 * NQ; ++j)
         {
             acc[j] = lv_dot2u(st.pr[PH][j], k.t01, 32768u);           // rows i-6, i-5
             acc[j] = lv_dot2u(st.pr[(PH + 2) % 6][j], k.t23, acc[j]); // rows i-4, i-3
             acc[j] = lv_dot2u(st.pr[(PH + 4) % 6][j], k.t45, acc[j]); // rows i-2, i-1
             acc[j] += __umul24(hv[j], k.t6);                          // row i
         }
-        out = __builtin_amdgcn_perm(acc[1], acc[0], 0x0C0C0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020C0Cu);
+#pragma unroll
+        for(int q = 0; q < NQ; ++q)
+            out[q] = __builtin_amdgcn_perm(acc[4 * q + 1], acc[4 * q], 0x0C0C0602u) | __builtin_amdgcn_perm(acc[4 * q + 3], acc[4 * q + 2], 0x06020C0Cu);
     }
-    return out;
+}
+
+// one dword (NQ = 1) or one 8-byte pair (NQ = 2) per lane; what must not be written is dropped by the buffer's range check
+template <int NQ>
+__device__ __forceinline__ void store_quads(const uint32_t (&v)[NQ], BufRsrc rs, uint32_t voff, uint32_t soff)
+{
+    static_assert(NQ == 1 || NQ == 2, "lane width");
+    if constexpr(NQ == 1)
+        __builtin_amdgcn_raw_buffer_store_b32(v[0], rs, (int)voff, (int)soff, 0);
+    else
+    {
+        u32x2 p;
+        p.x = v[0], p.y = v[1];
+        __builtin_amdgcn_raw_buffer_store_b64(p, rs, (int)voff, (int)soff, 0);
+    }
 }
 
 // REFLECT_101 of a wave-uniform row index (|y|, then min(y, 2 (h - 1) - y))
@@ -171,10 +202,16 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I..
 // DEEP = N > 0: the launch is a handful of waves (the synchronous single-frame call) and lasts as long as ONE wave's walk, so
 // all N = R + 6 rows of the block are requested before the first is used (N x 3 registers) instead of two rows ahead: one
 // memory round trip per block instead of one per two rows.
-// the walk of ONE wave: wave gw of the launch's (frame, quad) items, row block `by`
-template <bool TILED, int DEEP>
+// NQ: quads per lane.  1: a lane owns one dword of every row (the handful-of-frames launches and k_level_chain).  2: a
+// lane owns eight adjacent pixels — one 8-byte raw and one 8-byte blurred store per row, the inner quad boundary inside the
+// lane (half the store instructions, DPP exchanges and halo lanes per pixel).  A row whose width is 4 (mod 8) ends in the
+// middle of its last lane: that lane's second quad re-reads the first one's source (no read past the batch) and its
+// results land in the row's padding (pitch is a multiple of 16); the reflection selectors know the true width.
+// the walk of ONE wave: wave gw of the launch's (frame, lane item) items, row block `by`
+template <bool TILED, int DEEP, int NQ>
 __device__ __forceinline__ void gray_blur_wave(const GrayBlurArgs& a, const int gw, const int by)
 {
+    static_assert(DEEP == 0 || NQ == 1, "the deep-prefetch instances are 4-pixel walks");
     const int lane = threadIdx.x & 63;
     const int n_items = a.n_frames * a.quads;
     const int item_raw = gw * 62 - 1 + lane;
@@ -184,19 +221,26 @@ __device__ __forceinline__ void gray_blur_wave(const GrayBlurArgs& a, const int 
     const int item = max(0, min(item_raw, n_items - 1));
     const int f = (int)(((float)item + 0.5f) * a.inv_quads); // item / quads, exact for items < 2^22 (host check)
     const int q = item - f * a.quads;
+    const int x0 = 4 * NQ * q;
     const int R = 6 * a.k6 + 2;
     const int y0 = min(by * R, a.H - R); // the last block ends at the last row (host: R <= H)
-    const EdgeSel e = edge_selectors(4 * q, a.W);
-    const uint32_t src_v = (uint32_t)(f + a.frame0) * (uint32_t)(a.W * a.H * 3) + 12u * (uint32_t)q;
+    EdgeSel e[NQ];
+    uint32_t src_v[NQ];
+#pragma unroll
+    for(int j = 0; j < NQ; ++j)
+    {
+        e[j] = edge_selectors(x0 + 4 * j, a.W);
+        src_v[j] = (uint32_t)(f + a.frame0) * (uint32_t)(a.W * a.H * 3) + 3u * (uint32_t)(x0 + 4 * j < a.W ? x0 + 4 * j : x0);
+    }
     // Every lane stores every row, unconditionally: the compiler can then count the stores in its vmcnt waits and the
     // loads stay two rows ahead (a store that may or may not issue makes every counted wait stricter).  The stores are
     // buffer stores: the lane's column offset rides in the vector operand, the wave-uniform row offset in the scalar one (no
     // vector address arithmetic per row), and what must not be written is dropped by the buffer's range check — a halo lane
     // carries an offset beyond the buffer (kDropLane), a halo row is stored against an empty buffer (0 records).  Neither
     // reaches the cache.  (Round 3 first wrote those to dump words behind the slab: one more write request per store.)
-    const uint32_t col_v = (uint32_t)(f + a.frame0) * a.slab + 4u * (uint32_t)q;
+    const uint32_t col_v = (uint32_t)(f + a.frame0) * a.slab + (uint32_t)x0;
     const uint32_t raw_v = productive ? col_v : kDropLane;
-    const uint32_t blur_v = !productive ? kDropLane : TILED ? (uint32_t)(f + a.frame0) * a.slab + tiled_off((unsigned)a.pitch, 4 * q, 0) : col_v;
+    const uint32_t blur_v = !productive ? kDropLane : TILED ? (uint32_t)(f + a.frame0) * a.slab + tiled_off((unsigned)a.pitch, x0, 0) : col_v;
     const uint32_t n_rec = (uint32_t)(a.frame0 + a.n_frames) * a.slab;
     const BufRsrc blur_rs = __builtin_amdgcn_make_buffer_rsrc(a.blur, 0, (int)n_rec, 0x00020000);
     const uint32_t row_bytes = (uint32_t)a.W * 3u;
@@ -204,34 +248,46 @@ __device__ __forceinline__ void gray_blur_wave(const GrayBlurArgs& a, const int 
     // buffer loads: the wave-uniform row offset rides in the scalar offset operand, the lane's offset in the vector one —
     // no 64-bit vector address arithmetic per load (the compiler built a v_mad_u64_u32 per row for `row pointer + lane offset`)
     const BufRsrc bgr_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.bgr), 0, -1, 0x00020000);
+    struct BgrRow
+    {
+        Bgr3 q[NQ];
+    };
     auto load = [&](int i) {
         const int y = reflect_row(y0 - 3 + i, a.H);
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(bgr_rs, (int)src_v, (int)((uint32_t)y * row_bytes), 0);
-        return Bgr3{v.x, v.y, v.z};
-    };
-    BlurRing st;
+        BgrRow r;
 #pragma unroll
-    for(int j = 0; j < 4; ++j)
+        for(int j = 0; j < NQ; ++j)
+        {
+            const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(bgr_rs, (int)src_v[j], (int)((uint32_t)y * row_bytes), 0);
+            r.q[j] = Bgr3{v.x, v.y, v.z};
+        }
+        return r;
+    };
+    BlurRing<NQ> st;
+#pragma unroll
+    for(int j = 0; j < 4 * NQ; ++j)
         st.pr[4][j] = 0; // (row 0 pairs with "row -1": never looked at, but defined)
     // one row: i = i0 + PH, PH = i % 6 (static); RAW: the row belongs to the block (rows 3 .. R+2), BLUR: i >= 6
-    auto compute = [&](auto ph, auto emit, auto sraw, int i, bool raw, const Bgr3& w) {
+    auto compute = [&](auto ph, auto emit, auto sraw, int i, bool raw, const BgrRow& w) {
         constexpr int PH = decltype(ph)::value;
         constexpr bool EMIT = decltype(emit)::value;
         constexpr bool SRAW = decltype(sraw)::value; // false for block rows 0 .. 2: no raw store is emitted at all
-        const uint32_t g = lv_gray4(w.a, w.b, w.c);
+        uint32_t g[NQ], o[NQ];
+#pragma unroll
+        for(int j = 0; j < NQ; ++j)
+            g[j] = lv_gray4(w.q[j].a, w.q[j].b, w.q[j].c);
         if(SRAW) // rows 3 .. R+2 need no reflection; a halo row is stored against an empty buffer
-            __builtin_amdgcn_raw_buffer_store_b32(g, __builtin_amdgcn_make_buffer_rsrc(a.pyr, 0, __builtin_amdgcn_readfirstlane(raw ? (int)n_rec : 0), 0x00020000),
-                                                  (int)raw_v, (y0 - 3 + i) * a.pitch, 0);
-        const uint32_t o = blur_feed<PH, EMIT>(st, g, e, a.bk);
+            store_quads<NQ>(g, __builtin_amdgcn_make_buffer_rsrc(a.pyr, 0, __builtin_amdgcn_readfirstlane(raw ? (int)n_rec : 0), 0x00020000), raw_v,
+                            (uint32_t)((y0 - 3 + i) * a.pitch));
+        blur_feed<PH, EMIT, NQ>(st, g, e, a.bk, o);
         if(EMIT)
-            __builtin_amdgcn_raw_buffer_store_b32(o, blur_rs, (int)blur_v,
-                                                  (int)(TILED ? tiled_off((unsigned)a.pitch, 0, y0 - 6 + i) : (unsigned)((y0 - 6 + i) * a.pitch)), 0);
+            store_quads<NQ>(o, blur_rs, blur_v, TILED ? tiled_off((unsigned)a.pitch, 0, y0 - 6 + i) : (unsigned)((y0 - 6 + i) * a.pitch));
     };
     using std::integral_constant;
     if constexpr(DEEP > 0)
     {
         // (host: R + 6 == DEEP) every row of the block in flight at once, then the rows in order
-        Bgr3 all[DEEP];
+        BgrRow all[DEEP];
 #pragma unroll
         for(int i = 0; i < DEEP; ++i)
             all[i] = load(i);
@@ -243,7 +299,7 @@ __device__ __forceinline__ void gray_blur_wave(const GrayBlurArgs& a, const int 
         }, std::make_integer_sequence<int, DEEP>{});
         return;
     }
-    Bgr3 ring[3];
+    BgrRow ring[3];
     ring[0] = load(0);
     ring[1] = load(1);
     auto row = [&](auto ph, auto emit, auto sraw, int i, bool raw) {
@@ -275,14 +331,14 @@ __device__ __forceinline__ void gray_blur_wave(const GrayBlurArgs& a, const int 
 #undef MSLAM_ROW
 }
 
-template <bool TILED, int DEEP>
+template <bool TILED, int DEEP, int NQ>
 __global__ __launch_bounds__(256) void k_gray_blur(GrayBlurArgs a)
 {
     // XCD-aware wave numbering: workgroups go to the 8 XCDs round-robin by linear id (gridDim.x is a multiple of 8, so the
     // XCD of a workgroup is blockIdx.x & 7 for every row block).  Each XCD gets a contiguous eighth of the waves: waves that
     // are neighbours in the image (shared 128-byte lines at their edges, shared halo rows between row blocks) meet in one L2.
     const int gw = __builtin_amdgcn_readfirstlane((int)((blockIdx.x & 7) * a.waves_per_xcd + (blockIdx.x >> 3) * 4 + (threadIdx.x >> 6)));
-    gray_blur_wave<TILED, DEEP>(a, gw, (int)blockIdx.y);
+    gray_blur_wave<TILED, DEEP, NQ>(a, gw, (int)blockIdx.y);
 }
 
 // ---- level l > 0: resize + blur --------------------------------------------------------------------------------------
@@ -292,25 +348,33 @@ __global__ __launch_bounds__(256) void k_gray_blur(GrayBlurArgs a)
 // (hA, hB) with their wave-uniform row numbers: a row re-uses them, advances by one source row, or reloads both (scale
 // factors up to 2, and the reflected rows at the top / bottom of the level, which walk backwards).  The source rows of
 // destination row i+1 are requested while row i is computed (PA / PB).
-struct Raw3
+template <int NQ>
+struct SrcWin
 {
-    uint32_t d0, d1, d2;
+    uint32_t d[NQ + 2]; // the lane's source-row window: 12 bytes for one quad, 16 for two
 };
+template <int NQ>
 struct HRow
 {
-    uint32_t h[4];
+    uint32_t h[4 * NQ];
 };
+// the window dword pixel k of an eight-pixel lane takes the low byte of its (S[x], S[x+1]) pair from, before its NEED step
+__device__ __forceinline__ constexpr int oct_dword(int k) { return k < 4 ? 0 : k < 7 ? 1 : 2; }
 
-// NEED: bit k set = pixel k of a quad may take its (S[x], S[x+1]) pair from window dwords (1,2) instead of (0,1) — a
-// compile-time superset of the level's mask (at scale 1.2 only the fourth pixel ever does), so that the other pixels carry
-// no per-lane selects
+// NEED: bit k set = pixel k of a lane may take its (S[x], S[x+1]) pair one window dword further up than its fixed place
+// (NQ = 1: dwords (1,2) instead of (0,1); NQ = 2: oct_dword(k) + 1, kOctNeed at most) — a compile-time superset of the
+// level's mask (at scale 1.2 only the fourth pixel of a quad ever does), so that the other pixels carry no per-lane selects
 // DEEP = N > 0: as in k_gray_blur — both source-row windows of all N = R + 6 rows of the block are requested up front (the
 // single-frame launches, whose duration is one wave's walk: 6 N registers)
-// the walk of ONE wave: wave gw of the launch's (frame, quad) items, row block `by`.  COH: the source level was written by
+// NQ = 2: the eight-pixel lane of k_gray_blur; one 16-byte window per source row (host table: build_oct_table)
+// the walk of ONE wave: wave gw of the launch's (frame, lane item) items, row block `by`.  COH: the source level was written by
 // this very kernel (k_level_chain): its loads go past the CU's L1 (sc0).
-template <bool EXACT, int NEED, bool TILED, int DEEP, bool COH>
+template <bool EXACT, int NEED, bool TILED, int DEEP, bool COH, int NQ>
 __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const int gw, const int by)
 {
+    static_assert(DEEP == 0 || NQ == 1, "the deep-prefetch instances are 4-pixel walks");
+    static_assert(NQ == 1 || (NEED & ~kOctNeed) == 0, "an eight-pixel window has two stepping pixels");
+    constexpr int NP = 4 * NQ;
     const int lane = threadIdx.x & 63;
     const int n_items = a.n_frames * a.quads;
     const int R = 6 * a.k6 + 2; // host: R + 6 <= 64 (the block's row table lives in lane registers), R <= dh
@@ -327,42 +391,69 @@ __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const 
     const int item = max(0, min(item_raw, n_items - 1));
     const int f = (int)(((float)item + 0.5f) * a.inv_quads); // item / quads, exact for items < 2^22 (host check)
     const int qx = item - f * a.quads;
-    const EdgeSel e = edge_selectors(4 * qx, a.dw);
-    const uint4 t0 = a.qt[3 * qx], t1 = a.qt[3 * qx + 1], t2 = a.qt[3 * qx + 2];
-    const uint32_t sel[4] = {t0.z, t0.w, t1.x, t1.y}, coef[4] = {t1.z, t1.w, t2.x, t2.y};
-    const uint32_t src_v = (uint32_t)(f + a.frame0) * a.slab + t0.x;
+    const int x0 = NP * qx;
+    EdgeSel e[NQ];
+#pragma unroll
+    for(int j = 0; j < NQ; ++j)
+        e[j] = edge_selectors(x0 + 4 * j, a.dw);
+    uint32_t sel[NP], coef[NP], win_off, up_flags;
+    if constexpr(NQ == 1)
+    {
+        const uint4 t0 = a.qt[3 * qx], t1 = a.qt[3 * qx + 1], t2 = a.qt[3 * qx + 2];
+        win_off = t0.x, up_flags = t0.y;
+        sel[0] = t0.z, sel[1] = t0.w, sel[2] = t1.x, sel[3] = t1.y;
+        coef[0] = t1.z, coef[1] = t1.w, coef[2] = t2.x, coef[3] = t2.y;
+    }
+    else
+    {
+        const uint4 t0 = a.qt[5 * qx], t1 = a.qt[5 * qx + 1], t2 = a.qt[5 * qx + 2], t3 = a.qt[5 * qx + 3], t4 = a.qt[5 * qx + 4];
+        win_off = t0.x, up_flags = t0.y;
+        sel[0] = t0.z, sel[1] = t0.w, sel[2] = t1.x, sel[3] = t1.y, sel[4] = t1.z, sel[5] = t1.w, sel[6] = t2.x, sel[7] = t2.y;
+        coef[0] = t2.z, coef[1] = t2.w, coef[2] = t3.x, coef[3] = t3.y, coef[4] = t3.z, coef[5] = t3.w, coef[6] = t4.x, coef[7] = t4.y;
+    }
+    const uint32_t src_v = (uint32_t)(f + a.frame0) * a.slab + win_off;
     // unconditional buffer stores, halo lanes / halo rows dropped by the range check: see k_gray_blur
-    const uint32_t col_v = (uint32_t)(f + a.frame0) * a.slab + (uint32_t)a.dst_off + 4u * (uint32_t)qx;
+    const uint32_t col_v = (uint32_t)(f + a.frame0) * a.slab + (uint32_t)a.dst_off + (uint32_t)x0;
     const uint32_t raw_v = productive ? col_v : kDropLane;
     const uint32_t blur_v = !productive ? kDropLane
-                            : TILED   ? (uint32_t)(f + a.frame0) * a.slab + (uint32_t)a.dst_off + tiled_off((unsigned)a.dpitch, 4 * qx, 0)
+                            : TILED   ? (uint32_t)(f + a.frame0) * a.slab + (uint32_t)a.dst_off + tiled_off((unsigned)a.dpitch, x0, 0)
                                       : col_v;
     const uint32_t n_rec = (uint32_t)(a.frame0 + a.n_frames) * a.slab;
     const BufRsrc blur_rs = __builtin_amdgcn_make_buffer_rsrc(a.blur, 0, (int)n_rec, 0x00020000);
     const uint8_t* src_lv = a.pyr + a.src_off;
 
-    const BufRsrc src_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src_lv), 0, -1, 0x00020000);
-    auto load = [&](int sy) { // (buffer load: scalar row offset + vector lane offset, see k_gray_blur)
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(src_rs, (int)src_v, (int)((uint32_t)sy * (uint32_t)a.spitch), COH ? 1 : 0);
-        return Raw3{v.x, v.y, v.z};
+    auto load_rs = [&](BufRsrc rs, int sy) { // (buffer load: scalar row offset + vector lane offset, see k_gray_blur)
+        SrcWin<NQ> w;
+        if constexpr(NQ == 1)
+        {
+            const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)src_v, (int)((uint32_t)sy * (uint32_t)a.spitch), COH ? 1 : 0);
+            w.d[0] = v.x, w.d[1] = v.y, w.d[2] = v.z;
+        }
+        else
+        {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)src_v, (int)((uint32_t)sy * (uint32_t)a.spitch), COH ? 1 : 0);
+            w.d[0] = v.x, w.d[1] = v.y, w.d[2] = v.z, w.d[3] = v.w;
+        }
+        return w;
     };
+    const BufRsrc src_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src_lv), 0, -1, 0x00020000);
+    auto load = [&](int sy) { return load_rs(src_rs, sy); };
     auto load_if = [&](int sy, bool need) {
         // (readfirstlane: the record count must be a scalar register for the compiler, else it wraps the load in a waterfall loop)
-        const BufRsrc rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src_lv), 0, __builtin_amdgcn_readfirstlane(need ? -1 : 0), 0x00020000);
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)src_v, (int)((uint32_t)sy * (uint32_t)a.spitch), COH ? 1 : 0);
-        return Raw3{v.x, v.y, v.z};
+        return load_rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src_lv), 0, __builtin_amdgcn_readfirstlane(need ? -1 : 0), 0x00020000), sy);
     };
-    auto hinterp = [&](const Raw3& w) {
-        HRow r;
+    auto hinterp = [&](const SrcWin<NQ>& w) {
+        HRow<NQ> r;
 #pragma unroll
-        for(int k = 0; k < 4; ++k)
+        for(int k = 0; k < NP; ++k)
         {
-            uint32_t lo = w.d0, hi = w.d1;
+            const int m = NQ == 1 ? 0 : oct_dword(k);
+            uint32_t lo = w.d[m], hi = w.d[m + 1];
             if(NEED & (1 << k))
             {
-                const bool up = (t0.y >> k) & 1u;
-                lo = up ? w.d1 : w.d0;
-                hi = up ? w.d2 : w.d1;
+                const bool up = (up_flags >> k) & 1u;
+                lo = up ? w.d[m + 1] : w.d[m];
+                hi = up ? w.d[m + 2 < NQ + 2 ? m + 2 : m + 1] : w.d[m + 1]; // (m + 2 is inside the window wherever NEED allows the step)
             }
             const uint32_t pr = __builtin_amdgcn_perm(hi, lo, sel[k]);
             u16x2_t pv, cv;
@@ -381,15 +472,15 @@ __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const 
         sy1 = max(0, min(t + 1, a.sh - 1));
     };
 
-    BlurRing st;
+    BlurRing<NQ> st;
 #pragma unroll
-    for(int j = 0; j < 4; ++j)
+    for(int j = 0; j < NP; ++j)
         st.pr[4][j] = 0; // (row 0 pairs with "row -1": never looked at, but defined)
-    HRow hA{}, hB{};
+    HRow<NQ> hA{}, hB{};
     int rowA = -1, rowB = -1; // wave-uniform: which source rows hA / hB hold
     // both source rows of every destination row are requested two rows ahead, unconditionally (static 3-deep ring: the
     // compiler can count its vmcnt waits); whether a row is interpolated again or taken over from hB is decided at use
-    auto compute = [&](auto ph, auto emit, auto sraw, int i, bool raw, int sy0, int sy1, const Raw3& wA, const Raw3& wB) {
+    auto compute = [&](auto ph, auto emit, auto sraw, int i, bool raw, int sy0, int sy1, const SrcWin<NQ>& wA, const SrcWin<NQ>& wB) {
         constexpr int PH = decltype(ph)::value;
         constexpr bool EMIT = decltype(emit)::value;
         constexpr bool SRAW = decltype(sraw)::value; // false for block rows 0 .. 2: no raw store is emitted at all
@@ -423,54 +514,55 @@ __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const 
         }
         const uint32_t yc = (uint32_t)__builtin_amdgcn_readlane((int)my_yc, i);
         const uint32_t b0 = yc & 0xFFFF, b1 = yc >> 16;
-        auto blend = [&](const HRow& h0, const HRow& h1) {
-            uint32_t r = 0;
-            if(EXACT)
-            {
-                uint32_t acc[4];
+        auto blend = [&](const HRow<NQ>& h0, const HRow<NQ>& h1, uint32_t (&r)[NQ]) {
 #pragma unroll
-                for(int k = 0; k < 4; ++k) // h <= 65280, weights <= 256: the 24-bit multiply-adds are exact
-                    acc[k] = __umul24(b1, h1.h[k]) + (__umul24(b0, h0.h[k]) + 32768u);
-                r = __builtin_amdgcn_perm(acc[1], acc[0], 0x0C0C0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020C0Cu);
-            }
-            else
+            for(int j = 0; j < NQ; ++j)
             {
-                const uint32_t b0s = b0 << 16, b1s = b1 << 16; // (b * h) >> 16 as the high half of (b << 16) * h
-                uint32_t v[4];
+                if(EXACT)
+                {
+                    uint32_t acc[4];
 #pragma unroll
-                for(int k = 0; k < 4; ++k)
-                    v[k] = __umulhi(h0.h[k], b0s) + __umulhi(h1.h[k], b1s) + 2u; // <= 1022; the pixel is v >> 2
-                // two sums per register, ONE shift per pair (a pair's low bits fall into bits 14, 15 of the other's field,
-                // which no byte of the result is taken from), one byte gather
-                const uint32_t p01 = (v[0] | (v[1] << 16)) >> 2, p23 = (v[2] | (v[3] << 16)) >> 2;
-                r = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+                    for(int k = 0; k < 4; ++k) // h <= 65280, weights <= 256: the 24-bit multiply-adds are exact
+                        acc[k] = __umul24(b1, h1.h[4 * j + k]) + (__umul24(b0, h0.h[4 * j + k]) + 32768u);
+                    r[j] = __builtin_amdgcn_perm(acc[1], acc[0], 0x0C0C0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020C0Cu);
+                }
+                else
+                {
+                    const uint32_t b0s = b0 << 16, b1s = b1 << 16; // (b * h) >> 16 as the high half of (b << 16) * h
+                    uint32_t v[4];
+#pragma unroll
+                    for(int k = 0; k < 4; ++k)
+                        v[k] = __umulhi(h0.h[4 * j + k], b0s) + __umulhi(h1.h[4 * j + k], b1s) + 2u; // <= 1022; the pixel is v >> 2
+                    // two sums per register, ONE shift per pair (a pair's low bits fall into bits 14, 15 of the other's field,
+                    // which no byte of the result is taken from), one byte gather
+                    const uint32_t p01 = (v[0] | (v[1] << 16)) >> 2, p23 = (v[2] | (v[3] << 16)) >> 2;
+                    r[j] = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+                }
             }
-            return r;
         };
-        uint32_t g;
+        uint32_t g[NQ], o[NQ];
         if(sy0 == rowA)
         {
             asm volatile("");
-            g = blend(hA, hB);
+            blend(hA, hB, g);
         }
         else // a re-used pair whose lower row is hB as well (up-scaling only)
         {
             asm volatile("");
-            g = blend(hB, hB);
+            blend(hB, hB, g);
         }
         if(SRAW) // rows 3 .. R+2 need no reflection; a halo row is stored against an empty buffer (see k_gray_blur)
-            __builtin_amdgcn_raw_buffer_store_b32(g, __builtin_amdgcn_make_buffer_rsrc(a.pyr, 0, __builtin_amdgcn_readfirstlane(raw ? (int)n_rec : 0), 0x00020000),
-                                                  (int)raw_v, (y0 - 3 + i) * a.dpitch, 0);
-        const uint32_t o = blur_feed<PH, EMIT>(st, g, e, a.bk);
+            store_quads<NQ>(g, __builtin_amdgcn_make_buffer_rsrc(a.pyr, 0, __builtin_amdgcn_readfirstlane(raw ? (int)n_rec : 0), 0x00020000), raw_v,
+                            (uint32_t)((y0 - 3 + i) * a.dpitch));
+        blur_feed<PH, EMIT, NQ>(st, g, e, a.bk, o);
         if(EMIT)
-            __builtin_amdgcn_raw_buffer_store_b32(o, blur_rs, (int)blur_v,
-                                                  (int)(TILED ? tiled_off((unsigned)a.dpitch, 0, y0 - 6 + i) : (unsigned)((y0 - 6 + i) * a.dpitch)), 0);
+            store_quads<NQ>(o, blur_rs, blur_v, TILED ? tiled_off((unsigned)a.dpitch, 0, y0 - 6 + i) : (unsigned)((y0 - 6 + i) * a.dpitch));
     };
     using std::integral_constant;
     if constexpr(DEEP > 0)
     {
         // (host: R + 6 == DEEP) both windows of every row of the block in flight at once, then the rows in order
-        Raw3 allA[DEEP], allB[DEEP];
+        SrcWin<NQ> allA[DEEP], allB[DEEP];
 #pragma unroll
         for(int i = 0; i < DEEP; ++i)
         {
@@ -490,7 +582,7 @@ __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const 
         }, std::make_integer_sequence<int, DEEP>{});
         return;
     }
-    Raw3 RA[3], RB[3];
+    SrcWin<NQ> RA[3], RB[3];
     // the source rows of block rows i and i + 1 are carried from the iterations that requested them (one table lookup per row)
     int c0_y0, c0_y1, c1_y0, c1_y1;
     rows_of(0, c0_y0, c0_y1);
@@ -539,12 +631,12 @@ __device__ __forceinline__ void resize_blur_wave(const ResizeBlurArgs& a, const 
 #undef MSLAM_ROW
 }
 
-template <bool EXACT, int NEED, bool TILED, int DEEP>
+template <bool EXACT, int NEED, bool TILED, int DEEP, int NQ>
 __global__ __launch_bounds__(256) void k_resize_blur(ResizeBlurArgs a)
 {
     // XCD-aware wave numbering, as in k_gray_blur
     const int gw = __builtin_amdgcn_readfirstlane((int)((blockIdx.x & 7) * a.waves_per_xcd + (blockIdx.x >> 3) * 4 + (threadIdx.x >> 6)));
-    resize_blur_wave<EXACT, NEED, TILED, DEEP, false>(a, gw, (int)blockIdx.y);
+    resize_blur_wave<EXACT, NEED, TILED, DEEP, false, NQ>(a, gw, (int)blockIdx.y);
 }
 
 // ---- the whole level chain of a group of frames in ONE launch (round 6) ------------------------------------------------
@@ -575,7 +667,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_level_chain(LevelChainArgs ch)
         for(int item = wave; item < nwx * nby; item += WAVES)
         {
             const int by = item / nwx;
-            gray_blur_wave<TILED, 0>(a, item - by * nwx, by);
+            gray_blur_wave<TILED, 0, 1>(a, item - by * nwx, by);
         }
     }
 #pragma unroll 1
@@ -595,7 +687,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_level_chain(LevelChainArgs ch)
         for(int item = wave; item < nwx * nby; item += WAVES)
         {
             const int by = item / nwx;
-            resize_blur_wave<EXACT, NEED, TILED, 0, COH>(a, item - by * nwx, by);
+            resize_blur_wave<EXACT, NEED, TILED, 0, COH, 1>(a, item - by * nwx, by);
         }
     }
 }
@@ -662,13 +754,21 @@ void launch_resize_blur(const ResizeBlurArgs& a, hipStream_t s)
     ResizeBlurArgs b = a;
     b.waves_per_xcd = ((n_waves + 31) / 32) * 4; // whole workgroups per XCD
     dim3 grid(8 * (b.waves_per_xcd / 4), (a.dh + R - 1) / R);
+    if(a.wide) // eight-pixel lanes (a.qt is the octet table): one instance per EXACT, both stepping pixels carry their select
+    {
+#define MSLAM_RB8(E) do { if(a.blur_tiled) hipLaunchKernelGGL((k_resize_blur<E, kOctNeed, true, 0, 2>), grid, dim3(256), 0, s, b); \
+                         else hipLaunchKernelGGL((k_resize_blur<E, kOctNeed, false, 0, 2>), grid, dim3(256), 0, s, b); } while(0)
+        if(a.exact) MSLAM_RB8(true); else MSLAM_RB8(false);
+#undef MSLAM_RB8
+        return;
+    }
     const int need = (a.need_mask & ~8) == 0 ? (a.need_mask ? 8 : 0) : (a.need_mask & ~12) == 0 ? 12 : 15;
     // a handful of frames (always_load) with 2- or 8-row blocks: the deep-prefetch instances (MSLAM_HIP_LEVEL_DEEP=0: off)
     static const bool deep_env = [] { const char* e = getenv("MSLAM_HIP_LEVEL_DEEP"); return !e || atoi(e) != 0; }();
     const int deep = (a.always_load && deep_env && a.k6 <= 1) ? R + 6 : 0;
-#define MSLAM_RB3(E, N, T) do { if(deep == 8) hipLaunchKernelGGL((k_resize_blur<E, N, T, 8>), grid, dim3(256), 0, s, b); \
-                               else if(deep == 14) hipLaunchKernelGGL((k_resize_blur<E, N, T, 14>), grid, dim3(256), 0, s, b); \
-                               else hipLaunchKernelGGL((k_resize_blur<E, N, T, 0>), grid, dim3(256), 0, s, b); } while(0)
+#define MSLAM_RB3(E, N, T) do { if(deep == 8) hipLaunchKernelGGL((k_resize_blur<E, N, T, 8, 1>), grid, dim3(256), 0, s, b); \
+                               else if(deep == 14) hipLaunchKernelGGL((k_resize_blur<E, N, T, 14, 1>), grid, dim3(256), 0, s, b); \
+                               else hipLaunchKernelGGL((k_resize_blur<E, N, T, 0, 1>), grid, dim3(256), 0, s, b); } while(0)
 #define MSLAM_RB(E, N) do { if(a.blur_tiled) MSLAM_RB3(E, N, true); else MSLAM_RB3(E, N, false); } while(0)
     if(a.exact)
     {
@@ -689,11 +789,19 @@ void launch_gray_blur(const GrayBlurArgs& a, hipStream_t s)
     GrayBlurArgs b = a;
     b.waves_per_xcd = ((n_waves + 31) / 32) * 4; // whole workgroups per XCD
     dim3 grid(8 * (b.waves_per_xcd / 4), (a.H + R - 1) / R);
+    if(a.wide) // eight-pixel lanes
+    {
+        if(a.blur_tiled)
+            hipLaunchKernelGGL((k_gray_blur<true, 0, 2>), grid, dim3(256), 0, s, b);
+        else
+            hipLaunchKernelGGL((k_gray_blur<false, 0, 2>), grid, dim3(256), 0, s, b);
+        return;
+    }
     static const bool deep_env = [] { const char* e = getenv("MSLAM_HIP_LEVEL_DEEP"); return !e || atoi(e) != 0; }();
     const int deep = (a.n_frames < 8 && deep_env && a.k6 <= 1) ? R + 6 : 0;
-#define MSLAM_GB(T) do { if(deep == 8) hipLaunchKernelGGL((k_gray_blur<T, 8>), grid, dim3(256), 0, s, b); \
-                        else if(deep == 14) hipLaunchKernelGGL((k_gray_blur<T, 14>), grid, dim3(256), 0, s, b); \
-                        else hipLaunchKernelGGL((k_gray_blur<T, 0>), grid, dim3(256), 0, s, b); } while(0)
+#define MSLAM_GB(T) do { if(deep == 8) hipLaunchKernelGGL((k_gray_blur<T, 8, 1>), grid, dim3(256), 0, s, b); \
+                        else if(deep == 14) hipLaunchKernelGGL((k_gray_blur<T, 14, 1>), grid, dim3(256), 0, s, b); \
+                        else hipLaunchKernelGGL((k_gray_blur<T, 0, 1>), grid, dim3(256), 0, s, b); } while(0)
     if(a.blur_tiled)
         MSLAM_GB(true);
     else
