@@ -156,8 +156,63 @@ enum
 int mslam_hip_set_matcher(mslam_hip_ctx* ctx, int kind);
 int mslam_hip_get_matcher(const mslam_hip_ctx* ctx);
 /* which kernel the last matcher launch of this context took: 0 = none yet, 1 = matrix cores, 2 = xor/popcount (AUTO decides on
- * the CAPACITY of the train side: max_keypoints on the batched path, n_from on the host-pointer calls) */
+ * the CAPACITY of the train side: max_keypoints on the batched path, n_from on the host-pointer calls), 3 = the guided stage
+ * below */
 int mslam_hip_last_match_kernel(const mslam_hip_ctx* ctx);
+
+/* ---- guided matching: landmarks matched in a window round their projection ---------------------------
+ * matchLandmarks (rgbd_feature_frontend.cpp:237-254) matches the local map's landmarks against ALL keypoints of the frame
+ * and carries "TODO: use boost geometry rtree for keypoints" (:242); track() projects every matched landmark with
+ * currentPose (:300), but only to draw it.  Here the projection gates the matcher, as ORB-SLAM's SearchByProjection does.
+ *
+ * Inputs: keypoints i < n_kp (descriptor 32 B, xy f32), landmarks j < n_lm (descriptor 32 B, world point 3 x f64), a pose
+ * world -> camera R (9 f64, row-major) and t (3 f64), the intrinsics, a frame extent width x height, radius (f64, > 0).
+ *
+ *   projection   SAME as mslam_hip_kf_visible's, in f64 with every operation rounded on its own:
+ *                c_r = ((R[r][0] X + R[r][1] Y) + R[r][2] Z) + t[r],  u = (c_0 / c_2) fx + cx,  v = (c_1 / c_2) fy + cy.
+ *   candidate    keypoint i is a candidate of landmark j iff  c_2 > 0,  x_i and y_i are finite with
+ *                0 <= (double)x_i < width and 0 <= (double)y_i < height,  and
+ *                fabs((double)x_i - u) <= radius && fabs((double)y_i - v) <= radius.  The window is square; every
+ *                comparison is written so that a NaN anywhere gives "not a candidate".  Keypoints a caller masks out
+ *                (relocalize's `valid`, the depth filter of track) are candidates like any other: the mask is applied to
+ *                the matches afterwards, as it is after the brute-force matcher.
+ *   knn-2        SAME rule as mslam_hip_match_knn2, over the candidates only: per landmark the two candidates of least
+ *                Hamming distance, ties to the lower keypoint index; absent: index -1, distance INT32_MAX.
+ *                n_cand[j] = the number of candidates of landmark j.
+ *   acceptance   d0 <= max_distance && (no second candidate || (double)d0 < ratio * (double)d1) — mslam_hip_match's
+ *                expression and its table where a second candidate exists, so the two accept alike bit for bit.
+ *                max_distance lies in 0..256; 256 = no gate.  DEVIATES from mslam_hip_match in that a lone candidate is
+ *                accepted: there is no "fewer than two keypoints" rule here.
+ *   order        by landmark index, at most one match per landmark; two landmarks may name one keypoint, as in
+ *                mslam_hip_match.
+ *   vs reference DEVIATES: the reference matches brute force, so a landmark whose descriptor has a look-alike anywhere in
+ *                the frame fails its ratio test; here only look-alikes inside the window count.  With a window that
+ *                covers the frame and every keypoint in the frame, knn-2 equals mslam_hip_match_knn2's.
+ *
+ * Returns MSLAM_HIP_E_INVALID for a radius that is not > 0 (NaN included), max_distance outside 0..256, an extent outside
+ * 1..8192, fx or fy zero or NaN, and n_kp or n_lm above 65535.  n_kp = 0 or n_lm = 0 is OK with no matches (knn2: every
+ * landmark absent).  Outputs have capacity n_lm; n_cand may be NULL. */
+int mslam_hip_match_guided_knn2(mslam_hip_ctx* ctx, const uint8_t* kp_desc, const float* kp_xy, int n_kp, const uint8_t* lm_desc,
+                                const double* lm_world, int n_lm, const double* R, const double* t, double fx, double fy,
+                                double cx, double cy, int width, int height, double radius, int32_t* idx0, int32_t* idx1,
+                                int32_t* dist0, int32_t* dist1, int32_t* n_cand /* may be NULL */);
+/* from_idx = keypoint, to_idx = landmark, as mslam_hip_match(from = keypoints, to = landmarks) */
+int mslam_hip_match_guided(mslam_hip_ctx* ctx, const uint8_t* kp_desc, const float* kp_xy, int n_kp, const uint8_t* lm_desc,
+                           const double* lm_world, int n_lm, const double* R, const double* t, double fx, double fy, double cx,
+                           double cy, int width, int height, double radius, int max_distance, double ratio, int32_t* from_idx,
+                           int32_t* to_idx, int* n_out);
+/* The mode.  With a radius > 0 set, mslam_hip_relocalize, mslam_hip_track, mslam_hip_track_window and
+ * mslam_hip_track_window_dev take the guided stage in place of the brute-force matcher WHEN use_extrinsic_guess != 0: the
+ * pose is the call's guess (rvec turned into R on the host, exactly as the PnP stage turns it into its starting rotation),
+ * the intrinsics are the call's, the extent and max_distance are the mode's, the ratio is the call's.  Every frame of a
+ * window, and every candidate of a relocalisation, shares that pose, as they share the guess: a window's radius has to
+ * cover the camera's motion across the window.  Without a guess there is no pose to project with: the brute-force stage
+ * runs and the outputs are byte-identical to mode off.  The PnP, the vote and the keyframe construction are untouched; they
+ * consume the same match arrays.  mslam_hip_last_match_kernel returns 3 after a guided stage.
+ * radius <= 0 switches the mode off (the default; width and height are then not checked).  MSLAM_HIP_E_INVALID for a NaN
+ * radius, max_distance outside 0..256, and — with radius > 0 — an extent outside 1..8192. */
+int mslam_hip_set_guided_match(mslam_hip_ctx* ctx, double radius, int max_distance, int width, int height);
+int mslam_hip_get_guided_match(mslam_hip_ctx* ctx, double* radius, int* max_distance, int* width, int* height);
 
 /* ---- IRelocalizer / ILoopDetector: DBoW3 bag of words ---------------------------------------------
  * Replaces what OrbRelocalizer is wired for (orb_relocalizer.cpp:26-50, relocalizer.hpp:11-20,

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_reserve", "mslam_hip_kf_read", "mslam_hip_relocalize",
     "mslam_hip_kf_visible", "mslam_hip_track", "mslam_hip_track_window", "mslam_hip_track_window_dev",
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
+    "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
 ]
 
 
@@ -262,8 +263,8 @@ class Context:
         self._chk(self.L.mslam_hip_set_cv_keypoint_order(self._h, int(order)))
 
     def last_match_kernel(self):
-        """'matrix' / 'popcount': the kernel the last matcher launch took (None before the first)"""
-        return {1: "matrix", 2: "popcount"}.get(self.L.mslam_hip_last_match_kernel(self._h))
+        """'matrix' / 'popcount' / 'guided': the kernel the last matcher launch took (None before the first)"""
+        return {1: "matrix", 2: "popcount", 3: "guided"}.get(self.L.mslam_hip_last_match_kernel(self._h))
 
     def match_knn2(self, from_desc, to_desc):
         f = np.ascontiguousarray(from_desc, np.uint8).reshape(-1, 32)
@@ -272,6 +273,56 @@ class Context:
         out = [np.empty(n, np.int32) for _ in range(4)]
         self._chk(self.L.mslam_hip_match_knn2(self._h, _p(f), len(f), _p(t), len(t), *[_p(o) for o in out]))
         return tuple(o[:len(t)].copy() for o in out)
+
+    # ---- guided matching: landmarks matched in a window round their projection ---------------------
+    def _guided_inputs(self, kp_desc, kp_xy, lm_desc, lm_world, R, t):
+        kd = np.ascontiguousarray(kp_desc, np.uint8).reshape(-1, 32)
+        kx = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        ld = np.ascontiguousarray(lm_desc, np.uint8).reshape(-1, 32)
+        lw = np.ascontiguousarray(lm_world, np.float64).reshape(-1, 3)
+        if len(kd) != len(kx) or len(ld) != len(lw):
+            raise MslamHipError(E_INVALID, "match_guided: descriptors and points do not pair up")
+        return kd, kx, ld, lw, np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
+
+    def match_guided_knn2(self, kp_desc, kp_xy, lm_desc, lm_world, R, t, radius, focal=(525.0, 525.0),
+                          principal=(319.5, 239.5), width=640, height=480):
+        """per landmark the two keypoints of least Hamming distance among those within `radius` px (square window) of its
+        projection under the world -> camera pose (R, t) -> (idx0, idx1, dist0, dist1, n_cand), each [n_lm] int32"""
+        kd, kx, ld, lw, R, t = self._guided_inputs(kp_desc, kp_xy, lm_desc, lm_world, R, t)
+        out = [np.empty(max(len(ld), 1), np.int32) for _ in range(5)]
+        self._chk(self.L.mslam_hip_match_guided_knn2(self._h, _p(kd), _p(kx), len(kd), _p(ld), _p(lw), len(ld), _p(R), _p(t),
+                                                     C.c_double(focal[0]), C.c_double(focal[1]), C.c_double(principal[0]),
+                                                     C.c_double(principal[1]), int(width), int(height), C.c_double(radius),
+                                                     *[_p(o) for o in out]))
+        return tuple(o[:len(ld)].copy() for o in out)
+
+    def match_guided(self, kp_desc, kp_xy, lm_desc, lm_world, R, t, radius, max_distance=256, ratio=0.7, focal=(525.0, 525.0),
+                     principal=(319.5, 239.5), width=640, height=480):
+        """match_guided_knn2 + acceptance (d0 <= max_distance, and the ratio test where a second candidate exists)
+        -> (keypoint indices, landmark indices), ordered by landmark"""
+        kd, kx, ld, lw, R, t = self._guided_inputs(kp_desc, kp_xy, lm_desc, lm_world, R, t)
+        fi = np.empty(max(len(ld), 1), np.int32)
+        ti = np.empty(max(len(ld), 1), np.int32)
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_match_guided(self._h, _p(kd), _p(kx), len(kd), _p(ld), _p(lw), len(ld), _p(R), _p(t),
+                                                C.c_double(focal[0]), C.c_double(focal[1]), C.c_double(principal[0]),
+                                                C.c_double(principal[1]), int(width), int(height), C.c_double(radius),
+                                                int(max_distance), C.c_double(ratio), _p(fi), _p(ti), C.byref(n)))
+        return fi[:n.value].copy(), ti[:n.value].copy()
+
+    def set_guided_match(self, radius, max_distance=256, width=None, height=None):
+        """radius > 0: relocalize, track, track_window and track_window_dev match each landmark among the keypoints within
+        `radius` px of its projection under the call's guess (calls without a guess keep the brute-force matcher);
+        radius <= 0: off (the default).  width, height: the frame extent (default: the context's)."""
+        self._chk(self.L.mslam_hip_set_guided_match(self._h, C.c_double(radius), int(max_distance),
+                                                    int(self.params.width if width is None else width),
+                                                    int(self.params.height if height is None else height)))
+
+    def get_guided_match(self):
+        """-> (radius, max_distance, width, height); radius 0 = off"""
+        r, d, w, h = C.c_double(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.mslam_hip_get_guided_match(self._h, C.byref(r), C.byref(d), C.byref(w), C.byref(h)))
+        return r.value, d.value, w.value, h.value
 
     # ---- RGB-D back-projection (rgbd_feature_frontend.cpp:101-138) ------------------------------
     def backproject(self, depth, xy, factor=1.0 / 5000.0, focal=(525.0, 525.0), principal=(319.5, 239.5)):
@@ -968,14 +1019,21 @@ class HipKeyframeTracker:
     ids (DEVIATES: a union lists at most 64 entries).  The union is enqueued without a synchronisation, only when the
     reference keyframe changed or a keyframe was added, and track runs with ref_id = LOCAL_MAP_ID; the reserved id is never
     in self.ids, the vote list or the relocalisation candidates.  The context's max_keypoints must hold the union; one that
-    does not fit raises MslamHipError(E_CAPACITY)."""
+    does not fit raises MslamHipError(E_CAPACITY).
+
+    guided_radius = r (> 0): Context.set_guided_match(r, guided_max_distance) with the context's frame size — every track
+    call here has a guess, so every one of them matches each landmark within r px of its projection under the previous
+    pose (DEVIATES: the reference matches brute force); the relocalisation after a failure has no guess and matches brute
+    force.  With process_window the radius has to cover the motion across a window.  None leaves the context's mode alone."""
 
     LOCAL_MAP_ID = 0x7fffffff
 
     def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
                  reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
-                 reloc_min_inliers=60, local_map_depth=None):
+                 reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256):
         self.ctx = ctx
+        if guided_radius is not None:
+            ctx.set_guided_match(guided_radius, guided_max_distance)
         self.local_map_depth = local_map_depth
         self.graph = {}            # covisibility: id -> set of ids
         self.local_map = []        # the entries the current union lists

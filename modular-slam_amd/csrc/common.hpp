@@ -329,4 +329,52 @@ void launch_ratio_compact(const RatioArgs& a, int n_pairs, hipStream_t s);
 // false: the arguments do not fit this form and nothing was launched
 bool launch_match_ratio_single(const MatchArgs& a, const RatioArgs& r, hipStream_t s);
 
+// ---- guided matching (k_match_guided.hip): knn-2 among the keypoints inside a square window round each landmark's
+// projection.  Row r = one (keypoint set, landmark set) pair, addressed as MatchArgs addresses its pairs (keypoints = the
+// train side "from", landmarks = the query side "to"); the world points of row r's landmarks are
+// world + slots[r * slot_stride] * world_slot (slots == nullptr: world itself).
+constexpr int kGuidedMaxCells = 4096; // cells of a row's grid: the LDS histogram of k_guided_bin
+struct GuidedGrid
+{
+    int shift, nx, ny; // square cells of (1 << shift) px; nx x ny of them cover the frame
+};
+// the smallest cell edge from 32 px on whose grid has at most kGuidedMaxCells cells (extents up to 8192: 32, 64 or 128 px)
+inline GuidedGrid guided_grid(int width, int height)
+{
+    int s = 5;
+    while((long long)(((width - 1) >> s) + 1) * (((height - 1) >> s) + 1) > kGuidedMaxCells)
+        ++s;
+    return GuidedGrid{s, ((width - 1) >> s) + 1, ((height - 1) >> s) + 1};
+}
+struct GuidedArgs
+{
+    const uint8_t* kp_desc;  // row r at + r * kp_stride * 32
+    const float* kp_xy;      // row r at + r * kp_stride * 2
+    long long kp_stride;     // keypoints between consecutive rows (0: shared)
+    const int32_t* kp_cnt;   // [rows] or nullptr -> n_kp_fixed; clamped to kp_cap
+    int n_kp_fixed, kp_cap;  // kp_cap: upper bound of every row's count = row stride of `list` / `list_desc`
+    const uint8_t* lm_desc;  // row r at + r * lm_stride BYTES
+    long long lm_stride;
+    const int32_t* lm_cnt;   // [rows] or nullptr -> n_lm_fixed; clamped to cap
+    int n_lm_fixed, cap;     // cap: row stride of the outputs
+    const double* world;
+    const int32_t* slots;
+    int slot_stride;
+    long long world_slot;    // doubles per slot
+    double R[9], t[3], fx, fy, cx, cy, radius;
+    int width, height;
+    GuidedGrid grid;
+    int32_t* cell_off;       // [rows][kGuidedMaxCells + 1] exclusive offsets into the row's list
+    // the row's in-frame keypoints cell by cell, as copies, so that a list position gives the matcher everything without a
+    // second dependent fetch: {x, y, keypoint index (as bits), -} and the descriptor
+    float4* list;            // [rows][kp_cap]
+    uint8_t* list_desc;      // [rows][kp_cap][32]
+    int32_t *idx0, *idx1, *dist0, *dist1; // [rows][cap], MatchArgs' layout
+    int32_t* n_cand;         // [rows][cap] or nullptr
+};
+void launch_guided_bin(const GuidedArgs& a, int rows, hipStream_t s);
+void launch_match_guided(const GuidedArgs& a, int rows, hipStream_t s);
+// acceptance d0 <= max_distance && (no second candidate || d0 < thr[d1]) + ordered compaction; RatioArgs' from counts are not read
+void launch_ratio_guided(const RatioArgs& a, int max_distance, int n_pairs, hipStream_t s);
+
 } // namespace mslam

@@ -113,7 +113,10 @@ struct mslam_hip_ctx
     hipStream_t stream_m = nullptr; // matcher stream
     bool overlap_match = true;
     int matcher_kind = 0; // MSLAM_HIP_MATCHER_*
-    int last_match_kernel = 0; // kernel of the last matcher launch: 0 none yet, 1 matrix cores, 2 xor/popcount
+    int last_match_kernel = 0; // kernel of the last matcher launch: 0 none yet, 1 matrix cores, 2 xor/popcount, 3 guided
+    // mslam_hip_set_guided_match: radius > 0 = the match-to-PnP sequence takes the guided stage when the call has a guess
+    double guided_radius = 0.0;
+    int guided_max_distance = 256, guided_width = 0, guided_height = 0;
     int n_last = 0;         // frames in the last detect batch
     unsigned long long detect_seq = 0; // counts detect batches; points_seq = the batch the back-projected points belong to
     unsigned long long points_seq = ~0ull;
@@ -239,6 +242,7 @@ struct PnpBatchLaunch
 };
 int pnp_launch_batch(mslam_hip_ctx* c, const PnpBatchLaunch& l);
 void pnp_rotation_to_rvec(const double R[9], double rvec[3]);
+void pnp_rvec_to_rotation(const double rvec[3], double R[9]); // the R0 the PnP launch makes of its guess
 } // namespace mslam
 
 // api.hip: uploads the ratio-test table of `ratio` unless it is the cached one (not part of the C ABI)

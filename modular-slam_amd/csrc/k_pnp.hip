@@ -1042,6 +1042,7 @@ int pnp_launch_batch(mslam_hip_ctx* c, const PnpBatchLaunch& l)
     return MSLAM_HIP_OK;
 }
 void pnp_rotation_to_rvec(const double R[9], double rvec[3]) { R_to_rodrigues(R, rvec); }
+void pnp_rvec_to_rotation(const double rvec[3], double R[9]) { rodrigues_to_R(rvec, R); }
 } // namespace mslam
 
 extern "C" int mslam_hip_get_pnp_view(mslam_hip_ctx* c, mslam_hip_pnp_view* v)

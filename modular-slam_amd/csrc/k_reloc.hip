@@ -551,10 +551,10 @@ namespace
 // where the sequence's arrays lie in the arena, each 256-byte aligned
 struct SeqArena
 {
-    size_t gdesc, gcnt, idx0, idx1, dist0, dist1, mfrom, mto, mcount, obj, img, ncorr, mask, hyp, counts, out, bytes;
+    size_t gdesc, gcnt, idx0, idx1, dist0, dist1, mfrom, mto, mcount, obj, img, ncorr, mask, hyp, counts, out, cells, list, ldesc, bytes;
 };
 
-SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot)
+SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from)
 {
     size_t off = 0;
     auto carve = [&](size_t bytes) {
@@ -569,21 +569,24 @@ SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot)
     a.mfrom = carve(RS * 4), a.mto = carve(RS * 4), a.mcount = carve(R * 4);
     a.obj = carve(RS * 12), a.img = carve(RS * 8), a.ncorr = carve(R * 4), a.mask = carve(RS);
     a.hyp = carve(R * it * 96), a.counts = carve(R * it * 4), a.out = carve(R * 128);
+    // the guided stage's lists come last: without them every array lies where it always did
+    a.cells = carve(guided ? R * (kGuidedMaxCells + 1) * 4 : 0), a.list = carve(guided ? R * (size_t)std::max(cap_from, 1) * 16 : 0);
+    a.ldesc = carve(guided ? R * (size_t)std::max(cap_from, 1) * 32 : 0);
     a.bytes = off;
     return a;
 }
 } // namespace
 
-size_t mslam::seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot)
+size_t mslam::seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from)
 {
-    return seq_carve(rows, S, iterations, one_slot).bytes;
+    return seq_carve(rows, S, iterations, one_slot, guided, cap_from).bytes;
 }
 
 int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* out)
 {
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints, R = a.rows, S = (int)a.S;
-    const SeqArena o = seq_carve(R, a.S, a.iterations, a.one_slot);
+    const SeqArena o = seq_carve(R, a.S, a.iterations, a.one_slot, a.guided, a.cap_from);
     hipStream_t s = c->stream;
     int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o.gcnt);
     {
@@ -607,10 +610,6 @@ int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* o
     m.idx1 = reinterpret_cast<int32_t*>(A + o.idx1);
     m.dist0 = reinterpret_cast<int32_t*>(A + o.dist0);
     m.dist1 = reinterpret_cast<int32_t*>(A + o.dist1);
-    {
-        StageScope ts(c, "match_knn2");
-        c->last_match_kernel = launch_match_knn2(m, R, s);
-    }
     RatioArgs q{};
     q.idx0 = m.idx0, q.dist0 = m.dist0, q.dist1 = m.dist1;
     q.from_cnt = a.from_cnt, q.n_from_fixed = a.n_from_fixed;
@@ -620,7 +619,39 @@ int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* o
     q.from_idx = reinterpret_cast<int32_t*>(A + o.mfrom);
     q.to_idx = reinterpret_cast<int32_t*>(A + o.mto);
     q.n_out = reinterpret_cast<int32_t*>(A + o.mcount);
+    if(a.guided)
     {
+        // the same operands, addressed the same way; the pose is the guess as the PnP launch below turns it into R0
+        GuidedArgs g{};
+        g.kp_desc = a.desc, g.kp_xy = a.xy, g.kp_stride = (long long)a.from_stride;
+        g.kp_cnt = a.from_cnt, g.n_kp_fixed = a.n_from_fixed, g.kp_cap = std::max(a.cap_from, 1);
+        g.lm_desc = m.to_desc, g.lm_stride = m.to_stride, g.lm_cnt = g_cnt, g.cap = S;
+        g.world = r->d_world, g.slots = a.slots, g.slot_stride = a.one_slot ? 0 : 1, g.world_slot = (long long)K * 3;
+        pnp_rvec_to_rotation(a.rvec, g.R);
+        g.t[0] = a.tvec[0], g.t[1] = a.tvec[1], g.t[2] = a.tvec[2];
+        g.fx = a.fx, g.fy = a.fy, g.cx = a.cx, g.cy = a.cy, g.radius = c->guided_radius;
+        g.width = c->guided_width, g.height = c->guided_height, g.grid = guided_grid(g.width, g.height);
+        g.cell_off = reinterpret_cast<int32_t*>(A + o.cells), g.list = reinterpret_cast<float4*>(A + o.list);
+        g.list_desc = A + o.ldesc;
+        g.idx0 = m.idx0, g.idx1 = m.idx1, g.dist0 = m.dist0, g.dist1 = m.dist1;
+        {
+            StageScope ts(c, "guided_bin");
+            launch_guided_bin(g, R, s);
+        }
+        {
+            StageScope ts(c, "match_guided");
+            launch_match_guided(g, R, s);
+        }
+        c->last_match_kernel = 3;
+        StageScope ts(c, "ratio_guided");
+        launch_ratio_guided(q, c->guided_max_distance, R, s);
+    }
+    else
+    {
+        {
+            StageScope ts(c, "match_knn2");
+            c->last_match_kernel = launch_match_knn2(m, R, s);
+        }
         StageScope ts(c, "ratio_compact");
         launch_ratio_compact(q, R, s);
     }
@@ -705,7 +736,8 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     const size_t extra_bytes = hooks ? hooks->extra_up_bytes[0] + hooks->extra_up_bytes[1] : 0;
     const size_t up = extra_bytes ? off_extra + extra_bytes : off_valid + (valid ? (size_t)n : 0);
     // ---- device arena: the sequence's arrays, then a hook's own
-    const size_t o_extra = seq_arena_bytes(n_cand, S, iterations, false);
+    const bool guided = seq_guided(c, use_extrinsic_guess);
+    const size_t o_extra = seq_arena_bytes(n_cand, S, iterations, false, guided, n);
     // ---- result block (mapped): [best, pad | RelocRes[64] | pair_from P x S | pair_to P x S | inliers P x S]
     const size_t res_head = 16 + kRelocMaxCand * sizeof(RelocRes);
     const size_t res_extra = (res_head + (want_pairs ? PS * 9 : 0) + 15) & ~(size_t)15; // a hook's own results
@@ -734,6 +766,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.use_guess = use_extrinsic_guess, a.rvec = rvec, a.tvec = tvec;
     a.iterations = iterations, a.reprojection_error = reprojection_error, a.seed = seed;
+    a.guided = guided;
     RelocDev dev{};
     if(hooks)
     {

@@ -178,7 +178,8 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     const size_t u_depth = host ? u_xy + al256((size_t)S * st1 * 8) : u_desc;
     const size_t up = host ? u_depth + al256((size_t)S * npx * 2) : u_desc;
     // ---- device arena: the sequence's arrays, then the window's own
-    size_t off = seq_arena_bytes(S, Srow, p.iterations, true);
+    const bool guided = seq_guided(c, p.use_guess);
+    size_t off = seq_arena_bytes(S, Srow, p.iterations, true, guided, w.cap_from);
     auto carve = [&](size_t bytes) {
         const size_t o = off;
         off += al256(bytes);
@@ -235,6 +236,7 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     a.fx = p.fx, a.fy = p.fy, a.cx = p.cx, a.cy = p.cy;
     a.use_guess = p.use_guess, a.rvec = p.rvec, a.tvec = p.tvec;
     a.iterations = p.iterations, a.reprojection_error = p.reprojection_error, a.seed = p.seed;
+    a.guided = guided;
     SeqDev d{};
     rc = seq_enqueue(c, a, A, &d);
     if(rc)

@@ -109,7 +109,13 @@ struct SeqArgs
     int iterations = 0;
     double reprojection_error = 0;
     unsigned long long seed = 0;
+    // seq_guided(): the guided stage (k_match_guided.hip) in place of the brute-force matcher, every row projecting with
+    // the guess
+    bool guided = false;
 };
+
+// the mode of mslam_hip_set_guided_match applies to a call that has a guess: there is no pose to project with otherwise
+inline bool seq_guided(const mslam_hip_ctx* c, int use_guess) { return c->guided_radius > 0.0 && use_guess != 0; }
 
 // what the sequence leaves on the device; rows of the per-row arrays are S entries apart
 struct SeqDev
@@ -124,7 +130,9 @@ inline size_t seq_row_stride(int n_upper) // an entry of at most n_upper landmar
 {
     return al256((size_t)(n_upper > 1 ? n_upper : 1));
 }
-size_t seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot); // a multiple of 256: a caller's own arrays follow
+// a multiple of 256: a caller's own arrays follow.  guided: with the cell offsets and the keypoint list (cap_from entries of coordinates, index and descriptor) of
+// every row behind the sequence's own arrays, which keep their places
+size_t seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided = false, int cap_from = 0);
 // enqueues the sequence on c->stream, its arrays carved from `arena`; sets c->last_match_kernel
 int seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* arena, SeqDev* out);
 

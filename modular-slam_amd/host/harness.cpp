@@ -26,6 +26,9 @@
 //                                    the same loop against the local map, as the reference tracks (:256-277): ILocalMapTracker's
 //                                    buildLocalMap over the reference keyframe's covisibility neighbourhood (rebuilt when the
 //                                    reference changes or a keyframe is added), trackLocalMap, covisibleLandmarks for the edges
+//        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> [--local-map <depth>] --guided <radius>
+//                                    either loop with IKeyframeTracker::setGuidedMatch(radius): every tracking call matches each
+//                                    landmark within <radius> px of its projection under the previous pose
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -205,11 +208,24 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if((argc == 5 || (argc == 7 && std::strcmp(argv[5], "--local-map") == 0)) && std::strcmp(argv[2], "--track") == 0)
+        // --track <vocabulary> <scene> followed by any of: --local-map <depth>, --guided <radius>
+        bool trackArgs = argc >= 5 && (argc - 5) % 2 == 0 && std::strcmp(argv[2], "--track") == 0;
+        int mapDepthArg = -1;
+        double guidedRadius = 0.0;
+        for(int k = 5; trackArgs && k + 1 < argc; k += 2)
+        {
+            if(std::strcmp(argv[k], "--local-map") == 0)
+                mapDepthArg = std::atoi(argv[k + 1]);
+            else if(std::strcmp(argv[k], "--guided") == 0)
+                guidedRadius = std::atof(argv[k + 1]);
+            else
+                trackArgs = false;
+        }
+        if(trackArgs)
         {
             // --local-map <depth>: track against the union of the reference keyframe's covisibility neighbourhood
             // (ILocalMapTracker) instead of the reference keyframe's own landmarks; the reference uses depth 2
-            const int mapDepth = argc == 7 ? std::atoi(argv[6]) : -1;
+            const int mapDepth = mapDepthArg;
             // scene file, little-endian: 'MSTK', i32 version = 1, n_frames, width, height; f64 fx, fy, cx, cy; f32 factor; i32 seed,
             // min_matched_points, new_keyframe_min_landmarks; f64 z_max; per frame: i32 n, n x 32 descriptor bytes, n x 2 f32
             // keypoint coordinates, height x width u16 depth
@@ -224,6 +240,8 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "the plugin does not offer the keyframe tracking step\n");
                 return 6;
             }
+            if(guidedRadius > 0.0)
+                tracker->setGuidedMatch(guidedRadius);
             std::ifstream in(argv[4], std::ios::binary);
             char magic[4] = {0, 0, 0, 0};
             std::int32_t head[4] = {0, 0, 0, 0}, par[3] = {0, 0, 0};

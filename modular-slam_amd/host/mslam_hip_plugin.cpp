@@ -449,6 +449,14 @@ class BowDatabase
         const int cap = static_cast<int>(keypoints.size());
         std::vector<std::int32_t> src(keypoints.size() + 1), kp(keypoints.size() + 1);
         const bool guess = rvecGuess && tvecGuess;
+        if(guidedRadius > 0.0 || guidedSet)
+        {
+            // the mode's frame extent is this call's
+            const int grc = mslam_hip_set_guided_match(ctx.h, guidedRadius, guidedMaxDistance, width, height);
+            if(grc != MSLAM_HIP_OK)
+                raise(ctx.h, "mslam_hip_set_guided_match", grc);
+            guidedSet = guidedRadius > 0.0;
+        }
         mslam_hip_track_result out;
         // the matcher's ratio and OpenCvRansacPnp's operating point, as relocalizePose (orb_feature.cpp:101, cv_ransac_pnp.cpp:56-57)
         const int rc = mslam_hip_track(ctx.h, desc.data(), xy.data(), cap, depth, width, height, camera.factor, camera.focal.x(),
@@ -495,6 +503,14 @@ class BowDatabase
         if(best)
             *best = b;
         return std::vector<int>(counts.begin(), counts.begin() + static_cast<std::ptrdiff_t>(neighbours.size()));
+    }
+
+    void setGuidedMatch(double radius, int maxDistance)
+    {
+        if(!(radius == radius) || maxDistance < 0 || maxDistance > 256)
+            throw std::invalid_argument("setGuidedMatch: the radius is NaN or maxDistance lies outside 0..256");
+        guidedRadius = radius > 0.0 ? radius : 0.0;
+        guidedMaxDistance = maxDistance;
     }
 
   private:
@@ -568,6 +584,9 @@ class BowDatabase
     int nextTrackedId = 1 << 30; // store ids of the keyframes trackKeyframe inserts (BoW entry ids count from 0)
     static constexpr int kLocalMapId = 0x7fffffff; // the store id of the local map (above every keyframe's)
     bool haveLocalMap = false;
+    double guidedRadius = 0.0; // setGuidedMatch; applied to the context by the next tracking call, with that call's frame size
+    int guidedMaxDistance = 256;
+    bool guidedSet = false;    // the context's mode is on
     std::vector<float> xy;
     KeyframePtr lastLoop;
     std::vector<OrbKeypoint> lastFed;
@@ -614,6 +633,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, p
     {
         return db->visibleLandmarks(neighbours, R, t, camera, width, height, best);
     }
+    void setGuidedMatch(double radius, int maxDistance) override { db->setGuidedMatch(radius, maxDistance); }
     void addKeyframeLandmarksWithIds(BowDatabase::KeyframePtr keyframe, const std::vector<OrbKeypoint>& keypoints,
                                      const std::vector<Vector3>& worldPoints, const std::vector<std::int64_t>& landmarkIds) override
     {

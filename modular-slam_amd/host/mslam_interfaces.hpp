@@ -270,6 +270,11 @@ class IKeyframeTracker
     // frame seen from (R, t); *best = the position of the first maximum, -1 for an empty list
     virtual std::vector<int> visibleLandmarks(const std::vector<KeyframePtr>& neighbours, const double R[9], const double t[3],
                                               const CameraParameters& camera, int width, int height, int* best) = 0;
+    // extension (the reference matches brute force; its matchLandmarks carries "TODO: use boost geometry rtree for
+    // keypoints", :242): radius > 0 makes trackKeyframe and trackLocalMap calls that have a guess match every landmark
+    // among the keypoints within `radius` px of its projection under that guess, no further than maxDistance bits
+    // (mslam_hip_set_guided_match; the frame size is each call's); radius <= 0: brute force, the default
+    virtual void setGuidedMatch(double radius, int maxDistance = 256) = 0;
     virtual ~IKeyframeTracker() = default;
 };
 // ---- extension (not in the reference): tracking against the local map (mslam_hip_kf_union, mslam_hip_kf_covisible) ---------

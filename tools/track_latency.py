@@ -12,7 +12,11 @@ usage: python tools/track_latency.py [--blocks 12] [--calls 100] [--runs 2] [--o
 next one, so their union holds 12750; the same query).  Timed alternately, in blocks, in the same process: the union
 build on its own (mslam_hip_kf_union of the 16 entries, one synchronisation), the track step against the union, and the
 single-reference track step against one of the 16 entries.  A tracker pays the build only when the reference keyframe
-changes or a keyframe is added, the step every frame."""
+changes or a keyframe is added, the step every frame.
+
+--local-map --guided <radius>: every track step gets the scene's true pose as its guess, and two more sides join the
+alternation: the step against the union and against the single entry with mslam_hip_set_guided_match(radius,
+--max-distance) on (the setter is switched per call: a host-side assignment)."""
 import argparse
 import json
 import os
@@ -35,6 +39,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--trace", choices=["new", "old"])
     ap.add_argument("--local-map", action="store_true")
+    ap.add_argument("--guided", type=float, default=0.0, metavar="RADIUS")
+    ap.add_argument("--max-distance", type=int, default=256, help="the guided sides' distance gate")
     a = ap.parse_args()
     import reloc_ref as rr
     import track_ref as tr
@@ -120,6 +126,19 @@ def local_map(a, pkg, rr):
     for k, cid in enumerate(ids):                       # entry k shares its upper half with the lower half of entry k + 1
         c.kf_add(cid, *sc["store"][cid], lids=k * (n_lm // 2) + np.arange(n_lm))
     kw = dict(seed=1, new_keyframe_min_landmarks=1 << 20)
+    if a.guided > 0:
+        R = sc["R"]
+        th = np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))
+        kw.update(rvec=th / (2 * np.sin(th)) * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]), tvec=sc["t"])
+
+    def guided(step):
+        def run():
+            c.set_guided_match(a.guided, a.max_distance, 640, 480)
+            try:
+                return step()
+            finally:
+                c.set_guided_match(0.0, 256, 640, 480)
+        return run
 
     def build():
         return c.kf_union(U, ids)
@@ -133,6 +152,10 @@ def local_map(a, pkg, rr):
     rm, rs = step_map(), step_single()
     assert n_union == (n_kf + 1) * (n_lm // 2) and rm["tracked"] and rs["tracked"] and rm["keyframe_added"] and rs["keyframe_added"]
     sides = (("union_build", build), ("track_local_map", step_map), ("track_single_reference", step_single))
+    if a.guided > 0:
+        sides += (("track_local_map_guided", guided(step_map)), ("track_single_reference_guided", guided(step_single)))
+        gm, gs = sides[3][1](), sides[4][1]()
+        assert gm["tracked"] and gs["tracked"]
     for _ in range(30):
         for _, f in sides:
             f()
@@ -156,6 +179,10 @@ def local_map(a, pkg, rr):
                union_stages_us=stages,
                step_local_map=dict(n_matches=rm["n_matches"], n_correspondences=rm["n_correspondences"], n_inliers=rm["n_inliers"]),
                step_single=dict(n_matches=rs["n_matches"], n_correspondences=rs["n_correspondences"], n_inliers=rs["n_inliers"]))
+    if a.guided > 0:
+        out["guided_radius"], out["guided_max_distance"] = a.guided, a.max_distance
+        out["step_local_map_guided"] = dict(n_matches=gm["n_matches"], n_correspondences=gm["n_correspondences"], n_inliers=gm["n_inliers"])
+        out["step_single_guided"] = dict(n_matches=gs["n_matches"], n_correspondences=gs["n_correspondences"], n_inliers=gs["n_inliers"])
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
