@@ -494,6 +494,69 @@ int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* ctx, const double* d_object, 
                                     int n_problems, int capacity, double fx, double fy, double cx, double cy,
                                     double* d_pose, double* d_info);
 
+/* ---- CeresBackend::bundleAdjustment (ceres_backend.cpp:185-240): bundle adjustment ------------------------------------
+ * What the reference's backend solves on every new keyframe: Levenberg-Marquardt over keyframe poses and landmarks of
+ *   cost = 1/2 sum_m |r_m|^2,   r_m = rot(q^-1, X) - rot(q^-1, p) - obs_cam[m]      (ReprojectionError::operator(), :31-47)
+ * with (q, p) the state of keyframe obs_kf[m] (orientation x y z w, position; camera -> world), X landmark obs_lm[m] and
+ * obs_cam[m] the camera-frame point ReprojectionError's constructor forms from the keypoint and its depth (:24-28); no loss
+ * function, all in double.  The problem is handed over explicitly:
+ *   poses      K x 7 (qx qy qz qw px py pz), K in 0..64, in: start, out: result; fixed[k] != 0 holds pose k constant (the
+ *              reference fixes keyframe id 1, :155-159); fixed == NULL: none;
+ *   landmarks  L x 3, in / out;   obs_kf, obs_lm, obs_cam: M observations, indices into poses / landmarks.
+ * A free pose has 6 tangent dimensions (EigenQuaternionManifold's Plus, q_delta (x) q with q_delta = (sin|d| d/|d|, cos|d|),
+ * and the position), a landmark 3.  A pose or landmark without an observation is not part of the problem and stays as it is.
+ * After the solve outlier[m] (may be NULL) = |r_m|^2 > outlier_threshold^2 at the returned state (createOutput, :212-230;
+ * the reference's threshold is 0.15); nothing is removed (removeObservation's body is commented out there).
+ * summary (may be NULL): termination (ceres::TerminationType 0 CONVERGENCE / 1 NO_CONVERGENCE / 2 FAILURE), iterations (the
+ * index of the trust-region iteration that ended the solve), rejected and invalid steps, initial and final cost, n_outliers.
+ * Returns MSLAM_HIP_OK for terminations 0 and 1; MSLAM_HIP_E_NO_MODEL for FAILURE: poses and landmarks are left unchanged
+ * and the outliers are judged at the inputs.  MSLAM_HIP_E_INVALID: K outside 0..64, a negative count, an index out of range,
+ * max_iterations < 0, a threshold that is not >= 0, or a quaternion whose norm is off 1 by more than 1e-6 (DEVIATES: the
+ * reference's quaternions are unit by construction).  M = 0 is CONVERGENCE at cost 0, nothing touched (as n = 0 is for
+ * mslam_hip_pnp_min_mse).  Two calls on the same input return the same bits: no sum uses an atomic, every sum has one order.
+ * Against Ceres 2.2 with the Solver::Options bundleAdjustment sets (:193-195: max_num_iterations; everything else default,
+ * restated from the published solver.h: function tolerance 1e-6, gradient tolerance 1e-10, parameter tolerance 1e-8, initial
+ * radius 1e4, monotonic steps, Jacobi scaling).  PARITY UNPINNED: no Ceres build exists to compare with; the tests compare
+ * with an independent numpy restatement (tests/ba_ref.py, two linear solvers) and with ground truth.
+ *   residual                 SAME expression: Eigen's inverse() (conjugate / squared norm) and _transformVector
+ *                            (v + w 2(u x v) + u x 2(u x v)) on both X and p;
+ *   derivatives              DEVIATES in rounding: analytic, dr/dX = R^T, dr/dp = -R^T, dr/d(delta) = 2 R^T [X - p]x with R^T
+ *                            the matrix of the same linear map, instead of jets times PlusJacobian; equal for unit q;
+ *   sums                     DEVIATES in rounding: per landmark in row order, per keyframe by lane stride then a fixed
+ *                            butterfly, costs by a fixed two-stage tree; not Ceres's evaluation order;
+ *   linear solver            DEVIATES in rounding: Schur complement on the landmarks (3x3 blocks inverted in closed form),
+ *                            dense Cholesky of the reduced camera system (at most 384 x 384) in global memory, back-
+ *                            substitution; the reference asks for SPARSE_NORMAL_CHOLESKY on the whole system.  A non-positive
+ *                            pivot or a non-finite step is an invalid step, as a linear-solver failure is in Ceres;
+ *   Jacobi scaling           SAME: 1 / (1 + |J_col|) per tangent column from the Jacobian at the start, once;
+ *   trust region             SAME as mslam_hip_pnp_min_mse: radius 1e4 .. 1e16, D^2 = clamp(diag, 1e-6, 1e32) / radius,
+ *                            model cost change -(J_s s) . (f + J_s s / 2) summed per observation without the damping,
+ *                            relative decrease > 1e-3, radius /= max(1/3, 1 - (2 rho - 1)^3), rejected: radius /= factor,
+ *                            factor *= 2; 5 invalid steps in a row: FAILURE;
+ *   termination              SAME order, on the ambient parameters (7 per pose, 3 per landmark) of the blocks that have
+ *                            observations and are not constant: max_iterations -> NO_CONVERGENCE; successful step with
+ *                            |x - Plus(x, -g)|_inf <= 1e-10, radius <= 1e-32, |x - x_candidate| <= 1e-8 (|x| + 1e-8) or
+ *                            |cost change| <= 1e-6 cost -> CONVERGENCE; non-finite cost or gradient -> FAILURE;
+ *   FAILURE result           DEVIATES: the state is left unchanged (Ceres writes its best point back);
+ *   sizes                    DEVIATES: at most 64 keyframes per solve (the reduced system is dense); the reference has no
+ *                            bound. */
+typedef struct
+{
+    int32_t termination, iterations, rejected_steps, invalid_steps, n_outliers, reserved;
+    double initial_cost, final_cost;
+} mslam_hip_ba_summary;
+int mslam_hip_bundle_adjust(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out */, const uint8_t* fixed /* K, or NULL */,
+                            int K /* 0..64 */, double* landmarks /* L x 3, in/out */, int L, const int32_t* obs_kf,
+                            const int32_t* obs_lm, const double* obs_cam /* M x 3 */, int M, int max_iterations /* 100 */,
+                            double outlier_threshold /* 0.15 */, uint8_t* outlier /* M, may be NULL */,
+                            mslam_hip_ba_summary* summary /* may be NULL */);
+/* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
+ * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
+ * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of
+ * store landmarks written.  Nothing else calls it: the store changes only when the caller asks. */
+int mslam_hip_kf_update_world(mslam_hip_ctx* ctx, const int64_t* landmark_ids, const double* world_xyz /* n x 3 */, int n,
+                              int* n_written /* may be NULL */);
+
 /* ---- verified relocalisation: keyframe store + one query against N keyframes (match -> correspondences -> PnP) --------
  * What RgbdFeatureFrontend::relocalize is written to do with the relocalizer's candidates (rgbd_feature_frontend.cpp:495-534,
  * its body is commented out there and the function returns nullptr): per candidate keyframe matchLandmarks(keypoints,

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_visible", "mslam_hip_track", "mslam_hip_track_window", "mslam_hip_track_window_dev",
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
+    "mslam_hip_bundle_adjust", "mslam_hip_kf_update_world",
 ]
 
 
@@ -122,6 +123,12 @@ class TrackResult(C.Structure):
                 ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("R", C.c_double * 9), ("tracked", C.c_int32),
                 ("keyframe_required", C.c_int32), ("keyframe_added", C.c_int32), ("n_entry", C.c_int32),
                 ("n_inherited", C.c_int32), ("vote_best", C.c_int32), ("vote_best_count", C.c_int32)]
+
+
+class BaSummary(C.Structure):
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("rejected_steps", C.c_int32),
+                ("invalid_steps", C.c_int32), ("n_outliers", C.c_int32), ("reserved", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
 class BowView(C.Structure):
@@ -473,6 +480,44 @@ class Context:
         l = np.empty(max(n.value, 1), np.int64)
         self._chk(self.L.mslam_hip_kf_read_ids(self._h, int(id), _p(l), n.value, C.byref(n)))
         return l[:n.value].copy()
+
+    # ---- bundle adjustment (ceres_backend.cpp:185-240) ----------------------------------------------
+    def bundle_adjust(self, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed=None, max_iterations=100, outlier_threshold=0.15):
+        """CeresBackend::bundleAdjustment's solve: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 64), landmarks
+        [L, 3], observations (keyframe index, landmark index, camera-frame point [M, 3]); fixed = [K] flags or None.
+        -> dict(poses, landmarks, outlier [M] bool, termination, iterations, rejected_steps, invalid_steps, n_outliers,
+        initial_cost, final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): poses and landmarks
+        come back unchanged."""
+        x = np.array(poses, np.float64).reshape(-1, 7)
+        lm = np.array(landmarks, np.float64).reshape(-1, 3)
+        ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+        ol = np.ascontiguousarray(obs_lm, np.int32).reshape(-1)
+        oc = np.ascontiguousarray(obs_cam, np.float64).reshape(-1, 3)
+        if not len(ok) == len(ol) == len(oc):
+            raise MslamHipError(E_INVALID, "bundle_adjust: %d / %d / %d observations" % (len(ok), len(ol), len(oc)))
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+        if fx is not None and len(fx) != len(x):
+            raise MslamHipError(E_INVALID, "bundle_adjust: %d poses, %d fixed flags" % (len(x), len(fx)))
+        mask = np.zeros(max(len(ok), 1), np.uint8)
+        out = BaSummary()
+        rc = self.L.mslam_hip_bundle_adjust(self._h, _p(x), _p(fx), len(x), _p(lm), len(lm), _p(ok), _p(ol), _p(oc), len(ok),
+                                            int(max_iterations), C.c_double(outlier_threshold), _p(mask), C.byref(out))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        res = {k: getattr(out, k) for k, _ in BaSummary._fields_ if k != "reserved"}
+        res.update(poses=x, landmarks=lm, outlier=mask[:len(ok)].astype(bool))
+        return res
+
+    def kf_update_world(self, landmark_ids, world_xyz):
+        """every landmark of every stored keyframe whose landmark id is listed takes the listed world point -> the number
+        of store landmarks written"""
+        l = np.ascontiguousarray(landmark_ids, np.int64).reshape(-1)
+        w = np.ascontiguousarray(world_xyz, np.float64).reshape(-1, 3)
+        if len(l) != len(w):
+            raise MslamHipError(E_INVALID, "kf_update_world: %d ids, %d points" % (len(l), len(w)))
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_update_world(self._h, _p(l), _p(w), len(l), C.byref(n)))
+        return n.value
 
     # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
     def kf_covisible(self, id, ids):
@@ -999,6 +1044,116 @@ class HipLoopDetector:
         return self.reloc._verify(self._last_keypoints, [self._last_entry], camera, valid, rvec, tvec, min_inliers, seed)
 
 
+def rotation_to_quaternion(R):
+    """unit quaternion (x, y, z, w), w >= 0, of a rotation matrix (the branch with the largest divisor)"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = [R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1], R[0, 0] + R[1, 1] + R[2, 2]]
+    i = int(np.argmax(t))
+    r = np.sqrt(1.0 + t[i])
+    if i == 3:
+        q = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], r * r]) / (2.0 * r)
+    else:
+        j, k = (i + 1) % 3, (i + 2) % 3
+        q = np.zeros(4)
+        q[i], q[j], q[k], q[3] = r * r, R[j, i] + R[i, j], R[k, i] + R[i, k], R[k, j] - R[j, k]
+        q /= 2.0 * r
+    q /= np.linalg.norm(q)
+    return q if q[3] >= 0 else -q
+
+
+def quaternion_to_rotation(q):
+    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+class HipBackend:
+    """CeresBackend (ceres_backend.cpp) on Context.bundle_adjust: the keyframes' states (camera -> world: qx qy qz qw px py
+    pz), their observations (landmark id, camera-frame point: what ReprojectionError's constructor forms, :24-28) and the
+    landmarks' world points, kept on the host; the solve runs on the device.  The first keyframe added is constant, as the
+    reference's keyframe 1 is (:155-159).  Nothing is removed: the outlier observations are returned
+    (removeObservation's body is commented out in the reference)."""
+
+    MAX_KEYFRAMES = 64
+
+    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15):
+        self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
+        self.poses = {}       # id -> [7]
+        self.obs = {}         # id -> (landmark ids [n] i64, camera points [n, 3])
+        self.landmarks = {}   # landmark id -> [3]
+        self.first = None
+
+    def add_keyframe(self, id, pose, landmark_ids, cam_points):
+        """a keyframe with its observations; a landmark id the backend has not seen starts at the world point the
+        observation gives under this pose (addNewLandmarks' toGlobalCoordinates)"""
+        pose = np.array(pose, np.float64).reshape(7)
+        lids = np.array(landmark_ids, np.int64).reshape(-1)
+        cam = np.array(cam_points, np.float64).reshape(-1, 3)
+        if len(lids) != len(cam):
+            raise MslamHipError(E_INVALID, "add_keyframe: %d landmark ids, %d camera points" % (len(lids), len(cam)))
+        if self.first is None:
+            self.first = int(id)
+        self.poses[int(id)] = pose
+        self.obs[int(id)] = (lids, cam)
+        world = cam @ quaternion_to_rotation(pose[:4]).T + pose[4:]
+        for l, w in zip(lids.tolist(), world):
+            self.landmarks.setdefault(l, w.copy())
+
+    def neighbours(self, ref, graph, deep_level=1):
+        """getNeighbourKeyframes (basic_map.cpp:209-237) with its `level <= deepLevel` test, as HipKeyframeTracker.neighbours
+        restates it; more than 64: the 64 largest ids"""
+        result, queue = set(), [(ref, 0)]
+        while queue:
+            cur, level = queue.pop(0)
+            result.add(cur)
+            if level <= deep_level:
+                queue.extend((nb, level + 1) for nb in sorted(graph.get(cur, ())) if nb not in result)
+        return sorted(k for k in result if k in self.poses)[-self.MAX_KEYFRAMES:]
+
+    def problem(self, kf_ids):
+        """the arrays Context.bundle_adjust takes for the listed keyframes -> (poses, fixed, landmark id list, landmarks,
+        obs_kf, obs_lm, obs_cam)"""
+        index, lids, okf, olm, ocam = {}, [], [], [], []
+        for k, id in enumerate(kf_ids):
+            ids, cam = self.obs[id]
+            for l in ids.tolist():
+                if l not in index:
+                    index[l] = len(lids)
+                    lids.append(l)
+            okf.append(np.full(len(ids), k, np.int32))
+            olm.append(np.array([index[l] for l in ids.tolist()], np.int32))
+            ocam.append(cam)
+        poses = np.array([self.poses[id] for id in kf_ids], np.float64).reshape(-1, 7)
+        fixed = np.array([id == self.first for id in kf_ids], np.uint8)
+        lm = np.array([self.landmarks[l] for l in lids], np.float64).reshape(-1, 3)
+        cat = lambda a, dt, w: np.concatenate(a) if a else np.zeros((0,) + w, dt)
+        return poses, fixed, lids, lm, cat(okf, np.int32, ()), cat(olm, np.int32, ()), cat(ocam, np.float64, (3,))
+
+    def _solve(self, kf_ids):
+        poses, fixed, lids, lm, okf, olm, ocam = self.problem(kf_ids)
+        res = self.ctx.bundle_adjust(poses, lm, okf, olm, ocam, fixed, self.max_iterations, self.outlier_threshold)
+        if res["termination"] != 2:
+            for k, id in enumerate(kf_ids):
+                self.poses[id] = res["poses"][k].copy()
+            for i, l in enumerate(lids):
+                self.landmarks[l] = res["landmarks"][i].copy()
+        res.update(keyframes=list(kf_ids), landmark_ids=np.array(lids, np.int64),
+                   outlier_observations=[(kf_ids[k], lids[l]) for k, l in zip(okf[res["outlier"]], olm[res["outlier"]])])
+        return res
+
+    def local_ba(self, ref_id, graph):
+        """localBundleAdjustment (:162-171): the observations of getNeighbourKeyframes(ref, deepLevel = 1)"""
+        return self._solve(self.neighbours(ref_id, graph, 1))
+
+    def global_ba(self):
+        """globalBundleAdjustment (:173-183) over every keyframe; more than 64 is MslamHipError(E_CAPACITY): the reduced
+        system is dense"""
+        if len(self.poses) > self.MAX_KEYFRAMES:
+            raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), self.MAX_KEYFRAMES))
+        return self._solve(sorted(self.poses))
+
+
 class HipKeyframeTracker:
     """The reference front end's loop over frames (RgbdFeatureFrontend::processSensorData, rgbd_feature_frontend.cpp:185-222)
     on the device-resident keyframe store: initFirstKeyframe on the first frame (:433-470: every keypoint with a valid
@@ -1021,6 +1176,12 @@ class HipKeyframeTracker:
     in self.ids, the vote list or the relocalisation candidates.  The context's max_keypoints must hold the union; one that
     does not fit raises MslamHipError(E_CAPACITY).
 
+    local_ba = True (needs local_map_depth, for the graph): a HipBackend is fed at every keyframe — the pose from the tracked
+    pose, the landmark ids from Context.kf_read_ids, the camera points from entry_kp and Context.backproject — and runs
+    local_ba on the new keyframe's neighbourhood (CeresBackend::process, ceres_backend.cpp:92-106); Context.kf_update_world
+    then writes the refined points into the store and the refined keyframe poses are kept in self.backend.poses;
+    self.ba_results holds every solve's summary.  Off by default: every call computes what it computed before.
+
     guided_radius = r (> 0): Context.set_guided_match(r, guided_max_distance) with the context's frame size — every track
     call here has a guess, so every one of them matches each landmark within r px of its projection under the previous
     pose (DEVIATES: the reference matches brute force); the relocalisation after a failure has no guess and matches brute
@@ -1030,8 +1191,12 @@ class HipKeyframeTracker:
 
     def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
                  reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
-                 reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256):
+                 reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False):
         self.ctx = ctx
+        if local_ba and local_map_depth is None:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: local_ba needs local_map_depth (the covisibility graph)")
+        self.backend = HipBackend(ctx) if local_ba else None
+        self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)
         self.local_map_depth = local_map_depth
@@ -1057,6 +1222,8 @@ class HipKeyframeTracker:
             xyz, valid = self.ctx.backproject(depth, xy, self.factor, self.focal, self.principal)
             keep = valid & (xyz[:, 2] <= self.z_max)
             self.ctx.kf_add(0, np.asarray(desc, np.uint8).reshape(-1, 32)[keep], xyz[keep])   # identity pose: world = camera point
+            if self.backend is not None:
+                self.backend.add_keyframe(0, (0, 0, 0, 1, 0, 0, 0), self.ctx.kf_read_ids(0), xyz[keep])
             self.ids, self.reference = [0], 0
             self.graph = {0: set()}
             return dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
@@ -1090,6 +1257,8 @@ class HipKeyframeTracker:
                             self.graph[new_id].add(other)
                             self.graph[other].add(new_id)
                     self._local_map_of = None   # a keyframe was added: the local map is rebuilt
+                    if self.backend is not None:
+                        self._local_ba(new_id, res, xy, depth)
         else:
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
@@ -1146,6 +1315,8 @@ class HipKeyframeTracker:
                     if res["keyframe_added"]:
                         self._keyframe_added(new_id)
                         o["keyframe"] = new_id
+                        if self.backend is not None:
+                            self._local_ba(new_id, res, xys[i + s], depths[i + s])
                 else:
                     reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
                                                 self.iterations, self.reprojection_error, seed + s,
@@ -1170,6 +1341,18 @@ class HipKeyframeTracker:
                     self.graph[new_id].add(other)
                     self.graph[other].add(new_id)
             self._local_map_of = None
+
+    def _local_ba(self, new_id, res, xy, depth):
+        """CeresBackend::process for the keyframe just added: feed the backend, solve, write the refined points back"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        cam, ok = self.ctx.backproject(depth, xy[res["entry_kp"]], self.factor, self.focal, self.principal)
+        R = np.asarray(res["R"], np.float64).reshape(3, 3)      # world -> camera; the keyframe's state is camera -> world
+        pose = np.concatenate([rotation_to_quaternion(R.T), -R.T @ np.asarray(res["tvec"], np.float64)])
+        self.backend.add_keyframe(new_id, pose, self.ctx.kf_read_ids(new_id)[ok], cam[ok])   # (an entry's keypoints have a depth)
+        ba = self.backend.local_ba(new_id, self.graph)
+        if ba["termination"] != 2:
+            ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
+        self.ba_results.append(ba)
 
     def neighbours(self, ref):
         """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than

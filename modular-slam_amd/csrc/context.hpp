@@ -150,6 +150,10 @@ struct mslam_hip_ctx
     // single-problem min-MSE PnP scratch (mslam_hip_pnp_min_mse): [obj | img | pose | info | n] in one block, grown on demand
     mslam::DevBuf<double> d_mse1;
     bool pnp_attr_set = false; // the > 64 KB dynamic-LDS attribute of the PnP kernels, per context (= per device)
+    // bundle adjustment (mslam_hip_bundle_adjust, k_ba.hip), grown on demand: every device array of one solve, and the
+    // mapped termination word the host reads between batches of iterations
+    mslam::DevBuf<uint8_t> d_ba;
+    mslam::PinnedBuf<int32_t> h_ba;
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

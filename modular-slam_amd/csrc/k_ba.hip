@@ -1,0 +1,964 @@
+// k_ba.hip — bundle adjustment: the solve of CeresBackend::bundleAdjustment (reference ceres_backend.cpp:185-240).
+//
+// Levenberg-Marquardt over keyframe poses (q, p) and landmarks X of cost = 1/2 sum_m |r_m|^2 with
+//     r_m = rot(q^-1, X) - rot(q^-1, p) - obs_cam[m]                                  (ReprojectionError::operator(), :31-47)
+// The trust-region loop is the one k_pnp_mse.hip restates from Ceres 2.2's published sources (trust_region_minimizer.cc,
+// levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc) with the Solver::Options defaults of solver.h: function
+// tolerance 1e-6, gradient tolerance 1e-10, parameter tolerance 1e-8, initial radius 1e4, monotonic steps, Jacobi scaling.
+// The SAME / DEVIATES table is in include/mslam_hip.h, the walk-through in DESIGN.md 4.14.  PARITY UNPINNED: no Ceres
+// build exists here; tests/ba_ref.py restates the same algorithm in numpy with two linear solvers.
+//
+// A free pose has the tangent (delta, dp): EigenQuaternionManifold's Plus q_delta (x) q and the position.  With R^T the matrix
+// of v -> rot(q^-1, v) and d = X - p the derivatives are dr/dX = R^T, dr/dp = -R^T, dr/d(delta) = 2 R^T [d]x.
+//
+// One trust-region iteration is nine launches on the context's stream; every one reads the control block first and returns
+// when the solve has ended, so the host may enqueue iterations ahead and look at a mapped word between batches:
+//   k_ba_landmarks  a lane per landmark walks the landmark's row in order: V_l = sum J_l^T J_l, g_l = sum J_l^T r; the
+//                   column scaling at the first pass; then (S V_l S + D^2)^-1 for this iteration's radius
+//   k_ba_cameras    a workgroup per free keyframe walks the keyframe's row by lane stride: U_k (21 entries), g_k, by a
+//                   fixed butterfly and a fixed sum over the four waves; W = J_c^T J_l (6 x 3) stored per observation
+//   k_ba_check      one wave: FinalizeIterationAndCheckIfMinimizerCanContinue (iteration cap, gradient, radius)
+//   k_ba_schur      a wave per pair k1 <= k2 of free keyframes joins the two rows (both sorted by landmark):
+//                   S_k1k2 = delta U_k1 - sum_l W_k1l V_l^-1 W_k2l^T and, on the diagonal, the reduced right-hand side
+//   k_ba_solve      one workgroup: Cholesky of the reduced system (at most 384 x 384, in global memory), both substitutions
+//   k_ba_backsub    a lane per landmark: y_l = V_l^-1 (g_l - sum W^T y_c), in row order
+//   k_ba_candidate  Plus on every pose and landmark
+//   k_ba_eval       a lane per observation: the model cost change term -(J_s s) . (f + J_s s / 2) at x and the cost at the
+//                   candidate, summed per block by a fixed tree
+//   k_ba_control    one wave: sums the block partials in a fixed order, step validity, parameter / function tolerance,
+//                   accept or reject, radius
+// Jacobians are kept unscaled (U, V, W, g) and scaled where they are used, as k_pnp_mse.hip does; after a rejected step the
+// state has not moved, so the block kernels reuse what they stored and only the damping is redone.
+// No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
+// another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
+#include "context.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace mslam
+{
+
+constexpr int kBaMaxKeyframes = 64;
+constexpr int kBaSolveThreads = 6 * kBaMaxKeyframes; // one thread per row of the reduced system
+constexpr int kBaBatch = 4;                          // iterations enqueued between two looks at the termination word
+constexpr int kBaMaxInvalidSteps = 5;
+constexpr double kBaInitialRadius = 1e4, kBaMaxRadius = 1e16, kBaMinRadius = 1e-32;
+constexpr double kBaMinDiagonal = 1e-6, kBaMaxDiagonal = 1e32;
+constexpr double kBaMinRelativeDecrease = 1e-3;
+constexpr double kBaFunctionTol = 1e-6, kBaGradientTol = 1e-10, kBaParameterTol = 1e-8;
+constexpr int kBaConvergence = 0, kBaNoConvergence = 1, kBaFailure = 2;
+
+struct BaCtrl
+{
+    int32_t done, termination, iteration, need_jac, first, successful, invalid_run, solve_bad;
+    int32_t rejected, invalid_total, max_iterations, pad;
+    double radius, decrease_factor, x_cost, initial_cost;
+};
+
+struct BaArgs
+{
+    int K, L, M, n;     // n = 6 x (free keyframes with observations): the reduced system's size
+    int n_pairs, n_blocks; // pairs of free keyframes; blocks of k_ba_eval
+    // the problem
+    const int32_t *obs_kf, *obs_lm;
+    const double* obs_cam;
+    const int32_t *lm_ptr, *lm_obs;         // observations by landmark (rows in input order)
+    const int32_t *kf_ptr, *kf_obs, *kf_lm; // observations by keyframe, every row sorted by landmark; kf_lm = the landmark
+    const int32_t* ci;                      // [K] the keyframe's block in the reduced system, -1: constant or unobserved
+    const int32_t* pairs;                   // [n_pairs][2] keyframes k1, k2 with ci[k1] <= ci[k2]
+    const uint8_t* lm_active;               // [L] the landmark has an observation
+    // state and candidate
+    double *pose, *lm, *cand_pose, *cand_lm;
+    // blocks
+    double *V, *gl, *Vinv, *sl; // [L] x 6, 3, 6, 3
+    double *U, *gc, *sc, *W;    // [K] x 21, 6, 6; [M] x 18
+    double *S, *rhs, *yc, *yl;  // n x n column-major, n, n, [L] x 3
+    double* part;               // [2][n_blocks]: model cost change, candidate cost
+    BaCtrl* ctrl;
+    int32_t* h_done; // mapped
+};
+
+__device__ __forceinline__ double ba_wave_sum(double s)
+{
+    for(int m = 32; m >= 1; m >>= 1)
+        s += __shfl_xor(s, m, 64);
+    return s;
+}
+__device__ __forceinline__ double ba_wave_max(double s)
+{
+    for(int m = 32; m >= 1; m >>= 1)
+        s = fmax(s, __shfl_xor(s, m, 64));
+    return s;
+}
+
+__device__ __forceinline__ int ba_tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c < 6
+__device__ __forceinline__ int ba_tri3(int r, int c) { return r * 3 - r * (r - 1) / 2 + (c - r); } // r <= c < 3
+
+// Eigen's inverse(): conjugate / squared norm
+__device__ __forceinline__ void ba_inverse(const double* __restrict__ q, double qi[4])
+{
+    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    qi[0] = -q[0] / n2, qi[1] = -q[1] / n2, qi[2] = -q[2] / n2, qi[3] = q[3] / n2;
+}
+// Eigen's _transformVector: v + w uv + u x uv, uv = 2 (u x v)
+__device__ __forceinline__ void ba_rotate(const double qi[4], const double v[3], double out[3])
+{
+    double uv[3] = {qi[1] * v[2] - qi[2] * v[1], qi[2] * v[0] - qi[0] * v[2], qi[0] * v[1] - qi[1] * v[0]};
+    uv[0] += uv[0], uv[1] += uv[1], uv[2] += uv[2];
+    out[0] = v[0] + qi[3] * uv[0] + (qi[1] * uv[2] - qi[2] * uv[1]);
+    out[1] = v[1] + qi[3] * uv[1] + (qi[2] * uv[0] - qi[0] * uv[2]);
+    out[2] = v[2] + qi[3] * uv[2] + (qi[0] * uv[1] - qi[1] * uv[0]);
+}
+__device__ __forceinline__ void ba_residual(const double* __restrict__ pose, const double* __restrict__ X, const double* __restrict__ obs,
+                                            double r[3])
+{
+    double qi[4], a[3], b[3];
+    ba_inverse(pose, qi);
+    const double x[3] = {X[0], X[1], X[2]}, p[3] = {pose[4], pose[5], pose[6]};
+    ba_rotate(qi, x, a);
+    ba_rotate(qi, p, b);
+    r[0] = a[0] - b[0] - obs[0], r[1] = a[1] - b[1] - obs[1], r[2] = a[2] - b[2] - obs[2];
+}
+// the matrix of v -> ba_rotate(qi, v): (1 - 2 |u|^2) I + 2 u u^T + 2 w [u]x, row-major
+__device__ __forceinline__ void ba_matrix(const double qi[4], double Rt[9])
+{
+    const double x = qi[0], y = qi[1], z = qi[2], w = qi[3];
+    const double xx = x * x, yy = y * y, zz = z * z;
+    Rt[0] = 1.0 - 2.0 * (yy + zz), Rt[1] = 2.0 * (x * y - w * z), Rt[2] = 2.0 * (x * z + w * y);
+    Rt[3] = 2.0 * (x * y + w * z), Rt[4] = 1.0 - 2.0 * (xx + zz), Rt[5] = 2.0 * (y * z - w * x);
+    Rt[6] = 2.0 * (x * z - w * y), Rt[7] = 2.0 * (y * z + w * x), Rt[8] = 1.0 - 2.0 * (xx + yy);
+}
+// J_c = [2 R^T [d]x | -R^T] (3 x 6), d = X - p
+__device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const double d[3], double Jc[3][6])
+{
+    const double dx[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+    for(int i = 0; i < 3; ++i)
+        for(int j = 0; j < 3; ++j)
+        {
+            Jc[i][j] = 2.0 * (Rt[i * 3] * dx[j] + Rt[i * 3 + 1] * dx[3 + j] + Rt[i * 3 + 2] * dx[6 + j]);
+            Jc[i][3 + j] = -Rt[i * 3 + j];
+        }
+}
+
+// EigenQuaternionManifold::Plus (manifold.h QuaternionPlus, x y z w): q_delta (x) q
+__device__ __forceinline__ void ba_quaternion_plus(const double* __restrict__ q, const double d[3], double out[4])
+{
+    const double norm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if(!(norm > 0.0))
+    {
+        out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
+        return;
+    }
+    const double sbd = sin(norm) / norm;
+    const double ax = sbd * d[0], ay = sbd * d[1], az = sbd * d[2], aw = cos(norm);
+    out[0] = aw * q[0] + ax * q[3] + ay * q[2] - az * q[1];
+    out[1] = aw * q[1] + ay * q[3] + az * q[0] - ax * q[2];
+    out[2] = aw * q[2] + az * q[3] + ax * q[1] - ay * q[0];
+    out[3] = aw * q[3] - ax * q[0] - ay * q[1] - az * q[2];
+}
+
+// ---- blocks ------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
+{
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if(l >= a.L || !a.lm_active[l])
+        return;
+    double V[6], g[3];
+    if(ct->need_jac)
+    {
+        for(int k = 0; k < 6; ++k)
+            V[k] = 0.0;
+        g[0] = g[1] = g[2] = 0.0;
+        const double* X = a.lm + (size_t)l * 3;
+        for(int i = a.lm_ptr[l]; i < a.lm_ptr[l + 1]; ++i)
+        {
+            const int m = a.lm_obs[i];
+            const double* pose = a.pose + (size_t)a.obs_kf[m] * 7;
+            double qi[4], Rt[9], r[3];
+            ba_inverse(pose, qi);
+            ba_matrix(qi, Rt);
+            ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
+            for(int rr = 0; rr < 3; ++rr)
+            {
+                for(int c = rr; c < 3; ++c)
+                    V[ba_tri3(rr, c)] += Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c];
+                g[rr] += Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2];
+            }
+        }
+        for(int k = 0; k < 6; ++k)
+            a.V[(size_t)l * 6 + k] = V[k];
+        for(int k = 0; k < 3; ++k)
+            a.gl[(size_t)l * 3 + k] = g[k];
+    }
+    else
+        for(int k = 0; k < 6; ++k)
+            V[k] = a.V[(size_t)l * 6 + k];
+    double s[3];
+    for(int k = 0; k < 3; ++k)
+    {
+        if(ct->first)
+            a.sl[(size_t)l * 3 + k] = s[k] = 1.0 / (1.0 + sqrt(V[ba_tri3(k, k)]));
+        else
+            s[k] = a.sl[(size_t)l * 3 + k];
+    }
+    // A = S V S + D^2, D^2 = clamp(diag(S V S), 1e-6, 1e32) / radius; its inverse from the cofactors
+    const double radius = ct->radius;
+    double A[6];
+    for(int r = 0; r < 3; ++r)
+        for(int c = r; c < 3; ++c)
+            A[ba_tri3(r, c)] = s[r] * V[ba_tri3(r, c)] * s[c];
+    for(int k = 0; k < 3; ++k)
+        A[ba_tri3(k, k)] += fmin(fmax(A[ba_tri3(k, k)], kBaMinDiagonal), kBaMaxDiagonal) / radius;
+    const double a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
+    const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+    const double det = a00 * c00 + a01 * c01 + a02 * c02;
+    double* I = a.Vinv + (size_t)l * 6;
+    I[0] = c00 / det, I[1] = c01 / det, I[2] = c02 / det;
+    I[3] = (a00 * a22 - a02 * a02) / det, I[4] = (a01 * a02 - a00 * a12) / det, I[5] = (a00 * a11 - a01 * a01) / det;
+}
+
+__global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
+{
+    __shared__ double red[4][27];
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done || !ct->need_jac)
+        return;
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if(a.ci[k] < 0)
+        return;
+    const double* pose = a.pose + (size_t)k * 7;
+    double qi[4], Rt[9];
+    ba_inverse(pose, qi);
+    ba_matrix(qi, Rt);
+    double acc[27];
+    for(int j = 0; j < 27; ++j)
+        acc[j] = 0.0;
+    for(int pos = a.kf_ptr[k] + tid; pos < a.kf_ptr[k + 1]; pos += 256)
+    {
+        const int m = a.kf_obs[pos];
+        const double* X = a.lm + (size_t)a.obs_lm[m] * 3;
+        const double d[3] = {X[0] - pose[4], X[1] - pose[5], X[2] - pose[6]};
+        double r[3], Jc[3][6];
+        ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
+        ba_camera_jacobian(Rt, d, Jc);
+        int j = 0;
+        for(int rr = 0; rr < 6; ++rr)
+            for(int c = rr; c < 6; ++c)
+                acc[j++] += Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c];
+        for(int rr = 0; rr < 6; ++rr)
+            acc[21 + rr] += Jc[0][rr] * r[0] + Jc[1][rr] * r[1] + Jc[2][rr] * r[2];
+        double* W = a.W + (size_t)m * 18; // J_c^T J_l, J_l = R^T
+        for(int rr = 0; rr < 6; ++rr)
+            for(int c = 0; c < 3; ++c)
+                W[rr * 3 + c] = Jc[0][rr] * Rt[c] + Jc[1][rr] * Rt[3 + c] + Jc[2][rr] * Rt[6 + c];
+    }
+    for(int j = 0; j < 27; ++j)
+    {
+        const double v = ba_wave_sum(acc[j]);
+        if(lane == 0)
+            red[wave][j] = v;
+    }
+    __syncthreads();
+    if(tid < 27)
+    {
+        const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        if(tid < 21)
+            a.U[(size_t)k * 21 + tid] = v;
+        else
+            a.gc[(size_t)k * 6 + (tid - 21)] = v;
+    }
+    if(tid < 6 && ct->first)
+    {
+        const int j = ba_tri(tid, tid);
+        a.sc[(size_t)k * 6 + tid] = 1.0 / (1.0 + sqrt(((red[0][j] + red[1][j]) + red[2][j]) + red[3][j]));
+    }
+}
+
+// ---- FinalizeIterationAndCheckIfMinimizerCanContinue: one wave ------------------------------------------------------------
+
+__device__ __forceinline__ void ba_finish(const BaArgs& a, int lane, int termination)
+{
+    if(lane == 0)
+    {
+        a.ctrl->termination = termination;
+        a.ctrl->done = 1;
+        *a.h_done = 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
+{
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    double x_cost = ct->x_cost;
+    if(ct->first)
+    {
+        // iteration 0: the cost at the start, from k_ba_eval's block partials
+        double s = 0.0;
+        for(int b = lane; b < a.n_blocks; b += 64)
+            s += a.part[a.n_blocks + b];
+        x_cost = ba_wave_sum(s);
+    }
+    // the evaluation is usable (ResidualBlock::Evaluate's validity, seen through the sums as in k_pnp_mse.hip), and
+    // |x - Plus(x, -g)|_inf over the ambient parameters
+    bool ok = isfinite(x_cost);
+    double gmax = 0.0;
+    for(int k = lane; k < a.K; k += 64)
+    {
+        if(a.ci[k] < 0)
+            continue;
+        const double* q = a.pose + (size_t)k * 7;
+        const double* g = a.gc + (size_t)k * 6;
+        const double md[3] = {-g[0], -g[1], -g[2]};
+        double qp[4];
+        ba_quaternion_plus(q, md, qp);
+        for(int j = 0; j < 4; ++j)
+            gmax = fmax(gmax, fabs(q[j] - qp[j]));
+        for(int j = 0; j < 3; ++j)
+            gmax = fmax(gmax, fabs(q[4 + j] - (q[4 + j] + (-g[3 + j]))));
+        for(int j = 0; j < 6; ++j)
+            ok = ok && isfinite(g[j]) && isfinite(a.U[(size_t)k * 21 + ba_tri(j, j)]);
+    }
+    for(int l = lane; l < a.L; l += 64)
+    {
+        if(!a.lm_active[l])
+            continue;
+        const double* X = a.lm + (size_t)l * 3;
+        const double* g = a.gl + (size_t)l * 3;
+        for(int j = 0; j < 3; ++j)
+        {
+            gmax = fmax(gmax, fabs(X[j] - (X[j] + (-g[j]))));
+            ok = ok && isfinite(g[j]) && isfinite(a.V[(size_t)l * 6 + ba_tri3(j, j)]);
+        }
+    }
+    gmax = ba_wave_max(gmax);
+    ok = __all(ok);
+    if(lane == 0 && ct->first)
+        ct->x_cost = ct->initial_cost = x_cost;
+    if(!ok)
+        return ba_finish(a, lane, kBaFailure);
+    if(ct->iteration >= ct->max_iterations)
+        return ba_finish(a, lane, kBaNoConvergence);
+    if(ct->successful && gmax <= kBaGradientTol)
+        return ba_finish(a, lane, kBaConvergence);
+    if(ct->radius <= kBaMinRadius)
+        return ba_finish(a, lane, kBaConvergence);
+    if(lane == 0)
+    {
+        ct->iteration += 1;
+        ct->successful = 0;
+        ct->first = 0;
+        ct->solve_bad = 0;
+    }
+}
+
+// ---- the reduced camera system ------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_ba_schur(BaArgs a)
+{
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    const int k1 = a.pairs[blockIdx.x * 2], k2 = a.pairs[blockIdx.x * 2 + 1];
+    const int b1 = a.ci[k1], b2 = a.ci[k2];
+    const bool diag = k1 == k2;
+    double s1[6], s2[6];
+    for(int j = 0; j < 6; ++j)
+        s1[j] = a.sc[(size_t)k1 * 6 + j], s2[j] = a.sc[(size_t)k2 * 6 + j];
+    double acc[36], accr[6];
+    for(int j = 0; j < 36; ++j)
+        acc[j] = 0.0;
+    for(int j = 0; j < 6; ++j)
+        accr[j] = 0.0;
+    const int lo2 = a.kf_ptr[k2], hi2 = a.kf_ptr[k2 + 1];
+    for(int pos = a.kf_ptr[k1] + lane; pos < a.kf_ptr[k1 + 1]; pos += 64)
+    {
+        const int l = a.kf_lm[pos];
+        // the first observation of landmark l in row k2
+        int lo = lo2, hi = hi2;
+        while(lo < hi)
+        {
+            const int mid = (lo + hi) >> 1;
+            if(a.kf_lm[mid] < l)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if(!diag && (lo >= hi2 || a.kf_lm[lo] != l))
+            continue;
+        const double* W1 = a.W + (size_t)a.kf_obs[pos] * 18;
+        const double* Vi = a.Vinv + (size_t)l * 6;
+        const double* sl = a.sl + (size_t)l * 3;
+        // T = W1s V^-1 (6 x 3), W1s = S_c W1 S_l
+        double T[6][3];
+        for(int r = 0; r < 6; ++r)
+        {
+            const double w0 = s1[r] * W1[r * 3] * sl[0], w1 = s1[r] * W1[r * 3 + 1] * sl[1], w2 = s1[r] * W1[r * 3 + 2] * sl[2];
+            T[r][0] = w0 * Vi[0] + w1 * Vi[1] + w2 * Vi[2];
+            T[r][1] = w0 * Vi[1] + w1 * Vi[3] + w2 * Vi[4];
+            T[r][2] = w0 * Vi[2] + w1 * Vi[4] + w2 * Vi[5];
+        }
+        if(diag)
+        {
+            const double* g = a.gl + (size_t)l * 3;
+            const double g0 = sl[0] * g[0], g1 = sl[1] * g[1], g2 = sl[2] * g[2];
+            for(int r = 0; r < 6; ++r)
+                accr[r] += T[r][0] * g0 + T[r][1] * g1 + T[r][2] * g2;
+        }
+        for(int p2 = lo; p2 < hi2 && a.kf_lm[p2] == l; ++p2)
+        {
+            const double* W2 = a.W + (size_t)a.kf_obs[p2] * 18;
+            for(int c = 0; c < 6; ++c)
+            {
+                const double w0 = s2[c] * W2[c * 3] * sl[0], w1 = s2[c] * W2[c * 3 + 1] * sl[1], w2 = s2[c] * W2[c * 3 + 2] * sl[2];
+                for(int r = 0; r < 6; ++r)
+                    acc[r * 6 + c] += T[r][0] * w0 + T[r][1] * w1 + T[r][2] * w2;
+            }
+        }
+    }
+    // lane j keeps entry j of the block (j < 36), lane 36 + r entry r of the right-hand side
+    double mine = 0.0;
+    for(int j = 0; j < 36; ++j)
+    {
+        const double v = ba_wave_sum(acc[j]);
+        if(lane == j)
+            mine = v;
+    }
+    if(diag)
+        for(int j = 0; j < 6; ++j)
+        {
+            const double v = ba_wave_sum(accr[j]);
+            if(lane == 36 + j)
+                mine = v;
+        }
+    const size_t n = (size_t)a.n;
+    if(lane < 36)
+    {
+        const int r = lane / 6, c = lane % 6;
+        double v = -mine;
+        if(diag)
+        {
+            const double u = s1[r] * a.U[(size_t)k1 * 21 + (r <= c ? ba_tri(r, c) : ba_tri(c, r))] * s1[c];
+            v = u - mine;
+            if(r == c)
+                v = (u + fmin(fmax(u, kBaMinDiagonal), kBaMaxDiagonal) / ct->radius) - mine;
+        }
+        const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
+        a.S[row + col * n] = v;
+        if(!diag)
+            a.S[col + row * n] = v;
+    }
+    else if(diag && lane < 42)
+    {
+        const int r = lane - 36;
+        a.rhs[(size_t)b1 * 6 + r] = s1[r] * a.gc[(size_t)k1 * 6 + r] - mine;
+    }
+}
+
+// Cholesky S = L L^T in place (lower triangle, column-major), then L y = rhs and L^T x = y.  Thread i owns row i.
+__global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
+{
+    __shared__ double rowj[kBaSolveThreads], b[kBaSolveThreads];
+    __shared__ double sdiag;
+    __shared__ int bad;
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int i = threadIdx.x, n = a.n;
+    double* S = a.S;
+    if(i == 0)
+        bad = 0;
+    for(int j = 0; j < n; ++j)
+    {
+        if(i < j)
+            rowj[i] = S[(size_t)j + (size_t)i * n];
+        __syncthreads();
+        double v = 0.0;
+        if(i >= j && i < n)
+        {
+            v = S[(size_t)i + (size_t)j * n];
+            for(int k = 0; k < j; ++k)
+                v -= S[(size_t)i + (size_t)k * n] * rowj[k];
+        }
+        if(i == j)
+        {
+            if(!(v > 0.0))
+                bad = 1; // a non-positive pivot: the step is invalid; the factorisation goes on with bounded values
+            sdiag = sqrt(fmax(v, DBL_MIN));
+        }
+        __syncthreads();
+        if(i >= j && i < n)
+            S[(size_t)i + (size_t)j * n] = i == j ? sdiag : v / sdiag;
+        __syncthreads();
+    }
+    if(i < n)
+        b[i] = a.rhs[i];
+    __syncthreads();
+    for(int k = 0; k < n; ++k)
+    {
+        if(i == k)
+            b[k] = b[k] / S[(size_t)k + (size_t)k * n];
+        __syncthreads();
+        if(i > k && i < n)
+            b[i] -= S[(size_t)i + (size_t)k * n] * b[k];
+        __syncthreads();
+    }
+    for(int k = n - 1; k >= 0; --k)
+    {
+        if(i == k)
+            b[k] = b[k] / S[(size_t)k + (size_t)k * n];
+        __syncthreads();
+        if(i < k)
+            b[i] -= S[(size_t)k + (size_t)i * n] * b[k];
+        __syncthreads();
+    }
+    if(i < n)
+        a.yc[i] = b[i];
+    if(i == 0 && bad)
+        ct->solve_bad = 1;
+}
+
+__global__ __launch_bounds__(256) void k_ba_backsub(BaArgs a)
+{
+    if(a.ctrl->done)
+        return;
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if(l >= a.L || !a.lm_active[l])
+        return;
+    const double* sl = a.sl + (size_t)l * 3;
+    const double* g = a.gl + (size_t)l * 3;
+    double t[3] = {sl[0] * g[0], sl[1] * g[1], sl[2] * g[2]};
+    for(int i = a.lm_ptr[l]; i < a.lm_ptr[l + 1]; ++i)
+    {
+        const int m = a.lm_obs[i], k = a.obs_kf[m], bk = a.ci[k];
+        if(bk < 0)
+            continue;
+        const double* W = a.W + (size_t)m * 18;
+        const double* sc = a.sc + (size_t)k * 6;
+        const double* y = a.yc + (size_t)bk * 6;
+        for(int c = 0; c < 3; ++c)
+        {
+            double s = 0.0;
+            for(int r = 0; r < 6; ++r)
+                s += sc[r] * W[r * 3 + c] * sl[c] * y[r];
+            t[c] -= s;
+        }
+    }
+    const double* Vi = a.Vinv + (size_t)l * 6;
+    double* y = a.yl + (size_t)l * 3;
+    y[0] = Vi[0] * t[0] + Vi[1] * t[1] + Vi[2] * t[2];
+    y[1] = Vi[1] * t[0] + Vi[3] * t[1] + Vi[4] * t[2];
+    y[2] = Vi[2] * t[0] + Vi[4] * t[1] + Vi[5] * t[2];
+}
+
+// delta = step * scaling with step = -y; Plus.  Blocks outside the problem are copied.
+__global__ __launch_bounds__(256) void k_ba_candidate(BaArgs a)
+{
+    if(a.ctrl->done)
+        return;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if(t < a.K)
+    {
+        const double* x = a.pose + (size_t)t * 7;
+        double* c = a.cand_pose + (size_t)t * 7;
+        const int bk = a.ci[t];
+        if(bk < 0)
+        {
+            for(int j = 0; j < 7; ++j)
+                c[j] = x[j];
+            return;
+        }
+        const double* y = a.yc + (size_t)bk * 6;
+        const double* sc = a.sc + (size_t)t * 6;
+        const double d[3] = {-y[0] * sc[0], -y[1] * sc[1], -y[2] * sc[2]};
+        double q[4];
+        ba_quaternion_plus(x, d, q);
+        c[0] = q[0], c[1] = q[1], c[2] = q[2], c[3] = q[3];
+        for(int j = 0; j < 3; ++j)
+            c[4 + j] = x[4 + j] + (-y[3 + j] * sc[3 + j]);
+    }
+    else if(t < a.K + a.L)
+    {
+        const int l = t - a.K;
+        const double* x = a.lm + (size_t)l * 3;
+        double* c = a.cand_lm + (size_t)l * 3;
+        const bool on = a.lm_active[l];
+        for(int j = 0; j < 3; ++j)
+            c[j] = on ? x[j] + (-a.yl[(size_t)l * 3 + j] * a.sl[(size_t)l * 3 + j]) : x[j];
+    }
+}
+
+// the sum of v over the block, by a fixed tree: butterfly per wave, then the four waves in order; valid in thread 0
+__device__ __forceinline__ double ba_block_sum(double v, double* red)
+{
+    v = ba_wave_sum(v);
+    if((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+    return s;
+}
+
+// at_start: only the cost at the state (pose, lm), for iteration 0
+__global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
+{
+    __shared__ double red[4];
+    if(a.ctrl->done)
+        return;
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    double model = 0.0, cost = 0.0;
+    if(m < a.M)
+    {
+        const int k = a.obs_kf[m], l = a.obs_lm[m];
+        const double* obs = a.obs_cam + (size_t)m * 3;
+        double r[3];
+        if(at_start)
+            ba_residual(a.pose + (size_t)k * 7, a.lm + (size_t)l * 3, obs, r);
+        else
+        {
+            const double* pose = a.pose + (size_t)k * 7;
+            const double* X = a.lm + (size_t)l * 3;
+            double f[3], qi[4], Rt[9];
+            ba_residual(pose, X, obs, f);
+            ba_inverse(pose, qi);
+            ba_matrix(qi, Rt);
+            // J_s s = R^T (2 d x delta - dp + dX)
+            double v[3] = {-a.yl[(size_t)l * 3] * a.sl[(size_t)l * 3], -a.yl[(size_t)l * 3 + 1] * a.sl[(size_t)l * 3 + 1],
+                           -a.yl[(size_t)l * 3 + 2] * a.sl[(size_t)l * 3 + 2]};
+            const int bk = a.ci[k];
+            if(bk >= 0)
+            {
+                const double* y = a.yc + (size_t)bk * 6;
+                const double* sc = a.sc + (size_t)k * 6;
+                const double dl[3] = {-y[0] * sc[0], -y[1] * sc[1], -y[2] * sc[2]};
+                const double d[3] = {X[0] - pose[4], X[1] - pose[5], X[2] - pose[6]};
+                v[0] += 2.0 * (d[1] * dl[2] - d[2] * dl[1]) - (-y[3] * sc[3]);
+                v[1] += 2.0 * (d[2] * dl[0] - d[0] * dl[2]) - (-y[4] * sc[4]);
+                v[2] += 2.0 * (d[0] * dl[1] - d[1] * dl[0]) - (-y[5] * sc[5]);
+            }
+            double Js[3];
+            for(int j = 0; j < 3; ++j)
+                Js[j] = Rt[j * 3] * v[0] + Rt[j * 3 + 1] * v[1] + Rt[j * 3 + 2] * v[2];
+            model = -(Js[0] * (f[0] + Js[0] / 2.0) + Js[1] * (f[1] + Js[1] / 2.0) + Js[2] * (f[2] + Js[2] / 2.0));
+            ba_residual(a.cand_pose + (size_t)k * 7, a.cand_lm + (size_t)l * 3, obs, r);
+        }
+        cost = 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    }
+    const double ms = ba_block_sum(model, red), cs = ba_block_sum(cost, red);
+    if(threadIdx.x == 0)
+    {
+        a.part[blockIdx.x] = ms;
+        a.part[a.n_blocks + blockIdx.x] = cs;
+    }
+}
+
+// ---- the trust-region bookkeeping of one iteration: one wave ----------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_ba_control(BaArgs a)
+{
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    double ms = 0.0, cs = 0.0;
+    for(int b = lane; b < a.n_blocks; b += 64)
+        ms += a.part[b], cs += a.part[a.n_blocks + b];
+    const double model_cost_change = ba_wave_sum(ms);
+    double cand_cost = ba_wave_sum(cs);
+    // the step is finite; |x|^2 and |x - candidate|^2 over the ambient parameters of the problem's blocks
+    bool finite = true;
+    double xn = 0.0, sn = 0.0;
+    for(int k = lane; k < a.K; k += 64)
+    {
+        const int bk = a.ci[k];
+        if(bk < 0)
+            continue;
+        for(int j = 0; j < 6; ++j)
+            finite = finite && isfinite(a.yc[(size_t)bk * 6 + j]);
+        for(int j = 0; j < 7; ++j)
+        {
+            const double x = a.pose[(size_t)k * 7 + j], d = x - a.cand_pose[(size_t)k * 7 + j];
+            xn += x * x, sn += d * d;
+        }
+    }
+    for(int l = lane; l < a.L; l += 64)
+    {
+        if(!a.lm_active[l])
+            continue;
+        for(int j = 0; j < 3; ++j)
+        {
+            finite = finite && isfinite(a.yl[(size_t)l * 3 + j]);
+            const double x = a.lm[(size_t)l * 3 + j], d = x - a.cand_lm[(size_t)l * 3 + j];
+            xn += x * x, sn += d * d;
+        }
+    }
+    finite = __all(finite);
+    const double x_norm = sqrt(ba_wave_sum(xn)), step_norm = sqrt(ba_wave_sum(sn));
+    const double x_cost = ct->x_cost;
+    double radius = ct->radius, decrease_factor = ct->decrease_factor;
+    if(!(finite && !ct->solve_bad && model_cost_change > 0.0))
+    {
+        // HandleInvalidStep
+        if(lane == 0)
+            ct->invalid_total += 1;
+        if(ct->invalid_run + 1 >= kBaMaxInvalidSteps)
+            return ba_finish(a, lane, kBaFailure);
+        if(lane == 0)
+        {
+            ct->invalid_run += 1;
+            ct->radius = radius / decrease_factor;
+            ct->decrease_factor = decrease_factor * 2.0;
+            ct->need_jac = 0;
+        }
+        return;
+    }
+    if(!isfinite(cand_cost))
+        cand_cost = DBL_MAX;
+    if(lane == 0)
+        ct->invalid_run = 0;
+    if(step_norm <= kBaParameterTol * (x_norm + kBaParameterTol))
+        return ba_finish(a, lane, kBaConvergence);
+    if(fabs(x_cost - cand_cost) <= kBaFunctionTol * x_cost)
+        return ba_finish(a, lane, kBaConvergence);
+    const double relative_decrease = cand_cost >= DBL_MAX ? -DBL_MAX : (x_cost - cand_cost) / model_cost_change;
+    if(relative_decrease > kBaMinRelativeDecrease)
+    {
+        for(int k = lane; k < a.K; k += 64)
+            if(a.ci[k] >= 0)
+                for(int j = 0; j < 7; ++j)
+                    a.pose[(size_t)k * 7 + j] = a.cand_pose[(size_t)k * 7 + j];
+        for(int l = lane; l < a.L; l += 64)
+            if(a.lm_active[l])
+                for(int j = 0; j < 3; ++j)
+                    a.lm[(size_t)l * 3 + j] = a.cand_lm[(size_t)l * 3 + j];
+        if(lane == 0)
+        {
+            const double q = 2.0 * relative_decrease - 1.0;
+            radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
+            ct->radius = fmin(kBaMaxRadius, radius);
+            ct->decrease_factor = 2.0;
+            ct->x_cost = cand_cost;
+            ct->successful = 1;
+            ct->need_jac = 1;
+        }
+    }
+    else if(lane == 0)
+    {
+        ct->rejected += 1;
+        ct->radius = radius / decrease_factor;
+        ct->decrease_factor = decrease_factor * 2.0;
+        ct->need_jac = 0;
+    }
+}
+
+// createOutput (:212-230): |r_m|^2 > threshold^2 at (pose, lm)
+__global__ __launch_bounds__(256) void k_ba_outliers(BaArgs a, const double* __restrict__ pose, const double* __restrict__ lm,
+                                                     double threshold2, uint8_t* __restrict__ out)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if(m >= a.M)
+        return;
+    double r[3];
+    ba_residual(pose + (size_t)a.obs_kf[m] * 7, lm + (size_t)a.obs_lm[m] * 3, a.obs_cam + (size_t)m * 3, r);
+    out[m] = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) > threshold2 ? 1 : 0;
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
+                                       const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M,
+                                       int max_iterations, double outlier_threshold, uint8_t* outlier,
+                                       mslam_hip_ba_summary* summary)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(K < 0 || K > kBaMaxKeyframes)
+        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: K outside 0..64");
+    if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !poses) ||
+       (L > 0 && !landmarks) || (M > 0 && (!obs_kf || !obs_lm || !obs_cam)))
+        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: bad argument (counts, pointers, max_iterations >= 0, threshold >= 0)");
+    for(int m = 0; m < M; ++m)
+        if(obs_kf[m] < 0 || obs_kf[m] >= K || obs_lm[m] < 0 || obs_lm[m] >= L)
+            return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: observation " + std::to_string(m) + " names a keyframe or landmark out of range");
+    for(int k = 0; k < K; ++k)
+    {
+        const double* q = poses + (size_t)k * 7;
+        const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        if(!(std::fabs(norm - 1.0) <= 1e-6))
+            return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: the quaternion of pose " + std::to_string(k) + " is not unit");
+    }
+    mslam_hip_ba_summary sum{};
+    if(M == 0)
+    {
+        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
+        if(summary)
+            *summary = sum;
+        return MSLAM_HIP_OK;
+    }
+    // the two orders of the observations, by stable counting sorts: by landmark; by keyframe with rows sorted by landmark
+    std::vector<int32_t> lm_ptr((size_t)L + 1, 0), lm_obs((size_t)M), kf_ptr((size_t)K + 1, 0), kf_obs((size_t)M), kf_lm((size_t)M);
+    for(int m = 0; m < M; ++m)
+        ++lm_ptr[(size_t)obs_lm[m] + 1], ++kf_ptr[(size_t)obs_kf[m] + 1];
+    for(int l = 0; l < L; ++l)
+        lm_ptr[(size_t)l + 1] += lm_ptr[(size_t)l];
+    for(int k = 0; k < K; ++k)
+        kf_ptr[(size_t)k + 1] += kf_ptr[(size_t)k];
+    {
+        std::vector<int32_t> at(lm_ptr.begin(), lm_ptr.end() - 1);
+        for(int m = 0; m < M; ++m)
+            lm_obs[(size_t)at[(size_t)obs_lm[m]]++] = m;
+        at.assign(kf_ptr.begin(), kf_ptr.end() - 1);
+        for(int i = 0; i < M; ++i) // in landmark order: every keyframe's row comes out sorted by landmark
+        {
+            const int m = lm_obs[(size_t)i];
+            const int pos = at[(size_t)obs_kf[m]]++;
+            kf_obs[(size_t)pos] = m, kf_lm[(size_t)pos] = obs_lm[m];
+        }
+    }
+    std::vector<int32_t> ci((size_t)K, -1), pairs;
+    std::vector<uint8_t> lm_active((size_t)L, 0);
+    int n_free = 0;
+    for(int k = 0; k < K; ++k)
+        if(!(fixed && fixed[k]) && kf_ptr[(size_t)k + 1] > kf_ptr[(size_t)k])
+            ci[(size_t)k] = n_free++;
+    for(int k1 = 0; k1 < K; ++k1)
+        for(int k2 = k1; k2 < K; ++k2)
+            if(ci[(size_t)k1] >= 0 && ci[(size_t)k2] >= 0)
+                pairs.push_back(k1), pairs.push_back(k2);
+    for(int l = 0; l < L; ++l)
+        lm_active[(size_t)l] = lm_ptr[(size_t)l + 1] > lm_ptr[(size_t)l];
+
+    BaArgs a{};
+    a.K = K, a.L = L, a.M = M, a.n = 6 * n_free;
+    a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (M + 255) / 256;
+    // one block: what is uploaded first, then the working arrays
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_ctrl = carve(sizeof(BaCtrl)), o_pose = carve((size_t)K * 56), o_lm = carve((size_t)L * 24), o_cam = carve((size_t)M * 24);
+    const size_t o_okf = carve((size_t)M * 4), o_olm = carve((size_t)M * 4), o_lptr = carve(((size_t)L + 1) * 4), o_lobs = carve((size_t)M * 4);
+    const size_t o_kptr = carve(((size_t)K + 1) * 4), o_kobs = carve((size_t)M * 4), o_klm = carve((size_t)M * 4), o_ci = carve((size_t)K * 4);
+    const size_t o_pairs = carve(pairs.size() * 4), o_act = carve((size_t)L);
+    const size_t up_bytes = off;
+    const size_t o_pose0 = carve((size_t)K * 56), o_lm0 = carve((size_t)L * 24), o_cpose = carve((size_t)K * 56), o_clm = carve((size_t)L * 24);
+    const size_t o_V = carve((size_t)L * 48), o_gl = carve((size_t)L * 24), o_Vinv = carve((size_t)L * 48), o_sl = carve((size_t)L * 24);
+    const size_t o_U = carve((size_t)K * 168), o_gc = carve((size_t)K * 48), o_sc = carve((size_t)K * 48), o_W = carve((size_t)M * 144);
+    const size_t o_S = carve((size_t)a.n * a.n * 8), o_rhs = carve((size_t)a.n * 8), o_yc = carve((size_t)a.n * 8), o_yl = carve((size_t)L * 24);
+    const size_t o_part = carve((size_t)a.n_blocks * 16), o_out = carve((size_t)M);
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, grow(c->d_ba, off, c->stream));
+    if(!c->h_ba)
+        MSLAM_CHK(c, c->h_ba.alloc(4));
+    std::vector<uint8_t> stage(up_bytes, 0);
+    BaCtrl ctrl{};
+    ctrl.need_jac = 1, ctrl.first = 1, ctrl.successful = 1, ctrl.max_iterations = max_iterations;
+    ctrl.radius = kBaInitialRadius, ctrl.decrease_factor = 2.0;
+    std::memcpy(&stage[o_ctrl], &ctrl, sizeof(ctrl));
+    auto put = [&](size_t at, const void* src, size_t bytes) {
+        if(bytes)
+            std::memcpy(&stage[at], src, bytes);
+    };
+    put(o_pose, poses, (size_t)K * 56), put(o_lm, landmarks, (size_t)L * 24), put(o_cam, obs_cam, (size_t)M * 24);
+    put(o_okf, obs_kf, (size_t)M * 4), put(o_olm, obs_lm, (size_t)M * 4), put(o_lptr, lm_ptr.data(), ((size_t)L + 1) * 4);
+    put(o_lobs, lm_obs.data(), (size_t)M * 4), put(o_kptr, kf_ptr.data(), ((size_t)K + 1) * 4), put(o_kobs, kf_obs.data(), (size_t)M * 4);
+    put(o_klm, kf_lm.data(), (size_t)M * 4), put(o_ci, ci.data(), (size_t)K * 4), put(o_pairs, pairs.data(), pairs.size() * 4);
+    put(o_act, lm_active.data(), (size_t)L);
+    uint8_t* d = c->d_ba;
+    hipStream_t s = c->stream;
+    MSLAM_CHK(c, hipMemcpyAsync(d, stage.data(), up_bytes, hipMemcpyHostToDevice, s));
+    // the inputs are kept: a FAILURE judges the outliers there
+    MSLAM_CHK(c, hipMemcpyAsync(d + o_pose0, d + o_pose, (size_t)K * 56, hipMemcpyDeviceToDevice, s));
+    MSLAM_CHK(c, hipMemcpyAsync(d + o_lm0, d + o_lm, (size_t)L * 24, hipMemcpyDeviceToDevice, s));
+    auto dbl = [&](size_t at) { return reinterpret_cast<double*>(d + at); };
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t*>(d + at); };
+    a.obs_kf = i32(o_okf), a.obs_lm = i32(o_olm), a.obs_cam = dbl(o_cam);
+    a.lm_ptr = i32(o_lptr), a.lm_obs = i32(o_lobs), a.kf_ptr = i32(o_kptr), a.kf_obs = i32(o_kobs), a.kf_lm = i32(o_klm);
+    a.ci = i32(o_ci), a.pairs = i32(o_pairs), a.lm_active = d + o_act;
+    a.pose = dbl(o_pose), a.lm = dbl(o_lm), a.cand_pose = dbl(o_cpose), a.cand_lm = dbl(o_clm);
+    a.V = dbl(o_V), a.gl = dbl(o_gl), a.Vinv = dbl(o_Vinv), a.sl = dbl(o_sl);
+    a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.W = dbl(o_W);
+    a.S = dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
+    a.ctrl = reinterpret_cast<BaCtrl*>(d + o_ctrl);
+    a.h_done = c->h_ba.dev();
+    *c->h_ba.get() = 0;
+
+    const dim3 g_lm((unsigned)((L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((K + L + 255) / 256));
+    {
+        StageScope ts(c, "ba_start_cost");
+        hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
+    }
+    // iteration max_iterations + 1 only reaches k_ba_check, which ends the solve with NO_CONVERGENCE
+    for(int it = 0; it <= max_iterations;)
+    {
+        StageScope ts(c, "ba_iterations");
+        for(int b = 0; b < kBaBatch && it <= max_iterations; ++b, ++it)
+        {
+            hipLaunchKernelGGL(k_ba_landmarks, g_lm, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
+            if(a.n_pairs > 0)
+            {
+                hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
+            }
+            hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
+            hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+        }
+        MSLAM_CHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
+            break;
+    }
+    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(!ctrl.done)
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bundle_adjust: the kernels left no termination");
+    const bool usable = ctrl.termination != kBaFailure;
+    std::vector<uint8_t> mask((size_t)M);
+    hipLaunchKernelGGL(k_ba_outliers, g_obs, dim3(256), 0, s, a, dbl(usable ? o_pose : o_pose0), dbl(usable ? o_lm : o_lm0),
+                       outlier_threshold * outlier_threshold, d + o_out);
+    MSLAM_CHK(c, hipGetLastError());
+    MSLAM_CHK(c, hipMemcpyAsync(mask.data(), d + o_out, (size_t)M, hipMemcpyDeviceToHost, s));
+    std::vector<double> xp((size_t)K * 7), xl((size_t)L * 3);
+    if(usable)
+    {
+        MSLAM_CHK(c, hipMemcpyAsync(xp.data(), a.pose, (size_t)K * 56, hipMemcpyDeviceToHost, s));
+        MSLAM_CHK(c, hipMemcpyAsync(xl.data(), a.lm, (size_t)L * 24, hipMemcpyDeviceToHost, s));
+    }
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
+    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
+    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
+    for(int m = 0; m < M; ++m)
+        sum.n_outliers += mask[(size_t)m] ? 1 : 0;
+    if(outlier)
+        std::memcpy(outlier, mask.data(), (size_t)M);
+    if(summary)
+        *summary = sum;
+    if(!usable)
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "bundle_adjust: the minimiser ended in FAILURE (non-finite cost or gradient, or 5 "
+                                             "invalid steps in a row)");
+    std::memcpy(poses, xp.data(), (size_t)K * 56);
+    std::memcpy(landmarks, xl.data(), (size_t)L * 24);
+    return MSLAM_HIP_OK;
+}

@@ -1,6 +1,7 @@
 // k_localmap.hip — the local map on the keyframe store: the union of up to 64 entries as an ordinary entry
 // (mslam_hip_kf_union[_dev]) and covisibility counts (mslam_hip_kf_covisible), both on the landmark ids the store keeps
-// next to every landmark.
+// next to every landmark; and mslam_hip_kf_update_world, which writes a list of refined world points into every entry that
+// holds their ids (the way back from bundle adjustment, k_ba.hip).
 //
 // What getLandmarksWithKeypoints builds for track() (reference rgbd_feature_frontend.cpp:256-277): the most recent
 // observation of every landmark seen from a set of keyframes (RecentObservationsVisitor, :57-80: the observation whose
@@ -23,6 +24,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <vector>
 
 namespace mslam
 {
@@ -240,6 +242,48 @@ __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict_
         h_counts[k] = (int32_t)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
 }
 
+// mslam_hip_kf_update_world: the table of a caller's list, value = ~(position in the list), lowered with atomicMin: of an id
+// listed twice the later position wins
+__global__ __launch_bounds__(256) void k_lm_insert_list(const int64_t* __restrict__ ids, int n, LmBucket* __restrict__ table,
+                                                        unsigned long long mask)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if(i >= n)
+        return;
+    const long long b = lm_claim(table, mask, (unsigned long long)ids[i]);
+    if(b >= 0)
+        atomicMin(&table[b].val, ~(unsigned long long)i);
+}
+
+// One thread per (live slot = blockIdx.y, landmark position): a landmark whose id the table holds takes the listed world
+// point.  *written counts them (an integer count: its value does not depend on the order of the additions).
+__global__ __launch_bounds__(256) void k_lm_update_world(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n,
+                                                         const int32_t* __restrict__ slots, int K, const LmBucket* __restrict__ table,
+                                                         unsigned long long mask, const double* __restrict__ xyz, int n_list,
+                                                         double* __restrict__ store_world, uint32_t* __restrict__ written)
+{
+    const int slot = slots[blockIdx.y], i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(max(store_n[slot], 0), K);
+    bool hit = false;
+    if(i < n)
+    {
+        const size_t at = (size_t)slot * K + i;
+        const long long b = lm_find(table, mask, (unsigned long long)store_lid[at]);
+        if(b >= 0)
+        {
+            const unsigned long long src = ~table[b].val;
+            if(src < (unsigned long long)n_list)
+            {
+                hit = true;
+                store_world[at * 3] = xyz[src * 3], store_world[at * 3 + 1] = xyz[src * 3 + 1], store_world[at * 3 + 2] = xyz[src * 3 + 2];
+            }
+        }
+    }
+    const unsigned long long bal = __ballot(hit);
+    if((threadIdx.x & 63) == 0 && bal)
+        atomicAdd(written, (uint32_t)__popcll(bal));
+}
+
 } // namespace mslam
 
 using namespace mslam;
@@ -429,6 +473,66 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
         if(h_counts[k] < 0 || h_counts[k] > K)
             return fail(c, MSLAM_HIP_E_RUNTIME, "kf_covisible: the kernel left no result");
     std::memcpy(counts, h_counts, (size_t)n_ids * 4);
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_kf_update_world(mslam_hip_ctx* c, const int64_t* landmark_ids, const double* world_xyz, int n, int* n_written)
+{
+    if(n_written)
+        *n_written = 0;
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(n < 0 || n > (1 << 24) || (n > 0 && (!landmark_ids || !world_xyz)))
+        return fail(c, MSLAM_HIP_E_INVALID, "kf_update_world: bad argument");
+    RelocState* r = c->reloc;
+    if(n == 0 || r->slot_of.empty())
+        return MSLAM_HIP_OK;
+    const int K = c->p.max_keypoints;
+    std::vector<int32_t> slots;
+    int n_max = 0;
+    for(const auto& e : r->slot_of)
+    {
+        slots.push_back(e.second);
+        n_max = std::max(n_max, r->n_upper[(size_t)e.second]);
+    }
+    std::sort(slots.begin(), slots.end());
+    // one upload: [ids n x i64 | points n x 3 f64 | live slots | the count, zero]
+    const size_t o_xyz = (size_t)n * 8, o_slots = o_xyz + (size_t)n * 24, o_cnt = o_slots + slots.size() * 4, up = o_cnt + 4;
+    const size_t buckets = lm_bucket_count((size_t)n);
+    rc = reloc_scratch(c, up, 0, 0);
+    if(rc)
+        return rc;
+    rc = lm_scratch(c, buckets, 1);
+    if(rc)
+        return rc;
+    uint8_t* h = r->h_up;
+    std::memcpy(h, landmark_ids, (size_t)n * 8);
+    std::memcpy(h + o_xyz, world_xyz, (size_t)n * 24);
+    std::memcpy(h + o_slots, slots.data(), slots.size() * 4);
+    std::memset(h + o_cnt, 0, 4);
+    hipStream_t s = c->stream;
+    uint8_t* d = r->d_up;
+    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
+    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
+    MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+    {
+        StageScope ts(c, "update_world_insert");
+        hipLaunchKernelGGL(k_lm_insert_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const int64_t*>(d), n, table,
+                           (unsigned long long)(buckets - 1));
+    }
+    {
+        StageScope ts(c, "update_world_write");
+        hipLaunchKernelGGL(k_lm_update_world, dim3((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)slots.size()), dim3(256), 0, s, r->d_lid,
+                           r->d_n, reinterpret_cast<const int32_t*>(d + o_slots), K, table, (unsigned long long)(buckets - 1),
+                           reinterpret_cast<const double*>(d + o_xyz), n, r->d_world, reinterpret_cast<uint32_t*>(d + o_cnt));
+    }
+    MSLAM_CHK(c, hipGetLastError());
+    uint32_t written = 0;
+    MSLAM_CHK(c, hipMemcpyAsync(&written, d + o_cnt, 4, hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(n_written)
+        *n_written = (int)written;
     return MSLAM_HIP_OK;
 }
 

@@ -29,6 +29,9 @@
 //        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> [--local-map <depth>] --guided <radius>
 //                                    either loop with IKeyframeTracker::setGuidedMatch(radius): every tracking call matches each
 //                                    landmark within <radius> px of its projection under the previous pose
+//        mslam_harness <plugin.so> --ba <scene>
+//                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
+//                                    keyframe's and landmark's state and the outlier observations
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -121,6 +124,82 @@ int main(int argc, char** argv)
                         result->pose.position.x(), result->pose.position.y(), result->pose.position.z(),
                         result->pose.orientation.w(), result->pose.orientation.x(), result->pose.orientation.y(),
                         result->pose.orientation.z(), inl);
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--ba") == 0)
+        {
+            // scene file: "MSBA", i32 version (1), K, L, M, max_iterations; K x i32 keyframe id; K x 7 f64 state (qx qy qz qw
+            // px py pz); L x 3 f64; M x i32 keyframe index; M x i32 landmark index; M x 3 f64 camera-frame point
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[5] = {0, 0, 0, 0, 0};
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            if(!in || std::memcmp(magic, "MSBA", 4) != 0 || head[0] != 1 || head[1] < 0 || head[2] < 0 || head[3] < 0)
+            {
+                std::fprintf(stderr, "%s is not a bundle-adjustment scene\n", argv[3]);
+                return 5;
+            }
+            const std::size_t K = head[1], L = head[2], M = head[3];
+            std::vector<std::int32_t> ids(K), okf(M), olm(M);
+            std::vector<double> poses(7 * K), points(3 * L), cam(3 * M);
+            in.read(reinterpret_cast<char*>(ids.data()), K * 4);
+            in.read(reinterpret_cast<char*>(poses.data()), K * 56);
+            in.read(reinterpret_cast<char*>(points.data()), L * 24);
+            in.read(reinterpret_cast<char*>(okf.data()), M * 4);
+            in.read(reinterpret_cast<char*>(olm.data()), M * 4);
+            in.read(reinterpret_cast<char*>(cam.data()), M * 24);
+            if(!in)
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                return 5;
+            }
+            std::vector<std::shared_ptr<mslam::Keyframe<mslam::slam3d::SensorState>>> keyframes;
+            std::vector<std::shared_ptr<mslam::Landmark<mslam::Vector3>>> landmarks;
+            for(std::size_t k = 0; k < K; ++k)
+            {
+                auto kf = std::make_shared<mslam::Keyframe<mslam::slam3d::SensorState>>();
+                const double* v = &poses[7 * k];
+                kf->id = static_cast<mslam::Id>(ids[k]);
+                kf->state.orientation = mslam::Quaternion(v[3], v[0], v[1], v[2]);
+                kf->state.position = mslam::Vector3(v[4], v[5], v[6]);
+                keyframes.push_back(kf);
+            }
+            for(std::size_t l = 0; l < L; ++l)
+            {
+                auto lm = std::make_shared<mslam::Landmark<mslam::Vector3>>();
+                lm->id = l;
+                lm->state = mslam::Vector3(points[3 * l], points[3 * l + 1], points[3 * l + 2]);
+                landmarks.push_back(lm);
+            }
+            std::vector<mslam::BackendObservation> observations;
+            for(std::size_t m = 0; m < M; ++m)
+            {
+                if(okf[m] < 0 || static_cast<std::size_t>(okf[m]) >= K || olm[m] < 0 || static_cast<std::size_t>(olm[m]) >= L)
+                {
+                    std::fprintf(stderr, "observation %zu of %s is out of range\n", m, argv[3]);
+                    return 5;
+                }
+                observations.push_back({keyframes[okf[m]], landmarks[olm[m]], mslam::Vector3(cam[3 * m], cam[3 * m + 1], cam[3 * m + 2])});
+            }
+            auto makeBackend = mslam::loadFactoryMethod<mslam::IBackend>(argv[1], "hipBundleAdjustBackendFactory");
+            if(!makeBackend)
+                return 3;
+            std::unique_ptr<mslam::IBackend> backend = makeBackend();
+            const mslam::BackendOutput out = backend->bundleAdjustment(observations, head[4]);
+            std::printf("ba termination %d iterations %d initial %.17g final %.17g keyframes %zu landmarks %zu outliers %zu\n", out.termination,
+                        out.iterations, out.initialCost, out.finalCost, out.updatedKeyframes.size(), out.updatedLandmarks.size(),
+                        out.outlierObservations.size());
+            for(std::size_t k = 0; k < K; ++k)
+            {
+                const auto& st = keyframes[k]->state;
+                std::printf("keyframe %zu %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", k, st.orientation.x(), st.orientation.y(),
+                            st.orientation.z(), st.orientation.w(), st.position.x(), st.position.y(), st.position.z());
+            }
+            for(std::size_t l = 0; l < L; ++l)
+                std::printf("landmark %zu %.17g %.17g %.17g\n", l, landmarks[l]->state.x(), landmarks[l]->state.y(), landmarks[l]->state.z());
+            for(const auto& o : out.outlierObservations)
+                std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
             return 0;
         }
         if(argc == 5 && std::strcmp(argv[2], "--reloc") == 0)

@@ -10,6 +10,7 @@
 //                                                           (orb_relocalizer.cpp:26-50, rgbd_feature_frontend.cpp:153,176)
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
+//   HipBundleAdjustBackend : IBackend                       CeresBackend's bundle adjustment (hipBundleAdjustBackendFactory)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -791,6 +792,80 @@ class HipMinMseTracker : public ISlam3dPnp
     std::vector<double> obj, img;
 };
 
+// drop-in for CeresBackend's solve (ceres_backend.cpp:140-240): the observations become mslam_hip_bundle_adjust's arrays —
+// keyframes and landmarks numbered in the order they first appear, the state as (qx qy qz qw px py pz), keyframe id 1
+// constant — and the result is written back into keyframe->state and landmark->state, as Ceres writes through the pointers
+// the reference hands it.  More than 64 keyframes is an error (the reduced system is dense); FAILURE updates nothing.
+class HipBundleAdjustBackend : public IBackend
+{
+  public:
+    BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
+    {
+        std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>> keyframes;
+        std::vector<std::shared_ptr<Landmark<Vector3>>> landmarks;
+        std::map<const void*, int> kfIndex, lmIndex;
+        std::vector<std::int32_t> obsKf, obsLm;
+        std::vector<double> obsCam;
+        for(const auto& o : observations)
+        {
+            auto k = kfIndex.emplace(o.keyframe.get(), static_cast<int>(keyframes.size()));
+            if(k.second)
+                keyframes.push_back(o.keyframe);
+            auto l = lmIndex.emplace(o.landmark.get(), static_cast<int>(landmarks.size()));
+            if(l.second)
+                landmarks.push_back(o.landmark);
+            obsKf.push_back(k.first->second);
+            obsLm.push_back(l.first->second);
+            obsCam.insert(obsCam.end(), {o.cameraPoint.x(), o.cameraPoint.y(), o.cameraPoint.z()});
+        }
+        std::vector<double> poses(7 * keyframes.size()), points(3 * landmarks.size());
+        std::vector<std::uint8_t> fixed(keyframes.size()), outlier(observations.size());
+        for(std::size_t k = 0; k < keyframes.size(); ++k)
+        {
+            const auto& st = keyframes[k]->state;
+            const double v[7] = {st.orientation.x(), st.orientation.y(), st.orientation.z(), st.orientation.w(),
+                                 st.position.x(),    st.position.y(),    st.position.z()};
+            std::copy(v, v + 7, poses.begin() + 7 * k);
+            fixed[k] = keyframes[k]->id == 1 ? 1 : 0;
+        }
+        for(std::size_t l = 0; l < landmarks.size(); ++l)
+        {
+            const Vector3& x = landmarks[l]->state;
+            points[3 * l] = x.x(), points[3 * l + 1] = x.y(), points[3 * l + 2] = x.z();
+        }
+        ctx.ensure(0, 0);
+        mslam_hip_ba_summary summary{};
+        const int rc = mslam_hip_bundle_adjust(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
+                                               static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
+                                               static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
+        if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
+            raise(ctx.h, "mslam_hip_bundle_adjust", rc);
+        BackendOutput out;
+        out.termination = summary.termination, out.iterations = summary.iterations;
+        out.initialCost = summary.initial_cost, out.finalCost = summary.final_cost;
+        if(rc == MSLAM_HIP_OK)
+        {
+            for(std::size_t k = 0; k < keyframes.size(); ++k)
+            {
+                const double* v = &poses[7 * k];
+                keyframes[k]->state.orientation = Quaternion(v[3], v[0], v[1], v[2]);
+                keyframes[k]->state.position = Vector3(v[4], v[5], v[6]);
+            }
+            for(std::size_t l = 0; l < landmarks.size(); ++l)
+                landmarks[l]->state = Vector3(points[3 * l], points[3 * l + 1], points[3 * l + 2]);
+        }
+        for(std::size_t m = 0; m < observations.size(); ++m)
+            if(outlier[m])
+                out.outlierObservations.push_back(observations[m]);
+        out.updatedKeyframes = std::move(keyframes);
+        out.updatedLandmarks = std::move(landmarks);
+        return out;
+    }
+
+  private:
+    Ctx ctx;
+};
+
 // ---- factories + aliases (what loadFactoryMethod<T>(lib, name) imports) -------------------------------
 std::unique_ptr<IOrbFeatureDetector> createHipOrbDetector() { return std::make_unique<HipOrbDetector>(); }
 // drop-in for OrbOpenCvDetector (orb_feature.cpp:25,33-65; wired by src/app/slam/rgbd_slam.cpp:74-76).  The reference leaves
@@ -804,6 +879,7 @@ std::unique_ptr<IOrbRelocalizer> createHipOrbRelocalizer() { return std::make_un
 std::unique_ptr<IOrbLoopDetector> createHipLoopDetector() { return std::make_unique<HipLoopDetector>(); }
 std::unique_ptr<ISlam3dPnp> createHipRansacPnp() { return std::make_unique<HipRansacPnp>(); }
 std::unique_ptr<ISlam3dPnp> createHipMinMseTracker() { return std::make_unique<HipMinMseTracker>(); }
+std::unique_ptr<IBackend> createHipBundleAdjustBackend() { return std::make_unique<HipBundleAdjustBackend>(); }
 
 } // namespace mslam
 
@@ -814,3 +890,4 @@ MSLAM_DLL_ALIAS(mslam::createHipOrbRelocalizer, hipOrbRelocalizerFactory)
 MSLAM_DLL_ALIAS(mslam::createHipLoopDetector, loopDetection) // key used by test/plugin_config.json
 MSLAM_DLL_ALIAS(mslam::createHipRansacPnp, hipRansacPnpFactory)
 MSLAM_DLL_ALIAS(mslam::createHipMinMseTracker, hipMinMseTrackerFactory)
+MSLAM_DLL_ALIAS(mslam::createHipBundleAdjustBackend, hipBundleAdjustBackendFactory)

@@ -196,6 +196,36 @@ using IOrbRelocalizer = IRelocalizer<slam3d::SensorState, std::uint8_t, 32>;
 using IOrbLoopDetector = ILoopDetector<slam3d::SensorState>;
 using ISlam3dPnp = IPnpAlgorithm<slam3d::SensorState, Vector3>;
 
+// ---- the backend (backend/backend_interface.hpp:13-21, backend/backend_output.hpp:13-22, observation.hpp) ---------------
+// The reference's BackendInterface::process takes the FrontendOutput and walks its map for the observations of the new
+// keyframe's neighbourhood (ceres_backend.cpp:162-171).  The map is host bookkeeping and is not mirrored here, so the
+// caller hands those observations over (DEVIATES); what happens to them is the reference's: keyframe->state and
+// landmark->state are refined in place for everyone who holds the pointers, keyframe id 1 stays constant (:155-159), and
+// the observations whose residual exceeds 0.15 m come back as outliers (:212-230).  `cameraPoint` is the camera-frame point
+// ReprojectionError's constructor forms from the keypoint and its depth (:24-28).
+struct BackendObservation
+{
+    std::shared_ptr<Keyframe<slam3d::SensorState>> keyframe;
+    std::shared_ptr<Landmark<Vector3>> landmark;
+    Vector3 cameraPoint;
+};
+struct BackendOutput
+{
+    std::vector<std::shared_ptr<Landmark<Vector3>>> updatedLandmarks;            // (unordered_set in the reference)
+    std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>> updatedKeyframes;
+    std::vector<BackendObservation> outlierObservations;
+    // extra: what the reference only logs (summary.FullReport(), :199)
+    int termination = 0, iterations = 0; // ceres::TerminationType; 2 = FAILURE: nothing was updated
+    double initialCost = 0, finalCost = 0;
+};
+class IBackend
+{
+  public:
+    virtual BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations = 100) = 0;
+    virtual ~IBackend() = default;
+};
+
+
 // ---- extension (not in the reference): candidates verified by match + RANSAC PnP against stored landmarks -----------------
 // What RgbdFeatureFrontend::relocalize's commented-out body does with IRelocalizer::relocalize's candidates
 // (rgbd_feature_frontend.cpp:495-534).  IRelocalizer / ILoopDetector themselves are untouched: an adapter that offers the
