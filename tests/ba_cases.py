@@ -35,6 +35,45 @@ def _k64():
     return _append(sc, kf, lm, _exact(sc, kf, lm) + 0.002 * rng.normal(size=(512, 3)))
 
 
+GROSS = [[0.4, 0, 0], [0, -0.5, 0.1], [0.2, 0.2, 0.3]]      # the three offsets of gross_outliers
+
+
+def _blocks(M):
+    """M observations of a 4-keyframe, 48-landmark scene in which every landmark is seen from every keyframe: the 192
+    (keyframe, landmark) pairs tiled, every repeat with noise of its own.  k_ba_eval's blocks are 256 observations: M = 16384
+    is 64 of them, one trip of the 64-lane folds of k_ba_check and k_ba_control, M = 16385 starts the second trip.  Rows of
+    M / 4 per keyframe, about M / 192 observations of every landmark in every keyframe.  Gross offsets on the first
+    observation, the last of block 64 and the last of all."""
+    sc = ba_ref.make_scene(4, 48, 7, noise=0.005, start_angle=0.1)
+    n = len(sc["obs_kf"])
+    reps = -(-M // n) - 1
+    kf, lm = np.tile(sc["obs_kf"], reps), np.tile(sc["obs_lm"], reps)
+    _append(sc, kf, lm, _exact(sc, kf, lm) + 0.005 * np.random.default_rng(8).normal(size=(len(kf), 3)))
+    for k in ("obs_kf", "obs_lm", "obs_cam"):
+        sc[k] = sc[k][:M]
+    for m, off in zip((0, 16383, M - 1), GROSS):
+        sc["obs_cam"][m] += off
+    return sc
+
+
+def _fixed_middle(two):
+    """6 keyframes, none constant at first: keyframe 1 loses its observations and keyframe 3 is constant at its truth, so the
+    free keyframes 0, 2, 4, 5 are blocks 0, 1, 2, 3 of the reduced system (ci[k] != k - 1); two: keyframe 0 constant too"""
+    sc = ba_ref.make_scene(6, 80, 21, noise=0.005, views=3, start_angle=0.1, fix_first=False)
+    keep = sc["obs_kf"] != 1
+    for k in ("obs_kf", "obs_lm", "obs_cam"):
+        sc[k] = sc[k][keep]
+    for k in (0, 3) if two else (3,):
+        sc["fixed"][k] = 1
+        sc["poses"][k] = sc["truth_poses"][k]
+    return sc
+
+
+def _capped(sc, cap):
+    sc["max_iterations"] = cap
+    return sc
+
+
 def scene(name):
     """-> the scene dict of ba_ref.make_scene (plus max_iterations where the case caps it)"""
     kind, _, rest = name.partition(":")
@@ -78,7 +117,7 @@ def scene(name):
         return sc
     if kind == "gross_outliers":
         sc = ba_ref.make_scene(3, 65, 11, noise=0.005, start_angle=0.1)
-        sc["obs_cam"][[4, 77, 150]] += [[0.4, 0, 0], [0, -0.5, 0.1], [0.2, 0.2, 0.3]]
+        sc["obs_cam"][[4, 77, 150]] += GROSS
         return sc
     if kind == "empty":
         sc = ba_ref.make_scene(2, 5, 12)
@@ -87,6 +126,22 @@ def scene(name):
         return sc
     if kind == "k64":
         return _k64()
+    if kind == "blocks":
+        return _blocks(int(rest))
+    if kind == "k64_dense":        # every landmark in 16 of 64 keyframes: every off-diagonal block of S sums over shared landmarks
+        return ba_ref.make_scene(64, 120, 64, noise=0.005, views=16, start_angle=0.05)
+    if kind in ("fixed_middle", "fixed_two"):
+        return _fixed_middle(kind == "fixed_two")
+    if kind in ("cap0", "cap1"):
+        return _capped(scene("rejected"), int(kind[3:]))
+    if kind == "cap4_converges":   # converges in its 4th iteration, the last kernel of the host's first batch
+        return _capped(scene("fixed:3,65,5"), 4)
+    if kind == "cap4_stops":       # would need a 5th
+        return _capped(scene("free:5,150,10"), 4)
+    if kind == "at_minimum":       # the start is the minimum: the gradient test ends the solve before the first iteration
+        sc = ba_ref.make_scene(3, 65, 5, noise=0.0)
+        sc["poses"], sc["landmarks"] = sc["truth_poses"].copy(), sc["truth_landmarks"].copy()
+        return sc
     raise KeyError(name)
 
 
@@ -97,7 +152,9 @@ FAMILIES = {
     "all_fixed": ["all_fixed"],
 }
 EDGES = (["k1_fixed", "twice_in_keyframe", "fixed_only_landmarks", "keyframe_one_observation", "gross_outliers", "empty", "cap3",
-          "k64"] + ["single_view:%d" % L for L in (63, 64, 65, 257)] + ["two_views:%d" % L for L in (63, 64, 65, 257)])
+          "k64"] + ["single_view:%d" % L for L in (63, 64, 65, 257)] + ["two_views:%d" % L for L in (63, 64, 65, 257)] +
+         ["blocks:16384", "blocks:16385", "k64_dense", "fixed_middle", "fixed_two", "cap0", "cap1", "cap4_converges", "cap4_stops",
+          "at_minimum"])
 ALL = [c for f in FAMILIES.values() for c in f] + EDGES
 
 

@@ -94,3 +94,38 @@ def test_named_cases_take_their_paths():
     assert pairs.count((1, 3)) == 3 and pairs.count((1, 17)) == 2
     sc = ba_cases.scene("keyframe_one_observation")
     assert np.sum(sc["obs_kf"] == 3) == 1
+    # the iteration cap next to the host's batch of four, and a start that is the minimum
+    t = {n: ba_cases.reference(n)[1] for n in ("cap0", "cap1", "cap4_converges", "cap4_stops", "at_minimum")}
+    for n, its in (("cap0", 0), ("cap1", 1), ("cap4_stops", 4)):
+        assert (t[n]["termination"], t[n]["iterations"], t[n]["reason"]) == (ba_ref.NO_CONVERGENCE, its, "max iterations"), n
+    assert t["cap0"]["final_cost"] == t["cap0"]["initial_cost"] and t["cap1"]["final_cost"] < t["cap1"]["initial_cost"]
+    assert (t["cap4_converges"]["termination"], t["cap4_converges"]["iterations"], t["cap4_converges"]["reason"]) == \
+           (ba_ref.CONVERGENCE, 4, "function tolerance")
+    assert ba_ref.solve_scene(ba_cases.scene("free:5,150,10"))["iterations"] == 5      # what cap4_stops is cut short of
+    assert (t["at_minimum"]["termination"], t["at_minimum"]["iterations"], t["at_minimum"]["reason"]) == \
+           (ba_ref.CONVERGENCE, 0, "gradient tolerance")
+    assert t["at_minimum"]["final_cost"] == 0.0
+    # gaps in the block numbering: keyframe 1 unobserved, keyframe 3 (and 0) constant
+    for n, free, const, fixed_only in (("fixed_middle", 4, 1, 0), ("fixed_two", 3, 2, 1)):
+        sc, qr = ba_cases.reference(n)[:2]
+        tr = qr["trace"]
+        assert (tr["free_poses"], tr["constant_poses"], tr["landmarks_fixed_only"]) == (free, const, fixed_only), n
+        assert not np.any(sc["obs_kf"] == 1) and sc["fixed"].tolist() == [n == "fixed_two", 0, 0, 1, 0, 0], n
+        assert np.bincount(sc["obs_lm"], minlength=80).min() >= 2, n
+        assert qr["termination"] == ba_ref.CONVERGENCE and qr["iterations"] == 4, n
+    # 64 and 65 blocks of 256 observations, long rows, long runs of one landmark in one keyframe
+    for n, blocks in (("blocks:16384", 64), ("blocks:16385", 65)):
+        sc, qr, _, _, mask, _ = ba_cases.reference(n)
+        M = len(sc["obs_kf"])
+        assert (M + 255) // 256 == blocks, n
+        assert np.bincount(sc["obs_kf"], minlength=4).min() >= 4000, n
+        assert np.bincount(sc["obs_kf"] * 48 + sc["obs_lm"], minlength=192).min() >= 85, n
+        assert mask[0] and mask[16383] and mask[M - 1] and np.flatnonzero(mask).max() >= 16383, n
+        assert int(mask.sum()) == blocks - 62, n
+        assert qr["termination"] == ba_ref.CONVERGENCE and qr["iterations"] == 4 and qr["trace"]["rejected"] == 0, n
+    # a dense reduced system: every pair of keyframes shares a landmark
+    sc, qr = ba_cases.reference("k64_dense")[:2]
+    assert qr["trace"]["free_poses"] == 63 and qr["termination"] == ba_ref.CONVERGENCE and qr["iterations"] == 4
+    seen = np.zeros((64, 120), np.int64)
+    seen[sc["obs_kf"], sc["obs_lm"]] = 1
+    assert (seen @ seen.T).min() >= 1
