@@ -550,6 +550,31 @@ int mslam_hip_bundle_adjust(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out *
                             const int32_t* obs_lm, const double* obs_cam /* M x 3 */, int M, int max_iterations /* 100 */,
                             double outlier_threshold /* 0.15 */, uint8_t* outlier /* M, may be NULL */,
                             mslam_hip_ba_summary* summary /* may be NULL */);
+/* ---- CeresBackend::globalBundleAdjustment (ceres_backend.cpp:173-183): the same solve over every keyframe of the map ----
+ * The reference's only loop correction (closeLoop is a TODO there).  Arguments, summary, residual, manifold, trust region,
+ * termination order, FAILURE behaviour, outlier mask, determinism and the MSLAM_HIP_E_INVALID rules are those of
+ * mslam_hip_bundle_adjust, with K in 0..MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES, and the reduced camera system is always built and
+ * solved by the blocked solver below, at any K (so small problems compare the two solvers).  Every row of
+ * mslam_hip_bundle_adjust's SAME / DEVIATES table holds here except these two:
+ *   linear solver            DEVIATES in rounding: Schur complement on the landmarks (3x3 blocks inverted in closed form) over
+ *                            the covisible pairs of keyframes only (pairs that share a landmark, from a sorted list built on
+ *                            the host), blocked dense Cholesky of the reduced camera system over many workgroups (panels of
+ *                            48 columns: the diagonal block in one workgroup, the panel's triangular solve by row tiles, the
+ *                            trailing update on the f64 matrix cores; the right-hand side is carried as one more row), blocked
+ *                            back-substitution; the reference asks for SPARSE_NORMAL_CHOLESKY on the whole system.  A
+ *                            non-positive pivot in any panel or a non-finite step is an invalid step.  UNTESTED: no test
+ *                            reaches a non-positive pivot (the damping keeps the reduced system positive definite for
+ *                            finite input and no scene found so far loses that to rounding), so the path from a panel's
+ *                            pivot flag through the invalid-step handling to a retry or FAILURE has never run, here or
+ *                            in mslam_hip_bundle_adjust;
+ *   sizes                    DEVIATES: at most 1024 keyframes per solve: the reduced system is kept dense, 6144^2 doubles
+ *                            = 302 MB of device memory at the bound; the reference has no bound. */
+#define MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES 1024
+int mslam_hip_bundle_adjust_global(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out */, const uint8_t* fixed /* K, or NULL */,
+                                   int K /* 0..1024 */, double* landmarks /* L x 3, in/out */, int L, const int32_t* obs_kf,
+                                   const int32_t* obs_lm, const double* obs_cam /* M x 3 */, int M, int max_iterations /* 100 */,
+                                   double outlier_threshold /* 0.15 */, uint8_t* outlier /* M, may be NULL */,
+                                   mslam_hip_ba_summary* summary /* may be NULL */);
 /* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
  * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
  * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of

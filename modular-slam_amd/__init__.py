@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_visible", "mslam_hip_track", "mslam_hip_track_window", "mslam_hip_track_window_dev",
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
-    "mslam_hip_bundle_adjust", "mslam_hip_kf_update_world",
+    "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world",
 ]
 
 
@@ -488,6 +488,16 @@ class Context:
         -> dict(poses, landmarks, outlier [M] bool, termination, iterations, rejected_steps, invalid_steps, n_outliers,
         initial_cost, final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): poses and landmarks
         come back unchanged."""
+        return self._bundle_adjust(self.L.mslam_hip_bundle_adjust, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed,
+                                   max_iterations, outlier_threshold)
+
+    def bundle_adjust_global(self, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed=None, max_iterations=100, outlier_threshold=0.15):
+        """CeresBackend::globalBundleAdjustment's solve: bundle_adjust's arguments and result with K <= 1024, always through
+        the blocked solver (covisible-pair Schur complement, blocked Cholesky over many workgroups), at any K."""
+        return self._bundle_adjust(self.L.mslam_hip_bundle_adjust_global, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed,
+                                   max_iterations, outlier_threshold)
+
+    def _bundle_adjust(self, entry, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed, max_iterations, outlier_threshold):
         x = np.array(poses, np.float64).reshape(-1, 7)
         lm = np.array(landmarks, np.float64).reshape(-1, 3)
         ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
@@ -500,8 +510,8 @@ class Context:
             raise MslamHipError(E_INVALID, "bundle_adjust: %d poses, %d fixed flags" % (len(x), len(fx)))
         mask = np.zeros(max(len(ok), 1), np.uint8)
         out = BaSummary()
-        rc = self.L.mslam_hip_bundle_adjust(self._h, _p(x), _p(fx), len(x), _p(lm), len(lm), _p(ok), _p(ol), _p(oc), len(ok),
-                                            int(max_iterations), C.c_double(outlier_threshold), _p(mask), C.byref(out))
+        rc = entry(self._h, _p(x), _p(fx), len(x), _p(lm), len(lm), _p(ok), _p(ol), _p(oc), len(ok), int(max_iterations),
+                   C.c_double(outlier_threshold), _p(mask), C.byref(out))
         if rc != E_NO_MODEL:
             self._chk(rc)
         res = {k: getattr(out, k) for k, _ in BaSummary._fields_ if k != "reserved"}
@@ -1073,12 +1083,15 @@ class HipBackend:
     pz), their observations (landmark id, camera-frame point: what ReprojectionError's constructor forms, :24-28) and the
     landmarks' world points, kept on the host; the solve runs on the device.  The first keyframe added is constant, as the
     reference's keyframe 1 is (:155-159).  Nothing is removed: the outlier observations are returned
-    (removeObservation's body is commented out in the reference)."""
+    (removeObservation's body is commented out in the reference).  global_solver = True: global_ba() goes through
+    Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes."""
 
     MAX_KEYFRAMES = 64
+    MAX_GLOBAL_KEYFRAMES = 1024
 
-    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15):
+    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False):
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
+        self.global_solver = bool(global_solver)
         self.poses = {}       # id -> [7]
         self.obs = {}         # id -> (landmark ids [n] i64, camera points [n, 3])
         self.landmarks = {}   # landmark id -> [3]
@@ -1130,9 +1143,10 @@ class HipBackend:
         cat = lambda a, dt, w: np.concatenate(a) if a else np.zeros((0,) + w, dt)
         return poses, fixed, lids, lm, cat(okf, np.int32, ()), cat(olm, np.int32, ()), cat(ocam, np.float64, (3,))
 
-    def _solve(self, kf_ids):
+    def _solve(self, kf_ids, blocked=False):
         poses, fixed, lids, lm, okf, olm, ocam = self.problem(kf_ids)
-        res = self.ctx.bundle_adjust(poses, lm, okf, olm, ocam, fixed, self.max_iterations, self.outlier_threshold)
+        solve = self.ctx.bundle_adjust_global if blocked else self.ctx.bundle_adjust
+        res = solve(poses, lm, okf, olm, ocam, fixed, self.max_iterations, self.outlier_threshold)
         if res["termination"] != 2:
             for k, id in enumerate(kf_ids):
                 self.poses[id] = res["poses"][k].copy()
@@ -1147,11 +1161,12 @@ class HipBackend:
         return self._solve(self.neighbours(ref_id, graph, 1))
 
     def global_ba(self):
-        """globalBundleAdjustment (:173-183) over every keyframe; more than 64 is MslamHipError(E_CAPACITY): the reduced
-        system is dense"""
-        if len(self.poses) > self.MAX_KEYFRAMES:
-            raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), self.MAX_KEYFRAMES))
-        return self._solve(sorted(self.poses))
+        """globalBundleAdjustment (:173-183) over every keyframe; more than 64 (1024 with global_solver) is
+        MslamHipError(E_CAPACITY), raised before the context is touched: the reduced system is dense"""
+        cap = self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
+        if len(self.poses) > cap:
+            raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
+        return self._solve(sorted(self.poses), self.global_solver)
 
 
 class HipKeyframeTracker:

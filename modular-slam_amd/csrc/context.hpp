@@ -154,6 +154,9 @@ struct mslam_hip_ctx
     // mapped termination word the host reads between batches of iterations
     mslam::DevBuf<uint8_t> d_ba;
     mslam::PinnedBuf<int32_t> h_ba;
+    // the padded dense reduced system of mslam_hip_bundle_adjust_global, an owner of its own: a global solve leaves d_ba,
+    // which the local solve sizes, as small as the local solve needs it
+    mslam::DevBuf<double> d_ba_S;
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;
@@ -190,11 +193,12 @@ inline int fail(mslam_hip_ctx* c, int code, const std::string& msg)
 // Records a [start, stop] HIP-event pair around a stage.  Mode 1 (profiling): everything runs on the context's
 // stream, so the events go there and the stages do not overlap.  Mode 2 (inplace_timing): the events are
 // recorded on the stream the stage is launched on, which does not change the schedule; entries accumulate until
-// mslam_hip_get_stage_times reads them.
+// mslam_hip_get_stage_times reads them.  Scopes may nest (a stage inside a stage): a scope keeps the index of its entry, not
+// a pointer, because an inner scope's push_back may move the vector while the outer one is open.
 struct StageScope
 {
     mslam_hip_ctx* c;
-    mslam::StageTimer* t = nullptr;
+    size_t slot = ~(size_t)0; // index into c->timers; ~0: not timed
     hipStream_t st;
     StageScope(mslam_hip_ctx* ctx, const char* name, hipStream_t launch_stream = nullptr) : c(ctx)
     {
@@ -210,14 +214,14 @@ struct StageScope
                 return;
             c->timers.push_back(nt);
         }
-        t = &c->timers[c->timers_used++];
-        t->name = name;
-        (void)hipEventRecord(t->start, st);
+        slot = c->timers_used++;
+        c->timers[slot].name = name;
+        (void)hipEventRecord(c->timers[slot].start, st);
     }
     ~StageScope()
     {
-        if(t)
-            (void)hipEventRecord(t->stop, st);
+        if(slot != ~(size_t)0)
+            (void)hipEventRecord(c->timers[slot].stop, st);
     }
 };
 

@@ -44,6 +44,8 @@ namespace mslam
 {
 
 constexpr int kBaMaxKeyframes = 64;
+constexpr int kBagMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES; // mslam_hip_bundle_adjust_global: 6144^2 doubles = 302 MB
+constexpr int kBagNB = 48; // panel width of the blocked factor: 8 keyframe blocks, 3 MFMA tiles
 constexpr int kBaSolveThreads = 6 * kBaMaxKeyframes; // one thread per row of the reduced system
 constexpr int kBaBatch = 4;                          // iterations enqueued between two looks at the termination word
 constexpr int kBaMaxInvalidSteps = 5;
@@ -64,6 +66,7 @@ struct BaArgs
 {
     int K, L, M, n;     // n = 6 x (free keyframes with observations): the reduced system's size
     int n_pairs, n_blocks; // pairs of free keyframes; blocks of k_ba_eval
+    int n_pad, ld;         // the blocked solver: n rounded up to kBagNB; leading dimension n_pad + 16 (row n_pad: the right-hand side)
     // the problem
     const int32_t *obs_kf, *obs_lm;
     const double* obs_cam;
@@ -365,7 +368,11 @@ __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
 
 // ---- the reduced camera system ------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(64) void k_ba_schur(BaArgs a)
+// kBlocked = false: S is n x n, both halves written, the right-hand side in a.rhs (k_ba_solve).  kBlocked = true: S has the
+// leading dimension a.ld, only the lower half is written (an off-diagonal block as its transpose), and the right-hand side
+// is row a.n_pad of S (the k_bag_* kernels).
+template <bool kBlocked>
+__device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
 {
     const BaCtrl* ct = a.ctrl;
     if(ct->done)
@@ -443,7 +450,7 @@ __global__ __launch_bounds__(64) void k_ba_schur(BaArgs a)
             if(lane == 36 + j)
                 mine = v;
         }
-    const size_t n = (size_t)a.n;
+    const size_t n = kBlocked ? (size_t)a.ld : (size_t)a.n;
     if(lane < 36)
     {
         const int r = lane / 6, c = lane % 6;
@@ -456,16 +463,23 @@ __global__ __launch_bounds__(64) void k_ba_schur(BaArgs a)
                 v = (u + fmin(fmax(u, kBaMinDiagonal), kBaMaxDiagonal) / ct->radius) - mine;
         }
         const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
-        a.S[row + col * n] = v;
+        if(!kBlocked || diag)
+            a.S[row + col * n] = v;
         if(!diag)
             a.S[col + row * n] = v;
     }
     else if(diag && lane < 42)
     {
         const int r = lane - 36;
-        a.rhs[(size_t)b1 * 6 + r] = s1[r] * a.gc[(size_t)k1 * 6 + r] - mine;
+        const double v = s1[r] * a.gc[(size_t)k1 * 6 + r] - mine;
+        if(kBlocked)
+            a.S[(size_t)a.n_pad + ((size_t)b1 * 6 + r) * n] = v;
+        else
+            a.rhs[(size_t)b1 * 6 + r] = v;
     }
 }
+
+__global__ __launch_bounds__(64) void k_ba_schur(BaArgs a) { ba_schur_pair<false>(a); }
 
 // Cholesky S = L L^T in place (lower triangle, column-major), then L y = rhs and L^T x = y.  Thread i owns row i.
 __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
@@ -528,6 +542,214 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
         a.yc[i] = b[i];
     if(i == 0 && bad)
         ct->solve_bad = 1;
+}
+
+// ---- the blocked solver of mslam_hip_bundle_adjust_global ---------------------------------------------------------------------
+// S is dense, column-major, n_pad = n rounded up to kBagNB columns, leading dimension ld = n_pad + 16: row n_pad carries the
+// right-hand side, so the factorisation of [S b; b^T .] leaves y = L^-1 b there (the forward solve costs one more 16-row
+// tile per panel and no launch).  Right-looking, three launches per panel j on one stream: k_bag_potrf (the diagonal block, one
+// workgroup, in LDS), k_bag_trsm (the rows below it), k_bag_update (every lower tile right of it, on the matrix cores); then
+// k_bag_backsolve per panel from the last to the first.  Only the lower triangle is read.  Every tile's sums have one order.
+
+typedef double bag_d4 __attribute__((ext_vector_type(4)));
+
+// zero below (and in) the diagonal kBagNB-block of every column, 1 on the pad's diagonal; a block per column
+__global__ __launch_bounds__(256) void k_bag_clear(BaArgs a)
+{
+    if(a.ctrl->done)
+        return;
+    const int c = blockIdx.x;
+    double* col = a.S + (size_t)c * a.ld;
+    for(int r = (c / kBagNB) * kBagNB + threadIdx.x; r < a.ld; r += 256)
+        col[r] = (r == c && c >= a.n) ? 1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(64) void k_bag_schur(BaArgs a) { ba_schur_pair<true>(a); }
+
+// the diagonal block of panel j into LDS (lower triangle, the rest 0)
+__device__ __forceinline__ void bag_load_diag(const BaArgs& a, int j, double (*A)[kBagNB + 1])
+{
+    const double* D = a.S + (size_t)j * kBagNB * ((size_t)a.ld + 1);
+    const int i = threadIdx.x;
+    if(i < kBagNB)
+        for(int c = 0; c < kBagNB; ++c)
+            A[i][c] = c <= i ? D[(size_t)i + (size_t)c * a.ld] : 0.0;
+    __syncthreads();
+}
+
+// Cholesky of the diagonal block of panel j; thread i owns row i, k_ba_solve's pivot rule
+__global__ __launch_bounds__(64) void k_bag_potrf(BaArgs a, int j)
+{
+    __shared__ double A[kBagNB][kBagNB + 1];
+    __shared__ double sdiag;
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int i = threadIdx.x;
+    bag_load_diag(a, j, A);
+    bool bad = false;
+    for(int jj = 0; jj < kBagNB; ++jj)
+    {
+        double v = 0.0;
+        if(i >= jj && i < kBagNB)
+        {
+            v = A[i][jj];
+            for(int k = 0; k < jj; ++k)
+                v -= A[i][k] * A[jj][k];
+        }
+        if(i == jj)
+        {
+            if(!(v > 0.0))
+                bad = true; // a non-positive pivot: the step is invalid; the factorisation goes on with bounded values
+            sdiag = sqrt(fmax(v, DBL_MIN));
+        }
+        __syncthreads();
+        if(i >= jj && i < kBagNB)
+            A[i][jj] = i == jj ? sdiag : v / sdiag;
+        __syncthreads();
+    }
+    double* D = a.S + (size_t)j * kBagNB * ((size_t)a.ld + 1);
+    if(i < kBagNB)
+        for(int c = 0; c <= i; ++c)
+            D[(size_t)i + (size_t)c * a.ld] = A[i][c];
+    if(bad)
+        ct->solve_bad = 1;
+}
+
+// X L_jj^T = A for the rows below the diagonal block of panel j (the right-hand side's row included): a thread per row
+__global__ __launch_bounds__(64) void k_bag_trsm(BaArgs a, int j)
+{
+    __shared__ double Lj[kBagNB][kBagNB + 1];
+    if(a.ctrl->done)
+        return;
+    bag_load_diag(a, j, Lj);
+    const int row = (j + 1) * kBagNB + blockIdx.x * 64 + threadIdx.x;
+    if(row >= a.ld)
+        return;
+    double* P = a.S + (size_t)row + (size_t)j * kBagNB * a.ld;
+    double x[kBagNB];
+#pragma unroll
+    for(int c = 0; c < kBagNB; ++c)
+        x[c] = P[(size_t)c * a.ld];
+#pragma unroll
+    for(int c = 0; c < kBagNB; ++c)
+    {
+        double v = x[c];
+#pragma unroll
+        for(int k = 0; k < c; ++k)
+            v -= x[k] * Lj[c][k];
+        x[c] = v / Lj[c][c];
+    }
+#pragma unroll
+    for(int c = 0; c < kBagNB; ++c)
+        P[(size_t)c * a.ld] = x[c];
+}
+
+// A_rc -= L_rj L_cj^T for the tile (row block r, column block c), j < c <= r; r = n_pad / kBagNB is the right-hand side's
+// 16 rows.  One wave per tile: 3 x 3 accumulators of v_mfma_f64_16x16x4_f64, 12 steps over the panel's 48 columns.  The wave
+// computes the transposed product (A operand from the column block, B from the row block): a result register then holds 16
+// consecutive rows of one column of S (D: column = lane & 15, row = (lane >> 4) + 4 reg).
+__global__ __launch_bounds__(64) void k_bag_update(BaArgs a, int j)
+{
+    if(a.ctrl->done)
+        return;
+    const int np = a.n_pad / kBagNB;
+    // the grid is the tiles themselves: with nt = np - j - 1 column blocks right of the panel, the lower triangle of nt x nt
+    // blocks row by row (x (x + 1) / 2 + y, y <= x), then the nt tiles of the right-hand side's row
+    const int nt = np - j - 1, tri = nt * (nt + 1) / 2, b = (int)blockIdx.x;
+    int x, y;
+    if(b < tri)
+    {
+        x = (int)((sqrt(8.0 * b + 1.0) - 1.0) / 2.0);
+        if(x * (x + 1) / 2 > b) // the root rounded up or down by one: at most one step either way
+            --x;
+        else if((x + 1) * (x + 2) / 2 <= b)
+            ++x;
+        y = b - x * (x + 1) / 2;
+    }
+    else
+        x = nt, y = b - tri;
+    if(x > nt || y < 0 || y >= nt || y > x)
+        return; // cannot happen for a grid of tri + t blocks: no tile outside S is ever written
+    const int rb = j + 1 + x, cb = j + 1 + y;
+    const int lane = threadIdx.x, lo = lane & 15, hi = lane >> 4;
+    const int mt = rb == np ? 1 : 3; // 16-row tiles of the row block
+    const size_t ld = (size_t)a.ld;
+    const double* Lr = a.S + (size_t)rb * kBagNB + lo + ((size_t)j * kBagNB + hi) * ld;
+    const double* Lc = a.S + (size_t)cb * kBagNB + lo + ((size_t)j * kBagNB + hi) * ld;
+    bag_d4 acc[3][3];
+#pragma unroll
+    for(int ti = 0; ti < 3; ++ti)
+#pragma unroll
+        for(int tj = 0; tj < 3; ++tj)
+            acc[ti][tj] = bag_d4{0.0, 0.0, 0.0, 0.0};
+    for(int ks = 0; ks < kBagNB / 4; ++ks)
+    {
+        double cv[3], rv[3];
+#pragma unroll
+        for(int t = 0; t < 3; ++t)
+        {
+            cv[t] = Lc[t * 16 + (size_t)ks * 4 * ld];
+            rv[t] = t < mt ? Lr[t * 16 + (size_t)ks * 4 * ld] : 0.0;
+        }
+#pragma unroll
+        for(int ti = 0; ti < 3; ++ti)
+#pragma unroll
+            for(int tj = 0; tj < 3; ++tj)
+                acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv[tj], rv[ti], acc[ti][tj], 0, 0, 0);
+    }
+#pragma unroll
+    for(int ti = 0; ti < 3; ++ti)
+    {
+        if(ti >= mt) // wave-uniform
+            break;
+#pragma unroll
+        for(int tj = 0; tj < 3; ++tj)
+#pragma unroll
+            for(int reg = 0; reg < 4; ++reg)
+            {
+                double* C = a.S + ((size_t)rb * kBagNB + ti * 16 + lo) + ((size_t)cb * kBagNB + tj * 16 + hi + 4 * reg) * ld;
+                *C -= acc[ti][tj][reg];
+            }
+    }
+}
+
+// Panel j of L^T x = y, from the last panel to the first.  Every workgroup solves the diagonal block for x_j (the same
+// arithmetic, so the same bits); workgroup j writes it to yc, workgroup b < j takes L_jb^T x_j off y_b.
+__global__ __launch_bounds__(64) void k_bag_backsolve(BaArgs a, int j)
+{
+    __shared__ double Lj[kBagNB][kBagNB + 1];
+    __shared__ double x[kBagNB];
+    if(a.ctrl->done)
+        return;
+    const int i = threadIdx.x, b = blockIdx.x;
+    const size_t ld = (size_t)a.ld, np_ = (size_t)a.n_pad;
+    bag_load_diag(a, j, Lj);
+    if(i < kBagNB)
+        x[i] = a.S[np_ + ((size_t)j * kBagNB + i) * ld];
+    __syncthreads();
+    for(int k = kBagNB - 1; k >= 0; --k)
+    {
+        if(i == k)
+            x[k] = x[k] / Lj[k][k];
+        __syncthreads();
+        if(i < k)
+            x[i] -= Lj[k][i] * x[k];
+        __syncthreads();
+    }
+    if(i >= kBagNB)
+        return;
+    if(b == j)
+    {
+        if(j * kBagNB + i < a.n)
+            a.yc[j * kBagNB + i] = x[i];
+        return;
+    }
+    const size_t col = (size_t)b * kBagNB + i;
+    double s = a.S[np_ + col * ld];
+    for(int r = 0; r < kBagNB; ++r)
+        s -= a.S[(size_t)j * kBagNB + r + col * ld] * x[r];
+    a.S[np_ + col * ld] = s;
 }
 
 __global__ __launch_bounds__(256) void k_ba_backsub(BaArgs a)
@@ -780,15 +1002,16 @@ __global__ __launch_bounds__(256) void k_ba_outliers(BaArgs a, const double* __r
 
 using namespace mslam;
 
-extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
-                                       const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M,
-                                       int max_iterations, double outlier_threshold, uint8_t* outlier,
-                                       mslam_hip_ba_summary* summary)
+// Both entry points.  blocked = false: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_solve, S inside d_ba);
+// blocked = true: mslam_hip_bundle_adjust_global (covisible pairs, the k_bag_* kernels, S in d_ba_S).
+static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
+                  const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M, int max_iterations,
+                  double outlier_threshold, uint8_t* outlier, mslam_hip_ba_summary* summary)
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    if(K < 0 || K > kBaMaxKeyframes)
-        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: K outside 0..64");
+    if(K < 0 || K > (blocked ? kBagMaxKeyframes : kBaMaxKeyframes))
+        return fail(c, MSLAM_HIP_E_INVALID, blocked ? "bundle_adjust_global: K outside 0..1024" : "bundle_adjust: K outside 0..64");
     if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !poses) ||
        (L > 0 && !landmarks) || (M > 0 && (!obs_kf || !obs_lm || !obs_cam)))
         return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: bad argument (counts, pointers, max_iterations >= 0, threshold >= 0)");
@@ -836,16 +1059,53 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
     for(int k = 0; k < K; ++k)
         if(!(fixed && fixed[k]) && kf_ptr[(size_t)k + 1] > kf_ptr[(size_t)k])
             ci[(size_t)k] = n_free++;
-    for(int k1 = 0; k1 < K; ++k1)
-        for(int k2 = k1; k2 < K; ++k2)
-            if(ci[(size_t)k1] >= 0 && ci[(size_t)k2] >= 0)
-                pairs.push_back(k1), pairs.push_back(k2);
+    if(!blocked)
+    {
+        for(int k1 = 0; k1 < K; ++k1)
+            for(int k2 = k1; k2 < K; ++k2)
+                if(ci[(size_t)k1] >= 0 && ci[(size_t)k2] >= 0)
+                    pairs.push_back(k1), pairs.push_back(k2);
+    }
+    else
+    {
+        // the covisible pairs: every k1 <= k2 of free keyframes that share a landmark, and every diagonal pair.  A K x K bit
+        // table, a row of W words per keyframe: a landmark's row becomes one bit set, which every keyframe of the row ORs
+        // into its own (views x W word operations per landmark, not views^2), read out in (k1, k2) order: sorted, each
+        // pair once
+        const size_t W = ((size_t)K + 63) / 64;
+        std::vector<uint64_t> shares((size_t)K * W, 0), seen(W);
+        for(int l = 0; l < L; ++l)
+        {
+            if(lm_ptr[(size_t)l + 1] - lm_ptr[(size_t)l] < 2)
+                continue; // one view: only the diagonal pair, which is listed anyway
+            std::fill(seen.begin(), seen.end(), 0);
+            for(int i = lm_ptr[(size_t)l]; i < lm_ptr[(size_t)l + 1]; ++i)
+            {
+                const int k = obs_kf[lm_obs[(size_t)i]];
+                if(ci[(size_t)k] >= 0)
+                    seen[(size_t)k >> 6] |= 1ull << (k & 63);
+            }
+            for(size_t w = 0; w < W; ++w)
+                for(uint64_t bits = seen[w]; bits; bits &= bits - 1)
+                {
+                    uint64_t* mine = &shares[(w * 64 + (size_t)__builtin_ctzll(bits)) * W];
+                    for(size_t v = 0; v < W; ++v)
+                        mine[v] |= seen[v];
+                }
+        }
+        for(int k1 = 0; k1 < K; ++k1)
+            for(int k2 = k1; k2 < K; ++k2)
+                if(ci[(size_t)k1] >= 0 && (k1 == k2 || (shares[(size_t)k1 * W + ((size_t)k2 >> 6)] >> (k2 & 63) & 1)))
+                    pairs.push_back(k1), pairs.push_back(k2);
+    }
     for(int l = 0; l < L; ++l)
         lm_active[(size_t)l] = lm_ptr[(size_t)l + 1] > lm_ptr[(size_t)l];
 
     BaArgs a{};
     a.K = K, a.L = L, a.M = M, a.n = 6 * n_free;
     a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (M + 255) / 256;
+    if(blocked)
+        a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
     // one block: what is uploaded first, then the working arrays
     size_t off = 0;
     auto carve = [&](size_t bytes) {
@@ -861,10 +1121,12 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
     const size_t o_pose0 = carve((size_t)K * 56), o_lm0 = carve((size_t)L * 24), o_cpose = carve((size_t)K * 56), o_clm = carve((size_t)L * 24);
     const size_t o_V = carve((size_t)L * 48), o_gl = carve((size_t)L * 24), o_Vinv = carve((size_t)L * 48), o_sl = carve((size_t)L * 24);
     const size_t o_U = carve((size_t)K * 168), o_gc = carve((size_t)K * 48), o_sc = carve((size_t)K * 48), o_W = carve((size_t)M * 144);
-    const size_t o_S = carve((size_t)a.n * a.n * 8), o_rhs = carve((size_t)a.n * 8), o_yc = carve((size_t)a.n * 8), o_yl = carve((size_t)L * 24);
+    const size_t o_S = carve(blocked ? 0 : (size_t)a.n * a.n * 8), o_rhs = carve((size_t)a.n * 8), o_yc = carve((size_t)a.n * 8), o_yl = carve((size_t)L * 24);
     const size_t o_part = carve((size_t)a.n_blocks * 16), o_out = carve((size_t)M);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
     MSLAM_CHK(c, grow(c->d_ba, off, c->stream));
+    if(blocked)
+        MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
     std::vector<uint8_t> stage(up_bytes, 0);
@@ -895,7 +1157,7 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
     a.pose = dbl(o_pose), a.lm = dbl(o_lm), a.cand_pose = dbl(o_cpose), a.cand_lm = dbl(o_clm);
     a.V = dbl(o_V), a.gl = dbl(o_gl), a.Vinv = dbl(o_Vinv), a.sl = dbl(o_sl);
     a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.W = dbl(o_W);
-    a.S = dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
+    a.S = blocked ? c->d_ba_S.get() : dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
     a.ctrl = reinterpret_cast<BaCtrl*>(d + o_ctrl);
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
@@ -914,10 +1176,40 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
             hipLaunchKernelGGL(k_ba_landmarks, g_lm, dim3(256), 0, s, a);
             hipLaunchKernelGGL(k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
             hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
-            if(a.n_pairs > 0)
+            if(a.n_pairs > 0 && !blocked)
             {
-                hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
+                {
+                    StageScope tk(c, "solver_schur");
+                    hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
+                }
+                StageScope tk(c, "solver_factor_subst");
                 hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
+            }
+            else if(a.n_pairs > 0)
+            {
+                // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
+                const int np = a.n_pad / kBagNB;
+                {
+                    StageScope tk(c, "solver_schur");
+                    hipLaunchKernelGGL(k_bag_clear, dim3((unsigned)a.n_pad), dim3(256), 0, s, a);
+                    hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
+                }
+                {
+                    StageScope tk(c, "solver_factor");
+                    for(int j = 0; j < np; ++j)
+                    {
+                        hipLaunchKernelGGL(k_bag_potrf, dim3(1), dim3(64), 0, s, a, j);
+                        hipLaunchKernelGGL(k_bag_trsm, dim3((unsigned)((a.ld - (j + 1) * kBagNB + 63) / 64)), dim3(64), 0, s, a, j);
+                        if(j + 1 < np)
+                        {
+                            const unsigned t = (unsigned)(np - j - 1); // column blocks right of the panel
+                            hipLaunchKernelGGL(k_bag_update, dim3(t * (t + 1) / 2 + t), dim3(64), 0, s, a, j);
+                        }
+                    }
+                }
+                StageScope tk(c, "solver_subst");
+                for(int j = np - 1; j >= 0; --j)
+                    hipLaunchKernelGGL(k_bag_backsolve, dim3((unsigned)(j + 1)), dim3(64), 0, s, a, j);
             }
             hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
             hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
@@ -961,4 +1253,22 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
     std::memcpy(poses, xp.data(), (size_t)K * 56);
     std::memcpy(landmarks, xl.data(), (size_t)L * 24);
     return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
+                                       const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M,
+                                       int max_iterations, double outlier_threshold, uint8_t* outlier,
+                                       mslam_hip_ba_summary* summary)
+{
+    return ba_run(c, false, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
+                  summary);
+}
+
+extern "C" int mslam_hip_bundle_adjust_global(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks,
+                                              int L, const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M,
+                                              int max_iterations, double outlier_threshold, uint8_t* outlier,
+                                              mslam_hip_ba_summary* summary)
+{
+    return ba_run(c, true, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
+                  summary);
 }

@@ -30,6 +30,7 @@
 //                                    either loop with IKeyframeTracker::setGuidedMatch(radius): every tracking call matches each
 //                                    landmark within <radius> px of its projection under the previous pose
 //        mslam_harness <plugin.so> --ba <scene>
+//        mslam_harness <plugin.so> --ba-global <scene>
 //                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
 //                                    keyframe's and landmark's state and the outlier observations
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
@@ -126,8 +127,9 @@ int main(int argc, char** argv)
                         result->pose.orientation.z(), inl);
             return 0;
         }
-        if(argc == 4 && std::strcmp(argv[2], "--ba") == 0)
+        if(argc == 4 && (std::strcmp(argv[2], "--ba") == 0 || std::strcmp(argv[2], "--ba-global") == 0))
         {
+            const bool global = std::strcmp(argv[2], "--ba-global") == 0; // IGlobalBackend::globalBundleAdjustment: up to 1024 keyframes
             // scene file: "MSBA", i32 version (1), K, L, M, max_iterations; K x i32 keyframe id; K x 7 f64 state (qx qy qz qw
             // px py pz); L x 3 f64; M x i32 keyframe index; M x i32 landmark index; M x 3 f64 camera-frame point
             std::ifstream in(argv[3], std::ios::binary);
@@ -186,7 +188,14 @@ int main(int argc, char** argv)
             if(!makeBackend)
                 return 3;
             std::unique_ptr<mslam::IBackend> backend = makeBackend();
-            const mslam::BackendOutput out = backend->bundleAdjustment(observations, head[4]);
+            auto* globalBackend = dynamic_cast<mslam::IGlobalBackend*>(backend.get());
+            if(global && !globalBackend)
+            {
+                std::fprintf(stderr, "the plugin does not offer the global bundle adjustment\n");
+                return 6;
+            }
+            const mslam::BackendOutput out =
+                global ? globalBackend->globalBundleAdjustment(observations, head[4]) : backend->bundleAdjustment(observations, head[4]);
             std::printf("ba termination %d iterations %d initial %.17g final %.17g keyframes %zu landmarks %zu outliers %zu\n", out.termination,
                         out.iterations, out.initialCost, out.finalCost, out.updatedKeyframes.size(), out.updatedLandmarks.size(),
                         out.outlierObservations.size());

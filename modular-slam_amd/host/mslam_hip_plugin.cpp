@@ -10,7 +10,7 @@
 //                                                           (orb_relocalizer.cpp:26-50, rgbd_feature_frontend.cpp:153,176)
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
-//   HipBundleAdjustBackend : IBackend                       CeresBackend's bundle adjustment (hipBundleAdjustBackendFactory)
+//   HipBundleAdjustBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global (hipBundleAdjustBackendFactory)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -796,10 +796,21 @@ class HipMinMseTracker : public ISlam3dPnp
 // keyframes and landmarks numbered in the order they first appear, the state as (qx qy qz qw px py pz), keyframe id 1
 // constant — and the result is written back into keyframe->state and landmark->state, as Ceres writes through the pointers
 // the reference hands it.  More than 64 keyframes is an error (the reduced system is dense); FAILURE updates nothing.
-class HipBundleAdjustBackend : public IBackend
+// globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.
+class HipBundleAdjustBackend : public IGlobalBackend
 {
   public:
     BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
+    {
+        return solve(observations, maxIterations, false);
+    }
+    BackendOutput globalBundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
+    {
+        return solve(observations, maxIterations, true);
+    }
+
+  private:
+    BackendOutput solve(const std::vector<BackendObservation>& observations, int maxIterations, bool global)
     {
         std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>> keyframes;
         std::vector<std::shared_ptr<Landmark<Vector3>>> landmarks;
@@ -835,11 +846,12 @@ class HipBundleAdjustBackend : public IBackend
         }
         ctx.ensure(0, 0);
         mslam_hip_ba_summary summary{};
-        const int rc = mslam_hip_bundle_adjust(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
-                                               static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
-                                               static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
+        const auto entry = global ? mslam_hip_bundle_adjust_global : mslam_hip_bundle_adjust;
+        const int rc = entry(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
+                             static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
+                             static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
         if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
-            raise(ctx.h, "mslam_hip_bundle_adjust", rc);
+            raise(ctx.h, global ? "mslam_hip_bundle_adjust_global" : "mslam_hip_bundle_adjust", rc);
         BackendOutput out;
         out.termination = summary.termination, out.iterations = summary.iterations;
         out.initialCost = summary.initial_cost, out.finalCost = summary.final_cost;
@@ -862,7 +874,6 @@ class HipBundleAdjustBackend : public IBackend
         return out;
     }
 
-  private:
     Ctx ctx;
 };
 

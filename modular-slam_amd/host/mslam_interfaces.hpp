@@ -224,6 +224,14 @@ class IBackend
     virtual BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations = 100) = 0;
     virtual ~IBackend() = default;
 };
+// extension: the reference's globalBundleAdjustment (ceres_backend.cpp:173-183) is the same bundleAdjustment over every
+// keyframe of the map; here it is a solver of its own (mslam_hip_bundle_adjust_global: up to 1024 keyframes).  IBackend is
+// untouched: an adapter that offers the global solve derives from this, and a caller reaches it with dynamic_cast.
+class IGlobalBackend : public IBackend
+{
+  public:
+    virtual BackendOutput globalBundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations = 100) = 0;
+};
 
 
 // ---- extension (not in the reference): candidates verified by match + RANSAC PnP against stored landmarks -----------------
