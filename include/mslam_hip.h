@@ -842,8 +842,11 @@ enum
     MSLAM_HIP_DBG_SELECTED = 3,   /* float triples after the quadtree, node-list order           */
     MSLAM_HIP_DBG_CELLS = 4,      /* int32 sextuples (x0, y0, cw, ch, ox, oy): the level's FAST cells in launch order
                                      (in-tree detector; host table, `frame` is not used)         */
-    MSLAM_HIP_DBG_FORMS = 5       /* int32 pair: levels produced by the fused level kernels, blurred slab kept in
+    MSLAM_HIP_DBG_FORMS = 5,      /* int32 pair: levels produced by the fused level kernels, blurred slab kept in
                                      tiles (1) or rows (0); host values, `frame` and `level` are not used */
+    MSLAM_HIP_DBG_QUAD_DIRECT = 6 /* uint32: bit l set = the quadtree selection of level l runs in its direct form
+                                     (k_quadtree_direct) for (level, frame) pairs of at most 1024 candidates; host value,
+                                     `frame` and `level` are not used */
 };
 int mslam_hip_level_geometry(mslam_hip_ctx* ctx, int* widths, int* heights, float* scales);
 int mslam_hip_debug_read(mslam_hip_ctx* ctx, int what, int frame, int level, void* dst, size_t dst_bytes,

@@ -24,7 +24,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmslam_hip.so")
 
 OK, E_INVALID, E_RUNTIME, E_CAPACITY, E_NO_VOCABULARY, E_FORMAT, E_NO_MODEL = range(7)
-DBG_PYRAMID, DBG_BLURRED, DBG_CANDIDATES, DBG_SELECTED, DBG_CELLS, DBG_FORMS = range(6)
+DBG_PYRAMID, DBG_BLURRED, DBG_CANDIDATES, DBG_SELECTED, DBG_CELLS, DBG_FORMS, DBG_QUAD_DIRECT = range(7)
+QUAD_DIRECT_MAX_CANDIDATES = 1024    # k_quadtree_direct: pairs with more candidates run the list passes
 MATCHER_AUTO, MATCHER_POPCOUNT = 0, 1
 DETECTOR_DISTRIBUTED, DETECTOR_CV_ORB = 0, 1
 BOW_ASSIGN_TREE, BOW_ASSIGN_FLAT = 0, 1
@@ -872,6 +873,13 @@ class Context:
         n = C.c_size_t(0)
         self._chk(self.L.mslam_hip_debug_read(self._h, DBG_FORMS, 0, 0, _p(out), C.c_size_t(out.nbytes), C.byref(n)))
         return int(out[0]), int(out[1])
+
+    def debug_quad_direct_levels(self):
+        """per level: True when its quadtree selection runs in the direct form (pairs of at most QUAD_DIRECT_MAX_CANDIDATES)"""
+        out = np.zeros(1, np.uint32)
+        n = C.c_size_t(0)
+        self._chk(self.L.mslam_hip_debug_read(self._h, DBG_QUAD_DIRECT, 0, 0, _p(out), C.c_size_t(out.nbytes), C.byref(n)))
+        return [bool((int(out[0]) >> l) & 1) for l in range(self.params.n_levels)]
 
     def debug_counts(self, what, n_frames):
         """[n_frames, n_levels] FAST candidates (DBG_CANDIDATES) or selected keypoints (DBG_SELECTED) of the last batch"""

@@ -223,6 +223,7 @@ static int build_geometry(mslam_hip_ctx* c)
         }
         if(lv.nxg * lv.nyg > 64)
             return fail(c, MSLAM_HIP_E_INVALID, "aspect ratio beyond 64:1 is not supported");
+        lv.qdepth = quad_depth_bound(lv, (unsigned)p.min_node_area);
     }
     g.slab = offset + 256;
     g.n_cells = (int)c->cells.size();
@@ -246,6 +247,7 @@ static int build_geometry_cv(mslam_hip_ctx* c)
     {
         LevelGeom& lv = g.lv[l];
         lv = LevelGeom{};
+        lv.qdepth = -1; // (no quadtree in this mode)
         lv.scale = (float)std::pow(sf, (double)l);
         const float inv = 1.0f / lv.scale;
         lv.w = cv_round_f((float)p.width * inv);
@@ -1861,6 +1863,15 @@ int mslam_hip_debug_read(mslam_hip_ctx* c, int what, int frame, int level, void*
             return fail(c, MSLAM_HIP_E_CAPACITY, "debug_read: buffer too small");
         const int32_t rec[2] = {c->fused_levels, c->geom.blur_tiled};
         std::memcpy(dst, rec, sizeof(rec));
+        return MSLAM_HIP_OK;
+    }
+    if(what == MSLAM_HIP_DBG_QUAD_DIRECT)
+    {
+        *n_items = 1;
+        if(dst_bytes < 4)
+            return fail(c, MSLAM_HIP_E_CAPACITY, "debug_read: buffer too small");
+        const uint32_t m = c->p.detector == MSLAM_HIP_DETECTOR_DISTRIBUTED ? quad_direct_levels(c->geom) : 0u;
+        std::memcpy(dst, &m, sizeof(m));
         return MSLAM_HIP_OK;
     }
     return fail(c, MSLAM_HIP_E_INVALID, "debug_read: unknown item");

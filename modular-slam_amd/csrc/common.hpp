@@ -29,6 +29,7 @@ struct LevelGeom
     // quadtree initial grid (:1031-1052)
     int nxg, nyg;
     double delta_x, delta_y;
+    int qdepth;     // depth at which every quadtree node keeps by area (quad_depth_bound); -1: unbounded
 };
 
 struct Geometry
@@ -143,6 +144,8 @@ struct QuadArgs
     unsigned min_size;
 };
 void launch_quadtree(const Geometry& g, const QuadArgs& a, int frame0, int n_frames, hipStream_t s);
+int quad_depth_bound(const LevelGeom& lv, unsigned min_size); // host: fills LevelGeom::qdepth
+unsigned quad_direct_levels(const Geometry& g);               // host: bit l = k_quadtree_direct takes level l
 // the 7 Gaussian taps arranged for the kernels (k_blur2, k_level.hip)
 struct BlurK
 {

@@ -14,7 +14,11 @@
 // undivided node at T+U_i: two workgroup-wide exclusive scans per pass.  Keypoints never move; each
 // carries the list position of its node.  The per-leaf winner ("first maximum", :1142-1149) is an
 // atomicMax over (score, -original index).
+//
+// Two forms: quad_run (k_quadtree, k_quadtree_big) runs those passes for any level; k_quadtree_direct computes the same
+// list without passes for the levels whose tree fits its LDS table (see there), and leaves the other pairs to quad_run.
 #include "common.hpp"
+#include <algorithm>
 #include <cstdlib>
 
 namespace mslam
@@ -31,6 +35,9 @@ constexpr int kBigNodes = 4096;   // k_quadtree_big: node arrays in LDS up to th
 constexpr int kBigKp = 12288;     //                 keypoint -> node links in LDS up to this many candidates
 constexpr int kBigMinPixels = 400000; // levels with more pixels than this get the k_quadtree_big launch
 constexpr int kMaxInitNodes = 64;
+// k_quadtree_direct: at most kDirectKp candidates and a tree table of at most kDirectSlots slots (640x480 at min-area 1000:
+// 1365 on levels 0-2, 341 above).  LDS: 4 bytes per candidate + 7 per slot = 13.7 KB, 256 threads: 8 workgroups per CU
+constexpr int kDirectKp = 1024, kDirectQT = 256, kDirectSlots = 1365, kDirectMaxDepth = 10;
 constexpr int kMaxPasses = 40;
 
 struct Scan
@@ -420,7 +427,7 @@ __device__ __forceinline__ int quad_class(uint32_t N, int n_cells, unsigned clas
 }
 // (waves per SIMD: the small and mid instances must fit 8 — 8 x 4 resp. 4 x 8 waves per CU —, i.e. 64 registers)
 template <int KP, int NT, int CLS>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(CLS == 2 ? 4 : 8))) void k_quadtree(Geometry g, QuadArgs a, unsigned big_levels)
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(CLS == 2 ? 4 : 8))) void k_quadtree(Geometry g, QuadArgs a, unsigned big_levels, unsigned direct_levels)
 {
     __shared__ Scan scan, scan2;
     __shared__ uint32_t l_cand[KP];
@@ -455,6 +462,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(CLS == 2 ? 4
         return; // (a larger class takes the level)
     const uint32_t* ccnt = a.cell_cnt + frame * g.n_cells + lv.cell_base;
     const uint32_t N = quad_cell_offsets<NT>(ccnt, n_cells, cell_off, scan);
+    if(((direct_levels >> level) & 1u) && N <= (uint32_t)kDirectKp)
+        return; // k_quadtree_direct's pair
     if(quad_class(N, n_cells, classes) != CLS)
         return; // another instance's pair
     if(N > (uint32_t)a.cand_cap)
@@ -548,6 +557,286 @@ __global__ __launch_bounds__(QT) void k_quadtree_big(Geometry g, QuadArgs a, uns
     }
 }
 
+// ---- the direct form --------------------------------------------------------------------------------------------------
+// What the passes of quad_run compute is a closed-form function of the candidates:
+//   1. keep-or-divide is static (one candidate, or the area rule), a child's rectangle depends only on its parent's and a
+//      candidate's child on two centre compares: a candidate's path (init node i0, children c1, c2, ...) is geometry, and
+//      a node divides in the pass after the one that made it, or never;
+//   2. the final list is the nodes grouped by depth, deepest first; inside the depth-d group the order is lexicographic in
+//      (i0, c1), c2, ..., cd, digit j DEscending when d - j is even (i0 goes with c1), the depth-0 group ascending;
+//   3. with K[d] / M[d] the real keep / non-keep nodes of depth d (real: not empty, no proper ancestor keeps), the list
+//      after pass p holds K[0] + ... + K[p] + M[p] nodes, so the last pass P is the first p >= 1 with K[p] + M[p] == M[p-1];
+//      the leaves are the real keep nodes of depth <= P and the real non-keep nodes of depth P.
+// So: every candidate walks down to the level's depth bound (LevelGeom::qdepth: where the largest rectangle keeps by
+// area) with its rectangle in registers and counts itself into a table of the implicit tree — slot (d, i0 4^d + c1 .. cd),
+// block d starting at n_init (4^d - 1) / 3 —; one phase classifies the slots and totals K / M; the candidates vote for
+// their leaf's winner; one scan over the slots in list order ranks the leaves and writes them out.
+template <int SLOTS>
+struct DirectTable
+{
+    uint32_t cnt[(SLOTS + 1) / 2]; // candidates per slot, 16 bits each
+    uint32_t best[SLOTS];          // winner per slot; before that the cell offsets of the gather
+    uint8_t flag[SLOTS];           // phase 1: 1 = keeps by area; from phase 2: 1 = real keep node, 2 = real non-keep node
+};
+
+__device__ __forceinline__ uint32_t direct_block_start(uint32_t n_init, int d) { return n_init * (((1u << (2 * d)) - 1u) / 3u); }
+
+template <int KP, int SLOTS, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8))) void k_quadtree_direct(Geometry g, QuadArgs a, unsigned direct_levels)
+{
+    constexpr int PER = KP / NT; // candidates per thread: their paths stay in registers between the phases
+    static_assert(KP % NT == 0 && KP == kDirectKp, "instance shape");
+    __shared__ Scan scan;
+    __shared__ uint32_t l_cand[KP];
+    __shared__ DirectTable<SLOTS> t;
+    __shared__ uint32_t tot[2 * (kDirectMaxDepth + 2)]; // K[d], M[d]
+
+    const int level = (int)((blockIdx.x + blockIdx.y) % (unsigned)g.n_levels); // (k_quadtree's XCD rotation)
+    if(!((direct_levels >> level) & 1u))
+        return;
+    const size_t frame = blockIdx.y + g.frame0;
+    const LevelGeom& lv = g.lv[level];
+    const int tid = threadIdx.x;
+    const size_t slot = frame * g.n_levels + level;
+    const size_t cap = (size_t)a.cand_cap;
+    uint32_t* g_cand = a.cand + slot * cap;
+    uint32_t* sel = a.sel + slot * cap;
+    const int D = lv.qdepth;
+    const uint32_t n_init = (uint32_t)(lv.nxg * lv.nyg);
+    const uint32_t n_slots = direct_block_start(n_init, D + 1); // <= SLOTS (quad_direct_levels)
+
+    for(uint32_t i = tid; i < (n_slots + 1) / 2; i += NT)
+        t.cnt[i] = 0;
+    for(uint32_t i = tid; i < n_slots; i += NT)
+        t.flag[i] = 0;
+    if(tid < 2 * (kDirectMaxDepth + 2))
+        tot[tid] = 0;
+
+    // ---- 0. the gather, as k_quadtree's
+    const int n_cells = lv.n_cells; // < SLOTS (quad_direct_levels)
+    uint32_t* cell_off = t.best;
+    const uint32_t* ccnt = a.cell_cnt + frame * g.n_cells + lv.cell_base;
+    const uint32_t N = quad_cell_offsets<NT>(ccnt, n_cells, cell_off, scan);
+    if(N > (uint32_t)KP)
+        return; // k_quadtree's pair
+    if(N > (uint32_t)a.cand_cap)
+    {
+        if(tid == 0)
+        {
+            atomicOr(a.flags, kFlagCandOverflow);
+            a.cand_cnt[slot] = 0;
+            a.sel_cnt[slot] = 0;
+        }
+        return;
+    }
+    if(tid == 0)
+        a.cand_cnt[slot] = N;
+    if(N == 0)
+    {
+        if(tid == 0)
+            a.sel_cnt[slot] = 0;
+        return;
+    }
+
+    // ---- 1. gather, descent and counting: one phase, every candidate on its own
+    const uint32_t* ckp = a.cell_kp + (frame * g.n_cells + lv.cell_base) * (size_t)kCellCap;
+    const float sf = lv.scale;
+    const float min_size_f = (float)a.min_size;
+    uint32_t path[PER]; // (depth the walk ended at) << 24 | index inside that depth's block; ~0: dropped or none
+#pragma unroll
+    for(int i = 0; i < PER; ++i)
+    {
+        const uint32_t k = (uint32_t)(tid + i * NT);
+        path[i] = ~0u;
+        if(k >= N)
+            continue;
+        int lo = 0, hi = n_cells - 1; // last cell with cell_off <= k
+        while(lo < hi)
+        {
+            const int mid = (lo + hi + 1) >> 1;
+            if(cell_off[mid] <= k)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        const uint32_t p = ckp[(size_t)lo * kCellCap + (k - cell_off[lo])];
+        l_cand[k] = p;
+        g_cand[k] = p; // the global copy is kept for mslam_hip_debug_read
+        const int x = kp_x(p), y = kp_y(p);
+        const unsigned ix = (unsigned)((double)(float)x / lv.delta_x);
+        const unsigned iy = (unsigned)((double)(float)y / lv.delta_y);
+        const unsigned idx = ix + iy * (unsigned)lv.nxg;
+        if(idx >= n_init)
+            continue; // (:1025-1105: a candidate outside the init grid is in no node)
+        int bx = (int)(lv.delta_x * ix), by = (int)(lv.delta_y * iy);
+        int ex = (int)(lv.delta_x * (ix + 1)), ey = (int)(lv.delta_y * (iy + 1));
+        uint32_t q = idx;
+        int d = 0;
+        for(;;)
+        {
+            const uint32_t s = direct_block_start(n_init, d) + q;
+            atomicAdd(&t.cnt[s >> 1], 1u << (16 * (s & 1u)));
+            const unsigned area = (unsigned)((ex - bx) * (ey - by));
+            if(__fmul_rn(__fmul_rn((float)area, sf), sf) <= min_size_f || d == D)
+            {
+                t.flag[s] = 1; // (every writer writes the same value)
+                break;
+            }
+            const int cx = bx + ((ex - bx + 1) >> 1), cy = by + ((ey - by + 1) >> 1); // cvCeil(d/2.0)
+            const bool right = cx <= x, low = cy <= y;
+            bx = right ? cx : bx, ex = right ? ex : cx;
+            by = low ? cy : by, ey = low ? ey : cy;
+            q = (q << 2) | (right ? 1u : 0u) | (low ? 2u : 0u);
+            ++d;
+        }
+        path[i] = ((uint32_t)d << 24) | q;
+    }
+    __syncthreads();
+
+    // ---- 2. node classes, depth by depth (a wave's ballots make the totals), and the winners' cells
+    for(int d = 0; d <= D; ++d)
+    {
+        const uint32_t start = direct_block_start(n_init, d), n_d = n_init << (2 * d);
+        const uint32_t pstart = direct_block_start(n_init, d > 0 ? d - 1 : 0);
+        uint32_t kd = 0, md = 0;
+        for(uint32_t base = 0; base < n_d; base += NT)
+        {
+            const uint32_t q = base + tid;
+            bool keep = false, open = false;
+            if(q < n_d)
+            {
+                const uint32_t s = start + q, ps = pstart + (q >> 2);
+                const uint32_t c = (t.cnt[s >> 1] >> (16 * (s & 1u))) & 0xFFFFu;
+                const uint32_t pc = d > 0 ? (t.cnt[ps >> 1] >> (16 * (ps & 1u))) & 0xFFFFu : 2u;
+                const bool real = c > 0 && pc >= 2; // counts do not grow downwards: the parent's covers every ancestor's
+                keep = real && (c == 1 || t.flag[s] != 0);
+                open = real && !keep;
+                t.flag[s] = keep ? 1 : open ? 2 : 0;
+                t.best[s] = 0;
+            }
+            kd += (uint32_t)__popcll(__ballot(keep));
+            md += (uint32_t)__popcll(__ballot(open));
+        }
+        if((tid & 63) == 0 && (kd | md) != 0)
+        {
+            atomicAdd(&tot[2 * d], kd);
+            atomicAdd(&tot[2 * d + 1], md);
+        }
+    }
+    __syncthreads();
+    int P = 1; // the last pass: the first that leaves the list as long as it was (tot[] ends with zeros: P <= D + 1)
+    while(tot[2 * P] + tot[2 * P + 1] != tot[2 * P - 1])
+        ++P;
+    const int top = P < D ? P : D; // deepest depth with leaves
+
+    // ---- 3. winners: a candidate's leaf is the first keep node on its path, or its depth-P node
+#pragma unroll
+    for(int i = 0; i < PER; ++i)
+    {
+        if(path[i] == ~0u)
+            continue;
+        const uint32_t k = (uint32_t)(tid + i * NT);
+        const int dk = (int)(path[i] >> 24);
+        const uint32_t q = path[i] & 0xFFFFFFu;
+        const int last = dk < top ? dk : top;
+        uint32_t leaf = 0;
+        for(int d = 0; d <= last; ++d)
+        {
+            leaf = direct_block_start(n_init, d) + (q >> (2 * (dk - d)));
+            if(t.flag[leaf] == 1)
+                break;
+        }
+        atomicMax(&t.best[leaf], ((uint32_t)kp_score(l_cand[k]) << 24) | (0xFFFFFFu - k));
+    }
+    __syncthreads();
+
+    // ---- 4. rank and emit in list order: depth blocks from `top` down, the descending digits complemented (an XOR per
+    //         depth; n_init - 1 - i0 for the init digit at odd depths).  Each thread takes consecutive entries.
+    const uint32_t n_entries = direct_block_start(n_init, top + 1);
+    const uint32_t per = (n_entries + NT - 1) / NT;
+    const uint32_t e0 = (uint32_t)tid * per, e1 = e0 + per < n_entries ? e0 + per : n_entries;
+    auto entry_slot = [&](uint32_t e, bool& is_leaf) {
+        int d = top;
+        uint32_t n_d = n_init << (2 * d);
+        while(e >= n_d) // (entries of depth d come before those of depth d - 1)
+        {
+            e -= n_d;
+            --d;
+            n_d >>= 2;
+        }
+        const uint32_t bits = 2u * (uint32_t)d, low_mask = (1u << bits) - 1u;
+        uint32_t i0 = e >> bits;
+        if(d & 1)
+            i0 = n_init - 1u - i0;
+        const uint32_t s = direct_block_start(n_init, d) + ((i0 << bits) | ((e ^ 0x33333333u) & low_mask));
+        const uint32_t f = t.flag[s];
+        is_leaf = f == 1 || (f == 2 && d == P);
+        return s;
+    };
+    uint32_t mine = 0;
+    for(uint32_t e = e0; e < e1; ++e)
+    {
+        bool is_leaf;
+        entry_slot(e, is_leaf);
+        mine += is_leaf ? 1u : 0u;
+    }
+    uint32_t n_leaves;
+    uint32_t r = block_excl_scan<NT>(mine, scan, n_leaves);
+    for(uint32_t e = e0; e < e1 && mine != 0; ++e)
+    {
+        bool is_leaf;
+        const uint32_t s = entry_slot(e, is_leaf);
+        if(is_leaf)
+            sel[r++] = l_cand[0xFFFFFFu - (t.best[s] & 0xFFFFFFu)];
+    }
+    if(tid == 0)
+        a.sel_cnt[slot] = n_leaves;
+}
+
+// which levels of a geometry the direct kernel takes (bit l): a bounded depth whose table, and the level's cell offsets,
+// fit the instance.  MSLAM_HIP_QUAD_DIRECT=0: none (every pair runs quad_run's passes); read at every launch, so that one
+// process can run both forms.
+unsigned quad_direct_levels(const Geometry& g)
+{
+    const char* env = getenv("MSLAM_HIP_QUAD_DIRECT");
+    const bool on = !env || atoi(env) != 0;
+    unsigned m = 0;
+    for(int l = 0; on && l < g.n_levels; ++l)
+    {
+        const LevelGeom& lv = g.lv[l];
+        if(lv.qdepth < 0 || lv.qdepth > kDirectMaxDepth || lv.n_cells + 1 > kDirectSlots)
+            continue;
+        const long long slots = (long long)lv.nxg * lv.nyg * (((1ll << (2 * (lv.qdepth + 1))) - 1) / 3);
+        if(slots <= kDirectSlots)
+            m |= 1u << l;
+    }
+    return m;
+}
+
+// LevelGeom::qdepth: the depth at which every node keeps by area — the largest init rectangle, both sides halved with ceil
+// until the rule holds (a child is never larger than that, and the rule is monotone in both sides); -1: it never does
+int quad_depth_bound(const LevelGeom& lv, unsigned min_size)
+{
+    int dx = 0, dy = 0;
+    for(int iy = 0; iy < lv.nyg; ++iy)
+        for(int ix = 0; ix < lv.nxg; ++ix)
+        {
+            dx = std::max(dx, (int)(lv.delta_x * (ix + 1)) - (int)(lv.delta_x * ix));
+            dy = std::max(dy, (int)(lv.delta_y * (iy + 1)) - (int)(lv.delta_y * iy));
+        }
+    for(int d = 0; d <= 15; ++d)
+    {
+        const unsigned area = (unsigned)(dx * dy);
+        const float scaled = (float)area * lv.scale; // (two roundings, as the kernels' __fmul_rn pair)
+        if(scaled * lv.scale <= (float)min_size)
+            return d;
+        if(dx <= 1 && dy <= 1)
+            break;
+        dx = (dx + 1) >> 1, dy = (dy + 1) >> 1;
+    }
+    return -1;
+}
+
 void launch_quadtree(const Geometry& g, const QuadArgs& a, int frame0, int n_frames, hipStream_t s)
 {
     dim3 grid(g.n_levels, n_frames);
@@ -559,15 +848,21 @@ void launch_quadtree(const Geometry& g, const QuadArgs& a, int frame0, int n_fra
             big_levels |= 1u << l;
     // MSLAM_HIP_QUAD_CLASSES: bit 0 = small instance, bit 1 = mid instance (default both; 0 = the large instance alone)
     static const unsigned classes_env = [] { const char* e = getenv("MSLAM_HIP_QUAD_CLASSES"); return e ? (unsigned)atoi(e) & 3u : 3u; }();
-    // a handful of frames (the synchronous single-frame call): one launch — there is no occupancy to gain, and every launch
+    // the direct kernel takes the pairs of its levels that have at most kDirectKp candidates; quad_run's instances take the
+    // rest.  When every level is direct that rest is rare (a level-0 burst): the large instance alone serves it
+    const unsigned direct = quad_direct_levels(g);
+    const bool all_direct = direct == (g.n_levels >= 32 ? ~0u : (1u << g.n_levels) - 1u);
+    // a handful of frames (the synchronous single-frame call): no classes — there is no occupancy to gain, and every launch
     // is a few microseconds of the call's latency
-    const unsigned classes = n_frames < 8 ? 0u : classes_env;
+    const unsigned classes = n_frames < 8 || all_direct ? 0u : classes_env;
     const unsigned bl = big_levels | (classes << 30);
-    hipLaunchKernelGGL((k_quadtree<kLdsKp, QT, 2>), grid, dim3(QT), 0, s, gg, a, bl);
+    if(direct != 0)
+        hipLaunchKernelGGL((k_quadtree_direct<kDirectKp, kDirectSlots, kDirectQT>), grid, dim3(kDirectQT), 0, s, gg, a, direct);
+    hipLaunchKernelGGL((k_quadtree<kLdsKp, QT, 2>), grid, dim3(QT), 0, s, gg, a, bl, direct);
     if(classes & 2u)
-        hipLaunchKernelGGL((k_quadtree<kMidKp, kMidQT, 1>), grid, dim3(kMidQT), 0, s, gg, a, bl);
+        hipLaunchKernelGGL((k_quadtree<kMidKp, kMidQT, 1>), grid, dim3(kMidQT), 0, s, gg, a, bl, direct);
     if(classes & 1u)
-        hipLaunchKernelGGL((k_quadtree<kSmallKp, kSmallQT, 0>), grid, dim3(kSmallQT), 0, s, gg, a, bl);
+        hipLaunchKernelGGL((k_quadtree<kSmallKp, kSmallQT, 0>), grid, dim3(kSmallQT), 0, s, gg, a, bl, direct);
     if(big_levels != 0)
     {
         constexpr size_t lds = (size_t)kBigNodes * (8 + 8 + 8 + 2 + 2 + 2 + 1) + (size_t)kBigKp * 2;
