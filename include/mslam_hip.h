@@ -575,6 +575,53 @@ int mslam_hip_bundle_adjust_global(mslam_hip_ctx* ctx, double* poses /* K x 7, i
                                    const int32_t* obs_lm, const double* obs_cam /* M x 3 */, int M, int max_iterations /* 100 */,
                                    double outlier_threshold /* 0.15 */, uint8_t* outlier /* M, may be NULL */,
                                    mslam_hip_ba_summary* summary /* may be NULL */);
+/* ---- RgbdFeatureFrontend::closeLoop (rgbd_feature_frontend.cpp:577-580, an empty body; called at :198-205): pose graph ----
+ * The correction a detected loop asks for: Levenberg-Marquardt over keyframe poses of
+ *   cost = 1/2 sum_e |r_e|^2,   r_e = sqrt_info_e [p_ab - p_meas ; 2 vec(delta)]
+ *   p_ab = rot(q_a^-1, p_b - p_a),  q_ab = q_a^-1 (x) q_b,  delta = q_meas (x) q_ab^-1
+ * the error term of Ceres's published pose_graph_3d example (pose_graph_3d_error_term.h), taken because the reference's
+ * backend is Ceres with EigenQuaternionManifold.  NO SIGN FIX is applied on delta: q and -q name one rotation, but a
+ * measurement or a pose entered with the other sign turns 2 vec(delta) round (delta is then near (0, 0, 0, -1)); the solve
+ * still reaches the same poses, with the quaternion's sign kept, because the rotation error enters squared.
+ *   poses      K x 7 (qx qy qz qw px py pz, camera -> world; mslam_hip_bundle_adjust's layout), K in
+ *              0..MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES, in: start, out: result; fixed[k] != 0 holds pose k constant; NULL: none;
+ *   edge_a, edge_b   E edges, E in 0..MSLAM_HIP_POSE_GRAPH_MAX_EDGES, indices into poses; duplicates and both directions
+ *              between one pair are allowed;
+ *   edge_meas  E x 7: q then p of pose b expressed in a's frame (T_a^-1 T_b);
+ *   sqrt_info  E x 36, row-major 6 x 6 per edge (rows and columns: position, then rotation), or NULL for identity.
+ * A free pose has the 6 tangent dimensions of mslam_hip_bundle_adjust.  A pose without an edge, or a constant one, is not
+ * part of the problem and comes back bit for bit.  summary: mslam_hip_ba_summary with n_outliers = 0.
+ * Returns MSLAM_HIP_OK for terminations 0 and 1; MSLAM_HIP_E_NO_MODEL for FAILURE: the poses are left unchanged.
+ * MSLAM_HIP_E_INVALID: K or E out of range, an index out of range, edge_a[e] == edge_b[e], max_iterations < 0, a pose or
+ * measurement quaternion whose norm is off 1 by more than 1e-6, a non-finite sqrt_info.  E = 0 is CONVERGENCE at cost 0,
+ * nothing touched.  Two calls on the same input return the same bits: no sum uses an atomic, every sum has one order.  All
+ * arithmetic is f64.  Against Ceres 2.2 with default Solver::Options but max_num_iterations.  PARITY UNPINNED: no Ceres build
+ * exists to compare with; the tests compare with an independent numpy restatement (tests/pose_graph_ref.py: jets, two linear
+ * solvers) and with ground truth.
+ *   residual                 SAME expression for unit quaternions: Eigen's inverse() (conjugate / squared norm) where the
+ *                            example writes conjugate(), Eigen's quaternion product and _transformVector;
+ *   derivatives              DEVIATES in rounding: analytic (the matrices are written out in k_posegraph.hip and DESIGN.md
+ *                            4.17) instead of jets times PlusJacobian; equal for unit q;
+ *   sums                     DEVIATES in rounding: per pose over its edges by lane stride then a fixed butterfly, per pair of
+ *                            poses in edge order, costs by a fixed two-stage tree; not Ceres's evaluation order.  The sum of a
+ *                            pair is one wave's serial loop over the pair's edges: bounded by E, and the slow shape when
+ *                            many duplicate edges join one pair (65536 between two poses is one loop of 65536 steps);
+ *   linear solver            DEVIATES in rounding: the damped normal equations J^T J + D^2 over the free poses, dense, by
+ *                            mslam_hip_bundle_adjust_global's blocked Cholesky (the same kernels) at every K; the example
+ *                            asks for SPARSE_NORMAL_CHOLESKY.  A non-positive pivot or a non-finite step is an invalid step;
+ *   Jacobi scaling, trust region, termination order, FAILURE result
+ *                            those of mslam_hip_bundle_adjust (SAME / DEVIATES as stated there); termination is judged on
+ *                            the ambient parameters (7 per pose) of the free poses that have an edge;
+ *   sizes                    DEVIATES: at most 1024 poses and 65536 edges per solve.  The reduced system is the DENSE 6 K x 6 K
+ *                            matrix of the free poses (6144^2 doubles = 302 MB at the bound, the buffer global bundle
+ *                            adjustment uses; no second one is allocated), although a pose graph's normal equations are sparse
+ *                            (a chain's are block-tridiagonal): a sparse factor is out of scope here.  The per-edge blocks
+ *                            (residual, two Jacobians, measurement, sqrt_info: 121 doubles) take 63 MB at the edge bound. */
+#define MSLAM_HIP_POSE_GRAPH_MAX_EDGES 65536
+int mslam_hip_pose_graph(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out */, const uint8_t* fixed /* K, or NULL */,
+                         int K /* 0..1024 */, const int32_t* edge_a, const int32_t* edge_b, const double* edge_meas /* E x 7 */,
+                         const double* sqrt_info /* E x 36, or NULL */, int E, int max_iterations /* 100 */,
+                         mslam_hip_ba_summary* summary /* may be NULL */);
 /* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
  * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
  * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of

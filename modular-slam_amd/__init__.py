@@ -30,6 +30,7 @@ MATCHER_AUTO, MATCHER_POPCOUNT = 0, 1
 DETECTOR_DISTRIBUTED, DETECTOR_CV_ORB = 0, 1
 BOW_ASSIGN_TREE, BOW_ASSIGN_FLAT = 0, 1
 CV_ORDER_LIBSTDCXX, CV_ORDER_RASTER = 0, 1
+POSE_GRAPH_MAX_KEYFRAMES, POSE_GRAPH_MAX_EDGES = 1024, 65536    # mslam_hip_pose_graph's bounds (include/mslam_hip.h)
 
 # every symbol include/mslam_hip.h declares (tests/test_cabi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -52,7 +53,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_visible", "mslam_hip_track", "mslam_hip_track_window", "mslam_hip_track_window_dev",
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
-    "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world",
+    "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world", "mslam_hip_pose_graph",
 ]
 
 
@@ -517,6 +518,31 @@ class Context:
             self._chk(rc)
         res = {k: getattr(out, k) for k, _ in BaSummary._fields_ if k != "reserved"}
         res.update(poses=x, landmarks=lm, outlier=mask[:len(ok)].astype(bool))
+        return res
+
+    def pose_graph(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100):
+        """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024), E edges
+        (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
+        flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
+        final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged."""
+        x = np.array(poses, np.float64).reshape(-1, 7)
+        ea = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+        eb = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+        z = np.ascontiguousarray(edge_meas, np.float64).reshape(-1, 7)
+        w = None if sqrt_info is None else np.ascontiguousarray(sqrt_info, np.float64).reshape(-1, 36)
+        if not len(ea) == len(eb) == len(z) or (w is not None and len(w) != len(ea)):
+            raise MslamHipError(E_INVALID, "pose_graph: %d / %d edge ends, %d measurements, %s sqrt_info" % (
+                len(ea), len(eb), len(z), "no" if w is None else len(w)))
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+        if fx is not None and len(fx) != len(x):
+            raise MslamHipError(E_INVALID, "pose_graph: %d poses, %d fixed flags" % (len(x), len(fx)))
+        out = BaSummary()
+        rc = self.L.mslam_hip_pose_graph(self._h, _p(x), _p(fx), len(x), _p(ea), _p(eb), _p(z), _p(w), len(ea),
+                                         int(max_iterations), C.byref(out))
+        if rc != E_NO_MODEL:
+            self._chk(rc)
+        res = {k: getattr(out, k) for k, _ in BaSummary._fields_ if k != "reserved"}
+        res.update(poses=x)
         return res
 
     def kf_update_world(self, landmark_ids, world_xyz):
@@ -1086,13 +1112,49 @@ def quaternion_to_rotation(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
+def rvec_to_rotation(rvec):
+    """Rodrigues' formula: the rotation matrix of an axis-angle vector"""
+    w = np.asarray(rvec, np.float64).reshape(3)
+    th = np.linalg.norm(w)
+    if th < 1e-300:
+        return np.eye(3)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)
+
+
+def rotation_to_rvec(R):
+    """the axis-angle vector of a rotation matrix, through the unit quaternion with w >= 0 (an angle in [0, pi])"""
+    q = rotation_to_quaternion(R)
+    n = np.linalg.norm(q[:3])
+    return np.zeros(3) if n < 1e-300 else 2.0 * np.arctan2(n, q[3]) * q[:3] / n
+
+
+def quaternion_product(a, b):
+    """a (x) b, x y z w"""
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
+
+
+def relative_pose(Ta, Tb):
+    """T_a^-1 o T_b for two states (qx qy qz qw px py pz): pose b in a's frame, the measurement of a pose-graph edge (a, b)"""
+    Ta, Tb = np.asarray(Ta, np.float64), np.asarray(Tb, np.float64)
+    qi = np.array([-Ta[0], -Ta[1], -Ta[2], Ta[3]]) / np.dot(Ta[:4], Ta[:4])
+    q = quaternion_product(qi, Tb[:4])
+    return np.concatenate([q / np.linalg.norm(q), quaternion_to_rotation(Ta[:4]).T @ (Tb[4:] - Ta[4:])])
+
+
 class HipBackend:
     """CeresBackend (ceres_backend.cpp) on Context.bundle_adjust: the keyframes' states (camera -> world: qx qy qz qw px py
     pz), their observations (landmark id, camera-frame point: what ReprojectionError's constructor forms, :24-28) and the
     landmarks' world points, kept on the host; the solve runs on the device.  The first keyframe added is constant, as the
     reference's keyframe 1 is (:155-159).  Nothing is removed: the outlier observations are returned
     (removeObservation's body is commented out in the reference).  global_solver = True: global_ba() goes through
-    Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes."""
+    Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes.
+    close_loop() is the body of the reference's empty closeLoop (rgbd_feature_frontend.cpp:577-580): a pose graph over every
+    keyframe on Context.pose_graph; self.anchor names, per landmark, the keyframe that created it."""
 
     MAX_KEYFRAMES = 64
     MAX_GLOBAL_KEYFRAMES = 1024
@@ -1103,6 +1165,7 @@ class HipBackend:
         self.poses = {}       # id -> [7]
         self.obs = {}         # id -> (landmark ids [n] i64, camera points [n, 3])
         self.landmarks = {}   # landmark id -> [3]
+        self.anchor = {}      # landmark id -> the keyframe that created it (close_loop moves the landmark with that keyframe)
         self.first = None
 
     def add_keyframe(self, id, pose, landmark_ids, cam_points):
@@ -1120,6 +1183,7 @@ class HipBackend:
         world = cam @ quaternion_to_rotation(pose[:4]).T + pose[4:]
         for l, w in zip(lids.tolist(), world):
             self.landmarks.setdefault(l, w.copy())
+            self.anchor.setdefault(l, int(id))
 
     def neighbours(self, ref, graph, deep_level=1):
         """getNeighbourKeyframes (basic_map.cpp:209-237) with its `level <= deepLevel` test, as HipKeyframeTracker.neighbours
@@ -1176,6 +1240,56 @@ class HipBackend:
             raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
         return self._solve(sorted(self.poses), self.global_solver)
 
+    def loop_problem(self, cur_id, loop_id, rvec, tvec, graph, sqrt_info=None):
+        """the arrays Context.pose_graph takes for a loop between keyframes loop_id and cur_id -> (keyframe ids, poses,
+        fixed, edge_a, edge_b, edge_meas, sqrt_info): every graph edge i < j with both ends in self.poses, in sorted order,
+        measured on the current poses (T_i^-1 T_j: an odometry edge holds what is believed now); the loop edge
+        (loop_id, cur_id, Z) last, Z = T_loop^-1 o T_cur* with T_cur* = (R^T, -R^T t) the pose (rvec, tvec) names.
+        sqrt_info (6 x 6, or None) weighs the loop edge; the others are identity."""
+        ids = sorted(self.poses)
+        index = {id: k for k, id in enumerate(ids)}
+        poses = np.array([self.poses[id] for id in ids], np.float64).reshape(-1, 7)
+        ea, eb, meas = [], [], []
+        for i in ids:
+            for j in sorted(graph.get(i, ())):
+                if i < j and j in index:
+                    ea.append(index[i]), eb.append(index[j]), meas.append(relative_pose(self.poses[i], self.poses[j]))
+        R = rvec_to_rotation(rvec)
+        T_cur = np.concatenate([rotation_to_quaternion(R.T), -R.T @ np.asarray(tvec, np.float64).reshape(3)])
+        ea.append(index[int(loop_id)]), eb.append(index[int(cur_id)]), meas.append(relative_pose(self.poses[int(loop_id)], T_cur))
+        info = None
+        if sqrt_info is not None:
+            info = np.tile(np.eye(6), (len(ea), 1, 1))
+            info[-1] = np.asarray(sqrt_info, np.float64).reshape(6, 6)
+        fixed = np.array([id == self.first for id in ids], np.uint8)
+        return ids, poses, fixed, np.array(ea, np.int32), np.array(eb, np.int32), np.array(meas, np.float64).reshape(-1, 7), info
+
+    def close_loop(self, cur_id, loop_id, rvec, tvec, graph, sqrt_info=None):
+        """closeLoop: (rvec, tvec) is the world -> camera pose of keyframe cur_id found by PnP against loop_id's stored
+        landmarks.  Solves loop_problem() on the device; on a usable termination the poses are replaced and every landmark
+        moves rigidly with its anchor keyframe, X' = T_a' T_a^-1 X.  -> the summary and keyframes, poses_before, poses,
+        landmark_ids, landmarks (FAILURE: everything as it was).  More than 1024 keyframes is MslamHipError(E_CAPACITY),
+        a keyframe the backend does not hold MslamHipError(E_INVALID), both raised before the context is touched."""
+        if len(self.poses) > POSE_GRAPH_MAX_KEYFRAMES:
+            raise MslamHipError(E_CAPACITY, "close_loop: %d keyframes, at most %d per solve" % (len(self.poses), POSE_GRAPH_MAX_KEYFRAMES))
+        if int(cur_id) not in self.poses or int(loop_id) not in self.poses or int(cur_id) == int(loop_id):
+            raise MslamHipError(E_INVALID, "close_loop: keyframes %r and %r must be two keyframes of the backend" % (cur_id, loop_id))
+        ids, poses, fixed, ea, eb, meas, info = self.loop_problem(cur_id, loop_id, rvec, tvec, graph, sqrt_info)
+        res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+        lids = sorted(l for l in self.landmarks if self.anchor.get(l) in self.poses)
+        lm = np.array([self.landmarks[l] for l in lids], np.float64).reshape(-1, 3)
+        if res["termination"] != 2:
+            index = {id: k for k, id in enumerate(ids)}
+            for i, l in enumerate(lids):
+                k = index[self.anchor[l]]
+                local = quaternion_to_rotation(poses[k, :4]).T @ (lm[i] - poses[k, 4:])
+                lm[i] = quaternion_to_rotation(res["poses"][k, :4]) @ local + res["poses"][k, 4:]
+                self.landmarks[l] = lm[i].copy()
+            for k, id in enumerate(ids):
+                self.poses[id] = res["poses"][k].copy()
+        res.update(keyframes=ids, poses_before=poses, landmark_ids=np.array(lids, np.int64), landmarks=lm)
+        return res
+
 
 class HipKeyframeTracker:
     """The reference front end's loop over frames (RgbdFeatureFrontend::processSensorData, rgbd_feature_frontend.cpp:185-222)
@@ -1208,17 +1322,47 @@ class HipKeyframeTracker:
     guided_radius = r (> 0): Context.set_guided_match(r, guided_max_distance) with the context's frame size — every track
     call here has a guess, so every one of them matches each landmark within r px of its projection under the previous
     pose (DEVIATES: the reference matches brute force); the relocalisation after a failure has no guess and matches brute
-    force.  With process_window the radius has to cover the motion across a window.  None leaves the context's mode alone."""
+    force.  With process_window the radius has to cover the motion across a window.  None leaves the context's mode alone.
+
+    loop_closure = True (needs local_ba and a vocabulary loaded into the context, else MslamHipError(E_INVALID)): the call
+    site rgbd_feature_frontend.cpp:198-205, `loopDetector->detectLoop(); closeLoop(candidate)`, with the body the reference
+    leaves empty.  At every keyframe, after the covisibility edges and local BA: Context.bow_db_query of the frame's
+    descriptors, then bow_db_add (self._bow_entry maps the database's entries to keyframes).  Candidates are the hits with a
+    score >= loop_min_score whose keyframe is at least loop_min_gap keyframes older than the new one and not in
+    self.neighbours(new_id), and only when the last closure is at least loop_min_gap keyframes back.  Context.relocalize,
+    without a guess and with min_inliers = loop_min_inliers, verifies at most loop_max_candidates of them (best score
+    first).  On a winner: HipBackend.close_loop, Context.kf_update_world with the moved landmarks, the tracker's pose becomes
+    the corrected pose of the new keyframe, the local map is rebuilt, and with loop_global_ba HipBackend.global_ba and
+    kf_update_world follow.  self.loop_results holds every attempt; the frame's dict gains loop = (cur, loop) or None.
+    DELIBERATELY OUT: landmark fusion (giving the new keyframe's matched landmarks the old keyframe's ids), so no covisibility
+    edge joins the two keyframes and the loop is known to the pose graph of that one call only."""
 
     LOCAL_MAP_ID = 0x7fffffff
+    LOOP_QUERY_RESULTS = 64    # hits asked of the database before the filters: the newest keyframes fill the top of the list
 
     def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
                  reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
-                 reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False):
+                 reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False,
+                 loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
+                 loop_global_ba=False):
         self.ctx = ctx
         if local_ba and local_map_depth is None:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: local_ba needs local_map_depth (the covisibility graph)")
-        self.backend = HipBackend(ctx) if local_ba else None
+        if loop_closure:
+            if not local_ba:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_closure needs local_ba (the backend holds the poses)")
+            try:
+                ctx.bow_info()
+            except MslamHipError:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_closure needs a vocabulary (Context.bow_load)")
+        self.loop_closure, self.loop_min_score, self.loop_min_gap = bool(loop_closure), float(loop_min_score), int(loop_min_gap)
+        self.loop_min_inliers, self.loop_max_candidates = int(loop_min_inliers), int(loop_max_candidates)
+        self.loop_global_ba = bool(loop_global_ba)
+        self.loop_results = []
+        self._bow_entry = {}         # BoW database entry -> keyframe id
+        self._last_closure = None    # the keyframe at which the last loop was closed
+        # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
+        self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba)) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)
@@ -1249,8 +1393,11 @@ class HipKeyframeTracker:
                 self.backend.add_keyframe(0, (0, 0, 0, 1, 0, 0, 0), self.ctx.kf_read_ids(0), xyz[keep])
             self.ids, self.reference = [0], 0
             self.graph = {0: set()}
-            return dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
-                        keyframe=0, relocalized=False, step=None)
+            first = dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
+                         keyframe=0, relocalized=False, step=None)
+            if self.loop_closure:
+                first["loop"] = self._close_loops(0, desc, xy, seed)
+            return first
         vote = self.ids[-64:]
         new_id = self.ids[-1] + 1
         ref_id, rebuilt = self.reference, False
@@ -1282,11 +1429,15 @@ class HipKeyframeTracker:
                     self._local_map_of = None   # a keyframe was added: the local map is rebuilt
                     if self.backend is not None:
                         self._local_ba(new_id, res, xy, depth)
+                    if self.loop_closure:
+                        out["loop"] = self._close_loops(new_id, desc, xy, seed)
         else:
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
             if reloc["best"] >= 0:
                 self.reference, out["relocalized"] = vote[reloc["best"]], True
+        if self.loop_closure:
+            out.setdefault("loop", None)
         out.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
         return out
 
@@ -1340,12 +1491,16 @@ class HipKeyframeTracker:
                         o["keyframe"] = new_id
                         if self.backend is not None:
                             self._local_ba(new_id, res, xys[i + s], depths[i + s])
+                        if self.loop_closure:
+                            o["loop"] = self._close_loops(new_id, descs[i + s], xys[i + s], seed + s)
                 else:
                     reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
                                                 self.iterations, self.reprojection_error, seed + s,
                                                 min_inliers=self.reloc_min_inliers)
                     if reloc["best"] >= 0:
                         self.reference, o["relocalized"] = vote[reloc["best"]], True
+                if self.loop_closure:
+                    o.setdefault("loop", None)
                 o.update(rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=self.reference)
                 out.append(o)
             self.frame += n_acc
@@ -1376,6 +1531,51 @@ class HipKeyframeTracker:
         if ba["termination"] != 2:
             ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
         self.ba_results.append(ba)
+
+    def loop_candidates(self, new_id, entries, scores):
+        """the filters between the database's hits and the verification -> keyframe ids, best score first, at most
+        loop_max_candidates: score >= loop_min_score; at least loop_min_gap keyframes older than new_id; not in
+        self.neighbours(new_id); none at all while the last closure is fewer than loop_min_gap keyframes back"""
+        if self._last_closure is not None and new_id - self._last_closure < self.loop_min_gap:
+            return []
+        near = set(self.neighbours(new_id))
+        hits = sorted(((float(s), self._bow_entry[int(e)]) for e, s in zip(entries, scores) if int(e) in self._bow_entry),
+                      key=lambda h: (-h[0], h[1]))
+        return [k for s, k in hits if s >= self.loop_min_score and new_id - k >= self.loop_min_gap and k not in near][:self.loop_max_candidates]
+
+    def _close_loops(self, new_id, desc, xy, seed):
+        """detectLoop and closeLoop for the keyframe just added -> (new_id, loop keyframe) or None.  An attempt (a verification
+        that ran) is appended to self.loop_results: keyframe, candidates, inliers, loop = the verified keyframe or None, and
+        for a verified one the PnP pose, close_loop's result (termination 2: nothing was corrected) and global_ba's"""
+        entries, scores = self.ctx.bow_db_query(desc, max_results=self.LOOP_QUERY_RESULTS)
+        self._bow_entry[self.ctx.bow_db_add(desc)] = new_id
+        cands = self.loop_candidates(new_id, entries, scores)
+        if not cands:
+            return None
+        reloc = self.ctx.relocalize(desc, xy, cands, self.focal, self.principal, None, self.ratio, self.iterations,
+                                    self.reprojection_error, seed, min_inliers=self.loop_min_inliers)
+        attempt = dict(keyframe=new_id, candidates=list(cands), inliers=[c["n_inliers"] for c in reloc["candidates"]], loop=None)
+        self.loop_results.append(attempt)
+        if reloc["best"] < 0:
+            return None
+        loop_id, win = cands[reloc["best"]], reloc["candidates"][reloc["best"]]
+        res = self.backend.close_loop(new_id, loop_id, win["rvec"], win["tvec"], self.graph)
+        attempt.update(loop=loop_id, rvec=win["rvec"], tvec=win["tvec"], result=res)
+        if res["termination"] == 2:
+            return None
+        res["n_written"] = self.ctx.kf_update_world(res["landmark_ids"], res["landmarks"])
+        pose = self.backend.poses[new_id]                   # camera -> world; the tracker's pose is world -> camera
+        self.R = quaternion_to_rotation(pose[:4]).T
+        self.tvec = -self.R @ pose[4:]
+        self.rvec = rotation_to_rvec(self.R)
+        self._local_map_of = None
+        self._last_closure = new_id
+        if self.loop_global_ba:
+            ba = self.backend.global_ba()
+            if ba["termination"] != 2:
+                ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
+            attempt["global_ba"] = ba
+        return (new_id, loop_id)
 
     def neighbours(self, ref):
         """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than

@@ -157,6 +157,9 @@ struct mslam_hip_ctx
     // the padded dense reduced system of mslam_hip_bundle_adjust_global, an owner of its own: a global solve leaves d_ba,
     // which the local solve sizes, as small as the local solve needs it
     mslam::DevBuf<double> d_ba_S;
+    // pose-graph optimisation (mslam_hip_pose_graph, k_posegraph.hip), grown on demand: every device array of one solve but
+    // the normal equations, which live in d_ba_S; the termination word is h_ba
+    mslam::DevBuf<uint8_t> d_pg;
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

@@ -31,7 +31,7 @@
 // state has not moved, so the block kernels reuse what they stored and only the damping is redone.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
-#include "context.hpp"
+#include "ba_solver.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -45,7 +45,6 @@ namespace mslam
 
 constexpr int kBaMaxKeyframes = 64;
 constexpr int kBagMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES; // mslam_hip_bundle_adjust_global: 6144^2 doubles = 302 MB
-constexpr int kBagNB = 48; // panel width of the blocked factor: 8 keyframe blocks, 3 MFMA tiles
 constexpr int kBaSolveThreads = 6 * kBaMaxKeyframes; // one thread per row of the reduced system
 constexpr int kBaBatch = 4;                          // iterations enqueued between two looks at the termination word
 constexpr int kBaMaxInvalidSteps = 5;
@@ -54,37 +53,6 @@ constexpr double kBaMinDiagonal = 1e-6, kBaMaxDiagonal = 1e32;
 constexpr double kBaMinRelativeDecrease = 1e-3;
 constexpr double kBaFunctionTol = 1e-6, kBaGradientTol = 1e-10, kBaParameterTol = 1e-8;
 constexpr int kBaConvergence = 0, kBaNoConvergence = 1, kBaFailure = 2;
-
-struct BaCtrl
-{
-    int32_t done, termination, iteration, need_jac, first, successful, invalid_run, solve_bad;
-    int32_t rejected, invalid_total, max_iterations, pad;
-    double radius, decrease_factor, x_cost, initial_cost;
-};
-
-struct BaArgs
-{
-    int K, L, M, n;     // n = 6 x (free keyframes with observations): the reduced system's size
-    int n_pairs, n_blocks; // pairs of free keyframes; blocks of k_ba_eval
-    int n_pad, ld;         // the blocked solver: n rounded up to kBagNB; leading dimension n_pad + 16 (row n_pad: the right-hand side)
-    // the problem
-    const int32_t *obs_kf, *obs_lm;
-    const double* obs_cam;
-    const int32_t *lm_ptr, *lm_obs;         // observations by landmark (rows in input order)
-    const int32_t *kf_ptr, *kf_obs, *kf_lm; // observations by keyframe, every row sorted by landmark; kf_lm = the landmark
-    const int32_t* ci;                      // [K] the keyframe's block in the reduced system, -1: constant or unobserved
-    const int32_t* pairs;                   // [n_pairs][2] keyframes k1, k2 with ci[k1] <= ci[k2]
-    const uint8_t* lm_active;               // [L] the landmark has an observation
-    // state and candidate
-    double *pose, *lm, *cand_pose, *cand_lm;
-    // blocks
-    double *V, *gl, *Vinv, *sl; // [L] x 6, 3, 6, 3
-    double *U, *gc, *sc, *W;    // [K] x 21, 6, 6; [M] x 18
-    double *S, *rhs, *yc, *yl;  // n x n column-major, n, n, [L] x 3
-    double* part;               // [2][n_blocks]: model cost change, candidate cost
-    BaCtrl* ctrl;
-    int32_t* h_done; // mapped
-};
 
 __device__ __forceinline__ double ba_wave_sum(double s)
 {
@@ -998,6 +966,33 @@ __global__ __launch_bounds__(256) void k_ba_outliers(BaArgs a, const double* __r
     out[m] = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) > threshold2 ? 1 : 0;
 }
 
+// ba_solver.hpp: the blocked solve of mslam_hip_bundle_adjust_global and of mslam_hip_pose_graph (k_posegraph.hip)
+void ba_blocked_solve(mslam_hip_ctx* c, const BaArgs& a, hipStream_t s, const std::function<void()>& assemble)
+{
+    const int np = a.n_pad / kBagNB;
+    {
+        StageScope tk(c, "solver_schur");
+        hipLaunchKernelGGL(k_bag_clear, dim3((unsigned)a.n_pad), dim3(256), 0, s, a);
+        assemble();
+    }
+    {
+        StageScope tk(c, "solver_factor");
+        for(int j = 0; j < np; ++j)
+        {
+            hipLaunchKernelGGL(k_bag_potrf, dim3(1), dim3(64), 0, s, a, j);
+            hipLaunchKernelGGL(k_bag_trsm, dim3((unsigned)((a.ld - (j + 1) * kBagNB + 63) / 64)), dim3(64), 0, s, a, j);
+            if(j + 1 < np)
+            {
+                const unsigned t = (unsigned)(np - j - 1); // column blocks right of the panel
+                hipLaunchKernelGGL(k_bag_update, dim3(t * (t + 1) / 2 + t), dim3(64), 0, s, a, j);
+            }
+        }
+    }
+    StageScope tk(c, "solver_subst");
+    for(int j = np - 1; j >= 0; --j)
+        hipLaunchKernelGGL(k_bag_backsolve, dim3((unsigned)(j + 1)), dim3(64), 0, s, a, j);
+}
+
 } // namespace mslam
 
 using namespace mslam;
@@ -1188,28 +1183,7 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
             else if(a.n_pairs > 0)
             {
                 // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
-                const int np = a.n_pad / kBagNB;
-                {
-                    StageScope tk(c, "solver_schur");
-                    hipLaunchKernelGGL(k_bag_clear, dim3((unsigned)a.n_pad), dim3(256), 0, s, a);
-                    hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
-                }
-                {
-                    StageScope tk(c, "solver_factor");
-                    for(int j = 0; j < np; ++j)
-                    {
-                        hipLaunchKernelGGL(k_bag_potrf, dim3(1), dim3(64), 0, s, a, j);
-                        hipLaunchKernelGGL(k_bag_trsm, dim3((unsigned)((a.ld - (j + 1) * kBagNB + 63) / 64)), dim3(64), 0, s, a, j);
-                        if(j + 1 < np)
-                        {
-                            const unsigned t = (unsigned)(np - j - 1); // column blocks right of the panel
-                            hipLaunchKernelGGL(k_bag_update, dim3(t * (t + 1) / 2 + t), dim3(64), 0, s, a, j);
-                        }
-                    }
-                }
-                StageScope tk(c, "solver_subst");
-                for(int j = np - 1; j >= 0; --j)
-                    hipLaunchKernelGGL(k_bag_backsolve, dim3((unsigned)(j + 1)), dim3(64), 0, s, a, j);
+                ba_blocked_solve(c, a, s, [&] { hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
             }
             hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
             hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);

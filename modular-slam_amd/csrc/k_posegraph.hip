@@ -1,0 +1,800 @@
+// k_posegraph.hip — pose-graph optimisation: the body of RgbdFeatureFrontend::closeLoop (reference
+// rgbd_feature_frontend.cpp:577-580, empty there; the call site is :198-205).
+//
+// Levenberg-Marquardt over keyframe poses (q, p; camera -> world) of cost = 1/2 sum_e |r_e|^2 with, for the edge e = (a, b)
+// and its measurement (q_meas, p_meas) = pose b expressed in a's frame, the error term of Ceres's published pose_graph_3d
+// example (pose_graph_3d_error_term.h):
+//     p_ab = rot(q_a^-1, p_b - p_a)     q_ab = q_a^-1 (x) q_b     delta = q_meas (x) q_ab^-1
+//     r_e  = sqrt_info_e [p_ab - p_meas ; 2 vec(delta)]
+// No sign fix is applied on delta: a measurement entered as -q_meas, or a pose as -q, turns vec(delta) round.  Inverses are
+// Eigen's inverse() (conjugate / squared norm), products Eigen's quaternion product, as in k_ba.hip.
+// The trust-region loop is the one k_ba.hip restates from k_pnp_mse.hip (Ceres 2.2's trust_region_minimizer.cc,
+// levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc, the Solver::Options defaults of solver.h); it is restated
+// here once more, without the landmarks.  The SAME / DEVIATES table is in include/mslam_hip.h, the walk-through in DESIGN.md
+// 4.17.  PARITY UNPINNED: no Ceres build exists here; tests/pose_graph_ref.py restates the algorithm in numpy (jets, two
+// linear solvers).
+//
+// A free pose has the tangent (delta, dp) of k_ba.hip: Plus = q_delta (x) q and the position.  With R_a^T the matrix of
+// v -> rot(q_a^-1, v), v = p_b - p_a, and M the 3 x 3 matrix of u -> vec(A (x) (u, 0) (x) B), A = q_meas (x) q_b^-1, B = q_a
+// (delta moves by A (x) (d_a - d_b, 0) (x) B to first order), the unweighted derivatives of [p_ab ; 2 vec(delta)] are
+//     pose a: [ 2 R_a^T [v]x   -R_a^T ]        pose b: [  0     R_a^T ]
+//             [ 2 M             0     ]                [ -2 M   0     ]
+// and the edge's Jacobians are sqrt_info times these.
+//
+// One trust-region iteration on the context's stream; every launch reads the control block first and returns when the solve
+// has ended, so the host enqueues iterations ahead and looks at a mapped word between batches:
+//   k_pg_edges      a lane per edge: r_e and the two 6 x 6 tangent Jacobians (skipped after a rejected step: the state has
+//                   not moved)
+//   k_pg_poses      a wave per free pose: U_k = sum J^T J (21 entries) and g_k = sum J^T r over the pose's incidence list
+//                   (edge order, built on the host) by lane stride, then a fixed butterfly; the column scaling at the first pass
+//   k_pg_check      one wave: FinalizeIterationAndCheckIfMinimizerCanContinue
+//   ba_blocked_solve (ba_solver.hpp): k_bag_clear; k_pg_assemble — a wave per unique sorted pair (i <= j) of free poses: the
+//                   diagonal pair writes the scaled U_i with the damping and the scaled gradient into the right-hand-side row,
+//                   an off-diagonal pair sums J_i^T J_j over the edges the host listed for it, in that order (a serial loop
+//                   of one wave: the slow shape when thousands of duplicate edges join one pair), lane (r, c)
+//                   keeping entry (r, c), and writes the scaled block into the lower triangle; the blocked Cholesky, the
+//                   back-substitution
+//   k_pg_candidate  Plus on every pose
+//   k_pg_eval       a lane per edge: the model cost change -(J_s s) . (f + J_s s / 2) and the cost at the candidate, summed per
+//                   block by a fixed tree
+//   k_pg_control    one wave: sums the block partials in a fixed order, step validity, parameter / function tolerance,
+//                   accept or reject, radius
+// No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
+// another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
+#include "ba_solver.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace mslam
+{
+
+constexpr int kPgMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES;
+constexpr int kPgMaxEdges = MSLAM_HIP_POSE_GRAPH_MAX_EDGES;
+constexpr int kPgBatch = 4; // iterations enqueued between two looks at the termination word
+constexpr int kPgMaxInvalidSteps = 5;
+constexpr double kPgInitialRadius = 1e4, kPgMaxRadius = 1e16, kPgMinRadius = 1e-32;
+constexpr double kPgMinDiagonal = 1e-6, kPgMaxDiagonal = 1e32;
+constexpr double kPgMinRelativeDecrease = 1e-3;
+constexpr double kPgFunctionTol = 1e-6, kPgGradientTol = 1e-10, kPgParameterTol = 1e-8;
+constexpr int kPgConvergence = 0, kPgNoConvergence = 1, kPgFailure = 2;
+
+struct PgArgs
+{
+    int K, E, n;           // n = 6 x (free poses with an edge): the size of the normal equations
+    int n_pairs, n_blocks; // pairs of free poses; blocks of k_pg_eval
+    int n_pad, ld;         // as BaArgs: n rounded up to kBagNB; leading dimension n_pad + 16 (row n_pad: the right-hand side)
+    // the problem
+    const int32_t *ea, *eb; // [E]
+    const double* meas;     // [E] x 7: q then p
+    const double* info;     // [E] x 36 row-major, nullptr: identity
+    const int32_t *inc_ptr, *inc; // incidences by pose, in edge order: 2 e + (0: the pose is the edge's a, 1: its b)
+    const int32_t* ci;            // [K] the pose's block in the normal equations, -1: constant or without an edge
+    const int32_t* pairs;         // [n_pairs][2] poses k1 <= k2, sorted
+    const int32_t *pair_ptr, *pair_edge; // the edges between k1 and k2, in edge order (none for k1 == k2)
+    // state and candidate
+    double *pose, *cand;
+    // blocks
+    double *r, *J;       // [E] x 6; [E] x 72: J_a then J_b, 6 x 6 row-major
+    double *U, *gc, *sc; // [K] x 21, 6, 6
+    double *S, *yc;      // the padded normal equations (the context's d_ba_S); the solution, n
+    double* part;        // [2][n_blocks]: model cost change, candidate cost
+    BaCtrl* ctrl;
+    int32_t* h_done; // mapped
+};
+
+__device__ __forceinline__ double pg_wave_sum(double s)
+{
+    for(int m = 32; m >= 1; m >>= 1)
+        s += __shfl_xor(s, m, 64);
+    return s;
+}
+__device__ __forceinline__ double pg_wave_max(double s)
+{
+    for(int m = 32; m >= 1; m >>= 1)
+        s = fmax(s, __shfl_xor(s, m, 64));
+    return s;
+}
+__device__ __forceinline__ int pg_tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c < 6
+
+// Eigen's inverse(): conjugate / squared norm
+__device__ __forceinline__ void pg_inverse(const double* __restrict__ q, double qi[4])
+{
+    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    qi[0] = -q[0] / n2, qi[1] = -q[1] / n2, qi[2] = -q[2] / n2, qi[3] = q[3] / n2;
+}
+// Eigen's quaternion product (x y z w)
+__device__ __forceinline__ void pg_product(const double a[4], const double b[4], double out[4])
+{
+    out[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    out[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    out[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    out[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+}
+// Eigen's _transformVector: v + w uv + u x uv, uv = 2 (u x v)
+__device__ __forceinline__ void pg_rotate(const double qi[4], const double v[3], double out[3])
+{
+    double uv[3] = {qi[1] * v[2] - qi[2] * v[1], qi[2] * v[0] - qi[0] * v[2], qi[0] * v[1] - qi[1] * v[0]};
+    uv[0] += uv[0], uv[1] += uv[1], uv[2] += uv[2];
+    out[0] = v[0] + qi[3] * uv[0] + (qi[1] * uv[2] - qi[2] * uv[1]);
+    out[1] = v[1] + qi[3] * uv[1] + (qi[2] * uv[0] - qi[0] * uv[2]);
+    out[2] = v[2] + qi[3] * uv[2] + (qi[0] * uv[1] - qi[1] * uv[0]);
+}
+// the matrix of v -> pg_rotate(qi, v), row-major
+__device__ __forceinline__ void pg_matrix(const double qi[4], double Rt[9])
+{
+    const double x = qi[0], y = qi[1], z = qi[2], w = qi[3];
+    const double xx = x * x, yy = y * y, zz = z * z;
+    Rt[0] = 1.0 - 2.0 * (yy + zz), Rt[1] = 2.0 * (x * y - w * z), Rt[2] = 2.0 * (x * z + w * y);
+    Rt[3] = 2.0 * (x * y + w * z), Rt[4] = 1.0 - 2.0 * (xx + zz), Rt[5] = 2.0 * (y * z - w * x);
+    Rt[6] = 2.0 * (x * z - w * y), Rt[7] = 2.0 * (y * z + w * x), Rt[8] = 1.0 - 2.0 * (xx + yy);
+}
+// EigenQuaternionManifold::Plus (manifold.h QuaternionPlus, x y z w): q_delta (x) q
+__device__ __forceinline__ void pg_quaternion_plus(const double* __restrict__ q, const double d[3], double out[4])
+{
+    const double norm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if(!(norm > 0.0))
+    {
+        out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
+        return;
+    }
+    const double sbd = sin(norm) / norm;
+    const double ax = sbd * d[0], ay = sbd * d[1], az = sbd * d[2], aw = cos(norm);
+    out[0] = aw * q[0] + ax * q[3] + ay * q[2] - az * q[1];
+    out[1] = aw * q[1] + ay * q[3] + az * q[0] - ax * q[2];
+    out[2] = aw * q[2] + az * q[3] + ax * q[1] - ay * q[0];
+    out[3] = aw * q[3] - ax * q[0] - ay * q[1] - az * q[2];
+}
+
+// entry (i, k) of the edge's sqrt_info
+__device__ __forceinline__ double pg_info(const double* __restrict__ info, int i, int k)
+{
+    return info ? info[i * 6 + k] : (i == k ? 1.0 : 0.0);
+}
+
+// u = [p_ab - p_meas ; 2 vec(delta)], the unweighted error of edge e at the poses xa, xb
+__device__ __forceinline__ void pg_error(const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ z, double u[6])
+{
+    double qai[4], qab[4], qabi[4], dq[4], pab[3];
+    pg_inverse(xa, qai);
+    const double v[3] = {xb[4] - xa[4], xb[5] - xa[5], xb[6] - xa[6]};
+    pg_rotate(qai, v, pab);
+    const double qb[4] = {xb[0], xb[1], xb[2], xb[3]}, qm[4] = {z[0], z[1], z[2], z[3]};
+    pg_product(qai, qb, qab);
+    pg_inverse(qab, qabi);
+    pg_product(qm, qabi, dq);
+    u[0] = pab[0] - z[4], u[1] = pab[1] - z[5], u[2] = pab[2] - z[6];
+    u[3] = 2.0 * dq[0], u[4] = 2.0 * dq[1], u[5] = 2.0 * dq[2];
+}
+__device__ __forceinline__ void pg_residual(const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ z,
+                                            const double* __restrict__ info, double r[6])
+{
+    double u[6];
+    pg_error(xa, xb, z, u);
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+    {
+        double s = 0.0;
+#pragma unroll
+        for(int k = 0; k < 6; ++k)
+            s += pg_info(info, i, k) * u[k];
+        r[i] = s;
+    }
+}
+
+// ---- blocks ------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_pg_edges(PgArgs a)
+{
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done || !ct->need_jac)
+        return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if(e >= a.E)
+        return;
+    const double* xa = a.pose + (size_t)a.ea[e] * 7;
+    const double* xb = a.pose + (size_t)a.eb[e] * 7;
+    const double* z = a.meas + (size_t)e * 7;
+    const double* info = a.info ? a.info + (size_t)e * 36 : nullptr;
+    double r[6];
+    pg_residual(xa, xb, z, info, r);
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+        a.r[(size_t)e * 6 + i] = r[i];
+    // P = R_a^T, G = 2 P [v]x, M2 = 2 M
+    double qai[4], qbi[4], A[4], P[9], G[9], M2[9];
+    pg_inverse(xa, qai);
+    pg_inverse(xb, qbi);
+    pg_matrix(qai, P);
+    const double v[3] = {xb[4] - xa[4], xb[5] - xa[5], xb[6] - xa[6]};
+    const double vx[9] = {0.0, -v[2], v[1], v[2], 0.0, -v[0], -v[1], v[0], 0.0};
+#pragma unroll
+    for(int i = 0; i < 3; ++i)
+#pragma unroll
+        for(int j = 0; j < 3; ++j)
+            G[i * 3 + j] = 2.0 * (P[i * 3] * vx[j] + P[i * 3 + 1] * vx[3 + j] + P[i * 3 + 2] * vx[6 + j]);
+    const double qm[4] = {z[0], z[1], z[2], z[3]}, B[4] = {xa[0], xa[1], xa[2], xa[3]};
+    pg_product(qm, qbi, A);
+#pragma unroll
+    for(int j = 0; j < 3; ++j)
+    {
+        const double ej[4] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, 0.0};
+        double t[4], w[4];
+        pg_product(A, ej, t);
+        pg_product(t, B, w);
+        M2[j] = 2.0 * w[0], M2[3 + j] = 2.0 * w[1], M2[6 + j] = 2.0 * w[2];
+    }
+    double* Ja = a.J + (size_t)e * 72;
+    double* Jb = Ja + 36;
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+    {
+        const double w0 = pg_info(info, i, 0), w1 = pg_info(info, i, 1), w2 = pg_info(info, i, 2);
+        const double w3 = pg_info(info, i, 3), w4 = pg_info(info, i, 4), w5 = pg_info(info, i, 5);
+#pragma unroll
+        for(int j = 0; j < 3; ++j)
+        {
+            const double wp = w0 * P[j] + w1 * P[3 + j] + w2 * P[6 + j];
+            const double wm = w3 * M2[j] + w4 * M2[3 + j] + w5 * M2[6 + j];
+            Ja[i * 6 + j] = (w0 * G[j] + w1 * G[3 + j] + w2 * G[6 + j]) + wm;
+            Ja[i * 6 + 3 + j] = -wp;
+            Jb[i * 6 + j] = -wm;
+            Jb[i * 6 + 3 + j] = wp;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pg_poses(PgArgs a)
+{
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done || !ct->need_jac)
+        return;
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if(a.ci[k] < 0)
+        return;
+    double acc[27];
+#pragma unroll
+    for(int j = 0; j < 27; ++j)
+        acc[j] = 0.0;
+    for(int pos = a.inc_ptr[k] + lane; pos < a.inc_ptr[k + 1]; pos += 64)
+    {
+        const int code = a.inc[pos];
+        const double* Jp = a.J + (size_t)(code >> 1) * 72 + (code & 1) * 36;
+        const double* rp = a.r + (size_t)(code >> 1) * 6;
+        double J[36], r[6];
+#pragma unroll
+        for(int j = 0; j < 36; ++j)
+            J[j] = Jp[j];
+#pragma unroll
+        for(int j = 0; j < 6; ++j)
+            r[j] = rp[j];
+        int j = 0;
+#pragma unroll
+        for(int rr = 0; rr < 6; ++rr)
+#pragma unroll
+            for(int c = rr; c < 6; ++c)
+            {
+                double s = 0.0;
+#pragma unroll
+                for(int i = 0; i < 6; ++i)
+                    s += J[i * 6 + rr] * J[i * 6 + c];
+                acc[j++] += s;
+            }
+#pragma unroll
+        for(int rr = 0; rr < 6; ++rr)
+        {
+            double s = 0.0;
+#pragma unroll
+            for(int i = 0; i < 6; ++i)
+                s += J[i * 6 + rr] * r[i];
+            acc[21 + rr] += s;
+        }
+    }
+#pragma unroll
+    for(int j = 0; j < 27; ++j)
+        acc[j] = pg_wave_sum(acc[j]);
+    if(lane == 0)
+    {
+#pragma unroll
+        for(int j = 0; j < 21; ++j)
+            a.U[(size_t)k * 21 + j] = acc[j];
+#pragma unroll
+        for(int j = 0; j < 6; ++j)
+            a.gc[(size_t)k * 6 + j] = acc[21 + j];
+        if(ct->first)
+        {
+            int d = 0;
+#pragma unroll
+            for(int j = 0; j < 6; ++j)
+            {
+                a.sc[(size_t)k * 6 + j] = 1.0 / (1.0 + sqrt(acc[d]));
+                d += 6 - j;
+            }
+        }
+    }
+}
+
+// ---- FinalizeIterationAndCheckIfMinimizerCanContinue: one wave ------------------------------------------------------------
+
+__device__ __forceinline__ void pg_finish(const PgArgs& a, int lane, int termination)
+{
+    if(lane == 0)
+    {
+        a.ctrl->termination = termination;
+        a.ctrl->done = 1;
+        *a.h_done = 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pg_check(PgArgs a)
+{
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    double x_cost = ct->x_cost;
+    if(ct->first)
+    {
+        // iteration 0: the cost at the start, from k_pg_eval's block partials
+        double s = 0.0;
+        for(int b = lane; b < a.n_blocks; b += 64)
+            s += a.part[a.n_blocks + b];
+        x_cost = pg_wave_sum(s);
+    }
+    // the evaluation is usable (seen through the sums, as in k_ba.hip), and |x - Plus(x, -g)|_inf over the ambient parameters
+    bool ok = isfinite(x_cost);
+    double gmax = 0.0;
+    for(int k = lane; k < a.K; k += 64)
+    {
+        if(a.ci[k] < 0)
+            continue;
+        const double* q = a.pose + (size_t)k * 7;
+        const double* g = a.gc + (size_t)k * 6;
+        const double md[3] = {-g[0], -g[1], -g[2]};
+        double qp[4];
+        pg_quaternion_plus(q, md, qp);
+        for(int j = 0; j < 4; ++j)
+            gmax = fmax(gmax, fabs(q[j] - qp[j]));
+        for(int j = 0; j < 3; ++j)
+            gmax = fmax(gmax, fabs(q[4 + j] - (q[4 + j] + (-g[3 + j]))));
+        for(int j = 0; j < 6; ++j)
+            ok = ok && isfinite(g[j]) && isfinite(a.U[(size_t)k * 21 + pg_tri(j, j)]);
+    }
+    gmax = pg_wave_max(gmax);
+    ok = __all(ok);
+    if(lane == 0 && ct->first)
+        ct->x_cost = ct->initial_cost = x_cost;
+    if(!ok)
+        return pg_finish(a, lane, kPgFailure);
+    if(ct->iteration >= ct->max_iterations)
+        return pg_finish(a, lane, kPgNoConvergence);
+    if(ct->successful && gmax <= kPgGradientTol)
+        return pg_finish(a, lane, kPgConvergence);
+    if(ct->radius <= kPgMinRadius)
+        return pg_finish(a, lane, kPgConvergence);
+    if(lane == 0)
+    {
+        ct->iteration += 1;
+        ct->successful = 0;
+        ct->first = 0;
+        ct->solve_bad = 0;
+    }
+}
+
+// ---- the normal equations: a wave per pair of free poses ------------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
+{
+    const BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    const int k1 = a.pairs[blockIdx.x * 2], k2 = a.pairs[blockIdx.x * 2 + 1];
+    const size_t b1 = (size_t)a.ci[k1], b2 = (size_t)a.ci[k2], ld = (size_t)a.ld;
+    if(k1 == k2)
+    {
+        if(lane < 36)
+        {
+            const int r = lane / 6, c = lane % 6;
+            const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? pg_tri(r, c) : pg_tri(c, r))] * a.sc[(size_t)k1 * 6 + c];
+            a.S[(b1 * 6 + r) + (b1 * 6 + c) * ld] = r == c ? u + fmin(fmax(u, kPgMinDiagonal), kPgMaxDiagonal) / ct->radius : u;
+        }
+        else if(lane < 42)
+        {
+            const int r = lane - 36;
+            a.S[(size_t)a.n_pad + (b1 * 6 + r) * ld] = a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r];
+        }
+        return;
+    }
+    if(lane >= 36)
+        return;
+    // entry (r, c) of sum_e J_k1^T J_k2, in the order of the pair's list; its transpose's place is in the lower triangle
+    const int r = lane / 6, c = lane % 6;
+    double s = 0.0;
+    for(int pos = a.pair_ptr[blockIdx.x]; pos < a.pair_ptr[blockIdx.x + 1]; ++pos)
+    {
+        const int e = a.pair_edge[pos];
+        const bool fwd = a.ea[e] == k1;
+        const double* J1 = a.J + (size_t)e * 72 + (fwd ? 0 : 36);
+        const double* J2 = a.J + (size_t)e * 72 + (fwd ? 36 : 0);
+        double t = 0.0;
+#pragma unroll
+        for(int i = 0; i < 6; ++i)
+            t += J1[i * 6 + r] * J2[i * 6 + c];
+        s += t;
+    }
+    a.S[(b2 * 6 + c) + (b1 * 6 + r) * ld] = a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c];
+}
+
+// delta = step * scaling with step = -y; Plus.  Poses outside the problem are copied.
+__global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
+{
+    if(a.ctrl->done)
+        return;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if(t >= a.K)
+        return;
+    const double* x = a.pose + (size_t)t * 7;
+    double* c = a.cand + (size_t)t * 7;
+    const int bk = a.ci[t];
+    if(bk < 0)
+    {
+        for(int j = 0; j < 7; ++j)
+            c[j] = x[j];
+        return;
+    }
+    const double* y = a.yc + (size_t)bk * 6;
+    const double* sc = a.sc + (size_t)t * 6;
+    const double d[3] = {-y[0] * sc[0], -y[1] * sc[1], -y[2] * sc[2]};
+    double q[4];
+    pg_quaternion_plus(x, d, q);
+    c[0] = q[0], c[1] = q[1], c[2] = q[2], c[3] = q[3];
+    for(int j = 0; j < 3; ++j)
+        c[4 + j] = x[4 + j] + (-y[3 + j] * sc[3 + j]);
+}
+
+// the sum of v over the block, by a fixed tree: butterfly per wave, then the four waves in order; valid in thread 0
+__device__ __forceinline__ double pg_block_sum(double v, double* red)
+{
+    v = pg_wave_sum(v);
+    if((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+    return s;
+}
+
+// the step of pose k in its tangent, 0 for a pose outside the problem
+__device__ __forceinline__ void pg_step(const PgArgs& a, int k, double s[6])
+{
+    const int bk = a.ci[k];
+#pragma unroll
+    for(int j = 0; j < 6; ++j)
+        s[j] = 0.0;
+    if(bk >= 0)
+    {
+#pragma unroll
+        for(int j = 0; j < 6; ++j)
+            s[j] = -a.yc[(size_t)bk * 6 + j] * a.sc[(size_t)k * 6 + j];
+    }
+}
+
+// at_start: only the cost at the state, for iteration 0
+__global__ __launch_bounds__(256) void k_pg_eval(PgArgs a, int at_start)
+{
+    __shared__ double red[4];
+    if(a.ctrl->done)
+        return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    double model = 0.0, cost = 0.0;
+    if(e < a.E)
+    {
+        const int ka = a.ea[e], kb = a.eb[e];
+        const double* z = a.meas + (size_t)e * 7;
+        const double* info = a.info ? a.info + (size_t)e * 36 : nullptr;
+        double r[6];
+        if(at_start)
+            pg_residual(a.pose + (size_t)ka * 7, a.pose + (size_t)kb * 7, z, info, r);
+        else
+        {
+            double sa[6], sb[6];
+            pg_step(a, ka, sa);
+            pg_step(a, kb, sb);
+            const double* Ja = a.J + (size_t)e * 72;
+            const double* f = a.r + (size_t)e * 6;
+#pragma unroll
+            for(int i = 0; i < 6; ++i)
+            {
+                double js = 0.0;
+#pragma unroll
+                for(int j = 0; j < 6; ++j)
+                    js += Ja[i * 6 + j] * sa[j];
+#pragma unroll
+                for(int j = 0; j < 6; ++j)
+                    js += Ja[36 + i * 6 + j] * sb[j];
+                model += js * (f[i] + js / 2.0);
+            }
+            model = -model;
+            pg_residual(a.cand + (size_t)ka * 7, a.cand + (size_t)kb * 7, z, info, r);
+        }
+        cost = 0.5 * (((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]));
+    }
+    const double ms = pg_block_sum(model, red), cs = pg_block_sum(cost, red);
+    if(threadIdx.x == 0)
+    {
+        a.part[blockIdx.x] = ms;
+        a.part[a.n_blocks + blockIdx.x] = cs;
+    }
+}
+
+// ---- the trust-region bookkeeping of one iteration: one wave ----------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_pg_control(PgArgs a)
+{
+    BaCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    double ms = 0.0, cs = 0.0;
+    for(int b = lane; b < a.n_blocks; b += 64)
+        ms += a.part[b], cs += a.part[a.n_blocks + b];
+    const double model_cost_change = pg_wave_sum(ms);
+    double cand_cost = pg_wave_sum(cs);
+    // the step is finite; |x|^2 and |x - candidate|^2 over the ambient parameters of the problem's poses
+    bool finite = true;
+    double xn = 0.0, sn = 0.0;
+    for(int k = lane; k < a.K; k += 64)
+    {
+        const int bk = a.ci[k];
+        if(bk < 0)
+            continue;
+        for(int j = 0; j < 6; ++j)
+            finite = finite && isfinite(a.yc[(size_t)bk * 6 + j]);
+        for(int j = 0; j < 7; ++j)
+        {
+            const double x = a.pose[(size_t)k * 7 + j], d = x - a.cand[(size_t)k * 7 + j];
+            xn += x * x, sn += d * d;
+        }
+    }
+    finite = __all(finite);
+    const double x_norm = sqrt(pg_wave_sum(xn)), step_norm = sqrt(pg_wave_sum(sn));
+    const double x_cost = ct->x_cost;
+    double radius = ct->radius, decrease_factor = ct->decrease_factor;
+    if(!(finite && !ct->solve_bad && model_cost_change > 0.0))
+    {
+        // HandleInvalidStep
+        if(lane == 0)
+            ct->invalid_total += 1;
+        if(ct->invalid_run + 1 >= kPgMaxInvalidSteps)
+            return pg_finish(a, lane, kPgFailure);
+        if(lane == 0)
+        {
+            ct->invalid_run += 1;
+            ct->radius = radius / decrease_factor;
+            ct->decrease_factor = decrease_factor * 2.0;
+            ct->need_jac = 0;
+        }
+        return;
+    }
+    if(!isfinite(cand_cost))
+        cand_cost = DBL_MAX;
+    if(lane == 0)
+        ct->invalid_run = 0;
+    if(step_norm <= kPgParameterTol * (x_norm + kPgParameterTol))
+        return pg_finish(a, lane, kPgConvergence);
+    if(fabs(x_cost - cand_cost) <= kPgFunctionTol * x_cost)
+        return pg_finish(a, lane, kPgConvergence);
+    const double relative_decrease = cand_cost >= DBL_MAX ? -DBL_MAX : (x_cost - cand_cost) / model_cost_change;
+    if(relative_decrease > kPgMinRelativeDecrease)
+    {
+        for(int k = lane; k < a.K; k += 64)
+            if(a.ci[k] >= 0)
+                for(int j = 0; j < 7; ++j)
+                    a.pose[(size_t)k * 7 + j] = a.cand[(size_t)k * 7 + j];
+        if(lane == 0)
+        {
+            const double q = 2.0 * relative_decrease - 1.0;
+            radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
+            ct->radius = fmin(kPgMaxRadius, radius);
+            ct->decrease_factor = 2.0;
+            ct->x_cost = cand_cost;
+            ct->successful = 1;
+            ct->need_jac = 1;
+        }
+    }
+    else if(lane == 0)
+    {
+        ct->rejected += 1;
+        ct->radius = radius / decrease_factor;
+        ct->decrease_factor = decrease_factor * 2.0;
+        ct->need_jac = 0;
+    }
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, const int32_t* edge_a,
+                                    const int32_t* edge_b, const double* edge_meas, const double* sqrt_info, int E,
+                                    int max_iterations, mslam_hip_ba_summary* summary)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(K < 0 || K > kPgMaxKeyframes)
+        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: K outside 0.." + std::to_string(kPgMaxKeyframes));
+    if(E < 0 || E > kPgMaxEdges)
+        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: E outside 0.." + std::to_string(kPgMaxEdges));
+    if(max_iterations < 0 || (K > 0 && !poses) || (E > 0 && (!edge_a || !edge_b || !edge_meas)))
+        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: bad argument (pointers, max_iterations >= 0)");
+    auto unit = [](const double* q) {
+        const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        return std::fabs(norm - 1.0) <= 1e-6;
+    };
+    for(int e = 0; e < E; ++e)
+    {
+        if(edge_a[e] < 0 || edge_a[e] >= K || edge_b[e] < 0 || edge_b[e] >= K)
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: edge " + std::to_string(e) + " names a pose out of range");
+        if(edge_a[e] == edge_b[e])
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: edge " + std::to_string(e) + " joins a pose with itself");
+        if(!unit(edge_meas + (size_t)e * 7))
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: the quaternion of measurement " + std::to_string(e) + " is not unit");
+        if(sqrt_info)
+            for(int j = 0; j < 36; ++j)
+                if(!std::isfinite(sqrt_info[(size_t)e * 36 + j]))
+                    return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: sqrt_info of edge " + std::to_string(e) + " is not finite");
+    }
+    for(int k = 0; k < K; ++k)
+        if(!unit(poses + (size_t)k * 7))
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: the quaternion of pose " + std::to_string(k) + " is not unit");
+    mslam_hip_ba_summary sum{};
+    if(E == 0)
+    {
+        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
+        if(summary)
+            *summary = sum;
+        return MSLAM_HIP_OK;
+    }
+    // incidences by pose in edge order (a stable counting sort), the blocks of the free poses, the pairs with their edges
+    std::vector<int32_t> inc_ptr((size_t)K + 1, 0), inc((size_t)E * 2), ci((size_t)K, -1);
+    for(int e = 0; e < E; ++e)
+        ++inc_ptr[(size_t)edge_a[e] + 1], ++inc_ptr[(size_t)edge_b[e] + 1];
+    for(int k = 0; k < K; ++k)
+        inc_ptr[(size_t)k + 1] += inc_ptr[(size_t)k];
+    {
+        std::vector<int32_t> at(inc_ptr.begin(), inc_ptr.end() - 1);
+        for(int e = 0; e < E; ++e)
+            inc[(size_t)at[(size_t)edge_a[e]]++] = 2 * e, inc[(size_t)at[(size_t)edge_b[e]]++] = 2 * e + 1;
+    }
+    int n_free = 0;
+    for(int k = 0; k < K; ++k)
+        if(!(fixed && fixed[k]) && inc_ptr[(size_t)k + 1] > inc_ptr[(size_t)k])
+            ci[(size_t)k] = n_free++;
+    std::map<std::pair<int, int>, std::vector<int32_t>> by_pair; // sorted by (k1, k2); every list in edge order
+    for(int k = 0; k < K; ++k)
+        if(ci[(size_t)k] >= 0)
+            by_pair[{k, k}];
+    for(int e = 0; e < E; ++e)
+        if(ci[(size_t)edge_a[e]] >= 0 && ci[(size_t)edge_b[e]] >= 0)
+            by_pair[{std::min(edge_a[e], edge_b[e]), std::max(edge_a[e], edge_b[e])}].push_back(e);
+    std::vector<int32_t> pairs, pair_ptr(1, 0), pair_edge;
+    for(const auto& kv : by_pair)
+    {
+        pairs.push_back(kv.first.first), pairs.push_back(kv.first.second);
+        pair_edge.insert(pair_edge.end(), kv.second.begin(), kv.second.end());
+        pair_ptr.push_back((int32_t)pair_edge.size());
+    }
+
+    PgArgs a{};
+    a.K = K, a.E = E, a.n = 6 * n_free;
+    a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (E + 255) / 256;
+    a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
+    // one block: what is uploaded first, then the working arrays
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t n_info = sqrt_info ? (size_t)E * 288 : 0;
+    const size_t o_ctrl = carve(sizeof(BaCtrl)), o_pose = carve((size_t)K * 56), o_meas = carve((size_t)E * 56), o_info = carve(n_info);
+    const size_t o_ea = carve((size_t)E * 4), o_eb = carve((size_t)E * 4), o_iptr = carve(((size_t)K + 1) * 4), o_inc = carve((size_t)E * 8);
+    const size_t o_ci = carve((size_t)K * 4), o_pairs = carve(pairs.size() * 4), o_pptr = carve(pair_ptr.size() * 4);
+    const size_t o_pedge = carve(pair_edge.size() * 4);
+    const size_t up_bytes = off;
+    const size_t o_cand = carve((size_t)K * 56), o_r = carve((size_t)E * 48), o_J = carve((size_t)E * 576);
+    const size_t o_U = carve((size_t)K * 168), o_gc = carve((size_t)K * 48), o_sc = carve((size_t)K * 48), o_yc = carve((size_t)a.n * 8);
+    const size_t o_part = carve((size_t)a.n_blocks * 16);
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, grow(c->d_pg, off, c->stream));
+    if(a.n > 0)
+        MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
+    if(!c->h_ba)
+        MSLAM_CHK(c, c->h_ba.alloc(4));
+    std::vector<uint8_t> stage(up_bytes, 0);
+    BaCtrl ctrl{};
+    ctrl.need_jac = 1, ctrl.first = 1, ctrl.successful = 1, ctrl.max_iterations = max_iterations;
+    ctrl.radius = kPgInitialRadius, ctrl.decrease_factor = 2.0;
+    std::memcpy(&stage[o_ctrl], &ctrl, sizeof(ctrl));
+    auto put = [&](size_t at, const void* src, size_t bytes) {
+        if(bytes)
+            std::memcpy(&stage[at], src, bytes);
+    };
+    put(o_pose, poses, (size_t)K * 56), put(o_meas, edge_meas, (size_t)E * 56), put(o_info, sqrt_info, n_info);
+    put(o_ea, edge_a, (size_t)E * 4), put(o_eb, edge_b, (size_t)E * 4), put(o_iptr, inc_ptr.data(), ((size_t)K + 1) * 4);
+    put(o_inc, inc.data(), (size_t)E * 8), put(o_ci, ci.data(), (size_t)K * 4), put(o_pairs, pairs.data(), pairs.size() * 4);
+    put(o_pptr, pair_ptr.data(), pair_ptr.size() * 4), put(o_pedge, pair_edge.data(), pair_edge.size() * 4);
+    uint8_t* d = c->d_pg;
+    hipStream_t s = c->stream;
+    MSLAM_CHK(c, hipMemcpyAsync(d, stage.data(), up_bytes, hipMemcpyHostToDevice, s));
+    auto dbl = [&](size_t at) { return reinterpret_cast<double*>(d + at); };
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t*>(d + at); };
+    a.ea = i32(o_ea), a.eb = i32(o_eb), a.meas = dbl(o_meas), a.info = sqrt_info ? dbl(o_info) : nullptr;
+    a.inc_ptr = i32(o_iptr), a.inc = i32(o_inc), a.ci = i32(o_ci);
+    a.pairs = i32(o_pairs), a.pair_ptr = i32(o_pptr), a.pair_edge = i32(o_pedge);
+    a.pose = dbl(o_pose), a.cand = dbl(o_cand), a.r = dbl(o_r), a.J = dbl(o_J);
+    a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.S = c->d_ba_S.get(), a.yc = dbl(o_yc), a.part = dbl(o_part);
+    a.ctrl = reinterpret_cast<BaCtrl*>(d + o_ctrl);
+    a.h_done = c->h_ba.dev();
+    *c->h_ba.get() = 0;
+    // what the k_bag_* kernels read of their argument block
+    BaArgs sa{};
+    sa.n = a.n, sa.n_pad = a.n_pad, sa.ld = a.ld, sa.S = a.S, sa.yc = a.yc, sa.ctrl = a.ctrl;
+
+    const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256));
+    {
+        StageScope ts(c, "pg_start_cost");
+        hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
+    }
+    // iteration max_iterations + 1 only reaches k_pg_check, which ends the solve with NO_CONVERGENCE
+    for(long long it = 0; it <= max_iterations;) // a wide counter: max_iterations + 1 must not wrap for INT_MAX
+    {
+        StageScope ts(c, "pg_iterations");
+        for(int b = 0; b < kPgBatch && it <= max_iterations; ++b, ++it)
+        {
+            {
+                StageScope tk(c, "pg_blocks");
+                hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
+                hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
+            }
+            if(a.n_pairs > 0)
+                ba_blocked_solve(c, sa, s, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+            StageScope tk(c, "pg_step");
+            hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
+            hipLaunchKernelGGL(k_pg_control, dim3(1), dim3(64), 0, s, a);
+        }
+        MSLAM_CHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
+            break;
+    }
+    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(!ctrl.done)
+        return fail(c, MSLAM_HIP_E_RUNTIME, "pose_graph: the kernels left no termination");
+    const bool usable = ctrl.termination != kPgFailure;
+    std::vector<double> xp((size_t)K * 7);
+    if(usable)
+    {
+        MSLAM_CHK(c, hipMemcpyAsync(xp.data(), a.pose, (size_t)K * 56, hipMemcpyDeviceToHost, s));
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+    }
+    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
+    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
+    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
+    if(summary)
+        *summary = sum;
+    if(!usable)
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "pose_graph: the minimiser ended in FAILURE (non-finite cost or gradient, or 5 invalid "
+                                             "steps in a row)");
+    std::memcpy(poses, xp.data(), (size_t)K * 56);
+    return MSLAM_HIP_OK;
+}

@@ -33,6 +33,9 @@
 //        mslam_harness <plugin.so> --ba-global <scene>
 //                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
 //                                    keyframe's and landmark's state and the outlier observations
+//        mslam_harness <plugin.so> --pose-graph <scene>
+//                                    ILoopClosingBackend::closeLoop of the same factory's object on one pose-graph scene: the
+//                                    summary, then every keyframe's state
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -209,6 +212,83 @@ int main(int argc, char** argv)
                 std::printf("landmark %zu %.17g %.17g %.17g\n", l, landmarks[l]->state.x(), landmarks[l]->state.y(), landmarks[l]->state.z());
             for(const auto& o : out.outlierObservations)
                 std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--pose-graph") == 0)
+        {
+            // scene file: "MSPG", i32 version (1), K, E, max_iterations, has_info; K x i32 keyframe id; K x 7 f64 state (qx qy qz
+            // qw px py pz); E x i32 a; E x i32 b; E x 7 f64 measurement (q then p of b in a's frame); has_info: E x 36 f64
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[5] = {0, 0, 0, 0, 0};
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            if(!in || std::memcmp(magic, "MSPG", 4) != 0 || head[0] != 1 || head[1] < 0 || head[2] < 0)
+            {
+                std::fprintf(stderr, "%s is not a pose-graph scene\n", argv[3]);
+                return 5;
+            }
+            const std::size_t K = head[1], E = head[2];
+            std::vector<std::int32_t> ids(K), ea(E), eb(E);
+            std::vector<double> poses(7 * K), meas(7 * E), info(head[4] ? 36 * E : 0);
+            in.read(reinterpret_cast<char*>(ids.data()), K * 4);
+            in.read(reinterpret_cast<char*>(poses.data()), K * 56);
+            in.read(reinterpret_cast<char*>(ea.data()), E * 4);
+            in.read(reinterpret_cast<char*>(eb.data()), E * 4);
+            in.read(reinterpret_cast<char*>(meas.data()), E * 56);
+            in.read(reinterpret_cast<char*>(info.data()), info.size() * 8);
+            if(!in)
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                return 5;
+            }
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::vector<std::shared_ptr<Kf>> keyframes;
+            for(std::size_t k = 0; k < K; ++k)
+            {
+                auto kf = std::make_shared<Kf>();
+                const double* v = &poses[7 * k];
+                kf->id = static_cast<mslam::Id>(ids[k]);
+                kf->state.orientation = mslam::Quaternion(v[3], v[0], v[1], v[2]);
+                kf->state.position = mslam::Vector3(v[4], v[5], v[6]);
+                keyframes.push_back(kf);
+            }
+            std::vector<mslam::PoseGraphEdge> edges;
+            for(std::size_t e = 0; e < E; ++e)
+            {
+                if(ea[e] < 0 || static_cast<std::size_t>(ea[e]) >= K || eb[e] < 0 || static_cast<std::size_t>(eb[e]) >= K)
+                {
+                    std::fprintf(stderr, "edge %zu of %s is out of range\n", e, argv[3]);
+                    return 5;
+                }
+                mslam::PoseGraphEdge edge;
+                const double* v = &meas[7 * e];
+                edge.a = keyframes[ea[e]], edge.b = keyframes[eb[e]];
+                edge.measurement.orientation = mslam::Quaternion(v[3], v[0], v[1], v[2]);
+                edge.measurement.position = mslam::Vector3(v[4], v[5], v[6]);
+                if(head[4])
+                    edge.sqrtInformation.assign(info.begin() + 36 * e, info.begin() + 36 * (e + 1));
+                edges.push_back(edge);
+            }
+            auto makeBackend = mslam::loadFactoryMethod<mslam::IBackend>(argv[1], "hipBundleAdjustBackendFactory");
+            if(!makeBackend)
+                return 3;
+            std::unique_ptr<mslam::IBackend> backend = makeBackend();
+            auto* loopBackend = dynamic_cast<mslam::ILoopClosingBackend*>(backend.get());
+            if(!loopBackend)
+            {
+                std::fprintf(stderr, "the plugin does not offer closeLoop\n");
+                return 6;
+            }
+            const mslam::BackendOutput out = loopBackend->closeLoop(keyframes, edges, head[3]);
+            std::printf("pose_graph termination %d iterations %d initial %.17g final %.17g keyframes %zu edges %zu\n", out.termination,
+                        out.iterations, out.initialCost, out.finalCost, out.updatedKeyframes.size(), E);
+            for(std::size_t k = 0; k < K; ++k)
+            {
+                const auto& st = keyframes[k]->state;
+                std::printf("keyframe %zu %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", k, st.orientation.x(), st.orientation.y(),
+                            st.orientation.z(), st.orientation.w(), st.position.x(), st.position.y(), st.position.z());
+            }
             return 0;
         }
         if(argc == 5 && std::strcmp(argv[2], "--reloc") == 0)

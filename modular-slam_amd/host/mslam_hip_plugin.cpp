@@ -10,7 +10,7 @@
 //                                                           (orb_relocalizer.cpp:26-50, rgbd_feature_frontend.cpp:153,176)
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
-//   HipBundleAdjustBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global (hipBundleAdjustBackendFactory)
+//   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -796,8 +796,9 @@ class HipMinMseTracker : public ISlam3dPnp
 // keyframes and landmarks numbered in the order they first appear, the state as (qx qy qz qw px py pz), keyframe id 1
 // constant — and the result is written back into keyframe->state and landmark->state, as Ceres writes through the pointers
 // the reference hands it.  More than 64 keyframes is an error (the reduced system is dense); FAILURE updates nothing.
-// globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.
-class HipBundleAdjustBackend : public IGlobalBackend
+// globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.  closeLoop hands the
+// keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way.
+class HipBundleAdjustBackend : public ILoopClosingBackend
 {
   public:
     BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
@@ -807,6 +808,60 @@ class HipBundleAdjustBackend : public IGlobalBackend
     BackendOutput globalBundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
     {
         return solve(observations, maxIterations, true);
+    }
+    BackendOutput closeLoop(const std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>>& keyframes,
+                            const std::vector<PoseGraphEdge>& edges, int maxIterations) override
+    {
+        std::map<const void*, int> kfIndex;
+        for(std::size_t k = 0; k < keyframes.size(); ++k)
+            kfIndex.emplace(keyframes[k].get(), static_cast<int>(k));
+        std::vector<double> poses(7 * keyframes.size()), meas(7 * edges.size()), info;
+        std::vector<std::uint8_t> fixed(keyframes.size());
+        std::vector<std::int32_t> edgeA, edgeB;
+        auto put = [](const slam3d::SensorState& st, double* v) {
+            v[0] = st.orientation.x(), v[1] = st.orientation.y(), v[2] = st.orientation.z(), v[3] = st.orientation.w();
+            v[4] = st.position.x(), v[5] = st.position.y(), v[6] = st.position.z();
+        };
+        for(std::size_t k = 0; k < keyframes.size(); ++k)
+        {
+            put(keyframes[k]->state, &poses[7 * k]);
+            fixed[k] = keyframes[k]->id == 1 ? 1 : 0;
+        }
+        bool anyInfo = false;
+        for(const auto& e : edges)
+            anyInfo = anyInfo || !e.sqrtInformation.empty();
+        if(anyInfo)
+            info.assign(36 * edges.size(), 0.0);
+        for(std::size_t e = 0; e < edges.size(); ++e)
+        {
+            const auto a = kfIndex.find(edges[e].a.get()), b = kfIndex.find(edges[e].b.get());
+            if(a == kfIndex.end() || b == kfIndex.end() || (!edges[e].sqrtInformation.empty() && edges[e].sqrtInformation.size() != 36))
+                throw std::runtime_error("closeLoop: an edge names a keyframe that is not listed, or its sqrtInformation is not 6 x 6");
+            edgeA.push_back(a->second), edgeB.push_back(b->second);
+            put(edges[e].measurement, &meas[7 * e]);
+            if(anyInfo)
+                for(int j = 0; j < 36; ++j)
+                    info[36 * e + j] = edges[e].sqrtInformation.empty() ? (j % 7 == 0 ? 1.0 : 0.0) : edges[e].sqrtInformation[j];
+        }
+        ctx.ensure(0, 0);
+        mslam_hip_ba_summary summary{};
+        const int rc = mslam_hip_pose_graph(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), edgeA.data(),
+                                            edgeB.data(), meas.data(), anyInfo ? info.data() : nullptr, static_cast<int>(edges.size()),
+                                            maxIterations, &summary);
+        if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
+            raise(ctx.h, "mslam_hip_pose_graph", rc);
+        BackendOutput out;
+        out.termination = summary.termination, out.iterations = summary.iterations;
+        out.initialCost = summary.initial_cost, out.finalCost = summary.final_cost;
+        if(rc == MSLAM_HIP_OK)
+            for(std::size_t k = 0; k < keyframes.size(); ++k)
+            {
+                const double* v = &poses[7 * k];
+                keyframes[k]->state.orientation = Quaternion(v[3], v[0], v[1], v[2]);
+                keyframes[k]->state.position = Vector3(v[4], v[5], v[6]);
+            }
+        out.updatedKeyframes = keyframes;
+        return out;
     }
 
   private:

@@ -232,6 +232,23 @@ class IGlobalBackend : public IBackend
   public:
     virtual BackendOutput globalBundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations = 100) = 0;
 };
+// extension: the body of RgbdFeatureFrontend::closeLoop (rgbd_feature_frontend.cpp:577-580, empty in the reference): a
+// pose-graph optimisation over the listed keyframes (mslam_hip_pose_graph: up to 1024 keyframes, 65536 edges).  An edge
+// carries pose b expressed in a's frame (T_a^-1 T_b) and, optionally, the square root of its 6 x 6 information matrix
+// (row-major, position rows first; empty: identity).  keyframe->state is corrected in place, keyframe id 1 stays constant;
+// the output lists the keyframes and the summary (no landmarks, no outliers).  Reached with dynamic_cast, like IGlobalBackend.
+struct PoseGraphEdge
+{
+    std::shared_ptr<Keyframe<slam3d::SensorState>> a, b;
+    slam3d::SensorState measurement;
+    std::vector<double> sqrtInformation;
+};
+class ILoopClosingBackend : public IGlobalBackend
+{
+  public:
+    virtual BackendOutput closeLoop(const std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>>& keyframes,
+                                    const std::vector<PoseGraphEdge>& edges, int maxIterations = 100) = 0;
+};
 
 
 // ---- extension (not in the reference): candidates verified by match + RANSAC PnP against stored landmarks -----------------
