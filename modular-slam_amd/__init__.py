@@ -500,8 +500,8 @@ class Context:
                                    max_iterations, outlier_threshold)
 
     def _bundle_adjust(self, entry, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed, max_iterations, outlier_threshold):
-        x = np.array(poses, np.float64).reshape(-1, 7)
-        lm = np.array(landmarks, np.float64).reshape(-1, 3)
+        x = np.array(poses, np.float64, order="C").reshape(-1, 7)        # a copy in row-major order, whatever the argument's
+        lm = np.array(landmarks, np.float64, order="C").reshape(-1, 3)
         ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
         ol = np.ascontiguousarray(obs_lm, np.int32).reshape(-1)
         oc = np.ascontiguousarray(obs_cam, np.float64).reshape(-1, 3)
@@ -525,7 +525,7 @@ class Context:
         (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
         flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
         final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged."""
-        x = np.array(poses, np.float64).reshape(-1, 7)
+        x = np.array(poses, np.float64, order="C").reshape(-1, 7)        # a copy in row-major order, whatever the argument's
         ea = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
         eb = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
         z = np.ascontiguousarray(edge_meas, np.float64).reshape(-1, 7)

@@ -4,7 +4,9 @@ every named case takes the path it is named for.
 
 A scene: K truth poses with positions in [-2, 2]^3 and random orientations, edges whose measurements are the truth's relative
 poses with a little noise, and a start that is the truth moved per free pose (Plus with a tangent of length `angle`, a shift
-of `shift` m).  So |p_b - p_a| <= 4 sqrt(3) < 7 m at the truth and below 8 m at every point a solve visits.
+of `shift` m).  So |p_b - p_a| <= 4 sqrt(3) < 7 m at the truth and below 8 m at every point a solve visits (`far` adds one
+offset to every position, which leaves the differences where they were).  ALL are the cases of the first tests; EDGES, of
+tests/test_pose_graph_edges.py and tests/test_gpu_pose_graph_edges.py, reach the index ranges and branches ALL leaves out.
 This is test infrastructure like ba_cases.py (not a conftest.py, not under oracle/)."""
 import functools
 
@@ -52,6 +54,31 @@ def upper_info(E, seed):
     W = np.triu(rng.uniform(-0.3, 0.3, (E, 6, 6)), 1)
     W[:, np.arange(6), np.arange(6)] = rng.uniform(0.5, 2.0, (E, 6))
     return W
+
+
+def dense_info(E, seed):
+    """full sqrt_info: off-diagonal entries in [-0.3, 0.3] above and below the diagonal, a diagonal of magnitude in [0.5, 2]
+    with random signs; edge 2 has rows 3 to 5 zero (it weighs the position only), the last edge's matrix is zero"""
+    rng = np.random.default_rng(seed)
+    W = rng.uniform(-0.3, 0.3, (E, 6, 6))
+    W[:, np.arange(6), np.arange(6)] = rng.uniform(0.5, 2.0, (E, 6)) * rng.choice([-1.0, 1.0], (E, 6))
+    W[2, 3:, :] = 0.0
+    W[E - 1] = 0.0
+    return W
+
+
+def random_pairs(K, E, seed):
+    """E ordered pairs (a, b), a != b, uniform over the K (K - 1) of them: both directions of every pair of poses"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, K, E)
+    b = (a + rng.integers(1, K, E)) % K
+    return list(zip(a.tolist(), b.tolist()))
+
+
+SPARSE_NODES = [0, 1, 63, 64, 65, 255, 256, 511, 1022, 1023]
+SPARSE_EDGES = list(zip(SPARSE_NODES[:-1], SPARSE_NODES[1:])) + [(1023, 0), (511, 63)]
+FAR_SEED, FAR_OFFSET = 19, 5e4
+NEG_MEAS_EDGES = [1, 3, 5]   # two odometry edges and the loop edge
 
 
 def drift_scene(N=39, seed=3, step_noise=0.05, angle_noise=0.03):
@@ -110,18 +137,53 @@ def scene(name):
         sc["sqrt_info"] = upper_info(len(sc["edge_a"]), 14)
         return sc
     if kind == "rejected":             # a start far from the truth: the reference trace shows rejected steps
-        return make_scene(8, chain(8, 2), 4, angle=1.2, shift=2.0)
+        sc = make_scene(8, chain(8, 2), 4, angle=1.2, shift=2.0)
+        return dict(sc, max_iterations=int(rest[3:])) if rest else sc       # rejected:capN -> the same under a cap
     if kind == "cap0":
         return dict(make_scene(6, chain(6), 15), max_iterations=0)
     if kind == "cap1":
         return dict(make_scene(6, chain(6), 15), max_iterations=1)
     if kind == "drift40":
         return drift_scene()
+    if kind == "edges":                # edges:E -> E random ordered pairs a != b among few poses: whole blocks of 256 edges
+        E = int(rest)
+        K = 12 if E > 4096 else 20
+        return make_scene(K, random_pairs(K, E, 20 + E % 1000), 21 + E % 1000)
+    if kind == "sparse1024":           # the cap of K; ten poses carry edges, 700 is constant without one
+        return make_scene(1024, SPARSE_EDGES, 31, fixed=(0, 700))
+    if kind == "far":                  # chain:9's shape, moved away from the origin: |x| is large, the parameter test ends it
+        sc = make_scene(9, chain(9), FAR_SEED)
+        sc["poses"][:, 4:] += FAR_OFFSET
+        sc["truth_poses"] = sc["truth_poses"] + np.concatenate([np.zeros(4), np.full(3, FAR_OFFSET)])
+        return sc
+    if kind == "zero_start":           # the start is the truth and the measurements are exact: every residual is exactly 0
+        tp = np.zeros((5, 7))
+        tp[:, 3], tp[:, 4] = 1.0, 0.5 * np.arange(5)
+        sc = make_scene(5, chain(5, 0), 32, noise=0.0, truth=tp)
+        sc["poses"] = tp.copy()
+        return sc
+    if kind == "neg_meas":             # three measurements entered as -q_meas: vec(delta) turns round on these edges
+        sc = make_scene(6, chain(6, 2), 33)
+        sc["edge_meas"][NEG_MEAS_EDGES, :4] *= -1.0
+        return sc
+    if kind in ("info_dense", "info_dense_dropped"):   # full sqrt_info, a position-only edge, an all-zero last edge (or none)
+        sc = make_scene(7, chain(7, 2), 34)
+        sc["sqrt_info"] = dense_info(len(sc["edge_a"]), 35)
+        if kind == "info_dense_dropped":
+            for key in ("edge_a", "edge_b", "edge_meas", "sqrt_info"):
+                sc[key] = sc[key][:-1].copy()
+        return sc
     raise KeyError(name)
 
 
 ALL = ["pair", "chain:9", "chain:10", "chain:17", "star70", "duplicates", "two_components", "isolated_fixed_middle", "all_fixed",
        "empty", "rot170", "neg_q", "info_upper", "rejected", "cap0", "cap1", "drift40"]
+
+
+# the second pass over the kernels' index ranges and branches: tests/test_pose_graph_edges.py shows on the CPU that each takes
+# the path it is named for, tests/test_gpu_pose_graph_edges.py compares them.  ALL stays: the host-harness test runs its names.
+EDGES = ["edges:16641", "edges:256", "edges:257", "sparse1024", "far", "zero_start", "neg_meas", "info_dense", "info_dense_dropped",
+         "rejected:cap2", "rejected:cap3", "rejected:cap4", "rejected:cap5", "rejected:cap8"]
 
 
 def solve(sc, linear_solver="qr", **kw):

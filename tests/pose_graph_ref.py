@@ -209,11 +209,14 @@ def _step_chol(Js, D, f):
 def pose_graph(poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100, linear_solver="qr"):
     """-> dict(poses, termination, iterations, initial_cost, final_cost, gradient_max_norm, reason, trace).  poses are the
     inputs when termination is FAILURE.  trace counts `rejected`, `accepted_after_rejected`, `invalid`, `dbl_max` and gives
-    `free_poses`."""
+    `free_poses`; trace["steps"] has one entry per iteration, the decisions of the loop: `parameter_ratio` = step_norm /
+    (PARAMETER_TOLERANCE (|x| + PARAMETER_TOLERANCE)) and `function_ratio` = |x_cost - candidate_cost| / (FUNCTION_TOLERANCE
+    x_cost) (a test fires at a ratio <= 1; both None for an invalid step) and `decision`: "accepted", "rejected", "invalid",
+    or "converged" for the iteration one of the two tests ended."""
     lm_step = {"qr": _step_qr, "chol": _step_chol}[linear_solver]
     poses0, ea, eb, meas, info = _arrays(poses, edge_a, edge_b, edge_meas, sqrt_info)
     fixed = np.zeros(len(poses0), bool) if fixed is None else np.asarray(fixed).astype(bool)
-    trace = dict(rejected=0, accepted_after_rejected=0, invalid=0, dbl_max=0, free_poses=0)
+    trace = dict(rejected=0, accepted_after_rejected=0, invalid=0, dbl_max=0, free_poses=0, steps=[])
     x = poses0.copy()
 
     def out(term, it, c0, c, reason, gmax=np.nan, usable=True):
@@ -254,6 +257,7 @@ def pose_graph(poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max
         if not (np.all(np.isfinite(step)) and model_cost_change > 0.0):
             invalid += 1
             trace["invalid"] += 1
+            trace["steps"].append(dict(parameter_ratio=None, function_ratio=None, decision="invalid"))
             if invalid >= MAX_NUM_CONSECUTIVE_INVALID_STEPS:
                 return out(FAILURE, iteration, initial_cost, x_cost, "too many invalid steps", gmax, usable=False)
             radius /= decrease_factor
@@ -267,12 +271,18 @@ def pose_graph(poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max
             trace["dbl_max"] += 1
         x_amb = prob.ambient(x)
         step_norm = np.linalg.norm(x_amb - prob.ambient(c_x))
+        with np.errstate(all="ignore"):
+            entry = dict(parameter_ratio=float(step_norm / (PARAMETER_TOLERANCE * (np.linalg.norm(x_amb) + PARAMETER_TOLERANCE))),
+                         function_ratio=float(np.float64(abs(x_cost - candidate_cost)) / np.float64(FUNCTION_TOLERANCE * x_cost)),
+                         decision="converged")
+        trace["steps"].append(entry)
         if step_norm <= PARAMETER_TOLERANCE * (np.linalg.norm(x_amb) + PARAMETER_TOLERANCE):
             return out(CONVERGENCE, iteration, initial_cost, x_cost, "parameter tolerance", gmax)
         if abs(x_cost - candidate_cost) <= FUNCTION_TOLERANCE * x_cost:
             return out(CONVERGENCE, iteration, initial_cost, x_cost, "function tolerance", gmax)
         relative_decrease = -DBL_MAX if candidate_cost >= DBL_MAX else (x_cost - candidate_cost) / model_cost_change
         if relative_decrease > MIN_RELATIVE_DECREASE:
+            entry["decision"] = "accepted"
             if not c_ok:
                 return out(FAILURE, iteration, initial_cost, x_cost, "evaluation at the accepted point failed", gmax, usable=False)
             x = c_x
@@ -284,6 +294,7 @@ def pose_graph(poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max
             decrease_factor = 2.0
         else:
             trace["rejected"] += 1
+            entry["decision"] = "rejected"
             radius /= decrease_factor
             decrease_factor *= 2.0
 

@@ -104,7 +104,8 @@ def test_device_lift_equals_add_new_landmarks(pkg):
     depth = np.tile((np.linspace(1.0, 4.2, 640) * 5000).astype(np.uint16), (B, 480, 1))
     depth[:, 100:180, :] = 0
     c = pkg.Context(width=640, height=480, max_batch=B, max_keypoints=K)
-    c.detect_batch_dev(torch.from_numpy(np.stack(frames)).cuda().data_ptr(), B)
+    d_frames = torch.from_numpy(np.stack(frames)).cuda()   # held until the sync: detection is only enqueued here, and a freed
+    c.detect_batch_dev(d_frames.data_ptr(), B)              # tensor's block is what the depth upload below would be given
     d_depth = torch.from_numpy(depth.view(np.int16)).cuda()
     with pytest.raises(pkg.MslamHipError) as e:      # not back-projected yet
         c.kf_add_from_batch_dev(1, 0)
