@@ -712,6 +712,61 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* ctx, int id, const int32_t* ids, int n
 int mslam_hip_kf_union_dev(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */);
 int mslam_hip_kf_union(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */, int* n_out /* may be NULL */);
 
+/* ---- landmark fusion: one identity for the duplicates a loop closure leaves ------------------------------------------
+ * AN EXTENSION, NOT A RESTATEMENT: the reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580) and
+ * nothing in it merges landmarks.  The model is ORB-SLAM's SearchAndFuse: project the landmarks of the old side of a loop
+ * into the corrected new keyframe, match inside a window, give matched pairs one identity.
+ *
+ * mslam_hip_kf_fuse_search finds the duplicates between two distinct store entries keep_id and drop_id (ordinary entries
+ * or unions) and changes nothing.  R (9 f64, row-major), t (3 f64): a pose world -> camera.
+ *   projection   both entries' landmarks are projected with the expression mslam_hip_match_guided_knn2 documents (f64,
+ *                every operation rounded on its own, in that order).  A drop landmark is IN FRAME iff c_2 > 0 and
+ *                ((float)u, (float)v) passes the in-frame test guided matching applies to a keypoint.  From here on the
+ *                drop entry's landmarks play the part of keypoints with xy = ((float)u, (float)v), the keep entry's the
+ *                part of landmarks.
+ *   eligibility  a keep landmark whose id occurs anywhere in the drop entry is neither a searcher nor a candidate (it is
+ *                shared already), and likewise a drop landmark whose id occurs anywhere in the keep entry.  So the two id
+ *                sets of a call's pairs are disjoint and no chain of replacements can arise.
+ *   candidate    drop landmark i is a candidate of keep landmark j iff both are eligible, the guided window test holds with
+ *                `radius` (c_2 of j > 0, i in frame, fabs((double)x_i - u_j) <= radius && fabs((double)y_i - v_j) <= radius),
+ *                and ((dx dx + dy dy) + dz dz) <= max_world_distance max_world_distance on the two f64 world points
+ *                (d = drop - keep; a NaN gives "not a candidate").  The 3-D gate is applied BEFORE the knn-2, so the ratio
+ *                test compares geometrically plausible candidates only; max_world_distance = +inf switches it off.
+ *   knn-2, acceptance
+ *                guided matching's: key dist << 16 | drop position, ties to the lower drop position, a lone candidate is
+ *                accepted, d0 <= max_distance, and (double)d0 < ratio (double)d1 where a second candidate exists.
+ *   one to one   of several keep landmarks that accept the same drop position the one with the least (d0, keep position)
+ *                keeps the pair; the others get no pair (no second choice).
+ *   order        pairs are ordered by keep position.  Row p: keep_pos / drop_pos = the positions inside the entries,
+ *                keep_lid / drop_lid = their landmark ids, dist = d0.
+ * Errors: MSLAM_HIP_E_INVALID for keep_id == drop_id, an id that is not in the store, a radius that is not > 0,
+ * max_distance outside 0..256, an extent outside 1..8192, fx or fy zero or NaN, max_world_distance not > 0 (NaN included),
+ * an entry above 65535 landmarks; MSLAM_HIP_E_CAPACITY with *n_pairs = the count needed (nothing is copied) when the pairs
+ * exceed `capacity` rows.  An empty entry is OK with 0 pairs.  A clear, five launches (ids, projection, k_guided_bin,
+ * search, resolution), one synchronisation; every output is deterministic.
+ *
+ * mslam_hip_kf_replace_ids is the store-wide pass: every landmark of every live entry whose id equals from_ids[p] gets the
+ * id to_ids[p] and, with world_xyz given, that world point bit for bit.  The substitution is simultaneous (the lookup is on
+ * the id the landmark had before the call; nothing is applied transitively).  A `from` id listed twice: the later one wins,
+ * as in mslam_hip_kf_update_world; from == to is allowed (the world point alone changes); ids outside [0, 2^63) are
+ * MSLAM_HIP_E_INVALID; ids the store does not hold are ignored.  *n_rewritten (may be NULL) = the number of store landmarks
+ * whose id matched.  One upload, one clear, two launches, one synchronisation.
+ *
+ * mslam_hip_kf_fuse runs the search and then the replacement drop_lid -> keep_lid with the keep landmark's world point.
+ * The pair list never leaves the device between the two (the table is built from the device list) and there is one
+ * synchronisation at the end.  The pair arrays may be NULL; `capacity` bounds the pairs either way: when they do not fit,
+ * nothing is rewritten and the call returns MSLAM_HIP_E_CAPACITY with *n_pairs = the count needed. */
+int mslam_hip_kf_fuse_search(mslam_hip_ctx* ctx, int keep_id, int drop_id, const double* R, const double* t, double fx, double fy,
+                             double cx, double cy, int width, int height, double radius, int max_distance, double ratio,
+                             double max_world_distance, int32_t* keep_pos, int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid,
+                             int32_t* dist, int capacity, int* n_pairs);
+int mslam_hip_kf_replace_ids(mslam_hip_ctx* ctx, const int64_t* from_ids, const int64_t* to_ids, const double* world_xyz /* n x 3 or NULL */,
+                             int n, int* n_rewritten /* may be NULL */);
+int mslam_hip_kf_fuse(mslam_hip_ctx* ctx, int keep_id, int drop_id, const double* R, const double* t, double fx, double fy, double cx,
+                      double cy, int width, int height, double radius, int max_distance, double ratio, double max_world_distance,
+                      int32_t* keep_pos /* may be NULL, as the next four */, int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid,
+                      int32_t* dist, int capacity, int* n_pairs, int* n_rewritten /* may be NULL */);
+
 /* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
  * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
  * valid; a mask is track()'s depth filter, :317-334).  Per candidate c = cand_ids[k]:

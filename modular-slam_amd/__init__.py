@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_add_ids", "mslam_hip_kf_read_ids", "mslam_hip_kf_covisible", "mslam_hip_kf_union", "mslam_hip_kf_union_dev",
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
     "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world", "mslam_hip_pose_graph",
+    "mslam_hip_kf_fuse_search", "mslam_hip_kf_replace_ids", "mslam_hip_kf_fuse",
 ]
 
 
@@ -555,6 +556,58 @@ class Context:
         n = C.c_int(0)
         self._chk(self.L.mslam_hip_kf_update_world(self._h, _p(l), _p(w), len(l), C.byref(n)))
         return n.value
+
+    # ---- landmark fusion (an extension: the reference's closeLoop is empty) ------------------------
+    def _fuse_call(self, entry, keep_id, drop_id, R, t, radius, max_distance, ratio, max_world_distance, focal, principal,
+                   width, height, capacity, tail):
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        cap = int(self.params.max_keypoints if capacity is None else capacity)
+        kp, dp, di = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
+        kl, dl = (np.zeros(max(cap, 1), np.int64) for _ in range(2))
+        n = C.c_int(0)
+        rc = entry(self._h, int(keep_id), int(drop_id), _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]),
+                   C.c_double(principal[0]), C.c_double(principal[1]), int(self.params.width if width is None else width),
+                   int(self.params.height if height is None else height), C.c_double(radius), int(max_distance), C.c_double(ratio),
+                   C.c_double(max_world_distance), _p(kp), _p(dp), _p(kl), _p(dl), _p(di), cap, C.byref(n), *tail)
+        if rc == E_CAPACITY:
+            e = MslamHipError(rc, (self.L.mslam_hip_last_error(self._h) or b"").decode())
+            e.needed = n.value
+            raise e
+        self._chk(rc)
+        k = n.value
+        return dict(keep_pos=kp[:k].copy(), drop_pos=dp[:k].copy(), keep_lid=kl[:k].copy(), drop_lid=dl[:k].copy(), dist=di[:k].copy())
+
+    def kf_fuse_search(self, keep_id, drop_id, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf,
+                       focal=(525.0, 525.0), principal=(319.5, 239.5), width=None, height=None, capacity=None):
+        """the landmarks of entry drop_id that duplicate landmarks of entry keep_id: both projected under the world -> camera
+        pose (R, t), each keep landmark matched among the drop landmarks within `radius` px and max_world_distance metres,
+        one to one -> dict(keep_pos, drop_pos, keep_lid, drop_lid, dist), ordered by keep position.  Changes nothing.
+        More pairs than `capacity` (default: max_keypoints): MslamHipError E_CAPACITY carrying `needed`."""
+        return self._fuse_call(self.L.mslam_hip_kf_fuse_search, keep_id, drop_id, R, t, radius, max_distance, ratio,
+                               max_world_distance, focal, principal, width, height, capacity, ())
+
+    def kf_replace_ids(self, from_ids, to_ids, world_xyz=None):
+        """every landmark of every stored keyframe whose id is from_ids[p] takes the id to_ids[p] and, when given, the world
+        point world_xyz[p]; simultaneous, the later of a repeated `from` wins -> the number of store landmarks that matched"""
+        f = np.ascontiguousarray(from_ids, np.int64).reshape(-1)
+        t = np.ascontiguousarray(to_ids, np.int64).reshape(-1)
+        w = None if world_xyz is None else np.ascontiguousarray(world_xyz, np.float64).reshape(-1, 3)
+        if len(f) != len(t) or (w is not None and len(w) != len(f)):
+            raise MslamHipError(E_INVALID, "kf_replace_ids: %d from ids, %d to ids, %s points" % (len(f), len(t), "no" if w is None else len(w)))
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_replace_ids(self._h, _p(f), _p(t), _p(w), len(f), C.byref(n)))
+        return n.value
+
+    def kf_fuse(self, keep_id, drop_id, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf, focal=(525.0, 525.0),
+                principal=(319.5, 239.5), width=None, height=None, capacity=None):
+        """kf_fuse_search, then every store landmark with a pair's drop id takes the keep id and the keep landmark's world
+        point, in one call with one synchronisation -> kf_fuse_search's dict plus n_rewritten"""
+        nr = C.c_int(0)
+        out = self._fuse_call(self.L.mslam_hip_kf_fuse, keep_id, drop_id, R, t, radius, max_distance, ratio,
+                              max_world_distance, focal, principal, width, height, capacity, (C.byref(nr),))
+        out["n_rewritten"] = nr.value
+        return out
 
     # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
     def kf_covisible(self, id, ids):
@@ -1240,6 +1293,26 @@ class HipBackend:
             raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
         return self._solve(sorted(self.poses), self.global_solver)
 
+    def fuse(self, keep_lids, drop_lids):
+        """landmark fusion's bookkeeping: every observation of drop_lids[p] becomes one of keep_lids[p] (simultaneously, the
+        later of a repeated drop id wins, as Context.kf_replace_ids), `landmarks` and `anchor` lose the dropped ids, the kept
+        landmark keeps its point and its anchor -> the number of observations rewritten"""
+        keep = np.asarray(keep_lids, np.int64).reshape(-1).tolist()
+        drop = np.asarray(drop_lids, np.int64).reshape(-1).tolist()
+        if len(keep) != len(drop):
+            raise MslamHipError(E_INVALID, "fuse: %d keep ids, %d drop ids" % (len(keep), len(drop)))
+        to = dict(zip(drop, keep))
+        n = 0
+        for id, (lids, cam) in self.obs.items():
+            new = np.array([to.get(l, l) for l in lids.tolist()], np.int64).reshape(-1)
+            n += int(np.count_nonzero([l in to for l in lids.tolist()]))
+            self.obs[id] = (new, cam)
+        for d, k in to.items():
+            if d != k:
+                self.landmarks.pop(d, None)
+                self.anchor.pop(d, None)
+        return n
+
     def loop_problem(self, cur_id, loop_id, rvec, tvec, graph, sqrt_info=None):
         """the arrays Context.pose_graph takes for a loop between keyframes loop_id and cur_id -> (keyframe ids, poses,
         fixed, edge_a, edge_b, edge_meas, sqrt_info): every graph edge i < j with both ends in self.poses, in sorted order,
@@ -1334,18 +1407,36 @@ class HipKeyframeTracker:
     first).  On a winner: HipBackend.close_loop, Context.kf_update_world with the moved landmarks, the tracker's pose becomes
     the corrected pose of the new keyframe, the local map is rebuilt, and with loop_global_ba HipBackend.global_ba and
     kf_update_world follow.  self.loop_results holds every attempt; the frame's dict gains loop = (cur, loop) or None.
-    DELIBERATELY OUT: landmark fusion (giving the new keyframe's matched landmarks the old keyframe's ids), so no covisibility
-    edge joins the two keyframes and the loop is known to the pose graph of that one call only."""
+    Without loop_fusion the new keyframe's landmarks keep their own ids, so no covisibility edge joins the two keyframes and
+    the loop is known to the pose graph of that one call only.
+
+    loop_fusion = True (needs loop_closure, else MslamHipError(E_INVALID); an extension, the reference has no such step):
+    after close_loop and kf_update_world and before the optional global BA, the duplicates across the loop get one
+    identity.  Two unions under the reserved ids FUSE_KEEP_ID and FUSE_DROP_ID hold self.neighbours(loop keyframe) (keep)
+    and self.neighbours(new keyframe) (drop); Context.kf_fuse with the corrected pose of the new keyframe, the frame's
+    extent, loop_fuse_radius, loop_fuse_max_distance, the tracker's ratio and loop_fuse_world_distance rewrites the store;
+    the unions are removed; HipBackend.fuse renames the observations; Context.kf_covisible of every member of the new side
+    against the old side adds a graph edge wherever the count is positive; the local map is rebuilt.  The attempt's dict
+    gains fusion = dict(n_pairs, n_rewritten, edges).  The reserved ids are never in self.ids, the vote list or the
+    candidates.  Off (the default): none of this runs and no union is built, so serials and fresh ids are unchanged.
+    STILL OUT: duplicates outside the corrected keyframe's view stay unfused."""
 
     LOCAL_MAP_ID = 0x7fffffff
+    FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
     LOOP_QUERY_RESULTS = 64    # hits asked of the database before the filters: the newest keyframes fill the top of the list
 
     def __init__(self, ctx, focal=(525.0, 525.0), principal=(319.5, 239.5), factor=1.0 / 5000.0, ratio=0.7, iterations=100,
                  reprojection_error=5.0, seed=0, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0,
                  reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False,
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
-                 loop_global_ba=False):
+                 loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
+                 loop_fuse_world_distance=0.1):
         self.ctx = ctx
+        if loop_fusion and not loop_closure:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_fusion needs loop_closure")
+        self.loop_fusion, self.loop_fuse_radius = bool(loop_fusion), float(loop_fuse_radius)
+        self.loop_fuse_max_distance, self.loop_fuse_world_distance = int(loop_fuse_max_distance), float(loop_fuse_world_distance)
+        self._extent = None          # (width, height) of the last frame's depth image: the frame loop_fusion projects into
         if local_ba and local_map_depth is None:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: local_ba needs local_map_depth (the covisibility graph)")
         if loop_closure:
@@ -1385,6 +1476,7 @@ class HipKeyframeTracker:
         -> dict(tracked, n_inliers, rvec, tvec, R, reference, keyframe = the id added or -1, relocalized, step)"""
         seed = self.seed + self.frame
         self.frame += 1
+        self._extent = np.asarray(depth).shape[1::-1]
         if self.reference is None:
             xyz, valid = self.ctx.backproject(depth, xy, self.factor, self.focal, self.principal)
             keep = valid & (xyz[:, 2] <= self.z_max)
@@ -1492,6 +1584,7 @@ class HipKeyframeTracker:
                         if self.backend is not None:
                             self._local_ba(new_id, res, xys[i + s], depths[i + s])
                         if self.loop_closure:
+                            self._extent = np.asarray(depths[i + s]).shape[1::-1]
                             o["loop"] = self._close_loops(new_id, descs[i + s], xys[i + s], seed + s)
                 else:
                     reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
@@ -1570,12 +1663,40 @@ class HipKeyframeTracker:
         self.rvec = rotation_to_rvec(self.R)
         self._local_map_of = None
         self._last_closure = new_id
+        if self.loop_fusion:
+            attempt["fusion"] = self._fuse_loop(new_id, loop_id)
         if self.loop_global_ba:
             ba = self.backend.global_ba()
             if ba["termination"] != 2:
                 ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
             attempt["global_ba"] = ba
         return (new_id, loop_id)
+
+    def _fuse_loop(self, new_id, loop_id):
+        """landmark fusion across the loop just closed: the new side's duplicates take the old side's ids and points
+        -> dict(n_pairs, n_rewritten, edges = the (new side, old side) graph edges the shared landmarks add)"""
+        old, new = self.neighbours(loop_id), self.neighbours(new_id)
+        self.ctx.kf_union(self.FUSE_KEEP_ID, old)
+        try:
+            self.ctx.kf_union(self.FUSE_DROP_ID, new)
+            try:
+                got = self.ctx.kf_fuse(self.FUSE_KEEP_ID, self.FUSE_DROP_ID, self.R, self.tvec, self.loop_fuse_radius,
+                                       self.loop_fuse_max_distance, self.ratio, self.loop_fuse_world_distance, self.focal,
+                                       self.principal, self._extent[0], self._extent[1])
+            finally:
+                self.ctx.kf_remove(self.FUSE_DROP_ID)
+        finally:
+            self.ctx.kf_remove(self.FUSE_KEEP_ID)
+        self.backend.fuse(got["keep_lid"], got["drop_lid"])
+        edges = []
+        for k in new:
+            for other, n in zip(old, self.ctx.kf_covisible(k, old)):
+                if n > 0 and other != k and other not in self.graph[k]:
+                    self.graph[k].add(other)
+                    self.graph[other].add(k)
+                    edges.append((k, other))
+        self._local_map_of = None
+        return dict(n_pairs=len(got["keep_lid"]), n_rewritten=got["n_rewritten"], edges=edges)
 
     def neighbours(self, ref):
         """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than

@@ -8,9 +8,8 @@
 // keyframe id is the largest), and the edge test of BasicMap::updateCovisibility (basic_map.cpp:141-164: two keyframes are
 // neighbours when they observe a landmark in common).
 //
-// Both run on one open-addressing hash table in device scratch: {u64 key, u64 val} buckets, a power of two of them and
-// at least twice the landmarks that can be inserted, cleared to all-ones (a landmark id is never all-ones: ids are below
-// 2^63), linear probing.  A key is claimed with one compare-and-swap; what the value holds differs:
+// Both run on one open-addressing hash table in device scratch (lm_table.hpp).  A key is claimed with one compare-and-swap;
+// what the value holds differs:
 //   union        ~pack, pack = (rank + 1) << 32 | list position << 16 | landmark position, lowered with atomicMin: the
 //                smallest ~pack is the largest pack, i.e. the listed entry with the largest keyframe id (rank = the rank
 //                of its id among the listed ids), and inside one entry the highest position.  The cleared value (all
@@ -19,6 +18,7 @@
 // The union's result order is by list position, then landmark position: the grid is laid out that way (blockIdx.y = list
 // position), winners are counted per block, one workgroup scans the block counts, and the scatter places every winner
 // at its block's offset plus its ballot / popcount prefix, as k_kf_lift does inside one block.
+#include "lm_table.hpp"
 #include "reloc.hpp"
 
 #include <algorithm>
@@ -28,13 +28,6 @@
 
 namespace mslam
 {
-
-struct LmBucket
-{
-    unsigned long long key, val;
-};
-
-constexpr unsigned long long kLmEmpty = ~0ull;
 
 // the listed entries of one call, passed by value: nothing is uploaded
 struct LmList
@@ -47,47 +40,6 @@ struct LmHead // the mapped result block's first 16 bytes, then counts[64]
 {
     int32_t needed, pad[3];
 };
-
-__device__ __forceinline__ unsigned long long lm_hash(unsigned long long x)
-{
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return x;
-}
-
-// the bucket of `key`, claimed if no thread has claimed one for it yet.  The table has at least twice as many buckets as
-// keys are ever inserted, so the walk ends; it is bounded by the table's size all the same (-1: cannot happen).
-__device__ __forceinline__ long long lm_claim(LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
-{
-    unsigned long long h = lm_hash(key) & mask;
-    for(unsigned long long step = 0; step <= mask; ++step)
-    {
-        const unsigned long long prev = atomicCAS(&table[h].key, kLmEmpty, key);
-        if(prev == kLmEmpty || prev == key)
-            return (long long)h;
-        h = (h + 1) & mask;
-    }
-    return -1;
-}
-
-// the bucket of `key`, -1 when the table does not hold it (read-only: every insert is in an earlier launch)
-__device__ __forceinline__ long long lm_find(const LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
-{
-    unsigned long long h = lm_hash(key) & mask;
-    for(unsigned long long step = 0; step <= mask; ++step)
-    {
-        const unsigned long long k = table[h].key;
-        if(k == key)
-            return (long long)h;
-        if(k == kLmEmpty)
-            return -1;
-        h = (h + 1) & mask;
-    }
-    return -1;
-}
 
 __device__ __forceinline__ unsigned long long lm_pack(int rank, int k, int i)
 {
@@ -301,14 +253,6 @@ static int lm_scratch(mslam_hip_ctx* c, size_t buckets, size_t blocks)
     if(!r->h_lm)
         MSLAM_CHK(c, r->h_lm.alloc(sizeof(LmHead) + kRelocMaxCand * 4));
     return MSLAM_HIP_OK;
-}
-
-static size_t lm_bucket_count(size_t keys)
-{
-    size_t b = 64;
-    while(b < 2 * keys)
-        b <<= 1;
-    return b;
 }
 
 // the launches of both union forms; *dst_slot receives the new entry's slot

@@ -438,6 +438,38 @@ class BowDatabase
         return trackAgainst(kLocalMapId, keypoints, depth, width, height, camera, neighbours, rvecGuess, tvecGuess, newKeyframe, o);
     }
 
+    // ---- extension: landmark fusion (mslam_hip_kf_fuse) ----
+    LandmarkFusion fuseLandmarks(const KeyframePtr& keepEntry, const KeyframePtr& dropEntry, const double R[9], const double t[3],
+                                 const LandmarkFuseParams& p)
+    {
+        const int keep = storedLandmarksOf(keepEntry), drop = storedLandmarksOf(dropEntry);
+        int cap = 0, nDrop = 0;
+        int rc = mslam_hip_kf_read_ids(ctx.h, keep, nullptr, 0, &cap);
+        if(rc == MSLAM_HIP_OK)
+            rc = mslam_hip_kf_read_ids(ctx.h, drop, nullptr, 0, &nDrop);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_read_ids", rc);
+        cap = std::min(cap, nDrop); // one pair per landmark of either entry at most
+        const std::size_t rows = static_cast<std::size_t>(cap) + 1;
+        std::vector<std::int32_t> keepPos(rows), dropPos(rows), dist(rows);
+        std::vector<std::int64_t> keepId(rows), dropId(rows);
+        int n = 0;
+        LandmarkFusion out;
+        rc = mslam_hip_kf_fuse(ctx.h, keep, drop, R, t, p.camera.focal.x(), p.camera.focal.y(), p.camera.principalPoint.x(),
+                               p.camera.principalPoint.y(), p.width, p.height, p.radius, p.maxDistance, p.ratio, p.maxWorldDistance,
+                               keepPos.data(), dropPos.data(), keepId.data(), dropId.data(), dist.data(), cap, &n, &out.rewritten);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_fuse", rc);
+        for(int k = 0; k < n; ++k)
+        {
+            FusedLandmarkPair pair;
+            pair.keepPosition = keepPos[k], pair.dropPosition = dropPos[k], pair.keepId = keepId[k], pair.dropId = dropId[k];
+            pair.distance = dist[k];
+            out.pairs.push_back(pair);
+        }
+        return out;
+    }
+
     KeyframeTrackResult trackAgainst(int refId, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                      const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
                                      const double* tvecGuess, const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
@@ -593,7 +625,11 @@ class BowDatabase
     std::vector<OrbKeypoint> lastFed;
 };
 
-class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, public IKeyframeTracker, public ILocalMapTracker
+class HipOrbRelocalizer : public IOrbRelocalizer,
+                          public IVerifiedRelocalizer,
+                          public IKeyframeTracker,
+                          public ILocalMapTracker,
+                          public ILandmarkFuser
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -646,6 +682,11 @@ class HipOrbRelocalizer : public IOrbRelocalizer, public IVerifiedRelocalizer, p
         return db->covisibleLandmarks(keyframe, others);
     }
     int buildLocalMap(const std::vector<BowDatabase::KeyframePtr>& members) override { return db->buildLocalMap(members); }
+    LandmarkFusion fuseLandmarks(BowDatabase::KeyframePtr keepEntry, BowDatabase::KeyframePtr dropEntry, const double R[9],
+                                 const double t[3], const LandmarkFuseParams& params) override
+    {
+        return db->fuseLandmarks(keepEntry, dropEntry, R, t, params);
+    }
     KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                       const CameraParameters& camera, const std::vector<BowDatabase::KeyframePtr>& neighbours,
                                       const double* rvecGuess, const double* tvecGuess, BowDatabase::KeyframePtr newKeyframe,

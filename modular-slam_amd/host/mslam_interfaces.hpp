@@ -360,4 +360,39 @@ class ILocalMapTracker
                                               const KeyframeTrackOptions& options = KeyframeTrackOptions()) = 0;
     virtual ~ILocalMapTracker() = default;
 };
+
+// ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
+// The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
+// The landmarks of `dropEntry` that duplicate landmarks of `keepEntry` — both projected under one world -> camera pose, each
+// keep landmark matched among the drop landmarks inside a window and a 3-D gate, one to one — take the keep landmark's id
+// and world point in every stored keyframe.  Offered by the adapter that owns the store (the one that offers
+// ILocalMapTracker).
+struct LandmarkFuseParams
+{
+    CameraParameters camera;
+    int width = 640, height = 480; // the frame the pose looks into
+    double radius = 8.0;           // px, the half edge of the search window
+    int maxDistance = 50;          // Hamming
+    double ratio = 0.7;
+    double maxWorldDistance = 0.1; // metres; infinity switches the gate off
+};
+struct FusedLandmarkPair
+{
+    int keepPosition = 0, dropPosition = 0; // inside the two entries
+    std::int64_t keepId = 0, dropId = 0;    // landmark ids: every dropId in the store has become keepId
+    int distance = 0;
+};
+struct LandmarkFusion
+{
+    std::vector<FusedLandmarkPair> pairs; // ordered by keepPosition
+    int rewritten = 0;                    // store landmarks whose id was replaced
+};
+class ILandmarkFuser
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual LandmarkFusion fuseLandmarks(KeyframePtr keepEntry, KeyframePtr dropEntry, const double R[9], const double t[3],
+                                         const LandmarkFuseParams& params) = 0;
+    virtual ~ILandmarkFuser() = default;
+};
 } // namespace mslam
