@@ -17,7 +17,8 @@ struct LmBucket
 
 constexpr unsigned long long kLmEmpty = ~0ull;
 
-__device__ __forceinline__ unsigned long long lm_hash(unsigned long long x)
+// splitmix64's finaliser (callable on the host as well: tests/test_lm_table_edges.py holds its restatement to this one)
+__host__ __device__ __forceinline__ unsigned long long lm_hash(unsigned long long x)
 {
     x ^= x >> 30;
     x *= 0xbf58476d1ce4e5b9ull;

@@ -5,7 +5,9 @@ agree bit for bit; HipBackend.fuse's bookkeeping; and the tracker's fusion step 
 tests/reloc_ref.py.  Shares no code with the product.
 
 An entry is (desc [n, 32] u8, world [n, 3] f64, landmark ids [n] i64).  Also here: the case table tests/test_fuse.py proves
-and tests/test_gpu_fuse.py runs, and the scene file `mslam_harness --fuse` reads."""
+and tests/test_gpu_fuse.py runs, the cases away from the default frame (other extents and radii, a real pose and camera)
+that tests/test_lm_table_edges.py proves and tests/test_gpu_fuse_edges.py runs, and the scene file `mslam_harness --fuse`
+reads."""
 import struct
 
 import numpy as np
@@ -197,11 +199,12 @@ def near(rng, desc, bits):
     return rr._flip_bits(rng, np.asarray(desc, np.uint8).reshape(-1, 32), bits)
 
 
-def random_case(seed, nk, nd, shared=0, width=640, height=480, spread=1.5):
+def random_case(seed, nk, nd, shared=0, width=640, height=480, spread=1.5, twin_spread=1.0, deeper=0.001):
     """nk keep landmarks at Z = 1 uniform over the frame and a little beyond; of the nd drop landmarks up to two thirds (at most
-    4/3 of nk: one per keep landmark, a third of those a second copy) sit within `spread` px of a keep landmark, 0.0 .. 0.001 deeper, and carry its descriptor with
-    a few flipped bits; a quarter of the keep landmarks are look-alikes of another keep landmark within a pixel of it, so two
-    keep landmarks claim one drop landmark; `shared` ids occur on both sides.
+    4/3 of nk: one per keep landmark, a third of those a second copy) sit within `spread` px of a keep landmark, 0.0 .. `deeper`
+    (0.001) deeper, and carry its descriptor with a few flipped bits; a quarter of the keep landmarks are look-alikes of another keep landmark within a pixel of it, so two
+    keep landmarks claim one drop landmark (`twin_spread`: how far, in px, a look-alike sits from its model); `shared` ids
+    occur on both sides.
     -> dict(keep, drop, radius, kw)"""
     rng = np.random.default_rng(seed)
     kw_ = np.stack([rng.uniform(-10, width + 10, nk), rng.uniform(-10, height + 10, nk), np.ones(nk)], 1)
@@ -211,12 +214,12 @@ def random_case(seed, nk, nd, shared=0, width=640, height=480, spread=1.5):
     if nk and nd:
         twin = rng.choice(nk, nk // 4, replace=False)          # keep landmarks that are look-alikes of another one, next to it:
         of = rng.integers(0, nk, len(twin))                    # both claim that one's duplicate
-        kw_[twin, :2] = kw_[of, :2] + rng.uniform(-1.0, 1.0, (len(twin), 2))
+        kw_[twin, :2] = kw_[of, :2] + rng.uniform(-twin_spread, twin_spread, (len(twin), 2))
         kd[twin] = near(rng, kd[of], 3)
         dup = rng.choice(nd, min((2 * nd + 2) // 3, nk + nk // 3), replace=False)
         src = np.concatenate([rng.permutation(nk), rng.integers(0, nk, nk // 3)])[:len(dup)]   # a third of them a second copy
         dw[dup, :2] = kw_[src, :2] + rng.uniform(-spread, spread, (len(dup), 2))
-        dw[dup, 2] = 1.0 + rng.uniform(0.0, 0.001, len(dup))
+        dw[dup, 2] = 1.0 + rng.uniform(0.0, deeper, len(dup))
         for i, k in zip(dup, src):                             # 1 .. 15 flipped bits: where several drop landmarks copy one
             dd[i] = near(rng, kd[k], int(rng.integers(1, 16)))[0]   # keep landmark the ratio test passes some and fails others
     kl = 1000 + np.arange(nk, dtype=np.int64)
@@ -227,9 +230,134 @@ def random_case(seed, nk, nd, shared=0, width=640, height=480, spread=1.5):
                 kw=dict(IDENTITY, width=width, height=height, max_distance=50, ratio=0.7, max_world_distance=2.0))
 
 
+CHUNK = 1024                                   # keep landmarks per pass of the one-workgroup resolution
+CHUNK_SIZES = [(1024, 1024), (1025, 1100), (2100, 2100)]   # exactly one pass; one landmark in the second; three passes
 SIZES = [(0, 5), (5, 0), (1, 1), (2, 2), (7, 40), (8, 40), (9, 40), (31, 20), (32, 20), (33, 20), (255, 257), (256, 256),
-         (257, 255), (4500, 3), (3, 3000)]     # (keep, drop): the search's 8 / 32 landmarks per workgroup (the latter above
-                                               # 4096 keep landmarks), the other kernels' 256, either side large
+         (257, 255), (4500, 3), (3, 3000)] + CHUNK_SIZES   # (keep, drop): the search's 8 / 32 landmarks per workgroup (the
+                                               # latter above 4096 keep landmarks), the other kernels' 256, either side large,
+                                               # and many pairs in every pass of the resolution
+
+
+def plant_chunks(case, seed, tail=60):
+    """Into a random_case, in place: the last `tail` keep landmarks each get a place of their own in the frame and a
+    duplicate among the last `tail` drop landmarks, so the last pass of the resolution compacts (nearly) a pair per landmark;
+    and per pass after the first, up to three drop landmarks claimed by a keep landmark of that pass AND by one of the first
+    pass: the later one at distance 2 against 4 (it takes the pair), at 6 against 4 (it gets none) and at 4 against 4 (the lower
+    keep position takes it).  -> the planted (first-pass keep, later keep, drop position, winner) rows"""
+    rng = np.random.default_rng(seed)
+    (kd, kw_, kl), (dd, dw, dl) = case["keep"], case["drop"]
+    nk, nd, w, h = len(kd), len(dd), case["kw"]["width"], case["kw"]["height"]
+
+    def place(j, i, bits):                                      # keep j somewhere new, drop i its duplicate
+        kw_[j] = (rng.uniform(20, w - 20), rng.uniform(20, h - 20), 1.0)
+        kd[j] = rng.integers(0, 256, 32, dtype=np.uint8)
+        dw[i] = (kw_[j, 0] + rng.uniform(-1, 1), kw_[j, 1] + rng.uniform(-1, 1), 1.0 + rng.uniform(0.0, 0.001))
+        dd[i] = near(rng, kd[j], bits)[0]
+
+    tail = min(tail, nk, nd)
+    for m in range(tail):
+        place(nk - tail + m, nd - tail + m, int(rng.integers(1, 4)))
+    rows = []
+    for c in range(1, (nk + CHUNK - 1) // CHUNK):
+        for m, bits in enumerate((2, 6, 4)):
+            b, i = 100 + 40 * c + 7 * m, 200 + 40 * c + 11 * m          # clear of the shared ids' positions
+            a = c * CHUNK + 5 + 300 * m
+            if a >= nk or (a >= nk - tail and bits >= 4):                # (one of the tail gives its pair up only for another)
+                continue
+            place(b, i, 4)
+            kw_[a] = kw_[b] + (0.25, -0.25, 0.0)
+            kd[a] = near(rng, dd[i], bits)[0]
+            rows.append((b, a, i, a if bits < 4 else b))
+    return rows
+
+
+def sized_case(nk, nd):
+    """the case of one entry of SIZES"""
+    case = random_case(100 + nk + nd, nk, nd, shared=3 if min(nk, nd) > 30 else 1 if min(nk, nd) > 3 else 0)
+    case["planted"] = plant_chunks(case, nk + nd) if (nk, nd) in CHUNK_SIZES else []
+    return case
+
+
+# ---- away from the default frame -------------------------------------------------------------------------------------------
+
+FRAMES = [(100, 80), (20, 20), (4114, 102), (8192, 8192)]
+FRAME_SIZES = [(65, 64), (513, 700)]
+
+
+def frame_radii(width, height):
+    """half a pixel, two radii of tests/test_gpu_guided_match.py and one beyond the frame (brute force: every eligible drop
+    landmark in the frame is a candidate of every keep landmark)"""
+    return [0.5, 15.0, 47.5, float(max(width, height) + 10)]
+
+
+def frame_case(nk, nd, width, height):
+    """random_case in a width x height frame with every duplicate inside the smallest radius: 0.2 px beside its keep
+    landmark and so little deeper that u = X / Z moves by 0.2 px at most, a look-alike 0.05 px from its model"""
+    return random_case(7 * width + height + nk, nk, nd, shared=3, width=width, height=height, spread=0.2, twin_spread=0.05,
+                       deeper=0.2 / (max(width, height) + 10))
+
+
+POSE_R = rr.po.rodrigues([0.3, -0.2, 0.1])
+POSE_T = np.array([0.4, -0.3, 0.6])
+POSED_SIZES = [(300, 280), (1025, 1100)]
+
+
+def posed_case(seed, nk, nd, shared=0, width=640, height=480, spread=1.5):
+    """random_case's scene in the frame of a camera at a real pose: pixels uniform over the frame and a little beyond, depths
+    uniform in 0.5 .. 4 m, camera point ((u - cx) / fx Z, (v - cy) / fy Z, Z) with guided_match_ref.CAM, and
+    world = R^T (c - t).  A duplicate is 0 .. 1 mm deeper than its keep landmark; half of the other drop landmarks are further
+    copies 0.1 .. 0.5 m behind a keep landmark: inside its window but beyond the gate of 0.05 m, which alone keeps them from
+    taking the pair or spoiling the ratio test.
+    -> dict(keep, drop, radius, kw)"""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = CAM
+
+    def world(px, z):
+        c = np.stack([(px[:, 0] - cx) / fx * z, (px[:, 1] - cy) / fy * z, z], 1)
+        return (c - POSE_T) @ POSE_R                                          # rows of R^T (c - t)
+
+    kpx = np.stack([rng.uniform(-10, width + 10, nk), rng.uniform(-10, height + 10, nk)], 1)
+    kz = rng.uniform(0.5, 4.0, nk)
+    kd = rng.integers(0, 256, (nk, 32), dtype=np.uint8)
+    dpx = np.stack([rng.uniform(-10, width + 10, nd), rng.uniform(-10, height + 10, nd)], 1)
+    dz = rng.uniform(0.5, 4.0, nd)
+    dd = rng.integers(0, 256, (nd, 32), dtype=np.uint8)
+    twin = rng.choice(nk, nk // 4, replace=False)
+    of = rng.integers(0, nk, len(twin))
+    kpx[twin] = kpx[of] + rng.uniform(-1.0, 1.0, (len(twin), 2))
+    kz[twin] = kz[of] + rng.uniform(0.0, 0.001, len(twin))
+    kd[twin] = near(rng, kd[of], 3)
+    dup = rng.choice(nd, min((2 * nd + 2) // 3, nk + nk // 3), replace=False)
+    src = np.concatenate([rng.permutation(nk), rng.integers(0, nk, nk // 3)])[:len(dup)]
+    dpx[dup] = kpx[src] + rng.uniform(-spread, spread, (len(dup), 2))
+    dz[dup] = kz[src] + rng.uniform(0.0, 0.001, len(dup))
+    rest = np.setdiff1d(np.arange(nd), dup)
+    far = rest[:len(rest) // 2]                                               # further copies, behind their keep landmark
+    far_src = src[rng.integers(0, len(src), len(far))]
+    dpx[far] = kpx[far_src] + rng.uniform(-spread, spread, (len(far), 2))
+    dz[far] = kz[far_src] + rng.uniform(0.1, 0.5, len(far))
+    for i, k in zip(np.concatenate([dup, far]), np.concatenate([src, far_src])):
+        dd[i] = near(rng, kd[k], int(rng.integers(1, 16)))[0]
+    kl = 1000 + np.arange(nk, dtype=np.int64)
+    dl = 500000 + np.arange(nd, dtype=np.int64)
+    for s in range(min(shared, nk, nd)):
+        dl[(7 * s) % nd] = kl[(3 * s) % nk]
+    return dict(keep=(kd, world(kpx, kz), kl), drop=(dd, world(dpx, dz), dl), radius=4.0,
+                kw=dict(R=POSE_R, t=POSE_T, cam=CAM, width=width, height=height, max_distance=50, ratio=0.7, max_world_distance=0.05))
+
+
+def gate_alone(case):
+    """the (keep, drop) position pairs that pass every test of the search but the 3-D gate"""
+    kw = case["kw"]
+    (kd, kw_, kl), (dd, dw, dl) = entry(*case["keep"]), entry(*case["drop"])
+    k_ok, d_ok = eligible(kl, dl)
+    xy, d_in = drop_keypoints(dw, kw["R"], kw["t"], kw["cam"], kw["width"], kw["height"])
+    u, v, c2 = gm.project(kw_, kw["R"], kw["t"], kw["cam"])
+    out = []
+    for j in np.flatnonzero(k_ok):
+        cand = gm.candidates(xy, u[j], v[j], c2[j], kw["width"], kw["height"], case["radius"]) & d_ok & d_in
+        out += [(int(j), int(i)) for i in np.flatnonzero(cand & ~gate(kw_[j], dw, kw["max_world_distance"]))]
+    return out
 
 
 def hand_case(name):

@@ -58,7 +58,7 @@ def _same_pairs(got, ref, what=""):
 @pytest.mark.parametrize("nk,nd", fr.SIZES)
 def test_entry_sizes(ctx, nk, nd):
     """search, then fuse, at every size at which a kernel takes another path; a few ids are shared between the sides"""
-    case = fr.random_case(100 + nk + nd, nk, nd, shared=3 if min(nk, nd) > 30 else 1 if min(nk, nd) > 3 else 0)
+    case = fr.sized_case(nk, nd)
     store = {1: case["keep"], 2: case["drop"]}
     _fill(ctx, store)
     ref = fr.search(case["keep"], case["drop"], radius=case["radius"], **case["kw"])
