@@ -767,6 +767,30 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* ctx, int keep_id, int drop_id, const double
                       int32_t* keep_pos /* may be NULL, as the next four */, int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid,
                       int32_t* dist, int capacity, int* n_pairs, int* n_rewritten /* may be NULL */);
 
+/* ---- RgbdFeatureFrontend::removeObservation (rgbd_feature_frontend.cpp:469-487, a commented-out body; called at :224-230) ----
+ * THE BODY THE REFERENCE LEAVES COMMENTED OUT: update(const BackendOutputType&) calls removeObservation for every outlier
+ * observation a bundle adjustment reports; the commented code erased the keyframe <-> landmark link and the landmark itself
+ * once no keyframe observed it.  Here the link is a position of a store entry, and the call removes positions.
+ *
+ * Row p names store entry kf_ids[p] and landmark landmark_ids[p]: every position of that entry whose landmark id equals it
+ * is removed.  A repeat inside an entry is one landmark, as for mslam_hip_kf_covisible, so all its positions go.
+ *   survivors   keep their relative order inside the entry; descriptor, world point and landmark id move bit for bit; the
+ *               entry's count drops by the number removed.  An entry emptied this way stays an entry with 0 landmarks.
+ *   untouched   entries that no row names, byte for byte.  What lies behind an entry's new count is unspecified.
+ *   removed[p]  (may be NULL) the number of positions of entry kf_ids[p] that held landmark_ids[p] before the call; 0 when
+ *               the entry does not hold it.  A row listed twice reports the same number in both places.
+ *   *n_removed  (may be NULL) the number of store positions removed, each counted once.
+ * Reserved ids of unions are ordinary entries and may be named.  Nothing else is updated: the landmark stays in every other
+ * entry that holds it, and a union built earlier keeps its copy until it is rebuilt.
+ * Errors: MSLAM_HIP_E_INVALID for n < 0, n > 2^24, NULL lists with n > 0, a landmark id outside [0, 2^63), a keyframe id
+ * that is not in the store; on every error the store is untouched and the outputs are zeroed.  n = 0 is OK.
+ * One upload, one launch (one workgroup per named entry, compacting in place), one synchronisation; deterministic.
+ *   what is erased   SAME as the commented body for the keyframe's side of the link;
+ *   the landmark     DEVIATES: the store has no landmark objects; a landmark no entry holds any more is simply gone.  The
+ *                    host-side bookkeeping of the commented body's last step is HipBackend.remove_observations'. */
+int mslam_hip_kf_remove_observations(mslam_hip_ctx* ctx, const int32_t* kf_ids /* n */, const int64_t* landmark_ids /* n */, int n,
+                                     int32_t* removed /* n, may be NULL */, int* n_removed /* may be NULL */);
+
 /* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
  * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
  * valid; a mask is track()'s depth filter, :317-334).  Per candidate c = cand_ids[k]:

@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
     "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world", "mslam_hip_pose_graph",
     "mslam_hip_kf_fuse_search", "mslam_hip_kf_replace_ids", "mslam_hip_kf_fuse",
+    "mslam_hip_kf_remove_observations",
 ]
 
 
@@ -608,6 +609,20 @@ class Context:
                               max_world_distance, focal, principal, width, height, capacity, (C.byref(nr),))
         out["n_rewritten"] = nr.value
         return out
+
+    # ---- removeObservation (rgbd_feature_frontend.cpp:469-487, commented out in the reference) ----
+    def kf_remove_observations(self, kf_ids, landmark_ids):
+        """row p removes landmark landmark_ids[p] from store entry kf_ids[p], every position that holds it; the survivors
+        keep their order and the entry's count drops -> dict(removed = [n] i32: the positions row p's landmark held before
+        the call, n_removed = the store positions removed, each counted once)"""
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        l = np.ascontiguousarray(landmark_ids, np.int64).reshape(-1)
+        if len(k) != len(l):
+            raise MslamHipError(E_INVALID, "kf_remove_observations: %d keyframe ids, %d landmark ids" % (len(k), len(l)))
+        removed = np.zeros(max(len(k), 1), np.int32)
+        n = C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_remove_observations(self._h, _p(k), _p(l), len(k), _p(removed), C.byref(n)))
+        return dict(removed=removed[:len(k)].copy(), n_removed=n.value)
 
     # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
     def kf_covisible(self, id, ids):
@@ -1203,8 +1218,15 @@ class HipBackend:
     """CeresBackend (ceres_backend.cpp) on Context.bundle_adjust: the keyframes' states (camera -> world: qx qy qz qw px py
     pz), their observations (landmark id, camera-frame point: what ReprojectionError's constructor forms, :24-28) and the
     landmarks' world points, kept on the host; the solve runs on the device.  The first keyframe added is constant, as the
-    reference's keyframe 1 is (:155-159).  Nothing is removed: the outlier observations are returned
-    (removeObservation's body is commented out in the reference).  global_solver = True: global_ba() goes through
+    reference's keyframe 1 is (:155-159).  By default nothing is removed: the outlier observations are returned.
+    remove_observations() is the backend's side of removeObservation (rgbd_feature_frontend.cpp:469-487, a body the
+    reference leaves commented out), and local_ba / global_ba with prune = True use it: solve, remove the result's
+    outlier_observations, and when any were removed solve once more from the refined state (one extra round, not a loop).
+    The returned dict is the last solve's and gains pruned = dict(pairs = [(keyframe id, landmark id), ...], first = the
+    first solve's dict); a FAILURE of the first solve prunes nothing.  The cost has no loss function, so one gross outlier
+    can drag its landmark until the landmark's good observations are flagged too, and the landmark then goes with them.
+    The backend never touches the keyframe store: its caller does (Context.kf_remove_observations with pruned["pairs"]).
+    global_solver = True: global_ba() goes through
     Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes.
     close_loop() is the body of the reference's empty closeLoop (rgbd_feature_frontend.cpp:577-580): a pose graph over every
     keyframe on Context.pose_graph; self.anchor names, per landmark, the keyframe that created it."""
@@ -1281,17 +1303,65 @@ class HipBackend:
                    outlier_observations=[(kf_ids[k], lids[l]) for k, l in zip(okf[res["outlier"]], olm[res["outlier"]])])
         return res
 
-    def local_ba(self, ref_id, graph):
-        """localBundleAdjustment (:162-171): the observations of getNeighbourKeyframes(ref, deepLevel = 1)"""
-        return self._solve(self.neighbours(ref_id, graph, 1))
+    def remove_observations(self, pairs):
+        """removeObservation's bookkeeping (rgbd_feature_frontend.cpp:469-487) for (keyframe id, landmark id) pairs: the
+        named observations leave self.obs, every position that holds the id; a landmark whose anchor keyframe no longer
+        observes it is re-anchored to the smallest keyframe id that still does; a landmark with no observation left leaves
+        `landmarks` and `anchor`.  A pair the backend does not hold is ignored.  -> the number of observations dropped"""
+        gone = {}
+        for kf, lid in pairs:
+            gone.setdefault(int(kf), set()).add(int(lid))
+        n, touched = 0, set()
+        for kf, drop in gone.items():
+            if kf not in self.obs:
+                continue
+            lids, cam = self.obs[kf]
+            hit = np.array([l in drop for l in lids.tolist()], bool).reshape(-1)
+            if hit.any():
+                n += int(np.count_nonzero(hit))
+                touched.update(lids[hit].tolist())
+                self.obs[kf] = (lids[~hit].copy(), cam[~hit].copy())
+        observers = {}
+        if touched:
+            for kf in sorted(self.obs):
+                for l in touched.intersection(self.obs[kf][0].tolist()):
+                    observers.setdefault(l, []).append(kf)
+        for l in touched:
+            who = observers.get(l)
+            if not who:
+                self.landmarks.pop(l, None)
+                self.anchor.pop(l, None)
+            elif self.anchor.get(l) not in who:
+                self.anchor[l] = who[0]
+        return n
 
-    def global_ba(self):
+    def _solve_pruned(self, kf_ids, blocked, prune):
+        """_solve; with prune, the result's outlier observations are removed and, when any were, one more solve from the
+        refined state follows (one extra round, not a loop): the last solve's dict plus pruned = dict(pairs, first)"""
+        res = self._solve(kf_ids, blocked)
+        if not prune:
+            return res
+        first, pairs = dict(res), []
+        if res["termination"] != 2:
+            pairs = sorted(set(res["outlier_observations"]))
+            if self.remove_observations(pairs) > 0:
+                res = self._solve(kf_ids, blocked)
+        res["pruned"] = dict(pairs=pairs, first=first)
+        return res
+
+    def local_ba(self, ref_id, graph, prune=False):
+        """localBundleAdjustment (:162-171): the observations of getNeighbourKeyframes(ref, deepLevel = 1).  prune: see
+        the class docstring"""
+        return self._solve_pruned(self.neighbours(ref_id, graph, 1), False, prune)
+
+    def global_ba(self, prune=False):
         """globalBundleAdjustment (:173-183) over every keyframe; more than 64 (1024 with global_solver) is
-        MslamHipError(E_CAPACITY), raised before the context is touched: the reduced system is dense"""
+        MslamHipError(E_CAPACITY), raised before the context is touched: the reduced system is dense.  prune: see the
+        class docstring"""
         cap = self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
         if len(self.poses) > cap:
             raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
-        return self._solve(sorted(self.poses), self.global_solver)
+        return self._solve_pruned(sorted(self.poses), self.global_solver, prune)
 
     def fuse(self, keep_lids, drop_lids):
         """landmark fusion's bookkeeping: every observation of drop_lids[p] becomes one of keep_lids[p] (simultaneously, the
@@ -1419,7 +1489,17 @@ class HipKeyframeTracker:
     against the old side adds a graph edge wherever the count is positive; the local map is rebuilt.  The attempt's dict
     gains fusion = dict(n_pairs, n_rewritten, edges).  The reserved ids are never in self.ids, the vote list or the
     candidates.  Off (the default): none of this runs and no union is built, so serials and fresh ids are unchanged.
-    STILL OUT: duplicates outside the corrected keyframe's view stay unfused."""
+    STILL OUT: duplicates outside the corrected keyframe's view stay unfused.
+
+    ba_prune = True (needs local_ba, else MslamHipError(E_INVALID)): the consumer of the backend's outlier mask,
+    RgbdFeatureFrontend::update(const BackendOutputType&) (rgbd_feature_frontend.cpp:224-230) with the removeObservation
+    body the reference leaves commented out (:469-487).  The keyframe's solve is HipBackend.local_ba(prune = True);
+    Context.kf_remove_observations then removes pruned["pairs"] from the store (pruned["n_removed"] = the store positions
+    removed), kf_update_world writes the final landmarks and the local map is rebuilt, because the entries changed.  With
+    loop_global_ba the global solve after a loop is pruned the same way.  ba_results still gets one dict per keyframe, and
+    the covisibility graph keeps its edges (the reference's neighbour sets never shrink either).  CAVEAT: there is no loss
+    function, so a gross outlier can drag its landmark until the landmark's good observations are flagged as well; removal
+    then deletes that landmark everywhere, as the reference's pipeline would.  Off by default: nothing is removed."""
 
     LOCAL_MAP_ID = 0x7fffffff
     FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
@@ -1430,8 +1510,11 @@ class HipKeyframeTracker:
                  reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False,
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
-                 loop_fuse_world_distance=0.1):
+                 loop_fuse_world_distance=0.1, ba_prune=False):
         self.ctx = ctx
+        if ba_prune and not local_ba:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_prune needs local_ba (the backend finds the outliers)")
+        self.ba_prune = bool(ba_prune)
         if loop_fusion and not loop_closure:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_fusion needs loop_closure")
         self.loop_fusion, self.loop_fuse_radius = bool(loop_fusion), float(loop_fuse_radius)
@@ -1620,10 +1703,21 @@ class HipKeyframeTracker:
         R = np.asarray(res["R"], np.float64).reshape(3, 3)      # world -> camera; the keyframe's state is camera -> world
         pose = np.concatenate([rotation_to_quaternion(R.T), -R.T @ np.asarray(res["tvec"], np.float64)])
         self.backend.add_keyframe(new_id, pose, self.ctx.kf_read_ids(new_id)[ok], cam[ok])   # (an entry's keypoints have a depth)
-        ba = self.backend.local_ba(new_id, self.graph)
+        ba = self.backend.local_ba(new_id, self.graph, prune=True) if self.ba_prune else self.backend.local_ba(new_id, self.graph)
+        self._prune_store(ba)
         if ba["termination"] != 2:
             ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
         self.ba_results.append(ba)
+
+    def _prune_store(self, ba):
+        """ba_prune: the observations a pruned solve removed from the backend leave the store too, and the union is rebuilt"""
+        pruned = ba.get("pruned")
+        if pruned is None:
+            return
+        pairs = pruned["pairs"]
+        pruned["n_removed"] = self.ctx.kf_remove_observations([k for k, _ in pairs], [l for _, l in pairs])["n_removed"] if pairs else 0
+        if pairs:
+            self._local_map_of = None
 
     def loop_candidates(self, new_id, entries, scores):
         """the filters between the database's hits and the verification -> keyframe ids, best score first, at most
@@ -1666,7 +1760,8 @@ class HipKeyframeTracker:
         if self.loop_fusion:
             attempt["fusion"] = self._fuse_loop(new_id, loop_id)
         if self.loop_global_ba:
-            ba = self.backend.global_ba()
+            ba = self.backend.global_ba(prune=True) if self.ba_prune else self.backend.global_ba()
+            self._prune_store(ba)
             if ba["termination"] != 2:
                 ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
             attempt["global_ba"] = ba

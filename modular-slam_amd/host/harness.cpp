@@ -41,6 +41,10 @@
 //                                    from MSLAM_ORB_VOCABULARY or ./orbvoc.dbow3) on the scene's first two entries, keep then
 //                                    drop: "fuse pairs N rewritten M", one "pair" line per pair, then every entry's landmark
 //                                    ids after the replacement
+//        mslam_harness <plugin.so> --prune <scene>
+//                                    IObservationRemover::removeObservations of the relocalizer adapter on the scene's entries
+//                                    and rows: "prune removed N", one "row <p> <count>" line per row, then per entry
+//                                    "entry <id> n <count> <ids...>" after the removal
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -374,6 +378,111 @@ int main(int argc, char** argv)
             {
                 std::printf("entry %zu ids", e);
                 for(const std::int64_t id : localMap->landmarkIds(entries[e]))
+                    std::printf(" %lld", static_cast<long long>(id));
+                std::printf("\n");
+            }
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--prune") == 0)
+        {
+            // scene file: "MSPR", i32 version (1), i32 number of entries, i32 number of rows; per entry i32 id, i32 n (>= 1),
+            // n x 32 descriptor bytes, n x 3 f64 world points, n x i64 landmark ids; then rows x i32 entry id, rows x i64
+            // landmark id
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[3] = {0, 0, 0};
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            if(!in || std::memcmp(magic, "MSPR", 4) != 0 || head[0] != 1 || head[1] < 1 || head[2] < 0)
+            {
+                std::fprintf(stderr, "%s is not a pruning scene\n", argv[3]);
+                return 5;
+            }
+            auto makeReloc = mslam::loadFactoryMethod<mslam::IOrbRelocalizer>(argv[1], "hipOrbRelocalizerFactory");
+            if(!makeReloc)
+                return 3;
+            std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
+            auto* remover = dynamic_cast<mslam::IObservationRemover*>(relocalizer.get());
+            auto* localMap = dynamic_cast<mslam::ILocalMapTracker*>(relocalizer.get());
+            if(!remover || !localMap)
+            {
+                std::fprintf(stderr, "the plugin does not offer the removal of observations\n");
+                return 6;
+            }
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::vector<std::shared_ptr<Kf>> entries;
+            std::map<std::int32_t, std::shared_ptr<Kf>> byId;
+            std::size_t before = 0;
+            for(std::int32_t e = 0; e < head[1]; ++e)
+            {
+                std::int32_t eh[2] = {0, 0};
+                in.read(reinterpret_cast<char*>(eh), sizeof(eh));
+                if(!in || eh[1] < 1 || eh[1] > 65535 || byId.count(eh[0]))
+                {
+                    std::fprintf(stderr, "entry %d of %s is malformed\n", e, argv[3]);
+                    return 5;
+                }
+                std::vector<mslam::OrbKeypoint> kps(static_cast<std::size_t>(eh[1]));
+                std::vector<mslam::Vector3> world(kps.size());
+                std::vector<std::int64_t> ids(kps.size());
+                for(std::size_t i = 0; i < kps.size(); ++i)
+                {
+                    kps[i].keypoint.id = i;
+                    in.read(reinterpret_cast<char*>(kps[i].descriptor.data()), 32);
+                }
+                for(auto& w : world)
+                    in.read(reinterpret_cast<char*>(w.v), sizeof(w.v));
+                in.read(reinterpret_cast<char*>(ids.data()), static_cast<std::streamsize>(ids.size() * 8));
+                if(!in)
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                    return 5;
+                }
+                auto kf = std::make_shared<Kf>();
+                kf->id = static_cast<mslam::Id>(eh[0]);
+                relocalizer->addKeyframe(kf, kps);
+                localMap->addKeyframeLandmarksWithIds(kf, kps, world, ids);
+                entries.push_back(kf);
+                byId[eh[0]] = kf;
+                before += kps.size();
+            }
+            const std::size_t nRows = static_cast<std::size_t>(head[2]);
+            std::vector<std::int32_t> rowKf(nRows + 1);
+            std::vector<std::int64_t> rowLid(nRows + 1);
+            in.read(reinterpret_cast<char*>(rowKf.data()), static_cast<std::streamsize>(nRows * 4));
+            in.read(reinterpret_cast<char*>(rowLid.data()), static_cast<std::streamsize>(nRows * 8));
+            if(!in)
+            {
+                std::fprintf(stderr, "cannot read the rows of %s\n", argv[3]);
+                return 5;
+            }
+            std::vector<std::pair<std::shared_ptr<Kf>, std::int64_t>> rows;
+            for(std::size_t p = 0; p < nRows; ++p)
+            {
+                const auto it = byId.find(rowKf[p]);
+                if(it == byId.end())
+                {
+                    std::fprintf(stderr, "row %zu of %s names no entry\n", p, argv[3]);
+                    return 5;
+                }
+                rows.emplace_back(it->second, rowLid[p]);
+            }
+            const std::vector<int> removed = remover->removeObservations(rows);
+            // the store's own account: what the entries lost
+            std::vector<std::vector<std::int64_t>> after;
+            std::size_t left = 0;
+            for(const auto& kf : entries)
+            {
+                after.push_back(localMap->landmarkIds(kf));
+                left += after.back().size();
+            }
+            std::printf("prune removed %zu\n", before - left);
+            for(std::size_t p = 0; p < removed.size(); ++p)
+                std::printf("row %zu %d\n", p, removed[p]);
+            for(std::size_t e = 0; e < entries.size(); ++e)
+            {
+                std::printf("entry %lld n %zu", static_cast<long long>(entries[e]->id), after[e].size());
+                for(const std::int64_t id : after[e])
                     std::printf(" %lld", static_cast<long long>(id));
                 std::printf("\n");
             }

@@ -470,7 +470,21 @@ class BowDatabase
         return out;
     }
 
-    KeyframeTrackResult trackAgainst(int refId, const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
+    // ---- removeObservation's body (mslam_hip_kf_remove_observations) ----
+    std::vector<int> removeObservations(const std::vector<std::pair<KeyframePtr, std::int64_t>>& observations)
+    {
+        const std::size_t n = observations.size();
+        std::vector<std::int32_t> ids(n + 1), removed(n + 1);
+        std::vector<std::int64_t> lids(n + 1);
+        for(std::size_t p = 0; p < n; ++p)
+            ids[p] = storedLandmarksOf(observations[p].first), lids[p] = observations[p].second;
+        const int rc = mslam_hip_kf_remove_observations(ctx.h, ids.data(), lids.data(), static_cast<int>(n), removed.data(), nullptr);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_remove_observations", rc);
+        return std::vector<int>(removed.begin(), removed.begin() + static_cast<std::ptrdiff_t>(n));
+    }
+
+    KeyframeTrackResult trackAgainst(int refId,const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                      const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
                                      const double* tvecGuess, const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
     {
@@ -629,7 +643,8 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public IVerifiedRelocalizer,
                           public IKeyframeTracker,
                           public ILocalMapTracker,
-                          public ILandmarkFuser
+                          public ILandmarkFuser,
+                          public IObservationRemover
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -686,6 +701,10 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                                  const double t[3], const LandmarkFuseParams& params) override
     {
         return db->fuseLandmarks(keepEntry, dropEntry, R, t, params);
+    }
+    std::vector<int> removeObservations(const std::vector<std::pair<BowDatabase::KeyframePtr, std::int64_t>>& observations) override
+    {
+        return db->removeObservations(observations);
     }
     KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                       const CameraParameters& camera, const std::vector<BowDatabase::KeyframePtr>& neighbours,

@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <memory>
 #include <optional>
+#include <utility>
 #include <vector>
 
 #include "mslam_camera.hpp"
@@ -394,5 +395,19 @@ class ILandmarkFuser
     virtual LandmarkFusion fuseLandmarks(KeyframePtr keepEntry, KeyframePtr dropEntry, const double R[9], const double t[3],
                                          const LandmarkFuseParams& params) = 0;
     virtual ~ILandmarkFuser() = default;
+};
+
+// ---- RgbdFeatureFrontend::removeObservation (rgbd_feature_frontend.cpp:469-487; mslam_hip_kf_remove_observations) ----------
+// The body the reference leaves commented out: update(const BackendOutputType&) calls it for every outlier observation of a
+// bundle adjustment (:224-230).  Observation p names a stored keyframe and a landmark id; every position of that keyframe's
+// entry that holds the id is removed, the survivors keep their order.  -> per observation, the number of positions its
+// landmark held in its keyframe before the call (0: the keyframe did not hold it; an observation listed twice reports the
+// same number twice).  A keyframe that is not stored throws.  Offered by the adapter that owns the store.
+class IObservationRemover
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual std::vector<int> removeObservations(const std::vector<std::pair<KeyframePtr, std::int64_t>>& observations) = 0;
+    virtual ~IObservationRemover() = default;
 };
 } // namespace mslam
