@@ -89,9 +89,9 @@ def build_entry(desc, xyz, valid, pairs, mask, ref_world, R, t, z_max=3.0, capac
 # ---- one step -------------------------------------------------------------------------------------------------------------
 
 def track(desc, xy, depth, store, ref_id, vote_ids=(), cam=CAM, factor=FACTOR, ratio=0.7, iterations=100, thr=5.0, seed=0,
-          guess=None, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0, want_keyframe=True):
+          guess=None, min_matched_points=10, new_keyframe_min_landmarks=30, z_max=3.0, want_keyframe=True, capacity=None):
     """-> dict(pairs, mask, n_matches, n_correspondences, n_inliers, status, R, t, tracked, keyframe_required, vote_counts,
-    vote_best, vote_best_count, entry (or None), xyz, valid)"""
+    vote_best, vote_best_count, entry (or None), xyz, valid); capacity: the store's entry capacity, handed to build_entry"""
     h, w = np.asarray(depth).shape
     xyz, valid = _oracle().backproject(depth, xy, factor, cam[:2], cam[2:])
     c = rr.relocalize(desc, xy, store, [ref_id], cam, valid=valid, ratio=ratio, iterations=iterations, thr=thr, seed=seed,
@@ -105,7 +105,7 @@ def track(desc, xy, depth, store, ref_id, vote_ids=(), cam=CAM, factor=FACTOR, r
         out["vote_counts"], out["vote_best"] = vote(store, vote_ids, c["R"], c["t"], cam, w, h)
         out["vote_best_count"] = int(out["vote_counts"][out["vote_best"]])
     if required and want_keyframe:
-        out["entry"] = build_entry(desc, xyz, valid, c["pairs"], c["mask"], store[ref_id][1], c["R"], c["t"], z_max)
+        out["entry"] = build_entry(desc, xyz, valid, c["pairs"], c["mask"], store[ref_id][1], c["R"], c["t"], z_max, capacity)
     return out
 
 
