@@ -2,9 +2,9 @@
 //
 // Levenberg-Marquardt over keyframe poses (q, p) and landmarks X of cost = 1/2 sum_m |r_m|^2 with
 //     r_m = rot(q^-1, X) - rot(q^-1, p) - obs_cam[m]                                  (ReprojectionError::operator(), :31-47)
-// The trust-region loop is the one k_pnp_mse.hip restates from Ceres 2.2's published sources (trust_region_minimizer.cc,
-// levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc) with the Solver::Options defaults of solver.h: function
-// tolerance 1e-6, gradient tolerance 1e-10, parameter tolerance 1e-8, initial radius 1e4, monotonic steps, Jacobi scaling.
+// The trust-region loop is Ceres 2.2's, with the Solver::Options defaults: function tolerance 1e-6, gradient tolerance 1e-10,
+// parameter tolerance 1e-8, initial radius 1e4, monotonic steps, Jacobi scaling.  Its control block, decisions, reductions,
+// quaternions and host driver are trust_region.hpp's, shared with k_posegraph.hip; this file holds the blocks of the problem.
 // The SAME / DEVIATES table is in include/mslam_hip.h, the walk-through in DESIGN.md 4.14.  PARITY UNPINNED: no Ceres
 // build exists here; tests/ba_ref.py restates the same algorithm in numpy with two linear solvers.
 //
@@ -31,14 +31,9 @@
 // state has not moved, so the block kernels reuse what they stored and only the damping is redone.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
-#include "ba_solver.hpp"
+#include "chol_solver.hpp"
 
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
 
 namespace mslam
 {
@@ -46,63 +41,40 @@ namespace mslam
 constexpr int kBaMaxKeyframes = 64;
 constexpr int kBagMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES; // mslam_hip_bundle_adjust_global: 6144^2 doubles = 302 MB
 constexpr int kBaSolveThreads = 6 * kBaMaxKeyframes; // one thread per row of the reduced system
-constexpr int kBaBatch = 4;                          // iterations enqueued between two looks at the termination word
-constexpr int kBaMaxInvalidSteps = 5;
-constexpr double kBaInitialRadius = 1e4, kBaMaxRadius = 1e16, kBaMinRadius = 1e-32;
-constexpr double kBaMinDiagonal = 1e-6, kBaMaxDiagonal = 1e32;
-constexpr double kBaMinRelativeDecrease = 1e-3;
-constexpr double kBaFunctionTol = 1e-6, kBaGradientTol = 1e-10, kBaParameterTol = 1e-8;
-constexpr int kBaConvergence = 0, kBaNoConvergence = 1, kBaFailure = 2;
 
-__device__ __forceinline__ double ba_wave_sum(double s)
+struct BaArgs
 {
-    for(int m = 32; m >= 1; m >>= 1)
-        s += __shfl_xor(s, m, 64);
-    return s;
-}
-__device__ __forceinline__ double ba_wave_max(double s)
-{
-    for(int m = 32; m >= 1; m >>= 1)
-        s = fmax(s, __shfl_xor(s, m, 64));
-    return s;
-}
+    int K, L, M, n;     // n = 6 x (free keyframes with observations): the reduced system's size
+    int n_pairs, n_blocks; // pairs of free keyframes; blocks of k_ba_eval
+    int n_pad, ld;         // the blocked solver's padded size and leading dimension (CholArgs)
+    // the problem
+    const int32_t *obs_kf, *obs_lm;
+    const double* obs_cam;
+    const int32_t *lm_ptr, *lm_obs;         // observations by landmark (rows in input order)
+    const int32_t *kf_ptr, *kf_obs, *kf_lm; // observations by keyframe, every row sorted by landmark; kf_lm = the landmark
+    const int32_t* ci;                      // [K] the keyframe's block in the reduced system, -1: constant or unobserved
+    const int32_t* pairs;                   // [n_pairs][2] keyframes k1, k2 with ci[k1] <= ci[k2]
+    const uint8_t* lm_active;               // [L] the landmark has an observation
+    // state and candidate
+    double *pose, *lm, *cand_pose, *cand_lm;
+    // blocks
+    double *V, *gl, *Vinv, *sl; // [L] x 6, 3, 6, 3
+    double *U, *gc, *sc, *W;    // [K] x 21, 6, 6; [M] x 18
+    double *S, *rhs, *yc, *yl;  // n x n column-major, n, n, [L] x 3
+    double* part;               // [2][n_blocks]: model cost change, candidate cost
+    TrCtrl* ctrl;
+    int32_t* h_done; // mapped
+};
 
-__device__ __forceinline__ int ba_tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c < 6
-__device__ __forceinline__ int ba_tri3(int r, int c) { return r * 3 - r * (r - 1) / 2 + (c - r); } // r <= c < 3
-
-// Eigen's inverse(): conjugate / squared norm
-__device__ __forceinline__ void ba_inverse(const double* __restrict__ q, double qi[4])
-{
-    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    qi[0] = -q[0] / n2, qi[1] = -q[1] / n2, qi[2] = -q[2] / n2, qi[3] = q[3] / n2;
-}
-// Eigen's _transformVector: v + w uv + u x uv, uv = 2 (u x v)
-__device__ __forceinline__ void ba_rotate(const double qi[4], const double v[3], double out[3])
-{
-    double uv[3] = {qi[1] * v[2] - qi[2] * v[1], qi[2] * v[0] - qi[0] * v[2], qi[0] * v[1] - qi[1] * v[0]};
-    uv[0] += uv[0], uv[1] += uv[1], uv[2] += uv[2];
-    out[0] = v[0] + qi[3] * uv[0] + (qi[1] * uv[2] - qi[2] * uv[1]);
-    out[1] = v[1] + qi[3] * uv[1] + (qi[2] * uv[0] - qi[0] * uv[2]);
-    out[2] = v[2] + qi[3] * uv[2] + (qi[0] * uv[1] - qi[1] * uv[0]);
-}
 __device__ __forceinline__ void ba_residual(const double* __restrict__ pose, const double* __restrict__ X, const double* __restrict__ obs,
                                             double r[3])
 {
     double qi[4], a[3], b[3];
-    ba_inverse(pose, qi);
+    quat_inverse(pose, qi);
     const double x[3] = {X[0], X[1], X[2]}, p[3] = {pose[4], pose[5], pose[6]};
-    ba_rotate(qi, x, a);
-    ba_rotate(qi, p, b);
+    quat_rotate(qi, x, a);
+    quat_rotate(qi, p, b);
     r[0] = a[0] - b[0] - obs[0], r[1] = a[1] - b[1] - obs[1], r[2] = a[2] - b[2] - obs[2];
-}
-// the matrix of v -> ba_rotate(qi, v): (1 - 2 |u|^2) I + 2 u u^T + 2 w [u]x, row-major
-__device__ __forceinline__ void ba_matrix(const double qi[4], double Rt[9])
-{
-    const double x = qi[0], y = qi[1], z = qi[2], w = qi[3];
-    const double xx = x * x, yy = y * y, zz = z * z;
-    Rt[0] = 1.0 - 2.0 * (yy + zz), Rt[1] = 2.0 * (x * y - w * z), Rt[2] = 2.0 * (x * z + w * y);
-    Rt[3] = 2.0 * (x * y + w * z), Rt[4] = 1.0 - 2.0 * (xx + zz), Rt[5] = 2.0 * (y * z - w * x);
-    Rt[6] = 2.0 * (x * z - w * y), Rt[7] = 2.0 * (y * z + w * x), Rt[8] = 1.0 - 2.0 * (xx + yy);
 }
 // J_c = [2 R^T [d]x | -R^T] (3 x 6), d = X - p
 __device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const double d[3], double Jc[3][6])
@@ -116,28 +88,11 @@ __device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const dou
         }
 }
 
-// EigenQuaternionManifold::Plus (manifold.h QuaternionPlus, x y z w): q_delta (x) q
-__device__ __forceinline__ void ba_quaternion_plus(const double* __restrict__ q, const double d[3], double out[4])
-{
-    const double norm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if(!(norm > 0.0))
-    {
-        out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
-        return;
-    }
-    const double sbd = sin(norm) / norm;
-    const double ax = sbd * d[0], ay = sbd * d[1], az = sbd * d[2], aw = cos(norm);
-    out[0] = aw * q[0] + ax * q[3] + ay * q[2] - az * q[1];
-    out[1] = aw * q[1] + ay * q[3] + az * q[0] - ax * q[2];
-    out[2] = aw * q[2] + az * q[3] + ax * q[1] - ay * q[0];
-    out[3] = aw * q[3] - ax * q[0] - ay * q[1] - az * q[2];
-}
-
 // ---- blocks ------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
 {
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done)
         return;
     const int l = blockIdx.x * 256 + threadIdx.x;
@@ -155,13 +110,13 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
             const int m = a.lm_obs[i];
             const double* pose = a.pose + (size_t)a.obs_kf[m] * 7;
             double qi[4], Rt[9], r[3];
-            ba_inverse(pose, qi);
-            ba_matrix(qi, Rt);
+            quat_inverse(pose, qi);
+            quat_matrix(qi, Rt);
             ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
             for(int rr = 0; rr < 3; ++rr)
             {
                 for(int c = rr; c < 3; ++c)
-                    V[ba_tri3(rr, c)] += Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c];
+                    V[tri3(rr, c)] += Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c];
                 g[rr] += Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2];
             }
         }
@@ -177,7 +132,7 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
     for(int k = 0; k < 3; ++k)
     {
         if(ct->first)
-            a.sl[(size_t)l * 3 + k] = s[k] = 1.0 / (1.0 + sqrt(V[ba_tri3(k, k)]));
+            a.sl[(size_t)l * 3 + k] = s[k] = 1.0 / (1.0 + sqrt(V[tri3(k, k)]));
         else
             s[k] = a.sl[(size_t)l * 3 + k];
     }
@@ -186,9 +141,9 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
     double A[6];
     for(int r = 0; r < 3; ++r)
         for(int c = r; c < 3; ++c)
-            A[ba_tri3(r, c)] = s[r] * V[ba_tri3(r, c)] * s[c];
+            A[tri3(r, c)] = s[r] * V[tri3(r, c)] * s[c];
     for(int k = 0; k < 3; ++k)
-        A[ba_tri3(k, k)] += fmin(fmax(A[ba_tri3(k, k)], kBaMinDiagonal), kBaMaxDiagonal) / radius;
+        A[tri3(k, k)] += fmin(fmax(A[tri3(k, k)], kTrMinDiagonal), kTrMaxDiagonal) / radius;
     const double a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
     const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
     const double det = a00 * c00 + a01 * c01 + a02 * c02;
@@ -200,7 +155,7 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
 __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
 {
     __shared__ double red[4][27];
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done || !ct->need_jac)
         return;
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -208,8 +163,8 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
         return;
     const double* pose = a.pose + (size_t)k * 7;
     double qi[4], Rt[9];
-    ba_inverse(pose, qi);
-    ba_matrix(qi, Rt);
+    quat_inverse(pose, qi);
+    quat_matrix(qi, Rt);
     double acc[27];
     for(int j = 0; j < 27; ++j)
         acc[j] = 0.0;
@@ -234,7 +189,7 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
     }
     for(int j = 0; j < 27; ++j)
     {
-        const double v = ba_wave_sum(acc[j]);
+        const double v = wave_sum(acc[j]);
         if(lane == 0)
             red[wave][j] = v;
     }
@@ -249,58 +204,23 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
     }
     if(tid < 6 && ct->first)
     {
-        const int j = ba_tri(tid, tid);
+        const int j = tri6(tid, tid);
         a.sc[(size_t)k * 6 + tid] = 1.0 / (1.0 + sqrt(((red[0][j] + red[1][j]) + red[2][j]) + red[3][j]));
     }
 }
 
 // ---- FinalizeIterationAndCheckIfMinimizerCanContinue: one wave ------------------------------------------------------------
 
-__device__ __forceinline__ void ba_finish(const BaArgs& a, int lane, int termination)
-{
-    if(lane == 0)
-    {
-        a.ctrl->termination = termination;
-        a.ctrl->done = 1;
-        *a.h_done = 1;
-    }
-}
-
 __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
 {
-    BaCtrl* ct = a.ctrl;
-    if(ct->done)
+    if(a.ctrl->done)
         return;
     const int lane = threadIdx.x;
-    double x_cost = ct->x_cost;
-    if(ct->first)
-    {
-        // iteration 0: the cost at the start, from k_ba_eval's block partials
-        double s = 0.0;
-        for(int b = lane; b < a.n_blocks; b += 64)
-            s += a.part[a.n_blocks + b];
-        x_cost = ba_wave_sum(s);
-    }
-    // the evaluation is usable (ResidualBlock::Evaluate's validity, seen through the sums as in k_pnp_mse.hip), and
-    // |x - Plus(x, -g)|_inf over the ambient parameters
-    bool ok = isfinite(x_cost);
+    bool ok = true;
     double gmax = 0.0;
     for(int k = lane; k < a.K; k += 64)
-    {
-        if(a.ci[k] < 0)
-            continue;
-        const double* q = a.pose + (size_t)k * 7;
-        const double* g = a.gc + (size_t)k * 6;
-        const double md[3] = {-g[0], -g[1], -g[2]};
-        double qp[4];
-        ba_quaternion_plus(q, md, qp);
-        for(int j = 0; j < 4; ++j)
-            gmax = fmax(gmax, fabs(q[j] - qp[j]));
-        for(int j = 0; j < 3; ++j)
-            gmax = fmax(gmax, fabs(q[4 + j] - (q[4 + j] + (-g[3 + j]))));
-        for(int j = 0; j < 6; ++j)
-            ok = ok && isfinite(g[j]) && isfinite(a.U[(size_t)k * 21 + ba_tri(j, j)]);
-    }
+        if(a.ci[k] >= 0)
+            tr_pose_gradient(a.pose + (size_t)k * 7, a.gc + (size_t)k * 6, a.U + (size_t)k * 21, ok, gmax);
     for(int l = lane; l < a.L; l += 64)
     {
         if(!a.lm_active[l])
@@ -310,28 +230,10 @@ __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
         for(int j = 0; j < 3; ++j)
         {
             gmax = fmax(gmax, fabs(X[j] - (X[j] + (-g[j]))));
-            ok = ok && isfinite(g[j]) && isfinite(a.V[(size_t)l * 6 + ba_tri3(j, j)]);
+            ok = ok && isfinite(g[j]) && isfinite(a.V[(size_t)l * 6 + tri3(j, j)]);
         }
     }
-    gmax = ba_wave_max(gmax);
-    ok = __all(ok);
-    if(lane == 0 && ct->first)
-        ct->x_cost = ct->initial_cost = x_cost;
-    if(!ok)
-        return ba_finish(a, lane, kBaFailure);
-    if(ct->iteration >= ct->max_iterations)
-        return ba_finish(a, lane, kBaNoConvergence);
-    if(ct->successful && gmax <= kBaGradientTol)
-        return ba_finish(a, lane, kBaConvergence);
-    if(ct->radius <= kBaMinRadius)
-        return ba_finish(a, lane, kBaConvergence);
-    if(lane == 0)
-    {
-        ct->iteration += 1;
-        ct->successful = 0;
-        ct->first = 0;
-        ct->solve_bad = 0;
-    }
+    tr_check(a.ctrl, a.h_done, lane, a.part, a.n_blocks, ok, gmax);
 }
 
 // ---- the reduced camera system ------------------------------------------------------------------------------------------
@@ -342,7 +244,7 @@ __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
 template <bool kBlocked>
 __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
 {
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done)
         return;
     const int lane = threadIdx.x;
@@ -407,14 +309,14 @@ __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
     double mine = 0.0;
     for(int j = 0; j < 36; ++j)
     {
-        const double v = ba_wave_sum(acc[j]);
+        const double v = wave_sum(acc[j]);
         if(lane == j)
             mine = v;
     }
     if(diag)
         for(int j = 0; j < 6; ++j)
         {
-            const double v = ba_wave_sum(accr[j]);
+            const double v = wave_sum(accr[j]);
             if(lane == 36 + j)
                 mine = v;
         }
@@ -425,10 +327,10 @@ __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
         double v = -mine;
         if(diag)
         {
-            const double u = s1[r] * a.U[(size_t)k1 * 21 + (r <= c ? ba_tri(r, c) : ba_tri(c, r))] * s1[c];
+            const double u = s1[r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * s1[c];
             v = u - mine;
             if(r == c)
-                v = (u + fmin(fmax(u, kBaMinDiagonal), kBaMaxDiagonal) / ct->radius) - mine;
+                v = (u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius) - mine;
         }
         const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
         if(!kBlocked || diag)
@@ -455,7 +357,7 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
     __shared__ double rowj[kBaSolveThreads], b[kBaSolveThreads];
     __shared__ double sdiag;
     __shared__ int bad;
-    BaCtrl* ct = a.ctrl;
+    TrCtrl* ct = a.ctrl;
     if(ct->done)
         return;
     const int i = threadIdx.x, n = a.n;
@@ -512,213 +414,8 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
         ct->solve_bad = 1;
 }
 
-// ---- the blocked solver of mslam_hip_bundle_adjust_global ---------------------------------------------------------------------
-// S is dense, column-major, n_pad = n rounded up to kBagNB columns, leading dimension ld = n_pad + 16: row n_pad carries the
-// right-hand side, so the factorisation of [S b; b^T .] leaves y = L^-1 b there (the forward solve costs one more 16-row
-// tile per panel and no launch).  Right-looking, three launches per panel j on one stream: k_bag_potrf (the diagonal block, one
-// workgroup, in LDS), k_bag_trsm (the rows below it), k_bag_update (every lower tile right of it, on the matrix cores); then
-// k_bag_backsolve per panel from the last to the first.  Only the lower triangle is read.  Every tile's sums have one order.
-
-typedef double bag_d4 __attribute__((ext_vector_type(4)));
-
-// zero below (and in) the diagonal kBagNB-block of every column, 1 on the pad's diagonal; a block per column
-__global__ __launch_bounds__(256) void k_bag_clear(BaArgs a)
-{
-    if(a.ctrl->done)
-        return;
-    const int c = blockIdx.x;
-    double* col = a.S + (size_t)c * a.ld;
-    for(int r = (c / kBagNB) * kBagNB + threadIdx.x; r < a.ld; r += 256)
-        col[r] = (r == c && c >= a.n) ? 1.0 : 0.0;
-}
-
+// the reduced system of mslam_hip_bundle_adjust_global for the blocked solve (chol_solver.hpp)
 __global__ __launch_bounds__(64) void k_bag_schur(BaArgs a) { ba_schur_pair<true>(a); }
-
-// the diagonal block of panel j into LDS (lower triangle, the rest 0)
-__device__ __forceinline__ void bag_load_diag(const BaArgs& a, int j, double (*A)[kBagNB + 1])
-{
-    const double* D = a.S + (size_t)j * kBagNB * ((size_t)a.ld + 1);
-    const int i = threadIdx.x;
-    if(i < kBagNB)
-        for(int c = 0; c < kBagNB; ++c)
-            A[i][c] = c <= i ? D[(size_t)i + (size_t)c * a.ld] : 0.0;
-    __syncthreads();
-}
-
-// Cholesky of the diagonal block of panel j; thread i owns row i, k_ba_solve's pivot rule
-__global__ __launch_bounds__(64) void k_bag_potrf(BaArgs a, int j)
-{
-    __shared__ double A[kBagNB][kBagNB + 1];
-    __shared__ double sdiag;
-    BaCtrl* ct = a.ctrl;
-    if(ct->done)
-        return;
-    const int i = threadIdx.x;
-    bag_load_diag(a, j, A);
-    bool bad = false;
-    for(int jj = 0; jj < kBagNB; ++jj)
-    {
-        double v = 0.0;
-        if(i >= jj && i < kBagNB)
-        {
-            v = A[i][jj];
-            for(int k = 0; k < jj; ++k)
-                v -= A[i][k] * A[jj][k];
-        }
-        if(i == jj)
-        {
-            if(!(v > 0.0))
-                bad = true; // a non-positive pivot: the step is invalid; the factorisation goes on with bounded values
-            sdiag = sqrt(fmax(v, DBL_MIN));
-        }
-        __syncthreads();
-        if(i >= jj && i < kBagNB)
-            A[i][jj] = i == jj ? sdiag : v / sdiag;
-        __syncthreads();
-    }
-    double* D = a.S + (size_t)j * kBagNB * ((size_t)a.ld + 1);
-    if(i < kBagNB)
-        for(int c = 0; c <= i; ++c)
-            D[(size_t)i + (size_t)c * a.ld] = A[i][c];
-    if(bad)
-        ct->solve_bad = 1;
-}
-
-// X L_jj^T = A for the rows below the diagonal block of panel j (the right-hand side's row included): a thread per row
-__global__ __launch_bounds__(64) void k_bag_trsm(BaArgs a, int j)
-{
-    __shared__ double Lj[kBagNB][kBagNB + 1];
-    if(a.ctrl->done)
-        return;
-    bag_load_diag(a, j, Lj);
-    const int row = (j + 1) * kBagNB + blockIdx.x * 64 + threadIdx.x;
-    if(row >= a.ld)
-        return;
-    double* P = a.S + (size_t)row + (size_t)j * kBagNB * a.ld;
-    double x[kBagNB];
-#pragma unroll
-    for(int c = 0; c < kBagNB; ++c)
-        x[c] = P[(size_t)c * a.ld];
-#pragma unroll
-    for(int c = 0; c < kBagNB; ++c)
-    {
-        double v = x[c];
-#pragma unroll
-        for(int k = 0; k < c; ++k)
-            v -= x[k] * Lj[c][k];
-        x[c] = v / Lj[c][c];
-    }
-#pragma unroll
-    for(int c = 0; c < kBagNB; ++c)
-        P[(size_t)c * a.ld] = x[c];
-}
-
-// A_rc -= L_rj L_cj^T for the tile (row block r, column block c), j < c <= r; r = n_pad / kBagNB is the right-hand side's
-// 16 rows.  One wave per tile: 3 x 3 accumulators of v_mfma_f64_16x16x4_f64, 12 steps over the panel's 48 columns.  The wave
-// computes the transposed product (A operand from the column block, B from the row block): a result register then holds 16
-// consecutive rows of one column of S (D: column = lane & 15, row = (lane >> 4) + 4 reg).
-__global__ __launch_bounds__(64) void k_bag_update(BaArgs a, int j)
-{
-    if(a.ctrl->done)
-        return;
-    const int np = a.n_pad / kBagNB;
-    // the grid is the tiles themselves: with nt = np - j - 1 column blocks right of the panel, the lower triangle of nt x nt
-    // blocks row by row (x (x + 1) / 2 + y, y <= x), then the nt tiles of the right-hand side's row
-    const int nt = np - j - 1, tri = nt * (nt + 1) / 2, b = (int)blockIdx.x;
-    int x, y;
-    if(b < tri)
-    {
-        x = (int)((sqrt(8.0 * b + 1.0) - 1.0) / 2.0);
-        if(x * (x + 1) / 2 > b) // the root rounded up or down by one: at most one step either way
-            --x;
-        else if((x + 1) * (x + 2) / 2 <= b)
-            ++x;
-        y = b - x * (x + 1) / 2;
-    }
-    else
-        x = nt, y = b - tri;
-    if(x > nt || y < 0 || y >= nt || y > x)
-        return; // cannot happen for a grid of tri + t blocks: no tile outside S is ever written
-    const int rb = j + 1 + x, cb = j + 1 + y;
-    const int lane = threadIdx.x, lo = lane & 15, hi = lane >> 4;
-    const int mt = rb == np ? 1 : 3; // 16-row tiles of the row block
-    const size_t ld = (size_t)a.ld;
-    const double* Lr = a.S + (size_t)rb * kBagNB + lo + ((size_t)j * kBagNB + hi) * ld;
-    const double* Lc = a.S + (size_t)cb * kBagNB + lo + ((size_t)j * kBagNB + hi) * ld;
-    bag_d4 acc[3][3];
-#pragma unroll
-    for(int ti = 0; ti < 3; ++ti)
-#pragma unroll
-        for(int tj = 0; tj < 3; ++tj)
-            acc[ti][tj] = bag_d4{0.0, 0.0, 0.0, 0.0};
-    for(int ks = 0; ks < kBagNB / 4; ++ks)
-    {
-        double cv[3], rv[3];
-#pragma unroll
-        for(int t = 0; t < 3; ++t)
-        {
-            cv[t] = Lc[t * 16 + (size_t)ks * 4 * ld];
-            rv[t] = t < mt ? Lr[t * 16 + (size_t)ks * 4 * ld] : 0.0;
-        }
-#pragma unroll
-        for(int ti = 0; ti < 3; ++ti)
-#pragma unroll
-            for(int tj = 0; tj < 3; ++tj)
-                acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv[tj], rv[ti], acc[ti][tj], 0, 0, 0);
-    }
-#pragma unroll
-    for(int ti = 0; ti < 3; ++ti)
-    {
-        if(ti >= mt) // wave-uniform
-            break;
-#pragma unroll
-        for(int tj = 0; tj < 3; ++tj)
-#pragma unroll
-            for(int reg = 0; reg < 4; ++reg)
-            {
-                double* C = a.S + ((size_t)rb * kBagNB + ti * 16 + lo) + ((size_t)cb * kBagNB + tj * 16 + hi + 4 * reg) * ld;
-                *C -= acc[ti][tj][reg];
-            }
-    }
-}
-
-// Panel j of L^T x = y, from the last panel to the first.  Every workgroup solves the diagonal block for x_j (the same
-// arithmetic, so the same bits); workgroup j writes it to yc, workgroup b < j takes L_jb^T x_j off y_b.
-__global__ __launch_bounds__(64) void k_bag_backsolve(BaArgs a, int j)
-{
-    __shared__ double Lj[kBagNB][kBagNB + 1];
-    __shared__ double x[kBagNB];
-    if(a.ctrl->done)
-        return;
-    const int i = threadIdx.x, b = blockIdx.x;
-    const size_t ld = (size_t)a.ld, np_ = (size_t)a.n_pad;
-    bag_load_diag(a, j, Lj);
-    if(i < kBagNB)
-        x[i] = a.S[np_ + ((size_t)j * kBagNB + i) * ld];
-    __syncthreads();
-    for(int k = kBagNB - 1; k >= 0; --k)
-    {
-        if(i == k)
-            x[k] = x[k] / Lj[k][k];
-        __syncthreads();
-        if(i < k)
-            x[i] -= Lj[k][i] * x[k];
-        __syncthreads();
-    }
-    if(i >= kBagNB)
-        return;
-    if(b == j)
-    {
-        if(j * kBagNB + i < a.n)
-            a.yc[j * kBagNB + i] = x[i];
-        return;
-    }
-    const size_t col = (size_t)b * kBagNB + i;
-    double s = a.S[np_ + col * ld];
-    for(int r = 0; r < kBagNB; ++r)
-        s -= a.S[(size_t)j * kBagNB + r + col * ld] * x[r];
-    a.S[np_ + col * ld] = s;
-}
 
 __global__ __launch_bounds__(256) void k_ba_backsub(BaArgs a)
 {
@@ -761,23 +458,8 @@ __global__ __launch_bounds__(256) void k_ba_candidate(BaArgs a)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if(t < a.K)
     {
-        const double* x = a.pose + (size_t)t * 7;
-        double* c = a.cand_pose + (size_t)t * 7;
         const int bk = a.ci[t];
-        if(bk < 0)
-        {
-            for(int j = 0; j < 7; ++j)
-                c[j] = x[j];
-            return;
-        }
-        const double* y = a.yc + (size_t)bk * 6;
-        const double* sc = a.sc + (size_t)t * 6;
-        const double d[3] = {-y[0] * sc[0], -y[1] * sc[1], -y[2] * sc[2]};
-        double q[4];
-        ba_quaternion_plus(x, d, q);
-        c[0] = q[0], c[1] = q[1], c[2] = q[2], c[3] = q[3];
-        for(int j = 0; j < 3; ++j)
-            c[4 + j] = x[4 + j] + (-y[3 + j] * sc[3 + j]);
+        tr_pose_plus(a.pose + (size_t)t * 7, bk < 0 ? nullptr : a.yc + (size_t)bk * 6, a.sc + (size_t)t * 6, a.cand_pose + (size_t)t * 7);
     }
     else if(t < a.K + a.L)
     {
@@ -788,18 +470,6 @@ __global__ __launch_bounds__(256) void k_ba_candidate(BaArgs a)
         for(int j = 0; j < 3; ++j)
             c[j] = on ? x[j] + (-a.yl[(size_t)l * 3 + j] * a.sl[(size_t)l * 3 + j]) : x[j];
     }
-}
-
-// the sum of v over the block, by a fixed tree: butterfly per wave, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double ba_block_sum(double v, double* red)
-{
-    v = ba_wave_sum(v);
-    if((threadIdx.x & 63) == 0)
-        red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
 }
 
 // at_start: only the cost at the state (pose, lm), for iteration 0
@@ -823,8 +493,8 @@ __global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
             const double* X = a.lm + (size_t)l * 3;
             double f[3], qi[4], Rt[9];
             ba_residual(pose, X, obs, f);
-            ba_inverse(pose, qi);
-            ba_matrix(qi, Rt);
+            quat_inverse(pose, qi);
+            quat_matrix(qi, Rt);
             // J_s s = R^T (2 d x delta - dp + dX)
             double v[3] = {-a.yl[(size_t)l * 3] * a.sl[(size_t)l * 3], -a.yl[(size_t)l * 3 + 1] * a.sl[(size_t)l * 3 + 1],
                            -a.yl[(size_t)l * 3 + 2] * a.sl[(size_t)l * 3 + 2]};
@@ -847,7 +517,7 @@ __global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
         }
         cost = 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     }
-    const double ms = ba_block_sum(model, red), cs = ba_block_sum(cost, red);
+    const double ms = block_sum(model, red), cs = block_sum(cost, red);
     if(threadIdx.x == 0)
     {
         a.part[blockIdx.x] = ms;
@@ -859,31 +529,14 @@ __global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
 
 __global__ __launch_bounds__(64) void k_ba_control(BaArgs a)
 {
-    BaCtrl* ct = a.ctrl;
-    if(ct->done)
+    if(a.ctrl->done)
         return;
     const int lane = threadIdx.x;
-    double ms = 0.0, cs = 0.0;
-    for(int b = lane; b < a.n_blocks; b += 64)
-        ms += a.part[b], cs += a.part[a.n_blocks + b];
-    const double model_cost_change = ba_wave_sum(ms);
-    double cand_cost = ba_wave_sum(cs);
-    // the step is finite; |x|^2 and |x - candidate|^2 over the ambient parameters of the problem's blocks
     bool finite = true;
     double xn = 0.0, sn = 0.0;
     for(int k = lane; k < a.K; k += 64)
-    {
-        const int bk = a.ci[k];
-        if(bk < 0)
-            continue;
-        for(int j = 0; j < 6; ++j)
-            finite = finite && isfinite(a.yc[(size_t)bk * 6 + j]);
-        for(int j = 0; j < 7; ++j)
-        {
-            const double x = a.pose[(size_t)k * 7 + j], d = x - a.cand_pose[(size_t)k * 7 + j];
-            xn += x * x, sn += d * d;
-        }
-    }
+        if(a.ci[k] >= 0)
+            tr_pose_step(a.pose + (size_t)k * 7, a.cand_pose + (size_t)k * 7, a.yc + (size_t)a.ci[k] * 6, finite, xn, sn);
     for(int l = lane; l < a.L; l += 64)
     {
         if(!a.lm_active[l])
@@ -895,63 +548,16 @@ __global__ __launch_bounds__(64) void k_ba_control(BaArgs a)
             xn += x * x, sn += d * d;
         }
     }
-    finite = __all(finite);
-    const double x_norm = sqrt(ba_wave_sum(xn)), step_norm = sqrt(ba_wave_sum(sn));
-    const double x_cost = ct->x_cost;
-    double radius = ct->radius, decrease_factor = ct->decrease_factor;
-    if(!(finite && !ct->solve_bad && model_cost_change > 0.0))
-    {
-        // HandleInvalidStep
-        if(lane == 0)
-            ct->invalid_total += 1;
-        if(ct->invalid_run + 1 >= kBaMaxInvalidSteps)
-            return ba_finish(a, lane, kBaFailure);
-        if(lane == 0)
-        {
-            ct->invalid_run += 1;
-            ct->radius = radius / decrease_factor;
-            ct->decrease_factor = decrease_factor * 2.0;
-            ct->need_jac = 0;
-        }
+    if(!tr_control(a.ctrl, a.h_done, lane, a.part, a.n_blocks, finite, xn, sn))
         return;
-    }
-    if(!isfinite(cand_cost))
-        cand_cost = DBL_MAX;
-    if(lane == 0)
-        ct->invalid_run = 0;
-    if(step_norm <= kBaParameterTol * (x_norm + kBaParameterTol))
-        return ba_finish(a, lane, kBaConvergence);
-    if(fabs(x_cost - cand_cost) <= kBaFunctionTol * x_cost)
-        return ba_finish(a, lane, kBaConvergence);
-    const double relative_decrease = cand_cost >= DBL_MAX ? -DBL_MAX : (x_cost - cand_cost) / model_cost_change;
-    if(relative_decrease > kBaMinRelativeDecrease)
-    {
-        for(int k = lane; k < a.K; k += 64)
-            if(a.ci[k] >= 0)
-                for(int j = 0; j < 7; ++j)
-                    a.pose[(size_t)k * 7 + j] = a.cand_pose[(size_t)k * 7 + j];
-        for(int l = lane; l < a.L; l += 64)
-            if(a.lm_active[l])
-                for(int j = 0; j < 3; ++j)
-                    a.lm[(size_t)l * 3 + j] = a.cand_lm[(size_t)l * 3 + j];
-        if(lane == 0)
-        {
-            const double q = 2.0 * relative_decrease - 1.0;
-            radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
-            ct->radius = fmin(kBaMaxRadius, radius);
-            ct->decrease_factor = 2.0;
-            ct->x_cost = cand_cost;
-            ct->successful = 1;
-            ct->need_jac = 1;
-        }
-    }
-    else if(lane == 0)
-    {
-        ct->rejected += 1;
-        ct->radius = radius / decrease_factor;
-        ct->decrease_factor = decrease_factor * 2.0;
-        ct->need_jac = 0;
-    }
+    for(int k = lane; k < a.K; k += 64)
+        if(a.ci[k] >= 0)
+            for(int j = 0; j < 7; ++j)
+                a.pose[(size_t)k * 7 + j] = a.cand_pose[(size_t)k * 7 + j];
+    for(int l = lane; l < a.L; l += 64)
+        if(a.lm_active[l])
+            for(int j = 0; j < 3; ++j)
+                a.lm[(size_t)l * 3 + j] = a.cand_lm[(size_t)l * 3 + j];
 }
 
 // createOutput (:212-230): |r_m|^2 > threshold^2 at (pose, lm)
@@ -964,33 +570,6 @@ __global__ __launch_bounds__(256) void k_ba_outliers(BaArgs a, const double* __r
     double r[3];
     ba_residual(pose + (size_t)a.obs_kf[m] * 7, lm + (size_t)a.obs_lm[m] * 3, a.obs_cam + (size_t)m * 3, r);
     out[m] = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) > threshold2 ? 1 : 0;
-}
-
-// ba_solver.hpp: the blocked solve of mslam_hip_bundle_adjust_global and of mslam_hip_pose_graph (k_posegraph.hip)
-void ba_blocked_solve(mslam_hip_ctx* c, const BaArgs& a, hipStream_t s, const std::function<void()>& assemble)
-{
-    const int np = a.n_pad / kBagNB;
-    {
-        StageScope tk(c, "solver_schur");
-        hipLaunchKernelGGL(k_bag_clear, dim3((unsigned)a.n_pad), dim3(256), 0, s, a);
-        assemble();
-    }
-    {
-        StageScope tk(c, "solver_factor");
-        for(int j = 0; j < np; ++j)
-        {
-            hipLaunchKernelGGL(k_bag_potrf, dim3(1), dim3(64), 0, s, a, j);
-            hipLaunchKernelGGL(k_bag_trsm, dim3((unsigned)((a.ld - (j + 1) * kBagNB + 63) / 64)), dim3(64), 0, s, a, j);
-            if(j + 1 < np)
-            {
-                const unsigned t = (unsigned)(np - j - 1); // column blocks right of the panel
-                hipLaunchKernelGGL(k_bag_update, dim3(t * (t + 1) / 2 + t), dim3(64), 0, s, a, j);
-            }
-        }
-    }
-    StageScope tk(c, "solver_subst");
-    for(int j = np - 1; j >= 0; --j)
-        hipLaunchKernelGGL(k_bag_backsolve, dim3((unsigned)(j + 1)), dim3(64), 0, s, a, j);
 }
 
 } // namespace mslam
@@ -1014,12 +593,8 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
         if(obs_kf[m] < 0 || obs_kf[m] >= K || obs_lm[m] < 0 || obs_lm[m] >= L)
             return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: observation " + std::to_string(m) + " names a keyframe or landmark out of range");
     for(int k = 0; k < K; ++k)
-    {
-        const double* q = poses + (size_t)k * 7;
-        const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        if(!(std::fabs(norm - 1.0) <= 1e-6))
+        if(!tr_unit_quaternion(poses + (size_t)k * 7))
             return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: the quaternion of pose " + std::to_string(k) + " is not unit");
-    }
     mslam_hip_ba_summary sum{};
     if(M == 0)
     {
@@ -1101,46 +676,27 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (M + 255) / 256;
     if(blocked)
         a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
-    // one block: what is uploaded first, then the working arrays
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 15) & ~(size_t)15;
-        return at;
-    };
-    const size_t o_ctrl = carve(sizeof(BaCtrl)), o_pose = carve((size_t)K * 56), o_lm = carve((size_t)L * 24), o_cam = carve((size_t)M * 24);
-    const size_t o_okf = carve((size_t)M * 4), o_olm = carve((size_t)M * 4), o_lptr = carve(((size_t)L + 1) * 4), o_lobs = carve((size_t)M * 4);
-    const size_t o_kptr = carve(((size_t)K + 1) * 4), o_kobs = carve((size_t)M * 4), o_klm = carve((size_t)M * 4), o_ci = carve((size_t)K * 4);
-    const size_t o_pairs = carve(pairs.size() * 4), o_act = carve((size_t)L);
-    const size_t up_bytes = off;
-    const size_t o_pose0 = carve((size_t)K * 56), o_lm0 = carve((size_t)L * 24), o_cpose = carve((size_t)K * 56), o_clm = carve((size_t)L * 24);
-    const size_t o_V = carve((size_t)L * 48), o_gl = carve((size_t)L * 24), o_Vinv = carve((size_t)L * 48), o_sl = carve((size_t)L * 24);
-    const size_t o_U = carve((size_t)K * 168), o_gc = carve((size_t)K * 48), o_sc = carve((size_t)K * 48), o_W = carve((size_t)M * 144);
-    const size_t o_S = carve(blocked ? 0 : (size_t)a.n * a.n * 8), o_rhs = carve((size_t)a.n * 8), o_yc = carve((size_t)a.n * 8), o_yl = carve((size_t)L * 24);
-    const size_t o_part = carve((size_t)a.n_blocks * 16), o_out = carve((size_t)M);
+    // one block: what is uploaded first (the control block at 0), then the working arrays
+    TrStaging st(max_iterations);
+    const size_t o_pose = st.put(poses, (size_t)K * 56), o_lm = st.put(landmarks, (size_t)L * 24), o_cam = st.put(obs_cam, (size_t)M * 24);
+    const size_t o_okf = st.put(obs_kf, (size_t)M * 4), o_olm = st.put(obs_lm, (size_t)M * 4), o_lptr = st.put(lm_ptr.data(), ((size_t)L + 1) * 4);
+    const size_t o_lobs = st.put(lm_obs.data(), (size_t)M * 4), o_kptr = st.put(kf_ptr.data(), ((size_t)K + 1) * 4);
+    const size_t o_kobs = st.put(kf_obs.data(), (size_t)M * 4), o_klm = st.put(kf_lm.data(), (size_t)M * 4), o_ci = st.put(ci.data(), (size_t)K * 4);
+    const size_t o_pairs = st.put(pairs.data(), pairs.size() * 4), o_act = st.put(lm_active.data(), (size_t)L);
+    const size_t o_pose0 = st.carve((size_t)K * 56), o_lm0 = st.carve((size_t)L * 24), o_cpose = st.carve((size_t)K * 56), o_clm = st.carve((size_t)L * 24);
+    const size_t o_V = st.carve((size_t)L * 48), o_gl = st.carve((size_t)L * 24), o_Vinv = st.carve((size_t)L * 48), o_sl = st.carve((size_t)L * 24);
+    const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_W = st.carve((size_t)M * 144);
+    const size_t o_S = st.carve(blocked ? 0 : (size_t)a.n * a.n * 8), o_rhs = st.carve((size_t)a.n * 8), o_yc = st.carve((size_t)a.n * 8);
+    const size_t o_yl = st.carve((size_t)L * 24), o_part = st.carve((size_t)a.n_blocks * 16), o_out = st.carve((size_t)M);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
-    MSLAM_CHK(c, grow(c->d_ba, off, c->stream));
+    MSLAM_CHK(c, grow(c->d_ba, st.size, c->stream));
     if(blocked)
         MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
-    std::vector<uint8_t> stage(up_bytes, 0);
-    BaCtrl ctrl{};
-    ctrl.need_jac = 1, ctrl.first = 1, ctrl.successful = 1, ctrl.max_iterations = max_iterations;
-    ctrl.radius = kBaInitialRadius, ctrl.decrease_factor = 2.0;
-    std::memcpy(&stage[o_ctrl], &ctrl, sizeof(ctrl));
-    auto put = [&](size_t at, const void* src, size_t bytes) {
-        if(bytes)
-            std::memcpy(&stage[at], src, bytes);
-    };
-    put(o_pose, poses, (size_t)K * 56), put(o_lm, landmarks, (size_t)L * 24), put(o_cam, obs_cam, (size_t)M * 24);
-    put(o_okf, obs_kf, (size_t)M * 4), put(o_olm, obs_lm, (size_t)M * 4), put(o_lptr, lm_ptr.data(), ((size_t)L + 1) * 4);
-    put(o_lobs, lm_obs.data(), (size_t)M * 4), put(o_kptr, kf_ptr.data(), ((size_t)K + 1) * 4), put(o_kobs, kf_obs.data(), (size_t)M * 4);
-    put(o_klm, kf_lm.data(), (size_t)M * 4), put(o_ci, ci.data(), (size_t)K * 4), put(o_pairs, pairs.data(), pairs.size() * 4);
-    put(o_act, lm_active.data(), (size_t)L);
     uint8_t* d = c->d_ba;
     hipStream_t s = c->stream;
-    MSLAM_CHK(c, hipMemcpyAsync(d, stage.data(), up_bytes, hipMemcpyHostToDevice, s));
+    MSLAM_CHK(c, st.upload(d, s));
     // the inputs are kept: a FAILURE judges the outliers there
     MSLAM_CHK(c, hipMemcpyAsync(d + o_pose0, d + o_pose, (size_t)K * 56, hipMemcpyDeviceToDevice, s));
     MSLAM_CHK(c, hipMemcpyAsync(d + o_lm0, d + o_lm, (size_t)L * 24, hipMemcpyDeviceToDevice, s));
@@ -1153,53 +709,42 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     a.V = dbl(o_V), a.gl = dbl(o_gl), a.Vinv = dbl(o_Vinv), a.sl = dbl(o_sl);
     a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.W = dbl(o_W);
     a.S = blocked ? c->d_ba_S.get() : dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
-    a.ctrl = reinterpret_cast<BaCtrl*>(d + o_ctrl);
+    a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
+    const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
 
     const dim3 g_lm((unsigned)((L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((K + L + 255) / 256));
     {
         StageScope ts(c, "ba_start_cost");
         hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
     }
-    // iteration max_iterations + 1 only reaches k_ba_check, which ends the solve with NO_CONVERGENCE
-    for(int it = 0; it <= max_iterations;)
-    {
-        StageScope ts(c, "ba_iterations");
-        for(int b = 0; b < kBaBatch && it <= max_iterations; ++b, ++it)
+    const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
+        hipLaunchKernelGGL(k_ba_landmarks, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
+        if(a.n_pairs > 0 && !blocked)
         {
-            hipLaunchKernelGGL(k_ba_landmarks, g_lm, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
-            if(a.n_pairs > 0 && !blocked)
             {
-                {
-                    StageScope tk(c, "solver_schur");
-                    hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
-                }
-                StageScope tk(c, "solver_factor_subst");
-                hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
+                StageScope tk(c, "solver_schur");
+                hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
             }
-            else if(a.n_pairs > 0)
-            {
-                // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
-                ba_blocked_solve(c, a, s, [&] { hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-            }
-            hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
-            hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+            StageScope tk(c, "solver_factor_subst");
+            hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
         }
-        MSLAM_CHK(c, hipGetLastError());
-        MSLAM_CHK(c, hipStreamSynchronize(s));
-        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
-            break;
-    }
-    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    if(!ctrl.done)
-        return fail(c, MSLAM_HIP_E_RUNTIME, "bundle_adjust: the kernels left no termination");
-    const bool usable = ctrl.termination != kBaFailure;
+        else if(a.n_pairs > 0)
+        {
+            // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
+            ba_blocked_solve(c, chol, s, [&] { hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+        }
+        hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
+        hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+    }, sum);
+    if(rc != MSLAM_HIP_OK)
+        return rc;
+    const bool usable = sum.termination != kTrFailure;
     std::vector<uint8_t> mask((size_t)M);
     hipLaunchKernelGGL(k_ba_outliers, g_obs, dim3(256), 0, s, a, dbl(usable ? o_pose : o_pose0), dbl(usable ? o_lm : o_lm0),
                        outlier_threshold * outlier_threshold, d + o_out);
@@ -1212,9 +757,6 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
         MSLAM_CHK(c, hipMemcpyAsync(xl.data(), a.lm, (size_t)L * 24, hipMemcpyDeviceToHost, s));
     }
     MSLAM_CHK(c, hipStreamSynchronize(s));
-    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
-    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
-    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
     for(int m = 0; m < M; ++m)
         sum.n_outliers += mask[(size_t)m] ? 1 : 0;
     if(outlier)

@@ -4,8 +4,10 @@
 // solve over x = (r, t) (angle-axis r, translation t) of
 //     cost(x) = 1/2 sum_i |obs_i - proj(AngleAxisRotatePoint(r, P_i) + t)|^2,   proj(X) = (fx X/Z + cx, fy Y/Z + cy)
 // with no loss function, started from the caller's pose, gradient / function / parameter tolerance 1e-8 (:88-90) and
-// every other option at Solver::Options' default.  The minimiser restated here is Ceres 2.2's published trust-region
-// loop (trust_region_minimizer.cc, levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc, solver.cc); the
+// every other option at Solver::Options' default.  The minimiser is Ceres 2.2's published trust-region loop
+// (trust_region_minimizer.cc, levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc, solver.cc), written out
+// here for a wave that keeps one problem in registers; the defaults, the termination codes and the butterfly sum are
+// trust_region.hpp's, which holds the same loop as control-block kernels for k_ba.hip and k_posegraph.hip.  The
 // SAME / DEVIATES table is in include/mslam_hip.h, the walk-through in DESIGN.md.  Parity with a Ceres build is UNPINNED
 // (none exists in this image); tests/mse_pnp_ref.py restates the same algorithm in numpy and the tests pin both against
 // each other and against ground truth.
@@ -17,14 +19,9 @@
 // 6x6 solve and the trust-region bookkeeping redundantly in registers.  No LDS, no barriers, uniform control flow.
 // Each trust-region iteration is one sweep over the points at the candidate point (value and derivatives together:
 // an accepted candidate needs its Jacobian next, a rejected one discards it).  All arithmetic is f64.
-#include "context.hpp"
+#include "trust_region.hpp"
 
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
 
 namespace mslam
 {
@@ -32,16 +29,10 @@ namespace mslam
 constexpr int kMseWaves = 4; // problems (waves) per workgroup
 constexpr int kMseThreads = 64 * kMseWaves;
 
-// Solver::Options defaults (solver.h) and the three tolerances of the call site (ceres_reprojection_error_pnp.cpp:88-90)
+// what differs from trust_region.hpp's Solver::Options defaults: max_num_iterations, and the three tolerances of the call
+// site (ceres_reprojection_error_pnp.cpp:88-90)
 constexpr int kMseMaxIterations = 50;
-constexpr int kMseMaxInvalidSteps = 5;
-constexpr double kMseInitialRadius = 1e4, kMseMaxRadius = 1e16, kMseMinRadius = 1e-32;
-constexpr double kMseMinDiagonal = 1e-6, kMseMaxDiagonal = 1e32;
-constexpr double kMseMinRelativeDecrease = 1e-3;
 constexpr double kMseGradientTol = 1e-8, kMseFunctionTol = 1e-8, kMseParameterTol = 1e-8;
-
-// ceres::TerminationType
-constexpr int kMseConvergence = 0, kMseNoConvergence = 1, kMseFailure = 2;
 
 struct MseArgs
 {
@@ -211,14 +202,6 @@ struct MseSums
     double g[6];
 };
 
-__device__ __forceinline__ double wave_sum(double s)
-{
-    // fixed-order butterfly: after the step with mask m, lanes l and l ^ m hold s_l + s_(l^m) = s_(l^m) + s_l
-    for(int m = 32; m >= 1; m >>= 1)
-        s += __shfl_xor(s, m, 64);
-    return s;
-}
-
 __device__ void mse_sweep(const MseArgs& a, const double* obj, const double* img, int n, int lane, const double x[6], MseSums& S)
 {
     S.cost = 0.0;
@@ -247,8 +230,6 @@ __device__ void mse_sweep(const MseArgs& a, const double* obj, const double* img
         S.g[k] = wave_sum(S.g[k]);
 }
 
-__device__ __forceinline__ int tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c
-
 // the sums are usable as an evaluation with a Jacobian.  ResidualBlock::Evaluate rejects non-finite residuals or Jacobian
 // entries, and any such entry makes the cost or a diagonal entry of J^T J (a sum of squares) non-finite.  The converse
 // does not hold: a finite entry above sqrt(DBL_MAX), about 1.3e154, squares to infinity, so such an evaluation fails here
@@ -257,7 +238,7 @@ __device__ __forceinline__ bool sums_finite(const MseSums& S)
 {
     bool ok = isfinite(S.cost);
     for(int r = 0; r < 6; ++r)
-        ok = ok && isfinite(S.H[tri(r, r)]) && isfinite(S.g[r]);
+        ok = ok && isfinite(S.H[tri6(r, r)]) && isfinite(S.g[r]);
     return ok;
 }
 
@@ -289,13 +270,13 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
     };
     if(n < 0 || n > a.capacity)
     {
-        finish(kMseFailure, 0, NAN, NAN, false);
+        finish(kTrFailure, 0, NAN, NAN, false);
         return;
     }
     if(n == 0)
     {
         // solver.cc Minimize(): a reduced program without parameter blocks is CONVERGENCE at cost 0, parameters untouched
-        finish(kMseConvergence, 0, 0.0, 0.0, false);
+        finish(kTrConvergence, 0, 0.0, 0.0, false);
         return;
     }
     const double* obj = a.obj + (size_t)p * a.capacity * 3;
@@ -307,15 +288,15 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
     const double initial_cost = X.cost;
     if(!sums_finite(X))
     {
-        finish(kMseFailure, 0, initial_cost, initial_cost, false);
+        finish(kTrFailure, 0, initial_cost, initial_cost, false);
         return;
     }
     // Jacobi scaling, once, from the Jacobian at the start: 1 / (1 + |J_col|)
     double s[6];
     for(int k = 0; k < 6; ++k)
-        s[k] = 1.0 / (1.0 + sqrt(X.H[tri(k, k)]));
+        s[k] = 1.0 / (1.0 + sqrt(X.H[tri6(k, k)]));
     double gmax = gradient_max_norm(x, X.g);
-    double radius = kMseInitialRadius, decrease_factor = 2.0;
+    double radius = kTrInitialRadius, decrease_factor = 2.0;
     int invalid_steps = 0, iteration = 0;
     bool successful = true;
     for(;;)
@@ -323,17 +304,17 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         // FinalizeIterationAndCheckIfMinimizerCanContinue
         if(iteration >= kMseMaxIterations)
         {
-            finish(kMseNoConvergence, iteration, initial_cost, X.cost, true);
+            finish(kTrNoConvergence, iteration, initial_cost, X.cost, true);
             return;
         }
         if(successful && gmax <= kMseGradientTol)
         {
-            finish(kMseConvergence, iteration, initial_cost, X.cost, true);
+            finish(kTrConvergence, iteration, initial_cost, X.cost, true);
             return;
         }
-        if(radius <= kMseMinRadius)
+        if(radius <= kTrMinRadius)
         {
-            finish(kMseConvergence, iteration, initial_cost, X.cost, true);
+            finish(kTrConvergence, iteration, initial_cost, X.cost, true);
             return;
         }
         ++iteration;
@@ -346,34 +327,34 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         {
             gs[r] = s[r] * X.g[r];
             for(int c = r; c < 6; ++c)
-                A[tri(r, c)] = s[r] * X.H[tri(r, c)] * s[c];
+                A[tri6(r, c)] = s[r] * X.H[tri6(r, c)] * s[c];
         }
         double Hs_diag[6];
         for(int k = 0; k < 6; ++k)
         {
-            Hs_diag[k] = A[tri(k, k)];
-            A[tri(k, k)] += fmin(fmax(Hs_diag[k], kMseMinDiagonal), kMseMaxDiagonal) / radius;
+            Hs_diag[k] = A[tri6(k, k)];
+            A[tri6(k, k)] += fmin(fmax(Hs_diag[k], kTrMinDiagonal), kTrMaxDiagonal) / radius;
         }
-        // Cholesky A = L L^T in place (lower triangle stored at tri(c, r)); a non-positive pivot is a linear-solver failure
+        // Cholesky A = L L^T in place (lower triangle stored at tri6(c, r)); a non-positive pivot is a linear-solver failure
         bool solved = true;
         double L[21];
         for(int k = 0; k < 21; ++k)
             L[k] = A[k];
         for(int j = 0; j < 6; ++j)
         {
-            double d = L[tri(j, j)];
+            double d = L[tri6(j, j)];
             for(int k = 0; k < j; ++k)
-                d -= L[tri(k, j)] * L[tri(k, j)];
+                d -= L[tri6(k, j)] * L[tri6(k, j)];
             if(!(d > 0.0))
                 solved = false;
             d = sqrt(fmax(d, DBL_MIN));
-            L[tri(j, j)] = d;
+            L[tri6(j, j)] = d;
             for(int i = j + 1; i < 6; ++i)
             {
-                double e = L[tri(j, i)];
+                double e = L[tri6(j, i)];
                 for(int k = 0; k < j; ++k)
-                    e -= L[tri(k, i)] * L[tri(k, j)];
-                L[tri(j, i)] = e / d;
+                    e -= L[tri6(k, i)] * L[tri6(k, j)];
+                L[tri6(j, i)] = e / d;
             }
         }
         double ds[6];
@@ -381,15 +362,15 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         {
             double e = gs[i];
             for(int k = 0; k < i; ++k)
-                e -= L[tri(k, i)] * ds[k];
-            ds[i] = e / L[tri(i, i)];
+                e -= L[tri6(k, i)] * ds[k];
+            ds[i] = e / L[tri6(i, i)];
         }
         for(int i = 5; i >= 0; --i)
         {
             double e = ds[i];
             for(int k = i + 1; k < 6; ++k)
-                e -= L[tri(i, k)] * ds[k];
-            ds[i] = e / L[tri(i, i)];
+                e -= L[tri6(i, k)] * ds[k];
+            ds[i] = e / L[tri6(i, i)];
         }
         for(int k = 0; k < 6; ++k)
         {
@@ -406,7 +387,7 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
                 lin += gs[r] * ds[r];
                 double hr = 0.0;
                 for(int c = 0; c < 6; ++c)
-                    hr += s[r] * X.H[r <= c ? tri(r, c) : tri(c, r)] * s[c] * ds[c];
+                    hr += s[r] * X.H[r <= c ? tri6(r, c) : tri6(c, r)] * s[c] * ds[c];
                 quad += ds[r] * hr;
             }
             model_cost_change = -(lin + 0.5 * quad);
@@ -414,9 +395,9 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         if(!(solved && model_cost_change > 0.0))
         {
             // HandleInvalidStep
-            if(++invalid_steps >= kMseMaxInvalidSteps)
+            if(++invalid_steps >= kTrMaxInvalidSteps)
             {
-                finish(kMseFailure, iteration, initial_cost, X.cost, false);
+                finish(kTrFailure, iteration, initial_cost, X.cost, false);
                 return;
             }
             radius /= decrease_factor; // StepIsInvalid = StepRejected(0)
@@ -441,23 +422,23 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         }
         if(sqrt(step_norm2) <= kMseParameterTol * (sqrt(x_norm2) + kMseParameterTol))
         {
-            finish(kMseConvergence, iteration, initial_cost, X.cost, true);
+            finish(kTrConvergence, iteration, initial_cost, X.cost, true);
             return;
         }
         // FunctionToleranceReached
         if(fabs(X.cost - cand_cost) <= kMseFunctionTol * X.cost)
         {
-            finish(kMseConvergence, iteration, initial_cost, X.cost, true);
+            finish(kTrConvergence, iteration, initial_cost, X.cost, true);
             return;
         }
         // IsStepSuccessful (monotonic: the step evaluator's reference cost is the current cost)
         const double relative_decrease = cand_cost >= DBL_MAX ? -DBL_MAX : (X.cost - cand_cost) / model_cost_change;
-        if(relative_decrease > kMseMinRelativeDecrease)
+        if(relative_decrease > kTrMinRelativeDecrease)
         {
             // HandleSuccessfulStep: the Jacobian at the new point
             if(!sums_finite(C))
             {
-                finish(kMseFailure, iteration, initial_cost, X.cost, false);
+                finish(kTrFailure, iteration, initial_cost, X.cost, false);
                 return;
             }
             for(int k = 0; k < 6; ++k)
@@ -467,7 +448,7 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
             successful = true;
             const double q = 2.0 * relative_decrease - 1.0;
             radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
-            radius = fmin(kMseMaxRadius, radius);
+            radius = fmin(kTrMaxRadius, radius);
             decrease_factor = 2.0;
         }
         else
@@ -555,7 +536,7 @@ extern "C" int mslam_hip_pnp_min_mse(mslam_hip_ctx* c, const double* object_poin
         *iterations = (int)out[7];
     if(final_cost)
         *final_cost = out[9];
-    if(term == kMseFailure) // Summary::IsSolutionUsable() == false
+    if(term == kTrFailure) // Summary::IsSolutionUsable() == false
         return fail(MSLAM_HIP_E_NO_MODEL, "pnp_min_mse: the minimiser ended in FAILURE (non-finite cost or Jacobian, or "
                                           "5 invalid steps in a row)");
     rvec[0] = out[0], rvec[1] = out[1], rvec[2] = out[2];

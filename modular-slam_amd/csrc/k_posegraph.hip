@@ -8,11 +8,10 @@
 //     r_e  = sqrt_info_e [p_ab - p_meas ; 2 vec(delta)]
 // No sign fix is applied on delta: a measurement entered as -q_meas, or a pose as -q, turns vec(delta) round.  Inverses are
 // Eigen's inverse() (conjugate / squared norm), products Eigen's quaternion product, as in k_ba.hip.
-// The trust-region loop is the one k_ba.hip restates from k_pnp_mse.hip (Ceres 2.2's trust_region_minimizer.cc,
-// levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc, the Solver::Options defaults of solver.h); it is restated
-// here once more, without the landmarks.  The SAME / DEVIATES table is in include/mslam_hip.h, the walk-through in DESIGN.md
-// 4.17.  PARITY UNPINNED: no Ceres build exists here; tests/pose_graph_ref.py restates the algorithm in numpy (jets, two
-// linear solvers).
+// The trust-region loop is k_ba.hip's without the landmarks: its control block, decisions, reductions, quaternions and host
+// driver are trust_region.hpp's, and this file holds the blocks of the problem.  The SAME / DEVIATES table is in
+// include/mslam_hip.h, the walk-through in DESIGN.md 4.17.  PARITY UNPINNED: no Ceres build exists here;
+// tests/pose_graph_ref.py restates the algorithm in numpy (jets, two linear solvers).
 //
 // A free pose has the tangent (delta, dp) of k_ba.hip: Plus = q_delta (x) q and the position.  With R_a^T the matrix of
 // v -> rot(q_a^-1, v), v = p_b - p_a, and M the 3 x 3 matrix of u -> vec(A (x) (u, 0) (x) B), A = q_meas (x) q_b^-1, B = q_a
@@ -28,7 +27,7 @@
 //   k_pg_poses      a wave per free pose: U_k = sum J^T J (21 entries) and g_k = sum J^T r over the pose's incidence list
 //                   (edge order, built on the host) by lane stride, then a fixed butterfly; the column scaling at the first pass
 //   k_pg_check      one wave: FinalizeIterationAndCheckIfMinimizerCanContinue
-//   ba_blocked_solve (ba_solver.hpp): k_bag_clear; k_pg_assemble — a wave per unique sorted pair (i <= j) of free poses: the
+//   ba_blocked_solve (chol_solver.hpp): k_bag_clear; k_pg_assemble — a wave per unique sorted pair (i <= j) of free poses: the
 //                   diagonal pair writes the scaled U_i with the damping and the scaled gradient into the right-hand-side row,
 //                   an off-diagonal pair sums J_i^T J_j over the edges the host listed for it, in that order (a serial loop
 //                   of one wave: the slow shape when thousands of duplicate edges join one pair), lane (r, c)
@@ -41,34 +40,22 @@
 //                   accept or reject, radius
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
-#include "ba_solver.hpp"
+#include "chol_solver.hpp"
 
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
-#include <cstring>
 #include <map>
-#include <string>
-#include <vector>
 
 namespace mslam
 {
 
 constexpr int kPgMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES;
 constexpr int kPgMaxEdges = MSLAM_HIP_POSE_GRAPH_MAX_EDGES;
-constexpr int kPgBatch = 4; // iterations enqueued between two looks at the termination word
-constexpr int kPgMaxInvalidSteps = 5;
-constexpr double kPgInitialRadius = 1e4, kPgMaxRadius = 1e16, kPgMinRadius = 1e-32;
-constexpr double kPgMinDiagonal = 1e-6, kPgMaxDiagonal = 1e32;
-constexpr double kPgMinRelativeDecrease = 1e-3;
-constexpr double kPgFunctionTol = 1e-6, kPgGradientTol = 1e-10, kPgParameterTol = 1e-8;
-constexpr int kPgConvergence = 0, kPgNoConvergence = 1, kPgFailure = 2;
 
 struct PgArgs
 {
     int K, E, n;           // n = 6 x (free poses with an edge): the size of the normal equations
     int n_pairs, n_blocks; // pairs of free poses; blocks of k_pg_eval
-    int n_pad, ld;         // as BaArgs: n rounded up to kBagNB; leading dimension n_pad + 16 (row n_pad: the right-hand side)
+    int n_pad, ld;         // the blocked solver's padded size and leading dimension (CholArgs)
     // the problem
     const int32_t *ea, *eb; // [E]
     const double* meas;     // [E] x 7: q then p
@@ -84,72 +71,9 @@ struct PgArgs
     double *U, *gc, *sc; // [K] x 21, 6, 6
     double *S, *yc;      // the padded normal equations (the context's d_ba_S); the solution, n
     double* part;        // [2][n_blocks]: model cost change, candidate cost
-    BaCtrl* ctrl;
+    TrCtrl* ctrl;
     int32_t* h_done; // mapped
 };
-
-__device__ __forceinline__ double pg_wave_sum(double s)
-{
-    for(int m = 32; m >= 1; m >>= 1)
-        s += __shfl_xor(s, m, 64);
-    return s;
-}
-__device__ __forceinline__ double pg_wave_max(double s)
-{
-    for(int m = 32; m >= 1; m >>= 1)
-        s = fmax(s, __shfl_xor(s, m, 64));
-    return s;
-}
-__device__ __forceinline__ int pg_tri(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c < 6
-
-// Eigen's inverse(): conjugate / squared norm
-__device__ __forceinline__ void pg_inverse(const double* __restrict__ q, double qi[4])
-{
-    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    qi[0] = -q[0] / n2, qi[1] = -q[1] / n2, qi[2] = -q[2] / n2, qi[3] = q[3] / n2;
-}
-// Eigen's quaternion product (x y z w)
-__device__ __forceinline__ void pg_product(const double a[4], const double b[4], double out[4])
-{
-    out[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    out[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    out[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    out[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-}
-// Eigen's _transformVector: v + w uv + u x uv, uv = 2 (u x v)
-__device__ __forceinline__ void pg_rotate(const double qi[4], const double v[3], double out[3])
-{
-    double uv[3] = {qi[1] * v[2] - qi[2] * v[1], qi[2] * v[0] - qi[0] * v[2], qi[0] * v[1] - qi[1] * v[0]};
-    uv[0] += uv[0], uv[1] += uv[1], uv[2] += uv[2];
-    out[0] = v[0] + qi[3] * uv[0] + (qi[1] * uv[2] - qi[2] * uv[1]);
-    out[1] = v[1] + qi[3] * uv[1] + (qi[2] * uv[0] - qi[0] * uv[2]);
-    out[2] = v[2] + qi[3] * uv[2] + (qi[0] * uv[1] - qi[1] * uv[0]);
-}
-// the matrix of v -> pg_rotate(qi, v), row-major
-__device__ __forceinline__ void pg_matrix(const double qi[4], double Rt[9])
-{
-    const double x = qi[0], y = qi[1], z = qi[2], w = qi[3];
-    const double xx = x * x, yy = y * y, zz = z * z;
-    Rt[0] = 1.0 - 2.0 * (yy + zz), Rt[1] = 2.0 * (x * y - w * z), Rt[2] = 2.0 * (x * z + w * y);
-    Rt[3] = 2.0 * (x * y + w * z), Rt[4] = 1.0 - 2.0 * (xx + zz), Rt[5] = 2.0 * (y * z - w * x);
-    Rt[6] = 2.0 * (x * z - w * y), Rt[7] = 2.0 * (y * z + w * x), Rt[8] = 1.0 - 2.0 * (xx + yy);
-}
-// EigenQuaternionManifold::Plus (manifold.h QuaternionPlus, x y z w): q_delta (x) q
-__device__ __forceinline__ void pg_quaternion_plus(const double* __restrict__ q, const double d[3], double out[4])
-{
-    const double norm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if(!(norm > 0.0))
-    {
-        out[0] = q[0], out[1] = q[1], out[2] = q[2], out[3] = q[3];
-        return;
-    }
-    const double sbd = sin(norm) / norm;
-    const double ax = sbd * d[0], ay = sbd * d[1], az = sbd * d[2], aw = cos(norm);
-    out[0] = aw * q[0] + ax * q[3] + ay * q[2] - az * q[1];
-    out[1] = aw * q[1] + ay * q[3] + az * q[0] - ax * q[2];
-    out[2] = aw * q[2] + az * q[3] + ax * q[1] - ay * q[0];
-    out[3] = aw * q[3] - ax * q[0] - ay * q[1] - az * q[2];
-}
 
 // entry (i, k) of the edge's sqrt_info
 __device__ __forceinline__ double pg_info(const double* __restrict__ info, int i, int k)
@@ -161,13 +85,13 @@ __device__ __forceinline__ double pg_info(const double* __restrict__ info, int i
 __device__ __forceinline__ void pg_error(const double* __restrict__ xa, const double* __restrict__ xb, const double* __restrict__ z, double u[6])
 {
     double qai[4], qab[4], qabi[4], dq[4], pab[3];
-    pg_inverse(xa, qai);
+    quat_inverse(xa, qai);
     const double v[3] = {xb[4] - xa[4], xb[5] - xa[5], xb[6] - xa[6]};
-    pg_rotate(qai, v, pab);
+    quat_rotate(qai, v, pab);
     const double qb[4] = {xb[0], xb[1], xb[2], xb[3]}, qm[4] = {z[0], z[1], z[2], z[3]};
-    pg_product(qai, qb, qab);
-    pg_inverse(qab, qabi);
-    pg_product(qm, qabi, dq);
+    quat_product(qai, qb, qab);
+    quat_inverse(qab, qabi);
+    quat_product(qm, qabi, dq);
     u[0] = pab[0] - z[4], u[1] = pab[1] - z[5], u[2] = pab[2] - z[6];
     u[3] = 2.0 * dq[0], u[4] = 2.0 * dq[1], u[5] = 2.0 * dq[2];
 }
@@ -191,7 +115,7 @@ __device__ __forceinline__ void pg_residual(const double* __restrict__ xa, const
 
 __global__ __launch_bounds__(256) void k_pg_edges(PgArgs a)
 {
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done || !ct->need_jac)
         return;
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -208,9 +132,9 @@ __global__ __launch_bounds__(256) void k_pg_edges(PgArgs a)
         a.r[(size_t)e * 6 + i] = r[i];
     // P = R_a^T, G = 2 P [v]x, M2 = 2 M
     double qai[4], qbi[4], A[4], P[9], G[9], M2[9];
-    pg_inverse(xa, qai);
-    pg_inverse(xb, qbi);
-    pg_matrix(qai, P);
+    quat_inverse(xa, qai);
+    quat_inverse(xb, qbi);
+    quat_matrix(qai, P);
     const double v[3] = {xb[4] - xa[4], xb[5] - xa[5], xb[6] - xa[6]};
     const double vx[9] = {0.0, -v[2], v[1], v[2], 0.0, -v[0], -v[1], v[0], 0.0};
 #pragma unroll
@@ -219,14 +143,14 @@ __global__ __launch_bounds__(256) void k_pg_edges(PgArgs a)
         for(int j = 0; j < 3; ++j)
             G[i * 3 + j] = 2.0 * (P[i * 3] * vx[j] + P[i * 3 + 1] * vx[3 + j] + P[i * 3 + 2] * vx[6 + j]);
     const double qm[4] = {z[0], z[1], z[2], z[3]}, B[4] = {xa[0], xa[1], xa[2], xa[3]};
-    pg_product(qm, qbi, A);
+    quat_product(qm, qbi, A);
 #pragma unroll
     for(int j = 0; j < 3; ++j)
     {
         const double ej[4] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, 0.0};
         double t[4], w[4];
-        pg_product(A, ej, t);
-        pg_product(t, B, w);
+        quat_product(A, ej, t);
+        quat_product(t, B, w);
         M2[j] = 2.0 * w[0], M2[3 + j] = 2.0 * w[1], M2[6 + j] = 2.0 * w[2];
     }
     double* Ja = a.J + (size_t)e * 72;
@@ -251,7 +175,7 @@ __global__ __launch_bounds__(256) void k_pg_edges(PgArgs a)
 
 __global__ __launch_bounds__(64) void k_pg_poses(PgArgs a)
 {
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done || !ct->need_jac)
         return;
     const int k = blockIdx.x, lane = threadIdx.x;
@@ -297,7 +221,7 @@ __global__ __launch_bounds__(64) void k_pg_poses(PgArgs a)
     }
 #pragma unroll
     for(int j = 0; j < 27; ++j)
-        acc[j] = pg_wave_sum(acc[j]);
+        acc[j] = wave_sum(acc[j]);
     if(lane == 0)
     {
 #pragma unroll
@@ -321,76 +245,24 @@ __global__ __launch_bounds__(64) void k_pg_poses(PgArgs a)
 
 // ---- FinalizeIterationAndCheckIfMinimizerCanContinue: one wave ------------------------------------------------------------
 
-__device__ __forceinline__ void pg_finish(const PgArgs& a, int lane, int termination)
-{
-    if(lane == 0)
-    {
-        a.ctrl->termination = termination;
-        a.ctrl->done = 1;
-        *a.h_done = 1;
-    }
-}
-
 __global__ __launch_bounds__(64) void k_pg_check(PgArgs a)
 {
-    BaCtrl* ct = a.ctrl;
-    if(ct->done)
+    if(a.ctrl->done)
         return;
     const int lane = threadIdx.x;
-    double x_cost = ct->x_cost;
-    if(ct->first)
-    {
-        // iteration 0: the cost at the start, from k_pg_eval's block partials
-        double s = 0.0;
-        for(int b = lane; b < a.n_blocks; b += 64)
-            s += a.part[a.n_blocks + b];
-        x_cost = pg_wave_sum(s);
-    }
-    // the evaluation is usable (seen through the sums, as in k_ba.hip), and |x - Plus(x, -g)|_inf over the ambient parameters
-    bool ok = isfinite(x_cost);
+    bool ok = true;
     double gmax = 0.0;
     for(int k = lane; k < a.K; k += 64)
-    {
-        if(a.ci[k] < 0)
-            continue;
-        const double* q = a.pose + (size_t)k * 7;
-        const double* g = a.gc + (size_t)k * 6;
-        const double md[3] = {-g[0], -g[1], -g[2]};
-        double qp[4];
-        pg_quaternion_plus(q, md, qp);
-        for(int j = 0; j < 4; ++j)
-            gmax = fmax(gmax, fabs(q[j] - qp[j]));
-        for(int j = 0; j < 3; ++j)
-            gmax = fmax(gmax, fabs(q[4 + j] - (q[4 + j] + (-g[3 + j]))));
-        for(int j = 0; j < 6; ++j)
-            ok = ok && isfinite(g[j]) && isfinite(a.U[(size_t)k * 21 + pg_tri(j, j)]);
-    }
-    gmax = pg_wave_max(gmax);
-    ok = __all(ok);
-    if(lane == 0 && ct->first)
-        ct->x_cost = ct->initial_cost = x_cost;
-    if(!ok)
-        return pg_finish(a, lane, kPgFailure);
-    if(ct->iteration >= ct->max_iterations)
-        return pg_finish(a, lane, kPgNoConvergence);
-    if(ct->successful && gmax <= kPgGradientTol)
-        return pg_finish(a, lane, kPgConvergence);
-    if(ct->radius <= kPgMinRadius)
-        return pg_finish(a, lane, kPgConvergence);
-    if(lane == 0)
-    {
-        ct->iteration += 1;
-        ct->successful = 0;
-        ct->first = 0;
-        ct->solve_bad = 0;
-    }
+        if(a.ci[k] >= 0)
+            tr_pose_gradient(a.pose + (size_t)k * 7, a.gc + (size_t)k * 6, a.U + (size_t)k * 21, ok, gmax);
+    tr_check(a.ctrl, a.h_done, lane, a.part, a.n_blocks, ok, gmax);
 }
 
 // ---- the normal equations: a wave per pair of free poses ------------------------------------------------------------------
 
 __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
 {
-    const BaCtrl* ct = a.ctrl;
+    const TrCtrl* ct = a.ctrl;
     if(ct->done)
         return;
     const int lane = threadIdx.x;
@@ -401,8 +273,8 @@ __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
         if(lane < 36)
         {
             const int r = lane / 6, c = lane % 6;
-            const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? pg_tri(r, c) : pg_tri(c, r))] * a.sc[(size_t)k1 * 6 + c];
-            a.S[(b1 * 6 + r) + (b1 * 6 + c) * ld] = r == c ? u + fmin(fmax(u, kPgMinDiagonal), kPgMaxDiagonal) / ct->radius : u;
+            const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * a.sc[(size_t)k1 * 6 + c];
+            a.S[(b1 * 6 + r) + (b1 * 6 + c) * ld] = r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u;
         }
         else if(lane < 42)
         {
@@ -439,35 +311,8 @@ __global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if(t >= a.K)
         return;
-    const double* x = a.pose + (size_t)t * 7;
-    double* c = a.cand + (size_t)t * 7;
     const int bk = a.ci[t];
-    if(bk < 0)
-    {
-        for(int j = 0; j < 7; ++j)
-            c[j] = x[j];
-        return;
-    }
-    const double* y = a.yc + (size_t)bk * 6;
-    const double* sc = a.sc + (size_t)t * 6;
-    const double d[3] = {-y[0] * sc[0], -y[1] * sc[1], -y[2] * sc[2]};
-    double q[4];
-    pg_quaternion_plus(x, d, q);
-    c[0] = q[0], c[1] = q[1], c[2] = q[2], c[3] = q[3];
-    for(int j = 0; j < 3; ++j)
-        c[4 + j] = x[4 + j] + (-y[3 + j] * sc[3 + j]);
-}
-
-// the sum of v over the block, by a fixed tree: butterfly per wave, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double pg_block_sum(double v, double* red)
-{
-    v = pg_wave_sum(v);
-    if((threadIdx.x & 63) == 0)
-        red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
+    tr_pose_plus(a.pose + (size_t)t * 7, bk < 0 ? nullptr : a.yc + (size_t)bk * 6, a.sc + (size_t)t * 6, a.cand + (size_t)t * 7);
 }
 
 // the step of pose k in its tangent, 0 for a pose outside the problem
@@ -525,7 +370,7 @@ __global__ __launch_bounds__(256) void k_pg_eval(PgArgs a, int at_start)
         }
         cost = 0.5 * (((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]));
     }
-    const double ms = pg_block_sum(model, red), cs = pg_block_sum(cost, red);
+    const double ms = block_sum(model, red), cs = block_sum(cost, red);
     if(threadIdx.x == 0)
     {
         a.part[blockIdx.x] = ms;
@@ -537,84 +382,20 @@ __global__ __launch_bounds__(256) void k_pg_eval(PgArgs a, int at_start)
 
 __global__ __launch_bounds__(64) void k_pg_control(PgArgs a)
 {
-    BaCtrl* ct = a.ctrl;
-    if(ct->done)
+    if(a.ctrl->done)
         return;
     const int lane = threadIdx.x;
-    double ms = 0.0, cs = 0.0;
-    for(int b = lane; b < a.n_blocks; b += 64)
-        ms += a.part[b], cs += a.part[a.n_blocks + b];
-    const double model_cost_change = pg_wave_sum(ms);
-    double cand_cost = pg_wave_sum(cs);
-    // the step is finite; |x|^2 and |x - candidate|^2 over the ambient parameters of the problem's poses
     bool finite = true;
     double xn = 0.0, sn = 0.0;
     for(int k = lane; k < a.K; k += 64)
-    {
-        const int bk = a.ci[k];
-        if(bk < 0)
-            continue;
-        for(int j = 0; j < 6; ++j)
-            finite = finite && isfinite(a.yc[(size_t)bk * 6 + j]);
-        for(int j = 0; j < 7; ++j)
-        {
-            const double x = a.pose[(size_t)k * 7 + j], d = x - a.cand[(size_t)k * 7 + j];
-            xn += x * x, sn += d * d;
-        }
-    }
-    finite = __all(finite);
-    const double x_norm = sqrt(pg_wave_sum(xn)), step_norm = sqrt(pg_wave_sum(sn));
-    const double x_cost = ct->x_cost;
-    double radius = ct->radius, decrease_factor = ct->decrease_factor;
-    if(!(finite && !ct->solve_bad && model_cost_change > 0.0))
-    {
-        // HandleInvalidStep
-        if(lane == 0)
-            ct->invalid_total += 1;
-        if(ct->invalid_run + 1 >= kPgMaxInvalidSteps)
-            return pg_finish(a, lane, kPgFailure);
-        if(lane == 0)
-        {
-            ct->invalid_run += 1;
-            ct->radius = radius / decrease_factor;
-            ct->decrease_factor = decrease_factor * 2.0;
-            ct->need_jac = 0;
-        }
+        if(a.ci[k] >= 0)
+            tr_pose_step(a.pose + (size_t)k * 7, a.cand + (size_t)k * 7, a.yc + (size_t)a.ci[k] * 6, finite, xn, sn);
+    if(!tr_control(a.ctrl, a.h_done, lane, a.part, a.n_blocks, finite, xn, sn))
         return;
-    }
-    if(!isfinite(cand_cost))
-        cand_cost = DBL_MAX;
-    if(lane == 0)
-        ct->invalid_run = 0;
-    if(step_norm <= kPgParameterTol * (x_norm + kPgParameterTol))
-        return pg_finish(a, lane, kPgConvergence);
-    if(fabs(x_cost - cand_cost) <= kPgFunctionTol * x_cost)
-        return pg_finish(a, lane, kPgConvergence);
-    const double relative_decrease = cand_cost >= DBL_MAX ? -DBL_MAX : (x_cost - cand_cost) / model_cost_change;
-    if(relative_decrease > kPgMinRelativeDecrease)
-    {
-        for(int k = lane; k < a.K; k += 64)
-            if(a.ci[k] >= 0)
-                for(int j = 0; j < 7; ++j)
-                    a.pose[(size_t)k * 7 + j] = a.cand[(size_t)k * 7 + j];
-        if(lane == 0)
-        {
-            const double q = 2.0 * relative_decrease - 1.0;
-            radius = radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
-            ct->radius = fmin(kPgMaxRadius, radius);
-            ct->decrease_factor = 2.0;
-            ct->x_cost = cand_cost;
-            ct->successful = 1;
-            ct->need_jac = 1;
-        }
-    }
-    else if(lane == 0)
-    {
-        ct->rejected += 1;
-        ct->radius = radius / decrease_factor;
-        ct->decrease_factor = decrease_factor * 2.0;
-        ct->need_jac = 0;
-    }
+    for(int k = lane; k < a.K; k += 64)
+        if(a.ci[k] >= 0)
+            for(int j = 0; j < 7; ++j)
+                a.pose[(size_t)k * 7 + j] = a.cand[(size_t)k * 7 + j];
 }
 
 } // namespace mslam
@@ -633,17 +414,13 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
         return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: E outside 0.." + std::to_string(kPgMaxEdges));
     if(max_iterations < 0 || (K > 0 && !poses) || (E > 0 && (!edge_a || !edge_b || !edge_meas)))
         return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: bad argument (pointers, max_iterations >= 0)");
-    auto unit = [](const double* q) {
-        const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        return std::fabs(norm - 1.0) <= 1e-6;
-    };
     for(int e = 0; e < E; ++e)
     {
         if(edge_a[e] < 0 || edge_a[e] >= K || edge_b[e] < 0 || edge_b[e] >= K)
             return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: edge " + std::to_string(e) + " names a pose out of range");
         if(edge_a[e] == edge_b[e])
             return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: edge " + std::to_string(e) + " joins a pose with itself");
-        if(!unit(edge_meas + (size_t)e * 7))
+        if(!tr_unit_quaternion(edge_meas + (size_t)e * 7))
             return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: the quaternion of measurement " + std::to_string(e) + " is not unit");
         if(sqrt_info)
             for(int j = 0; j < 36; ++j)
@@ -651,7 +428,7 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
                     return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: sqrt_info of edge " + std::to_string(e) + " is not finite");
     }
     for(int k = 0; k < K; ++k)
-        if(!unit(poses + (size_t)k * 7))
+        if(!tr_unit_quaternion(poses + (size_t)k * 7))
             return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: the quaternion of pose " + std::to_string(k) + " is not unit");
     mslam_hip_ba_summary sum{};
     if(E == 0)
@@ -695,44 +472,25 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     a.K = K, a.E = E, a.n = 6 * n_free;
     a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (E + 255) / 256;
     a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
-    // one block: what is uploaded first, then the working arrays
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 15) & ~(size_t)15;
-        return at;
-    };
+    // one block: what is uploaded first (the control block at 0), then the working arrays
+    TrStaging st(max_iterations);
     const size_t n_info = sqrt_info ? (size_t)E * 288 : 0;
-    const size_t o_ctrl = carve(sizeof(BaCtrl)), o_pose = carve((size_t)K * 56), o_meas = carve((size_t)E * 56), o_info = carve(n_info);
-    const size_t o_ea = carve((size_t)E * 4), o_eb = carve((size_t)E * 4), o_iptr = carve(((size_t)K + 1) * 4), o_inc = carve((size_t)E * 8);
-    const size_t o_ci = carve((size_t)K * 4), o_pairs = carve(pairs.size() * 4), o_pptr = carve(pair_ptr.size() * 4);
-    const size_t o_pedge = carve(pair_edge.size() * 4);
-    const size_t up_bytes = off;
-    const size_t o_cand = carve((size_t)K * 56), o_r = carve((size_t)E * 48), o_J = carve((size_t)E * 576);
-    const size_t o_U = carve((size_t)K * 168), o_gc = carve((size_t)K * 48), o_sc = carve((size_t)K * 48), o_yc = carve((size_t)a.n * 8);
-    const size_t o_part = carve((size_t)a.n_blocks * 16);
+    const size_t o_pose = st.put(poses, (size_t)K * 56), o_meas = st.put(edge_meas, (size_t)E * 56), o_info = st.put(sqrt_info, n_info);
+    const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4), o_iptr = st.put(inc_ptr.data(), ((size_t)K + 1) * 4);
+    const size_t o_inc = st.put(inc.data(), (size_t)E * 8), o_ci = st.put(ci.data(), (size_t)K * 4), o_pairs = st.put(pairs.data(), pairs.size() * 4);
+    const size_t o_pptr = st.put(pair_ptr.data(), pair_ptr.size() * 4), o_pedge = st.put(pair_edge.data(), pair_edge.size() * 4);
+    const size_t o_cand = st.carve((size_t)K * 56), o_r = st.carve((size_t)E * 48), o_J = st.carve((size_t)E * 576);
+    const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_yc = st.carve((size_t)a.n * 8);
+    const size_t o_part = st.carve((size_t)a.n_blocks * 16);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
-    MSLAM_CHK(c, grow(c->d_pg, off, c->stream));
+    MSLAM_CHK(c, grow(c->d_pg, st.size, c->stream));
     if(a.n > 0)
         MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
-    std::vector<uint8_t> stage(up_bytes, 0);
-    BaCtrl ctrl{};
-    ctrl.need_jac = 1, ctrl.first = 1, ctrl.successful = 1, ctrl.max_iterations = max_iterations;
-    ctrl.radius = kPgInitialRadius, ctrl.decrease_factor = 2.0;
-    std::memcpy(&stage[o_ctrl], &ctrl, sizeof(ctrl));
-    auto put = [&](size_t at, const void* src, size_t bytes) {
-        if(bytes)
-            std::memcpy(&stage[at], src, bytes);
-    };
-    put(o_pose, poses, (size_t)K * 56), put(o_meas, edge_meas, (size_t)E * 56), put(o_info, sqrt_info, n_info);
-    put(o_ea, edge_a, (size_t)E * 4), put(o_eb, edge_b, (size_t)E * 4), put(o_iptr, inc_ptr.data(), ((size_t)K + 1) * 4);
-    put(o_inc, inc.data(), (size_t)E * 8), put(o_ci, ci.data(), (size_t)K * 4), put(o_pairs, pairs.data(), pairs.size() * 4);
-    put(o_pptr, pair_ptr.data(), pair_ptr.size() * 4), put(o_pedge, pair_edge.data(), pair_edge.size() * 4);
     uint8_t* d = c->d_pg;
     hipStream_t s = c->stream;
-    MSLAM_CHK(c, hipMemcpyAsync(d, stage.data(), up_bytes, hipMemcpyHostToDevice, s));
+    MSLAM_CHK(c, st.upload(d, s));
     auto dbl = [&](size_t at) { return reinterpret_cast<double*>(d + at); };
     auto i32 = [&](size_t at) { return reinterpret_cast<int32_t*>(d + at); };
     a.ea = i32(o_ea), a.eb = i32(o_eb), a.meas = dbl(o_meas), a.info = sqrt_info ? dbl(o_info) : nullptr;
@@ -740,56 +498,39 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     a.pairs = i32(o_pairs), a.pair_ptr = i32(o_pptr), a.pair_edge = i32(o_pedge);
     a.pose = dbl(o_pose), a.cand = dbl(o_cand), a.r = dbl(o_r), a.J = dbl(o_J);
     a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.S = c->d_ba_S.get(), a.yc = dbl(o_yc), a.part = dbl(o_part);
-    a.ctrl = reinterpret_cast<BaCtrl*>(d + o_ctrl);
+    a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
-    // what the k_bag_* kernels read of their argument block
-    BaArgs sa{};
-    sa.n = a.n, sa.n_pad = a.n_pad, sa.ld = a.ld, sa.S = a.S, sa.yc = a.yc, sa.ctrl = a.ctrl;
+    const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
 
     const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256));
     {
         StageScope ts(c, "pg_start_cost");
         hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
     }
-    // iteration max_iterations + 1 only reaches k_pg_check, which ends the solve with NO_CONVERGENCE
-    for(long long it = 0; it <= max_iterations;) // a wide counter: max_iterations + 1 must not wrap for INT_MAX
-    {
-        StageScope ts(c, "pg_iterations");
-        for(int b = 0; b < kPgBatch && it <= max_iterations; ++b, ++it)
+    const int rc = tr_run(c, "pg_iterations", "pose_graph", a.ctrl, max_iterations, [&] {
         {
-            {
-                StageScope tk(c, "pg_blocks");
-                hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
-                hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
-            }
-            if(a.n_pairs > 0)
-                ba_blocked_solve(c, sa, s, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-            StageScope tk(c, "pg_step");
-            hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
-            hipLaunchKernelGGL(k_pg_control, dim3(1), dim3(64), 0, s, a);
+            StageScope tk(c, "pg_blocks");
+            hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
+            hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
         }
-        MSLAM_CHK(c, hipGetLastError());
-        MSLAM_CHK(c, hipStreamSynchronize(s));
-        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
-            break;
-    }
-    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    if(!ctrl.done)
-        return fail(c, MSLAM_HIP_E_RUNTIME, "pose_graph: the kernels left no termination");
-    const bool usable = ctrl.termination != kPgFailure;
+        if(a.n_pairs > 0)
+            ba_blocked_solve(c, chol, s, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+        StageScope tk(c, "pg_step");
+        hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
+        hipLaunchKernelGGL(k_pg_control, dim3(1), dim3(64), 0, s, a);
+    }, sum);
+    if(rc != MSLAM_HIP_OK)
+        return rc;
+    const bool usable = sum.termination != kTrFailure;
     std::vector<double> xp((size_t)K * 7);
     if(usable)
     {
         MSLAM_CHK(c, hipMemcpyAsync(xp.data(), a.pose, (size_t)K * 56, hipMemcpyDeviceToHost, s));
         MSLAM_CHK(c, hipStreamSynchronize(s));
     }
-    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
-    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
-    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
     if(summary)
         *summary = sum;
     if(!usable)

@@ -1,5 +1,5 @@
-"""mslam_hip_bundle_adjust_global on the MI355X (the k_bag_* kernels of k_ba.hip: covisible-pair Schur complement, blocked
-Cholesky, blocked substitution) through Context.bundle_adjust_global: against tests/ba_ref.py's QR solve on the trajectory
+"""mslam_hip_bundle_adjust_global on the MI355X (k_bag_schur of k_ba.hip and the k_bag_* kernels of k_chol.hip: covisible-pair
+Schur complement, blocked Cholesky, blocked substitution) through Context.bundle_adjust_global: against tests/ba_ref.py's QR solve on the trajectory
 scenes of tests/ba_global_cases.py (tests/test_ba_global.py shows on the CPU that every scene takes the path it is named
 for); both solvers on cases of tests/ba_cases.py; determinism, also of a small solve after a large one; 300 keyframes against
 ground truth; arguments and FAILURE; HipBackend(global_solver=True).

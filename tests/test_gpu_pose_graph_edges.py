@@ -31,6 +31,12 @@ k_pg_candidate handling its first block only (chain300 fails there, sparse1024 h
 pass; far fails), sqrt_info's strict lower triangle ignored (old pass; info_dense and info_dense_dropped fail), the iteration cap
 looked at only when the Jacobians were re-evaluated (old pass; rejected:cap2, cap3, cap4 fail).
 
+The loop's decisions, reductions and quaternions now live once in csrc/trust_region.hpp, shared with k_ba.hip, so a break there
+shows in both solvers' tests.  Built and run in the same way against tests/test_gpu_ba.py and tests/test_gpu_pose_graph.py: the
+function tolerance compared without `* x_cost` (37 and 19 tests fail), the sign of w flipped in the quaternion inverse (54 and
+22 fail); the radius left undivided after an invalid step fails nothing in either file, for the reason given above: no case
+reaches the invalid-step branch.
+
 Measured on an MI355X (GPU / reference; dx = distance to the QR reference, beside the bound B):
   edges:16641          term 0/0  it 3/3  rejected 0/0  dx 6.661e-16  B 1.000e-09
   edges:256            term 0/0  it 3/3  rejected 0/0  dx 1.554e-15  B 1.000e-09
