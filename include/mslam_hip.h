@@ -791,6 +791,59 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* ctx, int keep_id, int drop_id, const double
 int mslam_hip_kf_remove_observations(mslam_hip_ctx* ctx, const int32_t* kf_ids /* n */, const int64_t* landmark_ids /* n */, int n,
                                      int32_t* removed /* n, may be NULL */, int* n_removed /* may be NULL */);
 
+/* ---- keyframe culling: observer counts and a greedy pass over a candidate list ----------------------------------------
+ * AN EXTENSION, NOT A RESTATEMENT: the reference has the removal primitives (BasicMap::removeKeyframe, basic_map.cpp:110-115;
+ * IRelocalizer::removeKeyframe, relocalizer.hpp:19) and no policy that calls them.  The model is ORB-SLAM's
+ * KeyFrameCulling: a keyframe is redundant when more than 90 % of its landmarks are seen by at least three other keyframes.
+ *
+ *   the map      ids[0..n_ids) are the store entries that count as observers.  The caller names them because the store also
+ *                holds unions under ids of the caller's choosing, and a union must not count as an observer.
+ *                1 <= n_ids <= MSLAM_HIP_CULL_MAX_ENTRIES, all distinct, all in the store.
+ *   obs(l)       the number of listed entries that hold landmark id l at one position at least.  A repeat inside an entry
+ *                counts once, as for mslam_hip_kf_covisible.
+ *
+ * mslam_hip_kf_observers: counts[p] = obs(landmark_ids[p]), 0 for an id no listed entry holds; an id listed twice reports the
+ * same count twice.  0 <= n <= 2^24; ids outside [0, 2^63) are MSLAM_HIP_E_INVALID; n = 0 is OK.
+ *
+ * mslam_hip_kf_cull_search judges the candidates cand[0..n_cand) in the order given and changes nothing in the store.  The
+ * candidates are distinct, each is one of `ids`, 0 <= n_cand <= n_ids; a keyframe the caller wants to protect is simply not
+ * a candidate.  At the turn of candidate c, with D = the set of distinct landmark ids of entry cand[c]:
+ *   n_landmarks[c] = |D|;
+ *   n_redundant[c] = |{ l in D : obs(l) - 1 >= min_observers }| with obs as it stands at that turn (the -1: the candidate
+ *                    itself is one of the observers);
+ *   culled[c]      = n_landmarks[c] >= min_landmarks && (double)n_redundant[c] > ratio * (double)n_landmarks[c]: one
+ *                    multiplication and one strict comparison, the strict `>` of ORB-SLAM's 0.9 * nMPs.  An empty entry is
+ *                    never culled;
+ *   greedy         when c is culled, obs(l) drops by one for every l in D before the next candidate is judged: two keyframes
+ *                    that make each other redundant do not both go.
+ * n_landmarks and n_redundant (each may be NULL) report what was seen at the candidate's turn; *n_culled (may be NULL) = the
+ * number of culled candidates.  min_observers in 1..65535, ratio in [0, 1] (NaN is MSLAM_HIP_E_INVALID), min_landmarks >= 1.
+ *
+ * mslam_hip_kf_cull is the search, after which the host removes the culled entries exactly as mslam_hip_kf_remove would
+ * (the slot goes to the free list, the serial is untouched).  Every other entry is untouched byte for byte.
+ *
+ * Errors: MSLAM_HIP_E_INVALID for the limits above, a NULL list or a NULL `culled` / `counts` with a positive count, a
+ * listed id that is not in the store or is listed twice, a candidate that is not listed or is named twice;
+ * MSLAM_HIP_E_CAPACITY when the sizes the host knows of the listed entries (an entry lifted on the device counts as
+ * max_keypoints) sum to more than MSLAM_HIP_CULL_MAX_LANDMARKS: the id table is sized by that sum.  On every error the
+ * store is untouched and the outputs are zeroed.
+ * One upload (the two lists; for kf_observers the ids and the list), three clears, two launches per 64 listed entries, one
+ * more launch (the lookup, or the greedy pass: one workgroup), one synchronisation.  Every output is a function of the store
+ * and the arguments alone: two runs give equal bytes.
+ *   rule         SAME as KeyFrameCulling's count and threshold (nRedundantObservations > 0.9 * nMPs, thObs = 3);
+ *   scale        DEVIATES: ORB-SLAM counts another observation only when it was made at the same or a finer pyramid level;
+ *                the store keeps no octave, so that test is absent;
+ *   order        DEVIATES: ORB-SLAM visits the local keyframes in covisibility order; here the order is the caller's. */
+#define MSLAM_HIP_CULL_MAX_ENTRIES 4096
+#define MSLAM_HIP_CULL_MAX_LANDMARKS (1 << 24)
+int mslam_hip_kf_observers(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int64_t* landmark_ids, int n, int32_t* counts /* n */);
+int mslam_hip_kf_cull_search(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int32_t* cand, int n_cand, int min_observers,
+                             double ratio, int min_landmarks, uint8_t* culled /* n_cand */, int32_t* n_landmarks /* n_cand, may be NULL */,
+                             int32_t* n_redundant /* n_cand, may be NULL */, int* n_culled /* may be NULL */);
+int mslam_hip_kf_cull(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int32_t* cand, int n_cand, int min_observers, double ratio,
+                      int min_landmarks, uint8_t* culled /* n_cand */, int32_t* n_landmarks /* n_cand, may be NULL */,
+                      int32_t* n_redundant /* n_cand, may be NULL */, int* n_culled /* may be NULL */);
+
 /* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
  * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
  * valid; a mask is track()'s depth filter, :317-334).  Per candidate c = cand_ids[k]:

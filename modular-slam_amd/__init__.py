@@ -31,6 +31,7 @@ DETECTOR_DISTRIBUTED, DETECTOR_CV_ORB = 0, 1
 BOW_ASSIGN_TREE, BOW_ASSIGN_FLAT = 0, 1
 CV_ORDER_LIBSTDCXX, CV_ORDER_RASTER = 0, 1
 POSE_GRAPH_MAX_KEYFRAMES, POSE_GRAPH_MAX_EDGES = 1024, 65536    # mslam_hip_pose_graph's bounds (include/mslam_hip.h)
+CULL_MAX_ENTRIES = 4096    # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 
 # every symbol include/mslam_hip.h declares (tests/test_cabi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -56,6 +57,7 @@ ABI_SYMBOLS = [
     "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world", "mslam_hip_pose_graph",
     "mslam_hip_kf_fuse_search", "mslam_hip_kf_replace_ids", "mslam_hip_kf_fuse",
     "mslam_hip_kf_remove_observations",
+    "mslam_hip_kf_observers", "mslam_hip_kf_cull_search", "mslam_hip_kf_cull",
 ]
 
 
@@ -623,6 +625,37 @@ class Context:
         n = C.c_int(0)
         self._chk(self.L.mslam_hip_kf_remove_observations(self._h, _p(k), _p(l), len(k), _p(removed), C.byref(n)))
         return dict(removed=removed[:len(k)].copy(), n_removed=n.value)
+
+    # ---- keyframe culling (an extension: the reference has removeKeyframe and no policy that calls it) ----
+    def kf_observers(self, ids, landmark_ids):
+        """-> counts [n] i32: how many of the listed store entries `ids` (1..4096, distinct) hold each landmark id at one
+        position at least; 0 for an id none of them holds"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        l = np.ascontiguousarray(landmark_ids, np.int64).reshape(-1)
+        counts = np.zeros(max(len(l), 1), np.int32)
+        self._chk(self.L.mslam_hip_kf_observers(self._h, _p(ids), len(ids), _p(l), len(l), _p(counts)))
+        return counts[:len(l)].copy()
+
+    def _cull_call(self, entry, ids, cand, min_observers, ratio, min_landmarks):
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        cand = np.ascontiguousarray(cand, np.int32).reshape(-1)
+        m = max(len(cand), 1)
+        culled, nl, nr, n = np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros(m, np.int32), C.c_int(0)
+        self._chk(entry(self._h, _p(ids), len(ids), _p(cand), len(cand), int(min_observers), C.c_double(ratio), int(min_landmarks),
+                        _p(culled), _p(nl), _p(nr), C.byref(n)))
+        k = len(cand)
+        return dict(culled=culled[:k].astype(bool), n_landmarks=nl[:k].copy(), n_redundant=nr[:k].copy(), n_culled=n.value)
+
+    def kf_cull_search(self, ids, cand, min_observers=3, ratio=0.9, min_landmarks=1):
+        """the greedy culling pass over the candidates `cand` (distinct, each one of the listed entries `ids`), in the order
+        given: a candidate goes when it has at least min_landmarks distinct landmark ids and more than `ratio` of them are
+        held by at least min_observers other listed entries, counted without the candidates culled before it
+        -> dict(culled [n_cand] bool, n_landmarks, n_redundant [n_cand] i32, n_culled).  Changes nothing."""
+        return self._cull_call(self.L.mslam_hip_kf_cull_search, ids, cand, min_observers, ratio, min_landmarks)
+
+    def kf_cull(self, ids, cand, min_observers=3, ratio=0.9, min_landmarks=1):
+        """kf_cull_search, then the culled entries leave the store as kf_remove would remove them -> the same dict"""
+        return self._cull_call(self.L.mslam_hip_kf_cull, ids, cand, min_observers, ratio, min_landmarks)
 
     # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
     def kf_covisible(self, id, ids):
@@ -1226,6 +1259,7 @@ class HipBackend:
     first solve's dict); a FAILURE of the first solve prunes nothing.  The cost has no loss function, so one gross outlier
     can drag its landmark until the landmark's good observations are flagged too, and the landmark then goes with them.
     The backend never touches the keyframe store: its caller does (Context.kf_remove_observations with pruned["pairs"]).
+    remove_keyframe() is the backend's side of keyframe culling (Context.kf_cull): every keyframe but the first can leave.
     global_solver = True: global_ba() goes through
     Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes.
     close_loop() is the body of the reference's empty closeLoop (rgbd_feature_frontend.cpp:577-580): a pose graph over every
@@ -1335,6 +1369,32 @@ class HipBackend:
                 self.anchor[l] = who[0]
         return n
 
+    def remove_keyframe(self, id):
+        """keyframe culling's bookkeeping (BasicMap::removeKeyframe, basic_map.cpp:110-115, with what the landmarks need):
+        the keyframe leaves `poses` and `obs`; a landmark anchored at it is re-anchored to the smallest remaining keyframe id
+        that observes it; a landmark nobody observes any more leaves `landmarks` and `anchor`.  The first keyframe (the
+        gauge: it alone is constant) and an id the backend does not hold are MslamHipError(E_INVALID)
+        -> dict(n_observations = the observations dropped, orphans = the landmark ids that left, ascending)"""
+        id = int(id)
+        if id not in self.poses or id == self.first:
+            raise MslamHipError(E_INVALID, "remove_keyframe: %r is the first keyframe or not a keyframe of the backend" % id)
+        lids, _ = self.obs.pop(id)
+        del self.poses[id]
+        touched, observers = set(lids.tolist()), {}
+        for kf in sorted(self.obs):
+            for l in touched.intersection(self.obs[kf][0].tolist()):
+                observers.setdefault(l, []).append(kf)
+        orphans = []
+        for l in sorted(touched):
+            who = observers.get(l)
+            if not who:
+                self.landmarks.pop(l, None)
+                self.anchor.pop(l, None)
+                orphans.append(l)
+            elif self.anchor.get(l) == id:
+                self.anchor[l] = who[0]
+        return dict(n_observations=len(lids), orphans=orphans)
+
     def _solve_pruned(self, kf_ids, blocked, prune):
         """_solve; with prune, the result's outlier observations are removed and, when any were, one more solve from the
         refined state follows (one extra round, not a loop): the last solve's dict plus pruned = dict(pairs, first)"""
@@ -1434,6 +1494,28 @@ class HipBackend:
         return res
 
 
+def remove_graph_node(graph, k):
+    """node k and its edges leave the covisibility graph (id -> set of ids), and the graph stays as connected as it was:
+    every former neighbour of k, in ascending order, that has no path left to the smallest former neighbour gets an edge to
+    it (the part ORB-SLAM's spanning-tree re-parenting plays) -> the bridges added, [(neighbour, smallest neighbour), ...]"""
+    nbrs = sorted(graph.pop(k, ()))
+    for n in nbrs:
+        graph[n].discard(k)
+    bridges = []
+    for n in nbrs[1:]:
+        seen, stack = {n}, [n]
+        while stack and nbrs[0] not in seen:
+            for m in graph[stack.pop()]:
+                if m not in seen:
+                    seen.add(m)
+                    stack.append(m)
+        if nbrs[0] not in seen:
+            graph[n].add(nbrs[0])
+            graph[nbrs[0]].add(n)
+            bridges.append((n, nbrs[0]))
+    return bridges
+
+
 class HipKeyframeTracker:
     """The reference front end's loop over frames (RgbdFeatureFrontend::processSensorData, rgbd_feature_frontend.cpp:185-222)
     on the device-resident keyframe store: initFirstKeyframe on the first frame (:433-470: every keypoint with a valid
@@ -1499,7 +1581,22 @@ class HipKeyframeTracker:
     loop_global_ba the global solve after a loop is pruned the same way.  ba_results still gets one dict per keyframe, and
     the covisibility graph keeps its edges (the reference's neighbour sets never shrink either).  CAVEAT: there is no loss
     function, so a gross outlier can drag its landmark until the landmark's good observations are flagged as well; removal
-    then deletes that landmark everywhere, as the reference's pipeline would.  Off by default: nothing is removed."""
+    then deletes that landmark everywhere, as the reference's pipeline would.  Off by default: nothing is removed.
+
+    kf_cull = True (needs local_ba, else MslamHipError(E_INVALID): the backend holds the observations, the graph the
+    neighbours; an extension, the reference has removeKeyframe — basic_map.cpp:110-115, relocalizer.hpp:19 — and no policy
+    that calls it; the model is ORB-SLAM's KeyFrameCulling): at every keyframe insertion, last, after the covisibility
+    edges, local BA, pruning and the loop closure, Context.kf_cull judges cull_candidates(new_id) — HipBackend.neighbours
+    of the new keyframe at depth 1, ascending, never the new keyframe, the reference keyframe, the backend's first keyframe,
+    a keyframe the backend does not hold or a reserved id — with self.ids as the map (more than 4096 keyframes:
+    MslamHipError(E_CAPACITY) before the context is touched): a candidate goes when more than cull_ratio of its landmarks
+    are held by at least cull_min_observers other keyframes, counted without the candidates that went before it.  A culled
+    keyframe leaves the store, self.ids, the backend (HipBackend.remove_keyframe), the BoW database (bow_db_remove, and
+    self._bow_entry) and the graph; remove_graph_node keeps the graph connected, which the pose graph needs: every former
+    neighbour with no path left to the smallest former neighbour gets an edge to it.  The local map is rebuilt.
+    self.cull_results gains one dict per call that had candidates: keyframe, listed, candidates, culled, n_landmarks,
+    n_redundant, bridges.  Off by default: nothing is removed.  STILL OUT: culling landmarks by age or by observer count
+    (Context.kf_observers is the primitive for it), and ORB-SLAM's scale condition (the store keeps no octave)."""
 
     LOCAL_MAP_ID = 0x7fffffff
     FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
@@ -1510,8 +1607,13 @@ class HipKeyframeTracker:
                  reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False,
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
-                 loop_fuse_world_distance=0.1, ba_prune=False):
+                 loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9):
         self.ctx = ctx
+        if kf_cull and not local_ba:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: kf_cull needs local_ba (the backend holds the observations, "
+                                           "the graph the neighbours)")
+        self.kf_cull, self.cull_min_observers, self.cull_ratio = bool(kf_cull), int(cull_min_observers), float(cull_ratio)
+        self.cull_results = []
         if ba_prune and not local_ba:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_prune needs local_ba (the backend finds the outliers)")
         self.ba_prune = bool(ba_prune)
@@ -1606,6 +1708,8 @@ class HipKeyframeTracker:
                         self._local_ba(new_id, res, xy, depth)
                     if self.loop_closure:
                         out["loop"] = self._close_loops(new_id, desc, xy, seed)
+                    if self.kf_cull:
+                        self._cull(new_id)
         else:
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
@@ -1669,6 +1773,8 @@ class HipKeyframeTracker:
                         if self.loop_closure:
                             self._extent = np.asarray(depths[i + s]).shape[1::-1]
                             o["loop"] = self._close_loops(new_id, descs[i + s], xys[i + s], seed + s)
+                        if self.kf_cull:
+                            self._cull(new_id)
                 else:
                     reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
                                                 self.iterations, self.reprojection_error, seed + s,
@@ -1718,6 +1824,39 @@ class HipKeyframeTracker:
         pruned["n_removed"] = self.ctx.kf_remove_observations([k for k, _ in pairs], [l for _, l in pairs])["n_removed"] if pairs else 0
         if pairs:
             self._local_map_of = None
+
+    def cull_candidates(self, new_id):
+        """the keyframes _cull may remove when new_id was inserted: HipBackend.neighbours(new_id, graph, 1), ascending,
+        without new_id, the reference keyframe and the backend's first keyframe (the gauge); a keyframe the backend or
+        self.ids does not hold (the reserved ids among them) is never one"""
+        keep, listed = {new_id, self.reference, self.backend.first}, set(self.ids)
+        return [k for k in self.backend.neighbours(new_id, self.graph, 1) if k not in keep and k in listed]
+
+    def _cull(self, new_id):
+        """kf_cull: Context.kf_cull over cull_candidates(new_id) with self.ids as the map, then the bookkeeping behind
+        every culled keyframe (ids, backend, BoW database, graph with its bridges); a call that had candidates is recorded
+        in self.cull_results"""
+        if len(self.ids) > CULL_MAX_ENTRIES:
+            raise MslamHipError(E_CAPACITY, "kf_cull: %d keyframes, at most %d per call" % (len(self.ids), CULL_MAX_ENTRIES))
+        cands = self.cull_candidates(new_id)
+        if not cands:
+            return
+        listed = list(self.ids)
+        res = self.ctx.kf_cull(listed, cands, self.cull_min_observers, self.cull_ratio)
+        gone = [k for k, c in zip(cands, res["culled"]) if c]
+        bridges = []
+        for k in gone:
+            self.ids.remove(k)
+            self.backend.remove_keyframe(k)
+            for entry in [e for e, kf in self._bow_entry.items() if kf == k]:
+                self.ctx.bow_db_remove(entry)
+                del self._bow_entry[entry]
+            bridges += remove_graph_node(self.graph, k)
+        if gone:
+            self._local_map_of = None
+        self.cull_results.append(dict(keyframe=new_id, listed=listed, candidates=cands, culled=gone,
+                                      n_landmarks=res["n_landmarks"].tolist(), n_redundant=res["n_redundant"].tolist(),
+                                      bridges=bridges))
 
     def loop_candidates(self, new_id, entries, scores):
         """the filters between the database's hits and the verification -> keyframe ids, best score first, at most

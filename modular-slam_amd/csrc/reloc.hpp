@@ -68,6 +68,9 @@ struct RelocState
     // [needed count, pad | covisibility counts 64 x i32]
     DevBuf<uint8_t> d_lm_table, d_lm_blocks;
     PinnedBuf<uint8_t> h_lm;
+    // ---- scratch of keyframe culling (k_cull.hip), next to d_lm_table and grown on demand: [observer counts, one u32 per
+    // bucket | first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32]
+    DevBuf<uint8_t> d_cull;
 };
 
 // A fresh landmark id: (1 << 62) | (serial << 16) | position in the entry.  Entries hold at most 65535 landmarks and the

@@ -45,6 +45,11 @@
 //                                    IObservationRemover::removeObservations of the relocalizer adapter on the scene's entries
 //                                    and rows: "prune removed N", one "row <p> <count>" line per row, then per entry
 //                                    "entry <id> n <count> <ids...>" after the removal
+//        mslam_harness <plugin.so> --cull <scene>
+//                                    IKeyframeCuller::cullKeyframes of the relocalizer adapter on the scene's entries, listed
+//                                    keyframes and candidates: "cull culled N", one "cand <p> <id> <culled> <landmarks>
+//                                    <redundant>" line per candidate, then "remaining <ids...>": the entries the adapter
+//                                    still holds
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -486,6 +491,115 @@ int main(int argc, char** argv)
                     std::printf(" %lld", static_cast<long long>(id));
                 std::printf("\n");
             }
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--cull") == 0)
+        {
+            // scene file: "MSCL", i32 version (1), i32 entries, i32 listed, i32 candidates, i32 min_observers, i32
+            // min_landmarks, f64 ratio; per entry i32 id, i32 n (>= 1), n x 32 descriptor bytes, n x 3 f64 world points,
+            // n x i64 landmark ids; then the listed ids and the candidates as i32
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[6] = {0, 0, 0, 0, 0, 0};
+            mslam::KeyframeCullParams params;
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            in.read(reinterpret_cast<char*>(&params.ratio), sizeof(params.ratio));
+            if(!in || std::memcmp(magic, "MSCL", 4) != 0 || head[0] != 1 || head[1] < 1 || head[2] < 0 || head[3] < 0)
+            {
+                std::fprintf(stderr, "%s is not a culling scene\n", argv[3]);
+                return 5;
+            }
+            params.minObservers = head[4], params.minLandmarks = head[5];
+            auto makeReloc = mslam::loadFactoryMethod<mslam::IOrbRelocalizer>(argv[1], "hipOrbRelocalizerFactory");
+            if(!makeReloc)
+                return 3;
+            std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
+            auto* culler = dynamic_cast<mslam::IKeyframeCuller*>(relocalizer.get());
+            auto* localMap = dynamic_cast<mslam::ILocalMapTracker*>(relocalizer.get());
+            if(!culler || !localMap)
+            {
+                std::fprintf(stderr, "the plugin does not offer keyframe culling\n");
+                return 6;
+            }
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::vector<std::shared_ptr<Kf>> entries;
+            std::map<std::int32_t, std::shared_ptr<Kf>> byId;
+            for(std::int32_t e = 0; e < head[1]; ++e)
+            {
+                std::int32_t eh[2] = {0, 0};
+                in.read(reinterpret_cast<char*>(eh), sizeof(eh));
+                if(!in || eh[1] < 1 || eh[1] > 65535 || byId.count(eh[0]))
+                {
+                    std::fprintf(stderr, "entry %d of %s is malformed\n", e, argv[3]);
+                    return 5;
+                }
+                std::vector<mslam::OrbKeypoint> kps(static_cast<std::size_t>(eh[1]));
+                std::vector<mslam::Vector3> world(kps.size());
+                std::vector<std::int64_t> ids(kps.size());
+                for(std::size_t i = 0; i < kps.size(); ++i)
+                {
+                    kps[i].keypoint.id = i;
+                    in.read(reinterpret_cast<char*>(kps[i].descriptor.data()), 32);
+                }
+                for(auto& w : world)
+                    in.read(reinterpret_cast<char*>(w.v), sizeof(w.v));
+                in.read(reinterpret_cast<char*>(ids.data()), static_cast<std::streamsize>(ids.size() * 8));
+                if(!in)
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                    return 5;
+                }
+                auto kf = std::make_shared<Kf>();
+                kf->id = static_cast<mslam::Id>(eh[0]);
+                relocalizer->addKeyframe(kf, kps);
+                localMap->addKeyframeLandmarksWithIds(kf, kps, world, ids);
+                entries.push_back(kf);
+                byId[eh[0]] = kf;
+            }
+            std::vector<std::shared_ptr<Kf>> lists[2];
+            for(int which = 0; which < 2; ++which)
+            {
+                std::vector<std::int32_t> named(static_cast<std::size_t>(head[2 + which]) + 1);
+                in.read(reinterpret_cast<char*>(named.data()), static_cast<std::streamsize>(head[2 + which]) * 4);
+                for(std::int32_t p = 0; in && p < head[2 + which]; ++p)
+                {
+                    const auto it = byId.find(named[static_cast<std::size_t>(p)]);
+                    if(it == byId.end())
+                    {
+                        std::fprintf(stderr, "%s names an entry it does not hold\n", argv[3]);
+                        return 5;
+                    }
+                    lists[which].push_back(it->second);
+                }
+                if(!in)
+                {
+                    std::fprintf(stderr, "cannot read the lists of %s\n", argv[3]);
+                    return 5;
+                }
+            }
+            const std::vector<mslam::KeyframeCullVerdict> verdicts = culler->cullKeyframes(lists[0], lists[1], params);
+            std::size_t gone = 0;
+            for(const auto& v : verdicts)
+                gone += v.culled ? 1 : 0;
+            std::printf("cull culled %zu\n", gone);
+            for(std::size_t p = 0; p < verdicts.size(); ++p)
+                std::printf("cand %zu %lld %d %d %d\n", p, static_cast<long long>(verdicts[p].keyframe->id), verdicts[p].culled ? 1 : 0,
+                            verdicts[p].landmarks, verdicts[p].redundant);
+            // the adapter's own account: an entry it no longer holds has no landmark ids to give
+            std::printf("remaining");
+            for(const auto& kf : entries)
+            {
+                try
+                {
+                    (void)localMap->landmarkIds(kf);
+                    std::printf(" %lld", static_cast<long long>(kf->id));
+                }
+                catch(const std::exception&)
+                {
+                }
+            }
+            std::printf("\n");
             return 0;
         }
         if(argc == 5 && std::strcmp(argv[2], "--reloc") == 0)

@@ -484,6 +484,33 @@ class BowDatabase
         return std::vector<int>(removed.begin(), removed.begin() + static_cast<std::ptrdiff_t>(n));
     }
 
+    // ---- keyframe culling (mslam_hip_kf_cull_search, then this adapter's own removeKeyframe for every culled keyframe: the
+    // store id is the BoW entry id, and both entries leave together) ----
+    std::vector<KeyframeCullVerdict> cullKeyframes(const std::vector<KeyframePtr>& map, const std::vector<KeyframePtr>& candidates,
+                                                   const KeyframeCullParams& p)
+    {
+        const std::size_t n = map.size(), m = candidates.size();
+        std::vector<std::int32_t> ids(n + 1), cand(m + 1), landmarks(m + 1), redundant(m + 1);
+        std::vector<std::uint8_t> culled(m + 1);
+        for(std::size_t k = 0; k < n; ++k)
+            ids[k] = storedLandmarksOf(map[k]);
+        for(std::size_t k = 0; k < m; ++k)
+            cand[k] = storedLandmarksOf(candidates[k]);
+        const int rc = mslam_hip_kf_cull_search(ctx.h, ids.data(), static_cast<int>(n), cand.data(), static_cast<int>(m), p.minObservers,
+                                                p.ratio, p.minLandmarks, culled.data(), landmarks.data(), redundant.data(), nullptr);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_cull_search", rc);
+        std::vector<KeyframeCullVerdict> out(m);
+        for(std::size_t k = 0; k < m; ++k)
+        {
+            out[k].keyframe = candidates[k];
+            out[k].culled = culled[k] != 0, out[k].landmarks = landmarks[k], out[k].redundant = redundant[k];
+            if(out[k].culled)
+                removeKeyframe(candidates[k]);
+        }
+        return out;
+    }
+
     KeyframeTrackResult trackAgainst(int refId,const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                      const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
                                      const double* tvecGuess, const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
@@ -644,7 +671,8 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public IKeyframeTracker,
                           public ILocalMapTracker,
                           public ILandmarkFuser,
-                          public IObservationRemover
+                          public IObservationRemover,
+                          public IKeyframeCuller
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -705,6 +733,12 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
     std::vector<int> removeObservations(const std::vector<std::pair<BowDatabase::KeyframePtr, std::int64_t>>& observations) override
     {
         return db->removeObservations(observations);
+    }
+    std::vector<KeyframeCullVerdict> cullKeyframes(const std::vector<BowDatabase::KeyframePtr>& map,
+                                                   const std::vector<BowDatabase::KeyframePtr>& candidates,
+                                                   const KeyframeCullParams& params) override
+    {
+        return db->cullKeyframes(map, candidates, params);
     }
     KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                       const CameraParameters& camera, const std::vector<BowDatabase::KeyframePtr>& neighbours,

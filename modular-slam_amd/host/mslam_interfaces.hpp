@@ -410,4 +410,33 @@ class IObservationRemover
     virtual std::vector<int> removeObservations(const std::vector<std::pair<KeyframePtr, std::int64_t>>& observations) = 0;
     virtual ~IObservationRemover() = default;
 };
+
+// ---- keyframe culling (mslam_hip_kf_cull_search; an extension) -------------------------------------------------------------
+// The reference has the removal primitives (BasicMap::removeKeyframe, basic_map.cpp:110-115; IRelocalizer::removeKeyframe,
+// relocalizer.hpp:19) and no policy that calls them; the model is ORB-SLAM's KeyFrameCulling.  `map` names the stored
+// keyframes that count as observers, `candidates` (distinct, each one of `map`) are judged in the order given: a candidate
+// with at least minLandmarks distinct landmark ids goes when more than `ratio` of them are held by at least minObservers
+// other keyframes of the map, counted without the candidates that went before it.  -> one verdict per candidate, in order,
+// with the two counts seen at its turn.  A culled keyframe has left the adapter the way removeKeyframe removes it (the BoW
+// database and the keyframe store).  A keyframe that is not stored throws.  Offered by the adapter that owns the store.
+struct KeyframeCullParams
+{
+    int minObservers = 3;
+    double ratio = 0.9;
+    int minLandmarks = 1;
+};
+struct KeyframeCullVerdict
+{
+    std::shared_ptr<Keyframe<slam3d::SensorState>> keyframe;
+    bool culled = false;
+    int landmarks = 0, redundant = 0; // distinct landmark ids; those with at least minObservers other observers
+};
+class IKeyframeCuller
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual std::vector<KeyframeCullVerdict> cullKeyframes(const std::vector<KeyframePtr>& map, const std::vector<KeyframePtr>& candidates,
+                                                           const KeyframeCullParams& params) = 0;
+    virtual ~IKeyframeCuller() = default;
+};
 } // namespace mslam
