@@ -44,41 +44,38 @@ struct CullRes // one candidate's record in the mapped result block
 
 // grid = (blocks of 256 positions, entries of the chunk).  slots = the chunk's part of the uploaded slot list.
 __global__ __launch_bounds__(256) void k_cull_mark(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n,
-                                                   const int32_t* __restrict__ slots, int K, LmBucket* __restrict__ table,
-                                                   unsigned long long mask)
+                                                   const int32_t* __restrict__ slots, int K, LmTable t)
 {
     const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const int slot = slots[k];
-    const int n = min(max(store_n[slot], 0), K);
-    if(i >= n)
+    if(i >= entry_count(store_n, slot, K))
         return;
-    const long long b = lm_claim(table, mask, (unsigned long long)store_lid[(size_t)slot * K + i]);
+    const long long b = lm_claim(t, (unsigned long long)store_lid[(size_t)slot * K + i]);
     if(b >= 0)
-        atomicAnd(&table[b].val, ~(1ull << k));
+        atomicAnd(&t.b[b].val, ~(1ull << k));
 }
 
 // one thread per bucket
-__global__ __launch_bounds__(256) void k_cull_count(LmBucket* __restrict__ table, size_t buckets, uint32_t* __restrict__ counts)
+__global__ __launch_bounds__(256) void k_cull_count(LmTable t, uint32_t* __restrict__ counts)
 {
     const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if(b >= buckets)
+    if(b > t.mask)
         return;
-    const unsigned long long v = table[b].val;
+    const unsigned long long v = t.b[b].val;
     if(v != kLmEmpty)
     {
         counts[b] += (uint32_t)__popcll(~v);
-        table[b].val = kLmEmpty;
+        t.b[b].val = kLmEmpty;
     }
 }
 
-__global__ __launch_bounds__(256) void k_cull_lookup(const int64_t* __restrict__ ids, int n, const LmBucket* __restrict__ table,
-                                                     unsigned long long mask, const uint32_t* __restrict__ counts,
+__global__ __launch_bounds__(256) void k_cull_lookup(const int64_t* __restrict__ ids, int n, LmTable t, const uint32_t* __restrict__ counts,
                                                      int32_t* __restrict__ out)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if(p >= n)
         return;
-    const long long b = lm_find(table, mask, (unsigned long long)ids[p]);
+    const long long b = lm_find(t, (unsigned long long)ids[p]);
     out[p] = b >= 0 ? (int32_t)counts[b] : 0;
 }
 
@@ -90,8 +87,7 @@ __device__ __forceinline__ uint32_t cull_load(const uint32_t* p)
 // One workgroup.  bkt[K]: the bucket of every position of the candidate at its turn (a thread reads only what it wrote).
 // An entry holds at most 65535 landmarks, so a thread has at most 64 positions and one 64-bit word names its winners.
 __global__ __launch_bounds__(kCullThreads) void k_cull_greedy(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n,
-                                                              const int32_t* __restrict__ cand_slots, int n_cand, int K,
-                                                              const LmBucket* __restrict__ table, unsigned long long mask,
+                                                              const int32_t* __restrict__ cand_slots, int n_cand, int K, LmTable t,
                                                               uint32_t* counts, uint32_t* stamp, uint32_t* __restrict__ bkt,
                                                               int min_observers, double ratio, int min_landmarks,
                                                               CullRes* __restrict__ res, int32_t* __restrict__ done)
@@ -102,7 +98,7 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_greedy(const int64_t* __r
     for(int c = 0; c < n_cand; ++c)
     {
         const int slot = cand_slots[c];
-        const int n = min(min(max(store_n[slot], 0), K), 65535);
+        const int n = min(entry_count(store_n, slot, K), 65535);
         const int64_t* lid = store_lid + (size_t)slot * K;
         // (A) the first position of every id
         for(int base = 0; base < n; base += kCullThreads)
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_greedy(const int64_t* __r
             const int i = base + tid;
             if(i < n)
             {
-                const long long b = lm_find(table, mask, (unsigned long long)lid[i]);
+                const long long b = lm_find(t, (unsigned long long)lid[i]);
                 bkt[i] = b >= 0 ? (uint32_t)b : kCullNoStamp; // (a candidate is a listed entry: its ids are in the table)
                 if(b >= 0)
                     atomicMin(&stamp[b], (uint32_t)i);
@@ -190,13 +186,12 @@ int cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, in
     pos_of->reserve((size_t)n_ids);
     for(int k = 0; k < n_ids; ++k)
     {
-        const auto it = r->slot_of.find(ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, me + ": id " + std::to_string(ids[k]) + " is not in the keyframe store");
+        const int rc = store_slot(c, me, "id", ids[k], &m->slots[(size_t)k]);
+        if(rc)
+            return rc;
         if(!pos_of->emplace(ids[k], k).second)
             return fail(c, MSLAM_HIP_E_INVALID, me + ": id " + std::to_string(ids[k]) + " is listed twice");
-        m->slots[(size_t)k] = it->second;
-        m->keys += (size_t)r->n_upper[(size_t)it->second];
+        m->keys += (size_t)r->n_upper[(size_t)m->slots[(size_t)k]];
     }
     if(m->keys > (size_t)MSLAM_HIP_CULL_MAX_LANDMARKS)
         return fail(c, MSLAM_HIP_E_CAPACITY, me + ": the listed entries hold up to " + std::to_string(m->keys) + " landmarks, more than " +
@@ -207,7 +202,7 @@ int cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, in
 // where the count arrays lie in d_cull: [counts buckets x u32 | stamps buckets x u32 | buckets of a candidate's positions K x u32]
 struct CullDev
 {
-    LmBucket* table;
+    LmTable table;
     uint32_t *counts, *stamp, *bkt;
     size_t buckets;
 };
@@ -215,10 +210,11 @@ struct CullDev
 int cull_scratch(mslam_hip_ctx* c, size_t keys, CullDev* d)
 {
     RelocState* r = c->reloc;
-    d->buckets = lm_bucket_count(keys);
-    MSLAM_CHK(c, grow(r->d_lm_table, d->buckets * sizeof(LmBucket), c->stream));
+    d->table = lm_table_grow(c, keys);
+    if(!d->table.b)
+        return MSLAM_HIP_E_RUNTIME;
+    d->buckets = (size_t)d->table.mask + 1;
     MSLAM_CHK(c, grow(r->d_cull, (2 * d->buckets + (size_t)c->p.max_keypoints) * 4, c->stream));
-    d->table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
     d->counts = reinterpret_cast<uint32_t*>(r->d_cull.get());
     d->stamp = d->counts + d->buckets;
     d->bkt = d->stamp + d->buckets;
@@ -231,10 +227,9 @@ int cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slot
     RelocState* r = c->reloc;
     hipStream_t s = c->stream;
     const int K = c->p.max_keypoints;
-    const unsigned long long mask = (unsigned long long)(d.buckets - 1);
     {
         StageScope ts(c, "cull_clear");
-        MSLAM_CHK(c, hipMemsetAsync(d.table, 0xFF, d.buckets * sizeof(LmBucket), s));
+        MSLAM_CHK(c, hipMemsetAsync(d.table.b, 0xFF, lm_bytes(d.table), s));
         MSLAM_CHK(c, hipMemsetAsync(d.counts, 0, d.buckets * 4, s));
         MSLAM_CHK(c, hipMemsetAsync(d.stamp, 0xFF, d.buckets * 4, s));
     }
@@ -246,8 +241,8 @@ int cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slot
         for(size_t k = 0; k < len; ++k)
             n_max = std::max(n_max, r->n_upper[(size_t)m.slots[base + k]]);
         const dim3 grid((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)len);
-        hipLaunchKernelGGL(k_cull_mark, grid, dim3(256), 0, s, r->d_lid.get(), r->d_n.get(), d_slots + base, K, d.table, mask);
-        hipLaunchKernelGGL(k_cull_count, dim3((unsigned)((d.buckets + 255) / 256)), dim3(256), 0, s, d.table, d.buckets, d.counts);
+        hipLaunchKernelGGL(k_cull_mark, grid, dim3(256), 0, s, r->d_lid.get(), r->d_n.get(), d_slots + base, K, d.table);
+        hipLaunchKernelGGL(k_cull_count, dim3((unsigned)((d.buckets + 255) / 256)), dim3(256), 0, s, d.table, d.counts);
     }
     MSLAM_CHK(c, hipGetLastError());
     return MSLAM_HIP_OK;
@@ -322,8 +317,8 @@ int cull_run(mslam_hip_ctx* c, const char* who, bool remove, const int32_t* ids,
     {
         StageScope ts(c, "cull_greedy");
         hipLaunchKernelGGL(k_cull_greedy, dim3(1), dim3(kCullThreads), 0, s, r->d_lid.get(), r->d_n.get(),
-                           reinterpret_cast<const int32_t*>(du + o_cand), n_cand, c->p.max_keypoints, d.table,
-                           (unsigned long long)(d.buckets - 1), d.counts, d.stamp, d.bkt, min_observers, ratio, min_landmarks,
+                           reinterpret_cast<const int32_t*>(du + o_cand), n_cand, c->p.max_keypoints, d.table, d.counts, d.stamp,
+                           d.bkt, min_observers, ratio, min_landmarks,
                            reinterpret_cast<CullRes*>(r->h_res.dev() + 16), reinterpret_cast<int32_t*>(r->h_res.dev()));
     }
     MSLAM_CHK(c, hipGetLastError());
@@ -344,11 +339,8 @@ int cull_run(mslam_hip_ctx* c, const char* who, bool remove, const int32_t* ids,
         if(n_redundant)
             n_redundant[k] = res[k].n_redundant;
         total += res[k].culled;
-        if(remove && res[k].culled) // as mslam_hip_kf_remove: the slot goes to the free list, the serial stays
-        {
-            r->free_slots.push_back(cand_slots[(size_t)k]);
-            r->slot_of.erase(cand[k]);
-        }
+        if(remove && res[k].culled)
+            store_release(r, cand[k], cand_slots[(size_t)k]);
     }
     if(n_culled)
         *n_culled = total;
@@ -371,11 +363,9 @@ int mslam_hip_kf_observers(mslam_hip_ctx* c, const int32_t* ids, int n_ids, cons
     rc = cull_resolve(c, me, ids, n_ids, &m, &pos_of);
     if(rc)
         return rc;
-    if(n < 0 || n > (1 << 24) || (n > 0 && (!landmark_ids || !counts)))
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
-    for(int p = 0; p < n; ++p)
-        if(landmark_ids[p] < 0)
-            return fail(c, MSLAM_HIP_E_INVALID, me + ": a landmark id lies outside [0, 2^63)");
+    rc = lid_list_check(c, me, n, landmark_ids && counts, landmark_ids);
+    if(rc)
+        return rc;
     if(n == 0)
         return MSLAM_HIP_OK;
     RelocState* r = c->reloc;
@@ -402,7 +392,7 @@ int mslam_hip_kf_observers(mslam_hip_ctx* c, const int32_t* ids, int n_ids, cons
     {
         StageScope ts(c, "cull_lookup");
         hipLaunchKernelGGL(k_cull_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const int64_t*>(du), n, d.table,
-                           (unsigned long long)(d.buckets - 1), d.counts, reinterpret_cast<int32_t*>(du + o_out));
+                           d.counts, reinterpret_cast<int32_t*>(du + o_out));
     }
     MSLAM_CHK(c, hipGetLastError());
     MSLAM_CHK(c, hipMemcpyAsync(r->h_res.get(), du + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, s));

@@ -2,7 +2,8 @@
 // that duplicate landmarks of another ("keep") by projecting both under one pose and matching inside a window,
 // mslam_hip_kf_replace_ids rewrites landmark ids (and world points) across the whole store, and mslam_hip_kf_fuse runs the
 // two back to back without the pair list leaving the device (the semantics are stated once, at mslam_hip_kf_fuse_search in
-// include/mslam_hip.h).
+// include/mslam_hip.h).  The rewrite itself is the list rewrite of k_localmap.hip (rewrite_enqueue, reloc.hpp), which
+// mslam_hip_kf_update_world shares: stages fuse_table and fuse_replace here.
 //
 // The reference has no code for this: closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580).  The model is
 // ORB-SLAM's SearchAndFuse; this is an extension, not a restatement.
@@ -16,10 +17,6 @@
 //                    acceptance test at the end: per keep landmark the accepted key d0 << 16 | drop position, or none
 //   k_fuse_resolve   one workgroup: atomicMin of d0 << 16 | keep position per claimed drop position, then the ordered
 //                    compaction (ballot + scan) of the keep landmarks that hold their claim
-//   k_fuse_table     the replacement table of a list of ids, value = ~(position): of an id listed twice the later wins
-//   k_fuse_replace   one thread per (live slot, landmark position): a landmark whose id the table holds takes the listed
-//                    id and, where given, the listed world point.  Every thread reads and writes its own landmark only,
-//                    so the substitution is simultaneous
 //
 // Every result is a function of the keys alone (distance, position), never of the order in which the binning scatter or
 // the atomics ran.  All projection arithmetic is f64, every operation rounded on its own (-ffp-contract=off).
@@ -54,8 +51,7 @@ struct FuseArgs
     const int64_t* lid;
     const int32_t* n;
     int K, keep_slot, drop_slot, nk_cap, nd_cap; // n*_cap: what the host knows the entries' counts not to exceed
-    LmBucket *tab_keep, *tab_drop;
-    unsigned long long mask_keep, mask_drop;
+    LmTable tab_keep, tab_drop;
     double R[9], t[3], fx, fy, cx, cy, radius, gate2, ratio;
     int max_distance, width, height;
     GuidedGrid grid;
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(256) void k_fuse_ids(FuseArgs a)
     if(i >= fuse_count(a, side))
         return;
     const size_t at = (size_t)(side ? a.drop_slot : a.keep_slot) * a.K + i;
-    (void)lm_claim(side ? a.tab_drop : a.tab_keep, side ? a.mask_drop : a.mask_keep, (unsigned long long)a.lid[at]);
+    (void)lm_claim(side ? a.tab_drop : a.tab_keep, (unsigned long long)a.lid[at]);
 }
 
 // grid (blocks, 2)
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256) void k_fuse_project(FuseArgs a)
     if(i >= fuse_count(a, side))
         return;
     const size_t at = (size_t)(side ? a.drop_slot : a.keep_slot) * a.K + i;
-    const bool eligible = lm_find(side ? a.tab_keep : a.tab_drop, side ? a.mask_keep : a.mask_drop, (unsigned long long)a.lid[at]) < 0;
+    const bool eligible = lm_find(side ? a.tab_keep : a.tab_drop, (unsigned long long)a.lid[at]) < 0;
     const double X = a.world[at * 3], Y = a.world[at * 3 + 1], Z = a.world[at * 3 + 2];
     const double c0 = ((a.R[0] * X + a.R[1] * Y) + a.R[2] * Z) + a.t[0];
     const double c1 = ((a.R[3] * X + a.R[4] * Y) + a.R[5] * Z) + a.t[1];
@@ -239,64 +235,6 @@ __global__ __launch_bounds__(kResolveThreads) void k_fuse_resolve(FuseArgs a)
     }
 }
 
-// the list of a replacement: n entries, or *n_dev of them when that fits `cap` and none otherwise
-struct ReplaceList
-{
-    const int64_t *from, *to;
-    const double* xyz; // n x 3, or nullptr: the ids alone
-    const int32_t* n_dev;
-    int n, cap;
-};
-
-__device__ __forceinline__ int replace_count(const ReplaceList& l)
-{
-    if(!l.n_dev)
-        return l.n;
-    const int n = *l.n_dev;
-    return n >= 0 && n <= l.cap ? n : 0;
-}
-
-__global__ __launch_bounds__(256) void k_fuse_table(ReplaceList l, LmBucket* __restrict__ table, unsigned long long mask)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if(i >= replace_count(l))
-        return;
-    const long long b = lm_claim(table, mask, (unsigned long long)l.from[i]);
-    if(b >= 0)
-        atomicMin(&table[b].val, ~(unsigned long long)i);
-}
-
-// grid (landmark blocks, live slots).  *rewritten counts the matches (an integer count: its value does not depend on the
-// order of the additions).
-__global__ __launch_bounds__(256) void k_fuse_replace(int64_t* __restrict__ store_lid, double* __restrict__ store_world,
-                                                      const int32_t* __restrict__ store_n, const int32_t* __restrict__ slots, int K,
-                                                      const LmBucket* __restrict__ table, unsigned long long mask, ReplaceList l,
-                                                      uint32_t* __restrict__ rewritten)
-{
-    const int slot = slots[blockIdx.y], i = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(max(store_n[slot], 0), K), n_list = replace_count(l);
-    bool hit = false;
-    if(i < n && n_list > 0)
-    {
-        const size_t at = (size_t)slot * K + i;
-        const long long b = lm_find(table, mask, (unsigned long long)store_lid[at]);
-        if(b >= 0)
-        {
-            const unsigned long long src = ~table[b].val;
-            if(src < (unsigned long long)n_list)
-            {
-                hit = true;
-                store_lid[at] = l.to[src];
-                if(l.xyz)
-                    store_world[at * 3] = l.xyz[src * 3], store_world[at * 3 + 1] = l.xyz[src * 3 + 1], store_world[at * 3 + 2] = l.xyz[src * 3 + 2];
-            }
-        }
-    }
-    const unsigned long long bal = __ballot(hit);
-    if((threadIdx.x & 63) == 0 && bal)
-        atomicAdd(rewritten, (uint32_t)__popcll(bal));
-}
-
 } // namespace mslam
 
 using namespace mslam;
@@ -319,22 +257,9 @@ struct SearchPlan
 {
     FuseArgs a{};
     int P = 0;                       // rows of the pair arrays: min of the two entries' upper bounds
-    size_t buckets_rep = 0, o_rep = 0; // the replacement table inside d_lm_table (kf_fuse)
+    LmTable tab_rep{};               // the replacement table inside d_lm_table (kf_fuse)
     bool empty = false;              // an entry holds nothing: no launch, no pairs
 };
-
-// the live slots in ascending order and the largest count among them
-int live_slots(const RelocState* r, std::vector<int32_t>* slots)
-{
-    int n_max = 0;
-    for(const auto& e : r->slot_of)
-    {
-        slots->push_back(e.second);
-        n_max = std::max(n_max, r->n_upper[(size_t)e.second]);
-    }
-    std::sort(slots->begin(), slots->end());
-    return n_max;
-}
 
 int search_check(mslam_hip_ctx* c, const std::string& me, const SearchParams& p, int* keep_slot, int* drop_slot)
 {
@@ -343,9 +268,11 @@ int search_check(mslam_hip_ctx* c, const std::string& me, const SearchParams& p,
         return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
     if(p.keep_id == p.drop_id)
         return fail(c, MSLAM_HIP_E_INVALID, me + ": keep_id and drop_id name one entry");
-    auto k = r->slot_of.find(p.keep_id), d = r->slot_of.find(p.drop_id);
-    if(k == r->slot_of.end() || d == r->slot_of.end())
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": id " + std::to_string(k == r->slot_of.end() ? p.keep_id : p.drop_id) + " is not in the keyframe store");
+    int rc = store_slot(c, me, "id", p.keep_id, keep_slot);
+    if(!rc)
+        rc = store_slot(c, me, "id", p.drop_id, drop_slot);
+    if(rc)
+        return rc;
     if(!(p.radius > 0.0))
         return fail(c, MSLAM_HIP_E_INVALID, me + ": the radius is not a positive number");
     if(p.max_distance < 0 || p.max_distance > 256)
@@ -356,9 +283,8 @@ int search_check(mslam_hip_ctx* c, const std::string& me, const SearchParams& p,
         return fail(c, MSLAM_HIP_E_INVALID, me + ": fx or fy is zero or NaN");
     if(!(p.max_world_distance > 0.0))
         return fail(c, MSLAM_HIP_E_INVALID, me + ": max_world_distance is not a positive number");
-    if(r->n_upper[(size_t)k->second] > 65535 || r->n_upper[(size_t)d->second] > 65535)
+    if(r->n_upper[(size_t)*keep_slot] > 65535 || r->n_upper[(size_t)*drop_slot] > 65535)
         return fail(c, MSLAM_HIP_E_INVALID, me + ": entries of more than 65535 landmarks are not supported");
-    *keep_slot = k->second, *drop_slot = d->second;
     return MSLAM_HIP_OK;
 }
 
@@ -393,14 +319,16 @@ int search_enqueue(mslam_hip_ctx* c, const SearchParams& p, int keep_slot, int d
     int rc = reloc_scratch(c, up, o, h_bytes);
     if(rc)
         return rc;
-    MSLAM_CHK(c, grow(r->d_lm_table, tab_bytes, c->stream));
-    uint8_t *A = r->d_arena, *T = r->d_lm_table, *H = r->h_res.dev();
     FuseArgs& a = plan->a;
+    a.tab_keep = lm_table_grow(c, (size_t)nk, tab_bytes);
+    if(!a.tab_keep.b)
+        return MSLAM_HIP_E_RUNTIME;
+    a.tab_drop = lm_table_grow(c, (size_t)nd, tab_bytes, bk * sizeof(LmBucket)); // (the block has its size: no growth, no failure)
+    if(with_rep)
+        plan->tab_rep = lm_table_grow(c, P, tab_bytes, (bk + bd) * sizeof(LmBucket));
+    uint8_t *A = r->d_arena, *T = r->d_lm_table, *H = r->h_res.dev();
     a.desc = r->d_desc, a.world = r->d_world, a.lid = r->d_lid, a.n = r->d_n;
     a.K = (int)K, a.keep_slot = keep_slot, a.drop_slot = drop_slot, a.nk_cap = nk, a.nd_cap = nd;
-    a.tab_keep = reinterpret_cast<LmBucket*>(T), a.tab_drop = a.tab_keep + bk;
-    a.mask_keep = bk - 1, a.mask_drop = bd - 1;
-    plan->o_rep = (bk + bd) * sizeof(LmBucket), plan->buckets_rep = bp;
     std::memcpy(a.R, p.R, sizeof(a.R));
     std::memcpy(a.t, p.t, sizeof(a.t));
     a.fx = p.fx, a.fy = p.fy, a.cx = p.cx, a.cy = p.cy, a.radius = p.radius, a.ratio = p.ratio;
@@ -520,56 +448,10 @@ int mslam_hip_kf_replace_ids(mslam_hip_ctx* c, const int64_t* from_ids, const in
     int rc = reloc_enter(c);
     if(rc)
         return rc;
-    if(n < 0 || n > (1 << 24) || (n > 0 && (!from_ids || !to_ids)))
-        return fail(c, MSLAM_HIP_E_INVALID, "kf_replace_ids: bad argument");
-    for(int i = 0; i < n; ++i)
-        if(from_ids[i] < 0 || to_ids[i] < 0)
-            return fail(c, MSLAM_HIP_E_INVALID, "kf_replace_ids: a landmark id lies outside [0, 2^63)");
-    RelocState* r = c->reloc;
-    if(n == 0 || r->slot_of.empty())
-        return MSLAM_HIP_OK;
-    const int K = c->p.max_keypoints;
-    std::vector<int32_t> slots;
-    const int n_max = live_slots(r, &slots);
-    // one upload: [from n x i64 | to n x i64 | points n x 3 f64 (when given) | live slots | the count, zero]
-    const size_t o_to = (size_t)n * 8, o_xyz = o_to + (size_t)n * 8, o_slots = o_xyz + (world_xyz ? (size_t)n * 24 : 0);
-    const size_t o_cnt = o_slots + slots.size() * 4, up = o_cnt + 4;
-    const size_t buckets = lm_bucket_count((size_t)n);
-    rc = reloc_scratch(c, up, 0, 0);
+    rc = lid_list_check(c, "kf_replace_ids", n, from_ids && to_ids, from_ids, to_ids);
     if(rc)
         return rc;
-    MSLAM_CHK(c, grow(r->d_lm_table, buckets * sizeof(LmBucket), c->stream));
-    uint8_t* h = r->h_up;
-    std::memcpy(h, from_ids, (size_t)n * 8);
-    std::memcpy(h + o_to, to_ids, (size_t)n * 8);
-    if(world_xyz)
-        std::memcpy(h + o_xyz, world_xyz, (size_t)n * 24);
-    std::memcpy(h + o_slots, slots.data(), slots.size() * 4);
-    std::memset(h + o_cnt, 0, 4);
-    hipStream_t s = c->stream;
-    uint8_t* d = r->d_up;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
-    const ReplaceList l{reinterpret_cast<const int64_t*>(d), reinterpret_cast<const int64_t*>(d + o_to),
-                        world_xyz ? reinterpret_cast<const double*>(d + o_xyz) : nullptr, nullptr, n, n};
-    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
-    MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
-    {
-        StageScope ts(c, "fuse_table");
-        hipLaunchKernelGGL(k_fuse_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, l, table, (unsigned long long)(buckets - 1));
-    }
-    {
-        StageScope ts(c, "fuse_replace");
-        hipLaunchKernelGGL(k_fuse_replace, dim3((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)slots.size()), dim3(256), 0, s,
-                           r->d_lid.get(), r->d_world.get(), r->d_n.get(), reinterpret_cast<const int32_t*>(d + o_slots), K, table,
-                           (unsigned long long)(buckets - 1), l, reinterpret_cast<uint32_t*>(d + o_cnt));
-    }
-    MSLAM_CHK(c, hipGetLastError());
-    uint32_t rewritten = 0;
-    MSLAM_CHK(c, hipMemcpyAsync(&rewritten, d + o_cnt, 4, hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    if(n_rewritten)
-        *n_rewritten = (int)rewritten;
-    return MSLAM_HIP_OK;
+    return rewrite_host_list(c, from_ids, to_ids, world_xyz, n, "fuse_table", "fuse_replace", n_rewritten);
 }
 
 int mslam_hip_kf_fuse(mslam_hip_ctx* c, int keep_id, int drop_id, const double* R, const double* t, double fx, double fy, double cx, double cy,
@@ -592,7 +474,6 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* c, int keep_id, int drop_id, const double* 
     if(rc)
         return rc;
     RelocState* r = c->reloc;
-    const int K = c->p.max_keypoints;
     std::vector<int32_t> slots;
     const int n_max = live_slots(r, &slots);
     // one upload: [live slots | the count, zero]
@@ -604,31 +485,15 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* c, int keep_id, int drop_id, const double* 
     uint8_t *h = r->h_up, *d = r->d_up;
     std::memcpy(h, slots.data(), slots.size() * 4);
     std::memset(h + o_cnt, 0, 4);
-    hipStream_t s = c->stream;
-    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
-    // drop_lid -> keep_lid with the keep landmark's world point, straight from the device list; nothing when the pairs
-    // exceed `capacity`
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table + plan.o_rep);
-    const unsigned long long mask = plan.buckets_rep - 1;
-    const ReplaceList l{plan.a.dev.drop_lid, plan.a.dev.keep_lid, plan.a.pair_world, plan.a.n_pairs, 0, std::min(capacity, plan.P)};
-    {
-        StageScope ts(c, "fuse_table");
-        hipLaunchKernelGGL(k_fuse_table, dim3((unsigned)((plan.P + 255) / 256)), dim3(256), 0, s, l, table, mask);
-    }
-    {
-        StageScope ts(c, "fuse_replace");
-        hipLaunchKernelGGL(k_fuse_replace, dim3((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)slots.size()), dim3(256), 0, s,
-                           r->d_lid.get(), r->d_world.get(), r->d_n.get(), reinterpret_cast<const int32_t*>(d), K, table, mask, l,
-                           reinterpret_cast<uint32_t*>(d + o_cnt));
-    }
-    MSLAM_CHK(c, hipGetLastError());
-    uint32_t rewritten = 0;
-    MSLAM_CHK(c, hipMemcpyAsync(&rewritten, d + o_cnt, 4, hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    rc = search_collect(c, me, plan, keep_pos, drop_pos, keep_lid, drop_lid, dist, capacity, n_pairs);
-    if(n_rewritten)
-        *n_rewritten = (int)rewritten;
-    return rc;
+    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c->stream));
+    // drop_lid -> keep_lid with the keep landmark's world point, straight from the device list (at most P places); nothing
+    // when the pairs exceed `capacity`
+    const ReplaceList l{plan.a.dev.drop_lid, plan.a.dev.keep_lid, plan.a.pair_world, plan.a.n_pairs, plan.P, std::min(capacity, plan.P)};
+    rc = rewrite_enqueue(c, l, plan.tab_rep, reinterpret_cast<const int32_t*>(d), (int)slots.size(), n_max,
+                         reinterpret_cast<uint32_t*>(d + o_cnt), "fuse_table", "fuse_replace");
+    if(!rc)
+        rc = rewrite_count(c, reinterpret_cast<const uint32_t*>(d + o_cnt), n_rewritten);
+    return rc ? rc : search_collect(c, me, plan, keep_pos, drop_pos, keep_lid, drop_lid, dist, capacity, n_pairs);
 }
 
 } // extern "C"

@@ -1,20 +1,22 @@
 // k_localmap.hip — the local map on the keyframe store: the union of up to 64 entries as an ordinary entry
 // (mslam_hip_kf_union[_dev]) and covisibility counts (mslam_hip_kf_covisible), both on the landmark ids the store keeps
-// next to every landmark; and mslam_hip_kf_update_world, which writes a list of refined world points into every entry that
-// holds their ids (the way back from bundle adjustment, k_ba.hip).
+// next to every landmark; and the list rewrite: mslam_hip_kf_update_world writes a list of refined world points into every
+// entry that holds their ids (the way back from bundle adjustment, k_ba.hip), and mslam_hip_kf_replace_ids / mslam_hip_kf_fuse
+// (k_fuse.hip) rewrite ids, and points, through the same two kernels (rewrite_enqueue, declared in reloc.hpp).
 //
 // What getLandmarksWithKeypoints builds for track() (reference rgbd_feature_frontend.cpp:256-277): the most recent
 // observation of every landmark seen from a set of keyframes (RecentObservationsVisitor, :57-80: the observation whose
 // keyframe id is the largest), and the edge test of BasicMap::updateCovisibility (basic_map.cpp:141-164: two keyframes are
 // neighbours when they observe a landmark in common).
 //
-// Both run on one open-addressing hash table in device scratch (lm_table.hpp).  A key is claimed with one compare-and-swap;
+// All run on one open-addressing hash table in device scratch (lm_table.hpp).  A key is claimed with one compare-and-swap;
 // what the value holds differs:
 //   union        ~pack, pack = (rank + 1) << 32 | list position << 16 | landmark position, lowered with atomicMin: the
 //                smallest ~pack is the largest pack, i.e. the listed entry with the largest keyframe id (rank = the rank
 //                of its id among the listed ids), and inside one entry the highest position.  The cleared value (all
 //                ones) is above every ~pack;
-//   covisible    a 64-bit mask, bit k = "entry ids[k] holds this landmark id", so a repeat inside an entry counts once.
+//   covisible    a 64-bit mask, bit k = "entry ids[k] holds this landmark id", so a repeat inside an entry counts once;
+//   rewrite      ~(place in the caller's list), lowered with atomicMin: of an id listed twice the later place wins.
 // The union's result order is by list position, then landmark position: the grid is laid out that way (blockIdx.y = list
 // position), winners are counted per block, one workgroup scans the block counts, and the scatter places every winner
 // at its block's offset plus its ballot / popcount prefix, as k_kf_lift does inside one block.
@@ -49,39 +51,35 @@ __device__ __forceinline__ unsigned long long lm_pack(int rank, int k, int i)
 // One thread per (list position k = blockIdx.y, landmark position i).  as_mask = 0: the union's insert (atomicMin of
 // ~pack); as_mask = 1: covisible's insert, every value becomes the empty mask 0.
 __global__ __launch_bounds__(256) void k_lm_insert(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
-                                                   int K, LmBucket* __restrict__ table, unsigned long long mask, int as_mask)
+                                                   int K, LmTable t, int as_mask)
 {
     const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const int slot = list.slot[k];
-    const int n = min(max(store_n[slot], 0), K);
-    if(i >= n)
+    if(i >= entry_count(store_n, slot, K))
         return;
-    const unsigned long long key = (unsigned long long)store_lid[(size_t)slot * K + i];
-    const long long b = lm_claim(table, mask, key);
+    const long long b = lm_claim(t, (unsigned long long)store_lid[(size_t)slot * K + i]);
     if(b < 0)
         return;
     if(as_mask)
-        atomicAnd(&table[b].val, 0ull);
+        atomicAnd(&t.b[b].val, 0ull);
     else
-        atomicMin(&table[b].val, ~lm_pack(list.rank[k], k, i));
+        atomicMin(&t.b[b].val, ~lm_pack(list.rank[k], k, i));
 }
 
 // Same grid: a thread wins when the bucket of its landmark id holds its own pack.  Per wave the ballot of the winners,
 // per block their count.
 __global__ __launch_bounds__(256) void k_lm_select(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
-                                                   int K, const LmBucket* __restrict__ table, unsigned long long mask,
-                                                   unsigned long long* __restrict__ win, uint32_t* __restrict__ cnt)
+                                                   int K, LmTable t, unsigned long long* __restrict__ win, uint32_t* __restrict__ cnt)
 {
     __shared__ uint32_t wsum[4];
     const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = blockIdx.x * 256 + tid;
     const size_t blk = (size_t)k * gridDim.x + blockIdx.x;
     const int slot = list.slot[k];
-    const int n = min(max(store_n[slot], 0), K);
     bool w = false;
-    if(i < n)
+    if(i < entry_count(store_n, slot, K))
     {
-        const long long b = lm_find(table, mask, (unsigned long long)store_lid[(size_t)slot * K + i]);
-        w = b >= 0 && table[b].val == ~lm_pack(list.rank[k], k, i);
+        const long long b = lm_find(t, (unsigned long long)store_lid[(size_t)slot * K + i]);
+        w = b >= 0 && t.b[b].val == ~lm_pack(list.rank[k], k, i);
     }
     const unsigned long long bal = __ballot(w);
     if(lane == 0)
@@ -167,13 +165,12 @@ __global__ __launch_bounds__(256) void k_lm_scatter(const uint8_t* __restrict__ 
 // One workgroup per listed entry k, over a table built from entry `id` with empty masks: a landmark id the table holds
 // sets bit k of its mask, and counts when the bit was clear (a repeat inside entry k counts once).
 __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
-                                                      int K, LmBucket* __restrict__ table, unsigned long long mask,
-                                                      int32_t* __restrict__ h_counts)
+                                                      int K, LmTable t, int32_t* __restrict__ h_counts)
 {
     __shared__ uint32_t wsum[4];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slot = list.slot[k];
-    const int n = min(max(store_n[slot], 0), K);
+    const int n = entry_count(store_n, slot, K);
     const unsigned long long bit = 1ull << k;
     uint32_t mine = 0; // (wave-uniform: every lane adds the same popcount)
     for(int base = 0; base < n; base += 256)
@@ -182,8 +179,8 @@ __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict_
         bool hit = false;
         if(i < n)
         {
-            const long long b = lm_find(table, mask, (unsigned long long)store_lid[(size_t)slot * K + i]);
-            hit = b >= 0 && !(atomicOr(&table[b].val, bit) & bit);
+            const long long b = lm_find(t, (unsigned long long)store_lid[(size_t)slot * K + i]);
+            hit = b >= 0 && !(atomicOr(&t.b[b].val, bit) & bit);
         }
         mine += (uint32_t)__popcll(__ballot(hit));
     }
@@ -194,61 +191,146 @@ __global__ __launch_bounds__(256) void k_lm_covisible(const int64_t* __restrict_
         h_counts[k] = (int32_t)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
 }
 
-// mslam_hip_kf_update_world: the table of a caller's list, value = ~(position in the list), lowered with atomicMin: of an id
-// listed twice the later position wins
-__global__ __launch_bounds__(256) void k_lm_insert_list(const int64_t* __restrict__ ids, int n, LmBucket* __restrict__ table,
-                                                        unsigned long long mask)
+__device__ __forceinline__ int replace_count(const ReplaceList& l)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if(i >= n)
-        return;
-    const long long b = lm_claim(table, mask, (unsigned long long)ids[i]);
-    if(b >= 0)
-        atomicMin(&table[b].val, ~(unsigned long long)i);
+    if(!l.n_dev)
+        return l.n;
+    const int n = *l.n_dev;
+    return n >= 0 && n <= l.cap ? n : 0;
 }
 
-// One thread per (live slot = blockIdx.y, landmark position): a landmark whose id the table holds takes the listed world
-// point.  *written counts them (an integer count: its value does not depend on the order of the additions).
-__global__ __launch_bounds__(256) void k_lm_update_world(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n,
-                                                         const int32_t* __restrict__ slots, int K, const LmBucket* __restrict__ table,
-                                                         unsigned long long mask, const double* __restrict__ xyz, int n_list,
-                                                         double* __restrict__ store_world, uint32_t* __restrict__ written)
+// the table of a rewrite's list: value = ~(place), lowered with atomicMin
+__global__ __launch_bounds__(256) void k_fuse_table(ReplaceList l, LmTable t)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if(i >= replace_count(l))
+        return;
+    const long long b = lm_claim(t, (unsigned long long)l.from[i]);
+    if(b >= 0)
+        atomicMin(&t.b[b].val, ~(unsigned long long)i);
+}
+
+// grid (landmark blocks, live slots): a landmark whose id the table holds takes the listed id and the listed world point,
+// whichever the list gives.  Every thread reads and writes its own landmark only, so the substitution is simultaneous.
+// *rewritten counts the matches (an integer count: its value does not depend on the order of the additions).
+__global__ __launch_bounds__(256) void k_fuse_replace(int64_t* __restrict__ store_lid, double* __restrict__ store_world,
+                                                      const int32_t* __restrict__ store_n, const int32_t* __restrict__ slots, int K,
+                                                      LmTable t, ReplaceList l, uint32_t* __restrict__ rewritten)
 {
     const int slot = slots[blockIdx.y], i = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(max(store_n[slot], 0), K);
+    const int n = entry_count(store_n, slot, K), n_list = replace_count(l);
     bool hit = false;
-    if(i < n)
+    if(i < n && n_list > 0)
     {
         const size_t at = (size_t)slot * K + i;
-        const long long b = lm_find(table, mask, (unsigned long long)store_lid[at]);
+        const long long b = lm_find(t, (unsigned long long)store_lid[at]);
         if(b >= 0)
         {
-            const unsigned long long src = ~table[b].val;
+            const unsigned long long src = ~t.b[b].val;
             if(src < (unsigned long long)n_list)
             {
                 hit = true;
-                store_world[at * 3] = xyz[src * 3], store_world[at * 3 + 1] = xyz[src * 3 + 1], store_world[at * 3 + 2] = xyz[src * 3 + 2];
+                if(l.to)
+                    store_lid[at] = l.to[src];
+                if(l.xyz)
+                    store_world[at * 3] = l.xyz[src * 3], store_world[at * 3 + 1] = l.xyz[src * 3 + 1], store_world[at * 3 + 2] = l.xyz[src * 3 + 2];
             }
         }
     }
     const unsigned long long bal = __ballot(hit);
     if((threadIdx.x & 63) == 0 && bal)
-        atomicAdd(written, (uint32_t)__popcll(bal));
+        atomicAdd(rewritten, (uint32_t)__popcll(bal));
 }
 
 } // namespace mslam
 
 using namespace mslam;
 
+// ---- the list rewrite (declared in reloc.hpp: k_fuse.hip calls it too)
+int mslam::live_slots(const RelocState* r, std::vector<int32_t>* slots)
+{
+    int n_max = 0;
+    for(const auto& e : r->slot_of)
+    {
+        slots->push_back(e.second);
+        n_max = std::max(n_max, r->n_upper[(size_t)e.second]);
+    }
+    std::sort(slots->begin(), slots->end());
+    return n_max;
+}
+
+int mslam::rewrite_enqueue(mslam_hip_ctx* c, const ReplaceList& l, LmTable t, const int32_t* d_slots, int n_slots, int n_max,
+                           uint32_t* d_count, const char* stage_table, const char* stage_write)
+{
+    RelocState* r = c->reloc;
+    {
+        StageScope ts(c, stage_table);
+        hipLaunchKernelGGL(k_fuse_table, dim3((unsigned)((l.n + 255) / 256)), dim3(256), 0, c->stream, l, t);
+    }
+    {
+        StageScope ts(c, stage_write);
+        hipLaunchKernelGGL(k_fuse_replace, dim3((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)n_slots), dim3(256), 0, c->stream,
+                           r->d_lid.get(), r->d_world.get(), r->d_n.get(), d_slots, c->p.max_keypoints, t, l, d_count);
+    }
+    MSLAM_CHK(c, hipGetLastError());
+    return MSLAM_HIP_OK;
+}
+
+int mslam::rewrite_count(mslam_hip_ctx* c, const uint32_t* d_count, int* n_out)
+{
+    uint32_t n = 0;
+    MSLAM_CHK(c, hipMemcpyAsync(&n, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+    MSLAM_CHK(c, hipStreamSynchronize(c->stream));
+    if(n_out)
+        *n_out = (int)n;
+    return MSLAM_HIP_OK;
+}
+
+int mslam::rewrite_host_list(mslam_hip_ctx* c, const int64_t* from, const int64_t* to, const double* xyz, int n, const char* stage_table,
+                             const char* stage_write, int* n_out)
+{
+    RelocState* r = c->reloc;
+    if(n == 0 || r->slot_of.empty())
+        return MSLAM_HIP_OK;
+    std::vector<int32_t> slots;
+    const int n_max = live_slots(r, &slots);
+    // one upload: [from n x i64 | to n x i64 | points n x 3 f64 | live slots | the count, zero], `to` and the points when given
+    const size_t o_to = (size_t)n * 8, o_xyz = o_to + (to ? (size_t)n * 8 : 0), o_slots = o_xyz + (xyz ? (size_t)n * 24 : 0);
+    const size_t o_cnt = o_slots + slots.size() * 4, up = o_cnt + 4;
+    int rc = reloc_scratch(c, up, 0, 0);
+    if(rc)
+        return rc;
+    const LmTable table = lm_table_grow(c, (size_t)n);
+    if(!table.b)
+        return MSLAM_HIP_E_RUNTIME;
+    uint8_t *h = r->h_up, *d = r->d_up;
+    std::memcpy(h, from, (size_t)n * 8);
+    if(to)
+        std::memcpy(h + o_to, to, (size_t)n * 8);
+    if(xyz)
+        std::memcpy(h + o_xyz, xyz, (size_t)n * 24);
+    std::memcpy(h + o_slots, slots.data(), slots.size() * 4);
+    std::memset(h + o_cnt, 0, 4);
+    const ReplaceList l{reinterpret_cast<const int64_t*>(d), to ? reinterpret_cast<const int64_t*>(d + o_to) : nullptr,
+                        xyz ? reinterpret_cast<const double*>(d + o_xyz) : nullptr, nullptr, n, n};
+    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c->stream));
+    MSLAM_CHK(c, hipMemsetAsync(table.b, 0xFF, lm_bytes(table), c->stream));
+    rc = rewrite_enqueue(c, l, table, reinterpret_cast<const int32_t*>(d + o_slots), (int)slots.size(), n_max,
+                         reinterpret_cast<uint32_t*>(d + o_cnt), stage_table, stage_write);
+    return rc ? rc : rewrite_count(c, reinterpret_cast<const uint32_t*>(d + o_cnt), n_out);
+}
+
 // the per-block arrays of nb blocks, in bytes: [win nb x 4 u64 | cnt nb | ofs nb + 1]; and nb of a block of `bytes`
 static size_t lm_blocks_bytes(size_t nb) { return nb * 32 + nb * 4 + (nb + 1) * 4; }
 static size_t lm_blocks_cap(size_t bytes) { return (bytes - 4) / 40; }
 
-// the scratch both calls share: a table of `buckets` buckets, per-block arrays for `blocks` blocks, the mapped result
-static int lm_scratch(mslam_hip_ctx* c, size_t buckets, size_t blocks)
+// the scratch union and covisible share: a table for `keys` keys, per-block arrays for `blocks` blocks, the mapped result
+static int lm_scratch(mslam_hip_ctx* c, size_t keys, size_t blocks, LmTable* t)
 {
     RelocState* r = c->reloc;
-    MSLAM_CHK(c, grow(r->d_lm_table, buckets * sizeof(LmBucket), c->stream));
+    *t = lm_table_grow(c, keys);
+    if(!t->b)
+        return MSLAM_HIP_E_RUNTIME;
     MSLAM_CHK(c, grow(r->d_lm_blocks, lm_blocks_bytes(std::max(blocks, (size_t)256)), c->stream));
     if(!r->h_lm)
         MSLAM_CHK(c, r->h_lm.alloc(sizeof(LmHead) + kRelocMaxCand * 4));
@@ -270,9 +352,9 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     int n_max = 0;
     for(int k = 0; k < n_ids; ++k)
     {
-        auto it = r->slot_of.find(ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is not in the keyframe store");
+        rc = store_slot(c, who, "id", ids[k], &list.slot[k]);
+        if(rc)
+            return rc;
         if(ids[k] == dst_id)
             return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": dst_id is one of the listed ids");
         int rank = 0;
@@ -282,14 +364,14 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
                 return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": id " + std::to_string(ids[k]) + " is listed twice");
             rank += ids[j] < ids[k] ? 1 : 0;
         }
-        list.slot[k] = it->second;
         list.rank[k] = rank;
-        keys += (size_t)r->n_upper[(size_t)it->second];
-        n_max = std::max(n_max, r->n_upper[(size_t)it->second]);
+        keys += (size_t)r->n_upper[(size_t)list.slot[k]];
+        n_max = std::max(n_max, r->n_upper[(size_t)list.slot[k]]);
     }
     const unsigned bx = (unsigned)std::max((n_max + 255) / 256, 1);
-    const size_t nb = (size_t)bx * (size_t)n_ids, buckets = lm_bucket_count(keys);
-    rc = lm_scratch(c, buckets, nb);
+    const size_t nb = (size_t)bx * (size_t)n_ids;
+    LmTable table{};
+    rc = lm_scratch(c, keys, nb, &table);
     if(rc)
         return rc;
     // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
@@ -299,7 +381,6 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     (void)store_next_lid_base(c); // a new serial for the entry; its landmarks keep the ids they have
     const size_t slot = (size_t)*dst_slot;
     hipStream_t s = c->stream;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
     unsigned long long* win = reinterpret_cast<unsigned long long*>(r->d_lm_blocks.get());
     const size_t cap_blocks = lm_blocks_cap(r->d_lm_blocks.size());
     uint32_t* cnt = reinterpret_cast<uint32_t*>(r->d_lm_blocks + cap_blocks * 32);
@@ -307,15 +388,15 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     const dim3 grid(bx, (unsigned)n_ids);
     {
         StageScope ts(c, "union_clear");
-        MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+        MSLAM_CHK(c, hipMemsetAsync(table.b, 0xFF, lm_bytes(table), s));
     }
     {
         StageScope ts(c, "union_insert");
-        hipLaunchKernelGGL(k_lm_insert, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, (unsigned long long)(buckets - 1), 0);
+        hipLaunchKernelGGL(k_lm_insert, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, 0);
     }
     {
         StageScope ts(c, "union_select");
-        hipLaunchKernelGGL(k_lm_select, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, (unsigned long long)(buckets - 1), win, cnt);
+        hipLaunchKernelGGL(k_lm_select, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, win, cnt);
     }
     {
         StageScope ts(c, "union_scan");
@@ -373,43 +454,34 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* c, int id, const int32_t* ids, int n_i
         return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: bad argument (at most 64 ids)");
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints;
-    auto own = r->slot_of.find(id);
-    if(own == r->slot_of.end())
-        return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(id) + " is not in the keyframe store");
     LmList list{}, self{};
-    for(int k = 0; k < n_ids; ++k)
-    {
-        auto it = r->slot_of.find(ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, "kf_covisible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
-        list.slot[k] = it->second;
-    }
-    if(n_ids == 0)
-        return MSLAM_HIP_OK;
-    self.slot[0] = own->second;
-    const int n_own = r->n_upper[(size_t)own->second];
-    const size_t buckets = lm_bucket_count((size_t)n_own);
-    rc = lm_scratch(c, buckets, 1);
+    rc = store_slot(c, "kf_covisible", "id", id, &self.slot[0]);
+    for(int k = 0; !rc && k < n_ids; ++k)
+        rc = store_slot(c, "kf_covisible", "id", ids[k], &list.slot[k]);
+    if(rc || n_ids == 0)
+        return rc;
+    const int n_own = r->n_upper[(size_t)self.slot[0]];
+    LmTable table{};
+    rc = lm_scratch(c, (size_t)n_own, 1, &table);
     if(rc)
         return rc;
     hipStream_t s = c->stream;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
     int32_t* h_counts = reinterpret_cast<int32_t*>(r->h_lm + sizeof(LmHead));
     for(int k = 0; k < n_ids; ++k)
         h_counts[k] = -1; // (overwritten by k_lm_covisible; checked after the synchronisation)
     {
         StageScope ts(c, "covisible_clear");
-        MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
+        MSLAM_CHK(c, hipMemsetAsync(table.b, 0xFF, lm_bytes(table), s));
     }
     {
         StageScope ts(c, "covisible_insert");
         hipLaunchKernelGGL(k_lm_insert, dim3((unsigned)std::max((n_own + 255) / 256, 1), 1), dim3(256), 0, s, r->d_lid, r->d_n, self, K, table,
-                           (unsigned long long)(buckets - 1), 1);
+                           1);
     }
     {
         StageScope ts(c, "covisible_count");
         hipLaunchKernelGGL(k_lm_covisible, dim3((unsigned)n_ids), dim3(256), 0, s, r->d_lid, r->d_n, list, K, table,
-                           (unsigned long long)(buckets - 1), reinterpret_cast<int32_t*>(r->h_lm.dev() + sizeof(LmHead)));
+                           reinterpret_cast<int32_t*>(r->h_lm.dev() + sizeof(LmHead)));
     }
     MSLAM_CHK(c, hipGetLastError());
     MSLAM_CHK(c, hipStreamSynchronize(s));
@@ -429,55 +501,7 @@ int mslam_hip_kf_update_world(mslam_hip_ctx* c, const int64_t* landmark_ids, con
         return rc;
     if(n < 0 || n > (1 << 24) || (n > 0 && (!landmark_ids || !world_xyz)))
         return fail(c, MSLAM_HIP_E_INVALID, "kf_update_world: bad argument");
-    RelocState* r = c->reloc;
-    if(n == 0 || r->slot_of.empty())
-        return MSLAM_HIP_OK;
-    const int K = c->p.max_keypoints;
-    std::vector<int32_t> slots;
-    int n_max = 0;
-    for(const auto& e : r->slot_of)
-    {
-        slots.push_back(e.second);
-        n_max = std::max(n_max, r->n_upper[(size_t)e.second]);
-    }
-    std::sort(slots.begin(), slots.end());
-    // one upload: [ids n x i64 | points n x 3 f64 | live slots | the count, zero]
-    const size_t o_xyz = (size_t)n * 8, o_slots = o_xyz + (size_t)n * 24, o_cnt = o_slots + slots.size() * 4, up = o_cnt + 4;
-    const size_t buckets = lm_bucket_count((size_t)n);
-    rc = reloc_scratch(c, up, 0, 0);
-    if(rc)
-        return rc;
-    rc = lm_scratch(c, buckets, 1);
-    if(rc)
-        return rc;
-    uint8_t* h = r->h_up;
-    std::memcpy(h, landmark_ids, (size_t)n * 8);
-    std::memcpy(h + o_xyz, world_xyz, (size_t)n * 24);
-    std::memcpy(h + o_slots, slots.data(), slots.size() * 4);
-    std::memset(h + o_cnt, 0, 4);
-    hipStream_t s = c->stream;
-    uint8_t* d = r->d_up;
-    LmBucket* table = reinterpret_cast<LmBucket*>(r->d_lm_table.get());
-    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
-    MSLAM_CHK(c, hipMemsetAsync(table, 0xFF, buckets * sizeof(LmBucket), s));
-    {
-        StageScope ts(c, "update_world_insert");
-        hipLaunchKernelGGL(k_lm_insert_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const int64_t*>(d), n, table,
-                           (unsigned long long)(buckets - 1));
-    }
-    {
-        StageScope ts(c, "update_world_write");
-        hipLaunchKernelGGL(k_lm_update_world, dim3((unsigned)std::max((n_max + 255) / 256, 1), (unsigned)slots.size()), dim3(256), 0, s, r->d_lid,
-                           r->d_n, reinterpret_cast<const int32_t*>(d + o_slots), K, table, (unsigned long long)(buckets - 1),
-                           reinterpret_cast<const double*>(d + o_xyz), n, r->d_world, reinterpret_cast<uint32_t*>(d + o_cnt));
-    }
-    MSLAM_CHK(c, hipGetLastError());
-    uint32_t written = 0;
-    MSLAM_CHK(c, hipMemcpyAsync(&written, d + o_cnt, 4, hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    if(n_written)
-        *n_written = (int)written;
-    return MSLAM_HIP_OK;
+    return rewrite_host_list(c, landmark_ids, nullptr, world_xyz, n, "update_world_insert", "update_world_write", n_written);
 }
 
 } // extern "C"

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kPruneChunk) void k_prune_compact(uint8_t* store_de
     __shared__ int s_wave[2][kWaves];
     const PruneSeg seg = segs[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min(max(store_n[seg.slot], 0), K);
+    const int n = entry_count(store_n, seg.slot, K);
     const size_t base = (size_t)seg.slot * K;
     int running = 0; // landmarks kept below this chunk: the same in every thread
     for(int start = 0, chunk = 0; start < n; start += kPruneChunk, ++chunk)
@@ -147,10 +147,10 @@ int mslam_hip_kf_remove_observations(mslam_hip_ctx* c, const int32_t* kf_ids, co
             return fail(c, MSLAM_HIP_E_INVALID, me + ": a landmark id lies outside [0, 2^63)");
         if(last_slot < 0 || kf_ids[p] != last_id)
         {
-            const auto it = r->slot_of.find(kf_ids[p]);
-            if(it == r->slot_of.end())
-                return fail(c, MSLAM_HIP_E_INVALID, me + ": id " + std::to_string(kf_ids[p]) + " is not in the keyframe store");
-            last_id = kf_ids[p], last_slot = it->second;
+            rc = store_slot(c, me, "id", kf_ids[p], &last_slot);
+            if(rc)
+                return rc;
+            last_id = kf_ids[p];
         }
         listed[(size_t)p] = Row{last_slot, landmark_ids[p], p};
         ++first[(size_t)last_slot + 1];

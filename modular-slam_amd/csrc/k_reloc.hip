@@ -269,29 +269,52 @@ int mslam::store_slot_for(mslam_hip_ctx* c, int id, int* slot)
     return MSLAM_HIP_OK;
 }
 
+int mslam::store_slot_missing(mslam_hip_ctx* c, const std::string& me, const char* what, int id)
+{
+    return fail(c, MSLAM_HIP_E_INVALID, me + ": " + what + " " + std::to_string(id) + " is not in the keyframe store");
+}
+
 int64_t mslam::store_next_lid_base(mslam_hip_ctx* c)
 {
     return fresh_lid_base(++c->reloc->serial);
 }
 
-int TrackSlots::resolve(mslam_hip_ctx* c, const char* who, int ref_id, const int32_t* vote_ids, int n_vote, int new_id_)
+int mslam::lid_list_check(mslam_hip_ctx* c, const std::string& me, int n, bool present, const int64_t* ids, const int64_t* more)
+{
+    if(n < 0 || n > (1 << 24) || (n > 0 && !present))
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
+    for(int i = 0; i < n; ++i)
+        if(ids[i] < 0 || (more && more[i] < 0))
+            return fail(c, MSLAM_HIP_E_INVALID, me + ": a landmark id lies outside [0, 2^63)");
+    return MSLAM_HIP_OK;
+}
+
+LmTable mslam::lm_table_grow(mslam_hip_ctx* c, size_t keys, size_t bytes, size_t offset)
 {
     RelocState* r = c->reloc;
+    const size_t buckets = lm_bucket_count(keys);
+    const hipError_t e = grow(r->d_lm_table, std::max(bytes, offset + buckets * sizeof(LmBucket)), c->stream);
+    if(e != hipSuccess)
+    {
+        c->err = std::string("the landmark-id table: ") + hipGetErrorString(e);
+        return LmTable{nullptr, 0};
+    }
+    return LmTable{reinterpret_cast<LmBucket*>(r->d_lm_table + offset), (unsigned long long)(buckets - 1)};
+}
+
+int TrackSlots::resolve(mslam_hip_ctx* c, const char* who, int ref_id, const int32_t* vote_ids, int n_vote, int new_id_)
+{
     const std::string me = who;
     new_id = new_id_;
-    auto ref = r->slot_of.find(ref_id);
-    if(ref == r->slot_of.end())
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": reference id " + std::to_string(ref_id) + " is not in the keyframe store");
-    ref_slot = ref->second;
+    int rc = store_slot(c, me, "reference id", ref_id, &ref_slot);
     bool collides = new_id >= 0 && new_id == ref_id;
-    for(int k = 0; k < n_vote; ++k)
+    for(int k = 0; !rc && k < n_vote; ++k)
     {
-        auto it = r->slot_of.find(vote_ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, me + ": vote id " + std::to_string(vote_ids[k]) + " is not in the keyframe store");
-        vote_slots[k] = it->second;
+        rc = store_slot(c, me, "vote id", vote_ids[k], &vote_slots[k]);
         collides = collides || (new_id >= 0 && vote_ids[k] == new_id);
     }
+    if(rc)
+        return rc;
     if(collides)
         return fail(c, MSLAM_HIP_E_INVALID, me + ": new_id names the reference keyframe or a keyframe of the vote list");
     return MSLAM_HIP_OK;
@@ -473,9 +496,7 @@ int mslam_hip_kf_remove(mslam_hip_ctx* c, int id)
     auto it = r->slot_of.find(id);
     if(it == r->slot_of.end())
         return fail(c, MSLAM_HIP_E_INVALID, "kf_remove: no such keyframe id");
-    // (work already enqueued on the slot runs before anything a later add enqueues: one stream)
-    r->free_slots.push_back(it->second);
-    r->slot_of.erase(it);
+    store_release(r, id, it->second);
     return MSLAM_HIP_OK;
 }
 
@@ -714,11 +735,10 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     int n_max = 0;
     for(int k = 0; k < n_cand; ++k)
     {
-        auto it = r->slot_of.find(cand_ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, "relocalize: candidate id " + std::to_string(cand_ids[k]) + " is not in the keyframe store");
-        slots[k] = it->second;
-        n_max = std::max(n_max, r->n_upper[(size_t)it->second]);
+        rc = store_slot(c, "relocalize", "candidate id", cand_ids[k], &slots[k]);
+        if(rc)
+            return rc;
+        n_max = std::max(n_max, r->n_upper[(size_t)slots[k]]);
     }
     for(int k = 0; k < n_cand; ++k)
         out[k] = mslam_hip_reloc_candidate{};

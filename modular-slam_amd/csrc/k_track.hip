@@ -169,10 +169,9 @@ int mslam_hip_kf_visible(mslam_hip_ctx* c, const int32_t* ids, int n_ids, const 
     } up{};
     for(int k = 0; k < n_ids; ++k)
     {
-        auto it = r->slot_of.find(ids[k]);
-        if(it == r->slot_of.end())
-            return fail(c, MSLAM_HIP_E_INVALID, "kf_visible: id " + std::to_string(ids[k]) + " is not in the keyframe store");
-        up.slots[k] = it->second;
+        rc = store_slot(c, "kf_visible", "id", ids[k], &up.slots[k]);
+        if(rc)
+            return rc;
     }
     if(n_ids == 0)
         return MSLAM_HIP_OK;

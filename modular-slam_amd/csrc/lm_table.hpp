@@ -1,7 +1,7 @@
-// lm_table.hpp — the open-addressing table on landmark ids that k_localmap.hip (union, covisibility, update_world) and
-// k_fuse.hip (eligibility, id replacement) share: {u64 key, u64 val} buckets, a power of two of them and at least twice the
-// keys that can be inserted, cleared to all-ones (a landmark id is never all-ones: ids are below 2^63), linear probing.  A
-// key is claimed with one compare-and-swap; what the value holds is the caller's.
+// lm_table.hpp — the open-addressing table on landmark ids that k_localmap.hip (union, covisibility, the list rewrite),
+// k_fuse.hip (eligibility) and k_cull.hip (observer counts) share: {u64 key, u64 val} buckets, a power of two of them and at
+// least twice the keys that can be inserted, cleared to all-ones (a landmark id is never all-ones: ids are below 2^63),
+// linear probing.  A key is claimed with one compare-and-swap; what the value holds is the caller's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -28,33 +28,40 @@ __host__ __device__ __forceinline__ unsigned long long lm_hash(unsigned long lon
     return x;
 }
 
+// a table as kernels take it, by value: its buckets and their number less one
+struct LmTable
+{
+    LmBucket* b;
+    unsigned long long mask;
+};
+
 // the bucket of `key`, claimed if no thread has claimed one for it yet.  The table has at least twice as many buckets as
 // keys are ever inserted, so the walk ends; it is bounded by the table's size all the same (-1: cannot happen).
-__device__ __forceinline__ long long lm_claim(LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
+__device__ __forceinline__ long long lm_claim(LmTable t, unsigned long long key)
 {
-    unsigned long long h = lm_hash(key) & mask;
-    for(unsigned long long step = 0; step <= mask; ++step)
+    unsigned long long h = lm_hash(key) & t.mask;
+    for(unsigned long long step = 0; step <= t.mask; ++step)
     {
-        const unsigned long long prev = atomicCAS(&table[h].key, kLmEmpty, key);
+        const unsigned long long prev = atomicCAS(&t.b[h].key, kLmEmpty, key);
         if(prev == kLmEmpty || prev == key)
             return (long long)h;
-        h = (h + 1) & mask;
+        h = (h + 1) & t.mask;
     }
     return -1;
 }
 
 // the bucket of `key`, -1 when the table does not hold it (read-only: every insert is in an earlier launch)
-__device__ __forceinline__ long long lm_find(const LmBucket* __restrict__ table, unsigned long long mask, unsigned long long key)
+__device__ __forceinline__ long long lm_find(LmTable t, unsigned long long key)
 {
-    unsigned long long h = lm_hash(key) & mask;
-    for(unsigned long long step = 0; step <= mask; ++step)
+    unsigned long long h = lm_hash(key) & t.mask;
+    for(unsigned long long step = 0; step <= t.mask; ++step)
     {
-        const unsigned long long k = table[h].key;
+        const unsigned long long k = t.b[h].key;
         if(k == key)
             return (long long)h;
         if(k == kLmEmpty)
             return -1;
-        h = (h + 1) & mask;
+        h = (h + 1) & t.mask;
     }
     return -1;
 }
@@ -65,6 +72,11 @@ inline size_t lm_bucket_count(size_t keys)
     while(b < 2 * keys)
         b <<= 1;
     return b;
+}
+
+inline size_t lm_bytes(LmTable t) // what a clear of the table covers
+{
+    return (size_t)(t.mask + 1) * sizeof(LmBucket);
 }
 
 } // namespace mslam

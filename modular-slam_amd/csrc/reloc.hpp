@@ -1,9 +1,11 @@
 // reloc.hpp — what the files on the keyframe store share (k_reloc.hip: the store and mslam_hip_relocalize; k_track.hip,
-// k_track_window.hip, k_localmap.hip): the store's state and scratch, the match-to-PnP sequence over R rows that relocalize
-// (one query, R entries) and a tracking window (R frames, one entry) both enqueue, relocalize's body with two places where a
-// caller can enqueue work of its own, and the launchers of k_backproject.
+// k_track_window.hip, k_localmap.hip, k_fuse.hip, k_cull.hip, k_prune.hip): the store's state and scratch, the lookup of an
+// id's slot, the landmark-id table in device scratch, the list rewrite of kf_update_world / kf_replace_ids / kf_fuse, the
+// match-to-PnP sequence over R rows that relocalize (one query, R entries) and a tracking window (R frames, one entry) both
+// enqueue, relocalize's body with two places where a caller can enqueue work of its own, and the launchers of k_backproject.
 #pragma once
 #include "context.hpp"
+#include "lm_table.hpp"
 
 #include <string>
 #include <unordered_map>
@@ -45,6 +47,12 @@ __device__ __forceinline__ void copy_desc(const uint8_t* __restrict__ src, uint8
     d[1] = s[1];
 }
 
+// an entry's landmark count as every kernel on the store reads it: whatever the word holds, no position lies outside the slot
+__device__ __forceinline__ int entry_count(const int32_t* __restrict__ store_n, int slot, int K)
+{
+    return min(max(store_n[slot], 0), K);
+}
+
 struct RelocState
 {
     // ---- keyframe store: slot s holds up to K landmarks at desc + s * K * 32, world + s * K * 3, count n[s]
@@ -63,13 +71,16 @@ struct RelocState
     DevBuf<uint8_t> d_up;                          // as large as h_up
     DevBuf<uint8_t> d_arena;                       // every device array of one call
     PinnedBuf<uint8_t> h_res;                      // mapped: what the host reads after the synchronisation
-    // ---- scratch of mslam_hip_kf_union / mslam_hip_kf_covisible (k_localmap.hip), grown on demand: the hash table
-    // ({u64 key, u64 val} buckets), the per-block arrays [win masks | counts | offsets], and the mapped result
-    // [needed count, pad | covisibility counts 64 x i32]
-    DevBuf<uint8_t> d_lm_table, d_lm_blocks;
+    // ---- the landmark-id table ({u64 key, u64 val} buckets, lm_table.hpp) of every call that builds one, grown on demand by
+    // lm_table_grow: union, covisibility and the list rewrite (k_localmap.hip), the observer counts (k_cull.hip), and the
+    // fusion search (k_fuse.hip), which carves [keep table | drop table | replacement table | best] from the one block
+    DevBuf<uint8_t> d_lm_table;
+    // ---- scratch of mslam_hip_kf_union / mslam_hip_kf_covisible (k_localmap.hip), grown on demand: the per-block arrays
+    // [win masks | counts | offsets], and the mapped result [needed count, pad | covisibility counts 64 x i32]
+    DevBuf<uint8_t> d_lm_blocks;
     PinnedBuf<uint8_t> h_lm;
-    // ---- scratch of keyframe culling (k_cull.hip), next to d_lm_table and grown on demand: [observer counts, one u32 per
-    // bucket | first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32]
+    // ---- scratch of keyframe culling (k_cull.hip), grown on demand: [observer counts, one u32 per table bucket |
+    // first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32]
     DevBuf<uint8_t> d_cull;
 };
 
@@ -176,6 +187,54 @@ int reloc_enter(mslam_hip_ctx* c);
 int reloc_scratch(mslam_hip_ctx* c, size_t up, size_t arena, size_t res);
 int store_reserve(mslam_hip_ctx* c, int want);
 int store_slot_for(mslam_hip_ctx* c, int id, int* slot);
+// *slot = the slot of entry `id`, or the failure "<me>: <what> <id> is not in the keyframe store".  The lookup is inline
+// (kf_remove_observations asks once per row), the failure is not.
+int store_slot_missing(mslam_hip_ctx* c, const std::string& me, const char* what, int id);
+inline int store_slot(mslam_hip_ctx* c, const std::string& me, const char* what, int id, int* slot)
+{
+    const auto it = c->reloc->slot_of.find(id);
+    if(it == c->reloc->slot_of.end())
+        return store_slot_missing(c, me, what, id);
+    *slot = it->second;
+    return MSLAM_HIP_OK;
+}
+// entry `id` leaves the store: its slot goes to the free list, the serial stays.  (Work already enqueued on the slot runs
+// before anything a later add enqueues: one stream.)
+inline void store_release(RelocState* r, int id, int slot)
+{
+    r->free_slots.push_back(slot);
+    r->slot_of.erase(id);
+}
+// a caller's list of n landmark ids (and a second list of n, or nullptr): 0 .. 2^24 of them, `present` = the caller's own
+// test of its pointers, every id in [0, 2^63)
+int lid_list_check(mslam_hip_ctx* c, const std::string& me, int n, bool present, const int64_t* ids, const int64_t* more = nullptr);
+// The table of `keys` keys that begins `offset` bytes into d_lm_table, which holds at least `bytes` bytes afterwards
+// (bytes = 0: what this table needs; growing waits for the stream first).  b == nullptr: the allocation failed and
+// c->err says why.
+LmTable lm_table_grow(mslam_hip_ctx* c, size_t keys, size_t bytes = 0, size_t offset = 0);
+
+// The list rewrite (k_localmap.hip): every landmark of the listed live slots whose id is l.from[p] takes l.to[p] (nullptr:
+// the ids stay) and the point l.xyz + 3 p (nullptr: the points stay); of a `from` listed twice the later place wins.  All
+// device pointers.  The launches cover n places; with n_dev, *n_dev of them count when that fits `cap`, none otherwise.
+struct ReplaceList
+{
+    const int64_t *from, *to;
+    const double* xyz;
+    const int32_t* n_dev;
+    int n, cap;
+};
+// the live slots in ascending order and the largest count among them
+int live_slots(const RelocState* r, std::vector<int32_t>* slots);
+// enqueues the two launches under the caller's stage names: the table of l.from in `t` (cleared beforehand), then one thread
+// per (slot of d_slots, position below n_max); *d_count, zero beforehand, counts the landmarks that matched
+int rewrite_enqueue(mslam_hip_ctx* c, const ReplaceList& l, LmTable t, const int32_t* d_slots, int n_slots, int n_max, uint32_t* d_count,
+                    const char* stage_table, const char* stage_write);
+// the count comes back: the call's one synchronisation
+int rewrite_count(mslam_hip_ctx* c, const uint32_t* d_count, int* n_out);
+// kf_update_world and kf_replace_ids after their own checks: a host list of n places (`to`, `xyz`: or nullptr) is uploaded
+// with the live slots, rewritten and counted
+int rewrite_host_list(mslam_hip_ctx* c, const int64_t* from, const int64_t* to, const double* xyz, int n, const char* stage_table,
+                      const char* stage_write, int* n_out);
 int64_t store_next_lid_base(mslam_hip_ctx* c); // advances the creation serial: call once per entry made, after store_slot_for
 
 // The store slots of one tracking call (mslam_hip_track, mslam_hip_track_window[_dev]).  resolve() looks the reference and the vote list up and rejects a
