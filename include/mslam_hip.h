@@ -844,6 +844,69 @@ int mslam_hip_kf_cull(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const i
                       int min_landmarks, uint8_t* culled /* n_cand */, int32_t* n_landmarks /* n_cand, may be NULL */,
                       int32_t* n_redundant /* n_cand, may be NULL */, int* n_culled /* may be NULL */);
 
+/* ---- landmark culling: the landmarks of the candidate entries that too few listed entries observe --------------------
+ * AN EXTENSION, NOT A RESTATEMENT: the reference has the removal primitive (BasicMap::removeLandmark, basic_map.cpp:133) and
+ * no step that calls it.  The model is ORB-SLAM's MapPointCulling: some keyframes
+ * after a landmark was created, it goes when too few keyframes observe it.  For RGB-D the published threshold
+ * (Observations() <= 3, two counts per depth observation) means "fewer than two keyframes": min_observers = 2.
+ *
+ *   the map      ids[0..n_ids), obs(l), the limits 1 <= n_ids <= MSLAM_HIP_CULL_MAX_ENTRIES and MSLAM_HIP_CULL_MAX_LANDMARKS:
+ *                exactly as in the keyframe-culling block above.  The listed entries are the observers and the ONLY entries
+ *                changed: an entry that is not listed (a union under a reserved id, say) is untouched byte for byte and does
+ *                not count as an observer.  A union built earlier keeps its copy until it is rebuilt, as after
+ *                mslam_hip_kf_remove_observations.
+ *   judged       cand[0..n_cand) are distinct, each one of `ids`, 0 <= n_cand <= n_ids.  A landmark id is judged iff at least
+ *                one candidate entry holds it.  n_cand = 0 is OK: nothing is found.  The rule reads no bits of the id: fresh,
+ *                inherited and caller-supplied ids are judged alike.
+ *   culled       l is culled iff it is judged and obs(l) < min_observers, min_observers in 1..65535 (1 culls nothing).  The
+ *                counts are taken once, before anything is removed: there is no greedy order, and removing a landmark
+ *                changes no other landmark's count.
+ *   the list     the culled ids in ascending order in landmark_ids[0..*n_found), observers[p] = obs(landmark_ids[p])
+ *                (`observers` may be NULL).  With landmark_ids == NULL no list is produced, `capacity` is not consulted and
+ *                only *n_found comes back.  Otherwise, when *n_found > capacity, the call returns MSLAM_HIP_E_CAPACITY with
+ *                *n_found = the count needed and nothing is copied; mslam_hip_kf_cull_landmarks removes nothing in that
+ *                case either (the decision is taken on the device from the device count, as mslam_hip_kf_fuse takes it).
+ *
+ * mslam_hip_kf_cull_landmarks_search changes nothing in the store.
+ *
+ * mslam_hip_kf_remove_landmarks removes every position of every listed entry whose landmark id is one of
+ * landmark_ids[0..n), 0 <= n <= 2^24, ids in [0, 2^63):
+ *   survivors         keep their relative order inside the entry; descriptor, world point and landmark id move bit for bit;
+ *                     an entry emptied this way stays an entry with 0 landmarks (mslam_hip_kf_remove_observations'
+ *                     guarantees).  What lies behind an entry's new count is unspecified.
+ *   removed[p]        (may be NULL) the store positions over the listed entries that held landmark_ids[p] before the call.
+ *                     An id listed twice reports the same number twice; an id nobody holds reports 0.
+ *   entry_removed[k]  (may be NULL) the positions entry ids[k] lost;  *n_removed (may be NULL) = their sum.
+ *   sizes             after the call the host knows the exact size of every listed entry (an entry lifted on the device
+ *                     counts as max_keypoints no longer).
+ *
+ * mslam_hip_kf_cull_landmarks is the search followed by the removal of what it found, with entry_removed / *n_removed as
+ * above; the list never has to leave the device in between and there is one synchronisation.
+ *
+ * Errors: MSLAM_HIP_E_INVALID and MSLAM_HIP_E_CAPACITY as in the keyframe-culling block (the listed ids, the candidates,
+ * min_observers), and MSLAM_HIP_E_INVALID for a NULL n_found, a negative capacity with a list, n outside 0..2^24, a NULL
+ * id list with n > 0, a landmark id outside [0, 2^63).  On every error the store is untouched and the outputs are zeroed
+ * (*n_found excepted when the list does not fit).
+ * One upload (the listed and candidate slots, or the id list and the slots), the clears, two launches per 64 listed
+ * entries for the counts (the search), at most three more launches (flags, gather, compaction with one workgroup per
+ * listed entry; or table, compaction, per-row counts), one synchronisation.  Every output is a function of the store and
+ * the arguments alone: two runs give equal bytes (the device gathers in arbitrary order; the host sorts the list by id).
+ *   threshold    SAME as MapPointCulling's observer threshold for RGB-D at min_observers = 2;
+ *   ratio        DEVIATES: the found / visible ratio test is absent, because the store keeps no such counters;
+ *   recent       DEVIATES: MapPointCulling judges the landmarks created in the last keyframes; here "recent" is whatever
+ *                the caller lists as `cand`;
+ *   inherited    DEVIATES: an inherited landmark of a candidate is judged as well (the rule reads no creation time). */
+int mslam_hip_kf_remove_landmarks(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int64_t* landmark_ids, int n,
+                                  int32_t* removed /* n, may be NULL */, int32_t* entry_removed /* n_ids, may be NULL */,
+                                  int* n_removed /* may be NULL */);
+int mslam_hip_kf_cull_landmarks_search(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int32_t* cand, int n_cand,
+                                       int min_observers, int64_t* landmark_ids /* capacity, may be NULL */,
+                                       int32_t* observers /* capacity, may be NULL */, int capacity, int* n_found);
+int mslam_hip_kf_cull_landmarks(mslam_hip_ctx* ctx, const int32_t* ids, int n_ids, const int32_t* cand, int n_cand, int min_observers,
+                                int64_t* landmark_ids /* capacity, may be NULL */, int32_t* observers /* capacity, may be NULL */,
+                                int capacity, int* n_found, int32_t* entry_removed /* n_ids, may be NULL */,
+                                int* n_removed /* may be NULL */);
+
 /* One query frame against n_cand <= 64 stored keyframes (64 = the BoW query's own limit), all on the device, one host
  * synchronisation at the end.  Query: desc = n x 32, xy = n x 2 f32 keypoint coordinates, valid = n bytes or NULL (all
  * valid; a mask is track()'s depth filter, :317-334).  Per candidate c = cand_ids[k]:

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_fuse_search", "mslam_hip_kf_replace_ids", "mslam_hip_kf_fuse",
     "mslam_hip_kf_remove_observations",
     "mslam_hip_kf_observers", "mslam_hip_kf_cull_search", "mslam_hip_kf_cull",
+    "mslam_hip_kf_remove_landmarks", "mslam_hip_kf_cull_landmarks_search", "mslam_hip_kf_cull_landmarks",
 ]
 
 
@@ -203,6 +204,7 @@ class Context:
             raise MslamHipError(rc, (lib().mslam_hip_last_error(None) or b"").decode())
         self._h = h
         self.L = lib()
+        self._lm_cull_capacity = 1024    # rows of kf_cull_landmarks[_search]'s list: grows to what a call reported
 
     def close(self):
         if getattr(self, "_h", None):
@@ -656,6 +658,47 @@ class Context:
     def kf_cull(self, ids, cand, min_observers=3, ratio=0.9, min_landmarks=1):
         """kf_cull_search, then the culled entries leave the store as kf_remove would remove them -> the same dict"""
         return self._cull_call(self.L.mslam_hip_kf_cull, ids, cand, min_observers, ratio, min_landmarks)
+
+    # ---- landmark culling (an extension: the reference has no such step; the model is ORB-SLAM's MapPointCulling) ----
+    def kf_remove_landmarks(self, ids, landmark_ids):
+        """every position of every listed store entry `ids` (1..4096, distinct) whose landmark id is listed is removed;
+        the survivors keep their order and the entries' counts drop; entries that are not listed are untouched
+        -> dict(removed = [n] i32: the store positions that held landmark_ids[p], entry_removed = [n_ids] i32: the
+        positions entry ids[k] lost, n_removed = their sum)"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        l = np.ascontiguousarray(landmark_ids, np.int64).reshape(-1)
+        removed, lost, n = np.zeros(max(len(l), 1), np.int32), np.zeros(max(len(ids), 1), np.int32), C.c_int(0)
+        self._chk(self.L.mslam_hip_kf_remove_landmarks(self._h, _p(ids), len(ids), _p(l), len(l), _p(removed), _p(lost), C.byref(n)))
+        return dict(removed=removed[:len(l)].copy(), entry_removed=lost[:len(ids)].copy(), n_removed=n.value)
+
+    def _lm_cull_call(self, entry, ids, cand, min_observers, tail):
+        """the search or the fused call with the wrapper's growing list capacity: on E_CAPACITY nothing has changed, so the
+        call is repeated once with the count it reported"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        cand = np.ascontiguousarray(cand, np.int32).reshape(-1)
+        for attempt in range(2):
+            cap = self._lm_cull_capacity
+            l, o, n = np.zeros(cap, np.int64), np.zeros(cap, np.int32), C.c_int(0)
+            rc = entry(self._h, _p(ids), len(ids), _p(cand), len(cand), int(min_observers), _p(l), _p(o), cap, C.byref(n), *tail)
+            if rc != E_CAPACITY or attempt or n.value <= cap:
+                break
+            self._lm_cull_capacity = n.value
+        self._chk(rc)
+        return dict(landmark_ids=l[:n.value].copy(), observers=o[:n.value].copy())
+
+    def kf_cull_landmarks_search(self, ids, cand, min_observers=2):
+        """the landmark ids that at least one candidate entry `cand` (distinct, each one of the listed entries `ids`) holds
+        and that fewer than min_observers listed entries hold -> dict(landmark_ids [n] i64, ascending, observers [n] i32).
+        Changes nothing."""
+        return self._lm_cull_call(self.L.mslam_hip_kf_cull_landmarks_search, ids, cand, min_observers, ())
+
+    def kf_cull_landmarks(self, ids, cand, min_observers=2):
+        """kf_cull_landmarks_search, then the found landmarks leave every listed entry as kf_remove_landmarks removes them,
+        in one call with one synchronisation -> the search's dict plus entry_removed [n_ids] i32 and n_removed"""
+        lost, nr = np.zeros(max(np.size(ids), 1), np.int32), C.c_int(0)
+        out = self._lm_cull_call(self.L.mslam_hip_kf_cull_landmarks, ids, cand, min_observers, (_p(lost), C.byref(nr)))
+        out.update(entry_removed=lost[:np.size(ids)].copy(), n_removed=nr.value)
+        return out
 
     # ---- the local map (basic_map.cpp:141-237, rgbd_feature_frontend.cpp:57-80, :256-277) ---------
     def kf_covisible(self, id, ids):
@@ -1260,6 +1303,7 @@ class HipBackend:
     can drag its landmark until the landmark's good observations are flagged too, and the landmark then goes with them.
     The backend never touches the keyframe store: its caller does (Context.kf_remove_observations with pruned["pairs"]).
     remove_keyframe() is the backend's side of keyframe culling (Context.kf_cull): every keyframe but the first can leave.
+    remove_landmarks() is the backend's side of landmark culling (Context.kf_cull_landmarks): the ids leave every keyframe.
     global_solver = True: global_ba() goes through
     Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes.
     close_loop() is the body of the reference's empty closeLoop (rgbd_feature_frontend.cpp:577-580): a pose graph over every
@@ -1394,6 +1438,25 @@ class HipBackend:
             elif self.anchor.get(l) == id:
                 self.anchor[l] = who[0]
         return dict(n_observations=len(lids), orphans=orphans)
+
+    def remove_landmarks(self, lids):
+        """landmark culling's bookkeeping (Context.kf_cull_landmarks): the listed landmark ids leave every keyframe's
+        observations, at every position, and leave `landmarks` and `anchor`; an id the backend does not hold is ignored
+        -> dict(n_observations = the observations dropped, n_landmarks = the landmarks that left)"""
+        gone = set(int(l) for l in np.asarray(lids, np.int64).reshape(-1).tolist())
+        n_obs = 0
+        if gone:
+            for kf in sorted(self.obs):
+                ids, cam = self.obs[kf]
+                hit = np.array([l in gone for l in ids.tolist()], bool).reshape(-1)
+                if hit.any():
+                    n_obs += int(np.count_nonzero(hit))
+                    self.obs[kf] = (ids[~hit].copy(), cam[~hit].copy())
+        n_lm = 0
+        for l in gone:
+            n_lm += self.landmarks.pop(l, None) is not None
+            self.anchor.pop(l, None)
+        return dict(n_observations=n_obs, n_landmarks=n_lm)
 
     def _solve_pruned(self, kf_ids, blocked, prune):
         """_solve; with prune, the result's outlier observations are removed and, when any were, one more solve from the
@@ -1595,8 +1658,21 @@ class HipKeyframeTracker:
     self._bow_entry) and the graph; remove_graph_node keeps the graph connected, which the pose graph needs: every former
     neighbour with no path left to the smallest former neighbour gets an edge to it.  The local map is rebuilt.
     self.cull_results gains one dict per call that had candidates: keyframe, listed, candidates, culled, n_landmarks,
-    n_redundant, bridges.  Off by default: nothing is removed.  STILL OUT: culling landmarks by age or by observer count
-    (Context.kf_observers is the primitive for it), and ORB-SLAM's scale condition (the store keeps no octave)."""
+    n_redundant, bridges.  Off by default: nothing is removed.  STILL OUT: ORB-SLAM's scale condition (the store keeps no
+    octave).
+
+    lm_cull = True (needs no other option; an extension, the reference has no such step; the model is ORB-SLAM's
+    MapPointCulling, run before KeyFrameCulling as there): at every keyframe insertion, on both paths, after the covisibility
+    edges, local BA, pruning and the loop closure and before kf_cull's step.  Part B of every new keyframe gives a fresh id
+    to each keypoint it did not match, and most of those are never matched again; nothing else removes them.  The new id
+    joins a pending list; the keyframes inserted at least lm_cull_age insertions ago leave it, and those of them still in
+    self.ids are the candidates of one Context.kf_cull_landmarks with self.ids as the map (more than 4096 keyframes:
+    MslamHipError(E_CAPACITY) before the context is touched; the reserved ids are never listed, so a union neither counts
+    as an observer nor changes): a landmark that a candidate holds (fresh or inherited) and that fewer than
+    lm_cull_min_observers keyframes hold leaves every keyframe's entry.  With a backend, HipBackend.remove_landmarks
+    follows.  The local map is rebuilt when anything was removed.  self.lm_cull_results gains one dict per call made:
+    keyframe, listed, candidates, landmark_ids, n_removed, n_backend.  Off by default: nothing is removed.  STILL OUT:
+    MapPointCulling's found / visible ratio (the store keeps no such counters)."""
 
     LOCAL_MAP_ID = 0x7fffffff
     FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
@@ -1607,8 +1683,13 @@ class HipKeyframeTracker:
                  reloc_min_inliers=60, local_map_depth=None, guided_radius=None, guided_max_distance=256, local_ba=False,
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
-                 loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9):
+                 loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
+                 lm_cull_min_observers=2, lm_cull_age=2):
         self.ctx = ctx
+        self.lm_cull, self.lm_cull_min_observers, self.lm_cull_age = bool(lm_cull), int(lm_cull_min_observers), int(lm_cull_age)
+        self.lm_cull_results = []
+        self._lm_pending = []        # (keyframe id, the insertion count at which it was inserted): not judged yet
+        self._lm_inserted = 0        # keyframe insertions seen by _lm_cull
         if kf_cull and not local_ba:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: kf_cull needs local_ba (the backend holds the observations, "
                                            "the graph the neighbours)")
@@ -1674,6 +1755,8 @@ class HipKeyframeTracker:
                          keyframe=0, relocalized=False, step=None)
             if self.loop_closure:
                 first["loop"] = self._close_loops(0, desc, xy, seed)
+            if self.lm_cull:
+                self._lm_cull(0)   # (the first insertion: keyframe 0 joins the pending list, nothing is due yet)
             return first
         vote = self.ids[-64:]
         new_id = self.ids[-1] + 1
@@ -1708,8 +1791,10 @@ class HipKeyframeTracker:
                         self._local_ba(new_id, res, xy, depth)
                     if self.loop_closure:
                         out["loop"] = self._close_loops(new_id, desc, xy, seed)
-                    if self.kf_cull:
-                        self._cull(new_id)
+                if self.lm_cull:
+                    self._lm_cull(new_id)
+                if self.kf_cull:
+                    self._cull(new_id)
         else:
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
@@ -1773,6 +1858,8 @@ class HipKeyframeTracker:
                         if self.loop_closure:
                             self._extent = np.asarray(depths[i + s]).shape[1::-1]
                             o["loop"] = self._close_loops(new_id, descs[i + s], xys[i + s], seed + s)
+                        if self.lm_cull:
+                            self._lm_cull(new_id)
                         if self.kf_cull:
                             self._cull(new_id)
                 else:
@@ -1824,6 +1911,28 @@ class HipKeyframeTracker:
         pruned["n_removed"] = self.ctx.kf_remove_observations([k for k, _ in pairs], [l for _, l in pairs])["n_removed"] if pairs else 0
         if pairs:
             self._local_map_of = None
+
+    def _lm_cull(self, new_id):
+        """lm_cull: the new keyframe joins the pending list; the keyframes inserted at least lm_cull_age insertions ago
+        leave it, and those of them still in self.ids are the candidates of one Context.kf_cull_landmarks with self.ids
+        as the map; the backend forgets the culled landmarks.  A call made is recorded in self.lm_cull_results"""
+        self._lm_inserted += 1
+        self._lm_pending.append((new_id, self._lm_inserted))
+        due = [k for k, at in self._lm_pending if self._lm_inserted - at >= self.lm_cull_age]
+        self._lm_pending = [(k, at) for k, at in self._lm_pending if self._lm_inserted - at < self.lm_cull_age]
+        held = set(self.ids)
+        cands = [k for k in due if k in held]
+        if not cands:
+            return
+        if len(self.ids) > CULL_MAX_ENTRIES:
+            raise MslamHipError(E_CAPACITY, "lm_cull: %d keyframes, at most %d per call" % (len(self.ids), CULL_MAX_ENTRIES))
+        listed = list(self.ids)
+        res = self.ctx.kf_cull_landmarks(listed, cands, self.lm_cull_min_observers)
+        n_backend = self.backend.remove_landmarks(res["landmark_ids"])["n_observations"] if self.backend is not None else 0
+        if res["n_removed"] > 0:
+            self._local_map_of = None
+        self.lm_cull_results.append(dict(keyframe=new_id, listed=listed, candidates=cands, landmark_ids=res["landmark_ids"],
+                                         n_removed=res["n_removed"], n_backend=n_backend))
 
     def cull_candidates(self, new_id):
         """the keyframes _cull may remove when new_id was inserted: HipBackend.neighbours(new_id, graph, 1), ascending,

@@ -12,7 +12,8 @@
 //                  one bit once and the cleared table needs no second pass to become "no bit set";
 //   k_cull_count   one thread per bucket: the count grows by the popcount of the cleared bits and the value goes back to
 //                  all-ones for the next chunk.  Integer sums of a fixed set of bits: the order does not matter.
-// Then
+// (cull_resolve, cull_cand_slots, cull_scratch and cull_count_enqueue are declared in reloc.hpp: landmark culling,
+// k_lmcull.hip, starts with the same counts.)  Then
 //   k_cull_lookup  (observers) one thread per asked id: the count of its bucket, 0 without one;
 //   k_cull_greedy  (search) ONE workgroup of 1024 threads walks the candidates in order.  Per candidate, three phases with a
 //                  workgroup barrier between them: (A) every position finds its bucket and lowers the bucket's stamp to
@@ -167,17 +168,8 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_greedy(const int64_t* __r
 
 using namespace mslam;
 
-namespace
-{
-// the listed entries of one call: their slots and the sum of the sizes the host knows (n_upper)
-struct CullMap
-{
-    std::vector<int32_t> slots;
-    size_t keys = 0;
-};
-
-// ids[0, n_ids): 1..MSLAM_HIP_CULL_MAX_ENTRIES distinct ids of the store
-int cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, int n_ids, CullMap* m, std::unordered_map<int, int>* pos_of)
+// ---- the observer counts (declared in reloc.hpp: k_lmcull.hip starts with them too)
+int mslam::cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, int n_ids, CullMap* m, std::unordered_map<int, int>* pos_of)
 {
     RelocState* r = c->reloc;
     if(!ids || n_ids < 1 || n_ids > MSLAM_HIP_CULL_MAX_ENTRIES)
@@ -199,15 +191,25 @@ int cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, in
     return MSLAM_HIP_OK;
 }
 
-// where the count arrays lie in d_cull: [counts buckets x u32 | stamps buckets x u32 | buckets of a candidate's positions K x u32]
-struct CullDev
+int mslam::cull_cand_slots(mslam_hip_ctx* c, const std::string& me, const CullMap& m, const std::unordered_map<int, int>& pos_of,
+                           const int32_t* cand, int n_cand, std::vector<int32_t>* cand_slots)
 {
-    LmTable table;
-    uint32_t *counts, *stamp, *bkt;
-    size_t buckets;
-};
+    cand_slots->resize((size_t)n_cand);
+    std::vector<uint8_t> seen(m.slots.size(), 0);
+    for(int k = 0; k < n_cand; ++k)
+    {
+        const auto it = pos_of.find(cand[k]);
+        if(it == pos_of.end())
+            return fail(c, MSLAM_HIP_E_INVALID, me + ": candidate " + std::to_string(cand[k]) + " is not one of the listed ids");
+        if(seen[(size_t)it->second])
+            return fail(c, MSLAM_HIP_E_INVALID, me + ": candidate " + std::to_string(cand[k]) + " is listed twice");
+        seen[(size_t)it->second] = 1;
+        (*cand_slots)[(size_t)k] = m.slots[(size_t)it->second];
+    }
+    return MSLAM_HIP_OK;
+}
 
-int cull_scratch(mslam_hip_ctx* c, size_t keys, CullDev* d)
+int mslam::cull_scratch(mslam_hip_ctx* c, size_t keys, CullDev* d)
 {
     RelocState* r = c->reloc;
     d->table = lm_table_grow(c, keys);
@@ -221,8 +223,7 @@ int cull_scratch(mslam_hip_ctx* c, size_t keys, CullDev* d)
     return MSLAM_HIP_OK;
 }
 
-// the clears and the 2 x ceil(n_ids / 64) launches that leave the observer count of every bucket; d_slots: the uploaded list
-int cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slots, const CullDev& d)
+int mslam::cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slots, const CullDev& d)
 {
     RelocState* r = c->reloc;
     hipStream_t s = c->stream;
@@ -248,6 +249,8 @@ int cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slot
     return MSLAM_HIP_OK;
 }
 
+namespace
+{
 int cull_run(mslam_hip_ctx* c, const char* who, bool remove, const int32_t* ids, int n_ids, const int32_t* cand, int n_cand,
              int min_observers, double ratio, int min_landmarks, uint8_t* culled, int32_t* n_landmarks, int32_t* n_redundant,
              int* n_culled)
@@ -277,20 +280,10 @@ int cull_run(mslam_hip_ctx* c, const char* who, bool remove, const int32_t* ids,
     if(min_observers < 1 || min_observers > 65535 || !(ratio >= 0.0 && ratio <= 1.0) || min_landmarks < 1)
         return fail(c, MSLAM_HIP_E_INVALID, me + ": min_observers in 1..65535, ratio in [0, 1], min_landmarks >= 1");
     RelocState* r = c->reloc;
-    std::vector<int32_t> cand_slots((size_t)n_cand);
-    {
-        std::vector<uint8_t> seen((size_t)n_ids, 0);
-        for(int k = 0; k < n_cand; ++k)
-        {
-            const auto it = pos_of.find(cand[k]);
-            if(it == pos_of.end())
-                return fail(c, MSLAM_HIP_E_INVALID, me + ": candidate " + std::to_string(cand[k]) + " is not one of the listed ids");
-            if(seen[(size_t)it->second])
-                return fail(c, MSLAM_HIP_E_INVALID, me + ": candidate " + std::to_string(cand[k]) + " is listed twice");
-            seen[(size_t)it->second] = 1;
-            cand_slots[(size_t)k] = m.slots[(size_t)it->second];
-        }
-    }
+    std::vector<int32_t> cand_slots;
+    rc = cull_cand_slots(c, me, m, pos_of, cand, n_cand, &cand_slots);
+    if(rc)
+        return rc;
     if(n_cand == 0)
         return MSLAM_HIP_OK;
     // one upload: [listed slots | candidate slots]; the mapped result: [done, pad x 3 | CullRes x n_cand]

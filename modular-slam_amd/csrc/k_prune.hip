@@ -7,14 +7,16 @@
 //
 //   k_prune_compact  one workgroup per affected entry.  The host sorts and de-duplicates the (slot, landmark id) rows, so
 //                    an entry's rows are one ascending segment [begin, end) of the uploaded id list.  The workgroup walks
-//                    its entry in chunks of kPruneChunk positions: a thread loads its landmark (id, descriptor, world
-//                    point: 8 + 32 + 24 bytes) into registers, binary-searches the id in the segment, and a workgroup scan
-//                    of the keep flags gives the landmark's destination.  The scan's barrier separates the chunk's loads
-//                    from its stores; a destination never lies above its source and a chunk's stores end below the next
-//                    chunk's loads, so the compaction needs no second buffer.  A hit is an integer atomicAdd on its row's
-//                    count: the value does not depend on the order.  Thread 0 leaves the new count.
+//                    its entry in chunks of kPruneChunk positions (compact_entry, compact.hpp, which k_lmcull.hip shares):
+//                    a thread loads its landmark (id, descriptor, world point: 8 + 32 + 24 bytes) into registers,
+//                    binary-searches the id in the segment, and a workgroup scan of the keep flags gives the landmark's
+//                    destination.  The scan's barrier separates the chunk's loads from its stores; a destination never
+//                    lies above its source and a chunk's stores end below the next chunk's loads, so the compaction needs
+//                    no second buffer.  A hit is an integer atomicAdd on its row's count: the value does not depend on
+//                    the order.  Thread 0 leaves the new count.
 //
 // No workgroup reads or writes another workgroup's entry, and the row counts are the only words two threads share.
+#include "compact.hpp"
 #include "reloc.hpp"
 
 #include <algorithm>
@@ -25,7 +27,7 @@
 namespace mslam
 {
 
-constexpr int kPruneChunk = 256; // positions per chunk = threads per workgroup (tests/prune_ref.py: T)
+constexpr int kPruneChunk = kCompactChunk; // positions per chunk = threads per workgroup (tests/prune_ref.py: T)
 
 struct PruneSeg // one affected entry: its slot and its rows [begin, end) of the distinct list
 {
@@ -53,62 +55,18 @@ __global__ __launch_bounds__(kPruneChunk) void k_prune_compact(uint8_t* store_de
                                                                const int64_t* __restrict__ row_lid, uint32_t* __restrict__ row_hits,
                                                                int32_t* __restrict__ new_n)
 {
-    constexpr int kWaves = kPruneChunk / 64;
-    __shared__ int s_wave[2][kWaves];
     const PruneSeg seg = segs[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = entry_count(store_n, seg.slot, K);
-    const size_t base = (size_t)seg.slot * K;
-    int running = 0; // landmarks kept below this chunk: the same in every thread
-    for(int start = 0, chunk = 0; start < n; start += kPruneChunk, ++chunk)
+    const int kept = compact_entry(store_desc, store_world, store_lid, (size_t)seg.slot * K, n, [&](int64_t lid) {
+        const int row = prune_find(row_lid, seg.begin, seg.end, lid);
+        if(row >= 0)
+            atomicAdd(&row_hits[row], 1u);
+        return row >= 0;
+    });
+    if(threadIdx.x == 0)
     {
-        const int i = start + tid;
-        const bool live = i < n;
-        bool keep = false;
-        int64_t lid = 0;
-        uint4 d0{}, d1{};
-        double w0 = 0.0, w1 = 0.0, w2 = 0.0;
-        if(live)
-        {
-            const size_t at = base + i;
-            lid = store_lid[at];
-            const uint4* d = reinterpret_cast<const uint4*>(store_desc + at * 32);
-            d0 = d[0], d1 = d[1];
-            w0 = store_world[at * 3], w1 = store_world[at * 3 + 1], w2 = store_world[at * 3 + 2];
-            const int row = prune_find(row_lid, seg.begin, seg.end, lid);
-            keep = row < 0;
-            if(row >= 0)
-                atomicAdd(&row_hits[row], 1u);
-        }
-        const unsigned long long bal = __ballot(keep);
-        if(lane == 0)
-            s_wave[chunk & 1][wave] = (int)__popcll(bal);
-        // every load of the chunk has returned before any of its stores is issued.  (The two halves of s_wave alternate:
-        // a thread that writes half h again has passed the barrier of the chunk in between, which every thread reaches
-        // only after its reads of h.)
-        __syncthreads();
-        int before = 0, total = 0;
-        for(int w = 0; w < kWaves; ++w)
-        {
-            const int cnt = s_wave[chunk & 1][w];
-            before += w < wave ? cnt : 0;
-            total += cnt;
-        }
-        const int dst = running + before + (int)__popcll(bal & ((1ull << lane) - 1ull));
-        if(keep && dst != i) // dst <= i always
-        {
-            const size_t to = base + dst;
-            store_lid[to] = lid;
-            uint4* d = reinterpret_cast<uint4*>(store_desc + to * 32);
-            d[0] = d0, d[1] = d1;
-            store_world[to * 3] = w0, store_world[to * 3 + 1] = w1, store_world[to * 3 + 2] = w2;
-        }
-        running += total;
-    }
-    if(tid == 0)
-    {
-        store_n[seg.slot] = running;
-        new_n[blockIdx.x] = running;
+        store_n[seg.slot] = kept;
+        new_n[blockIdx.x] = kept;
     }
 }
 

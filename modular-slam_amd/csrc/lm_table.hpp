@@ -1,5 +1,5 @@
 // lm_table.hpp — the open-addressing table on landmark ids that k_localmap.hip (union, covisibility, the list rewrite),
-// k_fuse.hip (eligibility) and k_cull.hip (observer counts) share: {u64 key, u64 val} buckets, a power of two of them and at
+// k_fuse.hip (eligibility), k_cull.hip (observer counts) and k_lmcull.hip (judged landmarks, the ids to remove) share: {u64 key, u64 val} buckets, a power of two of them and at
 // least twice the keys that can be inserted, cleared to all-ones (a landmark id is never all-ones: ids are below 2^63),
 // linear probing.  A key is claimed with one compare-and-swap; what the value holds is the caller's.
 #pragma once

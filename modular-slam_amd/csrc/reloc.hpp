@@ -1,5 +1,5 @@
 // reloc.hpp — what the files on the keyframe store share (k_reloc.hip: the store and mslam_hip_relocalize; k_track.hip,
-// k_track_window.hip, k_localmap.hip, k_fuse.hip, k_cull.hip, k_prune.hip): the store's state and scratch, the lookup of an
+// k_track_window.hip, k_localmap.hip, k_fuse.hip, k_cull.hip, k_lmcull.hip, k_prune.hip): the store's state and scratch, the lookup of an
 // id's slot, the landmark-id table in device scratch, the list rewrite of kf_update_world / kf_replace_ids / kf_fuse, the
 // match-to-PnP sequence over R rows that relocalize (one query, R entries) and a tracking window (R frames, one entry) both
 // enqueue, relocalize's body with two places where a caller can enqueue work of its own, and the launchers of k_backproject.
@@ -80,7 +80,8 @@ struct RelocState
     DevBuf<uint8_t> d_lm_blocks;
     PinnedBuf<uint8_t> h_lm;
     // ---- scratch of keyframe culling (k_cull.hip), grown on demand: [observer counts, one u32 per table bucket |
-    // first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32]
+    // first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32].  Landmark
+    // culling (k_lmcull.hip) uses the counts as they are (or as per-bucket hit counts) and the stamps as its judged flags
     DevBuf<uint8_t> d_cull;
 };
 
@@ -236,6 +237,31 @@ int rewrite_count(mslam_hip_ctx* c, const uint32_t* d_count, int* n_out);
 int rewrite_host_list(mslam_hip_ctx* c, const int64_t* from, const int64_t* to, const double* xyz, int n, const char* stage_table,
                       const char* stage_write, int* n_out);
 int64_t store_next_lid_base(mslam_hip_ctx* c); // advances the creation serial: call once per entry made, after store_slot_for
+
+// ---- the observer counts (k_cull.hip), which keyframe culling and landmark culling (k_lmcull.hip) both start with
+// the listed entries of one call: their slots and the sum of the sizes the host knows (n_upper)
+struct CullMap
+{
+    std::vector<int32_t> slots;
+    size_t keys = 0;
+};
+// where the count arrays lie in d_cull: [counts buckets x u32 | stamps buckets x u32 | buckets of a candidate's positions K x u32]
+struct CullDev
+{
+    LmTable table;
+    uint32_t *counts, *stamp, *bkt;
+    size_t buckets;
+};
+// ids[0, n_ids): 1..MSLAM_HIP_CULL_MAX_ENTRIES distinct ids of the store; pos_of: id -> position in the list
+int cull_resolve(mslam_hip_ctx* c, const std::string& me, const int32_t* ids, int n_ids, CullMap* m, std::unordered_map<int, int>* pos_of);
+// cand[0, n_cand): distinct, each one of the listed ids -> their slots
+int cull_cand_slots(mslam_hip_ctx* c, const std::string& me, const CullMap& m, const std::unordered_map<int, int>& pos_of,
+                    const int32_t* cand, int n_cand, std::vector<int32_t>* cand_slots);
+// the table of `keys` keys and the arrays behind it
+int cull_scratch(mslam_hip_ctx* c, size_t keys, CullDev* d);
+// the clears and the 2 x ceil(n_ids / 64) launches that leave the observer count of every bucket (the stamps: all-ones);
+// d_slots: the uploaded list
+int cull_count_enqueue(mslam_hip_ctx* c, const CullMap& m, const int32_t* d_slots, const CullDev& d);
 
 // The store slots of one tracking call (mslam_hip_track, mslam_hip_track_window[_dev]).  resolve() looks the reference and the vote list up and rejects a
 // new_id that names one of them; reserve() then takes new_id's slot (its own when the id exists: the entry is replaced)

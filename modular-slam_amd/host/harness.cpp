@@ -50,6 +50,10 @@
 //                                    keyframes and candidates: "cull culled N", one "cand <p> <id> <culled> <landmarks>
 //                                    <redundant>" line per candidate, then "remaining <ids...>": the entries the adapter
 //                                    still holds
+//        mslam_harness <plugin.so> --cull-landmarks <scene>
+//                                    ILandmarkCuller::cullLandmarks of the relocalizer adapter on the scene's entries, listed
+//                                    keyframes and candidates: "lmcull found N removed M", one "lm <id> <observers>" line per
+//                                    culled landmark id, then "entry <id> <count>" for every entry in scene order
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -493,21 +497,24 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if(argc == 4 && std::strcmp(argv[2], "--cull") == 0)
+        if(argc == 4 && (std::strcmp(argv[2], "--cull") == 0 || std::strcmp(argv[2], "--cull-landmarks") == 0))
         {
             // scene file: "MSCL", i32 version (1), i32 entries, i32 listed, i32 candidates, i32 min_observers, i32
             // min_landmarks, f64 ratio; per entry i32 id, i32 n (>= 1), n x 32 descriptor bytes, n x 3 f64 world points,
-            // n x i64 landmark ids; then the listed ids and the candidates as i32
+            // n x i64 landmark ids; then the listed ids and the candidates as i32.  --cull-landmarks: the same layout under
+            // the magic "MSLC", with min_observers as the only parameter (no min_landmarks, no ratio)
+            const bool landmarks = std::strcmp(argv[2], "--cull-landmarks") == 0;
             std::ifstream in(argv[3], std::ios::binary);
             char magic[4] = {0, 0, 0, 0};
             std::int32_t head[6] = {0, 0, 0, 0, 0, 0};
             mslam::KeyframeCullParams params;
             in.read(magic, 4);
-            in.read(reinterpret_cast<char*>(head), sizeof(head));
-            in.read(reinterpret_cast<char*>(&params.ratio), sizeof(params.ratio));
-            if(!in || std::memcmp(magic, "MSCL", 4) != 0 || head[0] != 1 || head[1] < 1 || head[2] < 0 || head[3] < 0)
+            in.read(reinterpret_cast<char*>(head), landmarks ? 5 * sizeof(head[0]) : sizeof(head));
+            if(!landmarks)
+                in.read(reinterpret_cast<char*>(&params.ratio), sizeof(params.ratio));
+            if(!in || std::memcmp(magic, landmarks ? "MSLC" : "MSCL", 4) != 0 || head[0] != 1 || head[1] < 1 || head[2] < 0 || head[3] < 0)
             {
-                std::fprintf(stderr, "%s is not a culling scene\n", argv[3]);
+                std::fprintf(stderr, "%s is not a %s scene\n", argv[3], landmarks ? "landmark-culling" : "culling");
                 return 5;
             }
             params.minObservers = head[4], params.minLandmarks = head[5];
@@ -516,10 +523,11 @@ int main(int argc, char** argv)
                 return 3;
             std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
             auto* culler = dynamic_cast<mslam::IKeyframeCuller*>(relocalizer.get());
+            auto* landmarkCuller = dynamic_cast<mslam::ILandmarkCuller*>(relocalizer.get());
             auto* localMap = dynamic_cast<mslam::ILocalMapTracker*>(relocalizer.get());
-            if(!culler || !localMap)
+            if((landmarks ? !landmarkCuller : !culler) || !localMap)
             {
-                std::fprintf(stderr, "the plugin does not offer keyframe culling\n");
+                std::fprintf(stderr, "the plugin does not offer %s culling\n", landmarks ? "landmark" : "keyframe");
                 return 6;
             }
             using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
@@ -577,6 +585,27 @@ int main(int argc, char** argv)
                     std::fprintf(stderr, "cannot read the lists of %s\n", argv[3]);
                     return 5;
                 }
+            }
+            if(landmarks)
+            {
+                // "lmcull found N removed M", one "lm <id> <observers>" line per culled id (ascending), then
+                // "entry <id> <count>" for every entry in scene order: the landmarks it holds afterwards
+                std::size_t before = 0, after = 0;
+                for(const auto& kf : entries)
+                    before += localMap->landmarkIds(kf).size();
+                const std::vector<mslam::CulledLandmark> culled = landmarkCuller->cullLandmarks(lists[0], lists[1], params.minObservers);
+                std::vector<std::size_t> counts;
+                for(const auto& kf : entries)
+                {
+                    counts.push_back(localMap->landmarkIds(kf).size());
+                    after += counts.back();
+                }
+                std::printf("lmcull found %zu removed %zu\n", culled.size(), before - after);
+                for(const auto& l : culled)
+                    std::printf("lm %lld %d\n", static_cast<long long>(l.id), l.observers);
+                for(std::size_t e = 0; e < entries.size(); ++e)
+                    std::printf("entry %lld %zu\n", static_cast<long long>(entries[e]->id), counts[e]);
+                return 0;
             }
             const std::vector<mslam::KeyframeCullVerdict> verdicts = culler->cullKeyframes(lists[0], lists[1], params);
             std::size_t gone = 0;

@@ -511,6 +511,46 @@ class BowDatabase
         return out;
     }
 
+    // ---- landmark culling (an extension).  cullLandmarks asks the search for the count first (a NULL list changes nothing
+    // and consults no capacity), then runs the fused call with room for exactly that many rows ----
+    std::vector<CulledLandmark> cullLandmarks(const std::vector<KeyframePtr>& map, const std::vector<KeyframePtr>& candidates, int minObservers)
+    {
+        const std::size_t n = map.size(), m = candidates.size();
+        std::vector<std::int32_t> ids(n + 1), cand(m + 1);
+        for(std::size_t k = 0; k < n; ++k)
+            ids[k] = storedLandmarksOf(map[k]);
+        for(std::size_t k = 0; k < m; ++k)
+            cand[k] = storedLandmarksOf(candidates[k]);
+        int found = 0;
+        int rc = mslam_hip_kf_cull_landmarks_search(ctx.h, ids.data(), static_cast<int>(n), cand.data(), static_cast<int>(m), minObservers,
+                                                    nullptr, nullptr, 0, &found);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_cull_landmarks_search", rc);
+        std::vector<std::int64_t> lids(static_cast<std::size_t>(found) + 1);
+        std::vector<std::int32_t> observers(lids.size());
+        rc = mslam_hip_kf_cull_landmarks(ctx.h, ids.data(), static_cast<int>(n), cand.data(), static_cast<int>(m), minObservers, lids.data(),
+                                         observers.data(), found, &found, nullptr, nullptr);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_cull_landmarks", rc);
+        std::vector<CulledLandmark> out(static_cast<std::size_t>(found));
+        for(std::size_t p = 0; p < out.size(); ++p)
+            out[p].id = lids[p], out[p].observers = observers[p];
+        return out;
+    }
+
+    std::vector<int> removeLandmarks(const std::vector<KeyframePtr>& map, const std::vector<std::int64_t>& landmarks)
+    {
+        const std::size_t n = map.size(), m = landmarks.size();
+        std::vector<std::int32_t> ids(n + 1), removed(m + 1);
+        for(std::size_t k = 0; k < n; ++k)
+            ids[k] = storedLandmarksOf(map[k]);
+        const int rc = mslam_hip_kf_remove_landmarks(ctx.h, ids.data(), static_cast<int>(n), landmarks.data(), static_cast<int>(m),
+                                                     removed.data(), nullptr, nullptr);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_remove_landmarks", rc);
+        return std::vector<int>(removed.begin(), removed.begin() + static_cast<std::ptrdiff_t>(m));
+    }
+
     KeyframeTrackResult trackAgainst(int refId,const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                      const CameraParameters& camera, const std::vector<KeyframePtr>& neighbours, const double* rvecGuess,
                                      const double* tvecGuess, const KeyframePtr& newKeyframe, const KeyframeTrackOptions& o)
@@ -672,7 +712,8 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public ILocalMapTracker,
                           public ILandmarkFuser,
                           public IObservationRemover,
-                          public IKeyframeCuller
+                          public IKeyframeCuller,
+                          public ILandmarkCuller
 {
   public:
     HipOrbRelocalizer() : db(BowDatabase::shared()) {}
@@ -739,6 +780,15 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                                                    const KeyframeCullParams& params) override
     {
         return db->cullKeyframes(map, candidates, params);
+    }
+    std::vector<CulledLandmark> cullLandmarks(const std::vector<BowDatabase::KeyframePtr>& map,
+                                              const std::vector<BowDatabase::KeyframePtr>& candidates, int minObservers) override
+    {
+        return db->cullLandmarks(map, candidates, minObservers);
+    }
+    std::vector<int> removeLandmarks(const std::vector<BowDatabase::KeyframePtr>& map, const std::vector<std::int64_t>& ids) override
+    {
+        return db->removeLandmarks(map, ids);
     }
     KeyframeTrackResult trackLocalMap(const std::vector<OrbKeypoint>& keypoints, const std::uint16_t* depth, int width, int height,
                                       const CameraParameters& camera, const std::vector<BowDatabase::KeyframePtr>& neighbours,

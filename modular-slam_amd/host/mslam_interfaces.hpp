@@ -439,4 +439,28 @@ class IKeyframeCuller
                                                            const KeyframeCullParams& params) = 0;
     virtual ~IKeyframeCuller() = default;
 };
+
+// ---- landmark culling (mslam_hip_kf_cull_landmarks, mslam_hip_kf_remove_landmarks; an extension) ---------------------------
+// The reference has no such step; the model is ORB-SLAM's MapPointCulling, of which this is the observer threshold (fewer
+// than two keyframes for RGB-D: minObservers = 2) without the found / visible ratio.  `map` names the stored keyframes that
+// count as observers and the only ones changed; a landmark id is judged when at least one of `candidates` (distinct, each
+// one of `map`) holds it, and goes from every keyframe of the map, at every position, when fewer than minObservers of them
+// hold it.  The counts are taken once, before anything is removed.  cullLandmarks -> the culled ids, ascending, with their
+// observer counts.  removeLandmarks removes the listed ids from every keyframe of the map -> per id, the positions that held
+// it (0: nobody did; an id listed twice reports the same number twice).  A keyframe that is not stored throws.  Offered by
+// the adapter that owns the store.
+struct CulledLandmark
+{
+    std::int64_t id = 0;
+    int observers = 0; // keyframes of the map that held it
+};
+class ILandmarkCuller
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual std::vector<CulledLandmark> cullLandmarks(const std::vector<KeyframePtr>& map, const std::vector<KeyframePtr>& candidates,
+                                                      int minObservers) = 0;
+    virtual std::vector<int> removeLandmarks(const std::vector<KeyframePtr>& map, const std::vector<std::int64_t>& ids) = 0;
+    virtual ~ILandmarkCuller() = default;
+};
 } // namespace mslam
