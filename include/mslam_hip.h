@@ -499,7 +499,8 @@ int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* ctx, const double* d_object, 
  *   cost = 1/2 sum_m |r_m|^2,   r_m = rot(q^-1, X) - rot(q^-1, p) - obs_cam[m]      (ReprojectionError::operator(), :31-47)
  * with (q, p) the state of keyframe obs_kf[m] (orientation x y z w, position; camera -> world), X landmark obs_lm[m] and
  * obs_cam[m] the camera-frame point ReprojectionError's constructor forms from the keypoint and its depth (:24-28); no loss
- * function, all in double.  The problem is handed over explicitly:
+ * function, all in double (mslam_hip_set_ba_loss below sets one: an extension, off by default).  The problem is handed over
+ * explicitly:
  *   poses      K x 7 (qx qy qz qw px py pz), K in 0..64, in: start, out: result; fixed[k] != 0 holds pose k constant (the
  *              reference fixes keyframe id 1, :155-159); fixed == NULL: none;
  *   landmarks  L x 3, in / out;   obs_kf, obs_lm, obs_cam: M observations, indices into poses / landmarks.
@@ -554,7 +555,8 @@ int mslam_hip_bundle_adjust(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out *
  * The reference's only loop correction (closeLoop is a TODO there).  Arguments, summary, residual, manifold, trust region,
  * termination order, FAILURE behaviour, outlier mask, determinism and the MSLAM_HIP_E_INVALID rules are those of
  * mslam_hip_bundle_adjust, with K in 0..MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES, and the reduced camera system is always built and
- * solved by the blocked solver below, at any K (so small problems compare the two solvers).  Every row of
+ * solved by the blocked solver below, at any K (so small problems compare the two solvers).  No loss function either, unless
+ * mslam_hip_set_ba_loss below sets one.  Every row of
  * mslam_hip_bundle_adjust's SAME / DEVIATES table holds here except these two:
  *   linear solver            DEVIATES in rounding: Schur complement on the landmarks (3x3 blocks inverted in closed form) over
  *                            the covisible pairs of keyframes only (pairs that share a landmark, from a sorted list built on
@@ -575,6 +577,35 @@ int mslam_hip_bundle_adjust_global(mslam_hip_ctx* ctx, double* poses /* K x 7, i
                                    const int32_t* obs_lm, const double* obs_cam /* M x 3 */, int M, int max_iterations /* 100 */,
                                    double outlier_threshold /* 0.15 */, uint8_t* outlier /* M, may be NULL */,
                                    mslam_hip_ba_summary* summary /* may be NULL */);
+/* ---- A loss function for both bundle adjustment entries (an extension: the reference passes lossFunction = nullptr) ----
+ * Context state, the idiom of mslam_hip_set_guided_match: mslam_hip_bundle_adjust and mslam_hip_bundle_adjust_global read it
+ * when they are called.  mslam_hip_pose_graph and mslam_hip_pnp_min_mse do NOT read it.  The default is NONE: both entries
+ * then launch the kernels they launched before this setting existed, and every result keeps its bits.
+ * The loss is per residual block, s = |r_m|^2 (the three camera-frame components together), scale a in metres, b = a^2:
+ *   HUBER    s <= b: rho = s, rho' = 1;   else rho = 2 a sqrt(s) - b, rho' = max(DBL_MIN, a / sqrt(s))
+ *   CAUCHY   rho = b log(1 + s / b), rho' = max(DBL_MIN, 1 / (1 + s / b))
+ * cost = 1/2 sum_m rho(|r_m|^2): initial_cost and final_cost of mslam_hip_ba_summary report that.  The residual and the
+ * three Jacobian blocks of observation m are scaled by sqrt(rho'); U, V, W, both gradients, the Jacobi scaling taken at the
+ * start, the model cost change, the gradient test and the function and parameter tolerances follow from the corrected
+ * blocks.  The outlier mask stays |r_m|^2 > outlier_threshold^2 on the UNCORRECTED residual at the returned state.  There is
+ * no default scale.  Two calls on the same input and setting return the same bits.
+ * set returns MSLAM_HIP_E_INVALID for a kind outside 0..2 or, for HUBER / CAUCHY, a scale that is not finite or not > 0; the
+ * setting is then unchanged.  With NONE the scale is ignored and reported as 0.  get: either pointer may be NULL.
+ * Against Ceres 2.2 (loss_function.h, corrector.cc, restated from the published text).  PARITY UNPINNED as for the solver:
+ * the tests compare with tests/ba_loss_ref.py, which applies the corrector to tests/ba_ref.py's residuals and Jacobians.
+ *   loss formulas            SAME: HuberLoss::Evaluate and CauchyLoss::Evaluate, s == b on Huber's inlier branch, Cauchy's
+ *                            1 + s c with c = 1 / b;
+ *   corrector                SAME branch: rho'' <= 0 everywhere for both kinds, so Corrector takes `sq_norm == 0 || rho[2] <=
+ *                            0`: sqrt(rho') on residual and Jacobians, no curvature term.  The other branch cannot occur;
+ *   weight                   DEVIATES in rounding: rho' multiplies every product of observation m (J^T J, J^T r, the model
+ *                            term) where Ceres scales the rows by sqrt(rho') first;
+ *   other losses             not built: SoftLOne, Arctan, Tolerant, Tukey (Tukey has rho'' > 0 and needs the full
+ *                            corrector), per-observation scales. */
+#define MSLAM_HIP_BA_LOSS_NONE 0
+#define MSLAM_HIP_BA_LOSS_HUBER 1
+#define MSLAM_HIP_BA_LOSS_CAUCHY 2
+int mslam_hip_set_ba_loss(mslam_hip_ctx* ctx, int kind, double scale);
+int mslam_hip_get_ba_loss(mslam_hip_ctx* ctx, int* kind, double* scale);
 /* ---- RgbdFeatureFrontend::closeLoop (rgbd_feature_frontend.cpp:577-580, an empty body; called at :198-205): pose graph ----
  * The correction a detected loop asks for: Levenberg-Marquardt over keyframe poses of
  *   cost = 1/2 sum_e |r_e|^2,   r_e = sqrt_info_e [p_ab - p_meas ; 2 vec(delta)]

@@ -141,6 +141,9 @@ struct mslam_hip_ctx
     mslam::DevBuf<uint8_t> d_pnp_mask;
     int pnp_iterations = 0;
     double pnp_confidence = 0.99; // cv_ransac_pnp.cpp:57 (mslam_hip_pnp_set_confidence)
+    // mslam_hip_set_ba_loss: read by both bundle adjustment entry points when they are called; NONE keeps scale 0
+    int ba_loss_kind = MSLAM_HIP_BA_LOSS_NONE;
+    double ba_loss_scale = 0.0;
     // single-problem PnP scratch (mslam_hip_pnp_ransac), grown on demand
     mslam::DevBuf<float> d_pnp1_obj, d_pnp1_img;
     mslam::DevBuf<double> d_pnp1_hyp, d_pnp1_out;

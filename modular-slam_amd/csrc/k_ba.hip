@@ -31,6 +31,13 @@
 // state has not moved, so the block kernels reuse what they stored and only the damping is redone.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
+//
+// mslam_hip_set_ba_loss (an extension: the reference passes lossFunction = nullptr): with HUBER or CAUCHY the cost is
+// 1/2 sum_m rho(|r_m|^2) and observation m carries the weight w_m = rho'(|r_m|^2) at the state (ba_loss below; Ceres's
+// corrector in its simple branch, since rho'' <= 0 for both).  k_ba_landmarks, k_ba_cameras and k_ba_eval have a second
+// instantiation that applies w_m to every product of observation m (V, g_l, U, g_c, W, the model term) and rho to the costs;
+// each recomputes w_m from ba_residual, so all three use the same bits.  Everything else reads only what these store.
+// With NONE the instantiations of before are launched.  DESIGN.md 4.22.
 #include "chol_solver.hpp"
 
 #include <algorithm>
@@ -64,6 +71,9 @@ struct BaArgs
     double* part;               // [2][n_blocks]: model cost change, candidate cost
     TrCtrl* ctrl;
     int32_t* h_done; // mapped
+    // mslam_hip_set_ba_loss: MSLAM_HIP_BA_LOSS_*, and a (metres) of HUBER / CAUCHY
+    int loss_kind;
+    double loss_scale;
 };
 
 __device__ __forceinline__ void ba_residual(const double* __restrict__ pose, const double* __restrict__ X, const double* __restrict__ obs,
@@ -75,6 +85,39 @@ __device__ __forceinline__ void ba_residual(const double* __restrict__ pose, con
     quat_rotate(qi, x, a);
     quat_rotate(qi, p, b);
     r[0] = a[0] - b[0] - obs[0], r[1] = a[1] - b[1] - obs[1], r[2] = a[2] - b[2] - obs[2];
+}
+// loss_function.h's HuberLoss / CauchyLoss Evaluate at s = |r|^2 with scale a: rho(s) and w = rho'(s).  b = a^2.
+//   Huber:  s > b: rho = 2 a sqrt(s) - b, rho' = max(DBL_MIN, a / sqrt(s)); else rho = s, rho' = 1 (s == b is the inlier branch)
+//   Cauchy: rho = b log(1 + s c), rho' = max(DBL_MIN, 1 / (1 + s c)), c = 1 / b
+// rho'' <= 0 for both, so corrector.cc takes the branch that scales residual and Jacobians by sqrt(rho') and nothing else.
+// s = 0 gives w = 1 in both (no 0 / 0); a NaN s gives a NaN rho, which the cost carries to FAILURE.
+__device__ __forceinline__ void ba_loss(int kind, double a, double s, double& rho, double& w)
+{
+    const double b = a * a;
+    if(kind == MSLAM_HIP_BA_LOSS_HUBER)
+    {
+        if(s > b)
+        {
+            const double r = sqrt(s);
+            rho = 2.0 * a * r - b;
+            w = fmax(DBL_MIN, a / r);
+        }
+        else
+            rho = s, w = 1.0;
+    }
+    else
+    {
+        const double sum = 1.0 + s * (1.0 / b);
+        rho = b * log(sum);
+        w = fmax(DBL_MIN, 1.0 / sum);
+    }
+}
+// w_m of observation m from its residual
+__device__ __forceinline__ double ba_weight(const BaArgs& a, const double r[3])
+{
+    double rho, w;
+    ba_loss(a.loss_kind, a.loss_scale, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho, w);
+    return w;
 }
 // J_c = [2 R^T [d]x | -R^T] (3 x 6), d = X - p
 __device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const double d[3], double Jc[3][6])
@@ -90,7 +133,10 @@ __device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const dou
 
 // ---- blocks ------------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
+// kLoss = false: no loss function, the kernels of mslam_hip_bundle_adjust as the reference states it; kLoss = true: every
+// product of observation m takes w_m
+template <bool kLoss>
+__device__ __forceinline__ void ba_landmarks_rows(const BaArgs& a)
 {
     const TrCtrl* ct = a.ctrl;
     if(ct->done)
@@ -113,6 +159,17 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
             quat_inverse(pose, qi);
             quat_matrix(qi, Rt);
             ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
+            if constexpr(kLoss)
+            {
+                const double w = ba_weight(a, r); // constant keyframes too: their rows are part of V and g_l
+                for(int rr = 0; rr < 3; ++rr)
+                {
+                    for(int c = rr; c < 3; ++c)
+                        V[tri3(rr, c)] += w * (Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c]);
+                    g[rr] += w * (Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2]);
+                }
+                continue;
+            }
             for(int rr = 0; rr < 3; ++rr)
             {
                 for(int c = rr; c < 3; ++c)
@@ -152,7 +209,10 @@ __global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a)
     I[3] = (a00 * a22 - a02 * a02) / det, I[4] = (a01 * a02 - a00 * a12) / det, I[5] = (a00 * a11 - a01 * a01) / det;
 }
 
-__global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
+__global__ __launch_bounds__(256) void k_ba_landmarks(BaArgs a) { ba_landmarks_rows<false>(a); }
+
+template <bool kLoss>
+__device__ __forceinline__ void ba_cameras_rows(const BaArgs& a)
 {
     __shared__ double red[4][27];
     const TrCtrl* ct = a.ctrl;
@@ -177,6 +237,20 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
         ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
         ba_camera_jacobian(Rt, d, Jc);
         int j = 0;
+        if constexpr(kLoss)
+        {
+            const double w = ba_weight(a, r);
+            for(int rr = 0; rr < 6; ++rr)
+                for(int c = rr; c < 6; ++c)
+                    acc[j++] += w * (Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c]);
+            for(int rr = 0; rr < 6; ++rr)
+                acc[21 + rr] += w * (Jc[0][rr] * r[0] + Jc[1][rr] * r[1] + Jc[2][rr] * r[2]);
+            double* W = a.W + (size_t)m * 18;
+            for(int rr = 0; rr < 6; ++rr)
+                for(int c = 0; c < 3; ++c)
+                    W[rr * 3 + c] = w * (Jc[0][rr] * Rt[c] + Jc[1][rr] * Rt[3 + c] + Jc[2][rr] * Rt[6 + c]);
+            continue;
+        }
         for(int rr = 0; rr < 6; ++rr)
             for(int c = rr; c < 6; ++c)
                 acc[j++] += Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c];
@@ -208,6 +282,8 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a)
         a.sc[(size_t)k * 6 + tid] = 1.0 / (1.0 + sqrt(((red[0][j] + red[1][j]) + red[2][j]) + red[3][j]));
     }
 }
+
+__global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) { ba_cameras_rows<false>(a); }
 
 // ---- FinalizeIterationAndCheckIfMinimizerCanContinue: one wave ------------------------------------------------------------
 
@@ -472,8 +548,10 @@ __global__ __launch_bounds__(256) void k_ba_candidate(BaArgs a)
     }
 }
 
-// at_start: only the cost at the state (pose, lm), for iteration 0
-__global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
+// at_start: only the cost at the state (pose, lm), for iteration 0.  kLoss: the model term takes w_m at the state, the cost
+// is rho(|r|^2) / 2
+template <bool kLoss>
+__device__ __forceinline__ void ba_eval_rows(const BaArgs& a, int at_start)
 {
     __shared__ double red[4];
     if(a.ctrl->done)
@@ -513,9 +591,18 @@ __global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
             for(int j = 0; j < 3; ++j)
                 Js[j] = Rt[j * 3] * v[0] + Rt[j * 3 + 1] * v[1] + Rt[j * 3 + 2] * v[2];
             model = -(Js[0] * (f[0] + Js[0] / 2.0) + Js[1] * (f[1] + Js[1] / 2.0) + Js[2] * (f[2] + Js[2] / 2.0));
+            if constexpr(kLoss)
+                model = ba_weight(a, f) * model;
             ba_residual(a.cand_pose + (size_t)k * 7, a.cand_lm + (size_t)l * 3, obs, r);
         }
-        cost = 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        if constexpr(kLoss)
+        {
+            double rho, w;
+            ba_loss(a.loss_kind, a.loss_scale, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho, w);
+            cost = 0.5 * rho;
+        }
+        else
+            cost = 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     }
     const double ms = block_sum(model, red), cs = block_sum(cost, red);
     if(threadIdx.x == 0)
@@ -524,6 +611,8 @@ __global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start)
         a.part[a.n_blocks + blockIdx.x] = cs;
     }
 }
+
+__global__ __launch_bounds__(256) void k_ba_eval(BaArgs a, int at_start) { ba_eval_rows<false>(a, at_start); }
 
 // ---- the trust-region bookkeeping of one iteration: one wave ----------------------------------------------------------------
 
@@ -571,6 +660,13 @@ __global__ __launch_bounds__(256) void k_ba_outliers(BaArgs a, const double* __r
     ba_residual(pose + (size_t)a.obs_kf[m] * 7, lm + (size_t)a.obs_lm[m] * 3, a.obs_cam + (size_t)m * 3, r);
     out[m] = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) > threshold2 ? 1 : 0;
 }
+
+// ---- the kernels of a solve with a loss function --------------------------------------------------------------------------
+// Defined after every kernel of before, so that those keep their place in the code object: a solve without a loss runs the
+// code it ran, where it was.
+__global__ __launch_bounds__(256) void k_ba_landmarks_loss(BaArgs a) { ba_landmarks_rows<true>(a); }
+__global__ __launch_bounds__(256) void k_ba_cameras_loss(BaArgs a) { ba_cameras_rows<true>(a); }
+__global__ __launch_bounds__(256) void k_ba_eval_loss(BaArgs a, int at_start) { ba_eval_rows<true>(a, at_start); }
 
 } // namespace mslam
 
@@ -711,17 +807,19 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     a.S = blocked ? c->d_ba_S.get() : dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
     a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
+    a.loss_kind = c->ba_loss_kind, a.loss_scale = c->ba_loss_scale;
+    const bool loss = a.loss_kind != MSLAM_HIP_BA_LOSS_NONE;
     *c->h_ba.get() = 0;
     const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
 
     const dim3 g_lm((unsigned)((L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((K + L + 255) / 256));
     {
         StageScope ts(c, "ba_start_cost");
-        hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
+        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
     }
     const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
-        hipLaunchKernelGGL(k_ba_landmarks, g_lm, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss ? k_ba_landmarks_loss : k_ba_landmarks, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss ? k_ba_cameras_loss : k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
         if(a.n_pairs > 0 && !blocked)
         {
@@ -739,7 +837,7 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
         }
         hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
+        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
         hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
     }, sum);
     if(rc != MSLAM_HIP_OK)
@@ -787,4 +885,29 @@ extern "C" int mslam_hip_bundle_adjust_global(mslam_hip_ctx* c, double* poses, c
 {
     return ba_run(c, true, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
                   summary);
+}
+
+// The loss of both entry points above: context state, read when they are called
+extern "C" int mslam_hip_set_ba_loss(mslam_hip_ctx* c, int kind, double scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY)
+        return fail(c, MSLAM_HIP_E_INVALID, "set_ba_loss: kind outside 0..2");
+    if(kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0))
+        return fail(c, MSLAM_HIP_E_INVALID, "set_ba_loss: the scale of HUBER / CAUCHY must be finite and > 0");
+    c->ba_loss_kind = kind;
+    c->ba_loss_scale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_ba_loss(mslam_hip_ctx* c, int* kind, double* scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind)
+        *kind = c->ba_loss_kind;
+    if(scale)
+        *scale = c->ba_loss_scale;
+    return MSLAM_HIP_OK;
 }

@@ -33,6 +33,10 @@
 //        mslam_harness <plugin.so> --ba-global <scene>
 //                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
 //                                    keyframe's and landmark's state and the outlier observations
+//        mslam_harness <plugin.so> --ba <scene> --loss huber:<a> | cauchy:<a>
+//        mslam_harness <plugin.so> --ba-global <scene> --loss huber:<a> | cauchy:<a>
+//                                    the same with IRobustBackend::setLoss(kind, a) first (a in metres, finite and > 0): the
+//                                    costs of the summary are then 1/2 sum rho
 //        mslam_harness <plugin.so> --pose-graph <scene>
 //                                    ILoopClosingBackend::closeLoop of the same factory's object on one pose-graph scene: the
 //                                    summary, then every keyframe's state
@@ -148,8 +152,16 @@ int main(int argc, char** argv)
                         result->pose.orientation.z(), inl);
             return 0;
         }
-        if(argc == 4 && (std::strcmp(argv[2], "--ba") == 0 || std::strcmp(argv[2], "--ba-global") == 0))
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--loss") == 0)) &&
+           (std::strcmp(argv[2], "--ba") == 0 || std::strcmp(argv[2], "--ba-global") == 0))
         {
+            int lossKind = 0;
+            double lossScale = 0.0;
+            if(argc == 6 && !mslam::parseLoss(argv[5], lossKind, lossScale))
+            {
+                std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[5]);
+                return 2;
+            }
             const bool global = std::strcmp(argv[2], "--ba-global") == 0; // IGlobalBackend::globalBundleAdjustment: up to 1024 keyframes
             // scene file: "MSBA", i32 version (1), K, L, M, max_iterations; K x i32 keyframe id; K x 7 f64 state (qx qy qz qw
             // px py pz); L x 3 f64; M x i32 keyframe index; M x i32 landmark index; M x 3 f64 camera-frame point
@@ -214,6 +226,16 @@ int main(int argc, char** argv)
             {
                 std::fprintf(stderr, "the plugin does not offer the global bundle adjustment\n");
                 return 6;
+            }
+            if(lossKind != 0)
+            {
+                auto* robust = dynamic_cast<mslam::IRobustBackend*>(backend.get());
+                if(!robust)
+                {
+                    std::fprintf(stderr, "the plugin does not offer a loss function\n");
+                    return 6;
+                }
+                robust->setLoss(lossKind, lossScale);
             }
             const mslam::BackendOutput out =
                 global ? globalBackend->globalBundleAdjustment(observations, head[4]) : backend->bundleAdjustment(observations, head[4]);

@@ -11,6 +11,7 @@
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
 //   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
+//                          : IRobustBackend                                       a Huber or Cauchy loss for both bundle adjustments (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -941,10 +942,18 @@ class HipMinMseTracker : public ISlam3dPnp
 // constant — and the result is written back into keyframe->state and landmark->state, as Ceres writes through the pointers
 // the reference hands it.  More than 64 keyframes is an error (the reduced system is dense); FAILURE updates nothing.
 // globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.  closeLoop hands the
-// keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way.
-class HipBundleAdjustBackend : public ILoopClosingBackend
+// keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way.  setLoss (IRobustBackend,
+// an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.
+class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
 {
   public:
+    void setLoss(int kind, double scale) override
+    {
+        if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY ||
+           (kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0)))
+            throw std::invalid_argument("setLoss: kind 0 (none), 1 (Huber) or 2 (Cauchy); their scale finite and > 0");
+        lossKind = kind, lossScale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    }
     BackendOutput bundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations) override
     {
         return solve(observations, maxIterations, false);
@@ -1046,6 +1055,9 @@ class HipBundleAdjustBackend : public ILoopClosingBackend
         ctx.ensure(0, 0);
         mslam_hip_ba_summary summary{};
         const auto entry = global ? mslam_hip_bundle_adjust_global : mslam_hip_bundle_adjust;
+        const int lrc = mslam_hip_set_ba_loss(ctx.h, lossKind, lossScale);
+        if(lrc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_ba_loss", lrc);
         const int rc = entry(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
                              static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
                              static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
@@ -1074,6 +1086,8 @@ class HipBundleAdjustBackend : public ILoopClosingBackend
     }
 
     Ctx ctx;
+    int lossKind = MSLAM_HIP_BA_LOSS_NONE;
+    double lossScale = 0.0;
 };
 
 // ---- factories + aliases (what loadFactoryMethod<T>(lib, name) imports) -------------------------------

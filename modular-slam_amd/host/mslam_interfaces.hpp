@@ -25,6 +25,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <optional>
 #include <utility>
@@ -250,6 +252,39 @@ class ILoopClosingBackend : public IGlobalBackend
     virtual BackendOutput closeLoop(const std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>>& keyframes,
                                     const std::vector<PoseGraphEdge>& edges, int maxIterations = 100) = 0;
 };
+// extension (the reference passes lossFunction = nullptr, ceres_backend.cpp:143): a loss function for bundleAdjustment and
+// globalBundleAdjustment (mslam_hip_set_ba_loss): kind 0 none (the default), 1 Ceres's HuberLoss(scale), 2 CauchyLoss(scale),
+// scale in metres.  It holds for every later solve of the object; closeLoop does not read it.  The costs of BackendOutput
+// are then 1/2 sum rho; the outliers are still judged on the plain residual.  A kind outside 0..2, or a scale that is not
+// finite or not > 0 with kind 1 or 2, throws std::invalid_argument and leaves the setting as it was.  An interface of its
+// own, reached with dynamic_cast: IBackend and IGlobalBackend mirror the reference and gain no virtual.
+class IRobustBackend
+{
+  public:
+    virtual void setLoss(int kind, double scale) = 0;
+    virtual ~IRobustBackend() = default;
+};
+// "huber:<a>" or "cauchy:<a>" -> kind 1 or 2 and a; false (nothing written) for anything else, a trailing character or an a
+// that is not finite or not > 0
+inline bool parseLoss(const char* text, int& kind, double& scale)
+{
+    if(!text)
+        return false;
+    int k = 0;
+    const char* number = nullptr;
+    if(std::strncmp(text, "huber:", 6) == 0)
+        k = 1, number = text + 6;
+    else if(std::strncmp(text, "cauchy:", 7) == 0)
+        k = 2, number = text + 7;
+    else
+        return false;
+    char* end = nullptr;
+    const double a = std::strtod(number, &end);
+    if(end == number || *end != '\0' || !std::isfinite(a) || !(a > 0.0))
+        return false;
+    kind = k, scale = a;
+    return true;
+}
 
 
 // ---- extension (not in the reference): candidates verified by match + RANSAC PnP against stored landmarks -----------------
