@@ -798,6 +798,51 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* ctx, int keep_id, int drop_id, const double
                       int32_t* keep_pos /* may be NULL, as the next four */, int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid,
                       int32_t* dist, int capacity, int* n_pairs, int* n_rewritten /* may be NULL */);
 
+/* ---- landmark fusion into many keyframes: SearchAndFuse's loop over the connected keyframes, in one call -------------
+ * AN EXTENSION, as the calls above.  mslam_hip_kf_fuse_search_multi finds the duplicates between entry keep_id (an ordinary
+ * entry or a union: the landmarks whose ids survive) and n_drop distinct target entries drop_ids[m], target m under its
+ * own pose world -> camera R + 9 m, t + 3 m, and changes nothing.
+ *   projection, candidate, knn-2, acceptance
+ *                per target m exactly those of mslam_hip_kf_fuse_search(keep_id, drop_ids[m], R + 9 m, t + 3 m, ...): the
+ *                same f64 expression, every operation rounded on its own; the drop entry's landmarks play the part of
+ *                keypoints with xy = ((float)u, (float)v); key dist << 16 | drop position.
+ *   eligibility  GLOBAL: a keep landmark whose id occurs anywhere in ANY listed drop entry is neither a searcher nor a
+ *                candidate in any target, and a drop landmark whose id occurs anywhere in the keep entry is ineligible.
+ *                (Otherwise an entry that shares K already and also holds D would hold K twice after D -> K.)  With
+ *                n_drop == 1 this is mslam_hip_kf_fuse_search's rule.  So the two id sets of a call's pairs are disjoint
+ *                and no chain of replacements can arise.
+ *   one to one   per target, as above: of several keep landmarks that accept the same drop position of target m the one
+ *                with the least (d0, keep position) keeps the row; the others get none (no second choice).  Then ACROSS
+ *                targets, on landmark ids and again without a second choice: (A) of all rows left, over all targets, that
+ *                carry the same drop_lid the one with the least (dist, target, keep_pos) stays; (B) of the rows left after
+ *                (A) that carry the same keep_lid the one with the least (dist, target, drop_pos) stays.  The result is one
+ *                to one on ids; the same (keep_lid, drop_lid) found in several targets is one row; an id repeated at
+ *                several positions of one entry is resolved like any other.
+ *   order        rows are ordered by (target, keep_pos).  Row p: target = m, keep_pos / drop_pos = the positions inside
+ *                the keep entry and entry drop_ids[m], keep_lid / drop_lid = their landmark ids, dist = d0.
+ * Errors: those of mslam_hip_kf_fuse_search, and MSLAM_HIP_E_INVALID for n_drop outside 1..64, a drop id equal to keep_id
+ * or listed twice, any entry above 65535 landmarks; MSLAM_HIP_E_CAPACITY with *n_pairs = the count needed (nothing is
+ * copied) when the pairs exceed `capacity` rows.  An empty entry, or a target with nothing in front of its camera, is OK
+ * with no rows.  One upload (the targets), a clear, eight launches whatever n_drop is (ids, projection, binning, search with
+ * the per-target claims, claims A, claims B, count, per-target compaction: the target is a grid dimension), one
+ * synchronisation; every output is deterministic.
+ *
+ * mslam_hip_kf_fuse_multi runs the search and then the replacement drop_lid -> keep_lid with the winning keep position's
+ * world point, bit for bit, store-wide (mslam_hip_kf_replace_ids' pass: two launches more).  The pair list never leaves the
+ * device between the two and there is one synchronisation at the end.  The pair arrays may be NULL; `capacity` bounds the
+ * pairs either way: when they do not fit, nothing is rewritten and the call returns MSLAM_HIP_E_CAPACITY with *n_pairs =
+ * the count needed. */
+int mslam_hip_kf_fuse_search_multi(mslam_hip_ctx* ctx, int keep_id, const int32_t* drop_ids, int n_drop /* 1..64 */,
+                                   const double* R /* n_drop x 9 */, const double* t /* n_drop x 3 */, double fx, double fy, double cx,
+                                   double cy, int width, int height, double radius, int max_distance, double ratio,
+                                   double max_world_distance, int32_t* target, int32_t* keep_pos, int32_t* drop_pos, int64_t* keep_lid,
+                                   int64_t* drop_lid, int32_t* dist, int capacity, int* n_pairs);
+int mslam_hip_kf_fuse_multi(mslam_hip_ctx* ctx, int keep_id, const int32_t* drop_ids, int n_drop /* 1..64 */,
+                            const double* R /* n_drop x 9 */, const double* t /* n_drop x 3 */, double fx, double fy, double cx, double cy,
+                            int width, int height, double radius, int max_distance, double ratio, double max_world_distance,
+                            int32_t* target /* may be NULL, as the next five */, int32_t* keep_pos, int32_t* drop_pos, int64_t* keep_lid,
+                            int64_t* drop_lid, int32_t* dist, int capacity, int* n_pairs, int* n_rewritten /* may be NULL */);
+
 /* ---- RgbdFeatureFrontend::removeObservation (rgbd_feature_frontend.cpp:469-487, a commented-out body; called at :224-230) ----
  * THE BODY THE REFERENCE LEAVES COMMENTED OUT: update(const BackendOutputType&) calls removeObservation for every outlier
  * observation a bundle adjustment reports; the commented code erased the keyframe <-> landmark link and the landmark itself

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "mslam_hip_match_guided_knn2", "mslam_hip_match_guided", "mslam_hip_set_guided_match", "mslam_hip_get_guided_match",
     "mslam_hip_bundle_adjust", "mslam_hip_bundle_adjust_global", "mslam_hip_kf_update_world", "mslam_hip_pose_graph",
     "mslam_hip_kf_fuse_search", "mslam_hip_kf_replace_ids", "mslam_hip_kf_fuse",
+    "mslam_hip_kf_fuse_search_multi", "mslam_hip_kf_fuse_multi",
     "mslam_hip_kf_remove_observations",
     "mslam_hip_kf_observers", "mslam_hip_kf_cull_search", "mslam_hip_kf_cull",
     "mslam_hip_kf_remove_landmarks", "mslam_hip_kf_cull_landmarks_search", "mslam_hip_kf_cull_landmarks",
@@ -632,6 +633,54 @@ class Context:
         nr = C.c_int(0)
         out = self._fuse_call(self.L.mslam_hip_kf_fuse, keep_id, drop_id, R, t, radius, max_distance, ratio,
                               max_world_distance, focal, principal, width, height, capacity, (C.byref(nr),))
+        out["n_rewritten"] = nr.value
+        return out
+
+    # ---- landmark fusion into many target entries (SearchAndFuse's loop over the connected keyframes, one call) ----
+    def _fuse_multi_call(self, entry, keep_id, drop_ids, R, t, radius, max_distance, ratio, max_world_distance, focal, principal,
+                         width, height, capacity, tail):
+        """the search or the fused call, as _fuse_call: the default capacity, max_keypoints, holds every result (a call has
+        at most one pair per keep landmark), a smaller one of the caller's gives E_CAPACITY carrying `needed`"""
+        ids = np.ascontiguousarray(drop_ids, np.int32).reshape(-1)
+        R = np.ascontiguousarray(R, np.float64).reshape(-1)
+        t = np.ascontiguousarray(t, np.float64).reshape(-1)
+        if len(R) != 9 * len(ids) or len(t) != 3 * len(ids):
+            raise MslamHipError(E_INVALID, "kf_fuse_multi: %d drop ids, %d R values, %d t values" % (len(ids), len(R), len(t)))
+        cap = int(self.params.max_keypoints if capacity is None else capacity)
+        tg, kp, dp, di = (np.zeros(max(cap, 1), np.int32) for _ in range(4))
+        kl, dl = (np.zeros(max(cap, 1), np.int64) for _ in range(2))
+        n = C.c_int(0)
+        rc = entry(self._h, int(keep_id), _p(ids), len(ids), _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]),
+                   C.c_double(principal[0]), C.c_double(principal[1]), int(self.params.width if width is None else width),
+                   int(self.params.height if height is None else height), C.c_double(radius), int(max_distance),
+                   C.c_double(ratio), C.c_double(max_world_distance), _p(tg), _p(kp), _p(dp), _p(kl), _p(dl), _p(di), cap,
+                   C.byref(n), *tail)
+        if rc == E_CAPACITY:
+            e = MslamHipError(rc, (self.L.mslam_hip_last_error(self._h) or b"").decode())
+            e.needed = n.value
+            raise e
+        self._chk(rc)
+        k = n.value
+        return dict(target=tg[:k].copy(), keep_pos=kp[:k].copy(), drop_pos=dp[:k].copy(), keep_lid=kl[:k].copy(),
+                    drop_lid=dl[:k].copy(), dist=di[:k].copy())
+
+    def kf_fuse_search_multi(self, keep_id, drop_ids, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf,
+                             focal=(525.0, 525.0), principal=(319.5, 239.5), width=None, height=None, capacity=None):
+        """the landmarks of the entries drop_ids (1..64, distinct) that duplicate landmarks of entry keep_id: kf_fuse_search
+        per target m under its own world -> camera pose (R[m], t[m]), with eligibility taken over all listed entries, then
+        one row per drop id (the least (dist, target, keep_pos)) and one per keep id (the least (dist, target, drop_pos))
+        -> dict(target, keep_pos, drop_pos, keep_lid, drop_lid, dist), ordered by (target, keep_pos).  Changes nothing.
+        More pairs than a given `capacity`: MslamHipError E_CAPACITY carrying `needed`."""
+        return self._fuse_multi_call(self.L.mslam_hip_kf_fuse_search_multi, keep_id, drop_ids, R, t, radius, max_distance, ratio,
+                                     max_world_distance, focal, principal, width, height, capacity, ())
+
+    def kf_fuse_multi(self, keep_id, drop_ids, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf,
+                      focal=(525.0, 525.0), principal=(319.5, 239.5), width=None, height=None, capacity=None):
+        """kf_fuse_search_multi, then every store landmark with a pair's drop id takes the keep id and the keep landmark's
+        world point, in one call with one synchronisation -> kf_fuse_search_multi's dict plus n_rewritten"""
+        nr = C.c_int(0)
+        out = self._fuse_multi_call(self.L.mslam_hip_kf_fuse_multi, keep_id, drop_ids, R, t, radius, max_distance, ratio,
+                                    max_world_distance, focal, principal, width, height, capacity, (C.byref(nr),))
         out["n_rewritten"] = nr.value
         return out
 
@@ -1668,7 +1717,15 @@ class HipKeyframeTracker:
     against the old side adds a graph edge wherever the count is positive; the local map is rebuilt.  The attempt's dict
     gains fusion = dict(n_pairs, n_rewritten, edges).  The reserved ids are never in self.ids, the vote list or the
     candidates.  Off (the default): none of this runs and no union is built, so serials and fresh ids are unchanged.
-    STILL OUT: duplicates outside the corrected keyframe's view stay unfused.
+
+    loop_fusion_keyframes = True (needs loop_fusion, else MslamHipError(E_INVALID); SearchAndFuse's loop over the connected
+    keyframes): the fusion step builds the keep union alone and calls Context.kf_fuse_multi with every keyframe of
+    self.neighbours(new keyframe) as a target of its own, each under the inverse of its corrected pose
+    self.backend.poses[k].  Keyframes that are on the old side as well stay in the list: eligibility is taken over all
+    listed entries, which makes them harmless.  One union is built instead of two, so later serials differ from a run
+    without the option.  The attempt's fusion dict gains targets.  Off (the default): the fusion step makes exactly the
+    calls described above.
+    STILL OUT: old-side landmarks that no new-side keyframe sees stay unfused, and the descriptors of a pair are not merged.
 
     ba_prune = True (needs local_ba, else MslamHipError(E_INVALID)): the consumer of the backend's outlier mask,
     RgbdFeatureFrontend::update(const BackendOutputType&) (rgbd_feature_frontend.cpp:224-230) with the removeObservation
@@ -1728,7 +1785,7 @@ class HipKeyframeTracker:
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
-                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None):
+                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False):
         self.ctx = ctx
         if ba_loss is not None and not local_ba:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_loss needs local_ba (the backend's solves take the loss)")
@@ -1747,6 +1804,9 @@ class HipKeyframeTracker:
         self.ba_prune = bool(ba_prune)
         if loop_fusion and not loop_closure:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_fusion needs loop_closure")
+        if loop_fusion_keyframes and not loop_fusion:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_fusion_keyframes needs loop_fusion")
+        self.loop_fusion_keyframes = bool(loop_fusion_keyframes)
         self.loop_fusion, self.loop_fuse_radius = bool(loop_fusion), float(loop_fuse_radius)
         self.loop_fuse_max_distance, self.loop_fuse_world_distance = int(loop_fuse_max_distance), float(loop_fuse_world_distance)
         self._extent = None          # (width, height) of the last frame's depth image: the frame loop_fusion projects into
@@ -2068,13 +2128,21 @@ class HipKeyframeTracker:
         old, new = self.neighbours(loop_id), self.neighbours(new_id)
         self.ctx.kf_union(self.FUSE_KEEP_ID, old)
         try:
-            self.ctx.kf_union(self.FUSE_DROP_ID, new)
-            try:
-                got = self.ctx.kf_fuse(self.FUSE_KEEP_ID, self.FUSE_DROP_ID, self.R, self.tvec, self.loop_fuse_radius,
-                                       self.loop_fuse_max_distance, self.ratio, self.loop_fuse_world_distance, self.focal,
-                                       self.principal, self._extent[0], self._extent[1])
-            finally:
-                self.ctx.kf_remove(self.FUSE_DROP_ID)
+            if self.loop_fusion_keyframes:
+                # every keyframe of the new side is a target under its own corrected pose (camera -> world in the backend)
+                Rs = [quaternion_to_rotation(self.backend.poses[k][:4]).T for k in new]
+                ts = [-R @ self.backend.poses[k][4:] for R, k in zip(Rs, new)]
+                got = self.ctx.kf_fuse_multi(self.FUSE_KEEP_ID, new, np.stack(Rs), np.stack(ts), self.loop_fuse_radius,
+                                             self.loop_fuse_max_distance, self.ratio, self.loop_fuse_world_distance, self.focal,
+                                             self.principal, self._extent[0], self._extent[1])
+            else:
+                self.ctx.kf_union(self.FUSE_DROP_ID, new)
+                try:
+                    got = self.ctx.kf_fuse(self.FUSE_KEEP_ID, self.FUSE_DROP_ID, self.R, self.tvec, self.loop_fuse_radius,
+                                           self.loop_fuse_max_distance, self.ratio, self.loop_fuse_world_distance, self.focal,
+                                           self.principal, self._extent[0], self._extent[1])
+                finally:
+                    self.ctx.kf_remove(self.FUSE_DROP_ID)
         finally:
             self.ctx.kf_remove(self.FUSE_KEEP_ID)
         self.backend.fuse(got["keep_lid"], got["drop_lid"])
@@ -2086,7 +2154,10 @@ class HipKeyframeTracker:
                     self.graph[other].add(k)
                     edges.append((k, other))
         self._local_map_of = None
-        return dict(n_pairs=len(got["keep_lid"]), n_rewritten=got["n_rewritten"], edges=edges)
+        out = dict(n_pairs=len(got["keep_lid"]), n_rewritten=got["n_rewritten"], edges=edges)
+        if self.loop_fusion_keyframes:
+            out["targets"] = list(new)
+        return out
 
     def neighbours(self, ref):
         """getNeighbourKeyframes (basic_map.cpp:209-237) on self.graph with deepLevel = local_map_depth, ascending; more than

@@ -45,6 +45,11 @@
 //                                    from MSLAM_ORB_VOCABULARY or ./orbvoc.dbow3) on the scene's first two entries, keep then
 //                                    drop: "fuse pairs N rewritten M", one "pair" line per pair, then every entry's landmark
 //                                    ids after the replacement
+//        mslam_harness <plugin.so> --fuse-multi <scene>
+//                                    IMultiLandmarkFuser::fuseLandmarksMulti of the relocalizer adapter on the scene's first
+//                                    entry (keep) and its targets, each under its own pose: "fuse-multi pairs N rewritten M",
+//                                    one "pair <target> <keep pos> <drop pos> <keep id> <drop id> <distance>" line per pair,
+//                                    then every entry's landmark ids after the replacement
 //        mslam_harness <plugin.so> --prune <scene>
 //                                    IObservationRemover::removeObservations of the relocalizer adapter on the scene's entries
 //                                    and rows: "prune removed N", one "row <p> <count>" line per row, then per entry
@@ -404,6 +409,100 @@ int main(int argc, char** argv)
             std::printf("fuse pairs %zu rewritten %d\n", fused.pairs.size(), fused.rewritten);
             for(const auto& p : fused.pairs)
                 std::printf("pair %d %d %lld %lld %d\n", p.keepPosition, p.dropPosition, static_cast<long long>(p.keepId),
+                            static_cast<long long>(p.dropId), p.distance);
+            for(std::size_t e = 0; e < entries.size(); ++e)
+            {
+                std::printf("entry %zu ids", e);
+                for(const std::int64_t id : localMap->landmarkIds(entries[e]))
+                    std::printf(" %lld", static_cast<long long>(id));
+                std::printf("\n");
+            }
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--fuse-multi") == 0)
+        {
+            // scene file: "MSFM", i32 version (1), width, height, max_distance, number of targets (1..64); f64 fx fy cx cy
+            // radius ratio max_world_distance; per target R (9 f64), t (3 f64); i32 number of entries (>= 1 + targets: keep,
+            // the targets, others); per entry i32 n (>= 1), n x 32 descriptor bytes, n x 3 f64 world points, n x i64 landmark ids
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[4] = {0, 0, 0, 0};
+            std::int32_t head[5] = {0, 0, 0, 0, 0}, nEntries = 0;
+            double par[7];
+            in.read(magic, 4);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            in.read(reinterpret_cast<char*>(par), sizeof(par));
+            if(!in || std::memcmp(magic, "MSFM", 4) != 0 || head[0] != 1 || head[4] < 1 || head[4] > 64)
+            {
+                std::fprintf(stderr, "%s is not a multi-target fusion scene\n", argv[3]);
+                return 5;
+            }
+            const std::size_t targets = static_cast<std::size_t>(head[4]);
+            std::vector<double> R(9 * targets), t(3 * targets);
+            for(std::size_t m = 0; m < targets; ++m)
+            {
+                in.read(reinterpret_cast<char*>(&R[9 * m]), 9 * sizeof(double));
+                in.read(reinterpret_cast<char*>(&t[3 * m]), 3 * sizeof(double));
+            }
+            in.read(reinterpret_cast<char*>(&nEntries), 4);
+            if(!in || nEntries < head[4] + 1)
+            {
+                std::fprintf(stderr, "%s is not a multi-target fusion scene\n", argv[3]);
+                return 5;
+            }
+            auto makeReloc = mslam::loadFactoryMethod<mslam::IOrbRelocalizer>(argv[1], "hipOrbRelocalizerFactory");
+            if(!makeReloc)
+                return 3;
+            std::unique_ptr<mslam::IOrbRelocalizer> relocalizer = makeReloc();
+            auto* fuser = dynamic_cast<mslam::IMultiLandmarkFuser*>(relocalizer.get());
+            auto* localMap = dynamic_cast<mslam::ILocalMapTracker*>(relocalizer.get());
+            if(!fuser || !localMap)
+            {
+                std::fprintf(stderr, "the plugin does not offer multi-target landmark fusion\n");
+                return 6;
+            }
+            using Kf = mslam::Keyframe<mslam::slam3d::SensorState>;
+            std::vector<std::shared_ptr<Kf>> entries;
+            for(std::int32_t e = 0; e < nEntries; ++e)
+            {
+                std::int32_t n = 0;
+                in.read(reinterpret_cast<char*>(&n), 4);
+                if(!in || n < 1 || n > 65535)
+                {
+                    std::fprintf(stderr, "entry %d of %s is malformed\n", e, argv[3]);
+                    return 5;
+                }
+                std::vector<mslam::OrbKeypoint> kps(static_cast<std::size_t>(n));
+                std::vector<mslam::Vector3> world(kps.size());
+                std::vector<std::int64_t> ids(kps.size());
+                for(std::size_t i = 0; i < kps.size(); ++i)
+                {
+                    kps[i].keypoint.id = i;
+                    in.read(reinterpret_cast<char*>(kps[i].descriptor.data()), 32);
+                }
+                for(auto& w : world)
+                    in.read(reinterpret_cast<char*>(w.v), sizeof(w.v));
+                in.read(reinterpret_cast<char*>(ids.data()), static_cast<std::streamsize>(ids.size() * 8));
+                if(!in)
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                    return 5;
+                }
+                auto kf = std::make_shared<Kf>();
+                kf->id = static_cast<mslam::Id>(100 + e);
+                relocalizer->addKeyframe(kf, kps);
+                localMap->addKeyframeLandmarksWithIds(kf, kps, world, ids);
+                entries.push_back(kf);
+            }
+            mslam::LandmarkFuseParams fp;
+            fp.camera.focal = mslam::Vector2(par[0], par[1]);
+            fp.camera.principalPoint = mslam::Vector2(par[2], par[3]);
+            fp.width = head[1], fp.height = head[2], fp.maxDistance = head[3];
+            fp.radius = par[4], fp.ratio = par[5], fp.maxWorldDistance = par[6];
+            const std::vector<std::shared_ptr<Kf>> drops(entries.begin() + 1, entries.begin() + 1 + static_cast<std::ptrdiff_t>(targets));
+            const mslam::MultiLandmarkFusion fused = fuser->fuseLandmarksMulti(entries[0], drops, R, t, fp);
+            std::printf("fuse-multi pairs %zu rewritten %d\n", fused.pairs.size(), fused.rewritten);
+            for(const auto& p : fused.pairs)
+                std::printf("pair %d %d %d %lld %lld %d\n", p.target, p.keepPosition, p.dropPosition, static_cast<long long>(p.keepId),
                             static_cast<long long>(p.dropId), p.distance);
             for(std::size_t e = 0; e < entries.size(); ++e)
             {

@@ -471,6 +471,48 @@ class BowDatabase
         return out;
     }
 
+    // ---- extension: landmark fusion into many keyframes (mslam_hip_kf_fuse_multi) ----
+    MultiLandmarkFusion fuseLandmarksMulti(const KeyframePtr& keepEntry, const std::vector<KeyframePtr>& dropEntries,
+                                           const std::vector<double>& R, const std::vector<double>& t, const LandmarkFuseParams& p)
+    {
+        const std::size_t targets = dropEntries.size();
+        if(R.size() != 9 * targets || t.size() != 3 * targets)
+            throw std::runtime_error("fuseLandmarksMulti: R and t do not hold one pose per target");
+        const int keep = storedLandmarksOf(keepEntry);
+        std::vector<std::int32_t> drops(targets + 1);
+        int cap = 0, nDropAll = 0;
+        int rc = mslam_hip_kf_read_ids(ctx.h, keep, nullptr, 0, &cap);
+        for(std::size_t m = 0; rc == MSLAM_HIP_OK && m < targets; ++m)
+        {
+            int n = 0;
+            drops[m] = storedLandmarksOf(dropEntries[m]);
+            rc = mslam_hip_kf_read_ids(ctx.h, drops[m], nullptr, 0, &n);
+            nDropAll += n;
+        }
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_read_ids", rc);
+        cap = std::min(cap, nDropAll); // one pair per keep id and per drop id at most
+        const std::size_t rows = static_cast<std::size_t>(cap) + 1;
+        std::vector<std::int32_t> target(rows), keepPos(rows), dropPos(rows), dist(rows);
+        std::vector<std::int64_t> keepId(rows), dropId(rows);
+        int n = 0;
+        MultiLandmarkFusion out;
+        rc = mslam_hip_kf_fuse_multi(ctx.h, keep, drops.data(), static_cast<int>(targets), R.data(), t.data(), p.camera.focal.x(),
+                                     p.camera.focal.y(), p.camera.principalPoint.x(), p.camera.principalPoint.y(), p.width, p.height,
+                                     p.radius, p.maxDistance, p.ratio, p.maxWorldDistance, target.data(), keepPos.data(), dropPos.data(),
+                                     keepId.data(), dropId.data(), dist.data(), cap, &n, &out.rewritten);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_kf_fuse_multi", rc);
+        for(int k = 0; k < n; ++k)
+        {
+            MultiFusedLandmarkPair pair;
+            pair.target = target[k], pair.keepPosition = keepPos[k], pair.dropPosition = dropPos[k];
+            pair.keepId = keepId[k], pair.dropId = dropId[k], pair.distance = dist[k];
+            out.pairs.push_back(pair);
+        }
+        return out;
+    }
+
     // ---- removeObservation's body (mslam_hip_kf_remove_observations) ----
     std::vector<int> removeObservations(const std::vector<std::pair<KeyframePtr, std::int64_t>>& observations)
     {
@@ -712,6 +754,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public IKeyframeTracker,
                           public ILocalMapTracker,
                           public ILandmarkFuser,
+                          public IMultiLandmarkFuser,
                           public IObservationRemover,
                           public IKeyframeCuller,
                           public ILandmarkCuller
@@ -771,6 +814,12 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                                  const double t[3], const LandmarkFuseParams& params) override
     {
         return db->fuseLandmarks(keepEntry, dropEntry, R, t, params);
+    }
+    MultiLandmarkFusion fuseLandmarksMulti(BowDatabase::KeyframePtr keepEntry, const std::vector<BowDatabase::KeyframePtr>& dropEntries,
+                                           const std::vector<double>& R, const std::vector<double>& t,
+                                           const LandmarkFuseParams& params) override
+    {
+        return db->fuseLandmarksMulti(keepEntry, dropEntries, R, t, params);
     }
     std::vector<int> removeObservations(const std::vector<std::pair<BowDatabase::KeyframePtr, std::int64_t>>& observations) override
     {

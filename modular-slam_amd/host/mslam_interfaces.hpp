@@ -432,6 +432,34 @@ class ILandmarkFuser
     virtual ~ILandmarkFuser() = default;
 };
 
+// ---- extension: landmark fusion into many keyframes in one call (mslam_hip_kf_fuse_multi) ----------------------------------
+// SearchAndFuse's loop over the keyframes connected to the current one.  Every entry of `dropEntries` (1..64, distinct, none
+// of them keepEntry) is a target under its own world -> camera pose R + 9 m, t + 3 m; what the targets find is resolved on
+// landmark ids, so that every drop id is replaced by one keep id and every keep id replaces one drop id.  A separate
+// interface: ILandmarkFuser stays as it is for the code that implements it.
+struct MultiFusedLandmarkPair
+{
+    int target = 0;                         // position in dropEntries
+    int keepPosition = 0, dropPosition = 0; // inside the keep entry and that target
+    std::int64_t keepId = 0, dropId = 0;
+    int distance = 0;
+};
+struct MultiLandmarkFusion
+{
+    std::vector<MultiFusedLandmarkPair> pairs; // ordered by (target, keepPosition)
+    int rewritten = 0;                         // store landmarks whose id was replaced
+};
+class IMultiLandmarkFuser
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual MultiLandmarkFusion fuseLandmarksMulti(KeyframePtr keepEntry, const std::vector<KeyframePtr>& dropEntries,
+                                                   const std::vector<double>& R /* 9 per target */,
+                                                   const std::vector<double>& t /* 3 per target */,
+                                                   const LandmarkFuseParams& params) = 0;
+    virtual ~IMultiLandmarkFuser() = default;
+};
+
 // ---- RgbdFeatureFrontend::removeObservation (rgbd_feature_frontend.cpp:469-487; mslam_hip_kf_remove_observations) ----------
 // The body the reference leaves commented out: update(const BackendOutputType&) calls it for every outlier observation of a
 // bundle adjustment (:224-230).  Observation p names a stored keyframe and a landmark id; every position of that keyframe's
