@@ -743,6 +743,34 @@ int mslam_hip_kf_covisible(mslam_hip_ctx* ctx, int id, const int32_t* ids, int n
 int mslam_hip_kf_union_dev(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */);
 int mslam_hip_kf_union(mslam_hip_ctx* ctx, int dst_id, const int32_t* ids, int n_ids /* 1..64 */, int* n_out /* may be NULL */);
 
+/* ---- Which descriptor a union row carries (AN EXTENSION: the reference matches against the most recent observation) ----
+ * Context state, the idiom of mslam_hip_set_guided_match and mslam_hip_set_ba_loss: mslam_hip_kf_union and
+ * mslam_hip_kf_union_dev read it when they are called.  RECENT is the default: both then launch what they launched before
+ * this setting existed, and every result keeps its bits.  The model of DISTINCTIVE is ORB-SLAM's
+ * MapPoint::ComputeDistinctiveDescriptors.  For every distinct landmark id L of the listed entries:
+ *   observations   O(L) = one observation per listed entry that holds L; an entry that holds L more than once counts at its
+ *                  highest position (the union's own rule inside an entry), so N = |O(L)| <= 64;
+ *   distance       d(a, b) = popcount of the xor over the 256 bits, 0 .. 256;
+ *   median         of a in O(L): the N values d(a, b), b in O(L), d(a, a) = 0 included, sorted ascending; median(a) =
+ *                  row[(N - 1) / 2] (integer division: ORB-SLAM's vDists[0.5 * (N - 1)]);
+ *   choice         the observation of the least median; of equal medians the one from the entry with the largest keyframe id.
+ *                  For N <= 2 every median is 0, so the choice is the most recent observation: those rows keep RECENT's bytes;
+ *   result         rows, order, world points, landmark ids, count, *n_out, MSLAM_HIP_E_CAPACITY, the _dev form's flag and the
+ *                  creation serial are those of RECENT.  Only the 32 descriptor bytes of a row may differ: they are the chosen
+ *                  observation's, bit for bit.  The listed entries are not written: every observation stays what it was.
+ * Three more launches and one more clear follow the union's own, on the same stream, nothing uploaded, whatever n_ids is
+ * (none at all for n_ids <= 2).  No result depends on the order of atomics.
+ * set returns MSLAM_HIP_E_INVALID for a mode outside 0..1 and leaves the setting alone.  get: mode may be NULL.
+ *   observations   DEVIATES: ORB-SLAM takes every observation of the map point; here one per listed entry, of the listed
+ *                  entries only;
+ *   ties           DEVIATES: ORB-SLAM keeps the first least median in the iteration order of a map keyed by pointers
+ *                  (unspecified); here the largest keyframe id;
+ *   what follows   DEVIATES: no UpdateNormalAndDepth, and the choice is not written back into the keyframes' entries. */
+#define MSLAM_HIP_UNION_DESC_RECENT 0
+#define MSLAM_HIP_UNION_DESC_DISTINCTIVE 1
+int mslam_hip_set_union_descriptor(mslam_hip_ctx* ctx, int mode);
+int mslam_hip_get_union_descriptor(mslam_hip_ctx* ctx, int* mode);
+
 /* ---- landmark fusion: one identity for the duplicates a loop closure leaves ------------------------------------------
  * AN EXTENSION, NOT A RESTATEMENT: the reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580) and
  * nothing in it merges landmarks.  The model is ORB-SLAM's SearchAndFuse: project the landmarks of the old side of a loop

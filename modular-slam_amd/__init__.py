@@ -34,6 +34,8 @@ POSE_GRAPH_MAX_KEYFRAMES, POSE_GRAPH_MAX_EDGES = 1024, 65536    # mslam_hip_pose
 CULL_MAX_ENTRIES = 4096    # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss's kinds
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
+UNION_DESC_RECENT, UNION_DESC_DISTINCTIVE = 0, 1    # mslam_hip_set_union_descriptor's modes
+_UNION_DESC_NAMES = {"recent": UNION_DESC_RECENT, "distinctive": UNION_DESC_DISTINCTIVE}
 
 # every symbol include/mslam_hip.h declares (tests/test_cabi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -63,6 +65,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_observers", "mslam_hip_kf_cull_search", "mslam_hip_kf_cull",
     "mslam_hip_kf_remove_landmarks", "mslam_hip_kf_cull_landmarks_search", "mslam_hip_kf_cull_landmarks",
     "mslam_hip_set_ba_loss", "mslam_hip_get_ba_loss",
+    "mslam_hip_set_union_descriptor", "mslam_hip_get_union_descriptor",
 ]
 
 
@@ -342,6 +345,24 @@ class Context:
         r, d, w, h = C.c_double(0), C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self.L.mslam_hip_get_guided_match(self._h, C.byref(r), C.byref(d), C.byref(w), C.byref(h)))
         return r.value, d.value, w.value, h.value
+
+    def set_union_descriptor(self, mode):
+        """Which descriptor a row of kf_union carries.  "recent" (UNION_DESC_RECENT, the default and the reference's rule):
+        the most recent observation's.  "distinctive" (UNION_DESC_DISTINCTIVE, an extension after ORB-SLAM's
+        ComputeDistinctiveDescriptors): among the landmark's observations in the listed entries, one per entry, the one
+        with the least median Hamming distance to all of them; ties go to the largest keyframe id.  Rows, order, world
+        points, ids, counts and serials do not depend on the mode."""
+        if isinstance(mode, str):
+            if mode not in _UNION_DESC_NAMES:
+                raise MslamHipError(E_INVALID, "set_union_descriptor: mode %r is not recent / distinctive" % mode)
+            mode = _UNION_DESC_NAMES[mode]
+        self._chk(self.L.mslam_hip_set_union_descriptor(self._h, int(mode)))
+
+    def get_union_descriptor(self):
+        """-> UNION_DESC_RECENT or UNION_DESC_DISTINCTIVE"""
+        m = C.c_int(0)
+        self._chk(self.L.mslam_hip_get_union_descriptor(self._h, C.byref(m)))
+        return m.value
 
     # ---- RGB-D back-projection (rgbd_feature_frontend.cpp:101-138) ------------------------------
     def backproject(self, depth, xy, factor=1.0 / 5000.0, focal=(525.0, 525.0), principal=(319.5, 239.5)):
@@ -1725,7 +1746,10 @@ class HipKeyframeTracker:
     listed entries, which makes them harmless.  One union is built instead of two, so later serials differ from a run
     without the option.  The attempt's fusion dict gains targets.  Off (the default): the fusion step makes exactly the
     calls described above.
-    STILL OUT: old-side landmarks that no new-side keyframe sees stay unfused, and the descriptors of a pair are not merged.
+    The keep and drop unions are Context.kf_union calls, so they follow the context's union descriptor mode (below).
+    STILL OUT: old-side landmarks that no new-side keyframe sees stay unfused.  The descriptors of a fused pair are not
+    merged in the store: every keyframe's entry keeps the observation it made.  With union_descriptor = "distinctive" the
+    unions built afterwards choose among the observations of both sides, which now share one id; nothing is written back.
 
     ba_prune = True (needs local_ba, else MslamHipError(E_INVALID)): the consumer of the backend's outlier mask,
     RgbdFeatureFrontend::update(const BackendOutputType&) (rgbd_feature_frontend.cpp:224-230) with the removeObservation
@@ -1762,6 +1786,16 @@ class HipKeyframeTracker:
     n_redundant, bridges.  Off by default: nothing is removed.  STILL OUT: ORB-SLAM's scale condition (the store keeps no
     octave).
 
+    union_descriptor = "distinctive" (needs local_map_depth, else MslamHipError(E_INVALID); an extension, the reference
+    matches against the most recent observation; the model is ORB-SLAM's MapPoint::ComputeDistinctiveDescriptors):
+    Context.set_union_descriptor at construction, so every union built on the context from then on — the local map, and
+    the keep and drop unions of loop_fusion — carries, for a landmark observed in three or more of the listed keyframes,
+    the descriptor with the least median Hamming distance to the landmark's other observations (one per listed keyframe;
+    ties: the largest keyframe id) instead of the most recent one.  Rows, order, points, ids and serials are unchanged.
+    "recent" sets the reference's rule; None (the default) leaves the context's mode alone.  DEVIATES from ORB-SLAM: one
+    observation per listed keyframe, the tie rule, no UpdateNormalAndDepth, no write-back into the keyframes.  NOT
+    MEASURED: whether the trajectory improves on any sequence.
+
     lm_cull = True (needs no other option; an extension, the reference has no such step; the model is ORB-SLAM's
     MapPointCulling, run before KeyFrameCulling as there): at every keyframe insertion, on both paths, after the covisibility
     edges, local BA, pruning and the loop closure and before kf_cull's step.  Part B of every new keyframe gives a fresh id
@@ -1785,8 +1819,13 @@ class HipKeyframeTracker:
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
-                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False):
+                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None):
         self.ctx = ctx
+        if union_descriptor is not None:
+            if local_map_depth is None:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: union_descriptor needs local_map_depth (the union it applies to)")
+            if union_descriptor not in _UNION_DESC_NAMES and union_descriptor not in _UNION_DESC_NAMES.values():
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: union_descriptor %r is not recent / distinctive" % (union_descriptor,))
         if ba_loss is not None and not local_ba:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_loss needs local_ba (the backend's solves take the loss)")
         self.ba_loss = None if ba_loss is None else (ba_loss[0], float(ba_loss[1]))
@@ -1830,6 +1869,8 @@ class HipKeyframeTracker:
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)
+        if union_descriptor is not None:
+            ctx.set_union_descriptor(union_descriptor)
         self.local_map_depth = local_map_depth
         self.graph = {}            # covisibility: id -> set of ids
         self.local_map = []        # the entries the current union lists

@@ -117,6 +117,8 @@ struct mslam_hip_ctx
     // mslam_hip_set_guided_match: radius > 0 = the match-to-PnP sequence takes the guided stage when the call has a guess
     double guided_radius = 0.0;
     int guided_max_distance = 256, guided_width = 0, guided_height = 0;
+    // mslam_hip_set_union_descriptor: read by mslam_hip_kf_union[_dev] when they are called
+    int union_descriptor = MSLAM_HIP_UNION_DESC_RECENT;
     int n_last = 0;         // frames in the last detect batch
     unsigned long long detect_seq = 0; // counts detect batches; points_seq = the batch the back-projected points belong to
     unsigned long long points_seq = ~0ull;

@@ -20,6 +20,18 @@
 // The union's result order is by list position, then landmark position: the grid is laid out that way (blockIdx.y = list
 // position), winners are counted per block, one workgroup scans the block counts, and the scatter places every winner
 // at its block's offset plus its ballot / popcount prefix, as k_kf_lift does inside one block.
+//
+// mslam_hip_set_union_descriptor(DISTINCTIVE) (an extension: the reference matches against the most recent observation)
+// enqueues three more launches behind the scatter, which leave rows, order, points and ids alone and may replace a row's 32
+// descriptor bytes by those of another observation of its landmark — the one with the least median Hamming distance to all
+// of them (ORB-SLAM's MapPoint::ComputeDistinctiveDescriptors; distinct.hpp has the rule):
+//   k_lm_place     every winner writes its output row into its bucket (one writer per bucket; ~pack is dead after the select);
+//   k_lm_observe   the insert's grid: thread (k, i) raises obs[row][k] to i + 1 with atomicMax — one observation per listed
+//                  entry, its highest position, whatever the order;
+//   k_lm_distinct  one wave per row, lane k = the observation of list position k: all-pairs distances through a per-wave
+//                  LDS block, each lane's median by bisection, the wave's minimum of (median, 63 - rank), and the winning
+//                  lane overwrites the row's descriptor.  Rows of one or two observations keep the scatter's bytes.
+#include "distinct.hpp"
 #include "lm_table.hpp"
 #include "reloc.hpp"
 
@@ -160,6 +172,109 @@ __global__ __launch_bounds__(256) void k_lm_scatter(const uint8_t* __restrict__ 
     copy_desc(store_desc + src * 32, out_desc + o * 32);
     out_world[o * 3] = store_world[src * 3], out_world[o * 3 + 1] = store_world[src * 3 + 1], out_world[o * 3 + 2] = store_world[src * 3 + 2];
     out_lid[o] = store_lid[src];
+}
+
+// ---- the DISTINCTIVE descriptor mode: three launches behind k_lm_scatter
+
+// k_lm_scatter's grid and row arithmetic: every winner leaves its output row o in the bucket of its landmark id.  `cap` is
+// the number of rows the observation table has (<= K): nothing is written when the union does not fit.
+__global__ __launch_bounds__(256) void k_lm_place(const int64_t* __restrict__ store_lid, LmList list, int K, LmTable t,
+                                                  const unsigned long long* __restrict__ win, const uint32_t* __restrict__ ofs, int nb,
+                                                  int cap)
+{
+    if(ofs[nb] > (uint32_t)cap)
+        return;
+    const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = blockIdx.x * 256 + tid;
+    const size_t blk = (size_t)k * gridDim.x + blockIdx.x;
+    const unsigned long long mine = win[blk * 4 + wave];
+    if(!((mine >> lane) & 1ull))
+        return;
+    uint32_t pre = 0;
+    for(int w = 0; w < wave; ++w)
+        pre += (uint32_t)__popcll(win[blk * 4 + w]);
+    const uint32_t o = ofs[blk] + pre + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
+    const long long b = lm_find(t, (unsigned long long)store_lid[(size_t)list.slot[k] * K + i]);
+    if(b >= 0)
+        t.b[b].val = (unsigned long long)o; // the one winner of this id: a plain store
+}
+
+// k_lm_insert's grid: obs[o][k] = 1 + the highest position at which entry k holds the landmark of row o (0: it does not)
+__global__ __launch_bounds__(256) void k_lm_observe(const int64_t* __restrict__ store_lid, const int32_t* __restrict__ store_n, LmList list,
+                                                    int K, LmTable t, const uint32_t* __restrict__ ofs, int nb, int cap,
+                                                    uint32_t* __restrict__ obs)
+{
+    if(ofs[nb] > (uint32_t)cap)
+        return;
+    const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int slot = list.slot[k];
+    if(i >= entry_count(store_n, slot, K))
+        return;
+    const long long b = lm_find(t, (unsigned long long)store_lid[(size_t)slot * K + i]);
+    if(b < 0)
+        return;
+    const unsigned long long o = t.b[b].val;
+    if(o < (unsigned long long)ofs[nb]) // (every key has a winner, which placed its row: always)
+        atomicMax(&obs[o * kRelocMaxCand + k], (uint32_t)i + 1u);
+}
+
+// One wave per union row, four rows per block.  The list's slots and ranks are wanted per lane: thread 0 stages them in LDS
+// from the by-value argument with uniform indices (a lane-indexed read of the argument would go through scratch).
+__global__ __launch_bounds__(256) void k_lm_distinct(const uint8_t* __restrict__ store_desc, LmList list, int n_ids, int K,
+                                                     const uint32_t* __restrict__ ofs, int nb, int cap,
+                                                     const uint32_t* __restrict__ obs, uint8_t* __restrict__ out_desc)
+{
+    __shared__ int32_t s_slot[kRelocMaxCand], s_rank[kRelocMaxCand];
+    __shared__ uint16_t s_dist[4][kRelocMaxCand][64]; // [wave][column c][lane]: lane-contiguous, no bank conflicts
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if(tid == 0)
+    {
+#pragma unroll
+        for(int k = 0; k < kRelocMaxCand; ++k)
+            s_slot[k] = list.slot[k], s_rank[k] = list.rank[k];
+    }
+    __syncthreads();
+    const uint32_t total = ofs[nb];
+    const uint32_t o = blockIdx.x * 4u + (uint32_t)wave;
+    if(total > (uint32_t)cap || o >= total)
+        return;
+    const uint32_t p = lane < n_ids ? obs[(size_t)o * kRelocMaxCand + lane] : 0u;
+    const bool present = p > 0u && p <= (uint32_t)K;
+    const unsigned long long bal = __ballot(present);
+    const int N = __popcll(bal);
+    if(N <= 2)
+        return; // the most recent observation is the choice, and the scatter wrote it
+    uint32_t d[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if(present)
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(store_desc + ((size_t)s_slot[lane] * K + (p - 1u)) * 32);
+        const uint4 a = src[0], b = src[1];
+        d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w, d[4] = b.x, d[5] = b.y, d[6] = b.z, d[7] = b.w;
+    }
+    // column c of every lane's row: the distance to the c-th present lane (wave-uniform loop)
+    int c = 0;
+    for(unsigned long long rest = bal; rest; rest &= rest - 1ull, ++c)
+    {
+        const int j = __ffsll((long long)rest) - 1;
+        uint32_t e[8];
+#pragma unroll
+        for(int w = 0; w < 8; ++w)
+            e[w] = (uint32_t)__builtin_amdgcn_readlane((int)d[w], j);
+        s_dist[wave][c][lane] = (uint16_t)distinct_distance(d, e);
+    }
+    // (each lane reads back what it wrote itself: no barrier)
+    uint32_t key = kDistinctAbsent;
+    if(present)
+        key = distinct_key(distinct_mth_smallest(&s_dist[wave][0][lane], 64, N, (N - 1) / 2), s_rank[lane]);
+    uint32_t best = key;
+#pragma unroll
+    for(int s = 32; s > 0; s >>= 1)
+        best = min(best, (uint32_t)__shfl_xor((int)best, s));
+    if(present && key == best)
+    {
+        uint4* dst = reinterpret_cast<uint4*>(out_desc + (size_t)o * 32);
+        dst[0] = make_uint4(d[0], d[1], d[2], d[3]);
+        dst[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    }
 }
 
 // One workgroup per listed entry k, over a table built from entry `id` with empty masks: a landmark id the table holds
@@ -347,6 +462,7 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
         return fail(c, MSLAM_HIP_E_INVALID, std::string(who) + ": bad argument (1 to 64 ids)");
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints;
+    hipStream_t s = c->stream;
     LmList list{};
     size_t keys = 0;
     int n_max = 0;
@@ -374,13 +490,18 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
     rc = lm_scratch(c, keys, nb, &table);
     if(rc)
         return rc;
+    // DISTINCTIVE: the observation table, one row of 64 words per union row there can be.  A landmark has at most one
+    // observation per listed entry, so with one or two entries every choice is the most recent one: nothing more runs.
+    const size_t obs_rows = std::min(keys, (size_t)K);
+    const bool distinct = c->union_descriptor == MSLAM_HIP_UNION_DESC_DISTINCTIVE && n_ids > 2 && obs_rows > 0;
+    if(distinct)
+        MSLAM_CHK(c, grow(r->d_lm_obs, obs_rows * kRelocMaxCand, s));
     // the store grows here, on the host, before anything is enqueued (slots keep their numbers)
     rc = store_slot_for(c, dst_id, dst_slot);
     if(rc)
         return rc;
     (void)store_next_lid_base(c); // a new serial for the entry; its landmarks keep the ids they have
     const size_t slot = (size_t)*dst_slot;
-    hipStream_t s = c->stream;
     unsigned long long* win = reinterpret_cast<unsigned long long*>(r->d_lm_blocks.get());
     const size_t cap_blocks = lm_blocks_cap(r->d_lm_blocks.size());
     uint32_t* cnt = reinterpret_cast<uint32_t*>(r->d_lm_blocks + cap_blocks * 32);
@@ -408,12 +529,52 @@ static int union_enqueue(mslam_hip_ctx* c, const char* who, int dst_id, const in
         hipLaunchKernelGGL(k_lm_scatter, grid, dim3(256), 0, s, r->d_desc, r->d_world, r->d_lid, list, K, win, ofs, (int)nb,
                            r->d_desc + slot * K * 32, r->d_world + slot * K * 3, r->d_lid + slot * K);
     }
+    if(distinct)
+    {
+        uint32_t* obs = r->d_lm_obs.get();
+        {
+            StageScope ts(c, "union_obs_clear");
+            MSLAM_CHK(c, hipMemsetAsync(obs, 0, obs_rows * kRelocMaxCand * sizeof(uint32_t), s));
+        }
+        {
+            StageScope ts(c, "union_place");
+            hipLaunchKernelGGL(k_lm_place, grid, dim3(256), 0, s, r->d_lid, list, K, table, win, ofs, (int)nb, (int)obs_rows);
+        }
+        {
+            StageScope ts(c, "union_observe");
+            hipLaunchKernelGGL(k_lm_observe, grid, dim3(256), 0, s, r->d_lid, r->d_n, list, K, table, ofs, (int)nb, (int)obs_rows, obs);
+        }
+        {
+            StageScope ts(c, "union_distinct");
+            hipLaunchKernelGGL(k_lm_distinct, dim3((unsigned)((obs_rows + 3) / 4)), dim3(256), 0, s, r->d_desc, list, n_ids, K, ofs, (int)nb,
+                               (int)obs_rows, obs, r->d_desc + slot * K * 32);
+        }
+    }
     MSLAM_CHK(c, hipGetLastError());
     r->n_upper[slot] = (int)std::min(keys, (size_t)K); // (the count stays on the device)
     return MSLAM_HIP_OK;
 }
 
 extern "C" {
+
+int mslam_hip_set_union_descriptor(mslam_hip_ctx* c, int mode)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(mode != MSLAM_HIP_UNION_DESC_RECENT && mode != MSLAM_HIP_UNION_DESC_DISTINCTIVE)
+        return fail(c, MSLAM_HIP_E_INVALID, "set_union_descriptor: mode outside 0..1");
+    c->union_descriptor = mode;
+    return MSLAM_HIP_OK;
+}
+
+int mslam_hip_get_union_descriptor(mslam_hip_ctx* c, int* mode)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(mode)
+        *mode = c->union_descriptor;
+    return MSLAM_HIP_OK;
+}
 
 int mslam_hip_kf_union_dev(mslam_hip_ctx* c, int dst_id, const int32_t* ids, int n_ids)
 {

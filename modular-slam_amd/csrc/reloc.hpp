@@ -79,6 +79,9 @@ struct RelocState
     // [win masks | counts | offsets], and the mapped result [needed count, pad | covisibility counts 64 x i32]
     DevBuf<uint8_t> d_lm_blocks;
     PinnedBuf<uint8_t> h_lm;
+    // ---- the observation table of a union in DISTINCTIVE descriptor mode (mslam_hip_set_union_descriptor), grown on demand:
+    // [union row][list position] = 1 + the highest position at which that listed entry holds the row's landmark, 0: nowhere
+    DevBuf<uint32_t> d_lm_obs;
     // ---- scratch of keyframe culling (k_cull.hip), grown on demand: [observer counts, one u32 per table bucket |
     // first-position stamps, one u32 per bucket | the bucket of every position of one entry, max_keypoints x u32].  Landmark
     // culling (k_lmcull.hip) uses the counts as they are (or as per-bucket hit counts) and the stamps as its judged flags

@@ -29,6 +29,9 @@
 //        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> [--local-map <depth>] --guided <radius>
 //                                    either loop with IKeyframeTracker::setGuidedMatch(radius): every tracking call matches each
 //                                    landmark within <radius> px of its projection under the previous pose
+//        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> --local-map <depth> --distinct
+//                                    the local-map loop with IDistinctiveLocalMap::setUnionDescriptor(1): every landmark of the
+//                                    local map carries its most distinctive descriptor instead of the most recent one
 //        mslam_harness <plugin.so> --ba <scene>
 //        mslam_harness <plugin.so> --ba-global <scene>
 //                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
@@ -837,16 +840,19 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        // --track <vocabulary> <scene> followed by any of: --local-map <depth>, --guided <radius>
-        bool trackArgs = argc >= 5 && (argc - 5) % 2 == 0 && std::strcmp(argv[2], "--track") == 0;
+        // --track <vocabulary> <scene> followed by any of: --local-map <depth>, --guided <radius>, --distinct
+        bool trackArgs = argc >= 5 && std::strcmp(argv[2], "--track") == 0;
         int mapDepthArg = -1;
         double guidedRadius = 0.0;
-        for(int k = 5; trackArgs && k + 1 < argc; k += 2)
+        bool distinct = false;
+        for(int k = 5; trackArgs && k < argc;)
         {
-            if(std::strcmp(argv[k], "--local-map") == 0)
-                mapDepthArg = std::atoi(argv[k + 1]);
-            else if(std::strcmp(argv[k], "--guided") == 0)
-                guidedRadius = std::atof(argv[k + 1]);
+            if(std::strcmp(argv[k], "--distinct") == 0)
+                distinct = true, k += 1;
+            else if(k + 1 < argc && std::strcmp(argv[k], "--local-map") == 0)
+                mapDepthArg = std::atoi(argv[k + 1]), k += 2;
+            else if(k + 1 < argc && std::strcmp(argv[k], "--guided") == 0)
+                guidedRadius = std::atof(argv[k + 1]), k += 2;
             else
                 trackArgs = false;
         }
@@ -871,6 +877,17 @@ int main(int argc, char** argv)
             }
             if(guidedRadius > 0.0)
                 tracker->setGuidedMatch(guidedRadius);
+            if(distinct)
+            {
+                // --distinct (needs --local-map): the local map carries the most distinctive descriptor of every landmark
+                auto* distinctive = dynamic_cast<mslam::IDistinctiveLocalMap*>(relocalizer.get());
+                if(!distinctive || mapDepth < 0)
+                {
+                    std::fprintf(stderr, "--distinct needs --local-map and a plugin that offers IDistinctiveLocalMap\n");
+                    return 6;
+                }
+                distinctive->setUnionDescriptor(1);
+            }
             std::ifstream in(argv[4], std::ios::binary);
             char magic[4] = {0, 0, 0, 0};
             std::int32_t head[4] = {0, 0, 0, 0}, par[3] = {0, 0, 0};

@@ -422,7 +422,10 @@ class BowDatabase
         for(std::size_t k = 0; k < members.size(); ++k)
             ids[k] = storedLandmarksOf(members[k]);
         int n = 0;
-        const int rc = mslam_hip_kf_union(ctx.h, kLocalMapId, ids.data(), static_cast<int>(members.size()), &n);
+        int rc = mslam_hip_set_union_descriptor(ctx.h, unionDescriptor);
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_union_descriptor", rc);
+        rc = mslam_hip_kf_union(ctx.h, kLocalMapId, ids.data(), static_cast<int>(members.size()), &n);
         if(rc != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_kf_union", rc);
         haveLocalMap = true;
@@ -670,6 +673,13 @@ class BowDatabase
         guidedMaxDistance = maxDistance;
     }
 
+    void setUnionDescriptor(int mode)
+    {
+        if(mode != MSLAM_HIP_UNION_DESC_RECENT && mode != MSLAM_HIP_UNION_DESC_DISTINCTIVE)
+            throw std::invalid_argument("setUnionDescriptor: the mode is neither 0 (recent) nor 1 (distinctive)");
+        unionDescriptor = mode;
+    }
+
   private:
     // descriptors into `desc`, coordinates (as float, what the detector produced) into `xy`
     void gather(const std::vector<OrbKeypoint>& keypoints)
@@ -744,6 +754,7 @@ class BowDatabase
     double guidedRadius = 0.0; // setGuidedMatch; applied to the context by the next tracking call, with that call's frame size
     int guidedMaxDistance = 256;
     bool guidedSet = false;    // the context's mode is on
+    int unionDescriptor = MSLAM_HIP_UNION_DESC_RECENT; // setUnionDescriptor; applied to the context by every buildLocalMap
     std::vector<float> xy;
     KeyframePtr lastLoop;
     std::vector<OrbKeypoint> lastFed;
@@ -753,6 +764,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public IVerifiedRelocalizer,
                           public IKeyframeTracker,
                           public ILocalMapTracker,
+                          public IDistinctiveLocalMap,
                           public ILandmarkFuser,
                           public IMultiLandmarkFuser,
                           public IObservationRemover,
@@ -810,6 +822,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
         return db->covisibleLandmarks(keyframe, others);
     }
     int buildLocalMap(const std::vector<BowDatabase::KeyframePtr>& members) override { return db->buildLocalMap(members); }
+    void setUnionDescriptor(int mode) override { db->setUnionDescriptor(mode); }
     LandmarkFusion fuseLandmarks(BowDatabase::KeyframePtr keepEntry, BowDatabase::KeyframePtr dropEntry, const double R[9],
                                  const double t[3], const LandmarkFuseParams& params) override
     {

@@ -396,6 +396,18 @@ class ILocalMapTracker
                                               const KeyframeTrackOptions& options = KeyframeTrackOptions()) = 0;
     virtual ~ILocalMapTracker() = default;
 };
+// ---- extension (not in the reference): the most distinctive descriptor per landmark of the local map ----------------------
+// (mslam_hip_set_union_descriptor; the model is ORB-SLAM's MapPoint::ComputeDistinctiveDescriptors).  mode 0 (the default):
+// every landmark of buildLocalMap carries the descriptor of its most recent observation, the reference's rule.  mode 1: of
+// its observations among the members, one per member, the one with the least median Hamming distance to all of them; ties
+// go to the member stored last.  Landmarks, their order, points and ids do not depend on the mode.  It applies to every
+// buildLocalMap after the call.  An interface of its own, reached with dynamic_cast: ILocalMapTracker gains no virtual.
+class IDistinctiveLocalMap
+{
+  public:
+    virtual void setUnionDescriptor(int mode) = 0;
+    virtual ~IDistinctiveLocalMap() = default;
+};
 
 // ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
 // The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
