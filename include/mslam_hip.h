@@ -615,7 +615,7 @@ int mslam_hip_get_ba_loss(mslam_hip_ctx* ctx, int* kind, double* scale);
  * measurement or a pose entered with the other sign turns 2 vec(delta) round (delta is then near (0, 0, 0, -1)); the solve
  * still reaches the same poses, with the quaternion's sign kept, because the rotation error enters squared.
  *   poses      K x 7 (qx qy qz qw px py pz, camera -> world; mslam_hip_bundle_adjust's layout), K in
- *              0..MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES, in: start, out: result; fixed[k] != 0 holds pose k constant; NULL: none;
+ *              0..MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES (0..MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE with the SPARSE solver), in: start, out: result; fixed[k] != 0 holds pose k constant; NULL: none;
  *   edge_a, edge_b   E edges, E in 0..MSLAM_HIP_POSE_GRAPH_MAX_EDGES, indices into poses; duplicates and both directions
  *              between one pair are allowed;
  *   edge_meas  E x 7: q then p of pose b expressed in a's frame (T_a^-1 T_b);
@@ -637,22 +637,59 @@ int mslam_hip_get_ba_loss(mslam_hip_ctx* ctx, int* kind, double* scale);
  *                            poses in edge order, costs by a fixed two-stage tree; not Ceres's evaluation order.  The sum of a
  *                            pair is one wave's serial loop over the pair's edges: bounded by E, and the slow shape when
  *                            many duplicate edges join one pair (65536 between two poses is one loop of 65536 steps);
- *   linear solver            DEVIATES in rounding: the damped normal equations J^T J + D^2 over the free poses, dense, by
- *                            mslam_hip_bundle_adjust_global's blocked Cholesky (the same kernels) at every K; the example
- *                            asks for SPARSE_NORMAL_CHOLESKY.  A non-positive pivot or a non-finite step is an invalid step;
+ *   linear solver            DEVIATES in rounding: the damped normal equations J^T J + D^2 over the free poses.  DENSE (the
+ *                            default): dense, by mslam_hip_bundle_adjust_global's blocked Cholesky (the same kernels) at
+ *                            every K.  SPARSE (mslam_hip_set_pose_graph_solver below): a Cholesky factor on the block
+ *                            envelope after a NATURAL or reverse Cuthill-McKee order, the shape of the example's
+ *                            SPARSE_NORMAL_CHOLESKY, though not its ordering (AMD) or its supernodal factor; the diagonal's
+ *                            reciprocal is multiplied with where DENSE divides.  In both a pivot that is not > 0 (SPARSE:
+ *                            or not finite) or a non-finite step is an invalid step;
  *   Jacobi scaling, trust region, termination order, FAILURE result
  *                            those of mslam_hip_bundle_adjust (SAME / DEVIATES as stated there); termination is judged on
  *                            the ambient parameters (7 per pose) of the free poses that have an edge;
- *   sizes                    DEVIATES: at most 1024 poses and 65536 edges per solve.  The reduced system is the DENSE 6 K x 6 K
- *                            matrix of the free poses (6144^2 doubles = 302 MB at the bound, the buffer global bundle
- *                            adjustment uses; no second one is allocated), although a pose graph's normal equations are sparse
- *                            (a chain's are block-tridiagonal): a sparse factor is out of scope here.  The per-edge blocks
- *                            (residual, two Jacobians, measurement, sqrt_info: 121 doubles) take 63 MB at the edge bound. */
+ *   sizes                    DEVIATES: at most 65536 edges per solve and, with DENSE, 1024 poses: the reduced system is then the
+ *                            dense 6 K x 6 K matrix of the free poses (6144^2 doubles = 302 MB at the bound, the buffer global
+ *                            bundle adjustment uses; no second one is allocated), although a pose graph's normal equations are
+ *                            sparse (a chain's are block-tridiagonal).  With SPARSE at most 16384 poses and an envelope of
+ *                            1048576 blocks (288 MiB, in the same buffer).  The per-edge blocks (residual, two Jacobians,
+ *                            measurement, sqrt_info: 121 doubles) take 63 MB at the edge bound. */
 #define MSLAM_HIP_POSE_GRAPH_MAX_EDGES 65536
 int mslam_hip_pose_graph(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out */, const uint8_t* fixed /* K, or NULL */,
-                         int K /* 0..1024 */, const int32_t* edge_a, const int32_t* edge_b, const double* edge_meas /* E x 7 */,
+                         int K /* 0..1024; SPARSE: 0..16384 */, const int32_t* edge_a, const int32_t* edge_b, const double* edge_meas /* E x 7 */,
                          const double* sqrt_info /* E x 36, or NULL */, int E, int max_iterations /* 100 */,
                          mslam_hip_ba_summary* summary /* may be NULL */);
+/* ---- The linear solver of mslam_hip_pose_graph (an extension) ----
+ * Context state, the idiom of mslam_hip_set_ba_loss and mslam_hip_set_guided_match: mslam_hip_pose_graph reads it when it is
+ * called.  DENSE is the default: every launch and every result bit is what it was before this setting existed, and K > 1024
+ * is MSLAM_HIP_E_INVALID.  With SPARSE K may reach MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE and the linear solve of an
+ * iteration is a Cholesky factor on the block envelope (skyline) of the damped normal equations in 6 x 6 blocks; memory and
+ * work follow the envelope, not K^2.  Everything else of the solve (blocks, step, trust region, Jacobi scaling, damping,
+ * termination order, the FAILURE rule) is shared.  set returns MSLAM_HIP_E_INVALID for a kind outside 0..1 and the setting
+ * stays.  Two SPARSE calls on the same input return the same bits; SPARSE and DENSE differ in rounding.
+ * The symbolic phase (host, per call).  Nodes are the free poses that have an edge; two nodes are adjacent when an edge joins
+ * them (duplicates count once, edges to constant poses not at all).  Two orders are computed:
+ *   NATURAL  ascending pose index;
+ *   RCM      components one after another; each starts at the unvisited node of least degree (ties: the smallest index; no
+ *            pseudo-peripheral search); breadth first from there, the unvisited neighbours of the node being expanded appended in
+ *            ascending (degree, index); the whole visiting order reversed at the end.
+ * With first[i] the least position among row i's neighbours and i itself, the envelope is sum (i - first[i] + 1) blocks; the
+ * order with the smaller envelope is taken, NATURAL on a tie.  An envelope above MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS is
+ * MSLAM_HIP_E_CAPACITY from mslam_hip_pose_graph (the message names the count; nothing is touched).  One workgroup factors
+ * the envelope column by column, so a dense pattern is far slower than with DENSE: SPARSE is for long, thin graphs.
+ * mslam_hip_pose_graph_analyze is that phase without a context or a GPU: order (pose index per position) and first take K
+ * entries of which *n_free are written; *ordering is 0 NATURAL or 1 RCM; any output may be NULL.  Its checks are those of
+ * mslam_hip_pose_graph with SPARSE: K in 0..16384, E in 0..65536, indices in range, no edge from a pose to itself
+ * (MSLAM_HIP_E_INVALID, nothing written).  It returns MSLAM_HIP_E_CAPACITY, with every output written, when the envelope is
+ * above the bound. */
+#define MSLAM_HIP_PG_SOLVER_DENSE 0
+#define MSLAM_HIP_PG_SOLVER_SPARSE 1
+#define MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE 16384
+#define MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS 1048576
+int mslam_hip_set_pose_graph_solver(mslam_hip_ctx* ctx, int kind);
+int mslam_hip_get_pose_graph_solver(mslam_hip_ctx* ctx, int* kind);
+int mslam_hip_pose_graph_analyze(const uint8_t* fixed /* K, or NULL */, int K, const int32_t* edge_a, const int32_t* edge_b, int E,
+                                 int32_t* order /* K: pose index per position, n_free used */, int32_t* first /* K */,
+                                 int* n_free, int* ordering /* 0 NATURAL, 1 RCM */, int64_t* envelope_blocks);
 /* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
  * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
  * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of

@@ -31,6 +31,10 @@ DETECTOR_DISTRIBUTED, DETECTOR_CV_ORB = 0, 1
 BOW_ASSIGN_TREE, BOW_ASSIGN_FLAT = 0, 1
 CV_ORDER_LIBSTDCXX, CV_ORDER_RASTER = 0, 1
 POSE_GRAPH_MAX_KEYFRAMES, POSE_GRAPH_MAX_EDGES = 1024, 65536    # mslam_hip_pose_graph's bounds (include/mslam_hip.h)
+POSE_GRAPH_MAX_KEYFRAMES_SPARSE, POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 16384, 1048576    # with the SPARSE solver
+PG_SOLVER_DENSE, PG_SOLVER_SPARSE = 0, 1    # mslam_hip_set_pose_graph_solver's kinds
+_PG_SOLVER_NAMES = {"dense": PG_SOLVER_DENSE, "sparse": PG_SOLVER_SPARSE}
+PG_ORDER_NATURAL, PG_ORDER_RCM = 0, 1    # mslam_hip_pose_graph_analyze's orderings
 CULL_MAX_ENTRIES = 4096    # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss's kinds
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
@@ -66,6 +70,7 @@ ABI_SYMBOLS = [
     "mslam_hip_kf_remove_landmarks", "mslam_hip_kf_cull_landmarks_search", "mslam_hip_kf_cull_landmarks",
     "mslam_hip_set_ba_loss", "mslam_hip_get_ba_loss",
     "mslam_hip_set_union_descriptor", "mslam_hip_get_union_descriptor",
+    "mslam_hip_set_pose_graph_solver", "mslam_hip_get_pose_graph_solver", "mslam_hip_pose_graph_analyze",
 ]
 
 
@@ -188,6 +193,40 @@ def lib():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _pg_solver_kind(kind, who):
+    if isinstance(kind, str):
+        if kind.lower() not in _PG_SOLVER_NAMES:
+            raise MslamHipError(E_INVALID, "%s: solver %r is not dense / sparse" % (who, kind))
+        return _PG_SOLVER_NAMES[kind.lower()]
+    return int(kind)
+
+
+def pose_graph_analyze(fixed, K, edge_a, edge_b):
+    """The symbolic phase of Context.pose_graph's SPARSE solver (mslam_hip_pose_graph_analyze): host only, no context, no GPU.
+    fixed: [K] flags or None; edges (a, b) as indices below K.  Nodes are the free poses that have an edge.  -> dict(order =
+    pose index per position [n_free], first = the least position among a row's neighbours and itself [n_free], n_free,
+    ordering = PG_ORDER_NATURAL or PG_ORDER_RCM, envelope_blocks, fits = the envelope is within
+    POSE_GRAPH_MAX_ENVELOPE_BLOCKS (the library's E_CAPACITY is fits = False here: the analysis itself is complete)).
+    MslamHipError(E_INVALID): K above 16384, more than 65536 edges, an index out of range, an edge from a pose to itself."""
+    K = int(K)
+    ea = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    eb = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    if len(ea) != len(eb):
+        raise MslamHipError(E_INVALID, "pose_graph_analyze: %d / %d edge ends" % (len(ea), len(eb)))
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+    if fx is not None and len(fx) != K:
+        raise MslamHipError(E_INVALID, "pose_graph_analyze: %d poses, %d fixed flags" % (K, len(fx)))
+    order, first = np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1), np.int32)
+    n, kind, blocks = C.c_int(0), C.c_int(0), C.c_int64(0)
+    rc = lib().mslam_hip_pose_graph_analyze(_p(fx), K, _p(ea), _p(eb), len(ea), _p(order), _p(first), C.byref(n), C.byref(kind),
+                                            C.byref(blocks))
+    if rc not in (OK, E_CAPACITY):
+        raise MslamHipError(rc, "pose_graph_analyze: K outside 0..%d, E outside 0..%d, an index out of range or an edge from a "
+                                "pose to itself" % (POSE_GRAPH_MAX_KEYFRAMES_SPARSE, POSE_GRAPH_MAX_EDGES))
+    return dict(order=order[:n.value].copy(), first=first[:n.value].copy(), n_free=n.value, ordering=kind.value,
+                envelope_blocks=blocks.value, fits=rc == OK)
 
 
 def default_params(**kw):
@@ -569,8 +608,22 @@ class Context:
         res.update(poses=x, landmarks=lm, outlier=mask[:len(ok)].astype(bool))
         return res
 
+    def set_pose_graph_solver(self, kind):
+        """the linear solver of pose_graph from now on: "dense" (the default state: the blocked Cholesky of the dense normal
+        equations, K <= 1024) / "sparse" (a Cholesky factor on the block envelope after a NATURAL or reverse Cuthill-McKee
+        order, K <= 16384, an envelope of at most POSE_GRAPH_MAX_ENVELOPE_BLOCKS blocks, else E_CAPACITY) or PG_SOLVER_*.
+        Nothing else reads the setting."""
+        self._chk(self.L.mslam_hip_set_pose_graph_solver(self._h, _pg_solver_kind(kind, "set_pose_graph_solver")))
+
+    def get_pose_graph_solver(self):
+        """-> PG_SOLVER_DENSE or PG_SOLVER_SPARSE"""
+        k = C.c_int(0)
+        self._chk(self.L.mslam_hip_get_pose_graph_solver(self._h, C.byref(k)))
+        return k.value
+
     def pose_graph(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100):
-        """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024), E edges
+        """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024, or 16384
+        after set_pose_graph_solver("sparse")), E edges
         (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
         flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
         final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged."""
@@ -1401,13 +1454,20 @@ class HipBackend:
     global_solver = True: global_ba() goes through
     Context.bundle_adjust_global and takes up to 1024 keyframes; local_ba and neighbours are the same in both modes.
     close_loop() is the body of the reference's empty closeLoop (rgbd_feature_frontend.cpp:577-580): a pose graph over every
-    keyframe on Context.pose_graph; self.anchor names, per landmark, the keyframe that created it."""
+    keyframe on Context.pose_graph; self.anchor names, per landmark, the keyframe that created it.
+    pose_graph_solver = "sparse": close_loop runs with Context.set_pose_graph_solver("sparse") and puts the context's previous
+    setting back afterwards, also when the solve raises, and takes up to 16384 keyframes.  "dense" (the default) never touches
+    the setting, as loss = None does not (a context is DENSE unless its owner said otherwise), and takes up to 1024.
+    global_ba() keeps its own cap of 1024 keyframes in both."""
 
     MAX_KEYFRAMES = 64
     MAX_GLOBAL_KEYFRAMES = 1024
 
-    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None):
+    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense"):
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
+        self.pose_graph_solver = _pg_solver_kind(pose_graph_solver, "HipBackend")    # of Context.set_pose_graph_solver
+        if self.pose_graph_solver not in (PG_SOLVER_DENSE, PG_SOLVER_SPARSE):
+            raise MslamHipError(E_INVALID, "HipBackend: pose_graph_solver %r is not dense / sparse" % (pose_graph_solver,))
         self.global_solver = bool(global_solver)
         self.loss = None if loss is None else (loss[0], float(loss[1]))    # (kind, scale) of Context.set_ba_loss
         self.poses = {}       # id -> [7]
@@ -1638,14 +1698,24 @@ class HipBackend:
         """closeLoop: (rvec, tvec) is the world -> camera pose of keyframe cur_id found by PnP against loop_id's stored
         landmarks.  Solves loop_problem() on the device; on a usable termination the poses are replaced and every landmark
         moves rigidly with its anchor keyframe, X' = T_a' T_a^-1 X.  -> the summary and keyframes, poses_before, poses,
-        landmark_ids, landmarks (FAILURE: everything as it was).  More than 1024 keyframes is MslamHipError(E_CAPACITY),
-        a keyframe the backend does not hold MslamHipError(E_INVALID), both raised before the context is touched."""
-        if len(self.poses) > POSE_GRAPH_MAX_KEYFRAMES:
-            raise MslamHipError(E_CAPACITY, "close_loop: %d keyframes, at most %d per solve" % (len(self.poses), POSE_GRAPH_MAX_KEYFRAMES))
+        landmark_ids, landmarks (FAILURE: everything as it was).  More than 1024 keyframes (16384 with
+        pose_graph_solver = "sparse") is MslamHipError(E_CAPACITY), a keyframe the backend does not hold
+        MslamHipError(E_INVALID), both raised before the context is touched."""
+        cap = POSE_GRAPH_MAX_KEYFRAMES_SPARSE if self.pose_graph_solver == PG_SOLVER_SPARSE else POSE_GRAPH_MAX_KEYFRAMES
+        if len(self.poses) > cap:
+            raise MslamHipError(E_CAPACITY, "close_loop: %d keyframes, at most %d per solve" % (len(self.poses), cap))
         if int(cur_id) not in self.poses or int(loop_id) not in self.poses or int(cur_id) == int(loop_id):
             raise MslamHipError(E_INVALID, "close_loop: keyframes %r and %r must be two keyframes of the backend" % (cur_id, loop_id))
         ids, poses, fixed, ea, eb, meas, info = self.loop_problem(cur_id, loop_id, rvec, tvec, graph, sqrt_info)
-        res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+        if self.pose_graph_solver == PG_SOLVER_SPARSE:
+            before = self.ctx.get_pose_graph_solver()
+            self.ctx.set_pose_graph_solver(PG_SOLVER_SPARSE)
+            try:
+                res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+            finally:
+                self.ctx.set_pose_graph_solver(before)
+        else:
+            res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
         lids = sorted(l for l in self.landmarks if self.anchor.get(l) in self.poses)
         lm = np.array([self.landmarks[l] for l in lids], np.float64).reshape(-1, 3)
         if res["termination"] != 2:
@@ -1726,6 +1796,9 @@ class HipKeyframeTracker:
     first).  On a winner: HipBackend.close_loop, Context.kf_update_world with the moved landmarks, the tracker's pose becomes
     the corrected pose of the new keyframe, the local map is rebuilt, and with loop_global_ba HipBackend.global_ba and
     kf_update_world follow.  self.loop_results holds every attempt; the frame's dict gains loop = (cur, loop) or None.
+    pose_graph_solver = "dense" (the default) or "sparse" goes to the backend: close_loop then takes up to 1024 or up to
+    16384 keyframes (HipBackend; Context.set_pose_graph_solver).  The optional global solve behind a closure
+    (loop_global_ba) keeps its own cap of 1024 keyframes and its behaviour in both modes.
     Without loop_fusion the new keyframe's landmarks keep their own ids, so no covisibility edge joins the two keyframes and
     the loop is known to the pose graph of that one call only.
 
@@ -1819,7 +1892,8 @@ class HipKeyframeTracker:
                  loop_closure=False, loop_min_score=0.05, loop_min_gap=10, loop_min_inliers=60, loop_max_candidates=4,
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
-                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None):
+                 lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
+                 pose_graph_solver="dense"):
         self.ctx = ctx
         if union_descriptor is not None:
             if local_map_depth is None:
@@ -1865,7 +1939,8 @@ class HipKeyframeTracker:
         self._bow_entry = {}         # BoW database entry -> keyframe id
         self._last_closure = None    # the keyframe at which the last loop was closed
         # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
-        self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss) if local_ba else None
+        self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss,
+                                  pose_graph_solver=pose_graph_solver) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)

@@ -165,6 +165,8 @@ struct mslam_hip_ctx
     // pose-graph optimisation (mslam_hip_pose_graph, k_posegraph.hip), grown on demand: every device array of one solve but
     // the normal equations, which live in d_ba_S; the termination word is h_ba
     mslam::DevBuf<uint8_t> d_pg;
+    // mslam_hip_set_pose_graph_solver: read by mslam_hip_pose_graph when it is called
+    int pg_solver = MSLAM_HIP_PG_SOLVER_DENSE;
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

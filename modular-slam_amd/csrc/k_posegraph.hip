@@ -32,7 +32,10 @@
 //                   an off-diagonal pair sums J_i^T J_j over the edges the host listed for it, in that order (a serial loop
 //                   of one wave: the slow shape when thousands of duplicate edges join one pair), lane (r, c)
 //                   keeping entry (r, c), and writes the scaled block into the lower triangle; the blocked Cholesky, the
-//                   back-substitution
+//                   back-substitution.  With MSLAM_HIP_PG_SOLVER_SPARSE (mslam_hip_set_pose_graph_solver) pg_sparse_solve
+//                   (pg_sparse.hpp) stands here instead: the factor on the block envelope, with k_pg_assemble_env, the same
+//                   pairs, lists and expressions written to the permuted envelope position; ci[k] is then the pose's
+//                   position in the chosen order (every sum of the other kernels runs over k, none over ci)
 //   k_pg_candidate  Plus on every pose
 //   k_pg_eval       a lane per edge: the model cost change -(J_s s) . (f + J_s s / 2) and the cost at the candidate, summed per
 //                   block by a fixed tree
@@ -41,6 +44,7 @@
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
 #include "chol_solver.hpp"
+#include "pg_sparse.hpp"
 
 #include <algorithm>
 #include <map>
@@ -70,6 +74,9 @@ struct PgArgs
     double *r, *J;       // [E] x 6; [E] x 72: J_a then J_b, 6 x 6 row-major
     double *U, *gc, *sc; // [K] x 21, 6, 6
     double *S, *yc;      // the padded normal equations (the context's d_ba_S); the solution, n
+    // MSLAM_HIP_PG_SOLVER_SPARSE: S is the block envelope; row i's first block and first column, the right-hand side
+    const int32_t *env_off, *env_first;
+    double* rhs;
     double* part;        // [2][n_blocks]: model cost change, candidate cost
     TrCtrl* ctrl;
     int32_t* h_done; // mapped
@@ -303,6 +310,56 @@ __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
     a.S[(b2 * 6 + c) + (b1 * 6 + r) * ld] = a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c];
 }
 
+// The envelope form (pg_sparse.hpp): the same pairs, lists, sums and expressions; ci is the position in the chosen order, the
+// block of (row, column) lies at env_off[row] + column - env_first[row], row-major inside.  A pair whose first pose comes later
+// in the order is written transposed.
+__global__ __launch_bounds__(64) void k_pg_assemble_env(PgArgs a)
+{
+    const TrCtrl* ct = a.ctrl;
+    if(ct->done)
+        return;
+    const int lane = threadIdx.x;
+    const int k1 = a.pairs[blockIdx.x * 2], k2 = a.pairs[blockIdx.x * 2 + 1];
+    const int p1 = a.ci[k1], p2 = a.ci[k2];
+    if(k1 == k2)
+    {
+        double* D = a.S + (size_t)(a.env_off[p1] + p1 - a.env_first[p1]) * 36;
+        if(lane < 36)
+        {
+            const int r = lane / 6, c = lane % 6;
+            const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * a.sc[(size_t)k1 * 6 + c];
+            D[r * 6 + c] = r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u;
+        }
+        else if(lane < 42)
+        {
+            const int r = lane - 36;
+            a.rhs[(size_t)p1 * 6 + r] = a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r];
+        }
+        return;
+    }
+    if(lane >= 36)
+        return;
+    const int r = lane / 6, c = lane % 6;
+    double s = 0.0;
+    for(int pos = a.pair_ptr[blockIdx.x]; pos < a.pair_ptr[blockIdx.x + 1]; ++pos)
+    {
+        const int e = a.pair_edge[pos];
+        const bool fwd = a.ea[e] == k1;
+        const double* J1 = a.J + (size_t)e * 72 + (fwd ? 0 : 36);
+        const double* J2 = a.J + (size_t)e * 72 + (fwd ? 36 : 0);
+        double t = 0.0;
+#pragma unroll
+        for(int i = 0; i < 6; ++i)
+            t += J1[i * 6 + r] * J2[i * 6 + c];
+        s += t;
+    }
+    const double val = a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c];
+    if(p2 > p1)
+        a.S[(size_t)(a.env_off[p2] + p1 - a.env_first[p2]) * 36 + c * 6 + r] = val;
+    else
+        a.S[(size_t)(a.env_off[p1] + p2 - a.env_first[p1]) * 36 + r * 6 + c] = val;
+}
+
 // delta = step * scaling with step = -y; Plus.  Poses outside the problem are copied.
 __global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
 {
@@ -408,8 +465,10 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    if(K < 0 || K > kPgMaxKeyframes)
-        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: K outside 0.." + std::to_string(kPgMaxKeyframes));
+    const bool sparse = c->pg_solver == MSLAM_HIP_PG_SOLVER_SPARSE;
+    const int k_max = sparse ? MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE : kPgMaxKeyframes;
+    if(K < 0 || K > k_max)
+        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: K outside 0.." + std::to_string(k_max));
     if(E < 0 || E > kPgMaxEdges)
         return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: E outside 0.." + std::to_string(kPgMaxEdges));
     if(max_iterations < 0 || (K > 0 && !poses) || (E > 0 && (!edge_a || !edge_b || !edge_meas)))
@@ -450,9 +509,23 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
             inc[(size_t)at[(size_t)edge_a[e]]++] = 2 * e, inc[(size_t)at[(size_t)edge_b[e]]++] = 2 * e + 1;
     }
     int n_free = 0;
-    for(int k = 0; k < K; ++k)
-        if(!(fixed && fixed[k]) && inc_ptr[(size_t)k + 1] > inc_ptr[(size_t)k])
-            ci[(size_t)k] = n_free++;
+    PgSymbolic sy;
+    if(sparse)
+    {
+        // the symbolic phase: the order, the envelope; a pose's block is its position in the order
+        pg_symbolic(fixed, K, edge_a, edge_b, E, sy);
+        if(sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS)
+            return fail(c, MSLAM_HIP_E_CAPACITY, "pose_graph: the envelope needs " + std::to_string(sy.blocks) + " blocks, at most " +
+                                                     std::to_string(MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS) + " per solve");
+        pg_layout(sy);
+        n_free = sy.n_free;
+        for(int i = 0; i < n_free; ++i)
+            ci[(size_t)sy.order[(size_t)i]] = i;
+    }
+    else
+        for(int k = 0; k < K; ++k)
+            if(!(fixed && fixed[k]) && inc_ptr[(size_t)k + 1] > inc_ptr[(size_t)k])
+                ci[(size_t)k] = n_free++;
     std::map<std::pair<int, int>, std::vector<int32_t>> by_pair; // sorted by (k1, k2); every list in edge order
     for(int k = 0; k < K; ++k)
         if(ci[(size_t)k] >= 0)
@@ -479,13 +552,17 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4), o_iptr = st.put(inc_ptr.data(), ((size_t)K + 1) * 4);
     const size_t o_inc = st.put(inc.data(), (size_t)E * 8), o_ci = st.put(ci.data(), (size_t)K * 4), o_pairs = st.put(pairs.data(), pairs.size() * 4);
     const size_t o_pptr = st.put(pair_ptr.data(), pair_ptr.size() * 4), o_pedge = st.put(pair_edge.data(), pair_edge.size() * 4);
+    const size_t o_roff = st.put(sy.row_off.data(), sy.row_off.size() * 4), o_first = st.put(sy.first.data(), sparse ? (size_t)n_free * 4 : 0);
+    const size_t o_cptr = st.put(sy.col_ptr.data(), sy.col_ptr.size() * 4), o_cblk = st.put(sy.col_blk.data(), sy.col_blk.size() * 4);
+    const size_t o_crow = st.put(sy.col_row.data(), sy.col_row.size() * 4);
     const size_t o_cand = st.carve((size_t)K * 56), o_r = st.carve((size_t)E * 48), o_J = st.carve((size_t)E * 576);
     const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_yc = st.carve((size_t)a.n * 8);
     const size_t o_part = st.carve((size_t)a.n_blocks * 16);
+    const size_t o_rhs = st.carve(sparse ? (size_t)a.n * 8 : 0), o_dinv = st.carve(sparse ? (size_t)a.n * 8 : 0);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
     MSLAM_CHK(c, grow(c->d_pg, st.size, c->stream));
     if(a.n > 0)
-        MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
+        MSLAM_CHK(c, grow(c->d_ba_S, sparse ? (size_t)sy.blocks * 36 : (size_t)a.ld * a.n_pad, c->stream));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
     uint8_t* d = c->d_pg;
@@ -501,7 +578,9 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
+    a.env_off = i32(o_roff), a.env_first = i32(o_first), a.rhs = dbl(o_rhs);
     const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
+    const PgsArgs env{n_free, sy.blocks, a.env_off, a.env_first, i32(o_cptr), i32(o_cblk), i32(o_crow), a.S, a.rhs, dbl(o_dinv), a.yc, a.ctrl};
 
     const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256));
     {
@@ -515,7 +594,9 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
             hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
             hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
         }
-        if(a.n_pairs > 0)
+        if(a.n_pairs > 0 && sparse)
+            pg_sparse_solve(c, env, s, [&] { hipLaunchKernelGGL(k_pg_assemble_env, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+        else if(a.n_pairs > 0)
             ba_blocked_solve(c, chol, s, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
         StageScope tk(c, "pg_step");
         hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
@@ -537,5 +618,24 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
         return fail(c, MSLAM_HIP_E_NO_MODEL, "pose_graph: the minimiser ended in FAILURE (non-finite cost or gradient, or 5 invalid "
                                              "steps in a row)");
     std::memcpy(poses, xp.data(), (size_t)K * 56);
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_set_pose_graph_solver(mslam_hip_ctx* c, int kind)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind != MSLAM_HIP_PG_SOLVER_DENSE && kind != MSLAM_HIP_PG_SOLVER_SPARSE)
+        return fail(c, MSLAM_HIP_E_INVALID, "set_pose_graph_solver: kind outside 0..1");
+    c->pg_solver = kind;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_pose_graph_solver(mslam_hip_ctx* c, int* kind)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind)
+        *kind = c->pg_solver;
     return MSLAM_HIP_OK;
 }

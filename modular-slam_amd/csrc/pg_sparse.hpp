@@ -1,0 +1,46 @@
+// pg_sparse.hpp — the block-envelope (skyline) Cholesky solve of k_pg_sparse.hip: mslam_hip_pose_graph's second linear solver
+// (MSLAM_HIP_PG_SOLVER_SPARSE) and the symbolic phase mslam_hip_pose_graph_analyze exposes.  DESIGN.md 4.25.
+#pragma once
+#include "trust_region.hpp"
+
+#include <functional>
+
+namespace mslam
+{
+
+// The symbolic phase of one solve, host only.  Nodes are the free poses that have an edge; position i of the chosen order
+// is block row i of the factor.
+struct PgSymbolic
+{
+    int n_free = 0, ordering = 0; // ordering: 0 NATURAL, 1 RCM
+    int64_t blocks = 0;           // the envelope of the chosen order in 6 x 6 blocks, diagonal included
+    std::vector<int32_t> order;   // [n_free] pose index per position
+    std::vector<int32_t> first;   // [n_free] the least position among row i's neighbours and i itself
+    // the layout (pg_layout): row i holds the blocks of columns first[i] .. i from block row_off[i] on; column j's rows below
+    // the diagonal, ascending, as the block of (row, j) and the row, from col_ptr[j] on
+    std::vector<int32_t> row_off, col_ptr, col_blk, col_row;
+};
+
+// the orders and the envelope; the caller has checked K, E, the indices and the self-edges
+void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, int E, PgSymbolic& sy);
+// row offsets and column lists of an envelope that fits MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS
+void pg_layout(PgSymbolic& sy);
+
+struct PgsArgs
+{
+    int n;          // block rows
+    int64_t blocks; // the envelope
+    const int32_t *row_off, *first, *col_ptr, *col_blk, *col_row;
+    double* S;    // the envelope, 36 doubles per block, row-major inside a block (the context's d_ba_S)
+    double* rhs;  // [6 n] the right-hand side; y = L^-1 b after the factor
+    double* dinv; // [6 n] 1 / diagonal of L
+    double* yc;   // [6 n] the solution
+    TrCtrl* ctrl; // done: every launch returns at once; solve_bad: set by a pivot that is not finite or not > 0
+};
+
+// One solve of S y = b, enqueued on s: the clear, then `assemble` has to enqueue whatever writes the envelope and rhs, then
+// the factor with the forward substitution (one workgroup), then the back-substitution (one workgroup).  The stages are
+// timed under ba_blocked_solve's names: solver_schur, solver_factor, solver_subst.
+void pg_sparse_solve(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble);
+
+} // namespace mslam

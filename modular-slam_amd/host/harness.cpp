@@ -43,6 +43,11 @@
 //        mslam_harness <plugin.so> --pose-graph <scene>
 //                                    ILoopClosingBackend::closeLoop of the same factory's object on one pose-graph scene: the
 //                                    summary, then every keyframe's state
+//        mslam_harness <plugin.so> --pose-graph <scene> --sparse | --solver <kind>
+//                                    the same with ISparsePoseGraphBackend::setPoseGraphSolver(kind) first (--sparse: kind 1,
+//                                    the block-envelope factor, up to 16384 keyframes); a kind the backend refuses is its
+//                                    std::invalid_argument: "error: ..." and exit code 1; a kind that is no integer is a
+//                                    usage error, exit code 2
 //        mslam_harness <plugin.so> --fuse <scene>
 //                                    ILandmarkFuser::fuseLandmarks of the relocalizer adapter (the vocabulary it loads comes
 //                                    from MSLAM_ORB_VOCABULARY or ./orbvoc.dbow3) on the scene's first two entries, keep then
@@ -262,8 +267,23 @@ int main(int argc, char** argv)
                 std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
             return 0;
         }
-        if(argc == 4 && std::strcmp(argv[2], "--pose-graph") == 0)
+        if((argc == 4 || (argc == 5 && std::strcmp(argv[4], "--sparse") == 0) || (argc == 6 && std::strcmp(argv[4], "--solver") == 0)) &&
+           std::strcmp(argv[2], "--pose-graph") == 0)
         {
+            const bool setSolver = argc > 4;
+            int solverKind = 1;
+            if(argc == 6)
+            {
+                // a whole integer or nothing: "abc" and "1x" are usage errors, not kind 0 or 1
+                char* end = nullptr;
+                const long v = std::strtol(argv[5], &end, 10);
+                if(end == argv[5] || *end != '\0' || v < -1000 || v > 1000)
+                {
+                    std::fprintf(stderr, "--solver takes an integer kind (0 dense, 1 sparse), not %s\n", argv[5]);
+                    return 2;
+                }
+                solverKind = static_cast<int>(v);
+            }
             // scene file: "MSPG", i32 version (1), K, E, max_iterations, has_info; K x i32 keyframe id; K x 7 f64 state (qx qy qz
             // qw px py pz); E x i32 a; E x i32 b; E x 7 f64 measurement (q then p of b in a's frame); has_info: E x 36 f64
             std::ifstream in(argv[3], std::ios::binary);
@@ -327,6 +347,16 @@ int main(int argc, char** argv)
             {
                 std::fprintf(stderr, "the plugin does not offer closeLoop\n");
                 return 6;
+            }
+            if(setSolver)
+            {
+                auto* sparseBackend = dynamic_cast<mslam::ISparsePoseGraphBackend*>(backend.get());
+                if(!sparseBackend)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setPoseGraphSolver\n");
+                    return 6;
+                }
+                sparseBackend->setPoseGraphSolver(solverKind);
             }
             const mslam::BackendOutput out = loopBackend->closeLoop(keyframes, edges, head[3]);
             std::printf("pose_graph termination %d iterations %d initial %.17g final %.17g keyframes %zu edges %zu\n", out.termination,

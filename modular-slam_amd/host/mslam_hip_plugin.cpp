@@ -12,6 +12,7 @@
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
 //   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
 //                          : IRobustBackend                                       a Huber or Cauchy loss for both bundle adjustments (an extension)
+//                          : ISparsePoseGraphBackend                              closeLoop's linear solver: dense or the block-envelope factor (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -1004,11 +1005,18 @@ class HipMinMseTracker : public ISlam3dPnp
 // constant — and the result is written back into keyframe->state and landmark->state, as Ceres writes through the pointers
 // the reference hands it.  More than 64 keyframes is an error (the reduced system is dense); FAILURE updates nothing.
 // globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.  closeLoop hands the
-// keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way.  setLoss (IRobustBackend,
+// keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way; setPoseGraphSolver
+// (ISparsePoseGraphBackend, an extension) keeps its linear solver, set on the context before each closeLoop.  setLoss (IRobustBackend,
 // an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.
-class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
+class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend
 {
   public:
+    void setPoseGraphSolver(int kind) override
+    {
+        if(kind != MSLAM_HIP_PG_SOLVER_DENSE && kind != MSLAM_HIP_PG_SOLVER_SPARSE)
+            throw std::invalid_argument("setPoseGraphSolver: kind 0 (dense) or 1 (sparse)");
+        poseGraphSolver = kind;
+    }
     void setLoss(int kind, double scale) override
     {
         if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY ||
@@ -1059,6 +1067,8 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
                     info[36 * e + j] = edges[e].sqrtInformation.empty() ? (j % 7 == 0 ? 1.0 : 0.0) : edges[e].sqrtInformation[j];
         }
         ctx.ensure(0, 0);
+        if(const int rs = mslam_hip_set_pose_graph_solver(ctx.h, poseGraphSolver); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_pose_graph_solver", rs);
         mslam_hip_ba_summary summary{};
         const int rc = mslam_hip_pose_graph(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), edgeA.data(),
                                             edgeB.data(), meas.data(), anyInfo ? info.data() : nullptr, static_cast<int>(edges.size()),
@@ -1148,6 +1158,7 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     }
 
     Ctx ctx;
+    int poseGraphSolver = MSLAM_HIP_PG_SOLVER_DENSE;
     int lossKind = MSLAM_HIP_BA_LOSS_NONE;
     double lossScale = 0.0;
 };

@@ -236,7 +236,8 @@ class IGlobalBackend : public IBackend
     virtual BackendOutput globalBundleAdjustment(const std::vector<BackendObservation>& observations, int maxIterations = 100) = 0;
 };
 // extension: the body of RgbdFeatureFrontend::closeLoop (rgbd_feature_frontend.cpp:577-580, empty in the reference): a
-// pose-graph optimisation over the listed keyframes (mslam_hip_pose_graph: up to 1024 keyframes, 65536 edges).  An edge
+// pose-graph optimisation over the listed keyframes (mslam_hip_pose_graph: up to 1024 keyframes, 65536 edges; up to 16384
+// keyframes after ISparsePoseGraphBackend::setPoseGraphSolver(1)).  An edge
 // carries pose b expressed in a's frame (T_a^-1 T_b) and, optionally, the square root of its 6 x 6 information matrix
 // (row-major, position rows first; empty: identity).  keyframe->state is corrected in place, keyframe id 1 stays constant;
 // the output lists the keyframes and the summary (no landmarks, no outliers).  Reached with dynamic_cast, like IGlobalBackend.
@@ -263,6 +264,17 @@ class IRobustBackend
   public:
     virtual void setLoss(int kind, double scale) = 0;
     virtual ~IRobustBackend() = default;
+};
+// extension: the linear solver of closeLoop (mslam_hip_set_pose_graph_solver): kind 0 dense (the default: the blocked Cholesky
+// of the dense normal equations, up to 1024 keyframes), 1 sparse (a Cholesky factor on the block envelope after a NATURAL or
+// reverse Cuthill-McKee order: up to 16384 keyframes, an envelope of up to 1048576 blocks).  It holds for every later
+// closeLoop of the object; the bundle adjustments do not read it.  A kind outside 0..1 throws std::invalid_argument and leaves
+// the setting as it was.  An interface of its own, reached with dynamic_cast like IRobustBackend.
+class ISparsePoseGraphBackend
+{
+  public:
+    virtual void setPoseGraphSolver(int kind) = 0;
+    virtual ~ISparsePoseGraphBackend() = default;
 };
 // "huber:<a>" or "cauchy:<a>" -> kind 1 or 2 and a; false (nothing written) for anything else, a trailing character or an a
 // that is not finite or not > 0
