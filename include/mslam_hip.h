@@ -570,7 +570,9 @@ int mslam_hip_bundle_adjust(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out *
  *                            pivot flag through the invalid-step handling to a retry or FAILURE has never run, here or
  *                            in mslam_hip_bundle_adjust;
  *   sizes                    DEVIATES: at most 1024 keyframes per solve: the reduced system is kept dense, 6144^2 doubles
- *                            = 302 MB of device memory at the bound; the reference has no bound. */
+ *                            = 302 MB of device memory at the bound; the reference has no bound.  With
+ *                            mslam_hip_set_ba_global_solver(SPARSE), further down, 16384 keyframes and an envelope of
+ *                            1048576 blocks. */
 #define MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES 1024
 int mslam_hip_bundle_adjust_global(mslam_hip_ctx* ctx, double* poses /* K x 7, in/out */, const uint8_t* fixed /* K, or NULL */,
                                    int K /* 0..1024 */, double* landmarks /* L x 3, in/out */, int L, const int32_t* obs_kf,
@@ -690,6 +692,47 @@ int mslam_hip_get_pose_graph_solver(mslam_hip_ctx* ctx, int* kind);
 int mslam_hip_pose_graph_analyze(const uint8_t* fixed /* K, or NULL */, int K, const int32_t* edge_a, const int32_t* edge_b, int E,
                                  int32_t* order /* K: pose index per position, n_free used */, int32_t* first /* K */,
                                  int* n_free, int* ordering /* 0 NATURAL, 1 RCM */, int64_t* envelope_blocks);
+/* ---- The linear solver of mslam_hip_bundle_adjust_global (an extension) ----
+ * Context state, the idiom of mslam_hip_set_pose_graph_solver: mslam_hip_bundle_adjust_global reads it when it is called;
+ * mslam_hip_bundle_adjust (at most 64 keyframes) and mslam_hip_pose_graph do NOT read it.  DENSE is the default: every launch,
+ * every result bit and every error code is what it was before this setting existed, and K > 1024 is MSLAM_HIP_E_INVALID.
+ * With SPARSE K may reach MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE (above it: MSLAM_HIP_E_INVALID; L and M at most 2^24 as
+ * before) and the reduced camera system is kept and factored on its block envelope (skyline) in 6 x 6 blocks, by the factor
+ * and the substitution of the pose graph's SPARSE solver (the same kernels); the Schur complement over the covisible pairs
+ * is written into the envelope, one wave per pair, with the sums of DENSE in their order.  Memory and work follow the
+ * envelope, not K^2.  Everything else of the solve is shared with DENSE, one code: the blocks U / V / W, Jacobi scaling,
+ * damping, the loss (mslam_hip_set_ba_loss applies unchanged), candidate, evaluation, trust-region control, termination
+ * order, the FAILURE rule, the outlier mask, the stage names solver_schur / solver_factor / solver_subst.  A pivot that is
+ * not > 0 or not finite is an invalid step.  set returns MSLAM_HIP_E_INVALID for a kind outside 0..1 and the setting stays.
+ * Two SPARSE calls on the same input return the same bits; SPARSE and DENSE differ in rounding (another elimination order,
+ * and the diagonal's reciprocal is multiplied with where DENSE divides).
+ * The symbolic phase (host, per call).  Nodes are the free keyframes that have at least one observation; unlike in the pose
+ * graph, a node needs no neighbour: a free keyframe that shares no landmark with another free keyframe is a row all the
+ * same, a node of degree 0.  Two nodes are adjacent when they share a landmark (landmarks shared with a constant keyframe
+ * only join nothing).  The orders NATURAL and RCM, first[], the envelope and the choice (the smaller envelope, NATURAL on a
+ * tie) are those of mslam_hip_set_pose_graph_solver above, word for word; under RCM the nodes of degree 0 start first and so
+ * end last.  The bound is MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS, the same buffer (288 MiB): an envelope above it is
+ * MSLAM_HIP_E_CAPACITY from mslam_hip_bundle_adjust_global; the message names the block count and nothing is touched
+ * (poses, landmarks and the outlier array keep their bytes).
+ * One workgroup factors the envelope column by column, so a map with wide covisibility (a landmark many keyframes see, a
+ * keyframe covisible with most others) is far slower than with DENSE at K <= 1024: SPARSE is for long trajectories whose
+ * keyframes share landmarks with their neighbours and at loop closures.  tools/ba_global_sparse_latency.py measures both;
+ * DESIGN.md 4.26 has one run of it (thin rings: SPARSE about 3x faster per iteration up to 1024 keyframes; a complete map
+ * of 128 keyframes: 12x slower).
+ * mslam_hip_bundle_adjust_global_analyze is the symbolic phase without a context or a GPU: order (keyframe index per
+ * position) and first take K entries of which *n_free are written; *ordering is 0 NATURAL or 1 RCM; *n_pairs the covisible
+ * pairs k1 <= k2, diagonal included (the waves of the Schur kernel); any output may be NULL.  Its checks are those of the
+ * solve with SPARSE: K in 0..16384, L and M in 0..2^24, indices in range (MSLAM_HIP_E_INVALID, nothing written).  It returns
+ * MSLAM_HIP_E_CAPACITY, with every output written, when the envelope is above the bound. */
+#define MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE 0
+#define MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE 1
+#define MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE 16384
+int mslam_hip_set_ba_global_solver(mslam_hip_ctx* ctx, int kind);
+int mslam_hip_get_ba_global_solver(mslam_hip_ctx* ctx, int* kind);
+int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed /* K, or NULL */, int K, const int32_t* obs_kf, const int32_t* obs_lm,
+                                           int M, int L, int32_t* order /* K: keyframe index per position, n_free used */,
+                                           int32_t* first /* K */, int* n_free, int* ordering /* 0 NATURAL, 1 RCM */,
+                                           int64_t* envelope_blocks, int* n_pairs);
 /* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
  * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
  * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of

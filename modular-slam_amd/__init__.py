@@ -35,6 +35,8 @@ POSE_GRAPH_MAX_KEYFRAMES_SPARSE, POSE_GRAPH_MAX_ENVELOPE_BLOCKS = 16384, 1048576
 PG_SOLVER_DENSE, PG_SOLVER_SPARSE = 0, 1    # mslam_hip_set_pose_graph_solver's kinds
 _PG_SOLVER_NAMES = {"dense": PG_SOLVER_DENSE, "sparse": PG_SOLVER_SPARSE}
 PG_ORDER_NATURAL, PG_ORDER_RCM = 0, 1    # mslam_hip_pose_graph_analyze's orderings
+BA_GLOBAL_MAX_KEYFRAMES, BA_GLOBAL_MAX_KEYFRAMES_SPARSE = 1024, 16384    # mslam_hip_bundle_adjust_global's bounds, DENSE / SPARSE
+BA_GLOBAL_SOLVER_DENSE, BA_GLOBAL_SOLVER_SPARSE = 0, 1    # mslam_hip_set_ba_global_solver's kinds
 CULL_MAX_ENTRIES = 4096    # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss's kinds
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
@@ -71,6 +73,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_ba_loss", "mslam_hip_get_ba_loss",
     "mslam_hip_set_union_descriptor", "mslam_hip_get_union_descriptor",
     "mslam_hip_set_pose_graph_solver", "mslam_hip_get_pose_graph_solver", "mslam_hip_pose_graph_analyze",
+    "mslam_hip_set_ba_global_solver", "mslam_hip_get_ba_global_solver", "mslam_hip_bundle_adjust_global_analyze",
 ]
 
 
@@ -227,6 +230,34 @@ def pose_graph_analyze(fixed, K, edge_a, edge_b):
                                 "pose to itself" % (POSE_GRAPH_MAX_KEYFRAMES_SPARSE, POSE_GRAPH_MAX_EDGES))
     return dict(order=order[:n.value].copy(), first=first[:n.value].copy(), n_free=n.value, ordering=kind.value,
                 envelope_blocks=blocks.value, fits=rc == OK)
+
+
+def ba_global_analyze(fixed, K, obs_kf, obs_lm, L=None):
+    """The symbolic phase of Context.bundle_adjust_global's SPARSE solver (mslam_hip_bundle_adjust_global_analyze): host only,
+    no context, no GPU.  fixed: [K] flags or None; observations (keyframe index below K, landmark index below L; L defaults
+    to one past the largest).  Nodes are the free keyframes that have an observation, adjacent when they share a landmark; a
+    node needs no neighbour.  -> dict(order = keyframe index per position [n_free], first [n_free], n_free, ordering =
+    PG_ORDER_NATURAL or PG_ORDER_RCM, envelope_blocks, n_pairs = the covisible pairs k1 <= k2 with the diagonal, fits = the
+    envelope is within POSE_GRAPH_MAX_ENVELOPE_BLOCKS (the library's E_CAPACITY is fits = False here: the analysis itself is
+    complete)).  MslamHipError(E_INVALID): K above 16384, L or M above 2^24, an index out of range."""
+    K = int(K)
+    ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+    ol = np.ascontiguousarray(obs_lm, np.int32).reshape(-1)
+    if len(ok) != len(ol):
+        raise MslamHipError(E_INVALID, "ba_global_analyze: %d / %d observation ends" % (len(ok), len(ol)))
+    L = (int(ol.max()) + 1 if len(ol) else 0) if L is None else int(L)
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+    if fx is not None and len(fx) != K:
+        raise MslamHipError(E_INVALID, "ba_global_analyze: %d keyframes, %d fixed flags" % (K, len(fx)))
+    order, first = np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1), np.int32)
+    n, kind, blocks, pairs = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int(0)
+    rc = lib().mslam_hip_bundle_adjust_global_analyze(_p(fx), K, _p(ok), _p(ol), len(ok), L, _p(order), _p(first), C.byref(n),
+                                                      C.byref(kind), C.byref(blocks), C.byref(pairs))
+    if rc not in (OK, E_CAPACITY):
+        raise MslamHipError(rc, "ba_global_analyze: K outside 0..%d, L or M outside 0..2^24 or an index out of range"
+                            % BA_GLOBAL_MAX_KEYFRAMES_SPARSE)
+    return dict(order=order[:n.value].copy(), first=first[:n.value].copy(), n_free=n.value, ordering=kind.value,
+                envelope_blocks=blocks.value, n_pairs=pairs.value, fits=rc == OK)
 
 
 def default_params(**kw):
@@ -565,9 +596,28 @@ class Context:
 
     def bundle_adjust_global(self, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed=None, max_iterations=100, outlier_threshold=0.15):
         """CeresBackend::globalBundleAdjustment's solve: bundle_adjust's arguments and result with K <= 1024, always through
-        the blocked solver (covisible-pair Schur complement, blocked Cholesky over many workgroups), at any K."""
+        the blocked solver (covisible-pair Schur complement, blocked Cholesky over many workgroups), at any K.  After
+        set_ba_global_solver("sparse"): K <= 16384, the reduced system on its block envelope (E_CAPACITY when the envelope
+        is above POSE_GRAPH_MAX_ENVELOPE_BLOCKS: nothing touched)."""
         return self._bundle_adjust(self.L.mslam_hip_bundle_adjust_global, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed,
                                    max_iterations, outlier_threshold)
+
+    def set_ba_global_solver(self, kind):
+        """the linear solver of bundle_adjust_global from now on: "dense" (the default state: the blocked Cholesky of the dense
+        reduced camera system, K <= 1024) / "sparse" (a Cholesky factor on the block envelope of the covisibility graph after a
+        NATURAL or reverse Cuthill-McKee order, K <= 16384, an envelope of at most POSE_GRAPH_MAX_ENVELOPE_BLOCKS blocks, else
+        E_CAPACITY) or BA_GLOBAL_SOLVER_*.  bundle_adjust and pose_graph do not read the setting."""
+        self._chk(self.L.mslam_hip_set_ba_global_solver(self._h, _pg_solver_kind(kind, "set_ba_global_solver")))
+
+    def get_ba_global_solver(self):
+        """-> BA_GLOBAL_SOLVER_DENSE or BA_GLOBAL_SOLVER_SPARSE"""
+        k = C.c_int(0)
+        self._chk(self.L.mslam_hip_get_ba_global_solver(self._h, C.byref(k)))
+        return k.value
+
+    def ba_global_analyze(self, fixed, K, obs_kf, obs_lm, L=None):
+        """the module's ba_global_analyze: the symbolic phase bundle_adjust_global would run with "sparse" (no GPU work)"""
+        return ba_global_analyze(fixed, K, obs_kf, obs_lm, L)
 
     def set_ba_loss(self, kind, scale=0.0):
         """the loss function of bundle_adjust and bundle_adjust_global from now on (an extension: the reference has none):
@@ -1458,17 +1508,24 @@ class HipBackend:
     pose_graph_solver = "sparse": close_loop runs with Context.set_pose_graph_solver("sparse") and puts the context's previous
     setting back afterwards, also when the solve raises, and takes up to 16384 keyframes.  "dense" (the default) never touches
     the setting, as loss = None does not (a context is DENSE unless its owner said otherwise), and takes up to 1024.
-    global_ba() keeps its own cap of 1024 keyframes in both."""
+    global_ba() has its own setting: global_linear_solver = "sparse" (with global_solver = True) runs it with
+    Context.set_ba_global_solver("sparse"), puts the context's previous setting back afterwards, also when the solve raises,
+    and takes up to 16384 keyframes; "dense" (the default) never touches the setting and takes up to 1024."""
 
     MAX_KEYFRAMES = 64
     MAX_GLOBAL_KEYFRAMES = 1024
+    MAX_GLOBAL_KEYFRAMES_SPARSE = BA_GLOBAL_MAX_KEYFRAMES_SPARSE
 
-    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense"):
+    def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense",
+                 global_linear_solver="dense"):
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
         self.pose_graph_solver = _pg_solver_kind(pose_graph_solver, "HipBackend")    # of Context.set_pose_graph_solver
         if self.pose_graph_solver not in (PG_SOLVER_DENSE, PG_SOLVER_SPARSE):
             raise MslamHipError(E_INVALID, "HipBackend: pose_graph_solver %r is not dense / sparse" % (pose_graph_solver,))
         self.global_solver = bool(global_solver)
+        self.global_linear_solver = _pg_solver_kind(global_linear_solver, "HipBackend")    # of Context.set_ba_global_solver
+        if self.global_linear_solver not in (BA_GLOBAL_SOLVER_DENSE, BA_GLOBAL_SOLVER_SPARSE):
+            raise MslamHipError(E_INVALID, "HipBackend: global_linear_solver %r is not dense / sparse" % (global_linear_solver,))
         self.loss = None if loss is None else (loss[0], float(loss[1]))    # (kind, scale) of Context.set_ba_loss
         self.poses = {}       # id -> [7]
         self.obs = {}         # id -> (landmark ids [n] i64, camera points [n, 3])
@@ -1642,13 +1699,21 @@ class HipBackend:
         return self._solve_pruned(self.neighbours(ref_id, graph, 1), False, prune)
 
     def global_ba(self, prune=False):
-        """globalBundleAdjustment (:173-183) over every keyframe; more than 64 (1024 with global_solver) is
-        MslamHipError(E_CAPACITY), raised before the context is touched: the reduced system is dense.  prune: see the
-        class docstring"""
-        cap = self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
+        """globalBundleAdjustment (:173-183) over every keyframe; more than 64 (with global_solver 1024: the reduced system is
+        dense; 16384 with global_linear_solver = "sparse" too) is MslamHipError(E_CAPACITY), raised before the context is
+        touched.  prune: see the class docstring"""
+        sparse = self.global_solver and self.global_linear_solver == BA_GLOBAL_SOLVER_SPARSE
+        cap = self.MAX_GLOBAL_KEYFRAMES_SPARSE if sparse else self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
         if len(self.poses) > cap:
             raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
-        return self._solve_pruned(sorted(self.poses), self.global_solver, prune)
+        if not sparse:
+            return self._solve_pruned(sorted(self.poses), self.global_solver, prune)
+        before = self.ctx.get_ba_global_solver()
+        self.ctx.set_ba_global_solver(BA_GLOBAL_SOLVER_SPARSE)
+        try:
+            return self._solve_pruned(sorted(self.poses), True, prune)
+        finally:
+            self.ctx.set_ba_global_solver(before)
 
     def fuse(self, keep_lids, drop_lids):
         """landmark fusion's bookkeeping: every observation of drop_lids[p] becomes one of keep_lids[p] (simultaneously, the
@@ -1798,7 +1863,9 @@ class HipKeyframeTracker:
     kf_update_world follow.  self.loop_results holds every attempt; the frame's dict gains loop = (cur, loop) or None.
     pose_graph_solver = "dense" (the default) or "sparse" goes to the backend: close_loop then takes up to 1024 or up to
     16384 keyframes (HipBackend; Context.set_pose_graph_solver).  The optional global solve behind a closure
-    (loop_global_ba) keeps its own cap of 1024 keyframes and its behaviour in both modes.
+    (loop_global_ba) has its own setting, whatever pose_graph_solver is: ba_global_solver = "dense" (the default: a cap of
+    1024 keyframes, the behaviour it had) or "sparse" (HipBackend(global_linear_solver="sparse"); Context.set_ba_global_solver:
+    up to 16384 keyframes, the reduced camera system on its block envelope).
     Without loop_fusion the new keyframe's landmarks keep their own ids, so no covisibility edge joins the two keyframes and
     the loop is known to the pose graph of that one call only.
 
@@ -1893,7 +1960,7 @@ class HipKeyframeTracker:
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
-                 pose_graph_solver="dense"):
+                 pose_graph_solver="dense", ba_global_solver="dense"):
         self.ctx = ctx
         if union_descriptor is not None:
             if local_map_depth is None:
@@ -1940,7 +2007,7 @@ class HipKeyframeTracker:
         self._last_closure = None    # the keyframe at which the last loop was closed
         # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
         self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss,
-                                  pose_graph_solver=pose_graph_solver) if local_ba else None
+                                  pose_graph_solver=pose_graph_solver, global_linear_solver=ba_global_solver) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)

@@ -167,6 +167,9 @@ struct mslam_hip_ctx
     mslam::DevBuf<uint8_t> d_pg;
     // mslam_hip_set_pose_graph_solver: read by mslam_hip_pose_graph when it is called
     int pg_solver = MSLAM_HIP_PG_SOLVER_DENSE;
+    // mslam_hip_set_ba_global_solver: read by mslam_hip_bundle_adjust_global when it is called; SPARSE keeps the envelope in
+    // d_ba_S
+    int bag_solver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

@@ -38,7 +38,15 @@
 // instantiation that applies w_m to every product of observation m (V, g_l, U, g_c, W, the model term) and rho to the costs;
 // each recomputes w_m from ba_residual, so all three use the same bits.  Everything else reads only what these store.
 // With NONE the instantiations of before are launched.  DESIGN.md 4.22.
+//
+// mslam_hip_set_ba_global_solver (an extension, read by mslam_hip_bundle_adjust_global alone): with SPARSE the reduced camera
+// system lives on its block envelope (pg_sparse.hpp).  The host lists the covisible pairs without a K x K table, orders the
+// covisibility graph of the free observed keyframes (pg_symbolic with a node mask: a keyframe without a partner is a row of
+// degree 0) and makes ci the position in that order; k_bag_schur_env, the third form of ba_schur_pair, writes every pair's
+// block into its envelope slot, and k_pgs_clear / k_pgs_factor / k_pgs_backsolve of k_pg_sparse.hip stand where the blocked
+// solver stands.  Every other kernel is the one DENSE launches.  With DENSE the launches of before.  DESIGN.md 4.26.
 #include "chol_solver.hpp"
+#include "pg_sparse.hpp"
 
 #include <algorithm>
 
@@ -74,6 +82,9 @@ struct BaArgs
     // mslam_hip_set_ba_loss: MSLAM_HIP_BA_LOSS_*, and a (metres) of HUBER / CAUCHY
     int loss_kind;
     double loss_scale;
+    // MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE: S is the block envelope (pg_sparse.hpp), ci the position in the chosen order; row i's
+    // first block and first column.  The right-hand side is rhs
+    const int32_t *env_off, *env_first;
 };
 
 __device__ __forceinline__ void ba_residual(const double* __restrict__ pose, const double* __restrict__ X, const double* __restrict__ obs,
@@ -316,8 +327,11 @@ __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
 
 // kBlocked = false: S is n x n, both halves written, the right-hand side in a.rhs (k_ba_solve).  kBlocked = true: S has the
 // leading dimension a.ld, only the lower half is written (an off-diagonal block as its transpose), and the right-hand side
-// is row a.n_pad of S (the k_bag_* kernels).
-template <bool kBlocked>
+// is row a.n_pad of S (the k_bag_* kernels).  kEnv = true (with kBlocked = false): S is the block envelope of pg_sparse.hpp,
+// b1 and b2 are positions in the chosen order; the block of (row, column), row >= column, lies at env_off[row] + column -
+// env_first[row], row-major inside; a pair whose first keyframe comes later in the order is written transposed, of a diagonal
+// block only the lower triangle; the right-hand side in a.rhs.
+template <bool kBlocked, bool kEnv = false>
 __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
 {
     const TrCtrl* ct = a.ctrl;
@@ -408,11 +422,26 @@ __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
             if(r == c)
                 v = (u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius) - mine;
         }
-        const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
-        if(!kBlocked || diag)
-            a.S[row + col * n] = v;
-        if(!diag)
-            a.S[col + row * n] = v;
+        if constexpr(kEnv)
+        {
+            if(diag)
+            {
+                if(c <= r)
+                    a.S[(size_t)(a.env_off[b1] + b1 - a.env_first[b1]) * 36 + r * 6 + c] = v;
+            }
+            else if(b2 > b1)
+                a.S[(size_t)(a.env_off[b2] + b1 - a.env_first[b2]) * 36 + c * 6 + r] = v;
+            else
+                a.S[(size_t)(a.env_off[b1] + b2 - a.env_first[b1]) * 36 + r * 6 + c] = v;
+        }
+        else
+        {
+            const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
+            if(!kBlocked || diag)
+                a.S[row + col * n] = v;
+            if(!diag)
+                a.S[col + row * n] = v;
+        }
     }
     else if(diag && lane < 42)
     {
@@ -668,39 +697,39 @@ __global__ __launch_bounds__(256) void k_ba_landmarks_loss(BaArgs a) { ba_landma
 __global__ __launch_bounds__(256) void k_ba_cameras_loss(BaArgs a) { ba_cameras_rows<true>(a); }
 __global__ __launch_bounds__(256) void k_ba_eval_loss(BaArgs a, int at_start) { ba_eval_rows<true>(a, at_start); }
 
+// ---- the reduced system of mslam_hip_bundle_adjust_global on its block envelope (MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE) -----------
+// After the kernels above, for the same reason.  One wave per covisible pair; k_pgs_clear has zeroed the blocks no pair
+// writes (the fill-in) before it, k_pgs_factor and k_pgs_backsolve follow (pg_sparse_solve).  DESIGN.md 4.26.
+__global__ __launch_bounds__(64) void k_bag_schur_env(BaArgs a) { ba_schur_pair<false, true>(a); }
+
 } // namespace mslam
 
 using namespace mslam;
 
-// Both entry points.  blocked = false: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_solve, S inside d_ba);
-// blocked = true: mslam_hip_bundle_adjust_global (covisible pairs, the k_bag_* kernels, S in d_ba_S).
-static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
-                  const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M, int max_iterations,
-                  double outlier_threshold, uint8_t* outlier, mslam_hip_ba_summary* summary)
+// the first observation that names a keyframe or landmark out of range, -1: none
+static int ba_bad_observation(int K, int L, const int32_t* obs_kf, const int32_t* obs_lm, int M)
 {
-    if(!c)
-        return MSLAM_HIP_E_INVALID;
-    if(K < 0 || K > (blocked ? kBagMaxKeyframes : kBaMaxKeyframes))
-        return fail(c, MSLAM_HIP_E_INVALID, blocked ? "bundle_adjust_global: K outside 0..1024" : "bundle_adjust: K outside 0..64");
-    if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !poses) ||
-       (L > 0 && !landmarks) || (M > 0 && (!obs_kf || !obs_lm || !obs_cam)))
-        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: bad argument (counts, pointers, max_iterations >= 0, threshold >= 0)");
     for(int m = 0; m < M; ++m)
         if(obs_kf[m] < 0 || obs_kf[m] >= K || obs_lm[m] < 0 || obs_lm[m] >= L)
-            return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: observation " + std::to_string(m) + " names a keyframe or landmark out of range");
-    for(int k = 0; k < K; ++k)
-        if(!tr_unit_quaternion(poses + (size_t)k * 7))
-            return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: the quaternion of pose " + std::to_string(k) + " is not unit");
-    mslam_hip_ba_summary sum{};
-    if(M == 0)
-    {
-        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
-        if(summary)
-            *summary = sum;
-        return MSLAM_HIP_OK;
-    }
+            return m;
+    return -1;
+}
+
+// the host's view of the observations: both orders, and the free keyframes that have an observation
+struct BaRows
+{
+    std::vector<int32_t> lm_ptr, lm_obs;         // observations by landmark (rows in input order)
+    std::vector<int32_t> kf_ptr, kf_obs, kf_lm;  // observations by keyframe, every row sorted by landmark
+    std::vector<int32_t> ci;                     // [K] the keyframe's block in index order, -1: constant or unobserved
+    int n_free = 0;
+};
+
+static void ba_rows(const uint8_t* fixed, int K, int L, const int32_t* obs_kf, const int32_t* obs_lm, int M, BaRows& rw)
+{
+    std::vector<int32_t>&lm_ptr = rw.lm_ptr, &lm_obs = rw.lm_obs, &kf_ptr = rw.kf_ptr, &kf_obs = rw.kf_obs, &kf_lm = rw.kf_lm;
     // the two orders of the observations, by stable counting sorts: by landmark; by keyframe with rows sorted by landmark
-    std::vector<int32_t> lm_ptr((size_t)L + 1, 0), lm_obs((size_t)M), kf_ptr((size_t)K + 1, 0), kf_obs((size_t)M), kf_lm((size_t)M);
+    lm_ptr.assign((size_t)L + 1, 0), lm_obs.assign((size_t)M, 0), kf_ptr.assign((size_t)K + 1, 0), kf_obs.assign((size_t)M, 0);
+    kf_lm.assign((size_t)M, 0);
     for(int m = 0; m < M; ++m)
         ++lm_ptr[(size_t)obs_lm[m] + 1], ++kf_ptr[(size_t)obs_kf[m] + 1];
     for(int l = 0; l < L; ++l)
@@ -719,13 +748,102 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
             kf_obs[(size_t)pos] = m, kf_lm[(size_t)pos] = obs_lm[m];
         }
     }
-    std::vector<int32_t> ci((size_t)K, -1), pairs;
-    std::vector<uint8_t> lm_active((size_t)L, 0);
-    int n_free = 0;
+    rw.ci.assign((size_t)K, -1);
+    rw.n_free = 0;
     for(int k = 0; k < K; ++k)
         if(!(fixed && fixed[k]) && kf_ptr[(size_t)k + 1] > kf_ptr[(size_t)k])
-            ci[(size_t)k] = n_free++;
-    if(!blocked)
+            rw.ci[(size_t)k] = rw.n_free++;
+}
+
+// The symbolic phase of MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE (mslam_hip_bundle_adjust_global_analyze exposes it).  pairs: the
+// covisible pairs k1 <= k2 of free observed keyframes, every diagonal pair included, sorted by (k1, k2), each once: the list
+// the bit table of the DENSE path reads out, built without a K x K pass.  Keyframe k1 walks its row, and for every landmark of
+// it that landmark's row, and notes each later keyframe the first time it meets it (a stamp per keyframe): sum over the
+// landmarks of views^2 steps and O(K) memory, then a sort per keyframe.  The nodes are the free observed keyframes, the edges
+// the pairs off the diagonal; pg_symbolic gives the two orders and keeps the smaller envelope.
+static void ba_symbolic(const uint8_t* fixed, int K, const int32_t* obs_kf, const BaRows& rw, std::vector<int32_t>& pairs, PgSymbolic& sy)
+{
+    std::vector<int32_t> stamp((size_t)K, -1), later, ea, eb;
+    std::vector<uint8_t> node((size_t)K, 0);
+    pairs.clear();
+    for(int k1 = 0; k1 < K; ++k1)
+    {
+        if(rw.ci[(size_t)k1] < 0)
+            continue;
+        node[(size_t)k1] = 1;
+        later.clear();
+        for(int pos = rw.kf_ptr[(size_t)k1]; pos < rw.kf_ptr[(size_t)k1 + 1]; ++pos)
+        {
+            const int l = rw.kf_lm[(size_t)pos];
+            if(pos > rw.kf_ptr[(size_t)k1] && rw.kf_lm[(size_t)pos - 1] == l)
+                continue; // the landmark twice in this keyframe: its row has been walked
+            for(int i = rw.lm_ptr[(size_t)l]; i < rw.lm_ptr[(size_t)l + 1]; ++i)
+            {
+                const int k2 = obs_kf[rw.lm_obs[(size_t)i]];
+                if(k2 > k1 && rw.ci[(size_t)k2] >= 0 && stamp[(size_t)k2] != k1)
+                    stamp[(size_t)k2] = k1, later.push_back(k2);
+            }
+        }
+        std::sort(later.begin(), later.end());
+        pairs.push_back(k1), pairs.push_back(k1);
+        for(const int32_t k2 : later)
+        {
+            pairs.push_back(k1), pairs.push_back(k2);
+            ea.push_back(k1), eb.push_back(k2);
+        }
+    }
+    pg_symbolic(fixed, K, ea.data(), eb.data(), ea.size(), sy, node.data());
+}
+
+// Both entry points.  blocked = false: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_solve, S inside d_ba);
+// blocked = true: mslam_hip_bundle_adjust_global (covisible pairs, S in d_ba_S): with solver DENSE the k_bag_* kernels, with
+// SPARSE k_bag_schur_env and the envelope factor of pg_sparse.hpp.
+static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
+                  const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M, int max_iterations,
+                  double outlier_threshold, uint8_t* outlier, mslam_hip_ba_summary* summary)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    const bool sparse = blocked && c->bag_solver == MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE;
+    if(K < 0 || K > (sparse ? MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE : blocked ? kBagMaxKeyframes : kBaMaxKeyframes))
+        return fail(c, MSLAM_HIP_E_INVALID, sparse    ? "bundle_adjust_global: K outside 0..16384 (the SPARSE solver)"
+                                            : blocked ? "bundle_adjust_global: K outside 0..1024"
+                                                      : "bundle_adjust: K outside 0..64");
+    if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !poses) ||
+       (L > 0 && !landmarks) || (M > 0 && (!obs_kf || !obs_lm || !obs_cam)))
+        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: bad argument (counts, pointers, max_iterations >= 0, threshold >= 0)");
+    if(const int m = ba_bad_observation(K, L, obs_kf, obs_lm, M); m >= 0)
+        return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: observation " + std::to_string(m) + " names a keyframe or landmark out of range");
+    for(int k = 0; k < K; ++k)
+        if(!tr_unit_quaternion(poses + (size_t)k * 7))
+            return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: the quaternion of pose " + std::to_string(k) + " is not unit");
+    mslam_hip_ba_summary sum{};
+    if(M == 0)
+    {
+        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
+        if(summary)
+            *summary = sum;
+        return MSLAM_HIP_OK;
+    }
+    BaRows rw;
+    ba_rows(fixed, K, L, obs_kf, obs_lm, M, rw);
+    std::vector<int32_t>&lm_ptr = rw.lm_ptr, &lm_obs = rw.lm_obs, &kf_ptr = rw.kf_ptr, &kf_obs = rw.kf_obs, &kf_lm = rw.kf_lm, &ci = rw.ci;
+    std::vector<int32_t> pairs;
+    std::vector<uint8_t> lm_active((size_t)L, 0);
+    const int n_free = rw.n_free;
+    PgSymbolic sy;
+    if(sparse)
+    {
+        // the order and the envelope; a keyframe's block is its position in the order
+        ba_symbolic(fixed, K, obs_kf, rw, pairs, sy);
+        if(sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS)
+            return fail(c, MSLAM_HIP_E_CAPACITY, "bundle_adjust_global: the envelope needs " + std::to_string(sy.blocks) + " blocks, at most " +
+                                                     std::to_string(MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS) + " per solve");
+        pg_layout(sy);
+        for(int i = 0; i < n_free; ++i)
+            ci[(size_t)sy.order[(size_t)i]] = i;
+    }
+    else if(!blocked)
     {
         for(int k1 = 0; k1 < K; ++k1)
             for(int k2 = k1; k2 < K; ++k2)
@@ -779,15 +897,20 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     const size_t o_lobs = st.put(lm_obs.data(), (size_t)M * 4), o_kptr = st.put(kf_ptr.data(), ((size_t)K + 1) * 4);
     const size_t o_kobs = st.put(kf_obs.data(), (size_t)M * 4), o_klm = st.put(kf_lm.data(), (size_t)M * 4), o_ci = st.put(ci.data(), (size_t)K * 4);
     const size_t o_pairs = st.put(pairs.data(), pairs.size() * 4), o_act = st.put(lm_active.data(), (size_t)L);
+    // the envelope's layout: nothing with DENSE, whose block keeps the offsets it had
+    const size_t o_roff = st.put(sy.row_off.data(), sy.row_off.size() * 4), o_first = st.put(sy.first.data(), sparse ? (size_t)n_free * 4 : 0);
+    const size_t o_cptr = st.put(sy.col_ptr.data(), sy.col_ptr.size() * 4), o_cblk = st.put(sy.col_blk.data(), sy.col_blk.size() * 4);
+    const size_t o_crow = st.put(sy.col_row.data(), sy.col_row.size() * 4);
     const size_t o_pose0 = st.carve((size_t)K * 56), o_lm0 = st.carve((size_t)L * 24), o_cpose = st.carve((size_t)K * 56), o_clm = st.carve((size_t)L * 24);
     const size_t o_V = st.carve((size_t)L * 48), o_gl = st.carve((size_t)L * 24), o_Vinv = st.carve((size_t)L * 48), o_sl = st.carve((size_t)L * 24);
     const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_W = st.carve((size_t)M * 144);
     const size_t o_S = st.carve(blocked ? 0 : (size_t)a.n * a.n * 8), o_rhs = st.carve((size_t)a.n * 8), o_yc = st.carve((size_t)a.n * 8);
     const size_t o_yl = st.carve((size_t)L * 24), o_part = st.carve((size_t)a.n_blocks * 16), o_out = st.carve((size_t)M);
+    const size_t o_dinv = st.carve(sparse ? (size_t)a.n * 8 : 0);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
     MSLAM_CHK(c, grow(c->d_ba, st.size, c->stream));
     if(blocked)
-        MSLAM_CHK(c, grow(c->d_ba_S, (size_t)a.ld * a.n_pad, c->stream));
+        MSLAM_CHK(c, grow(c->d_ba_S, sparse ? (size_t)sy.blocks * 36 : (size_t)a.ld * a.n_pad, c->stream));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
     uint8_t* d = c->d_ba;
@@ -811,6 +934,8 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     const bool loss = a.loss_kind != MSLAM_HIP_BA_LOSS_NONE;
     *c->h_ba.get() = 0;
     const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
+    a.env_off = i32(o_roff), a.env_first = i32(o_first);
+    const PgsArgs env{n_free, sy.blocks, a.env_off, a.env_first, i32(o_cptr), i32(o_cblk), i32(o_crow), a.S, a.rhs, dbl(o_dinv), a.yc, a.ctrl};
 
     const dim3 g_lm((unsigned)((L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((K + L + 255) / 256));
     {
@@ -830,6 +955,8 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
             StageScope tk(c, "solver_factor_subst");
             hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
         }
+        else if(a.n_pairs > 0 && sparse)
+            pg_sparse_solve(c, env, s, [&] { hipLaunchKernelGGL(k_bag_schur_env, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
         else if(a.n_pairs > 0)
         {
             // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
@@ -885,6 +1012,59 @@ extern "C" int mslam_hip_bundle_adjust_global(mslam_hip_ctx* c, double* poses, c
 {
     return ba_run(c, true, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
                   summary);
+}
+
+// The symbolic phase of the SPARSE solver without a context or a GPU: the argument checks of the solve, ba_rows, ba_symbolic
+extern "C" int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed, int K, const int32_t* obs_kf, const int32_t* obs_lm, int M,
+                                                      int L, int32_t* order, int32_t* first, int* n_free, int* ordering,
+                                                      int64_t* envelope_blocks, int* n_pairs)
+{
+    if(K < 0 || K > MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE || L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) ||
+       (M > 0 && (!obs_kf || !obs_lm)))
+        return MSLAM_HIP_E_INVALID;
+    if(ba_bad_observation(K, L, obs_kf, obs_lm, M) >= 0)
+        return MSLAM_HIP_E_INVALID;
+    BaRows rw;
+    ba_rows(fixed, K, L, obs_kf, obs_lm, M, rw);
+    std::vector<int32_t> pairs;
+    PgSymbolic sy;
+    ba_symbolic(fixed, K, obs_kf, rw, pairs, sy);
+    for(int i = 0; i < sy.n_free; ++i)
+    {
+        if(order)
+            order[i] = sy.order[(size_t)i];
+        if(first)
+            first[i] = sy.first[(size_t)i];
+    }
+    if(n_free)
+        *n_free = sy.n_free;
+    if(ordering)
+        *ordering = sy.ordering;
+    if(envelope_blocks)
+        *envelope_blocks = sy.blocks;
+    if(n_pairs)
+        *n_pairs = (int)(pairs.size() / 2);
+    return sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS ? MSLAM_HIP_E_CAPACITY : MSLAM_HIP_OK;
+}
+
+// The linear solver of mslam_hip_bundle_adjust_global: context state, read when it is called
+extern "C" int mslam_hip_set_ba_global_solver(mslam_hip_ctx* c, int kind)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind != MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE && kind != MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE)
+        return fail(c, MSLAM_HIP_E_INVALID, "set_ba_global_solver: kind outside 0..1");
+    c->bag_solver = kind;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_ba_global_solver(mslam_hip_ctx* c, int* kind)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind)
+        *kind = c->bag_solver;
+    return MSLAM_HIP_OK;
 }
 
 // The loss of both entry points above: context state, read when they are called

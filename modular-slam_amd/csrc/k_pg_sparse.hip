@@ -4,7 +4,8 @@
 //
 // Symbolic phase (host, per call): pg_symbolic computes the NATURAL and the RCM order of the free poses that have an edge and
 // keeps the one with the smaller envelope; pg_layout gives every row its offset and every column the list of the rows whose
-// envelope holds it.  mslam_hip_pose_graph_analyze exposes the first without a context.
+// envelope holds it.  mslam_hip_pose_graph_analyze exposes the first without a context.  mslam_hip_bundle_adjust_global's
+// SPARSE solver (k_ba.hip) uses both, with a node mask, and the three kernels below on its reduced camera system.
 //
 // Numeric phase: row i of the lower triangle lies contiguously from column first[i] to i; the right-hand side is one more
 // block column, kept in rhs.  Four launches per solve on one stream; each reads the control block first:
@@ -250,11 +251,15 @@ static int64_t pg_envelope(const std::vector<int32_t>& order, const std::vector<
     return blocks;
 }
 
-void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, int E, PgSymbolic& sy)
+void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, size_t E, PgSymbolic& sy,
+                 const uint8_t* node_mask)
 {
     std::vector<uint8_t> node((size_t)K, 0);
-    for(int e = 0; e < E; ++e)
-        node[(size_t)edge_a[e]] = node[(size_t)edge_b[e]] = 1;
+    if(node_mask)
+        node.assign(node_mask, node_mask + K);
+    else
+        for(size_t e = 0; e < E; ++e)
+            node[(size_t)edge_a[e]] = node[(size_t)edge_b[e]] = 1;
     std::vector<int32_t> natural;
     for(int k = 0; k < K; ++k)
     {
@@ -265,7 +270,7 @@ void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32
     const int n = (int)natural.size();
     // the neighbours of every node, ascending, duplicates once, constant poses left out
     std::vector<std::pair<int32_t, int32_t>> pr;
-    for(int e = 0; e < E; ++e)
+    for(size_t e = 0; e < E; ++e)
         if(node[(size_t)edge_a[e]] && node[(size_t)edge_b[e]])
             pr.push_back({edge_a[e], edge_b[e]}), pr.push_back({edge_b[e], edge_a[e]});
     std::sort(pr.begin(), pr.end());

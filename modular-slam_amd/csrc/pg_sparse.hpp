@@ -21,8 +21,12 @@ struct PgSymbolic
     std::vector<int32_t> row_off, col_ptr, col_blk, col_row;
 };
 
-// the orders and the envelope; the caller has checked K, E, the indices and the self-edges
-void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, int E, PgSymbolic& sy);
+// the orders and the envelope; the caller has checked K, E, the indices and the self-edges.  node_mask (K flags, or nullptr):
+// the nodes are the free poses it marks, with or without an edge (mslam_hip_bundle_adjust_global's SPARSE solver: a free
+// keyframe that shares no landmark is still a row, of degree 0); without it, the free poses that have an edge.  E is a
+// size_t's worth there: a covisibility graph has more edges than a pose graph may
+void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, size_t E, PgSymbolic& sy,
+                 const uint8_t* node_mask = nullptr);
 // row offsets and column lists of an envelope that fits MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS
 void pg_layout(PgSymbolic& sy);
 

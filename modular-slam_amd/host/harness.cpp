@@ -40,6 +40,9 @@
 //        mslam_harness <plugin.so> --ba-global <scene> --loss huber:<a> | cauchy:<a>
 //                                    the same with IRobustBackend::setLoss(kind, a) first (a in metres, finite and > 0): the
 //                                    costs of the summary are then 1/2 sum rho
+//        mslam_harness <plugin.so> --ba-global <scene> --sparse
+//                                    the global solve with ISparseGlobalBackend::setGlobalSolver(1) first: the reduced camera
+//                                    system on its block envelope, up to 16384 keyframes
 //        mslam_harness <plugin.so> --pose-graph <scene>
 //                                    ILoopClosingBackend::closeLoop of the same factory's object on one pose-graph scene: the
 //                                    summary, then every keyframe's state
@@ -165,9 +168,11 @@ int main(int argc, char** argv)
                         result->pose.orientation.z(), inl);
             return 0;
         }
-        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--loss") == 0)) &&
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--loss") == 0) ||
+            (argc == 5 && std::strcmp(argv[4], "--sparse") == 0 && std::strcmp(argv[2], "--ba-global") == 0)) &&
            (std::strcmp(argv[2], "--ba") == 0 || std::strcmp(argv[2], "--ba-global") == 0))
         {
+            const bool sparseSolver = argc == 5;
             int lossKind = 0;
             double lossScale = 0.0;
             if(argc == 6 && !mslam::parseLoss(argv[5], lossKind, lossScale))
@@ -175,7 +180,7 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[5]);
                 return 2;
             }
-            const bool global = std::strcmp(argv[2], "--ba-global") == 0; // IGlobalBackend::globalBundleAdjustment: up to 1024 keyframes
+            const bool global = std::strcmp(argv[2], "--ba-global") == 0; // IGlobalBackend::globalBundleAdjustment: up to 1024 keyframes (--sparse: 16384)
             // scene file: "MSBA", i32 version (1), K, L, M, max_iterations; K x i32 keyframe id; K x 7 f64 state (qx qy qz qw
             // px py pz); L x 3 f64; M x i32 keyframe index; M x i32 landmark index; M x 3 f64 camera-frame point
             std::ifstream in(argv[3], std::ios::binary);
@@ -249,6 +254,16 @@ int main(int argc, char** argv)
                     return 6;
                 }
                 robust->setLoss(lossKind, lossScale);
+            }
+            if(sparseSolver)
+            {
+                auto* sparseBackend = dynamic_cast<mslam::ISparseGlobalBackend*>(backend.get());
+                if(!sparseBackend)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setGlobalSolver\n");
+                    return 6;
+                }
+                sparseBackend->setGlobalSolver(1);
             }
             const mslam::BackendOutput out =
                 global ? globalBackend->globalBundleAdjustment(observations, head[4]) : backend->bundleAdjustment(observations, head[4]);

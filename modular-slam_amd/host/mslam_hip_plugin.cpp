@@ -13,6 +13,7 @@
 //   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
 //                          : IRobustBackend                                       a Huber or Cauchy loss for both bundle adjustments (an extension)
 //                          : ISparsePoseGraphBackend                              closeLoop's linear solver: dense or the block-envelope factor (an extension)
+//                          : ISparseGlobalBackend                                 globalBundleAdjustment's linear solver, the same choice (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -1007,10 +1008,18 @@ class HipMinMseTracker : public ISlam3dPnp
 // globalBundleAdjustment is the same adapter on mslam_hip_bundle_adjust_global: up to 1024 keyframes.  closeLoop hands the
 // keyframes and edges to mslam_hip_pose_graph and writes the corrected states back the same way; setPoseGraphSolver
 // (ISparsePoseGraphBackend, an extension) keeps its linear solver, set on the context before each closeLoop.  setLoss (IRobustBackend,
-// an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.
-class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend
+// an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.  setGlobalSolver
+// (ISparseGlobalBackend, an extension) keeps the linear solver of globalBundleAdjustment, set the same way: with kind 1 up to
+// 16384 keyframes.
+class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend
 {
   public:
+    void setGlobalSolver(int kind) override
+    {
+        if(kind != MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE && kind != MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE)
+            throw std::invalid_argument("setGlobalSolver: kind 0 (dense) or 1 (sparse)");
+        globalSolver = kind;
+    }
     void setPoseGraphSolver(int kind) override
     {
         if(kind != MSLAM_HIP_PG_SOLVER_DENSE && kind != MSLAM_HIP_PG_SOLVER_SPARSE)
@@ -1130,6 +1139,8 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
         const int lrc = mslam_hip_set_ba_loss(ctx.h, lossKind, lossScale);
         if(lrc != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_set_ba_loss", lrc);
+        if(const int rs = mslam_hip_set_ba_global_solver(ctx.h, globalSolver); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_ba_global_solver", rs);
         const int rc = entry(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
                              static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
                              static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
@@ -1159,6 +1170,7 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
 
     Ctx ctx;
     int poseGraphSolver = MSLAM_HIP_PG_SOLVER_DENSE;
+    int globalSolver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;
     int lossKind = MSLAM_HIP_BA_LOSS_NONE;
     double lossScale = 0.0;
 };

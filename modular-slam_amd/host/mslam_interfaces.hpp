@@ -276,6 +276,18 @@ class ISparsePoseGraphBackend
     virtual void setPoseGraphSolver(int kind) = 0;
     virtual ~ISparsePoseGraphBackend() = default;
 };
+// extension: the linear solver of globalBundleAdjustment (mslam_hip_set_ba_global_solver): kind 0 dense (the default: the
+// blocked Cholesky of the dense reduced camera system, up to 1024 keyframes), 1 sparse (the reduced camera system on its block
+// envelope after a NATURAL or reverse Cuthill-McKee order of the covisibility graph: up to 16384 keyframes, an envelope of up
+// to 1048576 blocks).  It holds for every later globalBundleAdjustment of the object; bundleAdjustment and closeLoop do not
+// read it.  A kind outside 0..1 throws std::invalid_argument and leaves the setting as it was.  An interface of its own,
+// reached with dynamic_cast like ISparsePoseGraphBackend.
+class ISparseGlobalBackend
+{
+  public:
+    virtual void setGlobalSolver(int kind) = 0;
+    virtual ~ISparseGlobalBackend() = default;
+};
 // "huber:<a>" or "cauchy:<a>" -> kind 1 or 2 and a; false (nothing written) for anything else, a trailing character or an a
 // that is not finite or not > 0
 inline bool parseLoss(const char* text, int& kind, double& scale)
