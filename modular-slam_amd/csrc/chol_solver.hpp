@@ -1,5 +1,6 @@
 // chol_solver.hpp — the blocked f64 Cholesky solve of k_chol.hip.  mslam_hip_bundle_adjust_global (k_ba.hip) solves its
-// reduced camera system through it, mslam_hip_pose_graph (k_posegraph.hip) its damped normal equations.
+// reduced camera system through it, mslam_hip_pose_graph (k_posegraph.hip) its damped normal equations, both with their DENSE
+// solver and both through LinearSolve of reduced_system.hpp, whose SysView<SysLayout::PaddedLower> is the layout of S below.
 #pragma once
 #include "trust_region.hpp"
 

@@ -45,8 +45,13 @@
 // degree 0) and makes ci the position in that order; k_bag_schur_env, the third form of ba_schur_pair, writes every pair's
 // block into its envelope slot, and k_pgs_clear / k_pgs_factor / k_pgs_backsolve of k_pg_sparse.hip stand where the blocked
 // solver stands.  Every other kernel is the one DENSE launches.  With DENSE the launches of before.  DESIGN.md 4.26.
-#include "chol_solver.hpp"
-#include "pg_sparse.hpp"
+//
+// ba_schur_pair has one form per layout of the reduced system (SysLayout of reduced_system.hpp: Full for k_ba_schur,
+// PaddedLower for k_bag_schur, Envelope for k_bag_schur_env) and stores through SysView; on the host ba_run decides one BaMode
+// (local, global dense, global sparse) and runs in parts: ba_validate, ba_rows, a pair lister (ba_pairs_all, ba_pairs_table,
+// ba_symbolic), ba_stage, the iteration, ba_read_back.  The global modes take cap, block index, envelope staging, sizes and
+// the solve from LinearSolve (reduced_system.hpp), which mslam_hip_pose_graph uses too.
+#include "reduced_system.hpp"
 
 #include <algorithm>
 
@@ -54,7 +59,6 @@ namespace mslam
 {
 
 constexpr int kBaMaxKeyframes = 64;
-constexpr int kBagMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES; // mslam_hip_bundle_adjust_global: 6144^2 doubles = 302 MB
 constexpr int kBaSolveThreads = 6 * kBaMaxKeyframes; // one thread per row of the reduced system
 
 struct BaArgs
@@ -130,6 +134,15 @@ __device__ __forceinline__ double ba_weight(const BaArgs& a, const double r[3])
     ba_loss(a.loss_kind, a.loss_scale, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho, w);
     return w;
 }
+// a product of observation m: w x with a loss, x itself (no multiplication by 1) without; w is then not evaluated by the caller
+template <bool kLoss>
+__device__ __forceinline__ double ba_weighted(double w, double x)
+{
+    if constexpr(kLoss)
+        return w * x;
+    else
+        return x;
+}
 // J_c = [2 R^T [d]x | -R^T] (3 x 6), d = X - p
 __device__ __forceinline__ void ba_camera_jacobian(const double Rt[9], const double d[3], double Jc[3][6])
 {
@@ -170,22 +183,14 @@ __device__ __forceinline__ void ba_landmarks_rows(const BaArgs& a)
             quat_inverse(pose, qi);
             quat_matrix(qi, Rt);
             ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
+            double w = 1.0; // read only with a loss.  Constant keyframes too: their rows are part of V and g_l
             if constexpr(kLoss)
-            {
-                const double w = ba_weight(a, r); // constant keyframes too: their rows are part of V and g_l
-                for(int rr = 0; rr < 3; ++rr)
-                {
-                    for(int c = rr; c < 3; ++c)
-                        V[tri3(rr, c)] += w * (Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c]);
-                    g[rr] += w * (Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2]);
-                }
-                continue;
-            }
+                w = ba_weight(a, r);
             for(int rr = 0; rr < 3; ++rr)
             {
                 for(int c = rr; c < 3; ++c)
-                    V[tri3(rr, c)] += Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c];
-                g[rr] += Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2];
+                    V[tri3(rr, c)] += ba_weighted<kLoss>(w, Rt[rr] * Rt[c] + Rt[3 + rr] * Rt[3 + c] + Rt[6 + rr] * Rt[6 + c]);
+                g[rr] += ba_weighted<kLoss>(w, Rt[rr] * r[0] + Rt[3 + rr] * r[1] + Rt[6 + rr] * r[2]);
             }
         }
         for(int k = 0; k < 6; ++k)
@@ -248,29 +253,18 @@ __device__ __forceinline__ void ba_cameras_rows(const BaArgs& a)
         ba_residual(pose, X, a.obs_cam + (size_t)m * 3, r);
         ba_camera_jacobian(Rt, d, Jc);
         int j = 0;
+        double w = 1.0; // read only with a loss
         if constexpr(kLoss)
-        {
-            const double w = ba_weight(a, r);
-            for(int rr = 0; rr < 6; ++rr)
-                for(int c = rr; c < 6; ++c)
-                    acc[j++] += w * (Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c]);
-            for(int rr = 0; rr < 6; ++rr)
-                acc[21 + rr] += w * (Jc[0][rr] * r[0] + Jc[1][rr] * r[1] + Jc[2][rr] * r[2]);
-            double* W = a.W + (size_t)m * 18;
-            for(int rr = 0; rr < 6; ++rr)
-                for(int c = 0; c < 3; ++c)
-                    W[rr * 3 + c] = w * (Jc[0][rr] * Rt[c] + Jc[1][rr] * Rt[3 + c] + Jc[2][rr] * Rt[6 + c]);
-            continue;
-        }
+            w = ba_weight(a, r);
         for(int rr = 0; rr < 6; ++rr)
             for(int c = rr; c < 6; ++c)
-                acc[j++] += Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c];
+                acc[j++] += ba_weighted<kLoss>(w, Jc[0][rr] * Jc[0][c] + Jc[1][rr] * Jc[1][c] + Jc[2][rr] * Jc[2][c]);
         for(int rr = 0; rr < 6; ++rr)
-            acc[21 + rr] += Jc[0][rr] * r[0] + Jc[1][rr] * r[1] + Jc[2][rr] * r[2];
+            acc[21 + rr] += ba_weighted<kLoss>(w, Jc[0][rr] * r[0] + Jc[1][rr] * r[1] + Jc[2][rr] * r[2]);
         double* W = a.W + (size_t)m * 18; // J_c^T J_l, J_l = R^T
         for(int rr = 0; rr < 6; ++rr)
             for(int c = 0; c < 3; ++c)
-                W[rr * 3 + c] = Jc[0][rr] * Rt[c] + Jc[1][rr] * Rt[3 + c] + Jc[2][rr] * Rt[6 + c];
+                W[rr * 3 + c] = ba_weighted<kLoss>(w, Jc[0][rr] * Rt[c] + Jc[1][rr] * Rt[3 + c] + Jc[2][rr] * Rt[6 + c]);
     }
     for(int j = 0; j < 27; ++j)
     {
@@ -325,13 +319,10 @@ __global__ __launch_bounds__(64) void k_ba_check(BaArgs a)
 
 // ---- the reduced camera system ------------------------------------------------------------------------------------------
 
-// kBlocked = false: S is n x n, both halves written, the right-hand side in a.rhs (k_ba_solve).  kBlocked = true: S has the
-// leading dimension a.ld, only the lower half is written (an off-diagonal block as its transpose), and the right-hand side
-// is row a.n_pad of S (the k_bag_* kernels).  kEnv = true (with kBlocked = false): S is the block envelope of pg_sparse.hpp,
-// b1 and b2 are positions in the chosen order; the block of (row, column), row >= column, lies at env_off[row] + column -
-// env_first[row], row-major inside; a pair whose first keyframe comes later in the order is written transposed, of a diagonal
-// block only the lower triangle; the right-hand side in a.rhs.
-template <bool kBlocked, bool kEnv = false>
+// The block of a pair and, on the diagonal, the reduced right-hand side, stored through SysView (reduced_system.hpp): Full for
+// k_ba_solve, PaddedLower for the blocked solve, Envelope for the envelope factor, where b1 and b2 are positions in the chosen
+// order and of a diagonal block only the lower triangle is written.
+template <SysLayout kLayout>
 __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
 {
     const TrCtrl* ct = a.ctrl;
@@ -410,7 +401,7 @@ __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
             if(lane == 36 + j)
                 mine = v;
         }
-    const size_t n = kBlocked ? (size_t)a.ld : (size_t)a.n;
+    const SysView<kLayout> sys(a);
     if(lane < 36)
     {
         const int r = lane / 6, c = lane % 6;
@@ -422,39 +413,16 @@ __device__ __forceinline__ void ba_schur_pair(const BaArgs& a)
             if(r == c)
                 v = (u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius) - mine;
         }
-        if constexpr(kEnv)
-        {
-            if(diag)
-            {
-                if(c <= r)
-                    a.S[(size_t)(a.env_off[b1] + b1 - a.env_first[b1]) * 36 + r * 6 + c] = v;
-            }
-            else if(b2 > b1)
-                a.S[(size_t)(a.env_off[b2] + b1 - a.env_first[b2]) * 36 + c * 6 + r] = v;
-            else
-                a.S[(size_t)(a.env_off[b1] + b2 - a.env_first[b1]) * 36 + r * 6 + c] = v;
-        }
-        else
-        {
-            const size_t row = (size_t)b1 * 6 + r, col = (size_t)b2 * 6 + c;
-            if(!kBlocked || diag)
-                a.S[row + col * n] = v;
-            if(!diag)
-                a.S[col + row * n] = v;
-        }
+        sys.store(b1, b2, diag, r, c, v, true);
     }
     else if(diag && lane < 42)
     {
         const int r = lane - 36;
-        const double v = s1[r] * a.gc[(size_t)k1 * 6 + r] - mine;
-        if(kBlocked)
-            a.S[(size_t)a.n_pad + ((size_t)b1 * 6 + r) * n] = v;
-        else
-            a.rhs[(size_t)b1 * 6 + r] = v;
+        sys.store_rhs(b1, r, s1[r] * a.gc[(size_t)k1 * 6 + r] - mine);
     }
 }
 
-__global__ __launch_bounds__(64) void k_ba_schur(BaArgs a) { ba_schur_pair<false>(a); }
+__global__ __launch_bounds__(64) void k_ba_schur(BaArgs a) { ba_schur_pair<SysLayout::Full>(a); }
 
 // Cholesky S = L L^T in place (lower triangle, column-major), then L y = rhs and L^T x = y.  Thread i owns row i.
 __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
@@ -520,7 +488,7 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaArgs a)
 }
 
 // the reduced system of mslam_hip_bundle_adjust_global for the blocked solve (chol_solver.hpp)
-__global__ __launch_bounds__(64) void k_bag_schur(BaArgs a) { ba_schur_pair<true>(a); }
+__global__ __launch_bounds__(64) void k_bag_schur(BaArgs a) { ba_schur_pair<SysLayout::PaddedLower>(a); }
 
 __global__ __launch_bounds__(256) void k_ba_backsub(BaArgs a)
 {
@@ -700,7 +668,7 @@ __global__ __launch_bounds__(256) void k_ba_eval_loss(BaArgs a, int at_start) { 
 // ---- the reduced system of mslam_hip_bundle_adjust_global on its block envelope (MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE) -----------
 // After the kernels above, for the same reason.  One wave per covisible pair; k_pgs_clear has zeroed the blocks no pair
 // writes (the fill-in) before it, k_pgs_factor and k_pgs_backsolve follow (pg_sparse_solve).  DESIGN.md 4.26.
-__global__ __launch_bounds__(64) void k_bag_schur_env(BaArgs a) { ba_schur_pair<false, true>(a); }
+__global__ __launch_bounds__(64) void k_bag_schur_env(BaArgs a) { ba_schur_pair<SysLayout::Envelope>(a); }
 
 } // namespace mslam
 
@@ -795,122 +763,117 @@ static void ba_symbolic(const uint8_t* fixed, int K, const int32_t* obs_kf, cons
     pg_symbolic(fixed, K, ea.data(), eb.data(), ea.size(), sy, node.data());
 }
 
-// Both entry points.  blocked = false: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_solve, S inside d_ba);
-// blocked = true: mslam_hip_bundle_adjust_global (covisible pairs, S in d_ba_S): with solver DENSE the k_bag_* kernels, with
-// SPARSE k_bag_schur_env and the envelope factor of pg_sparse.hpp.
-static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
-                  const int32_t* obs_kf, const int32_t* obs_lm, const double* obs_cam, int M, int max_iterations,
-                  double outlier_threshold, uint8_t* outlier, mslam_hip_ba_summary* summary)
+// every pair k1 <= k2 of free observed keyframes (mslam_hip_bundle_adjust)
+static void ba_pairs_all(int K, const std::vector<int32_t>& ci, std::vector<int32_t>& pairs)
 {
-    if(!c)
-        return MSLAM_HIP_E_INVALID;
-    const bool sparse = blocked && c->bag_solver == MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE;
-    if(K < 0 || K > (sparse ? MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE : blocked ? kBagMaxKeyframes : kBaMaxKeyframes))
-        return fail(c, MSLAM_HIP_E_INVALID, sparse    ? "bundle_adjust_global: K outside 0..16384 (the SPARSE solver)"
-                                            : blocked ? "bundle_adjust_global: K outside 0..1024"
-                                                      : "bundle_adjust: K outside 0..64");
-    if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !poses) ||
-       (L > 0 && !landmarks) || (M > 0 && (!obs_kf || !obs_lm || !obs_cam)))
+    for(int k1 = 0; k1 < K; ++k1)
+        for(int k2 = k1; k2 < K; ++k2)
+            if(ci[(size_t)k1] >= 0 && ci[(size_t)k2] >= 0)
+                pairs.push_back(k1), pairs.push_back(k2);
+}
+
+// The covisible pairs by a K x K bit table (the DENSE solver, K <= 1024): every k1 <= k2 of free keyframes that share a landmark,
+// and every diagonal pair.  A row of W words per keyframe: a landmark's row becomes one bit set, which every keyframe of the
+// row ORs into its own (views x W word operations per landmark, not views^2), read out in (k1, k2) order: sorted, each pair
+// once.  The list ba_symbolic walks out; the host costs differ by shape, so each solver keeps its lister.
+static void ba_pairs_table(int K, int L, const int32_t* obs_kf, const BaRows& rw, std::vector<int32_t>& pairs)
+{
+    const std::vector<int32_t>&lm_ptr = rw.lm_ptr, &lm_obs = rw.lm_obs, &ci = rw.ci;
+    const size_t W = ((size_t)K + 63) / 64;
+    std::vector<uint64_t> shares((size_t)K * W, 0), seen(W);
+    for(int l = 0; l < L; ++l)
+    {
+        if(lm_ptr[(size_t)l + 1] - lm_ptr[(size_t)l] < 2)
+            continue; // one view: only the diagonal pair, which is listed anyway
+        std::fill(seen.begin(), seen.end(), 0);
+        for(int i = lm_ptr[(size_t)l]; i < lm_ptr[(size_t)l + 1]; ++i)
+        {
+            const int k = obs_kf[lm_obs[(size_t)i]];
+            if(ci[(size_t)k] >= 0)
+                seen[(size_t)k >> 6] |= 1ull << (k & 63);
+        }
+        for(size_t w = 0; w < W; ++w)
+            for(uint64_t bits = seen[w]; bits; bits &= bits - 1)
+            {
+                uint64_t* mine = &shares[(w * 64 + (size_t)__builtin_ctzll(bits)) * W];
+                for(size_t v = 0; v < W; ++v)
+                    mine[v] |= seen[v];
+            }
+    }
+    for(int k1 = 0; k1 < K; ++k1)
+        for(int k2 = k1; k2 < K; ++k2)
+            if(ci[(size_t)k1] >= 0 && (k1 == k2 || (shares[(size_t)k1 * W + ((size_t)k2 >> 6)] >> (k2 & 63) & 1)))
+                pairs.push_back(k1), pairs.push_back(k2);
+}
+
+// Local: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_schur, k_ba_solve, S inside d_ba).  The other two:
+// mslam_hip_bundle_adjust_global (covisible pairs, S in d_ba_S) with its solver DENSE (k_bag_schur, the blocked factor) or
+// SPARSE (k_bag_schur_env, the envelope factor).  Decided once, at the top of ba_run.
+enum class BaMode { Local, GlobalDense, GlobalSparse };
+
+// the caller's problem, as the entry points take it
+struct BaProblem
+{
+    double *poses, *landmarks;
+    const uint8_t* fixed;
+    const int32_t *obs_kf, *obs_lm;
+    const double* obs_cam;
+    int K, L, M;
+};
+
+static int ba_validate(mslam_hip_ctx* c, BaMode mode, const BaProblem& p, int k_max, int max_iterations, double outlier_threshold)
+{
+    const int K = p.K, L = p.L, M = p.M;
+    if(K < 0 || K > k_max)
+        return fail(c, MSLAM_HIP_E_INVALID, mode == BaMode::GlobalSparse  ? "bundle_adjust_global: K outside 0..16384 (the SPARSE solver)"
+                                            : mode == BaMode::GlobalDense ? "bundle_adjust_global: K outside 0..1024"
+                                                                          : "bundle_adjust: K outside 0..64");
+    if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !p.poses) ||
+       (L > 0 && !p.landmarks) || (M > 0 && (!p.obs_kf || !p.obs_lm || !p.obs_cam)))
         return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: bad argument (counts, pointers, max_iterations >= 0, threshold >= 0)");
-    if(const int m = ba_bad_observation(K, L, obs_kf, obs_lm, M); m >= 0)
+    if(const int m = ba_bad_observation(K, L, p.obs_kf, p.obs_lm, M); m >= 0)
         return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: observation " + std::to_string(m) + " names a keyframe or landmark out of range");
     for(int k = 0; k < K; ++k)
-        if(!tr_unit_quaternion(poses + (size_t)k * 7))
+        if(!tr_unit_quaternion(p.poses + (size_t)k * 7))
             return fail(c, MSLAM_HIP_E_INVALID, "bundle_adjust: the quaternion of pose " + std::to_string(k) + " is not unit");
-    mslam_hip_ba_summary sum{};
-    if(M == 0)
-    {
-        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
-        if(summary)
-            *summary = sum;
-        return MSLAM_HIP_OK;
-    }
-    BaRows rw;
-    ba_rows(fixed, K, L, obs_kf, obs_lm, M, rw);
-    std::vector<int32_t>&lm_ptr = rw.lm_ptr, &lm_obs = rw.lm_obs, &kf_ptr = rw.kf_ptr, &kf_obs = rw.kf_obs, &kf_lm = rw.kf_lm, &ci = rw.ci;
-    std::vector<int32_t> pairs;
-    std::vector<uint8_t> lm_active((size_t)L, 0);
-    const int n_free = rw.n_free;
-    PgSymbolic sy;
-    if(sparse)
-    {
-        // the order and the envelope; a keyframe's block is its position in the order
-        ba_symbolic(fixed, K, obs_kf, rw, pairs, sy);
-        if(sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS)
-            return fail(c, MSLAM_HIP_E_CAPACITY, "bundle_adjust_global: the envelope needs " + std::to_string(sy.blocks) + " blocks, at most " +
-                                                     std::to_string(MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS) + " per solve");
-        pg_layout(sy);
-        for(int i = 0; i < n_free; ++i)
-            ci[(size_t)sy.order[(size_t)i]] = i;
-    }
-    else if(!blocked)
-    {
-        for(int k1 = 0; k1 < K; ++k1)
-            for(int k2 = k1; k2 < K; ++k2)
-                if(ci[(size_t)k1] >= 0 && ci[(size_t)k2] >= 0)
-                    pairs.push_back(k1), pairs.push_back(k2);
-    }
-    else
-    {
-        // the covisible pairs: every k1 <= k2 of free keyframes that share a landmark, and every diagonal pair.  A K x K bit
-        // table, a row of W words per keyframe: a landmark's row becomes one bit set, which every keyframe of the row ORs
-        // into its own (views x W word operations per landmark, not views^2), read out in (k1, k2) order: sorted, each
-        // pair once
-        const size_t W = ((size_t)K + 63) / 64;
-        std::vector<uint64_t> shares((size_t)K * W, 0), seen(W);
-        for(int l = 0; l < L; ++l)
-        {
-            if(lm_ptr[(size_t)l + 1] - lm_ptr[(size_t)l] < 2)
-                continue; // one view: only the diagonal pair, which is listed anyway
-            std::fill(seen.begin(), seen.end(), 0);
-            for(int i = lm_ptr[(size_t)l]; i < lm_ptr[(size_t)l + 1]; ++i)
-            {
-                const int k = obs_kf[lm_obs[(size_t)i]];
-                if(ci[(size_t)k] >= 0)
-                    seen[(size_t)k >> 6] |= 1ull << (k & 63);
-            }
-            for(size_t w = 0; w < W; ++w)
-                for(uint64_t bits = seen[w]; bits; bits &= bits - 1)
-                {
-                    uint64_t* mine = &shares[(w * 64 + (size_t)__builtin_ctzll(bits)) * W];
-                    for(size_t v = 0; v < W; ++v)
-                        mine[v] |= seen[v];
-                }
-        }
-        for(int k1 = 0; k1 < K; ++k1)
-            for(int k2 = k1; k2 < K; ++k2)
-                if(ci[(size_t)k1] >= 0 && (k1 == k2 || (shares[(size_t)k1 * W + ((size_t)k2 >> 6)] >> (k2 & 63) & 1)))
-                    pairs.push_back(k1), pairs.push_back(k2);
-    }
-    for(int l = 0; l < L; ++l)
-        lm_active[(size_t)l] = lm_ptr[(size_t)l + 1] > lm_ptr[(size_t)l];
+    return MSLAM_HIP_OK;
+}
 
-    BaArgs a{};
-    a.K = K, a.L = L, a.M = M, a.n = 6 * n_free;
+// what the read-back needs beside BaArgs: the kept inputs and the outlier mask, on the device
+struct BaKept
+{
+    double *pose0, *lm0;
+    uint8_t* out;
+};
+
+// Staging and argument wiring: one device block (what is uploaded first, the control block at 0, then the working arrays),
+// S where the mode keeps it, and a filled in.  st is the caller's: the upload reads its host block
+static int ba_stage(mslam_hip_ctx* c, BaMode mode, const BaProblem& p, const BaRows& rw, const std::vector<int32_t>& pairs,
+                    LinearSolve& ls, TrStaging& st, BaArgs& a, BaKept& kept)
+{
+    const int K = p.K, L = p.L, M = p.M;
+    const bool local = mode == BaMode::Local;
+    std::vector<uint8_t> lm_active((size_t)L, 0);
+    for(int l = 0; l < L; ++l)
+        lm_active[(size_t)l] = rw.lm_ptr[(size_t)l + 1] > rw.lm_ptr[(size_t)l];
+    a.K = K, a.L = L, a.M = M, a.n = 6 * rw.n_free, a.n_pad = ls.n_pad, a.ld = ls.ld;
     a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (M + 255) / 256;
-    if(blocked)
-        a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
-    // one block: what is uploaded first (the control block at 0), then the working arrays
-    TrStaging st(max_iterations);
-    const size_t o_pose = st.put(poses, (size_t)K * 56), o_lm = st.put(landmarks, (size_t)L * 24), o_cam = st.put(obs_cam, (size_t)M * 24);
-    const size_t o_okf = st.put(obs_kf, (size_t)M * 4), o_olm = st.put(obs_lm, (size_t)M * 4), o_lptr = st.put(lm_ptr.data(), ((size_t)L + 1) * 4);
-    const size_t o_lobs = st.put(lm_obs.data(), (size_t)M * 4), o_kptr = st.put(kf_ptr.data(), ((size_t)K + 1) * 4);
-    const size_t o_kobs = st.put(kf_obs.data(), (size_t)M * 4), o_klm = st.put(kf_lm.data(), (size_t)M * 4), o_ci = st.put(ci.data(), (size_t)K * 4);
+    const size_t o_pose = st.put(p.poses, (size_t)K * 56), o_lm = st.put(p.landmarks, (size_t)L * 24), o_cam = st.put(p.obs_cam, (size_t)M * 24);
+    const size_t o_okf = st.put(p.obs_kf, (size_t)M * 4), o_olm = st.put(p.obs_lm, (size_t)M * 4), o_lptr = st.put(rw.lm_ptr.data(), ((size_t)L + 1) * 4);
+    const size_t o_lobs = st.put(rw.lm_obs.data(), (size_t)M * 4), o_kptr = st.put(rw.kf_ptr.data(), ((size_t)K + 1) * 4);
+    const size_t o_kobs = st.put(rw.kf_obs.data(), (size_t)M * 4), o_klm = st.put(rw.kf_lm.data(), (size_t)M * 4), o_ci = st.put(rw.ci.data(), (size_t)K * 4);
     const size_t o_pairs = st.put(pairs.data(), pairs.size() * 4), o_act = st.put(lm_active.data(), (size_t)L);
-    // the envelope's layout: nothing with DENSE, whose block keeps the offsets it had
-    const size_t o_roff = st.put(sy.row_off.data(), sy.row_off.size() * 4), o_first = st.put(sy.first.data(), sparse ? (size_t)n_free * 4 : 0);
-    const size_t o_cptr = st.put(sy.col_ptr.data(), sy.col_ptr.size() * 4), o_cblk = st.put(sy.col_blk.data(), sy.col_blk.size() * 4);
-    const size_t o_crow = st.put(sy.col_row.data(), sy.col_row.size() * 4);
+    ls.put(st);
     const size_t o_pose0 = st.carve((size_t)K * 56), o_lm0 = st.carve((size_t)L * 24), o_cpose = st.carve((size_t)K * 56), o_clm = st.carve((size_t)L * 24);
     const size_t o_V = st.carve((size_t)L * 48), o_gl = st.carve((size_t)L * 24), o_Vinv = st.carve((size_t)L * 48), o_sl = st.carve((size_t)L * 24);
     const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_W = st.carve((size_t)M * 144);
-    const size_t o_S = st.carve(blocked ? 0 : (size_t)a.n * a.n * 8), o_rhs = st.carve((size_t)a.n * 8), o_yc = st.carve((size_t)a.n * 8);
+    const size_t o_S = st.carve(local ? (size_t)a.n * a.n * 8 : 0), o_rhs = st.carve((size_t)a.n * 8), o_yc = st.carve((size_t)a.n * 8);
     const size_t o_yl = st.carve((size_t)L * 24), o_part = st.carve((size_t)a.n_blocks * 16), o_out = st.carve((size_t)M);
-    const size_t o_dinv = st.carve(sparse ? (size_t)a.n * 8 : 0);
+    ls.carve(st, &o_rhs);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
     MSLAM_CHK(c, grow(c->d_ba, st.size, c->stream));
-    if(blocked)
-        MSLAM_CHK(c, grow(c->d_ba_S, sparse ? (size_t)sy.blocks * 36 : (size_t)a.ld * a.n_pad, c->stream));
+    if(!local)
+        MSLAM_CHK(c, ls.grow_S(c));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
     uint8_t* d = c->d_ba;
@@ -927,54 +890,30 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     a.pose = dbl(o_pose), a.lm = dbl(o_lm), a.cand_pose = dbl(o_cpose), a.cand_lm = dbl(o_clm);
     a.V = dbl(o_V), a.gl = dbl(o_gl), a.Vinv = dbl(o_Vinv), a.sl = dbl(o_sl);
     a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.W = dbl(o_W);
-    a.S = blocked ? c->d_ba_S.get() : dbl(o_S), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
+    a.S = local ? dbl(o_S) : c->d_ba_S.get(), a.rhs = dbl(o_rhs), a.yc = dbl(o_yc), a.yl = dbl(o_yl), a.part = dbl(o_part);
     a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
     a.loss_kind = c->ba_loss_kind, a.loss_scale = c->ba_loss_scale;
-    const bool loss = a.loss_kind != MSLAM_HIP_BA_LOSS_NONE;
     *c->h_ba.get() = 0;
-    const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
-    a.env_off = i32(o_roff), a.env_first = i32(o_first);
-    const PgsArgs env{n_free, sy.blocks, a.env_off, a.env_first, i32(o_cptr), i32(o_cblk), i32(o_crow), a.S, a.rhs, dbl(o_dinv), a.yc, a.ctrl};
+    if(!local)
+        ls.bind(c, d, a.yc);
+    a.env_off = ls.env.row_off, a.env_first = ls.env.first;
+    kept = {dbl(o_pose0), dbl(o_lm0), d + o_out};
+    return MSLAM_HIP_OK;
+}
 
-    const dim3 g_lm((unsigned)((L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((K + L + 255) / 256));
-    {
-        StageScope ts(c, "ba_start_cost");
-        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
-    }
-    const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
-        hipLaunchKernelGGL(loss ? k_ba_landmarks_loss : k_ba_landmarks, g_lm, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(loss ? k_ba_cameras_loss : k_ba_cameras, dim3((unsigned)K), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
-        if(a.n_pairs > 0 && !blocked)
-        {
-            {
-                StageScope tk(c, "solver_schur");
-                hipLaunchKernelGGL(k_ba_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a);
-            }
-            StageScope tk(c, "solver_factor_subst");
-            hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
-        }
-        else if(a.n_pairs > 0 && sparse)
-            pg_sparse_solve(c, env, s, [&] { hipLaunchKernelGGL(k_bag_schur_env, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-        else if(a.n_pairs > 0)
-        {
-            // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
-            ba_blocked_solve(c, chol, s, [&] { hipLaunchKernelGGL(k_bag_schur, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-        }
-        hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
-        hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
-    }, sum);
-    if(rc != MSLAM_HIP_OK)
-        return rc;
+// Read-back: the outliers at the result (after a FAILURE: at the inputs), then poses and landmarks
+static int ba_read_back(mslam_hip_ctx* c, const BaProblem& p, const BaArgs& a, const BaKept& kept, double outlier_threshold,
+                        uint8_t* outlier, mslam_hip_ba_summary& sum, mslam_hip_ba_summary* summary)
+{
+    const int K = p.K, L = p.L, M = p.M;
+    hipStream_t s = c->stream;
     const bool usable = sum.termination != kTrFailure;
     std::vector<uint8_t> mask((size_t)M);
-    hipLaunchKernelGGL(k_ba_outliers, g_obs, dim3(256), 0, s, a, dbl(usable ? o_pose : o_pose0), dbl(usable ? o_lm : o_lm0),
-                       outlier_threshold * outlier_threshold, d + o_out);
+    hipLaunchKernelGGL(k_ba_outliers, dim3((unsigned)a.n_blocks), dim3(256), 0, s, a, usable ? a.pose : kept.pose0, usable ? a.lm : kept.lm0,
+                       outlier_threshold * outlier_threshold, kept.out);
     MSLAM_CHK(c, hipGetLastError());
-    MSLAM_CHK(c, hipMemcpyAsync(mask.data(), d + o_out, (size_t)M, hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipMemcpyAsync(mask.data(), kept.out, (size_t)M, hipMemcpyDeviceToHost, s));
     std::vector<double> xp((size_t)K * 7), xl((size_t)L * 3);
     if(usable)
     {
@@ -991,9 +930,82 @@ static int ba_run(mslam_hip_ctx* c, bool blocked, double* poses, const uint8_t* 
     if(!usable)
         return fail(c, MSLAM_HIP_E_NO_MODEL, "bundle_adjust: the minimiser ended in FAILURE (non-finite cost or gradient, or 5 "
                                              "invalid steps in a row)");
-    std::memcpy(poses, xp.data(), (size_t)K * 56);
-    std::memcpy(landmarks, xl.data(), (size_t)L * 24);
+    std::memcpy(p.poses, xp.data(), (size_t)K * 56);
+    std::memcpy(p.landmarks, xl.data(), (size_t)L * 24);
     return MSLAM_HIP_OK;
+}
+
+// Both entry points
+static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_iterations, double outlier_threshold, uint8_t* outlier,
+                  mslam_hip_ba_summary* summary)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    const BaMode mode = !global                                              ? BaMode::Local
+                        : c->bag_solver == MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE ? BaMode::GlobalSparse
+                                                                             : BaMode::GlobalDense;
+    LinearSolve ls(mode == BaMode::GlobalSparse); // not used by Local, which stages nothing of it and has its own solve
+    if(const int rc = ba_validate(c, mode, p, global ? ls.k_max() : kBaMaxKeyframes, max_iterations, outlier_threshold); rc != MSLAM_HIP_OK)
+        return rc;
+    mslam_hip_ba_summary sum{};
+    if(p.M == 0)
+    {
+        // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
+        if(summary)
+            *summary = sum;
+        return MSLAM_HIP_OK;
+    }
+    BaRows rw;
+    ba_rows(p.fixed, p.K, p.L, p.obs_kf, p.obs_lm, p.M, rw);
+    std::vector<int32_t> pairs;
+    if(mode == BaMode::Local)
+        ba_pairs_all(p.K, rw.ci, pairs);
+    else if(mode == BaMode::GlobalDense)
+        ba_pairs_table(p.K, p.L, p.obs_kf, rw, pairs);
+    else
+        ba_symbolic(p.fixed, p.K, p.obs_kf, rw, pairs, ls.sy);
+    if(mode != BaMode::Local)
+        if(const int rc = ls.index(c, "bundle_adjust_global", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+            return rc;
+    BaArgs a{};
+    BaKept kept{};
+    TrStaging st(max_iterations);
+    if(const int rc = ba_stage(c, mode, p, rw, pairs, ls, st, a, kept); rc != MSLAM_HIP_OK)
+        return rc;
+
+    hipStream_t s = c->stream;
+    const bool loss = a.loss_kind != MSLAM_HIP_BA_LOSS_NONE;
+    const dim3 g_lm((unsigned)((p.L + 255) / 256)), g_obs((unsigned)a.n_blocks), g_x((unsigned)((p.K + p.L + 255) / 256)), g_pair((unsigned)a.n_pairs);
+    {
+        StageScope ts(c, "ba_start_cost");
+        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
+    }
+    const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
+        hipLaunchKernelGGL(loss ? k_ba_landmarks_loss : k_ba_landmarks, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss ? k_ba_cameras_loss : k_ba_cameras, dim3((unsigned)p.K), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
+        if(a.n_pairs > 0 && mode == BaMode::Local)
+        {
+            {
+                StageScope tk(c, "solver_schur");
+                hipLaunchKernelGGL(k_ba_schur, g_pair, dim3(64), 0, s, a);
+            }
+            StageScope tk(c, "solver_factor_subst");
+            hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, s, a);
+        }
+        else if(a.n_pairs > 0)
+        {
+            // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
+            ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_bag_schur_env : k_bag_schur, g_pair, dim3(64), 0, s, a); });
+        }
+        hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
+        hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+    }, sum);
+    if(rc != MSLAM_HIP_OK)
+        return rc;
+    return ba_read_back(c, p, a, kept, outlier_threshold, outlier, sum, summary);
 }
 
 extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks, int L,
@@ -1001,8 +1013,7 @@ extern "C" int mslam_hip_bundle_adjust(mslam_hip_ctx* c, double* poses, const ui
                                        int max_iterations, double outlier_threshold, uint8_t* outlier,
                                        mslam_hip_ba_summary* summary)
 {
-    return ba_run(c, false, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
-                  summary);
+    return ba_run(c, false, {poses, landmarks, fixed, obs_kf, obs_lm, obs_cam, K, L, M}, max_iterations, outlier_threshold, outlier, summary);
 }
 
 extern "C" int mslam_hip_bundle_adjust_global(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, double* landmarks,
@@ -1010,8 +1021,7 @@ extern "C" int mslam_hip_bundle_adjust_global(mslam_hip_ctx* c, double* poses, c
                                               int max_iterations, double outlier_threshold, uint8_t* outlier,
                                               mslam_hip_ba_summary* summary)
 {
-    return ba_run(c, true, poses, fixed, K, landmarks, L, obs_kf, obs_lm, obs_cam, M, max_iterations, outlier_threshold, outlier,
-                  summary);
+    return ba_run(c, true, {poses, landmarks, fixed, obs_kf, obs_lm, obs_cam, K, L, M}, max_iterations, outlier_threshold, outlier, summary);
 }
 
 // The symbolic phase of the SPARSE solver without a context or a GPU: the argument checks of the solve, ba_rows, ba_symbolic
@@ -1029,22 +1039,9 @@ extern "C" int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed, int 
     std::vector<int32_t> pairs;
     PgSymbolic sy;
     ba_symbolic(fixed, K, obs_kf, rw, pairs, sy);
-    for(int i = 0; i < sy.n_free; ++i)
-    {
-        if(order)
-            order[i] = sy.order[(size_t)i];
-        if(first)
-            first[i] = sy.first[(size_t)i];
-    }
-    if(n_free)
-        *n_free = sy.n_free;
-    if(ordering)
-        *ordering = sy.ordering;
-    if(envelope_blocks)
-        *envelope_blocks = sy.blocks;
     if(n_pairs)
         *n_pairs = (int)(pairs.size() / 2);
-    return sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS ? MSLAM_HIP_E_CAPACITY : MSLAM_HIP_OK;
+    return pg_symbolic_out(sy, order, first, n_free, ordering, envelope_blocks);
 }
 
 // The linear solver of mslam_hip_bundle_adjust_global: context state, read when it is called

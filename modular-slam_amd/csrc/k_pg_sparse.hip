@@ -344,6 +344,24 @@ void pg_layout(PgSymbolic& sy)
         }
 }
 
+int pg_symbolic_out(const PgSymbolic& sy, int32_t* order, int32_t* first, int* n_free, int* ordering, int64_t* envelope_blocks)
+{
+    for(int i = 0; i < sy.n_free; ++i)
+    {
+        if(order)
+            order[i] = sy.order[(size_t)i];
+        if(first)
+            first[i] = sy.first[(size_t)i];
+    }
+    if(n_free)
+        *n_free = sy.n_free;
+    if(ordering)
+        *ordering = sy.ordering;
+    if(envelope_blocks)
+        *envelope_blocks = sy.blocks;
+    return sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS ? MSLAM_HIP_E_CAPACITY : MSLAM_HIP_OK;
+}
+
 } // namespace mslam
 
 using namespace mslam;
@@ -360,18 +378,5 @@ extern "C" int mslam_hip_pose_graph_analyze(const uint8_t* fixed, int K, const i
             return MSLAM_HIP_E_INVALID;
     PgSymbolic sy;
     pg_symbolic(fixed, K, edge_a, edge_b, E, sy);
-    for(int i = 0; i < sy.n_free; ++i)
-    {
-        if(order)
-            order[i] = sy.order[(size_t)i];
-        if(first)
-            first[i] = sy.first[(size_t)i];
-    }
-    if(n_free)
-        *n_free = sy.n_free;
-    if(ordering)
-        *ordering = sy.ordering;
-    if(envelope_blocks)
-        *envelope_blocks = sy.blocks;
-    return sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS ? MSLAM_HIP_E_CAPACITY : MSLAM_HIP_OK;
+    return pg_symbolic_out(sy, order, first, n_free, ordering, envelope_blocks);
 }

@@ -34,8 +34,9 @@
 //                   keeping entry (r, c), and writes the scaled block into the lower triangle; the blocked Cholesky, the
 //                   back-substitution.  With MSLAM_HIP_PG_SOLVER_SPARSE (mslam_hip_set_pose_graph_solver) pg_sparse_solve
 //                   (pg_sparse.hpp) stands here instead: the factor on the block envelope, with k_pg_assemble_env, the same
-//                   pairs, lists and expressions written to the permuted envelope position; ci[k] is then the pose's
-//                   position in the chosen order (every sum of the other kernels runs over k, none over ci)
+//                   body (pg_assemble_pair) storing to the permuted envelope position; ci[k] is then the pose's
+//                   position in the chosen order (every sum of the other kernels runs over k, none over ci).  Where an
+//                   entry goes is SysView's, which solver runs LinearSolve's (both reduced_system.hpp)
 //   k_pg_candidate  Plus on every pose
 //   k_pg_eval       a lane per edge: the model cost change -(J_s s) . (f + J_s s / 2) and the cost at the candidate, summed per
 //                   block by a fixed tree
@@ -43,8 +44,7 @@
 //                   accept or reject, radius
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
-#include "chol_solver.hpp"
-#include "pg_sparse.hpp"
+#include "reduced_system.hpp"
 
 #include <algorithm>
 #include <map>
@@ -52,7 +52,6 @@
 namespace mslam
 {
 
-constexpr int kPgMaxKeyframes = MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES;
 constexpr int kPgMaxEdges = MSLAM_HIP_POSE_GRAPH_MAX_EDGES;
 
 struct PgArgs
@@ -267,32 +266,37 @@ __global__ __launch_bounds__(64) void k_pg_check(PgArgs a)
 
 // ---- the normal equations: a wave per pair of free poses ------------------------------------------------------------------
 
-__global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
+// One body for both layouts: the pair's lookup, the diagonal with its damping, the sum over the pair's edge list and the
+// scaling; SysView (reduced_system.hpp) knows where the entries go.  ci is the block in index order with PaddedLower, the
+// position in the chosen order with Envelope.
+template <SysLayout kLayout>
+__device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
 {
     const TrCtrl* ct = a.ctrl;
     if(ct->done)
         return;
     const int lane = threadIdx.x;
     const int k1 = a.pairs[blockIdx.x * 2], k2 = a.pairs[blockIdx.x * 2 + 1];
-    const size_t b1 = (size_t)a.ci[k1], b2 = (size_t)a.ci[k2], ld = (size_t)a.ld;
+    const int b1 = a.ci[k1], b2 = a.ci[k2];
+    const SysView<kLayout> sys(a);
     if(k1 == k2)
     {
         if(lane < 36)
         {
             const int r = lane / 6, c = lane % 6;
             const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * a.sc[(size_t)k1 * 6 + c];
-            a.S[(b1 * 6 + r) + (b1 * 6 + c) * ld] = r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u;
+            sys.store(b1, b1, true, r, c, r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u);
         }
         else if(lane < 42)
         {
             const int r = lane - 36;
-            a.S[(size_t)a.n_pad + (b1 * 6 + r) * ld] = a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r];
+            sys.store_rhs(b1, r, a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r]);
         }
         return;
     }
     if(lane >= 36)
         return;
-    // entry (r, c) of sum_e J_k1^T J_k2, in the order of the pair's list; its transpose's place is in the lower triangle
+    // entry (r, c) of sum_e J_k1^T J_k2, in the order of the pair's list
     const int r = lane / 6, c = lane % 6;
     double s = 0.0;
     for(int pos = a.pair_ptr[blockIdx.x]; pos < a.pair_ptr[blockIdx.x + 1]; ++pos)
@@ -307,58 +311,11 @@ __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a)
             t += J1[i * 6 + r] * J2[i * 6 + c];
         s += t;
     }
-    a.S[(b2 * 6 + c) + (b1 * 6 + r) * ld] = a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c];
+    sys.store(b1, b2, false, r, c, a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c]);
 }
 
-// The envelope form (pg_sparse.hpp): the same pairs, lists, sums and expressions; ci is the position in the chosen order, the
-// block of (row, column) lies at env_off[row] + column - env_first[row], row-major inside.  A pair whose first pose comes later
-// in the order is written transposed.
-__global__ __launch_bounds__(64) void k_pg_assemble_env(PgArgs a)
-{
-    const TrCtrl* ct = a.ctrl;
-    if(ct->done)
-        return;
-    const int lane = threadIdx.x;
-    const int k1 = a.pairs[blockIdx.x * 2], k2 = a.pairs[blockIdx.x * 2 + 1];
-    const int p1 = a.ci[k1], p2 = a.ci[k2];
-    if(k1 == k2)
-    {
-        double* D = a.S + (size_t)(a.env_off[p1] + p1 - a.env_first[p1]) * 36;
-        if(lane < 36)
-        {
-            const int r = lane / 6, c = lane % 6;
-            const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * a.sc[(size_t)k1 * 6 + c];
-            D[r * 6 + c] = r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u;
-        }
-        else if(lane < 42)
-        {
-            const int r = lane - 36;
-            a.rhs[(size_t)p1 * 6 + r] = a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r];
-        }
-        return;
-    }
-    if(lane >= 36)
-        return;
-    const int r = lane / 6, c = lane % 6;
-    double s = 0.0;
-    for(int pos = a.pair_ptr[blockIdx.x]; pos < a.pair_ptr[blockIdx.x + 1]; ++pos)
-    {
-        const int e = a.pair_edge[pos];
-        const bool fwd = a.ea[e] == k1;
-        const double* J1 = a.J + (size_t)e * 72 + (fwd ? 0 : 36);
-        const double* J2 = a.J + (size_t)e * 72 + (fwd ? 36 : 0);
-        double t = 0.0;
-#pragma unroll
-        for(int i = 0; i < 6; ++i)
-            t += J1[i * 6 + r] * J2[i * 6 + c];
-        s += t;
-    }
-    const double val = a.sc[(size_t)k1 * 6 + r] * s * a.sc[(size_t)k2 * 6 + c];
-    if(p2 > p1)
-        a.S[(size_t)(a.env_off[p2] + p1 - a.env_first[p2]) * 36 + c * 6 + r] = val;
-    else
-        a.S[(size_t)(a.env_off[p1] + p2 - a.env_first[p1]) * 36 + r * 6 + c] = val;
-}
+__global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a) { pg_assemble_pair<SysLayout::PaddedLower>(a); }
+__global__ __launch_bounds__(64) void k_pg_assemble_env(PgArgs a) { pg_assemble_pair<SysLayout::Envelope>(a); }
 
 // delta = step * scaling with step = -y; Plus.  Poses outside the problem are copied.
 __global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
@@ -459,14 +416,10 @@ __global__ __launch_bounds__(64) void k_pg_control(PgArgs a)
 
 using namespace mslam;
 
-extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, const int32_t* edge_a,
-                                    const int32_t* edge_b, const double* edge_meas, const double* sqrt_info, int E,
-                                    int max_iterations, mslam_hip_ba_summary* summary)
+// the argument checks of mslam_hip_pose_graph; k_max: the K cap of the solver in use
+static int pg_validate(mslam_hip_ctx* c, int k_max, const double* poses, int K, const int32_t* edge_a, const int32_t* edge_b,
+                       const double* edge_meas, const double* sqrt_info, int E, int max_iterations)
 {
-    if(!c)
-        return MSLAM_HIP_E_INVALID;
-    const bool sparse = c->pg_solver == MSLAM_HIP_PG_SOLVER_SPARSE;
-    const int k_max = sparse ? MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE : kPgMaxKeyframes;
     if(K < 0 || K > k_max)
         return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: K outside 0.." + std::to_string(k_max));
     if(E < 0 || E > kPgMaxEdges)
@@ -489,6 +442,66 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     for(int k = 0; k < K; ++k)
         if(!tr_unit_quaternion(poses + (size_t)k * 7))
             return fail(c, MSLAM_HIP_E_INVALID, "pose_graph: the quaternion of pose " + std::to_string(k) + " is not unit");
+    return MSLAM_HIP_OK;
+}
+
+// the host's view of the edges
+struct PgRows
+{
+    std::vector<int32_t> inc_ptr, inc;               // incidences by pose in edge order
+    std::vector<int32_t> ci;                         // [K] the pose's block, -1: constant or without an edge
+    std::vector<int32_t> pairs, pair_ptr, pair_edge; // the pairs of free poses, sorted by (k1, k2); every list in edge order
+    int n_free = 0;
+};
+
+// incidences by pose in edge order (a stable counting sort) and the blocks of the free poses in index order
+static void pg_incidences(const uint8_t* fixed, int K, const int32_t* edge_a, const int32_t* edge_b, int E, PgRows& rw)
+{
+    std::vector<int32_t>&inc_ptr = rw.inc_ptr, &inc = rw.inc;
+    inc_ptr.assign((size_t)K + 1, 0), inc.assign((size_t)E * 2, 0);
+    for(int e = 0; e < E; ++e)
+        ++inc_ptr[(size_t)edge_a[e] + 1], ++inc_ptr[(size_t)edge_b[e] + 1];
+    for(int k = 0; k < K; ++k)
+        inc_ptr[(size_t)k + 1] += inc_ptr[(size_t)k];
+    std::vector<int32_t> at(inc_ptr.begin(), inc_ptr.end() - 1);
+    for(int e = 0; e < E; ++e)
+        inc[(size_t)at[(size_t)edge_a[e]]++] = 2 * e, inc[(size_t)at[(size_t)edge_b[e]]++] = 2 * e + 1;
+    rw.ci.assign((size_t)K, -1);
+    rw.n_free = 0;
+    for(int k = 0; k < K; ++k)
+        if(!(fixed && fixed[k]) && inc_ptr[(size_t)k + 1] > inc_ptr[(size_t)k])
+            rw.ci[(size_t)k] = rw.n_free++;
+}
+
+// the pairs with their edges; only the sign of ci is read
+static void pg_pairs(int K, const int32_t* edge_a, const int32_t* edge_b, int E, PgRows& rw)
+{
+    const std::vector<int32_t>& ci = rw.ci;
+    std::map<std::pair<int, int>, std::vector<int32_t>> by_pair;
+    for(int k = 0; k < K; ++k)
+        if(ci[(size_t)k] >= 0)
+            by_pair[{k, k}];
+    for(int e = 0; e < E; ++e)
+        if(ci[(size_t)edge_a[e]] >= 0 && ci[(size_t)edge_b[e]] >= 0)
+            by_pair[{std::min(edge_a[e], edge_b[e]), std::max(edge_a[e], edge_b[e])}].push_back(e);
+    rw.pair_ptr.assign(1, 0);
+    for(const auto& kv : by_pair)
+    {
+        rw.pairs.push_back(kv.first.first), rw.pairs.push_back(kv.first.second);
+        rw.pair_edge.insert(rw.pair_edge.end(), kv.second.begin(), kv.second.end());
+        rw.pair_ptr.push_back((int32_t)rw.pair_edge.size());
+    }
+}
+
+extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8_t* fixed, int K, const int32_t* edge_a,
+                                    const int32_t* edge_b, const double* edge_meas, const double* sqrt_info, int E,
+                                    int max_iterations, mslam_hip_ba_summary* summary)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    LinearSolve ls(c->pg_solver == MSLAM_HIP_PG_SOLVER_SPARSE);
+    if(const int rc = pg_validate(c, ls.k_max(), poses, K, edge_a, edge_b, edge_meas, sqrt_info, E, max_iterations); rc != MSLAM_HIP_OK)
+        return rc;
     mslam_hip_ba_summary sum{};
     if(E == 0)
     {
@@ -497,72 +510,33 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
             *summary = sum;
         return MSLAM_HIP_OK;
     }
-    // incidences by pose in edge order (a stable counting sort), the blocks of the free poses, the pairs with their edges
-    std::vector<int32_t> inc_ptr((size_t)K + 1, 0), inc((size_t)E * 2), ci((size_t)K, -1);
-    for(int e = 0; e < E; ++e)
-        ++inc_ptr[(size_t)edge_a[e] + 1], ++inc_ptr[(size_t)edge_b[e] + 1];
-    for(int k = 0; k < K; ++k)
-        inc_ptr[(size_t)k + 1] += inc_ptr[(size_t)k];
-    {
-        std::vector<int32_t> at(inc_ptr.begin(), inc_ptr.end() - 1);
-        for(int e = 0; e < E; ++e)
-            inc[(size_t)at[(size_t)edge_a[e]]++] = 2 * e, inc[(size_t)at[(size_t)edge_b[e]]++] = 2 * e + 1;
-    }
-    int n_free = 0;
-    PgSymbolic sy;
-    if(sparse)
-    {
-        // the symbolic phase: the order, the envelope; a pose's block is its position in the order
-        pg_symbolic(fixed, K, edge_a, edge_b, E, sy);
-        if(sy.blocks > MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS)
-            return fail(c, MSLAM_HIP_E_CAPACITY, "pose_graph: the envelope needs " + std::to_string(sy.blocks) + " blocks, at most " +
-                                                     std::to_string(MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS) + " per solve");
-        pg_layout(sy);
-        n_free = sy.n_free;
-        for(int i = 0; i < n_free; ++i)
-            ci[(size_t)sy.order[(size_t)i]] = i;
-    }
-    else
-        for(int k = 0; k < K; ++k)
-            if(!(fixed && fixed[k]) && inc_ptr[(size_t)k + 1] > inc_ptr[(size_t)k])
-                ci[(size_t)k] = n_free++;
-    std::map<std::pair<int, int>, std::vector<int32_t>> by_pair; // sorted by (k1, k2); every list in edge order
-    for(int k = 0; k < K; ++k)
-        if(ci[(size_t)k] >= 0)
-            by_pair[{k, k}];
-    for(int e = 0; e < E; ++e)
-        if(ci[(size_t)edge_a[e]] >= 0 && ci[(size_t)edge_b[e]] >= 0)
-            by_pair[{std::min(edge_a[e], edge_b[e]), std::max(edge_a[e], edge_b[e])}].push_back(e);
-    std::vector<int32_t> pairs, pair_ptr(1, 0), pair_edge;
-    for(const auto& kv : by_pair)
-    {
-        pairs.push_back(kv.first.first), pairs.push_back(kv.first.second);
-        pair_edge.insert(pair_edge.end(), kv.second.begin(), kv.second.end());
-        pair_ptr.push_back((int32_t)pair_edge.size());
-    }
+    PgRows rw;
+    pg_incidences(fixed, K, edge_a, edge_b, E, rw);
+    if(ls.sparse)
+        pg_symbolic(fixed, K, edge_a, edge_b, E, ls.sy); // its nodes are the free poses that have an edge: rw.n_free of them
+    if(const int rc = ls.index(c, "pose_graph", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+        return rc;
+    pg_pairs(K, edge_a, edge_b, E, rw);
 
     PgArgs a{};
-    a.K = K, a.E = E, a.n = 6 * n_free;
-    a.n_pairs = (int)(pairs.size() / 2), a.n_blocks = (E + 255) / 256;
-    a.n_pad = (a.n + kBagNB - 1) / kBagNB * kBagNB, a.ld = a.n_pad + 16;
+    a.K = K, a.E = E, a.n = ls.n, a.n_pad = ls.n_pad, a.ld = ls.ld;
+    a.n_pairs = (int)(rw.pairs.size() / 2), a.n_blocks = (E + 255) / 256;
     // one block: what is uploaded first (the control block at 0), then the working arrays
     TrStaging st(max_iterations);
     const size_t n_info = sqrt_info ? (size_t)E * 288 : 0;
     const size_t o_pose = st.put(poses, (size_t)K * 56), o_meas = st.put(edge_meas, (size_t)E * 56), o_info = st.put(sqrt_info, n_info);
-    const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4), o_iptr = st.put(inc_ptr.data(), ((size_t)K + 1) * 4);
-    const size_t o_inc = st.put(inc.data(), (size_t)E * 8), o_ci = st.put(ci.data(), (size_t)K * 4), o_pairs = st.put(pairs.data(), pairs.size() * 4);
-    const size_t o_pptr = st.put(pair_ptr.data(), pair_ptr.size() * 4), o_pedge = st.put(pair_edge.data(), pair_edge.size() * 4);
-    const size_t o_roff = st.put(sy.row_off.data(), sy.row_off.size() * 4), o_first = st.put(sy.first.data(), sparse ? (size_t)n_free * 4 : 0);
-    const size_t o_cptr = st.put(sy.col_ptr.data(), sy.col_ptr.size() * 4), o_cblk = st.put(sy.col_blk.data(), sy.col_blk.size() * 4);
-    const size_t o_crow = st.put(sy.col_row.data(), sy.col_row.size() * 4);
+    const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4), o_iptr = st.put(rw.inc_ptr.data(), ((size_t)K + 1) * 4);
+    const size_t o_inc = st.put(rw.inc.data(), (size_t)E * 8), o_ci = st.put(rw.ci.data(), (size_t)K * 4);
+    const size_t o_pairs = st.put(rw.pairs.data(), rw.pairs.size() * 4), o_pptr = st.put(rw.pair_ptr.data(), rw.pair_ptr.size() * 4);
+    const size_t o_pedge = st.put(rw.pair_edge.data(), rw.pair_edge.size() * 4);
+    ls.put(st);
     const size_t o_cand = st.carve((size_t)K * 56), o_r = st.carve((size_t)E * 48), o_J = st.carve((size_t)E * 576);
     const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_yc = st.carve((size_t)a.n * 8);
     const size_t o_part = st.carve((size_t)a.n_blocks * 16);
-    const size_t o_rhs = st.carve(sparse ? (size_t)a.n * 8 : 0), o_dinv = st.carve(sparse ? (size_t)a.n * 8 : 0);
+    ls.carve(st);
     MSLAM_CHK(c, hipSetDevice(c->p.device));
     MSLAM_CHK(c, grow(c->d_pg, st.size, c->stream));
-    if(a.n > 0)
-        MSLAM_CHK(c, grow(c->d_ba_S, sparse ? (size_t)sy.blocks * 36 : (size_t)a.ld * a.n_pad, c->stream));
+    MSLAM_CHK(c, ls.grow_S(c));
     if(!c->h_ba)
         MSLAM_CHK(c, c->h_ba.alloc(4));
     uint8_t* d = c->d_pg;
@@ -578,11 +552,10 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     a.ctrl = reinterpret_cast<TrCtrl*>(d);
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
-    a.env_off = i32(o_roff), a.env_first = i32(o_first), a.rhs = dbl(o_rhs);
-    const CholArgs chol{a.n, a.n_pad, a.ld, a.S, a.yc, a.ctrl};
-    const PgsArgs env{n_free, sy.blocks, a.env_off, a.env_first, i32(o_cptr), i32(o_cblk), i32(o_crow), a.S, a.rhs, dbl(o_dinv), a.yc, a.ctrl};
+    ls.bind(c, d, a.yc);
+    a.env_off = ls.env.row_off, a.env_first = ls.env.first, a.rhs = ls.env.rhs;
 
-    const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256));
+    const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256)), g_pair((unsigned)a.n_pairs);
     {
         StageScope ts(c, "pg_start_cost");
         hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
@@ -594,10 +567,8 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
             hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
             hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
         }
-        if(a.n_pairs > 0 && sparse)
-            pg_sparse_solve(c, env, s, [&] { hipLaunchKernelGGL(k_pg_assemble_env, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-        else if(a.n_pairs > 0)
-            ba_blocked_solve(c, chol, s, [&] { hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+        if(a.n_pairs > 0)
+            ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_pg_assemble_env : k_pg_assemble, g_pair, dim3(64), 0, s, a); });
         StageScope tk(c, "pg_step");
         hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);

@@ -1,5 +1,7 @@
 // pg_sparse.hpp — the block-envelope (skyline) Cholesky solve of k_pg_sparse.hip: mslam_hip_pose_graph's second linear solver
-// (MSLAM_HIP_PG_SOLVER_SPARSE) and the symbolic phase mslam_hip_pose_graph_analyze exposes.  DESIGN.md 4.25.
+// (MSLAM_HIP_PG_SOLVER_SPARSE), mslam_hip_bundle_adjust_global's (MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE), and the symbolic phase the
+// two *_analyze entry points expose.  The callers reach pg_sparse_solve through LinearSolve and address the envelope through
+// SysView<SysLayout::Envelope> (both reduced_system.hpp).  DESIGN.md 4.25, 4.26.
 #pragma once
 #include "trust_region.hpp"
 
@@ -29,6 +31,9 @@ void pg_symbolic(const uint8_t* fixed, int K, const int32_t* edge_a, const int32
                  const uint8_t* node_mask = nullptr);
 // row offsets and column lists of an envelope that fits MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS
 void pg_layout(PgSymbolic& sy);
+// the tail of the two *_analyze entry points: copies out through pointers that may be NULL; MSLAM_HIP_E_CAPACITY for an
+// envelope above the bound, MSLAM_HIP_OK otherwise
+int pg_symbolic_out(const PgSymbolic& sy, int32_t* order, int32_t* first, int* n_free, int* ordering, int64_t* envelope_blocks);
 
 struct PgsArgs
 {
