@@ -439,7 +439,8 @@ int mslam_hip_get_pnp_view(mslam_hip_ctx* ctx, mslam_hip_pnp_view* view);
  * The reference's second IPnpAlgorithm: a Ceres Levenberg-Marquardt solve over x = (r, t), r an angle-axis vector and t a
  * translation, of cost = 1/2 sum_i |observed_i - projected_i|^2 with
  *   projected_i = (fx X/Z + cx, fy Y/Z + cy),  (X, Y, Z) = ceres::AngleAxisRotatePoint(r, P_i) + t,
- * no loss function, all in double, started from the caller's (r, t).  Every point takes part (no outlier rejection).
+ * no loss function (mslam_hip_set_pnp_mse_loss below sets one: an extension, off by default), all in double, started from
+ * the caller's (r, t).  Every point takes part (no outlier rejection).
  * object_points = n x 3 f64, image_points = n x 2 f64, rvec / tvec = the start on input, the result on output.
  * termination (ceres::TerminationType: 0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE), iterations (trust-region iterations
  * after iteration 0: the index of the iteration that ended the solve) and final_cost may be NULL.
@@ -581,7 +582,8 @@ int mslam_hip_bundle_adjust_global(mslam_hip_ctx* ctx, double* poses /* K x 7, i
                                    mslam_hip_ba_summary* summary /* may be NULL */);
 /* ---- A loss function for both bundle adjustment entries (an extension: the reference passes lossFunction = nullptr) ----
  * Context state, the idiom of mslam_hip_set_guided_match: mslam_hip_bundle_adjust and mslam_hip_bundle_adjust_global read it
- * when they are called.  mslam_hip_pose_graph and mslam_hip_pnp_min_mse do NOT read it.  The default is NONE: both entries
+ * when they are called.  mslam_hip_pose_graph and mslam_hip_pnp_min_mse do NOT read it (they have settings of their own:
+ * mslam_hip_set_pose_graph_loss and mslam_hip_set_pnp_mse_loss below).  The default is NONE: both entries
  * then launch the kernels they launched before this setting existed, and every result keeps its bits.
  * The loss is per residual block, s = |r_m|^2 (the three camera-frame components together), scale a in metres, b = a^2:
  *   HUBER    s <= b: rho = s, rho' = 1;   else rho = 2 a sqrt(s) - b, rho' = max(DBL_MIN, a / sqrt(s))
@@ -733,6 +735,61 @@ int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed /* K, or NULL */
                                            int M, int L, int32_t* order /* K: keyframe index per position, n_free used */,
                                            int32_t* first /* K */, int* n_free, int* ordering /* 0 NATURAL, 1 RCM */,
                                            int64_t* envelope_blocks, int* n_pairs);
+/* ---- A loss function on the edges of mslam_hip_pose_graph (an extension) ----
+ * Context state, the idiom of mslam_hip_set_ba_loss: mslam_hip_pose_graph reads it when it is called, with either linear
+ * solver (DENSE and SPARSE), and so does mslam_hip_pose_graph_edge_weights.  The bundle adjustments and mslam_hip_pnp_min_mse
+ * do NOT read it, and mslam_hip_set_ba_loss does not reach the pose graph.  The kinds are MSLAM_HIP_BA_LOSS_NONE / _HUBER /
+ * _CAUCHY.  The default is NONE: the entry then launches the kernels it launched before this setting existed, whose machine
+ * code is what it was, and every result keeps its bits.
+ * The loss is per edge, s = |r_e|^2 over all six weighted components (after sqrt_info), the scale a in the unit of the
+ * weighted residual (metres and radians times sqrt_info), b = a^2; the formulas are those of mslam_hip_set_ba_loss:
+ *   HUBER    s <= b: rho = s, rho' = 1;   else rho = 2 a sqrt(s) - b, rho' = max(DBL_MIN, a / sqrt(s))
+ *   CAUCHY   rho = b log(1 + s / b), rho' = max(DBL_MIN, 1 / (1 + s / b))
+ * cost = 1/2 sum_e rho(|r_e|^2): initial_cost and final_cost report that.  k_pg_edges_loss stores r_e and both 6 x 6 Jacobians
+ * of the edge multiplied by sqrt(rho') at the state; the per-pose sums, the normal equations in both layouts, the Jacobi
+ * scaling taken at the start, the gradient test, the model cost change, the function and parameter tolerances and the step
+ * acceptance follow from the corrected blocks through the kernels that ran before.  s = 0 gives rho' = 1 (no 0 / 0).  There
+ * is no default scale.  Two calls on the same input and setting return the same bits: no atomics, no new order of summation.
+ * set returns MSLAM_HIP_E_INVALID for a kind outside 0..2 or, for HUBER / CAUCHY, a scale that is not finite or not > 0; the
+ * setting is then unchanged.  With NONE the scale is ignored and reported as 0.  get: either pointer may be NULL.
+ * Against Ceres 2.2 (loss_function.h, corrector.cc, restated from the published text).  PARITY UNPINNED as for the solver: the
+ * tests compare with tests/pose_graph_loss_ref.py, which applies the corrector to tests/pose_graph_ref.py's residuals and
+ * Jacobians.
+ *   loss formulas            SAME: HuberLoss::Evaluate and CauchyLoss::Evaluate, s == b on Huber's inlier branch, Cauchy's
+ *                            1 + s c with c = 1 / b;
+ *   corrector                SAME branch: rho'' <= 0 everywhere for both kinds, so Corrector takes `sq_norm == 0 || rho[2] <=
+ *                            0`: sqrt(rho') on residual and Jacobians, no curvature term.  SAME form: the rows are scaled, as
+ *                            Corrector::CorrectResiduals and CorrectJacobian do (the bundle adjustment kernels weight the
+ *                            products instead);
+ *   other losses             not built: SoftLOne, Arctan, Tolerant, Tukey, a loss or a scale chosen per edge.
+ * mslam_hip_pose_graph_edge_weights is how a caller sees which edges a solve down-weighted: one launch, a lane per edge,
+ * chi2[e] = |r_e|^2 at the given poses and weight[e] = rho'(chi2[e]) under the context's pose-graph loss (1.0 with NONE).
+ * Either output may be NULL.  The argument checks are mslam_hip_pose_graph's with K in
+ * 0..MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE whichever solver is set (no linear system is formed); E = 0 writes nothing. */
+int mslam_hip_set_pose_graph_loss(mslam_hip_ctx* ctx, int kind, double scale);
+int mslam_hip_get_pose_graph_loss(mslam_hip_ctx* ctx, int* kind, double* scale);
+int mslam_hip_pose_graph_edge_weights(mslam_hip_ctx* ctx, const double* poses /* K x 7 */, int K, const int32_t* edge_a,
+                                      const int32_t* edge_b, const double* edge_meas /* E x 7 */,
+                                      const double* sqrt_info /* E x 36, or NULL */, int E, double* chi2 /* E, may be NULL */,
+                                      double* weight /* E, may be NULL */);
+/* ---- A loss function for mslam_hip_pnp_min_mse and mslam_hip_pnp_min_mse_batch_dev (an extension) ----
+ * Context state, read by both entries when they are called; independent of mslam_hip_set_ba_loss and
+ * mslam_hip_set_pose_graph_loss, which do not reach these entries.  The kinds are MSLAM_HIP_BA_LOSS_*.  The default is NONE:
+ * both entries then launch k_pnp_min_mse, whose machine code is what it was, and every result keeps its bits.  With HUBER or
+ * CAUCHY they launch k_pnp_min_mse_loss: per point s = |observed_i - projected_i|^2, the scale a in pixels, the formulas
+ * above; cost = 1/2 sum_i rho(s_i) (info[2], info[3] and final_cost report that) and rho'(s_i) multiplies the point's share
+ * of J^T J and J^T f.  The trust-region loop, the validity test on the sums, the model cost change from the normal
+ * equations, the terminations and the 50-iteration cap are untouched.  The single call and the batch call still give the
+ * same bits for the same problem.  set / get: the rules of mslam_hip_set_pose_graph_loss.  The RANSAC PnP entries and
+ * mslam_hip_track do not use min-MSE PnP and take no loss.
+ * PARITY UNPINNED; the tests compare with tests/mse_pnp_loss_ref.py (the corrector on tests/mse_pnp_ref.py's rows).
+ *   loss formulas, corrector branch     SAME as stated for mslam_hip_set_pose_graph_loss;
+ *   weight                   DEVIATES in rounding: the sweep keeps its sums in registers and has no stored rows to scale,
+ *                            so rho' multiplies every product of point i where Ceres scales the rows by sqrt(rho') first
+ *                            (as in the bundle adjustment kernels);
+ *   other losses             not built. */
+int mslam_hip_set_pnp_mse_loss(mslam_hip_ctx* ctx, int kind, double scale);
+int mslam_hip_get_pnp_mse_loss(mslam_hip_ctx* ctx, int* kind, double* scale);
 /* The reference updates landmark->state in place for everyone who holds the pointer; here every landmark of every store
  * entry whose landmark id is landmark_ids[i] gets world_xyz[i] (an id listed twice: the later one wins; ids the store does
  * not hold are ignored).  One upload, a clear, two launches, one synchronisation; *n_written (may be NULL) = the number of

@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     "mslam_hip_set_union_descriptor", "mslam_hip_get_union_descriptor",
     "mslam_hip_set_pose_graph_solver", "mslam_hip_get_pose_graph_solver", "mslam_hip_pose_graph_analyze",
     "mslam_hip_set_ba_global_solver", "mslam_hip_get_ba_global_solver", "mslam_hip_bundle_adjust_global_analyze",
+    "mslam_hip_set_pose_graph_loss", "mslam_hip_get_pose_graph_loss", "mslam_hip_pose_graph_edge_weights",
+    "mslam_hip_set_pnp_mse_loss", "mslam_hip_get_pnp_mse_loss",
 ]
 
 
@@ -196,6 +198,15 @@ def lib():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _loss_kind(kind, who):
+    """a loss kind given by name ("none" / "huber" / "cauchy") or as BA_LOSS_* -> the number the C ABI takes"""
+    if isinstance(kind, str):
+        if kind.lower() not in _BA_LOSS_NAMES:
+            raise MslamHipError(E_INVALID, "%s: kind %r is not none / huber / cauchy" % (who, kind))
+        return _BA_LOSS_NAMES[kind.lower()]
+    return int(kind)
 
 
 def _pg_solver_kind(kind, who):
@@ -520,6 +531,19 @@ class Context:
                                                C.byref(term), C.byref(iters), C.byref(cost)))
         return r, t, term.value, iters.value, cost.value
 
+    def set_pnp_mse_loss(self, kind, scale=0.0):
+        """the loss function of pnp_min_mse and pnp_min_mse_batch_dev from now on (an extension: the reference's call has
+        none, so every mismatch pulls the pose with full weight): kind "none" (the default state) / "huber" / "cauchy" or
+        BA_LOSS_*; scale a in pixels, finite and > 0 for huber and cauchy, ignored for none.  s = |observed - projected|^2
+        per point; the formulas are set_ba_loss's.  The costs become 1/2 sum rho.  Nothing else reads the setting."""
+        self._chk(self.L.mslam_hip_set_pnp_mse_loss(self._h, _loss_kind(kind, "set_pnp_mse_loss"), C.c_double(scale)))
+
+    def get_pnp_mse_loss(self):
+        """-> (kind as BA_LOSS_*, scale); (BA_LOSS_NONE, 0.0) when no loss is set"""
+        k, s = C.c_int(0), C.c_double(0)
+        self._chk(self.L.mslam_hip_get_pnp_mse_loss(self._h, C.byref(k), C.byref(s)))
+        return k.value, s.value
+
     def pnp_min_mse_batch_dev(self, d_object, d_image, d_n, n_problems, capacity, d_pose, d_info, focal=(525.0, 525.0),
                               principal=(319.5, 239.5)):
         """one min-MSE PnP per problem on device data (raw device pointers), asynchronous on the context's stream:
@@ -624,12 +648,9 @@ class Context:
         kind "none" (the default state) / "huber" / "cauchy" or BA_LOSS_*; scale a in metres, finite and > 0 for huber and
         cauchy, ignored for none.  s = |r_m|^2 per observation, b = a^2: huber rho = s for s <= b, else 2 a sqrt(s) - b;
         cauchy rho = b log(1 + s / b).  The costs a solve reports become 1/2 sum rho; the outlier mask is still judged on
-        the plain residual.  pose_graph and pnp_min_mse do not read the setting."""
-        if isinstance(kind, str):
-            if kind.lower() not in _BA_LOSS_NAMES:
-                raise MslamHipError(E_INVALID, "set_ba_loss: kind %r is not none / huber / cauchy" % kind)
-            kind = _BA_LOSS_NAMES[kind.lower()]
-        self._chk(self.L.mslam_hip_set_ba_loss(self._h, int(kind), C.c_double(scale)))
+        the plain residual.  pose_graph and pnp_min_mse do not read the setting: set_pose_graph_loss and set_pnp_mse_loss
+        are theirs."""
+        self._chk(self.L.mslam_hip_set_ba_loss(self._h, _loss_kind(kind, "set_ba_loss"), C.c_double(scale)))
 
     def get_ba_loss(self):
         """-> (kind as BA_LOSS_*, scale); (BA_LOSS_NONE, 0.0) when no loss is set"""
@@ -671,20 +692,50 @@ class Context:
         self._chk(self.L.mslam_hip_get_pose_graph_solver(self._h, C.byref(k)))
         return k.value
 
-    def pose_graph(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100):
-        """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024, or 16384
-        after set_pose_graph_solver("sparse")), E edges
-        (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
-        flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
-        final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged."""
-        x = np.array(poses, np.float64, order="C").reshape(-1, 7)        # a copy in row-major order, whatever the argument's
+    def set_pose_graph_loss(self, kind, scale=0.0):
+        """the loss function of pose_graph from now on, with either linear solver (an extension): kind "none" (the default
+        state) / "huber" / "cauchy" or BA_LOSS_*; scale a in the unit of the weighted residual, finite and > 0 for huber and
+        cauchy, ignored for none.  s = |r_e|^2 per edge over all six components after sqrt_info; the formulas are
+        set_ba_loss's.  The costs a solve reports become 1/2 sum rho.  pose_graph_edge_weights reads it too; the bundle
+        adjustments and pnp_min_mse do not."""
+        self._chk(self.L.mslam_hip_set_pose_graph_loss(self._h, _loss_kind(kind, "set_pose_graph_loss"), C.c_double(scale)))
+
+    def get_pose_graph_loss(self):
+        """-> (kind as BA_LOSS_*, scale); (BA_LOSS_NONE, 0.0) when no loss is set"""
+        k, s = C.c_int(0), C.c_double(0)
+        self._chk(self.L.mslam_hip_get_pose_graph_loss(self._h, C.byref(k), C.byref(s)))
+        return k.value, s.value
+
+    def _pose_graph_edges(self, who, edge_a, edge_b, edge_meas, sqrt_info):
         ea = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
         eb = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
         z = np.ascontiguousarray(edge_meas, np.float64).reshape(-1, 7)
         w = None if sqrt_info is None else np.ascontiguousarray(sqrt_info, np.float64).reshape(-1, 36)
         if not len(ea) == len(eb) == len(z) or (w is not None and len(w) != len(ea)):
-            raise MslamHipError(E_INVALID, "pose_graph: %d / %d edge ends, %d measurements, %s sqrt_info" % (
-                len(ea), len(eb), len(z), "no" if w is None else len(w)))
+            raise MslamHipError(E_INVALID, "%s: %d / %d edge ends, %d measurements, %s sqrt_info" % (
+                who, len(ea), len(eb), len(z), "no" if w is None else len(w)))
+        return ea, eb, z, w
+
+    def pose_graph_edge_weights(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None):
+        """what the pose-graph loss makes of every edge at the given poses (pose_graph's arguments; K <= 16384 whichever
+        solver is set) -> (chi2 [E], weight [E]): chi2 = |r_e|^2 and weight = rho'(chi2) under set_pose_graph_loss, 1.0
+        without a loss.  At a solve's result it shows which edges the solve down-weighted."""
+        x = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        ea, eb, z, w = self._pose_graph_edges("pose_graph_edge_weights", edge_a, edge_b, edge_meas, sqrt_info)
+        chi2, weight = np.zeros(max(len(ea), 1)), np.zeros(max(len(ea), 1))
+        self._chk(self.L.mslam_hip_pose_graph_edge_weights(self._h, _p(x), len(x), _p(ea), _p(eb), _p(z), _p(w), len(ea),
+                                                           _p(chi2), _p(weight)))
+        return chi2[:len(ea)], weight[:len(ea)]
+
+    def pose_graph(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100):
+        """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024, or 16384
+        after set_pose_graph_solver("sparse")), E edges
+        (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
+        flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
+        final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged.
+        After set_pose_graph_loss the cost is 1/2 sum rho(|r_e|^2) and both costs report that."""
+        x = np.array(poses, np.float64, order="C").reshape(-1, 7)        # a copy in row-major order, whatever the argument's
+        ea, eb, z, w = self._pose_graph_edges("pose_graph", edge_a, edge_b, edge_meas, sqrt_info)
         fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
         if fx is not None and len(fx) != len(x):
             raise MslamHipError(E_INVALID, "pose_graph: %d poses, %d fixed flags" % (len(x), len(fx)))
@@ -1510,14 +1561,20 @@ class HipBackend:
     the setting, as loss = None does not (a context is DENSE unless its owner said otherwise), and takes up to 1024.
     global_ba() has its own setting: global_linear_solver = "sparse" (with global_solver = True) runs it with
     Context.set_ba_global_solver("sparse"), puts the context's previous setting back afterwards, also when the solve raises,
-    and takes up to 16384 keyframes; "dense" (the default) never touches the setting and takes up to 1024."""
+    and takes up to 16384 keyframes; "dense" (the default) never touches the setting and takes up to 1024.
+    pose_graph_loss = ("huber", a) or ("cauchy", a) (a in the unit of the weighted residual; an extension): close_loop runs
+    with Context.set_pose_graph_loss(kind, a) and puts the context's previous setting back afterwards, also when the solve
+    raises; its result gains edge_chi2 and edge_weight (Context.pose_graph_edge_weights at the returned poses; the loop edge
+    is the last).  None (the default) never touches the setting.  No rejection policy follows from the weights here:
+    loop_problem() has one loop edge on odometry edges measured at the current poses, a chain always bends to such an
+    edge, and the weight at the solution says nothing about whether the loop was right."""
 
     MAX_KEYFRAMES = 64
     MAX_GLOBAL_KEYFRAMES = 1024
     MAX_GLOBAL_KEYFRAMES_SPARSE = BA_GLOBAL_MAX_KEYFRAMES_SPARSE
 
     def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense",
-                 global_linear_solver="dense"):
+                 global_linear_solver="dense", pose_graph_loss=None):
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
         self.pose_graph_solver = _pg_solver_kind(pose_graph_solver, "HipBackend")    # of Context.set_pose_graph_solver
         if self.pose_graph_solver not in (PG_SOLVER_DENSE, PG_SOLVER_SPARSE):
@@ -1527,6 +1584,8 @@ class HipBackend:
         if self.global_linear_solver not in (BA_GLOBAL_SOLVER_DENSE, BA_GLOBAL_SOLVER_SPARSE):
             raise MslamHipError(E_INVALID, "HipBackend: global_linear_solver %r is not dense / sparse" % (global_linear_solver,))
         self.loss = None if loss is None else (loss[0], float(loss[1]))    # (kind, scale) of Context.set_ba_loss
+        # (kind, scale) of Context.set_pose_graph_loss
+        self.pose_graph_loss = None if pose_graph_loss is None else (pose_graph_loss[0], float(pose_graph_loss[1]))
         self.poses = {}       # id -> [7]
         self.obs = {}         # id -> (landmark ids [n] i64, camera points [n, 3])
         self.landmarks = {}   # landmark id -> [3]
@@ -1772,15 +1831,25 @@ class HipBackend:
         if int(cur_id) not in self.poses or int(loop_id) not in self.poses or int(cur_id) == int(loop_id):
             raise MslamHipError(E_INVALID, "close_loop: keyframes %r and %r must be two keyframes of the backend" % (cur_id, loop_id))
         ids, poses, fixed, ea, eb, meas, info = self.loop_problem(cur_id, loop_id, rvec, tvec, graph, sqrt_info)
-        if self.pose_graph_solver == PG_SOLVER_SPARSE:
-            before = self.ctx.get_pose_graph_solver()
-            self.ctx.set_pose_graph_solver(PG_SOLVER_SPARSE)
-            try:
+        if self.pose_graph_loss is not None:
+            loss_before = self.ctx.get_pose_graph_loss()
+            self.ctx.set_pose_graph_loss(*self.pose_graph_loss)
+        try:
+            if self.pose_graph_solver == PG_SOLVER_SPARSE:
+                before = self.ctx.get_pose_graph_solver()
+                self.ctx.set_pose_graph_solver(PG_SOLVER_SPARSE)
+                try:
+                    res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+                finally:
+                    self.ctx.set_pose_graph_solver(before)
+            else:
                 res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
-            finally:
-                self.ctx.set_pose_graph_solver(before)
-        else:
-            res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+            if self.pose_graph_loss is not None:
+                chi2, weight = self.ctx.pose_graph_edge_weights(res["poses"], ea, eb, meas, info)
+                res.update(edge_chi2=chi2, edge_weight=weight)
+        finally:
+            if self.pose_graph_loss is not None:
+                self.ctx.set_pose_graph_loss(*loss_before)
         lids = sorted(l for l in self.landmarks if self.anchor.get(l) in self.poses)
         lm = np.array([self.landmarks[l] for l in lids], np.float64).reshape(-1, 3)
         if res["termination"] != 2:
@@ -1866,6 +1935,13 @@ class HipKeyframeTracker:
     (loop_global_ba) has its own setting, whatever pose_graph_solver is: ba_global_solver = "dense" (the default: a cap of
     1024 keyframes, the behaviour it had) or "sparse" (HipBackend(global_linear_solver="sparse"); Context.set_ba_global_solver:
     up to 16384 keyframes, the reduced camera system on its block envelope).
+    pose_graph_loss = ("huber", a) or ("cauchy", a) (needs loop_closure, else MslamHipError(E_INVALID); an extension) goes to
+    the backend too: close_loop solves with that loss on every edge and its dict in self.loop_results gains edge_chi2 and
+    edge_weight (HipBackend; Context.set_pose_graph_loss; the context is left with the setting it had).  None (the default)
+    is the tracker without the option, bit for bit.  NO REJECTION POLICY is built on the weights: the problem has one loop
+    edge on odometry edges measured at the current poses, a chain always bends to such an edge, and so the loop edge's
+    weight at the solution does not tell a wrong loop from a right one.  The loss matters to callers of Context.pose_graph
+    whose graphs carry several loop edges.
     Without loop_fusion the new keyframe's landmarks keep their own ids, so no covisibility edge joins the two keyframes and
     the loop is known to the pose graph of that one call only.
 
@@ -1960,7 +2036,7 @@ class HipKeyframeTracker:
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
-                 pose_graph_solver="dense", ba_global_solver="dense"):
+                 pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None):
         self.ctx = ctx
         if union_descriptor is not None:
             if local_map_depth is None:
@@ -1970,6 +2046,9 @@ class HipKeyframeTracker:
         if ba_loss is not None and not local_ba:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_loss needs local_ba (the backend's solves take the loss)")
         self.ba_loss = None if ba_loss is None else (ba_loss[0], float(ba_loss[1]))
+        if pose_graph_loss is not None and not loop_closure:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: pose_graph_loss needs loop_closure (close_loop takes the loss)")
+        self.pose_graph_loss = None if pose_graph_loss is None else (pose_graph_loss[0], float(pose_graph_loss[1]))
         self.lm_cull, self.lm_cull_min_observers, self.lm_cull_age = bool(lm_cull), int(lm_cull_min_observers), int(lm_cull_age)
         self.lm_cull_results = []
         self._lm_pending = []        # (keyframe id, the insertion count at which it was inserted): not judged yet
@@ -2007,7 +2086,8 @@ class HipKeyframeTracker:
         self._last_closure = None    # the keyframe at which the last loop was closed
         # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
         self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss,
-                                  pose_graph_solver=pose_graph_solver, global_linear_solver=ba_global_solver) if local_ba else None
+                                  pose_graph_solver=pose_graph_solver, global_linear_solver=ba_global_solver,
+                                  pose_graph_loss=self.pose_graph_loss) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)

@@ -167,6 +167,12 @@ struct mslam_hip_ctx
     mslam::DevBuf<uint8_t> d_pg;
     // mslam_hip_set_pose_graph_solver: read by mslam_hip_pose_graph when it is called
     int pg_solver = MSLAM_HIP_PG_SOLVER_DENSE;
+    // mslam_hip_set_pose_graph_loss: read by mslam_hip_pose_graph and mslam_hip_pose_graph_edge_weights when they are called;
+    // mslam_hip_set_pnp_mse_loss: read by mslam_hip_pnp_min_mse[_batch_dev].  Kinds are MSLAM_HIP_BA_LOSS_*; NONE keeps scale 0
+    int pg_loss_kind = MSLAM_HIP_BA_LOSS_NONE;
+    double pg_loss_scale = 0.0;
+    int mse_loss_kind = MSLAM_HIP_BA_LOSS_NONE;
+    double mse_loss_scale = 0.0;
     // mslam_hip_set_ba_global_solver: read by mslam_hip_bundle_adjust_global when it is called; SPARSE keeps the envelope in
     // d_ba_S
     int bag_solver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;

@@ -3,8 +3,9 @@
 // Replaces MinMseTracker::solvePnp (reference ceres_reprojection_error_pnp.cpp:18-110): a Ceres Levenberg-Marquardt
 // solve over x = (r, t) (angle-axis r, translation t) of
 //     cost(x) = 1/2 sum_i |obs_i - proj(AngleAxisRotatePoint(r, P_i) + t)|^2,   proj(X) = (fx X/Z + cx, fy Y/Z + cy)
-// with no loss function, started from the caller's pose, gradient / function / parameter tolerance 1e-8 (:88-90) and
-// every other option at Solver::Options' default.  The minimiser is Ceres 2.2's published trust-region loop
+// with no loss function (mslam_hip_set_pnp_mse_loss sets one, an extension: k_pnp_min_mse_loss below, cost 1/2 sum rho, rho' on
+// every product of a point's share of the sums), started from the caller's pose, gradient / function /
+// parameter tolerance 1e-8 (:88-90) and every other option at Solver::Options' default.  The minimiser is Ceres 2.2's published trust-region loop
 // (trust_region_minimizer.cc, levenberg_marquardt_strategy.cc, trust_region_step_evaluator.cc, solver.cc), written out
 // here for a wave that keeps one problem in registers; the defaults, the termination codes and the butterfly sum are
 // trust_region.hpp's, which holds the same loop as control-block kernels for k_ba.hip and k_posegraph.hip.  The
@@ -202,7 +203,18 @@ struct MseSums
     double g[6];
 };
 
-__device__ void mse_sweep(const MseArgs& a, const double* obj, const double* img, int n, int lane, const double x[6], MseSums& S)
+// what k_pnp_min_mse_loss's launch carries.  The loss travels in the argument's type (Args below), not as one more parameter
+// of mse_sweep and mse_problem: with a further parameter k_pnp_min_mse's registers are numbered anew
+struct MseLossArgs : MseArgs
+{
+    TrLoss loss; // mslam_hip_set_pnp_mse_loss: HUBER or CAUCHY, a in pixels
+};
+
+// kLoss (Args = MseLossArgs): with s = res0^2 + res1^2 the lane adds 0.5 rho(s) to the cost and w = rho'(s) times the
+// product to each of the 21 + 6 sums.  The sweep keeps no rows that could be scaled by sqrt(w), so the weight goes on the
+// products, as in k_ba.hip (DEVIATES in rounding from Ceres's corrector, include/mslam_hip.h)
+template <bool kLoss, class Args>
+__device__ void mse_sweep(const Args& a, const double* obj, const double* img, int n, int lane, const double x[6], MseSums& S)
 {
     S.cost = 0.0;
     for(int k = 0; k < 21; ++k)
@@ -214,13 +226,29 @@ __device__ void mse_sweep(const MseArgs& a, const double* obj, const double* img
         const double P[3] = {obj[(size_t)i * 3], obj[(size_t)i * 3 + 1], obj[(size_t)i * 3 + 2]};
         double res[2], J[2][6];
         mse_residual(x, P, img[(size_t)i * 2], img[(size_t)i * 2 + 1], a.fx, a.fy, a.cx, a.cy, res, J);
-        S.cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
-        int k = 0;
-        for(int r = 0; r < 6; ++r)
+        if constexpr(kLoss)
         {
-            for(int c = r; c < 6; ++c)
-                S.H[k++] += J[0][r] * J[0][c] + J[1][r] * J[1][c];
-            S.g[r] += J[0][r] * res[0] + J[1][r] * res[1];
+            double rho, w;
+            tr_loss(a.loss.kind, a.loss.scale, res[0] * res[0] + res[1] * res[1], rho, w);
+            S.cost += 0.5 * rho;
+            int k = 0;
+            for(int r = 0; r < 6; ++r)
+            {
+                for(int c = r; c < 6; ++c)
+                    S.H[k++] += w * (J[0][r] * J[0][c] + J[1][r] * J[1][c]);
+                S.g[r] += w * (J[0][r] * res[0] + J[1][r] * res[1]);
+            }
+        }
+        else
+        {
+            S.cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
+            int k = 0;
+            for(int r = 0; r < 6; ++r)
+            {
+                for(int c = r; c < 6; ++c)
+                    S.H[k++] += J[0][r] * J[0][c] + J[1][r] * J[1][c];
+                S.g[r] += J[0][r] * res[0] + J[1][r] * res[1];
+            }
         }
     }
     S.cost = wave_sum(S.cost);
@@ -251,7 +279,8 @@ __device__ __forceinline__ double gradient_max_norm(const double x[6], const dou
     return m;
 }
 
-__device__ void mse_problem(const MseArgs& a, int p, int lane)
+template <bool kLoss, class Args>
+__device__ void mse_problem(const Args& a, int p, int lane)
 {
     double* pose = a.pose + (size_t)p * 6;
     double* info = a.info + (size_t)p * 4;
@@ -284,7 +313,7 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
 
     // iteration 0 (TrustRegionMinimizer::IterationZero)
     MseSums X;
-    mse_sweep(a, obj, img, n, lane, x, X);
+    mse_sweep<kLoss>(a, obj, img, n, lane, x, X);
     const double initial_cost = X.cost;
     if(!sums_finite(X))
     {
@@ -409,7 +438,7 @@ __device__ void mse_problem(const MseArgs& a, int p, int lane)
         for(int k = 0; k < 6; ++k)
             cand[k] = x[k] + ds[k] * s[k]; // delta = step * jacobian_scaling, Plus = x + delta
         MseSums C;
-        mse_sweep(a, obj, img, n, lane, cand, C);
+        mse_sweep<kLoss>(a, obj, img, n, lane, cand, C);
         // a candidate that fails to evaluate is a step of infinite cost (ComputeCandidatePointAndEvaluateCost)
         const double cand_cost = isfinite(C.cost) ? C.cost : DBL_MAX;
         // ParameterToleranceReached
@@ -464,12 +493,31 @@ __global__ __launch_bounds__(kMseThreads) void k_pnp_min_mse(MseArgs a)
     const int p = blockIdx.x * kMseWaves + (int)(threadIdx.x >> 6);
     if(p >= a.n_problems)
         return;
-    mse_problem(a, p, (int)(threadIdx.x & 63));
+    mse_problem<false>(a, p, (int)(threadIdx.x & 63));
 }
 
-static void launch_min_mse(const MseArgs& a, hipStream_t stream)
+// mslam_hip_set_pnp_mse_loss: the second form, launched only with HUBER or CAUCHY
+__global__ __launch_bounds__(kMseThreads) void k_pnp_min_mse_loss(MseLossArgs a)
 {
-    hipLaunchKernelGGL(k_pnp_min_mse, dim3((a.n_problems + kMseWaves - 1) / kMseWaves), dim3(kMseThreads), 0, stream, a);
+    const int p = blockIdx.x * kMseWaves + (int)(threadIdx.x >> 6);
+    if(p >= a.n_problems)
+        return;
+    mse_problem<true>(a, p, (int)(threadIdx.x & 63));
+}
+
+// the context's loss; NONE: the launch of before the setting existed
+static void launch_min_mse(const mslam_hip_ctx* c, const MseArgs& a, hipStream_t stream)
+{
+    const dim3 grid((a.n_problems + kMseWaves - 1) / kMseWaves);
+    if(c->mse_loss_kind != MSLAM_HIP_BA_LOSS_NONE)
+    {
+        MseLossArgs la{};
+        static_cast<MseArgs&>(la) = a;
+        la.loss = TrLoss{c->mse_loss_kind, c->mse_loss_scale};
+        hipLaunchKernelGGL(k_pnp_min_mse_loss, grid, dim3(kMseThreads), 0, stream, la);
+    }
+    else
+        hipLaunchKernelGGL(k_pnp_min_mse, grid, dim3(kMseThreads), 0, stream, a);
 }
 
 } // namespace mslam
@@ -518,7 +566,7 @@ extern "C" int mslam_hip_pnp_min_mse(mslam_hip_ctx* c, const double* object_poin
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.pose = d + (size_t)n * 5, a.info = d + (size_t)n * 5 + 6;
     if(e == hipSuccess)
-        launch_min_mse(a, c->stream);
+        launch_min_mse(c, a, c->stream);
     PCHK(hipGetLastError());
     double out[10];
     PCHK(hipMemcpyAsync(out, a.pose, sizeof(out), hipMemcpyDeviceToHost, c->stream));
@@ -570,12 +618,36 @@ extern "C" int mslam_hip_pnp_min_mse_batch_dev(mslam_hip_ctx* c, const double* d
     a.pose = d_pose, a.info = d_info;
     {
         StageScope t(c, "pnp_min_mse");
-        launch_min_mse(a, c->stream);
+        launch_min_mse(c, a, c->stream);
     }
     if(hipGetLastError() != hipSuccess)
     {
         c->err = "pnp_min_mse_batch_dev: launch failed";
         return MSLAM_HIP_E_RUNTIME;
     }
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_set_pnp_mse_loss(mslam_hip_ctx* c, int kind, double scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY)
+        return mslam::fail(c, MSLAM_HIP_E_INVALID, "set_pnp_mse_loss: kind outside 0..2");
+    if(kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0))
+        return mslam::fail(c, MSLAM_HIP_E_INVALID, "set_pnp_mse_loss: the scale of HUBER / CAUCHY must be finite and > 0");
+    c->mse_loss_kind = kind;
+    c->mse_loss_scale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_pnp_mse_loss(mslam_hip_ctx* c, int* kind, double* scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind)
+        *kind = c->mse_loss_kind;
+    if(scale)
+        *scale = c->mse_loss_scale;
     return MSLAM_HIP_OK;
 }

@@ -42,6 +42,10 @@
 //                   block by a fixed tree
 //   k_pg_control    one wave: sums the block partials in a fixed order, step validity, parameter / function tolerance,
 //                   accept or reject, radius
+// mslam_hip_set_pose_graph_loss (an extension, NONE by default): with HUBER or CAUCHY k_pg_edges_loss and k_pg_eval_loss stand
+// where k_pg_edges and k_pg_eval stand: the stored r_e and Jacobians are multiplied by sqrt(rho'(|r_e|^2)), Ceres's corrector on
+// the rows, the cost is 1/2 sum rho, and every other kernel of the list runs unchanged on the corrected blocks.
+// k_pg_edge_weights (mslam_hip_pose_graph_edge_weights) reports |r_e|^2 and rho' per edge at given poses.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
 #include "reduced_system.hpp"
@@ -115,6 +119,12 @@ __device__ __forceinline__ void pg_residual(const double* __restrict__ xa, const
             s += pg_info(info, i, k) * u[k];
         r[i] = s;
     }
+}
+
+// s = |r_e|^2 over the six weighted components, in the order of the cost
+__device__ __forceinline__ double pg_sq_norm(const double r[6])
+{
+    return ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]);
 }
 
 // ---- blocks ------------------------------------------------------------------------------------------------------------
@@ -412,6 +422,162 @@ __global__ __launch_bounds__(64) void k_pg_control(PgArgs a)
                 a.pose[(size_t)k * 7 + j] = a.cand[(size_t)k * 7 + j];
 }
 
+// ---- mslam_hip_set_pose_graph_loss: the second forms, launched only with HUBER or CAUCHY -----------------------------------
+
+// Both repeat their NONE twin's text instead of sharing a body with it: k_pg_edges and k_pg_eval read the kernel argument in
+// place, and moving their bodies into a function reorders their instructions (k_ba.hip keeps its ba_loss for the same reason:
+// the kernels of before the setting keep their machine code).  A change to one of the twins belongs in the other.
+
+// Ceres's corrector as corrector.cc writes it, on the rows: the body of k_pg_edges, then the stored r_e and both stored
+// Jacobians times sqrt(w_e), w_e = rho'(|r_e|^2) at the state.  Everything that reads a.r and a.J then runs on the corrected
+// blocks.  sqrt(1.0) is 1.0 and a product with 1.0 keeps its bits: an edge of weight 1 stores what k_pg_edges stores
+__global__ __launch_bounds__(256) void k_pg_edges_loss(PgArgs a, TrLoss loss)
+{
+    const TrCtrl* ct = a.ctrl;
+    if(ct->done || !ct->need_jac)
+        return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if(e >= a.E)
+        return;
+    const double* xa = a.pose + (size_t)a.ea[e] * 7;
+    const double* xb = a.pose + (size_t)a.eb[e] * 7;
+    const double* z = a.meas + (size_t)e * 7;
+    const double* info = a.info ? a.info + (size_t)e * 36 : nullptr;
+    double r[6];
+    pg_residual(xa, xb, z, info, r);
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+        a.r[(size_t)e * 6 + i] = r[i];
+    // P = R_a^T, G = 2 P [v]x, M2 = 2 M
+    double qai[4], qbi[4], A[4], P[9], G[9], M2[9];
+    quat_inverse(xa, qai);
+    quat_inverse(xb, qbi);
+    quat_matrix(qai, P);
+    const double v[3] = {xb[4] - xa[4], xb[5] - xa[5], xb[6] - xa[6]};
+    const double vx[9] = {0.0, -v[2], v[1], v[2], 0.0, -v[0], -v[1], v[0], 0.0};
+#pragma unroll
+    for(int i = 0; i < 3; ++i)
+#pragma unroll
+        for(int j = 0; j < 3; ++j)
+            G[i * 3 + j] = 2.0 * (P[i * 3] * vx[j] + P[i * 3 + 1] * vx[3 + j] + P[i * 3 + 2] * vx[6 + j]);
+    const double qm[4] = {z[0], z[1], z[2], z[3]}, B[4] = {xa[0], xa[1], xa[2], xa[3]};
+    quat_product(qm, qbi, A);
+#pragma unroll
+    for(int j = 0; j < 3; ++j)
+    {
+        const double ej[4] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, 0.0};
+        double t[4], w[4];
+        quat_product(A, ej, t);
+        quat_product(t, B, w);
+        M2[j] = 2.0 * w[0], M2[3 + j] = 2.0 * w[1], M2[6 + j] = 2.0 * w[2];
+    }
+    double* Ja = a.J + (size_t)e * 72;
+    double* Jb = Ja + 36;
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+    {
+        const double w0 = pg_info(info, i, 0), w1 = pg_info(info, i, 1), w2 = pg_info(info, i, 2);
+        const double w3 = pg_info(info, i, 3), w4 = pg_info(info, i, 4), w5 = pg_info(info, i, 5);
+#pragma unroll
+        for(int j = 0; j < 3; ++j)
+        {
+            const double wp = w0 * P[j] + w1 * P[3 + j] + w2 * P[6 + j];
+            const double wm = w3 * M2[j] + w4 * M2[3 + j] + w5 * M2[6 + j];
+            Ja[i * 6 + j] = (w0 * G[j] + w1 * G[3 + j] + w2 * G[6 + j]) + wm;
+            Ja[i * 6 + 3 + j] = -wp;
+            Jb[i * 6 + j] = -wm;
+            Jb[i * 6 + 3 + j] = wp;
+        }
+    }
+    double rho, w;
+    tr_loss(loss.kind, loss.scale, pg_sq_norm(r), rho, w);
+    const double sw = sqrt(w);
+#pragma unroll
+    for(int i = 0; i < 6; ++i)
+        a.r[(size_t)e * 6 + i] = sw * r[i];
+#pragma unroll
+    for(int j = 0; j < 72; ++j)
+        Ja[j] = sw * Ja[j];
+}
+
+// k_pg_eval with cost = 1/2 rho(|r|^2) of the uncorrected residual, at the state (at_start) and at the candidate; the model
+// term reads the corrected blocks k_pg_edges_loss stored
+__global__ __launch_bounds__(256) void k_pg_eval_loss(PgArgs a, int at_start, TrLoss loss)
+{
+    __shared__ double red[4];
+    if(a.ctrl->done)
+        return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    double model = 0.0, cost = 0.0;
+    if(e < a.E)
+    {
+        const int ka = a.ea[e], kb = a.eb[e];
+        const double* z = a.meas + (size_t)e * 7;
+        const double* info = a.info ? a.info + (size_t)e * 36 : nullptr;
+        double r[6];
+        if(at_start)
+            pg_residual(a.pose + (size_t)ka * 7, a.pose + (size_t)kb * 7, z, info, r);
+        else
+        {
+            double sa[6], sb[6];
+            pg_step(a, ka, sa);
+            pg_step(a, kb, sb);
+            const double* Ja = a.J + (size_t)e * 72;
+            const double* f = a.r + (size_t)e * 6;
+#pragma unroll
+            for(int i = 0; i < 6; ++i)
+            {
+                double js = 0.0;
+#pragma unroll
+                for(int j = 0; j < 6; ++j)
+                    js += Ja[i * 6 + j] * sa[j];
+#pragma unroll
+                for(int j = 0; j < 6; ++j)
+                    js += Ja[36 + i * 6 + j] * sb[j];
+                model += js * (f[i] + js / 2.0);
+            }
+            model = -model;
+            pg_residual(a.cand + (size_t)ka * 7, a.cand + (size_t)kb * 7, z, info, r);
+        }
+        double rho, w;
+        tr_loss(loss.kind, loss.scale, pg_sq_norm(r), rho, w);
+        cost = 0.5 * rho;
+    }
+    const double ms = block_sum(model, red), cs = block_sum(cost, red);
+    if(threadIdx.x == 0)
+    {
+        a.part[blockIdx.x] = ms;
+        a.part[a.n_blocks + blockIdx.x] = cs;
+    }
+}
+
+// mslam_hip_pose_graph_edge_weights: a lane per edge, chi2 = |r_e|^2 at the given poses and weight = rho'(chi2)
+struct PgWeightArgs
+{
+    int E, loss_kind;
+    double loss_scale;
+    const double* pose;     // [K] x 7
+    const int32_t *ea, *eb; // [E]
+    const double *meas, *info; // [E] x 7; [E] x 36 or nullptr
+    double *chi2, *weight;  // [E] each
+};
+
+__global__ __launch_bounds__(256) void k_pg_edge_weights(PgWeightArgs a)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if(e >= a.E)
+        return;
+    double r[6];
+    pg_residual(a.pose + (size_t)a.ea[e] * 7, a.pose + (size_t)a.eb[e] * 7, a.meas + (size_t)e * 7,
+                a.info ? a.info + (size_t)e * 36 : nullptr, r);
+    const double s = pg_sq_norm(r);
+    double rho, w = 1.0;
+    if(a.loss_kind != MSLAM_HIP_BA_LOSS_NONE)
+        tr_loss(a.loss_kind, a.loss_scale, s, rho, w);
+    a.chi2[e] = s;
+    a.weight[e] = w;
+}
+
 } // namespace mslam
 
 using namespace mslam;
@@ -554,16 +720,25 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     *c->h_ba.get() = 0;
     ls.bind(c, d, a.yc);
     a.env_off = ls.env.row_off, a.env_first = ls.env.first, a.rhs = ls.env.rhs;
+    // NONE: the launches of before the setting existed
+    const TrLoss tl{c->pg_loss_kind, c->pg_loss_scale};
+    const bool loss = tl.kind != MSLAM_HIP_BA_LOSS_NONE;
 
     const dim3 g_edge((unsigned)a.n_blocks), g_x((unsigned)((K + 255) / 256)), g_pair((unsigned)a.n_pairs);
     {
         StageScope ts(c, "pg_start_cost");
-        hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
+        if(loss)
+            hipLaunchKernelGGL(k_pg_eval_loss, g_edge, dim3(256), 0, s, a, 1, tl);
+        else
+            hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
     }
     const int rc = tr_run(c, "pg_iterations", "pose_graph", a.ctrl, max_iterations, [&] {
         {
             StageScope tk(c, "pg_blocks");
-            hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
+            if(loss)
+                hipLaunchKernelGGL(k_pg_edges_loss, g_edge, dim3(256), 0, s, a, tl);
+            else
+                hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
             hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
             hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
         }
@@ -571,7 +746,10 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
             ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_pg_assemble_env : k_pg_assemble, g_pair, dim3(64), 0, s, a); });
         StageScope tk(c, "pg_step");
         hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
+        if(loss)
+            hipLaunchKernelGGL(k_pg_eval_loss, g_edge, dim3(256), 0, s, a, 0, tl);
+        else
+            hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
         hipLaunchKernelGGL(k_pg_control, dim3(1), dim3(64), 0, s, a);
     }, sum);
     if(rc != MSLAM_HIP_OK)
@@ -608,5 +786,73 @@ extern "C" int mslam_hip_get_pose_graph_solver(mslam_hip_ctx* c, int* kind)
         return MSLAM_HIP_E_INVALID;
     if(kind)
         *kind = c->pg_solver;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_set_pose_graph_loss(mslam_hip_ctx* c, int kind, double scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY)
+        return fail(c, MSLAM_HIP_E_INVALID, "set_pose_graph_loss: kind outside 0..2");
+    if(kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0))
+        return fail(c, MSLAM_HIP_E_INVALID, "set_pose_graph_loss: the scale of HUBER / CAUCHY must be finite and > 0");
+    c->pg_loss_kind = kind;
+    c->pg_loss_scale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_pose_graph_loss(mslam_hip_ctx* c, int* kind, double* scale)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(kind)
+        *kind = c->pg_loss_kind;
+    if(scale)
+        *scale = c->pg_loss_scale;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_pose_graph_edge_weights(mslam_hip_ctx* c, const double* poses, int K, const int32_t* edge_a,
+                                                 const int32_t* edge_b, const double* edge_meas, const double* sqrt_info, int E,
+                                                 double* chi2, double* weight)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    // no linear system is formed: the cap on K is the SPARSE solver's, whichever solver is set
+    if(const int rc = pg_validate(c, MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE, poses, K, edge_a, edge_b, edge_meas, sqrt_info, E, 0);
+       rc != MSLAM_HIP_OK)
+        return rc;
+    if(E == 0)
+        return MSLAM_HIP_OK;
+    // one block: the problem, then chi2 and weight side by side, so the call is one upload, one launch and one download
+    TrStaging st(0);
+    const size_t o_pose = st.put(poses, (size_t)K * 56), o_meas = st.put(edge_meas, (size_t)E * 56);
+    const size_t o_info = st.put(sqrt_info, sqrt_info ? (size_t)E * 288 : 0);
+    const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4);
+    const size_t o_out = st.carve((size_t)E * 16);
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, grow(c->d_pg, st.size, c->stream));
+    uint8_t* d = c->d_pg;
+    hipStream_t s = c->stream;
+    MSLAM_CHK(c, st.upload(d, s));
+    PgWeightArgs a{};
+    a.E = E, a.loss_kind = c->pg_loss_kind, a.loss_scale = c->pg_loss_scale;
+    a.pose = reinterpret_cast<const double*>(d + o_pose), a.meas = reinterpret_cast<const double*>(d + o_meas);
+    a.info = sqrt_info ? reinterpret_cast<const double*>(d + o_info) : nullptr;
+    a.ea = reinterpret_cast<const int32_t*>(d + o_ea), a.eb = reinterpret_cast<const int32_t*>(d + o_eb);
+    a.chi2 = reinterpret_cast<double*>(d + o_out), a.weight = a.chi2 + E;
+    {
+        StageScope ts(c, "pg_edge_weights");
+        hipLaunchKernelGGL(k_pg_edge_weights, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, a);
+    }
+    MSLAM_CHK(c, hipGetLastError());
+    std::vector<double> out((size_t)E * 2);
+    MSLAM_CHK(c, hipMemcpyAsync(out.data(), a.chi2, (size_t)E * 16, hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(chi2)
+        std::memcpy(chi2, out.data(), (size_t)E * 8);
+    if(weight)
+        std::memcpy(weight, out.data() + E, (size_t)E * 8);
     return MSLAM_HIP_OK;
 }

@@ -69,6 +69,42 @@ __device__ __forceinline__ double block_sum(double v, double* red)
 __device__ __forceinline__ int tri6(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); } // r <= c < 6
 __device__ __forceinline__ int tri3(int r, int c) { return r * 3 - r * (r - 1) / 2 + (c - r); } // r <= c < 3
 
+// ---- the loss of the pose graph and of min-MSE PnP (k_ba.hip keeps its own ba_loss, the same formulas) -------------------
+
+// what a loss form's launch carries: MSLAM_HIP_BA_LOSS_HUBER or _CAUCHY and its scale a
+struct TrLoss
+{
+    int kind;
+    double scale;
+};
+// loss_function.h's HuberLoss / CauchyLoss Evaluate at s = |r|^2 with scale a: rho(s) and w = rho'(s).  b = a^2.
+//   HUBER:  s <= b: rho = s, w = 1 (s == b is the inlier branch); else rho = 2 a sqrt(s) - b, w = max(DBL_MIN, a / sqrt(s))
+//   CAUCHY: rho = b log(1 + s / b), w = max(DBL_MIN, 1 / (1 + s / b)), s / b evaluated as s (1 / b)
+// kind is MSLAM_HIP_BA_LOSS_HUBER or _CAUCHY (the callers keep NONE away).  rho'' <= 0 for both, so corrector.cc takes the
+// branch that scales residual and Jacobians by sqrt(w) and nothing else.  s = 0 gives w = 1 in both (no 0 / 0); a NaN s
+// gives a NaN rho, which the cost carries to FAILURE.
+__device__ __forceinline__ void tr_loss(int kind, double a, double s, double& rho, double& w)
+{
+    const double b = a * a;
+    if(kind == MSLAM_HIP_BA_LOSS_HUBER)
+    {
+        if(s <= b)
+            rho = s, w = 1.0;
+        else
+        {
+            const double r = sqrt(s);
+            rho = 2.0 * a * r - b;
+            w = fmax(DBL_MIN, a / r);
+        }
+    }
+    else
+    {
+        const double sum = 1.0 + s * (1.0 / b);
+        rho = b * log(sum);
+        w = fmax(DBL_MIN, 1.0 / sum);
+    }
+}
+
 // ---- quaternions, Eigen's x y z w ----------------------------------------------------------------------------------------
 
 // Eigen's inverse(): conjugate / squared norm

@@ -51,6 +51,12 @@
 //                                    the block-envelope factor, up to 16384 keyframes); a kind the backend refuses is its
 //                                    std::invalid_argument: "error: ..." and exit code 1; a kind that is no integer is a
 //                                    usage error, exit code 2
+//        mslam_harness <plugin.so> --pose-graph <scene> [--sparse] --loss huber:<a> | cauchy:<a>
+//                                    the same with IRobustPoseGraphBackend::setPoseGraphLoss(kind, a) first (a in the unit of the
+//                                    weighted residual, finite and > 0), after --sparse when both are given: the costs of the
+//                                    summary are then 1/2 sum rho
+//        mslam_harness <plugin.so> --pnp-mse <scene> --loss huber:<a> | cauchy:<a>
+//                                    hipMinMseTrackerFactory with IRobustPnp::setLoss(kind, a) first (a in pixels)
 //        mslam_harness <plugin.so> --fuse <scene>
 //                                    ILandmarkFuser::fuseLandmarks of the relocalizer adapter (the vocabulary it loads comes
 //                                    from MSLAM_ORB_VOCABULARY or ./orbvoc.dbow3) on the scene's first two entries, keep then
@@ -115,9 +121,17 @@ int main(int argc, char** argv)
         std::unique_ptr<mslam::IOrbFeatureDetector> detector = makeDetector();
         std::unique_ptr<mslam::IOrbMatcher> matcher = makeMatcher();
         std::printf("loaded %s\n", detector && matcher ? "ok" : "null");
-        const bool pnp_mse = argc == 4 && std::strcmp(argv[2], "--pnp-mse") == 0;
-        if(argc == 4 && (std::strcmp(argv[2], "--pnp") == 0 || pnp_mse))
+        const bool pnp_mse_loss = argc == 6 && std::strcmp(argv[2], "--pnp-mse") == 0 && std::strcmp(argv[4], "--loss") == 0;
+        const bool pnp_mse = (argc == 4 && std::strcmp(argv[2], "--pnp-mse") == 0) || pnp_mse_loss;
+        if((argc == 4 && std::strcmp(argv[2], "--pnp") == 0) || pnp_mse)
         {
+            int lossKind = 0;
+            double lossScale = 0.0;
+            if(pnp_mse_loss && !mslam::parseLoss(argv[5], lossKind, lossScale))
+            {
+                std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[5]);
+                return 2;
+            }
             // scene file: u32 n, then n x (3 f64 landmark, 2 f64 image point), then the initial sensor pose (3 f64 position,
             // 4 f64 quaternion w x y z) and fx fy cx cy
             std::ifstream in(argv[3], std::ios::binary);
@@ -145,6 +159,16 @@ int main(int argc, char** argv)
             auto makePnp = mslam::loadFactoryMethod<mslam::ISlam3dPnp>(argv[1], pnp_mse ? "hipMinMseTrackerFactory"
                                                                                           : "hipRansacPnpFactory");
             std::unique_ptr<mslam::ISlam3dPnp> pnp = makePnp();
+            if(pnp_mse_loss)
+            {
+                auto* robust = dynamic_cast<mslam::IRobustPnp*>(pnp.get());
+                if(!robust)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setLoss on its min-MSE tracker\n");
+                    return 6;
+                }
+                robust->setLoss(lossKind, lossScale);
+            }
             mslam::CameraParameters cp;
             cp.focal = mslam::Vector2(cam[0], cam[1]);
             cp.principalPoint = mslam::Vector2(cam[2], cam[3]);
@@ -282,12 +306,23 @@ int main(int argc, char** argv)
                 std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
             return 0;
         }
-        if((argc == 4 || (argc == 5 && std::strcmp(argv[4], "--sparse") == 0) || (argc == 6 && std::strcmp(argv[4], "--solver") == 0)) &&
+        // --pose-graph <scene>, then nothing, --sparse, --solver <kind>, --loss <spec> or --sparse --loss <spec>
+        const bool pgLossOnly = argc == 6 && std::strcmp(argv[4], "--loss") == 0;
+        const bool pgSparseLoss = argc == 7 && std::strcmp(argv[4], "--sparse") == 0 && std::strcmp(argv[5], "--loss") == 0;
+        if((argc == 4 || (argc == 5 && std::strcmp(argv[4], "--sparse") == 0) || (argc == 6 && std::strcmp(argv[4], "--solver") == 0) ||
+            pgLossOnly || pgSparseLoss) &&
            std::strcmp(argv[2], "--pose-graph") == 0)
         {
-            const bool setSolver = argc > 4;
+            const bool setSolver = argc > 4 && !pgLossOnly;
             int solverKind = 1;
-            if(argc == 6)
+            int lossKind = 0;
+            double lossScale = 0.0;
+            if((pgLossOnly || pgSparseLoss) && !mslam::parseLoss(argv[argc - 1], lossKind, lossScale))
+            {
+                std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[argc - 1]);
+                return 2;
+            }
+            if(argc == 6 && !pgLossOnly)
             {
                 // a whole integer or nothing: "abc" and "1x" are usage errors, not kind 0 or 1
                 char* end = nullptr;
@@ -372,6 +407,16 @@ int main(int argc, char** argv)
                     return 6;
                 }
                 sparseBackend->setPoseGraphSolver(solverKind);
+            }
+            if(pgLossOnly || pgSparseLoss)
+            {
+                auto* robust = dynamic_cast<mslam::IRobustPoseGraphBackend*>(backend.get());
+                if(!robust)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setPoseGraphLoss\n");
+                    return 6;
+                }
+                robust->setPoseGraphLoss(lossKind, lossScale);
             }
             const mslam::BackendOutput out = loopBackend->closeLoop(keyframes, edges, head[3]);
             std::printf("pose_graph termination %d iterations %d initial %.17g final %.17g keyframes %zu edges %zu\n", out.termination,

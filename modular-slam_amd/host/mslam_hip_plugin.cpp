@@ -10,10 +10,12 @@
 //                                                           (orb_relocalizer.cpp:26-50, rgbd_feature_frontend.cpp:153,176)
 //   HipRansacPnp      : IPnpAlgorithm<SensorState,Vector3>  drop-in for OpenCvRansacPnp (cv_ransac_pnp.cpp:14-85)
 //   HipMinMseTracker  : IPnpAlgorithm<SensorState,Vector3>  drop-in for MinMseTracker
+//                     : IRobustPnp                          a Huber or Cauchy loss on its reprojection errors (an extension)
 //   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
 //                          : IRobustBackend                                       a Huber or Cauchy loss for both bundle adjustments (an extension)
 //                          : ISparsePoseGraphBackend                              closeLoop's linear solver: dense or the block-envelope factor (an extension)
 //                          : ISparseGlobalBackend                                 globalBundleAdjustment's linear solver, the same choice (an extension)
+//                          : IRobustPoseGraphBackend                              a Huber or Cauchy loss on closeLoop's edges (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -949,11 +951,19 @@ class HipRansacPnp : public ISlam3dPnp
 // OpenCvRansacPnp's: the initial orientation becomes angle-axis as Eigen::AngleAxisd(q) does it and the initial position is
 // the translation itself, with no world -> camera inversion (:71-75); the result's angle, axis and position are cast to
 // float and the axis is divided by the float angle before the quaternion is built (:99-109); the inlier set stays empty
-// (the reference never sizes it).  DEVIATES: a result angle of exactly 0 gives the identity quaternion (the reference
+// (the reference never sizes it).  setLoss (IRobustPnp, an extension) keeps a loss for every later solve: it is set on the
+// adapter's own context before each one.  DEVIATES: a result angle of exactly 0 gives the identity quaternion (the reference
 // divides by zero and returns NaN).  Ceres's progress printout (minimizer_progress_to_stdout, :91) is not reproduced.
-class HipMinMseTracker : public ISlam3dPnp
+class HipMinMseTracker : public ISlam3dPnp, public IRobustPnp
 {
   public:
+    void setLoss(int kind, double scale) override
+    {
+        if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY ||
+           (kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0)))
+            throw std::invalid_argument("setLoss: kind 0 (none), 1 (Huber) or 2 (Cauchy); their scale finite and > 0");
+        lossKind = kind, lossScale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    }
     std::optional<PnpResult> solvePnp(const std::vector<std::shared_ptr<Landmark<Vector3>>>& landmarks,
                                       const std::vector<Vector2>& sensorPoints, const slam3d::SensorState& initial) override
     {
@@ -974,6 +984,8 @@ class HipMinMseTracker : public ISlam3dPnp
         const Quaternion& q = initial.orientation;
         toRodrigues(q.w(), q.x(), q.y(), q.z(), rvec);
         ctx.ensure(0, 0);
+        if(const int lrc = mslam_hip_set_pnp_mse_loss(ctx.h, lossKind, lossScale); lrc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_pnp_mse_loss", lrc);
         const int rc = mslam_hip_pnp_min_mse(ctx.h, obj.data(), img.data(), static_cast<int>(n), cameraParams.focal.x(),
                                              cameraParams.focal.y(), cameraParams.principalPoint.x(),
                                              cameraParams.principalPoint.y(), rvec, tvec, nullptr, nullptr, nullptr);
@@ -999,6 +1011,8 @@ class HipMinMseTracker : public ISlam3dPnp
   private:
     Ctx ctx;
     std::vector<double> obj, img;
+    int lossKind = MSLAM_HIP_BA_LOSS_NONE;
+    double lossScale = 0.0;
 };
 
 // drop-in for CeresBackend's solve (ceres_backend.cpp:140-240): the observations become mslam_hip_bundle_adjust's arrays —
@@ -1010,10 +1024,19 @@ class HipMinMseTracker : public ISlam3dPnp
 // (ISparsePoseGraphBackend, an extension) keeps its linear solver, set on the context before each closeLoop.  setLoss (IRobustBackend,
 // an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.  setGlobalSolver
 // (ISparseGlobalBackend, an extension) keeps the linear solver of globalBundleAdjustment, set the same way: with kind 1 up to
-// 16384 keyframes.
-class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend
+// 16384 keyframes.  setPoseGraphLoss (IRobustPoseGraphBackend, an extension) keeps a loss for the edges of closeLoop, set the
+// same way.
+class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend,
+                               public IRobustPoseGraphBackend
 {
   public:
+    void setPoseGraphLoss(int kind, double scale) override
+    {
+        if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY ||
+           (kind != MSLAM_HIP_BA_LOSS_NONE && !(std::isfinite(scale) && scale > 0.0)))
+            throw std::invalid_argument("setPoseGraphLoss: kind 0 (none), 1 (Huber) or 2 (Cauchy); their scale finite and > 0");
+        pgLossKind = kind, pgLossScale = kind == MSLAM_HIP_BA_LOSS_NONE ? 0.0 : scale;
+    }
     void setGlobalSolver(int kind) override
     {
         if(kind != MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE && kind != MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE)
@@ -1078,6 +1101,8 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
         ctx.ensure(0, 0);
         if(const int rs = mslam_hip_set_pose_graph_solver(ctx.h, poseGraphSolver); rs != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_set_pose_graph_solver", rs);
+        if(const int rs = mslam_hip_set_pose_graph_loss(ctx.h, pgLossKind, pgLossScale); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_pose_graph_loss", rs);
         mslam_hip_ba_summary summary{};
         const int rc = mslam_hip_pose_graph(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), edgeA.data(),
                                             edgeB.data(), meas.data(), anyInfo ? info.data() : nullptr, static_cast<int>(edges.size()),
@@ -1173,6 +1198,8 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     int globalSolver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;
     int lossKind = MSLAM_HIP_BA_LOSS_NONE;
     double lossScale = 0.0;
+    int pgLossKind = MSLAM_HIP_BA_LOSS_NONE;
+    double pgLossScale = 0.0;
 };
 
 // ---- factories + aliases (what loadFactoryMethod<T>(lib, name) imports) -------------------------------

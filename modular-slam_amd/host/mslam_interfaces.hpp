@@ -288,6 +288,29 @@ class ISparseGlobalBackend
     virtual void setGlobalSolver(int kind) = 0;
     virtual ~ISparseGlobalBackend() = default;
 };
+// extension: a loss function on the edges of closeLoop (mslam_hip_set_pose_graph_loss): kind 0 none (the default), 1 Ceres's
+// HuberLoss(scale), 2 CauchyLoss(scale), scale in the unit of the weighted residual of an edge.  It holds for every later
+// closeLoop of the object, with either linear solver; the bundle adjustments do not read it, and IRobustBackend::setLoss does not
+// reach closeLoop.  The costs of closeLoop's BackendOutput are then 1/2 sum rho.  A kind outside 0..2, or a scale that is not
+// finite or not > 0 with kind 1 or 2, throws std::invalid_argument and leaves the setting as it was.  An interface of its own,
+// reached with dynamic_cast like IRobustBackend: ILoopClosingBackend gains no virtual.
+class IRobustPoseGraphBackend
+{
+  public:
+    virtual void setPoseGraphLoss(int kind, double scale) = 0;
+    virtual ~IRobustPoseGraphBackend() = default;
+};
+// extension (the reference's MinMseTracker gives its residual blocks no loss, so every mismatch pulls the pose with full
+// weight): a loss function for solvePnp of hipMinMseTrackerFactory's object (mslam_hip_set_pnp_mse_loss): kinds as above,
+// scale in pixels.  It holds for every later solvePnp of the object.  Bad input throws std::invalid_argument and leaves the
+// setting as it was.  An interface of its own, reached with dynamic_cast: IPnpAlgorithm mirrors the reference and gains no
+// virtual.
+class IRobustPnp
+{
+  public:
+    virtual void setLoss(int kind, double scale) = 0;
+    virtual ~IRobustPnp() = default;
+};
 // "huber:<a>" or "cauchy:<a>" -> kind 1 or 2 and a; false (nothing written) for anything else, a trailing character or an a
 // that is not finite or not > 0
 inline bool parseLoss(const char* text, int& kind, double& scale)
