@@ -772,6 +772,54 @@ int mslam_hip_pose_graph_edge_weights(mslam_hip_ctx* ctx, const double* poses /*
                                       const int32_t* edge_b, const double* edge_meas /* E x 7 */,
                                       const double* sqrt_info /* E x 36, or NULL */, int E, double* chi2 /* E, may be NULL */,
                                       double* weight /* E, may be NULL */);
+/* ---- Marginal covariances of mslam_hip_pose_graph's problem (an extension) ----
+ * How certain a pose-graph answer is: blocks of Sigma = (J^T J)^-1 at the given poses, what ceres::Covariance computes next
+ * to Solve.  THE PROBLEM is mslam_hip_pose_graph's: the same arguments with the same checks (K in
+ * 0..MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE, E in 0..MSLAM_HIP_POSE_GRAPH_MAX_EDGES) and the same parameter blocks, the
+ * free poses that have an edge.  poses is read only.  J holds the edge Jacobians of mslam_hip_pose_graph on its tangent
+ * (delta, dp) per pose; there is no damping.  mslam_hip_set_pose_graph_loss is read: with HUBER / CAUCHY the Jacobians are the
+ * corrected ones (rows times sqrt(rho')) at the given poses.  mslam_hip_set_pose_graph_solver is NOT read: the factor runs on
+ * the block envelope at every K, in the order and with the envelope of mslam_hip_pose_graph_analyze; an envelope above
+ * MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS is MSLAM_HIP_E_CAPACITY.
+ *   pose_idx   P poses, P in 0..65536;  cov[p] is the 6 x 6 block of pose_idx[p], row-major, rows and columns (delta, dp); it
+ *              equals its transpose bit for bit (one triangle is computed and mirrored);
+ *   pair_a, pair_b   Q pairs, Q in 0..65536;  cross[q] = E[d_a d_b^T], rows from pair_a[q]; cross of (a, b) and of (b, a) are
+ *              transposes of each other bit for bit.
+ * THE TANGENT.  Plus(q, delta) = (sin|delta| delta / |delta|, cos|delta|) (x) q: delta is HALF a rotation vector, applied on
+ * the left (in the world frame).  The covariance of the rotation vector theta = 2 delta is 4 x the delta block, its cross
+ * terms with a position 2 x.  dp is the position's own increment.
+ * A CONSTANT pose gives a block of zeros, in cov and in cross (Ceres's rule for constant parameter blocks).
+ * MSLAM_HIP_E_INVALID beyond mslam_hip_pose_graph's: P or Q out of range; an index out of range; a free pose without an edge
+ * (it is not a parameter block); a pair with a == b; a pair of free poses that no edge joins (its block may lie outside the
+ * envelope, and only blocks inside it are computed).
+ * RANK.  Two cases are detected, both MSLAM_HIP_E_NO_MODEL: (structural, on the host before any launch) a connected component
+ * of the free poses none of whose members has an edge to a constant pose: its gauge is free, the message names its least
+ * pose; (numerical, on the device) a pivot of the Cholesky factor that is not > 0 or not finite.  Nothing rank-revealing is
+ * promised beyond these two: a problem that is singular in exact arithmetic but whose pivots round to small positive numbers
+ * returns large numbers, not an error.
+ * On every error nothing is written to cov / cross.  Two calls on the same input return the same bytes: no sum uses an
+ * atomic, every sum has one order, all arithmetic is f64, no kernel waits on another workgroup.  The envelope lives in the
+ * buffer of the SPARSE solves and the dense reduced systems; every later solve clears and assembles it anew and returns the
+ * bits it returns without this call.  One workgroup walks the envelope column by column, backwards, as one workgroup factors it.
+ * Against ceres::Covariance (Compute on the requested blocks, GetCovarianceBlockInTangentSpace, Options::apply_loss_function
+ * = true), restated from the published text.  PARITY UNPINNED: no Ceres build exists to compare with; the tests compare with
+ * tests/pose_graph_cov_ref.py (two dense inverses, R^-1 R^-T of a QR of J and L^-T L^-1 of a Cholesky of J^T J, on
+ * tests/pose_graph_ref.py's Jacobians; sparse LU solves at 16384 poses).
+ *   quantity                 SAME: (J^T J)^-1 in the tangent space of EigenQuaternionManifold, the loss applied;
+ *   constant blocks          SAME: zeros;
+ *   algorithm                DEVIATES in rounding: a Cholesky factor of the Jacobi-scaled J^T J on the block envelope and the
+ *                            Takahashi recursion over it (the scaling undone at the read-out), where Ceres's default is a
+ *                            sparse QR of J (SPARSE_QR) or an SVD (DENSE_SVD); J^T J squares the condition number;
+ *   which blocks             DEVIATES: only blocks inside the envelope: every pose, and the pairs an edge joins.  Ceres
+ *                            computes any requested pair;
+ *   rank deficiency          DEVIATES: Ceres's SPARSE_QR fails on a rank-deficient J by its own test, DENSE_SVD truncates by
+ *                            min_reciprocal_condition_number or null_space_rank (a pseudo-inverse); here the two cases above;
+ *   ambient space            not built: GetCovarianceBlock (7 x 7 per pose, through PlusJacobian). */
+int mslam_hip_pose_graph_covariance(mslam_hip_ctx* ctx, const double* poses /* K x 7 */, const uint8_t* fixed /* K, or NULL */,
+                                    int K, const int32_t* edge_a, const int32_t* edge_b, const double* edge_meas /* E x 7 */,
+                                    const double* sqrt_info /* E x 36, or NULL */, int E, const int32_t* pose_idx, int P,
+                                    double* cov /* P x 36 */, const int32_t* pair_a, const int32_t* pair_b, int Q,
+                                    double* cross /* Q x 36 */);
 /* ---- A loss function for mslam_hip_pnp_min_mse and mslam_hip_pnp_min_mse_batch_dev (an extension) ----
  * Context state, read by both entries when they are called; independent of mslam_hip_set_ba_loss and
  * mslam_hip_set_pose_graph_loss, which do not reach these entries.  The kinds are MSLAM_HIP_BA_LOSS_*.  The default is NONE:

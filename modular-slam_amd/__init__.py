@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_ba_global_solver", "mslam_hip_get_ba_global_solver", "mslam_hip_bundle_adjust_global_analyze",
     "mslam_hip_set_pose_graph_loss", "mslam_hip_get_pose_graph_loss", "mslam_hip_pose_graph_edge_weights",
     "mslam_hip_set_pnp_mse_loss", "mslam_hip_get_pnp_mse_loss",
+    "mslam_hip_pose_graph_covariance",
 ]
 
 
@@ -747,6 +748,28 @@ class Context:
         res = {k: getattr(out, k) for k, _ in BaSummary._fields_ if k != "reserved"}
         res.update(poses=x)
         return res
+
+    def pose_graph_covariance(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, poses_of=(), pairs=()):
+        """Marginal covariances of pose_graph's problem at `poses` (mslam_hip_pose_graph_covariance; pose_graph's arguments,
+        K <= 16384 whichever solver is set): blocks of (J^T J)^-1 over the free poses that have an edge, on the solver's
+        tangent (delta, dp) per pose (delta is half a rotation vector in the world frame), under set_pose_graph_loss.
+        poses_of: pose indices; pairs: (a, b) index pairs, each joined by an edge unless one of the two is constant.
+        -> dict(cov [P, 6, 6], cross [Q, 6, 6]): cov[p] the block of poses_of[p], cross[q] = E[d_a d_b^T] with rows from a.  A
+        constant pose gives zeros.  MslamHipError: E_INVALID for a free pose without an edge, a pair a == b or a pair no
+        edge joins; E_NO_MODEL for a rank-deficient problem (a component without an edge to a constant pose, a pivot that
+        is not > 0); E_CAPACITY for an envelope above POSE_GRAPH_MAX_ENVELOPE_BLOCKS.  Nothing is returned then."""
+        x = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        ea, eb, z, w = self._pose_graph_edges("pose_graph_covariance", edge_a, edge_b, edge_meas, sqrt_info)
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+        if fx is not None and len(fx) != len(x):
+            raise MslamHipError(E_INVALID, "pose_graph_covariance: %d poses, %d fixed flags" % (len(x), len(fx)))
+        idx = np.ascontiguousarray(poses_of, np.int32).reshape(-1)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        cov, cross = np.zeros((max(len(idx), 1), 6, 6)), np.zeros((max(len(pr), 1), 6, 6))
+        self._chk(self.L.mslam_hip_pose_graph_covariance(self._h, _p(x), _p(fx), len(x), _p(ea), _p(eb), _p(z), _p(w), len(ea),
+                                                         _p(idx), len(idx), _p(cov), _p(pa), _p(pb), len(pr), _p(cross)))
+        return dict(cov=cov[:len(idx)], cross=cross[:len(pr)])
 
     def kf_update_world(self, landmark_ids, world_xyz):
         """every landmark of every stored keyframe whose landmark id is listed takes the listed world point -> the number
@@ -1818,13 +1841,18 @@ class HipBackend:
         fixed = np.array([id == self.first for id in ids], np.uint8)
         return ids, poses, fixed, np.array(ea, np.int32), np.array(eb, np.int32), np.array(meas, np.float64).reshape(-1, 7), info
 
-    def close_loop(self, cur_id, loop_id, rvec, tvec, graph, sqrt_info=None):
+    def close_loop(self, cur_id, loop_id, rvec, tvec, graph, sqrt_info=None, covariance=False):
         """closeLoop: (rvec, tvec) is the world -> camera pose of keyframe cur_id found by PnP against loop_id's stored
         landmarks.  Solves loop_problem() on the device; on a usable termination the poses are replaced and every landmark
         moves rigidly with its anchor keyframe, X' = T_a' T_a^-1 X.  -> the summary and keyframes, poses_before, poses,
         landmark_ids, landmarks (FAILURE: everything as it was).  More than 1024 keyframes (16384 with
         pose_graph_solver = "sparse") is MslamHipError(E_CAPACITY), a keyframe the backend does not hold
-        MslamHipError(E_INVALID), both raised before the context is touched."""
+        MslamHipError(E_INVALID), both raised before the context is touched.
+        covariance = True (an extension): after a usable termination one Context.pose_graph_covariance call on the same
+        problem at the solved poses, under the same loss; the result gains covariance = dict(cur, loop, cross): the 6 x 6
+        marginals of cur_id and loop_id on the tangent (delta, dp) and cross = E[d_cur d_loop^T] (the loop edge joins the
+        two, so the block is inside the envelope; a constant keyframe gives zeros).  None when the problem is rank
+        deficient (E_NO_MODEL: no constant keyframe in the graph's component).  With False nothing new runs."""
         cap = POSE_GRAPH_MAX_KEYFRAMES_SPARSE if self.pose_graph_solver == PG_SOLVER_SPARSE else POSE_GRAPH_MAX_KEYFRAMES
         if len(self.poses) > cap:
             raise MslamHipError(E_CAPACITY, "close_loop: %d keyframes, at most %d per solve" % (len(self.poses), cap))
@@ -1847,6 +1875,15 @@ class HipBackend:
             if self.pose_graph_loss is not None:
                 chi2, weight = self.ctx.pose_graph_edge_weights(res["poses"], ea, eb, meas, info)
                 res.update(edge_chi2=chi2, edge_weight=weight)
+            if covariance and res["termination"] != 2:
+                kc, kl = ids.index(int(cur_id)), ids.index(int(loop_id))
+                try:
+                    cv = self.ctx.pose_graph_covariance(res["poses"], ea, eb, meas, info, fixed, poses_of=[kc, kl], pairs=[(kc, kl)])
+                    res.update(covariance=dict(cur=cv["cov"][0], loop=cv["cov"][1], cross=cv["cross"][0]))
+                except MslamHipError as e:
+                    if e.code != E_NO_MODEL:
+                        raise
+                    res.update(covariance=None)
         finally:
             if self.pose_graph_loss is not None:
                 self.ctx.set_pose_graph_loss(*loss_before)
@@ -1935,6 +1972,10 @@ class HipKeyframeTracker:
     (loop_global_ba) has its own setting, whatever pose_graph_solver is: ba_global_solver = "dense" (the default: a cap of
     1024 keyframes, the behaviour it had) or "sparse" (HipBackend(global_linear_solver="sparse"); Context.set_ba_global_solver:
     up to 16384 keyframes, the reduced camera system on its block envelope).
+    loop_covariance = True (needs loop_closure, else MslamHipError(E_INVALID); an extension): close_loop runs with
+    covariance = True and the attempt's dict in self.loop_results gains covariance = dict(cur, loop, cross), the marginal
+    covariances of the two ends of the loop edge at the solved poses (HipBackend.close_loop; Context.pose_graph_covariance).
+    With False (the default) nothing new runs and the records are what they were.
     pose_graph_loss = ("huber", a) or ("cauchy", a) (needs loop_closure, else MslamHipError(E_INVALID); an extension) goes to
     the backend too: close_loop solves with that loss on every edge and its dict in self.loop_results gains edge_chi2 and
     edge_weight (HipBackend; Context.set_pose_graph_loss; the context is left with the setting it had).  None (the default)
@@ -2036,8 +2077,11 @@ class HipKeyframeTracker:
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
-                 pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None):
+                 pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False):
         self.ctx = ctx
+        if loop_covariance and not loop_closure:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_covariance needs loop_closure (close_loop computes it)")
+        self.loop_covariance = bool(loop_covariance)
         if union_descriptor is not None:
             if local_map_depth is None:
                 raise MslamHipError(E_INVALID, "HipKeyframeTracker: union_descriptor needs local_map_depth (the union it applies to)")
@@ -2364,7 +2408,11 @@ class HipKeyframeTracker:
         if reloc["best"] < 0:
             return None
         loop_id, win = cands[reloc["best"]], reloc["candidates"][reloc["best"]]
-        res = self.backend.close_loop(new_id, loop_id, win["rvec"], win["tvec"], self.graph)
+        if self.loop_covariance:
+            res = self.backend.close_loop(new_id, loop_id, win["rvec"], win["tvec"], self.graph, covariance=True)
+            attempt.update(covariance=res.get("covariance"))
+        else:
+            res = self.backend.close_loop(new_id, loop_id, win["rvec"], win["tvec"], self.graph)
         attempt.update(loop=loop_id, rvec=win["rvec"], tvec=win["tvec"], result=res)
         if res["termination"] == 2:
             return None

@@ -27,6 +27,7 @@
 //                    bits), then y_k -= L_ik^T x_i for the row's columns k, a thread per entry;  barrier.
 // No kernel waits on another workgroup; every loop is bounded by a count the host computed (n, the lists' lengths, the
 // rows' widths).  All arithmetic is f64.  The diagonal's reciprocal is taken once per column and multiplied with.
+// mslam_hip_pose_graph_covariance stops after the factor (pg_sparse_factor) and goes on in k_pg_cov.hip.
 #include "pg_sparse.hpp"
 
 #include <algorithm>
@@ -213,17 +214,20 @@ __global__ __launch_bounds__(256) void k_pgs_backsolve(PgsArgs a)
     }
 }
 
-void pg_sparse_solve(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble)
+void pg_sparse_factor(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble)
 {
     {
         StageScope tk(c, "solver_schur");
         hipLaunchKernelGGL(k_pgs_clear, dim3((unsigned)(((size_t)a.blocks * 36 + 255) / 256)), dim3(256), 0, s, a);
         assemble();
     }
-    {
-        StageScope tk(c, "solver_factor");
-        hipLaunchKernelGGL(k_pgs_factor, dim3(1), dim3(256), 0, s, a);
-    }
+    StageScope tk(c, "solver_factor");
+    hipLaunchKernelGGL(k_pgs_factor, dim3(1), dim3(256), 0, s, a);
+}
+
+void pg_sparse_solve(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble)
+{
+    pg_sparse_factor(c, a, s, assemble);
     StageScope tk(c, "solver_subst");
     hipLaunchKernelGGL(k_pgs_backsolve, dim3(1), dim3(256), 0, s, a);
 }

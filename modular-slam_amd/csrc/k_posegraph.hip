@@ -46,6 +46,9 @@
 // where k_pg_edges and k_pg_eval stand: the stored r_e and Jacobians are multiplied by sqrt(rho'(|r_e|^2)), Ceres's corrector on
 // the rows, the cost is 1/2 sum rho, and every other kernel of the list runs unchanged on the corrected blocks.
 // k_pg_edge_weights (mslam_hip_pose_graph_edge_weights) reports |r_e|^2 and rho' per edge at given poses.
+// mslam_hip_pose_graph_covariance runs k_pg_edges (or _loss) and k_pg_poses under a control block at its start,
+// k_pg_assemble_env_undamped (pg_assemble_pair without the damping term, a right-hand side of zeros), the factor of
+// k_pg_sparse.hip and the two kernels of k_pg_cov.hip: blocks of (J^T J)^-1 inside the envelope.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
 #include "reduced_system.hpp"
@@ -278,8 +281,9 @@ __global__ __launch_bounds__(64) void k_pg_check(PgArgs a)
 
 // One body for both layouts: the pair's lookup, the diagonal with its damping, the sum over the pair's edge list and the
 // scaling; SysView (reduced_system.hpp) knows where the entries go.  ci is the block in index order with PaddedLower, the
-// position in the chosen order with Envelope.
-template <SysLayout kLayout>
+// position in the chosen order with Envelope.  kDamped = false (mslam_hip_pose_graph_covariance): the scaled J^T J itself and a
+// right-hand side of zeros.
+template <SysLayout kLayout, bool kDamped = true>
 __device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
 {
     const TrCtrl* ct = a.ctrl;
@@ -295,12 +299,18 @@ __device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
         {
             const int r = lane / 6, c = lane % 6;
             const double u = a.sc[(size_t)k1 * 6 + r] * a.U[(size_t)k1 * 21 + (r <= c ? tri6(r, c) : tri6(c, r))] * a.sc[(size_t)k1 * 6 + c];
-            sys.store(b1, b1, true, r, c, r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u);
+            if constexpr(kDamped)
+                sys.store(b1, b1, true, r, c, r == c ? u + fmin(fmax(u, kTrMinDiagonal), kTrMaxDiagonal) / ct->radius : u);
+            else
+                sys.store(b1, b1, true, r, c, u);
         }
         else if(lane < 42)
         {
             const int r = lane - 36;
-            sys.store_rhs(b1, r, a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r]);
+            if constexpr(kDamped)
+                sys.store_rhs(b1, r, a.sc[(size_t)k1 * 6 + r] * a.gc[(size_t)k1 * 6 + r]);
+            else
+                sys.store_rhs(b1, r, 0.0);
         }
         return;
     }
@@ -326,6 +336,7 @@ __device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
 
 __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a) { pg_assemble_pair<SysLayout::PaddedLower>(a); }
 __global__ __launch_bounds__(64) void k_pg_assemble_env(PgArgs a) { pg_assemble_pair<SysLayout::Envelope>(a); }
+__global__ __launch_bounds__(64) void k_pg_assemble_env_undamped(PgArgs a) { pg_assemble_pair<SysLayout::Envelope, false>(a); }
 
 // delta = step * scaling with step = -y; Plus.  Poses outside the problem are copied.
 __global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
@@ -854,5 +865,182 @@ extern "C" int mslam_hip_pose_graph_edge_weights(mslam_hip_ctx* c, const double*
         std::memcpy(chi2, out.data(), (size_t)E * 8);
     if(weight)
         std::memcpy(weight, out.data() + E, (size_t)E * 8);
+    return MSLAM_HIP_OK;
+}
+
+// ---- mslam_hip_pose_graph_covariance ---------------------------------------------------------------------------------------
+
+// The structural rank test: a connected component of the node graph (the free poses that have an edge, joined by the edges
+// between them) none of whose members has an edge to a constant pose has a free gauge.  -> the least pose of such a
+// component, or -1.
+static int pg_free_gauge(const std::vector<int32_t>& ci, const int32_t* edge_a, const int32_t* edge_b, int E)
+{
+    const int K = (int)ci.size();
+    std::vector<int32_t> root((size_t)K);
+    for(int k = 0; k < K; ++k)
+        root[(size_t)k] = k;
+    auto find = [&](int k) {
+        while(root[(size_t)k] != k)
+            k = root[(size_t)k] = root[(size_t)root[(size_t)k]];
+        return k;
+    };
+    for(int e = 0; e < E; ++e)
+        if(ci[(size_t)edge_a[e]] >= 0 && ci[(size_t)edge_b[e]] >= 0)
+        {
+            const int ra = find(edge_a[e]), rb = find(edge_b[e]);
+            root[(size_t)std::max(ra, rb)] = std::min(ra, rb); // the root is the component's least pose
+        }
+    std::vector<uint8_t> held((size_t)K, 0);
+    for(int e = 0; e < E; ++e)
+    {
+        const bool fa = ci[(size_t)edge_a[e]] >= 0, fb = ci[(size_t)edge_b[e]] >= 0;
+        if(fa != fb) // a pose of an edge has an edge: the other end is constant
+            held[(size_t)find(fa ? edge_a[e] : edge_b[e])] = 1;
+    }
+    for(int k = 0; k < K; ++k)
+        if(ci[(size_t)k] >= 0 && find(k) == k && !held[(size_t)k])
+            return k;
+    return -1;
+}
+
+extern "C" int mslam_hip_pose_graph_covariance(mslam_hip_ctx* c, const double* poses, const uint8_t* fixed, int K, const int32_t* edge_a,
+                                               const int32_t* edge_b, const double* edge_meas, const double* sqrt_info, int E,
+                                               const int32_t* pose_idx, int P, double* cov, const int32_t* pair_a,
+                                               const int32_t* pair_b, int Q, double* cross)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    LinearSolve ls(true); // the envelope at every K; mslam_hip_set_pose_graph_solver is not read
+    if(const int rc = pg_validate(c, ls.k_max(), poses, K, edge_a, edge_b, edge_meas, sqrt_info, E, 0); rc != MSLAM_HIP_OK)
+        return rc;
+    constexpr int kMaxBlocks = 65536;
+    if(P < 0 || P > kMaxBlocks || Q < 0 || Q > kMaxBlocks || (P > 0 && (!pose_idx || !cov)) || (Q > 0 && (!pair_a || !pair_b || !cross)))
+        return fail(c, MSLAM_HIP_E_INVALID, "pose_graph_covariance: bad argument (P and Q in 0..65536, pointers)");
+    PgRows rw;
+    pg_incidences(fixed, K, edge_a, edge_b, E, rw);
+    // the requests: a constant pose gives zeros, a free pose must be in the problem
+    auto constant = [&](int k) { return fixed && fixed[k]; };
+    auto in_problem = [&](int k, const char* what, int at) {
+        if(k < 0 || k >= K)
+            return fail(c, MSLAM_HIP_E_INVALID, std::string("pose_graph_covariance: ") + what + " " + std::to_string(at) + " names a pose out of range");
+        if(!constant(k) && rw.ci[(size_t)k] < 0)
+            return fail(c, MSLAM_HIP_E_INVALID, std::string("pose_graph_covariance: ") + what + " " + std::to_string(at) + " names pose " +
+                                                    std::to_string(k) + ", which is free and has no edge");
+        return (int)MSLAM_HIP_OK;
+    };
+    for(int p = 0; p < P; ++p)
+        if(const int rc = in_problem(pose_idx[p], "pose_idx", p); rc != MSLAM_HIP_OK)
+            return rc;
+    pg_pairs(K, edge_a, edge_b, E, rw);
+    for(int q = 0; q < Q; ++q)
+    {
+        if(const int rc = in_problem(pair_a[q], "pair_a", q); rc != MSLAM_HIP_OK)
+            return rc;
+        if(const int rc = in_problem(pair_b[q], "pair_b", q); rc != MSLAM_HIP_OK)
+            return rc;
+        if(pair_a[q] == pair_b[q])
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph_covariance: pair " + std::to_string(q) + " names one pose twice (its block is cov's)");
+        if(constant(pair_a[q]) || constant(pair_b[q]))
+            continue;
+        // rw.pairs is sorted by (k1, k2): is the pair among the pairs an edge joins?
+        const int32_t lo = std::min(pair_a[q], pair_b[q]), hi = std::max(pair_a[q], pair_b[q]);
+        size_t l = 0, r = rw.pairs.size() / 2;
+        while(l < r)
+        {
+            const size_t mid = (l + r) / 2;
+            if(std::make_pair(rw.pairs[mid * 2], rw.pairs[mid * 2 + 1]) < std::make_pair(lo, hi))
+                l = mid + 1;
+            else
+                r = mid;
+        }
+        if(l == rw.pairs.size() / 2 || rw.pairs[l * 2] != lo || rw.pairs[l * 2 + 1] != hi)
+            return fail(c, MSLAM_HIP_E_INVALID, "pose_graph_covariance: no edge joins the poses of pair " + std::to_string(q) +
+                                                    ": the block may lie outside the envelope");
+    }
+    if(const int k = pg_free_gauge(rw.ci, edge_a, edge_b, E); k >= 0)
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "pose_graph_covariance: the component of pose " + std::to_string(k) +
+                                                 " has no edge to a constant pose: its gauge is free and J^T J is singular");
+    const int n_req = P + Q;
+    if(rw.n_free == 0)
+    {
+        // every pose of the problem is constant: zeros
+        if(P > 0)
+            std::memset(cov, 0, (size_t)P * 288);
+        if(Q > 0)
+            std::memset(cross, 0, (size_t)Q * 288);
+        return MSLAM_HIP_OK;
+    }
+    pg_symbolic(fixed, K, edge_a, edge_b, E, ls.sy);
+    if(const int rc = ls.index(c, "pose_graph_covariance", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+        return rc;
+    int longest = 0; // the longest column list: the rows of k_pgs_selinv's scratch
+    for(int j = 0; j < ls.n_free; ++j)
+        longest = std::max(longest, ls.sy.col_ptr[(size_t)j + 1] - ls.sy.col_ptr[(size_t)j]);
+    std::vector<int32_t> req((size_t)n_req * 2);
+    for(int p = 0; p < P; ++p)
+        req[(size_t)p * 2] = req[(size_t)p * 2 + 1] = pose_idx[p];
+    for(int q = 0; q < Q; ++q)
+        req[(size_t)(P + q) * 2] = pair_a[q], req[(size_t)(P + q) * 2 + 1] = pair_b[q];
+
+    PgArgs a{};
+    a.K = K, a.E = E, a.n = ls.n, a.n_pad = ls.n_pad, a.ld = ls.ld;
+    a.n_pairs = (int)(rw.pairs.size() / 2), a.n_blocks = (E + 255) / 256;
+    // mslam_hip_pose_graph's block: the control block of a solve at its start (done = 0, need_jac, first), so k_pg_edges and
+    // k_pg_poses run as in the first iteration and take the Jacobi scaling at the given poses
+    TrStaging st(0);
+    const size_t n_info = sqrt_info ? (size_t)E * 288 : 0;
+    const size_t o_pose = st.put(poses, (size_t)K * 56), o_meas = st.put(edge_meas, (size_t)E * 56), o_info = st.put(sqrt_info, n_info);
+    const size_t o_ea = st.put(edge_a, (size_t)E * 4), o_eb = st.put(edge_b, (size_t)E * 4), o_iptr = st.put(rw.inc_ptr.data(), ((size_t)K + 1) * 4);
+    const size_t o_inc = st.put(rw.inc.data(), (size_t)E * 8), o_ci = st.put(rw.ci.data(), (size_t)K * 4);
+    const size_t o_pairs = st.put(rw.pairs.data(), rw.pairs.size() * 4), o_pptr = st.put(rw.pair_ptr.data(), rw.pair_ptr.size() * 4);
+    const size_t o_pedge = st.put(rw.pair_edge.data(), rw.pair_edge.size() * 4), o_req = st.put(req.data(), req.size() * 4);
+    ls.put(st);
+    const size_t o_r = st.carve((size_t)E * 48), o_J = st.carve((size_t)E * 576);
+    const size_t o_U = st.carve((size_t)K * 168), o_gc = st.carve((size_t)K * 48), o_sc = st.carve((size_t)K * 48), o_yc = st.carve((size_t)a.n * 8);
+    const size_t o_scratch = st.carve((size_t)longest * 288), o_out = st.carve((size_t)n_req * 288 + 8);
+    ls.carve(st);
+    MSLAM_CHK(c, hipSetDevice(c->p.device));
+    MSLAM_CHK(c, grow(c->d_pg, st.size, c->stream));
+    MSLAM_CHK(c, ls.grow_S(c));
+    uint8_t* d = c->d_pg;
+    hipStream_t s = c->stream;
+    MSLAM_CHK(c, st.upload(d, s));
+    auto dbl = [&](size_t at) { return reinterpret_cast<double*>(d + at); };
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t*>(d + at); };
+    a.ea = i32(o_ea), a.eb = i32(o_eb), a.meas = dbl(o_meas), a.info = sqrt_info ? dbl(o_info) : nullptr;
+    a.inc_ptr = i32(o_iptr), a.inc = i32(o_inc), a.ci = i32(o_ci);
+    a.pairs = i32(o_pairs), a.pair_ptr = i32(o_pptr), a.pair_edge = i32(o_pedge);
+    a.pose = dbl(o_pose), a.r = dbl(o_r), a.J = dbl(o_J);
+    a.U = dbl(o_U), a.gc = dbl(o_gc), a.sc = dbl(o_sc), a.S = c->d_ba_S.get(), a.yc = dbl(o_yc);
+    a.ctrl = reinterpret_cast<TrCtrl*>(d);
+    ls.bind(c, d, a.yc);
+    a.env_off = ls.env.row_off, a.env_first = ls.env.first, a.rhs = ls.env.rhs;
+    const TrLoss tl{c->pg_loss_kind, c->pg_loss_scale};
+    const dim3 g_edge((unsigned)a.n_blocks), g_pair((unsigned)a.n_pairs);
+    {
+        StageScope tk(c, "cov_blocks");
+        if(tl.kind != MSLAM_HIP_BA_LOSS_NONE)
+            hipLaunchKernelGGL(k_pg_edges_loss, g_edge, dim3(256), 0, s, a, tl);
+        else
+            hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
+    }
+    pg_sparse_factor(c, ls.env, s, [&] { hipLaunchKernelGGL(k_pg_assemble_env_undamped, g_pair, dim3(64), 0, s, a); });
+    PgCovArgs g{};
+    g.n = a.n, g.n_pad = a.n_pad, g.ld = a.ld, g.S = a.S, g.rhs = a.rhs, g.env_off = a.env_off, g.env_first = a.env_first;
+    g.ci = a.ci, g.sc = a.sc, g.req = i32(o_req), g.n_req = n_req, g.out = dbl(o_out), g.ctrl = a.ctrl;
+    pg_cov_enqueue(c, ls.env, g, dbl(o_scratch), s);
+    MSLAM_CHK(c, hipGetLastError());
+    // one download: the blocks, then the factor's verdict
+    std::vector<double> out((size_t)n_req * 36 + 1);
+    MSLAM_CHK(c, hipMemcpyAsync(out.data(), g.out, out.size() * 8, hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(out.back() != 0.0)
+        return fail(c, MSLAM_HIP_E_NO_MODEL, "pose_graph_covariance: a pivot of the factor of J^T J is not > 0 or not finite: the "
+                                             "problem is rank deficient at these poses");
+    if(P > 0)
+        std::memcpy(cov, out.data(), (size_t)P * 288);
+    if(Q > 0)
+        std::memcpy(cross, out.data() + (size_t)P * 36, (size_t)Q * 288);
     return MSLAM_HIP_OK;
 }

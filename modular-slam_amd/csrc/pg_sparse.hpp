@@ -52,4 +52,27 @@ struct PgsArgs
 // timed under ba_blocked_solve's names: solver_schur, solver_factor, solver_subst.
 void pg_sparse_solve(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble);
 
+// ---- k_pg_cov.hip: the blocks of the inverse inside the envelope (mslam_hip_pose_graph_covariance) ----------
+
+// the clear, `assemble` and the factor of pg_sparse_solve without the back-substitution: the envelope then holds L
+void pg_sparse_factor(mslam_hip_ctx* c, const PgsArgs& a, hipStream_t s, const std::function<void()>& assemble);
+
+// what k_pg_cov_gather reads; the members SysView<SysLayout::Envelope> takes have PgArgs's names
+struct PgCovArgs
+{
+    int n, n_pad, ld; // SysView's; only the envelope's members are read
+    double *S, *rhs;
+    const int32_t *env_off, *env_first;
+    const int32_t* ci;  // [K] position in the chosen order, -1: constant (the host rejects a free pose without an edge)
+    const double* sc;   // [K] x 6 the Jacobi scaling of the factor
+    const int32_t* req; // [n_req][2] poses (a, b) per output block; a == b for a marginal
+    int n_req;
+    double* out;        // [n_req] x 36 row-major, then one word: solve_bad as 0.0 / 1.0
+    const TrCtrl* ctrl;
+};
+
+// After the factor, enqueued on s: k_pgs_selinv (one workgroup; the envelope then holds the blocks of the inverse; scratch
+// takes 36 doubles per row of the longest column list), then k_pg_cov_gather.  Stages cov_selinv, cov_gather.
+void pg_cov_enqueue(mslam_hip_ctx* c, const PgsArgs& env, const PgCovArgs& cov, double* scratch, hipStream_t s);
+
 } // namespace mslam

@@ -55,6 +55,10 @@
 //                                    the same with IRobustPoseGraphBackend::setPoseGraphLoss(kind, a) first (a in the unit of the
 //                                    weighted residual, finite and > 0), after --sparse when both are given: the costs of the
 //                                    summary are then 1/2 sum rho
+//        mslam_harness <plugin.so> --pose-graph <scene> --covariance
+//                                    no solve: IPoseGraphCovariance::poseGraphCovariance of the same object at the scene's
+//                                    states, for every keyframe that is not constant and has an edge: "covariance blocks N",
+//                                    then per keyframe "cov <index>" and its 36 entries (row-major, %.17g)
 //        mslam_harness <plugin.so> --pnp-mse <scene> --loss huber:<a> | cauchy:<a>
 //                                    hipMinMseTrackerFactory with IRobustPnp::setLoss(kind, a) first (a in pixels)
 //        mslam_harness <plugin.so> --fuse <scene>
@@ -306,14 +310,15 @@ int main(int argc, char** argv)
                 std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
             return 0;
         }
-        // --pose-graph <scene>, then nothing, --sparse, --solver <kind>, --loss <spec> or --sparse --loss <spec>
+        // --pose-graph <scene>, then nothing, --sparse, --solver <kind>, --loss <spec>, --sparse --loss <spec> or --covariance
+        const bool pgCovariance = argc == 5 && std::strcmp(argv[4], "--covariance") == 0;
         const bool pgLossOnly = argc == 6 && std::strcmp(argv[4], "--loss") == 0;
         const bool pgSparseLoss = argc == 7 && std::strcmp(argv[4], "--sparse") == 0 && std::strcmp(argv[5], "--loss") == 0;
         if((argc == 4 || (argc == 5 && std::strcmp(argv[4], "--sparse") == 0) || (argc == 6 && std::strcmp(argv[4], "--solver") == 0) ||
-            pgLossOnly || pgSparseLoss) &&
+            pgLossOnly || pgSparseLoss || pgCovariance) &&
            std::strcmp(argv[2], "--pose-graph") == 0)
         {
-            const bool setSolver = argc > 4 && !pgLossOnly;
+            const bool setSolver = argc > 4 && !pgLossOnly && !pgCovariance;
             int solverKind = 1;
             int lossKind = 0;
             double lossScale = 0.0;
@@ -417,6 +422,33 @@ int main(int argc, char** argv)
                     return 6;
                 }
                 robust->setPoseGraphLoss(lossKind, lossScale);
+            }
+            if(pgCovariance)
+            {
+                auto* covBackend = dynamic_cast<mslam::IPoseGraphCovariance*>(backend.get());
+                if(!covBackend)
+                {
+                    std::fprintf(stderr, "the plugin does not offer poseGraphCovariance\n");
+                    return 6;
+                }
+                std::vector<bool> hasEdge(K, false);
+                for(std::size_t e = 0; e < E; ++e)
+                    hasEdge[ea[e]] = hasEdge[eb[e]] = true;
+                std::vector<std::shared_ptr<Kf>> of;
+                std::vector<std::size_t> ofIndex;
+                for(std::size_t k = 0; k < K; ++k)
+                    if(hasEdge[k] && keyframes[k]->id != 1)
+                        of.push_back(keyframes[k]), ofIndex.push_back(k);
+                const mslam::PoseGraphCovariance cov = covBackend->poseGraphCovariance(keyframes, edges, of, {});
+                std::printf("covariance blocks %zu\n", of.size());
+                for(std::size_t p = 0; p < of.size(); ++p)
+                {
+                    std::printf("cov %zu", ofIndex[p]);
+                    for(int j = 0; j < 36; ++j)
+                        std::printf(" %.17g", cov.blocks[36 * p + j]);
+                    std::printf("\n");
+                }
+                return 0;
             }
             const mslam::BackendOutput out = loopBackend->closeLoop(keyframes, edges, head[3]);
             std::printf("pose_graph termination %d iterations %d initial %.17g final %.17g keyframes %zu edges %zu\n", out.termination,

@@ -14,6 +14,7 @@
 //   HipBundleAdjustBackend : ILoopClosingBackend : IGlobalBackend : IBackend      CeresBackend's bundle adjustment, local and global, and closeLoop (hipBundleAdjustBackendFactory)
 //                          : IRobustBackend                                       a Huber or Cauchy loss for both bundle adjustments (an extension)
 //                          : ISparsePoseGraphBackend                              closeLoop's linear solver: dense or the block-envelope factor (an extension)
+//                          : IPoseGraphCovariance                                 marginal covariances of closeLoop's problem (an extension)
 //                          : ISparseGlobalBackend                                 globalBundleAdjustment's linear solver, the same choice (an extension)
 //                          : IRobustPoseGraphBackend                              a Huber or Cauchy loss on closeLoop's edges (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
@@ -1025,11 +1026,44 @@ class HipMinMseTracker : public ISlam3dPnp, public IRobustPnp
 // an extension) keeps a loss for every later solve: it is set on the adapter's own context before each one.  setGlobalSolver
 // (ISparseGlobalBackend, an extension) keeps the linear solver of globalBundleAdjustment, set the same way: with kind 1 up to
 // 16384 keyframes.  setPoseGraphLoss (IRobustPoseGraphBackend, an extension) keeps a loss for the edges of closeLoop, set the
-// same way.
+// same way.  poseGraphCovariance (IPoseGraphCovariance, an extension) hands closeLoop's arrays to
+// mslam_hip_pose_graph_covariance and writes nothing back.
 class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend,
-                               public IRobustPoseGraphBackend
+                               public IRobustPoseGraphBackend, public IPoseGraphCovariance
 {
   public:
+    // IPoseGraphCovariance (an extension): closeLoop's arrays at the keyframes' present states to
+    // mslam_hip_pose_graph_covariance, under closeLoop's loss; nothing is written back
+    PoseGraphCovariance poseGraphCovariance(const std::vector<KeyframePtr>& keyframes, const std::vector<PoseGraphEdge>& edges,
+                                            const std::vector<KeyframePtr>& of,
+                                            const std::vector<std::pair<KeyframePtr, KeyframePtr>>& pairs) override
+    {
+        PoseGraphArrays pg = poseGraphArrays(keyframes, edges, "poseGraphCovariance");
+        auto index = [&](const KeyframePtr& kf) {
+            const auto at = pg.kfIndex.find(kf.get());
+            if(at == pg.kfIndex.end())
+                throw std::runtime_error("poseGraphCovariance: a requested keyframe is not listed");
+            return static_cast<std::int32_t>(at->second);
+        };
+        std::vector<std::int32_t> idx, pairA, pairB;
+        for(const auto& kf : of)
+            idx.push_back(index(kf));
+        for(const auto& pr : pairs)
+            pairA.push_back(index(pr.first)), pairB.push_back(index(pr.second));
+        PoseGraphCovariance out;
+        out.blocks.assign(36 * idx.size(), 0.0), out.cross.assign(36 * pairA.size(), 0.0);
+        ctx.ensure(0, 0);
+        if(const int rs = mslam_hip_set_pose_graph_loss(ctx.h, pgLossKind, pgLossScale); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_pose_graph_loss", rs);
+        const int rc = mslam_hip_pose_graph_covariance(ctx.h, pg.poses.data(), pg.fixed.data(), static_cast<int>(keyframes.size()),
+                                                       pg.edgeA.data(), pg.edgeB.data(), pg.meas.data(), pg.anyInfo ? pg.info.data() : nullptr,
+                                                       static_cast<int>(edges.size()), idx.data(), static_cast<int>(idx.size()),
+                                                       out.blocks.data(), pairA.data(), pairB.data(), static_cast<int>(pairA.size()),
+                                                       out.cross.data());
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_pose_graph_covariance", rc);
+        return out;
+    }
     void setPoseGraphLoss(int kind, double scale) override
     {
         if(kind < MSLAM_HIP_BA_LOSS_NONE || kind > MSLAM_HIP_BA_LOSS_CAUCHY ||
@@ -1067,37 +1101,11 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     BackendOutput closeLoop(const std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>>& keyframes,
                             const std::vector<PoseGraphEdge>& edges, int maxIterations) override
     {
-        std::map<const void*, int> kfIndex;
-        for(std::size_t k = 0; k < keyframes.size(); ++k)
-            kfIndex.emplace(keyframes[k].get(), static_cast<int>(k));
-        std::vector<double> poses(7 * keyframes.size()), meas(7 * edges.size()), info;
-        std::vector<std::uint8_t> fixed(keyframes.size());
-        std::vector<std::int32_t> edgeA, edgeB;
-        auto put = [](const slam3d::SensorState& st, double* v) {
-            v[0] = st.orientation.x(), v[1] = st.orientation.y(), v[2] = st.orientation.z(), v[3] = st.orientation.w();
-            v[4] = st.position.x(), v[5] = st.position.y(), v[6] = st.position.z();
-        };
-        for(std::size_t k = 0; k < keyframes.size(); ++k)
-        {
-            put(keyframes[k]->state, &poses[7 * k]);
-            fixed[k] = keyframes[k]->id == 1 ? 1 : 0;
-        }
-        bool anyInfo = false;
-        for(const auto& e : edges)
-            anyInfo = anyInfo || !e.sqrtInformation.empty();
-        if(anyInfo)
-            info.assign(36 * edges.size(), 0.0);
-        for(std::size_t e = 0; e < edges.size(); ++e)
-        {
-            const auto a = kfIndex.find(edges[e].a.get()), b = kfIndex.find(edges[e].b.get());
-            if(a == kfIndex.end() || b == kfIndex.end() || (!edges[e].sqrtInformation.empty() && edges[e].sqrtInformation.size() != 36))
-                throw std::runtime_error("closeLoop: an edge names a keyframe that is not listed, or its sqrtInformation is not 6 x 6");
-            edgeA.push_back(a->second), edgeB.push_back(b->second);
-            put(edges[e].measurement, &meas[7 * e]);
-            if(anyInfo)
-                for(int j = 0; j < 36; ++j)
-                    info[36 * e + j] = edges[e].sqrtInformation.empty() ? (j % 7 == 0 ? 1.0 : 0.0) : edges[e].sqrtInformation[j];
-        }
+        PoseGraphArrays pg = poseGraphArrays(keyframes, edges, "closeLoop");
+        std::vector<double>&poses = pg.poses, &meas = pg.meas, &info = pg.info;
+        std::vector<std::uint8_t>& fixed = pg.fixed;
+        std::vector<std::int32_t>&edgeA = pg.edgeA, &edgeB = pg.edgeB;
+        const bool anyInfo = pg.anyInfo;
         ctx.ensure(0, 0);
         if(const int rs = mslam_hip_set_pose_graph_solver(ctx.h, poseGraphSolver); rs != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_set_pose_graph_solver", rs);
@@ -1124,6 +1132,53 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     }
 
   private:
+    // closeLoop's problem as mslam_hip_pose_graph's arrays: keyframe id 1 constant, sqrt_info only when an edge carries one
+    struct PoseGraphArrays
+    {
+        std::map<const void*, int> kfIndex;
+        std::vector<double> poses, meas, info;
+        std::vector<std::uint8_t> fixed;
+        std::vector<std::int32_t> edgeA, edgeB;
+        bool anyInfo = false;
+    };
+    static PoseGraphArrays poseGraphArrays(const std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>>& keyframes,
+                                           const std::vector<PoseGraphEdge>& edges, const char* who)
+    {
+        PoseGraphArrays pg;
+        std::map<const void*, int>& kfIndex = pg.kfIndex;
+        for(std::size_t k = 0; k < keyframes.size(); ++k)
+            kfIndex.emplace(keyframes[k].get(), static_cast<int>(k));
+        pg.poses.assign(7 * keyframes.size(), 0.0), pg.meas.assign(7 * edges.size(), 0.0), pg.fixed.assign(keyframes.size(), 0);
+        std::vector<double>&poses = pg.poses, &meas = pg.meas, &info = pg.info;
+        std::vector<std::uint8_t>& fixed = pg.fixed;
+        std::vector<std::int32_t>&edgeA = pg.edgeA, &edgeB = pg.edgeB;
+        bool& anyInfo = pg.anyInfo;
+        auto put = [](const slam3d::SensorState& st, double* v) {
+            v[0] = st.orientation.x(), v[1] = st.orientation.y(), v[2] = st.orientation.z(), v[3] = st.orientation.w();
+            v[4] = st.position.x(), v[5] = st.position.y(), v[6] = st.position.z();
+        };
+        for(std::size_t k = 0; k < keyframes.size(); ++k)
+        {
+            put(keyframes[k]->state, &poses[7 * k]);
+            fixed[k] = keyframes[k]->id == 1 ? 1 : 0;
+        }
+        for(const auto& e : edges)
+            anyInfo = anyInfo || !e.sqrtInformation.empty();
+        if(anyInfo)
+            info.assign(36 * edges.size(), 0.0);
+        for(std::size_t e = 0; e < edges.size(); ++e)
+        {
+            const auto a = kfIndex.find(edges[e].a.get()), b = kfIndex.find(edges[e].b.get());
+            if(a == kfIndex.end() || b == kfIndex.end() || (!edges[e].sqrtInformation.empty() && edges[e].sqrtInformation.size() != 36))
+                throw std::runtime_error(std::string(who) + ": an edge names a keyframe that is not listed, or its sqrtInformation is not 6 x 6");
+            edgeA.push_back(a->second), edgeB.push_back(b->second);
+            put(edges[e].measurement, &meas[7 * e]);
+            if(anyInfo)
+                for(int j = 0; j < 36; ++j)
+                    info[36 * e + j] = edges[e].sqrtInformation.empty() ? (j % 7 == 0 ? 1.0 : 0.0) : edges[e].sqrtInformation[j];
+        }
+        return pg;
+    }
     BackendOutput solve(const std::vector<BackendObservation>& observations, int maxIterations, bool global)
     {
         std::vector<std::shared_ptr<Keyframe<slam3d::SensorState>>> keyframes;

@@ -300,6 +300,28 @@ class IRobustPoseGraphBackend
     virtual void setPoseGraphLoss(int kind, double scale) = 0;
     virtual ~IRobustPoseGraphBackend() = default;
 };
+// extension: how certain closeLoop's answer is (mslam_hip_pose_graph_covariance; ceres::Covariance's part next to Solve).  The
+// problem is closeLoop's, at the states the keyframes hold now: blocks of (J^T J)^-1 over the keyframes that are not constant
+// (id 1 is) and have an edge, on the tangent (delta, dp) per keyframe, delta half a rotation vector in the world frame; under
+// the loss of IRobustPoseGraphBackend::setPoseGraphLoss; always on the block envelope, whatever setPoseGraphSolver says.
+// `of` lists keyframes, `pairs` pairs of keyframes an edge joins (or one of which is constant).  -> blocks: 36 doubles
+// (6 x 6 row-major) per keyframe of `of`; cross: 36 per pair, E[d_first d_second^T].  The constant keyframe gives zeros.  Nothing
+// is changed.  A keyframe that is not listed, a free one without an edge, a pair of one keyframe, a pair no edge joins, a
+// rank-deficient problem or an envelope above the bound throw std::runtime_error with the library's message.  An interface of
+// its own, reached with dynamic_cast like ISparsePoseGraphBackend: ILoopClosingBackend gains no virtual.
+struct PoseGraphCovariance
+{
+    std::vector<double> blocks, cross;
+};
+class IPoseGraphCovariance
+{
+  public:
+    using KeyframePtr = std::shared_ptr<Keyframe<slam3d::SensorState>>;
+    virtual PoseGraphCovariance poseGraphCovariance(const std::vector<KeyframePtr>& keyframes, const std::vector<PoseGraphEdge>& edges,
+                                                    const std::vector<KeyframePtr>& of,
+                                                    const std::vector<std::pair<KeyframePtr, KeyframePtr>>& pairs) = 0;
+    virtual ~IPoseGraphCovariance() = default;
+};
 // extension (the reference's MinMseTracker gives its residual blocks no loss, so every mismatch pulls the pose with full
 // weight): a loss function for solvePnp of hipMinMseTrackerFactory's object (mslam_hip_set_pnp_mse_loss): kinds as above,
 // scale in pixels.  It holds for every later solvePnp of the object.  Bad input throws std::invalid_argument and leaves the
