@@ -720,7 +720,8 @@ int mslam_hip_pose_graph_analyze(const uint8_t* fixed /* K, or NULL */, int K, c
  * keyframe covisible with most others) is far slower than with DENSE at K <= 1024: SPARSE is for long trajectories whose
  * keyframes share landmarks with their neighbours and at loop closures.  tools/ba_global_sparse_latency.py measures both;
  * DESIGN.md 4.26 has one run of it (thin rings: SPARSE about 3x faster per iteration up to 1024 keyframes; a complete map
- * of 128 keyframes: 12x slower).
+ * of 128 keyframes: 12x slower).  A map that revisits its ground has neither a thin envelope nor few keyframes:
+ * mslam_hip_set_ba_global_pcg, below, is for it.
  * mslam_hip_bundle_adjust_global_analyze is the symbolic phase without a context or a GPU: order (keyframe index per
  * position) and first take K entries of which *n_free are written; *ordering is 0 NATURAL or 1 RCM; *n_pairs the covisible
  * pairs k1 <= k2, diagonal included (the waves of the Schur kernel); any output may be NULL.  Its checks are those of the
@@ -735,6 +736,59 @@ int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed /* K, or NULL */
                                            int M, int L, int32_t* order /* K: keyframe index per position, n_free used */,
                                            int32_t* first /* K */, int* n_free, int* ordering /* 0 NATURAL, 1 RCM */,
                                            int64_t* envelope_blocks, int* n_pairs);
+/* ---- An iterative linear solver for mslam_hip_bundle_adjust_global (an extension) ----
+ * Block-Jacobi preconditioned conjugate gradients (PCG) on the reduced camera system, for maps that revisit their ground:
+ * covisibility that is neither thin (SPARSE's envelope passes its bound) nor small (DENSE stops at 1024 keyframes), while the
+ * reduced system itself has few non-zero blocks.  A setting of its own, context state, read by mslam_hip_bundle_adjust_global
+ * alone when it is called; mslam_hip_bundle_adjust and mslam_hip_pose_graph do not read it.  Off by default: with enable = 0
+ * every launch, result bit and error code is what mslam_hip_set_ba_global_solver's kind gives.  With enable = 1 the global
+ * solve uses PCG whatever that kind is, and leaves it untouched.  mslam_hip_set_ba_global_solver keeps its two kinds.
+ *   max_iterations  the cap on CG iterations per linear solve, >= 1; MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS (500) by default;
+ *   tolerance       CG ends at |r_k|_2 <= tolerance |b|_2; in (0, 1); MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE (1e-6) by default.
+ * set returns MSLAM_HIP_E_INVALID and changes nothing for enable outside 0..1, max_iterations < 1 or a tolerance that is not
+ * inside (0, 1) (a NaN included); the three are checked whatever enable is.  get: any pointer may be NULL.
+ * Caps.  K <= MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE (above it: MSLAM_HIP_E_INVALID).  The stored 6 x 6 blocks are the free
+ * observed keyframes plus the covisible pairs k1 < k2 of them: *n_pairs of mslam_hip_bundle_adjust_global_analyze.  They live
+ * in the buffer of the other two solvers and may be at most MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS; above that the call is
+ * MSLAM_HIP_E_CAPACITY, the message names the count and nothing is touched.  No order and no envelope is computed.
+ * The solve.  The Schur complement over the covisible pairs is written block by block, one wave per pair, with the sums of
+ * DENSE in their order.  The preconditioner is the inverse of every diagonal block (Cholesky; a pivot that is not > 0 or not
+ * finite makes the step invalid, as a bad pivot of the other solvers does).  CG starts at y = 0; b = 0 gives y = 0 with no
+ * iteration; p . q that is not > 0 or not finite is a breakdown and makes the step invalid; at the cap the iterate is taken.
+ * The step is inexact; the model cost change is taken from J s per observation as before, which holds for any step, so the
+ * trust region is unchanged, as are the blocks U / V / W, Jacobi scaling, damping, the loss, the back-substitution, candidate,
+ * evaluation, control, termination order, the FAILURE rule and the outlier mask.  Stage names: solver_schur, solver_precond,
+ * solver_cg.  Every sum has one order that does not depend on the launch grid, there are no atomics, and the stopping index is
+ * decided on the device: two calls on the same input and setting return the same bits.
+ * mslam_hip_get_ba_global_pcg_stats reports the last mslam_hip_bundle_adjust_global of the context (all zero after a solve
+ * without PCG, or one that formed no system); mslam_hip_ba_summary is unchanged.
+ * Against Ceres 2.2's ITERATIVE_SCHUR (iterative_schur_complement_solver.cc, conjugate_gradients_solver.cc, restated from the
+ * published text).  PARITY UNPINNED as for every solver here: the tests compare with tests/ba_global_pcg_ref.py.
+ *   the system               DEVIATES: S is formed explicitly, block by block; Ceres's default applies it implicitly
+ *                            (ImplicitSchurComplement) and forms it only with use_explicit_schur_complement;
+ *   preconditioner           the block diagonal of S: Ceres's SCHUR_JACOBI.  DEVIATES from its default for this solver type
+ *                            (JACOBI, the block diagonal of the camera blocks U alone);
+ *   recurrence               SAME: preconditioned CG from x = 0, beta = r.z / (r.z)_old;
+ *   stopping rule            DEVIATES: |r| <= tolerance |b| with a fixed tolerance.  Ceres ends on its Q-tolerance
+ *                            (the decrease of the quadratic model, Nash & Sofer) or r_tolerance, with the forcing sequence
+ *                            eta of its trust-region strategy; neither is built.  tolerance 0.1 (Ceres's eta) is not safe
+ *                            here: DESIGN.md 4.29;
+ *   the cap                  SAME: max_linear_solver_iterations = 500, the iterate at the cap is used;
+ *   breakdown                Ceres reports LINEAR_SOLVER_FAILURE for a non-positive p . q; here the step is invalid, which
+ *                            the trust region treats alike. */
+#define MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS 500
+#define MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE 1e-6
+typedef struct mslam_hip_pcg_stats
+{
+    int64_t solves;     /* linear solves */
+    int64_t iterations; /* CG iterations over all of them */
+    int64_t longest;    /* CG iterations of the longest */
+    int64_t at_cap;     /* solves that ended at max_iterations */
+    int64_t breakdowns; /* solves that ended with p . q not > 0 or not finite */
+} mslam_hip_pcg_stats;
+int mslam_hip_set_ba_global_pcg(mslam_hip_ctx* ctx, int enable, int max_iterations, double tolerance);
+int mslam_hip_get_ba_global_pcg(mslam_hip_ctx* ctx, int* enable, int* max_iterations, double* tolerance);
+int mslam_hip_get_ba_global_pcg_stats(mslam_hip_ctx* ctx, mslam_hip_pcg_stats* stats);
 /* ---- A loss function on the edges of mslam_hip_pose_graph (an extension) ----
  * Context state, the idiom of mslam_hip_set_ba_loss: mslam_hip_pose_graph reads it when it is called, with either linear
  * solver (DENSE and SPARSE), and so does mslam_hip_pose_graph_edge_weights.  The bundle adjustments and mslam_hip_pnp_min_mse

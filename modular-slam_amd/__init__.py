@@ -37,7 +37,8 @@ _PG_SOLVER_NAMES = {"dense": PG_SOLVER_DENSE, "sparse": PG_SOLVER_SPARSE}
 PG_ORDER_NATURAL, PG_ORDER_RCM = 0, 1    # mslam_hip_pose_graph_analyze's orderings
 BA_GLOBAL_MAX_KEYFRAMES, BA_GLOBAL_MAX_KEYFRAMES_SPARSE = 1024, 16384    # mslam_hip_bundle_adjust_global's bounds, DENSE / SPARSE
 BA_GLOBAL_SOLVER_DENSE, BA_GLOBAL_SOLVER_SPARSE = 0, 1    # mslam_hip_set_ba_global_solver's kinds
-CULL_MAX_ENTRIES = 4096    # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
+BA_GLOBAL_PCG_MAX_ITERATIONS, BA_GLOBAL_PCG_TOLERANCE = 500, 1e-6    # mslam_hip_set_ba_global_pcg's defaults
+CULL_MAX_ENTRIES = 4096   # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss's kinds
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
 UNION_DESC_RECENT, UNION_DESC_DISTINCTIVE = 0, 1    # mslam_hip_set_union_descriptor's modes
@@ -77,6 +78,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_pose_graph_loss", "mslam_hip_get_pose_graph_loss", "mslam_hip_pose_graph_edge_weights",
     "mslam_hip_set_pnp_mse_loss", "mslam_hip_get_pnp_mse_loss",
     "mslam_hip_pose_graph_covariance",
+    "mslam_hip_set_ba_global_pcg", "mslam_hip_get_ba_global_pcg", "mslam_hip_get_ba_global_pcg_stats",
 ]
 
 
@@ -156,6 +158,11 @@ class BaSummary(C.Structure):
                 ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class PcgStats(C.Structure):
+    _fields_ = [("solves", C.c_int64), ("iterations", C.c_int64), ("longest", C.c_int64), ("at_cap", C.c_int64),
+                ("breakdowns", C.c_int64)]
+
+
 class BowView(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("words", C.c_void_p), ("values", C.c_void_p), ("n_words", C.c_void_p),
                 ("best_entry", C.c_void_p), ("best_score", C.c_void_p)]
@@ -216,6 +223,32 @@ def _pg_solver_kind(kind, who):
             raise MslamHipError(E_INVALID, "%s: solver %r is not dense / sparse" % (who, kind))
         return _PG_SOLVER_NAMES[kind.lower()]
     return int(kind)
+
+
+def _pcg_flag(enable):
+    """True / False / 0 / 1 -> 0 / 1; anything else goes to the C ABI as a number it rejects"""
+    return int(enable) if isinstance(enable, (bool, int, np.integer)) else -1
+
+
+def _pcg_int(v):
+    """an int32 for the C ABI; what does not fit becomes a number it rejects"""
+    return int(v) if isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 < int(v) < 2 ** 31 else 0
+
+
+def _pcg_setting(pcg, who):
+    """HipBackend's global_pcg: None, True (the defaults) or (max_iterations, tolerance) -> None or the checked pair"""
+    if pcg is None or pcg is False:
+        return None
+    if pcg is True:
+        return BA_GLOBAL_PCG_MAX_ITERATIONS, BA_GLOBAL_PCG_TOLERANCE
+    try:
+        it, tol = pcg
+        ok = isinstance(it, (int, np.integer)) and not isinstance(it, bool) and 1 <= int(it) < 2 ** 31 and 0.0 < float(tol) < 1.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise MslamHipError(E_INVALID, "%s: global_pcg %r is not (max_iterations >= 1, 0 < tolerance < 1)" % (who, pcg))
+    return int(it), float(tol)
 
 
 def pose_graph_analyze(fixed, K, edge_a, edge_b):
@@ -623,7 +656,8 @@ class Context:
         """CeresBackend::globalBundleAdjustment's solve: bundle_adjust's arguments and result with K <= 1024, always through
         the blocked solver (covisible-pair Schur complement, blocked Cholesky over many workgroups), at any K.  After
         set_ba_global_solver("sparse"): K <= 16384, the reduced system on its block envelope (E_CAPACITY when the envelope
-        is above POSE_GRAPH_MAX_ENVELOPE_BLOCKS: nothing touched)."""
+        is above POSE_GRAPH_MAX_ENVELOPE_BLOCKS: nothing touched).  After set_ba_global_pcg(): K <= 16384, the reduced
+        system by preconditioned conjugate gradients on its non-zero blocks, whatever set_ba_global_solver says."""
         return self._bundle_adjust(self.L.mslam_hip_bundle_adjust_global, poses, landmarks, obs_kf, obs_lm, obs_cam, fixed,
                                    max_iterations, outlier_threshold)
 
@@ -639,6 +673,27 @@ class Context:
         k = C.c_int(0)
         self._chk(self.L.mslam_hip_get_ba_global_solver(self._h, C.byref(k)))
         return k.value
+
+    def set_ba_global_pcg(self, enable=True, max_iterations=BA_GLOBAL_PCG_MAX_ITERATIONS, tolerance=BA_GLOBAL_PCG_TOLERANCE):
+        """bundle_adjust_global solves its reduced camera system by block-Jacobi preconditioned conjugate gradients from now
+        on (enable = False: by set_ba_global_solver's kind again, which this setting never changes): K <= 16384 and at most
+        POSE_GRAPH_MAX_ENVELOPE_BLOCKS non-zero blocks (ba_global_analyze's n_pairs), else E_CAPACITY.  CG ends at |r| <=
+        tolerance |b| or after max_iterations, whose iterate is taken.  For maps that revisit their ground; thin rings stay
+        "sparse"'s.  bundle_adjust and pose_graph do not read the setting."""
+        self._chk(self.L.mslam_hip_set_ba_global_pcg(self._h, _pcg_flag(enable), _pcg_int(max_iterations), C.c_double(float(tolerance))))
+
+    def get_ba_global_pcg(self):
+        """-> (enabled, max_iterations, tolerance)"""
+        e, m, t = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.mslam_hip_get_ba_global_pcg(self._h, C.byref(e), C.byref(m), C.byref(t)))
+        return bool(e.value), m.value, t.value
+
+    def ba_global_pcg_stats(self):
+        """the linear solves of the last bundle_adjust_global -> dict(solves, iterations (CG, in total), longest (CG
+        iterations of one solve), at_cap (solves that ended at max_iterations), breakdowns); zeros without PCG"""
+        st = PcgStats()
+        self._chk(self.L.mslam_hip_get_ba_global_pcg_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PcgStats._fields_}
 
     def ba_global_analyze(self, fixed, K, obs_kf, obs_lm, L=None):
         """the module's ba_global_analyze: the symbolic phase bundle_adjust_global would run with "sparse" (no GPU work)"""
@@ -1585,6 +1640,11 @@ class HipBackend:
     global_ba() has its own setting: global_linear_solver = "sparse" (with global_solver = True) runs it with
     Context.set_ba_global_solver("sparse"), puts the context's previous setting back afterwards, also when the solve raises,
     and takes up to 16384 keyframes; "dense" (the default) never touches the setting and takes up to 1024.
+    global_pcg = (max_iterations, tolerance) or True for the defaults (needs global_solver = True, else
+    MslamHipError(E_INVALID), as bad values are, before a context is touched; an extension): global_ba() runs with
+    Context.set_ba_global_pcg and puts the context's previous setting back afterwards, also when the solve raises, takes up to
+    16384 keyframes whatever global_linear_solver is, and its result gains pcg = Context.ba_global_pcg_stats().  None (the
+    default) never touches the setting.
     pose_graph_loss = ("huber", a) or ("cauchy", a) (a in the unit of the weighted residual; an extension): close_loop runs
     with Context.set_pose_graph_loss(kind, a) and puts the context's previous setting back afterwards, also when the solve
     raises; its result gains edge_chi2 and edge_weight (Context.pose_graph_edge_weights at the returned poses; the loop edge
@@ -1597,7 +1657,10 @@ class HipBackend:
     MAX_GLOBAL_KEYFRAMES_SPARSE = BA_GLOBAL_MAX_KEYFRAMES_SPARSE
 
     def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense",
-                 global_linear_solver="dense", pose_graph_loss=None):
+                 global_linear_solver="dense", pose_graph_loss=None, global_pcg=None):
+        self.global_pcg = _pcg_setting(global_pcg, "HipBackend")    # of Context.set_ba_global_pcg
+        if self.global_pcg is not None and not global_solver:
+            raise MslamHipError(E_INVALID, "HipBackend: global_pcg needs global_solver = True")
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
         self.pose_graph_solver = _pg_solver_kind(pose_graph_solver, "HipBackend")    # of Context.set_pose_graph_solver
         if self.pose_graph_solver not in (PG_SOLVER_DENSE, PG_SOLVER_SPARSE):
@@ -1785,9 +1848,19 @@ class HipBackend:
         dense; 16384 with global_linear_solver = "sparse" too) is MslamHipError(E_CAPACITY), raised before the context is
         touched.  prune: see the class docstring"""
         sparse = self.global_solver and self.global_linear_solver == BA_GLOBAL_SOLVER_SPARSE
-        cap = self.MAX_GLOBAL_KEYFRAMES_SPARSE if sparse else self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
+        pcg = self.global_pcg if self.global_solver else None
+        cap = self.MAX_GLOBAL_KEYFRAMES_SPARSE if sparse or pcg else self.MAX_GLOBAL_KEYFRAMES if self.global_solver else self.MAX_KEYFRAMES
         if len(self.poses) > cap:
             raise MslamHipError(E_CAPACITY, "global_ba: %d keyframes, at most %d per solve" % (len(self.poses), cap))
+        if pcg:
+            before = self.ctx.get_ba_global_pcg()
+            self.ctx.set_ba_global_pcg(True, *pcg)
+            try:
+                res = self._solve_pruned(sorted(self.poses), True, prune)
+                res["pcg"] = self.ctx.ba_global_pcg_stats()
+                return res
+            finally:
+                self.ctx.set_ba_global_pcg(*before)
         if not sparse:
             return self._solve_pruned(sorted(self.poses), self.global_solver, prune)
         before = self.ctx.get_ba_global_solver()
@@ -1971,7 +2044,9 @@ class HipKeyframeTracker:
     16384 keyframes (HipBackend; Context.set_pose_graph_solver).  The optional global solve behind a closure
     (loop_global_ba) has its own setting, whatever pose_graph_solver is: ba_global_solver = "dense" (the default: a cap of
     1024 keyframes, the behaviour it had) or "sparse" (HipBackend(global_linear_solver="sparse"); Context.set_ba_global_solver:
-    up to 16384 keyframes, the reduced camera system on its block envelope).
+    up to 16384 keyframes, the reduced camera system on its block envelope).  ba_global_pcg = (max_iterations, tolerance) or
+    True (needs loop_global_ba, else MslamHipError(E_INVALID)) goes to HipBackend(global_pcg=...): that solve then runs by
+    preconditioned conjugate gradients (Context.set_ba_global_pcg), whatever ba_global_solver is.
     loop_covariance = True (needs loop_closure, else MslamHipError(E_INVALID); an extension): close_loop runs with
     covariance = True and the attempt's dict in self.loop_results gains covariance = dict(cur, loop, cross), the marginal
     covariances of the two ends of the loop edge at the solved poses (HipBackend.close_loop; Context.pose_graph_covariance).
@@ -2077,8 +2152,11 @@ class HipKeyframeTracker:
                  loop_global_ba=False, loop_fusion=False, loop_fuse_radius=8.0, loop_fuse_max_distance=50,
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
-                 pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False):
+                 pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False,
+                 ba_global_pcg=None):
         self.ctx = ctx
+        if _pcg_setting(ba_global_pcg, "HipKeyframeTracker") is not None and not (loop_closure and loop_global_ba):
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_global_pcg needs loop_closure and loop_global_ba")
         if loop_covariance and not loop_closure:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: loop_covariance needs loop_closure (close_loop computes it)")
         self.loop_covariance = bool(loop_covariance)
@@ -2131,7 +2209,7 @@ class HipKeyframeTracker:
         # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
         self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss,
                                   pose_graph_solver=pose_graph_solver, global_linear_solver=ba_global_solver,
-                                  pose_graph_loss=self.pose_graph_loss) if local_ba else None
+                                  pose_graph_loss=self.pose_graph_loss, global_pcg=ba_global_pcg) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)

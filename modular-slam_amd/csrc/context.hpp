@@ -176,6 +176,11 @@ struct mslam_hip_ctx
     // mslam_hip_set_ba_global_solver: read by mslam_hip_bundle_adjust_global when it is called; SPARSE keeps the envelope in
     // d_ba_S
     int bag_solver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;
+    // mslam_hip_set_ba_global_pcg: read by mslam_hip_bundle_adjust_global when it is called; enabled, it takes the place of
+    // bag_solver's kind and leaves bag_solver as it is.  The blocks live in d_ba_S.  bag_pcg_stats: the last global solve's
+    int bag_pcg = 0, bag_pcg_max_iterations = MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS;
+    double bag_pcg_tolerance = MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE;
+    mslam_hip_pcg_stats bag_pcg_stats{};
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

@@ -46,10 +46,16 @@
 // block into its envelope slot, and k_pgs_clear / k_pgs_factor / k_pgs_backsolve of k_pg_sparse.hip stand where the blocked
 // solver stands.  Every other kernel is the one DENSE launches.  With DENSE the launches of before.  DESIGN.md 4.26.
 //
+// mslam_hip_set_ba_global_pcg (an extension, read by mslam_hip_bundle_adjust_global alone): the reduced camera system is kept as
+// its non-zero blocks, the diagonal ones and one per covisible pair (ba_symbolic's list, no order, no envelope), written by
+// k_bag_schur_pairs, the fourth form of ba_schur_pair, and solved by the block-Jacobi preconditioned conjugate gradients of
+// k_pcg.hip.  CG's length is the device's to decide, so ba_drive_pcg drives one trust-region iteration at a time instead of
+// tr_run's batches.  Every other kernel is the one DENSE launches.  Off: the launches of before.  DESIGN.md 4.29.
+//
 // ba_schur_pair has one form per layout of the reduced system (SysLayout of reduced_system.hpp: Full for k_ba_schur,
-// PaddedLower for k_bag_schur, Envelope for k_bag_schur_env) and stores through SysView; on the host ba_run decides one BaMode
-// (local, global dense, global sparse) and runs in parts: ba_validate, ba_rows, a pair lister (ba_pairs_all, ba_pairs_table,
-// ba_symbolic), ba_stage, the iteration, ba_read_back.  The global modes take cap, block index, envelope staging, sizes and
+// PaddedLower for k_bag_schur, Envelope for k_bag_schur_env, Pairs for k_bag_schur_pairs) and stores through SysView; on the
+// host ba_run decides one BaMode (local, global dense, global sparse, global PCG) and runs in parts: ba_validate, ba_rows, a
+// pair lister (ba_pairs_all, ba_pairs_table, ba_symbolic), ba_stage, the iteration, ba_read_back.  The global modes take cap, block index, envelope staging, sizes and
 // the solve from LinearSolve (reduced_system.hpp), which mslam_hip_pose_graph uses too.
 #include "reduced_system.hpp"
 
@@ -89,6 +95,9 @@ struct BaArgs
     // MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE: S is the block envelope (pg_sparse.hpp), ci the position in the chosen order; row i's
     // first block and first column.  The right-hand side is rhs
     const int32_t *env_off, *env_first;
+    // mslam_hip_set_ba_global_pcg: S holds the pairs' blocks themselves (SysLayout::Pairs), ci the index order; the block of
+    // pair i of `pairs`.  The right-hand side is rhs
+    const int32_t* pair_slot;
 };
 
 __device__ __forceinline__ void ba_residual(const double* __restrict__ pose, const double* __restrict__ X, const double* __restrict__ obs,
@@ -670,6 +679,11 @@ __global__ __launch_bounds__(256) void k_ba_eval_loss(BaArgs a, int at_start) { 
 // writes (the fill-in) before it, k_pgs_factor and k_pgs_backsolve follow (pg_sparse_solve).  DESIGN.md 4.26.
 __global__ __launch_bounds__(64) void k_bag_schur_env(BaArgs a) { ba_schur_pair<SysLayout::Envelope>(a); }
 
+// ---- the reduced system of mslam_hip_bundle_adjust_global as its non-zero blocks (mslam_hip_set_ba_global_pcg) ----------------
+// After the kernels above, for the same reason.  One wave per covisible pair writes all 36 entries of the pair's block and, on
+// the diagonal, the right-hand side: nothing is cleared before it.  The kernels of k_pcg.hip follow (pcg_solve).  DESIGN.md 4.29.
+__global__ __launch_bounds__(64) void k_bag_schur_pairs(BaArgs a) { ba_schur_pair<SysLayout::Pairs>(a); }
+
 } // namespace mslam
 
 using namespace mslam;
@@ -728,8 +742,9 @@ static void ba_rows(const uint8_t* fixed, int K, int L, const int32_t* obs_kf, c
 // the bit table of the DENSE path reads out, built without a K x K pass.  Keyframe k1 walks its row, and for every landmark of
 // it that landmark's row, and notes each later keyframe the first time it meets it (a stamp per keyframe): sum over the
 // landmarks of views^2 steps and O(K) memory, then a sort per keyframe.  The nodes are the free observed keyframes, the edges
-// the pairs off the diagonal; pg_symbolic gives the two orders and keeps the smaller envelope.
-static void ba_symbolic(const uint8_t* fixed, int K, const int32_t* obs_kf, const BaRows& rw, std::vector<int32_t>& pairs, PgSymbolic& sy)
+// the pairs off the diagonal; pg_symbolic gives the two orders and keeps the smaller envelope.  sy = nullptr: the pairs alone
+// (mslam_hip_set_ba_global_pcg needs no order and no envelope).
+static void ba_symbolic(const uint8_t* fixed, int K, const int32_t* obs_kf, const BaRows& rw, std::vector<int32_t>& pairs, PgSymbolic* sy)
 {
     std::vector<int32_t> stamp((size_t)K, -1), later, ea, eb;
     std::vector<uint8_t> node((size_t)K, 0);
@@ -757,10 +772,12 @@ static void ba_symbolic(const uint8_t* fixed, int K, const int32_t* obs_kf, cons
         for(const int32_t k2 : later)
         {
             pairs.push_back(k1), pairs.push_back(k2);
-            ea.push_back(k1), eb.push_back(k2);
+            if(sy)
+                ea.push_back(k1), eb.push_back(k2);
         }
     }
-    pg_symbolic(fixed, K, ea.data(), eb.data(), ea.size(), sy, node.data());
+    if(sy)
+        pg_symbolic(fixed, K, ea.data(), eb.data(), ea.size(), *sy, node.data());
 }
 
 // every pair k1 <= k2 of free observed keyframes (mslam_hip_bundle_adjust)
@@ -808,8 +825,9 @@ static void ba_pairs_table(int K, int L, const int32_t* obs_kf, const BaRows& rw
 
 // Local: mslam_hip_bundle_adjust (every pair of free keyframes, k_ba_schur, k_ba_solve, S inside d_ba).  The other two:
 // mslam_hip_bundle_adjust_global (covisible pairs, S in d_ba_S) with its solver DENSE (k_bag_schur, the blocked factor) or
-// SPARSE (k_bag_schur_env, the envelope factor).  Decided once, at the top of ba_run.
-enum class BaMode { Local, GlobalDense, GlobalSparse };
+// SPARSE (k_bag_schur_env, the envelope factor) or, after mslam_hip_set_ba_global_pcg, whatever that solver is, PCG
+// (k_bag_schur_pairs, k_pcg.hip).  Decided once, at the top of ba_run.
+enum class BaMode { Local, GlobalDense, GlobalSparse, GlobalPcg };
 
 // the caller's problem, as the entry points take it
 struct BaProblem
@@ -826,6 +844,7 @@ static int ba_validate(mslam_hip_ctx* c, BaMode mode, const BaProblem& p, int k_
     const int K = p.K, L = p.L, M = p.M;
     if(K < 0 || K > k_max)
         return fail(c, MSLAM_HIP_E_INVALID, mode == BaMode::GlobalSparse  ? "bundle_adjust_global: K outside 0..16384 (the SPARSE solver)"
+                                            : mode == BaMode::GlobalPcg   ? "bundle_adjust_global: K outside 0..16384 (PCG)"
                                             : mode == BaMode::GlobalDense ? "bundle_adjust_global: K outside 0..1024"
                                                                           : "bundle_adjust: K outside 0..64");
     if(L < 0 || M < 0 || L > (1 << 24) || M > (1 << 24) || max_iterations < 0 || !(outlier_threshold >= 0.0) || (K > 0 && !p.poses) ||
@@ -898,6 +917,7 @@ static int ba_stage(mslam_hip_ctx* c, BaMode mode, const BaProblem& p, const BaR
     if(!local)
         ls.bind(c, d, a.yc);
     a.env_off = ls.env.row_off, a.env_first = ls.env.first;
+    a.pair_slot = ls.pcg ? reinterpret_cast<const int32_t*>(d + ls.o_pslot) : nullptr;
     kept = {dbl(o_pose0), dbl(o_lm0), d + o_out};
     return MSLAM_HIP_OK;
 }
@@ -935,6 +955,43 @@ static int ba_read_back(mslam_hip_ctx* c, const BaProblem& p, const BaArgs& a, c
     return MSLAM_HIP_OK;
 }
 
+// The iterations of a global solve with PCG.  tr_run enqueues kTrBatch iterations blind; with a CG of unknown length inside
+// that is thousands of launches that do nothing, so one trust-region iteration is driven at a time: its launches are those of
+// ba_run's loop with pcg_solve (which looks at the mapped words between batches of CG iterations) where the factor stands,
+// then a look at the termination word.  Every decision is the device's; the looks only bound the launches that follow it.
+// blocks / step: ba_run's launches before and after the linear solve
+static int ba_drive_pcg(mslam_hip_ctx* c, const BaArgs& a, const LinearSolve& ls, int max_iterations, const std::function<void()>& blocks,
+                        const std::function<void()>& step, mslam_hip_ba_summary& sum)
+{
+    hipStream_t s = c->stream;
+    // iteration max_iterations + 1 only reaches the check kernel, which ends the solve with NO_CONVERGENCE
+    for(long long it = 0; it <= max_iterations; ++it)
+    {
+        StageScope ts(c, "ba_iterations");
+        blocks();
+        if(a.n_pairs > 0)
+            if(const int rc = ls.solve_pcg(c, s, [&] { hipLaunchKernelGGL(k_bag_schur_pairs, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
+               rc != MSLAM_HIP_OK)
+                return rc;
+        step();
+        MSLAM_CHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
+            break;
+    }
+    TrCtrl ctrl;
+    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
+    if(a.n_pairs > 0)
+        MSLAM_CHK(c, hipMemcpyAsync(&c->bag_pcg_stats, &ls.cg.cg->stats, sizeof(c->bag_pcg_stats), hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(!ctrl.done)
+        return fail(c, MSLAM_HIP_E_RUNTIME, "bundle_adjust: the kernels left no termination");
+    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
+    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
+    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
+    return MSLAM_HIP_OK;
+}
+
 // Both entry points
 static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_iterations, double outlier_threshold, uint8_t* outlier,
                   mslam_hip_ba_summary* summary)
@@ -942,12 +999,16 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
     if(!c)
         return MSLAM_HIP_E_INVALID;
     const BaMode mode = !global                                              ? BaMode::Local
+                        : c->bag_pcg                                         ? BaMode::GlobalPcg
                         : c->bag_solver == MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE ? BaMode::GlobalSparse
                                                                              : BaMode::GlobalDense;
-    LinearSolve ls(mode == BaMode::GlobalSparse); // not used by Local, which stages nothing of it and has its own solve
+    // not used by Local, which stages nothing of it and has its own solve
+    LinearSolve ls(mode == BaMode::GlobalSparse, mode == BaMode::GlobalPcg);
     if(const int rc = ba_validate(c, mode, p, global ? ls.k_max() : kBaMaxKeyframes, max_iterations, outlier_threshold); rc != MSLAM_HIP_OK)
         return rc;
     mslam_hip_ba_summary sum{};
+    if(global)
+        c->bag_pcg_stats = mslam_hip_pcg_stats{};
     if(p.M == 0)
     {
         // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
@@ -963,9 +1024,11 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
     else if(mode == BaMode::GlobalDense)
         ba_pairs_table(p.K, p.L, p.obs_kf, rw, pairs);
     else
-        ba_symbolic(p.fixed, p.K, p.obs_kf, rw, pairs, ls.sy);
+        ba_symbolic(p.fixed, p.K, p.obs_kf, rw, pairs, mode == BaMode::GlobalPcg ? nullptr : &ls.sy);
     if(mode != BaMode::Local)
-        if(const int rc = ls.index(c, "bundle_adjust_global", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+        if(const int rc = mode == BaMode::GlobalPcg ? ls.index_pairs(c, "bundle_adjust_global", pairs, rw.ci, rw.n_free)
+                                                    : ls.index(c, "bundle_adjust_global", rw.ci, rw.n_free);
+           rc != MSLAM_HIP_OK)
             return rc;
     BaArgs a{};
     BaKept kept{};
@@ -980,10 +1043,26 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
         StageScope ts(c, "ba_start_cost");
         hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 1);
     }
-    const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
+    // one iteration's launches before and after the linear solve
+    const auto blocks = [&] {
         hipLaunchKernelGGL(loss ? k_ba_landmarks_loss : k_ba_landmarks, g_lm, dim3(256), 0, s, a);
         hipLaunchKernelGGL(loss ? k_ba_cameras_loss : k_ba_cameras, dim3((unsigned)p.K), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_ba_check, dim3(1), dim3(64), 0, s, a);
+    };
+    const auto step = [&] {
+        hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
+        hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+    };
+    if(mode == BaMode::GlobalPcg)
+    {
+        if(const int rc = ba_drive_pcg(c, a, ls, max_iterations, blocks, step, sum); rc != MSLAM_HIP_OK)
+            return rc;
+        return ba_read_back(c, p, a, kept, outlier_threshold, outlier, sum, summary);
+    }
+    const int rc = tr_run(c, "ba_iterations", "bundle_adjust", a.ctrl, max_iterations, [&] {
+        blocks();
         if(a.n_pairs > 0 && mode == BaMode::Local)
         {
             {
@@ -998,10 +1077,7 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
             // the factor overwrote S and the radius moved: the reduced system is rebuilt in every iteration
             ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_bag_schur_env : k_bag_schur, g_pair, dim3(64), 0, s, a); });
         }
-        hipLaunchKernelGGL(k_ba_backsub, g_lm, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_ba_candidate, g_x, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(loss ? k_ba_eval_loss : k_ba_eval, g_obs, dim3(256), 0, s, a, 0);
-        hipLaunchKernelGGL(k_ba_control, dim3(1), dim3(64), 0, s, a);
+        step();
     }, sum);
     if(rc != MSLAM_HIP_OK)
         return rc;
@@ -1038,7 +1114,7 @@ extern "C" int mslam_hip_bundle_adjust_global_analyze(const uint8_t* fixed, int 
     ba_rows(fixed, K, L, obs_kf, obs_lm, M, rw);
     std::vector<int32_t> pairs;
     PgSymbolic sy;
-    ba_symbolic(fixed, K, obs_kf, rw, pairs, sy);
+    ba_symbolic(fixed, K, obs_kf, rw, pairs, &sy);
     if(n_pairs)
         *n_pairs = (int)(pairs.size() / 2);
     return pg_symbolic_out(sy, order, first, n_free, ordering, envelope_blocks);
@@ -1061,6 +1137,39 @@ extern "C" int mslam_hip_get_ba_global_solver(mslam_hip_ctx* c, int* kind)
         return MSLAM_HIP_E_INVALID;
     if(kind)
         *kind = c->bag_solver;
+    return MSLAM_HIP_OK;
+}
+
+// PCG for mslam_hip_bundle_adjust_global: context state, read when it is called
+extern "C" int mslam_hip_set_ba_global_pcg(mslam_hip_ctx* c, int enable, int max_iterations, double tolerance)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(enable < 0 || enable > 1 || max_iterations < 1 || !(tolerance > 0.0 && tolerance < 1.0))
+        return fail(c, MSLAM_HIP_E_INVALID, "set_ba_global_pcg: enable outside 0..1, max_iterations < 1 or a tolerance outside (0, 1)");
+    c->bag_pcg = enable, c->bag_pcg_max_iterations = max_iterations, c->bag_pcg_tolerance = tolerance;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_ba_global_pcg(mslam_hip_ctx* c, int* enable, int* max_iterations, double* tolerance)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(enable)
+        *enable = c->bag_pcg;
+    if(max_iterations)
+        *max_iterations = c->bag_pcg_max_iterations;
+    if(tolerance)
+        *tolerance = c->bag_pcg_tolerance;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_ba_global_pcg_stats(mslam_hip_ctx* c, mslam_hip_pcg_stats* stats)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(stats)
+        *stats = c->bag_pcg_stats;
     return MSLAM_HIP_OK;
 }
 

@@ -43,6 +43,10 @@
 //        mslam_harness <plugin.so> --ba-global <scene> --sparse
 //                                    the global solve with ISparseGlobalBackend::setGlobalSolver(1) first: the reduced camera
 //                                    system on its block envelope, up to 16384 keyframes
+//        mslam_harness <plugin.so> --ba-global <scene> --pcg [<max_iterations>:<tolerance>]
+//                                    the global solve with IIterativeGlobalBackend::setGlobalPcg(true, ...) first (500:1e-6
+//                                    without a value): the reduced camera system by preconditioned conjugate gradients; one more
+//                                    line, "pcg solves S iterations I longest L at_cap C breakdowns B", follows the summary
 //        mslam_harness <plugin.so> --pose-graph <scene>
 //                                    ILoopClosingBackend::closeLoop of the same factory's object on one pose-graph scene: the
 //                                    summary, then every keyframe's state
@@ -196,14 +200,30 @@ int main(int argc, char** argv)
                         result->pose.orientation.z(), inl);
             return 0;
         }
-        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--loss") == 0) ||
+        const bool baPcg = (argc == 5 || argc == 6) && std::strcmp(argv[4], "--pcg") == 0 && std::strcmp(argv[2], "--ba-global") == 0;
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--loss") == 0) || baPcg ||
             (argc == 5 && std::strcmp(argv[4], "--sparse") == 0 && std::strcmp(argv[2], "--ba-global") == 0)) &&
            (std::strcmp(argv[2], "--ba") == 0 || std::strcmp(argv[2], "--ba-global") == 0))
         {
-            const bool sparseSolver = argc == 5;
+            const bool sparseSolver = argc == 5 && !baPcg;
+            int pcgIterations = 500;
+            double pcgTolerance = 1e-6;
+            if(baPcg && argc == 6)
+            {
+                // <whole number>:<number>, all of it: "500", "500:" and "5x:0.1" are usage errors
+                char *end = nullptr, *end2 = nullptr;
+                const long v = std::strtol(argv[5], &end, 10);
+                const double t = end != argv[5] && *end == ':' ? std::strtod(end + 1, &end2) : 0.0;
+                if(end == argv[5] || *end != ':' || end2 == end + 1 || *end2 != '\0' || v < -1000000000 || v > 1000000000)
+                {
+                    std::fprintf(stderr, "--pcg takes <max_iterations>:<tolerance>, not %s\n", argv[5]);
+                    return 2;
+                }
+                pcgIterations = static_cast<int>(v), pcgTolerance = t;
+            }
             int lossKind = 0;
             double lossScale = 0.0;
-            if(argc == 6 && !mslam::parseLoss(argv[5], lossKind, lossScale))
+            if(argc == 6 && !baPcg && !mslam::parseLoss(argv[5], lossKind, lossScale))
             {
                 std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[5]);
                 return 2;
@@ -293,11 +313,27 @@ int main(int argc, char** argv)
                 }
                 sparseBackend->setGlobalSolver(1);
             }
+            auto* pcgBackend = baPcg ? dynamic_cast<mslam::IIterativeGlobalBackend*>(backend.get()) : nullptr;
+            if(baPcg)
+            {
+                if(!pcgBackend)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setGlobalPcg\n");
+                    return 6;
+                }
+                pcgBackend->setGlobalPcg(true, pcgIterations, pcgTolerance); // bad values: its std::invalid_argument, exit code 1
+            }
             const mslam::BackendOutput out =
                 global ? globalBackend->globalBundleAdjustment(observations, head[4]) : backend->bundleAdjustment(observations, head[4]);
             std::printf("ba termination %d iterations %d initial %.17g final %.17g keyframes %zu landmarks %zu outliers %zu\n", out.termination,
                         out.iterations, out.initialCost, out.finalCost, out.updatedKeyframes.size(), out.updatedLandmarks.size(),
                         out.outlierObservations.size());
+            if(pcgBackend)
+            {
+                const mslam::GlobalPcgStats st = pcgBackend->globalPcgStats();
+                std::printf("pcg solves %lld iterations %lld longest %lld at_cap %lld breakdowns %lld\n", st.solves, st.iterations, st.longest,
+                            st.atCap, st.breakdowns);
+            }
             for(std::size_t k = 0; k < K; ++k)
             {
                 const auto& st = keyframes[k]->state;

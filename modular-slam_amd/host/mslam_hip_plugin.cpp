@@ -17,6 +17,7 @@
 //                          : IPoseGraphCovariance                                 marginal covariances of closeLoop's problem (an extension)
 //                          : ISparseGlobalBackend                                 globalBundleAdjustment's linear solver, the same choice (an extension)
 //                          : IRobustPoseGraphBackend                              a Huber or Cauchy loss on closeLoop's edges (an extension)
+//                          : IIterativeGlobalBackend                              globalBundleAdjustment by preconditioned conjugate gradients (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -1029,9 +1030,17 @@ class HipMinMseTracker : public ISlam3dPnp, public IRobustPnp
 // same way.  poseGraphCovariance (IPoseGraphCovariance, an extension) hands closeLoop's arrays to
 // mslam_hip_pose_graph_covariance and writes nothing back.
 class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend,
-                               public IRobustPoseGraphBackend, public IPoseGraphCovariance
+                               public IRobustPoseGraphBackend, public IPoseGraphCovariance, public IIterativeGlobalBackend
 {
   public:
+    // IIterativeGlobalBackend (an extension): kept for every later globalBundleAdjustment, set on the context before each one
+    void setGlobalPcg(bool enable, int maxIterations, double tolerance) override
+    {
+        if(maxIterations < 1 || !(tolerance > 0.0 && tolerance < 1.0))
+            throw std::invalid_argument("setGlobalPcg: maxIterations >= 1 and a tolerance inside (0, 1)");
+        pcgEnable = enable, pcgMaxIterations = maxIterations, pcgTolerance = tolerance;
+    }
+    GlobalPcgStats globalPcgStats() const override { return pcgStats; }
     // IPoseGraphCovariance (an extension): closeLoop's arrays at the keyframes' present states to
     // mslam_hip_pose_graph_covariance, under closeLoop's loss; nothing is written back
     PoseGraphCovariance poseGraphCovariance(const std::vector<KeyframePtr>& keyframes, const std::vector<PoseGraphEdge>& edges,
@@ -1221,11 +1230,20 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
             raise(ctx.h, "mslam_hip_set_ba_loss", lrc);
         if(const int rs = mslam_hip_set_ba_global_solver(ctx.h, globalSolver); rs != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_set_ba_global_solver", rs);
+        if(const int rs = mslam_hip_set_ba_global_pcg(ctx.h, pcgEnable ? 1 : 0, pcgMaxIterations, pcgTolerance); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_ba_global_pcg", rs);
         const int rc = entry(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), points.data(),
                              static_cast<int>(landmarks.size()), obsKf.data(), obsLm.data(), obsCam.data(),
                              static_cast<int>(observations.size()), maxIterations, 0.15, outlier.data(), &summary);
         if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
             raise(ctx.h, global ? "mslam_hip_bundle_adjust_global" : "mslam_hip_bundle_adjust", rc);
+        if(global)
+        {
+            mslam_hip_pcg_stats st{};
+            if(const int rs = mslam_hip_get_ba_global_pcg_stats(ctx.h, &st); rs != MSLAM_HIP_OK)
+                raise(ctx.h, "mslam_hip_get_ba_global_pcg_stats", rs);
+            pcgStats = GlobalPcgStats{st.solves, st.iterations, st.longest, st.at_cap, st.breakdowns};
+        }
         BackendOutput out;
         out.termination = summary.termination, out.iterations = summary.iterations;
         out.initialCost = summary.initial_cost, out.finalCost = summary.final_cost;
@@ -1251,6 +1269,10 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     Ctx ctx;
     int poseGraphSolver = MSLAM_HIP_PG_SOLVER_DENSE;
     int globalSolver = MSLAM_HIP_BA_GLOBAL_SOLVER_DENSE;
+    bool pcgEnable = false;
+    int pcgMaxIterations = MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS;
+    double pcgTolerance = MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE;
+    GlobalPcgStats pcgStats;
     int lossKind = MSLAM_HIP_BA_LOSS_NONE;
     double lossScale = 0.0;
     int pgLossKind = MSLAM_HIP_BA_LOSS_NONE;

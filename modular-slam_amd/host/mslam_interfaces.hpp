@@ -288,6 +288,25 @@ class ISparseGlobalBackend
     virtual void setGlobalSolver(int kind) = 0;
     virtual ~ISparseGlobalBackend() = default;
 };
+// extension: globalBundleAdjustment solves its reduced camera system by block-Jacobi preconditioned conjugate gradients
+// (mslam_hip_set_ba_global_pcg) instead of a factor: for maps that revisit their ground, whose covisibility is neither thin
+// nor small (up to 16384 keyframes and 1048576 non-zero 6 x 6 blocks).  enable = false is the default; with true CG ends at
+// |r| <= tolerance |b| or after maxIterations, whose iterate is taken, whatever ISparseGlobalBackend::setGlobalSolver says.  It
+// holds for every later globalBundleAdjustment of the object; bundleAdjustment and closeLoop do not read it.  maxIterations < 1
+// or a tolerance outside (0, 1) throws std::invalid_argument and leaves the setting as it was.  globalPcgStats reports the
+// linear solves of the last globalBundleAdjustment (zeros without PCG).  An interface of its own, reached with dynamic_cast like
+// ISparseGlobalBackend.
+struct GlobalPcgStats
+{
+    long long solves = 0, iterations = 0, longest = 0, atCap = 0, breakdowns = 0;
+};
+class IIterativeGlobalBackend
+{
+  public:
+    virtual void setGlobalPcg(bool enable, int maxIterations, double tolerance) = 0;
+    virtual GlobalPcgStats globalPcgStats() const = 0;
+    virtual ~IIterativeGlobalBackend() = default;
+};
 // extension: a loss function on the edges of closeLoop (mslam_hip_set_pose_graph_loss): kind 0 none (the default), 1 Ceres's
 // HuberLoss(scale), 2 CauchyLoss(scale), scale in the unit of the weighted residual of an edge.  It holds for every later
 // closeLoop of the object, with either linear solver; the bundle adjustments do not read it, and IRobustBackend::setLoss does not
