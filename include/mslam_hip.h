@@ -789,6 +789,54 @@ typedef struct mslam_hip_pcg_stats
 int mslam_hip_set_ba_global_pcg(mslam_hip_ctx* ctx, int enable, int max_iterations, double tolerance);
 int mslam_hip_get_ba_global_pcg(mslam_hip_ctx* ctx, int* enable, int* max_iterations, double* tolerance);
 int mslam_hip_get_ba_global_pcg_stats(mslam_hip_ctx* ctx, mslam_hip_pcg_stats* stats);
+/* ---- An iterative linear solver for mslam_hip_pose_graph (an extension) ----
+ * The same block-Jacobi preconditioned conjugate gradients, on the pose graph's damped normal equations, for graphs that
+ * revisit their ground: HipBackend.close_loop builds its pose graph from the covisibility graph, so on such a map it has the
+ * sparsity of the reduced camera system above, which neither DENSE (1024 poses) nor SPARSE (the envelope bound) takes.  A
+ * setting of its own, context state, read by mslam_hip_pose_graph alone when it is called: mslam_hip_pose_graph_covariance
+ * and mslam_hip_pose_graph_edge_weights do not read it, mslam_hip_set_ba_global_pcg does not touch it and it does not touch
+ * that setting.  Off by default: with enable = 0 every launch, result bit and error code is what
+ * mslam_hip_set_pose_graph_solver's kind gives.  With enable = 1 mslam_hip_pose_graph uses PCG whatever that kind is, and
+ * leaves it untouched.
+ *   max_iterations  the cap on CG iterations per linear solve, >= 1; MSLAM_HIP_POSE_GRAPH_PCG_MAX_ITERATIONS (500) by default;
+ *   tolerance       CG ends at |r_k|_2 <= tolerance |b|_2; in (0, 1); MSLAM_HIP_POSE_GRAPH_PCG_TOLERANCE (1e-6) by default.
+ * set returns MSLAM_HIP_E_INVALID and changes nothing for enable outside 0..1, max_iterations < 1 or a tolerance that is not
+ * inside (0, 1) (a NaN included); the three are checked whatever enable is.  get: any pointer may be NULL.
+ * Caps.  K <= MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE (above it: MSLAM_HIP_E_INVALID).  The stored 6 x 6 blocks are the free
+ * poses that have an edge plus the unique pairs of them an edge joins.  They live in
+ * the buffer of the other two solvers and may be at most MSLAM_HIP_POSE_GRAPH_MAX_ENVELOPE_BLOCKS; above that the call is
+ * MSLAM_HIP_E_CAPACITY, the message names the count and nothing is touched.  While E <= MSLAM_HIP_POSE_GRAPH_MAX_EDGES (65536)
+ * and K <= 16384 the count is at most 81920 and the bound is never met: a graph with more edges is MSLAM_HIP_E_INVALID by the
+ * edge cap first.  No order and no envelope is computed.
+ * The solve.  J^T J + D^2 is written block by block, one wave per pair, with the sums of DENSE in their order (duplicate
+ * edges of one pair are that pair's serial sum in list order).  Preconditioner, start, breakdown rule and the iterate at the
+ * cap are those stated for mslam_hip_set_ba_global_pcg above: the kernels are the same.  The step is inexact; the model cost
+ * change is taken from J s per edge as before, which holds for any step, so the trust region is unchanged, as are the edge
+ * blocks, Jacobi scaling, damping, mslam_hip_set_pose_graph_loss (the rows are corrected before the assembly), candidate,
+ * evaluation, control, termination order and the FAILURE rule.  Stage names inside pg_iterations: solver_schur (the assembly),
+ * solver_precond, solver_cg.  Two calls on the same input and setting return the same bits.
+ * A chain is the preconditioner's hard case: CG needs about nine iterations per pose of a thin chain at tolerance 1e-12 and
+ * about seven at the default, so at the defaults a chain of more than about 70 poses ends solves at the cap,
+ * where the iterate is taken and the result is less exact; thin chains stay SPARSE's ground.  A graph that revisits needs 50 to 200 iterations at any size.
+ * mslam_hip_get_pose_graph_pcg_stats reports the last mslam_hip_pose_graph of the context (all zero after a solve without
+ * PCG, or one that formed no system: E == 0, or no free pose with an edge); mslam_hip_ba_summary is unchanged.
+ * Against Ceres 2.2's conjugate gradients on a pose graph (CGNR, cgnr_solver.cc, and ITERATIVE_SCHUR on a problem without
+ * landmarks; restated from the published text).  PARITY UNPINNED as for every solver here: the tests compare with
+ * tests/pose_graph_pcg_ref.py.
+ *   the system               DEVIATES: the normal equations J^T J + D^2 are formed explicitly, block by block; CGNR applies
+ *                            J and J^T in turn and never forms them;
+ *   preconditioner           SAME as CGNR's JACOBI: the inverse of the 6 x 6 block diagonal of J^T J + D^2;
+ *   recurrence               SAME: preconditioned CG from x = 0, beta = r.z / (r.z)_old;
+ *   stopping rule            DEVIATES: |r| <= tolerance |b| with a fixed tolerance; Ceres's Q-tolerance / r_tolerance with
+ *                            the forcing sequence eta is not built;
+ *   the cap                  SAME: max_linear_solver_iterations = 500, the iterate at the cap is used;
+ *   breakdown                Ceres reports LINEAR_SOLVER_FAILURE for a non-positive p . q; here the step is invalid, which
+ *                            the trust region treats alike. */
+#define MSLAM_HIP_POSE_GRAPH_PCG_MAX_ITERATIONS 500
+#define MSLAM_HIP_POSE_GRAPH_PCG_TOLERANCE 1e-6
+int mslam_hip_set_pose_graph_pcg(mslam_hip_ctx* ctx, int enable, int max_iterations, double tolerance);
+int mslam_hip_get_pose_graph_pcg(mslam_hip_ctx* ctx, int* enable, int* max_iterations, double* tolerance);
+int mslam_hip_get_pose_graph_pcg_stats(mslam_hip_ctx* ctx, mslam_hip_pcg_stats* stats);
 /* ---- A loss function on the edges of mslam_hip_pose_graph (an extension) ----
  * Context state, the idiom of mslam_hip_set_ba_loss: mslam_hip_pose_graph reads it when it is called, with either linear
  * solver (DENSE and SPARSE), and so does mslam_hip_pose_graph_edge_weights.  The bundle adjustments and mslam_hip_pnp_min_mse

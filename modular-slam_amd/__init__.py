@@ -38,6 +38,7 @@ PG_ORDER_NATURAL, PG_ORDER_RCM = 0, 1    # mslam_hip_pose_graph_analyze's orderi
 BA_GLOBAL_MAX_KEYFRAMES, BA_GLOBAL_MAX_KEYFRAMES_SPARSE = 1024, 16384    # mslam_hip_bundle_adjust_global's bounds, DENSE / SPARSE
 BA_GLOBAL_SOLVER_DENSE, BA_GLOBAL_SOLVER_SPARSE = 0, 1    # mslam_hip_set_ba_global_solver's kinds
 BA_GLOBAL_PCG_MAX_ITERATIONS, BA_GLOBAL_PCG_TOLERANCE = 500, 1e-6    # mslam_hip_set_ba_global_pcg's defaults
+POSE_GRAPH_PCG_MAX_ITERATIONS, POSE_GRAPH_PCG_TOLERANCE = 500, 1e-6    # mslam_hip_set_pose_graph_pcg's defaults
 CULL_MAX_ENTRIES = 4096   # mslam_hip_kf_observers / _cull_search / _cull: the listed entries of one call
 BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss's kinds
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
@@ -79,6 +80,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_pnp_mse_loss", "mslam_hip_get_pnp_mse_loss",
     "mslam_hip_pose_graph_covariance",
     "mslam_hip_set_ba_global_pcg", "mslam_hip_get_ba_global_pcg", "mslam_hip_get_ba_global_pcg_stats",
+    "mslam_hip_set_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg_stats",
 ]
 
 
@@ -235,19 +237,21 @@ def _pcg_int(v):
     return int(v) if isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 < int(v) < 2 ** 31 else 0
 
 
-def _pcg_setting(pcg, who):
-    """HipBackend's global_pcg: None, True (the defaults) or (max_iterations, tolerance) -> None or the checked pair"""
+def _pcg_setting(pcg, who, what="global_pcg"):
+    """HipBackend's global_pcg / pose_graph_pcg: None, True (the defaults) or (max_iterations, tolerance) -> None or the
+    checked pair"""
     if pcg is None or pcg is False:
         return None
     if pcg is True:
-        return BA_GLOBAL_PCG_MAX_ITERATIONS, BA_GLOBAL_PCG_TOLERANCE
+        return ((POSE_GRAPH_PCG_MAX_ITERATIONS, POSE_GRAPH_PCG_TOLERANCE) if what == "pose_graph_pcg"
+                else (BA_GLOBAL_PCG_MAX_ITERATIONS, BA_GLOBAL_PCG_TOLERANCE))
     try:
         it, tol = pcg
         ok = isinstance(it, (int, np.integer)) and not isinstance(it, bool) and 1 <= int(it) < 2 ** 31 and 0.0 < float(tol) < 1.0
     except (TypeError, ValueError):
         ok = False
     if not ok:
-        raise MslamHipError(E_INVALID, "%s: global_pcg %r is not (max_iterations >= 1, 0 < tolerance < 1)" % (who, pcg))
+        raise MslamHipError(E_INVALID, "%s: %s %r is not (max_iterations >= 1, 0 < tolerance < 1)" % (who, what, pcg))
     return int(it), float(tol)
 
 
@@ -748,6 +752,28 @@ class Context:
         self._chk(self.L.mslam_hip_get_pose_graph_solver(self._h, C.byref(k)))
         return k.value
 
+    def set_pose_graph_pcg(self, enable=True, max_iterations=POSE_GRAPH_PCG_MAX_ITERATIONS, tolerance=POSE_GRAPH_PCG_TOLERANCE):
+        """pose_graph solves its damped normal equations by block-Jacobi preconditioned conjugate gradients from now on
+        (enable = False: by set_pose_graph_solver's kind again, which this setting never changes): K <= 16384, the non-zero
+        blocks alone, no order and no envelope.  CG ends at |r| <= tolerance |b| or after max_iterations, whose iterate is
+        taken.  For graphs that revisit their ground; CG needs about nine iterations per pose of a thin chain, so thin chains
+        stay "sparse"'s.  A setting of its own: pose_graph_covariance, pose_graph_edge_weights and the bundle adjustments do
+        not read it, and set_ba_global_pcg does not touch it."""
+        self._chk(self.L.mslam_hip_set_pose_graph_pcg(self._h, _pcg_flag(enable), _pcg_int(max_iterations), C.c_double(float(tolerance))))
+
+    def get_pose_graph_pcg(self):
+        """-> (enabled, max_iterations, tolerance)"""
+        e, m, t = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        self._chk(self.L.mslam_hip_get_pose_graph_pcg(self._h, C.byref(e), C.byref(m), C.byref(t)))
+        return bool(e.value), m.value, t.value
+
+    def pose_graph_pcg_stats(self):
+        """the linear solves of the last pose_graph -> dict(solves, iterations (CG, in total), longest (CG iterations of one
+        solve), at_cap (solves that ended at max_iterations), breakdowns); zeros without PCG or without a system"""
+        st = PcgStats()
+        self._chk(self.L.mslam_hip_get_pose_graph_pcg_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in PcgStats._fields_}
+
     def set_pose_graph_loss(self, kind, scale=0.0):
         """the loss function of pose_graph from now on, with either linear solver (an extension): kind "none" (the default
         state) / "huber" / "cauchy" or BA_LOSS_*; scale a in the unit of the weighted residual, finite and > 0 for huber and
@@ -785,7 +811,7 @@ class Context:
 
     def pose_graph(self, poses, edge_a, edge_b, edge_meas, sqrt_info=None, fixed=None, max_iterations=100):
         """The pose-graph solve behind closeLoop: poses [K, 7] (qx qy qz qw px py pz, camera -> world, K <= 1024, or 16384
-        after set_pose_graph_solver("sparse")), E edges
+        after set_pose_graph_solver("sparse") or set_pose_graph_pcg()), E edges
         (a, b) with edge_meas [E, 7] = q then p of pose b in a's frame, sqrt_info [E, 6, 6] or None for identity, fixed = [K]
         flags or None.  -> dict(poses, termination, iterations, rejected_steps, invalid_steps, n_outliers = 0, initial_cost,
         final_cost).  termination 2 (FAILURE) is a result here (MSLAM_HIP_E_NO_MODEL): the poses come back unchanged.
@@ -1645,6 +1671,10 @@ class HipBackend:
     Context.set_ba_global_pcg and puts the context's previous setting back afterwards, also when the solve raises, takes up to
     16384 keyframes whatever global_linear_solver is, and its result gains pcg = Context.ba_global_pcg_stats().  None (the
     default) never touches the setting.
+    pose_graph_pcg = (max_iterations, tolerance) or True for the defaults (bad values are MslamHipError(E_INVALID) before a
+    context is touched; an extension): close_loop runs with Context.set_pose_graph_pcg and puts the context's previous setting
+    back afterwards, also when the solve raises, takes up to 16384 keyframes whatever pose_graph_solver is, and its result
+    gains pcg = Context.pose_graph_pcg_stats().  None (the default) never touches the setting.
     pose_graph_loss = ("huber", a) or ("cauchy", a) (a in the unit of the weighted residual; an extension): close_loop runs
     with Context.set_pose_graph_loss(kind, a) and puts the context's previous setting back afterwards, also when the solve
     raises; its result gains edge_chi2 and edge_weight (Context.pose_graph_edge_weights at the returned poses; the loop edge
@@ -1657,8 +1687,9 @@ class HipBackend:
     MAX_GLOBAL_KEYFRAMES_SPARSE = BA_GLOBAL_MAX_KEYFRAMES_SPARSE
 
     def __init__(self, ctx, max_iterations=100, outlier_threshold=0.15, global_solver=False, loss=None, pose_graph_solver="dense",
-                 global_linear_solver="dense", pose_graph_loss=None, global_pcg=None):
+                 global_linear_solver="dense", pose_graph_loss=None, global_pcg=None, pose_graph_pcg=None):
         self.global_pcg = _pcg_setting(global_pcg, "HipBackend")    # of Context.set_ba_global_pcg
+        self.pose_graph_pcg = _pcg_setting(pose_graph_pcg, "HipBackend", "pose_graph_pcg")    # of Context.set_pose_graph_pcg
         if self.global_pcg is not None and not global_solver:
             raise MslamHipError(E_INVALID, "HipBackend: global_pcg needs global_solver = True")
         self.ctx, self.max_iterations, self.outlier_threshold = ctx, int(max_iterations), float(outlier_threshold)
@@ -1919,14 +1950,18 @@ class HipBackend:
         landmarks.  Solves loop_problem() on the device; on a usable termination the poses are replaced and every landmark
         moves rigidly with its anchor keyframe, X' = T_a' T_a^-1 X.  -> the summary and keyframes, poses_before, poses,
         landmark_ids, landmarks (FAILURE: everything as it was).  More than 1024 keyframes (16384 with
-        pose_graph_solver = "sparse") is MslamHipError(E_CAPACITY), a keyframe the backend does not hold
-        MslamHipError(E_INVALID), both raised before the context is touched.
+        pose_graph_solver = "sparse" or with pose_graph_pcg) is MslamHipError(E_CAPACITY), a keyframe the backend does not
+        hold MslamHipError(E_INVALID), both raised before the context is touched.  With pose_graph_pcg the result gains pcg.
         covariance = True (an extension): after a usable termination one Context.pose_graph_covariance call on the same
         problem at the solved poses, under the same loss; the result gains covariance = dict(cur, loop, cross): the 6 x 6
         marginals of cur_id and loop_id on the tangent (delta, dp) and cross = E[d_cur d_loop^T] (the loop edge joins the
         two, so the block is inside the envelope; a constant keyframe gives zeros).  None when the problem is rank
-        deficient (E_NO_MODEL: no constant keyframe in the graph's component).  With False nothing new runs."""
-        cap = POSE_GRAPH_MAX_KEYFRAMES_SPARSE if self.pose_graph_solver == PG_SOLVER_SPARSE else POSE_GRAPH_MAX_KEYFRAMES
+        deficient (E_NO_MODEL: no constant keyframe in the graph's component).  With False nothing new runs.  The
+        covariance keeps the envelope factor and its bound under pose_graph_pcg too: on a graph whose envelope is above
+        POSE_GRAPH_MAX_ENVELOPE_BLOCKS the solve succeeds with PCG and the covariance call's MslamHipError(E_CAPACITY)
+        propagates, as it does with the other solvers."""
+        sparse_cap = self.pose_graph_solver == PG_SOLVER_SPARSE or self.pose_graph_pcg is not None
+        cap = POSE_GRAPH_MAX_KEYFRAMES_SPARSE if sparse_cap else POSE_GRAPH_MAX_KEYFRAMES
         if len(self.poses) > cap:
             raise MslamHipError(E_CAPACITY, "close_loop: %d keyframes, at most %d per solve" % (len(self.poses), cap))
         if int(cur_id) not in self.poses or int(loop_id) not in self.poses or int(cur_id) == int(loop_id):
@@ -1936,7 +1971,15 @@ class HipBackend:
             loss_before = self.ctx.get_pose_graph_loss()
             self.ctx.set_pose_graph_loss(*self.pose_graph_loss)
         try:
-            if self.pose_graph_solver == PG_SOLVER_SPARSE:
+            if self.pose_graph_pcg is not None:
+                before = self.ctx.get_pose_graph_pcg()
+                self.ctx.set_pose_graph_pcg(True, *self.pose_graph_pcg)
+                try:
+                    res = self.ctx.pose_graph(poses, ea, eb, meas, info, fixed, self.max_iterations)
+                    res["pcg"] = self.ctx.pose_graph_pcg_stats()
+                finally:
+                    self.ctx.set_pose_graph_pcg(*before)
+            elif self.pose_graph_solver == PG_SOLVER_SPARSE:
                 before = self.ctx.get_pose_graph_solver()
                 self.ctx.set_pose_graph_solver(PG_SOLVER_SPARSE)
                 try:
@@ -2047,6 +2090,10 @@ class HipKeyframeTracker:
     up to 16384 keyframes, the reduced camera system on its block envelope).  ba_global_pcg = (max_iterations, tolerance) or
     True (needs loop_global_ba, else MslamHipError(E_INVALID)) goes to HipBackend(global_pcg=...): that solve then runs by
     preconditioned conjugate gradients (Context.set_ba_global_pcg), whatever ba_global_solver is.
+    pose_graph_pcg = (max_iterations, tolerance) or True (needs loop_closure, else MslamHipError(E_INVALID)) goes to
+    HipBackend(pose_graph_pcg=...): close_loop then solves by preconditioned conjugate gradients (Context.set_pose_graph_pcg)
+    and takes up to 16384 keyframes, whatever pose_graph_solver is.  On a map that revisits its ground the pose graph has
+    the covisibility graph's sparsity, so the pair pose_graph_pcg and ba_global_pcg takes such a map through both solves.
     loop_covariance = True (needs loop_closure, else MslamHipError(E_INVALID); an extension): close_loop runs with
     covariance = True and the attempt's dict in self.loop_results gains covariance = dict(cur, loop, cross), the marginal
     covariances of the two ends of the loop edge at the solved poses (HipBackend.close_loop; Context.pose_graph_covariance).
@@ -2153,8 +2200,10 @@ class HipKeyframeTracker:
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
                  pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False,
-                 ba_global_pcg=None):
+                 ba_global_pcg=None, pose_graph_pcg=None):
         self.ctx = ctx
+        if _pcg_setting(pose_graph_pcg, "HipKeyframeTracker", "pose_graph_pcg") is not None and not loop_closure:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: pose_graph_pcg needs loop_closure (close_loop takes the setting)")
         if _pcg_setting(ba_global_pcg, "HipKeyframeTracker") is not None and not (loop_closure and loop_global_ba):
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: ba_global_pcg needs loop_closure and loop_global_ba")
         if loop_covariance and not loop_closure:
@@ -2209,7 +2258,8 @@ class HipKeyframeTracker:
         # with loop_global_ba the backend's global solve is the one without the 64-keyframe cap
         self.backend = HipBackend(ctx, global_solver=bool(loop_closure and loop_global_ba), loss=self.ba_loss,
                                   pose_graph_solver=pose_graph_solver, global_linear_solver=ba_global_solver,
-                                  pose_graph_loss=self.pose_graph_loss, global_pcg=ba_global_pcg) if local_ba else None
+                                  pose_graph_loss=self.pose_graph_loss, global_pcg=ba_global_pcg,
+                                  pose_graph_pcg=pose_graph_pcg) if local_ba else None
         self.ba_results = []
         if guided_radius is not None:
             ctx.set_guided_match(guided_radius, guided_max_distance)

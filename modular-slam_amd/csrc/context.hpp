@@ -181,6 +181,11 @@ struct mslam_hip_ctx
     int bag_pcg = 0, bag_pcg_max_iterations = MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS;
     double bag_pcg_tolerance = MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE;
     mslam_hip_pcg_stats bag_pcg_stats{};
+    // mslam_hip_set_pose_graph_pcg: read by mslam_hip_pose_graph when it is called; enabled, it takes the place of pg_solver's
+    // kind and leaves pg_solver as it is.  The blocks live in d_ba_S.  pg_pcg_stats: the last pose-graph solve's
+    int pg_pcg = 0, pg_pcg_max_iterations = MSLAM_HIP_POSE_GRAPH_PCG_MAX_ITERATIONS;
+    double pg_pcg_tolerance = MSLAM_HIP_POSE_GRAPH_PCG_TOLERANCE;
+    mslam_hip_pcg_stats pg_pcg_stats{};
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;

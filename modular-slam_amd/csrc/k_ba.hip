@@ -49,8 +49,8 @@
 // mslam_hip_set_ba_global_pcg (an extension, read by mslam_hip_bundle_adjust_global alone): the reduced camera system is kept as
 // its non-zero blocks, the diagonal ones and one per covisible pair (ba_symbolic's list, no order, no envelope), written by
 // k_bag_schur_pairs, the fourth form of ba_schur_pair, and solved by the block-Jacobi preconditioned conjugate gradients of
-// k_pcg.hip.  CG's length is the device's to decide, so ba_drive_pcg drives one trust-region iteration at a time instead of
-// tr_run's batches.  Every other kernel is the one DENSE launches.  Off: the launches of before.  DESIGN.md 4.29.
+// k_pcg.hip.  CG's length is the device's to decide, so tr_run_pcg (reduced_system.hpp) drives one trust-region iteration at a
+// time instead of tr_run's batches.  Every other kernel is the one DENSE launches.  Off: the launches of before.  DESIGN.md 4.29.
 //
 // ba_schur_pair has one form per layout of the reduced system (SysLayout of reduced_system.hpp: Full for k_ba_schur,
 // PaddedLower for k_bag_schur, Envelope for k_bag_schur_env, Pairs for k_bag_schur_pairs) and stores through SysView; on the
@@ -955,43 +955,6 @@ static int ba_read_back(mslam_hip_ctx* c, const BaProblem& p, const BaArgs& a, c
     return MSLAM_HIP_OK;
 }
 
-// The iterations of a global solve with PCG.  tr_run enqueues kTrBatch iterations blind; with a CG of unknown length inside
-// that is thousands of launches that do nothing, so one trust-region iteration is driven at a time: its launches are those of
-// ba_run's loop with pcg_solve (which looks at the mapped words between batches of CG iterations) where the factor stands,
-// then a look at the termination word.  Every decision is the device's; the looks only bound the launches that follow it.
-// blocks / step: ba_run's launches before and after the linear solve
-static int ba_drive_pcg(mslam_hip_ctx* c, const BaArgs& a, const LinearSolve& ls, int max_iterations, const std::function<void()>& blocks,
-                        const std::function<void()>& step, mslam_hip_ba_summary& sum)
-{
-    hipStream_t s = c->stream;
-    // iteration max_iterations + 1 only reaches the check kernel, which ends the solve with NO_CONVERGENCE
-    for(long long it = 0; it <= max_iterations; ++it)
-    {
-        StageScope ts(c, "ba_iterations");
-        blocks();
-        if(a.n_pairs > 0)
-            if(const int rc = ls.solve_pcg(c, s, [&] { hipLaunchKernelGGL(k_bag_schur_pairs, dim3((unsigned)a.n_pairs), dim3(64), 0, s, a); });
-               rc != MSLAM_HIP_OK)
-                return rc;
-        step();
-        MSLAM_CHK(c, hipGetLastError());
-        MSLAM_CHK(c, hipStreamSynchronize(s));
-        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
-            break;
-    }
-    TrCtrl ctrl;
-    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
-    if(a.n_pairs > 0)
-        MSLAM_CHK(c, hipMemcpyAsync(&c->bag_pcg_stats, &ls.cg.cg->stats, sizeof(c->bag_pcg_stats), hipMemcpyDeviceToHost, s));
-    MSLAM_CHK(c, hipStreamSynchronize(s));
-    if(!ctrl.done)
-        return fail(c, MSLAM_HIP_E_RUNTIME, "bundle_adjust: the kernels left no termination");
-    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
-    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
-    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
-    return MSLAM_HIP_OK;
-}
-
 // Both entry points
 static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_iterations, double outlier_threshold, uint8_t* outlier,
                   mslam_hip_ba_summary* summary)
@@ -1003,7 +966,7 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
                         : c->bag_solver == MSLAM_HIP_BA_GLOBAL_SOLVER_SPARSE ? BaMode::GlobalSparse
                                                                              : BaMode::GlobalDense;
     // not used by Local, which stages nothing of it and has its own solve
-    LinearSolve ls(mode == BaMode::GlobalSparse, mode == BaMode::GlobalPcg);
+    LinearSolve ls(mode == BaMode::GlobalSparse, mode == BaMode::GlobalPcg, c->bag_pcg_max_iterations, c->bag_pcg_tolerance);
     if(const int rc = ba_validate(c, mode, p, global ? ls.k_max() : kBaMaxKeyframes, max_iterations, outlier_threshold); rc != MSLAM_HIP_OK)
         return rc;
     mslam_hip_ba_summary sum{};
@@ -1057,7 +1020,11 @@ static int ba_run(mslam_hip_ctx* c, bool global, const BaProblem& p, int max_ite
     };
     if(mode == BaMode::GlobalPcg)
     {
-        if(const int rc = ba_drive_pcg(c, a, ls, max_iterations, blocks, step, sum); rc != MSLAM_HIP_OK)
+        // CG's length is the device's to decide: tr_run_pcg drives one trust-region iteration at a time
+        const auto assemble = [&] { hipLaunchKernelGGL(k_bag_schur_pairs, g_pair, dim3(64), 0, s, a); };
+        if(const int rc = tr_run_pcg(c, "ba_iterations", "bundle_adjust", a.ctrl, ls, a.n_pairs > 0, max_iterations, blocks, assemble, step,
+                                     &c->bag_pcg_stats, sum);
+           rc != MSLAM_HIP_OK)
             return rc;
         return ba_read_back(c, p, a, kept, outlier_threshold, outlier, sum, summary);
     }

@@ -1,7 +1,8 @@
 // k_pcg.hip — block-Jacobi preconditioned conjugate gradients on a symmetric positive definite system in 6 x 6 blocks, kept as
 // its non-zero blocks (SysLayout::Pairs of reduced_system.hpp: diagonal blocks first, every off-diagonal pair once) with a
 // list of neighbours per block row.  mslam_hip_bundle_adjust_global runs it on its reduced camera system after
-// mslam_hip_set_ba_global_pcg; pcg.hpp has the arguments and the control block.  DESIGN.md 4.29.
+// mslam_hip_set_ba_global_pcg, mslam_hip_pose_graph on its normal equations after mslam_hip_set_pose_graph_pcg; pcg.hpp has the
+// arguments and the control block.  DESIGN.md 4.29, 4.30.
 //
 //   x = 0, r = b, z = M^-1 r, p = z;  per iteration  q = S p, alpha = r.z / p.q, x += alpha p, r -= alpha q, z = M^-1 r,
 //   stop at |r| <= tol |b| or at the cap, else beta = r.z / (r.z)_old, p = z + beta p

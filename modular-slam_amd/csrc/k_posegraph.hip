@@ -49,6 +49,11 @@
 // mslam_hip_pose_graph_covariance runs k_pg_edges (or _loss) and k_pg_poses under a control block at its start,
 // k_pg_assemble_env_undamped (pg_assemble_pair without the damping term, a right-hand side of zeros), the factor of
 // k_pg_sparse.hip and the two kernels of k_pg_cov.hip: blocks of (J^T J)^-1 inside the envelope.
+// mslam_hip_set_pose_graph_pcg (an extension, off by default, read by mslam_hip_pose_graph alone): the normal equations are kept
+// as their non-zero blocks, the diagonal ones and one per pair an edge joins (pg_pairs's list, no order, no envelope), written
+// by k_pg_assemble_pairs, the fourth store of pg_assemble_pair, and solved by the block-Jacobi preconditioned conjugate
+// gradients of k_pcg.hip, unchanged.  CG's length is the device's to decide, so tr_run_pcg (reduced_system.hpp) drives one
+// trust-region iteration at a time instead of tr_run's batches.  Every other kernel is the one DENSE launches.  DESIGN.md 4.30.
 // No sum uses an atomic and every sum has one order: two calls on the same input return the same bits.  No kernel waits on
 // another workgroup; every device loop is bounded by a count the host validated.  All arithmetic is f64.
 #include "reduced_system.hpp"
@@ -86,6 +91,9 @@ struct PgArgs
     double* part;        // [2][n_blocks]: model cost change, candidate cost
     TrCtrl* ctrl;
     int32_t* h_done; // mapped
+    // mslam_hip_set_pose_graph_pcg: S holds the pairs' blocks themselves (SysLayout::Pairs), ci the index order; the block of
+    // pair i of `pairs`.  The right-hand side is rhs
+    const int32_t* pair_slot;
 };
 
 // entry (i, k) of the edge's sqrt_info
@@ -279,9 +287,10 @@ __global__ __launch_bounds__(64) void k_pg_check(PgArgs a)
 
 // ---- the normal equations: a wave per pair of free poses ------------------------------------------------------------------
 
-// One body for both layouts: the pair's lookup, the diagonal with its damping, the sum over the pair's edge list and the
+// One body for every layout: the pair's lookup, the diagonal with its damping, the sum over the pair's edge list and the
 // scaling; SysView (reduced_system.hpp) knows where the entries go.  ci is the block in index order with PaddedLower, the
-// position in the chosen order with Envelope.  kDamped = false (mslam_hip_pose_graph_covariance): the scaled J^T J itself and a
+// position in the chosen order with Envelope, the block in index order again with Pairs (k1 < k2 gives b1 < b2, which SysView's
+// Pairs store relies on).  kDamped = false (mslam_hip_pose_graph_covariance): the scaled J^T J itself and a
 // right-hand side of zeros.
 template <SysLayout kLayout, bool kDamped = true>
 __device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
@@ -337,6 +346,10 @@ __device__ __forceinline__ void pg_assemble_pair(const PgArgs& a)
 __global__ __launch_bounds__(64) void k_pg_assemble(PgArgs a) { pg_assemble_pair<SysLayout::PaddedLower>(a); }
 __global__ __launch_bounds__(64) void k_pg_assemble_env(PgArgs a) { pg_assemble_pair<SysLayout::Envelope>(a); }
 __global__ __launch_bounds__(64) void k_pg_assemble_env_undamped(PgArgs a) { pg_assemble_pair<SysLayout::Envelope, false>(a); }
+// mslam_hip_set_pose_graph_pcg: the normal equations as their non-zero blocks.  A diagonal wave writes all 36 entries of its
+// block and the six of the right-hand side, an off-diagonal wave all 36 of its pair's: nothing is cleared before it.  The
+// kernels of k_pcg.hip follow (pcg_solve).  DESIGN.md 4.30.
+__global__ __launch_bounds__(64) void k_pg_assemble_pairs(PgArgs a) { pg_assemble_pair<SysLayout::Pairs>(a); }
 
 // delta = step * scaling with step = -y; Plus.  Poses outside the problem are copied.
 __global__ __launch_bounds__(256) void k_pg_candidate(PgArgs a)
@@ -676,10 +689,12 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
 {
     if(!c)
         return MSLAM_HIP_E_INVALID;
-    LinearSolve ls(c->pg_solver == MSLAM_HIP_PG_SOLVER_SPARSE);
+    // mslam_hip_set_pose_graph_pcg stands where the solver's kind stands
+    LinearSolve ls(c->pg_solver == MSLAM_HIP_PG_SOLVER_SPARSE, c->pg_pcg != 0, c->pg_pcg_max_iterations, c->pg_pcg_tolerance);
     if(const int rc = pg_validate(c, ls.k_max(), poses, K, edge_a, edge_b, edge_meas, sqrt_info, E, max_iterations); rc != MSLAM_HIP_OK)
         return rc;
     mslam_hip_ba_summary sum{};
+    c->pg_pcg_stats = mslam_hip_pcg_stats{};
     if(E == 0)
     {
         // solver.cc Minimize(): no parameter blocks -> CONVERGENCE at cost 0, nothing touched
@@ -691,9 +706,19 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     pg_incidences(fixed, K, edge_a, edge_b, E, rw);
     if(ls.sparse)
         pg_symbolic(fixed, K, edge_a, edge_b, E, ls.sy); // its nodes are the free poses that have an edge: rw.n_free of them
-    if(const int rc = ls.index(c, "pose_graph", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
-        return rc;
-    pg_pairs(K, edge_a, edge_b, E, rw);
+    if(ls.pcg)
+    {
+        // no order and no envelope: the stored blocks are the pairs themselves
+        pg_pairs(K, edge_a, edge_b, E, rw);
+        if(const int rc = ls.index_pairs(c, "pose_graph", rw.pairs, rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+            return rc;
+    }
+    else
+    {
+        if(const int rc = ls.index(c, "pose_graph", rw.ci, rw.n_free); rc != MSLAM_HIP_OK)
+            return rc;
+        pg_pairs(K, edge_a, edge_b, E, rw);
+    }
 
     PgArgs a{};
     a.K = K, a.E = E, a.n = ls.n, a.n_pad = ls.n_pad, a.ld = ls.ld;
@@ -730,7 +755,8 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
     a.h_done = c->h_ba.dev();
     *c->h_ba.get() = 0;
     ls.bind(c, d, a.yc);
-    a.env_off = ls.env.row_off, a.env_first = ls.env.first, a.rhs = ls.env.rhs;
+    a.env_off = ls.env.row_off, a.env_first = ls.env.first, a.rhs = ls.pcg ? dbl(ls.o_rhs) : ls.env.rhs;
+    a.pair_slot = ls.pcg ? i32(ls.o_pslot) : nullptr;
     // NONE: the launches of before the setting existed
     const TrLoss tl{c->pg_loss_kind, c->pg_loss_scale};
     const bool loss = tl.kind != MSLAM_HIP_BA_LOSS_NONE;
@@ -743,18 +769,17 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
         else
             hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 1);
     }
-    const int rc = tr_run(c, "pg_iterations", "pose_graph", a.ctrl, max_iterations, [&] {
-        {
-            StageScope tk(c, "pg_blocks");
-            if(loss)
-                hipLaunchKernelGGL(k_pg_edges_loss, g_edge, dim3(256), 0, s, a, tl);
-            else
-                hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
-            hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
-        }
-        if(a.n_pairs > 0)
-            ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_pg_assemble_env : k_pg_assemble, g_pair, dim3(64), 0, s, a); });
+    // one iteration's launches before and after the linear solve
+    const auto blocks = [&] {
+        StageScope tk(c, "pg_blocks");
+        if(loss)
+            hipLaunchKernelGGL(k_pg_edges_loss, g_edge, dim3(256), 0, s, a, tl);
+        else
+            hipLaunchKernelGGL(k_pg_edges, g_edge, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pg_poses, dim3((unsigned)K), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_pg_check, dim3(1), dim3(64), 0, s, a);
+    };
+    const auto step = [&] {
         StageScope tk(c, "pg_step");
         hipLaunchKernelGGL(k_pg_candidate, g_x, dim3(256), 0, s, a);
         if(loss)
@@ -762,7 +787,21 @@ extern "C" int mslam_hip_pose_graph(mslam_hip_ctx* c, double* poses, const uint8
         else
             hipLaunchKernelGGL(k_pg_eval, g_edge, dim3(256), 0, s, a, 0);
         hipLaunchKernelGGL(k_pg_control, dim3(1), dim3(64), 0, s, a);
-    }, sum);
+    };
+    int rc;
+    if(ls.pcg)
+    {
+        // CG's length is the device's to decide: tr_run_pcg drives one trust-region iteration at a time
+        const auto assemble = [&] { hipLaunchKernelGGL(k_pg_assemble_pairs, g_pair, dim3(64), 0, s, a); };
+        rc = tr_run_pcg(c, "pg_iterations", "pose_graph", a.ctrl, ls, a.n_pairs > 0, max_iterations, blocks, assemble, step, &c->pg_pcg_stats, sum);
+    }
+    else
+        rc = tr_run(c, "pg_iterations", "pose_graph", a.ctrl, max_iterations, [&] {
+            blocks();
+            if(a.n_pairs > 0)
+                ls.solve(c, s, [&] { hipLaunchKernelGGL(ls.sparse ? k_pg_assemble_env : k_pg_assemble, g_pair, dim3(64), 0, s, a); });
+            step();
+        }, sum);
     if(rc != MSLAM_HIP_OK)
         return rc;
     const bool usable = sum.termination != kTrFailure;
@@ -797,6 +836,39 @@ extern "C" int mslam_hip_get_pose_graph_solver(mslam_hip_ctx* c, int* kind)
         return MSLAM_HIP_E_INVALID;
     if(kind)
         *kind = c->pg_solver;
+    return MSLAM_HIP_OK;
+}
+
+// PCG for mslam_hip_pose_graph: context state of its own, read when it is called
+extern "C" int mslam_hip_set_pose_graph_pcg(mslam_hip_ctx* c, int enable, int max_iterations, double tolerance)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(enable < 0 || enable > 1 || max_iterations < 1 || !(tolerance > 0.0 && tolerance < 1.0))
+        return fail(c, MSLAM_HIP_E_INVALID, "set_pose_graph_pcg: enable outside 0..1, max_iterations < 1 or a tolerance outside (0, 1)");
+    c->pg_pcg = enable, c->pg_pcg_max_iterations = max_iterations, c->pg_pcg_tolerance = tolerance;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_pose_graph_pcg(mslam_hip_ctx* c, int* enable, int* max_iterations, double* tolerance)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(enable)
+        *enable = c->pg_pcg;
+    if(max_iterations)
+        *max_iterations = c->pg_pcg_max_iterations;
+    if(tolerance)
+        *tolerance = c->pg_pcg_tolerance;
+    return MSLAM_HIP_OK;
+}
+
+extern "C" int mslam_hip_get_pose_graph_pcg_stats(mslam_hip_ctx* c, mslam_hip_pcg_stats* stats)
+{
+    if(!c)
+        return MSLAM_HIP_E_INVALID;
+    if(stats)
+        *stats = c->pg_pcg_stats;
     return MSLAM_HIP_OK;
 }
 

@@ -1,6 +1,7 @@
 // pcg.hpp — the block-Jacobi preconditioned conjugate gradients of k_pcg.hip on a symmetric system kept as its non-zero 6 x 6
-// blocks (SysLayout::Pairs of reduced_system.hpp): mslam_hip_bundle_adjust_global's third linear solver
-// (mslam_hip_set_ba_global_pcg).  The caller reaches pcg_solve through LinearSolve.  DESIGN.md 4.29.
+// blocks (SysLayout::Pairs of reduced_system.hpp): the third linear solver of mslam_hip_bundle_adjust_global
+// (mslam_hip_set_ba_global_pcg) and of mslam_hip_pose_graph (mslam_hip_set_pose_graph_pcg).  The caller reaches pcg_solve
+// through LinearSolve.  DESIGN.md 4.29, 4.30.
 #pragma once
 #include "trust_region.hpp"
 

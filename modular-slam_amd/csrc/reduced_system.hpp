@@ -4,7 +4,8 @@
 //   SysView      device: where entry (r, c) of the block of a pair and entry r of the right-hand side live, per layout
 //   LinearSolve  host: the choice DENSE / SPARSE / PCG of one solve and what follows from it (cap, block index, staging, sizes,
 //                solve)
-// DESIGN.md 4.17, 4.25, 4.26, 4.29.
+//   tr_run_pcg   host: the trust-region loop of a solve with PCG, one iteration at a time
+// DESIGN.md 4.17, 4.25, 4.26, 4.29, 4.30.
 #pragma once
 #include "chol_solver.hpp"
 #include "pcg.hpp"
@@ -87,10 +88,13 @@ static_assert(MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES_SPARSE == MSLAM_HIP_POSE_GRAPH_M
 // One solve's linear solver.  The calls, in this order: the K cap; the caller's symbolic phase into sy (SPARSE); index (PCG:
 // index_pairs); put after the caller's own puts, carve after its carves; grow_S; bind once the block is uploaded; solve in
 // every iteration (PCG: solve_pcg, which synchronises and so is not called from tr_run).  With DENSE nothing is staged and sy
-// stays empty.  PCG (pcg.hpp) is wired into mslam_hip_bundle_adjust_global alone; sparse is false with it.
+// stays empty.  PCG (pcg.hpp): sparse is false with it; the cap on CG's iterations and its tolerance are the caller's
+// (mslam_hip_set_ba_global_pcg for the bundle adjustment, mslam_hip_set_pose_graph_pcg for the pose graph).
 struct LinearSolve
 {
     const bool sparse, pcg;
+    const int cg_max_iterations; // PCG: CG iterations per solve at most; |r| <= cg_tolerance |b| ends it
+    const double cg_tolerance;
     PgSymbolic sy;
     int n_free = 0, n = 0, n_pad = 0, ld = 0; // blocks; 6 x blocks; CholArgs's padded size and leading dimension
     size_t o_roff = 0, o_first = 0, o_cptr = 0, o_cblk = 0, o_crow = 0, o_rhs = 0, o_dinv = 0;
@@ -104,7 +108,10 @@ struct LinearSolve
     PcgArgs cg{};
     size_t o_rptr = 0, o_ncol = 0, o_nslot = 0, o_pslot = 0, o_cg = 0, o_minv = 0, o_vec = 0, o_part = 0;
 
-    explicit LinearSolve(bool sparse_, bool pcg_ = false) : sparse(sparse_ && !pcg_), pcg(pcg_) {}
+    explicit LinearSolve(bool sparse_, bool pcg_ = false, int cg_max_iterations_ = 0, double cg_tolerance_ = 0.0)
+        : sparse(sparse_ && !pcg_), pcg(pcg_), cg_max_iterations(cg_max_iterations_), cg_tolerance(cg_tolerance_)
+    {
+    }
     // DENSE: (6 x 1024)^2 doubles = 302 MB of d_ba_S
     int k_max() const { return sparse || pcg ? MSLAM_HIP_POSE_GRAPH_MAX_KEYFRAMES_SPARSE : MSLAM_HIP_BA_GLOBAL_MAX_KEYFRAMES; }
 
@@ -204,7 +211,7 @@ struct LinearSolve
         {
             double *v = dbl(o_vec), *part = dbl(o_part);
             const size_t nn = (size_t)n;
-            cg = PcgArgs{n_free, n, pcg_prod_parts(), pcg_vec_parts(), c->bag_pcg_max_iterations, c->bag_pcg_tolerance, i32(o_rptr), i32(o_ncol),
+            cg = PcgArgs{n_free, n, pcg_prod_parts(), pcg_vec_parts(), cg_max_iterations, cg_tolerance, i32(o_rptr), i32(o_ncol),
                          i32(o_nslot), c->d_ba_S.get(), dbl(o_rhs), dbl(o_minv), yc, v, v + 2 * nn, v + 3 * nn, v + 4 * nn, part,
                          part + pcg_prod_parts(), part + pcg_prod_parts() + pcg_vec_parts(), reinterpret_cast<PcgCtrl*>(d + o_cg), ctrl,
                          c->h_ba.dev() + 1};
@@ -225,5 +232,44 @@ struct LinearSolve
     // PCG: assemble enqueues the caller's assembly kernel for Pairs.  Synchronises the stream; a MSLAM_HIP_* status
     int solve_pcg(mslam_hip_ctx* c, hipStream_t s, const std::function<void()>& assemble) const { return pcg_solve(c, cg, s, assemble); }
 };
+
+// tr_run for a solve with PCG.  tr_run enqueues kTrBatch iterations blind; with a CG of unknown length inside that is
+// thousands of launches that do nothing, so one trust-region iteration is driven at a time: `before` (the launches up to the
+// check kernel), pcg_solve with `assemble` where the factor stands (it looks at the mapped words between batches of CG
+// iterations; skipped when the problem has no system: !has_system), `after` (the step's launches), then a look at the
+// termination word.  Every decision is the device's; the looks only bound the launches that follow it.  At the end the
+// control block fills `sum` and, where a system was formed, CG's statistics come back into *stats.  `stage` names the timed
+// stage of an iteration, `who` the entry point in the error
+inline int tr_run_pcg(mslam_hip_ctx* c, const char* stage, const char* who, const TrCtrl* d_ctrl, const LinearSolve& ls, bool has_system,
+                      int max_iterations, const std::function<void()>& before, const std::function<void()>& assemble,
+                      const std::function<void()>& after, mslam_hip_pcg_stats* stats, mslam_hip_ba_summary& sum)
+{
+    hipStream_t s = c->stream;
+    // iteration max_iterations + 1 only reaches the check kernel, which ends the solve with NO_CONVERGENCE
+    for(long long it = 0; it <= max_iterations; ++it)
+    {
+        StageScope ts(c, stage);
+        before();
+        if(has_system)
+            if(const int rc = ls.solve_pcg(c, s, assemble); rc != MSLAM_HIP_OK)
+                return rc;
+        after();
+        MSLAM_CHK(c, hipGetLastError());
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+        if(*static_cast<volatile int32_t*>(c->h_ba.get()))
+            break;
+    }
+    TrCtrl ctrl;
+    MSLAM_CHK(c, hipMemcpyAsync(&ctrl, d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, s));
+    if(has_system)
+        MSLAM_CHK(c, hipMemcpyAsync(stats, &ls.cg.cg->stats, sizeof(*stats), hipMemcpyDeviceToHost, s));
+    MSLAM_CHK(c, hipStreamSynchronize(s));
+    if(!ctrl.done)
+        return fail(c, MSLAM_HIP_E_RUNTIME, std::string(who) + ": the kernels left no termination");
+    sum.termination = ctrl.termination, sum.iterations = ctrl.iteration;
+    sum.rejected_steps = ctrl.rejected, sum.invalid_steps = ctrl.invalid_total;
+    sum.initial_cost = ctrl.initial_cost, sum.final_cost = ctrl.x_cost;
+    return MSLAM_HIP_OK;
+}
 
 } // namespace mslam

@@ -59,6 +59,11 @@
 //                                    the same with IRobustPoseGraphBackend::setPoseGraphLoss(kind, a) first (a in the unit of the
 //                                    weighted residual, finite and > 0), after --sparse when both are given: the costs of the
 //                                    summary are then 1/2 sum rho
+//        mslam_harness <plugin.so> --pose-graph <scene> --pcg [<max_iterations>:<tolerance>]
+//                                    the same with IIterativePoseGraphBackend::setPoseGraphPcg(true, ...) first (500:1e-6 without
+//                                    a value): the normal equations by preconditioned conjugate gradients, up to 16384
+//                                    keyframes; one more line, "pcg solves S iterations I longest L at_cap C breakdowns B",
+//                                    follows the summary
 //        mslam_harness <plugin.so> --pose-graph <scene> --covariance
 //                                    no solve: IPoseGraphCovariance::poseGraphCovariance of the same object at the scene's
 //                                    states, for every keyframe that is not constant and has an edge: "covariance blocks N",
@@ -107,6 +112,18 @@ static std::uint32_t fnv(const void* p, std::size_t n, std::uint32_t h = 0x811C9
     for(std::size_t i = 0; i < n; ++i)
         h = (h ^ b[i]) * 0x01000193u;
     return h;
+}
+
+// --pcg's value: <whole number>:<number>, all of it: "500", "500:" and "5x:0.1" are not one
+static bool parsePcg(const char* text, int& maxIterations, double& tolerance)
+{
+    char *end = nullptr, *end2 = nullptr;
+    const long v = std::strtol(text, &end, 10);
+    const double t = end != text && *end == ':' ? std::strtod(end + 1, &end2) : 0.0;
+    if(end == text || *end != ':' || end2 == end + 1 || *end2 != '\0' || v < -1000000000 || v > 1000000000)
+        return false;
+    maxIterations = static_cast<int>(v), tolerance = t;
+    return true;
 }
 
 int main(int argc, char** argv)
@@ -208,18 +225,10 @@ int main(int argc, char** argv)
             const bool sparseSolver = argc == 5 && !baPcg;
             int pcgIterations = 500;
             double pcgTolerance = 1e-6;
-            if(baPcg && argc == 6)
+            if(baPcg && argc == 6 && !parsePcg(argv[5], pcgIterations, pcgTolerance))
             {
-                // <whole number>:<number>, all of it: "500", "500:" and "5x:0.1" are usage errors
-                char *end = nullptr, *end2 = nullptr;
-                const long v = std::strtol(argv[5], &end, 10);
-                const double t = end != argv[5] && *end == ':' ? std::strtod(end + 1, &end2) : 0.0;
-                if(end == argv[5] || *end != ':' || end2 == end + 1 || *end2 != '\0' || v < -1000000000 || v > 1000000000)
-                {
-                    std::fprintf(stderr, "--pcg takes <max_iterations>:<tolerance>, not %s\n", argv[5]);
-                    return 2;
-                }
-                pcgIterations = static_cast<int>(v), pcgTolerance = t;
+                std::fprintf(stderr, "--pcg takes <max_iterations>:<tolerance>, not %s\n", argv[5]);
+                return 2;
             }
             int lossKind = 0;
             double lossScale = 0.0;
@@ -346,15 +355,24 @@ int main(int argc, char** argv)
                 std::printf("outlier %llu %llu\n", static_cast<unsigned long long>(o.keyframe->id), static_cast<unsigned long long>(o.landmark->id));
             return 0;
         }
-        // --pose-graph <scene>, then nothing, --sparse, --solver <kind>, --loss <spec>, --sparse --loss <spec> or --covariance
+        // --pose-graph <scene>, then nothing, --sparse, --solver <kind>, --loss <spec>, --sparse --loss <spec>, --covariance or
+        // --pcg [<spec>]
+        const bool pgPcg = (argc == 5 || argc == 6) && std::strcmp(argv[4], "--pcg") == 0;
         const bool pgCovariance = argc == 5 && std::strcmp(argv[4], "--covariance") == 0;
         const bool pgLossOnly = argc == 6 && std::strcmp(argv[4], "--loss") == 0;
         const bool pgSparseLoss = argc == 7 && std::strcmp(argv[4], "--sparse") == 0 && std::strcmp(argv[5], "--loss") == 0;
         if((argc == 4 || (argc == 5 && std::strcmp(argv[4], "--sparse") == 0) || (argc == 6 && std::strcmp(argv[4], "--solver") == 0) ||
-            pgLossOnly || pgSparseLoss || pgCovariance) &&
+            pgLossOnly || pgSparseLoss || pgCovariance || pgPcg) &&
            std::strcmp(argv[2], "--pose-graph") == 0)
         {
-            const bool setSolver = argc > 4 && !pgLossOnly && !pgCovariance;
+            const bool setSolver = argc > 4 && !pgLossOnly && !pgCovariance && !pgPcg;
+            int pcgIterations = 500;
+            double pcgTolerance = 1e-6;
+            if(pgPcg && argc == 6 && !parsePcg(argv[5], pcgIterations, pcgTolerance))
+            {
+                std::fprintf(stderr, "--pcg takes <max_iterations>:<tolerance>, not %s\n", argv[5]);
+                return 2;
+            }
             int solverKind = 1;
             int lossKind = 0;
             double lossScale = 0.0;
@@ -363,7 +381,7 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "--loss takes huber:<a> or cauchy:<a> with a finite a > 0, not %s\n", argv[argc - 1]);
                 return 2;
             }
-            if(argc == 6 && !pgLossOnly)
+            if(argc == 6 && !pgLossOnly && !pgPcg)
             {
                 // a whole integer or nothing: "abc" and "1x" are usage errors, not kind 0 or 1
                 char* end = nullptr;
@@ -486,9 +504,25 @@ int main(int argc, char** argv)
                 }
                 return 0;
             }
+            auto* pcgBackend = pgPcg ? dynamic_cast<mslam::IIterativePoseGraphBackend*>(backend.get()) : nullptr;
+            if(pgPcg)
+            {
+                if(!pcgBackend)
+                {
+                    std::fprintf(stderr, "the plugin does not offer setPoseGraphPcg\n");
+                    return 6;
+                }
+                pcgBackend->setPoseGraphPcg(true, pcgIterations, pcgTolerance); // bad values: its std::invalid_argument, exit code 1
+            }
             const mslam::BackendOutput out = loopBackend->closeLoop(keyframes, edges, head[3]);
             std::printf("pose_graph termination %d iterations %d initial %.17g final %.17g keyframes %zu edges %zu\n", out.termination,
                         out.iterations, out.initialCost, out.finalCost, out.updatedKeyframes.size(), E);
+            if(pcgBackend)
+            {
+                const mslam::GlobalPcgStats st = pcgBackend->poseGraphPcgStats();
+                std::printf("pcg solves %lld iterations %lld longest %lld at_cap %lld breakdowns %lld\n", st.solves, st.iterations, st.longest,
+                            st.atCap, st.breakdowns);
+            }
             for(std::size_t k = 0; k < K; ++k)
             {
                 const auto& st = keyframes[k]->state;

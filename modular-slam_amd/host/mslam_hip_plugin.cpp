@@ -18,6 +18,7 @@
 //                          : ISparseGlobalBackend                                 globalBundleAdjustment's linear solver, the same choice (an extension)
 //                          : IRobustPoseGraphBackend                              a Huber or Cauchy loss on closeLoop's edges (an extension)
 //                          : IIterativeGlobalBackend                              globalBundleAdjustment by preconditioned conjugate gradients (an extension)
+//                          : IIterativePoseGraphBackend                           closeLoop by preconditioned conjugate gradients (an extension)
 //                                                           (ceres_reprojection_error_pnp.cpp:64-110)
 //   HipLoopDetector   : ILoopDetector                      (loop_detection.hpp:10-15, rgbd_feature_frontend.cpp:202);
 //                                                           both sit on ONE shared BoW database
@@ -1030,9 +1031,18 @@ class HipMinMseTracker : public ISlam3dPnp, public IRobustPnp
 // same way.  poseGraphCovariance (IPoseGraphCovariance, an extension) hands closeLoop's arrays to
 // mslam_hip_pose_graph_covariance and writes nothing back.
 class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend, public ISparsePoseGraphBackend, public ISparseGlobalBackend,
-                               public IRobustPoseGraphBackend, public IPoseGraphCovariance, public IIterativeGlobalBackend
+                               public IRobustPoseGraphBackend, public IPoseGraphCovariance, public IIterativeGlobalBackend,
+                               public IIterativePoseGraphBackend
 {
   public:
+    // IIterativePoseGraphBackend (an extension): kept for every later closeLoop, set on the context before each one
+    void setPoseGraphPcg(bool enable, int maxIterations, double tolerance) override
+    {
+        if(maxIterations < 1 || !(tolerance > 0.0 && tolerance < 1.0))
+            throw std::invalid_argument("setPoseGraphPcg: maxIterations >= 1 and a tolerance inside (0, 1)");
+        pgPcgEnable = enable, pgPcgMaxIterations = maxIterations, pgPcgTolerance = tolerance;
+    }
+    GlobalPcgStats poseGraphPcgStats() const override { return pgPcgStats; }
     // IIterativeGlobalBackend (an extension): kept for every later globalBundleAdjustment, set on the context before each one
     void setGlobalPcg(bool enable, int maxIterations, double tolerance) override
     {
@@ -1120,12 +1130,19 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
             raise(ctx.h, "mslam_hip_set_pose_graph_solver", rs);
         if(const int rs = mslam_hip_set_pose_graph_loss(ctx.h, pgLossKind, pgLossScale); rs != MSLAM_HIP_OK)
             raise(ctx.h, "mslam_hip_set_pose_graph_loss", rs);
+        if(const int rs = mslam_hip_set_pose_graph_pcg(ctx.h, pgPcgEnable ? 1 : 0, pgPcgMaxIterations, pgPcgTolerance); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_set_pose_graph_pcg", rs);
+        pgPcgStats = GlobalPcgStats{};
         mslam_hip_ba_summary summary{};
         const int rc = mslam_hip_pose_graph(ctx.h, poses.data(), fixed.data(), static_cast<int>(keyframes.size()), edgeA.data(),
                                             edgeB.data(), meas.data(), anyInfo ? info.data() : nullptr, static_cast<int>(edges.size()),
                                             maxIterations, &summary);
         if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_NO_MODEL)
             raise(ctx.h, "mslam_hip_pose_graph", rc);
+        mslam_hip_pcg_stats st{};
+        if(const int rs = mslam_hip_get_pose_graph_pcg_stats(ctx.h, &st); rs != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_get_pose_graph_pcg_stats", rs);
+        pgPcgStats = GlobalPcgStats{st.solves, st.iterations, st.longest, st.at_cap, st.breakdowns};
         BackendOutput out;
         out.termination = summary.termination, out.iterations = summary.iterations;
         out.initialCost = summary.initial_cost, out.finalCost = summary.final_cost;
@@ -1273,6 +1290,10 @@ class HipBundleAdjustBackend : public ILoopClosingBackend, public IRobustBackend
     int pcgMaxIterations = MSLAM_HIP_BA_GLOBAL_PCG_MAX_ITERATIONS;
     double pcgTolerance = MSLAM_HIP_BA_GLOBAL_PCG_TOLERANCE;
     GlobalPcgStats pcgStats;
+    bool pgPcgEnable = false;
+    int pgPcgMaxIterations = MSLAM_HIP_POSE_GRAPH_PCG_MAX_ITERATIONS;
+    double pgPcgTolerance = MSLAM_HIP_POSE_GRAPH_PCG_TOLERANCE;
+    GlobalPcgStats pgPcgStats;
     int lossKind = MSLAM_HIP_BA_LOSS_NONE;
     double lossScale = 0.0;
     int pgLossKind = MSLAM_HIP_BA_LOSS_NONE;

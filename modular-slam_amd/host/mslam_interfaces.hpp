@@ -307,6 +307,21 @@ class IIterativeGlobalBackend
     virtual GlobalPcgStats globalPcgStats() const = 0;
     virtual ~IIterativeGlobalBackend() = default;
 };
+// extension: closeLoop solves its damped normal equations by the same block-Jacobi preconditioned conjugate gradients
+// (mslam_hip_set_pose_graph_pcg) instead of a factor: for pose graphs built from the covisibility graph of a map that revisits
+// its ground (up to 16384 keyframes; no envelope and no order).  enable = false is the default; with true CG ends at |r| <=
+// tolerance |b| or after maxIterations, whose iterate is taken, whatever ISparsePoseGraphBackend::setPoseGraphSolver says.  It
+// holds for every later closeLoop of the object; the bundle adjustments and poseGraphCovariance do not read it, and
+// IIterativeGlobalBackend::setGlobalPcg does not reach closeLoop.  maxIterations < 1 or a tolerance outside (0, 1) throws
+// std::invalid_argument and leaves the setting as it was.  poseGraphPcgStats reports the linear solves of the last closeLoop
+// (zeros without PCG).  An interface of its own, reached with dynamic_cast like IIterativeGlobalBackend, whose mirror it is.
+class IIterativePoseGraphBackend
+{
+  public:
+    virtual void setPoseGraphPcg(bool enable, int maxIterations, double tolerance) = 0;
+    virtual GlobalPcgStats poseGraphPcgStats() const = 0;
+    virtual ~IIterativePoseGraphBackend() = default;
+};
 // extension: a loss function on the edges of closeLoop (mslam_hip_set_pose_graph_loss): kind 0 none (the default), 1 Ceres's
 // HuberLoss(scale), 2 CauchyLoss(scale), scale in the unit of the weighted residual of an edge.  It holds for every later
 // closeLoop of the object, with either linear solver; the bundle adjustments do not read it, and IRobustBackend::setLoss does not
