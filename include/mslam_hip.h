@@ -435,6 +435,76 @@ typedef struct
 } mslam_hip_pnp_view;
 int mslam_hip_get_pnp_view(mslam_hip_ctx* ctx, mslam_hip_pnp_view* view);
 
+/* ---- RANSAC rigid alignment of two 3-D point sets (k_align.hip) -----------------------------------------------------------
+ * The least-squares rigid transform between corresponding 3-D points inside a RANSAC loop: the estimator of the metric the
+ * back end minimises (the 3-D difference in the camera frame, mslam_hip_bundle_adjust), where RANSAC PnP estimates the
+ * reprojection error.  The reference tree has no such estimator (nothing to replace, no file:line): this is an extension,
+ * modelled on the fixed-scale Sim3Solver of ORB-SLAM's RGB-D tracking.
+ * src = n x 3 f32 (object / world points), dst = n x 3 f32 (camera-frame points); the result is the proper rotation R and
+ * translation t with dst_i ~ R src_i + t, i.e. world -> camera as in mslam_hip_pnp_ransac, returned as rvec (Rodrigues) and
+ * tvec, 3 doubles each, outputs only: no guess takes part.  inliers (n bytes, may be NULL) is the consensus mask of the best
+ * hypothesis, n_inliers (may be NULL) its size.  max_distance is in the unit of the points (metres in the keyframe store).
+ * Returns MSLAM_HIP_OK, or MSLAM_HIP_E_NO_MODEL when no hypothesis reaches 4 inliers (n = 3 never has a model) with rvec,
+ * tvec and inliers as they were and *n_inliers = 0; MSLAM_HIP_E_INVALID for n < 3, iterations outside 1..4096, a
+ * max_distance that is not > 0 (NaN included) or a NULL ctx, src, dst, rvec or tvec.
+ * Against mslam_hip_pnp_ransac's loop, piece by piece:
+ *   1 sampler          SAME rule (splitmix64 counter streams keyed by (`seed`, hypothesis), a repeated draw is drawn again, more
+ *                      than 64 redraws give no hypothesis), three draws instead of four;
+ *   2 minimal solver   DEVIATES: the closed-form least-squares rigid transform of the three pairs (centroids, then Horn's unit
+ *                      quaternion: the eigenvector of the largest eigenvalue of the 4 x 4 matrix of the cross-covariance, by
+ *                      cyclic Jacobi sweeps), never a reflection.  A sample whose source or destination triple has
+ *                      |a x b|^2 <= 1e-6 |a|^2 |b|^2 (collinear, coincident, NaN) yields no hypothesis;
+ *   3 consensus loop   SAME form: |R src_i + t - dst_i|^2 <= max_distance^2 (a non-finite value is no inlier), a hypothesis
+ *                      replaces the best one only with MORE inliers and more than 3 (the sample's own three points prove
+ *                      nothing), RANSACUpdateNumIters(confidence, outlier share, 3 model points) after every new best one with
+ *                      the confidence of mslam_hip_pnp_set_confidence, hypotheses looked at in order;
+ *   4 final refit      DEVIATES: the same closed form over the inliers of the best hypothesis (the optimum of the sum of squared
+ *                      3-D distances, no iterations, no start), sums in one fixed order.
+ * Two calls on the same input return the same bits.  All arithmetic is f64: + - * / sqrt. */
+int mslam_hip_align_ransac(mslam_hip_ctx* ctx, const float* src, const float* dst, int n, int iterations, double max_distance,
+                           uint64_t seed, double* rvec, double* tvec, uint8_t* inliers, int* n_inliers);
+
+/* Batched device form, the mirror of mslam_hip_pnp_batch_dev: for every frame t >= 1 of the last batch, the matches (frame t ->
+ * frame t-1) whose train keypoint AND query keypoint both have a valid back-projected point become the 3-D / 3-D
+ * correspondences
+ *   src = (float)xyz[t-1][to], dst = (float)xyz[t][from],
+ * in match order, and one alignment per frame (one workgroup each, the problem body of mslam_hip_align_ransac: the same bits,
+ * seed + t as the sampling seed) estimates the pose of camera t in the coordinates of camera t-1.  Frame 0 and every frame
+ * with fewer than 3 correspondences have status 0.  The buffers are allocated on first use.  Results: mslam_hip_align_view. */
+int mslam_hip_align_batch_dev(mslam_hip_ctx* ctx, int iterations, double max_distance, uint64_t seed);
+typedef struct
+{
+    int32_t capacity;          /* per-frame stride of the correspondence arrays (max_keypoints)                      */
+    const double* pose;        /* [max_batch][16]: R row-major (9), t (3), inliers, best hypothesis, status, 0;
+                                * status 1 = a model was found, 0 = none; NULL before the first batch call          */
+    const int32_t* n_points;   /* [max_batch] correspondences of the frame                                           */
+    const float* src_points;   /* [max_batch][capacity][3]                                                           */
+    const float* dst_points;   /* [max_batch][capacity][3]                                                           */
+    const uint8_t* inliers;    /* [max_batch][capacity] consensus mask of the best hypothesis                        */
+    const double* single_pose; /* [16] the same record of the last mslam_hip_align_ransac call; NULL before the first */
+} mslam_hip_align_view;
+/* MSLAM_HIP_E_INVALID until one of the two alignment calls has run. */
+int mslam_hip_get_align_view(mslam_hip_ctx* ctx, mslam_hip_align_view* view);
+
+/* Which estimator gives a tracked row its pose.  Context state, the idiom of mslam_hip_set_guided_match: mslam_hip_track,
+ * mslam_hip_track_window and mslam_hip_track_window_dev read it when they are called.
+ *   MSLAM_HIP_TRACK_POSE_PNP    (default) RANSAC PnP on (landmark, pixel): every entry point enqueues the launches and returns
+ *                               the bits it did before this setting existed; max_distance is ignored;
+ *   MSLAM_HIP_TRACK_POSE_ALIGN  RANSAC rigid alignment on the same correspondences (matches whose keypoint has a valid depth, in
+ *                               match order): src = (float)world[to], dst = (float) the camera-frame point of keypoint `from`,
+ *                               which the depth filter of the call already computes on the device; row r runs the call's
+ *                               `iterations` with seed + r and this setting's max_distance.  reprojection_error is not used
+ *                               (it is still checked), the guess does not reach the estimator and still drives guided
+ *                               matching.  Everything behind the pose record (tracked, the vote, the new entry, the window's
+ *                               event scan, the MSLAM_HIP_E_* rules) is unchanged.
+ * mslam_hip_relocalize has no depth: it runs PnP under either setting.
+ * set returns MSLAM_HIP_E_INVALID for an unknown kind, or for ALIGN with a max_distance that is not > 0, and the setting stays.
+ * get: either output may be NULL. */
+#define MSLAM_HIP_TRACK_POSE_PNP 0
+#define MSLAM_HIP_TRACK_POSE_ALIGN 1
+int mslam_hip_set_track_pose(mslam_hip_ctx* ctx, int kind, double max_distance);
+int mslam_hip_get_track_pose(mslam_hip_ctx* ctx, int* kind, double* max_distance);
+
 /* ---- MinMseTracker::solvePnp (ceres_reprojection_error_pnp.cpp:18-110): min-MSE PnP -----------------------------------
  * The reference's second IPnpAlgorithm: a Ceres Levenberg-Marquardt solve over x = (r, t), r an angle-axis vector and t a
  * translation, of cost = 1/2 sum_i |observed_i - projected_i|^2 with

@@ -14,6 +14,7 @@ There is NO CPU fallback: if the shared library is missing, or no HIP device is 
 raise.  (The directory name has a hyphen, so import it through `__graft_entry__.load_package()`,
 which registers it as module `modular_slam_amd`.)
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -44,6 +45,8 @@ BA_LOSS_NONE, BA_LOSS_HUBER, BA_LOSS_CAUCHY = 0, 1, 2    # mslam_hip_set_ba_loss
 _BA_LOSS_NAMES = {"none": BA_LOSS_NONE, "huber": BA_LOSS_HUBER, "cauchy": BA_LOSS_CAUCHY}
 UNION_DESC_RECENT, UNION_DESC_DISTINCTIVE = 0, 1    # mslam_hip_set_union_descriptor's modes
 _UNION_DESC_NAMES = {"recent": UNION_DESC_RECENT, "distinctive": UNION_DESC_DISTINCTIVE}
+TRACK_POSE_PNP, TRACK_POSE_ALIGN = 0, 1    # mslam_hip_set_track_pose's kinds
+_TRACK_POSE_NAMES = {"pnp": TRACK_POSE_PNP, "align": TRACK_POSE_ALIGN}
 
 # every symbol include/mslam_hip.h declares (tests/test_cabi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -81,6 +84,8 @@ ABI_SYMBOLS = [
     "mslam_hip_pose_graph_covariance",
     "mslam_hip_set_ba_global_pcg", "mslam_hip_get_ba_global_pcg", "mslam_hip_get_ba_global_pcg_stats",
     "mslam_hip_set_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg_stats",
+    "mslam_hip_align_ransac", "mslam_hip_align_batch_dev", "mslam_hip_get_align_view",
+    "mslam_hip_set_track_pose", "mslam_hip_get_track_pose",
 ]
 
 
@@ -140,6 +145,11 @@ def unpack_batch(buf):
 class PnpView(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("pose", C.c_void_p), ("n_points", C.c_void_p), ("object_points", C.c_void_p),
                 ("image_points", C.c_void_p), ("inliers", C.c_void_p)]
+
+
+class AlignView(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("pose", C.c_void_p), ("n_points", C.c_void_p), ("src_points", C.c_void_p),
+                ("dst_points", C.c_void_p), ("inliers", C.c_void_p), ("single_pose", C.c_void_p)]
 
 
 class RelocCandidate(C.Structure):
@@ -550,6 +560,51 @@ class Context:
             return None
         self._chk(rc)
         return r, t, mask.astype(bool)
+
+    # ---- RANSAC rigid alignment of 3-D points (k_align.hip; no reference counterpart) -------------
+    def align_ransac(self, src, dst, max_distance, iterations=100, seed=0, record=False):
+        """dst_i ~ R src_i + t -> (rvec[3], tvec[3], inlier mask[n]) of the world -> camera transform, or None when no
+        hypothesis reached 4 inliers.  max_distance: the inlier bound on |R src + t - dst|, in the points' unit.
+        record=True: a fourth item, the kernel's own record (16 doubles: R row-major, t, inliers, best hypothesis, status, 0)."""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dst, np.float32).reshape(-1, 3)
+        if len(s) != len(d):
+            raise MslamHipError(E_INVALID, "align_ransac: src and dst differ in length")
+        r, t = np.zeros(3, np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(len(s), np.uint8)
+        n_in = C.c_int(0)
+        rc = self.L.mslam_hip_align_ransac(self._h, _p(s), _p(d), len(s), int(iterations), C.c_double(max_distance),
+                                           C.c_uint64(seed), _p(r), _p(t), _p(mask), C.byref(n_in))
+        if rc == E_NO_MODEL:
+            return None
+        self._chk(rc)
+        if record:
+            return r, t, mask.astype(bool), read_device(self, self.align_view().single_pose, (16,), np.float64)
+        return r, t, mask.astype(bool)
+
+    def align_batch_dev(self, max_distance, iterations=100, seed=0):
+        """one alignment per frame t >= 1 of the last batch from its matches and the back-projected points of both frames
+        (after detect_batch_dev, match_batch_dev, backproject_batch_dev); results: align_view()"""
+        self._chk(self.L.mslam_hip_align_batch_dev(self._h, int(iterations), C.c_double(max_distance), C.c_uint64(seed)))
+
+    def align_view(self):
+        v = AlignView()
+        self._chk(self.L.mslam_hip_get_align_view(self._h, C.byref(v)))
+        return v
+
+    def set_track_pose(self, kind, max_distance=0.0):
+        """the estimator behind track / track_window / track_window_dev: "pnp" (default) or "align" with its inlier bound
+        (TRACK_POSE_* are accepted as well); relocalize runs PnP under either"""
+        k = _TRACK_POSE_NAMES.get(kind, kind)
+        if k not in _TRACK_POSE_NAMES.values():
+            raise MslamHipError(E_INVALID, "set_track_pose: %r is not pnp / align" % (kind,))
+        self._chk(self.L.mslam_hip_set_track_pose(self._h, int(k), C.c_double(max_distance)))
+
+    def get_track_pose(self):
+        """-> (kind, max_distance)"""
+        k, d = C.c_int(0), C.c_double(0)
+        self._chk(self.L.mslam_hip_get_track_pose(self._h, C.byref(k), C.byref(d)))
+        return k.value, d.value
 
     # ---- min-MSE PnP (MinMseTracker, ceres_reprojection_error_pnp.cpp:18-110) --------------------
     def pnp_min_mse(self, object_points, image_points, focal=(525.0, 525.0), principal=(319.5, 239.5), rvec=(0, 0, 0),
@@ -2073,6 +2128,11 @@ class HipKeyframeTracker:
     pose (DEVIATES: the reference matches brute force); the relocalisation after a failure has no guess and matches brute
     force.  With process_window the radius has to cover the motion across a window.  None leaves the context's mode alone.
 
+    track_pose = ("align", max_distance): every track / track_window call made here estimates its poses by RANSAC rigid
+    alignment of (world point, camera-frame point) with that inlier bound in metres (Context.set_track_pose; DEVIATES: the
+    reference estimates by PnP); the setting is applied around each call and the context's own comes back afterwards.  The
+    relocalisation after a failure has no depth and runs PnP.  None (the default) leaves the context's setting alone.
+
     loop_closure = True (needs local_ba and a vocabulary loaded into the context, else MslamHipError(E_INVALID)): the call
     site rgbd_feature_frontend.cpp:198-205, `loopDetector->detectLoop(); closeLoop(candidate)`, with the body the reference
     leaves empty.  At every keyframe, after the covisibility edges and local BA: Context.bow_db_query of the frame's
@@ -2200,8 +2260,14 @@ class HipKeyframeTracker:
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
                  pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False,
-                 ba_global_pcg=None, pose_graph_pcg=None):
+                 ba_global_pcg=None, pose_graph_pcg=None, track_pose=None):
         self.ctx = ctx
+        if track_pose is not None:
+            if len(track_pose) != 2 or track_pose[0] not in _TRACK_POSE_NAMES:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: track_pose is None or (\"pnp\" / \"align\", max_distance)")
+            if track_pose[0] == "align" and not float(track_pose[1]) > 0:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: track_pose align needs max_distance > 0")
+        self.track_pose = None if track_pose is None else (track_pose[0], float(track_pose[1]))
         if _pcg_setting(pose_graph_pcg, "HipKeyframeTracker", "pose_graph_pcg") is not None and not loop_closure:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: pose_graph_pcg needs loop_closure (close_loop takes the setting)")
         if _pcg_setting(ba_global_pcg, "HipKeyframeTracker") is not None and not (loop_closure and loop_global_ba):
@@ -2279,6 +2345,20 @@ class HipKeyframeTracker:
         self.frame = 0
         self.window_calls = self.window_computed = self.window_discarded = 0   # process_window's counters
 
+    @contextlib.contextmanager
+    def _track_pose_scope(self):
+        """the tracker's track_pose around one of its own tracking calls; the context's setting comes back afterwards, as
+        close_loop does with the solver settings.  None: the context's setting is left alone."""
+        if self.track_pose is None:
+            yield
+            return
+        before = self.ctx.get_track_pose()
+        self.ctx.set_track_pose(*self.track_pose)
+        try:
+            yield
+        finally:
+            self.ctx.set_track_pose(*before)
+
     def processSensorData(self, desc, xy, depth):
         """one frame: descriptors [n, 32], keypoint coordinates [n, 2], depth image [h, w] u16
         -> dict(tracked, n_inliers, rvec, tvec, R, reference, keyframe = the id added or -1, relocalized, step)"""
@@ -2309,9 +2389,10 @@ class HipKeyframeTracker:
                 self.ctx.kf_union(self.LOCAL_MAP_ID, self.local_map, sync=False)   # track's own synchronisation covers it
                 self._local_map_of, rebuilt = self.reference, True
             ref_id = self.LOCAL_MAP_ID
-        res = self.ctx.track(desc, xy, depth, ref_id, vote, new_id, self.factor, self.focal, self.principal, self.ratio,
-                             self.iterations, self.reprojection_error, seed, self.rvec, self.tvec, self.min_matched_points,
-                             self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
+        with self._track_pose_scope():
+            res = self.ctx.track(desc, xy, depth, ref_id, vote, new_id, self.factor, self.focal, self.principal, self.ratio,
+                                 self.iterations, self.reprojection_error, seed, self.rvec, self.tvec, self.min_matched_points,
+                                 self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
         if rebuilt:
             self.ctx.sync()   # a union that did not fit max_keypoints left an empty entry: it surfaces here as E_CAPACITY
         out = dict(tracked=bool(res["tracked"]), n_inliers=res["n_inliers"], keyframe=-1, relocalized=False, step=res)
@@ -2375,10 +2456,11 @@ class HipKeyframeTracker:
                     self.ctx.kf_union(self.LOCAL_MAP_ID, self.local_map, sync=False)   # the call's own synchronisation covers it
                     self._local_map_of, rebuilt = self.reference, True
                 ref_id = self.LOCAL_MAP_ID
-            recs, first = self.ctx.track_window(descs[i:i + S], xys[i:i + S], depths[i:i + S], ref_id, vote, new_id, pos, self.factor,
-                                                self.focal, self.principal, self.ratio, self.iterations, self.reprojection_error,
-                                                seed, self.rvec, self.tvec, self.min_matched_points,
-                                                self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
+            with self._track_pose_scope():
+                recs, first = self.ctx.track_window(descs[i:i + S], xys[i:i + S], depths[i:i + S], ref_id, vote, new_id, pos,
+                                                    self.factor, self.focal, self.principal, self.ratio, self.iterations,
+                                                    self.reprojection_error, seed, self.rvec, self.tvec, self.min_matched_points,
+                                                    self.new_keyframe_min_landmarks, self.z_max, with_entry=True)
             if rebuilt:
                 self.ctx.sync()   # a union that did not fit max_keypoints left an empty entry: it surfaces here as E_CAPACITY
             n_acc = min(first + 1, S)

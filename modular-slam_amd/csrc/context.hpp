@@ -154,6 +154,21 @@ struct mslam_hip_ctx
     int pnp1_n_cap = 0, pnp1_it_cap = 0;
     // single-problem min-MSE PnP scratch (mslam_hip_pnp_min_mse): [obj | img | pose | info | n] in one block, grown on demand
     mslam::DevBuf<double> d_mse1;
+    // RANSAC rigid alignment (k_align.hip).  Single problem (mslam_hip_align_ransac): scratch grown on demand; batched
+    // (mslam_hip_align_batch_dev): allocated on first use
+    mslam::DevBuf<float> d_align1_src, d_align1_dst;
+    mslam::DevBuf<double> d_align1_hyp, d_align1_out;
+    mslam::DevBuf<int32_t> d_align1_counts;
+    mslam::DevBuf<uint8_t> d_align1_mask;
+    int align1_n_cap = 0, align1_it_cap = 0;
+    mslam::DevBuf<float> d_align_src, d_align_dst;
+    mslam::DevBuf<int32_t> d_align_n, d_align_counts;
+    mslam::DevBuf<double> d_align_hyp, d_align_out;
+    mslam::DevBuf<uint8_t> d_align_mask;
+    int align_iterations = 0;
+    // mslam_hip_set_track_pose: read by mslam_hip_track and mslam_hip_track_window[_dev] when they are called
+    int track_pose_kind = MSLAM_HIP_TRACK_POSE_PNP;
+    double track_align_distance = 0.0;
     bool pnp_attr_set = false; // the > 64 KB dynamic-LDS attribute of the PnP kernels, per context (= per device)
     // bundle adjustment (mslam_hip_bundle_adjust, k_ba.hip), grown on demand: every device array of one solve, and the
     // mapped termination word the host reads between batches of iterations
@@ -280,6 +295,24 @@ struct PnpBatchLaunch
 int pnp_launch_batch(mslam_hip_ctx* c, const PnpBatchLaunch& l);
 void pnp_rotation_to_rvec(const double R[9], double rvec[3]);
 void pnp_rvec_to_rotation(const double rvec[3], double R[9]); // the R0 the PnP launch makes of its guess
+
+// k_align.hip for k_reloc.hip: k_align_ransac_batch on caller-owned device arrays, addressed as PnpBatchLaunch's are (src /
+// dst / mask at p * cap, hyp / counts at p * iterations, out[p * 16 ..], seed + p).  Enqueued on c->stream.
+struct AlignBatchLaunch
+{
+    const float* src;
+    const float* dst;
+    const int32_t* n; // [n_problems]
+    int n_problems, cap;
+    int iterations;
+    double max_distance;
+    unsigned long long seed;
+    double* hyp;
+    int32_t* counts;
+    uint8_t* mask;
+    double* out;
+};
+int align_launch_batch(mslam_hip_ctx* c, const AlignBatchLaunch& l);
 } // namespace mslam
 
 // api.hip: uploads the ratio-test table of `ratio` unless it is the cached one (not part of the C ABI)

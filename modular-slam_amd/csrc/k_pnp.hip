@@ -22,6 +22,7 @@
 // whole workgroup, and the refinement's normal equations are reduced in a fixed order (bit-reproducible).
 // All arithmetic is f64: + - * / sqrt and include/mslam_sincos.h.
 #include "context.hpp"
+#include "ransac_common.hpp"
 #include "../../include/mslam_sincos.h"
 
 #include <algorithm>
@@ -50,30 +51,6 @@ struct PnpArgs
     uint8_t* mask;   // [n]
     double* out;     // R[9], t[3], n_inliers, best hypothesis, status
 };
-
-__device__ __forceinline__ unsigned long long splitmix(unsigned long long& x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-struct V3
-{
-    double x, y, z;
-};
-__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3 mulR(const double* R, V3 p)
-{
-    return v3(R[0] * p.x + R[1] * p.y + R[2] * p.z, R[3] * p.x + R[4] * p.y + R[5] * p.z, R[6] * p.x + R[7] * p.y + R[8] * p.z);
-}
 
 // orthonormal frame of a triangle: e1 along (b - a), e3 normal, e2 = e3 x e1; false when degenerate
 __device__ bool tri_frame(V3 a, V3 b, V3 c, V3& e1, V3& e2, V3& e3)
@@ -263,28 +240,6 @@ __device__ bool p3p_hypothesis(const Cam& k, const V3* P, const double* uv, doub
     return found;
 }
 
-// OpenCV's RANSACUpdateNumIters(p, ep, modelPoints, maxIters) (calib3d/src/ptsetreg.cpp): the number of samples after which
-// an all-inlier sample has been drawn with probability p when a share ep of the points are outliers
-__device__ __forceinline__ int ransac_update_iters(double p, double ep, int model_points, int max_iters)
-{
-    if(!(p > 0.0) || !(p < 1.0))
-        return max_iters; // no early exit asked for
-    ep = fmax(ep, 0.0);
-    ep = fmin(ep, 1.0);
-    double num = fmax(1.0 - p, 2.2250738585072014e-308);
-    double w = 1.0 - ep, wm = 1.0;
-    for(int i = 0; i < model_points; ++i)
-        wm *= w; // pow(1 - ep, modelPoints) for a small integer exponent, in a fixed order
-    double denom = 1.0 - wm;
-    if(denom < 2.2250738585072014e-308)
-        return 0;
-    num = log(num);
-    denom = log(denom);
-    if(denom >= 0 || -num >= max_iters * (-denom))
-        return max_iters;
-    return (int)rint(num / denom); // cvRound
-}
-
 // modelPoints of the iteration-count formula: cv::solvePnPRansac called with the default flags (SOLVEPNP_ITERATIVE,
 // cv_ransac_pnp.cpp:56-57) samples 5 points per hypothesis when there are more than 4 (its minimal solver is then EPnP), so its
 // loop ends after log(1 - p) / log(1 - w^5) samples.  This library's hypotheses come from 3 + 1 points (P3P), but the stopping
@@ -292,44 +247,10 @@ __device__ __forceinline__ int ransac_update_iters(double p, double ep, int mode
 // outliers).  So does the consensus floor of the same loop: a hypothesis needs more than modelPoints - 1 inliers, i.e. at
 // least 5, to become the best one, and with no such hypothesis there is no model.
 constexpr int kPnpModelPoints = 5;
-constexpr int kPnpThreads = 256;
-
-// fixed-order workgroup sum of `cnt` doubles per thread (acc[cnt]); the totals land in red[0..cnt).  Butterfly inside
-// each wave (cross-lane moves, no memory), then the four wave totals are added in wave order: one barrier pair instead
-// of a nine-barrier LDS tree, and 1.2 KB of LDS instead of 57 KB (which held the batched kernel to 2 workgroups per CU).
-constexpr int kPnpRed = 32 + 28 * (kPnpThreads / 64); // doubles of LDS: totals [32] + per-wave partials [28][waves]
+constexpr int kPnpThreads = kRansacThreads;
+constexpr int kPnpRed = kRansacRed;          // wg_sum's doubles of LDS (ransac_common.hpp)
 constexpr int kPnpLdsPts = 2048;                      // points staged in LDS for the scoring loop (40 KB)
 constexpr int kPnpLdsHyp = 256;                       // hypotheses (12 doubles + a count) kept in LDS up to this many
-template <int CNT>
-__device__ __forceinline__ void wg_sum(double* acc, double* red, int tid)
-{
-    const int lane = tid & 63, wave = tid >> 6;
-    constexpr int W = kPnpThreads / 64;
-    // CNT independent butterflies, fully unrolled: the cross-lane moves of different sums overlap
-#pragma unroll
-    for(int o = 32; o > 0; o >>= 1)
-    {
-#pragma unroll
-        for(int j = 0; j < CNT; ++j)
-            acc[j] += __shfl_xor(acc[j], o);
-    }
-    if(lane == 0)
-    {
-#pragma unroll
-        for(int j = 0; j < CNT; ++j)
-            red[32 + j * W + wave] = acc[j];
-    }
-    __syncthreads();
-    if(tid < CNT)
-    {
-        double t = red[32 + tid * W];
-#pragma unroll
-        for(int w = 1; w < W; ++w)
-            t += red[32 + tid * W + w];
-        red[tid] = t;
-    }
-    __syncthreads();
-}
 
 // one problem, one workgroup (shared by the single-problem kernel and the batched one)
 __device__ __forceinline__ void pnp_problem(const PnpArgs& a, double* red /* LDS [kPnpRed] doubles + [kPnpLdsPts][5] floats */)

@@ -94,6 +94,9 @@ __global__ __launch_bounds__(256) void k_reloc_gather_desc(const uint8_t* __rest
 // row p (one workgroup): its matches whose keypoint is not masked out become correspondences, in match order:
 // object = (float) world point of landmark `to` of the row's entry, image = xy of keypoint `from`.  Rows are from_stride
 // keypoints and slot_stride list positions apart (0: shared); n_kp == nullptr: every row has nq keypoints.
+// ALIGN (mslam_hip_set_track_pose): the destination of a pair is the camera-frame point of keypoint `from` (cam_xyz, f64 x 3,
+// rows from_stride keypoints apart) cast to float, written to dst (x 3); img is not written.
+template <bool ALIGN>
 __global__ __launch_bounds__(256) void k_reloc_corr(const int32_t* __restrict__ mfrom, const int32_t* __restrict__ mto,
                                                     const int32_t* __restrict__ mcount, const int32_t* __restrict__ g_cnt,
                                                     const int32_t* __restrict__ slots, int slot_stride,
@@ -101,7 +104,8 @@ __global__ __launch_bounds__(256) void k_reloc_corr(const int32_t* __restrict__ 
                                                     const float* __restrict__ xy_all, const uint8_t* __restrict__ valid_all,
                                                     long long from_stride, const int32_t* __restrict__ n_kp, int nq,
                                                     float* __restrict__ obj, float* __restrict__ img, uint8_t* __restrict__ mask,
-                                                    int32_t* __restrict__ n_out)
+                                                    int32_t* __restrict__ n_out, const double* __restrict__ cam_xyz,
+                                                    float* __restrict__ dst)
 {
     __shared__ uint32_t wsum[4];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -138,12 +142,19 @@ __global__ __launch_bounds__(256) void k_reloc_corr(const int32_t* __restrict__ 
             const size_t o = row + running + pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); // < row + m <= row + S
             const double* P = world + (size_t)to * 3;
             obj[o * 3] = (float)P[0], obj[o * 3 + 1] = (float)P[1], obj[o * 3 + 2] = (float)P[2];
-            img[o * 2] = xy[(size_t)from * 2], img[o * 2 + 1] = xy[(size_t)from * 2 + 1];
+            if constexpr(ALIGN)
+            {
+                const double* Q = cam_xyz + ((size_t)p * from_stride + (size_t)from) * 3;
+                dst[o * 3] = (float)Q[0], dst[o * 3 + 1] = (float)Q[1], dst[o * 3 + 2] = (float)Q[2];
+            }
+            else
+                img[o * 2] = xy[(size_t)from * 2], img[o * 2 + 1] = xy[(size_t)from * 2 + 1];
         }
         running += tot;
         __syncthreads();
     }
-    // fewer than 4 correspondences: the PnP kernel reports "no model" without touching the mask
+    // fewer than 4 correspondences: the PnP kernel reports "no model" without touching the mask (the alignment kernel does
+    // so below 3 and writes every byte at 3)
     if(running < 4 && tid < (int)running)
         mask[row + tid] = 0;
     if(tid == 0)
@@ -572,10 +583,10 @@ namespace
 // where the sequence's arrays lie in the arena, each 256-byte aligned
 struct SeqArena
 {
-    size_t gdesc, gcnt, idx0, idx1, dist0, dist1, mfrom, mto, mcount, obj, img, ncorr, mask, hyp, counts, out, cells, list, ldesc, bytes;
+    size_t gdesc, gcnt, idx0, idx1, dist0, dist1, mfrom, mto, mcount, obj, img, ncorr, mask, hyp, counts, out, cells, list, ldesc, adst, bytes;
 };
 
-SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from)
+SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from, bool align)
 {
     size_t off = 0;
     auto carve = [&](size_t bytes) {
@@ -593,21 +604,23 @@ SeqArena seq_carve(int rows, size_t S, int iterations, bool one_slot, bool guide
     // the guided stage's lists come last: without them every array lies where it always did
     a.cells = carve(guided ? R * (kGuidedMaxCells + 1) * 4 : 0), a.list = carve(guided ? R * (size_t)std::max(cap_from, 1) * 16 : 0);
     a.ldesc = carve(guided ? R * (size_t)std::max(cap_from, 1) * 32 : 0);
+    a.adst = carve(align ? RS * 12 : 0); // the alignment's destination points, behind everything else for the same reason
     a.bytes = off;
     return a;
 }
 } // namespace
 
-size_t mslam::seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from)
+size_t mslam::seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided, int cap_from, bool align)
 {
-    return seq_carve(rows, S, iterations, one_slot, guided, cap_from).bytes;
+    return seq_carve(rows, S, iterations, one_slot, guided, cap_from, align).bytes;
 }
 
 int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* out)
 {
     RelocState* r = c->reloc;
     const int K = c->p.max_keypoints, R = a.rows, S = (int)a.S;
-    const SeqArena o = seq_carve(R, a.S, a.iterations, a.one_slot, a.guided, a.cap_from);
+    const bool align = a.align_distance > 0 && a.cam_xyz;
+    const SeqArena o = seq_carve(R, a.S, a.iterations, a.one_slot, a.guided, a.cap_from, align);
     hipStream_t s = c->stream;
     int32_t* g_cnt = reinterpret_cast<int32_t*>(A + o.gcnt);
     {
@@ -682,11 +695,34 @@ int mslam::seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* A, SeqDev* o
     uint8_t* d_mask = A + o.mask;
     {
         StageScope ts(c, "reloc_corr");
-        hipLaunchKernelGGL(k_reloc_corr, dim3((unsigned)R), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, a.slots,
-                           a.one_slot ? 0 : 1, r->d_world, K, S, a.xy, a.valid, (long long)a.from_stride, a.from_cnt, a.n_from_fixed,
-                           d_obj, d_img, d_mask, d_ncorr);
+        if(align)
+            hipLaunchKernelGGL(k_reloc_corr<true>, dim3((unsigned)R), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, a.slots,
+                               a.one_slot ? 0 : 1, r->d_world, K, S, a.xy, a.valid, (long long)a.from_stride, a.from_cnt,
+                               a.n_from_fixed, d_obj, d_img, d_mask, d_ncorr, a.cam_xyz, reinterpret_cast<float*>(A + o.adst));
+        else
+            hipLaunchKernelGGL(k_reloc_corr<false>, dim3((unsigned)R), dim3(256), 0, s, q.from_idx, q.to_idx, q.n_out, g_cnt, a.slots,
+                               a.one_slot ? 0 : 1, r->d_world, K, S, a.xy, a.valid, (long long)a.from_stride, a.from_cnt,
+                               a.n_from_fixed, d_obj, d_img, d_mask, d_ncorr, nullptr, nullptr);
     }
     MSLAM_CHK(c, hipGetLastError());
+    if(align)
+    {
+        AlignBatchLaunch l{};
+        l.src = d_obj, l.dst = reinterpret_cast<const float*>(A + o.adst), l.n = d_ncorr;
+        l.n_problems = R, l.cap = S;
+        l.iterations = a.iterations, l.max_distance = a.align_distance;
+        l.seed = a.seed; // problem r samples with seed + r
+        l.hyp = reinterpret_cast<double*>(A + o.hyp);
+        l.counts = reinterpret_cast<int32_t*>(A + o.counts);
+        l.mask = d_mask;
+        l.out = reinterpret_cast<double*>(A + o.out);
+        const int rc = align_launch_batch(c, l);
+        if(rc)
+            return rc;
+        out->g_cnt = g_cnt, out->mfrom = q.from_idx, out->mto = q.to_idx, out->mcount = q.n_out, out->ncorr = d_ncorr;
+        out->mask = d_mask, out->pnp_out = l.out, out->S = S;
+        return MSLAM_HIP_OK;
+    }
     PnpBatchLaunch l{};
     l.obj = d_obj, l.img = d_img, l.n = d_ncorr;
     l.n_problems = R, l.cap = S;
@@ -757,7 +793,9 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
     const size_t up = extra_bytes ? off_extra + extra_bytes : off_valid + (valid ? (size_t)n : 0);
     // ---- device arena: the sequence's arrays, then a hook's own
     const bool guided = seq_guided(c, use_extrinsic_guess);
-    const size_t o_extra = seq_arena_bytes(n_cand, S, iterations, false, guided, n);
+    // (a call with depth — tracking, whose after_upload hook leaves the camera-frame points — may estimate by alignment)
+    const double align_distance = hooks && hooks->after_upload ? seq_align_distance(c) : 0.0;
+    const size_t o_extra = seq_arena_bytes(n_cand, S, iterations, false, guided, n, align_distance > 0);
     // ---- result block (mapped): [best, pad | RelocRes[64] | pair_from P x S | pair_to P x S | inliers P x S]
     const size_t res_head = 16 + kRelocMaxCand * sizeof(RelocRes);
     const size_t res_extra = (res_head + (want_pairs ? PS * 9 : 0) + 15) & ~(size_t)15; // a hook's own results
@@ -799,6 +837,7 @@ int mslam::reloc_run(mslam_hip_ctx* c, const uint8_t* desc, const float* xy, con
             if(rc)
                 return rc;
             a.valid = dev.valid;
+            a.cam_xyz = dev.cam_xyz, a.align_distance = dev.cam_xyz ? align_distance : 0.0;
         }
     }
     rc = seq_enqueue(c, a, r->d_arena, &dev.seq);

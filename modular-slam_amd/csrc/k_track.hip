@@ -93,6 +93,7 @@ int track_after_upload(mslam_hip_ctx* c, void* user, RelocDev& d)
     }
     MSLAM_CHK(c, hipGetLastError());
     d.valid = t->d_valid = valid; // the depth filter of :317-334 is the matcher's mask
+    d.cam_xyz = t->d_xyz;         // ... and its points are the alignment's destinations (mslam_hip_set_track_pose)
     return MSLAM_HIP_OK;
 }
 

@@ -179,7 +179,8 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     const size_t up = host ? u_depth + al256((size_t)S * npx * 2) : u_desc;
     // ---- device arena: the sequence's arrays, then the window's own
     const bool guided = seq_guided(c, p.use_guess);
-    size_t off = seq_arena_bytes(S, Srow, p.iterations, true, guided, w.cap_from);
+    const double align_distance = seq_align_distance(c);
+    size_t off = seq_arena_bytes(S, Srow, p.iterations, true, guided, w.cap_from, align_distance > 0);
     auto carve = [&](size_t bytes) {
         const size_t o = off;
         off += al256(bytes);
@@ -237,6 +238,7 @@ int window_enqueue(mslam_hip_ctx* c, const WindowSource& w, const WindowParams& 
     a.use_guess = p.use_guess, a.rvec = p.rvec, a.tvec = p.tvec;
     a.iterations = p.iterations, a.reprojection_error = p.reprojection_error, a.seed = p.seed;
     a.guided = guided;
+    a.cam_xyz = d_xyz, a.align_distance = align_distance;
     SeqDev d{};
     rc = seq_enqueue(c, a, A, &d);
     if(rc)

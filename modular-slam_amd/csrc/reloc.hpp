@@ -130,10 +130,19 @@ struct SeqArgs
     // seq_guided(): the guided stage (k_match_guided.hip) in place of the brute-force matcher, every row projecting with
     // the guess
     bool guided = false;
+    // mslam_hip_set_track_pose's ALIGN (align_distance > 0): the rows' poses come from RANSAC rigid alignment (k_align.hip) of
+    // (world point of `to`, camera-frame point of `from`) instead of PnP; cam_xyz: x 3 f64, rows from_stride keypoints apart
+    const double* cam_xyz = nullptr;
+    double align_distance = 0;
 };
 
 // the mode of mslam_hip_set_guided_match applies to a call that has a guess: there is no pose to project with otherwise
 inline bool seq_guided(const mslam_hip_ctx* c, int use_guess) { return c->guided_radius > 0.0 && use_guess != 0; }
+// the setting of mslam_hip_set_track_pose for a tracking call (which has the camera-frame points); 0: PnP
+inline double seq_align_distance(const mslam_hip_ctx* c)
+{
+    return c->track_pose_kind == MSLAM_HIP_TRACK_POSE_ALIGN ? c->track_align_distance : 0.0;
+}
 
 // what the sequence leaves on the device; rows of the per-row arrays are S entries apart
 struct SeqDev
@@ -149,8 +158,8 @@ inline size_t seq_row_stride(int n_upper) // an entry of at most n_upper landmar
     return al256((size_t)(n_upper > 1 ? n_upper : 1));
 }
 // a multiple of 256: a caller's own arrays follow.  guided: with the cell offsets and the keypoint list (cap_from entries of coordinates, index and descriptor) of
-// every row behind the sequence's own arrays, which keep their places
-size_t seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided = false, int cap_from = 0);
+// every row behind the sequence's own arrays, which keep their places; align: with the rows' destination points behind those
+size_t seq_arena_bytes(int rows, size_t S, int iterations, bool one_slot, bool guided = false, int cap_from = 0, bool align = false);
 // enqueues the sequence on c->stream, its arrays carved from `arena`; sets c->last_match_kernel
 int seq_enqueue(mslam_hip_ctx* c, const SeqArgs& a, uint8_t* arena, SeqDev* out);
 
@@ -161,6 +170,7 @@ struct RelocDev
     const float* xy = nullptr;     // n x 2
     int n = 0;
     const uint8_t* valid = nullptr; // the mask k_reloc_corr applies; after_upload may point it at a mask it produces
+    const double* cam_xyz = nullptr; // n x 3 camera-frame points: after_upload of a call that has depth sets it (tracking)
     const uint8_t* extra_up = nullptr; // the hook's own upload block, on the device
     uint8_t* extra_arena = nullptr;    // the hook's own device scratch
     uint8_t *extra_res = nullptr, *h_extra_res = nullptr; // the hook's own part of the mapped result block (device / host address)

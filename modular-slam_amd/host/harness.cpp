@@ -32,6 +32,12 @@
 //        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> --local-map <depth> --distinct
 //                                    the local-map loop with IDistinctiveLocalMap::setUnionDescriptor(1): every landmark of the
 //                                    local map carries its most distinctive descriptor instead of the most recent one
+//        mslam_harness <plugin.so> --track <vocabulary.dbow3> <scene> [...] --align <max_distance>
+//                                    any of the loops above with IAlignedKeyframeTracker::setTrackPose(1, max_distance): the
+//                                    tracked pose comes from RANSAC rigid alignment of (landmark, camera-frame point)
+//        mslam_harness <plugin.so> --align <scene>
+//                                    hipRigidAlignerFactory on one scene (text: `n iterations max_distance seed`, then n lines
+//                                    of source xyz and target xyz): prints R, t and the inlier count, or `align none`
 //        mslam_harness <plugin.so> --ba <scene>
 //        mslam_harness <plugin.so> --ba-global <scene>
 //                                    hipBundleAdjustBackendFactory on one bundle-adjustment scene: the summary, then every
@@ -215,6 +221,53 @@ int main(int argc, char** argv)
                         result->pose.position.x(), result->pose.position.y(), result->pose.position.z(),
                         result->pose.orientation.w(), result->pose.orientation.x(), result->pose.orientation.y(),
                         result->pose.orientation.z(), inl);
+            return 0;
+        }
+        if(argc == 4 && std::strcmp(argv[2], "--align") == 0)
+        {
+            std::ifstream in(argv[3]);
+            long long n = 0, iterations = 0;
+            unsigned long long seed = 0;
+            double maxDistance = 0;
+            in >> n >> iterations >> maxDistance >> seed;
+            std::vector<mslam::Vector3> source, target;
+            for(long long i = 0; in && i < n; ++i)
+            {
+                std::string tok[6];
+                double v[6];
+                for(int k = 0; k < 6; ++k)
+                {
+                    in >> tok[k];
+                    v[k] = std::strtod(tok[k].c_str(), nullptr); // (reads "nan" too, which operator>> does not)
+                }
+                source.emplace_back(v[0], v[1], v[2]);
+                target.emplace_back(v[3], v[4], v[5]);
+            }
+            if(!in || n < 0)
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                return 5;
+            }
+            auto makeAligner = mslam::loadFactoryMethod<mslam::IRigidAligner>(argv[1], "hipRigidAlignerFactory");
+            if(!makeAligner)
+                return 3;
+            std::unique_ptr<mslam::IRigidAligner> aligner = makeAligner();
+            const auto result = aligner->align(source, target, maxDistance, static_cast<int>(iterations), seed);
+            if(!result)
+            {
+                std::printf("align none\n");
+                return 0;
+            }
+            std::size_t inl = 0;
+            for(bool b : result->inliers)
+                inl += b ? 1 : 0;
+            std::printf("align R");
+            for(double r : result->R)
+                std::printf(" %.17g", r);
+            std::printf(" t %.17g %.17g %.17g inliers %zu mask ", result->t[0], result->t[1], result->t[2], inl);
+            for(bool b : result->inliers)
+                std::putchar(b ? '1' : '0');
+            std::printf("\n");
             return 0;
         }
         const bool baPcg = (argc == 5 || argc == 6) && std::strcmp(argv[4], "--pcg") == 0 && std::strcmp(argv[2], "--ba-global") == 0;
@@ -1032,13 +1085,24 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        // --track <vocabulary> <scene> followed by any of: --local-map <depth>, --guided <radius>, --distinct
+        // --track <vocabulary> <scene> followed by any of: --local-map <depth>, --guided <radius>, --distinct, --align <max_distance>
         bool trackArgs = argc >= 5 && std::strcmp(argv[2], "--track") == 0;
         int mapDepthArg = -1;
         double guidedRadius = 0.0;
         bool distinct = false;
+        double alignDistance = 0.0;
         for(int k = 5; trackArgs && k < argc;)
         {
+            if(k + 1 < argc && std::strcmp(argv[k], "--align") == 0)
+            {
+                alignDistance = std::atof(argv[k + 1]), k += 2;
+                if(!(alignDistance > 0.0))
+                {
+                    std::fprintf(stderr, "--align takes a max_distance > 0, not %s\n", argv[k - 1]);
+                    return 2;
+                }
+                continue;
+            }
             if(std::strcmp(argv[k], "--distinct") == 0)
                 distinct = true, k += 1;
             else if(k + 1 < argc && std::strcmp(argv[k], "--local-map") == 0)
@@ -1069,6 +1133,16 @@ int main(int argc, char** argv)
             }
             if(guidedRadius > 0.0)
                 tracker->setGuidedMatch(guidedRadius);
+            if(alignDistance > 0.0)
+            {
+                auto* aligned = dynamic_cast<mslam::IAlignedKeyframeTracker*>(relocalizer.get());
+                if(!aligned)
+                {
+                    std::fprintf(stderr, "--align needs a plugin that offers IAlignedKeyframeTracker\n");
+                    return 6;
+                }
+                aligned->setTrackPose(1, alignDistance);
+            }
             if(distinct)
             {
                 // --distinct (needs --local-map): the local map carries the most distinctive descriptor of every landmark

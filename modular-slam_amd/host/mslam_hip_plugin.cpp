@@ -624,6 +624,23 @@ class BowDatabase
                 raise(ctx.h, "mslam_hip_set_guided_match", grc);
             guidedSet = guidedRadius > 0.0;
         }
+        // setTrackPose: on the context for this call, the default again behind it (relocalizePose shares the context)
+        struct PoseScope
+        {
+            mslam_hip_ctx* h;
+            bool on;
+            ~PoseScope()
+            {
+                if(on)
+                    mslam_hip_set_track_pose(h, MSLAM_HIP_TRACK_POSE_PNP, 0.0);
+            }
+        } poseScope{ctx.h, trackPoseKind != MSLAM_HIP_TRACK_POSE_PNP};
+        if(poseScope.on)
+        {
+            const int prc = mslam_hip_set_track_pose(ctx.h, trackPoseKind, trackPoseDistance);
+            if(prc != MSLAM_HIP_OK)
+                raise(ctx.h, "mslam_hip_set_track_pose", prc);
+        }
         mslam_hip_track_result out;
         // the matcher's ratio and OpenCvRansacPnp's operating point, as relocalizePose (orb_feature.cpp:101, cv_ransac_pnp.cpp:56-57)
         const int rc = mslam_hip_track(ctx.h, desc.data(), xy.data(), cap, depth, width, height, camera.factor, camera.focal.x(),
@@ -678,6 +695,15 @@ class BowDatabase
             throw std::invalid_argument("setGuidedMatch: the radius is NaN or maxDistance lies outside 0..256");
         guidedRadius = radius > 0.0 ? radius : 0.0;
         guidedMaxDistance = maxDistance;
+    }
+
+    void setTrackPose(int kind, double maxDistance)
+    {
+        if((kind != MSLAM_HIP_TRACK_POSE_PNP && kind != MSLAM_HIP_TRACK_POSE_ALIGN) ||
+           (kind == MSLAM_HIP_TRACK_POSE_ALIGN && !(maxDistance > 0.0)))
+            throw std::invalid_argument("setTrackPose: the kind is neither 0 (PnP) nor 1 (alignment), or alignment without a maxDistance > 0");
+        trackPoseKind = kind;
+        trackPoseDistance = kind == MSLAM_HIP_TRACK_POSE_ALIGN ? maxDistance : 0.0;
     }
 
     void setUnionDescriptor(int mode)
@@ -761,6 +787,8 @@ class BowDatabase
     double guidedRadius = 0.0; // setGuidedMatch; applied to the context by the next tracking call, with that call's frame size
     int guidedMaxDistance = 256;
     bool guidedSet = false;    // the context's mode is on
+    int trackPoseKind = MSLAM_HIP_TRACK_POSE_PNP; // setTrackPose; applied to the context around every tracking call
+    double trackPoseDistance = 0.0;
     int unionDescriptor = MSLAM_HIP_UNION_DESC_RECENT; // setUnionDescriptor; applied to the context by every buildLocalMap
     std::vector<float> xy;
     KeyframePtr lastLoop;
@@ -772,6 +800,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
                           public IKeyframeTracker,
                           public ILocalMapTracker,
                           public IDistinctiveLocalMap,
+                          public IAlignedKeyframeTracker,
                           public ILandmarkFuser,
                           public IMultiLandmarkFuser,
                           public IObservationRemover,
@@ -830,6 +859,7 @@ class HipOrbRelocalizer : public IOrbRelocalizer,
     }
     int buildLocalMap(const std::vector<BowDatabase::KeyframePtr>& members) override { return db->buildLocalMap(members); }
     void setUnionDescriptor(int mode) override { db->setUnionDescriptor(mode); }
+    void setTrackPose(int kind, double maxDistance) override { db->setTrackPose(kind, maxDistance); }
     LandmarkFusion fuseLandmarks(BowDatabase::KeyframePtr keepEntry, BowDatabase::KeyframePtr dropEntry, const double R[9],
                                  const double t[3], const LandmarkFuseParams& params) override
     {
@@ -947,6 +977,57 @@ class HipRansacPnp : public ISlam3dPnp
   private:
     Ctx ctx;
     std::vector<float> obj, img;
+    std::vector<std::uint8_t> mask;
+};
+
+// RANSAC rigid alignment of two 3-D point sets (mslam_hip_align_ransac): no reference counterpart.  The points are cast to
+// float as the PnP adapter casts its landmarks; the rotation comes back from the call's Rodrigues vector.
+class HipRigidAligner : public IRigidAligner
+{
+  public:
+    std::optional<RigidAlignment> align(const std::vector<Vector3>& source, const std::vector<Vector3>& target, double maxDistance,
+                                        int iterations, std::uint64_t seed) override
+    {
+        if(source.size() != target.size() || source.size() < 3)
+            return std::nullopt;
+        const std::size_t n = source.size();
+        src.resize(3 * n);
+        dst.resize(3 * n);
+        for(std::size_t i = 0; i < n; ++i)
+        {
+            src[3 * i] = static_cast<float>(source[i].x()), src[3 * i + 1] = static_cast<float>(source[i].y());
+            src[3 * i + 2] = static_cast<float>(source[i].z());
+            dst[3 * i] = static_cast<float>(target[i].x()), dst[3 * i + 1] = static_cast<float>(target[i].y());
+            dst[3 * i + 2] = static_cast<float>(target[i].z());
+        }
+        mask.assign(n, 0);
+        double rvec[3] = {0, 0, 0}, tvec[3] = {0, 0, 0};
+        int nInliers = 0;
+        ctx.ensure(0, 0);
+        const int rc = mslam_hip_align_ransac(ctx.h, src.data(), dst.data(), static_cast<int>(n), iterations, maxDistance, seed, rvec,
+                                              tvec, mask.data(), &nInliers);
+        if(rc == MSLAM_HIP_E_NO_MODEL)
+            return std::nullopt;
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, "mslam_hip_align_ransac", rc);
+        RigidAlignment out;
+        // Rodrigues: R = I + sin(a) K + (1 - cos(a)) K^2, K the cross-product matrix of the unit axis
+        const double a = std::sqrt(rvec[0] * rvec[0] + rvec[1] * rvec[1] + rvec[2] * rvec[2]);
+        const double kx = a > 0 ? rvec[0] / a : 0, ky = a > 0 ? rvec[1] / a : 0, kz = a > 0 ? rvec[2] / a : 0;
+        const double c = std::cos(a), s = std::sin(a), v = 1 - c;
+        const double R[9] = {c + kx * kx * v, kx * ky * v - kz * s, kx * kz * v + ky * s, ky * kx * v + kz * s, c + ky * ky * v,
+                             ky * kz * v - kx * s, kz * kx * v - ky * s, kz * ky * v + kx * s, c + kz * kz * v};
+        std::copy(R, R + 9, out.R);
+        std::copy(tvec, tvec + 3, out.t);
+        out.inliers.resize(n);
+        for(std::size_t i = 0; i < n; ++i)
+            out.inliers[i] = mask[i] != 0;
+        return out;
+    }
+
+  private:
+    Ctx ctx;
+    std::vector<float> src, dst;
     std::vector<std::uint8_t> mask;
 };
 
@@ -1313,6 +1394,7 @@ std::unique_ptr<IOrbRelocalizer> createHipOrbRelocalizer() { return std::make_un
 std::unique_ptr<IOrbLoopDetector> createHipLoopDetector() { return std::make_unique<HipLoopDetector>(); }
 std::unique_ptr<ISlam3dPnp> createHipRansacPnp() { return std::make_unique<HipRansacPnp>(); }
 std::unique_ptr<ISlam3dPnp> createHipMinMseTracker() { return std::make_unique<HipMinMseTracker>(); }
+std::unique_ptr<IRigidAligner> createHipRigidAligner() { return std::make_unique<HipRigidAligner>(); }
 std::unique_ptr<IBackend> createHipBundleAdjustBackend() { return std::make_unique<HipBundleAdjustBackend>(); }
 
 } // namespace mslam
@@ -1324,4 +1406,5 @@ MSLAM_DLL_ALIAS(mslam::createHipOrbRelocalizer, hipOrbRelocalizerFactory)
 MSLAM_DLL_ALIAS(mslam::createHipLoopDetector, loopDetection) // key used by test/plugin_config.json
 MSLAM_DLL_ALIAS(mslam::createHipRansacPnp, hipRansacPnpFactory)
 MSLAM_DLL_ALIAS(mslam::createHipMinMseTracker, hipMinMseTrackerFactory)
+MSLAM_DLL_ALIAS(mslam::createHipRigidAligner, hipRigidAlignerFactory)
 MSLAM_DLL_ALIAS(mslam::createHipBundleAdjustBackend, hipBundleAdjustBackendFactory)

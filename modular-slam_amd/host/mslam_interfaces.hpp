@@ -512,6 +512,36 @@ class IDistinctiveLocalMap
     virtual ~IDistinctiveLocalMap() = default;
 };
 
+// ---- extension (not in the reference): the tracked pose from RANSAC rigid alignment (mslam_hip_set_track_pose) -------------
+// kind 0 (the default): trackKeyframe / trackLocalMap estimate the pose by RANSAC PnP, the reference's way.  kind 1: by the
+// least-squares rigid transform between the matched landmarks' world points and the keypoints' camera-frame points (which the
+// depth filter of the call computes anyway) inside the same RANSAC loop; maxDistance is the inlier bound in metres.  The model
+// is ORB-SLAM's fixed-scale Sim3Solver.  It applies to every tracking call after this one; relocalizePose has no depth and
+// runs PnP.  Bad input throws std::invalid_argument and leaves the setting as it was.  An interface of its own, reached with
+// dynamic_cast: IKeyframeTracker gains no virtual.
+class IAlignedKeyframeTracker
+{
+  public:
+    virtual void setTrackPose(int kind, double maxDistance) = 0;
+    virtual ~IAlignedKeyframeTracker() = default;
+};
+// ---- extension (not in the reference): RANSAC rigid alignment of two 3-D point sets (mslam_hip_align_ransac) ---------------
+// target_i ~ R source_i + t over corresponding points, at least 3 of them: a proper rotation (row-major) and a translation,
+// the consensus mask of the best hypothesis, or nullopt when no hypothesis reaches 4 inliers.  maxDistance: the inlier bound in
+// the points' unit.  Behind hipRigidAlignerFactory.
+struct RigidAlignment
+{
+    double R[9], t[3];
+    std::vector<bool> inliers;
+};
+class IRigidAligner
+{
+  public:
+    virtual std::optional<RigidAlignment> align(const std::vector<Vector3>& source, const std::vector<Vector3>& target,
+                                                double maxDistance, int iterations = 100, std::uint64_t seed = 0) = 0;
+    virtual ~IRigidAligner() = default;
+};
+
 // ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
 // The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
 // The landmarks of `dropEntry` that duplicate landmarks of `keepEntry` — both projected under one world -> camera pose, each
