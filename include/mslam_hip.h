@@ -1536,6 +1536,82 @@ int mslam_hip_track_window_dev(mslam_hip_ctx* ctx, int first_frame, int n_frames
                                double z_max, mslam_hip_track_window_result* out /* n_frames */, int* first_event,
                                int32_t* vote_counts, int32_t* entry_src, int32_t* entry_kp, int entry_capacity);
 
+/* ---- dense TSDF map that follows the keyframe poses (k_tsdf.hip) ---------------------------------------------------------
+ * An extension: the reference's only dense output is the viewer's pointCloudFromRgbd (src/app/viewer/slam_thread.cpp:125-150),
+ * which back-projects the current frame on the CPU and keeps nothing.  The model here is the volumetric integration of
+ * Curless & Levoy / KinectFusion with BundleFusion's de-integration: a frame can be taken out of the volume at the pose it
+ * was integrated with and put back at a corrected one.  One volume per context, two int32 per voxel: S, the sum of quantised
+ * truncated signed distances, and W, the number of observations.  Integer accumulators make integration an exact,
+ * order-independent add and de-integration its exact inverse, hence the invariant every call keeps:
+ *   the volume equals the integration of the retained frames at their stored poses into a zeroed volume, bit for bit.
+ * One frame (depth u16 [height][width], pose R row-major / t, world -> camera as in mslam_hip_kf_visible, sign s = +-1)
+ * changes voxel (i, j, k) by this rule, all arithmetic f64, every operation rounded on its own, in this order:
+ *   X = ox + ((double)i + 0.5) * voxel                                    (Y, Z alike)
+ *   c_r = ((R[r][0] X + R[r][1] Y) + R[r][2] Z) + t[r];                   skip unless c_2 > 0
+ *   u = (c_0 / c_2) fx + cx;  v = (c_1 / c_2) fy + cy;  uh = u + 0.5;  vh = v + 0.5
+ *   skip unless uh >= 0 && uh < (double)width && vh >= 0 && vh < (double)height             (false for NaN)
+ *   px = (int)floor(uh);  py = (int)floor(vh);  d = (float)depth[py * width + px] * factor  (one f32 multiply, as
+ *                                                                                            mslam_hip_backproject)
+ *   skip unless d > FLT_EPSILON && (double)d <= max_depth
+ *   sdf = (double)d - c_2;  skip if sdf < -trunc
+ *   x = sdf / trunc;  if x > 1 then x = 1;  q = (int)rint(x * 32767.0)                      (round half to even)
+ *   S += s q;  W += s
+ * With at most 32768 frames |S| < 2^30.  Each voxel is owned by one thread, no atomics.  A batch of up to
+ * MSLAM_HIP_TSDF_CHUNK (frame, sign) entries is applied in ONE pass over the volume (every voxel loops over the entries a
+ * conservative per-wave frustum / range test leaves), so re-integrating M frames sweeps the volume ceil(2M / CHUNK) times.
+ *   pointCloudFromRgbd   DEVIATES: a fused, persistent volume instead of a per-frame cloud; no colour.
+ * Surface points (mslam_hip_tsdf_extract): f(a) = (double)S(a) / (double)W(a); a voxel is observed when W >= min_weight.  An
+ * observed voxel a = (i, j, k) and an axis e in (x, y, z) give a point when the neighbour b = a + e is inside the volume and
+ * observed and exactly one of S(a) < 0, S(b) < 0 holds: the centre of a, moved along e by (f(a) / (f(a) - f(b))) * voxel, in
+ * f64, cast to f32.  Its normal is the forward-difference gradient g = (f(a+x) - f(a), f(a+y) - f(a), f(a+z) - f(a)) over
+ * sqrt((gx^2 + gy^2) + gz^2), cast to f32, when all three forward neighbours are inside and observed and the length is > 0,
+ * else (0, 0, 0); it points from behind the surface towards free space.  Order: ascending (k ny + j) nx + i, then axis
+ * (count per workgroup, scan, write: no atomics decide an order).
+ * All calls run on the context's stream and return after it has drained (the host-pointer convention).  Every error is found
+ * before anything is enqueued: a failed call leaves the volume and the frame table untouched.
+ *   MSLAM_HIP_E_INVALID   NULL ctx or required pointer; no volume; nx, ny, nz < 1 or nx ny nz > 2^30; width, height < 1;
+ *                         max_frames outside 1..32768; voxel, trunc not finite or not > 0; max_depth not > 0 (+inf is fine);
+ *                         a non-finite origin, R or t entry; fx or fy zero or NaN; a frame_id that exists (add), does not
+ *                         exist (get / update / remove) or is listed twice (update); min_weight < 1; n < 0;
+ *   MSLAM_HIP_E_CAPACITY  a frame beyond max_frames; extract into a capacity that is too small: *n is the count needed and
+ *                         no row is written. */
+#define MSLAM_HIP_TSDF_CHUNK 64
+#define MSLAM_HIP_TSDF_MAX_VOXELS (1 << 30)
+#define MSLAM_HIP_TSDF_MAX_FRAMES 32768
+typedef struct
+{
+    int32_t nx, ny, nz;    /* voxels per axis; read-back layout [nz][ny][nx], x fastest                    */
+    int32_t max_frames;    /* 1..32768 retained frames                                                      */
+    double voxel;          /* edge in metres                                                                */
+    double origin[3];      /* world position of the corner of voxel (0, 0, 0)                               */
+    double trunc;          /* truncation distance in metres                                                 */
+    double max_depth;      /* depths above it are not integrated; may be +inf (reference zThreshold: 3.0)   */
+    int32_t width, height; /* the one camera of the volume                                                  */
+    float factor;          /* metres per raw depth unit (TUM: 1 / 5000)                                     */
+    int32_t reserved;      /* 0                                                                             */
+    double fx, fy, cx, cy;
+} mslam_hip_tsdf_params;
+/* A zeroed volume; replaces an existing one and drops its frames. */
+int mslam_hip_tsdf_create(mslam_hip_ctx* ctx, const mslam_hip_tsdf_params* params);
+int mslam_hip_tsdf_destroy(mslam_hip_ctx* ctx); /* OK without a volume */
+int mslam_hip_tsdf_info(mslam_hip_ctx* ctx, mslam_hip_tsdf_params* out /* may be NULL */, int* n_frames /* may be NULL */);
+/* Integrates the frame and retains it (the depth image on the device, the pose) under frame_id. */
+int mslam_hip_tsdf_add_frame(mslam_hip_ctx* ctx, int frame_id, const uint16_t* depth, const double* R, const double* t);
+/* The same from a device image (copied; the caller's buffer is free again when the call returns). */
+int mslam_hip_tsdf_add_frame_dev(mslam_hip_ctx* ctx, int frame_id, const uint16_t* d_depth, const double* R, const double* t);
+int mslam_hip_tsdf_get_frame(mslam_hip_ctx* ctx, int frame_id, double* R, double* t);
+/* Each listed frame whose 12 doubles are bit-identical to the stored ones is skipped; any other is de-integrated at its
+ * stored pose and integrated at the new one (the -1 and +1 entries of all moved frames go through the batched launch), and
+ * its stored pose is replaced.  *n_moved (may be NULL) = the frames not skipped. */
+int mslam_hip_tsdf_update_poses(mslam_hip_ctx* ctx, const int32_t* frame_ids, const double* R /* n x 9 */,
+                                const double* t /* n x 3 */, int n, int* n_moved);
+/* De-integrates the frame at its stored pose and forgets it. */
+int mslam_hip_tsdf_remove_frame(mslam_hip_ctx* ctx, int frame_id);
+/* Test / debug read-back: nx ny nz int32 each, either may be NULL. */
+int mslam_hip_tsdf_read(mslam_hip_ctx* ctx, int32_t* S, int32_t* W);
+/* xyz / normal: capacity x 3 f32 (normal may be NULL; xyz may be NULL when capacity is 0: the count call). */
+int mslam_hip_tsdf_extract(mslam_hip_ctx* ctx, int min_weight, float* xyz, float* normal, int capacity, int* n);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

@@ -47,6 +47,7 @@ UNION_DESC_RECENT, UNION_DESC_DISTINCTIVE = 0, 1    # mslam_hip_set_union_descri
 _UNION_DESC_NAMES = {"recent": UNION_DESC_RECENT, "distinctive": UNION_DESC_DISTINCTIVE}
 TRACK_POSE_PNP, TRACK_POSE_ALIGN = 0, 1    # mslam_hip_set_track_pose's kinds
 _TRACK_POSE_NAMES = {"pnp": TRACK_POSE_PNP, "align": TRACK_POSE_ALIGN}
+TSDF_CHUNK, TSDF_MAX_VOXELS, TSDF_MAX_FRAMES = 64, 1 << 30, 32768    # MSLAM_HIP_TSDF_*: (frame, sign) entries per sweep, limits
 
 # every symbol include/mslam_hip.h declares (tests/test_cabi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -86,6 +87,9 @@ ABI_SYMBOLS = [
     "mslam_hip_set_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg", "mslam_hip_get_pose_graph_pcg_stats",
     "mslam_hip_align_ransac", "mslam_hip_align_batch_dev", "mslam_hip_get_align_view",
     "mslam_hip_set_track_pose", "mslam_hip_get_track_pose",
+    "mslam_hip_tsdf_create", "mslam_hip_tsdf_destroy", "mslam_hip_tsdf_info", "mslam_hip_tsdf_add_frame",
+    "mslam_hip_tsdf_add_frame_dev", "mslam_hip_tsdf_get_frame", "mslam_hip_tsdf_update_poses", "mslam_hip_tsdf_remove_frame",
+    "mslam_hip_tsdf_read", "mslam_hip_tsdf_extract",
 ]
 
 
@@ -150,6 +154,15 @@ class PnpView(C.Structure):
 class AlignView(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("pose", C.c_void_p), ("n_points", C.c_void_p), ("src_points", C.c_void_p),
                 ("dst_points", C.c_void_p), ("inliers", C.c_void_p), ("single_pose", C.c_void_p)]
+
+
+class TsdfParams(C.Structure):
+    """mslam_hip_tsdf_params: the volume (nx, ny, nz voxels of edge `voxel` from the corner `origin`), its truncation and depth
+    cut, the number of frames it may retain and its one camera"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("max_frames", C.c_int32), ("voxel", C.c_double),
+                ("origin", C.c_double * 3), ("trunc", C.c_double), ("max_depth", C.c_double), ("width", C.c_int32),
+                ("height", C.c_int32), ("factor", C.c_float), ("reserved", C.c_int32), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double)]
 
 
 class RelocCandidate(C.Structure):
@@ -605,6 +618,86 @@ class Context:
         k, d = C.c_int(0), C.c_double(0)
         self._chk(self.L.mslam_hip_get_track_pose(self._h, C.byref(k), C.byref(d)))
         return k.value, d.value
+
+    # ---- dense TSDF map that follows the keyframe poses (k_tsdf.hip) ------------------------------
+    def tsdf_create(self, dims, voxel, origin, trunc=None, max_depth=3.0, max_frames=1024, width=640, height=480,
+                    factor=1.0 / 5000.0, focal=(525.0, 525.0), principal=(319.5, 239.5)):
+        """A zeroed volume of dims = (nx, ny, nz) voxels whose voxel (0, 0, 0) has its corner at `origin`; replaces an existing
+        volume and drops its frames.  trunc defaults to 4 voxels; max_depth may be inf."""
+        p = TsdfParams()
+        p.nx, p.ny, p.nz = (int(v) for v in dims)
+        p.max_frames = int(max_frames)
+        p.voxel = float(voxel)
+        p.origin[0], p.origin[1], p.origin[2] = (float(v) for v in origin)
+        p.trunc = 4.0 * float(voxel) if trunc is None else float(trunc)
+        p.max_depth = float(max_depth)
+        p.width, p.height, p.factor = int(width), int(height), float(factor)
+        p.fx, p.fy = (float(v) for v in focal)
+        p.cx, p.cy = (float(v) for v in principal)
+        self._chk(self.L.mslam_hip_tsdf_create(self._h, C.byref(p)))
+
+    def tsdf_destroy(self):
+        self._chk(self.L.mslam_hip_tsdf_destroy(self._h))
+
+    def tsdf_info(self):
+        """-> (TsdfParams, number of retained frames)"""
+        p, n = TsdfParams(), C.c_int(0)
+        self._chk(self.L.mslam_hip_tsdf_info(self._h, C.byref(p), C.byref(n)))
+        return p, n.value
+
+    @staticmethod
+    def _tsdf_pose(R, t, n=1):
+        return np.ascontiguousarray(R, np.float64).reshape(n, 9), np.ascontiguousarray(t, np.float64).reshape(n, 3)
+
+    def tsdf_add_frame(self, frame_id, depth, R, t):
+        """Integrates a depth image (u16 [height][width]: a host array, or an int device address that is copied) at the world
+        -> camera pose (R, t) and retains it under frame_id."""
+        R, t = self._tsdf_pose(R, t)
+        if isinstance(depth, (int, np.integer)):
+            self._chk(self.L.mslam_hip_tsdf_add_frame_dev(self._h, int(frame_id), C.c_void_p(int(depth)), _p(R), _p(t)))
+            return
+        p, _ = self.tsdf_info()
+        d = np.ascontiguousarray(depth, np.uint16)
+        if d.shape != (p.height, p.width):
+            raise MslamHipError(E_INVALID, "tsdf_add_frame: depth is %r, the volume's camera %d x %d" % (d.shape, p.width, p.height))
+        self._chk(self.L.mslam_hip_tsdf_add_frame(self._h, int(frame_id), _p(d), _p(R), _p(t)))
+
+    def tsdf_get_frame(self, frame_id):
+        """-> (R[3][3], t[3]): the pose the frame is integrated at"""
+        R, t = np.zeros((3, 3), np.float64), np.zeros(3, np.float64)
+        self._chk(self.L.mslam_hip_tsdf_get_frame(self._h, int(frame_id), _p(R), _p(t)))
+        return R, t
+
+    def tsdf_update_poses(self, frame_ids, R, t):
+        """Frames whose pose differs in any bit from the stored one are taken out at the stored pose and put back at the new
+        one, all in batched sweeps -> the number of frames moved."""
+        ids = np.ascontiguousarray(frame_ids, np.int32).reshape(-1)
+        R, t = self._tsdf_pose(R, t, len(ids))
+        moved = C.c_int(0)
+        self._chk(self.L.mslam_hip_tsdf_update_poses(self._h, _p(ids), _p(R), _p(t), len(ids), C.byref(moved)))
+        return moved.value
+
+    def tsdf_remove_frame(self, frame_id):
+        self._chk(self.L.mslam_hip_tsdf_remove_frame(self._h, int(frame_id)))
+
+    def tsdf_read(self):
+        """-> (S, W), int32 [nz][ny][nx] each (test / debug read-back)"""
+        p, _ = self.tsdf_info()
+        S, W = np.zeros((p.nz, p.ny, p.nx), np.int32), np.zeros((p.nz, p.ny, p.nx), np.int32)
+        self._chk(self.L.mslam_hip_tsdf_read(self._h, _p(S), _p(W)))
+        return S, W
+
+    def tsdf_extract(self, min_weight=1, normals=True):
+        """-> (xyz f32 [n][3], normal f32 [n][3] or None): the surface points in voxel order, by a count call and a fill"""
+        n = C.c_int(0)
+        rc = self.L.mslam_hip_tsdf_extract(self._h, int(min_weight), None, None, 0, C.byref(n))
+        if rc != E_CAPACITY:
+            self._chk(rc)
+        xyz = np.zeros((n.value, 3), np.float32)
+        nrm = np.zeros((n.value, 3), np.float32) if normals else None
+        if n.value:
+            self._chk(self.L.mslam_hip_tsdf_extract(self._h, int(min_weight), _p(xyz), _p(nrm), n.value, C.byref(n)))
+        return xyz, nrm
 
     # ---- min-MSE PnP (MinMseTracker, ceres_reprojection_error_pnp.cpp:18-110) --------------------
     def pnp_min_mse(self, object_points, image_points, focal=(525.0, 525.0), principal=(319.5, 239.5), rvec=(0, 0, 0),
@@ -2246,7 +2339,22 @@ class HipKeyframeTracker:
     lm_cull_min_observers keyframes hold leaves every keyframe's entry.  With a backend, HipBackend.remove_landmarks
     follows.  The local map is rebuilt when anything was removed.  self.lm_cull_results gains one dict per call made:
     keyframe, listed, candidates, landmark_ids, n_removed, n_backend.  Off by default: nothing is removed.  STILL OUT:
-    MapPointCulling's found / visible ratio (the store keeps no such counters)."""
+    MapPointCulling's found / visible ratio (the store keeps no such counters).
+
+    dense_map = dict(dims=(nx, ny, nz), voxel=, origin=(x, y, z), trunc=4 voxel, max_depth=3.0, max_frames=1024) (needs no
+    other option; an extension, the reference's only dense output is the viewer's per-frame cloud): a TSDF volume on the
+    context (Context.tsdf_create, at the first keyframe, with the frame's size and the tracker's intrinsics and depth factor;
+    max_depth's default is the reference's zThreshold) that holds exactly the retained keyframes at their current poses.  At
+    every keyframe insertion, on both paths, right after the keyframe has its id and before local BA, the keyframe's depth
+    image is added under the keyframe id at the tracked pose (keyframe 0: the identity).  After every step that changes
+    self.backend.poses — local BA, close_loop, global BA — one Context.tsdf_update_poses lists the keyframes whose back-end
+    pose (camera -> world, inverted to the library's world -> camera) differs from the pose they are integrated at by more
+    than dense_update = (translation in metres, between the two camera centres; angle in radians, of the relative rotation):
+    each is taken out at the old pose and put back at the new one.  The defaults are voxel / 2 and voxel / (2 max_depth),
+    half a voxel at the far end of the range (an infinite max_depth: 0).  NOT MEASURED: whether these defaults are good on any
+    sequence.  A keyframe kf_cull removes leaves the volume too.  self.dense_poses maps keyframe id -> (R, t) it is
+    integrated at; self.dense_results gains one dict per update call: listed, moved.  Without local_ba the poses never move
+    and nothing is re-integrated.  None (the default): nothing new runs."""
 
     LOCAL_MAP_ID = 0x7fffffff
     FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
@@ -2260,8 +2368,21 @@ class HipKeyframeTracker:
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
                  pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False,
-                 ba_global_pcg=None, pose_graph_pcg=None, track_pose=None):
+                 ba_global_pcg=None, pose_graph_pcg=None, track_pose=None, dense_map=None, dense_update=None):
         self.ctx = ctx
+        self.dense_map, self.dense_update, self.dense_poses, self.dense_results = None, None, {}, []
+        if dense_map is not None:
+            unknown = set(dense_map) - {"dims", "voxel", "origin", "trunc", "max_depth", "max_frames"}
+            if unknown or not {"dims", "voxel", "origin"} <= set(dense_map):
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: dense_map is dict(dims, voxel, origin[, trunc, max_depth, "
+                                               "max_frames])")
+            self.dense_map = dict(dense_map)
+            self.dense_map.setdefault("max_depth", 3.0)
+            voxel, far = float(self.dense_map["voxel"]), float(self.dense_map["max_depth"])
+            self.dense_update = (voxel / 2, voxel / (2 * far)) if dense_update is None else (float(dense_update[0]), float(dense_update[1]))
+        elif dense_update is not None:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker: dense_update needs dense_map")
+        self._dense_created = False
         if track_pose is not None:
             if len(track_pose) != 2 or track_pose[0] not in _TRACK_POSE_NAMES:
                 raise MslamHipError(E_INVALID, "HipKeyframeTracker: track_pose is None or (\"pnp\" / \"align\", max_distance)")
@@ -2373,6 +2494,8 @@ class HipKeyframeTracker:
                 self.backend.add_keyframe(0, (0, 0, 0, 1, 0, 0, 0), self.ctx.kf_read_ids(0), xyz[keep])
             self.ids, self.reference = [0], 0
             self.graph = {0: set()}
+            if self.dense_map is not None:
+                self._dense_add(0, depth, np.eye(3), np.zeros(3))
             first = dict(tracked=True, n_inliers=0, rvec=self.rvec.copy(), tvec=self.tvec.copy(), R=self.R.copy(), reference=0,
                          keyframe=0, relocalized=False, step=None)
             if self.loop_closure:
@@ -2403,6 +2526,8 @@ class HipKeyframeTracker:
             if res["keyframe_added"]:
                 self.ids.append(new_id)
                 self.reference = out["keyframe"] = new_id
+                if self.dense_map is not None:
+                    self._dense_add(new_id, depth, res["R"], res["tvec"])
                 if self.local_map_depth is not None:
                     self.graph[new_id] = set()
                     for other, n in zip(self.local_map, self.ctx.kf_covisible(new_id, self.local_map)):
@@ -2477,6 +2602,8 @@ class HipKeyframeTracker:
                     if res["keyframe_added"]:
                         self._keyframe_added(new_id)
                         o["keyframe"] = new_id
+                        if self.dense_map is not None:
+                            self._dense_add(new_id, depths[i + s], res["R"], res["tvec"])
                         if self.backend is not None:
                             self._local_ba(new_id, res, xys[i + s], depths[i + s])
                         if self.loop_closure:
@@ -2513,6 +2640,46 @@ class HipKeyframeTracker:
                     self.graph[other].add(new_id)
             self._local_map_of = None
 
+    def _dense_add(self, kf_id, depth, R, t):
+        """dense_map: the keyframe's depth image joins the volume under the keyframe id at its world -> camera pose; the
+        volume is created at the first keyframe, with that frame's size"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if not self._dense_created:
+            m = self.dense_map
+            self.ctx.tsdf_create(m["dims"], m["voxel"], m["origin"], m.get("trunc"), m["max_depth"], m.get("max_frames", 1024),
+                                 depth.shape[1], depth.shape[0], self.factor, self.focal, self.principal)
+            self._dense_created = True
+        R, t = np.array(R, np.float64).reshape(3, 3), np.array(t, np.float64).reshape(3)
+        self.ctx.tsdf_add_frame(kf_id, depth, R, t)
+        self.dense_poses[kf_id] = (R, t)
+
+    @staticmethod
+    def dense_pose_change(R0, t0, R1, t1):
+        """-> (metres between the camera centres, radians of the relative rotation) of two world -> camera poses"""
+        dc = R1.T @ t1 - R0.T @ t0
+        cos = (np.trace(R1 @ R0.T) - 1.0) / 2.0
+        return float(np.sqrt(dc @ dc)), float(np.arccos(min(1.0, max(-1.0, cos))))
+
+    def _dense_follow(self):
+        """dense_map, after a step that changed self.backend.poses: one Context.tsdf_update_poses with the keyframes whose
+        back-end pose left the pose they are integrated at by more than self.dense_update"""
+        ids, Rs, ts = [], [], []
+        for k in sorted(self.dense_poses):
+            pose = self.backend.poses.get(k)
+            if pose is None:
+                continue
+            R = quaternion_to_rotation(pose[:4]).T              # camera -> world in the backend; the volume takes world -> camera
+            t = -R @ np.asarray(pose[4:], np.float64)
+            d, a = self.dense_pose_change(*self.dense_poses[k], R, t)
+            if d > self.dense_update[0] or a > self.dense_update[1]:
+                ids.append(k)
+                Rs.append(R)
+                ts.append(t)
+        moved = self.ctx.tsdf_update_poses(ids, np.stack(Rs), np.stack(ts)) if ids else 0
+        for k, R, t in zip(ids, Rs, ts):
+            self.dense_poses[k] = (np.ascontiguousarray(R, np.float64), np.ascontiguousarray(t, np.float64))
+        self.dense_results.append(dict(listed=ids, moved=moved))
+
     def _local_ba(self, new_id, res, xy, depth):
         """CeresBackend::process for the keyframe just added: feed the backend, solve, write the refined points back"""
         xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
@@ -2525,6 +2692,8 @@ class HipKeyframeTracker:
         if ba["termination"] != 2:
             ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
         self.ba_results.append(ba)
+        if self.dense_map is not None:
+            self._dense_follow()
 
     def _prune_store(self, ba):
         """ba_prune: the observations a pruned solve removed from the backend leave the store too, and the union is rebuilt"""
@@ -2581,6 +2750,9 @@ class HipKeyframeTracker:
         for k in gone:
             self.ids.remove(k)
             self.backend.remove_keyframe(k)
+            if k in self.dense_poses:
+                self.ctx.tsdf_remove_frame(k)
+                del self.dense_poses[k]
             for entry in [e for e, kf in self._bow_entry.items() if kf == k]:
                 self.ctx.bow_db_remove(entry)
                 del self._bow_entry[entry]
@@ -2633,6 +2805,8 @@ class HipKeyframeTracker:
         self.rvec = rotation_to_rvec(self.R)
         self._local_map_of = None
         self._last_closure = new_id
+        if self.dense_map is not None:
+            self._dense_follow()
         if self.loop_fusion:
             attempt["fusion"] = self._fuse_loop(new_id, loop_id)
         if self.loop_global_ba:
@@ -2641,6 +2815,8 @@ class HipKeyframeTracker:
             if ba["termination"] != 2:
                 ba["n_written"] = self.ctx.kf_update_world(ba["landmark_ids"], ba["landmarks"])
             attempt["global_ba"] = ba
+            if self.dense_map is not None:
+                self._dense_follow()
         return (new_id, loop_id)
 
     def _fuse_loop(self, new_id, loop_id):

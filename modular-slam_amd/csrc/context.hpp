@@ -13,6 +13,8 @@ struct BowState; // k_bow.hip
 void bow_destroy(BowState*);
 struct RelocState; // k_reloc.hip: keyframe store + scratch of mslam_hip_relocalize
 void reloc_destroy(RelocState*);
+struct TsdfState; // tsdf.hpp / k_tsdf.hip: the dense map of mslam_hip_tsdf_*
+void tsdf_destroy(TsdfState*);
 void set_blur_taps(const int* taps);
 void build_blur_waves(const Geometry& g, int first_level, std::vector<BlurWave>& out);
 
@@ -204,6 +206,7 @@ struct mslam_hip_ctx
 
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;
+    mslam::TsdfState* tsdf = nullptr;
 
     bool profiling = false;      // mode 1: every stage timed, everything serialised on the context's stream
     bool inplace_timing = false; // mode 2: every stage launch is timed in place on the stream it runs on

@@ -99,6 +99,12 @@
 //                                    ILandmarkCuller::cullLandmarks of the relocalizer adapter on the scene's entries, listed
 //                                    keyframes and candidates: "lmcull found N removed M", one "lm <id> <observers>" line per
 //                                    culled landmark id, then "entry <id> <count>" for every entry in scene order
+//        mslam_harness <plugin.so> --dense <scene> [--dump <path>]
+//                                    hipDenseMapFactory on one scene file (tests/tsdf_ref.py::write_scene: the volume's
+//                                    parameters, the frames with their poses, an optional list of pose updates — one updatePoses
+//                                    call — and an optional list of removals): "dense frames F moved M points N sumS S sumW W",
+//                                    F the frames retained at the end, S and W the sums over the volume as int64.  --dump writes
+//                                    S, W (int32 [nz][ny][nx] each), then the points and the normals (f32, 3 per point), raw
 // prints one line per frame/match with an FNV-1a checksum the parity test compares with the oracle's.
 #include "mslam_interfaces.hpp"
 #include "plugin_loader.hpp"
@@ -268,6 +274,104 @@ int main(int argc, char** argv)
             for(bool b : result->inliers)
                 std::putchar(b ? '1' : '0');
             std::printf("\n");
+            return 0;
+        }
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--dump") == 0)) && std::strcmp(argv[2], "--dense") == 0)
+        {
+            // little endian: magic[8]; mslam_hip_tsdf_params' layout (4 i32, 6 f64, 2 i32, f32, i32, 4 f64); i32 F, U, M, min_weight;
+            // F x {i32 id, 0; f64 R[9], t[3]; u16 depth[height][width]}; U x {i32 id, 0; f64 R[9], t[3]}; M x i32 id
+            std::ifstream in(argv[3], std::ios::binary);
+            char magic[8] = {0};
+            std::int32_t head[4] = {0}, cam[2] = {0}, pad = 0, counts[4] = {0};
+            double vol[6] = {0}, intr[4] = {0};
+            float factor = 0;
+            in.read(magic, 8);
+            in.read(reinterpret_cast<char*>(head), sizeof(head));
+            in.read(reinterpret_cast<char*>(vol), sizeof(vol));
+            in.read(reinterpret_cast<char*>(cam), sizeof(cam));
+            in.read(reinterpret_cast<char*>(&factor), 4);
+            in.read(reinterpret_cast<char*>(&pad), 4);
+            in.read(reinterpret_cast<char*>(intr), sizeof(intr));
+            in.read(reinterpret_cast<char*>(counts), sizeof(counts));
+            if(!in || std::memcmp(magic, "MSTSDF1", 8) != 0 || counts[0] < 0 || counts[1] < 0 || counts[2] < 0 || cam[0] < 1 || cam[1] < 1 ||
+               static_cast<long long>(cam[0]) * cam[1] > (1 << 26))
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                return 5;
+            }
+            mslam::DenseMapParams dp;
+            dp.nx = head[0], dp.ny = head[1], dp.nz = head[2], dp.maxFrames = head[3];
+            dp.voxel = vol[0], dp.origin[0] = vol[1], dp.origin[1] = vol[2], dp.origin[2] = vol[3], dp.trunc = vol[4], dp.maxDepth = vol[5];
+            dp.width = cam[0], dp.height = cam[1];
+            dp.camera.factor = factor;
+            dp.camera.focal = mslam::Vector2(intr[0], intr[1]);
+            dp.camera.principalPoint = mslam::Vector2(intr[2], intr[3]);
+            auto makeDense = mslam::loadFactoryMethod<mslam::IDenseMap>(argv[1], "hipDenseMapFactory");
+            if(!makeDense)
+                return 3;
+            std::unique_ptr<mslam::IDenseMap> dense = makeDense();
+            dense->create(dp);
+            const auto readPose = [&in](std::int32_t& id, mslam::DensePose& pose) {
+                std::int32_t idPad[2] = {0, 0};
+                in.read(reinterpret_cast<char*>(idPad), sizeof(idPad));
+                in.read(reinterpret_cast<char*>(pose.R), sizeof(pose.R));
+                in.read(reinterpret_cast<char*>(pose.t), sizeof(pose.t));
+                id = idPad[0];
+            };
+            std::vector<std::uint16_t> depth(static_cast<std::size_t>(cam[0]) * cam[1]);
+            for(std::int32_t f = 0; f < counts[0]; ++f)
+            {
+                std::int32_t id = 0;
+                mslam::DensePose pose;
+                readPose(id, pose);
+                if(!in.read(reinterpret_cast<char*>(depth.data()), static_cast<std::streamsize>(depth.size() * 2)))
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                    return 5;
+                }
+                dense->addFrame(id, depth, pose);
+            }
+            std::vector<int> ids;
+            std::vector<mslam::DensePose> poses;
+            for(std::int32_t u = 0; u < counts[1]; ++u)
+            {
+                std::int32_t id = 0;
+                mslam::DensePose pose;
+                readPose(id, pose);
+                ids.push_back(id);
+                poses.push_back(pose);
+            }
+            std::vector<std::int32_t> gone(static_cast<std::size_t>(counts[2]));
+            in.read(reinterpret_cast<char*>(gone.data()), static_cast<std::streamsize>(gone.size() * 4));
+            if(!in)
+            {
+                std::fprintf(stderr, "cannot read %s\n", argv[3]);
+                return 5;
+            }
+            const int moved = ids.empty() ? 0 : dense->updatePoses(ids, poses);
+            for(std::int32_t id : gone)
+                dense->removeFrame(id);
+            std::vector<std::int32_t> S, W;
+            dense->read(S, W);
+            const mslam::DenseSurface surface = dense->extract(counts[3]);
+            long long sumS = 0, sumW = 0;
+            for(std::size_t i = 0; i < S.size(); ++i)
+                sumS += S[i], sumW += W[i];
+            std::printf("dense frames %d moved %d points %zu sumS %lld sumW %lld\n", dense->frames(), moved, surface.points.size() / 3,
+                        sumS, sumW);
+            if(argc == 6)
+            {
+                std::ofstream out(argv[5], std::ios::binary);
+                out.write(reinterpret_cast<const char*>(S.data()), static_cast<std::streamsize>(S.size() * 4));
+                out.write(reinterpret_cast<const char*>(W.data()), static_cast<std::streamsize>(W.size() * 4));
+                out.write(reinterpret_cast<const char*>(surface.points.data()), static_cast<std::streamsize>(surface.points.size() * 4));
+                out.write(reinterpret_cast<const char*>(surface.normals.data()), static_cast<std::streamsize>(surface.normals.size() * 4));
+                if(!out)
+                {
+                    std::fprintf(stderr, "cannot write %s\n", argv[5]);
+                    return 5;
+                }
+            }
             return 0;
         }
         const bool baPcg = (argc == 5 || argc == 6) && std::strcmp(argv[4], "--pcg") == 0 && std::strcmp(argv[2], "--ba-global") == 0;

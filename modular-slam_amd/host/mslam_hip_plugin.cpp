@@ -1031,6 +1031,93 @@ class HipRigidAligner : public IRigidAligner
     std::vector<std::uint8_t> mask;
 };
 
+// The dense TSDF map (mslam_hip_tsdf_*): no reference counterpart.  The context has no detector; the volume lives in it.
+class HipDenseMap : public IDenseMap
+{
+  public:
+    void create(const DenseMapParams& q) override
+    {
+        mslam_hip_tsdf_params p{};
+        p.nx = q.nx, p.ny = q.ny, p.nz = q.nz, p.max_frames = q.maxFrames;
+        p.voxel = q.voxel, p.trunc = q.trunc, p.max_depth = q.maxDepth;
+        std::copy(q.origin, q.origin + 3, p.origin);
+        p.width = q.width, p.height = q.height, p.factor = q.camera.factor;
+        p.fx = q.camera.focal.x(), p.fy = q.camera.focal.y(), p.cx = q.camera.principalPoint.x(), p.cy = q.camera.principalPoint.y();
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_create", mslam_hip_tsdf_create(ctx.h, &p));
+        params = p;
+    }
+    void addFrame(int id, const std::vector<std::uint16_t>& depth, const DensePose& pose) override
+    {
+        ctx.ensure(0, 0);
+        if(depth.size() != static_cast<std::size_t>(params.width) * static_cast<std::size_t>(params.height))
+            throw std::invalid_argument("HipDenseMap::addFrame: the depth image is not width x height of the volume's camera");
+        check("mslam_hip_tsdf_add_frame", mslam_hip_tsdf_add_frame(ctx.h, id, depth.data(), pose.R, pose.t));
+    }
+    int updatePoses(const std::vector<int>& ids, const std::vector<DensePose>& poses) override
+    {
+        if(ids.size() != poses.size())
+            throw std::invalid_argument("HipDenseMap::updatePoses: one pose per id");
+        std::vector<std::int32_t> list(ids.begin(), ids.end());
+        std::vector<double> R(9 * ids.size()), t(3 * ids.size());
+        for(std::size_t i = 0; i < ids.size(); ++i)
+        {
+            std::copy(poses[i].R, poses[i].R + 9, R.begin() + 9 * i);
+            std::copy(poses[i].t, poses[i].t + 3, t.begin() + 3 * i);
+        }
+        int moved = 0;
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_update_poses",
+              mslam_hip_tsdf_update_poses(ctx.h, list.data(), R.data(), t.data(), static_cast<int>(ids.size()), &moved));
+        return moved;
+    }
+    void removeFrame(int id) override
+    {
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_remove_frame", mslam_hip_tsdf_remove_frame(ctx.h, id));
+    }
+    int frames() override
+    {
+        int n = 0;
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_info", mslam_hip_tsdf_info(ctx.h, nullptr, &n));
+        return n;
+    }
+    void read(std::vector<std::int32_t>& sums, std::vector<std::int32_t>& weights) override
+    {
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_info", mslam_hip_tsdf_info(ctx.h, &params, nullptr));
+        const std::size_t n = static_cast<std::size_t>(params.nx) * params.ny * params.nz;
+        sums.assign(n, 0);
+        weights.assign(n, 0);
+        check("mslam_hip_tsdf_read", mslam_hip_tsdf_read(ctx.h, sums.data(), weights.data()));
+    }
+    DenseSurface extract(int minWeight) override
+    {
+        DenseSurface out;
+        int n = 0;
+        ctx.ensure(0, 0);
+        int rc = mslam_hip_tsdf_extract(ctx.h, minWeight, nullptr, nullptr, 0, &n); // the count call
+        if(rc != MSLAM_HIP_OK && rc != MSLAM_HIP_E_CAPACITY)
+            raise(ctx.h, "mslam_hip_tsdf_extract", rc);
+        if(n == 0)
+            return out;
+        out.points.assign(3 * static_cast<std::size_t>(n), 0.f);
+        out.normals.assign(3 * static_cast<std::size_t>(n), 0.f);
+        check("mslam_hip_tsdf_extract", mslam_hip_tsdf_extract(ctx.h, minWeight, out.points.data(), out.normals.data(), n, &n));
+        return out;
+    }
+
+  private:
+    void check(const char* what, int rc)
+    {
+        if(rc != MSLAM_HIP_OK)
+            raise(ctx.h, what, rc);
+    }
+    Ctx ctx;
+    mslam_hip_tsdf_params params{};
+};
+
 // drop-in for MinMseTracker (ceres_reprojection_error_pnp.cpp:64-110), keeping its conventions where they differ from
 // OpenCvRansacPnp's: the initial orientation becomes angle-axis as Eigen::AngleAxisd(q) does it and the initial position is
 // the translation itself, with no world -> camera inversion (:71-75); the result's angle, axis and position are cast to
@@ -1395,6 +1482,7 @@ std::unique_ptr<IOrbLoopDetector> createHipLoopDetector() { return std::make_uni
 std::unique_ptr<ISlam3dPnp> createHipRansacPnp() { return std::make_unique<HipRansacPnp>(); }
 std::unique_ptr<ISlam3dPnp> createHipMinMseTracker() { return std::make_unique<HipMinMseTracker>(); }
 std::unique_ptr<IRigidAligner> createHipRigidAligner() { return std::make_unique<HipRigidAligner>(); }
+std::unique_ptr<IDenseMap> createHipDenseMap() { return std::make_unique<HipDenseMap>(); }
 std::unique_ptr<IBackend> createHipBundleAdjustBackend() { return std::make_unique<HipBundleAdjustBackend>(); }
 
 } // namespace mslam
@@ -1407,4 +1495,5 @@ MSLAM_DLL_ALIAS(mslam::createHipLoopDetector, loopDetection) // key used by test
 MSLAM_DLL_ALIAS(mslam::createHipRansacPnp, hipRansacPnpFactory)
 MSLAM_DLL_ALIAS(mslam::createHipMinMseTracker, hipMinMseTrackerFactory)
 MSLAM_DLL_ALIAS(mslam::createHipRigidAligner, hipRigidAlignerFactory)
+MSLAM_DLL_ALIAS(mslam::createHipDenseMap, hipDenseMapFactory)
 MSLAM_DLL_ALIAS(mslam::createHipBundleAdjustBackend, hipBundleAdjustBackendFactory)

@@ -542,6 +542,47 @@ class IRigidAligner
     virtual ~IRigidAligner() = default;
 };
 
+// ---- extension (not in the reference): a dense TSDF map that follows the keyframe poses (mslam_hip_tsdf_*) -----------------
+// The reference's only dense output is the viewer's per-frame cloud (src/app/viewer/slam_thread.cpp:125-150).  One volume of
+// integer accumulators per object: addFrame integrates a depth image (row-major, width x height of the camera given to create)
+// at a world -> camera pose (R row-major, t) and retains it under an id; updatePoses takes every listed frame whose pose
+// changed in any bit out at its old pose and puts it back at the new one, in batched sweeps, and returns how many moved;
+// removeFrame takes a frame out for good.  At every moment the volume equals a fresh integration of the retained frames at
+// their current poses, bit for bit.  extract: the zero crossings between observed neighbours (weight >= minWeight) in voxel
+// order, with forward-difference normals that point towards free space.  Every failure throws, as the other adapters do.
+// Behind hipDenseMapFactory.
+struct DenseMapParams
+{
+    int nx = 0, ny = 0, nz = 0;  // voxels; at most 2^30 in all
+    int maxFrames = 1024;        // 1..32768
+    double voxel = 0;            // metres
+    double origin[3] = {0, 0, 0}; // the corner of voxel (0, 0, 0)
+    double trunc = 0;            // metres
+    double maxDepth = 3.0;       // the reference's zThreshold; may be infinite
+    int width = 640, height = 480;
+    CameraParameters camera;     // focal, principalPoint, factor
+};
+struct DensePose
+{
+    double R[9], t[3];
+};
+struct DenseSurface
+{
+    std::vector<float> points, normals; // 3 per point
+};
+class IDenseMap
+{
+  public:
+    virtual void create(const DenseMapParams& params) = 0;
+    virtual void addFrame(int id, const std::vector<std::uint16_t>& depth, const DensePose& pose) = 0;
+    virtual int updatePoses(const std::vector<int>& ids, const std::vector<DensePose>& poses) = 0;
+    virtual void removeFrame(int id) = 0;
+    virtual int frames() = 0;
+    virtual void read(std::vector<std::int32_t>& sums, std::vector<std::int32_t>& weights) = 0; // [nz][ny][nx] each
+    virtual DenseSurface extract(int minWeight = 1) = 0;
+    virtual ~IDenseMap() = default;
+};
+
 // ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
 // The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
 // The landmarks of `dropEntry` that duplicate landmarks of `keepEntry` — both projected under one world -> camera pose, each
