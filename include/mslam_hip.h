@@ -1612,6 +1612,56 @@ int mslam_hip_tsdf_read(mslam_hip_ctx* ctx, int32_t* S, int32_t* W);
 /* xyz / normal: capacity x 3 f32 (normal may be NULL; xyz may be NULL when capacity is 0: the count call). */
 int mslam_hip_tsdf_extract(mslam_hip_ctx* ctx, int min_weight, float* xyz, float* normal, int capacity, int* n);
 
+/* ---- ray-cast of the dense TSDF map: depth, point and normal images at a pose (k_tsdf_raycast.hip) --------------------------
+ * The view of the model from a pose (R row-major / t, world -> camera) through a render camera (width, height, fx, fy, cx, cy)
+ * that is independent of the volume's own: KinectFusion's surface prediction.  Like the volume, every pixel has one defined
+ * value, bit for bit: all arithmetic is f64, every operation rounded on its own, in the written order.
+ * Ray of pixel (px, py), parametrised by camera depth z (the output depth is z itself, the projective distance integration uses):
+ *   C_a = -((R[0][a] t0 + R[1][a] t1) + R[2][a] t2)                        (the camera centre)
+ *   dx = ((double)px - cx) / fx;  dy = ((double)py - cy) / fy
+ *   D_a = (R[0][a] dx + R[1][a] dy) + R[2][a];  P_a(z) = C_a + z * D_a
+ * Field value F(P):
+ *   g_a = (P_a - o_a) / voxel - 0.5;  b_a = floor(g_a);  w_a = g_a - b_a
+ *   the sample is VALID when for every axis b_a >= 0 and b_a + 1 <= n_a - 1 (false for NaN) and all eight corners
+ *   (b_x + {0,1}, b_y + {0,1}, b_z + {0,1}) have W >= min_weight; a corner's value is (double)S / (double)W (units of
+ *   trunc / 32767, as in extract); lerp(a, b, w) = a + w * (b - a), along x (four), then y (two), then z (one).
+ *   Observed free space therefore evaluates to exactly 32767.0; a sample is NEAR when it is valid and F < 32767.0.
+ * March: samples z_n = z_near + (double)n * step, n = 0 .. n_last, n_last the last n with z_n <= z_far (z is never
+ * accumulated).  If sample 0 is valid with F <= 0 the pixel is a miss.  From n = 0 repeat:
+ *   1. if n + K <= n_last (K = coarse): evaluate sample n + K; if neither sample n nor sample n + K is near, n += K and repeat;
+ *   2. otherwise walk m = n + 1 .. n + K one by one; going past n_last is a miss;
+ *   3. a sample m that is valid with F_m <= 0 ends the ray: a hit when sample m - 1 is valid (its F is then > 0), a miss
+ *      otherwise (a surface entered from behind or from unobserved space);
+ *   4. after the walk n += K.
+ * A hit gives z* = z_{m-1} + (F_{m-1} / (F_{m-1} - F_m)) * step.  K is part of the rule: a coarse stride may step over a
+ * sliver of surface a fine walk would have found.
+ * Outputs per pixel (row-major [height][width]): depth = (float)z*; xyz = (float)P_a(z*), world frame; normal: with
+ * h_a = F(P + voxel e_a) - F(P - voxel e_a) at the f64 hit point P = P(z*), h / sqrt((hx^2 + hy^2) + hz^2) cast to f32 when
+ * all six samples are valid and the length is > 0, else (0, 0, 0); it points towards free space, as extract's.  A miss
+ * writes zeros to all three.
+ * One thread per pixel, no atomics, nothing shared between pixels.  A per-ray clip of the sample range against the volume's
+ * box only skips samples the rule makes invalid.  The call does not change the volume.  *n_hits (may be NULL) = the pixels
+ * with a hit, summed from per-workgroup counts in index order.
+ *   MSLAM_HIP_E_INVALID   no volume; NULL ctx, params, R, t or depth; width or height < 1 or width height > 2^30; fx or fy
+ *                         zero or NaN; a non-finite cx, cy, R or t entry; z_near not finite or < 0; z_far not finite or
+ *                         < z_near; step not finite or not > 0; (z_far - z_near) / step >= 2^20; coarse < 1; min_weight < 1.
+ * Every error is found before anything is enqueued: the volume, the frames and the output buffers stay untouched. */
+typedef struct
+{
+    int32_t width, height; /* the render camera */
+    double fx, fy, cx, cy;
+    double z_near, z_far, step; /* metres of camera depth */
+    int32_t coarse;             /* K >= 1: samples per coarse stride */
+    int32_t min_weight;         /* >= 1 */
+} mslam_hip_tsdf_raycast_params;
+/* depth: height x width f32; xyz / normal: height x width x 3 f32, either may be NULL.  Host pointers; returns after the
+ * stream has drained. */
+int mslam_hip_tsdf_raycast(mslam_hip_ctx* ctx, const mslam_hip_tsdf_raycast_params* params, const double* R, const double* t,
+                           float* depth, float* xyz, float* normal, int* n_hits);
+/* The same into device buffers: enqueued on the context's stream, which is drained only when n_hits is not NULL. */
+int mslam_hip_tsdf_raycast_dev(mslam_hip_ctx* ctx, const mslam_hip_tsdf_raycast_params* params, const double* R, const double* t,
+                               float* d_depth, float* d_xyz, float* d_normal, int* n_hits);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

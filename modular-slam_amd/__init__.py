@@ -89,7 +89,7 @@ ABI_SYMBOLS = [
     "mslam_hip_set_track_pose", "mslam_hip_get_track_pose",
     "mslam_hip_tsdf_create", "mslam_hip_tsdf_destroy", "mslam_hip_tsdf_info", "mslam_hip_tsdf_add_frame",
     "mslam_hip_tsdf_add_frame_dev", "mslam_hip_tsdf_get_frame", "mslam_hip_tsdf_update_poses", "mslam_hip_tsdf_remove_frame",
-    "mslam_hip_tsdf_read", "mslam_hip_tsdf_extract",
+    "mslam_hip_tsdf_read", "mslam_hip_tsdf_extract", "mslam_hip_tsdf_raycast", "mslam_hip_tsdf_raycast_dev",
 ]
 
 
@@ -163,6 +163,14 @@ class TsdfParams(C.Structure):
                 ("origin", C.c_double * 3), ("trunc", C.c_double), ("max_depth", C.c_double), ("width", C.c_int32),
                 ("height", C.c_int32), ("factor", C.c_float), ("reserved", C.c_int32), ("fx", C.c_double), ("fy", C.c_double),
                 ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class TsdfRaycastParams(C.Structure):
+    """mslam_hip_tsdf_raycast_params: the render camera, the sample range and spacing in metres of camera depth, the coarse
+    stride in samples and the observation count a voxel needs"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("z_near", C.c_double), ("z_far", C.c_double), ("step", C.c_double), ("coarse", C.c_int32),
+                ("min_weight", C.c_int32)]
 
 
 class RelocCandidate(C.Structure):
@@ -698,6 +706,56 @@ class Context:
         if n.value:
             self._chk(self.L.mslam_hip_tsdf_extract(self._h, int(min_weight), _p(xyz), _p(nrm), n.value, C.byref(n)))
         return xyz, nrm
+
+    def tsdf_raycast_params(self, R, t, camera=None, z_near=0.1, z_far=None, step=None, coarse=None, min_weight=1):
+        """-> TsdfRaycastParams with the defaults of tsdf_raycast filled in"""
+        v, _ = self.tsdf_info()
+        R, t = self._tsdf_pose(R, t)
+        q = TsdfRaycastParams()
+        if camera is None:
+            camera = dict(width=v.width, height=v.height, focal=(v.fx, v.fy), principal=(v.cx, v.cy))
+        q.width, q.height = int(camera["width"]), int(camera["height"])
+        q.fx, q.fy = (float(x) for x in camera["focal"])
+        q.cx, q.cy = (float(x) for x in camera["principal"])
+        if z_far is None:
+            z_far = v.max_depth
+            if not np.isfinite(z_far):
+                ext = np.array([v.nx, v.ny, v.nz], np.float64) * v.voxel
+                mid = np.array(list(v.origin), np.float64) + 0.5 * ext
+                z_far = float(np.linalg.norm(ext) + np.linalg.norm(-R.reshape(3, 3).T @ t.reshape(3) - mid))
+        q.z_near, q.z_far = float(z_near), float(z_far)
+        q.step = v.voxel / 2 if step is None else float(step)
+        if coarse is None:
+            k = np.floor(v.trunc / (2 * q.step)) if q.step > 0 else 1.0    # (a bad step is the library's to refuse)
+            coarse = int(k) if np.isfinite(k) and k >= 1 else 1
+        q.coarse = min(int(coarse), 0x7fffffff)
+        q.min_weight = int(min_weight)
+        return q
+
+    def tsdf_raycast(self, R, t, camera=None, z_near=0.1, z_far=None, step=None, coarse=None, min_weight=1, normals=True,
+                     out=None, with_hits=False):
+        """The view of the volume from the world -> camera pose (R, t) -> (depth f32 [h][w], xyz f32 [h][w][3], normal f32
+        [h][w][3] or None); zeros where the ray finds no surface.  camera = dict(width, height, focal, principal) defaults to
+        the volume's; z_far to the volume's max_depth (when that is inf: the volume's diagonal plus the distance of the camera
+        centre to its middle); step to voxel / 2; coarse to max(1, floor(trunc / (2 step))).  out = (depth, xyz or None,
+        normal or None) as int device addresses renders into the caller's device buffers on the context's stream instead and
+        returns None (with_hits: the stream is drained and the number of hits returned).  with_hits on the host form
+        -> (depth, xyz, normal, n_hits)."""
+        q = self.tsdf_raycast_params(R, t, camera, z_near, z_far, step, coarse, min_weight)
+        R, t = self._tsdf_pose(R, t)
+        n = C.c_int(0)
+        hits = C.byref(n) if with_hits else None
+        if out is not None:
+            d_depth, d_xyz, d_normal = (None if a is None else C.c_void_p(int(a)) for a in out)
+            self._chk(self.L.mslam_hip_tsdf_raycast_dev(self._h, C.byref(q), _p(R), _p(t), d_depth, d_xyz, d_normal, hits))
+            return n.value if with_hits else None
+        if q.width < 1 or q.height < 1 or q.width * q.height > 1 << 30:
+            raise MslamHipError(E_INVALID, "tsdf_raycast: width, height must be >= 1 with at most 2^30 pixels")
+        depth = np.zeros((q.height, q.width), np.float32)
+        xyz = np.zeros((q.height, q.width, 3), np.float32)
+        nrm = np.zeros((q.height, q.width, 3), np.float32) if normals else None
+        self._chk(self.L.mslam_hip_tsdf_raycast(self._h, C.byref(q), _p(R), _p(t), _p(depth), _p(xyz), _p(nrm), hits))
+        return (depth, xyz, nrm, n.value) if with_hits else (depth, xyz, nrm)
 
     # ---- min-MSE PnP (MinMseTracker, ceres_reprojection_error_pnp.cpp:18-110) --------------------
     def pnp_min_mse(self, object_points, image_points, focal=(525.0, 525.0), principal=(319.5, 239.5), rvec=(0, 0, 0),
@@ -2652,6 +2710,17 @@ class HipKeyframeTracker:
         R, t = np.array(R, np.float64).reshape(3, 3), np.array(t, np.float64).reshape(3)
         self.ctx.tsdf_add_frame(kf_id, depth, R, t)
         self.dense_poses[kf_id] = (R, t)
+
+    def dense_render(self, R=None, t=None, **kw):
+        """dense_map: Context.tsdf_raycast of the volume at the world -> camera pose (R, t), by default the pose of the latest
+        tracked frame; the keywords are tsdf_raycast's.  Reads the volume only: tracking is not affected."""
+        if self.dense_map is None or not self._dense_created:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker.dense_render needs dense_map and a first keyframe")
+        if (R is None) != (t is None):
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker.dense_render: R and t go together")
+        if R is None:
+            R, t = self.R, self.tvec
+        return self.ctx.tsdf_raycast(R, t, **kw)
 
     @staticmethod
     def dense_pose_change(R0, t0, R1, t1):

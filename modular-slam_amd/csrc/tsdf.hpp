@@ -1,5 +1,6 @@
-// tsdf.hpp — the dense map behind mslam_hip_tsdf_* (k_tsdf.hip): the volume, the retained frames and the scratch of the
-// extraction.  The invariant: `vol` equals the integration of `frames` at their stored poses into a zeroed volume.
+// tsdf.hpp — the dense map behind mslam_hip_tsdf_* (k_tsdf.hip, k_tsdf_raycast.hip): the volume, the retained frames and the
+// scratch of the extraction and of the ray-cast.  The invariant: `vol` equals the integration of `frames` at their stored poses
+// into a zeroed volume.
 #pragma once
 #include "devmem.hpp"
 #include "../../include/mslam_hip.h"
@@ -31,5 +32,9 @@ struct TsdfState
     // extraction: crossings per workgroup and their exclusive scan (the last element is the total), the rows
     DevBuf<unsigned long long> d_block_ofs;
     DevBuf<float> d_xyz, d_normal;
+    // ray-cast (k_tsdf_raycast.hip): hits per workgroup, and the depth image of a call with host pointers (its point and
+    // normal images use d_xyz and d_normal)
+    DevBuf<unsigned> d_ray_hits;
+    DevBuf<float> d_ray_depth;
 };
 } // namespace mslam

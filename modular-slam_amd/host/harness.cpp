@@ -99,6 +99,10 @@
 //                                    ILandmarkCuller::cullLandmarks of the relocalizer adapter on the scene's entries, listed
 //                                    keyframes and candidates: "lmcull found N removed M", one "lm <id> <observers>" line per
 //                                    culled landmark id, then "entry <id> <count>" for every entry in scene order
+//        mslam_harness <plugin.so> --dense <scene> --raycast <views> [--dump <path>]
+//                                    the same, then IDenseMapRenderer (a dynamic_cast of the dense map) renders every view of
+//                                    the views file (tests/tsdf_raycast_ref.py::write_views): "raycast view V size W x H hits
+//                                    N" per view; the dump holds depth, xyz and normal per view instead of the volume
 //        mslam_harness <plugin.so> --dense <scene> [--dump <path>]
 //                                    hipDenseMapFactory on one scene file (tests/tsdf_ref.py::write_scene: the volume's
 //                                    parameters, the frames with their poses, an optional list of pose updates — one updatePoses
@@ -276,7 +280,8 @@ int main(int argc, char** argv)
             std::printf("\n");
             return 0;
         }
-        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--dump") == 0)) && std::strcmp(argv[2], "--dense") == 0)
+        const bool denseRaycast = (argc == 6 || (argc == 8 && std::strcmp(argv[6], "--dump") == 0)) && std::strcmp(argv[4], "--raycast") == 0;
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--dump") == 0) || denseRaycast) && std::strcmp(argv[2], "--dense") == 0)
         {
             // little endian: magic[8]; mslam_hip_tsdf_params' layout (4 i32, 6 f64, 2 i32, f32, i32, 4 f64); i32 F, U, M, min_weight;
             // F x {i32 id, 0; f64 R[9], t[3]; u16 depth[height][width]}; U x {i32 id, 0; f64 R[9], t[3]}; M x i32 id
@@ -298,6 +303,46 @@ int main(int argc, char** argv)
             {
                 std::fprintf(stderr, "cannot read %s\n", argv[3]);
                 return 5;
+            }
+            // --raycast <views> (tests/tsdf_raycast_ref.py::write_views), little endian: magic[8]; i32 V, 0; V x
+            // {mslam_hip_tsdf_raycast_params' layout (2 i32, 7 f64, 2 i32); f64 R[9], t[3]}
+            struct View
+            {
+                mslam::DenseRenderParams params;
+                mslam::DensePose pose;
+            };
+            std::vector<View> views;
+            if(denseRaycast)
+            {
+                std::ifstream vin(argv[5], std::ios::binary);
+                char vmagic[8] = {0};
+                std::int32_t nViews[2] = {0, 0};
+                vin.read(vmagic, 8);
+                vin.read(reinterpret_cast<char*>(nViews), sizeof(nViews));
+                bool good = vin && std::memcmp(vmagic, "MSTSDFV1", 8) == 0 && nViews[0] >= 0 && nViews[0] <= (1 << 16);
+                for(std::int32_t v = 0; good && v < nViews[0]; ++v)
+                {
+                    std::int32_t size[2] = {0, 0}, march[2] = {0, 0};
+                    double real[7] = {0};
+                    View view;
+                    vin.read(reinterpret_cast<char*>(size), sizeof(size));
+                    vin.read(reinterpret_cast<char*>(real), sizeof(real));
+                    vin.read(reinterpret_cast<char*>(march), sizeof(march));
+                    vin.read(reinterpret_cast<char*>(view.pose.R), sizeof(view.pose.R));
+                    vin.read(reinterpret_cast<char*>(view.pose.t), sizeof(view.pose.t));
+                    good = static_cast<bool>(vin) && size[0] >= 1 && size[1] >= 1 && static_cast<long long>(size[0]) * size[1] <= (1 << 26);
+                    view.params.width = size[0], view.params.height = size[1];
+                    view.params.camera.focal = mslam::Vector2(real[0], real[1]);
+                    view.params.camera.principalPoint = mslam::Vector2(real[2], real[3]);
+                    view.params.zNear = real[4], view.params.zFar = real[5], view.params.step = real[6];
+                    view.params.coarse = march[0], view.params.minWeight = march[1];
+                    views.push_back(view);
+                }
+                if(!good)
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[5]);
+                    return 5;
+                }
             }
             mslam::DenseMapParams dp;
             dp.nx = head[0], dp.ny = head[1], dp.nz = head[2], dp.maxFrames = head[3];
@@ -359,6 +404,43 @@ int main(int argc, char** argv)
                 sumS += S[i], sumW += W[i];
             std::printf("dense frames %d moved %d points %zu sumS %lld sumW %lld\n", dense->frames(), moved, surface.points.size() / 3,
                         sumS, sumW);
+            if(denseRaycast)
+            {
+                // the dump: magic[8]; i32 V, 0; V x {i32 width, height, hits, 0; f32 depth[h][w], xyz[h][w][3], normal[h][w][3]}
+                auto* renderer = dynamic_cast<mslam::IDenseMapRenderer*>(dense.get());
+                if(!renderer)
+                {
+                    std::fprintf(stderr, "the dense map offers no IDenseMapRenderer\n");
+                    return 3;
+                }
+                std::ofstream out;
+                if(argc == 8)
+                {
+                    out.open(argv[7], std::ios::binary);
+                    const std::int32_t n[2] = {static_cast<std::int32_t>(views.size()), 0};
+                    out.write("MSTSDFR1", 8);
+                    out.write(reinterpret_cast<const char*>(n), sizeof(n));
+                }
+                for(std::size_t v = 0; v < views.size(); ++v)
+                {
+                    const mslam::DenseRender r = renderer->render(views[v].params, views[v].pose);
+                    std::printf("raycast view %zu size %d x %d hits %d\n", v, views[v].params.width, views[v].params.height, r.hits);
+                    if(argc == 8)
+                    {
+                        const std::int32_t h[4] = {views[v].params.width, views[v].params.height, r.hits, 0};
+                        out.write(reinterpret_cast<const char*>(h), sizeof(h));
+                        out.write(reinterpret_cast<const char*>(r.depth.data()), static_cast<std::streamsize>(r.depth.size() * 4));
+                        out.write(reinterpret_cast<const char*>(r.points.data()), static_cast<std::streamsize>(r.points.size() * 4));
+                        out.write(reinterpret_cast<const char*>(r.normals.data()), static_cast<std::streamsize>(r.normals.size() * 4));
+                    }
+                }
+                if(argc == 8 && !out)
+                {
+                    std::fprintf(stderr, "cannot write %s\n", argv[7]);
+                    return 5;
+                }
+                return 0;
+            }
             if(argc == 6)
             {
                 std::ofstream out(argv[5], std::ios::binary);

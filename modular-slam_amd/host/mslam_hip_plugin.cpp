@@ -1032,7 +1032,7 @@ class HipRigidAligner : public IRigidAligner
 };
 
 // The dense TSDF map (mslam_hip_tsdf_*): no reference counterpart.  The context has no detector; the volume lives in it.
-class HipDenseMap : public IDenseMap
+class HipDenseMap : public IDenseMap, public IDenseMapRenderer
 {
   public:
     void create(const DenseMapParams& q) override
@@ -1105,6 +1105,25 @@ class HipDenseMap : public IDenseMap
         out.points.assign(3 * static_cast<std::size_t>(n), 0.f);
         out.normals.assign(3 * static_cast<std::size_t>(n), 0.f);
         check("mslam_hip_tsdf_extract", mslam_hip_tsdf_extract(ctx.h, minWeight, out.points.data(), out.normals.data(), n, &n));
+        return out;
+    }
+    DenseRender render(const DenseRenderParams& q, const DensePose& pose, bool normals) override
+    {
+        mslam_hip_tsdf_raycast_params p{};
+        p.width = q.width, p.height = q.height;
+        p.fx = q.camera.focal.x(), p.fy = q.camera.focal.y(), p.cx = q.camera.principalPoint.x(), p.cy = q.camera.principalPoint.y();
+        p.z_near = q.zNear, p.z_far = q.zFar, p.step = q.step, p.coarse = q.coarse, p.min_weight = q.minWeight;
+        if(q.width < 1 || q.height < 1 || static_cast<long long>(q.width) * q.height > (1 << 30))
+            throw std::invalid_argument("HipDenseMap::render: width, height must be >= 1 with at most 2^30 pixels");
+        DenseRender out;
+        const std::size_t px = static_cast<std::size_t>(q.width) * static_cast<std::size_t>(q.height);
+        out.depth.assign(px, 0.f);
+        out.points.assign(3 * px, 0.f);
+        if(normals)
+            out.normals.assign(3 * px, 0.f);
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_raycast", mslam_hip_tsdf_raycast(ctx.h, &p, pose.R, pose.t, out.depth.data(), out.points.data(),
+                                                               normals ? out.normals.data() : nullptr, &out.hits));
         return out;
     }
 

@@ -583,6 +583,33 @@ class IDenseMap
     virtual ~IDenseMap() = default;
 };
 
+// extension: the view of the dense map from a pose (mslam_hip_tsdf_raycast): per pixel of a render camera that is independent
+// of the volume's own, the depth along the optical axis of the first surface the ray meets, its world point and its normal
+// (towards free space); zeros where the ray finds none.  The march samples camera depth zNear + n step up to zFar, `coarse`
+// samples per stride through space that is not near a surface, and reads voxels observed at least minWeight times; every
+// value is explicit (the Python binding's defaults: zFar the volume's maxDepth, step voxel / 2, coarse
+// max(1, floor(trunc / (2 step)))).  The images have one defined value, bit for bit (include/mslam_hip.h has the rule).
+// Offered by hipDenseMapFactory's object: dynamic_cast<IDenseMapRenderer*>(denseMap.get()).
+struct DenseRenderParams
+{
+    int width = 640, height = 480;
+    CameraParameters camera; // focal, principalPoint
+    double zNear = 0.1, zFar = 3.0, step = 0;
+    int coarse = 1, minWeight = 1;
+};
+struct DenseRender
+{
+    std::vector<float> depth;           // [height][width]
+    std::vector<float> points, normals; // [height][width][3]; normals is empty when they were not asked for
+    int hits = 0;
+};
+class IDenseMapRenderer
+{
+  public:
+    virtual DenseRender render(const DenseRenderParams& params, const DensePose& pose, bool normals = true) = 0;
+    virtual ~IDenseMapRenderer() = default;
+};
+
 // ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
 // The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
 // The landmarks of `dropEntry` that duplicate landmarks of `keepEntry` — both projected under one world -> camera pose, each
