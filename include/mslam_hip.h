@@ -1662,6 +1662,137 @@ int mslam_hip_tsdf_raycast(mslam_hip_ctx* ctx, const mslam_hip_tsdf_raycast_para
 int mslam_hip_tsdf_raycast_dev(mslam_hip_ctx* ctx, const mslam_hip_tsdf_raycast_params* params, const double* R, const double* t,
                                float* d_depth, float* d_xyz, float* d_normal, int* n_hits);
 
+/* ---- frame-to-model alignment: point-to-plane ICP of a depth frame against a rendered model (k_icp.hip) -------------------
+ * An extension (the reference tracks by features only): KinectFusion's third part.  A depth frame is aligned against a model
+ * given as two f32 images, xyz and normal [mh][mw][3] in the world frame, a zero normal meaning "no surface": exactly what
+ * mslam_hip_tsdf_raycast writes.  Like the volume and its ray-cast the result has one value, bit for bit: all arithmetic is
+ * f64, every operation rounded on its own, sums of three written (a + b) + c, in the written order.
+ * Inputs: depth u16 [h][w] with its camera (w, h, fx, fy, cx, cy, factor, max_depth); the model images with their camera
+ * (mw, mh, mfx, mfy, mcx, mcy), independent of the frame's, and pose (Rm, tm), world -> camera; a guess (R0, t0), world ->
+ * camera.  All R are row-major.
+ * Frame vertex at (px, py): d = (float)raw * factor (one f32 multiply, as in integration); VALID when d > FLT_EPSILON &&
+ *   (double)d <= max_depth; z = (double)d; V = (((double)px - cx) / fx * z, ((double)py - cy) / fy * z, z).
+ * Frame normal at (px, py): needs 1 <= px <= w - 2, 1 <= py <= h - 2 and the vertex and its four neighbours valid;
+ *   a = V(px+1, py) - V(px-1, py);  b = V(px, py+1) - V(px, py-1);
+ *   c = b x a:  c0 = b1 a2 - b2 a1;  c1 = b2 a0 - b0 a2;  c2 = b0 a1 - b1 a0;
+ *   len = sqrt((c0 c0 + c1 c1) + c2 c2); needs len > 0 (false for NaN); n_f = c / len.  It points towards the camera, as the
+ *   model's normals point towards free space.
+ *   KinectFusion   DEVIATES: no bilateral filter; no depth-discontinuity gate (the normal test below rejects most edge
+ *   pixels); no smoothed pyramid (a level sub-samples the full-resolution frame, see Levels).
+ * State: the camera -> world transform (Q, s).  Q = R0^T;  s_a = -((R0[0][a] t0 + R0[1][a] t1) + R0[2][a] t2) (the ray-cast's
+ *   C_a).
+ * One pair, for a pixel with a frame normal ("skip": the pixel adds +0.0 to every sum and 0 to the count):
+ *   X_r = ((Q[r][0] V0 + Q[r][1] V1) + Q[r][2] V2) + s_r;   N_r = (Q[r][0] n0 + Q[r][1] n1) + Q[r][2] n2
+ *   c_r = ((Rm[r][0] X0 + Rm[r][1] X1) + Rm[r][2] X2) + tm[r];  skip unless c_2 > 0
+ *   u = (c_0 / c_2) mfx + mcx;  v = (c_1 / c_2) mfy + mcy;  uh = u + 0.5;  vh = v + 0.5
+ *   skip unless uh >= 0 && uh < (double)mw && vh >= 0 && vh < (double)mh (false for NaN); the model pixel is
+ *   ((int)floor(uh), (int)floor(vh)): integration's projection.  q, m = the model point and normal there, as (double).
+ *   skip when m0 == 0 && m1 == 0 && m2 == 0
+ *   e = X - q;  skip unless (e0 e0 + e1 e1) + e2 e2 <= dist_max * dist_max
+ *   skip unless (N0 m0 + N1 m1) + N2 m2 >= cos_min
+ *   r = (m0 e0 + m1 e1) + m2 e2
+ *   J = (X1 m2 - X2 m1,  X2 m0 - X0 m2,  X0 m1 - X1 m0,  m0,  m1,  m2)
+ *   terms: the 21 products J_i J_j, i <= j (row-major upper triangle: A21), the 6 products J_i r (g), r r (cost), the count.
+ * Levels: up to 4 (stride_l, iterations_l), in the given order.  Level l uses the pixels with px % stride == 0 && py % stride
+ *   == 0 of the full-resolution frame; frame normals always come from full-resolution neighbours; the model is never
+ *   sub-sampled.
+ * The sums (their order is part of the rule, as the march's stride K is): the level's pixels are enumerated row-major over
+ *   (py / stride, px / stride) as i = 0 .. M - 1, positions past M are +0.0.  Chunk i / 256: within each run of 64 the
+ *   butterfly as seen from position 0 (v_p += v_(p + 32) for p < 32, then 16, 8, 4, 2, 1); then the four runs as
+ *   ((g0 + g1) + g2) + g3.  The chunk sums are added in ascending chunk index, starting from +0.0.  No atomics.
+ * Solve A x = -g, x = (omega, tau), by an LDL^T without pivoting and without square root; for j = 0 .. 5:
+ *   v_k = L[j][k] D_k (k < j);  D_j = A[j][j] - L[j][0] v_0 - ... - L[j][j-1] v_(j-1)   (one subtraction after the other)
+ *   L[i][j] = (A[i][j] - L[i][0] v_0 - ... - L[i][j-1] v_(j-1)) / D_j   (i > j)
+ *   y_i = -g_i - L[i][0] y_0 - ... - L[i][i-1] y_(i-1);   x_i = y_i / D_i - L[i+1][i] x_(i+1) - ... - L[5][i] x_5  (i = 5 .. 0)
+ *   If the count < min_pairs (no pivot is computed: all six are reported 0.0) or a pivot D_j is not > 0 (false for NaN; the
+ *   later pivots are reported 0.0) the solve ends DEGENERATE.
+ * Update by the Cayley map (no transcendental function): a = omega * 0.5;  aa = (a0 a0 + a1 a1) + a2 a2;
+ *   dR[i][i] = ((1 - aa) + 2 (a_i a_i)) / (1 + aa);   dR[0][1] = (2 (a0 a1) - 2 a2) / (1 + aa);  dR[1][0] = (2 (a0 a1) + 2 a2) / ..;
+ *   dR[0][2] = (2 (a0 a2) + 2 a1) / ..;  dR[2][0] = (2 (a0 a2) - 2 a1) / ..;  dR[1][2] = (2 (a1 a2) - 2 a0) / ..;
+ *   dR[2][1] = (2 (a1 a2) + 2 a0) / ..
+ *   Q[i][j] <- (dR[i][0] Q[0][j] + dR[i][1] Q[1][j]) + dR[i][2] Q[2][j];   s_i <- ((dR[i][0] s0 + dR[i][1] s1) + dR[i][2] s2) + tau_i
+ *   A level ends early when, after an update, (w0 w0 + w1 w1) + w2 w2 <= rot_tol rot_tol && (tau likewise) <= trans_tol
+ *   trans_tol (w = omega).  Tolerances of 0 run every iteration (unless a step is exactly zero).
+ * Outputs: R = Q^T;  t_r = -((Q[0][r] s0 + Q[1][r] s1) + Q[2][r] s2);  status CONVERGED when the LAST level ended by the step
+ *   test, ITERATIONS otherwise, DEGENERATE as above: R and t are then the guess, bit for bit.  The result holds the number of
+ *   linearisations made, the level, count, sum r r and the six pivots of the last one; `record` (may be NULL) gets one row per
+ *   linearisation (a degenerate one has rot2 = trans2 = 0).  The call does not judge weak geometry: the pivots are reported
+ *   so that a caller can.  DEGENERATE is a status of a successful call, not an error code.
+ * The whole solve is enqueued up front, two launches per scheduled iteration; launches whose level or solve has ended return
+ * at once; the host synchronises once at the end.
+ *   MSLAM_HIP_E_INVALID   NULL ctx or required pointer; width, height, model_width or model_height < 1, width height > 2^24 or
+ *                         model_width model_height > 2^30; a non-finite fx, fy, cx, cy, mfx, mfy, mcx, mcy, factor or pose entry;
+ *                         fx, fy, mfx or mfy zero; max_depth NaN or not > 0 (+inf is fine); n_levels outside 1..4; a stride or an
+ *                         iteration count < 1; more than MSLAM_HIP_ICP_MAX_ITERATIONS iterations in all; dist_max not finite or
+ *                         not > 0; cos_min outside [-1, 1]; min_pairs < 6; a negative or non-finite tolerance; record given
+ *                         with record_capacity below the scheduled iterations; for the tsdf_ forms: no volume, or a frame camera
+ *                         (width .. max_depth) that differs from the volume's.
+ * Every error is found before anything is enqueued: all outputs stay untouched. */
+#define MSLAM_HIP_ICP_MAX_LEVELS 4
+#define MSLAM_HIP_ICP_MAX_ITERATIONS 256
+enum
+{
+    MSLAM_HIP_ICP_CONVERGED = 0,
+    MSLAM_HIP_ICP_ITERATIONS = 1,
+    MSLAM_HIP_ICP_DEGENERATE = 2
+};
+typedef struct
+{
+    int32_t width, height; /* the frame camera */
+    float factor;          /* metres per raw depth unit */
+    int32_t n_levels;      /* 1..4 */
+    double fx, fy, cx, cy;
+    double max_depth;                  /* deeper pixels have no vertex; may be +inf */
+    int32_t model_width, model_height; /* the model camera (not read by the tsdf_ forms: theirs is the ray-cast's) */
+    double mfx, mfy, mcx, mcy;
+    int32_t stride[MSLAM_HIP_ICP_MAX_LEVELS], iterations[MSLAM_HIP_ICP_MAX_LEVELS];
+    double dist_max, cos_min; /* the gates: metres between the pair, cosine between the normals */
+    int32_t min_pairs;        /* >= 6 */
+    int32_t reserved;         /* 0 */
+    double rot_tol, trans_tol; /* the step test; 0: every iteration runs */
+} mslam_hip_icp_params;
+typedef struct
+{
+    int32_t status;     /* MSLAM_HIP_ICP_* */
+    int32_t iterations; /* linearisations made */
+    int32_t count;      /* pairs of the last linearisation */
+    int32_t level;      /* its level */
+    double cost;        /* its sum r r */
+    double pivots[6];   /* its D_0 .. D_5 */
+} mslam_hip_icp_result;
+typedef struct
+{
+    int32_t level, count;
+    double cost, rot2, trans2; /* sum r r; omega . omega; tau . tau */
+} mslam_hip_icp_record;
+/* Host pointers: depth u16 [height][width]; model_xyz, model_normal f32 [model_height][model_width][3]; Rm, R0, R: 9 f64;
+ * tm, t0, t: 3 f64.  Needs no volume.  Returns after the stream has drained. */
+int mslam_hip_icp_point_plane(mslam_hip_ctx* ctx, const mslam_hip_icp_params* params, const uint16_t* depth, const float* model_xyz,
+                              const float* model_normal, const double* Rm, const double* tm, const double* R0, const double* t0,
+                              double* R, double* t, mslam_hip_icp_result* result, mslam_hip_icp_record* record /* may be NULL */,
+                              int record_capacity);
+/* The same with the three images on the device (poses, results and record stay host pointers), on the context's stream. */
+int mslam_hip_icp_point_plane_dev(mslam_hip_ctx* ctx, const mslam_hip_icp_params* params, const uint16_t* d_depth,
+                                  const float* d_model_xyz, const float* d_model_normal, const double* Rm, const double* tm,
+                                  const double* R0, const double* t0, double* R, double* t, mslam_hip_icp_result* result,
+                                  mslam_hip_icp_record* record, int record_capacity);
+/* One linearisation at the world -> camera pose (R, t) with the pixels of `stride` (tests and diagnostics; host pointers; the
+ * levels of params are checked but not used): A21 (21 f64), g6 (6 f64), *count, *cost. */
+int mslam_hip_icp_linearize(mslam_hip_ctx* ctx, const mslam_hip_icp_params* params, const uint16_t* depth, const float* model_xyz,
+                            const float* model_normal, const double* Rm, const double* tm, const double* R, const double* t,
+                            int stride, double* A21, double* g6, int* count, double* cost);
+/* Renders the volume at the guess with raycast_params into the volume's scratch images (model pose = the guess, model camera
+ * = the render camera), then solves: equal to mslam_hip_tsdf_raycast followed by mslam_hip_icp_point_plane, byte for byte.
+ * The frame camera is the volume's own. */
+int mslam_hip_tsdf_icp(mslam_hip_ctx* ctx, const mslam_hip_icp_params* params, const mslam_hip_tsdf_raycast_params* raycast_params,
+                       const uint16_t* depth, const double* R0, const double* t0, double* R, double* t, mslam_hip_icp_result* result,
+                       mslam_hip_icp_record* record, int record_capacity);
+/* The same for a depth image on the device. */
+int mslam_hip_tsdf_icp_dev(mslam_hip_ctx* ctx, const mslam_hip_icp_params* params,
+                           const mslam_hip_tsdf_raycast_params* raycast_params, const uint16_t* d_depth, const double* R0,
+                           const double* t0, double* R, double* t, mslam_hip_icp_result* result, mslam_hip_icp_record* record,
+                           int record_capacity);
+
 /* ---- test / debug access to intermediate stages (host copies; synchronises) -----------------------*/
 enum
 {

@@ -16,6 +16,7 @@ which registers it as module `modular_slam_amd`.)
 """
 import contextlib
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -90,6 +91,8 @@ ABI_SYMBOLS = [
     "mslam_hip_tsdf_create", "mslam_hip_tsdf_destroy", "mslam_hip_tsdf_info", "mslam_hip_tsdf_add_frame",
     "mslam_hip_tsdf_add_frame_dev", "mslam_hip_tsdf_get_frame", "mslam_hip_tsdf_update_poses", "mslam_hip_tsdf_remove_frame",
     "mslam_hip_tsdf_read", "mslam_hip_tsdf_extract", "mslam_hip_tsdf_raycast", "mslam_hip_tsdf_raycast_dev",
+    "mslam_hip_icp_point_plane", "mslam_hip_icp_point_plane_dev", "mslam_hip_icp_linearize", "mslam_hip_tsdf_icp",
+    "mslam_hip_tsdf_icp_dev",
 ]
 
 
@@ -171,6 +174,27 @@ class TsdfRaycastParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double), ("z_near", C.c_double), ("z_far", C.c_double), ("step", C.c_double), ("coarse", C.c_int32),
                 ("min_weight", C.c_int32)]
+
+
+class IcpParams(C.Structure):
+    """mslam_hip_icp_params: the frame camera, the model camera, the levels (stride, iterations), the gates, min_pairs and the
+    step tolerances of frame-to-model alignment"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("factor", C.c_float), ("n_levels", C.c_int32), ("fx", C.c_double),
+                ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("max_depth", C.c_double), ("model_width", C.c_int32),
+                ("model_height", C.c_int32), ("mfx", C.c_double), ("mfy", C.c_double), ("mcx", C.c_double), ("mcy", C.c_double),
+                ("stride", C.c_int32 * 4), ("iterations", C.c_int32 * 4), ("dist_max", C.c_double), ("cos_min", C.c_double),
+                ("min_pairs", C.c_int32), ("reserved", C.c_int32), ("rot_tol", C.c_double), ("trans_tol", C.c_double)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("count", C.c_int32), ("level", C.c_int32),
+                ("cost", C.c_double), ("pivots", C.c_double * 6)]
+
+
+ICP_CONVERGED, ICP_ITERATIONS, ICP_DEGENERATE = range(3)
+ICP_LEVELS = ((4, 4), (2, 5), (1, 10))
+ICP_DIST_MAX, ICP_COS_MIN, ICP_MIN_PAIRS = 0.1, math.cos(0.6), 64
+ICP_RECORD = np.dtype([("level", "<i4"), ("count", "<i4"), ("cost", "<f8"), ("rot2", "<f8"), ("trans2", "<f8")])
 
 
 class RelocCandidate(C.Structure):
@@ -756,6 +780,95 @@ class Context:
         nrm = np.zeros((q.height, q.width, 3), np.float32) if normals else None
         self._chk(self.L.mslam_hip_tsdf_raycast(self._h, C.byref(q), _p(R), _p(t), _p(depth), _p(xyz), _p(nrm), hits))
         return (depth, xyz, nrm, n.value) if with_hits else (depth, xyz, nrm)
+
+    # ---- frame-to-model alignment: point-to-plane ICP (k_icp.hip) ---------------------------------
+    @staticmethod
+    def icp_params(camera, model_camera=None, levels=ICP_LEVELS, dist_max=ICP_DIST_MAX, cos_min=ICP_COS_MIN,
+                   min_pairs=ICP_MIN_PAIRS, rot_tol=0.0, trans_tol=0.0):
+        """-> IcpParams.  camera = dict(width, height, focal, principal, factor, max_depth) is the frame's, model_camera =
+        dict(width, height, focal, principal) the model's (None: left zero, for tsdf_icp)."""
+        q = IcpParams()
+        q.width, q.height, q.factor = int(camera["width"]), int(camera["height"]), float(camera["factor"])
+        q.fx, q.fy = (float(v) for v in camera["focal"])
+        q.cx, q.cy = (float(v) for v in camera["principal"])
+        q.max_depth = float(camera["max_depth"])
+        if model_camera is not None:
+            q.model_width, q.model_height = int(model_camera["width"]), int(model_camera["height"])
+            q.mfx, q.mfy = (float(v) for v in model_camera["focal"])
+            q.mcx, q.mcy = (float(v) for v in model_camera["principal"])
+        levels = [(int(a), int(b)) for a, b in levels]
+        q.n_levels = len(levels) if len(levels) <= 4 else 5    # (more than 4 is the library's to refuse)
+        for l, (stride, iterations) in enumerate(levels[:4]):
+            q.stride[l], q.iterations[l] = stride, iterations
+        q.dist_max, q.cos_min, q.min_pairs = float(dist_max), float(cos_min), int(min_pairs)
+        q.rot_tol, q.trans_tol = float(rot_tol), float(trans_tol)
+        return q
+
+    @staticmethod
+    def _icp_out(R, t, res, rec):
+        return dict(R=R, t=t, status=res.status, iterations=res.iterations, count=res.count, level=res.level, cost=res.cost,
+                    pivots=np.array(list(res.pivots), np.float64), record=rec[:max(res.iterations, 0)], result=res)
+
+    def icp_point_plane(self, depth, camera, model_xyz, model_normal, model_camera, Rm, tm, R0=None, t0=None, **kw):
+        """Aligns a depth frame (u16 [h][w] with its camera) to a model given as world-frame xyz and normal images (f32
+        [mh][mw][3], a zero normal: no surface) seen through model_camera from the world -> camera pose (Rm, tm), from the
+        world -> camera guess (R0, t0) (default: the model's pose) -> dict(R, t, status, iterations, count, level, cost,
+        pivots, record, result).  The keywords are icp_params'.  The images are host arrays, or all three int device
+        addresses."""
+        q = self.icp_params(camera, model_camera, **kw)
+        Rm, tm = self._tsdf_pose(Rm, tm)
+        R0, t0 = (Rm, tm) if R0 is None else self._tsdf_pose(R0, t0)
+        R, t, res = np.zeros((3, 3), np.float64), np.zeros(3, np.float64), IcpResult()
+        rec = np.zeros(256, ICP_RECORD)
+        if isinstance(depth, (int, np.integer)):
+            self._chk(self.L.mslam_hip_icp_point_plane_dev(self._h, C.byref(q), C.c_void_p(int(depth)), C.c_void_p(int(model_xyz)),
+                                                           C.c_void_p(int(model_normal)), _p(Rm), _p(tm), _p(R0), _p(t0), _p(R),
+                                                           _p(t), C.byref(res), _p(rec), len(rec)))
+            return self._icp_out(R, t, res, rec)
+        d = np.ascontiguousarray(depth, np.uint16)
+        xyz, nrm = np.ascontiguousarray(model_xyz, np.float32), np.ascontiguousarray(model_normal, np.float32)
+        if d.shape != (q.height, q.width) or xyz.shape != (q.model_height, q.model_width, 3) or nrm.shape != xyz.shape:
+            raise MslamHipError(E_INVALID, "icp_point_plane: depth %r, model %r / %r do not fit the cameras" % (d.shape, xyz.shape, nrm.shape))
+        self._chk(self.L.mslam_hip_icp_point_plane(self._h, C.byref(q), _p(d), _p(xyz), _p(nrm), _p(Rm), _p(tm), _p(R0), _p(t0),
+                                                   _p(R), _p(t), C.byref(res), _p(rec), len(rec)))
+        return self._icp_out(R, t, res, rec)
+
+    def icp_linearize(self, depth, camera, model_xyz, model_normal, model_camera, Rm, tm, R, t, stride=1, **kw):
+        """One linearisation at the world -> camera pose (R, t) over the pixels of `stride` -> (A21 f64 [21], g f64 [6], count,
+        cost): the upper triangle of J^T J row-major, J^T r, the pairs, sum r r."""
+        q = self.icp_params(camera, model_camera, **kw)
+        Rm, tm = self._tsdf_pose(Rm, tm)
+        R, t = self._tsdf_pose(R, t)
+        d = np.ascontiguousarray(depth, np.uint16)
+        xyz, nrm = np.ascontiguousarray(model_xyz, np.float32), np.ascontiguousarray(model_normal, np.float32)
+        if d.shape != (q.height, q.width) or xyz.shape != (q.model_height, q.model_width, 3) or nrm.shape != xyz.shape:
+            raise MslamHipError(E_INVALID, "icp_linearize: depth %r, model %r / %r do not fit the cameras" % (d.shape, xyz.shape, nrm.shape))
+        A, g, n, cost = np.zeros(21, np.float64), np.zeros(6, np.float64), C.c_int(0), C.c_double(0)
+        self._chk(self.L.mslam_hip_icp_linearize(self._h, C.byref(q), _p(d), _p(xyz), _p(nrm), _p(Rm), _p(tm), _p(R), _p(t),
+                                                 int(stride), _p(A), _p(g), C.byref(n), C.byref(cost)))
+        return A, g, n.value, cost.value
+
+    def tsdf_icp(self, depth, R0, t0, raycast=None, **kw):
+        """Renders the volume at the world -> camera guess (R0, t0) (raycast: keywords of tsdf_raycast_params, by default its
+        defaults) and aligns the depth frame (u16 [h][w] of the volume's camera: a host array or an int device address) to the
+        render -> the dict of icp_point_plane.  The keywords are icp_params'."""
+        v, _ = self.tsdf_info()
+        rq = self.tsdf_raycast_params(R0, t0, **(raycast or {}))
+        q = self.icp_params(dict(width=v.width, height=v.height, focal=(v.fx, v.fy), principal=(v.cx, v.cy), factor=v.factor,
+                                 max_depth=v.max_depth), None, **kw)
+        R0, t0 = self._tsdf_pose(R0, t0)
+        R, t, res = np.zeros((3, 3), np.float64), np.zeros(3, np.float64), IcpResult()
+        rec = np.zeros(256, ICP_RECORD)
+        if isinstance(depth, (int, np.integer)):
+            self._chk(self.L.mslam_hip_tsdf_icp_dev(self._h, C.byref(q), C.byref(rq), C.c_void_p(int(depth)), _p(R0), _p(t0), _p(R),
+                                                    _p(t), C.byref(res), _p(rec), len(rec)))
+            return self._icp_out(R, t, res, rec)
+        d = np.ascontiguousarray(depth, np.uint16)
+        if d.shape != (v.height, v.width):
+            raise MslamHipError(E_INVALID, "tsdf_icp: depth is %r, the volume's camera %d x %d" % (d.shape, v.width, v.height))
+        self._chk(self.L.mslam_hip_tsdf_icp(self._h, C.byref(q), C.byref(rq), _p(d), _p(R0), _p(t0), _p(R), _p(t), C.byref(res),
+                                            _p(rec), len(rec)))
+        return self._icp_out(R, t, res, rec)
 
     # ---- min-MSE PnP (MinMseTracker, ceres_reprojection_error_pnp.cpp:18-110) --------------------
     def pnp_min_mse(self, object_points, image_points, focal=(525.0, 525.0), principal=(319.5, 239.5), rvec=(0, 0, 0),
@@ -2412,7 +2525,16 @@ class HipKeyframeTracker:
     half a voxel at the far end of the range (an infinite max_depth: 0).  NOT MEASURED: whether these defaults are good on any
     sequence.  A keyframe kf_cull removes leaves the volume too.  self.dense_poses maps keyframe id -> (R, t) it is
     integrated at; self.dense_results gains one dict per update call: listed, moved.  Without local_ba the poses never move
-    and nothing is re-integrated.  None (the default): nothing new runs."""
+    and nothing is re-integrated.  None (the default): nothing new runs.
+
+    dense_icp = dict(levels, dist_max, cos_min, min_pairs, max_rms) (every key optional; needs dense_map; an extension):
+    frame-to-model alignment where features fail.  When a frame is not tracked and the volume exists, Context.tsdf_icp aligns
+    the frame's depth image to the volume's render at the current pose, from the current pose.  The result is accepted when
+    its status is not DEGENERATE and sqrt(cost / count), the RMS point-to-plane residual in metres, is <= max_rms (default:
+    one voxel edge; NOT MEASURED on any real sequence): self.R, self.tvec and self.rvec become that pose and the frame's dict
+    gains dense_tracked=True; either way the result is reported under `dense` and relocalisation runs as before.  `tracked`
+    stays False: the keyframe policy, the store and the back end never see an ICP pose.  A frame that tracks is untouched, so
+    a run in which every frame tracks is the same with and without the option.  None (the default): nothing new runs."""
 
     LOCAL_MAP_ID = 0x7fffffff
     FUSE_KEEP_ID, FUSE_DROP_ID = 0x7ffffffe, 0x7ffffffd
@@ -2426,7 +2548,7 @@ class HipKeyframeTracker:
                  loop_fuse_world_distance=0.1, ba_prune=False, kf_cull=False, cull_min_observers=3, cull_ratio=0.9, lm_cull=False,
                  lm_cull_min_observers=2, lm_cull_age=2, ba_loss=None, loop_fusion_keyframes=False, union_descriptor=None,
                  pose_graph_solver="dense", ba_global_solver="dense", pose_graph_loss=None, loop_covariance=False,
-                 ba_global_pcg=None, pose_graph_pcg=None, track_pose=None, dense_map=None, dense_update=None):
+                 ba_global_pcg=None, pose_graph_pcg=None, track_pose=None, dense_map=None, dense_update=None, dense_icp=None):
         self.ctx = ctx
         self.dense_map, self.dense_update, self.dense_poses, self.dense_results = None, None, {}, []
         if dense_map is not None:
@@ -2441,6 +2563,14 @@ class HipKeyframeTracker:
         elif dense_update is not None:
             raise MslamHipError(E_INVALID, "HipKeyframeTracker: dense_update needs dense_map")
         self._dense_created = False
+        self.dense_icp = None
+        if dense_icp is not None:
+            if self.dense_map is None:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: dense_icp needs dense_map")
+            if set(dense_icp) - {"levels", "dist_max", "cos_min", "min_pairs", "max_rms"}:
+                raise MslamHipError(E_INVALID, "HipKeyframeTracker: dense_icp is dict([levels, dist_max, cos_min, min_pairs, max_rms])")
+            self.dense_icp = dict(dense_icp)
+            self.dense_icp.setdefault("max_rms", float(self.dense_map["voxel"]))
         if track_pose is not None:
             if len(track_pose) != 2 or track_pose[0] not in _TRACK_POSE_NAMES:
                 raise MslamHipError(E_INVALID, "HipKeyframeTracker: track_pose is None or (\"pnp\" / \"align\", max_distance)")
@@ -2602,6 +2732,7 @@ class HipKeyframeTracker:
                 if self.kf_cull:
                     self._cull(new_id)
         else:
+            self._dense_track(depth, out)
             reloc = self.ctx.relocalize(desc, xy, vote, self.focal, self.principal, None, self.ratio, self.iterations,
                                         self.reprojection_error, seed, min_inliers=self.reloc_min_inliers)
             if reloc["best"] >= 0:
@@ -2672,6 +2803,7 @@ class HipKeyframeTracker:
                         if self.kf_cull:
                             self._cull(new_id)
                 else:
+                    self._dense_track(depths[i + s], o)
                     reloc = self.ctx.relocalize(descs[i + s], xys[i + s], vote, self.focal, self.principal, None, self.ratio,
                                                 self.iterations, self.reprojection_error, seed + s,
                                                 min_inliers=self.reloc_min_inliers)
@@ -2721,6 +2853,31 @@ class HipKeyframeTracker:
         if R is None:
             R, t = self.R, self.tvec
         return self.ctx.tsdf_raycast(R, t, **kw)
+
+    def dense_align(self, depth, R=None, t=None, **kw):
+        """dense_map: Context.tsdf_icp of a depth image (u16 [h][w] of the volume's camera) against the volume's render at the
+        world -> camera guess (R, t), by default the pose of the latest tracked frame; the keywords are tsdf_icp's.  Reads
+        the volume only and changes no state of the tracker."""
+        if self.dense_map is None or not self._dense_created:
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker.dense_align needs dense_map and a first keyframe")
+        if (R is None) != (t is None):
+            raise MslamHipError(E_INVALID, "HipKeyframeTracker.dense_align: R and t go together")
+        if R is None:
+            R, t = self.R, self.tvec
+        return self.ctx.tsdf_icp(depth, R, t, **kw)
+
+    def _dense_track(self, depth, out):
+        """dense_icp, for a frame that was not tracked: the frame-to-model pose takes the place of the kept one when it is
+        accepted; `out` gains dense and dense_tracked"""
+        if self.dense_icp is None or not self._dense_created:
+            return
+        kw = {k: v for k, v in self.dense_icp.items() if k != "max_rms"}
+        res = self.ctx.tsdf_icp(depth, self.R, self.tvec, **kw)
+        ok = res["status"] != ICP_DEGENERATE and res["count"] > 0 and math.sqrt(res["cost"] / res["count"]) <= self.dense_icp["max_rms"]
+        if ok:
+            self.R, self.tvec = res["R"], res["t"]
+            self.rvec = rotation_to_rvec(self.R)
+        out["dense"], out["dense_tracked"] = res, bool(ok)
 
     @staticmethod
     def dense_pose_change(R0, t0, R1, t1):

@@ -398,6 +398,8 @@ void mslam_hip_destroy(mslam_hip_ctx* c)
         reloc_destroy(c->reloc);
     if(c->tsdf)
         tsdf_destroy(c->tsdf);
+    if(c->icp)
+        icp_destroy(c->icp);
     if(c->own_stream && c->stream)
         (void)hipStreamDestroy(c->stream);
     delete c; // every device and page-locked block goes with its owner (devmem.hpp)

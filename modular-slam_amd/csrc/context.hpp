@@ -15,6 +15,8 @@ struct RelocState; // k_reloc.hip: keyframe store + scratch of mslam_hip_relocal
 void reloc_destroy(RelocState*);
 struct TsdfState; // tsdf.hpp / k_tsdf.hip: the dense map of mslam_hip_tsdf_*
 void tsdf_destroy(TsdfState*);
+struct IcpState; // icp.hpp / k_icp.hip: the scratch of mslam_hip_icp_* and mslam_hip_tsdf_icp*
+void icp_destroy(IcpState*);
 void set_blur_taps(const int* taps);
 void build_blur_waves(const Geometry& g, int first_level, std::vector<BlurWave>& out);
 
@@ -207,6 +209,7 @@ struct mslam_hip_ctx
     mslam::BowState* bow = nullptr;
     mslam::RelocState* reloc = nullptr;
     mslam::TsdfState* tsdf = nullptr;
+    mslam::IcpState* icp = nullptr;
 
     bool profiling = false;      // mode 1: every stage timed, everything serialised on the context's stream
     bool inplace_timing = false; // mode 2: every stage launch is timed in place on the stream it runs on

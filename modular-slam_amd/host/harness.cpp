@@ -99,6 +99,10 @@
 //                                    ILandmarkCuller::cullLandmarks of the relocalizer adapter on the scene's entries, listed
 //                                    keyframes and candidates: "lmcull found N removed M", one "lm <id> <observers>" line per
 //                                    culled landmark id, then "entry <id> <count>" for every entry in scene order
+//        mslam_harness <plugin.so> --dense <scene> --icp <frames> [--dump <path>]
+//                                    the same, then IDenseAligner (a dynamic_cast of the dense map) aligns every frame of the
+//                                    frames file (tests/tsdf_icp_ref.py::write_frames) to the volume: "icp frame F status S
+//                                    iterations N pairs C"; --dump: tests/tsdf_icp_ref.py::read_dump
 //        mslam_harness <plugin.so> --dense <scene> --raycast <views> [--dump <path>]
 //                                    the same, then IDenseMapRenderer (a dynamic_cast of the dense map) renders every view of
 //                                    the views file (tests/tsdf_raycast_ref.py::write_views): "raycast view V size W x H hits
@@ -281,7 +285,8 @@ int main(int argc, char** argv)
             return 0;
         }
         const bool denseRaycast = (argc == 6 || (argc == 8 && std::strcmp(argv[6], "--dump") == 0)) && std::strcmp(argv[4], "--raycast") == 0;
-        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--dump") == 0) || denseRaycast) && std::strcmp(argv[2], "--dense") == 0)
+        const bool denseIcp = (argc == 6 || (argc == 8 && std::strcmp(argv[6], "--dump") == 0)) && std::strcmp(argv[4], "--icp") == 0;
+        if((argc == 4 || (argc == 6 && std::strcmp(argv[4], "--dump") == 0) || denseRaycast || denseIcp) && std::strcmp(argv[2], "--dense") == 0)
         {
             // little endian: magic[8]; mslam_hip_tsdf_params' layout (4 i32, 6 f64, 2 i32, f32, i32, 4 f64); i32 F, U, M, min_weight;
             // F x {i32 id, 0; f64 R[9], t[3]; u16 depth[height][width]}; U x {i32 id, 0; f64 R[9], t[3]}; M x i32 id
@@ -337,6 +342,58 @@ int main(int argc, char** argv)
                     view.params.zNear = real[4], view.params.zFar = real[5], view.params.step = real[6];
                     view.params.coarse = march[0], view.params.minWeight = march[1];
                     views.push_back(view);
+                }
+                if(!good)
+                {
+                    std::fprintf(stderr, "cannot read %s\n", argv[5]);
+                    return 5;
+                }
+            }
+            // --icp <frames> (tests/tsdf_icp_ref.py::write_frames), little endian: magic[8]; i32 F, 0; F x {the render as in a views
+            // file without its pose (2 i32, 7 f64, 2 i32); i32 n_levels, min_pairs, stride[4], iterations[4]; f64 dist_max, cos_min,
+            // rot_tol, trans_tol; f64 R0[9], t0[3]; u16 depth[height][width] of the volume's camera}
+            struct IcpFrame
+            {
+                mslam::DenseRenderParams render;
+                mslam::DenseAlignParams params;
+                mslam::DensePose guess;
+                std::vector<std::uint16_t> depth;
+            };
+            std::vector<IcpFrame> icpFrames;
+            if(denseIcp)
+            {
+                std::ifstream fin(argv[5], std::ios::binary);
+                char fmagic[8] = {0};
+                std::int32_t nFrames[2] = {0, 0};
+                fin.read(fmagic, 8);
+                fin.read(reinterpret_cast<char*>(nFrames), sizeof(nFrames));
+                bool good = fin && std::memcmp(fmagic, "MSTSDFI1", 8) == 0 && nFrames[0] >= 0 && nFrames[0] <= (1 << 16);
+                for(std::int32_t f = 0; good && f < nFrames[0]; ++f)
+                {
+                    std::int32_t size[2] = {0, 0}, march[2] = {0, 0}, ints[10] = {0};
+                    double real[7] = {0}, gates[4] = {0};
+                    IcpFrame fr;
+                    fin.read(reinterpret_cast<char*>(size), sizeof(size));
+                    fin.read(reinterpret_cast<char*>(real), sizeof(real));
+                    fin.read(reinterpret_cast<char*>(march), sizeof(march));
+                    fin.read(reinterpret_cast<char*>(ints), sizeof(ints));
+                    fin.read(reinterpret_cast<char*>(gates), sizeof(gates));
+                    fin.read(reinterpret_cast<char*>(fr.guess.R), sizeof(fr.guess.R));
+                    fin.read(reinterpret_cast<char*>(fr.guess.t), sizeof(fr.guess.t));
+                    fr.depth.resize(static_cast<std::size_t>(cam[0]) * cam[1]);
+                    fin.read(reinterpret_cast<char*>(fr.depth.data()), static_cast<std::streamsize>(fr.depth.size() * 2));
+                    good = static_cast<bool>(fin) && ints[0] >= 0 && ints[0] <= 4;
+                    fr.render.width = size[0], fr.render.height = size[1];
+                    fr.render.camera.focal = mslam::Vector2(real[0], real[1]);
+                    fr.render.camera.principalPoint = mslam::Vector2(real[2], real[3]);
+                    fr.render.zNear = real[4], fr.render.zFar = real[5], fr.render.step = real[6];
+                    fr.render.coarse = march[0], fr.render.minWeight = march[1];
+                    fr.params.levels.clear();
+                    for(std::int32_t l = 0; good && l < ints[0]; ++l)
+                        fr.params.levels.emplace_back(ints[2 + l], ints[6 + l]);
+                    fr.params.minPairs = ints[1];
+                    fr.params.distMax = gates[0], fr.params.cosMin = gates[1], fr.params.rotTol = gates[2], fr.params.transTol = gates[3];
+                    icpFrames.push_back(std::move(fr));
                 }
                 if(!good)
                 {
@@ -432,6 +489,49 @@ int main(int argc, char** argv)
                         out.write(reinterpret_cast<const char*>(r.depth.data()), static_cast<std::streamsize>(r.depth.size() * 4));
                         out.write(reinterpret_cast<const char*>(r.points.data()), static_cast<std::streamsize>(r.points.size() * 4));
                         out.write(reinterpret_cast<const char*>(r.normals.data()), static_cast<std::streamsize>(r.normals.size() * 4));
+                    }
+                }
+                if(argc == 8 && !out)
+                {
+                    std::fprintf(stderr, "cannot write %s\n", argv[7]);
+                    return 5;
+                }
+                return 0;
+            }
+            if(denseIcp)
+            {
+                // the dump: magic[8]; i32 F, 0; F x {f64 R[9], t[3]; i32 status, iterations, count, level; f64 cost, pivots[6];
+                // i32 rows, 0; rows x {i32 level, count; f64 cost, rot2, trans2}}
+                auto* aligner = dynamic_cast<mslam::IDenseAligner*>(dense.get());
+                if(!aligner)
+                {
+                    std::fprintf(stderr, "the dense map offers no IDenseAligner\n");
+                    return 3;
+                }
+                std::ofstream out;
+                if(argc == 8)
+                {
+                    out.open(argv[7], std::ios::binary);
+                    const std::int32_t n[2] = {static_cast<std::int32_t>(icpFrames.size()), 0};
+                    out.write("MSTSDFA1", 8);
+                    out.write(reinterpret_cast<const char*>(n), sizeof(n));
+                }
+                for(std::size_t f = 0; f < icpFrames.size(); ++f)
+                {
+                    const mslam::DenseAlignResult r = aligner->align(icpFrames[f].depth, icpFrames[f].guess, icpFrames[f].params, icpFrames[f].render);
+                    std::printf("icp frame %zu status %d iterations %d pairs %d\n", f, r.status, r.iterations, r.count);
+                    if(argc == 8)
+                    {
+                        const std::int32_t h[4] = {r.status, r.iterations, r.count, r.level};
+                        const std::int32_t rows[2] = {static_cast<std::int32_t>(r.record.size()), 0};
+                        out.write(reinterpret_cast<const char*>(r.pose.R), sizeof(r.pose.R));
+                        out.write(reinterpret_cast<const char*>(r.pose.t), sizeof(r.pose.t));
+                        out.write(reinterpret_cast<const char*>(h), sizeof(h));
+                        out.write(reinterpret_cast<const char*>(&r.cost), 8);
+                        out.write(reinterpret_cast<const char*>(r.pivots), sizeof(r.pivots));
+                        out.write(reinterpret_cast<const char*>(rows), sizeof(rows));
+                        static_assert(sizeof(mslam::DenseAlignRecord) == 32, "the dump's row");
+                        out.write(reinterpret_cast<const char*>(r.record.data()), static_cast<std::streamsize>(r.record.size() * 32));
                     }
                 }
                 if(argc == 8 && !out)

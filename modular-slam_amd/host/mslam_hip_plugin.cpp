@@ -1032,7 +1032,7 @@ class HipRigidAligner : public IRigidAligner
 };
 
 // The dense TSDF map (mslam_hip_tsdf_*): no reference counterpart.  The context has no detector; the volume lives in it.
-class HipDenseMap : public IDenseMap, public IDenseMapRenderer
+class HipDenseMap : public IDenseMap, public IDenseMapRenderer, public IDenseAligner
 {
   public:
     void create(const DenseMapParams& q) override
@@ -1124,6 +1124,38 @@ class HipDenseMap : public IDenseMap, public IDenseMapRenderer
         ctx.ensure(0, 0);
         check("mslam_hip_tsdf_raycast", mslam_hip_tsdf_raycast(ctx.h, &p, pose.R, pose.t, out.depth.data(), out.points.data(),
                                                                normals ? out.normals.data() : nullptr, &out.hits));
+        return out;
+    }
+    DenseAlignResult align(const std::vector<std::uint16_t>& depth, const DensePose& guess, const DenseAlignParams& q,
+                           const DenseRenderParams& render) override
+    {
+        ctx.ensure(0, 0);
+        check("mslam_hip_tsdf_info", mslam_hip_tsdf_info(ctx.h, &params, nullptr));
+        if(depth.size() != static_cast<std::size_t>(params.width) * static_cast<std::size_t>(params.height))
+            throw std::invalid_argument("HipDenseMap::align: the depth image is not width x height of the volume's camera");
+        if(q.levels.empty() || q.levels.size() > MSLAM_HIP_ICP_MAX_LEVELS)
+            throw std::invalid_argument("HipDenseMap::align: 1..4 levels");
+        mslam_hip_icp_params p{};
+        p.width = params.width, p.height = params.height, p.factor = params.factor;
+        p.fx = params.fx, p.fy = params.fy, p.cx = params.cx, p.cy = params.cy, p.max_depth = params.max_depth;
+        p.n_levels = static_cast<std::int32_t>(q.levels.size());
+        for(std::size_t l = 0; l < q.levels.size(); ++l)
+            p.stride[l] = q.levels[l].first, p.iterations[l] = q.levels[l].second;
+        p.dist_max = q.distMax, p.cos_min = q.cosMin, p.min_pairs = q.minPairs, p.rot_tol = q.rotTol, p.trans_tol = q.transTol;
+        mslam_hip_tsdf_raycast_params r{};
+        r.width = render.width, r.height = render.height;
+        r.fx = render.camera.focal.x(), r.fy = render.camera.focal.y();
+        r.cx = render.camera.principalPoint.x(), r.cy = render.camera.principalPoint.y();
+        r.z_near = render.zNear, r.z_far = render.zFar, r.step = render.step, r.coarse = render.coarse, r.min_weight = render.minWeight;
+        DenseAlignResult out;
+        mslam_hip_icp_result res{};
+        std::vector<mslam_hip_icp_record> rows(MSLAM_HIP_ICP_MAX_ITERATIONS);
+        check("mslam_hip_tsdf_icp", mslam_hip_tsdf_icp(ctx.h, &p, &r, depth.data(), guess.R, guess.t, out.pose.R, out.pose.t, &res,
+                                                       rows.data(), static_cast<int>(rows.size())));
+        out.status = res.status, out.iterations = res.iterations, out.count = res.count, out.level = res.level, out.cost = res.cost;
+        std::copy(res.pivots, res.pivots + 6, out.pivots);
+        for(int i = 0; i < res.iterations; ++i)
+            out.record.push_back(DenseAlignRecord{rows[i].level, rows[i].count, rows[i].cost, rows[i].rot2, rows[i].trans2});
         return out;
     }
 

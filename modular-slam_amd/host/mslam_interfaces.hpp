@@ -610,6 +610,41 @@ class IDenseMapRenderer
     virtual ~IDenseMapRenderer() = default;
 };
 
+// extension: frame-to-model alignment on the dense map (mslam_hip_tsdf_icp): the volume is rendered at the guess through the
+// render camera of `render` (every value explicit, as for IDenseMapRenderer), and a depth image of the volume's own camera is
+// aligned to that render by point-to-plane ICP over `levels` of (stride, iterations), at most four and 256 iterations in all.
+// The pose has one defined value, bit for bit (include/mslam_hip.h has the rule).  status: 0 CONVERGED (the last level ended by
+// the step test), 1 ITERATIONS, 2 DEGENERATE (fewer than minPairs pairs or a pivot that is not positive: pose is the guess).
+// The pivots of the last linearisation are reported; weak geometry is the caller's to judge.  Argument errors throw.
+// Offered by hipDenseMapFactory's object: dynamic_cast<IDenseAligner*>(denseMap.get()).
+struct DenseAlignParams
+{
+    std::vector<std::pair<int, int>> levels = {{4, 4}, {2, 5}, {1, 10}}; // (stride, iterations)
+    double distMax = 0.1;               // metres between a frame point and its model point
+    double cosMin = 0.8253356149096783; // cos(0.6): between the two normals
+    int minPairs = 64;
+    double rotTol = 0, transTol = 0; // the step test; 0: every iteration runs
+};
+struct DenseAlignRecord
+{
+    std::int32_t level, count;
+    double cost, rot2, trans2;
+};
+struct DenseAlignResult
+{
+    DensePose pose; // world -> camera
+    int status = 2, iterations = 0, count = 0, level = 0;
+    double cost = 0, pivots[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<DenseAlignRecord> record; // one row per linearisation
+};
+class IDenseAligner
+{
+  public:
+    virtual DenseAlignResult align(const std::vector<std::uint16_t>& depth, const DensePose& guess, const DenseAlignParams& params,
+                                   const DenseRenderParams& render) = 0;
+    virtual ~IDenseAligner() = default;
+};
+
 // ---- extension (not in the reference): landmark fusion after a loop closure (mslam_hip_kf_fuse) ---------------------------
 // The reference's closeLoop is an empty body (rgbd_feature_frontend.cpp:577-580); the model is ORB-SLAM's SearchAndFuse.
 // The landmarks of `dropEntry` that duplicate landmarks of `keepEntry` — both projected under one world -> camera pose, each
