@@ -1183,25 +1183,30 @@ class Context:
         return n.value
 
     # ---- landmark fusion (an extension: the reference's closeLoop is empty) ------------------------
-    def _fuse_call(self, entry, keep_id, drop_id, R, t, radius, max_distance, ratio, max_world_distance, focal, principal,
-                   width, height, capacity, tail):
-        R = np.ascontiguousarray(R, np.float64).reshape(9)
-        t = np.ascontiguousarray(t, np.float64).reshape(3)
+    def _fuse_pairs(self, entry, head, names, R, t, radius, max_distance, ratio, max_world_distance, focal, principal, width, height,
+                    capacity, tail):
+        """a fusion call: `head` = the C arguments that name the entries, `names` = its pair arrays in the C argument order
+        (the *_lid are i64, the others i32), each of `capacity` rows (default: max_keypoints, which holds every result: a
+        call has at most one pair per keep landmark) -> dict of the arrays cut to the count; E_CAPACITY raises carrying
+        `needed`, the count"""
         cap = int(self.params.max_keypoints if capacity is None else capacity)
-        kp, dp, di = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
-        kl, dl = (np.zeros(max(cap, 1), np.int64) for _ in range(2))
+        cols = {k: np.zeros(max(cap, 1), np.int64 if k.endswith("_lid") else np.int32) for k in names}
         n = C.c_int(0)
-        rc = entry(self._h, int(keep_id), int(drop_id), _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]),
-                   C.c_double(principal[0]), C.c_double(principal[1]), int(self.params.width if width is None else width),
+        rc = entry(self._h, *head, _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]), C.c_double(principal[0]),
+                   C.c_double(principal[1]), int(self.params.width if width is None else width),
                    int(self.params.height if height is None else height), C.c_double(radius), int(max_distance), C.c_double(ratio),
-                   C.c_double(max_world_distance), _p(kp), _p(dp), _p(kl), _p(dl), _p(di), cap, C.byref(n), *tail)
+                   C.c_double(max_world_distance), *(_p(v) for v in cols.values()), cap, C.byref(n), *tail)
         if rc == E_CAPACITY:
             e = MslamHipError(rc, (self.L.mslam_hip_last_error(self._h) or b"").decode())
             e.needed = n.value
             raise e
         self._chk(rc)
-        k = n.value
-        return dict(keep_pos=kp[:k].copy(), drop_pos=dp[:k].copy(), keep_lid=kl[:k].copy(), drop_lid=dl[:k].copy(), dist=di[:k].copy())
+        return {k: v[:n.value].copy() for k, v in cols.items()}
+
+    def _fuse_call(self, entry, keep_id, drop_id, R, t, *rest):
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        return self._fuse_pairs(entry, (int(keep_id), int(drop_id)), ("keep_pos", "drop_pos", "keep_lid", "drop_lid", "dist"), R, t, *rest)
 
     def kf_fuse_search(self, keep_id, drop_id, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf,
                        focal=(525.0, 525.0), principal=(319.5, 239.5), width=None, height=None, capacity=None):
@@ -1235,32 +1240,14 @@ class Context:
         return out
 
     # ---- landmark fusion into many target entries (SearchAndFuse's loop over the connected keyframes, one call) ----
-    def _fuse_multi_call(self, entry, keep_id, drop_ids, R, t, radius, max_distance, ratio, max_world_distance, focal, principal,
-                         width, height, capacity, tail):
-        """the search or the fused call, as _fuse_call: the default capacity, max_keypoints, holds every result (a call has
-        at most one pair per keep landmark), a smaller one of the caller's gives E_CAPACITY carrying `needed`"""
+    def _fuse_multi_call(self, entry, keep_id, drop_ids, R, t, *rest):
         ids = np.ascontiguousarray(drop_ids, np.int32).reshape(-1)
         R = np.ascontiguousarray(R, np.float64).reshape(-1)
         t = np.ascontiguousarray(t, np.float64).reshape(-1)
         if len(R) != 9 * len(ids) or len(t) != 3 * len(ids):
             raise MslamHipError(E_INVALID, "kf_fuse_multi: %d drop ids, %d R values, %d t values" % (len(ids), len(R), len(t)))
-        cap = int(self.params.max_keypoints if capacity is None else capacity)
-        tg, kp, dp, di = (np.zeros(max(cap, 1), np.int32) for _ in range(4))
-        kl, dl = (np.zeros(max(cap, 1), np.int64) for _ in range(2))
-        n = C.c_int(0)
-        rc = entry(self._h, int(keep_id), _p(ids), len(ids), _p(R), _p(t), C.c_double(focal[0]), C.c_double(focal[1]),
-                   C.c_double(principal[0]), C.c_double(principal[1]), int(self.params.width if width is None else width),
-                   int(self.params.height if height is None else height), C.c_double(radius), int(max_distance),
-                   C.c_double(ratio), C.c_double(max_world_distance), _p(tg), _p(kp), _p(dp), _p(kl), _p(dl), _p(di), cap,
-                   C.byref(n), *tail)
-        if rc == E_CAPACITY:
-            e = MslamHipError(rc, (self.L.mslam_hip_last_error(self._h) or b"").decode())
-            e.needed = n.value
-            raise e
-        self._chk(rc)
-        k = n.value
-        return dict(target=tg[:k].copy(), keep_pos=kp[:k].copy(), drop_pos=dp[:k].copy(), keep_lid=kl[:k].copy(),
-                    drop_lid=dl[:k].copy(), dist=di[:k].copy())
+        return self._fuse_pairs(entry, (int(keep_id), _p(ids), len(ids)), ("target", "keep_pos", "drop_pos", "keep_lid", "drop_lid", "dist"),
+                                R, t, *rest)
 
     def kf_fuse_search_multi(self, keep_id, drop_ids, R, t, radius, max_distance=50, ratio=0.7, max_world_distance=np.inf,
                              focal=(525.0, 525.0), principal=(319.5, 239.5), width=None, height=None, capacity=None):

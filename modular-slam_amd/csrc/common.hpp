@@ -375,21 +375,7 @@ struct GuidedArgs
     int32_t *idx0, *idx1, *dist0, *dist1; // [rows][cap], MatchArgs' layout
     int32_t* n_cand;         // [rows][cap] or nullptr
 };
-// (shared by k_match_guided and k_fuse_search) the cells [lo, hi] (inclusive) a window [u - radius, u + radius] can hold keypoints of, along one axis of `extent` pixels;
-// false: none.  Conservative: the window is widened by a pixel and by a bound of the roundings of u - radius, of the
-// membership test's x - u and of this sum, and everything is clamped in f64 before the conversion (u can be +-1e300, an
-// infinity or a NaN).  A NaN bound selects every cell; the exact membership test decides.
-__device__ __forceinline__ bool guided_span(double u, double radius, int extent, int shift, int* lo, int* hi)
-{
-    const double m = 1.0 + (fabs(u) + radius) * 0x1p-50;
-    const double a = (u - radius) - m, b = (u + radius) + m, last = (double)(extent - 1);
-    if(a > last || b < 0.0)
-        return false;
-    *lo = (a > 0.0 ? (int)a : 0) >> shift;        // 0 < a <= last
-    *hi = (b < last ? (int)b : extent - 1) >> shift; // 0 <= b < last
-    return true;
-}
-
+// (the device side — projection, binning, window walk — is guided_walk.hpp)
 void launch_guided_bin(const GuidedArgs& a, int rows, hipStream_t s);
 void launch_match_guided(const GuidedArgs& a, int rows, hipStream_t s);
 // acceptance d0 <= max_distance && (no second candidate || d0 < thr[d1]) + ordered compaction; RatioArgs' from counts are not read

@@ -9,19 +9,18 @@
 // ORB-SLAM's SearchAndFuse; this is an extension, not a restatement.
 //
 //   k_fuse_ids       both entries' landmark ids into one id table each (lm_table.hpp)
-//   k_fuse_project   one thread per landmark of either entry: eligibility (its id is absent from the other entry's table)
-//                    and the f64 projection.  A keep landmark leaves (u, v) and a flag; a drop landmark leaves the f32
-//                    "keypoint" ((float)u, (float)v), or NaNs when it is ineligible or behind the camera, so that
-//                    k_guided_bin (k_match_guided.hip, unchanged) bins exactly the drop landmarks that may be candidates
-//   k_fuse_search    k_match_guided's walk, eight lanes per keep landmark, with the 3-D gate in front of the knn-2 and the
-//                    acceptance test at the end: per keep landmark the accepted key d0 << 16 | drop position, or none
-//   k_fuse_resolve   one workgroup: atomicMin of d0 << 16 | keep position per claimed drop position, then the ordered
-//                    compaction (ballot + scan) of the keep landmarks that hold their claim
+//   k_fuse_project   one thread per landmark of either entry: fuse_project (fuse.hpp), so that k_guided_bin
+//                    (k_match_guided.hip) bins exactly the drop landmarks that may be candidates
+//   k_fuse_search    eight lanes per keep landmark: fuse_search_one (fuse.hpp), per keep landmark the accepted key
+//                    d0 << 16 | drop position, or none
+//   k_fuse_resolve   one workgroup: atomicMin of d0 << 16 | keep position per claimed drop position, then fuse_emit
+//                    (fuse.hpp) of the keep landmarks that hold their claim
 //
 // Every result is a function of the keys alone (distance, position), never of the order in which the binning scatter or
 // the atomics ran.  All projection arithmetic is f64, every operation rounded on its own (-ffp-contract=off).
-#include "lm_table.hpp"
-#include "reloc.hpp"
+//
+// The host side that k_fuse_multi.hip shares (fuse.hpp) is defined here as well.
+#include "fuse.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,46 +31,15 @@
 namespace mslam
 {
 
-struct FuseHead // the mapped result block's first 16 bytes
+struct FuseArgs : FuseCore
 {
-    int32_t n_pairs, pad[3];
-};
-
-// the pair list, on the device (what the replacement reads) and in the mapped result block (what the host reads)
-struct FusePairs
-{
-    int32_t *keep_pos, *drop_pos, *dist;
-    int64_t *keep_lid, *drop_lid;
-};
-
-struct FuseArgs
-{
-    const uint8_t* desc; // the store
-    const double* world;
-    const int64_t* lid;
-    const int32_t* n;
-    int K, keep_slot, drop_slot, nk_cap, nd_cap; // n*_cap: what the host knows the entries' counts not to exceed
-    LmTable tab_keep, tab_drop;
-    double R[9], t[3], fx, fy, cx, cy, radius, gate2, ratio;
-    int max_distance, width, height;
-    GuidedGrid grid;
-    float* drop_xy;   // [nd][2]
-    double* keep_uv;  // [nk][2]
-    uint8_t* keep_ok; // [nk] eligible and in front of the camera
-    const int32_t* cell_off;
-    const float4* list;
-    const uint8_t* list_desc;
-    uint32_t* acc;  // [nk] the accepted key, or ~0u
-    uint32_t* best; // [nd] cleared to ~0u
-    FusePairs dev, host;
-    double* pair_world; // [P][3] the keep landmark's world point
-    int32_t* n_pairs;   // device
-    FuseHead* head;     // mapped
+    int drop_slot, nd_cap; // nd_cap: what the host knows the drop entry's count not to exceed
+    double R[9], t[3];
 };
 
 __device__ __forceinline__ int fuse_count(const FuseArgs& a, int side) // side 0 = keep, 1 = drop
 {
-    return min(max(a.n[side ? a.drop_slot : a.keep_slot], 0), side ? a.nd_cap : a.nk_cap);
+    return side ? min(max(a.n[a.drop_slot], 0), a.nd_cap) : fuse_keep_count(a);
 }
 
 // grid (blocks, 2)
@@ -88,27 +56,8 @@ __global__ __launch_bounds__(256) void k_fuse_ids(FuseArgs a)
 __global__ __launch_bounds__(256) void k_fuse_project(FuseArgs a)
 {
     const int side = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if(i >= fuse_count(a, side))
-        return;
-    const size_t at = (size_t)(side ? a.drop_slot : a.keep_slot) * a.K + i;
-    const bool eligible = lm_find(side ? a.tab_keep : a.tab_drop, (unsigned long long)a.lid[at]) < 0;
-    const double X = a.world[at * 3], Y = a.world[at * 3 + 1], Z = a.world[at * 3 + 2];
-    const double c0 = ((a.R[0] * X + a.R[1] * Y) + a.R[2] * Z) + a.t[0];
-    const double c1 = ((a.R[3] * X + a.R[4] * Y) + a.R[5] * Z) + a.t[1];
-    const double c2 = ((a.R[6] * X + a.R[7] * Y) + a.R[8] * Z) + a.t[2];
-    const double u = (c0 / c2) * a.fx + a.cx, v = (c1 / c2) * a.fy + a.cy;
-    const bool ok = eligible && c2 > 0.0;
-    if(side)
-    {
-        const float nan = __int_as_float(0x7fc00000);
-        a.drop_xy[2 * (size_t)i] = ok ? (float)u : nan; // (the in-frame test is k_guided_bin's)
-        a.drop_xy[2 * (size_t)i + 1] = ok ? (float)v : nan;
-    }
-    else
-    {
-        a.keep_uv[2 * (size_t)i] = u, a.keep_uv[2 * (size_t)i + 1] = v;
-        a.keep_ok[i] = ok ? 1 : 0;
-    }
+    if(i < fuse_count(a, side))
+        fuse_project(a, a.R, a.t, side, side ? a.drop_slot : a.keep_slot, i, (size_t)i);
 }
 
 // 64 or 256 threads: 8 or 32 keep landmarks per workgroup
@@ -116,161 +65,47 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs a)
 {
     const int g = threadIdx.x & 7;
     const int j = blockIdx.x * (blockDim.x >> 3) + (threadIdx.x >> 3);
-    const bool live = j < fuse_count(a, 0); // (the eight lanes of a landmark agree)
-    uint32_t k0 = ~0u, k1 = ~0u;
-    if(live && a.keep_ok[j])
-    {
-        const double u = a.keep_uv[2 * (size_t)j], v = a.keep_uv[2 * (size_t)j + 1];
-        int cx0, cx1, cy0, cy1;
-        if(guided_span(u, a.radius, a.width, a.grid.shift, &cx0, &cx1) && guided_span(v, a.radius, a.height, a.grid.shift, &cy0, &cy1))
-        {
-            const size_t at = (size_t)a.keep_slot * a.K + j;
-            const uint4* q = reinterpret_cast<const uint4*>(a.desc + at * 32);
-            const uint4 qa = q[0], qb = q[1];
-            const double X = a.world[at * 3], Y = a.world[at * 3 + 1], Z = a.world[at * 3 + 2];
-            const double* dw = a.world + (size_t)a.drop_slot * a.K * 3;
-            const uint4* list_desc = reinterpret_cast<const uint4*>(a.list_desc);
-            int b = a.cell_off[cy0 * a.grid.nx + cx0], e = a.cell_off[cy0 * a.grid.nx + cx1 + 1];
-            for(int cy = cy0; cy <= cy1; ++cy)
-            {
-                int nb = 0, ne = 0;
-                if(cy < cy1)
-                    nb = a.cell_off[(cy + 1) * a.grid.nx + cx0], ne = a.cell_off[(cy + 1) * a.grid.nx + cx1 + 1];
-                for(int p = b + g; p < e; p += 8)
-                {
-                    const float4 pt = a.list[p];
-                    if(fabs((double)pt.x - u) <= a.radius && fabs((double)pt.y - v) <= a.radius)
-                    {
-                        const size_t i = (size_t)__float_as_int(pt.z); // a drop position: < the drop entry's count
-                        const double dx = dw[i * 3] - X, dy = dw[i * 3 + 1] - Y, dz = dw[i * 3 + 2] - Z;
-                        if(((dx * dx + dy * dy) + dz * dz) <= a.gate2) // (a NaN fails)
-                        {
-                            const uint4 da = list_desc[2 * (size_t)p], db = list_desc[2 * (size_t)p + 1];
-                            const uint32_t dist = (uint32_t)(((__popc(da.x ^ qa.x) + __popc(da.y ^ qa.y)) + (__popc(da.z ^ qa.z) + __popc(da.w ^ qa.w))) +
-                                                             ((__popc(db.x ^ qb.x) + __popc(db.y ^ qb.y)) + (__popc(db.z ^ qb.z) + __popc(db.w ^ qb.w))));
-                            const uint32_t key = (dist << 16) | (uint32_t)i; // position <= 65534
-                            k1 = min(k1, max(k0, key));
-                            k0 = min(k0, key);
-                        }
-                    }
-                }
-                b = nb, e = ne;
-            }
-        }
-    }
-    // the eight lanes' (k0 <= k1) pairs: keys are distinct (one per drop landmark) apart from the absent key
-    for(int o = 1; o < 8; o <<= 1)
-    {
-        const uint32_t o0 = __shfl_xor(k0, o), o1 = __shfl_xor(k1, o);
-        k1 = min(max(k0, o0), min(k1, o1));
-        k0 = min(k0, o0);
-    }
+    const bool live = j < fuse_keep_count(a); // (the eight lanes of a landmark agree)
+    const uint32_t key = fuse_search_one(a, live, j, (size_t)j, a.drop_slot, a.cell_off, a.list, a.list_desc, g);
     if(live && g == 0)
-    {
-        const int d0 = (int)(k0 >> 16), d1 = (int)(k1 >> 16);
-        const bool ok = k0 != ~0u && d0 <= a.max_distance && (k1 == ~0u || (double)d0 < a.ratio * (double)d1);
-        a.acc[j] = ok ? k0 : ~0u;
-    }
+        a.acc[j] = key;
 }
-
-constexpr int kResolveThreads = 1024;
 
 // one workgroup.  The claims go through atomicMin and are read back through it as well (an atomic that changes nothing),
 // so the second phase sees what the first one left whatever the caches hold.
-__global__ __launch_bounds__(kResolveThreads) void k_fuse_resolve(FuseArgs a)
+__global__ __launch_bounds__(kFuseEmitThreads) void k_fuse_resolve(FuseArgs a)
 {
-    __shared__ uint32_t wcnt[kResolveThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nk = fuse_count(a, 0);
-    for(int j = tid; j < nk; j += kResolveThreads)
+    __shared__ uint32_t wcnt[kFuseEmitThreads / 64];
+    const int nk = fuse_keep_count(a);
+    for(int j = threadIdx.x; j < nk; j += kFuseEmitThreads)
     {
         const uint32_t k = a.acc[j];
         if(k != ~0u)
             atomicMin(&a.best[k & 0xFFFFu], (k & 0xFFFF0000u) | (uint32_t)j);
     }
     __syncthreads();
-    uint32_t base = 0;
-    for(int j0 = 0; j0 < nk; j0 += kResolveThreads)
+    // one pair per drop position and per keep position: fewer than min(nk, nd) + 1 rows
+    const uint32_t n = fuse_emit(a, nk, 0, a.drop_slot, 0, wcnt, [&a](int j) {
+        const uint32_t k = a.acc[j];
+        return (k != ~0u && atomicMin(&a.best[k & 0xFFFFu], ~0u) == ((k & 0xFFFF0000u) | (uint32_t)j)) ? k : ~0u;
+    });
+    if(threadIdx.x == 0)
     {
-        const int j = j0 + tid;
-        uint32_t k = ~0u;
-        bool win = false;
-        if(j < nk)
-        {
-            k = a.acc[j];
-            win = k != ~0u && atomicMin(&a.best[k & 0xFFFFu], ~0u) == ((k & 0xFFFF0000u) | (uint32_t)j);
-        }
-        const unsigned long long bal = __ballot(win);
-        if(lane == 0)
-            wcnt[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t pre = 0, tot = 0;
-        for(int w = 0; w < kResolveThreads / 64; ++w)
-        {
-            if(w < wave)
-                pre += wcnt[w];
-            tot += wcnt[w];
-        }
-        if(win)
-        {
-            // one pair per drop position and per keep position: fewer than min(nk, nd) + 1 rows
-            const size_t p = base + pre + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            const int i = (int)(k & 0xFFFFu), d = (int)(k >> 16);
-            const size_t ka = (size_t)a.keep_slot * a.K + j, da = (size_t)a.drop_slot * a.K + i;
-            const int64_t kl = a.lid[ka], dl = a.lid[da];
-            a.dev.keep_pos[p] = a.host.keep_pos[p] = j;
-            a.dev.drop_pos[p] = a.host.drop_pos[p] = i;
-            a.dev.dist[p] = a.host.dist[p] = d;
-            a.dev.keep_lid[p] = a.host.keep_lid[p] = kl;
-            a.dev.drop_lid[p] = a.host.drop_lid[p] = dl;
-            a.pair_world[p * 3] = a.world[ka * 3], a.pair_world[p * 3 + 1] = a.world[ka * 3 + 1], a.pair_world[p * 3 + 2] = a.world[ka * 3 + 2];
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if(tid == 0)
-    {
-        *a.n_pairs = (int32_t)base;
-        a.head->n_pairs = (int32_t)base;
+        *a.n_pairs = (int32_t)n;
+        a.head->n_pairs = (int32_t)n;
     }
 }
 
-} // namespace mslam
+// ---- the host side both fusion files share (fuse.hpp) ------------------------------------------------------------------
 
-using namespace mslam;
-
-namespace
-{
-struct SearchParams
-{
-    int keep_id, drop_id;
-    const double *R, *t;
-    double fx, fy, cx, cy;
-    int width, height;
-    double radius;
-    int max_distance;
-    double ratio, max_world_distance;
-};
-
-// what one search leaves behind for the caller
-struct SearchPlan
-{
-    FuseArgs a{};
-    int P = 0;                       // rows of the pair arrays: min of the two entries' upper bounds
-    LmTable tab_rep{};               // the replacement table inside d_lm_table (kf_fuse)
-    bool empty = false;              // an entry holds nothing: no launch, no pairs
-};
-
-int search_check(mslam_hip_ctx* c, const std::string& me, const SearchParams& p, int* keep_slot, int* drop_slot)
+int fuse_check(mslam_hip_ctx* c, const std::string& me, const FuseParams& p, const int32_t* drop_ids, int n_drop, int* keep_slot,
+               std::vector<int>* drop_slots)
 {
     RelocState* r = c->reloc;
-    if(!p.R || !p.t)
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
-    if(p.keep_id == p.drop_id)
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": keep_id and drop_id name one entry");
     int rc = store_slot(c, me, "id", p.keep_id, keep_slot);
-    if(!rc)
-        rc = store_slot(c, me, "id", p.drop_id, drop_slot);
+    drop_slots->assign((size_t)n_drop, -1);
+    for(int m = 0; !rc && m < n_drop; ++m)
+        rc = store_slot(c, me, "id", drop_ids[m], &(*drop_slots)[(size_t)m]);
     if(rc)
         return rc;
     if(!(p.radius > 0.0))
@@ -283,78 +118,180 @@ int search_check(mslam_hip_ctx* c, const std::string& me, const SearchParams& p,
         return fail(c, MSLAM_HIP_E_INVALID, me + ": fx or fy is zero or NaN");
     if(!(p.max_world_distance > 0.0))
         return fail(c, MSLAM_HIP_E_INVALID, me + ": max_world_distance is not a positive number");
-    if(r->n_upper[(size_t)*keep_slot] > 65535 || r->n_upper[(size_t)*drop_slot] > 65535)
+    bool large = r->n_upper[(size_t)*keep_slot] > 65535;
+    for(const int s : *drop_slots)
+        large = large || r->n_upper[(size_t)s] > 65535;
+    if(large)
         return fail(c, MSLAM_HIP_E_INVALID, me + ": entries of more than 65535 landmarks are not supported");
     return MSLAM_HIP_OK;
 }
 
-// scratch and launches of one search on c->stream.  up: the bytes of the caller's own upload (the search uploads
-// nothing); with_rep: room for kf_fuse's replacement table.  The mapped result block is
-// [FuseHead | keep_pos P | drop_pos P | dist P | keep_lid P | drop_lid P].
-int search_enqueue(mslam_hip_ctx* c, const SearchParams& p, int keep_slot, int drop_slot, size_t up, bool with_rep, SearchPlan* plan)
+int fuse_setup(mslam_hip_ctx* c, const FuseParams& p, int keep_slot, const std::vector<int>& drop_slots, bool with_target, size_t up,
+               size_t extra_arena, bool with_rep, FuseCore* core, FusePlan* plan)
 {
     RelocState* r = c->reloc;
-    const int nk = r->n_upper[(size_t)keep_slot], nd = r->n_upper[(size_t)drop_slot];
-    plan->P = std::min(nk, nd);
+    const int nk = r->n_upper[(size_t)keep_slot];
+    size_t ND = 0;
+    for(const int s : drop_slots)
+        ND += (size_t)r->n_upper[(size_t)s];
+    plan->P = (int)std::min((size_t)nk, ND);
     plan->empty = plan->P == 0;
     if(plan->empty)
         return MSLAM_HIP_OK;
-    const size_t K = (size_t)c->p.max_keypoints, P = (size_t)plan->P;
-    const size_t bk = lm_bucket_count((size_t)nk), bd = lm_bucket_count((size_t)nd), bp = with_rep ? lm_bucket_count(P) : 0;
-    // one block, one clear: [keep table | drop table | replacement table | best nd x u32]
-    const size_t o_best = (bk + bd + bp) * sizeof(LmBucket), tab_bytes = o_best + (size_t)nd * 4;
-    // the arena
-    size_t o = 0;
-    auto carve = [&o](size_t bytes) {
-        const size_t at = o;
-        o += al256(bytes);
+    const size_t K = (size_t)c->p.max_keypoints, P = (size_t)plan->P, M = drop_slots.size(), rows = M * (size_t)nk;
+    const size_t bk = lm_bucket_count((size_t)nk), bd = lm_bucket_count(ND), bp = with_rep ? lm_bucket_count(P) : 0;
+    const size_t o_best = (bk + bd + bp) * sizeof(LmBucket);
+    plan->tab_bytes = o_best + ND * 4;
+    // the arena and the mapped result block
+    const auto carve = [](size_t* o, size_t bytes) {
+        const size_t at = *o;
+        *o += al256(bytes);
         return at;
     };
-    const size_t a_xy = carve((size_t)nd * 8), a_uv = carve((size_t)nk * 16), a_ok = carve((size_t)nk), a_off = carve((size_t)(kGuidedMaxCells + 1) * 4);
-    const size_t a_list = carve((size_t)nd * 16), a_ldesc = carve((size_t)nd * 32), a_acc = carve((size_t)nk * 4);
-    const size_t a_kpos = carve(P * 4), a_dpos = carve(P * 4), a_dist = carve(P * 4), a_klid = carve(P * 8), a_dlid = carve(P * 8);
-    const size_t a_world = carve(P * 24), a_n = carve(4);
-    const size_t h_kpos = al256(sizeof(FuseHead)), h_dpos = h_kpos + al256(P * 4), h_dist = h_dpos + al256(P * 4);
-    const size_t h_klid = h_dist + al256(P * 4), h_dlid = h_klid + al256(P * 8), h_bytes = h_dlid + al256(P * 8);
-    int rc = reloc_scratch(c, up, o, h_bytes);
+    struct PairsAt
+    {
+        size_t target, keep_pos, drop_pos, dist, keep_lid, drop_lid;
+    };
+    const auto carve_pairs = [&](size_t* o) {
+        PairsAt at{};
+        if(with_target)
+            at.target = carve(o, P * 4);
+        at.keep_pos = carve(o, P * 4), at.drop_pos = carve(o, P * 4), at.dist = carve(o, P * 4);
+        at.keep_lid = carve(o, P * 8), at.drop_lid = carve(o, P * 8);
+        return at;
+    };
+    const auto pairs = [&](uint8_t* base, const PairsAt& at) {
+        return FusePairs{with_target ? reinterpret_cast<int32_t*>(base + at.target) : nullptr,
+                         reinterpret_cast<int32_t*>(base + at.keep_pos),
+                         reinterpret_cast<int32_t*>(base + at.drop_pos),
+                         reinterpret_cast<int32_t*>(base + at.dist),
+                         reinterpret_cast<int64_t*>(base + at.keep_lid),
+                         reinterpret_cast<int64_t*>(base + at.drop_lid)};
+    };
+    size_t o = 0, h = al256(sizeof(FuseHead));
+    const size_t a_xy = carve(&o, ND * 8), a_uv = carve(&o, rows * 16), a_ok = carve(&o, rows), a_off = carve(&o, M * (kGuidedMaxCells + 1) * 4);
+    const size_t a_list = carve(&o, ND * 16), a_ldesc = carve(&o, ND * 32), a_acc = carve(&o, rows * 4);
+    const PairsAt a_pairs = carve_pairs(&o), h_pairs = carve_pairs(&h);
+    const size_t a_world = carve(&o, P * 24), a_n = carve(&o, 4);
+    plan->extra_at = carve(&o, extra_arena);
+    int rc = reloc_scratch(c, up, o, h);
     if(rc)
         return rc;
-    FuseArgs& a = plan->a;
-    a.tab_keep = lm_table_grow(c, (size_t)nk, tab_bytes);
+    FuseCore& a = *core;
+    a.tab_keep = lm_table_grow(c, (size_t)nk, plan->tab_bytes);
     if(!a.tab_keep.b)
         return MSLAM_HIP_E_RUNTIME;
-    a.tab_drop = lm_table_grow(c, (size_t)nd, tab_bytes, bk * sizeof(LmBucket)); // (the block has its size: no growth, no failure)
+    a.tab_drop = lm_table_grow(c, ND, plan->tab_bytes, bk * sizeof(LmBucket)); // (the block has its size: no growth, no failure)
     if(with_rep)
-        plan->tab_rep = lm_table_grow(c, P, tab_bytes, (bk + bd) * sizeof(LmBucket));
+        plan->tab_rep = lm_table_grow(c, P, plan->tab_bytes, (bk + bd) * sizeof(LmBucket));
     uint8_t *A = r->d_arena, *T = r->d_lm_table, *H = r->h_res.dev();
     a.desc = r->d_desc, a.world = r->d_world, a.lid = r->d_lid, a.n = r->d_n;
-    a.K = (int)K, a.keep_slot = keep_slot, a.drop_slot = drop_slot, a.nk_cap = nk, a.nd_cap = nd;
-    std::memcpy(a.R, p.R, sizeof(a.R));
-    std::memcpy(a.t, p.t, sizeof(a.t));
+    a.K = (int)K, a.keep_slot = keep_slot, a.nk_cap = nk;
     a.fx = p.fx, a.fy = p.fy, a.cx = p.cx, a.cy = p.cy, a.radius = p.radius, a.ratio = p.ratio;
     a.gate2 = p.max_world_distance * p.max_world_distance;
     a.max_distance = p.max_distance, a.width = p.width, a.height = p.height, a.grid = guided_grid(p.width, p.height);
     a.drop_xy = reinterpret_cast<float*>(A + a_xy), a.keep_uv = reinterpret_cast<double*>(A + a_uv), a.keep_ok = A + a_ok;
-    a.cell_off = reinterpret_cast<const int32_t*>(A + a_off), a.list = reinterpret_cast<const float4*>(A + a_list), a.list_desc = A + a_ldesc;
+    a.cell_off = reinterpret_cast<int32_t*>(A + a_off), a.list = reinterpret_cast<float4*>(A + a_list), a.list_desc = A + a_ldesc;
     a.acc = reinterpret_cast<uint32_t*>(A + a_acc), a.best = reinterpret_cast<uint32_t*>(T + o_best);
-    a.dev = FusePairs{reinterpret_cast<int32_t*>(A + a_kpos), reinterpret_cast<int32_t*>(A + a_dpos), reinterpret_cast<int32_t*>(A + a_dist),
-                      reinterpret_cast<int64_t*>(A + a_klid), reinterpret_cast<int64_t*>(A + a_dlid)};
-    a.host = FusePairs{reinterpret_cast<int32_t*>(H + h_kpos), reinterpret_cast<int32_t*>(H + h_dpos), reinterpret_cast<int32_t*>(H + h_dist),
-                       reinterpret_cast<int64_t*>(H + h_klid), reinterpret_cast<int64_t*>(H + h_dlid)};
+    a.dev = pairs(A, a_pairs), a.host = pairs(H, h_pairs);
     a.pair_world = reinterpret_cast<double*>(A + a_world), a.n_pairs = reinterpret_cast<int32_t*>(A + a_n);
     a.head = reinterpret_cast<FuseHead*>(H);
-    reinterpret_cast<FuseHead*>(r->h_res.get())->n_pairs = -1; // (overwritten by k_fuse_resolve; checked after the synchronisation)
+    reinterpret_cast<FuseHead*>(r->h_res.get())->n_pairs = -1; // (overwritten by the last kernel; checked after the synchronisation)
+    return MSLAM_HIP_OK;
+}
+
+int fuse_rewrite_upload(const RelocState* r, std::vector<int32_t>* slots)
+{
+    const int n_max = live_slots(r, slots);
+    slots->push_back(0);
+    return n_max;
+}
+
+int fuse_rewrite(mslam_hip_ctx* c, const FuseCore& a, const FusePlan& plan, uint8_t* d, int n_slots, int n_max, int capacity,
+                 const char* stage_table, const char* stage_write, int* n_rewritten)
+{
+    const ReplaceList l{a.dev.drop_lid, a.dev.keep_lid, a.pair_world, a.n_pairs, plan.P, std::min(capacity, plan.P)};
+    uint32_t* count = reinterpret_cast<uint32_t*>(d) + n_slots;
+    const int rc = rewrite_enqueue(c, l, plan.tab_rep, reinterpret_cast<const int32_t*>(d), n_slots, n_max, count, stage_table, stage_write);
+    return rc ? rc : rewrite_count(c, count, n_rewritten);
+}
+
+int fuse_collect(mslam_hip_ctx* c, const std::string& me, const FuseCore& a, const FusePlan& plan, const FusePairs& out, int capacity,
+                 int* n_pairs)
+{
+    RelocState* r = c->reloc;
+    const int32_t n = reinterpret_cast<const FuseHead*>(r->h_res.get())->n_pairs;
+    if(n < 0 || n > plan.P)
+        return fail(c, MSLAM_HIP_E_RUNTIME, me + ": the kernels left no result");
+    *n_pairs = n;
+    if(n > capacity)
+        return fail(c, MSLAM_HIP_E_CAPACITY, me + ": " + std::to_string(n) + " pairs, more than `capacity`");
+    const uint8_t* H = r->h_res.get();
+    const size_t dev = reinterpret_cast<size_t>(r->h_res.dev());
+    auto copy = [&](void* dst, const void* dev_ptr, size_t each) {
+        if(dst)
+            std::memcpy(dst, H + (reinterpret_cast<size_t>(dev_ptr) - dev), (size_t)n * each);
+    };
+    copy(out.target, a.host.target, 4), copy(out.keep_pos, a.host.keep_pos, 4), copy(out.drop_pos, a.host.drop_pos, 4);
+    copy(out.dist, a.host.dist, 4), copy(out.keep_lid, a.host.keep_lid, 8), copy(out.drop_lid, a.host.drop_lid, 8);
+    return MSLAM_HIP_OK;
+}
+
+} // namespace mslam
+
+using namespace mslam;
+
+namespace
+{
+// mslam_hip_kf_fuse_search (rewrite == false: the caller's arrays are required, the call ends in its own synchronisation)
+// and mslam_hip_kf_fuse (the rewrite's upload and launches follow the search's, and its count is the synchronisation)
+int fuse_call(mslam_hip_ctx* c, const std::string& me, bool rewrite, int drop_id, const FuseParams& p, const FusePairs& out, int capacity,
+              int* n_pairs, int* n_rewritten)
+{
+    if(n_pairs)
+        *n_pairs = 0;
+    if(n_rewritten)
+        *n_rewritten = 0;
+    int rc = reloc_enter(c);
+    if(rc)
+        return rc;
+    if(!n_pairs || capacity < 0 ||
+       (!rewrite && capacity > 0 && (!out.keep_pos || !out.drop_pos || !out.keep_lid || !out.drop_lid || !out.dist)))
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
+    if(!p.R || !p.t)
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
+    if(p.keep_id == drop_id)
+        return fail(c, MSLAM_HIP_E_INVALID, me + ": keep_id and drop_id name one entry");
+    int ks = -1;
+    std::vector<int> ds;
+    rc = fuse_check(c, me, p, &drop_id, 1, &ks, &ds);
+    if(rc)
+        return rc;
+    RelocState* r = c->reloc;
+    // kf_fuse's one upload: [live slots | the count, zero]
+    std::vector<int32_t> slots;
+    const int n_max = rewrite ? fuse_rewrite_upload(r, &slots) : 0;
+    const size_t up = slots.size() * 4;
+    FuseArgs a{};
+    FusePlan plan;
+    rc = fuse_setup(c, p, ks, ds, false, up, 0, rewrite, &a, &plan);
+    if(rc || plan.empty)
+        return rc;
+    const int nk = a.nk_cap, nd = r->n_upper[(size_t)ds[0]];
+    a.drop_slot = ds[0], a.nd_cap = nd;
+    std::memcpy(a.R, p.R, sizeof(a.R));
+    std::memcpy(a.t, p.t, sizeof(a.t));
     // the bin kernel's view: the drop entry's projections are the keypoints
     GuidedArgs g{};
-    g.kp_desc = r->d_desc + (size_t)drop_slot * K * 32, g.kp_xy = a.drop_xy;
-    g.kp_cnt = r->d_n + drop_slot, g.kp_cap = nd;
+    g.kp_desc = r->d_desc + (size_t)a.drop_slot * a.K * 32, g.kp_xy = a.drop_xy;
+    g.kp_cnt = r->d_n + a.drop_slot, g.kp_cap = nd;
     g.width = p.width, g.height = p.height, g.grid = a.grid;
-    g.cell_off = reinterpret_cast<int32_t*>(A + a_off), g.list = reinterpret_cast<float4*>(A + a_list), g.list_desc = A + a_ldesc;
+    g.cell_off = a.cell_off, g.list = a.list, g.list_desc = a.list_desc;
     hipStream_t s = c->stream;
     const dim3 both((unsigned)((std::max(nk, nd) + 255) / 256), 2);
     {
         StageScope ts(c, "fuse_clear");
-        MSLAM_CHK(c, hipMemsetAsync(T, 0xFF, tab_bytes, s));
+        MSLAM_CHK(c, hipMemsetAsync(r->d_lm_table, 0xFF, plan.tab_bytes, s));
     }
     {
         StageScope ts(c, "fuse_ids");
@@ -375,39 +312,20 @@ int search_enqueue(mslam_hip_ctx* c, const SearchParams& p, int keep_slot, int d
     }
     {
         StageScope ts(c, "fuse_resolve");
-        hipLaunchKernelGGL(k_fuse_resolve, dim3(1), dim3(kResolveThreads), 0, s, a);
+        hipLaunchKernelGGL(k_fuse_resolve, dim3(1), dim3(kFuseEmitThreads), 0, s, a);
     }
     MSLAM_CHK(c, hipGetLastError());
-    return MSLAM_HIP_OK;
-}
-
-// after the synchronisation: the count, and the pairs when they fit
-int search_collect(mslam_hip_ctx* c, const std::string& me, const SearchPlan& plan, int32_t* keep_pos, int32_t* drop_pos, int64_t* keep_lid,
-                   int64_t* drop_lid, int32_t* dist, int capacity, int* n_pairs)
-{
-    if(plan.empty)
-        return MSLAM_HIP_OK;
-    RelocState* r = c->reloc;
-    const int32_t n = reinterpret_cast<const FuseHead*>(r->h_res.get())->n_pairs;
-    if(n < 0 || n > plan.P)
-        return fail(c, MSLAM_HIP_E_RUNTIME, me + ": the kernels left no result");
-    *n_pairs = n;
-    if(n > capacity)
-        return fail(c, MSLAM_HIP_E_CAPACITY, me + ": " + std::to_string(n) + " pairs, more than `capacity`");
-    const uint8_t* H = r->h_res.get();
-    const size_t dev = reinterpret_cast<size_t>(r->h_res.dev());
-    auto at = [&](const void* dev_ptr) { return H + (reinterpret_cast<size_t>(dev_ptr) - dev); };
-    if(keep_pos)
-        std::memcpy(keep_pos, at(plan.a.host.keep_pos), (size_t)n * 4);
-    if(drop_pos)
-        std::memcpy(drop_pos, at(plan.a.host.drop_pos), (size_t)n * 4);
-    if(dist)
-        std::memcpy(dist, at(plan.a.host.dist), (size_t)n * 4);
-    if(keep_lid)
-        std::memcpy(keep_lid, at(plan.a.host.keep_lid), (size_t)n * 8);
-    if(drop_lid)
-        std::memcpy(drop_lid, at(plan.a.host.drop_lid), (size_t)n * 8);
-    return MSLAM_HIP_OK;
+    if(rewrite)
+    {
+        std::memcpy(r->h_up, slots.data(), up);
+        MSLAM_CHK(c, hipMemcpyAsync(r->d_up, r->h_up, up, hipMemcpyHostToDevice, s));
+        rc = fuse_rewrite(c, a, plan, r->d_up, (int)slots.size() - 1, n_max, capacity, "fuse_table", "fuse_replace", n_rewritten);
+        if(rc)
+            return rc;
+    }
+    else
+        MSLAM_CHK(c, hipStreamSynchronize(s));
+    return fuse_collect(c, me, a, plan, out, capacity, n_pairs);
 }
 } // namespace
 
@@ -418,26 +336,9 @@ int mslam_hip_kf_fuse_search(mslam_hip_ctx* c, int keep_id, int drop_id, const d
                              int32_t* keep_pos, int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid, int32_t* dist, int capacity,
                              int* n_pairs)
 {
-    if(n_pairs)
-        *n_pairs = 0;
-    int rc = reloc_enter(c);
-    if(rc)
-        return rc;
-    const std::string me = "kf_fuse_search";
-    if(!n_pairs || capacity < 0 || (capacity > 0 && (!keep_pos || !drop_pos || !keep_lid || !drop_lid || !dist)))
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
-    const SearchParams p{keep_id, drop_id, R, t, fx, fy, cx, cy, width, height, radius, max_distance, ratio, max_world_distance};
-    int ks = -1, ds = -1;
-    rc = search_check(c, me, p, &ks, &ds);
-    if(rc)
-        return rc;
-    SearchPlan plan;
-    rc = search_enqueue(c, p, ks, ds, 0, false, &plan);
-    if(rc)
-        return rc;
-    if(!plan.empty)
-        MSLAM_CHK(c, hipStreamSynchronize(c->stream));
-    return search_collect(c, me, plan, keep_pos, drop_pos, keep_lid, drop_lid, dist, capacity, n_pairs);
+    const FuseParams p{keep_id, R, t, fx, fy, cx, cy, width, height, radius, max_distance, ratio, max_world_distance};
+    return fuse_call(c, "kf_fuse_search", false, drop_id, p, FusePairs{nullptr, keep_pos, drop_pos, dist, keep_lid, drop_lid}, capacity, n_pairs,
+                     nullptr);
 }
 
 int mslam_hip_kf_replace_ids(mslam_hip_ctx* c, const int64_t* from_ids, const int64_t* to_ids, const double* world_xyz, int n,
@@ -458,42 +359,9 @@ int mslam_hip_kf_fuse(mslam_hip_ctx* c, int keep_id, int drop_id, const double* 
                       int width, int height, double radius, int max_distance, double ratio, double max_world_distance, int32_t* keep_pos,
                       int32_t* drop_pos, int64_t* keep_lid, int64_t* drop_lid, int32_t* dist, int capacity, int* n_pairs, int* n_rewritten)
 {
-    if(n_pairs)
-        *n_pairs = 0;
-    if(n_rewritten)
-        *n_rewritten = 0;
-    int rc = reloc_enter(c);
-    if(rc)
-        return rc;
-    const std::string me = "kf_fuse";
-    if(!n_pairs || capacity < 0)
-        return fail(c, MSLAM_HIP_E_INVALID, me + ": bad argument");
-    const SearchParams p{keep_id, drop_id, R, t, fx, fy, cx, cy, width, height, radius, max_distance, ratio, max_world_distance};
-    int ks = -1, ds = -1;
-    rc = search_check(c, me, p, &ks, &ds);
-    if(rc)
-        return rc;
-    RelocState* r = c->reloc;
-    std::vector<int32_t> slots;
-    const int n_max = live_slots(r, &slots);
-    // one upload: [live slots | the count, zero]
-    const size_t o_cnt = slots.size() * 4, up = o_cnt + 4;
-    SearchPlan plan;
-    rc = search_enqueue(c, p, ks, ds, up, true, &plan);
-    if(rc || plan.empty)
-        return rc;
-    uint8_t *h = r->h_up, *d = r->d_up;
-    std::memcpy(h, slots.data(), slots.size() * 4);
-    std::memset(h + o_cnt, 0, 4);
-    MSLAM_CHK(c, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c->stream));
-    // drop_lid -> keep_lid with the keep landmark's world point, straight from the device list (at most P places); nothing
-    // when the pairs exceed `capacity`
-    const ReplaceList l{plan.a.dev.drop_lid, plan.a.dev.keep_lid, plan.a.pair_world, plan.a.n_pairs, plan.P, std::min(capacity, plan.P)};
-    rc = rewrite_enqueue(c, l, plan.tab_rep, reinterpret_cast<const int32_t*>(d), (int)slots.size(), n_max,
-                         reinterpret_cast<uint32_t*>(d + o_cnt), "fuse_table", "fuse_replace");
-    if(!rc)
-        rc = rewrite_count(c, reinterpret_cast<const uint32_t*>(d + o_cnt), n_rewritten);
-    return rc ? rc : search_collect(c, me, plan, keep_pos, drop_pos, keep_lid, drop_lid, dist, capacity, n_pairs);
+    const FuseParams p{keep_id, R, t, fx, fy, cx, cy, width, height, radius, max_distance, ratio, max_world_distance};
+    return fuse_call(c, "kf_fuse", true, drop_id, p, FusePairs{nullptr, keep_pos, drop_pos, dist, keep_lid, drop_lid}, capacity, n_pairs,
+                     n_rewritten);
 }
 
 } // extern "C"

@@ -18,8 +18,9 @@
 //   k_ratio_guided   the acceptance test and the ordered compaction (k_ratio_compact's, with the distance gate, a lone
 //                    candidate accepted, and no "fewer than two train rows" rule)
 //
-// All projection arithmetic is f64, every operation rounded on its own (-ffp-contract=off), in the order written.
-#include "reloc.hpp"
+// The projection, the binning body and the walk are guided_walk.hpp's, which landmark fusion (k_fuse.hip, k_fuse_multi.hip)
+// uses as well.  All projection arithmetic is f64, every operation rounded on its own (-ffp-contract=off), in the order written.
+#include "guided_walk.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -36,80 +37,15 @@ __device__ __forceinline__ int guided_row_kp(const GuidedArgs& a, int row)
 {
     return min(max(a.kp_cnt ? a.kp_cnt[row] : a.n_kp_fixed, 0), a.kp_cap);
 }
-
-// the cell of a keypoint, or -1 when it is not in the frame (NaN and infinities fail the comparisons)
-__device__ __forceinline__ int guided_cell(float x, float y, int width, int height, const GuidedGrid& g)
-{
-    const double dx = (double)x, dy = (double)y;
-    if(!(dx >= 0.0 && dx < (double)width && dy >= 0.0 && dy < (double)height))
-        return -1;
-    return ((int)y >> g.shift) * g.nx + ((int)x >> g.shift); // (int) of [0, extent): 0 .. extent - 1
-}
-constexpr int kBinThreads = 1024;
 } // namespace
 
-// (1024 threads: the two walks over the row's keypoints are a chain of dependent fetches per thread; more threads, shorter chains)
-__global__ __launch_bounds__(kBinThreads) void k_guided_bin(GuidedArgs a)
+// one workgroup per row
+__global__ __launch_bounds__(kGuidedBinThreads) void k_guided_bin(GuidedArgs a)
 {
-    __shared__ uint32_t cell[kGuidedMaxCells]; // counts, then running offsets
-    __shared__ uint32_t wtot[kBinThreads / 64];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = guided_row_kp(a, row);
-    const int n_cells = a.grid.nx * a.grid.ny; // <= kGuidedMaxCells (guided_grid)
-    const float* xy = a.kp_xy + (size_t)row * a.kp_stride * 2;
-    int32_t* off = a.cell_off + (size_t)row * (kGuidedMaxCells + 1);
-    float4* list = a.list + (size_t)row * a.kp_cap;
-    uint8_t* list_desc = a.list_desc + (size_t)row * a.kp_cap * 32;
-    const uint8_t* kd = a.kp_desc + (size_t)row * a.kp_stride * 32;
-    for(int c = tid; c < n_cells; c += kBinThreads)
-        cell[c] = 0;
-    __syncthreads();
-    for(int i = tid; i < n; i += kBinThreads)
-    {
-        const int c = guided_cell(xy[2 * (size_t)i], xy[2 * (size_t)i + 1], a.width, a.height, a.grid);
-        if(c >= 0)
-            atomicAdd(&cell[c], 1u);
-    }
-    __syncthreads();
-    // exclusive scan: thread t owns the cells [t * per, t * per + per)
-    const int per = (n_cells + kBinThreads - 1) / kBinThreads, c0 = tid * per, c1 = min(c0 + per, n_cells);
-    uint32_t mine = 0;
-    for(int c = c0; c < c1; ++c)
-        mine += cell[c];
-    uint32_t incl = mine;
-    for(int o = 1; o < 64; o <<= 1)
-    {
-        const uint32_t up = __shfl_up(incl, o);
-        if(lane >= o)
-            incl += up;
-    }
-    if(lane == 63)
-        wtot[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - mine;
-    for(int w = 0; w < wave; ++w)
-        run += wtot[w];
-    for(int c = c0; c < c1; ++c)
-    {
-        const uint32_t k = cell[c];
-        cell[c] = run;
-        off[c] = (int32_t)run;
-        run += k;
-    }
-    if(tid == kBinThreads - 1)
-        off[n_cells] = (int32_t)run; // the in-frame keypoints of the row: <= n <= kp_cap
-    __syncthreads();
-    for(int i = tid; i < n; i += kBinThreads)
-    {
-        const float x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
-        const int c = guided_cell(x, y, a.width, a.height, a.grid);
-        if(c >= 0)
-        {
-            const size_t pos = atomicAdd(&cell[c], 1u); // < the row's in-frame count <= kp_cap
-            list[pos] = make_float4(x, y, __int_as_float(i), 0.f);
-            copy_desc(kd + (size_t)i * 32, list_desc + pos * 32);
-        }
-    }
+    const size_t row = blockIdx.x;
+    guided_bin_row(GuidedBinRow{a.kp_xy + row * a.kp_stride * 2, a.kp_desc + row * a.kp_stride * 32, guided_row_kp(a, (int)row),
+                                a.cell_off + row * (kGuidedMaxCells + 1), a.list + row * a.kp_cap, a.list_desc + row * a.kp_cap * 32},
+                   a.width, a.height, a.grid);
 }
 
 // 64 or 256 threads: 8 or 32 landmarks per workgroup
@@ -119,60 +55,22 @@ __global__ __launch_bounds__(256) void k_match_guided(GuidedArgs a)
     const int j = blockIdx.x * (blockDim.x >> 3) + (threadIdx.x >> 3);
     const int n_lm = min(max(a.lm_cnt ? a.lm_cnt[row] : a.n_lm_fixed, 0), a.cap);
     const bool live = j < n_lm; // (the eight lanes of a landmark agree)
-    uint32_t k0 = ~0u, k1 = ~0u, cnt = 0;
+    GuidedUV p{0.0, 0.0, 0.0};
     if(live)
-    {
-        const double* P = a.world + (a.slots ? (size_t)a.slots[(size_t)row * a.slot_stride] * a.world_slot : 0) + (size_t)j * 3;
-        const double X = P[0], Y = P[1], Z = P[2];
-        const double c0 = ((a.R[0] * X + a.R[1] * Y) + a.R[2] * Z) + a.t[0];
-        const double c1 = ((a.R[3] * X + a.R[4] * Y) + a.R[5] * Z) + a.t[1];
-        const double c2 = ((a.R[6] * X + a.R[7] * Y) + a.R[8] * Z) + a.t[2];
-        const double u = (c0 / c2) * a.fx + a.cx, v = (c1 / c2) * a.fy + a.cy;
-        int cx0, cx1, cy0, cy1;
-        if(c2 > 0.0 && guided_span(u, a.radius, a.width, a.grid.shift, &cx0, &cx1) &&
-           guided_span(v, a.radius, a.height, a.grid.shift, &cy0, &cy1))
-        {
-            const uint4* q = reinterpret_cast<const uint4*>(a.lm_desc + (size_t)row * a.lm_stride + (size_t)j * 32);
-            const uint4 qa = q[0], qb = q[1];
-            const int32_t* off = a.cell_off + (size_t)row * (kGuidedMaxCells + 1);
-            const float4* list = a.list + (size_t)row * a.kp_cap;
-            const uint4* list_desc = reinterpret_cast<const uint4*>(a.list_desc + (size_t)row * a.kp_cap * 32);
-            // cells cx0 .. cx1 of a cell row lie side by side in the list; the next cell row's span is fetched while this
-            // one is walked
-            int b = off[cy0 * a.grid.nx + cx0], e = off[cy0 * a.grid.nx + cx1 + 1];
-            for(int cy = cy0; cy <= cy1; ++cy)
-            {
-                int nb = 0, ne = 0;
-                if(cy < cy1)
-                    nb = off[(cy + 1) * a.grid.nx + cx0], ne = off[(cy + 1) * a.grid.nx + cx1 + 1];
-                for(int p = b + g; p < e; p += 8)
-                {
-                    const float4 pt = list[p];
-                    const uint4 da = list_desc[2 * (size_t)p], db = list_desc[2 * (size_t)p + 1];
-                    if(fabs((double)pt.x - u) <= a.radius && fabs((double)pt.y - v) <= a.radius)
-                    {
-                        const uint32_t dist = (uint32_t)(((__popc(da.x ^ qa.x) + __popc(da.y ^ qa.y)) + (__popc(da.z ^ qa.z) + __popc(da.w ^ qa.w))) +
-                                                         ((__popc(db.x ^ qb.x) + __popc(db.y ^ qb.y)) + (__popc(db.z ^ qb.z) + __popc(db.w ^ qb.w))));
-                        const uint32_t key = (dist << 16) | (uint32_t)__float_as_int(pt.z); // index <= 65534
-                        k1 = min(k1, max(k0, key));
-                        k0 = min(k0, key);
-                        ++cnt;
-                    }
-                }
-                b = nb, e = ne;
-            }
-        }
-    }
-    // the eight lanes' (k0 <= k1) pairs: keys are distinct (one per keypoint) apart from the absent key
+        p = guided_project(a.R, a.t, a.fx, a.fy, a.cx, a.cy,
+                           a.world + (a.slots ? (size_t)a.slots[(size_t)row * a.slot_stride] * a.world_slot : 0) + (size_t)j * 3);
+    uint32_t cnt = 0; // every keypoint inside the window is a candidate
+    const uint2 k = guided_walk<true>(live && p.c2 > 0.0, p.u, p.v, a.radius, a.width, a.height, a.grid, a.cell_off + (size_t)row * (kGuidedMaxCells + 1),
+                                a.list + (size_t)row * a.kp_cap, a.list_desc + (size_t)row * a.kp_cap * 32,
+                                a.lm_desc + (size_t)row * a.lm_stride + (size_t)j * 32, g, [&cnt](int) {
+                                    ++cnt;
+                                    return true;
+                                });
     for(int o = 1; o < 8; o <<= 1)
-    {
-        const uint32_t o0 = __shfl_xor(k0, o), o1 = __shfl_xor(k1, o);
         cnt += __shfl_xor(cnt, o);
-        k1 = min(max(k0, o0), min(k1, o1));
-        k0 = min(k0, o0);
-    }
     if(live && g == 0)
     {
+        const uint32_t k0 = k.x, k1 = k.y;
         const size_t o = (size_t)row * a.cap + j;
         a.idx0[o] = k0 == ~0u ? -1 : (int32_t)(k0 & 0xFFFFu);
         a.idx1[o] = k1 == ~0u ? -1 : (int32_t)(k1 & 0xFFFFu);
@@ -230,7 +128,7 @@ __global__ __launch_bounds__(256) void k_ratio_guided(RatioArgs a, int max_dista
 
 void launch_guided_bin(const GuidedArgs& a, int rows, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_guided_bin, dim3((unsigned)rows), dim3(kBinThreads), 0, s, a);
+    hipLaunchKernelGGL(k_guided_bin, dim3((unsigned)rows), dim3(kGuidedBinThreads), 0, s, a);
 }
 
 void launch_match_guided(const GuidedArgs& a, int rows, hipStream_t s)
